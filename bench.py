@@ -61,7 +61,13 @@ def parse():
     ap.add_argument("--sg-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--fast-bilinear", action="store_true",
                     help="fp32 interpolation instead of the Pillow-bit-exact fp64 path")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after each timed step loop, write what its last step computed (blurred and rotated frames, a "
+                         "fixed seeded sample of pixels) as DIR/<name>.npy in float32; rank 0 only")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def event_ms(fn, iters):
@@ -238,6 +244,27 @@ def cpu_baselines():
     return base, allrec
 
 
+DUMP_PIXELS = 1 << 20          # pixels sampled per dumped array: 4 arrays x 2^20 x 3 channels x 4 B = 48 MiB < 64 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(args, rank, tag, outputs):
+    """--dump-outputs: each (F, H, W, 3) uint8 output of the last timed step as DIR/<name>_<tag>.npy, float32 [n, 3]
+    rows of pixels.  Every pixel when the batch has at most DUMP_PIXELS, else the same seeded sample of pixel positions
+    (ascending) for every output of one shape, so two builds run with the same arguments compare output for output."""
+    if args.dump_outputs is None or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.reshape(-1, t.shape[-1])
+        n = flat.shape[0]
+        if n > DUMP_PIXELS:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_PIXELS, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(args.dump_outputs, f"{name}_{tag}.npy"), flat.float().cpu().numpy())
+
+
 def stats(ms):
     s = sorted(ms)
     return {"median": round(s[len(s) // 2], 4), "min": round(s[0], 4), "max": round(s[-1], 4),
@@ -288,7 +315,7 @@ def timed_step(H, W, F, args, rank, world, dist, dev, backend, precise):
         elapsed = float(t.item())
     g_ms = [e[0].elapsed_time(e[1]) for e in ev]
     r_ms = [e[1].elapsed_time(e[2]) for e in ev]
-    return elapsed, g_ms, r_ms, (frames, gaussian, rotate)
+    return elapsed, g_ms, r_ms, (frames, blurred, rotated, gaussian, rotate)
 
 
 def kernel_entry(name, bytes_per_px, px, ms, traffic):
@@ -526,6 +553,7 @@ def main():
     precise = not args.fast_bilinear
     if args.only_1080p:                                      # (tools/profile_round.sh: FETCH_SIZE / WRITE_SIZE passes at 1080p)
         el, g2, r2, keep = timed_step(HHD, WHD, 4 * F, args, rank, world, dist, dev, backend, precise)
+        dump_outputs(args, rank, f"{WHD}x{HHD}", {"blurred": keep[1], "rotated": keep[2]})
         if rank == 0:
             print(json.dumps({"only": "1920x1080", "frames_per_gpu": 4 * F, "ms_per_step": round(el / args.steps * 1e3, 4)}))
         if dist:
@@ -535,7 +563,8 @@ def main():
     sampler.start()
     elapsed, g_ms, r_ms, keep = timed_step(H4K, W4K, F, args, rank, world, dist, dev, backend, precise)
     sclk = sampler.stop()
-    frames, gaussian, rotate = keep
+    frames, blurred, rotated, gaussian, rotate = keep
+    dump_outputs(args, rank, f"{W4K}x{H4K}", {"blurred": blurred, "rotated": rotated})
     sclk_kernel = in_kernel_sclk(dev, lambda: (gaussian(), rotate()))        # outside the timed region
     px_per_step = F * H4K * W4K
     value = world * px_per_step * args.steps / elapsed / 1e6
@@ -561,12 +590,13 @@ def main():
     }
     resolutions = {"3840x2160": {"value": round(value, 1), "unit": "Mpix/s", "ms_per_step": result["ms_per_step"],
                                  "frames_per_gpu": F, "gaussian_frac": gauss["frac"], "affine_frac": affine["frac"]}}
-    del keep, frames, gaussian, rotate
+    del keep, frames, blurred, rotated, gaussian, rotate
     torch.cuda.empty_cache()
 
     if not args.no_1080p:
         FH = 4 * F                                           # same bytes per GPU as the 4K batch
         el, g2, r2, keep = timed_step(HHD, WHD, FH, args, rank, world, dist, dev, backend, precise)
+        dump_outputs(args, rank, f"{WHD}x{HHD}", {"blurred": keep[1], "rotated": keep[2]})
         pxh = FH * HHD * WHD
         gh = kernel_entry("sepconv_march (5x5 Gaussian, 1080p RGB)", GAUSS_BYTES_PER_PX, pxh, g2, pmc_traffic("sepconv", F, "kernels_1080p"))
         ah = kernel_entry("affine_bilinear_wq (rotate 30deg + 1.5x bilinear, 1080p RGB)", AFFINE_BYTES_PER_PX, pxh, r2,

@@ -1,6 +1,10 @@
 """CPU: pin the NumPy oracle against the installed Pillow / SciPy / NumPy — the third-party
 kernels the reference calls — using the reference's argument lists (file:line cited in
 oracle/imgxf_oracle.py).  Skipped where those libraries are not importable."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -12,6 +16,7 @@ ImageEnhance = pytest.importorskip("PIL.ImageEnhance")
 ndimage = pytest.importorskip("scipy.ndimage")
 
 SIZES = [(32, 32), (37, 61), (334, 500)]
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.mark.parametrize("hw", SIZES)
@@ -198,30 +203,32 @@ def test_cv_colour_space_restatement_properties():
     assert np.array_equal(O.equalize_hist_cv(np.full((5, 5), 9, np.uint8)), np.full((5, 5), 9, np.uint8))
 
 
-def _persp_cases():
-    import torch
-    rng = np.random.default_rng(11)
-    for trial in range(24):
-        w, h = int(rng.integers(8, 160)), int(rng.integers(8, 160))
-        g = torch.Generator().manual_seed(trial)
-        ds = (0.0, 0.05, 0.1, 0.2, 0.5, 0.9)[trial % 6]
-        st, en = O.perspective_endpoints(w, h, ds, lambda lo, hi: int(torch.randint(lo, hi, size=(1,), generator=g).item()))
-        yield trial, w, h, st, en
+def _perspective_golden():
+    spec = importlib.util.spec_from_file_location("make_perspective_golden", os.path.join(GOLD, "make_perspective_golden.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    with open(os.path.join(GOLD, "perspective_torch_cpu.json")) as fh:
+        return G, {(r["trial"], r["ch"]): r for r in json.load(fh)["cases"]}
 
 
 def test_perspective_warp_vs_torch_primitives():
     """fall_2025/transformations_code:54-66: the oracle's fp32 restatement of torchvision's
     _perspective_grid + grid_sample + mask blend + mul(255).byte() equals, bit for bit, the same
-    pipeline run on the installed torch's CPU primitives (tests/tv_perspective_ref.py)."""
+    pipeline run on torch's CPU primitives (tests/tv_perspective_ref.py).  Those primitives round
+    differently on CPUs whose kernels contract differently, so their coefficients and outputs are the
+    committed record of the build the oracle was pinned to (tests/golden/make_perspective_golden.py)."""
     pytest.importorskip("torch")
-    import tv_perspective_ref as TV
-    for trial, w, h, st, en in _persp_cases():
-        c = TV.coeffs(st, en)
-        c2 = O.perspective_coeffs(st, en)
-        assert np.allclose(np.asarray(c, np.float64), c2, rtol=1e-5, atol=1e-9), (st, en)
+    G, rows = _perspective_golden()
+    n = 0
+    for trial, w, h, st, en in G.cases():
         for ch in (3, 1, 4):
-            a = synth(100 + trial, h, w, ch) if ch != 1 else synth(100 + trial, h, w)[..., 0].copy()
-            assert np.array_equal(O.perspective_warp(a, c), TV.perspective_u8(a, c)), (trial, w, h, ch)
+            r = rows[(trial, ch)]
+            assert (r["w"], r["h"]) == (w, h), trial
+            c = r["coeffs"]
+            assert np.allclose(np.asarray(c, np.float64), O.perspective_coeffs(st, en), rtol=1e-5, atol=1e-9), (st, en)
+            assert G.sha256(O.perspective_warp(G.image(trial, h, w, ch), c)) == r["sha256"], (trial, w, h, ch)
+            n += 1
+    assert n == len(rows) == 72
 
 
 def test_perspective_draws_follow_torch_generator():
