@@ -521,6 +521,243 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const u8* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// PROGRESSIVE entropy decoding (jdphuff.c): a file is a script of scans, each one a spectral band Ss..Se of one component
+// (or the DC of several, interleaved) at a bit position Ah -> Al.  The host (imgxf_jpeg_layout_progressive_host) gives
+// every scan a dependency LEVEL: scans of one level touch disjoint coefficients, a scan of level L + 1 reads / refines
+// what level L wrote.  One workgroup per image; its lanes take the (scan, restart segment) pairs of a level round robin,
+// a barrier separates the levels.  Pillow's 3-component script is 10 scans in 3 levels; the critical path is the luma
+// chain.  A level's scans are taken PROG_SLOTS at a time, their Huffman tables copied to LDS first (in global memory every
+// symbol was an L1 round trip on the one busy lane).  An AC refinement reads every coefficient of its band, so a lane
+// keeps the block it refines in its own LDS row, and the next block's 128 bytes are loaded while this one is decoded: read
+// coefficient by coefficient from global memory, the refinement scans were 90 % of the kernel's time.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int PROG_NT = 64;
+constexpr int PROG_SLOTS = 8;                   // scans whose tables sit in LDS at a time (3 table slots each)
+
+struct ProgTabs { const uint16_t* look; const HuffWalk* walk; };
+
+__device__ __forceinline__ int prog_bits(BitReader& br, int n) {           // n in 1..16, after a refill
+    const int v = (int)br.peek(n);
+    br.skip(n);
+    return v;
+}
+
+__device__ __forceinline__ int prog_extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
+
+__device__ __forceinline__ int prog_symbol(BitReader& br, const ProgTabs& T, bool& bad) {
+    br.refill();
+    return huff_symbol(br, T.look, T.walk, bad);
+}
+
+// decode_mcu_AC_refine over the blocks u0 .. u1 - 1 of a one-component scan; `lb`: the lane's 64-coefficient LDS row
+__device__ __forceinline__ void prog_refine(BitReader& br, const imgxf_jpeg_dec_scan& S, const imgxf_jpeg_dec_comp& cp, int cbx, int u0, int u1,
+                            const ProgTabs& T, int16_t* __restrict__ coefs, int16_t* lb, bool& bad) {
+    const int p1 = 1 << S.al, m1 = -p1;
+    int eobrun = 0;
+    auto block_at = [&](int u) {
+        const int by = u / cbx, bx = u - by * cbx;
+        return coefs + cp.coef_off + ((int64_t)by * cp.blocks_x + bx) * 64;
+    };
+    // the next block's 128 bytes, in eight named registers (an array of them landed in scratch)
+    uint4 n0, n1, n2, n3, n4, n5, n6, n7;
+    auto fetch = [&](int u) {
+        const uint4* g = (const uint4*)block_at(u);
+        n0 = g[0]; n1 = g[1]; n2 = g[2]; n3 = g[3]; n4 = g[4]; n5 = g[5]; n6 = g[6]; n7 = g[7];
+    };
+    if (u0 < u1) fetch(u0);
+    for (int u = u0; u < u1 && !bad; ++u) {
+        int16_t* blk = block_at(u);
+        uint4* l4 = (uint4*)lb;
+        l4[0] = n0; l4[1] = n1; l4[2] = n2; l4[3] = n3; l4[4] = n4; l4[5] = n5; l4[6] = n6; l4[7] = n7;
+        const uint4 n_prev[8] = {n0, n1, n2, n3, n4, n5, n6, n7};
+        if (u + 1 < u1) fetch(u + 1);                                  // (only this lane writes this band of those blocks)
+        // which coefficients of the block are non-zero (what earlier scans sent): the refinement walks them with bit
+        // operations instead of testing the band coefficient by coefficient
+        uint64_t nz = 0;
+        {
+            const u32 w[32] = {n_prev[0].x, n_prev[0].y, n_prev[0].z, n_prev[0].w, n_prev[1].x, n_prev[1].y, n_prev[1].z, n_prev[1].w,
+                               n_prev[2].x, n_prev[2].y, n_prev[2].z, n_prev[2].w, n_prev[3].x, n_prev[3].y, n_prev[3].z, n_prev[3].w,
+                               n_prev[4].x, n_prev[4].y, n_prev[4].z, n_prev[4].w, n_prev[5].x, n_prev[5].y, n_prev[5].z, n_prev[5].w,
+                               n_prev[6].x, n_prev[6].y, n_prev[6].z, n_prev[6].w, n_prev[7].x, n_prev[7].y, n_prev[7].z, n_prev[7].w};
+#pragma unroll
+            for (int i = 0; i < 32; ++i)
+                nz |= (uint64_t)(((w[i] & 0xffffu) != 0) | (((w[i] >> 16) != 0) << 1)) << (2 * i);
+        }
+        // correction bits for the non-zero coefficients in `m` (jdphuff.c: one bit each, in zigzag order)
+        auto correct = [&](uint64_t m) {
+            while (m) {
+                const int q = __builtin_ctzll(m);
+                m &= m - 1;
+                br.refill();
+                if (prog_bits(br, 1)) {
+                    const int c = lb[q];
+                    if ((c & p1) == 0) blk[q] = (int16_t)(c + (c >= 0 ? p1 : m1));
+                }
+            }
+        };
+        const uint64_t band_hi = ~0ull >> (63 - S.se);
+        int k = S.ss;
+        if (eobrun == 0) {
+            while (k <= S.se) {
+                const int rs = prog_symbol(br, T, bad);
+                const int r = rs >> 4;
+                int s = rs & 15;
+                if (s) {
+                    if (s != 1) bad = true;                            // (libjpeg warns and goes on; refused here)
+                    s = prog_bits(br, 1) ? p1 : m1;
+                } else if (r != 15) {
+                    eobrun = 1 << r;
+                    if (r) eobrun += prog_bits(br, r);
+                    break;
+                }
+                // the (r + 1)-th zero coefficient from k on (ZRL: the 16th) is where the run ends; every non-zero one before
+                // it gets a correction bit
+                const uint64_t from_k = band_hi & (~0ull << k);
+                uint64_t z = ~nz & from_k;
+                for (int i = 0; i < r && z; ++i) z &= z - 1;
+                const int t = z ? __builtin_ctzll(z) : S.se + 1;
+                correct(nz & from_k & (t >= 64 ? ~0ull : ~(~0ull << t)));
+                k = t;
+                if (s) blk[min(k, 63)] = (int16_t)s;
+                ++k;
+            }
+        }
+        if (eobrun > 0) {
+            if (k <= S.se) correct(nz & band_hi & (~0ull << k));
+            --eobrun;
+        }
+        if (bad) break;
+        if (br.pos > br.len + 16) bad = true;                          // ran past the data: stop believing it
+    }
+}
+
+// one restart segment `sgi` of scan S: decode_mcu_DC_first / _DC_refine / _AC_first over its MCUs, or prog_refine
+__device__ __forceinline__ void prog_segment(const u8* seg, int len, const imgxf_jpeg_dec_scan& S, const imgxf_jpeg_dec_image& im,
+                                             int sgi, const uint16_t (*look)[256], const HuffWalk* walk, int16_t* __restrict__ coefs,
+                                             int16_t* lb, bool& bad) {
+    BitReader br;
+    br.start(seg, len);
+    const bool inter = S.ncomp > 1;
+    const imgxf_jpeg_dec_comp& c0 = im.comp[S.comp[0]];
+    const int cbx = (c0.dw + 7) >> 3, cby = (c0.dh + 7) >> 3;         // a one-component scan: the component's own grid
+    const int total = inter ? im.mcux * im.mcuy : cbx * cby;
+    const int u0 = sgi * S.restart_interval, u1 = min(total, u0 + S.restart_interval);
+    if (S.ss > 0 && S.ah > 0) { prog_refine(br, S, c0, cbx, u0, u1, ProgTabs{look[0], walk}, coefs, lb, bad); return; }
+    const int p1 = 1 << S.al;
+    int pred[3] = {0, 0, 0};
+    int eobrun = 0;                                                    // (both reset at every RSTn: a segment starts clean)
+    for (int u = u0; u < u1 && !bad; ++u) {
+        if (S.ss == 0) {                                               // DC: every block of the MCU (dummy blocks included)
+            const int my = inter ? u / im.mcux : u / cbx, mx = inter ? u - my * im.mcux : u - my * cbx;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {                              // (unrolled: pred[] stays in registers)
+                if (k >= S.ncomp) break;
+                const imgxf_jpeg_dec_comp& cp = im.comp[S.comp[k]];
+                const int nv = inter ? cp.v : 1, nh = inter ? cp.h : 1;
+                for (int by = 0; by < nv; ++by)
+                    for (int bx = 0; bx < nh; ++bx) {
+                        int16_t* blk = coefs + cp.coef_off + ((int64_t)(my * nv + by) * cp.blocks_x + (mx * nh + bx)) * 64;
+                        if (S.ah == 0) {
+                            const int s = prog_symbol(br, ProgTabs{look[k], walk + k}, bad) & 15;
+                            const int d = s ? prog_extend(prog_bits(br, s), s) : 0;
+                            pred[k] += d;
+                            blk[0] = (int16_t)(pred[k] * p1);                  // LEFT_SHIFT(s, Al)
+                        } else {
+                            br.refill();
+                            if (prog_bits(br, 1)) blk[0] = (int16_t)(blk[0] | p1);
+                        }
+                    }
+            }
+        } else {                                                       // decode_mcu_AC_first
+            if (eobrun > 0) { --eobrun; continue; }
+            const int by = u / cbx, bx = u - by * cbx;
+            int16_t* blk = coefs + c0.coef_off + ((int64_t)by * c0.blocks_x + bx) * 64;
+            for (int k = S.ss; k <= S.se; ++k) {
+                const int rs = prog_symbol(br, ProgTabs{look[0], walk}, bad), r = rs >> 4, s = rs & 15;
+                if (s) {
+                    k += r;
+                    blk[min(k, 63)] = (int16_t)(prog_extend(prog_bits(br, s), s) * p1);
+                } else if (r == 15) {
+                    k += 15;
+                } else {
+                    eobrun = 1 << r;
+                    if (r) eobrun += prog_bits(br, r);
+                    --eobrun;
+                    break;
+                }
+            }
+        }
+        if (br.pos > br.len + 16) bad = true;                          // ran past the data: stop believing it
+    }
+}
+
+__global__ __launch_bounds__(PROG_NT) void jpeg_prog_kernel(const u8* __restrict__ scan, const int64_t* __restrict__ seg_off,
+                                                           const int32_t* __restrict__ seg_len, const imgxf_jpeg_dec_scan* __restrict__ scans,
+                                                           int n_scans, const imgxf_jpeg_dec_image* __restrict__ images,
+                                                           const imgxf_jpeg_dec_lut* __restrict__ luts, int16_t* __restrict__ coefs,
+                                                           int32_t* __restrict__ status) {
+    __shared__ imgxf_jpeg_dec_image im_s;
+    __shared__ int range_s[2];
+    __shared__ uint16_t look_s[3 * PROG_SLOTS][256];
+    __shared__ HuffWalk walk_s[3 * PROG_SLOTS];
+    __shared__ __attribute__((aligned(16))) int16_t lblk_s[PROG_NT][64];
+    const int tid = threadIdx.x, img = blockIdx.x;
+    for (int i = tid; i < (int)(sizeof(imgxf_jpeg_dec_image) / 4); i += PROG_NT) ((u32*)&im_s)[i] = ((const u32*)(images + img))[i];
+    if (tid < 2) {                                                     // this image's rows: [lower bound of img, of img + 1)
+        int lo = 0, hi = n_scans;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (scans[mid].image < img + tid) lo = mid + 1; else hi = mid; }
+        range_s[tid] = lo;
+    }
+    __syncthreads();
+    const imgxf_jpeg_dec_image& im = im_s;
+    const int s0 = range_s[0], s1 = range_s[1];
+    int levels = 0;
+    for (int s = s0; s < s1; ++s) levels = max(levels, scans[s].level + 1);
+    bool bad = false;
+    for (int lev = 0; lev < levels && !bad; ++lev) {                   // (uniform)
+        for (int first = s0; first < s1 && !bad;) {                    // (uniform) the level's scans, PROG_SLOTS at a time
+            int last = first, q = 0;
+            for (; last < s1 && q < PROG_SLOTS; ++last) {              // tables of those scans -> LDS slots 3 q + k
+                const imgxf_jpeg_dec_scan& S = scans[last];
+                if (S.level != lev) continue;
+                for (int k = 0; k < 3; ++k) {
+                    const int t = S.ss == 0 ? (S.ah == 0 && k < S.ncomp ? S.dc_tab[k] : -1) : (k == 0 ? S.ac_tab : -1);
+                    if (t < 0) continue;
+                    const imgxf_jpeg_dec_lut& L = luts[t];
+                    const int slot = 3 * q + k;
+                    for (int i = tid; i < 256; i += PROG_NT) {
+                        look_s[slot][i] = L.look[i];
+                        walk_s[slot].huffval[i] = L.huffval[i];
+                        if (i < 18) walk_s[slot].maxcode[i] = L.maxcode[i];
+                        if (i < 17) walk_s[slot].valoff[i] = L.valoff[i];
+                    }
+                }
+                ++q;
+            }
+            __syncthreads();
+            int base = 0;
+            q = 0;
+            for (int s = first; s < last; ++s) {
+                const imgxf_jpeg_dec_scan& S = scans[s];
+                if (S.level != lev) continue;
+                const int slot0 = 3 * q++;
+                bool ok = true;                                        // rows the image cannot hold are damage, not addresses
+                for (int k = 0; k < S.ncomp; ++k) ok &= S.comp[k] < im.ncomp;
+                if (!ok) { bad = true; continue; }
+                for (int j = ((tid - base) % PROG_NT + PROG_NT) % PROG_NT; j < S.seg_count && !bad; j += PROG_NT)
+                    prog_segment(scan + seg_off[S.seg_first + j], seg_len[S.seg_first + j], S, im, j, look_s + slot0, walk_s + slot0, coefs,
+                                 lblk_s[tid], bad);
+                base += S.seg_count;
+            }
+            first = last;
+            __threadfence_block();                                     // these coefficients before a later level reads them,
+            if (__syncthreads_or(bad ? 1 : 0)) bad = true;             // and the table slots before they are overwritten
+        }
+    }
+    if (bad && status && tid == 0) atomicOr(status + img, 1);
+}
+
 static int dec_check_host(const imgxf_jpeg_dec_image* host, int n, int64_t* max_blocks, int64_t* max_quads) {
     *max_blocks = 0; *max_quads = 0;
     for (int i = 0; i < n; ++i) {
@@ -595,5 +832,29 @@ IMGXF_API int imgxf_jpeg_decode_color(const uint8_t* planes, const imgxf_jpeg_de
     int64_t mb, mq;
     IMGXF_CHECK(dec_check_host(images_host, n, &mb, &mq));
     hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((mq + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, planes, images, out);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_decode_progressive(const uint8_t* scan, const int64_t* seg_off, const int32_t* seg_len,
+                                            const imgxf_jpeg_dec_scan* scans, const imgxf_jpeg_dec_scan* scans_host, int n_scans,
+                                            const imgxf_jpeg_dec_image* images, int n, const imgxf_jpeg_dec_lut* luts, int16_t* coefs,
+                                            int32_t* status, void* stream) {
+    if (n < 0 || n_scans < 0) return IMGXF_ERR_ARG;
+    if (n == 0) return IMGXF_OK;
+    if (!scan || !seg_off || !seg_len || !images || !luts || !coefs || (n_scans && (!scans || !scans_host))) return IMGXF_ERR_NULL;
+    for (int s = 0; s < n_scans; ++s) {                                // the rows the kernel trusts for addresses
+        const imgxf_jpeg_dec_scan& S = scans_host[s];
+        if (S.image < 0 || S.image >= n || (s && S.image < scans_host[s - 1].image)) return IMGXF_ERR_ARG;
+        if (S.ncomp < 1 || S.ncomp > 3 || (S.ss > 0 && S.ncomp != 1)) return IMGXF_ERR_ARG;
+        if (S.ss < 0 || S.ss > S.se || S.se > 63 || (S.ss == 0 && S.se != 0) || S.ah < 0 || S.al < 0 || S.al > 13) return IMGXF_ERR_ARG;
+        if (S.restart_interval < 1 || S.seg_first < 0 || S.seg_count < 0 || S.level < 0 || S.level >= n_scans) return IMGXF_ERR_ARG;
+        for (int k = 0; k < S.ncomp; ++k) {
+            if (S.comp[k] < 0 || S.comp[k] > 2) return IMGXF_ERR_ARG;
+            if (S.ss == 0 && S.ah == 0 && S.dc_tab[k] < 0) return IMGXF_ERR_ARG;
+        }
+        if (S.ss > 0 && S.ac_tab < 0) return IMGXF_ERR_ARG;
+    }
+    hipLaunchKernelGGL(jpeg_prog_kernel, dim3((unsigned)n), dim3(PROG_NT), 0, (hipStream_t)stream, scan, seg_off, seg_len, scans, n_scans,
+                       images, luts, coefs, status);
     return launch_status();
 }

@@ -281,3 +281,281 @@ IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* 
     if (fill) { *coef_total = coef_pos; *plane_total = plane_pos; }
     return IMGXF_OK;
 }
+
+// ---- progressive files (SOF2) ----------------------------------------------------------------------------------------
+// The statement of oracle/jpeg_progressive_oracle.py `parse` for a batch: every marker from SOI to EOI (jdmarker.c), the
+// checks of jdphuff.c start_pass_phuff_decoder (coef_bits), jdinput.c latch_quant_tables, jdcoefct.c smoothing_ok and
+// jdapimin.c default_decompress_parms' colour space, and per scan the tables that were current at its SOS.
+namespace {
+
+struct ProgScan {
+    int ncomp, comp[3], td[3], ta[3], ss, se, ah, al, dri;
+    HuffSpec dc[3], ac;
+    size_t ecs_start;
+    int units, want;             // MCUs (blocks of a one-component scan) and restart segments
+};
+
+struct ProgParsed {
+    Parsed P;                    // frame, sampling (P.dri unused)
+    uint16_t quant[3][64];       // latched at each component's first scan
+    std::vector<ProgScan> scans;
+};
+
+// the first marker after data[pos] that is neither a stuffed zero nor RSTn (a lone 0xFF as the last byte belongs to the scan)
+size_t ecs_end(const uint8_t* d, size_t n, size_t pos) {
+    for (;;) {
+        const uint8_t* ff = pos < n ? (const uint8_t*)memchr(d + pos, 0xFF, n - pos) : nullptr;
+        if (!ff) return n;
+        const size_t at = (size_t)(ff - d);
+        if (at + 1 >= n) return n;
+        const uint8_t nxt = d[at + 1];
+        if (nxt == 0x00 || (nxt >= 0xD0 && nxt <= 0xD7)) { pos = at + 2; continue; }
+        return at;
+    }
+}
+
+// jdcoefct.c smoothing_ok (libjpeg-turbo >= 2.1: SAVED_COEFS = 10; Q00 Q01 Q10 Q20 Q11 Q02 Q03 Q12 Q21 Q30 in natural order)
+bool would_smooth(const ProgParsed& G, const int (*coef_bits)[64]) {
+    static const int kQ[10] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24};
+    bool useful = false;
+    for (int c = 0; c < G.P.ncomp; ++c) {
+        for (int j = 0; j < 10; ++j) if (G.quant[c][kQ[j]] == 0) return false;
+        if (coef_bits[c][0] < 0) return false;
+        for (int k = 1; k < 10; ++k) if (coef_bits[c][k] != 0) useful = true;
+    }
+    return useful;
+}
+
+int parse_progressive(const uint8_t* d, size_t n, ProgParsed& G) {
+    Parsed& P = G.P;
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return IMGXF_JPEG_E_NOT_JPEG;
+    size_t pos = 2;
+    bool have_frame = false, jfif = false, latched[3] = {false, false, false};
+    int adobe = -1;
+    int coef_bits[3][64];
+    Geometry g;
+    for (;;) {
+        const int damaged = G.scans.empty() ? IMGXF_JPEG_E_MARKERS : IMGXF_JPEG_E_TRUNCATED;
+        if (pos + 2 > n || d[pos] != 0xFF) return damaged;
+        while (pos + 2 < n && d[pos + 1] == 0xFF) ++pos;                 // fill bytes
+        const int marker = d[pos + 1];
+        if (marker == 0xD9) break;                                        // EOI
+        if (pos + 4 > n) return damaged;
+        const size_t seglen = ((size_t)d[pos + 2] << 8) | d[pos + 3];
+        if (seglen < 2 || pos + 2 + seglen > n) return damaged;
+        const uint8_t* seg = d + pos + 4;
+        const size_t sl = seglen - 2;
+        if (marker == 0xDB) {
+            size_t i = 0;
+            while (i < sl) {
+                const int pq = seg[i] >> 4, tq = seg[i] & 15;
+                ++i;
+                if (tq > 3 || i + (pq ? 128 : 64) > sl) return IMGXF_JPEG_E_MARKERS;
+                for (int k = 0; k < 64; ++k)
+                    P.qt[tq][kZigzag[k]] = pq ? (uint16_t)((seg[i + 2 * k] << 8) | seg[i + 2 * k + 1]) : seg[i + k];
+                P.have_qt[tq] = true;
+                i += pq ? 128 : 64;
+            }
+        } else if (marker == 0xC2) {
+            if (have_frame || sl < 6) return IMGXF_JPEG_E_MARKERS;
+            if (seg[0] != 8) return IMGXF_JPEG_E_PRECISION;
+            P.height = (seg[1] << 8) | seg[2]; P.width = (seg[3] << 8) | seg[4]; P.ncomp = seg[5];
+            if (P.ncomp != 1 && P.ncomp != 3) return IMGXF_JPEG_E_COMPONENTS;
+            if (sl < 6 + 3 * (size_t)P.ncomp) return IMGXF_JPEG_E_MARKERS;
+            for (int k = 0; k < P.ncomp; ++k) {
+                P.cid[k] = seg[6 + 3 * k]; P.ch[k] = seg[7 + 3 * k] >> 4; P.cv[k] = seg[7 + 3 * k] & 15; P.tq[k] = seg[8 + 3 * k];
+                for (int j = 0; j < 64; ++j) coef_bits[k][j] = -1;
+            }
+            if (P.width < 1 || P.height < 1) return IMGXF_JPEG_E_MARKERS;
+            have_frame = true;
+        } else if (marker >= 0xC0 && marker <= 0xCF && marker != 0xC4 && marker != 0xC8 && marker != 0xCC) {
+            return IMGXF_JPEG_E_PROCESS;                                 // baseline, lossless or arithmetic coding
+        } else if (marker == 0xC4) {
+            size_t i = 0;
+            while (i < sl) {
+                if (i + 17 > sl) return IMGXF_JPEG_E_MARKERS;
+                const int tc = seg[i] >> 4, th = seg[i] & 15;
+                int cnt = 0;
+                for (int k = 0; k < 16; ++k) cnt += seg[i + 1 + k];
+                if (tc > 1 || th > 3 || cnt > 256 || i + 17 + (size_t)cnt > sl) return IMGXF_JPEG_E_MARKERS;
+                HuffSpec& H = P.huff[tc][th];
+                H.present = true; H.nvals = cnt;
+                memcpy(H.bits, seg + i + 1, 16);
+                memset(H.vals, 0, sizeof(H.vals));
+                memcpy(H.vals, seg + i + 17, (size_t)cnt);
+                i += 17 + (size_t)cnt;
+            }
+        } else if (marker == 0xDD) {
+            if (sl < 2) return IMGXF_JPEG_E_MARKERS;
+            P.dri = (seg[0] << 8) | seg[1];
+        } else if (marker == 0xE0) {
+            if (sl >= 14 && !memcmp(seg, "JFIF\0", 5)) jfif = true;
+        } else if (marker == 0xEE) {
+            if (sl >= 12 && !memcmp(seg, "Adobe", 5)) adobe = seg[11];
+        } else if (marker == 0xDA) {
+            if (!have_frame || sl < 1) return IMGXF_JPEG_E_MARKERS;
+            if (G.scans.empty()) {                                       // jpeg_read_header's checks, at the first SOS
+                const int rc = geometry(P, g);
+                if (rc) return rc;
+                if (P.ncomp == 3) {                                      // jdapimin.c default_decompress_parms
+                    const bool ycc = jfif ? true : adobe >= 0 ? adobe == 1 : !(P.cid[0] == 'R' && P.cid[1] == 'G' && P.cid[2] == 'B');
+                    if (!ycc) return IMGXF_JPEG_E_COLORSPACE;
+                }
+            }
+            ProgScan S;
+            S.ncomp = seg[0];
+            if (S.ncomp < 1 || S.ncomp > P.ncomp || sl < 4 + 2 * (size_t)S.ncomp) return IMGXF_JPEG_E_MARKERS;
+            for (int k = 0; k < S.ncomp; ++k) {
+                int ci = -1;
+                for (int c = 0; c < P.ncomp; ++c) if (P.cid[c] == seg[1 + 2 * k]) { ci = c; break; }
+                if (ci < 0 || (k > 0 && ci <= S.comp[k - 1])) return IMGXF_JPEG_E_SCAN_ORDER;
+                S.comp[k] = ci; S.td[k] = seg[2 + 2 * k] >> 4; S.ta[k] = seg[2 + 2 * k] & 15;
+                if (S.td[k] > 3 || S.ta[k] > 3) return IMGXF_JPEG_E_MARKERS;
+            }
+            const uint8_t* q = seg + 1 + 2 * S.ncomp;
+            S.ss = q[0]; S.se = q[1]; S.ah = q[2] >> 4; S.al = q[2] & 15; S.dri = P.dri;
+            // jdphuff.c start_pass_phuff_decoder: ERREXIT (bad progression) and WARNMS (bogus progression) alike
+            bool bad = S.ss == 0 ? S.se != 0 : (S.ss > S.se || S.se > 63 || S.ncomp != 1);
+            if (S.ah != 0 && S.al != S.ah - 1) bad = true;
+            if (S.al > 13) bad = true;
+            if (bad) return IMGXF_JPEG_E_SCAN_SCRIPT;
+            for (int k = 0; k < S.ncomp; ++k) {
+                int* cb = coef_bits[S.comp[k]];
+                if (S.ss > 0 && cb[0] < 0) return IMGXF_JPEG_E_SCAN_SCRIPT;
+                for (int j = S.ss; j <= S.se; ++j) {
+                    if (S.ah != (cb[j] < 0 ? 0 : cb[j])) return IMGXF_JPEG_E_SCAN_SCRIPT;
+                    cb[j] = S.al;
+                }
+            }
+            for (int k = 0; k < S.ncomp; ++k) {
+                const int c = S.comp[k];
+                if (!latched[c]) {                                       // jdinput.c latch_quant_tables
+                    if (P.tq[c] > 3 || !P.have_qt[P.tq[c]]) return IMGXF_JPEG_E_NO_QUANT;
+                    memcpy(G.quant[c], P.qt[P.tq[c]], sizeof(G.quant[c]));
+                    latched[c] = true;
+                }
+                if (S.ss == 0 && S.ah == 0) {
+                    if (!P.huff[0][S.td[k]].present) return IMGXF_JPEG_E_NO_HUFF;
+                    S.dc[k] = P.huff[0][S.td[k]];
+                }
+                if (S.ss > 0) {
+                    if (!P.huff[1][S.ta[k]].present) return IMGXF_JPEG_E_NO_HUFF;
+                    S.ac = P.huff[1][S.ta[k]];
+                }
+            }
+            if (S.ncomp > 1) S.units = g.mcux * g.mcuy;
+            else {
+                const int c = S.comp[0];
+                const int dw = (P.width * g.ch[c] + g.hmax - 1) / g.hmax, dh = (P.height * g.cv[c] + g.vmax - 1) / g.vmax;
+                S.units = ((dw + 7) / 8) * ((dh + 7) / 8);
+            }
+            const int ri = S.dri ? S.dri : S.units;
+            S.want = (S.units + ri - 1) / ri;
+            S.ecs_start = pos + 2 + seglen;
+            G.scans.push_back(S);
+            pos = ecs_end(d, n, S.ecs_start);
+            continue;
+        } else if (marker == 0xD8 || (marker >= 0xD0 && marker <= 0xD7)) {
+            return IMGXF_JPEG_E_MARKERS;
+        }
+        pos += 2 + seglen;
+    }
+    if (G.scans.empty()) return IMGXF_JPEG_E_MARKERS;
+    if (would_smooth(G, coef_bits)) return IMGXF_JPEG_E_SMOOTHING;
+    return 0;
+}
+
+int lut_index(std::vector<HuffSpec>& uniq, const HuffSpec& H, imgxf_jpeg_dec_lut* luts, int lut_cap) {
+    for (size_t u = 0; u < uniq.size(); ++u)
+        if (!memcmp(uniq[u].bits, H.bits, 16) && uniq[u].nvals == H.nvals && !memcmp(uniq[u].vals, H.vals, (size_t)H.nvals)) return (int)u;
+    if ((int)uniq.size() >= lut_cap) return -1;
+    uniq.push_back(H);
+    derive_lut(H, luts[uniq.size() - 1]);
+    return (int)uniq.size() - 1;
+}
+
+} // namespace
+
+IMGXF_API int imgxf_jpeg_layout_progressive_host(const uint8_t* const* files, const size_t* sizes, int n, imgxf_jpeg_dec_image* images,
+                                                 imgxf_jpeg_dec_scan* scans, int scans_cap, int* n_scans,
+                                                 imgxf_jpeg_dec_lut* luts, int lut_cap, int* n_luts, uint16_t* quants, int quant_cap,
+                                                 int* n_quants, uint8_t* scan, size_t scan_cap, size_t* scan_bytes, int64_t* seg_off,
+                                                 int32_t* seg_len, int seg_cap, int* n_segs, int64_t* coef_total, int64_t* plane_total,
+                                                 int32_t* status) {
+    if (n < 0) return IMGXF_ERR_ARG;
+    if (!files || !sizes || !n_scans || !n_luts || !n_quants || !scan_bytes || !n_segs || !status) return IMGXF_ERR_NULL;
+    const bool fill = scan != nullptr;
+    if (fill && (!images || !scans || !luts || !quants || !seg_off || !seg_len || !coef_total || !plane_total)) return IMGXF_ERR_NULL;
+    std::vector<HuffSpec> uniq;
+    int nq = 0, nseg = 0, nsc = 0, nluts_bound = 0;
+    size_t spos = 0, cap_bound = 0;
+    int64_t coef_pos = 0, plane_pos = 0;
+    ProgParsed G;
+    for (int i = 0; i < n; ++i) {
+        status[i] = 0;
+        G.P = Parsed();
+        G.scans.clear();
+        int rc = files[i] ? parse_progressive(files[i], sizes[i], G) : IMGXF_JPEG_E_NOT_JPEG;
+        if (rc) { status[i] = rc; continue; }
+        const Parsed& P = G.P;
+        Geometry g;
+        geometry(P, g);
+        int want = 0;
+        for (const ProgScan& S : G.scans) { want += S.want; cap_bound += 32 * ((size_t)S.want + 1); }
+        cap_bound += sizes[i];
+        if (!fill) { nseg += want; nq += P.ncomp; nsc += (int)G.scans.size(); nluts_bound += 4 * (int)G.scans.size(); continue; }
+        if (nseg + want > seg_cap || nsc + (int)G.scans.size() > scans_cap) return IMGXF_ERR_WORKSPACE;
+        const int nseg0 = nseg, nsc0 = nsc;
+        const size_t spos0 = spos;
+        for (const ProgScan& S : G.scans) {
+            int got = 0; size_t end = 0;
+            rc = imgxf_jpeg_unstuff_host(files[i], sizes[i], S.ecs_start, scan, scan_cap, &spos, seg_off + nseg, seg_len + nseg, S.want, &got, &end);
+            if (rc != IMGXF_OK) return rc;
+            if (got < S.want) { status[i] = IMGXF_JPEG_E_TRUNCATED; break; }
+            imgxf_jpeg_dec_scan& R = scans[nsc];
+            memset(&R, 0, sizeof(R));
+            R.image = i; R.ncomp = S.ncomp;
+            R.ss = S.ss; R.se = S.se; R.ah = S.ah; R.al = S.al;
+            R.ac_tab = -1;
+            for (int k = 0; k < 3; ++k) { R.comp[k] = k < S.ncomp ? S.comp[k] : 0; R.dc_tab[k] = -1; }
+            for (int k = 0; k < S.ncomp; ++k)
+                if (S.ss == 0 && S.ah == 0 && (R.dc_tab[k] = lut_index(uniq, S.dc[k], luts, lut_cap)) < 0) return IMGXF_ERR_WORKSPACE;
+            if (S.ss > 0 && (R.ac_tab = lut_index(uniq, S.ac, luts, lut_cap)) < 0) return IMGXF_ERR_WORKSPACE;
+            R.restart_interval = S.dri ? S.dri : S.units;
+            R.seg_first = nseg; R.seg_count = S.want;
+            R.level = 0;
+            for (int e = nsc0; e < nsc; ++e) {                           // dependency: a shared component and an overlapping band
+                const imgxf_jpeg_dec_scan& E = scans[e];
+                bool share = false;
+                for (int a = 0; a < E.ncomp; ++a)
+                    for (int b = 0; b < R.ncomp; ++b) share |= E.comp[a] == R.comp[b];
+                if (share && E.ss <= R.se && R.ss <= E.se && E.level + 1 > R.level) R.level = E.level + 1;
+            }
+            nseg += S.want;
+            ++nsc;
+        }
+        if (status[i]) { nseg = nseg0; nsc = nsc0; spos = spos0; continue; }
+        imgxf_jpeg_dec_image& im = images[i];
+        memset(&im, 0, sizeof(im));
+        im.width = P.width; im.height = P.height; im.ncomp = P.ncomp; im.hmax = g.hmax; im.vmax = g.vmax; im.mcux = g.mcux; im.mcuy = g.mcuy;
+        for (int c = 0; c < P.ncomp; ++c) {
+            imgxf_jpeg_dec_comp& cp = im.comp[c];
+            cp.h = g.ch[c]; cp.v = g.cv[c];
+            cp.dc_tab = -1; cp.ac_tab = -1;
+            if (nq >= quant_cap) return IMGXF_ERR_WORKSPACE;
+            cp.quant = nq;
+            memcpy(quants + (size_t)nq * 64, G.quant[c], 64 * sizeof(uint16_t));
+            ++nq;
+            cp.blocks_x = g.mcux * cp.h; cp.blocks_y = g.mcuy * cp.v;
+            cp.dw = (P.width * cp.h + g.hmax - 1) / g.hmax; cp.dh = (P.height * cp.v + g.vmax - 1) / g.vmax;
+            cp.coef_off = coef_pos; cp.plane_off = plane_pos;
+            coef_pos += (int64_t)cp.blocks_x * cp.blocks_y * 64;
+            plane_pos += (int64_t)cp.blocks_x * cp.blocks_y * 64;
+        }
+    }
+    *n_segs = nseg; *n_quants = nq; *n_scans = nsc;
+    *n_luts = fill ? (int)uniq.size() : nluts_bound;
+    *scan_bytes = fill ? spos : cap_bound;
+    if (fill) { *coef_total = coef_pos; *plane_total = plane_pos; }
+    return IMGXF_OK;
+}

@@ -45,12 +45,13 @@ def _read(path: str):
 
 
 DECODE_STATS = {"device": 0, "pillow": 0}      # files decoded by the device reader / handed to Pillow by decoder="device"
+PROGRESSIVE_ON_DEVICE = os.environ.get("IMGXF_JPEG_PROGRESSIVE") == "1"   # progressive files on the device reader too (opt-in)
 
 
 def _decode_on_device(read):
     """[(bytes, path)] -> [(frame, path)]: one `jpeg_decode.decode` over the chunk; a file outside the device reader's
-    class (progressive, CMYK, ...: `UnsupportedJpeg`) or one it finds damaged is decoded by Pillow, as :83 does, and
-    uploaded — counted in DECODE_STATS so that the share is visible."""
+    class (progressive unless PROGRESSIVE_ON_DEVICE, CMYK, ...: `UnsupportedJpeg`) or one it finds damaged is decoded by
+    Pillow, as :83 does, and uploaded — counted in DECODE_STATS so that the share is visible."""
     import io
     import numpy as np
     import torch
@@ -58,14 +59,14 @@ def _decode_on_device(read):
     from ._ffi import ImgxfError
     items = [r for r in read if r is not None]
     try:
-        frames = jpeg_decode.decode([d for d, _ in items])
+        frames = jpeg_decode.decode([d for d, _ in items], progressive=PROGRESSIVE_ON_DEVICE)
         DECODE_STATS["device"] += len(items)
         return [(t, p) for t, (_, p) in zip(frames, items)]
     except (jpeg_decode.UnsupportedJpeg, ImgxfError):
         out = []
         for d, p in items:
             try:
-                out.append((jpeg_decode.decode([d])[0], p))
+                out.append((jpeg_decode.decode([d], progressive=PROGRESSIVE_ON_DEVICE)[0], p))
                 DECODE_STATS["device"] += 1
             except (jpeg_decode.UnsupportedJpeg, ImgxfError):
                 try:

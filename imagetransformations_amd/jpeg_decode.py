@@ -24,7 +24,8 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
 
 
 class UnsupportedJpeg(ValueError):
-    """Not a file the device reader covers (progressive, arithmetic, 12-bit, CMYK, non-interleaved scans, ...)."""
+    """Not a file the device reader covers (progressive unless asked for, arithmetic, 12-bit, CMYK, non-interleaved
+    baseline scans, ...)."""
 
 
 class DecComp(C.Structure):
@@ -168,7 +169,9 @@ def _segments(raw: bytes):
 _REFUSALS = {1: "not a JPEG (no SOI)", 2: "damaged marker structure", 3: "samples are not 8 bits",
              4: "progressive, lossless or arithmetic coding", 5: "neither 1 nor 3 components, or a non-interleaved scan",
              6: "the scan names an unknown component or not in frame order", 7: "sampling factors outside 1..2",
-             8: "chroma sampling other than 4:4:4, 4:2:2 (h2v1) or 4:2:0", 9: "missing quantisation table", 10: "missing Huffman table"}
+             8: "chroma sampling other than 4:4:4, 4:2:2 (h2v1) or 4:2:0", 9: "missing quantisation table", 10: "missing Huffman table",
+             12: "a progression libjpeg rejects or warns about", 13: "libjpeg would smooth blocks (coefficients 1..9 not fully refined)",
+             14: "a 3-component file libjpeg does not read as YCbCr"}
 
 
 def _raise_for_status(status, n: int) -> None:
@@ -181,13 +184,110 @@ def _raise_for_status(status, n: int) -> None:
             raise UnsupportedJpeg(f"file {i}: {_REFUSALS.get(code, code)}")
 
 
+class DecScan(C.Structure):
+    """struct imgxf_jpeg_dec_scan (include/imgxf.h)"""
+    _fields_ = [("image", C.c_int32), ("ncomp", C.c_int32), ("comp", C.c_int32 * 3), ("ss", C.c_int32), ("se", C.c_int32),
+                ("ah", C.c_int32), ("al", C.c_int32), ("dc_tab", C.c_int32 * 3), ("ac_tab", C.c_int32),
+                ("restart_interval", C.c_int32), ("seg_first", C.c_int32), ("seg_count", C.c_int32), ("level", C.c_int32)]
+
+
+def is_progressive(data: bytes) -> bool:
+    """Whether the file's frame marker (the first SOFn) is SOF2.  Anything unexpected answers False: the baseline reader
+    then refuses the file as it always has."""
+    pos, n = 2, len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        return False
+    while pos + 4 <= n and data[pos] == 0xFF:
+        marker = data[pos + 1]
+        if marker == 0xFF:
+            pos += 1
+            continue
+        if marker == 0xC2:
+            return True
+        if 0xC0 <= marker <= 0xCF and marker not in (0xC4, 0xC8, 0xCC) or marker == 0xDA:
+            return False
+        pos += 2 + ((data[pos + 2] << 8) | data[pos + 3])
+    return False
+
+
+class _Layout:
+    """One call pair of imgxf_jpeg_layout_host (progressive=False) or imgxf_jpeg_layout_progressive_host over some files of
+    the batch: __init__ is pass 1 (counts, status), fill() pass 2 (the arrays)."""
+
+    def __init__(self, files: List[bytes], progressive: bool):
+        n = self.n = len(files)
+        self.progressive = progressive
+        self.ptrs = (C.c_char_p * n)(*files)
+        self.sizes = (C.c_size_t * n)(*map(len, files))
+        self.status = (C.c_int32 * n)()
+        self.n_luts, self.n_quants, self.n_segs, self.n_scans = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self.scan_bytes, self.coef_total, self.plane_total = C.c_size_t(0), C.c_int64(0), C.c_int64(0)
+        self._call(None, None, 0, None, 0, None, 0, None, 0, None, None, 0, None, None)
+
+    def _call(self, images, scans, scans_cap, luts, lut_cap, quants, quant_cap, scan, scan_cap, seg_off, seg_len, seg_cap, coef, plane):
+        head = (self.ptrs, self.sizes, self.n, images)
+        if self.progressive:
+            head += (scans, scans_cap, C.addressof(self.n_scans))
+        F.call("imgxf_jpeg_layout_progressive_host" if self.progressive else "imgxf_jpeg_layout_host", *head, luts, lut_cap,
+               C.addressof(self.n_luts), quants, quant_cap, C.addressof(self.n_quants), scan, scan_cap, C.addressof(self.scan_bytes),
+               seg_off, seg_len, seg_cap, C.addressof(self.n_segs), coef, plane, self.status)
+
+    def fill(self) -> None:
+        n = self.n
+        self.images = (DecImage * n)()
+        lut_cap, quant_cap = max(1, self.n_luts.value), max(1, self.n_quants.value)
+        seg_cap, scan_cap, scans_cap = max(1, self.n_segs.value), max(64, self.scan_bytes.value), max(1, self.n_scans.value)
+        self.luts = (DecLut * lut_cap)()
+        self.scans = (DecScan * scans_cap)()
+        self.quants_h = torch.empty((quant_cap, 64), dtype=torch.int16)
+        self.scan_host = torch.empty((scan_cap,), dtype=torch.uint8)
+        self.seg_off_h = torch.zeros((seg_cap,), dtype=torch.int64)
+        self.seg_len_h = torch.zeros((seg_cap,), dtype=torch.int32)
+        self._call(self.images, self.scans, scans_cap, self.luts, lut_cap, self.quants_h.data_ptr(), quant_cap,
+                   self.scan_host.data_ptr(), scan_cap, self.seg_off_h.data_ptr(), self.seg_len_h.data_ptr(), seg_cap,
+                   C.addressof(self.coef_total), C.addressof(self.plane_total))
+
+    def run(self, device, stream, out, mark) -> torch.Tensor:
+        """Uploads, entropy decoding, IDCT, colour into `out` (out_off / out_pitch of the images are set); -> device status."""
+        n = self.n
+        scan_d = self.scan_host[:max(16, self.scan_bytes.value)].to(device, non_blocking=False)
+        seg_off_d = self.seg_off_h.to(device)
+        seg_len_d = self.seg_len_h.to(device)
+        images_d = torch.frombuffer(bytearray(bytes(self.images)), dtype=torch.uint8).to(device)
+        luts_d = torch.frombuffer(bytearray(bytes(self.luts)), dtype=torch.uint8).to(device)
+        quants_d = self.quants_h.to(device)
+        if self.progressive:
+            scans_d = torch.frombuffer(bytearray(bytes(self.scans)), dtype=torch.uint8).to(device)
+        coefs = torch.zeros((self.coef_total.value,), dtype=torch.int16, device=device)
+        planes = torch.empty((self.plane_total.value,), dtype=torch.uint8, device=device)
+        status = torch.zeros((n,), dtype=torch.int32, device=device)
+        mark("uploads + zero fill")
+        if self.progressive:
+            F.call("imgxf_jpeg_decode_progressive", scan_d.data_ptr(), seg_off_d.data_ptr(), seg_len_d.data_ptr(), scans_d.data_ptr(),
+                   C.addressof(self.scans), self.n_scans.value, images_d.data_ptr(), n, luts_d.data_ptr(), coefs.data_ptr(),
+                   status.data_ptr(), stream)
+            mark("progressive kernel")
+        else:
+            F.call("imgxf_jpeg_decode_huffman", scan_d.data_ptr(), seg_off_d.data_ptr(), seg_len_d.data_ptr(), images_d.data_ptr(), n,
+                   luts_d.data_ptr(), coefs.data_ptr(), status.data_ptr(), stream)
+            mark("huffman kernel")
+        F.call("imgxf_jpeg_decode_idct", coefs.data_ptr(), images_d.data_ptr(), C.addressof(self.images), n, quants_d.data_ptr(),
+               planes.data_ptr(), stream)
+        mark("idct kernel")
+        F.call("imgxf_jpeg_decode_color", planes.data_ptr(), images_d.data_ptr(), C.addressof(self.images), n, out.data_ptr(), stream)
+        mark("upsample + colour kernel")
+        return status
+
+
 LAST_PROFILE: dict = {}        # filled by decode(..., profile=True): seconds per stage of the last call (it synchronises)
 
 
-def decode(files: Sequence[bytes], device=None, profile: bool = False) -> List[torch.Tensor]:
+def decode(files: Sequence[bytes], device=None, profile: bool = False, *, progressive: bool = False) -> List[torch.Tensor]:
     """One [H, W, 3] uint8 RGB device tensor per file: the pixels of `Image.open(BytesIO(f)).convert("RGB")`.
     Files of equal size share one [N, H, W, 3] allocation (the views are its frames), which is what the batched drivers
-    group by.  Raises UnsupportedJpeg for a file outside the reader's class, ImgxfError for a damaged stream."""
+    group by.  Raises UnsupportedJpeg for a file outside the reader's class, ImgxfError for a damaged stream.
+    `progressive=True`: progressive (SOF2) files are read too (imgxf_jpeg_layout_progressive_host +
+    imgxf_jpeg_decode_progressive); the other files of the batch take the baseline reader, results stay in input order."""
     device = torch.device("cuda") if device is None else torch.device(device)
     if device.type != "cuda":
         raise F.ImgxfError(F.ERR_NO_DEVICE, "the JPEG reader runs on the GPU (no CPU fallback)", "jpeg_decode.decode")
@@ -197,49 +297,55 @@ def decode(files: Sequence[bytes], device=None, profile: bool = False) -> List[t
         return []
     t_start = time.perf_counter()
     files = [bytes(f) for f in files]
-    # host half in C (csrc/jpeg_layout.hip: the statement of parse / derive_lut / _segments above for a whole batch)
-    ptrs = (C.c_char_p * n)(*files)
-    sizes = (C.c_size_t * n)(*map(len, files))
-    status_h = (C.c_int32 * n)()
-    n_luts, n_quants, n_segs = C.c_int(0), C.c_int(0), C.c_int(0)
-    scan_bytes, coef_total, plane_total = C.c_size_t(0), C.c_int64(0), C.c_int64(0)
-    F.call("imgxf_jpeg_layout_host", ptrs, sizes, n, None, None, 0, C.addressof(n_luts), None, 0, C.addressof(n_quants), None, 0,
-           C.addressof(scan_bytes), None, None, 0, C.addressof(n_segs), None, None, status_h)
-    _raise_for_status(status_h, n)
-    images = (DecImage * n)()
-    lut_cap, quant_cap, seg_cap, scan_cap = max(1, n_luts.value), max(1, n_quants.value), max(1, n_segs.value), max(64, scan_bytes.value)
-    lut_arr = (DecLut * lut_cap)()
-    quants_h = torch.empty((quant_cap, 64), dtype=torch.int16)
-    scan_host = torch.empty((scan_cap,), dtype=torch.uint8)
-    seg_off_h = torch.zeros((seg_cap,), dtype=torch.int64)
-    seg_len_h = torch.zeros((seg_cap,), dtype=torch.int32)
-    F.call("imgxf_jpeg_layout_host", ptrs, sizes, n, images, lut_arr, lut_cap, C.addressof(n_luts), quants_h.data_ptr(), quant_cap,
-           C.addressof(n_quants), scan_host.data_ptr(), scan_cap, C.addressof(scan_bytes), seg_off_h.data_ptr(), seg_len_h.data_ptr(), seg_cap,
-           C.addressof(n_segs), C.addressof(coef_total), C.addressof(plane_total), status_h)
-    _raise_for_status(status_h, n)
-    coef_pos, plane_pos = coef_total.value, plane_total.value
+    # host half in C (csrc/jpeg_layout.hip: the statement of parse / derive_lut / _segments above for a whole batch); with
+    # `progressive`, one layout for the SOF2 files and one for the others: members[g][j] = input index of file j of group g
+    prog = [i for i in range(n) if is_progressive(files[i])] if progressive else []
+    if prog:
+        base = sorted(set(range(n)) - set(prog))
+        members = [m for m in (base, prog) if m]
+        layouts = [_Layout([files[i] for i in m], m is prog) for m in members]
+    else:
+        members, layouts = [list(range(n))], [_Layout(files, False)]
+
+    def merged_status():
+        st = [0] * n
+        for m, L in zip(members, layouts):
+            for j, i in enumerate(m):
+                st[i] = L.status[j]
+        return st
+
+    _raise_for_status(merged_status(), n)
+    for L in layouts:
+        L.fill()
+    _raise_for_status(merged_status(), n)
+    where = {}                                                   # input index -> (layout, its index there)
+    for m, L in zip(members, layouts):
+        for j, i in enumerate(m):
+            where[i] = (L, j)
     by_size: dict = {}
     for i in range(n):
-        by_size.setdefault((images[i].height, images[i].width), []).append(i)
+        L, j = where[i]
+        by_size.setdefault((L.images[j].height, L.images[j].width), []).append(i)
 
     # one [N, H, W, 3] tensor per size; frames are handed back in file order
     results: List[torch.Tensor] = [None] * n
     out_pos = 0
     spans = []
-    for (h, w), members in by_size.items():
-        for j, i in enumerate(members):
-            images[i].out_off = out_pos + j * h * w * 3
-            images[i].out_pitch = w * 3
-        spans.append((out_pos, len(members), h, w, members))
-        out_pos += (len(members) * h * w * 3 + 15) & ~15
+    for (h, w), group in by_size.items():
+        for k, i in enumerate(group):
+            L, j = where[i]
+            L.images[j].out_off = out_pos + k * h * w * 3
+            L.images[j].out_pitch = w * 3
+        spans.append((out_pos, len(group), h, w, group))
+        out_pos += (len(group) * h * w * 3 + 15) & ~15
     t_host = time.perf_counter()
+    t_mark = [t_host]
 
-    def mark(name, t0):
+    def mark(name):
         if profile:
             torch.cuda.synchronize(device)
-            LAST_PROFILE[name] = time.perf_counter() - t0
-            return time.perf_counter()
-        return t0
+            LAST_PROFILE[name] = LAST_PROFILE.get(name, 0.0) + time.perf_counter() - t_mark[0]
+            t_mark[0] = time.perf_counter()
 
     with torch.cuda.device(device):
         if profile:
@@ -247,31 +353,14 @@ def decode(files: Sequence[bytes], device=None, profile: bool = False) -> List[t
             LAST_PROFILE["host parse + tables"] = t_host - t_start
         stream = torch.cuda.current_stream(device).cuda_stream
         out = torch.empty((out_pos,), dtype=torch.uint8, device=device)
-        scan_d = scan_host[:max(16, scan_bytes.value)].to(device, non_blocking=False)
-        seg_off_d = seg_off_h.to(device)
-        seg_len_d = seg_len_h.to(device)
-        images_d = torch.frombuffer(bytearray(bytes(images)), dtype=torch.uint8).to(device)
-        luts_d = torch.frombuffer(bytearray(bytes(lut_arr)), dtype=torch.uint8).to(device)
-        quants_d = quants_h.to(device)
-        coefs = torch.zeros((coef_pos,), dtype=torch.int16, device=device)
-        planes = torch.empty((plane_pos,), dtype=torch.uint8, device=device)
-        status = torch.zeros((n,), dtype=torch.int32, device=device)
-        t0 = mark("uploads + zero fill", t_host)
-        F.call("imgxf_jpeg_decode_huffman", scan_d.data_ptr(), seg_off_d.data_ptr(), seg_len_d.data_ptr(), images_d.data_ptr(), n,
-               luts_d.data_ptr(), coefs.data_ptr(), status.data_ptr(), stream)
-        t0 = mark("huffman kernel", t0)
-        F.call("imgxf_jpeg_decode_idct", coefs.data_ptr(), images_d.data_ptr(), C.addressof(images), n, quants_d.data_ptr(),
-               planes.data_ptr(), stream)
-        t0 = mark("idct kernel", t0)
-        F.call("imgxf_jpeg_decode_color", planes.data_ptr(), images_d.data_ptr(), C.addressof(images), n, out.data_ptr(), stream)
-        t0 = mark("upsample + colour kernel", t0)
-        bad = torch.nonzero(status).flatten().tolist()
+        statuses = [L.run(device, stream, out, mark) for L in layouts]
+        bad = sorted(m[j] for m, st in zip(members, statuses) for j in torch.nonzero(st).flatten().tolist())
     if bad:
         raise F.ImgxfError(F.ERR_ARG, f"damaged entropy-coded data in file(s) {bad}", "jpeg_decode.decode")
-    for off, cnt, h, w, members in spans:
+    for off, cnt, h, w, group in spans:
         frames = out[off:off + cnt * h * w * 3].view(cnt, h, w, 3).unbind(0)     # (one call: indexing frame by frame costs 3 us each)
-        for j, i in enumerate(members):
-            results[i] = frames[j]
+        for k, i in enumerate(group):
+            results[i] = frames[k]
     return results
 
 

@@ -465,6 +465,57 @@ int imgxf_jpeg_decode_idct(const int16_t* coefs, const imgxf_jpeg_dec_image* ima
 int imgxf_jpeg_decode_color(const uint8_t* planes, const imgxf_jpeg_dec_image* images, const imgxf_jpeg_dec_image* images_host,
                             int n, uint8_t* out, void* stream);
 
+/* ---- the same load step for PROGRESSIVE files (SOF2, Huffman, 8 bit, 1 or 3 components, the samplings above) ---------
+ * Only the way the quantised coefficients reach coefs[] differs from a baseline file (libjpeg-turbo jdcoefct.c
+ * decompress_data over the whole-image buffer): imgxf_jpeg_decode_idct and imgxf_jpeg_decode_color are reused as they
+ * are.  Refusal codes after IMGXF_JPEG_E_TRUNCATED (status[] of imgxf_jpeg_layout_progressive_host): */
+enum { IMGXF_JPEG_E_SCAN_SCRIPT = 12, /* a progression jdphuff.c start_pass_phuff_decoder rejects or warns about (bad Ss / Se /
+                                         Ah / Al, an AC scan of several components or before the component's DC, Ah not the
+                                         previous Al) */
+       IMGXF_JPEG_E_SMOOTHING = 13,   /* jdcoefct.c smoothing_ok would hold: after the last scan a component's coefficient
+                                         1..9 is not fully refined, so libjpeg would smooth blocks (not restated) */
+       IMGXF_JPEG_E_COLORSPACE = 14   /* a 3-component file jdapimin.c default_decompress_parms does not read as YCbCr (no
+                                         JFIF marker, and Adobe transform 0 (or unknown), or component ids 'R','G','B') */ };
+/* One scan of a progressive file (jdphuff.c: Ss..Se is the spectral band in zigzag order, Ah / Al the successive
+ * approximation bits; a DC scan (Ss = 0) may hold several components and is then interleaved in the MCU order of the frame,
+ * dummy blocks included; every other scan holds one component and visits its ceil(dw / 8) x ceil(dh / 8) blocks in raster
+ * order).  Rows of one image are contiguous and in file order. */
+typedef struct imgxf_jpeg_dec_scan {
+    int32_t image;              /* index into images[] */
+    int32_t ncomp;              /* components in the scan */
+    int32_t comp[3];            /* their indices in the image's comp[] (increasing) */
+    int32_t ss, se, ah, al;
+    int32_t dc_tab[3];          /* luts[] of each scan component's DC table (DC first scans), else -1 */
+    int32_t ac_tab;             /* luts[] of the AC table (AC scans), else -1 */
+    int32_t restart_interval;   /* MCUs (blocks, in a one-component scan) per segment: the whole scan without DRI */
+    int32_t seg_first, seg_count; /* this scan's entries of seg_off[] / seg_len[] */
+    int32_t level;              /* 0 when no earlier scan of the image shares a component and overlaps its band, else
+                                   1 + the largest level of those that do: scans of one level can run in any order */
+} imgxf_jpeg_dec_scan;
+/* HOST half for progressive files, beside imgxf_jpeg_layout_host and with its two-call protocol: pass 1 (scan == NULL)
+ * gives bounds on *n_scans, *n_segs, *n_quants, *n_luts, *scan_bytes; pass 2 fills images[n] (the descriptor of
+ * imgxf_jpeg_layout_host: MCU-padded blocks_x / blocks_y, coef_off, plane_off; restart_interval / seg_first / seg_count
+ * are 0, the scans carry them), scans[*n_scans] (the rows of file i contiguous), luts, quants (latched per component at
+ * its first scan: jdinput.c latch_quant_tables) and the unstuffed, RSTn-split, 16-byte aligned segments of every scan
+ * (imgxf_jpeg_unstuff_host).  Every marker from SOI to EOI is walked (jdmarker.c); a file that ends before EOI, or whose
+ * scan ends before its last restart segment, is IMGXF_JPEG_E_TRUNCATED.  Baseline files are IMGXF_JPEG_E_PROCESS here. */
+int imgxf_jpeg_layout_progressive_host(const uint8_t* const* files, const size_t* sizes, int n, imgxf_jpeg_dec_image* images,
+                                       imgxf_jpeg_dec_scan* scans, int scans_cap, int* n_scans,
+                                       imgxf_jpeg_dec_lut* luts, int lut_cap, int* n_luts, uint16_t* quants, int quant_cap,
+                                       int* n_quants, uint8_t* scan, size_t scan_cap, size_t* scan_bytes, int64_t* seg_off,
+                                       int32_t* seg_len, int seg_cap, int* n_segs, int64_t* coef_total, int64_t* plane_total,
+                                       int32_t* status);
+/* Progressive entropy decoding (jdphuff.c decode_mcu_DC_first / _AC_first / _DC_refine / _AC_refine, EOBRUN, the DC
+ * predictors and EOBRUN reset at every RSTn) of n images into coefs[] (ZERO on entry; the zigzag layout
+ * imgxf_jpeg_decode_idct reads).  One workgroup per image; its lanes take the (scan, restart segment) pairs of one
+ * dependency level at a time.  status[i] (device, may be NULL) receives 1 when image i's data held an impossible code or
+ * ran out; its loops then end — damaged data never writes outside the image's blocks.  All pointers but `images_host`
+ * are device pointers; scans_host is the host copy of scans[] (its rows are checked before the launch). */
+int imgxf_jpeg_decode_progressive(const uint8_t* scan, const int64_t* seg_off, const int32_t* seg_len,
+                                  const imgxf_jpeg_dec_scan* scans, const imgxf_jpeg_dec_scan* scans_host, int n_scans,
+                                  const imgxf_jpeg_dec_image* images, int n, const imgxf_jpeg_dec_lut* luts, int16_t* coefs,
+                                  int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

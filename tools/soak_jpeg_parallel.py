@@ -1,5 +1,7 @@
 """Seeded soak of the reader's parallel entropy decoder against Pillow (development aid; the fixed cases live in
-tests/test_gpu_jpeg_decode.py): python tools/soak_jpeg_parallel.py [seeds] [first_seed]"""
+tests/test_gpu_jpeg_decode.py): python tools/soak_jpeg_parallel.py [seeds] [first_seed]
+PROGRESSIVE=1: the same seeded files written progressive and read with decode(..., progressive=True) (fixed cases:
+tests/test_gpu_jpeg_progressive.py)."""
 import io, os, sys
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -8,12 +10,14 @@ from imagetransformations_amd import jpeg_decode
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 s0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-bad = 0
+PROG = os.environ.get("PROGRESSIVE") == "1"
+bad = files = 0
 batch, meta = [], []
 def flush():
-    global bad, batch, meta
+    global bad, batch, meta, files
     if not batch: return
-    got = jpeg_decode.decode(batch, "cuda")
+    files += len(batch)
+    got = jpeg_decode.decode(batch, "cuda", progressive=PROG)
     for g, f, m in zip(got, batch, meta):
         want = np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
         if not np.array_equal(g.cpu().numpy(), want):
@@ -34,6 +38,8 @@ for seed in range(s0, s0 + n):
     if r == 1: kw["restart_marker_rows"] = int(rng.integers(1, 40))
     if r == 2: kw["restart_marker_blocks"] = int(rng.integers(1, 3000))
     gray = rng.integers(0, 6) == 0
+    if PROG:
+        kw["progressive"] = True
     buf = io.BytesIO()
     try:
         (Image.fromarray(img).convert("L") if gray else Image.fromarray(img)).save(buf, "JPEG", **kw)
@@ -42,4 +48,4 @@ for seed in range(s0, s0 + n):
     batch.append(buf.getvalue()); meta.append((seed, h, w, kind, kw, gray))
     if len(batch) == 16: flush()
 flush()
-print("seeds", n, "from", s0, "mismatches", bad)
+print("seeds", n, "from", s0, "files", files, "mismatches", bad)
