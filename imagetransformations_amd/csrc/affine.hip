@@ -1323,7 +1323,7 @@ static int launch_bilinear_tall(const View& s, const View& d, const AffineParams
                      (int64_t)s.h * s.rs < ((int64_t)1 << 32);
     // round 3: wave-private boxes + whole-line stores (affine_wq.inc) when a 32 x 16 block's box fits 28 x 27 pixels
     // and both images are 16-byte aligned with 16-byte multiples as rows
-    if (mf && !knob_set(K_AFFINE_NO_WQ) && !knob_set(K_AFFINE_NO_DMA)) {
+    if (mf && !knob_set(K_AFFINE_NO_DMA)) {
         const int bwq = (int)ceil(fabs(m[0]) * 31 + fabs(m[1]) * 15) + 4, bhq = (int)ceil(fabs(m[3]) * 31 + fabs(m[4]) * 15) + 4;
         const int nchq = (bwq * 3 + 15 + 15) / 16;
         const int ntxq = (d.w + 127) / 128, ntyq = (d.h + 15) / 16;
@@ -1340,43 +1340,21 @@ static int launch_bilinear_tall(const View& s, const View& d, const AffineParams
             dim3 grid((unsigned)(ntxq * ntyq), (unsigned)((d.n + fpbq - 1) / fpbq));
             // vertical strips of tile columns per XCD from 8 columns on: vertically adjacent tiles (whose boxes overlap 2x in y)
             // then sit a few workgroups apart on ONE L2 — at 1080p (15 columns) row-major ranges fetched every source byte twice
-            if (ntxq >= 8 && !knob_set(K_AFFINE_NO_STRIPS)) { Pq.strip_w = (ntxq + 7) / 8; grid.x = (unsigned)(8 * Pq.strip_w * ntyq); }
+            if (ntxq >= 8) { Pq.strip_w = (ntxq + 7) / 8; grid.x = (unsigned)(8 * Pq.strip_w * ntyq); }
             const size_t lds = (size_t)4 * ((size_t)bhq * WQ_PITCH * 4 + 2 * ((size_t)bhq * nchq * 16 + 64)) + 2 * 16 * 384;
-            if (pr) hipLaunchKernelGGL((affine_bilinear_wq_kernel<true>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq, knob_int(K_AFFINE_MF_DBG, 0));
-            else hipLaunchKernelGGL((affine_bilinear_wq_kernel<false>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq, knob_int(K_AFFINE_MF_DBG, 0));
-            return launch_status();
-        }
-    }
-    // (64 x 32 tiles, IMGXF_AFFINE_MF_WIDE: 192-byte rows; measured slower than 32 x 64 — 1.76 vs 1.63 ms — although their
-    // stores alone are faster: kept as an experiment knob)
-    if (dma && knob_set(K_AFFINE_MF_WIDE) && !knob_set(K_AFFINE_MF_NARROW)) {
-        // 64 x 32 tiles when THEIR source box fits the same LDS image: 192-byte output rows (two of three 128-byte lines
-        // written whole by one workgroup) instead of 96-byte ones — see affine_mf.inc, WIDE
-        const int bww = (int)ceil(fabs(m[0]) * 63 + fabs(m[1]) * 31) + 4, bhw = (int)ceil(fabs(m[3]) * 63 + fabs(m[4]) * 31) + 4;
-        const int nchw = (bww * 3 + 15 + 15) / 16;
-        const int ntxw = (d.w + 63) / 64, ntyw = (d.h + 31) / 32;
-        if (bww <= 52 && bhw <= 52 && 52 * nchw <= 768 && (int64_t)ntxw * ntyw < ((int64_t)1 << 28)) {
-            dim3 grid((unsigned)(ntxw * ntyw), (unsigned)((d.n + afpb - 1) / afpb));
-            const int npk = knob_set(K_AFFINE_PK3) ? 3 : 2;
-            AffineParams Ps = Pin;
-            Ps.ntx_magic = (u32)((((uint64_t)1 << 32) + ntxw - 1) / ntxw);
-            if (ntxw == 1) Ps.ntx_magic = 0;
-            if (ntxw >= 16 && !knob_set(K_AFFINE_NO_STRIPS)) { Ps.strip_w = (ntxw + 7) / 8; grid.x = (unsigned)(8 * Ps.strip_w * ntyw); }
-            const size_t lds = (size_t)52 * 56 * 4 + npk * ((size_t)52 * nchw * 16 + 64);
-            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, 56, 13, true, true>), grid, dim3(256), lds, st, s, d, Ps, ntxw, ntyw, fpb, nchw, npk, knob_int(K_AFFINE_MF_DBG, 0));
-            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, 56, 13, true, true>), grid, dim3(256), lds, st, s, d, Ps, ntxw, ntyw, fpb, nchw, npk, knob_int(K_AFFINE_MF_DBG, 0));
+            if (pr) hipLaunchKernelGGL((affine_bilinear_wq_kernel<true>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq);
+            else hipLaunchKernelGGL((affine_bilinear_wq_kernel<false>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq);
             return launch_status();
         }
     }
     if (dma) {
         dim3 grid((unsigned)(ntx * ntyt), (unsigned)((d.n + afpb - 1) / afpb));
         // RGBX pitch 56: fewest bank conflicts of the multiples of 4 (simulated for 30 deg / 1.5x: 4.0 vs 5.8 LDS cycles per gather read at 52)
-        const int npk = knob_set(K_AFFINE_PK3) ? 3 : 2;        // packed-row buffers (A/B knob)
         AffineParams Ps = Pin;
-        if (ntx >= 16 && !knob_set(K_AFFINE_NO_STRIPS)) { Ps.strip_w = (ntx + 7) / 8; grid.x = (unsigned)(8 * Ps.strip_w * ntyt); }
-        const size_t lds = (size_t)52 * 56 * 4 + npk * ((size_t)52 * nch * 16 + 64);
-        if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, 56, 13, true>), grid, dim3(256), lds, st, s, d, Ps, ntx, ntyt, fpb, nch, npk, knob_int(K_AFFINE_MF_DBG, 0));
-        else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, 56, 13, true>), grid, dim3(256), lds, st, s, d, Ps, ntx, ntyt, fpb, nch, npk, knob_int(K_AFFINE_MF_DBG, 0));
+        if (ntx >= 16) { Ps.strip_w = (ntx + 7) / 8; grid.x = (unsigned)(8 * Ps.strip_w * ntyt); }
+        const size_t lds = (size_t)52 * 56 * 4 + 2 * ((size_t)52 * nch * 16 + 64);      // RGBX image + two packed-row buffers
+        if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, 56, 13, true>), grid, dim3(256), lds, st, s, d, Ps, ntx, ntyt, fpb, nch);
+        else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, 56, 13, true>), grid, dim3(256), lds, st, s, d, Ps, ntx, ntyt, fpb, nch);
         return launch_status();
     }
     // the kernel's interior test (bilinear_tile<.., BHT, true>) with the same integers
@@ -1403,11 +1381,11 @@ static int launch_bilinear_tall(const View& s, const View& d, const AffineParams
         const dim3 grid((unsigned)(ntx * ntyt), (unsigned)((d.n + afpb - 1) / afpb));
         const size_t lds = (size_t)2 * PITCH * (bht <= 52 ? 52 : 64) * 4 + 16;     // all 4 * NBR rows are written
         if (bht <= 52) {
-            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, PITCH, 13, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0, 0, 0);
-            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, PITCH, 13, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0, 0, 0);
+            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, PITCH, 13, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
+            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, PITCH, 13, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
         } else {
-            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, PITCH, 16, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0, 0, 0);
-            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, PITCH, 16, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0, 0, 0);
+            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, PITCH, 16, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
+            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, PITCH, 16, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
         }
         IMGXF_CHECK(launch_status());
     } else if (list.n < ntx * ntyt) {                // at least one interior tile
@@ -1485,7 +1463,7 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
                 const bool aligned = ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0 &&
                                      (d.w * 3) % 16 == 0 && (s.w * 3) % 16 == 0 && s.w * 3 >= 16 &&
                                      (int64_t)s.h * s.rs < ((int64_t)1 << 32);
-                if (aligned && !no_dma && !knob_set(K_AFFINE_NO_WQ) && kwq <= NQ_KW && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
+                if (aligned && !no_dma && kwq <= NQ_KW && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
                     AffineParams Pq = P;
                     Pq.strip_w = 0;
                     unsigned gx = (unsigned)(ntxq * ntyq);
@@ -1515,8 +1493,8 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
                 if (bw64 <= 64 && bh64 <= 80 && !no_tall) {
                     const int nty64 = (d.h + 63) / 64;
                     unsigned gx = (unsigned)(ntx * nty64);
-                    // vertical strips per XCD (3 % at 4K: 0.86 -> 0.83 ms per 64 frames); IMGXF_AFFINE_NO_STRIPS = row-major ranges
-                    if (ntx >= 16 && !knob_set(K_AFFINE_NO_STRIPS)) { P.strip_w = (ntx + 7) / 8; gx = (unsigned)(8 * P.strip_w * nty64); }
+                    // vertical strips per XCD (3 % at 4K: 0.86 -> 0.83 ms per 64 frames, against row-major ranges)
+                    if (ntx >= 16) { P.strip_w = (ntx + 7) / 8; gx = (unsigned)(8 * P.strip_w * nty64); }
                     hipLaunchKernelGGL((affine_nearest_dma_kernel<64, 13>), dim3(gx, (unsigned)d.n), dim3(256),
                                        (size_t)13 * 16 * bh64 + 32, st, s, d, P, ntx, nty64);
                 } else {
@@ -1553,9 +1531,8 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
         P.y00 = (int64_t)floor(y0d * 1099511627776.0);
     }
     if (filter == IMGXF_FILTER_BILINEAR && (src->c == 1 || src->c == 3) && src->w >= 3 && src->h >= 2 && fixed_ok) {
-        const int tile_env = knob_int(K_AFFINE_TILE, 0);  // tuning knob
         const bool no_lds = knob_set(K_AFFINE_NO_LDS);
-        if (src->c == 3 && !no_lds && tile_env == 0 &&
+        if (src->c == 3 && !no_lds &&
             ((((uintptr_t)src->data) | (uintptr_t)src->row_stride | (uintptr_t)src->frame_stride) & 3) == 0) {
             // source bounding box of a 32x32 output tile (translation-invariant up to rounding)
             const int bw = (int)ceil(fabs(m[0]) * 31 + fabs(m[1]) * 31) + 4;
@@ -1605,7 +1582,6 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
         return launch_status();                                                                    \
     } while (0)
         if (src->c == 3) {
-            if (tile_env == 1) { if (pr) IMGXF_BIL(3, true, 64, 1); else IMGXF_BIL(3, false, 64, 1); }
             if (pr) IMGXF_BIL(3, true, 8, 2); else IMGXF_BIL(3, false, 8, 2);
         } else {
             if (pr) IMGXF_BIL(1, true, 8, 2); else IMGXF_BIL(1, false, 8, 2);

@@ -45,17 +45,12 @@ __device__ __forceinline__ void glds16_hidden(const u8* base, u32 voff, u32 lds_
 // by LDS-DMA (1 KiB per wave-level load, ~10x fewer L1 accesses) into a double-buffered packed
 // image, and one pass expands packed[f] -> the single RGBX tile (ds_read, v_alignbyte, ds_write_b128)
 // between two barriers while the DMA of frame f+1 is already in flight.
-// WIDE (DMA only): 64 x 32 tiles instead of 32 x 64.  A tile row is then 192 bytes instead of 96: two of three 128-byte
-// lines are written whole by one workgroup (96-byte segments never are), which is what the store path wants — a
-// stores-only build of this kernel runs 0.82 ms per 128 4K frames with 192-byte rows against 1.24 ms with 96-byte rows
-// (0.64 ms with whole lines; profiles/r03_experiments/affine_mf_ablation.txt) — and for a 30 deg / 1.5x map the
-// wide tile's source box is smaller as well (51 x 43 instead of 52 x 52 pixels).
-template <bool PRECISE, int PITCH, int MF_NBR, bool DMA, bool WIDE = false>
-__global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb, int nch, int npk, int dbg) {
-    constexpr int C = 3, BW = WIDE ? 64 : 32, BH = WIDE ? 32 : MF_TILE_H;
-    constexpr int XG = BW / 4, RPH = 64 / XG;       // 4-pixel groups per tile row; tile rows per wave-half (8 / 4)
-    constexpr int CPR = BW * C / 16;                // 16-byte chunks per tile row (6 / 12)
-    static_assert(!WIDE || DMA, "wide tiles use the DMA staging");
+// (64 x 32 tiles, with 192-byte tile rows, were measured slower and removed: DESIGN §3.2c.)
+template <bool PRECISE, int PITCH, int MF_NBR, bool DMA>
+__global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb, int nch) {
+    constexpr int C = 3, BW = 32, BH = MF_TILE_H;
+    constexpr int XG = BW / 4, RPH = 64 / XG;       // 4-pixel groups per tile row (8); tile rows per wave-half (8)
+    constexpr int CPR = BW * C / 16;                // 16-byte chunks per tile row (6)
     constexpr int P2 = DMA ? PITCH : 2 * PITCH;      // dwords between two rows of one RGBX buffer (no DMA: buffers interleaved by row)
     constexpr int ROWS = 4 * MF_NBR;
     constexpr float GUARDP = 4.0f / 32768.0f;        // 1.2207e-4: four ulps of [256, 512), so that 256 + GUARDP is exact
@@ -67,7 +62,7 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
     const int orig = blockIdx.x, xcd = orig & 7, q = nblocks >> 3, r = nblocks & 7;
     const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
     int tyb = P.ntx_magic ? (int)__umulhi((u32)logical, P.ntx_magic) : logical, txb = logical - tyb * ntx;
-    if (P.strip_w) {                 // vertical strips per XCD (A/B knob, see affine_nearest_dma_kernel)
+    if (P.strip_w) {                 // vertical strips per XCD (see affine_nearest_dma_kernel)
         const int l = orig >> 3;
         tyb = l / P.strip_w; txb = xcd * P.strip_w + (l - tyb * P.strip_w);
         if (txb >= ntx || tyb >= nty) return;
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
         }
     }
     if (!DMA || interior) okm = 0xffu;
-    // ---- output chunks: lane t < 48 re-reads chunk t % CPR of tile row t / CPR of the wave-half's RPH rows (96 B = 6 x 16 B per row; wide: 192 B = 12 x 16 B)
+    // ---- output chunks: lane t < 48 re-reads chunk t % CPR of tile row t / CPR of the wave-half's RPH rows (96 B = 6 x 16 B per row)
     const int sg = lane / CPR, ck = lane - sg * CPR;
     const bool storer = lane < 48;
     const bool dst16 = ((((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs | (uintptr_t)(txb * BW * C)) & 15) == 0 &&
@@ -290,16 +285,6 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
         for (int half = 0; half < 2; ++half)
             if (storer && (interior || tyb * BH + (wave * 2 + half) * RPH + sg < d.h)) {
                 const uint4 o4 = *(const uint4*)(wst + half * 192 + sg * (CPR * 4) + ck * 4);
-                if (dbg & (16 | 32 | 64)) {
-                    // timing-only store patterns (same bytes per frame, WRONG places): what would another tile shape's stores cost?
-                    const int t = tyb * ntx + txb, wh = wave * 2 + half;
-                    int64_t off;
-                    if (dbg & 16) off = (int64_t)t * 6144 + wh * 768 + lane * 16;                       // 768 contiguous bytes per wave-half
-                    else if (dbg & 32) off = (int64_t)((t / 60) * 32 + wh * 4 + lane / 12) * d.rs + (t % 60) * 192 + (lane % 12) * 16;   // 64 x 32 tiles: 192-byte rows
-                    else off = (int64_t)((t / 30) * 16 + wh * 2 + lane / 24) * d.rs + (t % 30) * 384 + (lane % 24) * 16;             // 128 x 16 tiles: 384-byte rows
-                    if (off + 16 <= (int64_t)d.h * d.rs) *(uint4*)(dframe + off) = o4;
-                    continue;
-                }
                 *(uint4*)(dframe + doff[half]) = o4;
             }
     };
@@ -363,7 +348,7 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
             }
         }
         need &= okm & ~fillm;                            // (fill / non-existent pixels trip the value guard with x = GUARD - 0.5)
-        if (need && !(dbg & 1)) slow_pixels(need, f, sb, od);
+        if (need) slow_pixels(need, f, sb, od);
         if (DMA && fillm && ((u32)P.fill[0] | (u32)P.fill[1] | (u32)P.fill[2])) {
             const u32 val = (u32)P.fill[0] | ((u32)P.fill[1] << 8) | ((u32)P.fill[2] << 16);
 #pragma unroll 1
@@ -389,8 +374,8 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
     };
 
     if constexpr (DMA) {
-        // ---- frame loop, DMA staging, three packed buffers, the DMA runs two frames ahead:
-        //   [wait: DMA f landed] barrier [issue DMA f+2] expand f, barrier, gather f.
+        // ---- frame loop, DMA staging, two packed buffers, the DMA runs two frames ahead:
+        //   [wait: DMA f landed] barrier, expand f, barrier [issue DMA f+2], gather f.
         // The wait is counted: the only LOADS this wave has issued after DMA f are the kw instructions
         // of DMA f+1 (loads complete in order among themselves), so at most kw outstanding operations
         // means DMA f is done.  Stores count too, whatever their order against loads — which is why frame
@@ -401,10 +386,6 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
         for (int i = 0; i < 3; ++i) kw += ((wave * 3 + i) * 64 < ROWS * nch) ? 1 : 0;
         dma_issue(f_begin, 0);
         if (f_begin + 1 < f_end) dma_issue(f_begin + 1, 1);
-        if (dbg & 128) {            // experiment: de-synchronise co-resident workgroups by a start delay of 0 .. 3/4 iteration
-            const int ph = (orig >> 3) & 3;
-            for (int i = 0; i < ph; ++i) __builtin_amdgcn_s_sleep(24);      // ~1500 cycles each
-        }
         int pb = 0;
 #pragma unroll 1
         for (int f = f_begin; f < f_end; ++f) {
@@ -413,18 +394,15 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
             else if (kw == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
             __builtin_amdgcn_s_barrier();                           // all chunks of f landed; every wave is done gathering f-1
-            if (f > f_begin && !(dbg & 8)) flush_stores(f - 1);     // a frame old by the next counted wait
-            // npk = 3 packed buffers: frame f+2 goes into the one expand(f-1) read last, before the expansion;
-            // npk = 2 (default): into the one expand(f) has just read, after its barrier — the same two frames
-            // of lead, 7.5 KB less LDS (a fourth workgroup per CU for the 30 deg / 1.5x geometry)
-            const int pb2 = pb >= 1 ? pb - 1 : 2;                   // (pb + 2) % 3
-            if (npk == 3 && f + 2 < f_end && !(dbg & 2)) dma_issue(f + 2, pb2);
-            if (!(dbg & 2) || f == f_begin) expand(pb);
+            if (f > f_begin) flush_stores(f - 1);                   // a frame old by the next counted wait
+            expand(pb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if (npk == 2 && f + 2 < f_end && !(dbg & 2)) dma_issue(f + 2, pb);
-            if (!(dbg & 4)) gather_frame(f, 0);
-            pb = pb + 1 == npk ? 0 : pb + 1;
+            // frame f+2 goes into the packed buffer expand(f) has just read, after its barrier: two frames of lead
+            // from two buffers (a third one cost 7.5 KB of LDS, a fourth workgroup per CU at 30 deg / 1.5x)
+            if (f + 2 < f_end) dma_issue(f + 2, pb);
+            gather_frame(f, 0);
+            pb ^= 1;
         }
         flush_stores(f_end - 1);
         return;

@@ -35,7 +35,7 @@ constexpr int WQ_MAXCH = 192;         // 16-byte chunks a wave moves per frame (
 
 template <bool PRECISE>
 __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb,
-                                                                   int nch, int rows, int dbg) {
+                                                                   int nch, int rows) {
     constexpr int C = 3, SW = 32, BH = 16, BW = 4 * SW, PITCH = WQ_PITCH, NG = PITCH / 4;
     constexpr float GUARDP = 4.0f / 32768.0f;
     constexpr u32 GTOP = 8u << 17;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
             }
         }
         need &= okm & ~fillm;
-        if (need && !(dbg & 1)) slow_pixels(need, f, od);
+        if (need) slow_pixels(need, f, od);
         if (fillm && ((u32)P.fill[0] | (u32)P.fill[1] | (u32)P.fill[2])) {
             const u32 val = (u32)P.fill[0] | ((u32)P.fill[1] << 8) | ((u32)P.fill[2] << 16);
 #pragma unroll 1
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
         for (int pass = 0; pass < 2; ++pass) {
             const int ch = pass * 64 + lane;                        // 0 .. 95
             const int r = wave * 4 + ch / 24, ck = ch - (ch / 24) * 24;
-            if (ch < 96 && sy0 + r < d.h && txb * 24 + ck < rb16 && !(dbg & 8)) {
+            if (ch < 96 && sy0 + r < d.h && txb * 24 + ck < rb16) {
                 const uint4 o4 = *(const uint4*)(slot + r * 96 + ck * 4);
                 *(uint4*)(dframe + (int64_t)(sy0 + r) * d.rs + (int64_t)txb * (BW * C) + ck * 16) = o4;
             }
@@ -314,10 +314,10 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
         }
         if (f > f_begin) flush(f - 1, slots + ((f - 1 - f_begin) & 1) * (16 * 96));     // a whole iteration old at the next wait
         if (wave_in) {
-            if (!(dbg & 2) || f == f_begin) expand(pb);
+            expand(pb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the expansion has read the packed rows: their buffer is free
-            if (f + 2 < f_end && !(dbg & 2)) dma_issue(f + 2, pb);
-            if (!(dbg & 4)) gather_frame(f, slot);
+            if (f + 2 < f_end) dma_issue(f + 2, pb);
+            gather_frame(f, slot);
             pb ^= 1;
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");

@@ -505,43 +505,39 @@ static int launch_v_fast(const imgxf_lanczos_plan* p, const View& s, const View&
     return launch_status();
 }
 
+// waves per workgroup of the fused kernel (8 measured a wash at 4K: DESIGN §3.6)
+constexpr int RS_MF_WAVES = 4;
+
 // the fused kernel reads and writes dwords at 4-byte aligned addresses and keeps row offsets in 32 bits
 static bool rs_mf_ok(const imgxf_lanczos_plan* p, const View& s, const View& d) {
     if (!p->mf_nkh) return false;
     if (((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 3) != 0) return false;
-    // the workgroup count of the launch (the widest setting of IMGXF_RESAMPLE_MFMA_WAVES gives the most) must fit
-    // the grid: decided HERE so that the workspace query and the run agree and an oversized call takes the
-    // two-pass path with its intermediate
-    const int64_t total = (int64_t)((p->mf_ng + 3) / 4) * p->mf_nchunks * s.n;
+    // the workgroup count of the launch (RS_MF_WAVES column groups per workgroup) must fit the grid: decided HERE so
+    // that the workspace query and the run agree and an oversized call takes the two-pass path with its intermediate
+    // 
+    const int64_t total = (int64_t)((p->mf_ng + RS_MF_WAVES - 1) / RS_MF_WAVES) * p->mf_nchunks * s.n;
     if (total > (int64_t(1) << 30)) return false;
     return s.rs > 0 && s.rs < (1 << 24) && p->rh < (1 << 24) && (int64_t)(p->ry0 + p->rh) * s.rs < (int64_t(1) << 31);
 }
 
-template <int NW>
-static void launch_rs_mf_t(int nkh, dim3 grid, hipStream_t st, const View& s, const View& d, const RsMfArgs& a) {
-    const dim3 block(NW * 64);
-    const size_t lds = rsmf_lds_bytes(NW);
-    switch (nkh) {
-        case 1: hipLaunchKernelGGL((resample_mfma_kernel<1, NW>), grid, block, lds, st, s, d, a); break;
-        case 2: hipLaunchKernelGGL((resample_mfma_kernel<2, NW>), grid, block, lds, st, s, d, a); break;
-        default: hipLaunchKernelGGL((resample_mfma_kernel<3, NW>), grid, block, lds, st, s, d, a); break;
-    }
-}
-
 static int launch_rs_mf(const imgxf_lanczos_plan* p, const View& s, const View& d, hipStream_t st) {
-    const int nw_env = knob_int(K_RESAMPLE_MFMA_WAVES, 4);         // waves per workgroup, 4 or 8 (A/B knob; a wash at 4K)
-    const int nw = nw_env == 8 ? 8 : 4;
+    constexpr int NW = RS_MF_WAVES;
     RsMfArgs a;
     a.ws = p->d_mf_ws; a.wh = (const rs_v4i*)p->d_mf_wh; a.kcol = p->d_mf_kcol; a.sched = p->d_mf_sched;
     a.chunks = p->d_mf_chunks; a.wv = (const u8*)p->d_mf_wv; a.krow = p->d_mf_krow;
-    a.ng = p->mf_ng; a.nsets = (p->mf_ng + nw - 1) / nw; a.nchunks = p->mf_nchunks;
+    a.ng = p->mf_ng; a.nsets = (p->mf_ng + NW - 1) / NW; a.nchunks = p->mf_nchunks;
     a.ry0 = p->ry0; a.rh = p->rh; a.out_h = d.h; a.out_rb = (int)d.rowbytes();
     const int64_t total = (int64_t)a.nsets * a.nchunks * s.n;
     if (total > (int64_t(1) << 30)) return IMGXF_ERR_UNSUPPORTED;
     a.total = (unsigned)total;
     const dim3 grid((unsigned)((total + 7) & ~int64_t(7)));
-    if (nw == 8) launch_rs_mf_t<8>(p->mf_nkh, grid, st, s, d, a);
-    else launch_rs_mf_t<4>(p->mf_nkh, grid, st, s, d, a);
+    const dim3 block(NW * 64);
+    const size_t lds = rsmf_lds_bytes(NW);
+    switch (p->mf_nkh) {
+        case 1: hipLaunchKernelGGL((resample_mfma_kernel<1, NW>), grid, block, lds, st, s, d, a); break;
+        case 2: hipLaunchKernelGGL((resample_mfma_kernel<2, NW>), grid, block, lds, st, s, d, a); break;
+        default: hipLaunchKernelGGL((resample_mfma_kernel<3, NW>), grid, block, lds, st, s, d, a); break;
+    }
     return launch_status();
 }
 

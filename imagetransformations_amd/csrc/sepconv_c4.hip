@@ -6,11 +6,10 @@
 namespace imgxf {
 int sepconv_c4(int R, const View& s, const View& d, const View& df, const Taps& taps,
                int border, hipStream_t st) {
-    const int rpw_env = knob_int(K_MARCH_RPW, 0);
     const bool no_march = knob_set(K_NO_MARCH);
     if (!no_march && march_eligible(s, d, df, 4, R, border)) {
         switch (R) {
-#define IMGXF_M(r) case r: return launch_sepconv_march<4, r>(s, d, df, taps, st, rpw_env);
+#define IMGXF_M(r) case r: return launch_sepconv_march<4, r>(s, d, df, taps, st);
             IMGXF_M(1) IMGXF_M(2) IMGXF_M(3)
 #undef IMGXF_M
             default: break;

@@ -56,12 +56,12 @@ constexpr int march_wave_lds(int J) { return 16 + J * MARCH_SLOT; }   // 16 B pa
 // is 11.25 strips: alone it costs 12 waves per row chunk, 6 % of them idle lanes that still issue
 // every VALU instruction; four frames' rows are exactly 45 strips (1080p: eight frames' rows).
 // Frame seams inside a strip are ordinary image borders of the two lanes next to them.
-template <int C, int R, bool FIXED = false, bool MIXED = true, int UU = 0>
+template <int C, int R, bool FIXED = false>
 __global__ __launch_bounds__(256) void sepconv_march_kernel(View src, View dst, View dstf, Taps taps,
                                                             int rows_per_wave, int nchunks, int gx,
-                                                            int G, int bpr, int wg_a, int groups_a, int rpw_b, int nchunks_b) {
+                                                            int G, int bpr) {
     constexpr int K = 2 * R + 1;
-    constexpr int U = UU ? UU : march_unroll(K), J = K * U;   // J rows in flight; slot == position in the unrolled body
+    constexpr int U = march_unroll(K), J = K * U;   // J rows in flight; slot == position in the unrolled body
     constexpr int HB = R * C;              // halo bytes per side (<= 16)
     constexpr int ND = (HB + 3) / 4;       // halo dwords per side
     constexpr int NF = 16 + 2 * HB;
@@ -74,18 +74,12 @@ __global__ __launch_bounds__(256) void sepconv_march_kernel(View src, View dst, 
     // -> logical = a contiguous range per XCD, decoded x-fastest.  The x-adjacent workgroups of
     // a row chunk then share one L2 and start back to back, so the 16-byte seam blocks each
     // fetches from its neighbour's strip are L2 hits instead of a second HBM fetch per XCD.
-    // Two regions: the first wg_a workgroups cut their frame groups into tall chunks (few re-read halo
-    // rows), the last ones — the frame groups behind them — into short chunks, so that the launch
-    // drains evenly: with ~9 workgroups per resident slot a uniform grid leaves half the chip idle
-    // during its last workgroup (measured: time follows halo overhead + half a workgroup's share).
-    const bool reg_b = (int)blockIdx.x >= wg_a;
-    if (reg_b) { rows_per_wave = rpw_b; nchunks = nchunks_b; }
-    const int nwg = reg_b ? (int)gridDim.x - wg_a : wg_a, orig = reg_b ? (int)blockIdx.x - wg_a : (int)blockIdx.x;
+    const int nwg = (int)gridDim.x, orig = (int)blockIdx.x;
     const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
     const int logical = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
     const int bx = logical % gx;
     const int chunk = (logical / gx) % nchunks;
-    const int f = ((reg_b ? groups_a : 0) + logical / (gx * nchunks)) * G;      // first frame of the group
+    const int f = logical / (gx * nchunks) * G;      // first frame of the group
     const int total = G * bpr;             // 16-byte blocks of the super-row (bpr > 64: host checks)
     const int strip = bx * (blockDim.x >> 6) + wave;   // a workgroup = 2..4 adjacent strips of every row
     if (strip * 64 >= total) return;           // wave-uniform
@@ -224,42 +218,28 @@ __global__ __launch_bounds__(256) void sepconv_march_kernel(View src, View dst, 
                 const int wb = 4 * ND - HB + j;
                 fl[j] = (float)((win[wb >> 2] >> (8 * (wb & 3))) & 0xffu);
             }
-            if constexpr (MIXED && (NF % 2 == 0)) {
-                // taps at an even byte offset read an even-aligned pair of the window: one
-                // v_pk_fma_f32 for both outputs; taps at an odd offset stay scalar v_fmac_f32
-                // (their pair would straddle two register pairs)
-                f32x2 fe[NF / 2];
+            // taps at an even byte offset read an even-aligned pair of the window: one
+            // v_pk_fma_f32 for both outputs; taps at an odd offset stay scalar v_fmac_f32
+            // (their pair would straddle two register pairs)
+            f32x2 fe[NF / 2];
 #pragma unroll
-                for (int m2 = 0; m2 < NF / 2; ++m2) fe[m2] = f32x2{fl[2 * m2], fl[2 * m2 + 1]};
-#pragma unroll
-                for (int op = 0; op < 8; ++op) {
-                    f32x2 acc = {0.0f, 0.0f};
-#pragma unroll
-                    for (int i = 0; i < K; ++i)
-                        if ((i * C) % 2 == 0)
-                            acc = __builtin_elementwise_fma(f32x2{taps.x[i], taps.x[i]}, fe[op + (i * C) / 2], acc);
-                    float a0 = acc.x, a1 = acc.y;
-#pragma unroll
-                    for (int i = 0; i < K; ++i)
-                        if ((i * C) % 2 != 0) {
-                            a0 = fmaf(taps.x[i], fe[op + (i * C - 1) / 2].y, a0);
-                            a1 = fmaf(taps.x[i], fe[op + (i * C + 1) / 2].x, a1);
-                        }
-                    asm volatile("" : "+v"(a0), "+v"(a1));   // keep them scalar: no re-vectorisation
-                    ring[s][op] = f32x2{a0, a1};
-                }
-            } else {
+            for (int m2 = 0; m2 < NF / 2; ++m2) fe[m2] = f32x2{fl[2 * m2], fl[2 * m2 + 1]};
 #pragma unroll
             for (int op = 0; op < 8; ++op) {
-                float a0 = 0.0f, a1 = 0.0f;
+                f32x2 acc = {0.0f, 0.0f};
 #pragma unroll
-                for (int i = 0; i < K; ++i) {
-                    a0 = fmaf(taps.x[i], fl[2 * op + i * C], a0);
-                    a1 = fmaf(taps.x[i], fl[2 * op + 1 + i * C], a1);
-                }
-                asm volatile("" : "+v"(a0), "+v"(a1));       // keep them scalar: no re-vectorisation
+                for (int i = 0; i < K; ++i)
+                    if ((i * C) % 2 == 0)
+                        acc = __builtin_elementwise_fma(f32x2{taps.x[i], taps.x[i]}, fe[op + (i * C) / 2], acc);
+                float a0 = acc.x, a1 = acc.y;
+#pragma unroll
+                for (int i = 0; i < K; ++i)
+                    if ((i * C) % 2 != 0) {
+                        a0 = fmaf(taps.x[i], fe[op + (i * C - 1) / 2].y, a0);
+                        a1 = fmaf(taps.x[i], fe[op + (i * C + 1) / 2].x, a1);
+                    }
+                asm volatile("" : "+v"(a0), "+v"(a1));   // keep them scalar: no re-vectorisation
                 ring[s][op] = f32x2{a0, a1};
-            }
             }
 
             // ---- vertical taps once the ring holds 2R+1 rows
@@ -340,11 +320,9 @@ inline int march_rows_per_wave(const View& s, int G) {
 }
 
 template <int C, int R, bool FIXED = false>
-inline int launch_sepconv_march(const View& s0, const View& d0, const View& df0, const Taps& taps,
-                                hipStream_t st, int rpw_override) {
+inline int launch_sepconv_march(const View& s0, const View& d0, const View& df0, const Taps& taps, hipStream_t st) {
     const int g_env = knob_int(K_MARCH_GROUP, 0);   // tuning knobs
     const int spb_env = knob_int(K_MARCH_SPB, 0);
-    const bool no_mixed = knob_set(K_MARCH_NO_MIXED);
     const int bpr = (int)(s0.rowbytes() / 16);
     // whole groups of G frames first, then the remainder with the best group size that still fits
     for (int f0 = 0; f0 < s0.n;) {
@@ -356,7 +334,7 @@ inline int launch_sepconv_march(const View& s0, const View& d0, const View& df0,
         if (df.p) df.p += (int64_t)f0 * df0.fs;
         const int groups = left / G;
         s.n = d.n = df.n = groups * G;
-        const int rpw = rpw_override > 0 ? rpw_override : march_rows_per_wave(s, G);
+        const int rpw = march_rows_per_wave(s, G);
         const int nchunks = (s.h + rpw - 1) / rpw;
         // strips per workgroup: single-wave workgroups (finest dispatch granularity; measured 1 % faster
         // than 2..4 adjacent strips per workgroup on every box)
@@ -364,35 +342,11 @@ inline int launch_sepconv_march(const View& s0, const View& d0, const View& df0,
         int spb = 1;
         if (spb_env >= 1 && spb_env <= 4) spb = spb_env;
         const int gx = (nstrips + spb - 1) / spb;
-        // region B (off by default; IMGXF_MARCH_TAIL="percent,rows"): the last frame groups in short chunks so
-        // that the launch drains evenly.  Measured per box: -3 % with "25,48" on one, +2.7 % on another
-        // (where plain 64-row chunks were the fastest setting) — the ranking of every launch shape within
-        // +-3 % changes from box to box (DESIGN §3.1), so the uniform grid stays the default
-        int tail_pct = 0, rpw_b = 0;
-        if (const char* te = knob_str(K_MARCH_TAIL)) sscanf(te, "%d,%d", &tail_pct, &rpw_b);
-        int groups_b = (groups >= 8 && tail_pct > 0 && rpw_b > 0 && rpw_b < rpw) ? std::max(1, (int)((int64_t)groups * tail_pct / 100)) : 0;
-        const int groups_a = groups - groups_b;
-        const int nchunks_b = groups_b ? (s.h + rpw_b - 1) / rpw_b : 1;
-        const int rpw_b2 = groups_b ? (s.h + nchunks_b - 1) / nchunks_b : rpw;      // balanced
-        const int64_t wg_a = (int64_t)gx * nchunks * groups_a;
-        const int64_t nwg = wg_a + (int64_t)gx * nchunks_b * groups_b;
+        const int64_t nwg = (int64_t)gx * nchunks * groups;
         if (nwg > 0x7fffffff) return IMGXF_ERR_SHAPE;
-        size_t lds = spb * march_wave_lds(march_rows_in_flight(R));
-#define IMGXF_MARCH_ARGS s, d, df, taps, rpw, nchunks, gx, G, bpr, (int)wg_a, groups_a, rpw_b2, nchunks_b
-        if constexpr (C == 3 && R == 2 && !FIXED) {
-            if (knob_set(K_MARCH_U2)) {          // development knob: 10 rows in flight instead of 5
-                lds = spb * march_wave_lds(2 * (2 * R + 1));
-                hipLaunchKernelGGL((sepconv_march_kernel<C, R, FIXED, true, 2>), dim3((unsigned)nwg), dim3(64 * spb), lds, st, IMGXF_MARCH_ARGS);
-                IMGXF_CHECK(launch_status());
-                f0 += groups * G;
-                continue;
-            }
-        }
-        if (no_mixed)
-            hipLaunchKernelGGL((sepconv_march_kernel<C, R, FIXED, false>), dim3((unsigned)nwg), dim3(64 * spb), lds, st, IMGXF_MARCH_ARGS);
-        else
-            hipLaunchKernelGGL((sepconv_march_kernel<C, R, FIXED, true>), dim3((unsigned)nwg), dim3(64 * spb), lds, st, IMGXF_MARCH_ARGS);
-#undef IMGXF_MARCH_ARGS
+        const size_t lds = spb * march_wave_lds(march_rows_in_flight(R));
+        hipLaunchKernelGGL((sepconv_march_kernel<C, R, FIXED>), dim3((unsigned)nwg), dim3(64 * spb), lds, st,
+                           s, d, df, taps, rpw, nchunks, gx, G, bpr);
         IMGXF_CHECK(launch_status());
         f0 += groups * G;
     }

@@ -9,9 +9,8 @@
 //   H pass   D1[32 rows][32 cols] = X[32 rows][K bytes] . Th[K][32]       Th[k][n] = wx[(k - n - off) / 3]
 //   V pass   Y [32 rows][32 cols] = Tv[32][64 rows]     . [D1(prev); D1(cur)]
 //
-// * X: the image bytes, staged by LDS-DMA as packed rows (pitch 272 B), are EXACT f16 values: a byte b is
-//   fed as the f16 bit pattern 0x00bb << 2 = b * 2^-22 (an f16 denormal, which the matrix pipe takes
-//   un-flushed — probed, tools/probe_mfma.hip): one v_perm_b32 and one shift per two bytes, no conversion.
+// * X: the image bytes are EXACT f16 values: a byte b is fed as the f16 bit pattern 0x00bb << 2 = b * 2^-22 (an f16
+//   denormal, which the matrix pipe takes un-flushed — probed, tools/probe_mfma.hip): one v_perm_b32 and one shift per two bytes, no conversion.
 // * Weights are split at a common scale, w 2^15 = hi + lo (hi = f16(w 2^15), lo = f16(w 2^15 - hi), both normal f16
 //   numbers), so the two products of a k-step extend ONE accumulation chain; D1 = acc 2^9.  Relative weight error 2^-22.
 // * D1 stays in the accumulator layout (column on the lane, 16 rows in registers), which IS the B
@@ -23,10 +22,18 @@
 //   denormal operand counts as exponent -14 whatever its leading zeros: at b * 2^-24 a constant image of value 1
 //   came out 1e-5 low (tools/probe_mfma_sum.hip; found by tests/test_gpu_soak.py).  Hence b * 2^-22 (two bits
 //   up inside the denormal field): < 4e-6 of the result for every pixel value, inside the 1e-5 contract.
-// * A workgroup = 4 waves = a 128-byte column tile; it marches down a chunk of rows in 32-row blocks:
-//   DMA block j+1 | H product of block j | V product of output rows [32 j - 16, 32 j + 16) from D1(j-1), D1(j)
-//   | bytes leave through an LDS tile as dense 16-byte stores.  REFLECT_101: rows by reflected DMA row
-//   indices, columns by rewriting the halo bytes of the two edge tiles in LDS.
+// * A WAVE owns 32 byte columns outright; a workgroup = 4 waves = a 128-byte column set x one chunk of 32-row blocks:
+//   - no LDS staging, no DMA bookkeeping, no per-block landing barrier: the rows of the 128-byte window
+//     [32 g - 48, 32 g + 80) are plain 16-byte global loads (lane = row, the block after next in flight
+//     in registers), and the loop body is straight-line, so hipcc counts the waits itself;
+//   - the H operands (8 k-steps x hi / lo) live in registers, built once per wave from a closed form that
+//     folds REFLECT_101 into the band matrix: source pixel xs also stands for the virtual pixels -xs and
+//     2 (W-1) - xs, so weight(xs, xo) = tap(xs - xo) + tap(-xs - xo) + tap(2 (W-1) - xs - xo).  Edge groups
+//     clamp their window into the row and need no byte rewriting; rows are reflected in the load address;
+//   - the V product is the transposed one (row on the lane), bytes leave through a double-buffered LDS
+//     tile: ONE barrier per 32-row block, the store of block j is issued during block j+1.
+//   (An earlier LDS-DMA-staged structure and a software-pipelined one were measured slower and removed:
+//   DESIGN §3.3b, profiles/r02_experiments/ab_mfma*.txt, profiles/r03_experiments/mfma3_pipelined.txt.)
 #pragma once
 #include "sepconv_tile.inc"
 #include <stdlib.h>
@@ -40,257 +47,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int MF_PITCH = 272;                  // bytes per staged row: 17 chunks (224 used), 2-way conflicts at most
-constexpr int MF_ROWS = 32;
-constexpr int MF_LEFT = 48;                    // window start = tile origin - 48 bytes (>= 3 * 15, 16-byte aligned)
-constexpr int MF_IN_BYTES = MF_ROWS * MF_PITCH;         // 8704
-constexpr int MF_OUT_PITCH = 144;              // 128 output bytes + pad
-constexpr int MF_TILES = 2 * MF_IN_BYTES + MF_ROWS * MF_OUT_PITCH;      // two input buffers + the out tile
-constexpr int mf_lds_bytes(int nsh) { return MF_TILES + (nsh + 4) * 2 * 64 * 16; }   // + operand tables [step][hi/lo][lane][8 x f16]
-
-__device__ __forceinline__ void mfma_glds16(const u8* base, u32 voff, u32 lds_dst) {
-    u32 keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(base) : "memory");
-}
-
-template <int R, bool HREG = true>
-__global__ __launch_bounds__(256, 3) void sepconv_mfma_rgb_kernel(View src, View dst, View dstf, Taps taps,
-                                                                  int ntx, int nchunks, int blocks_per_chunk, int fpw) {
-    constexpr int C = 3;
-    constexpr int OFF = MF_LEFT - C * R;                     // k = n + 3 t + OFF
-    constexpr int S0 = OFF / 16, S1 = (31 + 6 * R + OFF) / 16, NSH = S1 - S0 + 1;   // k-steps of the H product
-    extern __shared__ __attribute__((aligned(16))) char mlds[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = lane & 31, h = lane >> 5;
-    // XCD-aware order (ids are dealt round-robin over the 8 XCDs — speed only): every XCD walks a contiguous
-    // range of logical ids, x-fastest, so the ~90 column tiles of a row chunk run side by side on ONE XCD: its L2
-    // merges their overlapping 224-byte windows and HBM sees whole rows instead of 224-byte pieces
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, qq = nwg >> 3, rr8 = nwg & 7;
-    int bid = (xcd < rr8 ? xcd * (qq + 1) : rr8 * (qq + 1) + (xcd - rr8) * qq) + (orig >> 3);
-    const int bx = bid % ntx; bid /= ntx;
-    const int chunk = bid % nchunks, fg = bid / nchunks;
-    const int f_begin = fg * fpw, nfr = min(fpw, src.n - f_begin);          // this workgroup's frames
-    const int rowbytes = src.w * C;                          // multiple of 16 (host)
-    const int x0 = bx * 128;
-    const int y0 = chunk * blocks_per_chunk * 32;            // first output row of the chunk
-    const int y1 = min(src.h, y0 + blocks_per_chunk * 32);
-    const int nob = (y1 - y0 + 31) / 32;                     // output blocks of this chunk
-    const bool edge_l = x0 - MF_LEFT < 0, edge_r = x0 - MF_LEFT + 224 > rowbytes;   // block-uniform
-
-    // ---- constant operands (once per workgroup, amortised over fpw frames x nob blocks): the taps go
-    // to LDS so that a lane picks its weights by index instead of a 2R+1-way select chain
-    float* lt = (float*)(mlds + 2 * MF_IN_BYTES);            // (the out tile's space, free until the first V product)
-    if (threadIdx.x < 64) lt[threadIdx.x] = threadIdx.x < 32 ? (threadIdx.x <= 2 * R ? taps.x[threadIdx.x & 31] : 0.0f)
-                                                             : (threadIdx.x - 32 <= 2 * R ? taps.y[threadIdx.x & 31] : 0.0f);
-    __syncthreads();
-    // operand tables in LDS (registers would cost 96 VGPRs and a wave per SIMD): [step][hi | lo][lane] x 16 bytes,
-    // steps 0 .. NSH-1 = Th fragments B[k = 16 (S0 + s) + 8 h + j][n], steps NSH .. NSH+3 = Tv fragments
-    // A[i = n][k(s, h, j)] with k in D1's register order; wave w fills the steps s = w (mod 4)
-    f16x8* tab = (f16x8*)(mlds + MF_TILES);
-    for (int s = wave; s < NSH + 4; s += 4) {
-        f16x8 vhi, vlo;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float w;
-            if (s < NSH) {
-                const int k = 16 * (S0 + s) + 8 * h + j, t3 = k - n - OFF;
-                const int t = (int)(((u32)(t3 + 3) * 43691u) >> 17) - 1;      // floor(t3 / 3) for -3 <= t3 < 98301
-                const bool ok = t3 >= 0 && t * 3 == t3 && t <= 2 * R;
-                w = ok ? lt[ok ? t : 0] : 0.0f;
-            } else {
-                const int sv = s - NSH;
-                const int q = 32 * (sv >> 1) + 16 * (sv & 1) + 8 * (j >> 2) + 4 * h + (j & 3);   // row of [D1(prev); D1(cur)]
-                const int t = q - n - 16 + R;
-                const bool ok = t >= 0 && t <= 2 * R;
-                w = ok ? lt[32 + (ok ? t : 0)] : 0.0f;
-            }
-            // both halves at scale 2^15: hi = f16(w 2^15), lo = f16(w 2^15 - hi) is a NORMAL f16 for |w| >= 2^-18,
-            // so the two products of a k-step accumulate into one chain (no second accumulator, no recombination)
-            const float ws = w * 32768.0f;
-            const _Float16 hi = (_Float16)ws;
-            vhi[j] = hi;
-            vlo[j] = (_Float16)(ws - (float)hi);
-        }
-        tab[(s * 2 + 0) * 64 + lane] = vhi;
-        tab[(s * 2 + 1) * 64 + lane] = vlo;
-    }
-    __syncthreads();                                         // lt is overwritten by the first out tile
-
-    // ---- DMA of one 32-row block of frame f_begin + fi: chunk c = 64 i + lane of the [32 rows][17 chunks] grid,
-    // i = wave, wave + 4, (8)
-    const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)mlds;
-    int dma_row[3]; u32 dma_gx[3]; bool dma_ok[3];           // loop-invariant part of the three DMA instructions of a wave
-#pragma unroll
-    for (int ii = 0; ii < 3; ++ii) {
-        const int c = (wave + 4 * ii) * 64 + lane, row = c / 17, ch = c - row * 17;
-        dma_row[ii] = row;
-        dma_gx[ii] = (u32)min(max(x0 - MF_LEFT + 16 * ch, 0), rowbytes - 16);   // outside the row: any valid bytes (rewritten for edge tiles)
-        dma_ok[ii] = c < MF_ROWS * 17 && ch < 14;
-    }
-    auto dma_block = [&](int fi, int hb, int buf) {
-        const u8* sbase = src.p + (int64_t)(f_begin + fi) * src.fs;          // scalar
-        const int r0 = y0 - 16 + 32 * hb;                    // first input row of H block hb
-#pragma unroll
-        for (int ii = 0; ii < 3; ++ii) {
-            const int i = wave + 4 * ii;
-            if (i * 64 >= MF_ROWS * 17) continue;
-            int gy = r0 + dma_row[ii];
-            gy = gy < 0 ? -gy : (gy >= src.h ? 2 * src.h - 2 - gy : gy);     // REFLECT_101 (h >= 32: host)
-            gy = min(max(gy, 0), src.h - 1);                                  // rows far past a short last chunk
-            const u32 off = (u32)gy * (u32)src.rs + dma_gx[ii];              // < 2^32 (host)
-            const u32 ldst = __builtin_amdgcn_readfirstlane(lds0 + (u32)(buf * MF_IN_BYTES + i * 1024));
-            if (dma_ok[ii]) mfma_glds16(sbase, off, ldst);
-        }
-    };
-    // REFLECT_101 columns: bytes of the window that lie outside the row are copies of bytes inside it
-    auto fix_edges = [&](int buf) {
-        char* tile = mlds + buf * MF_IN_BYTES;
-        const int row = threadIdx.x >> 3, sub = threadIdx.x & 7;
-        for (int col = sub; col < 224; col += 8) {
-            const int p = x0 - MF_LEFT + col;
-            if (p >= 0 && p < rowbytes) continue;
-            const int px = p >= 0 ? p / 3 : -((-p + 2) / 3);
-            const int chn = p - 3 * px;
-            const int rp = px < 0 ? -px : 2 * src.w - 2 - px;
-            const int scol = 3 * rp + chn - (x0 - MF_LEFT);
-            if (scol >= 0 && scol < 224) tile[row * MF_PITCH + col] = tile[row * MF_PITCH + scol];
-        }
-    };
-
-    // H operands in registers (124 - 140 VGPRs, still 3 waves per SIMD): 6 - 7 % faster than re-reading them from LDS per k-step
-    f16x8 hw[HREG ? NSH : 1][2];
-    if constexpr (HREG) {
-#pragma unroll
-        for (int s = 0; s < NSH; ++s) { hw[s][0] = tab[(s * 2 + 0) * 64 + lane]; hw[s][1] = tab[(s * 2 + 1) * 64 + lane]; }
-    }
-    f16x8 prev_h[2], prev_l[2];                              // D1 of the previous block as two k-steps of f16 halves
-#pragma unroll
-    for (int s = 0; s < 2; ++s) { prev_h[s] = f16x8{}; prev_l[s] = f16x8{}; }
-    char* otile = mlds + 2 * MF_IN_BYTES;
-
-    // (frame, block) pairs form one sequence: the DMA of the next pair — the first block of the next frame
-    // included — is in flight while the current one is multiplied
-    const int per_frame = nob + 1, total = nfr * per_frame;
-    dma_block(0, 0, 0);
-    int fi = 0, hb = 0;
-    bool pending_store = false;                              // wave-uniform: a global store was issued after the last DMA
-#pragma unroll 1
-    for (int gb = 0; gb < total; ++gb) {
-        const int buf = gb & 1;
-        // this wave's chunks of the block must have landed; the one store instruction it may have issued after
-        // them (previous output block) is allowed to stay in flight — a store's acknowledge takes microseconds
-        if (pending_store) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        pending_store = false;
-        __builtin_amdgcn_s_barrier();                        // this block has landed; everybody is done with buffer buf^1 and the out tile
-        if (gb + 1 < total) {
-            const bool wrap = hb == nob;
-            dma_block(wrap ? fi + 1 : fi, wrap ? 0 : hb + 1, buf ^ 1);
-        }
-        u8* dbase = dst.p + (int64_t)(f_begin + fi) * dst.fs;
-        const int f = f_begin + fi;
-        if (edge_l || edge_r) {
-            fix_edges(buf);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        // ---- H product: rows of the block x this wave's 32 columns
-        const char* arow = mlds + buf * MF_IN_BYTES + n * MF_PITCH + 32 * wave + 8 * h;
-        f32x16 acc = {};
-#pragma unroll
-        for (int s = 0; s < NSH; ++s) {
-            const uint2 d = *(const uint2*)(arow + 16 * (S0 + s));
-            union { u32 u[4]; f16x8 v; } a;
-            a.u[0] = __builtin_amdgcn_perm(d.x, d.x, 0x0c010c00u) << 2;   // b * 2^-22: see sepconv_mfma2_rgb_kernel
-            a.u[1] = __builtin_amdgcn_perm(d.x, d.x, 0x0c030c02u) << 2;
-            a.u[2] = __builtin_amdgcn_perm(d.y, d.y, 0x0c010c00u) << 2;
-            a.u[3] = __builtin_amdgcn_perm(d.y, d.y, 0x0c030c02u) << 2;
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v, HREG ? hw[HREG ? s : 0][0] : tab[(s * 2 + 0) * 64 + lane], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a.v, HREG ? hw[HREG ? s : 0][1] : tab[(s * 2 + 1) * 64 + lane], acc, 0, 0, 0);
-        }
-        // ---- D1 = acc 2^7 (bytes at 2^-22, weights at 2^15), split into two f16 halves in accumulator (= operand) order
-        union H8 { u32 u[4]; f16x8 v; };
-        H8 ch[2], cl[2];
-#pragma unroll
-        for (int g = 0; g < 16; g += 2) {
-            const float v0 = acc[g] * 128.0f, v1 = acc[g + 1] * 128.0f;      // bytes at 2^-22, weights at 2^15
-            const auto hp = __builtin_amdgcn_cvt_pkrtz(v0, v1);
-            const f16x2 hh = __builtin_bit_cast(f16x2, hp);
-            ch[g >> 3].u[(g & 7) >> 1] = __builtin_bit_cast(u32, hp);
-            // residual = v - hi, exact (<= 13 significant bits); written as an fma so that it is ONE v_fma_mix_f32
-            // on the f16 half instead of a conversion and a subtraction
-            const _Float16 hx = hh.x, hy = hh.y;
-            cl[g >> 3].u[(g & 7) >> 1] = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_pkrtz(fmaf((float)hx, -1.0f, v0), fmaf((float)hy, -1.0f, v1)));
-        }
-        const f16x8 cur_h[2] = {ch[0].v, ch[1].v}, cur_l[2] = {cl[0].v, cl[1].v};
-        if (hb >= 1) {
-            // ---- V product: output rows [y0 + 32 (hb-1), +32) from D1(hb-1), D1(hb)
-            f32x16 ya = {};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const f16x8 xh = s < 2 ? prev_h[s] : cur_h[s - 2], xl = s < 2 ? prev_l[s] : cur_l[s - 2];
-                const f16x8 ah = tab[((NSH + s) * 2 + 0) * 64 + lane], al = tab[((NSH + s) * 2 + 1) * 64 + lane];
-                // transposed product Y^T = D1^T . Tv^T: the same registers in swapped roles (an A fragment of Tv
-                // lane-indexed by its row IS a B fragment of Tv^T lane-indexed by its column), so that the result has
-                // the OUTPUT ROW on the lane and 16 columns in registers: 4 packed dwords per lane instead of 16 bytes
-                ya = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, ah, ya, 0, 0, 0);
-                ya = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, ah, ya, 0, 0, 0);
-                ya = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, al, ya, 0, 0, 0);
-            }
-            const int yo = y0 + 32 * (hb - 1);
-            u32 w4[4];                                                     // w4[q]: columns 8 q + 4 h .. + 3 of row n
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                u32 pk = 0u;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pk = __builtin_amdgcn_cvt_pk_u8_f32(ya[4 * q4 + i] * (1.0f / 32768.0f), i, pk);
-                w4[q4] = pk;
-            }
-            if (dstf.p) {                                                  // fp32 side output (tests): one row per lane
-#pragma unroll
-                for (int g = 0; g < 16; ++g) {
-                    const int colb = x0 + 32 * wave + (g & 3) + 8 * (g >> 2) + 4 * h;
-                    if (yo + n < y1 && colb < rowbytes)
-                        ((float*)(dstf.p + (int64_t)f * dstf.fs + (int64_t)(yo + n) * dstf.rs))[colb] = ya[g] * (1.0f / 32768.0f);
-                }
-            }
-            {   // half exchanges: lower half-wave -> columns 0..15, upper -> 16..31 of its row, in (w0, w2, w1, w3) order
-                auto r0 = __builtin_amdgcn_permlane32_swap(w4[0], w4[2], false, false);
-                auto r1 = __builtin_amdgcn_permlane32_swap(w4[1], w4[3], false, false);
-                typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-                *(u32x4*)(otile + n * MF_OUT_PITCH + 32 * wave + 16 * h) = u32x4{r0[0], r0[1], r1[0], r1[1]};
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            // wave w stores rows 8 w .. 8 w + 7 of the out tile: 8 lanes x 16 B per row
-            const int orow = 8 * wave + (lane >> 3), ocol = 16 * (lane & 7);
-            pending_store = !dstf.p && __builtin_amdgcn_readfirstlane(yo + 8 * wave) < y1;   // lane 0's chunk exists <=> the store below executes
-            if (yo + orow < y1 && x0 + ocol < rowbytes) {
-                typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 o4 = *(const u32x4*)(otile + orow * MF_OUT_PITCH + ocol);
-                __builtin_nontemporal_store(o4, (u32x4*)(dbase + (int64_t)(yo + orow) * dst.rs + x0 + ocol));
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) { prev_h[s] = cur_h[s]; prev_l[s] = cur_l[s]; }
-        if (++hb > nob) { hb = 0; ++fi; }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// ---------------------------------------------------------------------------------------
-// Second structure (round 2, after the fused resample kernel showed what the skeleton costs): the same
-// two products and the same numerics, but a WAVE owns its 32 byte columns outright.
-//   * no LDS staging, no DMA bookkeeping, no per-block landing barrier: the rows of the 128-byte window
-//     [32 g - 48, 32 g + 80) are plain 16-byte global loads (lane = row, the block after next in flight
-//     in registers), and the loop body is straight-line, so hipcc counts the waits itself;
-//   * the H operands (8 k-steps x hi / lo) live in registers, built once per wave from a closed form that
-//     folds REFLECT_101 into the band matrix: source pixel xs also stands for the virtual pixels -xs and
-//     2 (W-1) - xs, so weight(xs, xo) = tap(xs - xo) + tap(-xs - xo) + tap(2 (W-1) - xs - xo).  Edge groups
-//     clamp their window into the row and need no byte rewriting; rows are reflected in the load address;
-//   * the V product is the transposed one (row on the lane), bytes leave through a double-buffered LDS
-//     tile: ONE barrier per 32-row block, the store of block j is issued during block j+1.
 // IMGXF_MFMA2_DBG (experiment builds only): 1 no barrier, 2 no stores, 4 no row loads inside the loop, 8 no H MFMAs, 16 no V MFMAs
 // (profiles/r03_experiments/mfma2_ablation.txt)
 #ifndef IMGXF_MFMA2_DBG
@@ -371,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void sepconv_mfma2_rgb_kernel(View src, Vie
             }
         }
     }
-    // ---- V operands (shared): as in sepconv_mfma_rgb_kernel, wave w fills step w
+    // ---- V operands (shared): wave w fills step w
     {
         f16x8 vhi, vlo;
 #pragma unroll
@@ -520,7 +276,7 @@ inline bool mfma_eligible(const View& s, const View& d, const View& df, int C, i
 }
 
 template <int R>
-inline int launch_sepconv_mfma2(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
+inline int launch_sepconv_mfma(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
     const int ng = (int)((s.rowbytes() + 31) / 32), ntx = (ng + 3) / 4;
     const int nblocks = (s.h + 31) / 32;
     // one frame, one 128-byte column set, one chunk of whole 32-row blocks per workgroup; every chunk costs one
@@ -534,40 +290,6 @@ inline int launch_sepconv_mfma2(const View& s, const View& d, const View& df, co
     const int64_t nwg = (int64_t)ntx * nchunks * s.n;
     if (nwg > 0x7fffffff) return IMGXF_ERR_SHAPE;
     hipLaunchKernelGGL((sepconv_mfma2_rgb_kernel<R>), dim3((unsigned)nwg), dim3(256), 0, st, s, d, df, taps, ntx, nchunks, bpc);
-    return launch_status();
-}
-
-} // namespace imgxf
-#ifdef IMGXF_EXPERIMENT_MFMA3
-#include "sepconv_mfma3.inc"          // the software-pipelined structure: measured slower (see its header), not built into the library
-#endif
-namespace imgxf {
-
-template <int R>
-inline int launch_sepconv_mfma(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
-#ifdef IMGXF_EXPERIMENT_MFMA3
-    if (!knob_set(K_MFMA_V1) && knob_set(K_MFMA_V3)) return launch_sepconv_mfma3<R>(s, d, df, taps, st);
-#endif
-    if (!knob_set(K_MFMA_V1)) return launch_sepconv_mfma2<R>(s, d, df, taps, st);
-    constexpr int OFFH = MF_LEFT - 3 * R, NSH_HOST = (31 + 6 * R + OFFH) / 16 - OFFH / 16 + 1;
-    const int ntx = (int)((s.rowbytes() + 127) / 128);
-    const int nblocks = (s.h + 31) / 32;
-    // a workgroup = one column tile x one chunk of whole 32-row blocks x up to 2 frames.  The operand set-up is paid
-    // once per workgroup and every chunk costs one extra H block, but the launch drains far better with many small
-    // workgroups than with few long ones (64 4K frames, k = 31: 2.07 ms at 8 frames x 17 blocks, 1.55 ms at 2 x 12,
-    // 1.75 ms at 1 x 6): aim at >= 16384 workgroups, chunks of >= 8 blocks
-    int fpw = s.n < 2 ? s.n : 2;
-    int bpc = nblocks;
-    auto count = [&]() { return (int64_t)ntx * ((nblocks + bpc - 1) / bpc) * ((s.n + fpw - 1) / fpw); };
-    while (count() < 16384 && bpc > 12) bpc = (nblocks + (nblocks + bpc - 1) / bpc) / ((nblocks + bpc - 1) / bpc + 1);   // one more chunk
-    while (count() < 4096 && fpw > 1) fpw = 1;
-    while (count() < 2048 && bpc > 4) bpc = (bpc + 1) / 2;
-    if (const char* sh = knob_str(K_MFMA_SHAPE)) { sscanf(sh, "%d,%d", &fpw, &bpc); fpw = std::max(1, std::min(fpw, s.n)); bpc = std::max(1, std::min(bpc, nblocks)); }
-    const int nchunks = (nblocks + bpc - 1) / bpc;
-    const int64_t nwg = (int64_t)ntx * nchunks * ((s.n + fpw - 1) / fpw);
-    if (nwg > 0x7fffffff) return IMGXF_ERR_SHAPE;
-    if (!knob_set(K_MFMA_NO_HREG)) hipLaunchKernelGGL((sepconv_mfma_rgb_kernel<R, true>), dim3((unsigned)nwg), dim3(256), mf_lds_bytes(NSH_HOST), st, s, d, df, taps, ntx, nchunks, bpc, fpw);
-    else hipLaunchKernelGGL((sepconv_mfma_rgb_kernel<R, false>), dim3((unsigned)nwg), dim3(256), mf_lds_bytes(NSH_HOST), st, s, d, df, taps, ntx, nchunks, bpc, fpw);
     return launch_status();
 }
 

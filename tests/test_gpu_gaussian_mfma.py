@@ -62,18 +62,6 @@ def test_mfma_equals_vector_kernel_up_to_rounding(device, monkeypatch):
         assert d.max() <= 1 and (d != 0).mean() < 1e-3
 
 
-@pytest.mark.parametrize("hw", [(37, 352), (129, 112), (270, 480)])
-@pytest.mark.parametrize("radius", [2.0, 3.5, 5.0])
-def test_lds_staged_mfma_kernel_still_within_contract(device, monkeypatch, hw, radius):
-    """IMGXF_MFMA_V1 selects the first structure (LDS-staged 128-byte tiles); the default is the wave-owned one."""
-    from imagetransformations_amd import ops
-    monkeypatch.setenv("IMGXF_MFMA_V1", "1")
-    a = synth(33, *hw)
-    k = O.blur_ksize(radius)
-    out, f32 = ops.gaussian_blur(dev(a, device), k, radius, return_f32=True)
-    assert_quantised_close(host(out), host(f32), O.gaussian_blur_f64(a, k, radius), O.saturate_u8, abs_term=MFMA_ABS * float(a.max()))
-
-
 def test_mfma_row_chunks_and_full_size_agree(device, monkeypatch):
     """Chunk length only changes which workgroup computes a row; 4K frames against the vector kernel."""
     from imagetransformations_amd import ops

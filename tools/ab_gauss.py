@@ -15,20 +15,17 @@ frames = torch.randint(0, 256, (F, H, W, 3), dtype=torch.uint8, device=dev, gene
 out = torch.empty_like(frames)
 st = torch.cuda.current_stream().cuda_stream
 vs, vo = _ffi.view_of(frames), _ffi.view_of(out)
-KNOBS = ("IMGXF_MARCH_TAIL", "IMGXF_MARCH_GROUP", "IMGXF_MARCH_SPB", "IMGXF_MARCH_NO_MIXED", "IMGXF_MARCH_RPW", "IMGXF_MARCH_U2")
+KNOBS = ("IMGXF_MARCH_GROUP", "IMGXF_MARCH_SPB")
 variants = {
-    "r1 (G=1, scalar H, spb4)": {"IMGXF_MARCH_GROUP": "1", "IMGXF_MARCH_NO_MIXED": "1", "IMGXF_MARCH_SPB": "4"},
     "default": {},
     "G=1": {"IMGXF_MARCH_GROUP": "1"},
     "G=2": {"IMGXF_MARCH_GROUP": "2"},
     "G=4": {"IMGXF_MARCH_GROUP": "4"},
     "G=8": {"IMGXF_MARCH_GROUP": "8"},
-    "rpw 64": {"IMGXF_MARCH_RPW": "64"},
-    "rpw 135": {"IMGXF_MARCH_RPW": "135"},
     "spb 3": {"IMGXF_MARCH_SPB": "3"},
 }
 extra = os.environ.get("AB_EXTRA")
-if extra:      # e.g. AB_EXTRA="rpw180:IMGXF_MARCH_RPW=180"
+if extra:      # e.g. AB_EXTRA="spb2:IMGXF_MARCH_SPB=2"
     for item in extra.split(";"):
         name, kv = item.split(":")
         variants[name] = dict(x.split("=") for x in kv.split(","))
