@@ -76,7 +76,8 @@ struct ParState { u32 p; u32 bk; };            // next symbol at bit p; bk = blo
 constexpr int PERSEG_SLOTS = 32;
 enum { HUFF_LANES = 0, HUFF_WAVE_PER_SEGMENT = 1, HUFF_WG256 = 2, HUFF_WG1024 = 3 };
 
-__device__ __forceinline__ int huff_class(const imgxf_jpeg_dec_image& im, const int32_t* seg_len) {
+template <class IM>                             // imgxf_jpeg_dec_image or imgxf_jpeg_dec_image_ext
+__device__ __forceinline__ int huff_class(const IM& im, const int32_t* seg_len) {
     const int64_t a = seg_len[im.seg_first], b = seg_len[im.seg_first + im.seg_count - 1];
     const int64_t L = (a + b) / 2;
     if (L < PAR_MIN_BYTES) return HUFF_LANES;
@@ -200,12 +201,15 @@ struct ParTables {
     const u8* comp_of_b;                        // block-in-MCU -> component
     int bpm;
 };
+// the block of the MCU that global block g of the segment is, and the MCU's block count: for these tables, the state's b
+__device__ __forceinline__ int mcu_block(const ParTables&, int b, int) { return b; }
+__device__ __forceinline__ int mcu_blocks(const ParTables& T) { return T.bpm; }
 
 // MODE 0: states and block count only.  MODE 1: write coefficients; `g` = number of the block the subsequence starts in,
 // blocks >= G are dropped.
-template <int MODE>
-__device__ __forceinline__ ParState par_run(const u8* seg, int len, ParState st, u32 p_end, const ParTables& T, int& nblk,
-                                            int g, int G, int m0, const imgxf_jpeg_dec_image& im, const u8* bx_of_b, const u8* by_of_b,
+template <int MODE, class IM, class TABS>
+__device__ __forceinline__ ParState par_run(const u8* seg, int len, ParState st, u32 p_end, const TABS& T, int& nblk,
+                                            int g, int G, int m0, const IM& im, const u8* bx_of_b, const u8* by_of_b,
                                             int16_t* coefs, bool& bad) {
     BitReader br;
     br.start_at(seg, len, st.p);
@@ -214,9 +218,10 @@ __device__ __forceinline__ ParState par_run(const u8* seg, int len, ParState st,
     int16_t* blk = nullptr;
     auto locate = [&]() {                       // MODE 1: address of block g
         if (g >= G) { blk = nullptr; return; }
-        const int m = m0 + g / T.bpm, my = m / im.mcux, mx = m - my * im.mcux;
-        const imgxf_jpeg_dec_comp& cp = im.comp[T.comp_of_b[b]];
-        blk = coefs + cp.coef_off + ((int64_t)(my * cp.v + by_of_b[b]) * cp.blocks_x + (mx * cp.h + bx_of_b[b])) * 64;
+        const int bb = mcu_block(T, b, g);
+        const int m = m0 + g / mcu_blocks(T), my = m / im.mcux, mx = m - my * im.mcux;
+        const imgxf_jpeg_dec_comp& cp = im.comp[T.comp_of_b[bb]];
+        blk = coefs + cp.coef_off + ((int64_t)(my * cp.v + by_of_b[bb]) * cp.blocks_x + (mx * cp.h + bx_of_b[bb])) * 64;
     };
     if (MODE == 1) locate();
     while (br.consumed() < p_end) {
@@ -788,6 +793,8 @@ static int dec_check_host(const imgxf_jpeg_dec_image* host, int n, int64_t* max_
     return IMGXF_OK;
 }
 
+#include "jpeg_decode_ext.inc"
+
 } // namespace imgxf
 
 using namespace imgxf;
@@ -856,5 +863,53 @@ IMGXF_API int imgxf_jpeg_decode_progressive(const uint8_t* scan, const int64_t* 
     }
     hipLaunchKernelGGL(jpeg_prog_kernel, dim3((unsigned)n), dim3(PROG_NT), 0, (hipStream_t)stream, scan, seg_off, seg_len, scans, n_scans,
                        images, luts, coefs, status);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_decode_huffman_ext(const uint8_t* scan, const int64_t* seg_off, const int32_t* seg_len,
+                                            const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host, int n,
+                                            const imgxf_jpeg_dec_lut* luts, int16_t* coefs, int32_t* status, void* stream) {
+    if (n < 0) return IMGXF_ERR_ARG;
+    if (n == 0) return IMGXF_OK;
+    if (!scan || !seg_off || !seg_len || !images || !images_host || !luts || !coefs) return IMGXF_ERR_NULL;
+    if (n > 65535) return IMGXF_ERR_SHAPE;
+    int64_t mb, mq;
+    IMGXF_CHECK(dec_check_ext_host(images_host, n, &mb, &mq));
+    // as imgxf_jpeg_decode_huffman: every kernel looks at every image and leaves the other classes alone
+    const int serial_only = knob_set(K_JPEG_SERIAL_HUFFMAN) ? 1 : 0;
+    hipLaunchKernelGGL(jpeg_huff_ext_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, scan, seg_off, seg_len, images, luts, coefs, status,
+                       serial_only);
+    if (!serial_only) {
+        hipLaunchKernelGGL((jpeg_huff_par_ext_kernel<256, false>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, scan, seg_off, seg_len,
+                           images, luts, coefs, status);
+        hipLaunchKernelGGL((jpeg_huff_par_ext_kernel<1024, false>), dim3((unsigned)n), dim3(1024), 0, (hipStream_t)stream, scan, seg_off, seg_len,
+                           images, luts, coefs, status);
+        hipLaunchKernelGGL((jpeg_huff_par_ext_kernel<64, true>), dim3((unsigned)n, PERSEG_SLOTS), dim3(64), 0, (hipStream_t)stream, scan, seg_off,
+                           seg_len, images, luts, coefs, status);
+    }
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_decode_idct_ext(const int16_t* coefs, const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host,
+                                         int n, const uint16_t* quants, uint8_t* planes, void* stream) {
+    if (n < 0) return IMGXF_ERR_ARG;
+    if (n == 0) return IMGXF_OK;
+    if (!coefs || !images || !images_host || !quants || !planes) return IMGXF_ERR_NULL;
+    if (n > 65535) return IMGXF_ERR_SHAPE;
+    int64_t mb, mq;
+    IMGXF_CHECK(dec_check_ext_host(images_host, n, &mb, &mq));
+    hipLaunchKernelGGL(jpeg_idct_ext_kernel, dim3((unsigned)((mb + 31) / 32), (unsigned)n), dim3(256), 0, (hipStream_t)stream, coefs, images, quants, planes);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_decode_color_ext(const uint8_t* planes, const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host,
+                                          int n, uint8_t* out, void* stream) {
+    if (n < 0) return IMGXF_ERR_ARG;
+    if (n == 0) return IMGXF_OK;
+    if (!planes || !images || !images_host || !out) return IMGXF_ERR_NULL;
+    if (n > 65535) return IMGXF_ERR_SHAPE;
+    int64_t mb, mq;
+    IMGXF_CHECK(dec_check_ext_host(images_host, n, &mb, &mq));
+    hipLaunchKernelGGL(jpeg_color_ext_kernel, dim3((unsigned)((mq + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, planes, images, out);
     return launch_status();
 }

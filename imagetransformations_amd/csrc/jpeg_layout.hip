@@ -21,7 +21,9 @@ struct HuffSpec { bool present = false; uint8_t bits[16]; uint8_t vals[256]; int
 
 struct Parsed {
     int width = 0, height = 0, ncomp = 0;
-    int cid[3], ch[3], cv[3], tq[3], td[3], ta[3];
+    int cid[4], ch[4], cv[4], tq[4], td[4], ta[4];
+    bool jfif = false;                                               // APP0 JFIF seen (before the scan)
+    int adobe = -1;                                                  // APP14 Adobe transform, -1: no Adobe marker
     bool have_qt[4] = {false, false, false, false};
     uint16_t qt[4][64];
     HuffSpec huff[2][4];
@@ -29,8 +31,18 @@ struct Parsed {
     size_t ecs_start = 0;
 };
 
-// jdmarker.c: the marker segments up to and including SOS.  Returns 0 or an IMGXF_JPEG_E_* code.
-int parse_header(const uint8_t* d, size_t n, Parsed& P) {
+// jdapimin.c default_decompress_parms: the colour space libjpeg reads a 3- or 4-component file in (an Adobe transform other
+// than 0 .. 2 draws a warning and reads as YCbCr / YCCK)
+int color_space(const Parsed& P) {
+    if (P.ncomp == 4) return P.adobe <= 0 ? IMGXF_JPEG_CS_CMYK : IMGXF_JPEG_CS_YCCK;
+    if (P.jfif) return IMGXF_JPEG_CS_YCBCR;
+    if (P.adobe >= 0) return P.adobe == 0 ? IMGXF_JPEG_CS_RGB : IMGXF_JPEG_CS_YCBCR;
+    return P.cid[0] == 'R' && P.cid[1] == 'G' && P.cid[2] == 'B' ? IMGXF_JPEG_CS_RGB : IMGXF_JPEG_CS_YCBCR;
+}
+
+// jdmarker.c: the marker segments up to and including SOS.  Returns 0 or an IMGXF_JPEG_E_* code.  `ext`: the extended class
+// (3 or 4 components, any colour space) instead of the baseline one (1 or 3 components, a 3-component file read as YCbCr).
+int parse_header(const uint8_t* d, size_t n, Parsed& P, bool ext = false) {
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return IMGXF_JPEG_E_NOT_JPEG;
     size_t pos = 2;
     bool have_frame = false;
@@ -58,7 +70,7 @@ int parse_header(const uint8_t* d, size_t n, Parsed& P) {
             if (sl < 6) return IMGXF_JPEG_E_MARKERS;
             if (seg[0] != 8) return IMGXF_JPEG_E_PRECISION;
             P.height = (seg[1] << 8) | seg[2]; P.width = (seg[3] << 8) | seg[4]; P.ncomp = seg[5];
-            if (P.ncomp != 1 && P.ncomp != 3) return IMGXF_JPEG_E_COMPONENTS;
+            if (ext ? P.ncomp != 3 && P.ncomp != 4 : P.ncomp != 1 && P.ncomp != 3) return IMGXF_JPEG_E_COMPONENTS;
             if (sl < 6 + 3 * (size_t)P.ncomp) return IMGXF_JPEG_E_MARKERS;
             for (int k = 0; k < P.ncomp; ++k) {
                 P.cid[k] = seg[6 + 3 * k]; P.ch[k] = seg[7 + 3 * k] >> 4; P.cv[k] = seg[7 + 3 * k] & 15; P.tq[k] = seg[8 + 3 * k];
@@ -66,6 +78,10 @@ int parse_header(const uint8_t* d, size_t n, Parsed& P) {
             have_frame = true;
         } else if (marker >= 0xC2 && marker <= 0xCF && marker != 0xC4 && marker != 0xC8 && marker != 0xCC) {
             return IMGXF_JPEG_E_PROCESS;                                 // progressive, lossless or arithmetic coding
+        } else if (marker == 0xE0) {
+            if (sl >= 14 && !memcmp(seg, "JFIF\0", 5)) P.jfif = true;
+        } else if (marker == 0xEE) {
+            if (sl >= 12 && !memcmp(seg, "Adobe", 5)) P.adobe = seg[11];
         } else if (marker == 0xC4) {
             size_t i = 0;
             while (i < sl) {
@@ -94,6 +110,10 @@ int parse_header(const uint8_t* d, size_t n, Parsed& P) {
                 if (seg[1 + 2 * k] != P.cid[k]) return IMGXF_JPEG_E_SCAN_ORDER;      // unknown component, or not in frame order
                 P.td[k] = seg[2 + 2 * k] >> 4; P.ta[k] = seg[2 + 2 * k] & 15;
                 if (P.td[k] > 3 || P.ta[k] > 3) return IMGXF_JPEG_E_MARKERS;
+            }
+            if (!ext && P.ncomp == 3) {                                  // the progressive layout's rule (no warning accepted)
+                const bool ycc = P.jfif ? true : P.adobe >= 0 ? P.adobe == 1 : !(P.cid[0] == 'R' && P.cid[1] == 'G' && P.cid[2] == 'B');
+                if (!ycc) return IMGXF_JPEG_E_COLORSPACE;
             }
             P.ecs_start = pos + 2 + seglen;
             return 0;
@@ -127,7 +147,7 @@ void derive_lut(const HuffSpec& H, imgxf_jpeg_dec_lut& L) {
     memcpy(L.huffval, H.vals, 256);
 }
 
-struct Geometry { int hmax, vmax, mcux, mcuy, ri, want; int ch[3], cv[3]; };
+struct Geometry { int hmax, vmax, mcux, mcuy, ri, want; int ch[4], cv[4]; };
 
 int geometry(const Parsed& P, Geometry& g) {
     for (int c = 0; c < P.ncomp; ++c) { g.ch[c] = P.ch[c]; g.cv[c] = P.cv[c]; }
@@ -207,13 +227,51 @@ IMGXF_API int imgxf_jpeg_unstuff_host(const uint8_t* data, size_t n, size_t star
     return IMGXF_OK;
 }
 
+namespace {
+
+// The extended class (imgxf_jpeg_dec_image_ext): each h, v in 1..4 (jdinput.c initial_setup), at most D_MAX_BLOCKS_IN_MCU
+// blocks per MCU (per_scan_setup), hmax / h and vmax / v integral (jdsample.c jinit_upsampler).
+int geometry_ext(const Parsed& P, Geometry& g) {
+    g.hmax = 1; g.vmax = 1;
+    for (int c = 0; c < P.ncomp; ++c) {
+        g.ch[c] = P.ch[c]; g.cv[c] = P.cv[c];
+        if (g.ch[c] < 1 || g.ch[c] > 4 || g.cv[c] < 1 || g.cv[c] > 4) return IMGXF_JPEG_E_SAMPLING;
+        if (g.ch[c] > g.hmax) g.hmax = g.ch[c];
+        if (g.cv[c] > g.vmax) g.vmax = g.cv[c];
+    }
+    if (P.width < 1 || P.height < 1) return IMGXF_JPEG_E_MARKERS;
+    int blocks = 0;
+    for (int c = 0; c < P.ncomp; ++c) blocks += g.ch[c] * g.cv[c];
+    if (blocks > 10) return IMGXF_JPEG_E_MCU_SIZE;
+    for (int c = 0; c < P.ncomp; ++c)
+        if (g.hmax % g.ch[c] || g.vmax % g.cv[c]) return IMGXF_JPEG_E_FRACTIONAL;
+    g.mcux = (P.width + 8 * g.hmax - 1) / (8 * g.hmax);
+    g.mcuy = (P.height + 8 * g.vmax - 1) / (8 * g.vmax);
+    const int total = g.mcux * g.mcuy;
+    g.ri = P.dri ? P.dri : total;
+    g.want = (total + g.ri - 1) / g.ri;
+    return 0;
+}
+
+// what the extended descriptor adds to the baseline one: the colour space and the MCU's block pattern
+void describe(imgxf_jpeg_dec_image&, const Parsed&) {}
+void describe(imgxf_jpeg_dec_image_ext& im, const Parsed& P) {
+    im.color = color_space(P);
+    int b = 0;
+    for (int c = 0; c < P.ncomp; ++c)
+        for (int by = 0; by < P.cv[c]; ++by)
+            for (int bx = 0; bx < P.ch[c]; ++bx) { im.mcu_comp[b] = (uint8_t)c; im.mcu_bx[b] = (uint8_t)bx; im.mcu_by[b] = (uint8_t)by; ++b; }
+    im.blocks_in_mcu = b;
+}
+
 // Pass 1 (scan == NULL): every file's header is parsed; *n_segs, *scan_cap (a bound), *n_quants, *n_luts (bounds) say what
 // pass 2 needs.  Pass 2: everything is filled.  status[i]: 0 or the IMGXF_JPEG_E_* code of file i (the call itself returns
-// IMGXF_OK; the caller raises for the first refused file).
-IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* sizes, int n, imgxf_jpeg_dec_image* images,
-                                     imgxf_jpeg_dec_lut* luts, int lut_cap, int* n_luts, uint16_t* quants, int quant_cap, int* n_quants,
-                                     uint8_t* scan, size_t scan_cap, size_t* scan_bytes, int64_t* seg_off, int32_t* seg_len, int seg_cap,
-                                     int* n_segs, int64_t* coef_total, int64_t* plane_total, int32_t* status) {
+// IMGXF_OK; the caller raises for the first refused file).  EXT: the extended class and its descriptor.
+template <class IM, bool EXT>
+int layout_sequential(const uint8_t* const* files, const size_t* sizes, int n, IM* images, imgxf_jpeg_dec_lut* luts, int lut_cap,
+                      int* n_luts, uint16_t* quants, int quant_cap, int* n_quants, uint8_t* scan, size_t scan_cap, size_t* scan_bytes,
+                      int64_t* seg_off, int32_t* seg_len, int seg_cap, int* n_segs, int64_t* coef_total, int64_t* plane_total,
+                      int32_t* status) {
     if (n < 0) return IMGXF_ERR_ARG;
     if (!files || !sizes || !n_luts || !n_quants || !scan_bytes || !n_segs || !status) return IMGXF_ERR_NULL;
     const bool fill = scan != nullptr;
@@ -226,9 +284,9 @@ IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* 
     for (int i = 0; i < n; ++i) {
         status[i] = 0;
         P = Parsed();
-        int rc = files[i] ? parse_header(files[i], sizes[i], P) : IMGXF_JPEG_E_NOT_JPEG;
+        int rc = files[i] ? parse_header(files[i], sizes[i], P, EXT) : IMGXF_JPEG_E_NOT_JPEG;
         Geometry g;
-        if (!rc) rc = geometry(P, g);
+        if (!rc) rc = EXT ? geometry_ext(P, g) : geometry(P, g);
         if (!rc)
             for (int c = 0; c < P.ncomp && !rc; ++c) {
                 if (P.tq[c] > 3 || !P.have_qt[P.tq[c]]) rc = IMGXF_JPEG_E_NO_QUANT;
@@ -237,7 +295,7 @@ IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* 
         if (rc) { status[i] = rc; continue; }
         cap_bound += sizes[i] - P.ecs_start + 32 * ((size_t)g.want + 1);
         if (!fill) { nseg += g.want; nq += P.ncomp; continue; }
-        imgxf_jpeg_dec_image& im = images[i];
+        IM& im = images[i];
         memset(&im, 0, sizeof(im));
         im.width = P.width; im.height = P.height; im.ncomp = P.ncomp; im.hmax = g.hmax; im.vmax = g.vmax; im.mcux = g.mcux; im.mcuy = g.mcuy;
         if (nseg + g.want > seg_cap) return IMGXF_ERR_WORKSPACE;
@@ -247,6 +305,7 @@ IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* 
         if (got < g.want) { status[i] = IMGXF_JPEG_E_TRUNCATED; continue; }
         im.restart_interval = g.ri; im.seg_first = nseg; im.seg_count = g.want;
         nseg += g.want;
+        describe(im, P);
         for (int c = 0; c < P.ncomp; ++c) {
             imgxf_jpeg_dec_comp& cp = im.comp[c];
             cp.h = g.ch[c]; cp.v = g.cv[c];
@@ -276,10 +335,30 @@ IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* 
             plane_pos += (int64_t)cp.blocks_x * cp.blocks_y * 64;
         }
     }
-    *n_segs = nseg; *n_quants = nq; *n_luts = fill ? (int)uniq.size() : 6 * n;
+    *n_segs = nseg; *n_quants = nq; *n_luts = fill ? (int)uniq.size() : (EXT ? 8 : 6) * n;
     *scan_bytes = fill ? spos : cap_bound;
     if (fill) { *coef_total = coef_pos; *plane_total = plane_pos; }
     return IMGXF_OK;
+}
+
+} // namespace
+
+IMGXF_API int imgxf_jpeg_layout_host(const uint8_t* const* files, const size_t* sizes, int n, imgxf_jpeg_dec_image* images,
+                                     imgxf_jpeg_dec_lut* luts, int lut_cap, int* n_luts, uint16_t* quants, int quant_cap, int* n_quants,
+                                     uint8_t* scan, size_t scan_cap, size_t* scan_bytes, int64_t* seg_off, int32_t* seg_len, int seg_cap,
+                                     int* n_segs, int64_t* coef_total, int64_t* plane_total, int32_t* status) {
+    return layout_sequential<imgxf_jpeg_dec_image, false>(files, sizes, n, images, luts, lut_cap, n_luts, quants, quant_cap, n_quants, scan,
+                                                          scan_cap, scan_bytes, seg_off, seg_len, seg_cap, n_segs, coef_total, plane_total, status);
+}
+
+IMGXF_API int imgxf_jpeg_layout_extended_host(const uint8_t* const* files, const size_t* sizes, int n, imgxf_jpeg_dec_image_ext* images,
+                                              imgxf_jpeg_dec_lut* luts, int lut_cap, int* n_luts, uint16_t* quants, int quant_cap,
+                                              int* n_quants, uint8_t* scan, size_t scan_cap, size_t* scan_bytes, int64_t* seg_off,
+                                              int32_t* seg_len, int seg_cap, int* n_segs, int64_t* coef_total, int64_t* plane_total,
+                                              int32_t* status) {
+    return layout_sequential<imgxf_jpeg_dec_image_ext, true>(files, sizes, n, images, luts, lut_cap, n_luts, quants, quant_cap, n_quants, scan,
+                                                             scan_cap, scan_bytes, seg_off, seg_len, seg_cap, n_segs, coef_total, plane_total,
+                                                             status);
 }
 
 // ---- progressive files (SOF2) ----------------------------------------------------------------------------------------

@@ -46,12 +46,14 @@ def _read(path: str):
 
 DECODE_STATS = {"device": 0, "pillow": 0}      # files decoded by the device reader / handed to Pillow by decoder="device"
 PROGRESSIVE_ON_DEVICE = os.environ.get("IMGXF_JPEG_PROGRESSIVE") == "1"   # progressive files on the device reader too (opt-in)
+EXTENDED_ON_DEVICE = os.environ.get("IMGXF_JPEG_EXTENDED") == "1"         # CMYK / YCCK / RGB-coded / odd sampling too (opt-in)
 
 
 def _decode_on_device(read):
     """[(bytes, path)] -> [(frame, path)]: one `jpeg_decode.decode` over the chunk; a file outside the device reader's
-    class (progressive unless PROGRESSIVE_ON_DEVICE, CMYK, ...: `UnsupportedJpeg`) or one it finds damaged is decoded by
-    Pillow, as :83 does, and uploaded — counted in DECODE_STATS so that the share is visible."""
+    class (progressive unless PROGRESSIVE_ON_DEVICE, CMYK unless EXTENDED_ON_DEVICE, ...) or one it finds damaged comes
+    back as None and is decoded by Pillow, as :83 does, and uploaded — counted in DECODE_STATS so that the share is
+    visible.  Only those files leave the batch."""
     import io
     import numpy as np
     import torch
@@ -59,23 +61,23 @@ def _decode_on_device(read):
     from ._ffi import ImgxfError
     items = [r for r in read if r is not None]
     try:
-        frames = jpeg_decode.decode([d for d, _ in items], progressive=PROGRESSIVE_ON_DEVICE)
-        DECODE_STATS["device"] += len(items)
-        return [(t, p) for t, (_, p) in zip(frames, items)]
-    except (jpeg_decode.UnsupportedJpeg, ImgxfError):
-        out = []
-        for d, p in items:
-            try:
-                out.append((jpeg_decode.decode([d], progressive=PROGRESSIVE_ON_DEVICE)[0], p))
-                DECODE_STATS["device"] += 1
-            except (jpeg_decode.UnsupportedJpeg, ImgxfError):
-                try:
-                    img = Image.open(io.BytesIO(d)).convert("RGB")
-                    out.append((torch.from_numpy(np.asarray(img)).cuda(), p))
-                    DECODE_STATS["pillow"] += 1
-                except Exception as e:
-                    print(f"Failed to load image {p}: {e}")
-        return out
+        frames = jpeg_decode.decode([d for d, _ in items], progressive=PROGRESSIVE_ON_DEVICE, extended=EXTENDED_ON_DEVICE,
+                                    statuses=[])
+    except (jpeg_decode.UnsupportedJpeg, ImgxfError):           # (not a per-file verdict: the whole chunk goes to Pillow)
+        frames = [None] * len(items)
+    out = []
+    for t, (d, p) in zip(frames, items):
+        if t is not None:
+            out.append((t, p))
+            DECODE_STATS["device"] += 1
+            continue
+        try:
+            img = Image.open(io.BytesIO(d)).convert("RGB")
+            out.append((torch.from_numpy(np.asarray(img)).cuda(), p))
+            DECODE_STATS["pillow"] += 1
+        except Exception as e:
+            print(f"Failed to load image {p}: {e}")
+    return out
 
 
 def _chunks(seq: Sequence, n: int) -> Iterable[Sequence]:

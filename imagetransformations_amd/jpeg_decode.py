@@ -24,8 +24,8 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
 
 
 class UnsupportedJpeg(ValueError):
-    """Not a file the device reader covers (progressive unless asked for, arithmetic, 12-bit, CMYK, non-interleaved
-    baseline scans, ...)."""
+    """Not a file the device reader covers (progressive or extended-class files unless asked for, arithmetic, 12-bit,
+    non-interleaved baseline scans, ...)."""
 
 
 class DecComp(C.Structure):
@@ -43,6 +43,18 @@ class DecImage(C.Structure):
                 ("comp", DecComp * 3)]
 
 
+class DecImageExt(C.Structure):
+    """struct imgxf_jpeg_dec_image_ext: the extended class (3 or 4 components, any sampling, colour space, MCU pattern)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
+                ("mcux", C.c_int32), ("mcuy", C.c_int32), ("restart_interval", C.c_int32), ("seg_first", C.c_int32),
+                ("seg_count", C.c_int32), ("color", C.c_int32), ("blocks_in_mcu", C.c_int32), ("mcu_comp", C.c_uint8 * 10),
+                ("mcu_bx", C.c_uint8 * 10), ("mcu_by", C.c_uint8 * 10), ("pad_", C.c_uint8 * 2), ("out_off", C.c_int64),
+                ("out_pitch", C.c_int64), ("comp", DecComp * 4)]
+
+
+CS_YCBCR, CS_RGB, CS_CMYK, CS_YCCK = 0, 1, 2, 3     # DecImageExt.color (IMGXF_JPEG_CS_*)
+
+
 class DecLut(C.Structure):
     """struct imgxf_jpeg_dec_lut"""
     _fields_ = [("look", C.c_uint16 * 256), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 17), ("huffval", C.c_uint8 * 256)]
@@ -54,6 +66,7 @@ def parse(data: bytes, find_end: bool = True) -> dict:
     if len(data) < 4 or data[0] != 0xFF or data[1] != 0xD8:
         raise UnsupportedJpeg("not a JPEG (no SOI)")
     pos, qt, huff, frame, dri = 2, {}, {}, None, 0
+    jfif, adobe = False, -1
     n = len(data)
     while True:
         if pos + 4 > n or data[pos] != 0xFF:
@@ -93,6 +106,11 @@ def parse(data: bytes, find_end: bool = True) -> dict:
                 i += 17 + cnt
         elif marker == 0xDD:
             dri = (seg[0] << 8) | seg[1]
+        elif marker == 0xE0:
+            jfif = jfif or (len(seg) >= 14 and seg[:5] == b"JFIF\0")
+        elif marker == 0xEE:
+            if len(seg) >= 12 and seg[:5] == b"Adobe":
+                adobe = seg[11]
         elif marker == 0xDA:
             if frame is None:
                 raise UnsupportedJpeg("SOS before SOF")
@@ -109,6 +127,8 @@ def parse(data: bytes, find_end: bool = True) -> dict:
                 scan.append((ids.index(cid), tt >> 4, tt & 15))
             if [s[0] for s in scan] != list(range(ns)):
                 raise UnsupportedJpeg("scan components out of frame order")
+            if ns == 3 and not reads_as_ycc(ids, jfif, adobe):
+                raise UnsupportedJpeg(_REFUSALS[14])
             start = pos + 2 + seglen
             end = None
             if find_end:
@@ -116,6 +136,16 @@ def parse(data: bytes, find_end: bool = True) -> dict:
                 end = m.start() if m else n
             return dict(width=w, height=h, comps=comps, qt=qt, huff=huff, scan=scan, dri=dri, ecs=(start, end))
         pos += 2 + seglen
+
+
+def reads_as_ycc(ids, jfif: bool, adobe: int) -> bool:
+    """Whether the baseline reader (which converts every 3-component file as YCbCr) may read a 3-component file:
+    jdapimin.c default_decompress_parms chooses YCbCr for it without a warning.  `adobe`: the APP14 transform, -1 if none."""
+    if jfif:
+        return True
+    if adobe >= 0:
+        return adobe == 1
+    return list(ids[:3]) != [ord("R"), ord("G"), ord("B")]
 
 
 _LUT_CACHE: dict = {}
@@ -171,7 +201,10 @@ _REFUSALS = {1: "not a JPEG (no SOI)", 2: "damaged marker structure", 3: "sample
              6: "the scan names an unknown component or not in frame order", 7: "sampling factors outside 1..2",
              8: "chroma sampling other than 4:4:4, 4:2:2 (h2v1) or 4:2:0", 9: "missing quantisation table", 10: "missing Huffman table",
              12: "a progression libjpeg rejects or warns about", 13: "libjpeg would smooth blocks (coefficients 1..9 not fully refined)",
-             14: "a 3-component file libjpeg does not read as YCbCr"}
+             14: "a 3-component file libjpeg does not read as YCbCr", 15: "sampling ratios that are not integral",
+             16: "more than 10 blocks per MCU"}
+_EXTENDED_COVERS = (5, 7, 8, 14)    # baseline refusals the extended layout may accept: components, sampling, chroma, colour space
+DAMAGED = -1                        # decode(..., statuses=): the entropy-coded data held an impossible code or ran out
 
 
 def _raise_for_status(status, n: int) -> None:
@@ -211,11 +244,16 @@ def is_progressive(data: bytes) -> bool:
 
 
 class _Layout:
-    """One call pair of imgxf_jpeg_layout_host (progressive=False) or imgxf_jpeg_layout_progressive_host over some files of
-    the batch: __init__ is pass 1 (counts, status), fill() pass 2 (the arrays)."""
+    """One call pair of imgxf_jpeg_layout_host, imgxf_jpeg_layout_progressive_host (progressive=True) or
+    imgxf_jpeg_layout_extended_host (extended=True) over some files of the batch: __init__ is pass 1 (counts, status),
+    fill() pass 2 (the arrays)."""
 
-    def __init__(self, files: List[bytes], progressive: bool):
+    _HOST = {"baseline": "imgxf_jpeg_layout_host", "progressive": "imgxf_jpeg_layout_progressive_host",
+             "extended": "imgxf_jpeg_layout_extended_host"}
+
+    def __init__(self, files: List[bytes], progressive: bool, extended: bool = False):
         n = self.n = len(files)
+        self.kind = "progressive" if progressive else "extended" if extended else "baseline"
         self.progressive = progressive
         self.ptrs = (C.c_char_p * n)(*files)
         self.sizes = (C.c_size_t * n)(*map(len, files))
@@ -228,13 +266,13 @@ class _Layout:
         head = (self.ptrs, self.sizes, self.n, images)
         if self.progressive:
             head += (scans, scans_cap, C.addressof(self.n_scans))
-        F.call("imgxf_jpeg_layout_progressive_host" if self.progressive else "imgxf_jpeg_layout_host", *head, luts, lut_cap,
+        F.call(self._HOST[self.kind], *head, luts, lut_cap,
                C.addressof(self.n_luts), quants, quant_cap, C.addressof(self.n_quants), scan, scan_cap, C.addressof(self.scan_bytes),
                seg_off, seg_len, seg_cap, C.addressof(self.n_segs), coef, plane, self.status)
 
     def fill(self) -> None:
         n = self.n
-        self.images = (DecImage * n)()
+        self.images = ((DecImageExt if self.kind == "extended" else DecImage) * n)()
         lut_cap, quant_cap = max(1, self.n_luts.value), max(1, self.n_quants.value)
         seg_cap, scan_cap, scans_cap = max(1, self.n_segs.value), max(64, self.scan_bytes.value), max(1, self.n_scans.value)
         self.luts = (DecLut * lut_cap)()
@@ -262,19 +300,24 @@ class _Layout:
         planes = torch.empty((self.plane_total.value,), dtype=torch.uint8, device=device)
         status = torch.zeros((n,), dtype=torch.int32, device=device)
         mark("uploads + zero fill")
+        ext = "_ext" if self.kind == "extended" else ""
         if self.progressive:
             F.call("imgxf_jpeg_decode_progressive", scan_d.data_ptr(), seg_off_d.data_ptr(), seg_len_d.data_ptr(), scans_d.data_ptr(),
                    C.addressof(self.scans), self.n_scans.value, images_d.data_ptr(), n, luts_d.data_ptr(), coefs.data_ptr(),
                    status.data_ptr(), stream)
             mark("progressive kernel")
+        elif ext:
+            F.call("imgxf_jpeg_decode_huffman_ext", scan_d.data_ptr(), seg_off_d.data_ptr(), seg_len_d.data_ptr(), images_d.data_ptr(),
+                   C.addressof(self.images), n, luts_d.data_ptr(), coefs.data_ptr(), status.data_ptr(), stream)
+            mark("huffman kernel")
         else:
             F.call("imgxf_jpeg_decode_huffman", scan_d.data_ptr(), seg_off_d.data_ptr(), seg_len_d.data_ptr(), images_d.data_ptr(), n,
                    luts_d.data_ptr(), coefs.data_ptr(), status.data_ptr(), stream)
             mark("huffman kernel")
-        F.call("imgxf_jpeg_decode_idct", coefs.data_ptr(), images_d.data_ptr(), C.addressof(self.images), n, quants_d.data_ptr(),
+        F.call("imgxf_jpeg_decode_idct" + ext, coefs.data_ptr(), images_d.data_ptr(), C.addressof(self.images), n, quants_d.data_ptr(),
                planes.data_ptr(), stream)
         mark("idct kernel")
-        F.call("imgxf_jpeg_decode_color", planes.data_ptr(), images_d.data_ptr(), C.addressof(self.images), n, out.data_ptr(), stream)
+        F.call("imgxf_jpeg_decode_color" + ext, planes.data_ptr(), images_d.data_ptr(), C.addressof(self.images), n, out.data_ptr(), stream)
         mark("upsample + colour kernel")
         return status
 
@@ -282,48 +325,74 @@ class _Layout:
 LAST_PROFILE: dict = {}        # filled by decode(..., profile=True): seconds per stage of the last call (it synchronises)
 
 
-def decode(files: Sequence[bytes], device=None, profile: bool = False, *, progressive: bool = False) -> List[torch.Tensor]:
+def decode(files: Sequence[bytes], device=None, profile: bool = False, *, progressive: bool = False, extended: bool = False,
+           statuses: list | None = None) -> List[torch.Tensor]:
     """One [H, W, 3] uint8 RGB device tensor per file: the pixels of `Image.open(BytesIO(f)).convert("RGB")`.
     Files of equal size share one [N, H, W, 3] allocation (the views are its frames), which is what the batched drivers
     group by.  Raises UnsupportedJpeg for a file outside the reader's class, ImgxfError for a damaged stream.
     `progressive=True`: progressive (SOF2) files are read too (imgxf_jpeg_layout_progressive_host +
-    imgxf_jpeg_decode_progressive); the other files of the batch take the baseline reader, results stay in input order."""
+    imgxf_jpeg_decode_progressive).  `extended=True`: sequential files the baseline layout refuses for their component
+    count, sampling or colour space (CMYK, YCCK, RGB-coded, 4:4:0, 4:1:1, ...) are read by the extended stages
+    (imgxf_jpeg_layout_extended_host + imgxf_jpeg_decode_*_ext).  The other files take the baseline reader; results stay
+    in input order.  `statuses`: a list, cleared and given one entry per file — 0 (decoded), the IMGXF_JPEG_E_* code of a
+    refused file or DAMAGED — and refused or damaged files come back as None instead of raising for the batch."""
     device = torch.device("cuda") if device is None else torch.device(device)
     if device.type != "cuda":
         raise F.ImgxfError(F.ERR_NO_DEVICE, "the JPEG reader runs on the GPU (no CPU fallback)", "jpeg_decode.decode")
     import time
     n = len(files)
+    keep_going = statuses is not None
+    if keep_going:
+        statuses.clear()
+        statuses.extend([0] * n)
     if n == 0:
         return []
     t_start = time.perf_counter()
     files = [bytes(f) for f in files]
-    # host half in C (csrc/jpeg_layout.hip: the statement of parse / derive_lut / _segments above for a whole batch); with
-    # `progressive`, one layout for the SOF2 files and one for the others: members[g][j] = input index of file j of group g
-    prog = [i for i in range(n) if is_progressive(files[i])] if progressive else []
-    if prog:
-        base = sorted(set(range(n)) - set(prog))
-        members = [m for m in (base, prog) if m]
-        layouts = [_Layout([files[i] for i in m], m is prog) for m in members]
-    else:
-        members, layouts = [list(range(n))], [_Layout(files, False)]
+    # host half in C (csrc/jpeg_layout.hip: the statement of parse / derive_lut / _segments above for a whole batch): one
+    # layout per class; kind_of[i] = the class of file i
+    kind_of = ["progressive" if progressive and is_progressive(f) else "baseline" for f in files]
+    st = [0] * n
 
-    def merged_status():
-        st = [0] * n
-        for m, L in zip(members, layouts):
+    def layouts_for(idx):
+        """pass 1 over the files `idx`, grouped by class -> [(members, layout)]; st[] gets their verdicts"""
+        out = []
+        for kind in ("baseline", "progressive", "extended"):
+            m = [i for i in idx if kind_of[i] == kind]
+            if m:
+                L = _Layout([files[i] for i in m], kind == "progressive", kind == "extended")
+                for j, i in enumerate(m):
+                    st[i] = L.status[j]
+                out.append((m, L))
+        return out
+
+    groups = layouts_for(range(n))
+    if extended:
+        moved = [i for i in range(n) if kind_of[i] == "baseline" and st[i] in _EXTENDED_COVERS]
+        if moved:
+            for i in moved:
+                kind_of[i] = "extended"
+            groups = layouts_for(range(n))
+    if not keep_going:
+        _raise_for_status(st, n)
+    elif any(st):                                                # lay out only the files that are read
+        groups = layouts_for([i for i in range(n) if not st[i]])
+    while True:                                                  # (each repeat lays out fewer files)
+        for m, L in groups:
+            L.fill()
             for j, i in enumerate(m):
                 st[i] = L.status[j]
-        return st
-
-    _raise_for_status(merged_status(), n)
-    for L in layouts:
-        L.fill()
-    _raise_for_status(merged_status(), n)
+        if not any(st[i] for m, _ in groups for i in m):
+            break
+        if not keep_going:                                       # the fill pass found a scan that ends early
+            _raise_for_status(st, n)
+        groups = layouts_for([i for i in range(n) if not st[i]])
     where = {}                                                   # input index -> (layout, its index there)
-    for m, L in zip(members, layouts):
+    for m, L in groups:
         for j, i in enumerate(m):
             where[i] = (L, j)
     by_size: dict = {}
-    for i in range(n):
+    for i in sorted(where):
         L, j = where[i]
         by_size.setdefault((L.images[j].height, L.images[j].width), []).append(i)
 
@@ -352,21 +421,26 @@ def decode(files: Sequence[bytes], device=None, profile: bool = False, *, progre
             LAST_PROFILE.clear()
             LAST_PROFILE["host parse + tables"] = t_host - t_start
         stream = torch.cuda.current_stream(device).cuda_stream
-        out = torch.empty((out_pos,), dtype=torch.uint8, device=device)
-        statuses = [L.run(device, stream, out, mark) for L in layouts]
-        bad = sorted(m[j] for m, st in zip(members, statuses) for j in torch.nonzero(st).flatten().tolist())
-    if bad:
+        out = torch.empty((max(out_pos, 16),), dtype=torch.uint8, device=device)
+        device_status = [(m, L.run(device, stream, out, mark)) for m, L in groups]
+        bad = sorted(m[j] for m, ds in device_status for j in torch.nonzero(ds).flatten().tolist())
+    if bad and not keep_going:
         raise F.ImgxfError(F.ERR_ARG, f"damaged entropy-coded data in file(s) {bad}", "jpeg_decode.decode")
+    for i in bad:
+        st[i] = DAMAGED
     for off, cnt, h, w, group in spans:
         frames = out[off:off + cnt * h * w * 3].view(cnt, h, w, 3).unbind(0)     # (one call: indexing frame by frame costs 3 us each)
         for k, i in enumerate(group):
-            results[i] = frames[k]
+            if not st[i]:
+                results[i] = frames[k]
+    if keep_going:
+        statuses[:] = st
     return results
 
 
-def decode_batches(files: Sequence[bytes], device=None):
+def decode_batches(files: Sequence[bytes], device=None, *, progressive: bool = False, extended: bool = False):
     """`decode`, grouped: {(height, width): ([N, H, W, 3] tensor, [file indices])} — the layout the batched drivers use."""
-    frames = decode(files, device)
+    frames = decode(files, device, progressive=progressive, extended=extended)
     groups: dict = {}
     for i, t in enumerate(frames):
         groups.setdefault((t.shape[0], t.shape[1]), []).append(i)

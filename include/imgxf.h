@@ -515,6 +515,49 @@ int imgxf_jpeg_decode_progressive(const uint8_t* scan, const int64_t* seg_off, c
                                   const imgxf_jpeg_dec_scan* scans, const imgxf_jpeg_dec_scan* scans_host, int n_scans,
                                   const imgxf_jpeg_dec_image* images, int n, const imgxf_jpeg_dec_lut* luts, int16_t* coefs,
                                   int32_t* status, void* stream);
+/* imgxf_jpeg_layout_host and the Python parse refuse a 3-component baseline file that default_decompress_parms does not read
+ * as YCbCr with IMGXF_JPEG_E_COLORSPACE too: the reader above converts every 3-component file as YCbCr. */
+
+/* ---- the same load step for EXTENDED sequential files: 3 or 4 components, any sampling libjpeg accepts ----------------
+ * SOF0 / SOF1 Huffman, 8 bit, all components in one interleaved scan; colour space as jdapimin.c default_decompress_parms
+ * chooses it (3 components: JFIF -> YCbCr, else Adobe transform 0 -> RGB / other -> YCbCr, else ids 'R','G','B' -> RGB,
+ * else YCbCr; 4 components: Adobe transform 0 -> CMYK / other -> YCCK, no Adobe marker -> CMYK); each h, v in 1..4 with
+ * hmax / h and vmax / v integral and at most 10 blocks per MCU (D_MAX_BLOCKS_IN_MCU).  Output: the RGB pixels of
+ * Image.open(f).convert("RGB") — for 4 components libjpeg's ycck_cmyk_convert (YCCK), Pillow's "CMYK;I" rawmode (every
+ * sample inverted) and Pillow's cmyk2rgb.  Refusal codes after IMGXF_JPEG_E_COLORSPACE (status[] of
+ * imgxf_jpeg_layout_extended_host, which also uses E_COMPONENTS for other than 3 or 4 components and E_SAMPLING for
+ * factors outside 1..4): */
+enum { IMGXF_JPEG_E_FRACTIONAL = 15,  /* hmax / h or vmax / v not integral (jdsample.c JERR_FRACT_SAMPLE_NOTIMPL) */
+       IMGXF_JPEG_E_MCU_SIZE = 16     /* more than 10 blocks per MCU (jdinput.c JERR_BAD_MCU_SIZE) */ };
+enum { IMGXF_JPEG_CS_YCBCR = 0, IMGXF_JPEG_CS_RGB = 1, IMGXF_JPEG_CS_CMYK = 2, IMGXF_JPEG_CS_YCCK = 3 };
+typedef struct imgxf_jpeg_dec_image_ext {
+    int32_t width, height, ncomp, hmax, vmax, mcux, mcuy;   /* as imgxf_jpeg_dec_image; ncomp 3 or 4 */
+    int32_t restart_interval, seg_first, seg_count;
+    int32_t color;              /* IMGXF_JPEG_CS_* */
+    int32_t blocks_in_mcu;      /* 1 .. 10 */
+    uint8_t mcu_comp[10];       /* block b of an MCU: component mcu_comp[b], block (mcu_bx[b], mcu_by[b]) of its h x v */
+    uint8_t mcu_bx[10], mcu_by[10];
+    uint8_t pad_[2];
+    int64_t out_off, out_pitch;
+    imgxf_jpeg_dec_comp comp[4]; /* h, v in 1..4; the rest as in imgxf_jpeg_dec_image */
+} imgxf_jpeg_dec_image_ext;
+/* HOST half for extended files: imgxf_jpeg_layout_host's two-call protocol and arrays, with imgxf_jpeg_dec_image_ext
+ * descriptors (pass 1: *n_luts is a bound of 8 per file). */
+int imgxf_jpeg_layout_extended_host(const uint8_t* const* files, const size_t* sizes, int n, imgxf_jpeg_dec_image_ext* images,
+                                    imgxf_jpeg_dec_lut* luts, int lut_cap, int* n_luts, uint16_t* quants, int quant_cap, int* n_quants,
+                                    uint8_t* scan, size_t scan_cap, size_t* scan_bytes, int64_t* seg_off, int32_t* seg_len, int seg_cap,
+                                    int* n_segs, int64_t* coef_total, int64_t* plane_total, int32_t* status);
+/* The three device stages of imgxf_jpeg_decode_huffman / _idct / _color over extended descriptors: entropy decoding (a lane
+ * per restart segment, or the in-segment parallel decoder for long segments), dequantisation + jpeg_idct_islow, and
+ * upsampling (jdsample.c: fullsize, h2v1 / h2v2 fancy when downsampled_width > 2, h1v2 fancy, int_upsample otherwise)
+ * + colour conversion into the RGB frames at out_off / out_pitch.  images_host: the host copy, checked before a launch. */
+int imgxf_jpeg_decode_huffman_ext(const uint8_t* scan, const int64_t* seg_off, const int32_t* seg_len,
+                                  const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host, int n,
+                                  const imgxf_jpeg_dec_lut* luts, int16_t* coefs, int32_t* status, void* stream);
+int imgxf_jpeg_decode_idct_ext(const int16_t* coefs, const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host,
+                               int n, const uint16_t* quants, uint8_t* planes, void* stream);
+int imgxf_jpeg_decode_color_ext(const uint8_t* planes, const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host,
+                                int n, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
