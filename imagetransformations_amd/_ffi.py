@@ -100,6 +100,10 @@ SIGNATURES = {
     "imgxf_jpeg_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_u8": [_VP, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                              C.c_void_p],
+    "imgxf_jpeg_workspace_bytes_ex": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_optimal_tables": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "imgxf_jpeg_encode_ex_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                C.c_size_t, C.c_void_p],
     "imgxf_np_accept": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "imgxf_np_normals_f32": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
@@ -133,6 +137,11 @@ class JpegTables(C.Structure):
     """struct imgxf_jpeg_tables (include/imgxf.h)."""
     _fields_ = [("quant", (C.c_uint16 * 64) * 2), ("dc_code", (C.c_uint16 * 16) * 2), ("dc_len", (C.c_uint8 * 16) * 2),
                 ("ac_code", (C.c_uint16 * 256) * 2), ("ac_len", (C.c_uint8 * 256) * 2)]
+
+
+class JpegEncParams(C.Structure):
+    """struct imgxf_jpeg_enc_params (include/imgxf.h)."""
+    _fields_ = [("ncomp", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32), ("optimize", C.c_int32)]
 
 
 def _load() -> C.CDLL:

@@ -187,6 +187,7 @@ __global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __r
         real = true;
     }
     if (mx0 + ml >= mw || !real) return;
+    // from here on the same statements as jpeg_code_block (jpeg_encode_ext.inc, the other layouts): keep them in step
     int d[64];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -689,6 +690,8 @@ static bool quant_entry(u32 qv, u32* m, u32* halfp) {
     return true;
 }
 
+#include "jpeg_encode_ext.inc"
+
 } // namespace imgxf
 
 using namespace imgxf;
@@ -761,5 +764,121 @@ IMGXF_API int imgxf_jpeg_encode_u8(const imgxf_view* src, const imgxf_jpeg_table
     IMGXF_CHECK(scan_rows(cnt, L.nchunks, L.nchunks, s.n, part, tot_ff, st));
     hipLaunchKernelGGL(jpeg_stuff_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits,
                        (const u32*)cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)tot_ff, out, (int64_t)out_frame_stride, sizes, hd);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_workspace_bytes_ex(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t out_frame_stride,
+                                            size_t* bytes) {
+    if (!bytes || !params) return IMGXF_ERR_NULL;
+    const int lay = enc_layout(params);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
+    *bytes = jpeg_layout_ex(lay, params->optimize != 0, n, h, w, out_frame_stride).total;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_jpeg_encode_ex_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
+                                      const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
+                                      uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+    IMGXF_CHECK(check_view(src));
+    if (!params || !tables || !header || !out || !sizes) return IMGXF_ERR_NULL;
+    const int lay = enc_layout(params);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    if (src->c != params->ncomp) return IMGXF_ERR_UNSUPPORTED;
+    const bool opt = params->optimize != 0;
+    if (lay == JL420 && !opt)                                  // the default file: the 4:2:0 writer as it is
+        return imgxf_jpeg_encode_u8(src, tables, header, header_bytes, out, out_frame_stride, sizes, workspace, workspace_bytes, stream);
+    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
+    if (src->n == 0) return IMGXF_OK;
+    if (empty_view(src)) return IMGXF_ERR_SHAPE;
+    if (src->n > 65535) return IMGXF_ERR_SHAPE;
+    if (out_frame_stride < (size_t)header_bytes + 2 || out_frame_stride > ((size_t)1 << 31)) return IMGXF_ERR_ARG;
+    const JpegLayoutEx X = jpeg_layout_ex(lay, opt, src->n, src->h, src->w, out_frame_stride);
+    const JpegLayout& L = X.L;
+    if (!workspace || workspace_bytes < X.total || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
+    if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;        // bit offsets are 32-bit
+    const int ntab = params->ncomp == 1 ? 1 : 2;
+    JpegQuant q;
+    memset(&q, 0, sizeof(q));
+    for (int t = 0; t < ntab; ++t)
+        for (int i = 0; i < 64; ++i) {
+            const u32 qv = tables->quant[t][i];
+            if (qv < 1 || qv > 255 || !quant_entry(qv, &q.m[t][i], &q.half[t][i])) return IMGXF_ERR_ARG;
+        }
+    JpegHuff hf;
+    for (int t = 0; t < 2; ++t) {
+        for (int i = 0; i < 16; ++i) hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
+        for (int i = 0; i < 256; ++i) {
+            hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
+            q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));
+        }
+    }
+    JpegHeader hd;
+    memset(&hd, 0, sizeof(hd));
+    memcpy(hd.b, header, (size_t)header_bytes);
+    hd.len = header_bytes;
+    const View s = make_view(src);
+    hipStream_t st = (hipStream_t)stream;
+    u8* ws = (u8*)workspace;
+    int16_t* coef = (int16_t*)(ws + L.off_coef);
+    int16_t* dcs = (int16_t*)(ws + L.off_dcs);
+    uint16_t* acb = (uint16_t*)(ws + L.off_acb);
+    u32* lens = (u32*)(ws + L.off_lens);
+    u32* part = (u32*)(ws + L.off_part);
+    u32* tot_bits = (u32*)(ws + L.off_tot);
+    u32* tot_ff = tot_bits + s.n;
+    u32* ustream = (u32*)(ws + L.off_stream);
+    u32* cnt = (u32*)(ws + L.off_cnt);
+    u32* sym = opt ? (u32*)(ws + X.off_sym) : nullptr;
+    JpegHuff* fh = opt ? (JpegHuff*)(ws + X.off_fh) : nullptr;
+    JpegDht* dht = opt ? (JpegDht*)(ws + X.off_dht) : nullptr;
+    const JpegGeom g = {L.mw, L.mh, L.bw, L.bh, L.nblk};
+    const int64_t coef_fs = (int64_t)((L.nblk + 63) / 64) * 64 * 64;
+    switch (lay) {
+    case JL420:
+        hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((L.mw + JM - 1) / JM), (unsigned)L.mh, (unsigned)s.n), dim3(JT), 0, st,
+                           s, coef, coef_fs, dcs, acb, L.nblk, L.mw, L.bw, L.bh, q);
+        break;
+    case JL422: launch_transform_ex<JL422>(s, coef, coef_fs, dcs, acb, L, q, st); break;
+    case JL444: launch_transform_ex<JL444>(s, coef, coef_fs, dcs, acb, L, q, st); break;
+    default: launch_transform_ex<JLGRAY>(s, coef, coef_fs, dcs, acb, L, q, st); break;
+    }
+    if (opt && hipMemsetAsync(sym, 0, (size_t)s.n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
+    switch (lay) {
+    case JL420: launch_entropy_ex<JL420>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
+    case JL422: launch_entropy_ex<JL422>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
+    case JL444: launch_entropy_ex<JL444>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
+    default: launch_entropy_ex<JLGRAY>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
+    }
+    IMGXF_CHECK(scan_rows(lens, L.nblk, L.nblk, s.n, part, tot_bits, st));
+    const dim3 bgrid((unsigned)((L.nblk + 255) / 256), (unsigned)s.n);
+    hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, st, ustream, L.stream_words, (const u32*)lens, (const u32*)tot_bits, L.nblk);
+    switch (lay) {
+    case JL420: launch_emit_ex<JL420>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
+    case JL422: launch_emit_ex<JL422>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
+    case JL444: launch_emit_ex<JL444>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
+    default: launch_emit_ex<JLGRAY>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
+    }
+    const unsigned cwg = (unsigned)((L.nchunks + 255) / 256);
+    const dim3 cgrid(cwg < 256u ? cwg : 256u, (unsigned)s.n);
+    hipLaunchKernelGGL(jpeg_ffcount_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits, cnt,
+                       (int64_t)L.nchunks, L.nchunks);
+    IMGXF_CHECK(scan_rows(cnt, L.nchunks, L.nchunks, s.n, part, tot_ff, st));
+    if (opt)
+        hipLaunchKernelGGL(jpeg_stuff_ex_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits,
+                           (const u32*)cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)tot_ff, out, (int64_t)out_frame_stride, sizes, hd,
+                           (const JpegDht*)dht, ntab * 2);
+    else
+        hipLaunchKernelGGL(jpeg_stuff_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits,
+                           (const u32*)cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)tot_ff, out, (int64_t)out_frame_stride, sizes, hd);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_optimal_tables(const uint32_t* counts, int n, uint8_t* dht, uint32_t* codes, void* stream) {
+    if (!counts || !dht || !codes) return IMGXF_ERR_NULL;
+    if (n < 0 || n > 65535) return IMGXF_ERR_SHAPE;
+    if (n == 0) return IMGXF_OK;
+    hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3((unsigned)JSLOTS, (unsigned)n), dim3(256), 0, (hipStream_t)stream, counts,
+                       (JpegHuff*)codes, (JpegDht*)dht);
     return launch_status();
 }

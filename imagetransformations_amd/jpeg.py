@@ -67,66 +67,143 @@ def tables(quality: int = 75) -> F.JpegTables:
     return t
 
 
+# Pillow's `subsampling` spellings for an array source → luma (h, v) sampling; -1 is libjpeg's default (2×2 for YCbCr, 1×1
+# for grayscale).  "keep" needs a JPEG source and is refused, as Pillow refuses it for an array.
+SUBSAMPLING = {-1: None, 0: (1, 1), 1: (2, 1), 2: (2, 2), "4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+
+
+def sampling(subsampling=-1, ncomp: int = 3):
+    """Pillow's `subsampling` value → the luma component's (h, v) sampling factors; ValueError for anything else."""
+    if isinstance(subsampling, bool) or not isinstance(subsampling, (int, str)) or subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling must be one of -1, 0, 1, 2, '4:4:4', '4:2:2', '4:2:0', not {subsampling!r}")
+    hv = SUBSAMPLING[subsampling]
+    return hv if hv is not None else ((1, 1) if ncomp == 1 else (2, 2))
+
+
 @lru_cache(maxsize=64)
-def header(width: int, height: int, quality: int = 75) -> bytes:
-    """SOI, APP0 (JFIF 1.01, no density), DQT ×2, SOF0 (Y 2×2, Cb / Cr 1×1), DHT ×4, SOS — jcmarker.c's order."""
+def header(width: int, height: int, quality: int = 75, *, ncomp: int = 3, subsampling=-1, optimize: bool = False) -> bytes:
+    """SOI, APP0 (JFIF 1.01, no density), DQT ×2 (×1 grayscale), SOF0 (Y h×v, Cb / Cr 1×1), DHT ×4 (×2 grayscale), SOS —
+    jcmarker.c's order.  With `optimize` the file's Huffman tables are the frame's own: the prefix ends with SOF and the
+    device writes DHT and SOS (imgxf_jpeg_encode_ex_u8)."""
     if not (0 < width < 65536 and 0 < height < 65536):
         raise ValueError("JPEG dimensions must be 1..65535")
+    if ncomp not in (1, 3):
+        raise ValueError("JPEG frames have 1 (grayscale) or 3 (RGB) channels")
+    hs, vs = sampling(subsampling, ncomp)
+    ntab = 1 if ncomp == 1 else 2
     out = bytearray(b"\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
-    for i, qt in enumerate(quant_tables(quality)):
+    for i, qt in enumerate(quant_tables(quality)[:ntab]):
         out += b"\xff\xdb\x00\x43" + bytes([i]) + bytes(qt[z] for z in ZIGZAG)
-    out += b"\xff\xc0\x00\x11\x08" + height.to_bytes(2, "big") + width.to_bytes(2, "big") + b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01"
-    for i in range(2):
+    comps = bytes([1, (hs << 4) | vs, 0]) + (b"\x02\x11\x01\x03\x11\x01" if ncomp == 3 else b"")
+    out += b"\xff\xc0" + (8 + len(comps)).to_bytes(2, "big") + b"\x08" + height.to_bytes(2, "big") + width.to_bytes(2, "big")
+    out += bytes([ncomp]) + comps
+    if optimize:
+        return bytes(out)
+    for i in range(ntab):
         for cls, bits, vals in ((0x00, DC_BITS[i], DC_VALS[i]), (0x10, AC_BITS[i], AC_VALS[i])):
             out += b"\xff\xc4" + (19 + len(vals)).to_bytes(2, "big") + bytes([cls | i]) + bytes(bits) + bytes(vals)
-    out += b"\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00"
+    out += b"\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00" if ncomp == 3 else b"\xff\xda\x00\x08\x01\x01\x00\x00\x3f\x00"
     return bytes(out)
 
 
-def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None = None):
-    """[N, H, W, 3] uint8 device tensor → (files [N, capacity] uint8, sizes [N] int64 on the device); frame f's file is
-    files[f, :sizes[f]].  Raises ImgxfError if a file does not fit in `capacity` bytes."""
-    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
-        raise ValueError("jpeg.encode expects a [N, H, W, 3] uint8 tensor")
+HUFF_OVERFLOW = 0xFFFFFFFE          # sizes[f] of imgxf_jpeg_encode_ex_u8: libjpeg's JERR_HUFF_CLEN_OVERFLOW
+
+
+def _check_overflow(lens):
+    if any(v == HUFF_OVERFLOW for v in lens):
+        raise F.ImgxfError(F.ERR_UNSUPPORTED, "an optimal Huffman code would be longer than 32 bits (libjpeg: "
+                           "JERR_HUFF_CLEN_OVERFLOW)", "jpeg.encode")
+
+
+def _frames(frames: torch.Tensor) -> torch.Tensor:
+    """[N, H, W, 3] RGB, [N, H, W, 1] or [N, H, W] grayscale uint8 → a 4-d view.  A 3-d tensor whose last dimension is 3
+    reads as one RGB frame without its batch dimension as much as a grayscale batch 3 pixels wide, so it is refused:
+    pass [1, H, W, 3] or [N, H, 3, 1]."""
+    if frames.dtype == torch.uint8 and frames.dim() == 3:
+        if frames.shape[-1] == 3:
+            raise ValueError("jpeg.encode: a [H, W, 3] / [N, H, 3] tensor is ambiguous; pass [1, H, W, 3] (one RGB frame) "
+                             "or [N, H, 3, 1] (grayscale frames 3 pixels wide)")
+        frames = frames.unsqueeze(-1)
+    if frames.dim() != 4 or frames.shape[-1] not in (1, 3) or frames.dtype != torch.uint8:
+        raise ValueError("jpeg.encode expects a [N, H, W, 3], [N, H, W, 1] or [N, H, W] uint8 tensor")
+    return frames
+
+
+def _capacities(h: int, w: int, ncomp: int, hv) -> tuple:
+    """(first, retry) bytes per file: the first try ~1.33 bytes per coded sample (2·h·w at 4:2:0, as always); the retry
+    holds any stream: 2048 bits per block (the 32-bit offsets' bound), every byte stuffed."""
+    if ncomp == 3 and hv == (2, 2):
+        return 2 * h * w + 4096, 12 * h * w + 4096
+    samples = 1 if ncomp == 1 else 1 + 2 / (hv[0] * hv[1])
+    mw, mh = -(-w // (8 * hv[0])), -(-h // (8 * hv[1]))
+    nblk = (-(-w // 8)) * (-(-h // 8)) if ncomp == 1 else mw * mh * (hv[0] * hv[1] + 2)
+    return int(samples * 4 / 3 * h * w) + 4096, nblk * 512 + 4096
+
+
+def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1, optimize: bool = False):
+    """[N, H, W, 3] (RGB) or [N, H, W, 1] / [N, H, W] (grayscale) uint8 device tensor → (files [N, capacity] uint8, sizes
+    [N] int64 on the device); frame f's file is files[f, :sizes[f]].  sizes[f] is 0xFFFFFFFF when the file does not fit in
+    `capacity` bytes and, with optimize, HUFF_OVERFLOW when its optimal Huffman table would need a code over 32 bits."""
+    frames = _frames(frames)
+    ncomp = frames.shape[-1]
+    hv = sampling(subsampling, ncomp)
+    optimize = bool(optimize)
     if not frames.is_cuda:
         raise F.ImgxfError(F.ERR_NO_DEVICE, "frames must live on the GPU (no CPU fallback)", "jpeg.encode")
     n, h, w, _ = frames.shape
-    hdr = header(w, h, quality)
-    cap = int(capacity) if capacity is not None else 2 * h * w + 4096
+    default = ncomp == 3 and hv == (2, 2) and not optimize        # the 4:2:0 / Annex-K file: imgxf_jpeg_encode_u8
+    hdr = header(w, h, quality) if default else header(w, h, quality, ncomp=ncomp, subsampling=subsampling, optimize=optimize)
+    cap = int(capacity) if capacity is not None else _capacities(h, w, ncomp, hv)[0]
     cap = (cap + 15) & ~15
     files = torch.empty((n, cap), dtype=torch.uint8, device=frames.device)
     sizes = torch.zeros((n,), dtype=torch.int32, device=frames.device)
     if n == 0:
         return files, sizes.to(torch.int64)
-    frames = frames if frames.stride(-1) == 1 and frames.stride(-2) == 3 else frames.contiguous()
+    frames = frames if frames.stride(-1) == 1 and frames.stride(-2) == ncomp else frames.contiguous()
     nbytes = ctypes.c_size_t()
-    F.call("imgxf_jpeg_workspace_bytes", n, h, w, cap, ctypes.byref(nbytes))
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
     view = F.view_of(frames)
-    with torch.cuda.device(frames.device):       # the frames' device, not torch's current one (as ops._launch)
-        F.call("imgxf_jpeg_encode_u8", F.vp(view), ctypes.addressof(tables(quality)), hdr, len(hdr), files.data_ptr(), cap,
-               sizes.data_ptr(), ws.data_ptr(), nbytes.value, torch.cuda.current_stream(frames.device).cuda_stream)
+    stream = torch.cuda.current_stream(frames.device).cuda_stream
+    if default:
+        F.call("imgxf_jpeg_workspace_bytes", n, h, w, cap, ctypes.byref(nbytes))
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
+        with torch.cuda.device(frames.device):   # the frames' device, not torch's current one (as ops._launch)
+            F.call("imgxf_jpeg_encode_u8", F.vp(view), ctypes.addressof(tables(quality)), hdr, len(hdr), files.data_ptr(), cap,
+                   sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
+    else:
+        params = F.JpegEncParams(ncomp, hv[0], hv[1], int(optimize))
+        F.call("imgxf_jpeg_workspace_bytes_ex", ctypes.byref(params), n, h, w, cap, ctypes.byref(nbytes))
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
+        with torch.cuda.device(frames.device):
+            F.call("imgxf_jpeg_encode_ex_u8", F.vp(view), ctypes.byref(params), ctypes.addressof(tables(quality)), hdr, len(hdr),
+                   files.data_ptr(), cap, sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
     return files, sizes.to(torch.int64) & 0xFFFFFFFF
 
 
-def encode(frames: torch.Tensor, quality: int = 75, capacity: int | None = None) -> List[bytes]:
-    """One JPEG file (`bytes`) per frame, equal to Pillow's `Image.fromarray(frame).save(fp, "JPEG", quality=quality)`."""
-    return [bytes(v) for v in encode_views(frames, quality, capacity)]
+def encode(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1,
+           optimize: bool = False) -> List[bytes]:
+    """One JPEG file (`bytes`) per frame, equal to Pillow's `Image.fromarray(frame).save(fp, "JPEG", quality=quality,
+    subsampling=subsampling, optimize=optimize)` (an "L" image for a grayscale frame)."""
+    return [bytes(v) for v in encode_views(frames, quality, capacity, subsampling=subsampling, optimize=optimize)]
 
 
-def encode_views(frames: torch.Tensor, quality: int = 75, capacity: int | None = None) -> List[memoryview]:
+def encode_views(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1,
+                 optimize: bool = False) -> List[memoryview]:
     """`encode` without the last host copy: one memoryview per file into the pinned staging block the single D2H filled
     (valid until they are dropped; `f.write(view)` writes a file straight from it)."""
-    n, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
-    files, sizes = encode_device(frames, quality, capacity)
+    frames = _frames(frames)
+    n, h, w, c = frames.shape
+    files, sizes = encode_device(frames, quality, capacity, subsampling=subsampling, optimize=optimize)
     lens = sizes.cpu().tolist()
+    _check_overflow(lens)
     if any(v == 0xFFFFFFFF for v in lens):
         if capacity is not None:
             raise F.ImgxfError(F.ERR_WORKSPACE, f"a JPEG stream does not fit in capacity={capacity} bytes", "jpeg.encode")
-        files, sizes = encode_device(frames, quality, 12 * h * w + 4096)      # beyond any baseline stream of this size
+        retry = _capacities(h, w, c, sampling(subsampling, c))[1]          # beyond any baseline stream of this size
+        files, sizes = encode_device(frames, quality, retry, subsampling=subsampling, optimize=optimize)
         lens = sizes.cpu().tolist()
+        _check_overflow(lens)
         if any(v == 0xFFFFFFFF for v in lens):
-            raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds 12 bytes per pixel", "jpeg.encode")
+            raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds the largest baseline stream", "jpeg.encode")
     # the files leave the device as ONE copy of sum(sizes) bytes: a device-side gather of the n streams (one torch.cat
     # kernel over views of exactly each file's length) into a packed buffer, then a single D2H into pinned memory.
     # (Round 2 issued one exact-size copy per file: 16 copies of ~0.7 MB cost 3.6 ms against 0.63 ms of encoding.)

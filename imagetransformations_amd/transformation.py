@@ -307,18 +307,36 @@ def plan_transformations(name: str):
 JPEG_ON_DEVICE = os.environ.get("IMGXF_JPEG_DEVICE", "0") == "1"
 
 
-def save_image(img: Image.Image, path: str) -> None:
-    """The reference's `transformed.save(path)` (:161-162).  With `JPEG_ON_DEVICE` (or IMGXF_JPEG_DEVICE=1) an RGB image
-    bound for a *.jpg / *.jpeg file is encoded by the GPU writer (`jpeg.encode`: the file Pillow would write, byte for
-    byte); every other mode / format, and images carrying a comment Pillow would embed, go through Pillow."""
-    if (JPEG_ON_DEVICE and img.mode == "RGB" and path.lower().endswith((".jpg", ".jpeg")) and "comment" not in img.info
-            and min(img.size) > 0):
+JPEG_DEVICE_PARAMS = ("quality", "subsampling", "optimize")     # what the device writer takes (jpeg.encode)
+
+
+def _device_jpeg_values(params) -> bool:
+    """Values the device writer takes as Pillow does: quality an int 1..100, subsampling one of jpeg.SUBSAMPLING.  Pillow
+    also accepts others (quality -1 or a preset name, subsampling 3, "4:1:1" or a bool), which stay with it."""
+    from . import jpeg
+    q, s = params.get("quality", 75), params.get("subsampling", -1)
+    return (isinstance(q, int) and not isinstance(q, bool) and 1 <= q <= 100
+            and isinstance(s, (int, str)) and not isinstance(s, bool) and s in jpeg.SUBSAMPLING)
+
+
+def save_image(img: Image.Image, path: str, **params) -> None:
+    """The reference's `transformed.save(path)` (:161-162), and `img.save(path, **params)`.  With `JPEG_ON_DEVICE` (or
+    IMGXF_JPEG_DEVICE=1) an RGB or "L" image bound for a *.jpg / *.jpeg file, with no parameters beyond quality (1..100) /
+    subsampling (jpeg.SUBSAMPLING) / optimize, is encoded by the GPU writer (`jpeg.encode`: the file Pillow would write, byte for byte);
+    every other mode / format / parameter, and images carrying a comment Pillow would embed, go through Pillow.  Without
+    parameters only RGB images take the device, as before."""
+    device = (JPEG_ON_DEVICE and path.lower().endswith((".jpg", ".jpeg")) and "comment" not in img.info and min(img.size) > 0
+              and set(params) <= set(JPEG_DEVICE_PARAMS) and (img.mode == "RGB" or (img.mode == "L" and params))
+              and _device_jpeg_values(params))
+    if device:
         from . import jpeg
-        data = jpeg.encode(_upload(img)[None])[0]
+        frame = _upload(img)
+        frame = frame[..., None] if frame.dim() == 2 else frame      # "L": [H, W, 1], whatever its width
+        data = jpeg.encode(frame[None], **params)[0]
         with open(path, "wb") as f:
             f.write(data)
     else:
-        img.save(path)
+        img.save(path, **params)
 
 
 DRIVER = os.environ.get("IMGXF_DRIVER", "batched")       # "per-image": apply_all_transformations runs the reference's literal loop

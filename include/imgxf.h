@@ -345,6 +345,40 @@ int imgxf_jpeg_encode_u8(const imgxf_view* src, const imgxf_jpeg_tables* tables,
                          int header_bytes, uint8_t* out, size_t out_frame_stride, uint32_t* sizes,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* The writer's options: Pillow's `save(fp, "JPEG", quality=q, subsampling=s, optimize=o)` for RGB (ncomp 3, a c == 3 view)
+ * and "L" frames (ncomp 1, c == 1), bit-identical to libjpeg-turbo.  Luma sampling h_samp x v_samp: 1x1 (4:4:4, MCU 8x8:
+ * Y Cb Cr; jcsample.c fullsize_downsample), 2x1 (4:2:2, MCU 16x8: Y Y Cb Cr; h2v1_downsample, bias 0,1 along a row, dummy
+ * luma blocks when ceil(w/8) is odd), 2x2 (4:2:0, the file of imgxf_jpeg_encode_u8).  A grayscale frame is one
+ * non-interleaved component, one block per MCU whatever its sampling: h_samp / v_samp then only reach the SOF the caller
+ * writes.  Rows / columns past the image repeat the last one (expand_right_edge, jcprepct.c); dummy blocks carry zero AC
+ * and the DC of the block before them (jccoefct.c).
+ * optimize = 1: per frame, the symbol counts of every block (jchuff.c htest_one_block, dummy blocks included; table 1 shared
+ * by Cb and Cr), jpeg_gen_optimal_table (code point 256 reserved, ties to the larger symbol, 16-bit limit) and
+ * jpeg_make_c_derived_tbl; the device then writes the frame's DHT segments (DC0, AC0[, DC1, AC1]) and SOS after `header`,
+ * which is then SOI .. SOF only, and only the quantisers of `tables` are read.  Without optimize `header` is SOI .. SOS
+ * for the Huffman tables in `tables`.  4:2:0 without optimize is imgxf_jpeg_encode_u8 itself.
+ * Errors as imgxf_jpeg_encode_u8, plus: c != ncomp -> IMGXF_ERR_UNSUPPORTED; ncomp, sampling or optimize out of range, a
+ * quantiser of a used table outside 1..255, header_bytes outside 2..1024 -> IMGXF_ERR_ARG.  Bit offsets are 32-bit: at most
+ * 2097143 blocks per frame — ceil(w/16)*ceil(h/16) < 349525 MCUs at 4:2:0 (6 blocks each), < 524287 at 4:2:2 (16x8, 4
+ * blocks), ceil(w/8)*ceil(h/8) < 699047 at 4:4:4 (3 blocks: twice the chroma blocks of 4:2:0) and < 2097143 grayscale;
+ * past it IMGXF_ERR_SHAPE.  With optimize, a frame whose optimal Huffman table would need a code longer than 32 bits
+ * (libjpeg's JERR_HUFF_CLEN_OVERFLOW: ~15 M symbols in Fibonacci-shaped counts) gets sizes[f] = 0xFFFFFFFE and no file. */
+typedef struct imgxf_jpeg_enc_params {
+    int32_t ncomp;              /* 1 (grayscale) or 3 (YCbCr from RGB) */
+    int32_t h_samp, v_samp;     /* luma sampling: 1x1, 2x1 or 2x2 */
+    int32_t optimize;           /* 0: the Huffman tables of `tables`; 1: per-frame optimal tables */
+} imgxf_jpeg_enc_params;
+int imgxf_jpeg_workspace_bytes_ex(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t out_frame_stride,
+                                  size_t* bytes);
+/* The optimize path's table stage alone (jchuff.c jpeg_gen_optimal_table + jpeg_make_c_derived_tbl), for n frames of
+ * four tables each (DC0, AC0, DC1, AC1).  Device pointers: counts uint32[n][4][256] (symbol counts); dht [n][4] records of
+ * 276 bytes — uint32 nvals (0xFFFFFFFF: a code would exceed 32 bits), BITS[16], HUFFVAL[256]; codes uint32[n][544] —
+ * code | length << 16 of DC tables 0, 1 (16 symbols each), then AC tables 0, 1 (256 each). */
+int imgxf_jpeg_optimal_tables(const uint32_t* counts, int n, uint8_t* dht, uint32_t* codes, void* stream);
+int imgxf_jpeg_encode_ex_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
+                            const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
+                            uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mask stage of apply_background_change  transformation.py:340-341 -----------------*/
 /* 256-bin histogram per frame of a c==1 view into hist[n][256] (uint32, device, zeroed by the call). */
 int imgxf_histogram_u8(const imgxf_view* src, uint32_t* hist, void* stream);

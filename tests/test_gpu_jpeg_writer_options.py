@@ -1,0 +1,226 @@
+"""GPU: the device writer's options (`jpeg.encode(..., subsampling=, optimize=)`, grayscale frames) — every file equals
+the bytes Pillow writes with the same options: a grid of shapes × qualities × subsampling spellings × RGB / "L" ×
+optimize, 4K frames of every layout, the reference JPEGs re-saved, batches whose frames get different optimal tables,
+strided views, the capacity retry; the C ABI's argument checks; `save_image` with parameters; the default call still
+going through imgxf_jpeg_encode_u8."""
+import ctypes
+import glob
+import io
+import os
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image, ImageFile
+
+from imagetransformations_amd import _ffi as F, jpeg
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (1, 17), (7, 9), (8, 8), (9, 16), (17, 33), (37, 53), (64, 48), (375, 500), (500, 333)]   # (h, w)
+QUALITIES = (1, 50, 75, 95, 100)
+SUBSAMPLINGS = (-1, 0, 1, 2, "4:4:4", "4:2:2", "4:2:0")
+REF = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "reference_outputs", "*.JPEG")))
+
+
+def pil_bytes(a, **params):
+    """Pillow's file.  With optimize, Pillow's encoder buffer must hold the whole file (ImageFile.MAXBLOCK or 1-2 bytes
+    per pixel, "Suspension not allowed here" past it): noise at quality 100 needs more, and the buffer size does not
+    change the bytes."""
+    b = io.BytesIO()
+    keep = ImageFile.MAXBLOCK
+    ImageFile.MAXBLOCK = max(keep, 8 * a.shape[0] * a.shape[1] + 65536)
+    try:
+        Image.fromarray(a).save(b, "JPEG", **params)
+    finally:
+        ImageFile.MAXBLOCK = keep
+    return b.getvalue()
+
+
+def photo(seed, h, w):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = 128 + 70 * np.sin(xx / 9.0 + seed) + 50 * np.cos(yy / 7.0)
+    return np.clip(base[..., None] + rng.normal(0, 12, (h, w, 3)) + np.array([10, -20, 30]), 0, 255).astype(np.uint8)
+
+
+def gray_of(a):
+    return np.asarray(Image.fromarray(a).convert("L"))
+
+
+def check(frames, **params):
+    """frames: list of HWC / HW uint8 arrays of one shape → device files == Pillow's"""
+    t = torch.from_numpy(np.stack(frames)).cuda()
+    got = jpeg.encode(t, **params)
+    for i, a in enumerate(frames):
+        assert got[i] == pil_bytes(a, **params), (i, a.shape, params)
+    return got
+
+
+@pytest.mark.parametrize("optimize", [False, True], ids=["std", "opt"])
+@pytest.mark.parametrize("gray", [False, True], ids=["rgb", "gray"])
+@pytest.mark.parametrize("h,w", SHAPES, ids=lambda v: str(v))
+def test_grid(h, w, gray, optimize):
+    rng = np.random.default_rng(h * 1000 + w)
+    for q in QUALITIES:
+        for s in SUBSAMPLINGS:
+            frames = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8), photo(q, h, w), np.full((h, w, 3), q, np.uint8)]
+            check([gray_of(a) for a in frames] if gray else frames, quality=q, subsampling=s, optimize=optimize)
+
+
+@pytest.mark.parametrize("optimize", [False, True], ids=["std", "opt"])
+@pytest.mark.parametrize("layout", ["4:4:4", "4:2:2", "4:2:0", "gray"])
+def test_4k(layout, optimize):
+    a = photo(5, 2160, 3840)
+    if layout == "gray":
+        check([gray_of(a)], quality=90, optimize=optimize)
+    else:
+        check([a], quality=90, subsampling=layout, optimize=optimize)
+
+
+OPTION_SETS = [dict(quality=95, subsampling=0), dict(quality=75, optimize=True), dict(quality=90, subsampling=1, optimize=True),
+               dict(quality=60, subsampling=0, optimize=True), dict(quality=85, subsampling="4:2:2")]
+
+
+@pytest.mark.parametrize("path", REF, ids=lambda p: os.path.basename(p)[:40])
+def test_reference_resaved(path):
+    a = np.asarray(Image.open(path).convert("RGB"))
+    for params in OPTION_SETS:
+        check([a], **params)
+        check([gray_of(a)], **params)
+
+
+def test_batch_frames_get_their_own_tables():
+    h, w = 48, 80
+    rng = np.random.default_rng(4)
+    frames = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8), photo(1, h, w), np.full((h, w, 3), 200, np.uint8),
+              np.repeat(np.arange(w, dtype=np.uint8)[None, :, None], h, 0).repeat(3, 2) * 3]
+    for s in (0, 1, 2):
+        got = check(frames, quality=80, subsampling=s, optimize=True)
+        dhts = {f[f.index(b"\xff\xc4"):f.index(b"\xff\xda")] for f in got}
+        assert len(dhts) == len(frames)
+
+
+def test_strided_and_unaligned_views():
+    big = torch.from_numpy(photo(2, 70, 90)).cuda()
+    view = big[3:60, 5:88]                                        # row stride 270 bytes, base not 16-byte aligned
+    a = view.cpu().numpy()
+    for params in OPTION_SETS:
+        assert jpeg.encode(view[None], **params)[0] == pil_bytes(a, **params)
+    flat = torch.empty(37 * 53 * 3 + 1, dtype=torch.uint8, device="cuda")[1:].view(37, 53, 3)
+    flat.copy_(torch.from_numpy(photo(3, 37, 53)))
+    for params in OPTION_SETS:
+        assert jpeg.encode(flat[None], **params)[0] == pil_bytes(flat.cpu().numpy(), **params)
+    g = torch.from_numpy(gray_of(photo(4, 600, 700))).cuda()[10:590, 7:650]     # 643 wide: the slow staging path
+    assert jpeg.encode(g[None], quality=70, optimize=True)[0] == pil_bytes(g.cpu().numpy(), quality=70, optimize=True)
+
+
+def test_gray_input_shapes():
+    a = np.stack([gray_of(photo(i, 33, 47)) for i in range(3)])
+    t = torch.from_numpy(a).cuda()
+    for params in ({}, dict(quality=95), dict(optimize=True), dict(subsampling=2, quality=40)):
+        want = [pil_bytes(x, **params) for x in a]
+        assert jpeg.encode(t, **params) == want
+        assert jpeg.encode(t[..., None], **params) == want
+
+
+def test_capacity_retry_444_q100(monkeypatch):
+    """Noise at quality 100 overflows the first capacity (4:4:4: 4·h·w + 4096 bytes, ~4.14 bytes per pixel here;
+    grayscale: 1.33·h·w + 4096, ~1.59): encode re-encodes once with room for any stream."""
+    h, w = 400, 500
+    rng = np.random.default_rng(8)
+    rgb = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(2)]
+    gray = [rng.integers(0, 256, (h, w), dtype=np.uint8) for _ in range(2)]
+    calls = []
+    real = jpeg.encode_device
+    monkeypatch.setattr(jpeg, "encode_device", lambda *a, **k: calls.append(a[2] if len(a) > 2 else None) or real(*a, **k))
+    for frames, params in ((rgb, dict(subsampling=0)), (gray, {})):
+        want = [pil_bytes(a, quality=100, **params) for a in frames]
+        calls.clear()
+        assert jpeg.encode(torch.from_numpy(np.stack(frames)).cuda(), 100, **params) == want
+        assert len(calls) == 2 and calls[0] is None and calls[1] > max(map(len, want)), params    # the retry happened
+    t = torch.from_numpy(np.stack(rgb)).cuda()
+    with pytest.raises(F.ImgxfError):
+        jpeg.encode(t, 100, 4 * h * w + 4096, subsampling=0)           # an explicit capacity is not retried
+
+
+def test_c_abi_argument_checks():
+    t3 = torch.zeros((1, 16, 16, 3), dtype=torch.uint8, device="cuda")
+    t1 = torch.zeros((1, 16, 16, 1), dtype=torch.uint8, device="cuda")
+    out = torch.zeros((8192,), dtype=torch.uint8, device="cuda")
+    sizes = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    tabs = jpeg.tables(75)
+
+    def need(p):
+        b = ctypes.c_size_t()
+        F.call("imgxf_jpeg_workspace_bytes_ex", ctypes.byref(p), 1, 16, 16, 8192, ctypes.byref(b))
+        return b.value
+
+    ws = torch.zeros((1 << 20,), dtype=torch.uint8, device="cuda")
+
+    def run(view, p, tables=tabs, header=None, hlen=None, wsb=None):
+        header = header if header is not None else jpeg.header(16, 16, 75, ncomp=p.ncomp, subsampling=0, optimize=bool(p.optimize))
+        return F.lib.imgxf_jpeg_encode_ex_u8(F.vp(F.view_of(view)), ctypes.byref(p), ctypes.addressof(tables), header,
+                                             len(header) if hlen is None else hlen, out.data_ptr(), 8192, sizes.data_ptr(),
+                                             ws.data_ptr(), need(p) if wsb is None else wsb, None)
+
+    p3, p1 = F.JpegEncParams(3, 1, 1, 1), F.JpegEncParams(1, 1, 1, 0)
+    assert run(t3, p3) == F.OK and run(t1, p1) == F.OK
+    torch.cuda.synchronize()
+    assert out[:sizes.item()].cpu().numpy().tobytes() == pil_bytes(np.zeros((16, 16), np.uint8), subsampling=0)
+    assert run(t1, p3) == F.ERR_UNSUPPORTED and run(t3, p1) == F.ERR_UNSUPPORTED          # c must agree with ncomp
+    for bad in (F.JpegEncParams(3, 1, 2, 0), F.JpegEncParams(3, 4, 1, 0), F.JpegEncParams(2, 1, 1, 0),
+                F.JpegEncParams(3, 1, 1, 2)):
+        assert run(t3, bad, header=jpeg.header(16, 16), wsb=ws.numel()) == F.ERR_ARG
+        b = ctypes.c_size_t()
+        assert F.lib.imgxf_jpeg_workspace_bytes_ex(ctypes.byref(bad), 1, 16, 16, 8192, ctypes.byref(b)) == F.ERR_ARG
+    zero = F.JpegTables.from_buffer_copy(tabs)
+    zero.quant[1][5] = 0
+    assert run(t3, p3, tables=zero) == F.ERR_ARG
+    assert run(t1, p1, tables=zero) == F.OK                       # grayscale reads table 0 only
+    assert run(t3, p3, wsb=need(p3) - 1) == F.ERR_WORKSPACE
+    assert run(t3, p3, header=b"\xff\xd8" * 600) == F.ERR_ARG     # header over 1024 bytes
+    assert run(t3, p3, hlen=1) == F.ERR_ARG
+    torch.cuda.synchronize()
+
+
+def test_save_image_params(tmp_path, monkeypatch):
+    from imagetransformations_amd import transformation as T
+    monkeypatch.setattr(T, "JPEG_ON_DEVICE", True)
+    img = Image.fromarray(photo(6, 45, 70))
+    for im in (img, img.convert("L")):
+        for params in ({}, dict(quality=95, subsampling=0), dict(optimize=True), dict(quality=60, subsampling="4:2:2", optimize=True),
+                       dict(quality=80, dpi=(300, 300)), dict(progressive=True)):
+            T.save_image(im, str(tmp_path / "d.jpg"), **params)
+            im.save(str(tmp_path / "p.jpg"), **params)
+            assert (tmp_path / "d.jpg").read_bytes() == (tmp_path / "p.jpg").read_bytes(), (im.mode, params)
+    T.save_image(img, str(tmp_path / "x.png"), compress_level=1)
+    assert np.array_equal(np.asarray(Image.open(tmp_path / "x.png")), np.asarray(img))
+
+
+def test_save_image_routing(tmp_path, monkeypatch):
+    from imagetransformations_amd import transformation as T
+    monkeypatch.setattr(T, "JPEG_ON_DEVICE", True)
+    calls = []
+    real = jpeg.encode
+    monkeypatch.setattr(jpeg, "encode", lambda *a, **k: calls.append(k) or real(*a, **k))
+    img = Image.fromarray(photo(7, 20, 30))
+    T.save_image(img, str(tmp_path / "a.jpg"), quality=90, subsampling=0)
+    T.save_image(img.convert("L"), str(tmp_path / "b.jpg"), optimize=True)
+    T.save_image(img, str(tmp_path / "c.jpg"), quality=90, dpi=(72, 72))            # a parameter only Pillow takes
+    T.save_image(img.convert("L"), str(tmp_path / "d.jpg"))                         # "L" without parameters: Pillow, as before
+    assert calls == [dict(quality=90, subsampling=0), dict(optimize=True)]
+
+
+def test_default_call_uses_the_420_writer(monkeypatch):
+    names = []
+    real = F.call
+    monkeypatch.setattr(F, "call", lambda name, *a: names.append(name) or real(name, *a))
+    a = photo(8, 40, 56)
+    t = torch.from_numpy(a).cuda()[None]
+    assert jpeg.encode(t)[0] == pil_bytes(a)
+    assert jpeg.encode(t, 90)[0] == pil_bytes(a, quality=90)
+    assert names == ["imgxf_jpeg_workspace_bytes", "imgxf_jpeg_encode_u8"] * 2
+    names.clear()
+    assert jpeg.encode(t, 90, subsampling=0)[0] == pil_bytes(a, quality=90, subsampling=0)
+    assert names == ["imgxf_jpeg_workspace_bytes_ex", "imgxf_jpeg_encode_ex_u8"]
