@@ -104,6 +104,9 @@ SIGNATURES = {
     "imgxf_jpeg_optimal_tables": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "imgxf_jpeg_encode_ex_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p],
+    "imgxf_jpeg_workspace_bytes_prog": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_encode_prog_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p],
     "imgxf_np_accept": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "imgxf_np_normals_f32": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],

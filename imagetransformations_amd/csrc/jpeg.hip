@@ -691,6 +691,7 @@ static bool quant_entry(u32 qv, u32* m, u32* halfp) {
 }
 
 #include "jpeg_encode_ext.inc"
+#include "jpeg_encode_prog.inc"
 
 } // namespace imgxf
 
@@ -880,5 +881,106 @@ IMGXF_API int imgxf_jpeg_optimal_tables(const uint32_t* counts, int n, uint8_t* 
     if (n == 0) return IMGXF_OK;
     hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3((unsigned)JSLOTS, (unsigned)n), dim3(256), 0, (hipStream_t)stream, counts,
                        (JpegHuff*)codes, (JpegDht*)dht);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_workspace_bytes_prog(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t out_frame_stride,
+                                              size_t* bytes) {
+    if (!bytes || !params) return IMGXF_ERR_NULL;
+    imgxf_jpeg_enc_params p = *params;
+    p.optimize = 0;                                            // ignored: progressive files always carry optimal tables
+    const int lay = enc_layout(&p);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
+    *bytes = jpeg_layout_prog(lay, n, h, w, out_frame_stride).total;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_jpeg_encode_prog_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
+                                        const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
+                                        uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+    IMGXF_CHECK(check_view(src));
+    if (!params || !tables || !header || !out || !sizes) return IMGXF_ERR_NULL;
+    imgxf_jpeg_enc_params p = *params;
+    p.optimize = 0;
+    const int lay = enc_layout(&p);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    if (src->c != p.ncomp) return IMGXF_ERR_UNSUPPORTED;
+    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
+    if (src->n == 0) return IMGXF_OK;
+    if (empty_view(src)) return IMGXF_ERR_SHAPE;
+    if (src->n > 65535) return IMGXF_ERR_SHAPE;
+    if (out_frame_stride < (size_t)header_bytes + 2 || out_frame_stride > ((size_t)1 << 31)) return IMGXF_ERR_ARG;
+    const JpegLayoutProg P = jpeg_layout_prog(lay, src->n, src->h, src->w, out_frame_stride);
+    const JpegLayoutEx& X = P.X;
+    const JpegLayout& L = X.L;
+    if (!workspace || workspace_bytes < P.total || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
+    // bit offsets are 32-bit: no block takes more than 2048 bits in one scan (the widest, a first scan over 1..63 at
+    // Al = 1: 63 symbols of <= 16 + 10 bits, 3 ZRLs, one EOBRUN of 16 + 14 bits)
+    if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;
+    const int ntab = p.ncomp == 1 ? 1 : 2;
+    JpegQuant q;
+    memset(&q, 0, sizeof(q));
+    for (int t = 0; t < ntab; ++t)
+        for (int i = 0; i < 64; ++i) {
+            const u32 qv = tables->quant[t][i];
+            if (qv < 1 || qv > 255 || !quant_entry(qv, &q.m[t][i], &q.half[t][i])) return IMGXF_ERR_ARG;
+        }
+    for (int t = 0; t < 2; ++t)                                // (the transform's AC bit counts are not used here)
+        for (int i = 0; i < 256; ++i) q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));
+    JpegHeader hd;
+    memset(&hd, 0, sizeof(hd));
+    memcpy(hd.b, header, (size_t)header_bytes);
+    hd.len = header_bytes;
+    const View s = make_view(src);
+    hipStream_t st = (hipStream_t)stream;
+    u8* ws = (u8*)workspace;
+    int16_t* coef = (int16_t*)(ws + L.off_coef);
+    int16_t* dcs = (int16_t*)(ws + L.off_dcs);
+    uint16_t* acb = (uint16_t*)(ws + L.off_acb);
+    const int64_t coef_fs = (int64_t)((L.nblk + 63) / 64) * 64 * 64;
+    switch (lay) {
+    case JL420:
+        hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((L.mw + JM - 1) / JM), (unsigned)L.mh, (unsigned)s.n), dim3(JT), 0, st,
+                           s, coef, coef_fs, dcs, acb, L.nblk, L.mw, L.bw, L.bh, q);
+        break;
+    case JL422: launch_transform_ex<JL422>(s, coef, coef_fs, dcs, acb, L, q, st); break;
+    case JL444: launch_transform_ex<JL444>(s, coef, coef_fs, dcs, acb, L, q, st); break;
+    default: launch_transform_ex<JLGRAY>(s, coef, coef_fs, dcs, acb, L, q, st); break;
+    }
+    JpProgArgs a;
+    a.coef = coef;
+    a.coef_fs = coef_fs;
+    a.dcs = dcs;
+    a.g = {L.mw, L.mh, L.bw, L.bh, L.nblk};
+    a.sym = (u32*)(ws + X.off_sym);
+    a.flags = (u32*)(ws + P.off_flags);
+    a.nbe = (u32*)(ws + P.off_nbe);
+    a.runlen = (u32*)(ws + P.off_runlen);
+    a.lens = (u32*)(ws + L.off_lens);
+    a.part = (u32*)(ws + L.off_part);
+    a.tot_bits = (u32*)(ws + L.off_tot);
+    a.tot_ff = a.tot_bits + s.n;
+    a.pos = (u32*)(ws + P.off_pos);
+    a.tot_be = a.pos + (size_t)(JP_MAXSCANS + 1) * s.n;
+    a.ustream = (u32*)(ws + L.off_stream);
+    a.cnt = (u32*)(ws + L.off_cnt);
+    a.sizes = sizes;
+    a.fh = (JpegHuff*)(ws + X.off_fh);
+    a.dht = (JpegDht*)(ws + X.off_dht);
+    a.L = &L;
+    a.out = out;
+    a.out_fs = (int64_t)out_frame_stride;
+    a.n = s.n;
+    a.nslots = ntab * 2;
+    a.hd = &hd;
+    int rc;
+    switch (lay) {
+    case JL420: rc = launch_prog<JL420>(a, p.ncomp, st); break;
+    case JL422: rc = launch_prog<JL422>(a, p.ncomp, st); break;
+    case JL444: rc = launch_prog<JL444>(a, p.ncomp, st); break;
+    default: rc = launch_prog<JLGRAY>(a, p.ncomp, st); break;
+    }
+    if (rc != IMGXF_OK) return rc;
     return launch_status();
 }

@@ -81,10 +81,12 @@ def sampling(subsampling=-1, ncomp: int = 3):
 
 
 @lru_cache(maxsize=64)
-def header(width: int, height: int, quality: int = 75, *, ncomp: int = 3, subsampling=-1, optimize: bool = False) -> bytes:
+def header(width: int, height: int, quality: int = 75, *, ncomp: int = 3, subsampling=-1, optimize: bool = False,
+           progressive: bool = False) -> bytes:
     """SOI, APP0 (JFIF 1.01, no density), DQT ×2 (×1 grayscale), SOF0 (Y h×v, Cb / Cr 1×1), DHT ×4 (×2 grayscale), SOS —
     jcmarker.c's order.  With `optimize` the file's Huffman tables are the frame's own: the prefix ends with SOF and the
-    device writes DHT and SOS (imgxf_jpeg_encode_ex_u8)."""
+    device writes DHT and SOS (imgxf_jpeg_encode_ex_u8).  With `progressive` the prefix is SOI .. SOF2 and the device
+    writes every scan's DHT and SOS (imgxf_jpeg_encode_prog_u8)."""
     if not (0 < width < 65536 and 0 < height < 65536):
         raise ValueError("JPEG dimensions must be 1..65535")
     if ncomp not in (1, 3):
@@ -95,9 +97,9 @@ def header(width: int, height: int, quality: int = 75, *, ncomp: int = 3, subsam
     for i, qt in enumerate(quant_tables(quality)[:ntab]):
         out += b"\xff\xdb\x00\x43" + bytes([i]) + bytes(qt[z] for z in ZIGZAG)
     comps = bytes([1, (hs << 4) | vs, 0]) + (b"\x02\x11\x01\x03\x11\x01" if ncomp == 3 else b"")
-    out += b"\xff\xc0" + (8 + len(comps)).to_bytes(2, "big") + b"\x08" + height.to_bytes(2, "big") + width.to_bytes(2, "big")
+    out += (b"\xff\xc2" if progressive else b"\xff\xc0") + (8 + len(comps)).to_bytes(2, "big") + b"\x08" + height.to_bytes(2, "big") + width.to_bytes(2, "big")
     out += bytes([ncomp]) + comps
-    if optimize:
+    if optimize or progressive:
         return bytes(out)
     for i in range(ntab):
         for cls, bits, vals in ((0x00, DC_BITS[i], DC_VALS[i]), (0x10, AC_BITS[i], AC_VALS[i])):
@@ -129,31 +131,41 @@ def _frames(frames: torch.Tensor) -> torch.Tensor:
     return frames
 
 
-def _capacities(h: int, w: int, ncomp: int, hv) -> tuple:
+def _capacities(h: int, w: int, ncomp: int, hv, progressive: bool = False) -> tuple:
     """(first, retry) bytes per file: the first try ~1.33 bytes per coded sample (2·h·w at 4:2:0, as always); the retry
-    holds any stream: 2048 bits per block (the 32-bit offsets' bound), every byte stuffed."""
-    if ncomp == 3 and hv == (2, 2):
-        return 2 * h * w + 4096, 12 * h * w + 4096
+    holds any stream: 2048 bits per block (the 32-bit offsets' bound), every byte stuffed.
+    Progressive retry: a block takes at most 4072 bits over all its scans — luma: DC first 16 + 11, AC 1..5 at Al 2
+    5·(16 + 9) + 16 + 14 (one EOBRUN symbol and its bits), AC 6..63 at Al 2 58·(16 + 9) + 3·16 + 30, two refinements of
+    63·(16 + 1) + 3·16 + 30 each (every coefficient is either a new symbol with its sign or one correction bit), DC
+    refinement 1; chroma less — so 509 bytes, 1018 stuffed, plus per scan one padding byte and its DHT + SOS (< 600
+    bytes; 10 scans and the SOI .. SOF2 prefix stay under 8192)."""
     samples = 1 if ncomp == 1 else 1 + 2 / (hv[0] * hv[1])
     mw, mh = -(-w // (8 * hv[0])), -(-h // (8 * hv[1]))
     nblk = (-(-w // 8)) * (-(-h // 8)) if ncomp == 1 else mw * mh * (hv[0] * hv[1] + 2)
+    if progressive:
+        return int(samples * 4 / 3 * h * w) + 8192, nblk * 1024 + 8192
+    if ncomp == 3 and hv == (2, 2):
+        return 2 * h * w + 4096, 12 * h * w + 4096
     return int(samples * 4 / 3 * h * w) + 4096, nblk * 512 + 4096
 
 
-def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1, optimize: bool = False):
+def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1, optimize: bool = False,
+                  progressive: bool = False):
     """[N, H, W, 3] (RGB) or [N, H, W, 1] / [N, H, W] (grayscale) uint8 device tensor → (files [N, capacity] uint8, sizes
     [N] int64 on the device); frame f's file is files[f, :sizes[f]].  sizes[f] is 0xFFFFFFFF when the file does not fit in
-    `capacity` bytes and, with optimize, HUFF_OVERFLOW when its optimal Huffman table would need a code over 32 bits."""
+    `capacity` bytes and, with optimize or progressive, HUFF_OVERFLOW when an optimal Huffman table would need a code over
+    32 bits.  `progressive` writes libjpeg's simple progression with optimal tables per scan (`optimize` is then moot)."""
     frames = _frames(frames)
     ncomp = frames.shape[-1]
     hv = sampling(subsampling, ncomp)
-    optimize = bool(optimize)
+    optimize, progressive = bool(optimize), bool(progressive)
     if not frames.is_cuda:
         raise F.ImgxfError(F.ERR_NO_DEVICE, "frames must live on the GPU (no CPU fallback)", "jpeg.encode")
     n, h, w, _ = frames.shape
-    default = ncomp == 3 and hv == (2, 2) and not optimize        # the 4:2:0 / Annex-K file: imgxf_jpeg_encode_u8
-    hdr = header(w, h, quality) if default else header(w, h, quality, ncomp=ncomp, subsampling=subsampling, optimize=optimize)
-    cap = int(capacity) if capacity is not None else _capacities(h, w, ncomp, hv)[0]
+    default = ncomp == 3 and hv == (2, 2) and not optimize and not progressive   # the 4:2:0 / Annex-K file: imgxf_jpeg_encode_u8
+    hdr = header(w, h, quality) if default else header(w, h, quality, ncomp=ncomp, subsampling=subsampling, optimize=optimize,
+                                                       progressive=progressive)
+    cap = int(capacity) if capacity is not None else _capacities(h, w, ncomp, hv, progressive)[0]
     cap = (cap + 15) & ~15
     files = torch.empty((n, cap), dtype=torch.uint8, device=frames.device)
     sizes = torch.zeros((n,), dtype=torch.int32, device=frames.device)
@@ -169,6 +181,13 @@ def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None 
         with torch.cuda.device(frames.device):   # the frames' device, not torch's current one (as ops._launch)
             F.call("imgxf_jpeg_encode_u8", F.vp(view), ctypes.addressof(tables(quality)), hdr, len(hdr), files.data_ptr(), cap,
                    sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
+    elif progressive:
+        params = F.JpegEncParams(ncomp, hv[0], hv[1], 1)
+        F.call("imgxf_jpeg_workspace_bytes_prog", ctypes.byref(params), n, h, w, cap, ctypes.byref(nbytes))
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
+        with torch.cuda.device(frames.device):
+            F.call("imgxf_jpeg_encode_prog_u8", F.vp(view), ctypes.byref(params), ctypes.addressof(tables(quality)), hdr, len(hdr),
+                   files.data_ptr(), cap, sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
     else:
         params = F.JpegEncParams(ncomp, hv[0], hv[1], int(optimize))
         F.call("imgxf_jpeg_workspace_bytes_ex", ctypes.byref(params), n, h, w, cap, ctypes.byref(nbytes))
@@ -180,26 +199,27 @@ def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None 
 
 
 def encode(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1,
-           optimize: bool = False) -> List[bytes]:
+           optimize: bool = False, progressive: bool = False) -> List[bytes]:
     """One JPEG file (`bytes`) per frame, equal to Pillow's `Image.fromarray(frame).save(fp, "JPEG", quality=quality,
-    subsampling=subsampling, optimize=optimize)` (an "L" image for a grayscale frame)."""
-    return [bytes(v) for v in encode_views(frames, quality, capacity, subsampling=subsampling, optimize=optimize)]
+    subsampling=subsampling, optimize=optimize, progressive=progressive)` (an "L" image for a grayscale frame)."""
+    return [bytes(v) for v in encode_views(frames, quality, capacity, subsampling=subsampling, optimize=optimize,
+                                           progressive=progressive)]
 
 
 def encode_views(frames: torch.Tensor, quality: int = 75, capacity: int | None = None, *, subsampling=-1,
-                 optimize: bool = False) -> List[memoryview]:
+                 optimize: bool = False, progressive: bool = False) -> List[memoryview]:
     """`encode` without the last host copy: one memoryview per file into the pinned staging block the single D2H filled
     (valid until they are dropped; `f.write(view)` writes a file straight from it)."""
     frames = _frames(frames)
     n, h, w, c = frames.shape
-    files, sizes = encode_device(frames, quality, capacity, subsampling=subsampling, optimize=optimize)
+    files, sizes = encode_device(frames, quality, capacity, subsampling=subsampling, optimize=optimize, progressive=progressive)
     lens = sizes.cpu().tolist()
     _check_overflow(lens)
     if any(v == 0xFFFFFFFF for v in lens):
         if capacity is not None:
             raise F.ImgxfError(F.ERR_WORKSPACE, f"a JPEG stream does not fit in capacity={capacity} bytes", "jpeg.encode")
-        retry = _capacities(h, w, c, sampling(subsampling, c))[1]          # beyond any baseline stream of this size
-        files, sizes = encode_device(frames, quality, retry, subsampling=subsampling, optimize=optimize)
+        retry = _capacities(h, w, c, sampling(subsampling, c), bool(progressive))[1]   # beyond any stream of this size
+        files, sizes = encode_device(frames, quality, retry, subsampling=subsampling, optimize=optimize, progressive=progressive)
         lens = sizes.cpu().tolist()
         _check_overflow(lens)
         if any(v == 0xFFFFFFFF for v in lens):

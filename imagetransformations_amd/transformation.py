@@ -307,7 +307,7 @@ def plan_transformations(name: str):
 JPEG_ON_DEVICE = os.environ.get("IMGXF_JPEG_DEVICE", "0") == "1"
 
 
-JPEG_DEVICE_PARAMS = ("quality", "subsampling", "optimize")     # what the device writer takes (jpeg.encode)
+JPEG_DEVICE_PARAMS = ("quality", "subsampling", "optimize", "progressive", "progression")   # what the device writer takes
 
 
 def _device_jpeg_values(params) -> bool:
@@ -316,13 +316,14 @@ def _device_jpeg_values(params) -> bool:
     from . import jpeg
     q, s = params.get("quality", 75), params.get("subsampling", -1)
     return (isinstance(q, int) and not isinstance(q, bool) and 1 <= q <= 100
-            and isinstance(s, (int, str)) and not isinstance(s, bool) and s in jpeg.SUBSAMPLING)
+            and isinstance(s, (int, str)) and not isinstance(s, bool) and s in jpeg.SUBSAMPLING
+            and all(isinstance(params.get(k, False), bool) for k in ("progressive", "progression")))
 
 
 def save_image(img: Image.Image, path: str, **params) -> None:
     """The reference's `transformed.save(path)` (:161-162), and `img.save(path, **params)`.  With `JPEG_ON_DEVICE` (or
     IMGXF_JPEG_DEVICE=1) an RGB or "L" image bound for a *.jpg / *.jpeg file, with no parameters beyond quality (1..100) /
-    subsampling (jpeg.SUBSAMPLING) / optimize, is encoded by the GPU writer (`jpeg.encode`: the file Pillow would write, byte for byte);
+    subsampling (jpeg.SUBSAMPLING) / optimize / progressive or progression (bools), is encoded by the GPU writer (`jpeg.encode`: the file Pillow would write, byte for byte);
     every other mode / format / parameter, and images carrying a comment Pillow would embed, go through Pillow.  Without
     parameters only RGB images take the device, as before."""
     device = (JPEG_ON_DEVICE and path.lower().endswith((".jpg", ".jpeg")) and "comment" not in img.info and min(img.size) > 0
@@ -332,7 +333,10 @@ def save_image(img: Image.Image, path: str, **params) -> None:
         from . import jpeg
         frame = _upload(img)
         frame = frame[..., None] if frame.dim() == 2 else frame      # "L": [H, W, 1], whatever its width
-        data = jpeg.encode(frame[None], **params)[0]
+        kw = {k: v for k, v in params.items() if k not in ("progressive", "progression")}
+        if params.get("progressive", False) or params.get("progression", False):   # Pillow: either name
+            kw["progressive"] = True
+        data = jpeg.encode(frame[None], **kw)[0]
         with open(path, "wb") as f:
             f.write(data)
     else:

@@ -379,6 +379,24 @@ int imgxf_jpeg_encode_ex_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* 
                             const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
                             uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Progressive files: Pillow's `save(fp, "JPEG", progressive=True, quality=q, subsampling=s)` for the frames and layouts of
+ * imgxf_jpeg_encode_ex_u8, bit-identical to libjpeg-turbo.  The coefficients are the sequential writer's; the file is
+ * jcparam.c jpeg_simple_progression (colour, 10 scans: Y Cb Cr DC 0-0 Al 1; Y 1-5 Al 2; Cr, Cb 1-63 Al 1; Y 6-63 Al 2;
+ * Y 1-63 Ah 2 Al 1; DC refinement; Cr, Cb, Y 1-63 Ah 1 Al 0 — grayscale, 6) coded by jcphuff.c: EOB runs across blocks
+ * (flushed at 0x7FFF), buffered correction bits (flushed past 937), optimal Huffman tables per scan (Y table 0, Cb / Cr
+ * table 1).  The interleaved DC scans include the dummy blocks; every AC scan covers only its component's own blocks.
+ * `header` is SOI .. SOF2; the device writes each scan's DHT segments (one table each, the ones the scan uses, in table-id
+ * order; none for a DC refinement), its SOS and its padded, stuffed data, then EOI.  params->optimize is ignored (libjpeg
+ * forces optimal tables for progressive files); only the quantisers of `tables` are read.  Workspace: 16-byte aligned,
+ * >= imgxf_jpeg_workspace_bytes_prog.  Errors and limits as imgxf_jpeg_encode_ex_u8 (at most 2097143 blocks per frame);
+ * sizes[f] = 0xFFFFFFFF when the file does not fit out_frame_stride (nblk * 1024 + 8192 bytes always suffice: a block
+ * takes at most 4072 bits over all scans), 0xFFFFFFFE when a scan's optimal table would need a code over 32 bits. */
+int imgxf_jpeg_workspace_bytes_prog(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t out_frame_stride,
+                                    size_t* bytes);
+int imgxf_jpeg_encode_prog_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
+                              const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
+                              uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mask stage of apply_background_change  transformation.py:340-341 -----------------*/
 /* 256-bin histogram per frame of a c==1 view into hist[n][256] (uint32, device, zeroed by the call). */
 int imgxf_histogram_u8(const imgxf_view* src, uint32_t* hist, void* stream);
