@@ -33,6 +33,14 @@ class View(C.Structure):
                 ("c", C.c_int32), ("row_stride", C.c_int64), ("frame_stride", C.c_int64)]
 
 
+class AugmixOp(C.Structure):
+    """struct imgxf_augmix_op (include/imgxf.h)."""
+    _fields_ = [("code", C.c_int32), ("arg", C.c_int32), ("m", C.c_double * 6)]
+
+
+AUGMIX_IDENTITY, AUGMIX_QUARTER, AUGMIX_AFFINE, AUGMIX_SCALE, AUGMIX_LUT, AUGMIX_EQUALIZE = 0, 1, 2, 3, 4, 5
+
+
 _VP = C.POINTER(View)
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -80,6 +88,11 @@ SIGNATURES = {
     "imgxf_lut_u8": [_VP, _VP, _U8, C.c_void_p],
     "imgxf_equalize_u8": [_VP, _VP, C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_channel_histogram_u8": [_VP, C.c_void_p, C.c_void_p],
+    "imgxf_augmix_record_bytes": [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)],
+    "imgxf_augmix_workspace_bytes": [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)],
+    "imgxf_augmix_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p,
+                         C.POINTER(AugmixOp), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                         C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_rgb2yuv_u8": [_VP, _VP, C.c_void_p],
     "imgxf_yuv2rgb_u8": [_VP, _VP, C.c_void_p],
     "imgxf_equalize_hist_cv_u8": [_VP, _VP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -1261,11 +1261,6 @@ __global__ __launch_bounds__(256) void shear_bicubic_kernel(View s, View d, Affi
     }
 }
 
-static inline int fix16(double v) {
-    const double t = v * 65536.0 + 0.5;
-    return t < 0.0 ? (int)floor(t) : (int)t;   // libImaging FLOOR()
-}
-
 template <int C, class A>
 static int launch_affine_filter(int filter, const View& s, const View& d, const AffineParams& P,
                                 const View& dbg, hipStream_t st) {
@@ -1421,9 +1416,7 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
     if (empty_view(src)) return IMGXF_ERR_SHAPE;
     AffineParams P; memset(&P, 0, sizeof(P));
     for (int i = 0; i < 6; ++i) P.m[i] = m[i];
-    P.fx[0] = fix16(m[0]); P.fx[1] = fix16(m[1]); P.fx[3] = fix16(m[3]); P.fx[4] = fix16(m[4]);
-    P.fx[2] = fix16(m[2] + m[0] * 0.5 + m[1] * 0.5);
-    P.fx[5] = fix16(m[5] + m[3] * 0.5 + m[4] * 0.5);
+    affine_fixed_matrix(m, P.fx);
     if (fill) for (int j = 0; j < dst->c; ++j) P.fill[j] = fill[j];
     View dbg; memset(&dbg, 0, sizeof(dbg));
     if (dbg_f32) {

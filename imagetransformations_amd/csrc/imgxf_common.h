@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <math.h>
 #include "imgxf.h"
 #include "knobs.h"
 
@@ -48,6 +49,18 @@ inline bool same_nhw(const imgxf_view* a, const imgxf_view* b) {
     return a->n == b->n && a->h == b->h && a->w == b->w;
 }
 inline bool empty_view(const imgxf_view* v) { return v->n == 0 || v->h == 0 || v->w == 0; }
+
+// libImaging affine_fixed: the NEAREST matrix in 16.16 fixed point, the half-pixel offsets folded
+// into the constants (imgxf_affine_u8, imgxf_augmix_f32)
+inline int fix16(double v) {
+    const double t = v * 65536.0 + 0.5;
+    return t < 0.0 ? (int)floor(t) : (int)t;   // libImaging FLOOR()
+}
+inline void affine_fixed_matrix(const double* m, int fx[6]) {
+    fx[0] = fix16(m[0]); fx[1] = fix16(m[1]); fx[3] = fix16(m[3]); fx[4] = fix16(m[4]);
+    fx[2] = fix16(m[2] + m[0] * 0.5 + m[1] * 0.5);
+    fx[5] = fix16(m[5] + m[3] * 0.5 + m[4] * 0.5);
+}
 
 inline int launch_status() {
     hipError_t e = hipGetLastError();

@@ -194,7 +194,7 @@ def affine(t: torch.Tensor, matrix: Sequence[float], out_size: tuple[int, int] |
         raise ValueError("affine matrix needs 6 coefficients")
     out = _out(out, _like_shape(t, oh, ow), t.device, lambda: _like(t, oh, ow))
     fill = _fill_bytes(fillcolor, c)
-    if resample == NEAREST and m[1] == 0.0 and m[3] == 0.0:
+    if is_scale_affine(m, resample):
         ws = torch.empty(ow + oh + 2, dtype=torch.int32, device=t.device)
         _launch(t, "imgxf_affine_scale_nearest_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.f64_array(m),
                fill, ws.data_ptr(), ws.numel() * 4)
@@ -205,6 +205,11 @@ def affine(t: torch.Tensor, matrix: Sequence[float], out_size: tuple[int, int] |
     _launch(t, "imgxf_affine_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.f64_array(m), int(resample),
            fill, 1 if precise else 0, F.vp(F.view_of(f32)) if return_f32 else None)
     return (out, f32) if return_f32 else out
+
+
+def is_scale_affine(m: Sequence[float], resample: int = NEAREST) -> bool:
+    """Whether libImaging takes ImagingScaleAffine (NEAREST, m1 == m3 == 0) instead of its generic path."""
+    return resample == NEAREST and m[1] == 0.0 and m[3] == 0.0
 
 
 def _fill_bytes(fillcolor, c: int):
@@ -279,11 +284,20 @@ def rotate(t: torch.Tensor, angle: float, resample: int = NEAREST, fillcolor=Non
     """Image.rotate(angle, resample, expand=False, fillcolor=fillcolor) incl. its fast paths."""
     t = _check_u8(t)
     h, w, _ = _hwc(t)
-    a = angle % 360.0
-    if a == 0 or a == 180 or (a in (90, 270) and w == h):
-        res = t.clone() if a == 0 else rot90(t, 2 if a == 180 else (1 if a == 90 else 3))
+    turns = rotate_turns(w, h, angle)
+    if turns is not None:
+        res = t.clone() if turns == 0 else rot90(t, turns)
         return res if out is None else out.copy_(res)
     return affine(t, rotate_matrix(w, h, angle), (w, h), resample, fillcolor, precise, out=out)
+
+
+def rotate_turns(w: int, h: int, angle: float) -> int | None:
+    """Image.rotate's fast paths: counter-clockwise quarter turns (0 = a copy) for multiples of 180
+    degrees, and of 90 on square frames; None when the affine resampler runs."""
+    a = angle % 360.0
+    if a == 0 or a == 180 or (a in (90, 270) and w == h):
+        return 0 if a == 0 else (2 if a == 180 else (1 if a == 90 else 3))
+    return None
 
 
 # ---------------------------------------------------------------- a3 Lanczos resize
@@ -607,15 +621,25 @@ def lut(t: torch.Tensor, table) -> torch.Tensor:
     return out
 
 
+def posterize_table(bits: int) -> list[int]:
+    """ImageOps.posterize's table (raises like it for bits > 8)."""
+    mask = ~(2 ** (8 - int(bits)) - 1)
+    return [i & mask for i in range(256)]
+
+
+def solarize_table(threshold: int = 128) -> list[int]:
+    """ImageOps.solarize's table."""
+    return [i if i < threshold else 255 - i for i in range(256)]
+
+
 def posterize(t: torch.Tensor, bits: int) -> torch.Tensor:
     """ImageOps.posterize (fall_2025/AugMix.py:31)."""
-    mask = ~(2 ** (8 - int(bits)) - 1)
-    return lut(t, [i & mask for i in range(256)])
+    return lut(t, posterize_table(bits))
 
 
 def solarize(t: torch.Tensor, threshold: int = 128) -> torch.Tensor:
     """ImageOps.solarize (fall_2025/AugMix.py:37)."""
-    return lut(t, [i if i < threshold else 255 - i for i in range(256)])
+    return lut(t, solarize_table(threshold))
 
 
 def equalize(t: torch.Tensor) -> torch.Tensor:

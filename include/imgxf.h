@@ -246,6 +246,54 @@ int imgxf_equalize_u8(const imgxf_view* src, const imgxf_view* dst, void* worksp
                       void* stream);
 int imgxf_channel_histogram_u8(const imgxf_view* src, uint32_t* hist, void* stream);
 
+/* ---- AugMix on a batch  fall_2025/AugMix.py:45-62 -------------------------------------------
+ * One launch runs augmix() for n float CHW images: per image `width` branches of operations on
+ * uint8 HWC frames, then the float32 mix, bit-identical to imagetransformations_amd.augmix.augmix().
+ *
+ * Operation table (HOST, copied into the launch): at most IMGXF_AUGMIX_MAX_OPS entries.
+ *   IDENTITY  no operation (Image.rotate by a multiple of 360 degrees);
+ *   QUARTER   arg = counter-clockwise quarter turns 1..3 (1 and 3 need h == w; imgxf_rot90_u8);
+ *   AFFINE    NEAREST Image.transform(AFFINE, m), fill 0, libImaging affine_fixed 16.16 (imgxf_affine_u8);
+ *   SCALE     NEAREST with m[1] == m[3] == 0, fill 0, ImagingScaleAffine (imgxf_affine_scale_nearest_u8);
+ *   LUT       dst = luts[arg][src] on every channel (ImageOps.posterize / solarize tables);
+ *   EQUALIZE  ImageOps.equalize per channel (imgxf_equalize_u8).
+ * m[6] is the destination->source matrix as Pillow takes it (AFFINE and SCALE; ignored otherwise).
+ * luts: HOST, nluts * 256 bytes, nluts <= IMGXF_AUGMIX_MAX_LUTS.
+ *
+ * plan (DEVICE, 4-byte aligned): n records of imgxf_augmix_record_bytes(width, depth) bytes each:
+ *   float   w[width]            branch weights, (float) of the Dirichlet draw
+ *   float   one_minus_m, m      (float)(1 - m) with 1 - m formed in double, and (float) m
+ *   uint8_t step[width][depth]  operation-table index of each step; indices >= nops end nothing and
+ *                               run nothing (0xFF marks the steps past a branch's drawn depth)
+ * src: n float CHW images in [0, 1] at element strides strides[0..3] (image, channel, row, column);
+ * dst: contiguous float [n][3][h][w], must not overlap src.
+ * workspace (DEVICE, 16-byte aligned): imgxf_augmix_workspace_bytes(n, h, w) bytes.  It is 0 when
+ * the two uint8 working frames stay in LDS, i.e. when
+ *     2 * R16(3*h*w) + R16(4*(h + w + 2)) + 4992 <= 163840   (R16 = round up to 16),
+ * which admits every square frame up to 162 x 162; otherwise 2 * R16(3*h*w) * n bytes hold the
+ * working frames of every image and the same kernel runs on them.
+ * Errors: IMGXF_ERR_NULL (strides, ops; src, dst, plan when n > 0; luts when nluts > 0; a NULL workspace of
+ * sufficient workspace_bytes when one is needed),
+ * IMGXF_ERR_SHAPE (h, w outside 1..32767, n < 0), IMGXF_ERR_ARG (unknown op code, an arg outside its
+ * range, a non-finite matrix entry, nops / nluts / width / depth out of range),
+ * IMGXF_ERR_WORKSPACE (workspace_bytes short).  All checks happen on the host before any HIP call. */
+enum { IMGXF_AUGMIX_IDENTITY = 0, IMGXF_AUGMIX_QUARTER = 1, IMGXF_AUGMIX_AFFINE = 2, IMGXF_AUGMIX_SCALE = 3,
+       IMGXF_AUGMIX_LUT = 4, IMGXF_AUGMIX_EQUALIZE = 5 };
+enum { IMGXF_AUGMIX_MAX_OPS = 16, IMGXF_AUGMIX_MAX_LUTS = 4, IMGXF_AUGMIX_MAX_WIDTH = 1024,
+       IMGXF_AUGMIX_MAX_DEPTH = 1024 };
+typedef struct imgxf_augmix_op {
+    int32_t code;   /* IMGXF_AUGMIX_* */
+    int32_t arg;    /* QUARTER: turns; LUT: table index; 0 otherwise */
+    double  m[6];
+} imgxf_augmix_op;
+/* Bytes of one plan record: 4 * width + 8 + width * depth, rounded up to a multiple of 4. */
+int imgxf_augmix_record_bytes(int32_t width, int32_t depth, size_t* bytes);
+int imgxf_augmix_workspace_bytes(int32_t n, int32_t h, int32_t w, size_t* bytes);
+int imgxf_augmix_f32(const float* src, int32_t n, int32_t h, int32_t w, const int64_t* strides, float* dst,
+                     const imgxf_augmix_op* ops, int32_t nops, const uint8_t* luts, int32_t nluts,
+                     const void* plan, int32_t width, int32_t depth, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ---- TransformationPool.histogram_equalization  cifar_image_transformations.py:122-129 -------
  * cv2.cvtColor(RGB2YUV / YUV2RGB) for 8-bit images (integer BT.601, yuv_shift 14) and
  * cv2.equalizeHist applied to one channel of an interleaved view.  PARITY UNPINNED: OpenCV is not
