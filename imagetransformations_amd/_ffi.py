@@ -41,6 +41,18 @@ class AugmixOp(C.Structure):
 AUGMIX_IDENTITY, AUGMIX_QUARTER, AUGMIX_AFFINE, AUGMIX_SCALE, AUGMIX_LUT, AUGMIX_EQUALIZE = 0, 1, 2, 3, 4, 5
 
 
+class PoolOp(C.Structure):
+    """struct imgxf_pool_op (include/imgxf.h)."""
+    _fields_ = [("code", C.c_int32), ("arg", C.c_int32), ("m", C.c_double * 10)]
+
+
+# TransformationPool member -> IMGXF_POOL_* op code (include/imgxf.h)
+POOL_CODES = {"defocus_blur": 0, "enhance_sharpness": 1, "enhance_contrast": 2, "enhance_color": 3,
+              "enhance_brightness": 4, "gaussian_noise": 5, "impulse_noise": 6, "shot_noise": 7, "motion_blur": 8,
+              "histogram_equalization": 9}
+POOL_MAX_OPS, POOL_MAX_STEPS, POOL_MAX_MOTION = 32, 16, 31
+
+
 _VP = C.POINTER(View)
 _F = C.POINTER(C.c_float)
 _D = C.POINTER(C.c_double)
@@ -93,6 +105,10 @@ SIGNATURES = {
     "imgxf_augmix_f32": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p,
                          C.POINTER(AugmixOp), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                          C.c_void_p, C.c_size_t, C.c_void_p],
+    "imgxf_pool_chain_record_bytes": [C.c_int32, C.POINTER(C.c_size_t)],
+    "imgxf_pool_chain_workspace_bytes": [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)],
+    "imgxf_pool_chain_u8": [_VP, _VP, C.POINTER(PoolOp), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                            C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_rgb2yuv_u8": [_VP, _VP, C.c_void_p],
     "imgxf_yuv2rgb_u8": [_VP, _VP, C.c_void_p],
     "imgxf_equalize_hist_cv_u8": [_VP, _VP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

@@ -9,27 +9,6 @@
 
 namespace imgxf {
 
-__device__ __forceinline__ int descale14(int x) { return (x + (1 << 13)) >> 14; }
-__device__ __forceinline__ u32 sat8(int v) { return (u32)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
-struct Rgb2Yuv {
-    __device__ __forceinline__ void operator()(const u32 (&c)[3], u32 (&o)[3]) const {
-        const int R = (int)c[0], G = (int)c[1], B = (int)c[2];
-        const int Y = descale14(R * 4899 + G * 9617 + B * 1868);
-        const int V = descale14((R - Y) * 14369 + (128 << 14));
-        const int U = descale14((B - Y) * 8061 + (128 << 14));
-        o[0] = sat8(Y); o[1] = sat8(U); o[2] = sat8(V);
-    }
-};
-struct Yuv2Rgb {
-    __device__ __forceinline__ void operator()(const u32 (&c)[3], u32 (&o)[3]) const {
-        const int Y = (int)c[0], U = (int)c[1] - 128, V = (int)c[2] - 128;
-        o[2] = sat8(Y + descale14(U * 33292));
-        o[1] = sat8(Y + descale14(U * -6472 + V * -9519));
-        o[0] = sat8(Y + descale14(V * 18678));
-    }
-};
-
 // 16 pixels (48 bytes) per lane, dense 16-byte accesses when the view allows it
 template <class Op>
 __global__ __launch_bounds__(256) void pixel3_map_kernel(View s, View d, Op op) {
@@ -92,23 +71,7 @@ __global__ void cv_equalize_lut_kernel(const u32* hist, u8* lut, int nframes, in
     if (f >= nframes) return;
     for (int j = 0; j < c; ++j)
         for (int i = 0; i < 256; ++i) lut[((int64_t)f * c + j) * 256 + i] = (u8)i;
-    const u32* h = hist + ((int64_t)f * c + ch) * 256;
-    u8* l = lut + ((int64_t)f * c + ch) * 256;
-    long long total = 0;
-    for (int i = 0; i < 256; ++i) total += h[i];
-    int i = 0;
-    while (i < 255 && !h[i]) ++i;
-    if ((long long)h[i] == total) {                         // one level: dst.setTo(i)
-        for (int k = 0; k < 256; ++k) l[k] = (u8)i;
-        return;
-    }
-    const float scale = 255.0f / (float)(total - (long long)h[i]);
-    int sum = 0;
-    l[i++] = 0;
-    for (; i < 256; ++i) {
-        sum += (int)h[i];
-        l[i] = (u8)sat_u8_rne((float)sum * scale);          // saturate_cast<uchar>(float): cvRound
-    }
+    cv_equalize_table(hist + ((int64_t)f * c + ch) * 256, lut + ((int64_t)f * c + ch) * 256);
 }
 
 static inline unsigned cs_grid(int64_t total) {

@@ -107,7 +107,6 @@ __global__ __launch_bounds__(256) void sobel_kernel(View s, View d, int variant)
 // order of Filter.c, the one-pixel frame copied from the input.  A lane owns 4 bytes of a row.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ int clampi_(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-struct K9 { float k[9]; float off; };
 __global__ __launch_bounds__(256) void filter3x3_kernel(View s, View d, K9 K) {
     const int C = s.c;
     const int rowbytes = s.w * C;
@@ -125,15 +124,7 @@ __global__ __launch_bounds__(256) void filter3x3_kernel(View s, View d, K9 K) {
         for (int e = 0; e < 4; ++e) {
             const int b = qd * 4 + e;
             if (b >= rowbytes) break;
-            u8 v = r0[b];
-            if (inner_row && b >= C && b < rowbytes - C) {
-                float ss = K.off;
-                ss += ((float)rp[b - C] * K.k[0] + (float)rp[b] * K.k[1]) + (float)rp[b + C] * K.k[2];
-                ss += ((float)r0[b - C] * K.k[3] + (float)r0[b] * K.k[4]) + (float)r0[b + C] * K.k[5];
-                ss += ((float)rm[b - C] * K.k[6] + (float)rm[b] * K.k[7]) + (float)rm[b + C] * K.k[8];
-                v = ss <= 0.0f ? (u8)0 : (ss >= 255.0f ? (u8)255 : (u8)(int)ss);
-            }
-            dp[b] = v;
+            dp[b] = inner_row && b >= C && b < rowbytes - C ? filter3x3_at(rm, r0, rp, b, C, K) : r0[b];
         }
     }
 }
@@ -192,15 +183,7 @@ __global__ __launch_bounds__(256) void filter3x3_rows16_kernel(View s, View d, K
         for (int e = 0; e < 16; ++e) {
             const int b = b0 + e;
             if (b >= rowbytes) break;
-            u8 v = r0[b];
-            if (inner_row && b >= C && b < rowbytes - C) {
-                float a = K.off;
-                a += ((float)rp[b - C] * K.k[0] + (float)rp[b] * K.k[1]) + (float)rp[b + C] * K.k[2];
-                a += ((float)r0[b - C] * K.k[3] + (float)r0[b] * K.k[4]) + (float)r0[b + C] * K.k[5];
-                a += ((float)rm[b - C] * K.k[6] + (float)rm[b] * K.k[7]) + (float)rm[b + C] * K.k[8];
-                v = a <= 0.0f ? (u8)0 : (a >= 255.0f ? (u8)255 : (u8)(int)a);
-            }
-            dp[b] = v;
+            dp[b] = inner_row && b >= C && b < rowbytes - C ? filter3x3_at(rm, r0, rp, b, C, K) : r0[b];
         }
     }
 }
@@ -229,8 +212,7 @@ __global__ __launch_bounds__(256) void box_pass_kernel(View s, View d, int radiu
             for (int i = -radius; i <= radius; ++i) acc += s.row(f, clampi_(y + i, 0, s.h - 1))[b];
             far = (u32)s.row(f, clampi_(y - radius - 1, 0, s.h - 1))[b] + (u32)s.row(f, clampi_(y + radius + 1, 0, s.h - 1))[b];
         }
-        const u32 bulk = acc * ww + far * fw;
-        d.row(f, y)[b] = (u8)((bulk + (1u << 23)) >> 24);
+        d.row(f, y)[b] = box_out(acc, far, ww, fw);
     }
 }
 
@@ -397,17 +379,6 @@ static bool launch_box_h16(const View& s, const View& d, int radius, u32 ww, u32
 
 using namespace imgxf;
 
-// BoxBlur.c _gaussian_blur_radius: float variables, double sqrt / floor (built un-contracted)
-static float gaussian_box_radius(float radius, int passes) {
-    float sigma2, L, l, a;
-    sigma2 = radius * radius / passes;
-    L = sqrt(12.0 * sigma2 + 1.0);
-    l = floor((L - 1.0) / 2.0);
-    a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2);
-    a /= 6 * (sigma2 - (l + 1) * (l + 1));
-    return l + a;
-}
-
 IMGXF_API int imgxf_box_blur_u8(const imgxf_view* src, const imgxf_view* dst, float xradius, float yradius,
                                 int passes, void* workspace, size_t workspace_bytes, void* stream) {
     IMGXF_CHECK(check_view(src));
@@ -438,9 +409,9 @@ IMGXF_API int imgxf_box_blur_u8(const imgxf_view* src, const imgxf_view* dst, fl
     for (int axis = 0; axis < 2; ++axis) {
         const float fr = axis == 0 ? xradius : yradius;
         if (fr == 0.0f) continue;
-        const int radius = (int)fr;
-        const u32 ww = (u32)((float)(1u << 24) / (fr * 2 + 1));
-        const u32 fw = ((u32)(1 << 24) - (u32)(radius * 2 + 1) * ww) / 2;
+        int radius;
+        u32 ww, fw;
+        box_weights(fr, &radius, &ww, &fw);
         for (int p = 0; p < passes; ++p) {
             // the last pass must land in dst: alternate so that parity works out
             const bool to_dst = ((total_passes - 1 - done) & 1) == 0;
@@ -484,9 +455,7 @@ IMGXF_API int imgxf_filter3x3_u8(const imgxf_view* src, const imgxf_view* dst, c
     if (!same_geometry(src, dst)) return IMGXF_ERR_SHAPE;
     if (scale == 0.0f) return IMGXF_ERR_ARG;
     if (empty_view(src)) return IMGXF_OK;
-    K9 K;
-    for (int i = 0; i < 9; ++i) K.k[i] = kernel9[i] / scale;      // FLOAT32 division, as _imaging.c does
-    K.off = offset + 0.5f;
+    const K9 K = filter3x3_taps(kernel9, scale, offset);
     const View s = make_view(src), d = make_view(dst);
     if (((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0 &&
         s.rowbytes() >= 48 && !knob_set(K_FILTER3X3_BYTES)) {

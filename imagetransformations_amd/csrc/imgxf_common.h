@@ -98,4 +98,101 @@ __device__ __forceinline__ u32 sat_u8_rne(float v) {
     return (u32)r;
 }
 
+// ---- scalar helpers shared by the per-image kernels and the pool chain (pool_chain.hip) ----
+
+// Blend.c: float32 in1 + alpha * (in2 - in1), truncated; floor() + the saturating pack of the
+// callers also give Blend.c's clip outside 0 <= alpha <= 1 (un-contracted: -ffp-contract=off)
+__device__ __forceinline__ float blend_floor(float in1, float in2, float alpha) {
+    return floorf(in1 + alpha * (in2 - in1));
+}
+__device__ __forceinline__ u32 pack_u8(float v) { return __builtin_amdgcn_cvt_pk_u8_f32(v, 0, 0u); }
+
+// Image.convert('L'): ITU-R 601-2 luma in 16.16 fixed point (libImaging Convert.c L24)
+__host__ __device__ __forceinline__ u32 luma_u8(u32 r, u32 g, u32 b) {
+    return (r * 19595u + g * 38470u + b * 7471u + 0x8000u) >> 16;
+}
+
+// ImageEnhance.Contrast's grey level: int(ImageStat.mean[0] + 0.5) of the frame's L, in float64
+__host__ __device__ __forceinline__ float contrast_mean(unsigned long long sum, int64_t count) {
+    return (float)(int)((double)sum / (double)count + 0.5);
+}
+
+// BoxBlur.c _gaussian_blur_radius: float variables, double sqrt / floor (built un-contracted)
+inline float gaussian_box_radius(float radius, int passes) {
+    float sigma2, L, l, a;
+    sigma2 = radius * radius / passes;
+    L = sqrt(12.0 * sigma2 + 1.0);
+    l = floor((L - 1.0) / 2.0);
+    a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2);
+    a /= 6 * (sigma2 - (l + 1) * (l + 1));
+    return l + a;
+}
+// ImagingLineBoxBlur weights of a box of float radius fr: out = (sum * ww + (far_l + far_r) * fw + 2^23) >> 24
+inline void box_weights(float fr, int* radius, u32* ww, u32* fw) {
+    *radius = (int)fr;
+    *ww = (u32)((float)(1u << 24) / (fr * 2 + 1));
+    *fw = ((u32)(1 << 24) - (u32)(*radius * 2 + 1) * *ww) / 2;
+}
+__device__ __forceinline__ u8 box_out(u32 acc, u32 far, u32 ww, u32 fw) {
+    return (u8)((acc * ww + far * fw + (1u << 23)) >> 24);
+}
+
+// ImagingFilter3x3 (Filter.c): taps kernel9[i] / scale in FLOAT32 as _imaging.c divides, offset + 0.5;
+// rp = the row below (y + 1), rm = the row above, the exact float32 operation order of the C code
+struct K9 { float k[9]; float off; };
+inline K9 filter3x3_taps(const float* kernel9, float scale, float offset) {
+    K9 K;
+    for (int i = 0; i < 9; ++i) K.k[i] = kernel9[i] / scale;
+    K.off = offset + 0.5f;
+    return K;
+}
+__device__ __forceinline__ u8 filter3x3_at(const u8* rm, const u8* r0, const u8* rp, int b, int C, const K9& K) {
+    float a = K.off;
+    a += ((float)rp[b - C] * K.k[0] + (float)rp[b] * K.k[1]) + (float)rp[b + C] * K.k[2];
+    a += ((float)r0[b - C] * K.k[3] + (float)r0[b] * K.k[4]) + (float)r0[b + C] * K.k[5];
+    a += ((float)rm[b - C] * K.k[6] + (float)rm[b] * K.k[7]) + (float)rm[b + C] * K.k[8];
+    return a <= 0.0f ? (u8)0 : (a >= 255.0f ? (u8)255 : (u8)(int)a);
+}
+
+// OpenCV 8-bit RGB <-> YUV (imgproc color_yuv: yuv_shift = 14, CV_DESCALE rounding, saturate_cast)
+__device__ __forceinline__ int descale14(int x) { return (x + (1 << 13)) >> 14; }
+__device__ __forceinline__ u32 sat8(int v) { return (u32)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+struct Rgb2Yuv {
+    __device__ __forceinline__ void operator()(const u32 (&c)[3], u32 (&o)[3]) const {
+        const int R = (int)c[0], G = (int)c[1], B = (int)c[2];
+        const int Y = descale14(R * 4899 + G * 9617 + B * 1868);
+        const int V = descale14((R - Y) * 14369 + (128 << 14));
+        const int U = descale14((B - Y) * 8061 + (128 << 14));
+        o[0] = sat8(Y); o[1] = sat8(U); o[2] = sat8(V);
+    }
+};
+struct Yuv2Rgb {
+    __device__ __forceinline__ void operator()(const u32 (&c)[3], u32 (&o)[3]) const {
+        const int Y = (int)c[0], U = (int)c[1] - 128, V = (int)c[2] - 128;
+        o[2] = sat8(Y + descale14(U * 33292));
+        o[1] = sat8(Y + descale14(U * -6472 + V * -9519));
+        o[0] = sat8(Y + descale14(V * 18678));
+    }
+};
+// cv2.equalizeHist table from one 256-bin histogram (histogram.cpp): scale = 255.f / (total - hist[first]),
+// lut = saturate(sum * scale); levels below the first occupied bin keep the identity; one level maps to itself
+__device__ __forceinline__ void cv_equalize_table(const u32* h, u8* l) {
+    for (int k = 0; k < 256; ++k) l[k] = (u8)k;
+    long long total = 0;
+    for (int k = 0; k < 256; ++k) total += h[k];
+    int i = 0;
+    while (i < 255 && !h[i]) ++i;
+    if ((long long)h[i] == total) {                         // one level: dst.setTo(i)
+        for (int k = 0; k < 256; ++k) l[k] = (u8)i;
+        return;
+    }
+    const float scale = 255.0f / (float)(total - (long long)h[i]);
+    int sum = 0;
+    l[i++] = 0;
+    for (; i < 256; ++i) {
+        sum += (int)h[i];
+        l[i] = (u8)sat_u8_rne((float)sum * scale);          // saturate_cast<uchar>(float): cvRound
+    }
+}
+
 } // namespace imgxf

@@ -87,8 +87,7 @@ struct BlendOp {
     __device__ __forceinline__ float operator()(float pa, float pb, int ch) const {
         const float i1 = const1 ? c1.v[ch] : pa;
         const float i2 = const2 ? c2.v[ch] : pb;
-        const float t = i1 + alpha * (i2 - i1);      // un-contracted (library-wide -ffp-contract=off)
-        return floorf(t);
+        return blend_floor(i1, i2, alpha);
     }
 };
 
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(256) void rgb2l_kernel(View s, View d) {
             const u32 R = (in[b0 >> 2] >> (8 * (b0 & 3))) & 0xffu;
             const u32 G = (in[(b0 + 1) >> 2] >> (8 * ((b0 + 1) & 3))) & 0xffu;
             const u32 B = (in[(b0 + 2) >> 2] >> (8 * ((b0 + 2) & 3))) & 0xffu;
-            const u32 L = (R * 19595u + G * 38470u + B * 7471u + 0x8000u) >> 16;
+            const u32 L = luma_u8(R, G, B);
             out[px >> 2] |= L << (8 * (px & 3));
         }
         if (vec) {
@@ -361,12 +360,11 @@ __global__ __launch_bounds__(256) void enhance_color_kernel(View s, View d, floa
             u32 ch[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) { const int b = px * 3 + j; ch[j] = (in[b >> 2] >> (8 * (b & 3))) & 0xffu; }
-            const float L = (float)((ch[0] * 19595u + ch[1] * 38470u + ch[2] * 7471u + 0x8000u) >> 16);
+            const float L = (float)luma_u8(ch[0], ch[1], ch[2]);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const int b = px * 3 + j;
-                const float tv = L + factor * ((float)ch[j] - L);          // Blend.c, un-contracted
-                out[b >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(floorf(tv), b & 3, out[b >> 2]);
+                out[b >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(blend_floor(L, (float)ch[j], factor), b & 3, out[b >> 2]);
             }
         }
         if (vec) {
@@ -412,7 +410,7 @@ __global__ __launch_bounds__(256) void lum_sum_kernel(View s, unsigned long long
                 if (C == 1) { part += R; continue; }
                 const u32 G = (in[(b0 + 1) >> 2] >> (8 * ((b0 + 1) & 3))) & 0xffu;
                 const u32 B = (in[(b0 + 2) >> 2] >> (8 * ((b0 + 2) & 3))) & 0xffu;
-                part += (R * 19595u + G * 38470u + B * 7471u + 0x8000u) >> 16;
+                part += luma_u8(R, G, B);
             }
         }
     } else {
@@ -420,7 +418,7 @@ __global__ __launch_bounds__(256) void lum_sum_kernel(View s, unsigned long long
         for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
             const int x = (int)(t % s.w), y = (int)(t / s.w);
             const u8* p = s.row(f, y) + x * C;
-            part += C == 1 ? (u32)p[0] : ((u32)p[0] * 19595u + (u32)p[1] * 38470u + (u32)p[2] * 7471u + 0x8000u) >> 16;
+            part += C == 1 ? (u32)p[0] : luma_u8(p[0], p[1], p[2]);
         }
     }
 #pragma unroll
@@ -437,7 +435,7 @@ __global__ __launch_bounds__(256) void lum_sum_kernel(View s, unsigned long long
 struct ContrastOp {
     float factor, mean;
     __device__ __forceinline__ float operator()(float pa, float, int) const {
-        return floorf(mean + factor * (pa - mean));
+        return blend_floor(mean, pa, factor);
     }
 };
 template <int C>
@@ -446,8 +444,7 @@ __global__ __launch_bounds__(256) void contrast_kernel(View s, View d, float fac
     const int rowbytes = d.w * C;
     const int nchunks = (rowbytes + CB - 1) / CB;
     const int f = blockIdx.y;
-    const double cnt = (double)((int64_t)s.h * s.w);
-    const float mean = (float)(int)((double)sums[f] / cnt + 0.5);        // int(ImageStat.mean[0] + 0.5)
+    const float mean = contrast_mean(sums[f], (int64_t)s.h * s.w);
     const int64_t total = (int64_t)d.h * nchunks;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
         const int ck = (int)(t % nchunks), y = (int)(t / nchunks);
@@ -467,7 +464,7 @@ __global__ __launch_bounds__(256) void contrast_kernel(View s, View d, float fac
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float pa = (float)((w[i] >> (8 * e)) & 0xffu);
-                        acc = __builtin_amdgcn_cvt_pk_u8_f32(floorf(mean + factor * (pa - mean)), e, acc);
+                        acc = __builtin_amdgcn_cvt_pk_u8_f32(blend_floor(mean, pa, factor), e, acc);
                     }
                     o[i] = acc;
                 }
@@ -475,8 +472,7 @@ __global__ __launch_bounds__(256) void contrast_kernel(View s, View d, float fac
             }
         } else {
             for (int e = 0; e < nv; ++e) {
-                const float tv = floorf(mean + factor * ((float)ap[e] - mean));
-                dp[e] = (u8)__builtin_amdgcn_cvt_pk_u8_f32(tv, 0, 0u);
+                dp[e] = (u8)pack_u8(blend_floor(mean, (float)ap[e], factor));
             }
         }
     }

@@ -6,13 +6,17 @@ installed where this was built; they follow OpenCV's definitions), the other eig
 against Pillow / the reference's NumPy expressions."""
 from __future__ import annotations
 
+import ctypes
 import random
+from collections.abc import Sequence
+from dataclasses import dataclass
 
 import numpy as np
 from PIL import Image
 
 import torch
 
+from . import _ffi as F
 from . import ops, transformation as T
 from .transformation import _device, _download, _upload
 
@@ -122,3 +126,383 @@ class TransformationPool:
         if image.mode not in ("RGB", "L"):
             raise NotImplementedError(f"enhance_brightness supports RGB and L images, got {image.mode!r}")
         return _download(ops.brightness(_upload(image), factor))
+
+
+# ---- chains of members on a whole batch in one launch ----------------------------------------------------------------
+# Individual.apply_transformations (cifar_image_transformations.py:141-152) applies a chain of the members above to
+# every image.  `apply_chain_batch` runs the chains of a batch in one kernel launch (two when a chain holds
+# shot_noise) and returns what the per-image loop returns:
+#
+#     for i, a in enumerate(frames.cpu().numpy()):
+#         img = Image.fromarray(a)
+#         for item in chains[i]:                              # or one chain for every image
+#             name, arg = (item, None) if isinstance(item, str) else item
+#             fn = getattr(TransformationPool, name)
+#             img = fn(img) if arg is None else fn(img, arg)
+#
+# The members' own tables (their argument meaning), restated for the plan; tests/test_pool_chain_plan.py holds them
+# to the members.
+_SEVERITY_TABLES = {
+    "defocus_blur": [3, 4, 6, 8, 10],                      # GaussianBlur radius
+    "gaussian_noise": [0.08, 0.12, 0.18, 0.26, 0.38],      # noise_std
+    "impulse_noise": [0.03, 0.06, 0.09, 0.17, 0.27],       # noise_prob
+    "shot_noise": [60, 25, 12, 5, 3],                       # lambda
+}
+_MOTION_SIZES = [5, 7, 9, 11]
+_FACTOR_RANGES = {"enhance_contrast": (0.5, 2.0), "enhance_sharpness": (0.5, 3.0), "enhance_color": (0.5, 2.0),
+                  "enhance_brightness": (0.5, 2.0)}
+_NP_DRAWING = ("gaussian_noise", "impulse_noise", "shot_noise")
+_CONV2D_MAX = 15           # imgxf_conv2d_u8 takes odd kernels up to 15 x 15; motion_blur raises past that
+_NO_STEP = 0xFF
+_STEP_BYTES = 16
+
+
+def _check_item(item):
+    """(name, arg) of one chain item, raising what the loop would raise for it, without drawing."""
+    name, arg = (item, None) if isinstance(item, str) else item
+    getattr(TransformationPool, name)                       # AttributeError / TypeError as the loop's getattr
+    if name not in F.POOL_CODES:
+        raise AttributeError(f"{name!r} is not a TransformationPool member")
+    if arg is None:
+        return name, None
+    if name == "histogram_equalization":
+        raise TypeError("histogram_equalization() takes 1 positional argument but 2 were given")
+    if name in _SEVERITY_TABLES:
+        _SEVERITY_TABLES[name][arg - 1]                     # the member's own lookup: TypeError / IndexError
+    elif name == "motion_blur":
+        kernel = np.zeros((arg, arg))                       # the member's own construction
+        kernel[int((arg - 1) / 2), :] = np.ones(arg)
+        if arg % 2 == 0 or arg > _CONV2D_MAX:               # imgxf_conv2d_u8: IMGXF_ERR_ARG -> ValueError
+            raise ValueError(f"motion_blur: size {arg} is not an odd size up to {_CONV2D_MAX} (imgxf_conv2d_u8)")
+    else:
+        ctypes.c_float(float(arg))                          # what ops' float(factor) and ctypes raise
+    return name, arg
+
+
+def _is_item(x) -> bool:
+    if isinstance(x, str):
+        return True
+    return isinstance(x, (tuple, list)) and len(x) == 2 and isinstance(x[0], str) and not isinstance(x[1], (str, tuple, list))
+
+
+def _chains_per_image(chains, n: int) -> list:
+    """One (name, arg) list per image; `chains` is one chain for every image or a sequence of n chains."""
+    if isinstance(chains, str) or not isinstance(chains, Sequence):
+        raise TypeError("chains must be a chain (a sequence of items) or a sequence of chains")
+    if all(_is_item(c) for c in chains):
+        one = [_check_item(it) for it in chains]
+        per = [one] * n
+    else:
+        if len(chains) != n:
+            raise ValueError(f"{len(chains)} chains for {n} images")
+        per = []
+        for c in chains:
+            if isinstance(c, str) or not isinstance(c, Sequence):
+                raise TypeError(f"a chain must be a sequence of items, got {c!r}")
+            per.append([_check_item(it) for it in c])
+    for c in per:
+        if len(c) > F.POOL_MAX_STEPS:
+            raise ValueError(f"a chain holds at most {F.POOL_MAX_STEPS} items, got {len(c)}")
+    return per
+
+
+def _kernel_takes(chain) -> bool:
+    """The kernel takes a chain in which shot_noise appears at most once and no member before it draws from np.random
+    (its Poisson draw depends on the pixels, and every later np.random position on it)."""
+    drew = False
+    for name, _ in chain:
+        if name == "shot_noise" and drew:
+            return False
+        drew = drew or name in _NP_DRAWING
+    return True
+
+
+def chain_runs(chains, n: int) -> list:
+    """[(start, stop, batched)]: maximal runs of images whose chains the kernel takes (batched) and the single images
+    between them that go through the per-image loop."""
+    per = _chains_per_image(chains, n)
+    runs = []
+    for i, c in enumerate(per):
+        ok = _kernel_takes(c)
+        if runs and ok and runs[-1][2]:
+            runs[-1] = (runs[-1][0], i + 1, True)
+        else:
+            runs.append((i, i + 1, ok))
+    return runs
+
+
+@dataclass
+class ChainPlan:
+    """The draws of the per-image loop for n images and what the kernel runs.
+
+    members / args: per image, the member names and their arguments as the loop hands them over (drawn or explicit);
+    index [n, steps] uint8: operation-table entry of each step (0xFF past a chain's end); factors [n, steps] float32:
+    the C float of an ENHANCE_* step's factor; table: entries (code, arg, m[10]); data: (image, step) -> the step's
+    float64 normals [h,w,3] (a numpy array, or a device tensor from numpy_stream), mask [h,w] or Poisson counts
+    [h,w,3]; late: the first image holding shot_noise (n if none) — its np.random draws and all after it wait for
+    `chain_plan_finish`; split [n]: the step each image's second launch starts at (its chain length if none)."""
+    n: int
+    h: int
+    w: int
+    members: list
+    args: list
+    index: np.ndarray
+    factors: np.ndarray
+    table: list
+    data: dict
+    late: int
+    split: np.ndarray
+    finished: bool = False
+
+    @property
+    def steps(self) -> int:
+        return self.index.shape[1]
+
+
+def _entry(name: str, arg):
+    """(key, (code, arg, m)) of the table entry a step of `name` with argument `arg` runs."""
+    code, m = F.POOL_CODES[name], [0.0] * 10
+    if name == "defocus_blur":
+        radius = _SEVERITY_TABLES[name][arg - 1]
+        m[0] = ctypes.c_float(float(radius)).value          # ops.gaussian_blur_pil: float(radius) -> c_float
+        return (name, m[0]), (code, 0, m)
+    if name == "impulse_noise":
+        p = _SEVERITY_TABLES[name][arg - 1]
+        m[0], m[1] = p / 2, 1 - p / 2                        # ops.impulse_noise(.., noise_prob / 2, 1 - noise_prob / 2)
+        return (name, p), (code, 0, m)
+    if name == "shot_noise":
+        lam = _SEVERITY_TABLES[name][arg - 1]
+        m[0] = float(lam)                                   # imgxf_shot_noise_u8(double lambda)
+        return (name, lam), (code, 0, m)
+    if name == "motion_blur":
+        return (name, int(arg)), (code, int(arg), m)
+    if name == "enhance_sharpness":
+        m[:9], m[9] = [float(v) for v in ops.SMOOTH_KERNEL], 13.0   # ops.enhance_sharpness: filter3x3(SMOOTH, 13)
+        return (name,), (code, 0, m)
+    return (name,), (code, 0, m)
+
+
+def _draw_np(plan: ChainPlan, i: int, s: int, frame, device) -> None:
+    """np.random draws of step s of image i, as the member makes them (frame: the host frame shot_noise reads)."""
+    name, arg = plan.members[i][s], plan.args[i][s]
+    h, w = plan.h, plan.w
+    if name == "gaussian_noise":
+        noise_std = _SEVERITY_TABLES[name][arg - 1]
+        size = h * w * 3
+        z = None
+        if T.NOISE_RNG != "numpy-host" and size >= T.NOISE_DEVICE_MIN:    # the member's device branch
+            from . import numpy_stream
+            state = np.random.get_state()
+            try:
+                got = numpy_stream.draw_on_device([(size, noise_std * 255)], _device() if device is None else device,
+                                                  f64=True)
+            except ValueError:
+                np.random.set_state(state)
+                got = None
+            z = got[0] if got is not None else None
+        plan.data[i, s] = z if z is not None else np.random.normal(0, noise_std * 255, (h, w, 3))
+    elif name == "impulse_noise":
+        plan.data[i, s] = np.random.random((h, w))
+    elif name == "shot_noise":
+        img_array = np.asarray(frame).astype(np.float32)
+        scaled = img_array / 255.0 * _SEVERITY_TABLES[name][arg - 1]
+        plan.data[i, s] = np.random.poisson(scaled).astype(np.float64)
+
+
+def chain_plan(n: int, h: int, w: int, chains, device=None) -> ChainPlan:
+    """Draw for n h x w images what the per-image loop draws from `random` (every draw) and `np.random` (every draw up
+    to the first image holding shot_noise), in the loop's order, and resolve each step for the kernel.  Every chain
+    must be one the kernel takes (`chain_runs`).  No device work apart from numpy_stream's, which the loop makes too;
+    `device` is where gaussian_noise's device-drawn normals go (the current device by default)."""
+    per = _chains_per_image(chains, n)
+    if not all(_kernel_takes(c) for c in per):
+        raise ValueError("chain_plan: a chain holds shot_noise after a member that draws from np.random (see chain_runs)")
+    choice, uniform = random.choice, random.uniform
+    severities, sizes = [1, 2, 3, 4, 5], _MOTION_SIZES
+    members, args = [], []
+    for c in per:                                            # `random` draws, in loop order
+        names, vals = [], []
+        for name, arg in c:
+            if arg is None:
+                if name in _SEVERITY_TABLES:
+                    arg = choice(severities)
+                elif name == "motion_blur":
+                    arg = choice(sizes)
+                elif name in _FACTOR_RANGES:
+                    arg = uniform(*_FACTOR_RANGES[name])
+            names.append(name)
+            vals.append(arg)
+        members.append(names)
+        args.append(vals)
+    steps = max([1] + [len(c) for c in per])
+    index = np.full((n, steps), _NO_STEP, np.uint8)
+    factors = np.zeros((n, steps), np.float32)
+    keys, table = {}, []
+    for i in range(n):
+        for s, (name, arg) in enumerate(zip(members[i], args[i])):
+            key, ent = _entry(name, arg)
+            k = keys.get(key)
+            if k is None:
+                if len(table) == F.POOL_MAX_OPS:
+                    raise ValueError(f"more than {F.POOL_MAX_OPS} distinct member arguments in one batch")
+                k = keys[key] = len(table)
+                table.append(ent)
+            index[i, s] = k
+            if name in _FACTOR_RANGES:
+                factors[i, s] = ctypes.c_float(float(arg)).value
+    late = next((i for i in range(n) if "shot_noise" in members[i]), n)
+    split = np.array([len(m) for m in members], np.int64)
+    for i in range(late, n):
+        split[i] = next((s for s, name in enumerate(members[i]) if name in _NP_DRAWING), len(members[i]))
+    plan = ChainPlan(n, h, w, members, args, index, factors, table, {}, late, split)
+    for i in range(late):                                    # `np.random` draws that do not wait for pixels
+        for s in range(len(members[i])):
+            _draw_np(plan, i, s, None, device)
+    plan.finished = late == n
+    return plan
+
+
+def chain_plan_finish(plan: ChainPlan, frames, device=None) -> ChainPlan:
+    """The second plan step of a batch holding shot_noise: the np.random draws of images plan.late.. in loop order.
+    frames: host uint8 [n, h, w, 3], image i as it stands before step plan.split[i] (only images with a draw at
+    their split are read)."""
+    if plan.finished:
+        raise ValueError("chain_plan_finish: the plan has no draws left")
+    for i in range(plan.late, plan.n):
+        for s in range(int(plan.split[i]), len(plan.members[i])):
+            _draw_np(plan, i, s, frames[i] if s == plan.split[i] else None, device)
+    plan.finished = True
+    return plan
+
+
+def chain_workspace_bytes(n: int, h: int, w: int) -> int:
+    """Device workspace of a batch: 0 while both working frames fit in LDS (up to 164 x 164)."""
+    out = ctypes.c_size_t()
+    F.call("imgxf_pool_chain_workspace_bytes", n, h, w, ctypes.byref(out))
+    return out.value
+
+
+def _records(plan: ChainPlan, lo, hi):
+    """(records uint8 [n, rb], host payload arrays [(offset, array)], device payload tensors [(offset, tensor)],
+    payload bytes) of the launch that runs steps lo[i] .. hi[i] - 1 of every image."""
+    n = plan.n
+    width = max([1] + [int(b - a) for a, b in zip(lo, hi)])
+    rec = np.zeros((n, width, _STEP_BYTES), np.uint8)
+    rec[:, :, 0] = _NO_STEP
+    offs = np.zeros((n, width), np.uint64)
+    host, dev, size = [], [], 0
+    for on_device in (False, True):                          # host slices first: they go up in one copy
+        for i in range(n):
+            a, b = int(lo[i]), int(hi[i])
+            for s in range(a, b):
+                d = plan.data.get((i, s))
+                if d is None or isinstance(d, torch.Tensor) != on_device:
+                    continue
+                offs[i, s - a] = size
+                if on_device:
+                    dev.append((size, d))
+                    size += d.numel() * 8
+                else:
+                    host.append((size, np.ascontiguousarray(d, np.float64)))
+                    size += d.size * 8
+    for i in range(n):
+        a, b = int(lo[i]), int(hi[i])
+        rec[i, :b - a, 0] = plan.index[i, a:b]
+        rec[i, :b - a, 4:8] = plan.factors[i, a:b].view(np.uint8).reshape(-1, 4)
+    rec[:, :, 8:16] = offs.view(np.uint8).reshape(n, width, 8)
+    return rec.reshape(n, width * _STEP_BYTES), host, dev, size
+
+
+def _run(plan: ChainPlan, src: torch.Tensor, dst: torch.Tensor, lo, hi) -> None:
+    """One launch: steps lo[i] .. hi[i] - 1 of image i from src into dst ([n,h,w,3] uint8 on one device)."""
+    _launch_staged(src, dst, *_stage(plan, src.device, lo, hi))
+
+
+def _stage(plan: ChainPlan, device, lo, hi):
+    """Records and payload of one launch on the device, the operation table and the workspace."""
+    n, h, w = plan.n, plan.h, plan.w
+    rec, host, dev, payload_bytes = _records(plan, lo, hi)
+    rec_bytes = (rec.nbytes + 15) & ~15
+    staged = torch.empty(rec_bytes + sum(a.nbytes for _, a in host), dtype=torch.uint8, pin_memory=True)
+    buf = staged.numpy()
+    buf[:rec.nbytes] = rec.reshape(-1)
+    for off, a in host:
+        buf[rec_bytes + off:rec_bytes + off + a.nbytes] = a.reshape(-1).view(np.uint8)
+    gpu = torch.empty(rec_bytes + payload_bytes, dtype=torch.uint8, device=device)
+    gpu[:staged.numel()].copy_(staged, non_blocking=True)   # one host-to-device copy per launch
+    for off, t in dev:                                       # numpy_stream's normals are already on the device
+        gpu[rec_bytes + off:rec_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
+    ws_bytes = chain_workspace_bytes(n, h, w)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
+    op_tab = (F.PoolOp * max(1, len(plan.table)))()
+    for k, (code, arg, m) in enumerate(plan.table):
+        op_tab[k].code, op_tab[k].arg = code, arg
+        op_tab[k].m[:] = m
+    return gpu, rec.shape[1] // _STEP_BYTES, rec_bytes, payload_bytes, op_tab, max(1, len(plan.table)), ws, ws_bytes
+
+
+def _launch_staged(src, dst, gpu, steps, rec_bytes, payload_bytes, op_tab, nops, ws, ws_bytes) -> None:
+    ops._launch(src, "imgxf_pool_chain_u8", F.vp(F.view_of(src)), F.vp(F.view_of(dst)), op_tab, nops, gpu.data_ptr(),
+                steps, gpu.data_ptr() + rec_bytes if payload_bytes else None, payload_bytes,
+                ws.data_ptr() if ws is not None else None, ws_bytes)
+
+
+def _run_batched(x: torch.Tensor, out: torch.Tensor, chains) -> None:
+    n, h, w, _ = x.shape
+    plan = chain_plan(n, h, w, chains, x.device)
+    if not plan.table:                                       # no chain has a step: a copy
+        out.copy_(x)
+        return
+    if plan.finished:
+        _run(plan, x, out, np.zeros(n, np.int64), [len(m) for m in plan.members])
+        return
+    mid = torch.empty_like(out)
+    _run(plan, x, mid, np.zeros(n, np.int64), plan.split)
+    chain_plan_finish(plan, mid.cpu().numpy(), x.device)     # the frames before shot_noise come back for the Poisson draw
+    _run(plan, mid, out, plan.split, [len(m) for m in plan.members])
+
+
+def _run_loop(frame: torch.Tensor, chain) -> torch.Tensor:
+    img = Image.fromarray(frame.cpu().numpy())
+    for name, arg in chain:
+        fn = getattr(TransformationPool, name)
+        img = fn(img) if arg is None else fn(img, arg)
+    return torch.from_numpy(np.asarray(img).copy()).to(frame.device)
+
+
+def apply_chain_batch(frames: torch.Tensor, chains) -> torch.Tensor:
+    """The per-image loop of Individual.apply_transformations over a batch, in one kernel launch per run of images.
+
+    frames: uint8 [N,H,W,3] or one [H,W,3] RGB frame on the device, any row and frame stride (`_ffi.view_of`).
+    chains: one chain for every image, or a sequence of N chains; a chain is a sequence of at most 16 items, each a
+    member name ("defocus_blur") or a pair (name, argument); a bare name or argument None draws the member's default.
+    Returns a new contiguous uint8 tensor of the input's shape with the loop's pixels, and leaves `random` and
+    `np.random` as the loop leaves them.
+
+    A chain holding shot_noise runs in two launches: the frames before it come back to the host for the Poisson draw,
+    as the member makes it.  The kernel does not take a chain with shot_noise after a member that draws from
+    np.random (a second shot_noise included): walking the images in order, maximal runs of chains it takes run
+    batched, and each other image goes through the per-image loop in its place; draws and results stay the loop's.
+    Invalid arguments (an unknown member, a severity the member's table cannot index, a motion_blur size that
+    imgxf_conv2d_u8 rejects: even or above 15, a factor float() refuses) raise the member's exception class before any
+    draw or launch, with both generators untouched — the only deviation from the loop, which would have drawn for the
+    images before.  N == 0 draws nothing and launches nothing."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise ValueError("apply_chain_batch expects a device tensor (no CPU fallback)")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"apply_chain_batch expects uint8 frames, got {frames.dtype}")
+    if frames.dim() not in (3, 4) or frames.shape[-1] != 3 or frames.shape[-2] == 0 or frames.shape[-3] == 0:
+        raise ValueError(f"apply_chain_batch expects RGB [N,H,W,3] or [H,W,3] frames with H, W > 0, got {tuple(frames.shape)}")
+    x = frames.unsqueeze(0) if frames.dim() == 3 else frames
+    F.view_of(x)                                             # the layouts the kernel reads (ValueError otherwise)
+    n, h, w, _ = x.shape
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=x.device)
+    if n == 0:
+        return out
+    per = _chains_per_image(chains, n)                       # every check before the first draw
+    for a, b, batched in chain_runs(per, n):
+        if batched:
+            _run_batched(x[a:b], out[a:b], per[a:b])
+        else:
+            out[a] = _run_loop(x[a], per[a])
+    return out[0] if frames.dim() == 3 else out

@@ -294,6 +294,62 @@ int imgxf_augmix_f32(const float* src, int32_t n, int32_t h, int32_t w, const in
                      const void* plan, int32_t width, int32_t depth, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- TransformationPool chains on a batch  cifar_image_transformations.py:37-129,141-152 ------
+ * One launch runs a chain of TransformationPool members on each of n RGB uint8 frames, bit-identical
+ * to the per-image members of imagetransformations_amd.pool (one or two launches per member each).
+ *
+ * Operation table (HOST, copied into the launch): at most IMGXF_POOL_MAX_OPS entries.
+ *   DEFOCUS_BLUR        m[0] = GaussianBlur radius (as a float); 3 + 3 box passes with the box radius
+ *                       of imgxf_gaussian_blur_pil_u8;
+ *   ENHANCE_SHARPNESS   m[0..8] = 3x3 kernel, m[9] = scale (ImageFilter.SMOOTH: ImagingFilter3x3,
+ *                       border pixels copied), then the blend with the frame by the step's factor;
+ *   ENHANCE_CONTRAST    blend with the frame's solid int(mean(L) + 0.5) by the step's factor;
+ *   ENHANCE_COLOR       blend with convert('L') replicated to RGB by the step's factor;
+ *   ENHANCE_BRIGHTNESS  blend with black by the step's factor;
+ *   GAUSSIAN_NOISE      trunc(clip(f64(p) + z, 0, 255)), z = the step's float64 [h][w][3] slice;
+ *   IMPULSE_NOISE       m[0] = lo, m[1] = hi: mask < lo -> 0, mask > hi -> 255, mask = the step's
+ *                       float64 [h][w] slice;
+ *   SHOT_NOISE          m[0] = lambda > 0: trunc(clip(k / lambda * 255, 0, 255)), k = the step's float64
+ *                       [h][w][3] slice of Poisson counts (the frame itself is not read);
+ *   MOTION_BLUR         arg = size, odd, 1..31: one row of (float)(1/size) taps, REFLECT_101, rounded;
+ *   HISTOGRAM_EQUALIZATION  RGB -> YUV, cv2.equalizeHist on Y, YUV -> RGB (imgxf_rgb2yuv_u8 ...).
+ * Blends are Blend.c's float32 in1 + factor * (in2 - in1), truncated, clipped outside [0, 1].
+ *
+ * plan (DEVICE, 8-byte aligned): n records of imgxf_pool_chain_record_bytes(steps) bytes; step s is
+ *   uint8_t  op          operation-table index; indices >= nops run nothing
+ *   uint8_t  pad[3]
+ *   float    factor      the blend factor of the ENHANCE_* ops (the C float of the member's argument)
+ *   uint64_t offset      byte offset into payload of the step's float64 slice (noise ops; 8-aligned);
+ *                        a slice that does not lie inside payload_bytes runs nothing
+ * payload (DEVICE, 8-byte aligned, may be NULL when payload_bytes is 0): the noise ops' float64 data.
+ * src: n RGB frames (c == 3), any row and frame stride; dst: same geometry, must not overlap src.
+ * workspace (DEVICE, 16-byte aligned): imgxf_pool_chain_workspace_bytes(n, h, w) bytes.  It is 0
+ * when the two uint8 working frames stay in LDS, i.e. when
+ *     2 * R16(3*h*w) + 1344 <= 163840   (R16 = round up to 16),
+ * which admits every square frame up to 164 x 164; otherwise 2 * R16(3*h*w) * n bytes hold the
+ * working frames of every image and the same kernel runs on them.
+ * Errors: IMGXF_ERR_NULL (src, dst, ops; plan when n > 0; payload when payload_bytes > 0; a NULL
+ * workspace of sufficient workspace_bytes when one is needed), IMGXF_ERR_SHAPE (a bad view, c != 3,
+ * src and dst geometry differ), IMGXF_ERR_ARG (unknown op code, an argument outside its range,
+ * nops or steps out of range, a misaligned plan, payload or workspace), IMGXF_ERR_WORKSPACE
+ * (workspace_bytes short).  All checks happen on the host before any HIP call. */
+enum { IMGXF_POOL_DEFOCUS_BLUR = 0, IMGXF_POOL_ENHANCE_SHARPNESS = 1, IMGXF_POOL_ENHANCE_CONTRAST = 2,
+       IMGXF_POOL_ENHANCE_COLOR = 3, IMGXF_POOL_ENHANCE_BRIGHTNESS = 4, IMGXF_POOL_GAUSSIAN_NOISE = 5,
+       IMGXF_POOL_IMPULSE_NOISE = 6, IMGXF_POOL_SHOT_NOISE = 7, IMGXF_POOL_MOTION_BLUR = 8,
+       IMGXF_POOL_HISTOGRAM_EQUALIZATION = 9 };
+enum { IMGXF_POOL_MAX_OPS = 32, IMGXF_POOL_MAX_STEPS = 16, IMGXF_POOL_MAX_MOTION = 31 };
+typedef struct imgxf_pool_op {
+    int32_t code;   /* IMGXF_POOL_* */
+    int32_t arg;    /* MOTION_BLUR: size; 0 otherwise */
+    double  m[10];
+} imgxf_pool_op;
+/* Bytes of one plan record: 16 * steps, steps in 1..IMGXF_POOL_MAX_STEPS. */
+int imgxf_pool_chain_record_bytes(int32_t steps, size_t* bytes);
+int imgxf_pool_chain_workspace_bytes(int32_t n, int32_t h, int32_t w, size_t* bytes);
+int imgxf_pool_chain_u8(const imgxf_view* src, const imgxf_view* dst, const imgxf_pool_op* ops, int32_t nops,
+                        const void* plan, int32_t steps, const void* payload, size_t payload_bytes,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- TransformationPool.histogram_equalization  cifar_image_transformations.py:122-129 -------
  * cv2.cvtColor(RGB2YUV / YUV2RGB) for 8-bit images (integer BT.601, yuv_shift 14) and
  * cv2.equalizeHist applied to one channel of an interleaved view.  PARITY UNPINNED: OpenCV is not
