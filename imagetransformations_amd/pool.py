@@ -38,19 +38,10 @@ class TransformationPool:
         img_array = np.array(image)
         noise_std = [0.08, 0.12, 0.18, 0.26, 0.38][severity - 1]
         dev = _device()
-        z = None
-        if T.NOISE_RNG != "numpy-host" and img_array.size >= T.NOISE_DEVICE_MIN:    # the same doubles, computed on the device
-            from . import numpy_stream
-            state = np.random.get_state()
-            try:
-                got = numpy_stream.draw_on_device([(img_array.size, noise_std * 255)], dev, f64=True)
-            except ValueError:
-                np.random.set_state(state)
-                got = None
-            z = got[0].view(img_array.shape) if got is not None else None
+        z = T._numpy_noise([(img_array.size, noise_std * 255)], dev, f64=True)[0]    # the same doubles, computed on the device
         if z is None:
             z = torch.from_numpy(np.random.normal(0, noise_std * 255, img_array.shape)).to(dev)
-        return _download(ops.add_noise_f64(torch.from_numpy(img_array).to(dev), z))
+        return _download(ops.add_noise_f64(torch.from_numpy(img_array).to(dev), z.view(img_array.shape)))
 
     def impulse_noise(image, severity=None):
         """cifar_image_transformations.py:50-59."""
@@ -288,18 +279,7 @@ def _draw_np(plan: ChainPlan, i: int, s: int, frame, device) -> None:
     h, w = plan.h, plan.w
     if name == "gaussian_noise":
         noise_std = _SEVERITY_TABLES[name][arg - 1]
-        size = h * w * 3
-        z = None
-        if T.NOISE_RNG != "numpy-host" and size >= T.NOISE_DEVICE_MIN:    # the member's device branch
-            from . import numpy_stream
-            state = np.random.get_state()
-            try:
-                got = numpy_stream.draw_on_device([(size, noise_std * 255)], _device() if device is None else device,
-                                                  f64=True)
-            except ValueError:
-                np.random.set_state(state)
-                got = None
-            z = got[0] if got is not None else None
+        z = T._numpy_noise([(h * w * 3, noise_std * 255)], device, f64=True)[0]    # the member's device branch
         plan.data[i, s] = z if z is not None else np.random.normal(0, noise_std * 255, (h, w, 3))
     elif name == "impulse_noise":
         plan.data[i, s] = np.random.random((h, w))

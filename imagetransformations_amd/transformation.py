@@ -18,7 +18,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import ops, staging
+from . import batched, ops, staging
 
 # Where apply_all_transformations writes its JPEGs (the reference hard-codes a
 # /Users/... path at transformation.py:13-17).  None = do not write files.
@@ -193,20 +193,29 @@ def apply_gaussian_noise(img: Image.Image, noise_std: float) -> Image.Image:
     return _download(out)
 
 
-def _numpy_noise(requests, dev):
-    """[(count, scale)] -> float32 device tensors holding np.random.normal(0, scale, count).astype(float32) for each request,
-    np.random's state advanced accordingly; [None, ...] (state untouched) when the host has to draw: mode "numpy-host", or
-    numpy_stream's uncertainty guard."""
+def _numpy_noise(requests, dev=None, f64=False, deferred=False):
+    """[(count, scale)] -> device tensors holding np.random.normal(0, scale, count) for each request (cast to float32
+    unless `f64`), np.random's state advanced accordingly; [None, ...] (state untouched) when the host has to draw: mode
+    "numpy-host", fewer than NOISE_DEVICE_MIN normals in all, or numpy_stream's uncertainty guard.  Below that gate nothing
+    touches the device (`dev` None: the current device, looked up past the gate).
+    `deferred`: the generator starts now on a side stream (numpy_stream.PendingDraw) and a function comes back that gives
+    the list later — nothing else may use np.random in between; None when the gate leaves the draw to the host."""
     if NOISE_RNG == "numpy-host" or not requests or sum(n for n, _ in requests) < NOISE_DEVICE_MIN:
-        return [None] * len(requests)               # (a CIFAR image is 3072 normals: 50 us on the host, less than one launch)
+        return None if deferred else [None] * len(requests)   # (a CIFAR image is 3072 normals: 50 us on the host, less than one launch)
     from . import numpy_stream
+    dev = _device() if dev is None else dev
     state = np.random.get_state()
-    try:
-        got = numpy_stream.draw_on_device(requests, dev)
-    except ValueError:                                  # fewer accepted groups than 12 standard deviations allow for: the host draws
-        np.random.set_state(state)
-        got = None
-    return got if got is not None else [None] * len(requests)
+    draw = numpy_stream.PendingDraw(requests, dev, f64).result if deferred else \
+        (lambda: numpy_stream.draw_on_device(requests, dev, f64))
+
+    def finish():
+        try:
+            got = draw()
+        except ValueError:                              # fewer accepted groups than 12 standard deviations allow for: the host draws
+            np.random.set_state(state)
+            got = None
+        return got if got is not None else [None] * len(requests)
+    return finish if deferred else finish()
 
 
 # ------------------------------------------------------------------ translation (:284-307)
@@ -279,6 +288,7 @@ _DISPATCH = {
     'contrast': apply_contrast,
     'shear': apply_shear,
     'blur': apply_blur,
+    'translation': apply_translation,
 }
 
 
@@ -359,7 +369,7 @@ def apply_all_transformations(images):
     transformed_images = []
     for c0 in range(0, len(images), DRIVER_CHUNK):
         chunk = images[c0:c0 + DRIVER_CHUNK]
-        if all(_is_rgb(img) for img, _ in chunk):
+        if all(batched.is_rgb(img) for img, _ in chunk):
             transformed_images.extend(apply_all_transformations_batched(chunk))
         else:
             transformed_images.extend(apply_all_transformations_per_image(chunk, _progress=False))
@@ -376,8 +386,7 @@ def apply_all_transformations_per_image(images, _progress: bool = True):
     for i, (img, path) in enumerate(images):
         name = os.path.splitext(os.path.basename(path))[0]
         for transform_type, args, new_filename in plan_transformations(name):
-            fn = apply_translation if transform_type == 'translation' else _DISPATCH[transform_type]
-            transformed_img = fn(img, *args)
+            transformed_img = _DISPATCH[transform_type](img, *args)
             if output_dir is not None:
                 save_image(transformed_img, os.path.join(output_dir, new_filename))
             transformed_images.append(transformed_img)
@@ -462,23 +471,20 @@ SINK_FRAMES = 1024                                        # frames of one shape 
 SINK_BYTES = 2 << 30                                      # ... or this many bytes of them (4K frames: 86 per call), whichever comes first
 
 
-def _size_of(img):
-    """(width, height) of a PIL image or of an [H, W, 3] device frame (the device JPEG reader's output)."""
-    return (int(img.shape[1]), int(img.shape[0])) if isinstance(img, torch.Tensor) else img.size
+_TENSOR_FNS = {                                           # type -> the apply_<type> body on a [B, H, W, 3] device batch
+    'scale': _scale_t,
+    'rotation': _rotation_t,
+    'lighten_darken': lambda t, b: ops.brightness(t, 1.0 + b),
+    'contrast': lambda t, a: ops.scale_abs(t, a, 0.0),
+    'shear': _shear_t,
+    'translation': _translation_t,
+}
 
 
-def _is_rgb(img) -> bool:
-    return (img.dim() == 3 and img.shape[-1] == 3 and img.dtype == torch.uint8) if isinstance(img, torch.Tensor) else img.mode == 'RGB'
-
-
-def _collect(item, results) -> int:
-    """Wait for one queued copy back and build its PIL images; returns the bytes it held."""
-    dl, entries, *flag = item                             # (download, entries[, frames are RGBX for staging.image_from_rgbx])
-    rgbx = bool(flag and flag[0])
-    host = dl.numpy()
-    for j, (_, i, k) in enumerate(entries):
-        results[i][k] = staging.image_from_rgbx(host[j]) if rgbx else Image.fromarray(host[j])
-    return host.nbytes
+def _blur_group(batch: torch.Tensor, blur_radius: float):
+    """apply_blur on a batch; None for radius 0, where the reference hands back the input object itself (:245-246)."""
+    ksize = _blur_ksize(blur_radius)
+    return ops.gaussian_blur(batch, ksize, blur_radius, fixed_point=BLUR_FIXED_POINT) if ksize else None
 
 
 def apply_all_transformations_batched_named(images, _sink=None, _tee=False):
@@ -500,109 +506,53 @@ def apply_all_transformations_batched_named(images, _sink=None, _tee=False):
         plans.append(plan)
         for k, (transform_type, args, _) in enumerate(plan):
             if transform_type == 'gaussian_noise':      # same np.random stream as the per-image loop
-                w, h = _size_of(img)
+                w, h = batched.size_of(img)
                 if NOISE_RNG == "device":               # opt-in: one seed per image instead of h * w * 3 normals
                     noise[(i, k)] = _noise_seed()
                 else:
                     draws.append((i, k, (h, w, 3), args[0] * 255))
-    pending_noise = None
+    noise_later = None
     if draws:
         # nothing else touches np.random between these calls (the grid values come from `random`): one pass over the stream
         # on the device serves them all, or the host makes them one by one.  The MT19937 block kernel (one workgroup) starts
         # NOW on a side stream; the numbers are collected when the first noise group comes up, after the other transformation
-        # types have been queued (tensor_fns order puts 'gaussian_noise' wherever the reference's dict has it).
-        reqs = [(h * w * c, scale) for _, _, (h, w, c), scale in draws]
-        if NOISE_RNG != "numpy-host" and sum(n for n, _ in reqs) >= NOISE_DEVICE_MIN:
-            from . import numpy_stream
-            pending_noise = numpy_stream.PendingDraw(reqs, dev)
-        else:
+        # types have been queued (the noise groups of a size run last).
+        noise_later = _numpy_noise([(h * w * c, scale) for _, _, (h, w, c), scale in draws], dev, deferred=True)
+        if noise_later is None:
             for (i, k, shape, scale) in draws:
                 noise[(i, k)] = np.random.normal(0, scale, shape).astype(np.float32)
 
     def collect_noise():
-        nonlocal pending_noise
-        if pending_noise is None:
+        nonlocal noise_later
+        if noise_later is None:
             return
-        p, pending_noise = pending_noise, None
-        state = p.state
-        try:
-            got = p.result()
-        except ValueError:                              # (a margin of 12 standard deviations was too short: the host draws)
-            np.random.set_state(state)
-            got = None
-        for n_, ((i, k, shape, scale)) in enumerate(draws):
-            z = got[n_] if got is not None else None
+        got, noise_later = noise_later(), None
+        for z, (i, k, shape, scale) in zip(got, draws):
             noise[(i, k)] = z.view(shape) if z is not None else np.random.normal(0, scale, shape).astype(np.float32)
 
-    results = [[None] * len(p) for p in plans]
-    by_size = {}
-    for i, (img, _) in enumerate(images):
-        if _is_rgb(img):
-            by_size.setdefault(_size_of(img), []).append(i)
-        else:                                           # rare: keep the reference's behaviour exactly
-            for k, (transform_type, args, _) in enumerate(plans[i]):
-                if transform_type == 'gaussian_noise':
-                    raise NotImplementedError("batched driver expects RGB images (load_data converts them)")
-                fn = apply_translation if transform_type == 'translation' else _DISPATCH[transform_type]
-                results[i][k] = fn(img, *args)
+    def per_image(i):                                   # not 8-bit RGB, rare: keep the reference's behaviour exactly
+        out = []
+        for transform_type, args, _ in plans[i]:
+            if transform_type == 'gaussian_noise':
+                raise NotImplementedError("batched driver expects RGB images (load_data converts them)")
+            out.append(_DISPATCH[transform_type](images[i][0], *args))
+        return out
 
-    tensor_fns = {
-        'scale': _scale_t,
-        'rotation': _rotation_t,
-        'lighten_darken': lambda t, b: ops.brightness(t, 1.0 + b),
-        'contrast': lambda t, a: ops.scale_abs(t, a, 0.0),
-        'shear': _shear_t,
-        'translation': _translation_t,
-    }
-    pending, queued = [], 0                             # (Download, entries): results still on their way back
-    for size, members in by_size.items():
-        if all(isinstance(images[i][0], torch.Tensor) for i in members):            # already on the device (JPEG reader)
-            frames = torch.stack([images[i][0] for i in members])
-        else:
-            frames = staging.upload([np.asarray(images[i][0].cpu() if isinstance(images[i][0], torch.Tensor) else images[i][0])
-                                     for i in members], dev)                        # one pinned block, async H2D
-        groups = {}
-        for row, i in enumerate(members):
-            for k, (transform_type, args, _) in enumerate(plans[i]):
-                groups.setdefault((transform_type, args), []).append((row, i, k))
-        # (noise groups last: their numbers come from the side stream's generator, which runs meanwhile)
-        ordered = sorted(groups.items(), key=lambda g: g[0][0] == 'gaussian_noise')
-        for (transform_type, args), entries in ordered:
-            rows = torch.tensor([e[0] for e in entries], device=dev)
-            batch = frames.index_select(0, rows)
-            if transform_type == 'blur':
-                ksize = _blur_ksize(args[0])
-                if ksize == 0:
-                    for _, i, k in entries:
-                        results[i][k] = images[i][0]    # the input object itself (:245-246)
-                    continue
-                out = ops.gaussian_blur(batch, ksize, args[0], fixed_point=BLUR_FIXED_POINT)
-            elif transform_type == 'gaussian_noise' and NOISE_RNG == "device":
-                out = torch.empty_like(batch)           # every image has its own seed (as the per-image call draws it)
-                for j, (_, i, k) in enumerate(entries):
-                    out[j] = ops.add_noise_device(batch[j], args[0] * 255, noise[(i, k)])
-            elif transform_type == 'gaussian_noise':
-                collect_noise()
-                zs = [noise[(i, k)] for _, i, k in entries]
-                z = torch.stack(zs) if isinstance(zs[0], torch.Tensor) else staging.upload(zs, dev)
-                out = ops.add_noise(batch, z)
-            else:
-                out = tensor_fns[transform_type](batch, *args)
-            if _sink is not None:
-                _sink(out, [plans[i][k][2] for _, i, k in entries])
-                if not _tee:
-                    continue
-            # queue the copy back and keep launching: the host waits per result only when it builds the images.
-            # The window of copies in flight is bounded (staging.PENDING_BUDGET bytes of pinned memory): beyond
-            # it the oldest results are turned into images before the next group is queued
-            # RGB frames go back as RGBX and become PIL images that share the pinned block (staging.image_from_rgbx)
-            rgbx = out.dim() == 4 and out.shape[-1] == 3 and out.dtype == torch.uint8 and \
-                staging.zero_copy_reserve(out.shape[0] * out.shape[1] * out.shape[2] * 4)
-            pending.append((staging.download(ops.permute_channels(out, (0, 1, 2, 2)) if rgbx else out), entries, rgbx))
-            queued += out.numel()
-            while queued > staging.PENDING_BUDGET and len(pending) > 1:
-                queued -= _collect(pending.pop(0), results)
-    while pending:
-        _collect(pending.pop(0), results)
+    def run_group(transform_type, args, batch, entries):
+        if transform_type == 'blur':
+            return _blur_group(batch, args[0])
+        if transform_type == 'gaussian_noise' and NOISE_RNG == "device":
+            out = torch.empty_like(batch)               # every image has its own seed (as the per-image call draws it)
+            for j, (_, i, k) in enumerate(entries):
+                out[j] = ops.add_noise_device(batch[j], args[0] * 255, noise[(i, k)])
+            return out
+        if transform_type == 'gaussian_noise':
+            collect_noise()
+            zs = [noise[(i, k)] for _, i, k in entries]
+            return ops.add_noise(batch, torch.stack(zs) if isinstance(zs[0], torch.Tensor) else staging.upload(zs, dev))
+        return _TENSOR_FNS[transform_type](batch, *args)
 
+    # (noise groups last: their numbers come from the side stream's generator, which runs meanwhile)
+    results = batched.run_grouped([img for img, _ in images], plans, dev, run_group, order=lambda g: g[0] == 'gaussian_noise',
+                                  other=per_image, sink=_sink, tee=_tee)
     return [(new_filename, results[i][k]) for i, plan in enumerate(plans) for k, (_, _, new_filename) in enumerate(plan)]

@@ -15,7 +15,8 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import ops, staging
+from . import batched, ops, staging
+from . import transformation as T
 from .transformation import (_download, _upload, apply_blur, apply_brightness, apply_contrast,  # noqa: F401
                              apply_gaussian_noise, apply_rotation, apply_scale, apply_shear,
                              apply_translation)
@@ -103,6 +104,7 @@ _DISPATCH = {
     'scale': apply_scale, 'rotation': apply_rotation, 'lighten_darken': apply_brightness,
     'gaussian_noise': apply_gaussian_noise, 'contrast': apply_contrast, 'shear': apply_shear,
     'blur': apply_blur, 'zoom': apply_random_zoom, 'perspective_warp': apply_perspective_warp,
+    'translation': apply_translation, 'vert_flip': vert_flip,
 }
 
 
@@ -119,8 +121,7 @@ def apply_all_transformations(images):
                 new_filename = f"{name}_{transform_type}_corrupted{ext}"
                 transformed_img = vert_flip(img) if transform_type == 'vert_flip' else rand_crop(img)
             else:
-                num_steps = int((params['max'] - params['min']) / params['step']) + 1
-                possible_values = [params['min'] + j * params['step'] for j in range(num_steps)]
+                possible_values = T.grid_values(params)
                 if transform_type == 'translation':
                     tx = random.choice(possible_values)
                     ty = random.choice(possible_values)
@@ -145,9 +146,7 @@ def apply_all_transformations_batched(images):
     the same output order — but every image is uploaded once and all RGB images of one size that
     drew the same (type, value) go through one batched launch (perspective warps and crops of one
     size share a launch with per-frame coefficients / windows).  images: [(PIL image, name)]."""
-    from . import transformation as T
-    from .transformation import (_blur_ksize, _device, _rotation_t, _scale_t, _shear_t, _translation_t)
-    dev = _device()
+    dev = T._device()
     # ---- draws, image by image, in the order the per-image loop makes them
     plans, extra = [], {}
     for i, (img, name) in enumerate(images):
@@ -161,14 +160,15 @@ def apply_all_transformations_batched(images):
                 extra[(i, len(plan))] = (np.random.randint(0, w - cs + 1), np.random.randint(0, h - cs + 1), cs)
                 plan.append((transform_type, (), f"{name}_{transform_type}_corrupted.jpg"))
             else:
-                num_steps = int((params['max'] - params['min']) / params['step']) + 1
-                possible_values = [params['min'] + j * params['step'] for j in range(num_steps)]
+                possible_values = T.grid_values(params)
                 if transform_type == 'translation':
                     tx, ty = random.choice(possible_values), random.choice(possible_values)
                     plan.append((transform_type, (tx, ty), f"{name}_{transform_type}_{tx}_{ty}_corrupted.jpg"))
                     continue
                 value = random.choice(possible_values)
                 if transform_type == 'gaussian_noise':
+                    # (on the host, image by image: rand_crop's randint calls come between one image's normals and the
+                    # next one's on the same np.random stream, so they cannot be pooled into one device draw)
                     shape = np.array(img).shape
                     extra[(i, len(plan))] = np.random.normal(0, value * 255, shape).astype(np.float32)
                 elif transform_type == 'perspective_warp':
@@ -176,75 +176,40 @@ def apply_all_transformations_batched(images):
                 plan.append((transform_type, (value,), f"{name}_{transform_type}_{value}_corrupted.jpg"))
         plans.append(plan)
 
-    results = [[None] * len(p) for p in plans]
-    by_size = {}
-    for i, (img, _) in enumerate(images):
-        if img.mode == 'RGB':
-            by_size.setdefault(img.size, []).append(i)
-        else:                                           # rare: the per-image bodies, with the draws made above
-            for k, (transform_type, args, _) in enumerate(plans[i]):
-                t = _upload(img)
-                if transform_type == 'gaussian_noise':
-                    results[i][k] = _download(ops.add_noise(t, torch.from_numpy(extra[(i, k)]).to(dev)))
-                elif transform_type == 'perspective_warp':
-                    results[i][k] = _download(ops.perspective(t, extra[(i, k)]))
-                elif transform_type == 'rand_crop':
-                    x, y, cs = extra[(i, k)]
-                    results[i][k] = _download(ops.resize(ops.crop(t, (x, y, x + cs, y + cs)), (32, 32), ops.RESAMPLE_BICUBIC))
-                elif transform_type == 'vert_flip':
-                    results[i][k] = vert_flip(img)
-                elif transform_type == 'translation':
-                    results[i][k] = apply_translation(img, *args)
-                else:
-                    results[i][k] = _DISPATCH[transform_type](img, *args)
+    def crop(t, i, k):
+        x, y, cs = (int(v) for v in extra[(i, k)])
+        return ops.crop(t, (x, y, x + cs, y + cs))
 
-    tensor_fns = {
-        'scale': _scale_t, 'zoom': _scale_t, 'rotation': _rotation_t, 'shear': _shear_t,
-        'lighten_darken': lambda t, b: ops.brightness(t, 1.0 + b),
-        'contrast': lambda t, a: ops.scale_abs(t, a, 0.0),
-        'translation': _translation_t,
-        'vert_flip': lambda t: ops.flip(t),
-    }
-    pending, queued = [], 0                                      # (Download, entries): results still on their way back
-    for size, members in by_size.items():
-        frames = staging.upload([np.asarray(images[i][0]) for i in members], dev)     # one pinned block, async H2D
-        groups = {}
-        for row, i in enumerate(members):
-            for k, (transform_type, args, _) in enumerate(plans[i]):
-                key = (transform_type, args) if transform_type not in ('perspective_warp', 'rand_crop') else (transform_type, ())
-                groups.setdefault(key, []).append((row, i, k))
-        for (transform_type, args), entries in groups.items():
-            rows = torch.tensor([e[0] for e in entries], device=dev)
-            batch = frames.index_select(0, rows)
-            if transform_type == 'blur':
-                ksize = _blur_ksize(args[0])
-                if ksize == 0:
-                    for _, i, k in entries:
-                        results[i][k] = images[i][0]    # the input object itself, as the reference returns it
-                    continue
-                out = ops.gaussian_blur(batch, ksize, args[0], fixed_point=T.BLUR_FIXED_POINT)
-            elif transform_type == 'gaussian_noise':
-                z = staging.upload([extra[(i, k)] for _, i, k in entries], dev)
-                out = ops.add_noise(batch, z)
+    def per_image(i):                                   # not 8-bit RGB, rare: the per-image bodies, with the draws made above
+        img, out = images[i][0], []
+        for k, (transform_type, args, _) in enumerate(plans[i]):
+            if transform_type == 'gaussian_noise':
+                out.append(_download(ops.add_noise(_upload(img), torch.from_numpy(extra[(i, k)]).to(dev))))
             elif transform_type == 'perspective_warp':
-                out = ops.perspective(batch, [extra[(i, k)] for _, i, k in entries])
+                out.append(_download(ops.perspective(_upload(img), extra[(i, k)])))
             elif transform_type == 'rand_crop':
-                # crops differ per image but share their size: gather them, then one resize launch
-                crops = []
-                for j, (_, i, k) in enumerate(entries):
-                    x, y, cs = (int(v) for v in extra[(i, k)])
-                    crops.append(ops.crop(batch[j], (x, y, x + cs, y + cs)))
-                out = ops.resize(torch.stack(crops), (32, 32), ops.RESAMPLE_BICUBIC)
+                out.append(_download(ops.resize(crop(_upload(img), i, k), (32, 32), ops.RESAMPLE_BICUBIC)))
             else:
-                out = tensor_fns[transform_type](batch, *args)
-            pending.append((staging.download(out), entries))    # async copy back; the host waits per result below
-            queued += out.numel()
-            while queued > staging.PENDING_BUDGET and len(pending) > 1:      # bounded window of pinned copies in flight
-                queued -= T._collect(pending.pop(0), results)
+                out.append(_DISPATCH[transform_type](img, *args))
+        return out
 
-    while pending:
-        T._collect(pending.pop(0), results)
+    def run_group(transform_type, args, batch, entries):
+        if transform_type == 'blur':
+            return T._blur_group(batch, args[0])
+        if transform_type == 'gaussian_noise':
+            return ops.add_noise(batch, staging.upload([extra[(i, k)] for _, i, k in entries], dev))
+        if transform_type == 'perspective_warp':
+            return ops.perspective(batch, [extra[(i, k)] for _, i, k in entries])
+        if transform_type == 'rand_crop':               # crops differ per image but share their size: gather them, then one resize launch
+            crops = torch.stack([crop(batch[j], i, k) for j, (_, i, k) in enumerate(entries)])
+            return ops.resize(crops, (32, 32), ops.RESAMPLE_BICUBIC)
+        if transform_type == 'vert_flip':
+            return ops.flip(batch)
+        return T._TENSOR_FNS['scale' if transform_type == 'zoom' else transform_type](batch, *args)
 
+    # perspective warps and crops of one size share a launch whatever they drew (per-frame coefficients / windows)
+    results = batched.run_grouped([img for img, _ in images], plans, dev, run_group, other=per_image,
+                                  key=lambda t, args: (t, () if t in ('perspective_warp', 'rand_crop') else args))
     transformed_images = []
     for i, plan in enumerate(plans):
         for k, (_, _, new_filename) in enumerate(plan):

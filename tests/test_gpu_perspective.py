@@ -157,7 +157,9 @@ def test_batched_twelve_transformation_driver_equals_per_image_driver(device):
     per-image loop (fall_2025/transformations_code:68-155), for mixed image sizes."""
     from imagetransformations_amd import transformations_code as TC
     imgs = [(Image.fromarray(synth(70 + i, *hw)), f"cifar10_test_{i}_label_{i % 10}")
-            for i, hw in enumerate([(32, 32), (64, 64), (32, 32), (50, 61), (64, 64), (32, 32), (32, 32)])]   # rand_crop needs h >= int(0.78 w)
+            for i, hw in enumerate([(32, 32), (64, 64), (32, 32), (50, 61), (64, 64), (32, 32), (32, 32),
+                                    (320, 320), (320, 320)])]   # rand_crop needs h >= int(0.78 w); 320 x 320 results are past
+                                                                # staging.SMALL: the pinned, asynchronous copy back and RGBX images
     for seed in (0, 1):
         random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)
         a = TC.apply_all_transformations(imgs)
