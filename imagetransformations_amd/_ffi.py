@@ -162,6 +162,8 @@ SIGNATURES = {
     "imgxf_jpeg_decode_color_ext": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "imgxf_percentile_mask_u8":[_VP, C.c_void_p, C.c_double, _VP, C.c_void_p, C.c_void_p],
     "imgxf_dilate_cross_u8": [_VP, _VP, C.c_int, C.c_void_p],
+    "imgxf_preprocess_list_layout_host": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "imgxf_preprocess_list_f32": [C.c_void_p, C.c_void_p, C.c_void_p, _F, _F, C.c_void_p],
 }
 
 

@@ -8,6 +8,7 @@
 // torch.  `mask` (optional) receives 1 where the value before the clamp lay in [0,1] — the set on
 // which torch.clamp's backward lets the gradient through.  16 bytes per lane, grid-stride.
 #include "imgxf_common.h"
+#include "to_tensor_math.h"
 
 namespace imgxf {
 
@@ -65,15 +66,7 @@ static int launch_f32_map(const float* src, const float* noise, float* dst, u8* 
 // ToTensor (+ Normalize): uint8 HWC -> float32 CHW, x/255 correctly rounded (Tensor.div(255)),
 // then (x - mean[c]) / std[c] as two fp32 operations (Tensor.sub_ / div_), the model-input step
 // that follows the transformations in every evaluation script of the reference
-// (e.g. fall_2025/transformations_code:57 ToTensor; T.Normalize at 68 call sites).
-struct NormArgs { float mean[4], std[4]; int normalize; };
-
-__device__ __forceinline__ float unit255f(u32 b) {
-    const float v = (float)b, r = __uint_as_float(0x3b808081u);      // RN(1/255); one residual step makes it exact
-    const float q = v * r;
-    return fmaf(fmaf(-255.0f, q, v), r, q);
-}
-
+// (e.g. fall_2025/transformations_code:57 ToTensor; T.Normalize at 68 call sites); the arithmetic is to_tensor_math.h's.
 template <int C>
 __global__ __launch_bounds__(256) void to_tensor_kernel(View s, float* __restrict__ dst, NormArgs a) {
     const int64_t plane = (int64_t)s.h * s.w;
@@ -86,9 +79,7 @@ __global__ __launch_bounds__(256) void to_tensor_kernel(View s, float* __restric
         float* dp = dst + (int64_t)f * C * plane + (int64_t)y * s.w + x;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            float v = unit255f(sp[c]);
-            if (a.normalize) v = (v - a.mean[c]) / a.std[c];
-            dp[c * plane] = v;
+            dp[c * plane] = to_tensor_value(sp[c], a, c);
         }
     }
 }
@@ -105,12 +96,7 @@ IMGXF_API int imgxf_to_tensor_f32(const imgxf_view* src, float* dst, const float
     if (((uintptr_t)dst) & 3) return IMGXF_ERR_ARG;
     if ((mean == nullptr) != (std == nullptr)) return IMGXF_ERR_NULL;
     if (src->c == 2) return IMGXF_ERR_UNSUPPORTED;
-    NormArgs a;
-    a.normalize = mean != nullptr;
-    for (int c = 0; c < 4; ++c) {
-        a.mean[c] = a.normalize && c < src->c ? mean[c] : 0.0f;
-        a.std[c] = a.normalize && c < src->c ? std[c] : 1.0f;
-    }
+    const NormArgs a = make_norm_args(mean, std, src->c);
     const View s = make_view(src);
     const int64_t total = (int64_t)s.n * s.h * s.w;
     int64_t blocks = (total + 255) / 256;

@@ -80,6 +80,18 @@ def _decode_on_device(read):
     return out
 
 
+def load_preprocessed(paths: Sequence[str], resize: int = 256, crop: int = 224, mean=None, std=None, workers: int = 8):
+    """From file names to a model input in one call: the files are read on a thread pool, decoded on the device as one
+    chunk (`_decode_on_device`: a file the device reader refuses or finds damaged goes to Pillow, one Pillow cannot open
+    is skipped with the reference's message) and preprocessed by `tensor_maps.preprocess_list` in one launch.
+    Returns (float32 [N, 3, crop, crop], the paths of the N files kept, in order)."""
+    from . import tensor_maps
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        read = list(pool.map(_read, paths))
+    items = _decode_on_device(read)
+    return tensor_maps.preprocess_list([t for t, _ in items], resize, crop, mean, std), [p for _, p in items]
+
+
 def _chunks(seq: Sequence, n: int) -> Iterable[Sequence]:
     for i in range(0, len(seq), n):
         yield seq[i:i + n]

@@ -715,6 +715,47 @@ int imgxf_jpeg_decode_idct_ext(const int16_t* coefs, const imgxf_jpeg_dec_image_
 int imgxf_jpeg_decode_color_ext(const uint8_t* planes, const imgxf_jpeg_dec_image_ext* images, const imgxf_jpeg_dec_image_ext* images_host,
                                 int n, uint8_t* out, void* stream);
 
+/* ---- the evaluation preprocessing of the reference's ImageNet scripts on a LIST of frames of different sizes ----------
+ * transforms.Compose([Resize(r), CenterCrop(crop), ToTensor(), Normalize(mean, std)]) on each RGB frame of a list, as
+ * Pillow / torchvision compute it on PIL images (BILINEAR Image.resize: horizontal pass, uint8 intermediate, vertical
+ * pass, 22-bit coefficients; only the crop window is filtered), all frames in ONE launch.  The HOST lays out one block
+ *     imgxf_preprocess_header | imgxf_preprocess_frame[n] | imgxf_preprocess_unit[n_units] | int32 tables
+ * which the caller copies to the device once; offsets of tables are int32 indices into the block. */
+typedef struct imgxf_preprocess_header {
+    int32_t n_frames, n_units, crop;
+    int32_t lds_bytes;          /* the largest unit's LDS need = the launch's dynamic LDS size */
+    int32_t frames_off, units_off, tables_off, total_bytes;   /* byte offsets of the sections, size of the block */
+} imgxf_preprocess_header;
+typedef struct imgxf_preprocess_frame {
+    uint64_t data;              /* DEVICE address of pixel (0, 0); filled by the caller, as is row_stride (bytes, >= 3 w) */
+    int64_t  row_stride;
+    int32_t  h, w;
+    int32_t  ksx, ksy;          /* taps per output column / row (row length of the coefficient tables) */
+    int32_t  bounds_x, coeffs_x, bounds_y, coeffs_y;   /* [crop][2] (first source index, count), [crop][ks]; frames of
+                                   equal geometry share them */
+    int32_t  row0, nrows, col0, ncols;   /* the source rows / columns the crop window touches */
+    int32_t  unit_rows;         /* output rows per work unit; 0: the frame exceeds the LDS budget and has no units */
+    int32_t  pad_;
+} imgxf_preprocess_frame;
+typedef struct imgxf_preprocess_unit {
+    int32_t frame, y0, ny;      /* one workgroup: output rows [y0, y0 + ny) of the crop window of frame `frame` */
+    int32_t lds_bytes;          /* touched source rows x 12 ceil(crop / 4) (rounded up to 16) + 4 staged source-row spans */
+} imgxf_preprocess_unit;
+/* HOST half (no device work).  geometry: int32 [n][6] = (h, w, nh, nw, left, top) per frame — source size, size after
+ * Resize, crop offsets (the caller states torchvision's rule).  The tables are precompute_coeffs' for (w -> nw) and
+ * (h -> nh), rows [left, left + crop) / [top, top + crop).  A unit takes up to 16 output rows, fewer where their touched
+ * source rows would not fit half of lds_budget bytes (three quarters, then the whole of it, where not even one row fits
+ * the smaller step; lds_budget is capped at 64 KiB, so that two workgroups fit a CU); a frame of which not even one row fits gets unit_rows = 0.  *block_bytes receives the block's size; block == NULL: only that.
+ * Errors: IMGXF_ERR_NULL; IMGXF_ERR_ARG for n < 0, crop < 1, lds_budget < 1, a size < 1, h or w > 32767, nh or nw > 2^24, a window outside the
+ * resized image; IMGXF_ERR_WORKSPACE when block_cap is too small. */
+int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, int crop, int lds_budget, void* block,
+                                      size_t block_cap, size_t* block_bytes);
+/* The launch: block_host is the caller's host copy of the block (its records are checked before the launch), block_dev
+ * the same bytes on the device (8-byte aligned).  out: float32 [n][3][crop][crop], contiguous; slots of frames without
+ * units are not written.  mean / std: HOST float[3], both or neither. */
+int imgxf_preprocess_list_f32(const void* block_host, const void* block_dev, float* out, const float* mean,
+                              const float* std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
