@@ -6,16 +6,22 @@
 //                           16 MCUs (16×256 px) per workgroup staged through LDS, one thread per 8×8 block, zigzag
 //                           int16 coefficients in MCU order (6 blocks per MCU), 16-byte pieces interleaved over groups
 //                           of 64 blocks, plus, per block, its DC value and the bits its AC symbols will take
-//   jpeg_lens_kernel        bits per block (DC difference code + AC bits)               → exclusive scan = bit offsets
+//   jpeg_lens_kernel<L, OPT>   bits per block (DC difference code + AC bits)            → exclusive scan = bit offsets
 //   jpeg_zero_kernel        clears the stream words the emit kernel ORs into
-//   jpeg_emit_kernel        one thread per block walks its coefficients; a workgroup's 256 blocks form one contiguous
-//                           span of the stream, merged in LDS and stored whole (atomics only on the two shared words)
+//   jpeg_emit_kernel<L, OWN>   one thread per block walks its coefficients; a workgroup's 256 blocks form one contiguous
+//                           span of the stream, merged in LDS and stored whole (span_write: atomics only on the two shared words)
 //   jpeg_ffcount / jpeg_stuff_kernel   0xFF → 0xFF 0x00 byte stuffing (count per 32-byte chunk on words, scan, expand
 //                           in LDS, coalesced stores), header, padding of the last byte with 1-bits, EOI, file size
+//
+// These stages and the host side serve every file the writer makes: L is the layout (4:2:0, 4:2:2, 4:4:4, grayscale;
+// jpeg_encode_ext.inc has the other layouts' transform), OPT / OWN the frame's own Huffman tables (optimize), and
+// jpeg_stuff_scan_kernel writes a scan behind its own DHT segments and SOS (optimize: one scan; jpeg_encode_prog.inc:
+// the progressive script).  The default file is <JL420, false> and jpeg_stuff_kernel.
 //
 // Integer arithmetic throughout: bit-identical to the library (tests/test_gpu_jpeg.py compares whole files).
 #include "imgxf_common.h"
 #include <string.h>
+#include <type_traits>
 
 namespace imgxf {
 
@@ -246,156 +252,196 @@ __global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __r
     }
 }
 
-// ---- entropy coding -------------------------------------------------------------------------------------------------
+// ---- layouts and block order ----------------------------------------------------------------------------------------
+
+enum { JL420 = 0, JL422 = 1, JL444 = 2, JLGRAY = 3 };
+constexpr int JXP = 512;                     // pixels per row of a jpeg_transform_ex_kernel strip (one MCU row of 8 rows)
+
+template <int L>
+struct JLay {
+    static constexpr int NY = L == JL420 ? 4 : L == JL422 ? 2 : 1;        // luminance blocks per MCU
+    static constexpr int B = NY + (L == JLGRAY ? 0 : 2);                   // blocks per MCU
+    static constexpr int MW = L == JL420 || L == JL422 ? 16 : 8;           // MCU width / height in pixels
+    static constexpr int MH = L == JL420 ? 16 : 8;
+    static constexpr int NC = L == JLGRAY ? 1 : 3;                         // input channels
+    static constexpr int CW = L == JL422 ? JXP / 2 : JXP;                  // chrominance samples per strip row
+    static constexpr int T = JXP / 8 + (NC == 3 ? 2 * CW / 8 : 0);         // one thread per block: 192, 128, 64
+};
 
 struct JpegGeom {
     int mw, mh, bw, bh, nblk;
 };
 
 // jccoefct.c compress_data: block k of an MCU is a dummy (zero AC, DC of the block before it) when it lies past the
-// component's last real block row / column; returns the block whose DC it carries.
+// component's last real block row / column; returns the block whose DC it carries.  4:2:0 has dummy rows and columns;
+// 4:2:2 only the right-hand luminance block of an MCU past the last block column (it carries the DC of the block to its
+// left); 4:4:4 and grayscale have none.
+template <int L>
 __device__ __forceinline__ int dc_source(const JpegGeom& g, int mx, int my, int k, bool& dummy) {
-    dummy = false;
-    if (k >= 4) return k;
-    const int yi = k >> 1, xi = k & 1;
-    const bool rowok = 2 * my + yi < g.bh, colok = 2 * mx + xi < g.bw;
-    if (rowok && colok) return k;
-    dummy = true;
-    if (!rowok) return (2 * mx + 1 < g.bw) ? 1 : 0;          // a whole dummy row: DC of the top row's last real block
-    return k - 1;                                              // right edge: the block to its left
+    if (L == JL420) {
+        dummy = false;
+        if (k >= 4) return k;
+        const int yi = k >> 1, xi = k & 1;
+        const bool rowok = 2 * my + yi < g.bh, colok = 2 * mx + xi < g.bw;
+        if (rowok && colok) return k;
+        dummy = true;
+        if (!rowok) return (2 * mx + 1 < g.bw) ? 1 : 0;      // a whole dummy row: DC of the top row's last real block
+        return k - 1;                                          // right edge: the block to its left
+    }
+    dummy = L == JL422 && k == 1 && 2 * mx + 1 >= g.bw;
+    return dummy ? 0 : k;
 }
 
 // DC value carried by block k of MCU (mx, my), and the one the DC difference is taken against (the block of the same
 // component before it in scan order; 0 at the start of the frame).
+template <int L>
 __device__ __forceinline__ int block_dc(const int16_t* __restrict__ dcs, const JpegGeom& g, int mcu, int mx, int my, int k, bool& dummy) {
-    return dcs[(int64_t)mcu * 6 + dc_source(g, mx, my, k, dummy)];
+    return dcs[(int64_t)mcu * JLay<L>::B + dc_source<L>(g, mx, my, k, dummy)];
 }
+template <int L>
 __device__ __forceinline__ int block_pred(const int16_t* __restrict__ dcs, const JpegGeom& g, int mcu, int mx, int my, int k) {
+    constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
     bool pd;
-    if (k >= 4) return mcu > 0 ? dcs[(int64_t)(mcu - 1) * 6 + k] : 0;
-    if (k > 0) return block_dc(dcs, g, mcu, mx, my, k - 1, pd);
+    if (k >= NY) return mcu > 0 ? dcs[(int64_t)(mcu - 1) * B + k] : 0;
+    if (k > 0) return block_dc<L>(dcs, g, mcu, mx, my, k - 1, pd);
     if (mcu == 0) return 0;
     const int pm = mcu - 1, pmy = pm / g.mw, pmx = pm - pmy * g.mw;
-    return block_dc(dcs, g, pm, pmx, pmy, 3, pd);
+    return block_dc<L>(dcs, g, pm, pmx, pmy, NY - 1, pd);
 }
 
-// bits of every block: DC category code + magnitude bits + the AC bits the transform kernel counted (EOB for a dummy)
-__global__ __launch_bounds__(256) void jpeg_lens_kernel(const int16_t* __restrict__ dcs, const uint16_t* __restrict__ acbits,
-                                                        u32* __restrict__ lens, JpegGeom g, JpegHuff hf) {
-    const int j = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
-    if (j >= g.nblk) return;
-    const int mcu = j / 6, k = j - mcu * 6, my = mcu / g.mw, mx = mcu - my * g.mw;
-    const int16_t* dd = dcs + (int64_t)f * g.nblk;
-    bool dummy;
-    const int diff = block_dc(dd, g, mcu, mx, my, k, dummy) - block_pred(dd, g, mcu, mx, my, k);
-    const int sg = diff >> 31, t = k >= 4 ? 1 : 0;
-    const u32 cat = 32 - (u32)__clz((diff ^ sg) - sg);
-    lens[(int64_t)f * g.nblk + j] = (hf.dc[t][cat] >> 16) + cat + (dummy ? hf.ac[t][0] >> 16 : (u32)acbits[(int64_t)f * g.nblk + j]);
+// ---- entropy coding -------------------------------------------------------------------------------------------------
+
+// jchuff.c encode_one_block's AC symbols of one block (coefficients interleaved as the transform kernels store them, so
+// that a wave's loads are consecutive 16-byte pieces): sym(symbol, coefficient, size) for every ZRL (0xF0),
+// (run << 4) | size and the final EOB (0x00).
+template <typename F>
+__device__ __forceinline__ void ac_symbols(const uint4* __restrict__ blk, F&& sym) {
+    u32 run = 0;
+    uint4 nxt = blk[0];
+    for (int g8 = 0; g8 < 8; ++g8) {
+        const uint4 cur = nxt;
+        if (g8 < 7) nxt = blk[(g8 + 1) * 64];
+        const u32 pairs[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const u32 pair = pairs[u];
+            const bool dcpair = g8 == 0 && u == 0;
+            if ((dcpair ? pair >> 16 : pair) == 0) {              // most of a photograph's coefficients
+                run += dcpair ? 1 : 2;
+                continue;
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (dcpair && h == 0) continue;
+                const int c = (int)(int16_t)(pair >> (16 * h));
+                if (c == 0) {
+                    ++run;
+                    continue;
+                }
+                for (u32 z = run >> 4; z > 0; --z) sym(0xF0u, 0, 0u);
+                const int sg = c >> 31;
+                const u32 cat = 32 - (u32)__clz((c ^ sg) - sg);
+                sym(((run & 15) << 4) | cat, c, cat);
+                run = 0;
+            }
+        }
+    }
+    if (run) sym(0u, 0, 0u);
 }
 
-// One thread per block: the coefficients come interleaved over 64 blocks (see jpeg_transform_kernel), so a wave's
-// loads are consecutive dwords; every thread walks its block and writes the codes MSB-first at the block's bit offset:
-// the first word it touches is shared with the previous block (atomic OR), the words after it are its own (plain
-// stores), the last partial word is shared with the next block (atomic OR).
-__global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
-                                                        const u32* __restrict__ offs, u32* __restrict__ stream, int64_t stream_fs_words,
-                                                        const u32* __restrict__ total_bits, JpegGeom g, JpegHuff hf) {
-    constexpr u32 LW = JLW;
+__device__ __forceinline__ u32 dc_category(int diff) {
+    const int sg = diff >> 31;
+    return 32 - (u32)__clz((diff ^ sg) - sg);
+}
+
+// Frame f's code words (code | len << 16) in LDS: the frame's own (fh, optimize) with OWN, else the call's (hf).
+// (the kernel argument is read in place: a pointer to it would make the compiler copy it to scratch)
+template <bool OWN>
+__device__ __forceinline__ void load_huff(u32 (*sdc)[16], u32 (*sac)[256], const JpegHuff& hf, const JpegHuff* __restrict__ fh, int f) {
+    for (int i = threadIdx.x; i < 32; i += 256) sdc[i >> 4][i & 15] = OWN ? fh[f].dc[i >> 4][i & 15] : hf.dc[i >> 4][i & 15];
+    for (int i = threadIdx.x; i < 512; i += 256) sac[i >> 8][i & 255] = OWN ? fh[f].ac[i >> 8][i & 255] : hf.ac[i >> 8][i & 255];
+}
+
+// bits of every block: DC category code + magnitude bits + the AC bits (EOB for a dummy): the transform's count under
+// the call's tables or, with OPT, a walk of the block under the frame's own tables
+template <int L, bool OPT>
+__global__ __launch_bounds__(256) void jpeg_lens_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
+                                                        const uint16_t* __restrict__ acbits, u32* __restrict__ lens, JpegGeom g,
+                                                        JpegHuff hf, const JpegHuff* __restrict__ fh) {
+    constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
     __shared__ u32 sdc[2][16];
     __shared__ u32 sac[2][256];
-    __shared__ u32 lbuf[LW];
-    const int f = blockIdx.y, j0 = blockIdx.x * 256, j = j0 + threadIdx.x;
-    if (((unsigned long long)total_bits[f] + 31) / 32 > (unsigned long long)stream_fs_words) return;   // reported by jpeg_stuff_kernel
-    for (int i = threadIdx.x; i < 32; i += 256) sdc[i >> 4][i & 15] = hf.dc[i >> 4][i & 15];
-    for (int i = threadIdx.x; i < 512; i += 256) sac[i >> 8][i & 255] = hf.ac[i >> 8][i & 255];
-    // the bits of this workgroup's 256 blocks are contiguous: [offs[j0], offs[j0 + 256]).  When that span fits LW words
-    // the codes are merged in LDS (ds_or) and leave as coalesced stores, with global atomics only on the two words
-    // shared with the neighbouring workgroups; longer spans (≈ > 500 bits per block) write to the stream directly.
-    const int j1 = min(j0 + 256, g.nblk);
-    const u32 sbit = offs[(int64_t)f * g.nblk + j0];
-    const u32 ebit = j1 < g.nblk ? offs[(int64_t)f * g.nblk + j1] : total_bits[f];
+    const int j = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (OPT) {
+        load_huff<true>(sdc, sac, hf, fh, f);
+        __syncthreads();
+    }
+    if (j >= g.nblk) return;
+    const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
+    const int16_t* dd = dcs + (int64_t)f * g.nblk;
+    bool dummy;
+    const int diff = block_dc<L>(dd, g, mcu, mx, my, k, dummy) - block_pred<L>(dd, g, mcu, mx, my, k);
+    const int t = k >= NY ? 1 : 0;
+    const u32 cat = dc_category(diff);
+    u32 n = ((OPT ? sdc[t][cat] : hf.dc[t][cat]) >> 16) + cat;
+    if (dummy) {
+        n += (OPT ? sac[t][0] : hf.ac[t][0]) >> 16;
+    } else if (OPT) {
+        const u32* la = sac[t];
+        ac_symbols((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63),
+                   [&](u32 s, int, u32 size) { n += (la[s] >> 16) + size; });
+    } else {
+        n += acbits[(int64_t)f * g.nblk + j];
+    }
+    lens[(int64_t)f * g.nblk + j] = n;
+}
+
+// The span protocol of every emit kernel (sequential and progressive).  One thread per block; block j of a frame's nb
+// blocks starts at bit offs[j] of the frame's stream gs (tb bits in all), so the bits of a workgroup's 256 blocks are one
+// contiguous span [offs[j0], offs[j0 + 256]).  When the span fits the JLW words of lbuf (LDS, declared by the kernel) the
+// codes are merged there (ds_or) and leave as coalesced stores, with global atomics only on the first and last word,
+// which the neighbouring workgroups share; a longer span (≈ > 500 bits per block) goes to the stream directly: the
+// first word a block touches is shared with the block before it (atomic OR), the words after it are its own (plain
+// stores), its last partial word is shared with the next block (atomic OR).  jpeg_zero_kernel has cleared exactly the
+// words that are ORed into.  body(j, put) calls put(code, len) (len <= 32, code < 2^len) for the fields of block j in
+// stream order, MSB first.  A span can be empty (nw == 0: blocks inside a progressive scan's EOB run write no bits); then
+// nothing is stored.  A stream over its capacity is left alone (the stuffing kernel reports it).  The barrier after the
+// zeroing also covers whatever the kernel staged in LDS before the call.
+template <typename Body>
+__device__ __forceinline__ void span_write(u32* lbuf, const u32* __restrict__ offs, int nb, u32 tb, u32* __restrict__ gs, int64_t fs_words,
+                                           Body&& body) {
+    if (((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words) return;
+    const int j0 = blockIdx.x * 256, j = j0 + threadIdx.x, j1 = min(j0 + 256, nb);
+    const u32 sbit = offs[j0];
+    const u32 ebit = j1 < nb ? offs[j1] : tb;
     const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
-    const bool merged = nw <= LW;
+    const bool merged = nw <= JLW;
     if (merged)
         for (u32 i = threadIdx.x; i < nw; i += 256) lbuf[i] = 0;
     __syncthreads();
-    u32* gs = stream + (int64_t)f * stream_fs_words;
-    if (j < g.nblk) {
-    const int mcu = j / 6, k = j - mcu * 6, my = mcu / g.mw, mx = mcu - my * g.mw;
-    const int16_t* dd = dcs + (int64_t)f * g.nblk;
-    bool dummy;
-    const int diff = block_dc(dd, g, mcu, mx, my, k, dummy) - block_pred(dd, g, mcu, mx, my, k);
-    const int t = k >= 4 ? 1 : 0;
-    const u32 off = offs[(int64_t)f * g.nblk + j];
-    unsigned long long acc = 0;
-    u32 nb = off & 31;
-    u32 wi = off >> 5;
-    bool first = true;
-    auto put = [&](u32 code, u32 len) {
-        acc |= (unsigned long long)code << (64 - nb - len);
-        nb += len;
-        if (nb >= 32) {
-            if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
-            else if (first) atomicOr(gs + wi, (u32)(acc >> 32));
-            else gs[wi] = (u32)(acc >> 32);
-            first = false;
-            ++wi;
-            acc <<= 32;
-            nb -= 32;
-        }
-    };
-    {
-        const int sg = diff >> 31;
-        const u32 cat = 32 - (u32)__clz((diff ^ sg) - sg);
-        const u32 e = sdc[t][cat];
-        put(((e & 0xffff) << cat) | ((u32)(diff + sg) & ((1u << cat) - 1)), (e >> 16) + cat);
-    }
-    if (!dummy) {
-        const uint4* blk = (const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63);
-        const u32 zrl = sac[t][0xF0];
-        u32 run = 0;
-        uint4 nxt = blk[0];
-        for (int g8 = 0; g8 < 8; ++g8) {
-            const uint4 cur = nxt;
-            if (g8 < 7) nxt = blk[(g8 + 1) * 64];
-            const u32 pairs[4] = {cur.x, cur.y, cur.z, cur.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const u32 pair = pairs[u];
-                const bool dcpair = g8 == 0 && u == 0;
-                if ((dcpair ? pair >> 16 : pair) == 0) {          // most of a photograph's coefficients
-                    run += dcpair ? 1 : 2;
-                    continue;
-                }
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    if (dcpair && h == 0) continue;
-                    const int c = (int)(int16_t)(pair >> (16 * h));
-                    if (c == 0) {
-                        ++run;
-                        continue;
-                    }
-                    for (u32 z = run >> 4; z > 0; --z) put(zrl & 0xffff, zrl >> 16);
-                    const int sg = c >> 31;
-                    const u32 cat = 32 - (u32)__clz((c ^ sg) - sg);
-                    const u32 e = sac[t][((run & 15) << 4) | cat];
-                    put(((e & 0xffff) << cat) | ((u32)(c + sg) & ((1u << cat) - 1)), (e >> 16) + cat);
-                    run = 0;
-                }
+    if (j < nb) {
+        const u32 off = offs[j];
+        unsigned long long acc = 0;
+        u32 nbits = off & 31;
+        u32 wi = off >> 5;
+        bool first = true;
+        body(j, [&](u32 code, u32 len) {
+            acc |= (unsigned long long)code << (64 - nbits - len);
+            nbits += len;
+            if (nbits >= 32) {
+                if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
+                else if (first) atomicOr(gs + wi, (u32)(acc >> 32));
+                else gs[wi] = (u32)(acc >> 32);
+                first = false;
+                ++wi;
+                acc <<= 32;
+                nbits -= 32;
             }
+        });
+        if (nbits) {
+            if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
+            else atomicOr(gs + wi, (u32)(acc >> 32));
         }
-        if (run) {
-            const u32 e = sac[t][0];
-            put(e & 0xffff, e >> 16);
-        }
-    } else {
-        const u32 e = sac[t][0];
-        put(e & 0xffff, e >> 16);
-    }
-    if (nb) {
-        if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
-        else atomicOr(gs + wi, (u32)(acc >> 32));
-    }
     }
     if (merged) {
         __syncthreads();
@@ -408,6 +454,39 @@ __global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restric
             }
         }
     }
+}
+
+// The sequential scan: every block's DC difference and AC symbols at the block's bit offset, under the call's tables or,
+// with OWN, the frame's own (optimize).
+template <int L, bool OWN>
+__global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
+                                                        const u32* __restrict__ offs, u32* __restrict__ stream, int64_t stream_fs_words,
+                                                        const u32* __restrict__ total_bits, JpegGeom g, JpegHuff hf,
+                                                        const JpegHuff* __restrict__ fh) {
+    constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
+    __shared__ u32 sdc[2][16];
+    __shared__ u32 sac[2][256];
+    __shared__ u32 lbuf[JLW];
+    const int f = blockIdx.y;
+    load_huff<OWN>(sdc, sac, hf, fh, f);
+    span_write(lbuf, offs + (int64_t)f * g.nblk, g.nblk, total_bits[f], stream + (int64_t)f * stream_fs_words, stream_fs_words,
+               [&](int j, auto&& put) {
+        const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
+        const int16_t* dd = dcs + (int64_t)f * g.nblk;
+        bool dummy;
+        const int diff = block_dc<L>(dd, g, mcu, mx, my, k, dummy) - block_pred<L>(dd, g, mcu, mx, my, k);
+        const u32 cat = dc_category(diff), e = sdc[k >= NY ? 1 : 0][cat];
+        put(((e & 0xffff) << cat) | ((u32)(diff + (diff >> 31)) & ((1u << cat) - 1)), (e >> 16) + cat);
+        const u32* ta = sac[k >= NY ? 1 : 0];
+        if (!dummy) {
+            ac_symbols((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63), [&](u32 s, int c, u32 size) {
+                const u32 e = ta[s];
+                put(((e & 0xffff) << size) | ((u32)(c + (c >> 31)) & ((1u << size) - 1)), (e >> 16) + size);
+            });
+        } else {
+            put(ta[0] & 0xffff, ta[0] >> 16);
+        }
+    });
 }
 
 // ---- exclusive scan of u32 rows (in place), 1024 elements per workgroup ---------------------------------------------
@@ -493,17 +572,20 @@ static int scan_rows(u32* data, int64_t fs, int len, int n, u32* part, u32* tota
 
 // ---- byte stuffing and the file around the entropy-coded segment ----------------------------------------------------
 
-// Before the emit kernel: the words it ORs into must start at zero.  A workgroup whose span is merged in LDS touches
-// only its first and last word that way (everything between is stored whole); a span too long for LDS is cleared entirely.
+// Before an emit kernel: the words span_write ORs into must start at zero.  A workgroup whose span is merged in LDS
+// touches only its first and last word that way (everything between is stored whole); a span too long for LDS is cleared
+// entirely.  offs: nb offsets per frame.
 __global__ __launch_bounds__(256) void jpeg_zero_kernel(u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ offs,
-                                                        const u32* __restrict__ total_bits, int nblk) {
+                                                        const u32* __restrict__ total_bits, int nb) {
     const int f = blockIdx.y, j0 = blockIdx.x * 256;
     const u32 tb = total_bits[f];
     if (((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words) return;
-    const int j1 = min(j0 + 256, nblk);
-    const u32 sbit = offs[(int64_t)f * nblk + j0];
-    const u32 ebit = j1 < nblk ? offs[(int64_t)f * nblk + j1] : tb;
+    const int j1 = min(j0 + 256, nb);
+    const u32 sbit = offs[(int64_t)f * nb + j0];
+    const u32 ebit = j1 < nb ? offs[(int64_t)f * nb + j1] : tb;
     const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
+    if (nw == 0) return;      // an empty span: blocks inside a progressive scan's EOB run write no bits (in the sequential
+                              // scan every block takes at least two); gs[nw - 1] would be the word before the span
     u32* gs = stream + (int64_t)f * fs_words + wlo;
     if (nw <= JLW) {
         if (threadIdx.x == 0) gs[0] = 0;
@@ -561,41 +643,18 @@ __global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const u32* __restrict
     }
 }
 
-// 256 chunks (8 KB of stream) per workgroup pass: every thread expands its chunk into LDS at its stuffed offset (byte
-// writes), then the workgroup copies its contiguous piece of the file out — whole dwords where the piece covers them,
-// single bytes at its two ends (the neighbouring workgroups own the rest of those dwords).
-__global__ __launch_bounds__(256) void jpeg_stuff_kernel(const u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ total_bits,
-                                                         const u32* __restrict__ cnt, int64_t cnt_fs, int nchunks,
-                                                         const u32* __restrict__ ff_total, u8* __restrict__ out, int64_t out_fs,
-                                                         u32* __restrict__ sizes, JpegHeader hd) {
-    __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
-    const int f = blockIdx.y;
-    const u32 tb = total_bits[f];
-    const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
-    const int64_t nbytes = ((int64_t)tb + 7) >> 3;
-    const u32 nff = ff_total[f];
-    const int64_t fsize = (int64_t)hd.len + nbytes + nff + 2;
-    const bool fits = !over && fsize <= out_fs;
-    u8* o = out + (int64_t)f * out_fs;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) sizes[f] = fits ? (u32)fsize : 0xffffffffu;
-        if (fits) {
-            for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
-            if (threadIdx.x == 0) {
-                o[fsize - 2] = 0xff;
-                o[fsize - 1] = 0xd9;
-            }
-        }
-    }
-    if (!fits) return;
-    const u32* w = stream + (int64_t)f * fs_words;
-    const u32* cf = cnt + (int64_t)f * cnt_fs;
+// The stuffed stream of frame f, written from `data` on (the file position where the scan's bytes start).  256 chunks
+// (8 KB of stream) per workgroup pass: every thread expands its chunk into LDS at its stuffed offset (byte writes), then
+// the workgroup copies its contiguous piece of the file out — whole dwords where the piece covers them, single bytes at
+// its two ends (the neighbouring workgroups own the rest of those dwords).  lb: 256 · 2 · JCHUNK + 8 bytes of LDS.
+__device__ __forceinline__ void stuff_chunks(u8* lb, const u32* __restrict__ w, const u32* __restrict__ cf, int nchunks, int64_t nbytes,
+                                             u32 tb, u32 nff, u8* __restrict__ data) {
     const int nvc = (int)((nbytes + JCHUNK - 1) / JCHUNK);         // chunks that hold stream bytes
     for (int c0 = blockIdx.x * 256; c0 < nvc; c0 += gridDim.x * 256) {
         const int ce = min(c0 + 256, nvc);
         const u32 pre0 = cf[c0];
         const u32 pre1 = ce < nchunks ? cf[ce] : nff;
-        u8* dst = o + hd.len + (int64_t)c0 * JCHUNK + pre0;        // where this pass's piece of the file starts
+        u8* dst = data + (int64_t)c0 * JCHUNK + pre0;              // where this pass's piece of the file starts
         const u32 mis = (u32)((uintptr_t)dst & 3);
         const u32 total = (u32)(min((int64_t)ce * JCHUNK, nbytes) - (int64_t)c0 * JCHUNK) + (pre1 - pre0);
         const int ci = c0 + threadIdx.x;
@@ -628,34 +687,184 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const u32* __restrict__
     }
 }
 
+// The file with the call's tables: the host's header (SOI .. SOS), the stuffed stream, EOI; sizes[f] = 0xFFFFFFFF when
+// it does not fit.  (jpeg_stuff_scan_kernel with no tables and no SOS would write the same file; the default call keeps
+// this kernel, which reads no per-frame table state.)
+__global__ __launch_bounds__(256) void jpeg_stuff_kernel(const u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ total_bits,
+                                                         const u32* __restrict__ cnt, int64_t cnt_fs, int nchunks,
+                                                         const u32* __restrict__ ff_total, u8* __restrict__ out, int64_t out_fs,
+                                                         u32* __restrict__ sizes, JpegHeader hd) {
+    __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
+    const int f = blockIdx.y;
+    const u32 tb = total_bits[f];
+    const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
+    const int64_t nbytes = ((int64_t)tb + 7) >> 3;
+    const u32 nff = ff_total[f];
+    const int64_t fsize = (int64_t)hd.len + nbytes + nff + 2;
+    const bool fits = !over && fsize <= out_fs;
+    u8* o = out + (int64_t)f * out_fs;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) sizes[f] = fits ? (u32)fsize : 0xffffffffu;
+        if (fits) {
+            for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
+            if (threadIdx.x == 0) {
+                o[fsize - 2] = 0xff;
+                o[fsize - 1] = 0xd9;
+            }
+        }
+    }
+    if (!fits) return;
+    stuff_chunks(lb, stream + (int64_t)f * fs_words, cnt + (int64_t)f * cnt_fs, nchunks, nbytes, tb, nff, o + hd.len);
+}
+
+// ---- per-frame tables and the scan header (optimize, progressive) ---------------------------------------------------
+
+constexpr int JSLOTS = 4;                    // tables per frame: DC0, AC0, DC1, AC1 (slot = 2·table + is_ac)
+struct JpegDht {                             // one optimal table as its DHT segment carries it
+    u32 nvals;                               // JDHT_OVERFLOW: a code would be longer than 32 bits (the frame fails)
+    u8 bits[16];
+    u8 vals[256];
+};
+static_assert(sizeof(JpegDht) == 276, "imgxf_jpeg_optimal_tables documents this layout");
+constexpr u32 JDHT_OVERFLOW = 0xffffffffu;
+constexpr u32 JSIZE_HUFF_OVERFLOW = 0xfffffffeu;   // sizes[f] of a frame whose optimal table overflows
+
+struct JpScanHdr {                           // what the device writes in front of a scan's data
+    u32 slots;                               // DHT segments: bit s = slot s, written in ascending slot order (jcmarker.c
+                                             // write_scan_header: DC0, AC0, DC1, AC1)
+    int soslen;
+    u8 sos[14];
+};
+
+// jcmarker.c emit_dht: table t of slot s as one DHT segment at o; returns its length
+__device__ __forceinline__ int write_dht_segment(u8* __restrict__ o, const JpegDht& t, int s) {
+    const int seg = 21 + (int)t.nvals;
+    for (int i = threadIdx.x; i < seg; i += 256) {
+        u8 v;
+        if (i == 0) v = 0xff;
+        else if (i == 1) v = 0xc4;
+        else if (i == 2) v = (u8)((seg - 2) >> 8);
+        else if (i == 3) v = (u8)(seg - 2);
+        else if (i == 4) v = (u8)(((s & 1) << 4) | (s >> 1));
+        else if (i < 21) v = t.bits[i - 5];
+        else v = t.vals[i - 21];
+        o[i] = v;
+    }
+    return seg;
+}
+
+// One scan with the frame's own tables, at the frame's running file position: the host's SOI .. SOF before the first
+// scan, the scan's DHT segments and SOS, its stuffed stream, EOI after the last.  pos[si][f] is where scan si of frame f
+// starts (kept on the device: no host round trip; the first scan starts at hd.len); the sequential optimize file is the
+// one-scan case (si = 0, last, pos unused).  Sentinels of pos[] / sizes[]: JSIZE_HUFF_OVERFLOW (an optimal code over 32
+// bits) and 0xFFFFFFFF (capacity); once a scan of frame f fails, the later scans carry the sentinel forward and write nothing.
+__global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restrict__ stream, int64_t fs_words,
+                                                              const u32* __restrict__ total_bits, const u32* __restrict__ cnt,
+                                                              int64_t cnt_fs, int nchunks, const u32* __restrict__ ff_total,
+                                                              u8* __restrict__ out, int64_t out_fs, u32* __restrict__ pos, int si, bool last,
+                                                              u32* __restrict__ sizes, JpegHeader hd, const JpegDht* __restrict__ dht,
+                                                              JpScanHdr sh) {
+    __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
+    const int f = blockIdx.y, n = gridDim.y;
+    const u32 base = si == 0 ? (u32)hd.len : pos[(int64_t)si * n + f];
+    const u32 tb = total_bits[f];
+    const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
+    const int64_t nbytes = ((int64_t)tb + 7) >> 3;
+    const u32 nff = ff_total[f];
+    u32 status = base >= JSIZE_HUFF_OVERFLOW ? base : 0u;
+    int hlen = sh.soslen;
+    for (int s = 0; s < JSLOTS; ++s)
+        if ((sh.slots >> s) & 1) {
+            const u32 nv = dht[(int64_t)f * JSLOTS + s].nvals;
+            if (nv == JDHT_OVERFLOW && !status) status = JSIZE_HUFF_OVERFLOW;
+            hlen += 21 + (int)nv;
+        }
+    const int64_t end = (int64_t)base + hlen + nbytes + nff;    // the scan's end; EOI (2 bytes) must still fit
+    if (!status && (over || end + 2 > out_fs)) status = 0xffffffffu;
+    u8* o = out + (int64_t)f * out_fs;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) {
+            if (!last) pos[(int64_t)(si + 1) * n + f] = status ? status : (u32)end;
+            else sizes[f] = status ? status : (u32)(end + 2);
+        }
+        if (!status) {
+            if (si == 0)
+                for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
+            int p = (int)base;
+            for (int s = 0; s < JSLOTS; ++s)
+                if ((sh.slots >> s) & 1) p += write_dht_segment(o + p, dht[(int64_t)f * JSLOTS + s], s);
+            if (threadIdx.x < sh.soslen) o[p + threadIdx.x] = sh.sos[threadIdx.x];
+            if (last && threadIdx.x == 0) {
+                o[end] = 0xff;
+                o[end + 1] = 0xd9;
+            }
+        }
+    }
+    if (status) return;
+    stuff_chunks(lb, stream + (int64_t)f * fs_words, cnt + (int64_t)f * cnt_fs, nchunks, nbytes, tb, nff, o + base + hlen);
+}
+
+// ---- host side: workspace, preparation, dispatch ---------------------------------------------------------------------
+
+constexpr int JP_MAXSCANS = 10;              // scans of a progressive file (jpeg_encode_prog.inc)
+
+template <typename F>
+static auto with_layout(int lay, F&& f) {    // f(std::integral_constant<int, L>{}) for the layout `lay`
+    switch (lay) {
+    case JL420: return f(std::integral_constant<int, JL420>{});
+    case JL422: return f(std::integral_constant<int, JL422>{});
+    case JL444: return f(std::integral_constant<int, JL444>{});
+    default: return f(std::integral_constant<int, JLGRAY>{});
+    }
+}
+
 struct JpegLayout {
     int mw, mh, bw, bh, nblk, nparts_blk, nchunks, nparts_chunk;
     int64_t stream_words;                                  // per frame
-    size_t off_coef, off_dcs, off_acb, off_lens, off_part, off_tot, off_stream, off_cnt, total;
+    size_t off_coef, off_dcs, off_acb, off_lens, off_part, off_tot, off_stream, off_cnt;
+    size_t off_sym, off_fh, off_dht;                       // own tables: symbol counts [n][4][256], tables [n], DHT [n][4]
+    size_t off_flags, off_nbe, off_runlen, off_pos;        // progressive: per block; pos[scan][n], then BE totals [n]
+    size_t total;
 };
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static JpegLayout jpeg_layout(int n, int h, int w, size_t out_frame_stride) {
+// The workspace of one call: the areas every writer uses, then those of the frame's own tables (optimize, progressive),
+// then the progressive scans'.
+static JpegLayout jpeg_layout(int lay, bool opt, bool prog, int n, int h, int w, size_t out_frame_stride) {
     JpegLayout L;
-    L.mw = (w + 15) / 16;
-    L.mh = (h + 15) / 16;
+    with_layout(lay, [&](auto l) {
+        using Y = JLay<decltype(l)::value>;
+        L.mw = (w + Y::MW - 1) / Y::MW;
+        L.mh = (h + Y::MH - 1) / Y::MH;
+        L.nblk = L.mw * L.mh * Y::B;
+    });
     L.bw = (w + 7) / 8;
     L.bh = (h + 7) / 8;
-    L.nblk = L.mw * L.mh * 6;
     L.nparts_blk = (L.nblk + 1023) / 1024;
     L.stream_words = (int64_t)((out_frame_stride + 3) / 4 + 4) & ~(int64_t)3;
     L.nchunks = (int)((L.stream_words * 4 + JCHUNK - 1) / JCHUNK);
     L.nparts_chunk = (L.nchunks + 1023) / 1024;
     size_t o = 0;
-    L.off_coef = o;   o += al256((size_t)n * (size_t)((L.nblk + 63) / 64) * 64 * 128);
-    L.off_dcs = o;    o += al256((size_t)n * L.nblk * 2);
-    L.off_acb = o;    o += al256((size_t)n * L.nblk * 2);
-    L.off_lens = o;   o += al256((size_t)n * L.nblk * 4);
-    L.off_part = o;   o += al256((size_t)n * (size_t)(L.nparts_blk > L.nparts_chunk ? L.nparts_blk : L.nparts_chunk) * 4);
-    L.off_tot = o;    o += al256((size_t)n * 8);
-    L.off_stream = o; o += al256((size_t)n * L.stream_words * 4);
-    L.off_cnt = o;    o += al256((size_t)n * L.nchunks * 4);
+    auto area = [&](size_t& off, bool used, size_t bytes) {
+        off = o;
+        if (used) o += al256(bytes);
+    };
+    area(L.off_coef, true, (size_t)n * (size_t)((L.nblk + 63) / 64) * 64 * 128);
+    area(L.off_dcs, true, (size_t)n * L.nblk * 2);
+    area(L.off_acb, true, (size_t)n * L.nblk * 2);
+    area(L.off_lens, true, (size_t)n * L.nblk * 4);
+    area(L.off_part, true, (size_t)n * (size_t)(L.nparts_blk > L.nparts_chunk ? L.nparts_blk : L.nparts_chunk) * 4);
+    area(L.off_tot, true, (size_t)n * 8);
+    area(L.off_stream, true, (size_t)n * L.stream_words * 4);
+    area(L.off_cnt, true, (size_t)n * L.nchunks * 4);
+    area(L.off_sym, opt || prog, (size_t)n * JSLOTS * 256 * 4);
+    area(L.off_fh, opt || prog, (size_t)n * sizeof(JpegHuff));
+    area(L.off_dht, opt || prog, (size_t)n * JSLOTS * sizeof(JpegDht));
+    area(L.off_flags, prog, (size_t)n * L.nblk * 4);
+    area(L.off_nbe, prog, (size_t)n * L.nblk * 4);
+    area(L.off_runlen, prog, (size_t)n * L.nblk * 4);
+    area(L.off_pos, prog, (size_t)(JP_MAXSCANS + 1) * n * 4 + (size_t)n * 4);
     L.total = o;
     return L;
 }
@@ -690,8 +899,183 @@ static bool quant_entry(u32 qv, u32* m, u32* halfp) {
     return true;
 }
 
+static int enc_layout(const imgxf_jpeg_enc_params* p) {
+    if (p->optimize != 0 && p->optimize != 1) return -1;
+    const bool s11 = p->h_samp == 1 && p->v_samp == 1, s21 = p->h_samp == 2 && p->v_samp == 1, s22 = p->h_samp == 2 && p->v_samp == 2;
+    if (!(s11 || s21 || s22)) return -1;
+    if (p->ncomp == 1) return JLGRAY;                          // one block per MCU whatever the sampling (the SOF byte only)
+    if (p->ncomp != 3) return -1;
+    return s11 ? JL444 : s21 ? JL422 : JL420;
+}
+
+// the three imgxf_jpeg_workspace_bytes* (progressive files always carry optimal tables: `optimize` is ignored there)
+static int jpeg_workspace_bytes(imgxf_jpeg_enc_params p, bool prog, int n, int h, int w, size_t out_frame_stride, size_t* bytes) {
+    if (prog) p.optimize = 0;
+    const int lay = enc_layout(&p);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
+    *bytes = jpeg_layout(lay, p.optimize != 0, prog, n, h, w, out_frame_stride).total;
+    return IMGXF_OK;
+}
+
+// One encode call, checked and laid out: what the sequential and the progressive encoder launch their kernels from.
+struct JpegJob {
+    int lay, ncomp, n;                         // n == 0: nothing to encode
+    bool opt;
+    View s;
+    hipStream_t st;
+    JpegLayout L;
+    JpegGeom g;
+    int64_t coef_fs;                           // int16 elements per frame, whole groups of 64 blocks
+    JpegQuant q;
+    JpegHuff hf;
+    JpegHeader hd;
+    int16_t *coef, *dcs;
+    uint16_t* acb;
+    u32 *lens, *part, *tot_bits, *tot_ff, *ustream, *cnt, *sym, *flags, *nbe, *runlen, *pos, *tot_be, *sizes;
+    JpegHuff* fh;
+    JpegDht* dht;
+    u8* out;
+    int64_t out_fs;
+};
+
+static int jpeg_prepare(JpegJob& J, const imgxf_view* src, const imgxf_jpeg_enc_params* params, bool prog, const imgxf_jpeg_tables* tables,
+                        const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride, uint32_t* sizes, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    J.n = 0;
+    IMGXF_CHECK(check_view(src));
+    if (!params || !tables || !header || !out || !sizes) return IMGXF_ERR_NULL;
+    imgxf_jpeg_enc_params p = *params;
+    if (prog) p.optimize = 0;                                  // ignored: progressive files always carry optimal tables
+    J.lay = enc_layout(&p);
+    if (J.lay < 0) return IMGXF_ERR_ARG;
+    if (src->c != p.ncomp) return IMGXF_ERR_UNSUPPORTED;
+    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
+    if (src->n == 0) return IMGXF_OK;
+    if (empty_view(src)) return IMGXF_ERR_SHAPE;
+    if (src->n > 65535) return IMGXF_ERR_SHAPE;
+    if (out_frame_stride < (size_t)header_bytes + 2 || out_frame_stride > ((size_t)1 << 31)) return IMGXF_ERR_ARG;
+    J.opt = p.optimize != 0;
+    J.ncomp = p.ncomp;
+    J.L = jpeg_layout(J.lay, J.opt, prog, src->n, src->h, src->w, out_frame_stride);
+    const JpegLayout& L = J.L;
+    if (!workspace || workspace_bytes < L.total || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
+    // bit offsets are 32-bit: no block takes more than 2048 bits in one scan (the widest, a progressive first scan over
+    // 1..63 at Al = 1: 63 symbols of <= 16 + 10 bits, 3 ZRLs, one EOBRUN of 16 + 14 bits)
+    if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;
+    memset(&J.q, 0, sizeof(J.q));
+    for (int t = 0; t < (p.ncomp == 1 ? 1 : 2); ++t)           // grayscale: table 0 only
+        for (int i = 0; i < 64; ++i) {
+            const u32 qv = tables->quant[t][i];
+            if (qv < 1 || qv > 255 || !quant_entry(qv, &J.q.m[t][i], &J.q.half[t][i])) return IMGXF_ERR_ARG;
+        }
+    for (int t = 0; t < 2; ++t) {
+        for (int i = 0; i < 16; ++i) J.hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
+        for (int i = 0; i < 256; ++i) {
+            J.hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
+            J.q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));    // code + magnitude bits of the symbol
+        }
+    }
+    memset(&J.hd, 0, sizeof(J.hd));
+    memcpy(J.hd.b, header, (size_t)header_bytes);
+    J.hd.len = header_bytes;
+    J.s = make_view(src);
+    J.n = J.s.n;
+    J.st = (hipStream_t)stream;
+    J.g = {L.mw, L.mh, L.bw, L.bh, L.nblk};
+    J.coef_fs = (int64_t)((L.nblk + 63) / 64) * 64 * 64;
+    u8* ws = (u8*)workspace;
+    J.coef = (int16_t*)(ws + L.off_coef);
+    J.dcs = (int16_t*)(ws + L.off_dcs);
+    J.acb = (uint16_t*)(ws + L.off_acb);
+    J.lens = (u32*)(ws + L.off_lens);
+    J.part = (u32*)(ws + L.off_part);
+    J.tot_bits = (u32*)(ws + L.off_tot);
+    J.tot_ff = J.tot_bits + J.n;
+    J.ustream = (u32*)(ws + L.off_stream);
+    J.cnt = (u32*)(ws + L.off_cnt);
+    J.sym = (u32*)(ws + L.off_sym);                            // (the areas a mode does not have are empty: never touched)
+    J.fh = (JpegHuff*)(ws + L.off_fh);
+    J.dht = (JpegDht*)(ws + L.off_dht);
+    J.flags = (u32*)(ws + L.off_flags);
+    J.nbe = (u32*)(ws + L.off_nbe);
+    J.runlen = (u32*)(ws + L.off_runlen);
+    J.pos = (u32*)(ws + L.off_pos);
+    J.tot_be = J.pos + (size_t)(JP_MAXSCANS + 1) * J.n;
+    J.sizes = sizes;
+    J.out = out;
+    J.out_fs = (int64_t)out_frame_stride;
+    return IMGXF_OK;
+}
+
+// The tail of every scan: the stream's 0xFF bytes counted per chunk, their prefix sums, the stuffed bytes into the file —
+// behind the host's whole header (sh == nullptr: the call's tables) or behind the scan's own DHT segments and SOS.
+static int launch_stuff(const JpegJob& J, const JpScanHdr* sh, int si, bool last) {
+    const JpegLayout& L = J.L;
+    const unsigned cwg = (unsigned)((L.nchunks + 255) / 256);
+    const dim3 cgrid(cwg < 256u ? cwg : 256u, (unsigned)J.n);         // grid-stride over the capacity
+    hipLaunchKernelGGL(jpeg_ffcount_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits, J.cnt,
+                       (int64_t)L.nchunks, L.nchunks);
+    IMGXF_CHECK(scan_rows(J.cnt, L.nchunks, L.nchunks, J.n, J.part, J.tot_ff, J.st));
+    if (sh)
+        hipLaunchKernelGGL(jpeg_stuff_scan_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits,
+                           (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs, J.pos, si, last, J.sizes,
+                           J.hd, (const JpegDht*)J.dht, *sh);
+    else
+        hipLaunchKernelGGL(jpeg_stuff_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits,
+                           (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs, J.sizes, J.hd);
+    return launch_status();
+}
+
 #include "jpeg_encode_ext.inc"
 #include "jpeg_encode_prog.inc"
+
+// The sequential file: transform → (optimize: symbol counts → the frame's own tables) → bits per block → bit offsets →
+// emit → stuffing.
+static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
+                           const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride, uint32_t* sizes,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    JpegJob J;
+    IMGXF_CHECK(jpeg_prepare(J, src, params, false, tables, header, header_bytes, out, out_frame_stride, sizes, workspace, workspace_bytes,
+                             stream));
+    if (J.n == 0) return IMGXF_OK;
+    return with_layout(J.lay, [&](auto l) -> int {
+        constexpr int L = decltype(l)::value;
+        const dim3 bgrid((unsigned)((J.g.nblk + 255) / 256), (unsigned)J.n);
+        const int16_t *coef = J.coef, *dcs = J.dcs;
+        const JpegHuff* fh = J.fh;
+        launch_transform<L>(J);
+        if (J.opt) {
+            if (hipMemsetAsync(J.sym, 0, (size_t)J.n * JSLOTS * 256 * 4, J.st) != hipSuccess) return launch_status();
+            hipLaunchKernelGGL(jpeg_gather_kernel<L>, bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, J.g, J.sym);
+            hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(L == JLGRAY ? 2u : 4u, (unsigned)J.n), dim3(256), 0, J.st, (const u32*)J.sym, J.fh,
+                               J.dht);
+            hipLaunchKernelGGL((jpeg_lens_kernel<L, true>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const uint16_t*)J.acb, J.lens,
+                               J.g, J.hf, fh);
+        } else {
+            hipLaunchKernelGGL((jpeg_lens_kernel<L, false>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const uint16_t*)J.acb, J.lens,
+                               J.g, J.hf, fh);
+        }
+        IMGXF_CHECK(scan_rows(J.lens, J.g.nblk, J.g.nblk, J.n, J.part, J.tot_bits, J.st));
+        hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, J.st, J.ustream, J.L.stream_words, (const u32*)J.lens,
+                           (const u32*)J.tot_bits, J.g.nblk);
+        if (J.opt)
+            hipLaunchKernelGGL((jpeg_emit_kernel<L, true>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens, J.ustream,
+                               J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh);
+        else
+            hipLaunchKernelGGL((jpeg_emit_kernel<L, false>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens, J.ustream,
+                               J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh);
+        if (!J.opt) return launch_stuff(J, nullptr, 0, true);
+        JpScanHdr sh;                                          // one scan over all components (jcmarker.c emit_sos)
+        memset(&sh, 0, sizeof(sh));
+        const u8 sos3[14] = {0xff, 0xda, 0x00, 0x0c, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3f, 0x00};
+        const u8 sos1[10] = {0xff, 0xda, 0x00, 0x08, 0x01, 0x01, 0x00, 0x00, 0x3f, 0x00};
+        sh.slots = J.ncomp == 3 ? 0xfu : 0x3u;
+        sh.soslen = J.ncomp == 3 ? 14 : 10;
+        memcpy(sh.sos, J.ncomp == 3 ? sos3 : sos1, (size_t)sh.soslen);
+        return launch_stuff(J, &sh, 0, true);
+    });
+}
 
 } // namespace imgxf
 
@@ -699,180 +1083,26 @@ using namespace imgxf;
 
 IMGXF_API int imgxf_jpeg_workspace_bytes(int n, int h, int w, size_t out_frame_stride, size_t* bytes) {
     if (!bytes) return IMGXF_ERR_NULL;
-    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
-    *bytes = jpeg_layout(n, h, w, out_frame_stride).total;
-    return IMGXF_OK;
+    return jpeg_workspace_bytes({3, 2, 2, 0}, false, n, h, w, out_frame_stride, bytes);
 }
 
 IMGXF_API int imgxf_jpeg_encode_u8(const imgxf_view* src, const imgxf_jpeg_tables* tables, const uint8_t* header,
                                    int header_bytes, uint8_t* out, size_t out_frame_stride, uint32_t* sizes,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    IMGXF_CHECK(check_view(src));
-    if (!tables || !header || !out || !sizes) return IMGXF_ERR_NULL;
-    if (src->c != 3) return IMGXF_ERR_UNSUPPORTED;
-    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
-    if (src->n == 0) return IMGXF_OK;
-    if (empty_view(src)) return IMGXF_ERR_SHAPE;
-    if (src->n > 65535) return IMGXF_ERR_SHAPE;
-    if (out_frame_stride < (size_t)header_bytes + 2 || out_frame_stride > ((size_t)1 << 31)) return IMGXF_ERR_ARG;
-    const JpegLayout L = jpeg_layout(src->n, src->h, src->w, out_frame_stride);
-    if (!workspace || workspace_bytes < L.total || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
-    if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;        // bit offsets are 32-bit
-    JpegQuant q;
-    for (int t = 0; t < 2; ++t)
-        for (int i = 0; i < 64; ++i) {
-            const u32 qv = tables->quant[t][i];
-            if (qv < 1 || qv > 255 || !quant_entry(qv, &q.m[t][i], &q.half[t][i])) return IMGXF_ERR_ARG;
-        }
-    JpegHuff hf;
-    for (int t = 0; t < 2; ++t) {
-        for (int i = 0; i < 16; ++i) hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
-        for (int i = 0; i < 256; ++i) {
-            hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
-            q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));      // code + magnitude bits of the symbol
-        }
-    }
-    JpegHeader hd;
-    memset(&hd, 0, sizeof(hd));
-    memcpy(hd.b, header, (size_t)header_bytes);
-    hd.len = header_bytes;
-    const View s = make_view(src);
-    hipStream_t st = (hipStream_t)stream;
-    u8* ws = (u8*)workspace;
-    int16_t* coef = (int16_t*)(ws + L.off_coef);
-    int16_t* dcs = (int16_t*)(ws + L.off_dcs);
-    uint16_t* acb = (uint16_t*)(ws + L.off_acb);
-    u32* lens = (u32*)(ws + L.off_lens);
-    u32* part = (u32*)(ws + L.off_part);
-    u32* tot_bits = (u32*)(ws + L.off_tot);
-    u32* tot_ff = tot_bits + s.n;
-    u32* ustream = (u32*)(ws + L.off_stream);
-    u32* cnt = (u32*)(ws + L.off_cnt);
-    const JpegGeom g = {L.mw, L.mh, L.bw, L.bh, L.nblk};
-    const int64_t coef_fs = (int64_t)((L.nblk + 63) / 64) * 64 * 64;          // int16 elements per frame, whole groups of 64 blocks
-    hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((L.mw + JM - 1) / JM), (unsigned)L.mh, (unsigned)s.n), dim3(JT), 0, st,
-                       s, coef, coef_fs, dcs, acb, L.nblk, L.mw, L.bw, L.bh, q);
-    const dim3 bgrid((unsigned)((L.nblk + 255) / 256), (unsigned)s.n);
-    hipLaunchKernelGGL(jpeg_lens_kernel, bgrid, dim3(256), 0, st, (const int16_t*)dcs, (const uint16_t*)acb, lens, g, hf);
-    IMGXF_CHECK(scan_rows(lens, L.nblk, L.nblk, s.n, part, tot_bits, st));
-    hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, st, ustream, L.stream_words, (const u32*)lens, (const u32*)tot_bits, L.nblk);
-    hipLaunchKernelGGL(jpeg_emit_kernel, bgrid, dim3(256), 0, st, (const int16_t*)coef, coef_fs, (const int16_t*)dcs, (const u32*)lens,
-                       ustream, L.stream_words, (const u32*)tot_bits, g, hf);
-    const unsigned cwg = (unsigned)((L.nchunks + 255) / 256);
-    const dim3 cgrid(cwg < 256u ? cwg : 256u, (unsigned)s.n);          // grid-stride over the capacity
-    hipLaunchKernelGGL(jpeg_ffcount_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits, cnt,
-                       (int64_t)L.nchunks, L.nchunks);
-    IMGXF_CHECK(scan_rows(cnt, L.nchunks, L.nchunks, s.n, part, tot_ff, st));
-    hipLaunchKernelGGL(jpeg_stuff_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits,
-                       (const u32*)cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)tot_ff, out, (int64_t)out_frame_stride, sizes, hd);
-    return launch_status();
+    const imgxf_jpeg_enc_params p = {3, 2, 2, 0};              // the default file: 4:2:0, the call's tables
+    return jpeg_encode_seq(src, &p, tables, header, header_bytes, out, out_frame_stride, sizes, workspace, workspace_bytes, stream);
 }
 
 IMGXF_API int imgxf_jpeg_workspace_bytes_ex(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t out_frame_stride,
                                             size_t* bytes) {
     if (!bytes || !params) return IMGXF_ERR_NULL;
-    const int lay = enc_layout(params);
-    if (lay < 0) return IMGXF_ERR_ARG;
-    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
-    *bytes = jpeg_layout_ex(lay, params->optimize != 0, n, h, w, out_frame_stride).total;
-    return IMGXF_OK;
+    return jpeg_workspace_bytes(*params, false, n, h, w, out_frame_stride, bytes);
 }
 
 IMGXF_API int imgxf_jpeg_encode_ex_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
                                       const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
                                       uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
-    IMGXF_CHECK(check_view(src));
-    if (!params || !tables || !header || !out || !sizes) return IMGXF_ERR_NULL;
-    const int lay = enc_layout(params);
-    if (lay < 0) return IMGXF_ERR_ARG;
-    if (src->c != params->ncomp) return IMGXF_ERR_UNSUPPORTED;
-    const bool opt = params->optimize != 0;
-    if (lay == JL420 && !opt)                                  // the default file: the 4:2:0 writer as it is
-        return imgxf_jpeg_encode_u8(src, tables, header, header_bytes, out, out_frame_stride, sizes, workspace, workspace_bytes, stream);
-    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
-    if (src->n == 0) return IMGXF_OK;
-    if (empty_view(src)) return IMGXF_ERR_SHAPE;
-    if (src->n > 65535) return IMGXF_ERR_SHAPE;
-    if (out_frame_stride < (size_t)header_bytes + 2 || out_frame_stride > ((size_t)1 << 31)) return IMGXF_ERR_ARG;
-    const JpegLayoutEx X = jpeg_layout_ex(lay, opt, src->n, src->h, src->w, out_frame_stride);
-    const JpegLayout& L = X.L;
-    if (!workspace || workspace_bytes < X.total || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
-    if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;        // bit offsets are 32-bit
-    const int ntab = params->ncomp == 1 ? 1 : 2;
-    JpegQuant q;
-    memset(&q, 0, sizeof(q));
-    for (int t = 0; t < ntab; ++t)
-        for (int i = 0; i < 64; ++i) {
-            const u32 qv = tables->quant[t][i];
-            if (qv < 1 || qv > 255 || !quant_entry(qv, &q.m[t][i], &q.half[t][i])) return IMGXF_ERR_ARG;
-        }
-    JpegHuff hf;
-    for (int t = 0; t < 2; ++t) {
-        for (int i = 0; i < 16; ++i) hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
-        for (int i = 0; i < 256; ++i) {
-            hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
-            q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));
-        }
-    }
-    JpegHeader hd;
-    memset(&hd, 0, sizeof(hd));
-    memcpy(hd.b, header, (size_t)header_bytes);
-    hd.len = header_bytes;
-    const View s = make_view(src);
-    hipStream_t st = (hipStream_t)stream;
-    u8* ws = (u8*)workspace;
-    int16_t* coef = (int16_t*)(ws + L.off_coef);
-    int16_t* dcs = (int16_t*)(ws + L.off_dcs);
-    uint16_t* acb = (uint16_t*)(ws + L.off_acb);
-    u32* lens = (u32*)(ws + L.off_lens);
-    u32* part = (u32*)(ws + L.off_part);
-    u32* tot_bits = (u32*)(ws + L.off_tot);
-    u32* tot_ff = tot_bits + s.n;
-    u32* ustream = (u32*)(ws + L.off_stream);
-    u32* cnt = (u32*)(ws + L.off_cnt);
-    u32* sym = opt ? (u32*)(ws + X.off_sym) : nullptr;
-    JpegHuff* fh = opt ? (JpegHuff*)(ws + X.off_fh) : nullptr;
-    JpegDht* dht = opt ? (JpegDht*)(ws + X.off_dht) : nullptr;
-    const JpegGeom g = {L.mw, L.mh, L.bw, L.bh, L.nblk};
-    const int64_t coef_fs = (int64_t)((L.nblk + 63) / 64) * 64 * 64;
-    switch (lay) {
-    case JL420:
-        hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((L.mw + JM - 1) / JM), (unsigned)L.mh, (unsigned)s.n), dim3(JT), 0, st,
-                           s, coef, coef_fs, dcs, acb, L.nblk, L.mw, L.bw, L.bh, q);
-        break;
-    case JL422: launch_transform_ex<JL422>(s, coef, coef_fs, dcs, acb, L, q, st); break;
-    case JL444: launch_transform_ex<JL444>(s, coef, coef_fs, dcs, acb, L, q, st); break;
-    default: launch_transform_ex<JLGRAY>(s, coef, coef_fs, dcs, acb, L, q, st); break;
-    }
-    if (opt && hipMemsetAsync(sym, 0, (size_t)s.n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
-    switch (lay) {
-    case JL420: launch_entropy_ex<JL420>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
-    case JL422: launch_entropy_ex<JL422>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
-    case JL444: launch_entropy_ex<JL444>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
-    default: launch_entropy_ex<JLGRAY>(opt, coef, coef_fs, dcs, acb, lens, sym, fh, dht, g, hf, s.n, st); break;
-    }
-    IMGXF_CHECK(scan_rows(lens, L.nblk, L.nblk, s.n, part, tot_bits, st));
-    const dim3 bgrid((unsigned)((L.nblk + 255) / 256), (unsigned)s.n);
-    hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, st, ustream, L.stream_words, (const u32*)lens, (const u32*)tot_bits, L.nblk);
-    switch (lay) {
-    case JL420: launch_emit_ex<JL420>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
-    case JL422: launch_emit_ex<JL422>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
-    case JL444: launch_emit_ex<JL444>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
-    default: launch_emit_ex<JLGRAY>(coef, coef_fs, dcs, lens, ustream, L.stream_words, tot_bits, g, hf, fh, s.n, st); break;
-    }
-    const unsigned cwg = (unsigned)((L.nchunks + 255) / 256);
-    const dim3 cgrid(cwg < 256u ? cwg : 256u, (unsigned)s.n);
-    hipLaunchKernelGGL(jpeg_ffcount_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits, cnt,
-                       (int64_t)L.nchunks, L.nchunks);
-    IMGXF_CHECK(scan_rows(cnt, L.nchunks, L.nchunks, s.n, part, tot_ff, st));
-    if (opt)
-        hipLaunchKernelGGL(jpeg_stuff_ex_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits,
-                           (const u32*)cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)tot_ff, out, (int64_t)out_frame_stride, sizes, hd,
-                           (const JpegDht*)dht, ntab * 2);
-    else
-        hipLaunchKernelGGL(jpeg_stuff_kernel, cgrid, dim3(256), 0, st, (const u32*)ustream, L.stream_words, (const u32*)tot_bits,
-                           (const u32*)cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)tot_ff, out, (int64_t)out_frame_stride, sizes, hd);
-    return launch_status();
+    return jpeg_encode_seq(src, params, tables, header, header_bytes, out, out_frame_stride, sizes, workspace, workspace_bytes, stream);
 }
 
 IMGXF_API int imgxf_jpeg_optimal_tables(const uint32_t* counts, int n, uint8_t* dht, uint32_t* codes, void* stream) {
@@ -887,100 +1117,19 @@ IMGXF_API int imgxf_jpeg_optimal_tables(const uint32_t* counts, int n, uint8_t* 
 IMGXF_API int imgxf_jpeg_workspace_bytes_prog(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t out_frame_stride,
                                               size_t* bytes) {
     if (!bytes || !params) return IMGXF_ERR_NULL;
-    imgxf_jpeg_enc_params p = *params;
-    p.optimize = 0;                                            // ignored: progressive files always carry optimal tables
-    const int lay = enc_layout(&p);
-    if (lay < 0) return IMGXF_ERR_ARG;
-    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
-    *bytes = jpeg_layout_prog(lay, n, h, w, out_frame_stride).total;
-    return IMGXF_OK;
+    return jpeg_workspace_bytes(*params, true, n, h, w, out_frame_stride, bytes);
 }
 
 IMGXF_API int imgxf_jpeg_encode_prog_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* params, const imgxf_jpeg_tables* tables,
                                         const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
                                         uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
-    IMGXF_CHECK(check_view(src));
-    if (!params || !tables || !header || !out || !sizes) return IMGXF_ERR_NULL;
-    imgxf_jpeg_enc_params p = *params;
-    p.optimize = 0;
-    const int lay = enc_layout(&p);
-    if (lay < 0) return IMGXF_ERR_ARG;
-    if (src->c != p.ncomp) return IMGXF_ERR_UNSUPPORTED;
-    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
-    if (src->n == 0) return IMGXF_OK;
-    if (empty_view(src)) return IMGXF_ERR_SHAPE;
-    if (src->n > 65535) return IMGXF_ERR_SHAPE;
-    if (out_frame_stride < (size_t)header_bytes + 2 || out_frame_stride > ((size_t)1 << 31)) return IMGXF_ERR_ARG;
-    const JpegLayoutProg P = jpeg_layout_prog(lay, src->n, src->h, src->w, out_frame_stride);
-    const JpegLayoutEx& X = P.X;
-    const JpegLayout& L = X.L;
-    if (!workspace || workspace_bytes < P.total || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
-    // bit offsets are 32-bit: no block takes more than 2048 bits in one scan (the widest, a first scan over 1..63 at
-    // Al = 1: 63 symbols of <= 16 + 10 bits, 3 ZRLs, one EOBRUN of 16 + 14 bits)
-    if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;
-    const int ntab = p.ncomp == 1 ? 1 : 2;
-    JpegQuant q;
-    memset(&q, 0, sizeof(q));
-    for (int t = 0; t < ntab; ++t)
-        for (int i = 0; i < 64; ++i) {
-            const u32 qv = tables->quant[t][i];
-            if (qv < 1 || qv > 255 || !quant_entry(qv, &q.m[t][i], &q.half[t][i])) return IMGXF_ERR_ARG;
-        }
-    for (int t = 0; t < 2; ++t)                                // (the transform's AC bit counts are not used here)
-        for (int i = 0; i < 256; ++i) q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));
-    JpegHeader hd;
-    memset(&hd, 0, sizeof(hd));
-    memcpy(hd.b, header, (size_t)header_bytes);
-    hd.len = header_bytes;
-    const View s = make_view(src);
-    hipStream_t st = (hipStream_t)stream;
-    u8* ws = (u8*)workspace;
-    int16_t* coef = (int16_t*)(ws + L.off_coef);
-    int16_t* dcs = (int16_t*)(ws + L.off_dcs);
-    uint16_t* acb = (uint16_t*)(ws + L.off_acb);
-    const int64_t coef_fs = (int64_t)((L.nblk + 63) / 64) * 64 * 64;
-    switch (lay) {
-    case JL420:
-        hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((L.mw + JM - 1) / JM), (unsigned)L.mh, (unsigned)s.n), dim3(JT), 0, st,
-                           s, coef, coef_fs, dcs, acb, L.nblk, L.mw, L.bw, L.bh, q);
-        break;
-    case JL422: launch_transform_ex<JL422>(s, coef, coef_fs, dcs, acb, L, q, st); break;
-    case JL444: launch_transform_ex<JL444>(s, coef, coef_fs, dcs, acb, L, q, st); break;
-    default: launch_transform_ex<JLGRAY>(s, coef, coef_fs, dcs, acb, L, q, st); break;
-    }
-    JpProgArgs a;
-    a.coef = coef;
-    a.coef_fs = coef_fs;
-    a.dcs = dcs;
-    a.g = {L.mw, L.mh, L.bw, L.bh, L.nblk};
-    a.sym = (u32*)(ws + X.off_sym);
-    a.flags = (u32*)(ws + P.off_flags);
-    a.nbe = (u32*)(ws + P.off_nbe);
-    a.runlen = (u32*)(ws + P.off_runlen);
-    a.lens = (u32*)(ws + L.off_lens);
-    a.part = (u32*)(ws + L.off_part);
-    a.tot_bits = (u32*)(ws + L.off_tot);
-    a.tot_ff = a.tot_bits + s.n;
-    a.pos = (u32*)(ws + P.off_pos);
-    a.tot_be = a.pos + (size_t)(JP_MAXSCANS + 1) * s.n;
-    a.ustream = (u32*)(ws + L.off_stream);
-    a.cnt = (u32*)(ws + L.off_cnt);
-    a.sizes = sizes;
-    a.fh = (JpegHuff*)(ws + X.off_fh);
-    a.dht = (JpegDht*)(ws + X.off_dht);
-    a.L = &L;
-    a.out = out;
-    a.out_fs = (int64_t)out_frame_stride;
-    a.n = s.n;
-    a.nslots = ntab * 2;
-    a.hd = &hd;
-    int rc;
-    switch (lay) {
-    case JL420: rc = launch_prog<JL420>(a, p.ncomp, st); break;
-    case JL422: rc = launch_prog<JL422>(a, p.ncomp, st); break;
-    case JL444: rc = launch_prog<JL444>(a, p.ncomp, st); break;
-    default: rc = launch_prog<JLGRAY>(a, p.ncomp, st); break;
-    }
-    if (rc != IMGXF_OK) return rc;
-    return launch_status();
+    JpegJob J;
+    IMGXF_CHECK(jpeg_prepare(J, src, params, true, tables, header, header_bytes, out, out_frame_stride, sizes, workspace, workspace_bytes,
+                             stream));
+    if (J.n == 0) return IMGXF_OK;
+    return with_layout(J.lay, [&](auto l) -> int {
+        launch_transform<decltype(l)::value>(J);
+        IMGXF_CHECK(launch_prog<decltype(l)::value>(J));
+        return launch_status();
+    });
 }

@@ -1,6 +1,7 @@
 // The writer's option space (included by jpeg.hip inside namespace imgxf): what Pillow's `save(fp, "JPEG", quality=q,
-// subsampling=s, optimize=o)` writes for an RGB or "L" frame.  The stages are those of the 4:2:0 writer above; a layout is a
-// template parameter of the kernels that depend on it:
+// subsampling=s, optimize=o)` writes for an RGB or "L" frame.  The stages and the host side are jpeg.hip's, templated on the
+// layout (JLay<L>: jpeg_lens_kernel<L, OPT>, jpeg_emit_kernel<L, OWN>, jpeg_stuff_scan_kernel); this file adds the kernels
+// only the options need:
 //
 //   jpeg_transform_ex_kernel<L>  4:4:4 (MCU 8×8: Y Cb Cr), 4:2:2 (MCU 16×8: Y Y Cb Cr; jcsample.c h2v1_downsample, bias
 //                                0, 1 along a row) and grayscale (one non-interleaved component: one block per MCU); one MCU row
@@ -11,27 +12,10 @@
 //   jpeg_opt_table_kernel        optimize: jchuff.c jpeg_gen_optimal_table + jpeg_make_c_derived_tbl, one workgroup per
 //                                (frame, table): the merge loop on one wave (five symbols per lane, two min-reductions per
 //                                step), the BITS / HUFFVAL of the DHT segment, the canonical codes
-//   jpeg_lens_ex_kernel<L, OPT>  bits per block; with OPT the AC bits come from a walk under the frame's own code lengths
-//   jpeg_emit_ex_kernel<L>       jpeg_emit_kernel over the layout's MCU, with the frame's own tables under optimize
-//   jpeg_stuff_ex_kernel         optimize: jpeg_stuff_kernel after a per-frame header: the host's SOI .. SOF, the frame's DHT
-//                                segments (jcmarker.c write_scan_header order: DC0, AC0, DC1, AC1), SOS
 //
-// jpeg_lens_kernel / jpeg_emit_kernel / jpeg_stuff_kernel and jpeg_transform_kernel are untouched: the 4:2:0 file with the
-// Annex-K tables goes through them exactly as imgxf_jpeg_encode_u8 runs them.
-
-enum { JL420 = 0, JL422 = 1, JL444 = 2, JLGRAY = 3 };
-constexpr int JXP = 512;                     // pixels per row of a jpeg_transform_ex_kernel strip (one MCU row of 8 rows)
-
-template <int L>
-struct JLay {
-    static constexpr int NY = L == JL420 ? 4 : L == JL422 ? 2 : 1;        // luminance blocks per MCU
-    static constexpr int B = NY + (L == JLGRAY ? 0 : 2);                   // blocks per MCU
-    static constexpr int MW = L == JL420 || L == JL422 ? 16 : 8;           // MCU width / height in pixels
-    static constexpr int MH = L == JL420 ? 16 : 8;
-    static constexpr int NC = L == JLGRAY ? 1 : 3;                         // input channels
-    static constexpr int CW = L == JL422 ? JXP / 2 : JXP;                  // chrominance samples per strip row
-    static constexpr int T = JXP / 8 + (NC == 3 ? 2 * CW / 8 : 0);         // one thread per block: 192, 128, 64
-};
+// With optimize the lengths come from a walk under the frame's own code lengths (jpeg_lens_kernel<L, true>), emit reads the
+// frame's own tables (jpeg_emit_kernel<L, true>) and the file's DHT segments and SOS are written on the device
+// (jpeg_stuff_scan_kernel with a one-scan header).
 
 // jpeg_transform_kernel's per-block stage — the same statements as that kernel's tail in jpeg.hip, which keeps its own
 // copy (factored into this function it compiled to different code); a change to one must be made to both.  8×8 samples from LDS (origin, stride bytes between rows) → fdct8 → the JpegQuant
@@ -174,85 +158,7 @@ __global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, i
     jpeg_code_block(origin, stride, chroma, q, slen, coef, coef_fs, dcs, acbits, nblk, f, ((int64_t)my * mw + mx) * Y::B + k);
 }
 
-// ---- the layout's block order -----------------------------------------------------------------------------------------
-
-// jccoefct.c dummy blocks: 4:2:0 as dc_source; 4:2:2: the right-hand luminance block of an MCU past the last block column
-// carries the DC of the block to its left; 4:4:4 and grayscale have none.
-template <int L>
-__device__ __forceinline__ int dc_source_ex(const JpegGeom& g, int mx, int my, int k, bool& dummy) {
-    if (L == JL420) return dc_source(g, mx, my, k, dummy);
-    dummy = L == JL422 && k == 1 && 2 * mx + 1 >= g.bw;
-    return dummy ? 0 : k;
-}
-template <int L>
-__device__ __forceinline__ int block_dc_ex(const int16_t* __restrict__ dcs, const JpegGeom& g, int mcu, int mx, int my, int k, bool& dummy) {
-    return dcs[(int64_t)mcu * JLay<L>::B + dc_source_ex<L>(g, mx, my, k, dummy)];
-}
-// the DC the difference is taken against: the previous block of the same component in scan order (0 at the frame's start)
-template <int L>
-__device__ __forceinline__ int block_pred_ex(const int16_t* __restrict__ dcs, const JpegGeom& g, int mcu, int mx, int my, int k) {
-    constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
-    bool pd;
-    if (k >= NY) return mcu > 0 ? dcs[(int64_t)(mcu - 1) * B + k] : 0;
-    if (k > 0) return block_dc_ex<L>(dcs, g, mcu, mx, my, k - 1, pd);
-    if (mcu == 0) return 0;
-    const int pm = mcu - 1, pmy = pm / g.mw, pmx = pm - pmy * g.mw;
-    return block_dc_ex<L>(dcs, g, pm, pmx, pmy, NY - 1, pd);
-}
-
-// jchuff.c encode_one_block's AC symbols of one block (coefficients interleaved as jpeg_code_block stores them):
-// sym(symbol, coefficient, size) for every ZRL (0xF0), (run << 4) | size and the final EOB (0x00).
-template <typename F>
-__device__ __forceinline__ void ac_symbols(const uint4* __restrict__ blk, F&& sym) {
-    u32 run = 0;
-    uint4 nxt = blk[0];
-    for (int g8 = 0; g8 < 8; ++g8) {
-        const uint4 cur = nxt;
-        if (g8 < 7) nxt = blk[(g8 + 1) * 64];
-        const u32 pairs[4] = {cur.x, cur.y, cur.z, cur.w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const u32 pair = pairs[u];
-            const bool dcpair = g8 == 0 && u == 0;
-            if ((dcpair ? pair >> 16 : pair) == 0) {
-                run += dcpair ? 1 : 2;
-                continue;
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (dcpair && h == 0) continue;
-                const int c = (int)(int16_t)(pair >> (16 * h));
-                if (c == 0) {
-                    ++run;
-                    continue;
-                }
-                for (u32 z = run >> 4; z > 0; --z) sym(0xF0u, 0, 0u);
-                const int sg = c >> 31;
-                const u32 cat = 32 - (u32)__clz((c ^ sg) - sg);
-                sym(((run & 15) << 4) | cat, c, cat);
-                run = 0;
-            }
-        }
-    }
-    if (run) sym(0u, 0, 0u);
-}
-
-__device__ __forceinline__ u32 dc_category(int diff) {
-    const int sg = diff >> 31;
-    return 32 - (u32)__clz((diff ^ sg) - sg);
-}
-
 // ---- optimize: symbol counts, optimal tables --------------------------------------------------------------------------
-
-constexpr int JSLOTS = 4;                    // tables per frame: DC0, AC0, DC1, AC1 (slot = 2·table + is_ac)
-struct JpegDht {                             // one optimal table as its DHT segment carries it
-    u32 nvals;                               // JDHT_OVERFLOW: a code would be longer than 32 bits (the frame fails)
-    u8 bits[16];
-    u8 vals[256];
-};
-static_assert(sizeof(JpegDht) == 276, "imgxf_jpeg_optimal_tables documents this layout");
-constexpr u32 JDHT_OVERFLOW = 0xffffffffu;
-constexpr u32 JSIZE_HUFF_OVERFLOW = 0xfffffffeu;   // sizes[f] of a frame whose optimal table overflows
 
 template <int L>
 __global__ __launch_bounds__(256) void jpeg_gather_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
@@ -266,7 +172,7 @@ __global__ __launch_bounds__(256) void jpeg_gather_kernel(const int16_t* __restr
         const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
         const int16_t* dd = dcs + (int64_t)f * g.nblk;
         bool dummy;
-        const int diff = block_dc_ex<L>(dd, g, mcu, mx, my, k, dummy) - block_pred_ex<L>(dd, g, mcu, mx, my, k);
+        const int diff = block_dc<L>(dd, g, mcu, mx, my, k, dummy) - block_pred<L>(dd, g, mcu, mx, my, k);
         const int t = k >= NY ? 1 : 0;
         atomicAdd(&hist[2 * t][dc_category(diff)], 1u);
         u32* ha = hist[2 * t + 1];
@@ -422,308 +328,17 @@ __global__ __launch_bounds__(256) void jpeg_opt_table_kernel(const u32* __restri
     else if (tid < 16) fh[f].dc[t][tid] = entry;
 }
 
-// ---- lengths, emit, stuffing ----------------------------------------------------------------------------------------
-
-// Code lengths of frame f's tables in LDS: the frame's own under optimize (fh), else the call's (hf).
-// (the kernel argument is read in place: a pointer to it would make the compiler copy it to scratch)
-__device__ __forceinline__ void load_huff(u32 (*sdc)[16], u32 (*sac)[256], const JpegHuff& hf, const JpegHuff* __restrict__ fh, int f) {
-    if (fh) {
-        for (int i = threadIdx.x; i < 32; i += 256) sdc[i >> 4][i & 15] = fh[f].dc[i >> 4][i & 15];
-        for (int i = threadIdx.x; i < 512; i += 256) sac[i >> 8][i & 255] = fh[f].ac[i >> 8][i & 255];
-    } else {
-        for (int i = threadIdx.x; i < 32; i += 256) sdc[i >> 4][i & 15] = hf.dc[i >> 4][i & 15];
-        for (int i = threadIdx.x; i < 512; i += 256) sac[i >> 8][i & 255] = hf.ac[i >> 8][i & 255];
-    }
-}
-
-// bits of every block: DC category code + magnitude bits + the AC bits (the transform's count under the call's tables,
-// or, with OPT, a walk of the block under the frame's own tables)
-template <int L, bool OPT>
-__global__ __launch_bounds__(256) void jpeg_lens_ex_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
-                                                           const uint16_t* __restrict__ acbits, u32* __restrict__ lens, JpegGeom g,
-                                                           JpegHuff hf, const JpegHuff* __restrict__ fh) {
-    constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
-    __shared__ u32 sdc[2][16];
-    __shared__ u32 sac[2][256];
-    const int j = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
-    if (OPT) {
-        load_huff(sdc, sac, hf, fh, f);
-        __syncthreads();
-    }
-    if (j >= g.nblk) return;
-    const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
-    const int16_t* dd = dcs + (int64_t)f * g.nblk;
-    bool dummy;
-    const int diff = block_dc_ex<L>(dd, g, mcu, mx, my, k, dummy) - block_pred_ex<L>(dd, g, mcu, mx, my, k);
-    const int t = k >= NY ? 1 : 0;
-    const u32 cat = dc_category(diff);
-    u32 n = ((OPT ? sdc[t][cat] : hf.dc[t][cat]) >> 16) + cat;
-    if (dummy) {
-        n += (OPT ? sac[t][0] : hf.ac[t][0]) >> 16;
-    } else if (OPT) {
-        const u32* la = sac[t];
-        ac_symbols((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63),
-                   [&](u32 s, int, u32 size) { n += (la[s] >> 16) + size; });
-    } else {
-        n += acbits[(int64_t)f * g.nblk + j];
-    }
-    lens[(int64_t)f * g.nblk + j] = n;
-}
-
-// jpeg_emit_kernel over the layout's MCU (same span merging in LDS), tables from fh[f] when given
-template <int L>
-__global__ __launch_bounds__(256) void jpeg_emit_ex_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
-                                                           const u32* __restrict__ offs, u32* __restrict__ stream, int64_t stream_fs_words,
-                                                           const u32* __restrict__ total_bits, JpegGeom g, JpegHuff hf,
-                                                           const JpegHuff* __restrict__ fh) {
-    constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
-    constexpr u32 LW = JLW;
-    __shared__ u32 sdc[2][16];
-    __shared__ u32 sac[2][256];
-    __shared__ u32 lbuf[LW];
-    const int f = blockIdx.y, j0 = blockIdx.x * 256, j = j0 + threadIdx.x;
-    if (((unsigned long long)total_bits[f] + 31) / 32 > (unsigned long long)stream_fs_words) return;   // reported by the stuffing
-    load_huff(sdc, sac, hf, fh, f);
-    const int j1 = min(j0 + 256, g.nblk);
-    const u32 sbit = offs[(int64_t)f * g.nblk + j0];
-    const u32 ebit = j1 < g.nblk ? offs[(int64_t)f * g.nblk + j1] : total_bits[f];
-    const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
-    const bool merged = nw <= LW;
-    if (merged)
-        for (u32 i = threadIdx.x; i < nw; i += 256) lbuf[i] = 0;
-    __syncthreads();
-    u32* gs = stream + (int64_t)f * stream_fs_words;
-    if (j < g.nblk) {
-        const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
-        const int16_t* dd = dcs + (int64_t)f * g.nblk;
-        bool dummy;
-        const int diff = block_dc_ex<L>(dd, g, mcu, mx, my, k, dummy) - block_pred_ex<L>(dd, g, mcu, mx, my, k);
-        const int t = k >= NY ? 1 : 0;
-        const u32 off = offs[(int64_t)f * g.nblk + j];
-        unsigned long long acc = 0;
-        u32 nb = off & 31;
-        u32 wi = off >> 5;
-        bool first = true;
-        auto put = [&](u32 code, u32 len) {
-            acc |= (unsigned long long)code << (64 - nb - len);
-            nb += len;
-            if (nb >= 32) {
-                if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
-                else if (first) atomicOr(gs + wi, (u32)(acc >> 32));
-                else gs[wi] = (u32)(acc >> 32);
-                first = false;
-                ++wi;
-                acc <<= 32;
-                nb -= 32;
-            }
-        };
-        {
-            const int sg = diff >> 31;
-            const u32 cat = dc_category(diff);
-            const u32 e = sdc[t][cat];
-            put(((e & 0xffff) << cat) | ((u32)(diff + sg) & ((1u << cat) - 1)), (e >> 16) + cat);
-        }
-        const u32* ta = sac[t];
-        if (!dummy) {
-            ac_symbols((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63), [&](u32 s, int c, u32 cat) {
-                const u32 e = ta[s];
-                put(((e & 0xffff) << cat) | ((u32)(c + (c >> 31)) & ((1u << cat) - 1)), (e >> 16) + cat);
-            });
-        } else {
-            put(ta[0] & 0xffff, ta[0] >> 16);
-        }
-        if (nb) {
-            if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
-            else atomicOr(gs + wi, (u32)(acc >> 32));
-        }
-    }
-    if (merged) {
-        __syncthreads();
-        for (u32 i = threadIdx.x; i < nw; i += 256) {
-            const u32 v = lbuf[i];
-            if (i == 0 || i + 1 == nw) {
-                if (v) atomicOr(gs + wlo + i, v);
-            } else {
-                gs[wlo + i] = v;
-            }
-        }
-    }
-}
-
-// Length of frame f's header under optimize: the host's SOI .. SOF, one DHT segment per table (2 + 2 + 1 + 16 + nvals
-// bytes), SOS (6 + 2·ncomp + 2 bytes).
-__device__ __forceinline__ int opt_header_len(int prefix, const JpegDht* __restrict__ dht, int f, int nslots) {
-    int len = prefix + (nslots == 4 ? 14 : 10);
-    for (int s = 0; s < nslots; ++s) len += 21 + (int)dht[(int64_t)f * JSLOTS + s].nvals;
-    return len;
-}
-
-// jpeg_stuff_kernel with a per-frame header: workgroup 0 writes prefix + DHT segments + SOS; the stuffed stream follows it.
-__global__ __launch_bounds__(256) void jpeg_stuff_ex_kernel(const u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ total_bits,
-                                                            const u32* __restrict__ cnt, int64_t cnt_fs, int nchunks,
-                                                            const u32* __restrict__ ff_total, u8* __restrict__ out, int64_t out_fs,
-                                                            u32* __restrict__ sizes, JpegHeader hd, const JpegDht* __restrict__ dht, int nslots) {
-    __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
-    const int f = blockIdx.y;
-    const u32 tb = total_bits[f];
-    const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
-    const int64_t nbytes = ((int64_t)tb + 7) >> 3;
-    const u32 nff = ff_total[f];
-    for (int s = 0; s < nslots; ++s)
-        if (dht[(int64_t)f * JSLOTS + s].nvals == JDHT_OVERFLOW) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) sizes[f] = JSIZE_HUFF_OVERFLOW;
-            return;
-        }
-    const int hlen = opt_header_len(hd.len, dht, f, nslots);
-    const int64_t fsize = (int64_t)hlen + nbytes + nff + 2;
-    const bool fits = !over && fsize <= out_fs;
-    u8* o = out + (int64_t)f * out_fs;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) sizes[f] = fits ? (u32)fsize : 0xffffffffu;
-        if (fits) {
-            for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
-            int pos = hd.len;
-            for (int s = 0; s < nslots; ++s) {                 // jcmarker.c emit_dht
-                const JpegDht& t = dht[(int64_t)f * JSLOTS + s];
-                const int seg = 21 + (int)t.nvals;
-                for (int i = threadIdx.x; i < seg; i += 256) {
-                    u8 b;
-                    if (i == 0) b = 0xff;
-                    else if (i == 1) b = 0xc4;
-                    else if (i == 2) b = (u8)((seg - 2) >> 8);
-                    else if (i == 3) b = (u8)(seg - 2);
-                    else if (i == 4) b = (u8)(((s & 1) << 4) | (s >> 1));
-                    else if (i < 21) b = t.bits[i - 5];
-                    else b = t.vals[i - 21];
-                    o[pos + i] = b;
-                }
-                pos += seg;
-            }
-            if (threadIdx.x < 14) {                            // jcmarker.c emit_sos
-                const u8 sos3[14] = {0xff, 0xda, 0x00, 0x0c, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3f, 0x00};
-                const u8 sos1[10] = {0xff, 0xda, 0x00, 0x08, 0x01, 0x01, 0x00, 0x00, 0x3f, 0x00};
-                if (nslots == 4) o[pos + threadIdx.x] = sos3[threadIdx.x];
-                else if (threadIdx.x < 10) o[pos + threadIdx.x] = sos1[threadIdx.x];
-            }
-            if (threadIdx.x == 0) {
-                o[fsize - 2] = 0xff;
-                o[fsize - 1] = 0xd9;
-            }
-        }
-    }
-    if (!fits) return;
-    const u32* w = stream + (int64_t)f * fs_words;
-    const u32* cf = cnt + (int64_t)f * cnt_fs;
-    const int nvc = (int)((nbytes + JCHUNK - 1) / JCHUNK);
-    for (int c0 = blockIdx.x * 256; c0 < nvc; c0 += gridDim.x * 256) {
-        const int ce = min(c0 + 256, nvc);
-        const u32 pre0 = cf[c0];
-        const u32 pre1 = ce < nchunks ? cf[ce] : nff;
-        u8* dst = o + hlen + (int64_t)c0 * JCHUNK + pre0;
-        const u32 mis = (u32)((uintptr_t)dst & 3);
-        const u32 total = (u32)(min((int64_t)ce * JCHUNK, nbytes) - (int64_t)c0 * JCHUNK) + (pre1 - pre0);
-        const int ci = c0 + threadIdx.x;
-        if (ci < ce) {
-            u32 ws[8];
-            chunk_words(w, ci, nbytes, tb, ws);
-            const int nv = (int)min((int64_t)JCHUNK, nbytes - (int64_t)ci * JCHUNK);
-            u8* p = lb + mis + threadIdx.x * JCHUNK + (cf[ci] - pre0);
-#pragma unroll
-            for (int e = 0; e < JCHUNK; ++e) {
-                if (e < nv) {
-                    const u32 b = (ws[e >> 2] >> (24 - 8 * (e & 3))) & 255;
-                    *p++ = (u8)b;
-                    if (b == 255) *p++ = 0;
-                }
-            }
-        }
-        __syncthreads();
-        u8* base = dst - mis;
-        const u32 end = mis + total;
-        for (u32 k = threadIdx.x * 4; k < end; k += 1024) {
-            if (k >= mis && k + 4 <= end) {
-                *(u32*)(base + k) = *(const u32*)(lb + k);
-            } else {
-                for (u32 e = 0; e < 4; ++e)
-                    if (k + e >= mis && k + e < end) base[k + e] = lb[k + e];
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static int enc_layout(const imgxf_jpeg_enc_params* p) {
-    if (p->optimize != 0 && p->optimize != 1) return -1;
-    const bool s11 = p->h_samp == 1 && p->v_samp == 1, s21 = p->h_samp == 2 && p->v_samp == 1, s22 = p->h_samp == 2 && p->v_samp == 2;
-    if (!(s11 || s21 || s22)) return -1;
-    if (p->ncomp == 1) return JLGRAY;                          // one block per MCU whatever the sampling (the SOF byte only)
-    if (p->ncomp != 3) return -1;
-    return s11 ? JL444 : s21 ? JL422 : JL420;
-}
-
-struct JpegLayoutEx {
-    JpegLayout L;                              // mw / mh / nblk of the layout; the 4:2:0 writer's areas
-    int bpm;                                   // blocks per MCU
-    size_t off_sym, off_fh, off_dht, total;    // optimize: symbol counts [n][4][256], tables [n], DHT [n][4]
-};
-
-static JpegLayoutEx jpeg_layout_ex(int lay, bool opt, int n, int h, int w, size_t out_frame_stride) {
-    JpegLayoutEx X;
-    X.L = jpeg_layout(n, h, w, out_frame_stride);
-    JpegLayout& L = X.L;
-    const int mcw = lay == JL420 || lay == JL422 ? 16 : 8, mch = lay == JL420 ? 16 : 8;
-    X.bpm = lay == JL420 ? 6 : lay == JL422 ? 4 : lay == JL444 ? 3 : 1;
-    L.mw = (w + mcw - 1) / mcw;
-    L.mh = (h + mch - 1) / mch;
-    L.nblk = L.mw * L.mh * X.bpm;
-    L.nparts_blk = (L.nblk + 1023) / 1024;
-    size_t o = 0;                              // jpeg_layout's areas, sized for this layout's blocks
-    L.off_coef = o;   o += al256((size_t)n * (size_t)((L.nblk + 63) / 64) * 64 * 128);
-    L.off_dcs = o;    o += al256((size_t)n * L.nblk * 2);
-    L.off_acb = o;    o += al256((size_t)n * L.nblk * 2);
-    L.off_lens = o;   o += al256((size_t)n * L.nblk * 4);
-    L.off_part = o;   o += al256((size_t)n * (size_t)(L.nparts_blk > L.nparts_chunk ? L.nparts_blk : L.nparts_chunk) * 4);
-    L.off_tot = o;    o += al256((size_t)n * 8);
-    L.off_stream = o; o += al256((size_t)n * L.stream_words * 4);
-    L.off_cnt = o;    o += al256((size_t)n * L.nchunks * 4);
-    L.total = o;
-    X.off_sym = X.off_fh = X.off_dht = o;
-    if (opt) {
-        X.off_sym = o; o += al256((size_t)n * JSLOTS * 256 * 4);
-        X.off_fh = o;  o += al256((size_t)n * sizeof(JpegHuff));
-        X.off_dht = o; o += al256((size_t)n * JSLOTS * sizeof(JpegDht));
+template <int L>
+static void launch_transform(const JpegJob& J) {
+    const JpegLayout& G = J.L;
+    if constexpr (L == JL420) {
+        hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((G.mw + JM - 1) / JM), (unsigned)G.mh, (unsigned)J.n), dim3(JT), 0, J.st,
+                           J.s, J.coef, J.coef_fs, J.dcs, J.acb, G.nblk, G.mw, G.bw, G.bh, J.q);
+    } else {
+        const int per = JXP / JLay<L>::MW;                     // MCUs per workgroup strip
+        hipLaunchKernelGGL(jpeg_transform_ex_kernel<L>, dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)J.n),
+                           dim3(JLay<L>::T), 0, J.st, J.s, J.coef, J.coef_fs, J.dcs, J.acb, G.nblk, G.mw, G.bw, J.q);
     }
-    X.total = o;
-    return X;
-}
-
-template <int L>
-static void launch_transform_ex(const View& s, int16_t* coef, int64_t coef_fs, int16_t* dcs, uint16_t* acb, const JpegLayout& G,
-                                const JpegQuant& q, hipStream_t st) {
-    const int per = JXP / JLay<L>::MW;                         // MCUs per workgroup strip
-    hipLaunchKernelGGL(jpeg_transform_ex_kernel<L>, dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)s.n),
-                       dim3(JLay<L>::T), 0, st, s, coef, coef_fs, dcs, acb, G.nblk, G.mw, G.bw, q);
-}
-
-template <int L>
-static void launch_entropy_ex(bool opt, const int16_t* coef, int64_t coef_fs, const int16_t* dcs, const uint16_t* acb, u32* lens,
-                              u32* sym, JpegHuff* fh, JpegDht* dht, const JpegGeom& g, const JpegHuff& hf, int n, hipStream_t st) {
-    const dim3 bgrid((unsigned)((g.nblk + 255) / 256), (unsigned)n);
-    if (opt) {
-        hipLaunchKernelGGL(jpeg_gather_kernel<L>, bgrid, dim3(256), 0, st, coef, coef_fs, dcs, g, sym);
-        hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(L == JLGRAY ? 2u : 4u, (unsigned)n), dim3(256), 0, st, (const u32*)sym, fh, dht);
-        hipLaunchKernelGGL((jpeg_lens_ex_kernel<L, true>), bgrid, dim3(256), 0, st, coef, coef_fs, dcs, acb, lens, g, hf, (const JpegHuff*)fh);
-    } else if constexpr (L != JL420) {                        // (4:2:0 with fixed tables is imgxf_jpeg_encode_u8)
-        hipLaunchKernelGGL((jpeg_lens_ex_kernel<L, false>), bgrid, dim3(256), 0, st, coef, coef_fs, dcs, acb, lens, g, hf,
-                           (const JpegHuff*)nullptr);
-    }
-}
-
-template <int L>
-static void launch_emit_ex(const int16_t* coef, int64_t coef_fs, const int16_t* dcs, const u32* offs, u32* ustream, int64_t words,
-                           const u32* tot_bits, const JpegGeom& g, const JpegHuff& hf, const JpegHuff* fh, int n, hipStream_t st) {
-    const dim3 bgrid((unsigned)((g.nblk + 255) / 256), (unsigned)n);
-    hipLaunchKernelGGL(jpeg_emit_ex_kernel<L>, bgrid, dim3(256), 0, st, coef, coef_fs, dcs, offs, ustream, words, tot_bits, g, hf, fh);
 }

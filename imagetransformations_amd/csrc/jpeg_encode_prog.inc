@@ -16,8 +16,8 @@
 //   jpeg_opt_table_kernel      the scan's optimal tables (unused slots get a one-symbol count so that the kernel stays in
 //                              bounds; their tables are never written)
 //   jprog_lens_kernel<L, K>    bits per block → scan_rows → bit offsets
-//   jprog_emit_kernel<L, K>    the codes at those offsets (jpeg_emit_ex_kernel's LDS span merging)
-//   jpeg_ffcount_kernel, scan_rows, jprog_stuff_kernel   byte stuffing behind the scan's DHT segments and SOS, at the
+//   jprog_emit_kernel<L, K>    the codes at those offsets (jpeg_zero_kernel, then span_write as jpeg_emit_kernel)
+//   jpeg_ffcount_kernel, scan_rows, jpeg_stuff_scan_kernel (launch_stuff)   byte stuffing behind the scan's DHT segments and SOS, at the
 //                              frame's running file position (pos[scan][frame] on the device: no host round trip)
 //
 // A run's bits are charged to the blocks that make it up: its first block carries the EOBRUN symbol (after its own
@@ -28,7 +28,6 @@ enum { JP_DCF = 0, JP_DCR = 1, JP_ACF = 2, JP_ACR = 3 };
 constexpr u32 JP_MAX_EOBRUN = 0x7FFF;
 constexpr u32 JP_BE_LIMIT = 1000 - 64 + 1;  // jcphuff.c: flush once BE > MAX_CORR_BITS - DCTSIZE2 + 1
 constexpr u32 JP_F = 1, JP_M = 2;           // flags: flushes the pending run; counts in a run
-constexpr int JP_MAXSCANS = 10;
 
 struct JpScan {
     int nb;                                  // blocks in the scan
@@ -131,10 +130,10 @@ __device__ __forceinline__ int jp_dc(const int16_t* __restrict__ dd, const JpegG
     constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
     const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
     bool dummy;
-    const int v = block_dc_ex<L>(dd, g, mcu, mx, my, k, dummy);
+    const int v = block_dc<L>(dd, g, mcu, mx, my, k, dummy);
     t = k >= NY ? 1 : 0;
     if (sc.ah) return (v >> sc.al) & 1;
-    return (v >> sc.al) - (block_pred_ex<L>(dd, g, mcu, mx, my, k) >> sc.al);
+    return (v >> sc.al) - (block_pred<L>(dd, g, mcu, mx, my, k) >> sc.al);
 }
 
 template <int L, int K>
@@ -295,211 +294,22 @@ __global__ __launch_bounds__(256) void jprog_lens_kernel(const int16_t* __restri
     lens[(int64_t)f * sc.nb + b] = n;                        // (offsets: frame stride sc.nb, as jpeg_zero_kernel reads them)
 }
 
-// jpeg_zero_kernel for a scan: blocks inside an EOB run write no bits, so a workgroup's span can be empty (nw == 0), which
-// the sequential writer never meets (every block there takes at least two bits)
-__global__ __launch_bounds__(256) void jprog_zero_kernel(u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ offs,
-                                                         const u32* __restrict__ total_bits, int nb) {
-    const int f = blockIdx.y, j0 = blockIdx.x * 256;
-    const u32 tb = total_bits[f];
-    if (((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words) return;
-    const int j1 = min(j0 + 256, nb);
-    const u32 sbit = offs[(int64_t)f * nb + j0];
-    const u32 ebit = j1 < nb ? offs[(int64_t)f * nb + j1] : tb;
-    const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
-    if (nw == 0) return;
-    u32* gs = stream + (int64_t)f * fs_words + wlo;
-    if (nw <= JLW) {
-        if (threadIdx.x == 0) gs[0] = 0;
-        if (threadIdx.x == 1) gs[nw - 1] = 0;
-    } else {
-        for (u32 i = threadIdx.x; i < nw; i += 256) gs[i] = 0;
-    }
-}
-
-// jpeg_emit_ex_kernel's scheme: a workgroup's 256 blocks are one span of the stream, merged in LDS when it fits
+// span_write around the scan's fields (offsets: sc.nb per frame)
 template <int L, int K>
 __global__ __launch_bounds__(256) void jprog_emit_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
                                                          const u32* __restrict__ runlen, const u32* __restrict__ offs, u32* __restrict__ stream,
                                                          int64_t stream_fs_words, const u32* __restrict__ total_bits, JpegGeom g, JpScan sc,
                                                          const JpegHuff* __restrict__ fh) {
-    constexpr u32 LW = JLW;
     __shared__ u32 sdc[2][16];
     __shared__ u32 sac[256];
-    __shared__ u32 lbuf[LW];
-    const int f = blockIdx.y, j0 = blockIdx.x * 256, b = j0 + threadIdx.x;
-    if (((unsigned long long)total_bits[f] + 31) / 32 > (unsigned long long)stream_fs_words) return;   // reported by the stuffing
+    __shared__ u32 lbuf[JLW];
+    const int f = blockIdx.y;
     jp_load_tables<L, K>(sdc, sac, fh, f, sc);
-    const int j1 = min(j0 + 256, sc.nb);
-    const u32 sbit = offs[(int64_t)f * sc.nb + j0];
-    const u32 ebit = j1 < sc.nb ? offs[(int64_t)f * sc.nb + j1] : total_bits[f];
-    const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
-    const bool merged = nw <= LW;
-    if (merged)
-        for (u32 i = threadIdx.x; i < nw; i += 256) lbuf[i] = 0;
-    __syncthreads();
-    u32* gs = stream + (int64_t)f * stream_fs_words;
-    if (b < sc.nb) {
-        const u32 off = offs[(int64_t)f * sc.nb + b];
-        unsigned long long acc = 0;
-        u32 nb = off & 31;
-        u32 wi = off >> 5;
-        bool first = true;
-        jp_block_codes<L, K>(coef, coef_fs, dcs, runlen, g, sc, f, b, sdc, sac, [&](u32 code, u32 len) {
-            acc |= (unsigned long long)code << (64 - nb - len);
-            nb += len;
-            if (nb >= 32) {
-                if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
-                else if (first) atomicOr(gs + wi, (u32)(acc >> 32));
-                else gs[wi] = (u32)(acc >> 32);
-                first = false;
-                ++wi;
-                acc <<= 32;
-                nb -= 32;
-            }
-        });
-        if (nb) {
-            if (merged) atomicOr(&lbuf[wi - wlo], (u32)(acc >> 32));
-            else atomicOr(gs + wi, (u32)(acc >> 32));
-        }
-    }
-    if (merged) {
-        __syncthreads();
-        for (u32 i = threadIdx.x; i < nw; i += 256) {
-            const u32 v = lbuf[i];
-            if (i == 0 || i + 1 == nw) {
-                if (v) atomicOr(gs + wlo + i, v);
-            } else {
-                gs[wlo + i] = v;
-            }
-        }
-    }
-}
-
-struct JpScanHdr {                           // what the device writes in front of a scan's data
-    u32 slots;                               // DHT segments: bit s = slot s (2·table + is_ac), written in table-id order
-    int soslen;
-    u8 sos[14];
-};
-
-// Sentinels of pos[] / sizes[]: JSIZE_HUFF_OVERFLOW (an optimal code over 32 bits) and 0xFFFFFFFF (capacity); once a scan
-// of frame f fails, the later scans carry the sentinel forward and write nothing.
-__global__ __launch_bounds__(256) void jprog_stuff_kernel(const u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ total_bits,
-                                                          const u32* __restrict__ cnt, int64_t cnt_fs, int nchunks,
-                                                          const u32* __restrict__ ff_total, u8* __restrict__ out, int64_t out_fs,
-                                                          u32* __restrict__ pos, int si, bool last, u32* __restrict__ sizes, JpegHeader hd,
-                                                          const JpegDht* __restrict__ dht, JpScanHdr sh) {
-    __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
-    const int f = blockIdx.y, n = gridDim.y;
-    const u32 base = si == 0 ? (u32)hd.len : pos[(int64_t)si * n + f];
-    const u32 tb = total_bits[f];
-    const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
-    const int64_t nbytes = ((int64_t)tb + 7) >> 3;
-    const u32 nff = ff_total[f];
-    u32 status = base >= JSIZE_HUFF_OVERFLOW ? base : 0u;
-    int hlen = sh.soslen;
-    for (int s = 0; s < JSLOTS; ++s)
-        if ((sh.slots >> s) & 1) {
-            const u32 nv = dht[(int64_t)f * JSLOTS + s].nvals;
-            if (nv == JDHT_OVERFLOW && !status) status = JSIZE_HUFF_OVERFLOW;
-            hlen += 21 + (int)nv;
-        }
-    const int64_t end = (int64_t)base + hlen + nbytes + nff;    // the scan's end; EOI (2 bytes) must still fit
-    if (!status && (over || end + 2 > out_fs)) status = 0xffffffffu;
-    u8* o = out + (int64_t)f * out_fs;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) {
-            if (!last) pos[(int64_t)(si + 1) * n + f] = status ? status : (u32)end;
-            else sizes[f] = status ? status : (u32)(end + 2);
-        }
-        if (!status) {
-            if (si == 0)
-                for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
-            int p = (int)base;
-            for (int s = 0; s < JSLOTS; ++s) {                 // jcmarker.c emit_dht, one table per segment
-                if (!((sh.slots >> s) & 1)) continue;
-                const JpegDht& t = dht[(int64_t)f * JSLOTS + s];
-                const int seg = 21 + (int)t.nvals;
-                for (int i = threadIdx.x; i < seg; i += 256) {
-                    u8 v;
-                    if (i == 0) v = 0xff;
-                    else if (i == 1) v = 0xc4;
-                    else if (i == 2) v = (u8)((seg - 2) >> 8);
-                    else if (i == 3) v = (u8)(seg - 2);
-                    else if (i == 4) v = (u8)(((s & 1) << 4) | (s >> 1));
-                    else if (i < 21) v = t.bits[i - 5];
-                    else v = t.vals[i - 21];
-                    o[p + i] = v;
-                }
-                p += seg;
-            }
-            if (threadIdx.x < sh.soslen) o[p + threadIdx.x] = sh.sos[threadIdx.x];
-            if (last && threadIdx.x == 0) {
-                o[end] = 0xff;
-                o[end + 1] = 0xd9;
-            }
-        }
-    }
-    if (status) return;
-    const int64_t dbase = (int64_t)base + hlen;
-    const u32* w = stream + (int64_t)f * fs_words;
-    const u32* cf = cnt + (int64_t)f * cnt_fs;
-    const int nvc = (int)((nbytes + JCHUNK - 1) / JCHUNK);
-    for (int c0 = blockIdx.x * 256; c0 < nvc; c0 += gridDim.x * 256) {
-        const int ce = min(c0 + 256, nvc);
-        const u32 pre0 = cf[c0];
-        const u32 pre1 = ce < nchunks ? cf[ce] : nff;
-        u8* dst = o + dbase + (int64_t)c0 * JCHUNK + pre0;
-        const u32 mis = (u32)((uintptr_t)dst & 3);
-        const u32 total = (u32)(min((int64_t)ce * JCHUNK, nbytes) - (int64_t)c0 * JCHUNK) + (pre1 - pre0);
-        const int ci = c0 + threadIdx.x;
-        if (ci < ce) {
-            u32 ws[8];
-            chunk_words(w, ci, nbytes, tb, ws);
-            const int nv = (int)min((int64_t)JCHUNK, nbytes - (int64_t)ci * JCHUNK);
-            u8* p = lb + mis + threadIdx.x * JCHUNK + (cf[ci] - pre0);
-#pragma unroll
-            for (int e = 0; e < JCHUNK; ++e) {
-                if (e < nv) {
-                    const u32 v = (ws[e >> 2] >> (24 - 8 * (e & 3))) & 255;
-                    *p++ = (u8)v;
-                    if (v == 255) *p++ = 0;
-                }
-            }
-        }
-        __syncthreads();
-        u8* bp = dst - mis;
-        const u32 endk = mis + total;
-        for (u32 k = threadIdx.x * 4; k < endk; k += 1024) {
-            if (k >= mis && k + 4 <= endk) {
-                *(u32*)(bp + k) = *(const u32*)(lb + k);
-            } else {
-                for (u32 e = 0; e < 4; ++e)
-                    if (k + e >= mis && k + e < endk) bp[k + e] = lb[k + e];
-            }
-        }
-        __syncthreads();
-    }
+    span_write(lbuf, offs + (int64_t)f * sc.nb, sc.nb, total_bits[f], stream + (int64_t)f * stream_fs_words, stream_fs_words,
+               [&](int b, auto&& put) { jp_block_codes<L, K>(coef, coef_fs, dcs, runlen, g, sc, f, b, sdc, sac, put); });
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-
-struct JpegLayoutProg {
-    JpegLayoutEx X;                          // the optimize layout (coefficients, lengths, stream, counts, tables)
-    size_t off_flags, off_nbe, off_runlen, off_pos, total;
-};
-
-static JpegLayoutProg jpeg_layout_prog(int lay, int n, int h, int w, size_t out_frame_stride) {
-    JpegLayoutProg P;
-    P.X = jpeg_layout_ex(lay, true, n, h, w, out_frame_stride);
-    const size_t nb = (size_t)n * P.X.L.nblk * 4;
-    size_t o = P.X.total;
-    P.off_flags = o;  o += al256(nb);
-    P.off_nbe = o;    o += al256(nb);
-    P.off_runlen = o; o += al256(nb);
-    P.off_pos = o;    o += al256((size_t)(JP_MAXSCANS + 1) * n * 4 + (size_t)n * 4);   // pos[scan][n], then BE totals [n]
-    P.total = o;
-    return P;
-}
 
 // jcparam.c jpeg_simple_progression: components (-1: all, interleaved), Ss, Se, Ah, Al
 static int prog_script(int ncomp, int (*sc)[5]) {
@@ -511,54 +321,34 @@ static int prog_script(int ncomp, int (*sc)[5]) {
     return ns;
 }
 
-struct JpProgArgs {
-    const int16_t* coef;
-    int64_t coef_fs;
-    const int16_t* dcs;
-    JpegGeom g;
-    u32 *sym, *flags, *nbe, *runlen, *lens, *part, *tot_bits, *tot_ff, *tot_be, *ustream, *cnt, *pos, *sizes;
-    JpegHuff* fh;
-    JpegDht* dht;
-    const JpegLayout* L;
-    u8* out;
-    int64_t out_fs;
-    int n, nslots;
-    const JpegHeader* hd;
-};
-
 template <int L, int K>
-static int launch_prog_scan(const JpProgArgs& a, const JpScan& sc, const JpScanHdr& sh, u32 unused, int si, bool last, hipStream_t st) {
+static int launch_prog_scan(const JpegJob& a, const JpScan& sc, const JpScanHdr& sh, u32 unused, int si, bool last) {
     const dim3 bgrid((unsigned)((sc.nb + 255) / 256), (unsigned)a.n);
-    const int64_t fs = a.g.nblk;
+    const int64_t fs = a.g.nblk, words = a.L.stream_words;
+    const int16_t *coef = a.coef, *dcs = a.dcs;
+    hipStream_t st = a.st;
     if (K != JP_DCR) {
         if (hipMemsetAsync(a.sym, 0, (size_t)a.n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
-        hipLaunchKernelGGL((jprog_count_kernel<L, K>), bgrid, dim3(256), 0, st, a.coef, a.coef_fs, a.dcs, a.g, sc, a.sym, a.flags, a.nbe,
+        hipLaunchKernelGGL((jprog_count_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, a.g, sc, a.sym, a.flags, a.nbe,
                            a.runlen, unused);
         if (K == JP_ACR) IMGXF_CHECK(scan_rows(a.nbe, fs, sc.nb, a.n, a.part, a.tot_be, st));
         if (K == JP_ACF || K == JP_ACR)
             hipLaunchKernelGGL(jprog_runs_kernel, bgrid, dim3(256), 0, st, (const u32*)a.flags, (const u32*)(K == JP_ACR ? a.nbe : nullptr),
                                (const u32*)a.tot_be, a.runlen, a.sym, sc.nb, fs, sc.slot);
-        hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3((unsigned)a.nslots, (unsigned)a.n), dim3(256), 0, st, (const u32*)a.sym, a.fh, a.dht);
+        hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(a.ncomp == 1 ? 2u : 4u, (unsigned)a.n), dim3(256), 0, st, (const u32*)a.sym, a.fh, a.dht);
     }
-    hipLaunchKernelGGL((jprog_lens_kernel<L, K>), bgrid, dim3(256), 0, st, a.coef, a.coef_fs, a.dcs, (const u32*)a.runlen, a.lens, a.g, sc,
+    hipLaunchKernelGGL((jprog_lens_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, a.lens, a.g, sc,
                        (const JpegHuff*)a.fh);
     IMGXF_CHECK(scan_rows(a.lens, sc.nb, sc.nb, a.n, a.part, a.tot_bits, st));
-    hipLaunchKernelGGL(jprog_zero_kernel, bgrid, dim3(256), 0, st, a.ustream, a.L->stream_words, (const u32*)a.lens, (const u32*)a.tot_bits, sc.nb);
-    hipLaunchKernelGGL((jprog_emit_kernel<L, K>), bgrid, dim3(256), 0, st, a.coef, a.coef_fs, a.dcs, (const u32*)a.runlen, (const u32*)a.lens,
-                       a.ustream, a.L->stream_words, (const u32*)a.tot_bits, a.g, sc, (const JpegHuff*)a.fh);
-    const unsigned cwg = (unsigned)((a.L->nchunks + 255) / 256);
-    const dim3 cgrid(cwg < 256u ? cwg : 256u, (unsigned)a.n);
-    hipLaunchKernelGGL(jpeg_ffcount_kernel, cgrid, dim3(256), 0, st, (const u32*)a.ustream, a.L->stream_words, (const u32*)a.tot_bits, a.cnt,
-                       (int64_t)a.L->nchunks, a.L->nchunks);
-    IMGXF_CHECK(scan_rows(a.cnt, a.L->nchunks, a.L->nchunks, a.n, a.part, a.tot_ff, st));
-    hipLaunchKernelGGL(jprog_stuff_kernel, cgrid, dim3(256), 0, st, (const u32*)a.ustream, a.L->stream_words, (const u32*)a.tot_bits,
-                       (const u32*)a.cnt, (int64_t)a.L->nchunks, a.L->nchunks, (const u32*)a.tot_ff, a.out, a.out_fs, a.pos, si, last,
-                       a.sizes, *a.hd, (const JpegDht*)a.dht, sh);
-    return launch_status();
+    hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, st, a.ustream, words, (const u32*)a.lens, (const u32*)a.tot_bits, sc.nb);
+    hipLaunchKernelGGL((jprog_emit_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, (const u32*)a.lens,
+                       a.ustream, words, (const u32*)a.tot_bits, a.g, sc, (const JpegHuff*)a.fh);
+    return launch_stuff(a, &sh, si, last);
 }
 
 template <int L>
-static int launch_prog(const JpProgArgs& a, int ncomp, hipStream_t st) {
+static int launch_prog(const JpegJob& a) {
+    const int ncomp = a.ncomp;
     int script[JP_MAXSCANS][5];
     const int ns = prog_script(ncomp, script);
     const u32 all = ncomp == 3 ? 0xfu : 0x3u;
@@ -598,8 +388,8 @@ static int launch_prog(const JpProgArgs& a, int ncomp, hipStream_t st) {
         const u32 unused = all & ~sh.slots;
         const bool last = si == ns - 1;
         int rc;
-        if (comp < 0) rc = sc.ah ? launch_prog_scan<L, JP_DCR>(a, sc, sh, unused, si, last, st) : launch_prog_scan<L, JP_DCF>(a, sc, sh, unused, si, last, st);
-        else rc = sc.ah ? launch_prog_scan<L, JP_ACR>(a, sc, sh, unused, si, last, st) : launch_prog_scan<L, JP_ACF>(a, sc, sh, unused, si, last, st);
+        if (comp < 0) rc = sc.ah ? launch_prog_scan<L, JP_DCR>(a, sc, sh, unused, si, last) : launch_prog_scan<L, JP_DCF>(a, sc, sh, unused, si, last);
+        else rc = sc.ah ? launch_prog_scan<L, JP_ACR>(a, sc, sh, unused, si, last) : launch_prog_scan<L, JP_ACF>(a, sc, sh, unused, si, last);
         if (rc != IMGXF_OK) return rc;
     }
     return IMGXF_OK;

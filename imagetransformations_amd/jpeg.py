@@ -176,25 +176,15 @@ def encode_device(frames: torch.Tensor, quality: int = 75, capacity: int | None 
     view = F.view_of(frames)
     stream = torch.cuda.current_stream(frames.device).cuda_stream
     if default:
-        F.call("imgxf_jpeg_workspace_bytes", n, h, w, cap, ctypes.byref(nbytes))
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
-        with torch.cuda.device(frames.device):   # the frames' device, not torch's current one (as ops._launch)
-            F.call("imgxf_jpeg_encode_u8", F.vp(view), ctypes.addressof(tables(quality)), hdr, len(hdr), files.data_ptr(), cap,
-                   sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
-    elif progressive:
-        params = F.JpegEncParams(ncomp, hv[0], hv[1], 1)
-        F.call("imgxf_jpeg_workspace_bytes_prog", ctypes.byref(params), n, h, w, cap, ctypes.byref(nbytes))
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
-        with torch.cuda.device(frames.device):
-            F.call("imgxf_jpeg_encode_prog_u8", F.vp(view), ctypes.byref(params), ctypes.addressof(tables(quality)), hdr, len(hdr),
-                   files.data_ptr(), cap, sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
-    else:
-        params = F.JpegEncParams(ncomp, hv[0], hv[1], int(optimize))
-        F.call("imgxf_jpeg_workspace_bytes_ex", ctypes.byref(params), n, h, w, cap, ctypes.byref(nbytes))
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
-        with torch.cuda.device(frames.device):
-            F.call("imgxf_jpeg_encode_ex_u8", F.vp(view), ctypes.byref(params), ctypes.addressof(tables(quality)), hdr, len(hdr),
-                   files.data_ptr(), cap, sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
+        suffix, params = "", ()
+    else:                                          # `optimize` is moot in a progressive file: the C side ignores it
+        suffix = "_prog" if progressive else "_ex"
+        params = (ctypes.byref(F.JpegEncParams(ncomp, hv[0], hv[1], 1 if progressive else int(optimize))),)
+    F.call(f"imgxf_jpeg_workspace_bytes{suffix}", *params, n, h, w, cap, ctypes.byref(nbytes))
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=frames.device)
+    with torch.cuda.device(frames.device):        # the frames' device, not torch's current one (as ops._launch)
+        F.call(f"imgxf_jpeg_encode{suffix}_u8", F.vp(view), *params, ctypes.addressof(tables(quality)), hdr, len(hdr), files.data_ptr(),
+               cap, sizes.data_ptr(), ws.data_ptr(), nbytes.value, stream)
     return files, sizes.to(torch.int64) & 0xFFFFFFFF
 
 

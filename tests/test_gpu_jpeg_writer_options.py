@@ -224,3 +224,24 @@ def test_default_call_uses_the_420_writer(monkeypatch):
     names.clear()
     assert jpeg.encode(t, 90, subsampling=0)[0] == pil_bytes(a, quality=90, subsampling=0)
     assert names == ["imgxf_jpeg_workspace_bytes_ex", "imgxf_jpeg_encode_ex_u8"]
+
+
+@pytest.mark.parametrize("mode", ["std", "opt", "prog"])
+@pytest.mark.parametrize("layout", ["gray", "4:2:0", "4:4:4"])
+def test_span_too_long_for_lds(layout, mode):
+    """An emit workgroup whose 256 blocks take more than the 4096 words of its LDS buffer writes to the stream directly:
+    one piece of code for the three encoders.  Binary noise at quality 100 takes over 512 bits per block even under
+    optimal tables; gray 128×128 is exactly one workgroup, so its whole stream is one span.  The precondition is asserted
+    on Pillow's own file (header < 1024 bytes), so the test cannot pass by missing the branch; a progressive scan's span
+    is shorter, those cases are here for equality only."""
+    rgb = (np.random.default_rng(5).integers(0, 2, (128, 128, 3)) * 255).astype(np.uint8)
+    a = np.ascontiguousarray(rgb[..., 0]) if layout == "gray" else rgb
+    params = dict(quality=100, optimize=mode == "opt", progressive=mode == "prog")
+    if layout != "gray":
+        params["subsampling"] = layout
+    ref = pil_bytes(a, **params)
+    if layout == "gray" and mode != "prog":
+        assert len(ref) - 1024 > 16384                          # 256 blocks: one span
+    if layout == "4:2:0" and mode == "std":
+        assert (len(ref) - 1024) * 256 / 384 > 16384            # 384 blocks: the mean span of 256
+    assert jpeg.encode(torch.from_numpy(a).cuda()[None], **params)[0] == ref
