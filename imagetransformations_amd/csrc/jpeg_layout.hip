@@ -147,7 +147,26 @@ void derive_lut(const HuffSpec& H, imgxf_jpeg_dec_lut& L) {
     memcpy(L.huffval, H.vals, 256);
 }
 
+// the index in luts[] of H's derived table: equal specifications share one (-1: luts[] is full)
+int lut_index(std::vector<HuffSpec>& uniq, const HuffSpec& H, imgxf_jpeg_dec_lut* luts, int lut_cap) {
+    for (size_t u = 0; u < uniq.size(); ++u)
+        if (!memcmp(uniq[u].bits, H.bits, 16) && uniq[u].nvals == H.nvals && !memcmp(uniq[u].vals, H.vals, (size_t)H.nvals)) return (int)u;
+    if ((int)uniq.size() >= lut_cap) return -1;
+    uniq.push_back(H);
+    derive_lut(H, luts[uniq.size() - 1]);
+    return (int)uniq.size() - 1;
+}
+
 struct Geometry { int hmax, vmax, mcux, mcuy, ri, want; int ch[4], cv[4]; };
+
+// the MCU grid and the restart segments of an interleaved scan, once ch / cv / hmax / vmax are known
+void mcu_grid(const Parsed& P, Geometry& g) {
+    g.mcux = (P.width + 8 * g.hmax - 1) / (8 * g.hmax);
+    g.mcuy = (P.height + 8 * g.vmax - 1) / (8 * g.vmax);
+    const int total = g.mcux * g.mcuy;
+    g.ri = P.dri ? P.dri : total;
+    g.want = (total + g.ri - 1) / g.ri;
+}
 
 int geometry(const Parsed& P, Geometry& g) {
     for (int c = 0; c < P.ncomp; ++c) { g.ch[c] = P.ch[c]; g.cv[c] = P.cv[c]; }
@@ -159,11 +178,7 @@ int geometry(const Parsed& P, Geometry& g) {
         if (g.cv[c] > g.vmax) g.vmax = g.cv[c];
     }
     if (P.width < 1 || P.height < 1) return IMGXF_JPEG_E_MARKERS;
-    g.mcux = (P.width + 8 * g.hmax - 1) / (8 * g.hmax);
-    g.mcuy = (P.height + 8 * g.vmax - 1) / (8 * g.vmax);
-    const int total = g.mcux * g.mcuy;
-    g.ri = P.dri ? P.dri : total;
-    g.want = (total + g.ri - 1) / g.ri;
+    mcu_grid(P, g);
     if (P.ncomp == 3) {
         const bool ok = g.ch[0] == g.hmax && g.cv[0] == g.vmax && g.ch[1] == g.ch[2] && g.cv[1] == g.cv[2] &&
                         (g.ch[1] * 2 == g.hmax || g.ch[1] == g.hmax) && (g.cv[1] * 2 == g.vmax || g.cv[1] == g.vmax) &&
@@ -245,11 +260,7 @@ int geometry_ext(const Parsed& P, Geometry& g) {
     if (blocks > 10) return IMGXF_JPEG_E_MCU_SIZE;
     for (int c = 0; c < P.ncomp; ++c)
         if (g.hmax % g.ch[c] || g.vmax % g.cv[c]) return IMGXF_JPEG_E_FRACTIONAL;
-    g.mcux = (P.width + 8 * g.hmax - 1) / (8 * g.hmax);
-    g.mcuy = (P.height + 8 * g.vmax - 1) / (8 * g.vmax);
-    const int total = g.mcux * g.mcuy;
-    g.ri = P.dri ? P.dri : total;
-    g.want = (total + g.ri - 1) / g.ri;
+    mcu_grid(P, g);
     return 0;
 }
 
@@ -309,21 +320,8 @@ int layout_sequential(const uint8_t* const* files, const size_t* sizes, int n, I
         for (int c = 0; c < P.ncomp; ++c) {
             imgxf_jpeg_dec_comp& cp = im.comp[c];
             cp.h = g.ch[c]; cp.v = g.cv[c];
-            int tabs[2];
-            for (int cls = 0; cls < 2; ++cls) {
-                const HuffSpec& H = P.huff[cls][cls ? P.ta[c] : P.td[c]];
-                int idx = -1;
-                for (size_t u = 0; u < uniq.size(); ++u)
-                    if (!memcmp(uniq[u].bits, H.bits, 16) && uniq[u].nvals == H.nvals && !memcmp(uniq[u].vals, H.vals, (size_t)H.nvals)) { idx = (int)u; break; }
-                if (idx < 0) {
-                    if ((int)uniq.size() >= lut_cap) return IMGXF_ERR_WORKSPACE;
-                    idx = (int)uniq.size();
-                    uniq.push_back(H);
-                    derive_lut(H, luts[idx]);
-                }
-                tabs[cls] = idx;
-            }
-            cp.dc_tab = tabs[0]; cp.ac_tab = tabs[1];
+            if ((cp.dc_tab = lut_index(uniq, P.huff[0][P.td[c]], luts, lut_cap)) < 0) return IMGXF_ERR_WORKSPACE;
+            if ((cp.ac_tab = lut_index(uniq, P.huff[1][P.ta[c]], luts, lut_cap)) < 0) return IMGXF_ERR_WORKSPACE;
             if (nq >= quant_cap) return IMGXF_ERR_WORKSPACE;
             cp.quant = nq;
             memcpy(quants + (size_t)nq * 64, P.qt[P.tq[c]], 64 * sizeof(uint16_t));
@@ -542,15 +540,6 @@ int parse_progressive(const uint8_t* d, size_t n, ProgParsed& G) {
     if (G.scans.empty()) return IMGXF_JPEG_E_MARKERS;
     if (would_smooth(G, coef_bits)) return IMGXF_JPEG_E_SMOOTHING;
     return 0;
-}
-
-int lut_index(std::vector<HuffSpec>& uniq, const HuffSpec& H, imgxf_jpeg_dec_lut* luts, int lut_cap) {
-    for (size_t u = 0; u < uniq.size(); ++u)
-        if (!memcmp(uniq[u].bits, H.bits, 16) && uniq[u].nvals == H.nvals && !memcmp(uniq[u].vals, H.vals, (size_t)H.nvals)) return (int)u;
-    if ((int)uniq.size() >= lut_cap) return -1;
-    uniq.push_back(H);
-    derive_lut(H, luts[uniq.size() - 1]);
-    return (int)uniq.size() - 1;
 }
 
 } // namespace

@@ -70,6 +70,82 @@ def test_4k_cmyk_and_440_without_restart_markers(device):
         assert np.array_equal(t.cpu().numpy(), pillow_rgb(data))
 
 
+def as_440(f: bytes) -> bytes:
+    """a 4:2:2 file as the 4:4:0 file of the transposed size: luma sampling byte and frame size swapped, the same blocks"""
+    g = bytearray(f)
+    sof = g.index(b"\xff\xc0")
+    assert g[sof + 11] == 0x21
+    g[sof + 11] = 0x12
+    g[sof + 5:sof + 7], g[sof + 7:sof + 9] = g[sof + 7:sof + 9], g[sof + 5:sof + 7]
+    return bytes(g)
+
+
+LANES, WAVE_PER_SEGMENT, WG256, WG1024 = range(4)
+
+
+def huff_classes(files, extended):
+    """csrc/jpeg_decode.hip huff_class, restated over the host layout: [(class, chunks of the first segment)] per file"""
+    from imagetransformations_amd import jpeg_decode
+    lay = jpeg_decode._Layout(files, False, extended)
+    assert list(lay.status) == [0] * len(files)
+    lay.fill()
+    out = []
+    for im in lay.images:
+        a, b = int(lay.seg_len_h[im.seg_first]), int(lay.seg_len_h[im.seg_first + im.seg_count - 1])
+        L = (a + b) // 2
+        chunks256 = (L * 8 // 1024 + 255) // 256 + 1
+        if L < 2048:
+            cls = LANES
+        elif L > 2 * 256 * 128:
+            cls = WG1024
+        elif im.seg_count >= 2 and L <= 16384:
+            cls = WAVE_PER_SEGMENT
+        else:
+            cls = WG256 if im.seg_count * chunks256 * 1900 < (im.seg_count + 63) // 64 * L else LANES
+        width = {WG256: 256, WG1024: 1024}.get(cls)
+        nsub = (a * 8 + 1023) // 1024                                 # subsequences of PAR_BITS bits, `width` per chunk
+        out.append((cls, (nsub + width - 1) // width if width else None))
+    return out
+
+
+def test_every_decoder_class_on_both_descriptors(device, monkeypatch):
+    """Both descriptors through each of the four entropy decoders (a lane, a wave or a workgroup of 256 / 1024 per segment;
+    workgroups with one chunk of subsequences and with two, where the state is carried over), asserting the class each file
+    takes — a file that silently moved to another class would hide a broken kernel instance — and the pixels against
+    Pillow, with the in-segment decoders and with IMGXF_JPEG_SERIAL_HUFFMAN=1."""
+    from imagetransformations_amd import jpeg_decode
+    P = photo_like
+    baseline = [(pillow_file(P(1, 64, 64), "RGB"), LANES, None),
+                (pillow_file(P(2, 48, 40), "L", restart_marker_blocks=2), LANES, None),
+                (pillow_file(P(3, 256, 512), "RGB", quality=95, subsampling=0, restart_marker_rows=1), WAVE_PER_SEGMENT, None),
+                (pillow_file(P(3, 256, 512), "RGB", quality=95, subsampling=2, restart_marker_rows=2), WAVE_PER_SEGMENT, None),
+                (pillow_file(P(4, 160, 200), "RGB", quality=90), WG256, 1),
+                (pillow_file(P(5, 200, 240), "L", quality=90), WG256, 1),
+                (pillow_file(P(6, 240, 320), "RGB", quality=90, subsampling=1), WG256, 2),
+                (pillow_file(P(7, 384, 512), "RGB", quality=95, subsampling=0), WG1024, 2)]
+    ext = [(pillow_file(P(8, 32, 40), "CMYK", quality=80), LANES, None),                      # CMYK, RGB-coded: table period 1
+           (pillow_file(P(9, 128, 512), "CMYK", quality=95, restart_marker_rows=1), WAVE_PER_SEGMENT, None),
+           (pillow_file(P(10, 128, 160), "CMYK", quality=90), WG256, 1),
+           (pillow_file(P(10, 160, 200), "CMYK", quality=92), WG256, 2),
+           (pillow_file(P(11, 320, 384), "CMYK", quality=95), WG1024, 2),
+           (pillow_file(P(12, 128, 160), "RGB", quality=90, keep_rgb=True), WG256, 1),
+           (as_440(pillow_file(P(13, 40, 56), "RGB", quality=80, subsampling=1)), LANES, None),    # 4:4:0: period = 4 = blocks per MCU
+           (as_440(pillow_file(P(14, 256, 512), "RGB", quality=95, subsampling=1, restart_marker_rows=2)), WAVE_PER_SEGMENT, None),
+           (as_440(pillow_file(P(15, 160, 200), "RGB", quality=90, subsampling=1)), WG256, 1),
+           (as_440(pillow_file(P(16, 512, 512), "RGB", quality=95, subsampling=1)), WG1024, 2)]
+    for group, extended in ((baseline, False), (ext, True)):
+        got = huff_classes([f for f, _, _ in group], extended)
+        assert got == [(c, n) for _, c, n in group]
+    files = [f for f, _, _ in baseline + ext]
+    ref = [pillow_rgb(f) for f in files]
+    for serial in (False, True):
+        if serial:
+            monkeypatch.setenv("IMGXF_JPEG_SERIAL_HUFFMAN", "1")
+        frames = jpeg_decode.decode(files, device, extended=True)
+        for i, (t, r) in enumerate(zip(frames, ref)):
+            assert np.array_equal(t.cpu().numpy(), r), (serial, i)
+
+
 def test_mixed_batch_order_sizes_statuses_and_damage(device):
     from imagetransformations_amd import jpeg_decode
     from imagetransformations_amd._ffi import ImgxfError
