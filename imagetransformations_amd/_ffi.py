@@ -139,6 +139,10 @@ SIGNATURES = {
     "imgxf_np_accept": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "imgxf_np_normals_f32": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "imgxf_np_mixed_walk": [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p],
+    "imgxf_np_mixed_fill": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                            C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "imgxf_mt19937_jump": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "imgxf_mt19937_stretches": [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p],
     "imgxf_mt19937_blocks": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],

@@ -262,6 +262,227 @@ __global__ __launch_bounds__(256) void np_normals_kernel(const u32* __restrict__
 }
 } // namespace imgxf
 
+namespace imgxf {
+// A list of MIXED legacy calls in call order — normal, random_sample, scalar randint — over the same word stream
+// (imagetransformations_amd/numpy_stream.py `mixed` states the rules).  Where a request starts depends on how many words the
+// requests before it consumed, so ONE workgroup walks the requests (np_mixed_walk_kernel): a random request advances by two
+// words per double, a randint runs its rejection loop, a normal request counts accepted groups chunk by chunk until it has
+// the groups it needs and notes the running count at every chunk start.  The whole grid then writes the values
+// (np_mixed_fill_kernel), one workgroup per (request, chunk), ranking inside the chunk and adding the walk's count.
+//
+// A chunk is MIX_CHUNK groups = MIX_ROUNDS rounds of one group per thread; group order inside a chunk is (round, wave, lane),
+// so the 16 waves x 4 rounds leave 64 wave counts, which one wave scans.
+constexpr int MIX_WG = 1024, MIX_ROUNDS = 4, MIX_CHUNK = MIX_WG * MIX_ROUNDS, MIX_WAVES = MIX_WG / 64;
+static_assert(MIX_WAVES * MIX_ROUNDS == 64, "one wave scans the wave counts of a chunk");
+enum { MIX_NORMAL = 0, MIX_RANDOM = 1, MIX_RANDINT = 2 };
+enum { MIX_LEAD_NONE = 0, MIX_LEAD_GIVEN = 1, MIX_LEAD_CARRIED = 2 };
+enum { MIX_INFO_ERR = 0, MIX_INFO_POS = 1, MIX_INFO_X1 = 2, MIX_INFO_R2 = 3, MIX_INFO_NRISKY = 4, MIX_INFO_WORDS = 8 };
+enum { MIX_ERR_STREAM = 1, MIX_ERR_MARGIN = 2 };
+
+// (host-built; imagetransformations_amd/numpy_stream.py _MIX_REQ)
+struct MixReq {
+    int kind, lead;              // lead (normal): the request's first sample is the cached normal — GIVEN: the one the call starts with
+                                 // (its exact value is `gauss0`), CARRIED: the one an earlier request of this list left
+    long long count;             // normal: samples (the leading cached one included); random: doubles
+    double scale;
+    long long out_off;           // byte offset of the request's results in `out`
+    long long tab_off;           // normal: where its chunk table starts
+    long long max_chunks;        // normal: chunks the host's margin allows (table entries and fill workgroups it reserved)
+    u32 rng, mask;               // randint: high - 1 - low and the smallest 2^k - 1 >= rng
+    long long blk0;              // the request's first fill workgroup
+};
+// what the walk leaves per request for the fill kernel
+struct MixWalk { long long start, chunks; double x1, r2; };       // (x1, r2): the CARRIED cached normal the request starts with
+
+// Acceptance of the chunk's groups first .. first + MIX_CHUNK - 1 (those below `limit`, the whole groups the stream holds from
+// `words` on) and their ranks: rank[j] = 1-based rank inside the chunk of this thread's group of round j if accepted, else 0.
+// Returns the chunk's accepted count.  cnt: 65 words of LDS; ends behind a barrier, and the caller puts one before the next use.
+__device__ __forceinline__ int mix_chunk_ranks(const u32* __restrict__ words, long long first, long long limit, int* cnt,
+                                               double (&x1)[MIX_ROUNDS], double (&x2)[MIX_ROUNDS], double (&r2)[MIX_ROUNDS], int (&rank)[MIX_ROUNDS]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int below[MIX_ROUNDS];
+    bool acc[MIX_ROUNDS];
+#pragma unroll
+    for (int j = 0; j < MIX_ROUNDS; ++j) {
+        const long long g = first + (long long)j * MIX_WG + tid;
+        acc[j] = false;
+        x1[j] = x2[j] = r2[j] = 0.0;
+        if (g < limit) {
+            np_group(words + 4 * g, x1[j], x2[j], r2[j]);
+            acc[j] = r2[j] < 1.0 && r2[j] != 0.0;
+        }
+        const unsigned long long b = __ballot(acc[j]);
+        below[j] = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) cnt[j * MIX_WAVES + wave] = __popcll(b);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int v = cnt[lane];
+        int s = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(s, d); if (lane >= d) s += o; }
+        cnt[lane] = s - v;
+        if (lane == 63) cnt[64] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MIX_ROUNDS; ++j) rank[j] = acc[j] ? cnt[j * MIX_WAVES + wave] + below[j] + 1 : 0;
+    return cnt[64];
+}
+
+// words: the raw stream, nwords of it; pos: the generator's position.  Every read is checked against nwords: running short
+// sets info[ERR] and ends the walk.  ints[i] = v of randint request i (the host adds low).  info: ERR, the final position, the
+// (x1, r2) of the cached normal the list leaves (if it is not the one it started with).
+__global__ __launch_bounds__(MIX_WG) void np_mixed_walk_kernel(const u32* __restrict__ words, long long nwords, long long pos,
+                                                               const MixReq* __restrict__ reqs, int nreq, MixWalk* __restrict__ walk,
+                                                               long long* __restrict__ table, long long* __restrict__ ints,
+                                                               long long* __restrict__ info) {
+    __shared__ int cnt[65];
+    __shared__ long long s_last;
+    __shared__ double s_x1, s_r2;
+    const int tid = threadIdx.x, lane = tid & 63;
+    double px1 = 0.0, pr2 = 0.0;                                     // the cached normal an odd request left: f x1 of (x1, r2)
+    int err = 0;
+    for (int i = 0; i < nreq && !err; ++i) {
+        const MixReq q = reqs[i];
+        long long chunks = 0;
+        const long long start = pos;
+        const double lx1 = px1, lr2 = pr2;                           // (a CARRIED lead: the request may leave a new one)
+        if (q.kind == MIX_RANDOM) {
+            if (pos + 2 * q.count > nwords) err = MIX_ERR_STREAM; else pos += 2 * q.count;
+        } else if (q.kind == MIX_RANDINT) {
+            if (q.rng != 0u) {                                       // (rng == 0 returns low and takes no word)
+                // the rejection loop, 64 trials at a time: the first lane of wave 0 whose word passes is where the loop stops
+                if (tid < 64) {
+                    long long p = pos;
+                    for (;;) {
+                        const bool in = p + lane < nwords;
+                        const u32 v = in ? (mt_temper(words[p + lane]) & q.mask) : 0u;
+                        const unsigned long long ok = __ballot(in && v <= q.rng);
+                        if (ok) {
+                            const int first = __ffsll((long long)ok) - 1;
+                            if (lane == first) { ints[i] = (long long)v; s_last = p + first + 1; }
+                            break;
+                        }
+                        if (p + 64 >= nwords) { if (lane == 0) s_last = -1; break; }
+                        p += 64;
+                    }
+                }
+                __syncthreads();
+                const long long np = s_last;
+                __syncthreads();
+                if (np < 0) err = MIX_ERR_STREAM; else pos = np;
+            }
+        } else if (q.count > 0) {
+            const long long n2 = q.count - (q.lead != MIX_LEAD_NONE ? 1 : 0);
+            if (n2 > 0) {
+                const long long need = (n2 + 1) >> 1;
+                const long long limit = pos < nwords ? (nwords - pos) >> 2 : 0;
+                long long before = 0;
+                for (;;) {
+                    if (chunks * MIX_CHUNK >= limit) { err = MIX_ERR_STREAM; break; }
+                    if (chunks >= q.max_chunks) { err = MIX_ERR_MARGIN; break; }
+                    if (tid == 0) table[q.tab_off + chunks] = before;
+                    double x1[MIX_ROUNDS], x2[MIX_ROUNDS], r2[MIX_ROUNDS];
+                    int rank[MIX_ROUNDS];
+                    const int total = mix_chunk_ranks(words + pos, chunks * MIX_CHUNK, limit, cnt, x1, x2, r2, rank);
+                    const bool done = before + total >= need;
+                    if (done) {
+                        const int target = (int)(need - before);
+#pragma unroll
+                        for (int j = 0; j < MIX_ROUNDS; ++j)
+                            if (rank[j] == target) { s_last = chunks * MIX_CHUNK + (long long)j * MIX_WG + tid; s_x1 = x1[j]; s_r2 = r2[j]; }
+                    }
+                    __syncthreads();
+                    ++chunks;
+                    if (done) {
+                        pos += 4 * (s_last + 1);
+                        if (n2 & 1) { px1 = s_x1; pr2 = s_r2; }
+                        break;
+                    }
+                    before += total;
+                }
+                __syncthreads();
+            }
+        }
+        if (tid == 0) {
+            MixWalk w;
+            w.start = start; w.chunks = chunks; w.x1 = 0.0; w.r2 = 0.0;
+            if (q.kind == MIX_NORMAL && q.count > 0 && q.lead == MIX_LEAD_CARRIED) { w.x1 = lx1; w.r2 = lr2; }
+            walk[i] = w;
+        }
+    }
+    if (tid == 0) {
+        info[MIX_INFO_ERR] = err;
+        info[MIX_INFO_POS] = pos;
+        info[MIX_INFO_X1] = __double_as_longlong(px1);
+        info[MIX_INFO_R2] = __double_as_longlong(pr2);
+    }
+}
+
+// One workgroup per (request, chunk): block_req[b] = the request of workgroup b, its chunk = b - blk0 of the request; workgroups
+// past the chunks the walk counted leave at once, all of them if the walk failed.  A random request's chunk is MIX_CHUNK doubles.
+// A normal request's accepted group with rank k (the walk's count before the chunk + its rank inside) yields samples 2 (k - 1)
+// (= f x2) and 2 (k - 1) + 1 (= f x1) behind the leading cached one: out = float(0.0 + scale * f x), or the double with `f64`.
+// Samples inside the guard — float32: within `margin` (relative) of a rounding boundary; float64: within `margin` (absolute) of
+// an integer — are appended to risky[] as {request, index in its results, x, r2} (info[NRISKY] counts them) for the host's libm.
+__global__ __launch_bounds__(MIX_WG) void np_mixed_fill_kernel(const u32* __restrict__ words, long long nwords, const MixReq* __restrict__ reqs,
+                                                               const int* __restrict__ block_req, const MixWalk* __restrict__ walk,
+                                                               const long long* __restrict__ table, double gauss0, int f64, double margin,
+                                                               u8* __restrict__ out, long long* __restrict__ info,
+                                                               long long* __restrict__ risky, long long risky_cap) {
+    __shared__ int cnt[65];
+    if (info[MIX_INFO_ERR]) return;
+    const int i = block_req[blockIdx.x], tid = threadIdx.x;
+    const MixReq q = reqs[i];
+    const MixWalk w = walk[i];
+    const long long c = (long long)blockIdx.x - q.blk0;
+    u8* o = out + q.out_off;
+    if (q.kind == MIX_RANDOM) {
+#pragma unroll
+        for (int j = 0; j < MIX_ROUNDS; ++j) {
+            const long long e = c * MIX_CHUNK + (long long)j * MIX_WG + tid;
+            if (e >= q.count) break;
+            const u32 a = mt_temper(words[w.start + 2 * e]) >> 5, b = mt_temper(words[w.start + 2 * e + 1]) >> 6;
+            ((double*)o)[e] = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;       // legacy_double
+        }
+        return;
+    }
+    const int lead = q.lead != MIX_LEAD_NONE ? 1 : 0;
+    const long long n2 = q.count - lead, need = (n2 + 1) >> 1;
+    auto put = [&](long long idx, double nd, double x, double r2v, bool guarded) {
+        bool risk;
+        if (f64) { ((double*)o)[idx] = nd; risk = fabs(nd - rint(nd)) < margin; }
+        else { ((float*)o)[idx] = (float)nd; risk = (float)(nd * (1.0 - margin)) != (float)(nd * (1.0 + margin)); }
+        if (risk && guarded) {
+            const long long slot = (long long)atomicAdd((unsigned long long*)&info[MIX_INFO_NRISKY], 1ull);
+            if (slot < risky_cap) {
+                risky[4 * slot] = i; risky[4 * slot + 1] = idx;
+                risky[4 * slot + 2] = __double_as_longlong(x); risky[4 * slot + 3] = __double_as_longlong(r2v);
+            }
+        }
+    };
+    if (c == 0 && tid == 0 && lead) {
+        if (q.lead == MIX_LEAD_GIVEN) put(0, 0.0 + q.scale * gauss0, 0.0, 0.0, false);           // (exact: the host's own value)
+        else put(0, 0.0 + q.scale * (sqrt(-2.0 * log(w.r2) / w.r2) * w.x1), w.x1, w.r2, true);
+    }
+    if (c >= w.chunks) return;
+    double x1[MIX_ROUNDS], x2[MIX_ROUNDS], r2[MIX_ROUNDS];
+    int rank[MIX_ROUNDS];
+    mix_chunk_ranks(words + w.start, c * MIX_CHUNK, (nwords - w.start) >> 2, cnt, x1, x2, r2, rank);
+    const long long before = table[q.tab_off + c];
+#pragma unroll
+    for (int j = 0; j < MIX_ROUNDS; ++j) {
+        const long long k = before + rank[j];
+        if (!rank[j] || k > need) continue;                          // rejected, or beyond what the request consumes
+        const double f = sqrt(-2.0 * log(r2[j]) / r2[j]);
+        const long long e = 2 * (k - 1);
+        put(lead + e, 0.0 + q.scale * (f * x2[j]), x2[j], r2[j], true);
+        if (e + 1 < n2) put(lead + e + 1, 0.0 + q.scale * (f * x1[j]), x1[j], r2[j], true);
+    }
+}
+} // namespace imgxf
+
 using namespace imgxf;
 
 IMGXF_API int imgxf_add_noise_philox_u8(const imgxf_view* src, const imgxf_view* dst, float sigma, uint64_t seed,
@@ -325,5 +546,26 @@ IMGXF_API int imgxf_np_normals_f32(const uint32_t* words, int64_t ngroups, const
     if (ngroups) hipLaunchKernelGGL(np_normals_kernel, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, words, (long long)ngroups,
                                     (const long long*)rank, (long long)groups, (long long)n2, lead, (const NpReq*)reqs, nreq, margin, out,
                                     (long long*)info, (long long*)risky, (long long)risky_cap, xr);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_np_mixed_walk(const uint32_t* words, int64_t nwords, int64_t pos, const void* reqs, int nreq, int chunk, void* walk,
+                                  int64_t* table, int64_t* ints, int64_t* info, void* stream) {
+    if (!words || !reqs || !walk || !table || !ints || !info) return IMGXF_ERR_NULL;
+    if (nwords < 0 || pos < 0 || pos > nwords || nreq < 1 || chunk != MIX_CHUNK) return IMGXF_ERR_ARG;
+    static_assert(sizeof(MixReq) == 64 && sizeof(MixWalk) == 32, "the host builds and reads these records");
+    hipLaunchKernelGGL(np_mixed_walk_kernel, dim3(1), dim3(MIX_WG), 0, (hipStream_t)stream, words, (long long)nwords, (long long)pos,
+                       (const MixReq*)reqs, nreq, (MixWalk*)walk, (long long*)table, (long long*)ints, (long long*)info);
+    return launch_status();
+}
+
+IMGXF_API int imgxf_np_mixed_fill(const uint32_t* words, int64_t nwords, const void* reqs, const int32_t* block_req, int64_t nblocks, int chunk,
+                                  const void* walk, const int64_t* table, double gauss0, int f64, double margin, void* out, int64_t* info,
+                                  int64_t* risky, int64_t risky_cap, void* stream) {
+    if (!words || !reqs || !block_req || !walk || !table || !out || !info || !risky) return IMGXF_ERR_NULL;
+    if (nwords < 0 || nblocks < 0 || nblocks > 0x7fffffff || risky_cap < 0 || chunk != MIX_CHUNK) return IMGXF_ERR_ARG;
+    if (nblocks) hipLaunchKernelGGL(np_mixed_fill_kernel, dim3((unsigned)nblocks), dim3(MIX_WG), 0, (hipStream_t)stream, words, (long long)nwords,
+                                    (const MixReq*)reqs, (const int*)block_req, (const MixWalk*)walk, (const long long*)table, gauss0, f64,
+                                    margin, (u8*)out, (long long*)info, (long long*)risky, (long long)risky_cap);
     return launch_status();
 }

@@ -241,6 +241,196 @@ def _normals_fused(raw, pos, has_gauss, gauss, requests, counts, total, n2) -> D
     return d
 
 
+
+# ---- mixed calls: normal, random and scalar randint in call order -----------------------------------------------------
+# Requests: ("normal", count, scale) = np.random.normal(0, scale, count); ("random", count) = np.random.random(count);
+# ("randint", low, high) = np.random.randint(low, high), scalar, default dtype.  The rules (numpy/random/src/legacy/
+# legacy-distributions.c, distributions.c, mt19937.c; restated):
+#   * next32() takes one tempered stream word;
+#   * random: each double is legacy_double, two words, row-major; the cached normal is left alone;
+#   * randint: rng = high - 1 - low; 0: low, no word.  Up to 32 bits: mask = the smallest 2^k - 1 >= rng, v = next32() & mask
+#     until v <= rng, one word per trial (rng = 2^32 - 1 takes exactly one), low + v.  Wider ranges take two words per trial
+#     and are refused here.  The cached normal is left alone: one cached before a randint is the first sample of the next normal;
+#   * normal: as `normals` states it — a cached value first, then groups of four words from the CURRENT position (odd after a
+#     randint), an odd number of new normals leaves f x1 cached, scale 0.0 still consumes, count 0 consumes nothing.
+MIX_CHUNK = 4096             # groups per chunk of the walk (csrc/noise_rng.hip MIX_CHUNK; the entry points refuse another value)
+RANDINT_WORDS = 64           # stream words allowed for one randint: a trial fails with probability < 1/2, so 2^-64 for all of them
+MIX_RISKY_FIRST = 1024       # risky samples that come back with the info block; more take a second copy
+_MIX_REQ = np.dtype([("kind", "<i4"), ("lead", "<i4"), ("count", "<i8"), ("scale", "<f8"), ("out_off", "<i8"), ("tab_off", "<i8"),
+                     ("max_chunks", "<i8"), ("rng", "<u4"), ("mask", "<u4"), ("blk0", "<i8")])      # struct MixReq
+_KINDS = {"normal": 0, "random": 1, "randint": 2}
+
+
+def _randint_range(low, high):
+    """(rng, mask) of a scalar randint, or None for what the device does not take: a range above 32 bits, or arguments
+    np.random.randint itself refuses (the host call then raises what it raises)."""
+    low, high = int(low), int(high)
+    rng = high - 1 - low
+    if rng < 0 or rng > 0xFFFFFFFF or low < -2 ** 63 or high > 2 ** 63:
+        return None
+    return rng, (1 << rng.bit_length()) - 1
+
+
+def _check_requests(requests):
+    """The requests with plain Python numbers, or None if one of them is outside what `mixed` takes."""
+    out = []
+    for r in requests:
+        kind = r[0]
+        if kind == "normal":
+            out.append((kind, int(r[1]), float(r[2])))
+        elif kind == "random":
+            out.append((kind, int(r[1])))
+        elif kind == "randint":
+            if _randint_range(r[1], r[2]) is None:
+                return None
+            out.append((kind, int(r[1]), int(r[2])))
+        else:
+            raise ValueError(f"unknown request kind {kind!r}")
+        if kind != "randint" and out[-1][1] < 0:
+            return None
+    return out
+
+
+def mixed_words(requests) -> int:
+    """Stream words that certainly hold the requests: words_needed per normal, two per uniform, RANDINT_WORDS per randint."""
+    total = 0
+    for r in requests:
+        total += words_needed(r[1]) if r[0] == "normal" and r[1] else 2 * r[1] if r[0] == "random" else RANDINT_WORDS if r[0] == "randint" else 0
+    return total
+
+
+def mixed(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, requests: Sequence[tuple], f64: bool = False) -> Draw:
+    """`normals` for a list of mixed calls (see above) in call order: `raw`, `start`, `has_gauss`, `gauss` as there.
+    Draw.noise holds, request by request: the float32 (`f64`: float64) tensor of a normal, the float64 tensor of a random,
+    the Python int of a randint; position / has_gauss / gauss: the generator after the last call; patched: samples
+    recomputed with the host's libm.  Raises ValueError if `raw` is too short (a normal's margin, a randint that runs to its
+    end) or a randint range exceeds 32 bits.
+    An int32 stream on the device takes ONE pass (imgxf_np_mixed_walk + imgxf_np_mixed_fill, one copy back, no
+    synchronisation per request); any other tensor is walked request by request with `normals`."""
+    reqs = _check_requests(requests)
+    if reqs is None:
+        raise ValueError("a randint range above 32 bits (or a negative count)")
+    if raw.is_cuda and raw.dtype == torch.int32 and reqs:
+        return _mixed_device(raw, int(start), bool(has_gauss), float(gauss), reqs, f64)
+    dev = raw.device
+    pos, has_gauss, gauss = int(start), bool(has_gauss), float(gauss)
+    d = Draw()
+    d.noise, d.patched = [], 0
+    for r in reqs:
+        if r[0] == "normal":
+            one = normals(raw, pos, has_gauss, gauss, [(r[1], r[2])], f64)
+            d.noise.append(one.noise[0])
+            pos, has_gauss, gauss = one.position, one.has_gauss, one.gauss
+            d.patched += one.patched
+        elif r[0] == "random":
+            n = r[1]
+            if pos + 2 * n > raw.numel():
+                raise ValueError("the MT19937 stream is shorter than the draw")
+            t = temper(raw[pos:pos + 2 * n].to(torch.int64) & 0xFFFFFFFF).view(-1, 2)
+            d.noise.append(((t[:, 0] >> 5).double() * 67108864.0 + (t[:, 1] >> 6).double()) / _TWO53)
+            pos += 2 * n
+        else:
+            low = r[1]
+            rng, mask = _randint_range(r[1], r[2])
+            v = 0
+            while rng:
+                if pos >= raw.numel():
+                    raise ValueError("the MT19937 stream ended inside a randint")
+                v = int(temper(raw[pos:pos + 1].to(torch.int64) & 0xFFFFFFFF).item()) & mask
+                pos += 1
+                if v <= rng:
+                    break
+            d.noise.append(low + v)
+    d.position, d.has_gauss, d.gauss = pos, has_gauss, gauss if has_gauss else 0.0
+    return d
+
+
+def _mixed_tables(reqs, has_gauss: bool, esz: int):
+    """What the host can know of a request list without the stream: the MixReq records — whether a cached normal leads a
+    normal request (the parity of the counts decides) and whose it is, where each result goes, how many chunks the request's
+    margin allows, its first fill workgroup — and (output bytes, chunk-table entries, fill workgroups, whether a normal stays
+    cached behind the list, whether that is still the one the call started with)."""
+    rows = []                                                # (kind, lead, count, scale, out_off, tab_off, max_chunks, rng, mask, blk0)
+    out_bytes = table_len = nblocks = 0
+    cached, given = has_gauss, has_gauss
+    for r in reqs:
+        kind, lead, count, scale, chunks, rng, mask = _KINDS[r[0]], 0, 0, 0.0, 0, 0, 0
+        at = (out_bytes, table_len, nblocks)
+        if r[0] == "normal":
+            count, scale = r[1], r[2]
+            if count:
+                lead = (1 if given else 2) if cached else 0
+                n2 = count - (1 if cached else 0)
+                chunks = -(-(words_needed(n2) // 4) // MIX_CHUNK) if n2 else 0
+                table_len += chunks
+                nblocks += max(1, chunks)                    # (a request that is only its cached normal still has it written)
+                out_bytes += (count * esz + 7) & ~7
+                cached, given = bool(n2 & 1), False
+        elif r[0] == "random":
+            count = r[1]
+            nblocks += -(-count // MIX_CHUNK)
+            out_bytes += 8 * count
+        else:
+            rng, mask = _randint_range(r[1], r[2])
+        rows.append((kind, lead, count, scale, at[0], at[1], chunks, rng, mask, at[2]))
+    tab = np.array(rows, _MIX_REQ) if rows else np.zeros(0, _MIX_REQ)
+    return tab, out_bytes, table_len, nblocks, cached, given
+
+
+def _mixed_device(raw, pos, has_gauss, gauss, reqs, f64) -> Draw:
+    """`mixed` on the device: the host's tables up, two launches, one copy back."""
+    from . import _ffi as F
+    dev = raw.device
+    nreq = len(reqs)
+    esz, odt = (8, torch.float64) if f64 else (4, torch.float32)
+    tab, out_bytes, table_len, nblocks, cached, given = _mixed_tables(reqs, has_gauss, esz)
+    blocks = np.diff(np.append(tab["blk0"], nblocks))
+    block_req = np.repeat(np.arange(nreq, dtype=np.int32), blocks)
+    host = np.concatenate((tab.view(np.uint8), block_req.view(np.uint8)))
+    nfirst = 8 + nreq + 4 * MIX_RISKY_FIRST
+    with torch.cuda.device(dev):
+        cs = torch.cuda.current_stream(dev).cuda_stream
+        up = torch.from_numpy(host).to(dev)
+        out = torch.empty((max(8, out_bytes),), dtype=torch.uint8, device=dev)
+        walk = torch.empty((4 * nreq,), dtype=torch.int64, device=dev)
+        table = torch.empty((max(1, table_len),), dtype=torch.int64, device=dev)
+        back = torch.empty((8 + nreq + 4 * RISKY_CAP,), dtype=torch.int64, device=dev)     # info[8], ints[nreq], risky[RISKY_CAP][4]
+        back[:8 + nreq].zero_()
+        info, ints, risky = back.data_ptr(), back.data_ptr() + 64, back.data_ptr() + 8 * (8 + nreq)
+        F.call("imgxf_np_mixed_walk", raw.data_ptr(), raw.numel(), pos, up.data_ptr(), nreq, MIX_CHUNK, walk.data_ptr(), table.data_ptr(),
+               ints, info, cs)
+        F.call("imgxf_np_mixed_fill", raw.data_ptr(), raw.numel(), up.data_ptr(), up.data_ptr() + tab.nbytes, nblocks, MIX_CHUNK,
+               walk.data_ptr(), table.data_ptr(), gauss, int(f64), 1e-9 if f64 else MARGIN, out.data_ptr(), info, risky, RISKY_CAP, cs)
+        got = back[:nfirst].cpu().numpy()                        # the one copy back (and the one synchronisation)
+        err, end, x1b, r2b, nrisky = (int(v) for v in got[:5])
+        if err:
+            raise ValueError("the MT19937 stream ended inside the draw" if err == 1 else "too few accepted groups inside the margin")
+        if nrisky > RISKY_CAP:
+            raise ValueError("more samples near a rounding boundary than the list holds")
+        entries = got[8 + nreq:8 + nreq + 4 * min(nrisky, MIX_RISKY_FIRST)]
+        if nrisky > MIX_RISKY_FIRST:
+            entries = back[8 + nreq:8 + nreq + 4 * nrisky].cpu().numpy()
+        if nrisky:
+            entries = entries.reshape(-1, 4)
+            xr = entries[:, 2:].copy().view(np.float64)
+            vals = [0.0 + float(tab["scale"][k]) * _host_gauss(float(x), float(r)) for k, (x, r) in zip(entries[:, 0], xr)]
+            at = torch.from_numpy(tab["out_off"][entries[:, 0]] // esz + entries[:, 1]).to(dev)
+            out.view(odt)[at] = torch.tensor(vals, dtype=torch.float64).to(odt).to(dev)
+    d = Draw()
+    d.noise = []
+    for i, r in enumerate(reqs):
+        off = int(tab["out_off"][i])
+        if r[0] == "normal":
+            d.noise.append(out[off:off + r[1] * esz].view(odt))
+        elif r[0] == "random":
+            d.noise.append(out[off:off + 8 * r[1]].view(torch.float64))
+        else:
+            d.noise.append(r[1] + int(got[8 + i]))
+    d.position, d.has_gauss, d.patched = end, cached, nrisky
+    d.gauss = (gauss if given else _host_gauss(*np.array([x1b, r2b], np.int64).view(np.float64).tolist())) if cached else 0.0
+    return d
+
+
 def state_at(raw: torch.Tensor, position: int, start: int):
     """(key[624] as a uint32 NumPy array, pos) of the generator after consuming the stream up to `position` — in NumPy's own
     representation: the block is only regenerated by the NEXT request, so a position on a block boundary is `pos = 624`
@@ -360,6 +550,72 @@ def _draw_pass(requests: Sequence[tuple], device, f64: bool = False) -> List[tor
             k, p = state_at(raw, d.position, int(pos))
             np.random.set_state((kind, k, p, int(d.has_gauss), float(d.gauss) if d.has_gauss else 0.0))
     return d.noise
+
+
+def host_mixed(requests: Sequence[tuple], f64: bool = False) -> list:
+    """The calls themselves, on the host: NumPy arrays (normals cast to float32 unless `f64`) and Python ints."""
+    out = []
+    for r in requests:
+        if r[0] == "normal":
+            z = np.random.normal(0, r[2], r[1])
+            out.append(z if f64 else z.astype(np.float32))
+        elif r[0] == "random":
+            out.append(np.random.random(r[1]))
+        else:
+            out.append(int(np.random.randint(r[1], r[2])))
+    return out
+
+
+def draw_mixed(requests: Sequence[tuple], device, f64: bool = False, stats: dict | None = None) -> list | None:
+    """The results of a list of mixed np.random calls (see `mixed`) — device tensors for normal and random requests, Python
+    ints for randint — with np.random's global state advanced exactly as the calls would have advanced it; None, with the
+    state untouched and nothing drawn, if the global generator is not the legacy MT19937, a randint range exceeds 32 bits
+    (or np.random itself would refuse a request), or the stream generated for the requests' margins turned out too short:
+    the caller then makes the calls on the host.  Lists of more than PASS_NORMALS samples take several passes.
+    `stats`, when given, receives "patched": the samples the host's libm recomputed (Draw.patched, summed over the passes)."""
+    reqs = _check_requests(requests)
+    if reqs is None:
+        return None
+    device = torch.device(device)
+    out: list = []
+    i = patched = 0
+    while i < len(reqs):
+        j, tot = i, 0
+        while j < len(reqs) and (j == i or tot + (reqs[j][1] if reqs[j][0] != "randint" else 0) <= PASS_NORMALS):
+            tot += reqs[j][1] if reqs[j][0] != "randint" else 0
+            j += 1
+        d = _mixed_pass(reqs[i:j], device, f64)
+        if d is None:
+            if i == 0:
+                return None
+            got = [torch.from_numpy(v).to(device) if isinstance(v, np.ndarray) else v for v in host_mixed(reqs[i:j], f64)]
+        else:
+            got, patched = d.noise, patched + d.patched
+        out.extend(got)
+        i = j
+    if stats is not None:
+        stats["patched"] = patched
+    return out
+
+
+def _mixed_pass(reqs: list, device: torch.device, f64: bool) -> Draw | None:
+    """One pass: the Draw of `mixed` with np.random's state set behind it, or None (state untouched)."""
+    st = np.random.get_state(legacy=False)
+    if st["bit_generator"] != "MT19937":
+        return None
+    kind, key, pos, has_gauss, gauss = "MT19937", st["state"]["key"], int(st["state"]["pos"]), st["has_gauss"], st["gauss"]
+    nblocks = (int(pos) + mixed_words(reqs)) // 624 + 2
+    with torch.cuda.device(device):
+        key_d = torch.from_numpy(key.astype(np.uint32).view(np.int32).copy()).to(device)
+        raw = generate_stream(key_d, nblocks, device, torch.cuda.current_stream(device).cuda_stream)
+        try:
+            d = mixed(raw, int(pos), bool(has_gauss), float(gauss), reqs, f64)
+        except ValueError:
+            return None
+        if d.position != int(pos) or bool(has_gauss) != d.has_gauss:
+            k, p = state_at(raw, d.position, int(pos)) if d.position != int(pos) else (key, pos)    # (only the cached normal went)
+            np.random.set_state((kind, k, p, int(d.has_gauss), float(d.gauss) if d.has_gauss else 0.0))
+    return d
 
 
 class PendingDraw:

@@ -49,10 +49,11 @@ class TransformationPool:
             severity = random.choice([1, 2, 3, 4, 5])
         img_array = np.array(image)
         noise_prob = [0.03, 0.06, 0.09, 0.17, 0.27][severity - 1]
-        mask = np.random.random(img_array.shape[:2])
+        h, w = img_array.shape[:2]
+        got = T._numpy_mixed([("random", h * w)])               # np.random.random's own doubles, computed on the device
         dev = _device()
-        out = ops.impulse_noise(torch.from_numpy(img_array).to(dev), torch.from_numpy(mask).to(dev),
-                                noise_prob / 2, 1 - noise_prob / 2)
+        mask = got[0].view(h, w) if got is not None else torch.from_numpy(np.random.random((h, w))).to(dev)
+        out = ops.impulse_noise(torch.from_numpy(img_array).to(dev), mask, noise_prob / 2, 1 - noise_prob / 2)
         return _download(out)
 
     def shot_noise(image, severity=None):
@@ -229,7 +230,7 @@ class ChainPlan:
     members / args: per image, the member names and their arguments as the loop hands them over (drawn or explicit);
     index [n, steps] uint8: operation-table entry of each step (0xFF past a chain's end); factors [n, steps] float32:
     the C float of an ENHANCE_* step's factor; table: entries (code, arg, m[10]); data: (image, step) -> the step's
-    float64 normals [h,w,3] (a numpy array, or a device tensor from numpy_stream), mask [h,w] or Poisson counts
+    float64 normals [h,w,3] or mask [h,w] (a numpy array, or a device tensor from numpy_stream) or Poisson counts
     [h,w,3]; late: the first image holding shot_noise (n if none) — its np.random draws and all after it wait for
     `chain_plan_finish`; split [n]: the step each image's second launch starts at (its chain length if none)."""
     n: int
@@ -335,8 +336,21 @@ def chain_plan(n: int, h: int, w: int, chains, device=None) -> ChainPlan:
     for i in range(late, n):
         split[i] = next((s for s, name in enumerate(members[i]) if name in _NP_DRAWING), len(members[i]))
     plan = ChainPlan(n, h, w, members, args, index, factors, table, {}, late, split)
-    for i in range(late):                                    # `np.random` draws that do not wait for pixels
-        for s in range(len(members[i])):
+    requests, slots = [], []                                 # `np.random` draws that do not wait for pixels, in loop order
+    for i in range(late):
+        for s, (name, arg) in enumerate(zip(members[i], args[i])):
+            if name == "gaussian_noise":
+                requests.append(("normal", h * w * 3, _SEVERITY_TABLES[name][arg - 1] * 255))
+                slots.append((i, s, (h, w, 3)))
+            elif name == "impulse_noise":
+                requests.append(("random", h * w))
+                slots.append((i, s, (h, w)))
+    got = T._numpy_mixed(requests, device, f64=True)         # one pass over the stream for the whole batch (the gate is on its total)
+    if got is not None:
+        for z, (i, s, shape) in zip(got, slots):
+            plan.data[i, s] = z.view(shape)
+    else:
+        for i, s, _ in slots:
             _draw_np(plan, i, s, None, device)
     plan.finished = late == n
     return plan
@@ -410,7 +424,7 @@ def _stage(plan: ChainPlan, device, lo, hi):
         buf[rec_bytes + off:rec_bytes + off + a.nbytes] = a.reshape(-1).view(np.uint8)
     gpu = torch.empty(rec_bytes + payload_bytes, dtype=torch.uint8, device=device)
     gpu[:staged.numel()].copy_(staged, non_blocking=True)   # one host-to-device copy per launch
-    for off, t in dev:                                       # numpy_stream's normals are already on the device
+    for off, t in dev:                                       # numpy_stream's normals and masks are already on the device
         gpu[rec_bytes + off:rec_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
     ws_bytes = chain_workspace_bytes(n, h, w)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None

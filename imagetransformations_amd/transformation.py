@@ -218,6 +218,22 @@ def _numpy_noise(requests, dev=None, f64=False, deferred=False):
     return finish if deferred else finish()
 
 
+def _numpy_mixed(requests, dev=None, f64=False):
+    """`_numpy_noise` for np.random calls of several kinds in call order — ("normal", count, scale), ("random", count),
+    ("randint", low, high); numpy_stream.draw_mixed — : device tensors for the normals (float32 unless `f64`) and the
+    uniforms, Python ints for the randints, np.random's state advanced as the calls would have; None (state untouched,
+    nothing on the device) when the host has to make the calls: mode "numpy-host", an empty list, fewer than
+    NOISE_DEVICE_MIN samples (normals + uniforms) in the whole list, no ROCm device, or draw_mixed refuses."""
+    if NOISE_RNG == "numpy-host" or not requests:
+        return None
+    if sum(r[1] for r in requests if r[0] != "randint") < NOISE_DEVICE_MIN:
+        return None
+    if not torch.cuda.is_available():
+        return None
+    from . import numpy_stream
+    return numpy_stream.draw_mixed(requests, _device() if dev is None else dev, f64)
+
+
 # ------------------------------------------------------------------ translation (:284-307)
 def _translation_t(t: torch.Tensor, tx: float, ty: float) -> torch.Tensor:
     """:284-307: black canvas, crop of what stays visible, paste at max(0, int(t)) — i.e. every pixel moves by

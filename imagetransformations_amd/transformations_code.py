@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from . import batched, ops, staging
+from . import batched, numpy_stream, ops, staging
 from . import transformation as T
 from .transformation import (_download, _upload, apply_blur, apply_brightness, apply_contrast,  # noqa: F401
                              apply_gaussian_noise, apply_rotation, apply_scale, apply_shear,
@@ -147,8 +147,11 @@ def apply_all_transformations_batched(images):
     drew the same (type, value) go through one batched launch (perspective warps and crops of one
     size share a launch with per-frame coefficients / windows).  images: [(PIL image, name)]."""
     dev = T._device()
-    # ---- draws, image by image, in the order the per-image loop makes them
+    # ---- draws, image by image, in the order the per-image loop makes them.  The np.random calls (the noise's normals, the
+    # crop's two randints) are only listed here, in that order: nothing else uses np.random, so one pass over its stream on
+    # the device serves them all afterwards (T._numpy_mixed), or the host makes them one by one
     plans, extra = [], {}
+    np_requests, np_slots = [], []                      # request -> where its result goes: (key of extra, None | 0 | 1, shape)
     for i, (img, name) in enumerate(images):
         w, h = img.size
         plan = []
@@ -157,7 +160,9 @@ def apply_all_transformations_batched(images):
                 plan.append((transform_type, (), f"{name}_{transform_type}_corrupted.jpg"))
             elif transform_type == 'rand_crop':
                 cs = int(0.78 * w)
-                extra[(i, len(plan))] = (np.random.randint(0, w - cs + 1), np.random.randint(0, h - cs + 1), cs)
+                extra[(i, len(plan))] = [None, None, cs]
+                np_requests += [("randint", 0, w - cs + 1), ("randint", 0, h - cs + 1)]
+                np_slots += [((i, len(plan)), 0, None), ((i, len(plan)), 1, None)]
                 plan.append((transform_type, (), f"{name}_{transform_type}_corrupted.jpg"))
             else:
                 possible_values = T.grid_values(params)
@@ -167,14 +172,25 @@ def apply_all_transformations_batched(images):
                     continue
                 value = random.choice(possible_values)
                 if transform_type == 'gaussian_noise':
-                    # (on the host, image by image: rand_crop's randint calls come between one image's normals and the
-                    # next one's on the same np.random stream, so they cannot be pooled into one device draw)
                     shape = np.array(img).shape
-                    extra[(i, len(plan))] = np.random.normal(0, value * 255, shape).astype(np.float32)
+                    np_requests.append(("normal", int(np.prod(shape)), value * 255))
+                    np_slots.append(((i, len(plan)), None, shape))
                 elif transform_type == 'perspective_warp':
                     extra[(i, len(plan))] = draw_perspective_coeffs(w, h, value)
                 plan.append((transform_type, (value,), f"{name}_{transform_type}_{value}_corrupted.jpg"))
         plans.append(plan)
+    drawn = T._numpy_mixed(np_requests, dev)
+    if drawn is None:
+        drawn = numpy_stream.host_mixed(np_requests)
+    for v, (key, slot, shape) in zip(drawn, np_slots):
+        if slot is None:
+            extra[key] = v.reshape(shape)               # float32 noise: a device tensor, or the host's array
+        else:
+            extra[key][slot] = v
+
+    def noise_on_device(i, k):
+        z = extra[(i, k)]
+        return z if isinstance(z, torch.Tensor) else torch.from_numpy(z).to(dev)
 
     def crop(t, i, k):
         x, y, cs = (int(v) for v in extra[(i, k)])
@@ -184,7 +200,7 @@ def apply_all_transformations_batched(images):
         img, out = images[i][0], []
         for k, (transform_type, args, _) in enumerate(plans[i]):
             if transform_type == 'gaussian_noise':
-                out.append(_download(ops.add_noise(_upload(img), torch.from_numpy(extra[(i, k)]).to(dev))))
+                out.append(_download(ops.add_noise(_upload(img), noise_on_device(i, k))))
             elif transform_type == 'perspective_warp':
                 out.append(_download(ops.perspective(_upload(img), extra[(i, k)])))
             elif transform_type == 'rand_crop':
@@ -197,7 +213,8 @@ def apply_all_transformations_batched(images):
         if transform_type == 'blur':
             return T._blur_group(batch, args[0])
         if transform_type == 'gaussian_noise':
-            return ops.add_noise(batch, staging.upload([extra[(i, k)] for _, i, k in entries], dev))
+            zs = [extra[(i, k)] for _, i, k in entries]
+            return ops.add_noise(batch, torch.stack(zs) if isinstance(zs[0], torch.Tensor) else staging.upload(zs, dev))
         if transform_type == 'perspective_warp':
             return ops.perspective(batch, [extra[(i, k)] for _, i, k in entries])
         if transform_type == 'rand_crop':               # crops differ per image but share their size: gather them, then one resize launch

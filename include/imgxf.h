@@ -590,6 +590,29 @@ int imgxf_np_normals_f32(const uint32_t* words, int64_t ngroups, const int64_t* 
                          const void* reqs, int nreq, double margin, float* out, int64_t* info, int64_t* risky, int64_t risky_cap,
                          double* xr, void* stream);
 
+/* A list of MIXED legacy calls in call order over the same word stream — np.random.normal(0, scale, count), np.random.random(count)
+ * and scalar np.random.randint(low, high) — in two launches (imagetransformations_amd/numpy_stream.py `mixed` states the rules and
+ * builds the tables).  words: the raw stream, nwords of it; pos: the generator's position.  reqs: nreq records of 64 bytes
+ * {int32 kind (0 normal, 1 random, 2 randint), int32 lead (normal: 0, or the first sample is the cached normal — 1: the one the call
+ * starts with, value gauss0; 2: one an earlier request left), int64 count, double scale, int64 out_off (bytes into out), int64 tab_off,
+ * int64 max_chunks, uint32 rng, uint32 mask, int64 blk0}.  chunk: the groups per chunk the tables were built for (4096; anything else
+ * is IMGXF_ERR_ARG).
+ * imgxf_np_mixed_walk, ONE workgroup, serial over the requests and parallel inside each: writes walk[i] = {int64 start position, int64
+ * chunks used, double x1, r2 of a lead of kind 2}, table[tab_off + c] = accepted groups of the request before its chunk c, ints[i] =
+ * v <= rng of a randint (the host adds low), info[0] = error (1: the stream ended, 2: a request needed more than max_chunks; the walk
+ * stops there and never reads past nwords), info[1] = final position, info[2 .. 3] = bits of (x1, r2) of the cached normal the list
+ * leaves.  info holds 8 words, zeroed by the caller.
+ * imgxf_np_mixed_fill, one workgroup per (request, chunk) — block_req[b] = request of workgroup b, nblocks of them, blk0 = the
+ * request's first: writes the doubles of random requests and float(0.0 + scale * f x) (f64: the double) of normal requests into out.
+ * Samples within `margin` of a float32 rounding boundary (relative; f64: of an integer, absolute) are appended to risky[] as {request,
+ * index in its results, bits of x, bits of r2} (risky_cap entries of 4 words; info[4] counts all of them) for the host's libm.
+ * Nothing is written if the walk reported an error. */
+int imgxf_np_mixed_walk(const uint32_t* words, int64_t nwords, int64_t pos, const void* reqs, int nreq, int chunk, void* walk,
+                        int64_t* table, int64_t* ints, int64_t* info, void* stream);
+int imgxf_np_mixed_fill(const uint32_t* words, int64_t nwords, const void* reqs, const int32_t* block_req, int64_t nblocks, int chunk,
+                        const void* walk, const int64_t* table, double gauss0, int f64, double margin, void* out, int64_t* info,
+                        int64_t* risky, int64_t risky_cap, void* stream);
+
 /* Why a file is outside the reader's class, or damaged (status[] of imgxf_jpeg_layout_host; 0 = accepted). */
 enum { IMGXF_JPEG_E_NOT_JPEG = 1,    /* no SOI */
        IMGXF_JPEG_E_MARKERS = 2,     /* damaged marker structure (also: SOS before SOF) */

@@ -1,0 +1,210 @@
+"""GPU: numpy_stream.draw_mixed (csrc/noise_rng.hip imgxf_np_mixed_walk + imgxf_np_mixed_fill) — interleaved np.random normal /
+random / scalar randint calls computed on the device — against np.random itself, and the three callers it serves: the
+twelve-type batched driver, TransformationPool.impulse_noise and pool.apply_chain_batch."""
+import random
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+from conftest import synth
+from imagetransformations_amd import numpy_stream as NS, ops, pool as P, transformation as T, transformations_code as TC
+from test_numpy_stream_mixed import LISTS, enter, raw_stream, same_state
+
+pytestmark = pytest.mark.gpu
+
+PATCH_CAP = 10000            # at most one sample in this many may come from the host's libm (the stated rate is 1 in 2^21)
+
+
+def samples(requests) -> int:
+    return sum(r[1] for r in requests if r[0] != "randint")
+
+
+def check_draw(requests, device, f64=False):
+    """draw_mixed from np.random's current state against the host calls from the same state: values, generator state, the
+    draw that follows, and the cap on host-patched samples.  Returns (device results, host results)."""
+    st = np.random.get_state()
+    want = NS.host_mixed(requests, f64)
+    after = np.random.get_state()
+    np.random.set_state(st)
+    stats = {}
+    got = NS.draw_mixed(requests, device, f64, stats)
+    assert got is not None and len(got) == len(requests)
+    assert stats["patched"] * PATCH_CAP <= samples(requests), stats
+    for r, g, w in zip(requests, got, want):
+        if r[0] == "randint":
+            assert isinstance(g, int) and g == w, r
+        elif r[0] == "random":
+            assert g.dtype == torch.float64 and np.array_equal(g.cpu().numpy().view(np.int64), w.view(np.int64)), r
+        elif not f64:
+            assert g.dtype == torch.float32 and np.array_equal(g.cpu().numpy(), w), r
+        else:
+            assert g.dtype == torch.float64 and g.numel() == w.size, r
+            assert np.all(np.abs(g.cpu().numpy() - w) <= NS.MARGIN * np.abs(w)), r
+    assert same_state(np.random.get_state(), after)
+    follow = (np.random.normal(0, 1, 5), np.random.randint(0, 1000), np.random.random(3))
+    np.random.set_state(after)
+    assert np.array_equal(follow[0], np.random.normal(0, 1, 5)) and follow[1] == np.random.randint(0, 1000)
+    assert np.array_equal(follow[2], np.random.random(3))
+    return got, want
+
+
+@pytest.mark.parametrize("cached", [False, True])
+@pytest.mark.parametrize("pos", [620, 621, 622, 623, 624, 17])
+@pytest.mark.parametrize("name", list(LISTS))
+def test_draw_mixed_is_np_random(device, name, pos, cached):
+    enter(11 + pos, pos, cached)
+    check_draw(LISTS[name], device)
+
+
+# np.random.seed(1), no cached normal: the last group these counts need, counted from the request's start
+EDGES = {"last_of_a_chunk": (6469, lambda g, c: g % c == c - 1 and g // c == 0),
+         "first_of_the_next_chunk": (6472, lambda g, c: g % c == 0 and g // c == 1),
+         "three_chunks": (13039, lambda g, c: g // c == 2)}
+
+
+@pytest.mark.parametrize("edge", list(EDGES))
+def test_chunk_edges_of_the_walk(device, edge):
+    """A normal request that ends on the last group of a walk chunk, on the first group of the next one, and one that spans
+    three chunks — each followed by a second normal request, whose numbers show a wrong base."""
+    n, holds = EDGES[edge]
+    np.random.seed(1)
+    _, key, pos, has_gauss, gauss = np.random.get_state()
+    d = NS.mixed(raw_stream(key, 90), pos, bool(has_gauss), gauss, [("normal", n, 1.0)])
+    last = (d.position - pos) // 4 - 1
+    assert holds(last, NS.MIX_CHUNK), (last, NS.MIX_CHUNK)          # (a change of the chunk length needs new counts)
+    check_draw([("normal", n, 1.0), ("normal", 1001, 2.0), ("randint", 0, 10)], device)
+
+
+def test_driver_shape(device):
+    """Five images' worth of the twelve-type driver's calls: an odd number of normals, so the cached one crosses the two
+    randints that follow."""
+    np.random.seed(21)
+    np.random.random(100)
+    check_draw([r for i in range(5) for r in (("normal", 61 * 83 * 3, 2.55 * (i + 1)), ("randint", 0, 19), ("randint", 0, 15))], device)
+
+
+def test_doubles(device):
+    """f64: the doubles are within MARGIN (relative) of np.random.normal's, and the pixels ops.add_noise_f64 makes of them are
+    the pixels of the host's doubles."""
+    np.random.seed(8)
+    h, w = 64, 83
+    requests = [("normal", h * w * 3, 0.18 * 255), ("random", h * w), ("randint", 0, 5), ("normal", h * w * 3 + 1, 0.38 * 255),
+                ("normal", h * w * 3, 0.08 * 255)]
+    got, want = check_draw(requests, device, f64=True)
+    img = torch.from_numpy(synth(4, h, w)).to(device)
+    for k in (0, 4):
+        a = ops.add_noise_f64(img, got[k].view(h, w, 3))
+        b = ops.add_noise_f64(img, torch.from_numpy(want[k]).to(device).view(h, w, 3))
+        assert torch.equal(a, b)
+
+
+def test_short_stream_is_refused(device, monkeypatch):
+    """With no allowance for the randints and no margin for the normals the generated stream ends inside the draw: the walk
+    stops at its bounds check, draw_mixed returns None, np.random is untouched and the host makes the calls."""
+    monkeypatch.setattr(NS, "RANDINT_WORDS", 0)
+    monkeypatch.setattr(NS, "words_needed", lambda n: 4 * ((n + 1) // 2))
+    for requests in ([("randint", 0, 3)] * 3000, [("normal", 20000, 1.0), ("random", 10)]):
+        np.random.seed(13)
+        before = np.random.get_state()
+        assert NS.draw_mixed(requests, device) is None
+        assert same_state(np.random.get_state(), before) and np.random.get_state()[4] == before[4]
+        got = NS.host_mixed(requests)
+        np.random.seed(13)
+        for g, w in zip(got, NS.host_mixed(requests)):
+            assert np.array_equal(g, w)
+
+
+def _raise(*a, **k):
+    raise AssertionError("the host drew from np.random")
+
+
+def test_twelve_type_driver_draws_on_the_device(device, monkeypatch):
+    """apply_all_transformations_batched in the default mode — its normals and rand_crop's randints taken from one mixed
+    draw on the device, np.random.normal and np.random.randint forbidden — against the host mode: images, names, and the
+    final np.random / random / torch states.  The images are 61 and 64 wide and 83 high: rand_crop's square of 0.78 times
+    the width has to fit the height (np.random.randint itself refuses the other orientation, on the host as here)."""
+    imgs = [(Image.fromarray(synth(700 + i, 83, 61 + 3 * (i % 2))), f"img_{i}") for i in range(5)]
+    assert all(im.size[1] >= int(0.78 * im.size[0]) for im, _ in imgs)
+    saved = []
+    monkeypatch.setattr(TC, "output_dir", "out")
+    monkeypatch.setattr(Image.Image, "save", lambda self, path, *a, **k: saved.append(path))
+    res = []
+    for mode in ("numpy", "numpy-host"):
+        monkeypatch.setattr(T, "NOISE_RNG", mode)
+        random.seed(4); np.random.seed(4); torch.manual_seed(4)
+        with monkeypatch.context() as m:
+            if mode == "numpy":
+                m.setattr(np.random, "normal", _raise)
+                m.setattr(np.random, "randint", _raise)
+            out = TC.apply_all_transformations_batched(imgs)
+        res.append(([np.asarray(im) for im in out], list(saved), np.random.get_state(), random.getstate(), torch.get_rng_state()))
+        saved.clear()
+    assert len(res[0][0]) == 12 * len(imgs) and len(res[0][1]) == 12 * len(imgs)
+    for a, b in zip(res[0][0], res[1][0]):
+        assert np.array_equal(a, b)
+    assert res[0][1] == res[1][1]
+    assert same_state(res[0][2], res[1][2]) and res[0][3] == res[1][3] and torch.equal(res[0][4], res[1][4])
+
+
+def test_pool_impulse_noise_mask_on_the_device(device, monkeypatch):
+    img = Image.fromarray(synth(31, 260, 260))
+    res = []
+    for mode in ("numpy", "numpy-host"):
+        monkeypatch.setattr(T, "NOISE_RNG", mode)
+        np.random.seed(19)
+        np.random.normal(0, 1, 3)                         # a cached normal, which the uniforms leave alone
+        with monkeypatch.context() as m:
+            if mode == "numpy":
+                m.setattr(np.random, "random", _raise)
+            a = np.asarray(P.TransformationPool.impulse_noise(img, 3))
+            b = np.asarray(P.TransformationPool.impulse_noise(img, 5))
+        res.append((a, b, np.random.get_state()))
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
+    assert (res[0][0] != np.asarray(img)).any()
+    assert same_state(res[0][2], res[1][2]) and res[0][2][3] == 1
+
+
+def _loop(frames, chains):
+    out = []
+    for a, chain in zip(frames.cpu().numpy(), chains):
+        img = Image.fromarray(a)
+        for item in chain:
+            name, arg = (item, None) if isinstance(item, str) else item
+            fn = getattr(P.TransformationPool, name)
+            img = fn(img) if arg is None else fn(img, arg)
+        out.append(np.asarray(img))
+    return np.stack(out)
+
+
+NOISE_CHAIN = ["gaussian_noise", "impulse_noise", "enhance_contrast"]
+MIXED_CHAINS = [[NOISE_CHAIN, ["impulse_noise", ("gaussian_noise", 2)], ["gaussian_noise"], [], ["enhance_contrast", "impulse_noise", "impulse_noise"],
+                 [("gaussian_noise", 5), "gaussian_noise", "defocus_blur"]][i % 6] for i in range(24)]
+WITH_SHOT = [c if i != 21 else ["defocus_blur", "shot_noise", "gaussian_noise"] for i, c in enumerate(MIXED_CHAINS)]
+
+
+@pytest.mark.parametrize("chains", [[NOISE_CHAIN] * 24, MIXED_CHAINS, WITH_SHOT], ids=["one_chain", "per_image", "with_shot_noise"])
+def test_chain_batch_draws_the_batch_in_one_pass(device, monkeypatch, chains):
+    """24 frames of 33 x 37 — 75 k samples and more in all, past the gate that no single frame passes: apply_chain_batch
+    equals the per-image loop and its own run with the host drawing, pixels and generator states."""
+    frames = torch.from_numpy(np.stack([synth(40 + i, 33, 37) for i in range(24)])).to(device)
+    names = [[it if isinstance(it, str) else it[0] for it in c] for c in chains]
+    late = next((i for i, c in enumerate(names) if "shot_noise" in c), len(chains))        # the plan's first draw covers the images before
+    requests = [("normal", 33 * 37 * 3, 1.0) if name == "gaussian_noise" else ("random", 33 * 37) for c in names[:late]
+                for name in c if name in ("gaussian_noise", "impulse_noise")]
+    assert samples(requests) >= T.NOISE_DEVICE_MIN > 33 * 37 * 4
+    random.seed(6); np.random.seed(6)
+    want = _loop(frames, chains)
+    states = random.getstate(), np.random.get_state()
+    for mode in ("numpy", "numpy-host"):
+        monkeypatch.setattr(T, "NOISE_RNG", mode)
+        random.seed(6); np.random.seed(6)
+        with monkeypatch.context() as m:
+            if mode == "numpy" and chains is not WITH_SHOT:
+                m.setattr(np.random, "normal", _raise)
+                m.setattr(np.random, "random", _raise)
+            got = P.apply_chain_batch(frames, chains).cpu().numpy()
+        assert np.array_equal(got, want), mode
+        assert random.getstate() == states[0] and same_state(np.random.get_state(), states[1]), mode
+        assert np.random.get_state()[4] == states[1][4]

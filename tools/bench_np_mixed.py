@@ -1,0 +1,49 @@
+"""The workloads of profiles/np_mixed_draw.txt: callers whose np.random calls numpy_stream.draw_mixed serves.
+
+    python tools/bench_np_mixed.py TREE WORKLOADS REPS [IMAGES]
+
+TREE: the checkout whose package is measured (a checkout of the parent commit with its library built gives the "before"
+column); WORKLOADS: comma-separated from driver12, chain_cifar, chain_big, impulse; REPS: timed whole calls after one
+warm-up call, each from freshly seeded generators and ended by a device synchronise; IMAGES: images of driver12 (256).
+Prints one JSON line: median, minimum and maximum seconds per call and items per second at the median."""
+import sys, time, random, statistics, json
+root, which, reps = sys.argv[1], sys.argv[2].split(","), int(sys.argv[3])
+sys.path.insert(0, root)
+import numpy as np, torch
+from PIL import Image
+import imagetransformations_amd
+from imagetransformations_amd import transformations_code as TC, pool as P, transformation as T
+assert imagetransformations_amd.__file__.startswith(root), imagetransformations_amd.__file__
+
+def synth(seed, h, w):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+def timed(fn, n_items):
+    ts = []
+    for r in range(reps + 1):                     # the first run is the warm-up
+        random.seed(r); np.random.seed(r); torch.manual_seed(r)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    ts = ts[1:]
+    med = statistics.median(ts)
+    return {"median_s": round(med, 5), "min_s": round(min(ts), 5), "max_s": round(max(ts), 5), "items_per_s": round(n_items / med, 1), "runs": reps}
+
+out = {}
+if "driver12" in which:
+    n = int(sys.argv[4]) if len(sys.argv) > 4 else 256
+    imgs = [(Image.fromarray(synth(i, 500, 375)), f"img_{i}") for i in range(n)]     # 375 wide, 500 high: rand_crop's square fits
+    out[f"driver12_{n}x375x500"] = timed(lambda: TC.apply_all_transformations_batched(imgs), n)
+chain = ["gaussian_noise", "impulse_noise", "enhance_contrast"]
+if "chain_cifar" in which:
+    fr = torch.from_numpy(np.stack([synth(i, 32, 32) for i in range(1024)])).cuda()
+    out["chain_1024x32x32"] = timed(lambda: P.apply_chain_batch(fr, chain), 1024)
+if "chain_big" in which:
+    fr = torch.from_numpy(np.stack([synth(i, 375, 500) for i in range(64)])).cuda()
+    out["chain_64x375x500"] = timed(lambda: P.apply_chain_batch(fr, chain), 64)
+if "impulse" in which:
+    img = Image.fromarray(synth(3, 375, 500))
+    out["impulse_375x500"] = timed(lambda: P.TransformationPool.impulse_noise(img, 3), 1)
+print(json.dumps({"tree": root, **out}))
