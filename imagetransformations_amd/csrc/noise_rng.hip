@@ -87,47 +87,10 @@ static unsigned noise_grid(int64_t total) {
 namespace imgxf {
 // MT19937's state sequence (numpy/random/src/mt19937/mt19937.c mt19937_gen restated): block 0 = the generator's current
 // key, block b = the 624 state words after b regenerations.  The recurrence runs over the block index, so ONE workgroup
-// walks it; inside a block, words 0..226 depend on the old block only, 227..453 on the new words 0..226, 454..622 on
-// 227..395, and 623 on the new words 396 and 0: four barriers per block.  The RAW words are written (tempering, the
-// doubles and the polar method are data parallel and run afterwards, imagetransformations_amd/numpy_stream.py): the
-// generator's state at any stream position is then a slice of the output.
-__global__ __launch_bounds__(256) void mt19937_blocks_kernel(const u32* __restrict__ key, u32* __restrict__ out, long long nblocks) {
-    __shared__ u32 st[2][624];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 624; i += 256) { const u32 v = key[i]; st[0][i] = v; out[i] = v; }
-    __syncthreads();
-    auto twist = [](u32 u, u32 v) { return (((u & 0x80000000u) | (v & 0x7fffffffu)) >> 1) ^ ((v & 1u) ? 0x9908b0dfu : 0u); };
-    // Inside a block, thread t computes new[t], new[227 + t] (from its own new[t]) and new[454 + t] (from its own new[227 + t]):
-    // the distance of the recurrence is 227, so the chain stays in the thread's registers.  Only new[623] needs other
-    // threads' words (new[396] and new[0]); thread 0 recomputes new[396] from the old block itself.  ONE barrier per block —
-    // the next block reads everybody's words — and it waits for the LDS traffic only (__syncthreads() would also drain the
-    // global stores: 535 ns per block with four of those).
-    for (long long b = 1; b <= nblocks; ++b) {
-        const u32* o = st[(b - 1) & 1];
-        u32* n = st[b & 1];
-        u32* dst = out + b * 624;
-        if (tid < 227) {
-            const u32 a = o[tid + 397] ^ twist(o[tid], o[tid + 1]);
-            const u32 c = a ^ twist(o[227 + tid], o[228 + tid]);
-            n[tid] = a; n[227 + tid] = c;
-            dst[tid] = a; dst[227 + tid] = c;
-            if (tid < 169) {
-                const u32 e = c ^ twist(o[454 + tid], o[455 + tid]);
-                n[454 + tid] = e; dst[454 + tid] = e;
-            }
-            if (tid == 0) {
-                const u32 n169 = o[566] ^ twist(o[169], o[170]);
-                const u32 n396 = n169 ^ twist(o[396], o[397]);
-                const u32 z = n396 ^ twist(o[623], a);
-                n[623] = z; dst[623] = z;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-}
-} // namespace imgxf
-
-namespace imgxf {
+// walks a stretch of it (mt19937_stretch_kernel below; imgxf_mt19937_blocks is one stretch).  The RAW words are written
+// (tempering, the doubles and the polar method are data parallel and run afterwards, imagetransformations_amd/numpy_stream.py):
+// the generator's state at any stream position is then a slice of the output.
+//
 // Jump-ahead (Haramoto et al.): out_keys[w] = F^((w+1) J) base = g_(w+1)(F) base, where F is the generator's one-word step on its
 // canonical state (S[t] .. S[t+623]) and g_m = x^(m J) mod (F's characteristic polynomial), evaluated by Horner's rule:
 // r = 0; for i = deg .. 0: r = F r (+ s if g_i).  One wave per jump (no barriers: a wave's LDS operations execute in order): lane 0
@@ -161,7 +124,7 @@ __global__ __launch_bounds__(64) void mt19937_jump_kernel(const u32* __restrict_
 }
 
 // The state sequence in STRETCHES of `bps` blocks: workgroup m starts from keys[m] (= block m * bps of the stream) and writes
-// blocks m * bps .. min((m + 1) * bps, total) - 1 (the loop of mt19937_blocks_kernel).
+// blocks m * bps .. min((m + 1) * bps, total) - 1.  One workgroup with bps = total is the whole sequence from one key.
 __global__ __launch_bounds__(256) void mt19937_stretch_kernel(const u32* __restrict__ keys, u32* __restrict__ out, long long bps, long long total) {
     __shared__ u32 st[2][624];
     const int tid = threadIdx.x;
@@ -172,6 +135,12 @@ __global__ __launch_bounds__(256) void mt19937_stretch_kernel(const u32* __restr
     for (int i = tid; i < 624; i += 256) { const u32 v = key[i]; st[0][i] = v; if (i || blockIdx.x == 0) out[b0 * 624 + i] = v; }
     __syncthreads();
     auto twist = [](u32 u, u32 v) { return (((u & 0x80000000u) | (v & 0x7fffffffu)) >> 1) ^ ((v & 1u) ? 0x9908b0dfu : 0u); };
+    // Inside a block, words 0..226 depend on the old block only, 227..453 on the new words 0..226, 454..622 on 227..395, and
+    // 623 on the new words 396 and 0.  Thread t computes new[t], new[227 + t] (from its own new[t]) and new[454 + t] (from its
+    // own new[227 + t]): the distance of the recurrence is 227, so the chain stays in the thread's registers.  Only new[623]
+    // needs other threads' words (new[396] and new[0]); thread 0 recomputes new[396] from the old block itself.  ONE barrier per
+    // block — the next block reads everybody's words — and it waits for the LDS traffic only (__syncthreads() would also drain
+    // the global stores: 535 ns per block with four of those).
     for (long long b = b0 + 1; b < b1; ++b) {
         const u32* o = st[(b - b0 - 1) & 1];
         u32* n = st[(b - b0) & 1];
@@ -208,12 +177,27 @@ __device__ __forceinline__ u32 mt_temper(u32 y) {
     y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
     return y;
 }
+// legacy_double of two raw stream words
+__device__ __forceinline__ double legacy_double(u32 w0, u32 w1) {
+    const u32 a = mt_temper(w0) >> 5, b = mt_temper(w1) >> 6;
+    return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
+}
 __device__ __forceinline__ void np_group(const u32* __restrict__ w, double& x1, double& x2, double& r2) {
-    const u32 a = mt_temper(w[0]) >> 5, b = mt_temper(w[1]) >> 6, c = mt_temper(w[2]) >> 5, d = mt_temper(w[3]) >> 6;
-    const double u1 = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;          // legacy_double
-    const double u2 = ((double)c * 67108864.0 + (double)d) / 9007199254740992.0;
+    const double u1 = legacy_double(w[0], w[1]), u2 = legacy_double(w[2], w[3]);
     x1 = 2.0 * u1 - 1.0; x2 = 2.0 * u2 - 1.0;
     r2 = x1 * x1 + x2 * x2;
+}
+// A normal and its guard: stores `nd` as o[idx] — a float, or the double with `f64` — and says whether the host's libm has to
+// confirm it: float32, within `margin` (relative) of a rounding boundary; float64, within `margin` (absolute) of an integer.
+__device__ __forceinline__ bool np_store(bool f64, void* __restrict__ o, long long idx, double nd, double margin) {
+    if (f64) { ((double*)o)[idx] = nd; return fabs(nd - rint(nd)) < margin; }
+    ((float*)o)[idx] = (float)nd;
+    return (float)(nd * (1.0 - margin)) != (float)(nd * (1.0 + margin));
+}
+// One sample of legacy_normal from an accepted group's (x, r2): loc + scale * (f x).  The operation order is NumPy's.
+__device__ __forceinline__ bool np_sample(bool f64, void* __restrict__ o, long long idx, double scale, double x, double r2, double margin) {
+    const double f = sqrt(-2.0 * log(r2) / r2);
+    return np_store(f64, o, idx, 0.0 + scale * (f * x), margin);
 }
 
 __global__ __launch_bounds__(256) void np_accept_kernel(const u32* __restrict__ words, long long ngroups, u8* __restrict__ acc) {
@@ -242,7 +226,6 @@ __global__ __launch_bounds__(256) void np_normals_kernel(const u32* __restrict__
     if (k == prev || k > groups) return;                             // rejected, or beyond what the draw consumes
     double x1, x2, r2;
     np_group(words + 4 * g, x1, x2, r2);
-    const double f = sqrt(-2.0 * log(r2) / r2);
     if (k == groups) { info[0] = g; xr[0] = x1; xr[1] = r2; }
     const double xs[2] = {x2, x1};
 #pragma unroll
@@ -252,9 +235,7 @@ __global__ __launch_bounds__(256) void np_normals_kernel(const u32* __restrict__
         const long long pos = e + lead;
         int lo = 0, hi = nreq - 1;                                   // the request whose range holds pos
         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (reqs[mid].begin <= pos) lo = mid; else hi = mid - 1; }
-        const double nd = 0.0 + reqs[lo].scale * (f * xs[h]);
-        out[pos] = (float)nd;
-        if ((float)(nd * (1.0 - margin)) != (float)(nd * (1.0 + margin))) {
+        if (np_sample(false, out, pos, reqs[lo].scale, xs[h], r2, margin)) {
             const long long slot = (long long)atomicAdd((unsigned long long*)&info[1], 1ull);
             if (slot < risky_cap) { risky[slot] = e; xr[2 + 2 * slot] = xs[h]; xr[3 + 2 * slot] = r2; }
         }
@@ -443,18 +424,14 @@ __global__ __launch_bounds__(MIX_WG) void np_mixed_fill_kernel(const u32* __rest
         for (int j = 0; j < MIX_ROUNDS; ++j) {
             const long long e = c * MIX_CHUNK + (long long)j * MIX_WG + tid;
             if (e >= q.count) break;
-            const u32 a = mt_temper(words[w.start + 2 * e]) >> 5, b = mt_temper(words[w.start + 2 * e + 1]) >> 6;
-            ((double*)o)[e] = ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;       // legacy_double
+            ((double*)o)[e] = legacy_double(words[w.start + 2 * e], words[w.start + 2 * e + 1]);
         }
         return;
     }
     const int lead = q.lead != MIX_LEAD_NONE ? 1 : 0;
     const long long n2 = q.count - lead, need = (n2 + 1) >> 1;
-    auto put = [&](long long idx, double nd, double x, double r2v, bool guarded) {
-        bool risk;
-        if (f64) { ((double*)o)[idx] = nd; risk = fabs(nd - rint(nd)) < margin; }
-        else { ((float*)o)[idx] = (float)nd; risk = (float)(nd * (1.0 - margin)) != (float)(nd * (1.0 + margin)); }
-        if (risk && guarded) {
+    auto put = [&](long long idx, double x, double r2v) {
+        if (np_sample(f64, o, idx, q.scale, x, r2v, margin)) {
             const long long slot = (long long)atomicAdd((unsigned long long*)&info[MIX_INFO_NRISKY], 1ull);
             if (slot < risky_cap) {
                 risky[4 * slot] = i; risky[4 * slot + 1] = idx;
@@ -463,8 +440,8 @@ __global__ __launch_bounds__(MIX_WG) void np_mixed_fill_kernel(const u32* __rest
         }
     };
     if (c == 0 && tid == 0 && lead) {
-        if (q.lead == MIX_LEAD_GIVEN) put(0, 0.0 + q.scale * gauss0, 0.0, 0.0, false);           // (exact: the host's own value)
-        else put(0, 0.0 + q.scale * (sqrt(-2.0 * log(w.r2) / w.r2) * w.x1), w.x1, w.r2, true);
+        if (q.lead == MIX_LEAD_GIVEN) np_store(f64, o, 0, 0.0 + q.scale * gauss0, margin);        // (exact: the host's own value)
+        else put(0, w.x1, w.r2);
     }
     if (c >= w.chunks) return;
     double x1[MIX_ROUNDS], x2[MIX_ROUNDS], r2[MIX_ROUNDS];
@@ -475,10 +452,9 @@ __global__ __launch_bounds__(MIX_WG) void np_mixed_fill_kernel(const u32* __rest
     for (int j = 0; j < MIX_ROUNDS; ++j) {
         const long long k = before + rank[j];
         if (!rank[j] || k > need) continue;                          // rejected, or beyond what the request consumes
-        const double f = sqrt(-2.0 * log(r2[j]) / r2[j]);
         const long long e = 2 * (k - 1);
-        put(lead + e, 0.0 + q.scale * (f * x2[j]), x2[j], r2[j], true);
-        if (e + 1 < n2) put(lead + e + 1, 0.0 + q.scale * (f * x1[j]), x1[j], r2[j], true);
+        put(lead + e, x2[j], r2[j]);
+        if (e + 1 < n2) put(lead + e + 1, x1[j], r2[j]);
     }
 }
 } // namespace imgxf
@@ -511,7 +487,8 @@ IMGXF_API int imgxf_philox4x32_u32(void* dst_u32, int64_t count, uint64_t seed, 
 IMGXF_API int imgxf_mt19937_blocks(const uint32_t* key, uint32_t* out, int64_t nblocks, void* stream) {
     if (!key || !out) return IMGXF_ERR_NULL;
     if (nblocks < 0) return IMGXF_ERR_ARG;
-    hipLaunchKernelGGL(mt19937_blocks_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, key, out, (long long)nblocks);
+    hipLaunchKernelGGL(mt19937_stretch_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, key, out, (long long)nblocks + 1,
+                       (long long)nblocks + 1);                         // one stretch: block 0 = the key, then nblocks blocks
     return launch_status();
 }
 

@@ -19,6 +19,11 @@ Exactness: every step is integer arithmetic or a correctly rounded IEEE operatio
 glibc's may differ in the last bit.  The float32 result can only differ if the double lies within 2^-46 (relative) of a
 float32 rounding boundary — one sample in two million; those are recomputed with the host's libm from their exact (x, r2)
 and patched in, as is the cached second normal that an odd-length draw hands back to NumPy as generator state.
+
+Layout: `normals` (all-normal lists, the prefix-sum pair of kernels) and `mixed` (normal / random / randint lists, walk and
+fill) evaluate a raw stream and know nothing of np.random; they share `legacy_double` and `_patch`.  np.random's global
+state is read in `start` and set in `_Pass.finish`, nowhere else; `_draw` cuts long lists into passes; `draw_on_device`,
+`draw_mixed` and `PendingDraw` are uses of those three.
 """
 from __future__ import annotations
 
@@ -40,6 +45,17 @@ def temper(y: torch.Tensor) -> torch.Tensor:
     y = y ^ ((y << 15) & 0xEFC60000)
     y = y ^ (y >> 18)
     return y & 0xFFFFFFFF
+
+
+def tempered(raw: torch.Tensor, lo: int, n: int) -> torch.Tensor:
+    """Stream words lo .. lo + n - 1 (next32's results) of the raw state sequence `raw` (int32 / int64 bit patterns)."""
+    return temper(raw[lo:lo + n].to(torch.int64) & 0xFFFFFFFF)
+
+
+def legacy_double(raw: torch.Tensor, lo: int, n: int) -> torch.Tensor:
+    """The `n` legacy_doubles that stream words lo .. lo + 2 n - 1 make: a = next >> 5, b = next >> 6, (a * 2^26 + b) / 2^53."""
+    t = tempered(raw, lo, 2 * n).view(-1, 2)
+    return ((t[:, 0] >> 5).double() * 67108864.0 + (t[:, 1] >> 6).double()) / _TWO53
 
 
 def mt_next_block(key: np.ndarray) -> np.ndarray:
@@ -79,6 +95,17 @@ def _host_gauss(x: float, r2: float) -> float:
 MARGIN = 2.0 ** -46          # relative; the device's log is within an ulp (2^-53) of glibc's, f x and the scaling add a few more
 
 
+def _patch(flat: torch.Tensor, req, idx, x, r2, scales, offsets) -> int:
+    """The samples an evaluator found inside its guard, recomputed with the host's libm: sample idx[j] of request req[j], which
+    came from (x[j], r2[j]), is flat[offsets[req[j]] + idx[j]] = 0.0 + scales[req[j]] * f x, rounded to flat's dtype.  Returns
+    their number."""
+    req = np.asarray(req, np.int64)
+    vals = [0.0 + float(scales[k]) * _host_gauss(float(a), float(b)) for k, a, b in zip(req, x, r2)]
+    at = torch.from_numpy(np.asarray(offsets, np.int64)[req] + np.asarray(idx, np.int64)).to(flat.device)
+    flat[at] = torch.tensor(vals, dtype=torch.float64).to(flat.dtype).to(flat.device)
+    return len(vals)
+
+
 def normals(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, requests: Sequence[tuple], f64: bool = False) -> Draw:
     """`raw`: the raw MT19937 state sequence as an int32 / int64 tensor of uint32 bit patterns (block 0 = the generator's
     current key; what imgxf_mt19937_blocks writes), `start`: the generator's position in it (its `pos`), `has_gauss` /
@@ -106,7 +133,7 @@ def normals(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, reques
         d.position, d.has_gauss, d.gauss, d.patched = pos, has_gauss, float(gauss), 0
         return d
     n2 = total - (1 if has_gauss else 0)                     # normals to take from new groups
-    if raw.is_cuda and not f64 and raw.dtype == torch.int32 and os.environ.get("IMGXF_NP_FUSED", "1") != "0":
+    if raw.is_cuda and not f64 and raw.dtype == torch.int32:
         return _normals_fused(raw, pos, has_gauss, float(gauss), requests, counts, total, n2)
     xs = ar = None
     if n2 > 0:
@@ -114,12 +141,9 @@ def normals(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, reques
         w = words_needed(n2)
         if pos + w > raw.numel():
             raise ValueError("the MT19937 stream is shorter than the draw's margin")
-        t = temper(raw[pos:pos + w].to(torch.int64) & 0xFFFFFFFF).view(-1, 4)
-        u1 = ((t[:, 0] >> 5).double() * 67108864.0 + (t[:, 1] >> 6).double()) / _TWO53
-        u2 = ((t[:, 2] >> 5).double() * 67108864.0 + (t[:, 3] >> 6).double()) / _TWO53
-        del t
-        x1, x2 = 2.0 * u1 - 1.0, 2.0 * u2 - 1.0
-        del u1, u2
+        u = legacy_double(raw, pos, w // 2).view(-1, 2)
+        x1, x2 = 2.0 * u[:, 0] - 1.0, 2.0 * u[:, 1] - 1.0
+        del u
         r2 = x1 * x1 + x2 * x2
         acc = (r2 < 1.0) & (r2 != 0.0)
         rank = torch.cumsum(acc, 0)
@@ -160,10 +184,8 @@ def normals(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, reques
                 risky = ((nd * (1.0 - MARGIN)).float() != (nd * (1.0 + MARGIN)).float()).nonzero().flatten()
             if risky.numel():
                 e = risky + lo
-                xv, rv = xs[e].cpu().tolist(), ar[e // 2].cpu().tolist()
-                exact = [0.0 + scale * _host_gauss(x, r) for x, r in zip(xv, rv)]
-                res[risky] = torch.tensor(exact if f64 else [np.float32(v) for v in exact], dtype=odt).to(dev)
-                patched += int(risky.numel())
+                patched += _patch(res, np.zeros(risky.numel(), np.int64), risky.cpu().numpy(), xs[e].cpu().tolist(), ar[e // 2].cpu().tolist(),
+                                  [scale], [0])
             out.append(torch.cat((torch.tensor(head, dtype=odt, device=dev), res)) if head else res)
         else:
             out.append(torch.tensor(head, dtype=odt, device=dev))
@@ -221,13 +243,10 @@ def _normals_fused(raw, pos, has_gauss, gauss, requests, counts, total, n2) -> D
         if nrisky > RISKY_CAP:
             raise ValueError("more samples near a float32 rounding boundary than the list holds")
         if nrisky:
-            e = risky[:nrisky].cpu().numpy()
+            at = risky[:nrisky].cpu().numpy() + lead
             xv = xr[2:2 + 2 * nrisky].cpu().numpy().reshape(-1, 2)
-            b_arr = np.array([b for b, _ in live]); s_arr = np.array([s for _, s in live])
-            which = np.searchsorted(b_arr, e + lead, side="right") - 1
-            fix = np.array([np.float32(0.0 + s_arr[k] * _host_gauss(float(x), float(r))) for k, (x, r) in zip(which, xv)], np.float32)
-            out[torch.from_numpy(e + lead).to(dev)] = torch.from_numpy(fix).to(dev)
-            patched = int(nrisky)
+            which = np.searchsorted(table["begin"], at, side="right") - 1
+            patched = _patch(out, which, at - table["begin"][which], xv[:, 0], xv[:, 1], table["scale"], table["begin"])
         pos += 4 * (last + 1)
         if n2 & 1:
             x1, r2 = xr[:2].cpu().tolist()
@@ -326,8 +345,7 @@ def mixed(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, requests
             n = r[1]
             if pos + 2 * n > raw.numel():
                 raise ValueError("the MT19937 stream is shorter than the draw")
-            t = temper(raw[pos:pos + 2 * n].to(torch.int64) & 0xFFFFFFFF).view(-1, 2)
-            d.noise.append(((t[:, 0] >> 5).double() * 67108864.0 + (t[:, 1] >> 6).double()) / _TWO53)
+            d.noise.append(legacy_double(raw, pos, n))
             pos += 2 * n
         else:
             low = r[1]
@@ -336,7 +354,7 @@ def mixed(raw: torch.Tensor, start: int, has_gauss: bool, gauss: float, requests
             while rng:
                 if pos >= raw.numel():
                     raise ValueError("the MT19937 stream ended inside a randint")
-                v = int(temper(raw[pos:pos + 1].to(torch.int64) & 0xFFFFFFFF).item()) & mask
+                v = int(tempered(raw, pos, 1).item()) & mask
                 pos += 1
                 if v <= rng:
                     break
@@ -413,9 +431,7 @@ def _mixed_device(raw, pos, has_gauss, gauss, reqs, f64) -> Draw:
         if nrisky:
             entries = entries.reshape(-1, 4)
             xr = entries[:, 2:].copy().view(np.float64)
-            vals = [0.0 + float(tab["scale"][k]) * _host_gauss(float(x), float(r)) for k, (x, r) in zip(entries[:, 0], xr)]
-            at = torch.from_numpy(tab["out_off"][entries[:, 0]] // esz + entries[:, 1]).to(dev)
-            out.view(odt)[at] = torch.tensor(vals, dtype=torch.float64).to(odt).to(dev)
+            _patch(out.view(odt), entries[:, 0], entries[:, 1], xr[:, 0], xr[:, 1], tab["scale"], tab["out_off"] // esz)
     d = Draw()
     d.noise = []
     for i, r in enumerate(reqs):
@@ -457,7 +473,7 @@ def _jump_tables(device: torch.device):
         return st if st else None
     _JUMP["state"] = False
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mt19937_jump.npz")
-    if not os.path.exists(path) or os.environ.get("IMGXF_MT_JUMP", "1") == "0":
+    if not os.path.exists(path):
         return None
     z = np.load(path)
     bps = 1 << int(z["log2_blocks"])
@@ -504,52 +520,45 @@ def generate_stream(key_d: torch.Tensor, nblocks: int, device: torch.device, cud
     # before it, one step past its last block)
     return raw
 
-PASS_NORMALS = 1 << 27       # normals per pass over the stream (the pass holds ~70 bytes per normal on the device for a moment)
+PASS_NORMALS = 1 << 27       # samples per pass over the stream (the pass holds ~70 bytes per normal on the device for a moment)
 
 
-def draw_on_device(requests: Sequence[tuple], device, f64: bool = False) -> List[torch.Tensor] | None:
-    """_draw_pass over stretches of at most PASS_NORMALS normals (np.random's state carries from one to the next)."""
-    requests = [(int(n), float(s)) for n, s in requests]
-    out: List[torch.Tensor] = []
-    i = 0
-    while i < len(requests):
-        j, tot = i, 0
-        while j < len(requests) and (j == i or tot + requests[j][0] <= PASS_NORMALS):
-            tot += requests[j][0]
-            j += 1
-        got = _draw_pass(requests[i:j], device, f64)
-        if got is None:
-            if i == 0:
+# ---- np.random's global generator: one pass over the stream in two halves, and lists longer than a pass ---------------------
+class _Pass:
+    """np.random's state as `start` read it, the requests of the pass and the raw stream generated for them."""
+    __slots__ = ("requests", "device", "key", "pos", "has_gauss", "gauss", "raw")
+
+    def finish(self, evaluate, f64: bool = False) -> Draw | None:
+        """The Draw of `evaluate(raw, pos, has_gauss, gauss, requests, f64)` (`mixed`, or `_only_normals`) with np.random's state
+        set behind it — or None, np.random untouched, if the evaluator raises ValueError: the stream generated for the
+        requests' margins turned out too short, or more samples need the host's libm than the list holds."""
+        with torch.cuda.device(self.device):
+            try:
+                d = evaluate(self.raw, self.pos, self.has_gauss, self.gauss, self.requests, f64)
+            except ValueError:
                 return None
-            got = [torch.from_numpy(np.random.normal(0, s, n) if f64 else np.random.normal(0, s, n).astype(np.float32)).to(device)
-                   for n, s in requests[i:j]]                    # (only if the generator changed kind in between)
-        out.extend(got)
-        i = j
-    return out
+            if d.position != self.pos or d.has_gauss != self.has_gauss:
+                moved = d.position != self.pos                   # (if not, only the cached normal went)
+                key, pos = state_at(self.raw, d.position, self.pos) if moved else (self.key, self.pos)
+                np.random.set_state(("MT19937", key, pos, int(d.has_gauss), float(d.gauss) if d.has_gauss else 0.0))
+        return d
 
 
-def _draw_pass(requests: Sequence[tuple], device, f64: bool = False) -> List[torch.Tensor] | None:
-    """The float32 results of `[np.random.normal(0, scale, count).astype(np.float32) for count, scale in requests]` as
-    device tensors, with np.random's global state advanced exactly as those calls would have advanced it — or None (state
-    untouched) if the global generator is not the legacy MT19937: the caller then makes the calls on the host."""
-    from . import _ffi as F
-    device = torch.device(device)
-    requests = [(int(n), float(s)) for n, s in requests]
-    if not any(n for n, _ in requests):
-        return [torch.empty((0,), dtype=torch.float64 if f64 else torch.float32, device=device) for _ in requests]
-    kind, key, pos, has_gauss, gauss = np.random.get_state()
-    if kind != "MT19937":
+def start(requests: list, words, device: torch.device, cuda_stream: int | None = None) -> _Pass | None:
+    """The first half of a pass: reads np.random's state and launches the generation of the `words(requests)` stream words
+    behind its position on `cuda_stream` (None: the current stream, which has to be the one torch allocates on).  None, and
+    `start` itself has touched nothing on the device, if the global generator is not the legacy MT19937."""
+    st = np.random.get_state(legacy=False)
+    if st["bit_generator"] != "MT19937":
         return None
-    total = words_needed(sum(n for n, _ in requests))
-    nblocks = (int(pos) + total) // 624 + 2
+    p = _Pass()
+    p.requests, p.device = requests, device
+    p.key, p.pos, p.has_gauss, p.gauss = st["state"]["key"], int(st["state"]["pos"]), bool(st["has_gauss"]), float(st["gauss"])
+    nblocks = (p.pos + words(requests)) // 624 + 2
     with torch.cuda.device(device):
-        key_d = torch.from_numpy(key.astype(np.uint32).view(np.int32).copy()).to(device)
-        raw = generate_stream(key_d, nblocks, device, torch.cuda.current_stream(device).cuda_stream)
-        d = normals(raw, int(pos), bool(has_gauss), float(gauss), requests, f64)
-        if d.position != int(pos) or bool(has_gauss) != d.has_gauss:
-            k, p = state_at(raw, d.position, int(pos))
-            np.random.set_state((kind, k, p, int(d.has_gauss), float(d.gauss) if d.has_gauss else 0.0))
-    return d.noise
+        key_d = torch.from_numpy(p.key.astype(np.uint32).view(np.int32).copy()).to(device)
+        p.raw = generate_stream(key_d, nblocks, device, torch.cuda.current_stream(device).cuda_stream if cuda_stream is None else cuda_stream)
+    return p
 
 
 def host_mixed(requests: Sequence[tuple], f64: bool = False) -> list:
@@ -566,16 +575,10 @@ def host_mixed(requests: Sequence[tuple], f64: bool = False) -> list:
     return out
 
 
-def draw_mixed(requests: Sequence[tuple], device, f64: bool = False, stats: dict | None = None) -> list | None:
-    """The results of a list of mixed np.random calls (see `mixed`) — device tensors for normal and random requests, Python
-    ints for randint — with np.random's global state advanced exactly as the calls would have advanced it; None, with the
-    state untouched and nothing drawn, if the global generator is not the legacy MT19937, a randint range exceeds 32 bits
-    (or np.random itself would refuse a request), or the stream generated for the requests' margins turned out too short:
-    the caller then makes the calls on the host.  Lists of more than PASS_NORMALS samples take several passes.
-    `stats`, when given, receives "patched": the samples the host's libm recomputed (Draw.patched, summed over the passes)."""
-    reqs = _check_requests(requests)
-    if reqs is None:
-        return None
+def _draw(reqs: list, device, f64: bool, words, evaluate, stats: dict | None = None) -> list | None:
+    """Passes of at most PASS_NORMALS samples over checked requests (np.random's state carries from one to the next).  A
+    pass that comes back None — a foreign generator, a stream that turned out too short — ends the call with None if it is
+    the first one (np.random is untouched); the host makes the calls of a later one."""
     device = torch.device(device)
     out: list = []
     i = patched = 0
@@ -584,7 +587,8 @@ def draw_mixed(requests: Sequence[tuple], device, f64: bool = False, stats: dict
         while j < len(reqs) and (j == i or tot + (reqs[j][1] if reqs[j][0] != "randint" else 0) <= PASS_NORMALS):
             tot += reqs[j][1] if reqs[j][0] != "randint" else 0
             j += 1
-        d = _mixed_pass(reqs[i:j], device, f64)
+        p = start(reqs[i:j], words, device)
+        d = p.finish(evaluate, f64) if p is not None else None
         if d is None:
             if i == 0:
                 return None
@@ -598,67 +602,74 @@ def draw_mixed(requests: Sequence[tuple], device, f64: bool = False, stats: dict
     return out
 
 
-def _mixed_pass(reqs: list, device: torch.device, f64: bool) -> Draw | None:
-    """One pass: the Draw of `mixed` with np.random's state set behind it, or None (state untouched)."""
-    st = np.random.get_state(legacy=False)
-    if st["bit_generator"] != "MT19937":
-        return None
-    kind, key, pos, has_gauss, gauss = "MT19937", st["state"]["key"], int(st["state"]["pos"]), st["has_gauss"], st["gauss"]
-    nblocks = (int(pos) + mixed_words(reqs)) // 624 + 2
-    with torch.cuda.device(device):
-        key_d = torch.from_numpy(key.astype(np.uint32).view(np.int32).copy()).to(device)
-        raw = generate_stream(key_d, nblocks, device, torch.cuda.current_stream(device).cuda_stream)
-        try:
-            d = mixed(raw, int(pos), bool(has_gauss), float(gauss), reqs, f64)
-        except ValueError:
-            return None
-        if d.position != int(pos) or bool(has_gauss) != d.has_gauss:
-            k, p = state_at(raw, d.position, int(pos)) if d.position != int(pos) else (key, pos)    # (only the cached normal went)
-            np.random.set_state((kind, k, p, int(d.has_gauss), float(d.gauss) if d.has_gauss else 0.0))
-    return d
+def draw_mixed(requests: Sequence[tuple], device, f64: bool = False, stats: dict | None = None) -> list | None:
+    """The results of a list of mixed np.random calls (see `mixed`) — device tensors for normal and random requests, Python
+    ints for randint — with np.random's global state advanced exactly as the calls would have advanced it; None, with the
+    state untouched and nothing drawn, if the global generator is not the legacy MT19937, a randint range exceeds 32 bits
+    (or np.random itself would refuse a request), or the stream generated for the requests' margins turned out too short:
+    the caller then makes the calls on the host.  Lists of more than PASS_NORMALS samples take several passes.
+    `stats`, when given, receives "patched": the samples the host's libm recomputed (Draw.patched, summed over the passes)."""
+    reqs = _check_requests(requests)
+    return None if reqs is None else _draw(reqs, device, f64, mixed_words, mixed, stats)
+
+
+# draw_on_device's lists are all normals, spelt (count, scale).  They keep the evaluator `normals` and ONE margin for the
+# list's total: mixed_words reserves a margin per request, which for the 256 requests of a driver batch is a longer stream.
+def _normal_requests(requests) -> list:
+    return [("normal", int(n), float(s)) for n, s in requests]
+
+
+def _normal_words(reqs) -> int:
+    return words_needed(sum(r[1] for r in reqs))
+
+
+def _only_normals(raw, pos, has_gauss, gauss, reqs, f64) -> Draw:
+    return normals(raw, pos, has_gauss, gauss, [r[1:] for r in reqs], f64)
+
+
+def draw_on_device(requests: Sequence[tuple], device, f64: bool = False) -> List[torch.Tensor] | None:
+    """The float32 (`f64`: float64) results of `[np.random.normal(0, scale, count) for count, scale in requests]` as device
+    tensors, with np.random's global state advanced exactly as those calls would have advanced it — or None, state
+    untouched, where draw_mixed returns None: the caller then makes the calls on the host."""
+    reqs = _normal_requests(requests)
+    if not any(r[1] for r in reqs):
+        return [torch.empty((0,), dtype=torch.float64 if f64 else torch.float32, device=torch.device(device)) for _ in reqs]
+    return _draw(reqs, device, f64, _normal_words, _only_normals)
 
 
 class PendingDraw:
     """draw_on_device in two halves, so that the MT19937 block kernel — one workgroup, 0.17 s for the 144 M normals of 256
     ImageNet-size images — runs on a side stream while the caller queues its other device work and does its host work:
-    `PendingDraw(requests, device)` reads np.random's state and launches the kernel, `result()` (later, same thread) evaluates
-    the stream, advances np.random and returns the tensors, or None where draw_on_device would.  Nothing else may use
-    np.random in between (the state is read at the start and set at the end)."""
+    `PendingDraw(requests, device)` is `start` on the side stream, `result()` (later, same thread) is `finish` on the main
+    one: it advances np.random and returns the tensors, or None where draw_on_device would.  Nothing else may use
+    np.random in between (the state is read at the start and set at the end).  An empty list, one above PASS_NORMALS and a
+    foreign generator are left to draw_on_device in result() (for the last, the side stream has by then waited for the main
+    one, and nothing else has happened on the device)."""
 
     def __init__(self, requests: Sequence[tuple], device, f64: bool = False):
-        from . import _ffi as F
-        self.requests = [(int(n), float(s)) for n, s in requests]
-        self.device, self.f64 = torch.device(device), f64
-        self.raw = None
-        total = sum(n for n, _ in self.requests)
-        self.state = np.random.get_state()
-        kind, key, pos = self.state[0], self.state[1], self.state[2]
-        if kind != "MT19937" or total == 0 or total > PASS_NORMALS:
-            return                                               # result() takes the one-call path
-        nblocks = (int(pos) + words_needed(total)) // 624 + 2
+        self.requests, self.device, self.f64 = _normal_requests(requests), torch.device(device), f64
+        self.run = None
+        if not 0 < sum(r[1] for r in self.requests) <= PASS_NORMALS:
+            return
         with torch.cuda.device(self.device):
             main = torch.cuda.current_stream(self.device)
-            self.side = _side_stream(self.device)
-            self.side.wait_stream(main)
-            with torch.cuda.stream(self.side):
-                self.key_d = torch.from_numpy(key.astype(np.uint32).view(np.int32).copy()).to(self.device)
-                self.raw = generate_stream(self.key_d, nblocks, self.device, self.side.cuda_stream)
-            self.done = torch.cuda.Event()
-            self.done.record(self.side)
+            side = _side_stream(self.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                self.run = start(self.requests, _normal_words, self.device, side.cuda_stream)
+            if self.run is not None:
+                self.done = torch.cuda.Event()
+                self.done.record(side)
 
     def result(self) -> List[torch.Tensor] | None:
-        if self.raw is None:
-            return draw_on_device(self.requests, self.device, self.f64)
-        kind, key, pos, has_gauss, gauss = self.state
+        if self.run is None:
+            return draw_on_device([r[1:] for r in self.requests], self.device, self.f64)
         with torch.cuda.device(self.device):
             main = torch.cuda.current_stream(self.device)
             main.wait_event(self.done)
-            self.raw.record_stream(main)
-            d = normals(self.raw, int(pos), bool(has_gauss), float(gauss), self.requests, self.f64)
-            if d.position != int(pos) or bool(has_gauss) != d.has_gauss:
-                k, p = state_at(self.raw, d.position, int(pos))
-                np.random.set_state((kind, k, p, int(d.has_gauss), float(d.gauss) if d.has_gauss else 0.0))
-        return d.noise
+            self.run.raw.record_stream(main)
+            d = self.run.finish(_only_normals, self.f64)
+        return None if d is None else d.noise
 
 
 _SIDE: dict = {}

@@ -193,27 +193,31 @@ def apply_gaussian_noise(img: Image.Image, noise_std: float) -> Image.Image:
     return _download(out)
 
 
+def _stream_device(samples: int, dev):
+    """The gate of the np.random stream on the device: the device that computes a call's numbers, or None where the host draws
+    them — mode "numpy-host", fewer than NOISE_DEVICE_MIN samples (normals + uniforms) in the whole call, no sample at all
+    (an empty list), or no ROCm device.
+    Below the gate nothing touches the device (`dev` None: the current device, looked up past it)."""
+    if NOISE_RNG == "numpy-host" or samples < max(1, NOISE_DEVICE_MIN) or not torch.cuda.is_available():
+        return None                                     # (a CIFAR image is 3072 normals: 50 us on the host, less than one launch)
+    return _device() if dev is None else dev
+
+
 def _numpy_noise(requests, dev=None, f64=False, deferred=False):
     """[(count, scale)] -> device tensors holding np.random.normal(0, scale, count) for each request (cast to float32
-    unless `f64`), np.random's state advanced accordingly; [None, ...] (state untouched) when the host has to draw: mode
-    "numpy-host", fewer than NOISE_DEVICE_MIN normals in all, or numpy_stream's uncertainty guard.  Below that gate nothing
-    touches the device (`dev` None: the current device, looked up past the gate).
+    unless `f64`), np.random's state advanced accordingly; [None, ...] (state untouched) when the host has to draw:
+    `_stream_device`'s gate, or numpy_stream.draw_on_device refuses.
     `deferred`: the generator starts now on a side stream (numpy_stream.PendingDraw) and a function comes back that gives
     the list later — nothing else may use np.random in between; None when the gate leaves the draw to the host."""
-    if NOISE_RNG == "numpy-host" or not requests or sum(n for n, _ in requests) < NOISE_DEVICE_MIN:
-        return None if deferred else [None] * len(requests)   # (a CIFAR image is 3072 normals: 50 us on the host, less than one launch)
+    dev = _stream_device(sum(n for n, _ in requests), dev)
+    if dev is None:
+        return None if deferred else [None] * len(requests)
     from . import numpy_stream
-    dev = _device() if dev is None else dev
-    state = np.random.get_state()
     draw = numpy_stream.PendingDraw(requests, dev, f64).result if deferred else \
         (lambda: numpy_stream.draw_on_device(requests, dev, f64))
 
     def finish():
-        try:
-            got = draw()
-        except ValueError:                              # fewer accepted groups than 12 standard deviations allow for: the host draws
-            np.random.set_state(state)
-            got = None
+        got = draw()
         return got if got is not None else [None] * len(requests)
     return finish if deferred else finish()
 
@@ -222,16 +226,13 @@ def _numpy_mixed(requests, dev=None, f64=False):
     """`_numpy_noise` for np.random calls of several kinds in call order — ("normal", count, scale), ("random", count),
     ("randint", low, high); numpy_stream.draw_mixed — : device tensors for the normals (float32 unless `f64`) and the
     uniforms, Python ints for the randints, np.random's state advanced as the calls would have; None (state untouched,
-    nothing on the device) when the host has to make the calls: mode "numpy-host", an empty list, fewer than
-    NOISE_DEVICE_MIN samples (normals + uniforms) in the whole list, no ROCm device, or draw_mixed refuses."""
-    if NOISE_RNG == "numpy-host" or not requests:
-        return None
-    if sum(r[1] for r in requests if r[0] != "randint") < NOISE_DEVICE_MIN:
-        return None
-    if not torch.cuda.is_available():
+    nothing on the device) when the host has to make the calls: `_stream_device`'s gate (an empty list is below it), or
+    draw_mixed refuses."""
+    dev = _stream_device(sum(r[1] for r in requests if r[0] != "randint"), dev)
+    if dev is None:
         return None
     from . import numpy_stream
-    return numpy_stream.draw_mixed(requests, _device() if dev is None else dev, f64)
+    return numpy_stream.draw_mixed(requests, dev, f64)
 
 
 # ------------------------------------------------------------------ translation (:284-307)

@@ -562,8 +562,10 @@ int imgxf_jpeg_unstuff_host(const uint8_t* data, size_t n, size_t start, uint8_t
                             int64_t* seg_off, int32_t* seg_len, int max_segs, int* nsegs, size_t* ecs_end);
 /* NumPy's legacy generator on the device (np.random.normal of apply_gaussian_noise, /root/reference/transformation.py:273-275):
  * the raw MT19937 state sequence — out[0 .. 623] = key (device pointer, the generator's current 624 state words), block b =
- * the state after b regenerations (mt19937_gen), (nblocks + 1) * 624 words in all.  One workgroup: the recurrence is
- * sequential in the block index.  Tempering, legacy_double and the polar method follow in imagetransformations_amd/numpy_stream.py. */
+ * the state after b regenerations (mt19937_gen), (nblocks + 1) * 624 words in all; nblocks = 0 writes the key only.  One
+ * workgroup: the recurrence is sequential in the block index.  This is imgxf_mt19937_stretches' kernel launched with one
+ * stretch of nblocks + 1 blocks from `key`, so both entry points run the same block loop.  Tempering, legacy_double and the
+ * polar method follow in imagetransformations_amd/numpy_stream.py. */
 int imgxf_mt19937_blocks(const uint32_t* key, uint32_t* out, int64_t nblocks, void* stream);
 
 /* The same sequence in parallel.  imgxf_mt19937_jump: out_keys[w * 624 ..] = the generator's canonical state (w + 1) * J words

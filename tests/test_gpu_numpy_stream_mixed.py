@@ -100,6 +100,18 @@ def test_doubles(device):
         assert torch.equal(a, b)
 
 
+def test_mixed_passes_over_the_stream_hand_the_state_on(device, monkeypatch):
+    """A mixed list beyond PASS_NORMALS is served by several passes (three here: 5000 samples, 4000, 9001); np.random's
+    state — a cached normal included — carries between them."""
+    monkeypatch.setattr(NS, "PASS_NORMALS", 5000)
+    real_start, passes = NS.start, []
+    monkeypatch.setattr(NS, "start", lambda reqs, *a, **k: passes.append(len(reqs)) or real_start(reqs, *a, **k))
+    np.random.seed(31)
+    check_draw([("normal", 3001, 2.0), ("randint", 0, 19), ("random", 1999), ("normal", 4000, 3.0), ("randint", 0, 15),
+                ("normal", 9001, 0.5)], device)
+    assert passes == [3, 2, 1]
+
+
 def test_short_stream_is_refused(device, monkeypatch):
     """With no allowance for the randints and no margin for the normals the generated stream ends inside the draw: the walk
     stops at its bounds check, draw_mixed returns None, np.random is untouched and the host makes the calls."""

@@ -1,10 +1,12 @@
-"""The workloads of profiles/np_mixed_draw.txt: callers whose np.random calls numpy_stream.draw_mixed serves.
+"""The workloads of profiles/np_mixed_draw.txt and profiles/np_stream_one_driver.txt: callers whose np.random calls
+numpy_stream.draw_mixed and numpy_stream.draw_on_device / PendingDraw serve.
 
     python tools/bench_np_mixed.py TREE WORKLOADS REPS [IMAGES]
 
 TREE: the checkout whose package is measured (a checkout of the parent commit with its library built gives the "before"
-column); WORKLOADS: comma-separated from driver12, chain_cifar, chain_big, impulse; REPS: timed whole calls after one
-warm-up call, each from freshly seeded generators and ended by a device synchronise; IMAGES: images of driver12 (256).
+column); WORKLOADS: comma-separated from driver12, driver8, chain_cifar, chain_big, impulse, normals, normals_f64; REPS:
+timed whole calls after one warm-up call, each from freshly seeded generators and ended by a device synchronise; IMAGES:
+images of driver12 and driver8 (256).
 Prints one JSON line: median, minimum and maximum seconds per call and items per second at the median."""
 import sys, time, random, statistics, json
 root, which, reps = sys.argv[1], sys.argv[2].split(","), int(sys.argv[3])
@@ -12,7 +14,7 @@ sys.path.insert(0, root)
 import numpy as np, torch
 from PIL import Image
 import imagetransformations_amd
-from imagetransformations_amd import transformations_code as TC, pool as P, transformation as T
+from imagetransformations_amd import numpy_stream as NS, transformations_code as TC, pool as P, transformation as T
 assert imagetransformations_amd.__file__.startswith(root), imagetransformations_amd.__file__
 
 def synth(seed, h, w):
@@ -36,6 +38,14 @@ if "driver12" in which:
     n = int(sys.argv[4]) if len(sys.argv) > 4 else 256
     imgs = [(Image.fromarray(synth(i, 500, 375)), f"img_{i}") for i in range(n)]     # 375 wide, 500 high: rand_crop's square fits
     out[f"driver12_{n}x375x500"] = timed(lambda: TC.apply_all_transformations_batched(imgs), n)
+if "driver8" in which:                            # the eight-type driver: its normals come from PendingDraw
+    n = int(sys.argv[4]) if len(sys.argv) > 4 else 256
+    imgs8 = [(Image.fromarray(synth(i, 375, 500)), f"img_{i}.jpeg") for i in range(n)]
+    out[f"driver8_{n}x375x500"] = timed(lambda: T.apply_all_transformations_batched(imgs8), n)
+if "normals" in which:
+    out["normals_64x562500"] = timed(lambda: NS.draw_on_device([(562500, 12.75)] * 64, "cuda"), 64)
+if "normals_f64" in which:
+    out["normals_f64_562500"] = timed(lambda: NS.draw_on_device([(562500, 12.75)], "cuda", f64=True), 1)
 chain = ["gaussian_noise", "impulse_noise", "enhance_contrast"]
 if "chain_cifar" in which:
     fr = torch.from_numpy(np.stack([synth(i, 32, 32) for i in range(1024)])).cuda()
