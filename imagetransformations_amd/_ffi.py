@@ -129,6 +129,10 @@ SIGNATURES = {
     "imgxf_jpeg_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_u8": [_VP, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                              C.c_void_p],
+    "imgxf_jpeg_encode_list_layout_host": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_encode_list_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                  C.c_size_t, C.c_void_p],
     "imgxf_jpeg_workspace_bytes_ex": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_optimal_tables": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "imgxf_jpeg_encode_ex_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
@@ -175,6 +179,26 @@ class JpegTables(C.Structure):
     """struct imgxf_jpeg_tables (include/imgxf.h)."""
     _fields_ = [("quant", (C.c_uint16 * 64) * 2), ("dc_code", (C.c_uint16 * 16) * 2), ("dc_len", (C.c_uint8 * 16) * 2),
                 ("ac_code", (C.c_uint16 * 256) * 2), ("ac_len", (C.c_uint8 * 256) * 2)]
+
+
+JPEG_LIST_STAGES, JPEG_LIST_AREAS = 5, 8
+
+
+class JpegListHeader(C.Structure):
+    """struct imgxf_jpeg_list_header (include/imgxf.h)."""
+    _fields_ = [("n_frames", C.c_int32), ("frames_off", C.c_int32), ("total_bytes", C.c_int32), ("pad_", C.c_int32),
+                ("n_units", C.c_int32 * JPEG_LIST_STAGES), ("units_off", C.c_int32 * JPEG_LIST_STAGES),
+                ("area_off", C.c_uint64 * JPEG_LIST_AREAS), ("workspace_bytes", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+class JpegListFrame(C.Structure):
+    """struct imgxf_jpeg_list_frame (include/imgxf.h)."""
+    _fields_ = [("data", C.c_uint64), ("row_stride", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
+                ("mw", C.c_int32), ("mh", C.c_int32), ("bw", C.c_int32), ("bh", C.c_int32), ("nblk", C.c_int32),
+                ("nparts_blk", C.c_int32), ("nchunks", C.c_int32), ("nparts_chunk", C.c_int32), ("chunk_groups", C.c_int32),
+                ("pad_", C.c_int32), ("stream_words", C.c_int64),
+                ("coef_off", C.c_int64), ("blk_off", C.c_int64), ("part_off", C.c_int64), ("stream_off", C.c_int64),
+                ("cnt_off", C.c_int64), ("out_off", C.c_int64), ("out_cap", C.c_int64)]
 
 
 class JpegEncParams(C.Structure):

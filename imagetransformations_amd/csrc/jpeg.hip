@@ -20,8 +20,11 @@
 //
 // Integer arithmetic throughout: bit-identical to the library (tests/test_gpu_jpeg.py compares whole files).
 #include "imgxf_common.h"
+#include <stddef.h>
 #include <string.h>
+#include <new>
 #include <type_traits>
+#include <vector>
 
 namespace imgxf {
 
@@ -44,6 +47,33 @@ struct JpegHeader {
     u8 b[1024];
     int len;
 };
+
+// Where a workgroup works.  A uniform batch (JpegUniform): frame blockIdx.y (blockIdx.z in the transform), item blockIdx.x,
+// every per-frame area at the uniform stride the kernel's arguments state.  A list of frames of different sizes (JpegList,
+// imgxf_jpeg_encode_list_u8): entry blockIdx.x of the stage's unit table names the frame and the item, and the frame's
+// record holds what the uniform arguments hold for a batch — geometry, the frame's offset in every area, its stream and
+// chunk counts, its slot of the output.  One copy of each stage serves both: W is the stage's last template parameter.
+struct JpegUniform {
+    static constexpr bool LIST = false;
+};
+struct JpegList {
+    static constexpr bool LIST = true;
+    const imgxf_jpeg_list_frame* fr;
+    const imgxf_jpeg_list_unit* units;       // the stage's table (imgxf_jpeg_list_header::units_off)
+    int which;                               // the scan kernels: 0 the frame's blocks, 1 its chunks
+    int sof;                                 // the stuffing kernel: where the header's SOF height / width bytes are
+};
+template <class W>
+__device__ __forceinline__ const imgxf_jpeg_list_frame* jpeg_where(const W& wh, int& f, int& bx) {
+    if constexpr (W::LIST) {
+        const imgxf_jpeg_list_unit u = wh.units[blockIdx.x];
+        f = u.frame;
+        bx = u.item;
+        return wh.fr + f;
+    } else {
+        return nullptr;
+    }
+}
 
 // jfdctint.c, one 1-D pass over eight values (FIRST: the row pass, results scaled up by 4).  Same sums as the library's
 // (32-bit two's complement, any association); the rounding constant of DESCALE rides in the shared terms z1 / z5 so
@@ -108,17 +138,35 @@ constexpr int zz(int i) {
 // One workgroup: rows y0 .. y0+15, columns x0 .. x0+16·JM-1 of frame f.  All threads stage and convert, then one thread
 // per block transforms — wave 0 the 64 luminance blocks, half of wave 1 the 32 chrominance blocks, so that the
 // quantiser table is wave-uniform (scalar loads).
+// (a list's unit: item = strip | MCU row << 16; the `fast` test then takes the frame's own address and stride)
+template <class W>
 __global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __restrict__ coef, int64_t coef_fs,
                                                              int16_t* __restrict__ dcs, uint16_t* __restrict__ acbits, int nblk,
-                                                             int mw, int bw, int bh, JpegQuant q) {
+                                                             int mw, int bw, int bh, JpegQuant q, W wh) {
     __shared__ __attribute__((aligned(4))) u8 slen[2][256];
     __shared__ __attribute__((aligned(16))) u8 rgb[16][JPX * 3];
     __shared__ __attribute__((aligned(16))) u8 yp[16][JPX + 8];
     __shared__ __attribute__((aligned(16))) u8 cp[2][8][JPX / 2 + 8];
-    const int tid = threadIdx.x, f = blockIdx.z, my = blockIdx.y, mx0 = blockIdx.x * JM;
+    const int tid = threadIdx.x;
+    int f = blockIdx.z, my = blockIdx.y, mx0 = blockIdx.x * JM, item = 0;
+    const u8* base;
+    int64_t coef_o, blk_o;
+    if constexpr (W::LIST) {
+        const imgxf_jpeg_list_frame* fr = jpeg_where(wh, f, item);
+        my = item >> 16;
+        mx0 = (item & 0xffff) * JM;
+        base = (const u8*)fr->data;
+        s.rs = fr->row_stride; s.h = fr->h; s.w = fr->w;
+        mw = fr->mw; bw = fr->bw; bh = fr->bh;
+        coef_o = fr->coef_off;
+        blk_o = fr->blk_off;
+    } else {
+        base = s.p + (int64_t)f * s.fs;
+        coef_o = (int64_t)f * coef_fs;
+        blk_o = (int64_t)f * nblk;
+    }
     const int y0 = my * 16, x0 = mx0 * 16;
     if (tid < 128) ((u32*)slen)[tid] = ((const u32*)q.aclen)[tid];
-    const u8* base = s.p + (int64_t)f * s.fs;
     const bool fast = (x0 + JPX <= s.w) && (((uintptr_t)base | (uintptr_t)s.rs) & 15) == 0;
     constexpr int CPR = JPX * 3 / 16;                          // 16-byte pieces per row
     for (int i = tid; i < 16 * CPR; i += JT) {
@@ -234,13 +282,13 @@ __global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __r
         }
         u32 bits = (acc & 0xffff) + (acc >> 16) * lt[0xF0];
         if (run16) bits += lt[0];
-        acbits[(int64_t)f * nblk + blk] = (uint16_t)bits;
-        dcs[(int64_t)f * nblk + blk] = (int16_t)d[0];
+        acbits[blk_o + blk] = (uint16_t)bits;
+        dcs[blk_o + blk] = (int16_t)d[0];
     }
     // zigzag order, eight coefficients (16 bytes) at a time, interleaved over groups of 64 blocks: piece g of block b
     // at 16-byte slot (b >> 6)·512 + g·64 + (b & 63), so that the emit kernel's one-thread-per-block walk reads
     // consecutive 16-byte pieces across a wave
-    uint4* out = (uint4*)(coef + (int64_t)f * coef_fs) + (blk >> 6) * 512 + (blk & 63);
+    uint4* out = (uint4*)(coef + coef_o) + (blk >> 6) * 512 + (blk & 63);
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
         uint4 v;
@@ -364,21 +412,25 @@ __device__ __forceinline__ void load_huff(u32 (*sdc)[16], u32 (*sac)[256], const
 
 // bits of every block: DC category code + magnitude bits + the AC bits (EOB for a dummy): the transform's count under
 // the call's tables or, with OPT, a walk of the block under the frame's own tables
-template <int L, bool OPT>
+template <int L, bool OPT, class W>
 __global__ __launch_bounds__(256) void jpeg_lens_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
                                                         const uint16_t* __restrict__ acbits, u32* __restrict__ lens, JpegGeom g,
-                                                        JpegHuff hf, const JpegHuff* __restrict__ fh) {
+                                                        JpegHuff hf, const JpegHuff* __restrict__ fh, W wh) {
     constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
     __shared__ u32 sdc[2][16];
     __shared__ u32 sac[2][256];
-    const int j = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    int f = blockIdx.y, bx = blockIdx.x;
+    const imgxf_jpeg_list_frame* fr = jpeg_where(wh, f, bx);
+    if constexpr (W::LIST) g = {fr->mw, fr->mh, fr->bw, fr->bh, fr->nblk};
+    const int j = bx * 256 + threadIdx.x;
     if (OPT) {
         load_huff<true>(sdc, sac, hf, fh, f);
         __syncthreads();
     }
     if (j >= g.nblk) return;
     const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
-    const int16_t* dd = dcs + (int64_t)f * g.nblk;
+    const int64_t blk_o = W::LIST ? fr->blk_off : (int64_t)f * g.nblk;
+    const int16_t* dd = dcs + blk_o;
     bool dummy;
     const int diff = block_dc<L>(dd, g, mcu, mx, my, k, dummy) - block_pred<L>(dd, g, mcu, mx, my, k);
     const int t = k >= NY ? 1 : 0;
@@ -388,15 +440,16 @@ __global__ __launch_bounds__(256) void jpeg_lens_kernel(const int16_t* __restric
         n += (OPT ? sac[t][0] : hf.ac[t][0]) >> 16;
     } else if (OPT) {
         const u32* la = sac[t];
-        ac_symbols((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63),
+        ac_symbols((const uint4*)(coef + (W::LIST ? fr->coef_off : (int64_t)f * coef_fs)) + (j >> 6) * 512 + (j & 63),
                    [&](u32 s, int, u32 size) { n += (la[s] >> 16) + size; });
     } else {
-        n += acbits[(int64_t)f * g.nblk + j];
+        n += acbits[blk_o + j];
     }
-    lens[(int64_t)f * g.nblk + j] = n;
+    lens[blk_o + j] = n;
 }
 
-// The span protocol of every emit kernel (sequential and progressive).  One thread per block; block j of a frame's nb
+// The span protocol of every emit kernel (sequential and progressive).  One thread per block (bx: the workgroup's index
+// among the frame's); block j of a frame's nb
 // blocks starts at bit offs[j] of the frame's stream gs (tb bits in all), so the bits of a workgroup's 256 blocks are one
 // contiguous span [offs[j0], offs[j0 + 256]).  When the span fits the JLW words of lbuf (LDS, declared by the kernel) the
 // codes are merged there (ds_or) and leave as coalesced stores, with global atomics only on the first and last word,
@@ -408,10 +461,10 @@ __global__ __launch_bounds__(256) void jpeg_lens_kernel(const int16_t* __restric
 // nothing is stored.  A stream over its capacity is left alone (the stuffing kernel reports it).  The barrier after the
 // zeroing also covers whatever the kernel staged in LDS before the call.
 template <typename Body>
-__device__ __forceinline__ void span_write(u32* lbuf, const u32* __restrict__ offs, int nb, u32 tb, u32* __restrict__ gs, int64_t fs_words,
-                                           Body&& body) {
+__device__ __forceinline__ void span_write(u32* lbuf, int bx, const u32* __restrict__ offs, int nb, u32 tb, u32* __restrict__ gs,
+                                           int64_t fs_words, Body&& body) {
     if (((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words) return;
-    const int j0 = blockIdx.x * 256, j = j0 + threadIdx.x, j1 = min(j0 + 256, nb);
+    const int j0 = bx * 256, j = j0 + threadIdx.x, j1 = min(j0 + 256, nb);
     const u32 sbit = offs[j0];
     const u32 ebit = j1 < nb ? offs[j1] : tb;
     const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
@@ -458,28 +511,34 @@ __device__ __forceinline__ void span_write(u32* lbuf, const u32* __restrict__ of
 
 // The sequential scan: every block's DC difference and AC symbols at the block's bit offset, under the call's tables or,
 // with OWN, the frame's own (optimize).
-template <int L, bool OWN>
+template <int L, bool OWN, class W>
 __global__ __launch_bounds__(256) void jpeg_emit_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
                                                         const u32* __restrict__ offs, u32* __restrict__ stream, int64_t stream_fs_words,
                                                         const u32* __restrict__ total_bits, JpegGeom g, JpegHuff hf,
-                                                        const JpegHuff* __restrict__ fh) {
+                                                        const JpegHuff* __restrict__ fh, W wh) {
     constexpr int NY = JLay<L>::NY, B = JLay<L>::B;
     __shared__ u32 sdc[2][16];
     __shared__ u32 sac[2][256];
     __shared__ u32 lbuf[JLW];
-    const int f = blockIdx.y;
+    int f = blockIdx.y, bx = blockIdx.x;
+    const imgxf_jpeg_list_frame* fr = jpeg_where(wh, f, bx);
+    if constexpr (W::LIST) {
+        g = {fr->mw, fr->mh, fr->bw, fr->bh, fr->nblk};
+        stream_fs_words = fr->stream_words;
+    }
     load_huff<OWN>(sdc, sac, hf, fh, f);
-    span_write(lbuf, offs + (int64_t)f * g.nblk, g.nblk, total_bits[f], stream + (int64_t)f * stream_fs_words, stream_fs_words,
+    span_write(lbuf, bx, offs + (W::LIST ? fr->blk_off : (int64_t)f * g.nblk), g.nblk, total_bits[f],
+               stream + (W::LIST ? fr->stream_off : (int64_t)f * stream_fs_words), stream_fs_words,
                [&](int j, auto&& put) {
         const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
-        const int16_t* dd = dcs + (int64_t)f * g.nblk;
+        const int16_t* dd = dcs + (W::LIST ? fr->blk_off : (int64_t)f * g.nblk);
         bool dummy;
         const int diff = block_dc<L>(dd, g, mcu, mx, my, k, dummy) - block_pred<L>(dd, g, mcu, mx, my, k);
         const u32 cat = dc_category(diff), e = sdc[k >= NY ? 1 : 0][cat];
         put(((e & 0xffff) << cat) | ((u32)(diff + (diff >> 31)) & ((1u << cat) - 1)), (e >> 16) + cat);
         const u32* ta = sac[k >= NY ? 1 : 0];
         if (!dummy) {
-            ac_symbols((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63), [&](u32 s, int c, u32 size) {
+            ac_symbols((const uint4*)(coef + (W::LIST ? fr->coef_off : (int64_t)f * coef_fs)) + (j >> 6) * 512 + (j & 63), [&](u32 s, int c, u32 size) {
                 const u32 e = ta[s];
                 put(((e & 0xffff) << size) | ((u32)(c + (c >> 31)) & ((1u << size) - 1)), (e >> 16) + size);
             });
@@ -513,22 +572,45 @@ __device__ __forceinline__ u32 wg_exclusive_scan(u32 v, u32* total) {          /
     return basev + x - v;
 }
 
+// A list's frame in the scan kernels: its blocks' or its chunks' row (wh.which) and its piece of the partial sums.
+template <class W>
+__device__ __forceinline__ void scan_where(const W& wh, int& f, int& bx, int64_t& row_o, int64_t& part_o, int& len, int& nparts,
+                                           int64_t fs, bool spine) {
+    if constexpr (W::LIST) {
+        const imgxf_jpeg_list_frame* fr = wh.fr + f;
+        if (!spine) fr = jpeg_where(wh, f, bx);
+        row_o = wh.which ? fr->cnt_off : fr->blk_off;
+        part_o = fr->part_off;
+        len = wh.which ? fr->nchunks : fr->nblk;
+        nparts = wh.which ? fr->nparts_chunk : fr->nparts_blk;
+    } else {
+        row_o = (int64_t)f * fs;
+        part_o = (int64_t)f * nparts;
+    }
+}
+
+template <class W>
 __global__ __launch_bounds__(256) void scan_partials_kernel(const u32* __restrict__ data, int64_t fs, int len, u32* __restrict__ part,
-                                                            int nparts) {
-    const int f = blockIdx.y;
-    const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-    const u32* p = data + (int64_t)f * fs;
+                                                            int nparts, W wh) {
+    int f = blockIdx.y, bx = blockIdx.x;
+    int64_t row_o, part_o;
+    scan_where(wh, f, bx, row_o, part_o, len, nparts, fs, false);
+    const int i0 = (bx * 256 + threadIdx.x) * 4;
+    const u32* p = data + row_o;
     u32 s = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) s += (i0 + e < len) ? p[i0 + e] : 0u;
     u32 tot;
     wg_exclusive_scan(s, &tot);
-    if (threadIdx.x == 0) part[(int64_t)f * nparts + blockIdx.x] = tot;
+    if (threadIdx.x == 0) part[part_o + bx] = tot;
 }
 
-__global__ __launch_bounds__(256) void scan_spine_kernel(u32* __restrict__ part, int nparts, u32* __restrict__ totals) {
-    const int f = blockIdx.x;
-    u32* p = part + (int64_t)f * nparts;
+template <class W>
+__global__ __launch_bounds__(256) void scan_spine_kernel(u32* __restrict__ part, int nparts, u32* __restrict__ totals, W wh) {
+    int f = blockIdx.x, bx = 0, len = 0;
+    int64_t row_o, part_o;
+    scan_where(wh, f, bx, row_o, part_o, len, nparts, 0, true);
+    u32* p = part + part_o;
     u32 carry = 0;
     for (int b = 0; b < nparts; b += 256) {
         const int i = b + threadIdx.x;
@@ -542,11 +624,14 @@ __global__ __launch_bounds__(256) void scan_spine_kernel(u32* __restrict__ part,
     if (threadIdx.x == 0) totals[f] = carry;
 }
 
+template <class W>
 __global__ __launch_bounds__(256) void scan_apply_kernel(u32* __restrict__ data, int64_t fs, int len, const u32* __restrict__ part,
-                                                         int nparts) {
-    const int f = blockIdx.y;
-    const int i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
-    u32* p = data + (int64_t)f * fs;
+                                                         int nparts, W wh) {
+    int f = blockIdx.y, bx = blockIdx.x;
+    int64_t row_o, part_o;
+    scan_where(wh, f, bx, row_o, part_o, len, nparts, fs, false);
+    const int i0 = (bx * 256 + threadIdx.x) * 4;
+    u32* p = data + row_o;
     u32 v[4], s = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -554,7 +639,7 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(u32* __restrict__ data,
         s += v[e];
     }
     u32 tot;
-    u32 ex = wg_exclusive_scan(s, &tot) + part[(int64_t)f * nparts + blockIdx.x];
+    u32 ex = wg_exclusive_scan(s, &tot) + part[part_o + bx];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (i0 + e < len) p[i0 + e] = ex;
@@ -564,9 +649,18 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(u32* __restrict__ data,
 
 static int scan_rows(u32* data, int64_t fs, int len, int n, u32* part, u32* totals, hipStream_t st) {
     const int nparts = (len + 1023) / 1024;
-    hipLaunchKernelGGL(scan_partials_kernel, dim3((unsigned)nparts, (unsigned)n), dim3(256), 0, st, data, fs, len, part, nparts);
-    hipLaunchKernelGGL(scan_spine_kernel, dim3((unsigned)n), dim3(256), 0, st, part, nparts, totals);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nparts, (unsigned)n), dim3(256), 0, st, data, fs, len, part, nparts);
+    const JpegUniform u;
+    hipLaunchKernelGGL(scan_partials_kernel<JpegUniform>, dim3((unsigned)nparts, (unsigned)n), dim3(256), 0, st, data, fs, len, part, nparts, u);
+    hipLaunchKernelGGL(scan_spine_kernel<JpegUniform>, dim3((unsigned)n), dim3(256), 0, st, part, nparts, totals, u);
+    hipLaunchKernelGGL(scan_apply_kernel<JpegUniform>, dim3((unsigned)nparts, (unsigned)n), dim3(256), 0, st, data, fs, len, part, nparts, u);
+    return launch_status();
+}
+
+// ... of a list: every frame's row of its own length (wh.which: blocks or chunks), n_units parts in all
+static int scan_rows_list(u32* data, int n, int n_units, u32* part, u32* totals, JpegList wh, hipStream_t st) {
+    hipLaunchKernelGGL(scan_partials_kernel<JpegList>, dim3((unsigned)n_units), dim3(256), 0, st, data, (int64_t)0, 0, part, 0, wh);
+    hipLaunchKernelGGL(scan_spine_kernel<JpegList>, dim3((unsigned)n), dim3(256), 0, st, part, 0, totals, wh);
+    hipLaunchKernelGGL(scan_apply_kernel<JpegList>, dim3((unsigned)n_units), dim3(256), 0, st, data, (int64_t)0, 0, part, 0, wh);
     return launch_status();
 }
 
@@ -575,18 +669,31 @@ static int scan_rows(u32* data, int64_t fs, int len, int n, u32* part, u32* tota
 // Before an emit kernel: the words span_write ORs into must start at zero.  A workgroup whose span is merged in LDS
 // touches only its first and last word that way (everything between is stored whole); a span too long for LDS is cleared
 // entirely.  offs: nb offsets per frame.
+template <class W>
 __global__ __launch_bounds__(256) void jpeg_zero_kernel(u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ offs,
-                                                        const u32* __restrict__ total_bits, int nb) {
-    const int f = blockIdx.y, j0 = blockIdx.x * 256;
+                                                        const u32* __restrict__ total_bits, int nb, W wh) {
+    int f = blockIdx.y, bx = blockIdx.x;
+    int64_t blk_o, stream_o;
+    if constexpr (W::LIST) {
+        const imgxf_jpeg_list_frame* fr = jpeg_where(wh, f, bx);
+        nb = fr->nblk;
+        fs_words = fr->stream_words;
+        blk_o = fr->blk_off;
+        stream_o = fr->stream_off;
+    } else {
+        blk_o = (int64_t)f * nb;
+        stream_o = (int64_t)f * fs_words;
+    }
+    const int j0 = bx * 256;
     const u32 tb = total_bits[f];
     if (((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words) return;
     const int j1 = min(j0 + 256, nb);
-    const u32 sbit = offs[(int64_t)f * nb + j0];
-    const u32 ebit = j1 < nb ? offs[(int64_t)f * nb + j1] : tb;
+    const u32 sbit = offs[blk_o + j0];
+    const u32 ebit = j1 < nb ? offs[blk_o + j1] : tb;
     const u32 wlo = sbit >> 5, nw = ((ebit + 31) >> 5) - wlo;
     if (nw == 0) return;      // an empty span: blocks inside a progressive scan's EOB run write no bits (in the sequential
                               // scan every block takes at least two); gs[nw - 1] would be the word before the span
-    u32* gs = stream + (int64_t)f * fs_words + wlo;
+    u32* gs = stream + stream_o + wlo;
     if (nw <= JLW) {
         if (threadIdx.x == 0) gs[0] = 0;
         if (threadIdx.x == 1) gs[nw - 1] = 0;
@@ -624,14 +731,35 @@ __device__ __forceinline__ u32 ff_bytes(u32 w) {                  // number of 0
     return __popc(t & 0x01010101u);
 }
 
+// A frame's stream, chunk counts and workgroups in the stuffing kernels (gdim: the workgroups that share the frame's chunks).
+template <class W>
+__device__ __forceinline__ void chunks_where(const W& wh, int& f, int& bx, int& gdim, int64_t& fs_words, int64_t& stream_o, int64_t& cnt_o,
+                                             int& nchunks, int64_t cnt_fs, const imgxf_jpeg_list_frame*& fr) {
+    fr = jpeg_where(wh, f, bx);
+    if constexpr (W::LIST) {
+        gdim = fr->chunk_groups;
+        fs_words = fr->stream_words;
+        stream_o = fr->stream_off;
+        cnt_o = fr->cnt_off;
+        nchunks = fr->nchunks;
+    } else {
+        stream_o = (int64_t)f * fs_words;
+        cnt_o = (int64_t)f * cnt_fs;
+    }
+}
+
+template <class W>
 __global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ total_bits,
-                                                           u32* __restrict__ cnt, int64_t cnt_fs, int nchunks) {
-    const int f = blockIdx.y;
+                                                           u32* __restrict__ cnt, int64_t cnt_fs, int nchunks, W wh) {
+    int f = blockIdx.y, bx = blockIdx.x, gdim = gridDim.x;
+    int64_t stream_o, cnt_o;
+    const imgxf_jpeg_list_frame* fr;
+    chunks_where(wh, f, bx, gdim, fs_words, stream_o, cnt_o, nchunks, cnt_fs, fr);
     const u32 tb = total_bits[f];
     const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
     const int64_t nbytes = over ? 0 : ((int64_t)tb + 7) >> 3;
-    const u32* w = stream + (int64_t)f * fs_words;
-    for (int ci = blockIdx.x * 256 + threadIdx.x; ci < nchunks; ci += gridDim.x * 256) {   // the capacity, mostly unused
+    const u32* w = stream + stream_o;
+    for (int ci = (u32)bx * 256 + threadIdx.x; ci < nchunks; ci += (u32)gdim * 256) {   // the capacity, mostly unused
         u32 c = 0;
         if ((int64_t)ci * JCHUNK < nbytes) {
             u32 ws[8];
@@ -639,7 +767,7 @@ __global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const u32* __restrict
 #pragma unroll
             for (int e = 0; e < 8; ++e) c += ff_bytes(ws[e]);
         }
-        cnt[(int64_t)f * cnt_fs + ci] = c;
+        cnt[cnt_o + ci] = c;
     }
 }
 
@@ -647,10 +775,11 @@ __global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const u32* __restrict
 // (8 KB of stream) per workgroup pass: every thread expands its chunk into LDS at its stuffed offset (byte writes), then
 // the workgroup copies its contiguous piece of the file out — whole dwords where the piece covers them, single bytes at
 // its two ends (the neighbouring workgroups own the rest of those dwords).  lb: 256 · 2 · JCHUNK + 8 bytes of LDS.
-__device__ __forceinline__ void stuff_chunks(u8* lb, const u32* __restrict__ w, const u32* __restrict__ cf, int nchunks, int64_t nbytes,
-                                             u32 tb, u32 nff, u8* __restrict__ data) {
+// Workgroup bx of the gdim that share the frame.
+__device__ __forceinline__ void stuff_chunks(u8* lb, int bx, int gdim, const u32* __restrict__ w, const u32* __restrict__ cf, int nchunks,
+                                             int64_t nbytes, u32 tb, u32 nff, u8* __restrict__ data) {
     const int nvc = (int)((nbytes + JCHUNK - 1) / JCHUNK);         // chunks that hold stream bytes
-    for (int c0 = blockIdx.x * 256; c0 < nvc; c0 += gridDim.x * 256) {
+    for (int c0 = bx * 256; c0 < nvc; c0 += gdim * 256) {
         const int ce = min(c0 + 256, nvc);
         const u32 pre0 = cf[c0];
         const u32 pre1 = ce < nchunks ? cf[ce] : nff;
@@ -689,24 +818,44 @@ __device__ __forceinline__ void stuff_chunks(u8* lb, const u32* __restrict__ w, 
 
 // The file with the call's tables: the host's header (SOI .. SOS), the stuffed stream, EOI; sizes[f] = 0xFFFFFFFF when
 // it does not fit.  (jpeg_stuff_scan_kernel with no tables and no SOS would write the same file; the default call keeps
-// this kernel, which reads no per-frame table state.)
+// this kernel, which reads no per-frame table state.)  A list's frames share the header but for the SOF segment's height
+// and width (big-endian, wh.sof .. wh.sof + 3), which the frame's record supplies; each has its own slot of `out`.
+template <class W>
 __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const u32* __restrict__ stream, int64_t fs_words, const u32* __restrict__ total_bits,
                                                          const u32* __restrict__ cnt, int64_t cnt_fs, int nchunks,
                                                          const u32* __restrict__ ff_total, u8* __restrict__ out, int64_t out_fs,
-                                                         u32* __restrict__ sizes, JpegHeader hd) {
+                                                         u32* __restrict__ sizes, JpegHeader hd, W wh) {
     __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
-    const int f = blockIdx.y;
+    int f = blockIdx.y, bx = blockIdx.x, gdim = gridDim.x;
+    int64_t stream_o, cnt_o, out_o;
+    const imgxf_jpeg_list_frame* fr;
+    chunks_where(wh, f, bx, gdim, fs_words, stream_o, cnt_o, nchunks, cnt_fs, fr);
+    u32 dims = 0;
+    if constexpr (W::LIST) {
+        out_o = fr->out_off;
+        out_fs = fr->out_cap;
+        dims = ((u32)fr->h << 16) | (u32)fr->w;
+    } else {
+        out_o = (int64_t)f * out_fs;
+    }
     const u32 tb = total_bits[f];
     const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
     const int64_t nbytes = ((int64_t)tb + 7) >> 3;
     const u32 nff = ff_total[f];
     const int64_t fsize = (int64_t)hd.len + nbytes + nff + 2;
     const bool fits = !over && fsize <= out_fs;
-    u8* o = out + (int64_t)f * out_fs;
-    if (blockIdx.x == 0) {
+    u8* o = out + out_o;
+    if (bx == 0) {
         if (threadIdx.x == 0) sizes[f] = fits ? (u32)fsize : 0xffffffffu;
         if (fits) {
-            for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
+            for (int i = threadIdx.x; i < hd.len; i += 256) {
+                u8 v = hd.b[i];
+                if constexpr (W::LIST) {
+                    const int d = i - wh.sof;
+                    if (d >= 0 && d < 4) v = (u8)(dims >> (24 - 8 * d));
+                }
+                o[i] = v;
+            }
             if (threadIdx.x == 0) {
                 o[fsize - 2] = 0xff;
                 o[fsize - 1] = 0xd9;
@@ -714,7 +863,7 @@ __global__ __launch_bounds__(256) void jpeg_stuff_kernel(const u32* __restrict__
         }
     }
     if (!fits) return;
-    stuff_chunks(lb, stream + (int64_t)f * fs_words, cnt + (int64_t)f * cnt_fs, nchunks, nbytes, tb, nff, o + hd.len);
+    stuff_chunks(lb, bx, gdim, stream + stream_o, cnt + cnt_o, nchunks, nbytes, tb, nff, o + hd.len);
 }
 
 // ---- per-frame tables and the scan header (optimize, progressive) ---------------------------------------------------
@@ -801,7 +950,7 @@ __global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restr
         }
     }
     if (status) return;
-    stuff_chunks(lb, stream + (int64_t)f * fs_words, cnt + (int64_t)f * cnt_fs, nchunks, nbytes, tb, nff, o + base + hlen);
+    stuff_chunks(lb, blockIdx.x, gridDim.x, stream + (int64_t)f * fs_words, cnt + (int64_t)f * cnt_fs, nchunks, nbytes, tb, nff, o + base + hlen);
 }
 
 // ---- host side: workspace, preparation, dispatch ---------------------------------------------------------------------
@@ -939,6 +1088,27 @@ struct JpegJob {
     int64_t out_fs;
 };
 
+// the call's tables and header as the kernels take them
+static int jpeg_prepare_tables(JpegJob& J, const imgxf_jpeg_tables* tables, int ncomp, const uint8_t* header, int header_bytes) {
+    memset(&J.q, 0, sizeof(J.q));
+    for (int t = 0; t < (ncomp == 1 ? 1 : 2); ++t)             // grayscale: table 0 only
+        for (int i = 0; i < 64; ++i) {
+            const u32 qv = tables->quant[t][i];
+            if (qv < 1 || qv > 255 || !quant_entry(qv, &J.q.m[t][i], &J.q.half[t][i])) return IMGXF_ERR_ARG;
+        }
+    for (int t = 0; t < 2; ++t) {
+        for (int i = 0; i < 16; ++i) J.hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
+        for (int i = 0; i < 256; ++i) {
+            J.hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
+            J.q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));    // code + magnitude bits of the symbol
+        }
+    }
+    memset(&J.hd, 0, sizeof(J.hd));
+    memcpy(J.hd.b, header, (size_t)header_bytes);
+    J.hd.len = header_bytes;
+    return IMGXF_OK;
+}
+
 static int jpeg_prepare(JpegJob& J, const imgxf_view* src, const imgxf_jpeg_enc_params* params, bool prog, const imgxf_jpeg_tables* tables,
                         const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride, uint32_t* sizes, void* workspace,
                         size_t workspace_bytes, void* stream) {
@@ -963,22 +1133,7 @@ static int jpeg_prepare(JpegJob& J, const imgxf_view* src, const imgxf_jpeg_enc_
     // bit offsets are 32-bit: no block takes more than 2048 bits in one scan (the widest, a progressive first scan over
     // 1..63 at Al = 1: 63 symbols of <= 16 + 10 bits, 3 ZRLs, one EOBRUN of 16 + 14 bits)
     if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;
-    memset(&J.q, 0, sizeof(J.q));
-    for (int t = 0; t < (p.ncomp == 1 ? 1 : 2); ++t)           // grayscale: table 0 only
-        for (int i = 0; i < 64; ++i) {
-            const u32 qv = tables->quant[t][i];
-            if (qv < 1 || qv > 255 || !quant_entry(qv, &J.q.m[t][i], &J.q.half[t][i])) return IMGXF_ERR_ARG;
-        }
-    for (int t = 0; t < 2; ++t) {
-        for (int i = 0; i < 16; ++i) J.hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
-        for (int i = 0; i < 256; ++i) {
-            J.hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
-            J.q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));    // code + magnitude bits of the symbol
-        }
-    }
-    memset(&J.hd, 0, sizeof(J.hd));
-    memcpy(J.hd.b, header, (size_t)header_bytes);
-    J.hd.len = header_bytes;
+    IMGXF_CHECK(jpeg_prepare_tables(J, tables, p.ncomp, header, header_bytes));
     J.s = make_view(src);
     J.n = J.s.n;
     J.st = (hipStream_t)stream;
@@ -1014,16 +1169,17 @@ static int launch_stuff(const JpegJob& J, const JpScanHdr* sh, int si, bool last
     const JpegLayout& L = J.L;
     const unsigned cwg = (unsigned)((L.nchunks + 255) / 256);
     const dim3 cgrid(cwg < 256u ? cwg : 256u, (unsigned)J.n);         // grid-stride over the capacity
-    hipLaunchKernelGGL(jpeg_ffcount_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits, J.cnt,
-                       (int64_t)L.nchunks, L.nchunks);
+    hipLaunchKernelGGL(jpeg_ffcount_kernel<JpegUniform>, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words,
+                       (const u32*)J.tot_bits, J.cnt, (int64_t)L.nchunks, L.nchunks, JpegUniform{});
     IMGXF_CHECK(scan_rows(J.cnt, L.nchunks, L.nchunks, J.n, J.part, J.tot_ff, J.st));
     if (sh)
         hipLaunchKernelGGL(jpeg_stuff_scan_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits,
                            (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs, J.pos, si, last, J.sizes,
                            J.hd, (const JpegDht*)J.dht, *sh);
     else
-        hipLaunchKernelGGL(jpeg_stuff_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits,
-                           (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs, J.sizes, J.hd);
+        hipLaunchKernelGGL(jpeg_stuff_kernel<JpegUniform>, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words,
+                           (const u32*)J.tot_bits, (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs,
+                           J.sizes, J.hd, JpegUniform{});
     return launch_status();
 }
 
@@ -1050,21 +1206,21 @@ static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* p
             hipLaunchKernelGGL(jpeg_gather_kernel<L>, bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, J.g, J.sym);
             hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(L == JLGRAY ? 2u : 4u, (unsigned)J.n), dim3(256), 0, J.st, (const u32*)J.sym, J.fh,
                                J.dht);
-            hipLaunchKernelGGL((jpeg_lens_kernel<L, true>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const uint16_t*)J.acb, J.lens,
-                               J.g, J.hf, fh);
+            hipLaunchKernelGGL((jpeg_lens_kernel<L, true, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs,
+                               (const uint16_t*)J.acb, J.lens, J.g, J.hf, fh, JpegUniform{});
         } else {
-            hipLaunchKernelGGL((jpeg_lens_kernel<L, false>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const uint16_t*)J.acb, J.lens,
-                               J.g, J.hf, fh);
+            hipLaunchKernelGGL((jpeg_lens_kernel<L, false, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs,
+                               (const uint16_t*)J.acb, J.lens, J.g, J.hf, fh, JpegUniform{});
         }
         IMGXF_CHECK(scan_rows(J.lens, J.g.nblk, J.g.nblk, J.n, J.part, J.tot_bits, J.st));
-        hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, J.st, J.ustream, J.L.stream_words, (const u32*)J.lens,
-                           (const u32*)J.tot_bits, J.g.nblk);
+        hipLaunchKernelGGL(jpeg_zero_kernel<JpegUniform>, bgrid, dim3(256), 0, J.st, J.ustream, J.L.stream_words, (const u32*)J.lens,
+                           (const u32*)J.tot_bits, J.g.nblk, JpegUniform{});
         if (J.opt)
-            hipLaunchKernelGGL((jpeg_emit_kernel<L, true>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens, J.ustream,
-                               J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh);
+            hipLaunchKernelGGL((jpeg_emit_kernel<L, true, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens,
+                               J.ustream, J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh, JpegUniform{});
         else
-            hipLaunchKernelGGL((jpeg_emit_kernel<L, false>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens, J.ustream,
-                               J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh);
+            hipLaunchKernelGGL((jpeg_emit_kernel<L, false, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens,
+                               J.ustream, J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh, JpegUniform{});
         if (!J.opt) return launch_stuff(J, nullptr, 0, true);
         JpScanHdr sh;                                          // one scan over all components (jcmarker.c emit_sos)
         memset(&sh, 0, sizeof(sh));
@@ -1077,9 +1233,226 @@ static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* p
     });
 }
 
+// ---- a list of frames of different sizes ------------------------------------------------------------------------------
+
+constexpr int JLIST_MAX_FRAMES = 1 << 20;
+static_assert(sizeof(imgxf_jpeg_list_header) == 136 && sizeof(imgxf_jpeg_list_frame) == 128 && sizeof(imgxf_jpeg_list_unit) == 8,
+              "include/imgxf.h documents these records");
+
+static inline int list_stage_units(const imgxf_jpeg_list_frame& f, int stage) {
+    switch (stage) {
+    case 0: return ((f.mw + JM - 1) / JM) * f.mh;
+    case 1: return (f.nblk + 255) / 256;
+    case 2: return f.nparts_blk;
+    case 3: return f.chunk_groups;
+    default: return f.nparts_chunk;
+    }
+}
+
+// The block of a list: get(i, h, w, cap) states frame i.  Every frame's geometry and stream capacity are what
+// jpeg_layout gives a batch of one such frame, and its piece of every area is at most that batch's (256-byte aligned)
+// area, so the workspace stays within the sum of the single-frame workspaces.  block == nullptr: the sizes alone.
+template <typename Get>
+static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_jpeg_list_header* out_hd) {
+    if (n < 0 || n > JLIST_MAX_FRAMES) return IMGXF_ERR_SHAPE;
+    imgxf_jpeg_list_header hd;
+    memset(&hd, 0, sizeof(hd));
+    hd.n_frames = n;
+    hd.frames_off = (int32_t)sizeof(imgxf_jpeg_list_header);
+    std::vector<imgxf_jpeg_list_frame> fr((size_t)n);
+    size_t area[IMGXF_JPEG_LIST_AREAS] = {0};                // bytes so far: coef, dcs, acb, lens, part, tot, stream, cnt
+    size_t units[IMGXF_JPEG_LIST_STAGES] = {0};
+    size_t out = 0;
+    for (int i = 0; i < n; ++i) {
+        int h, w;
+        uint64_t cap;
+        get(i, h, w, cap);
+        if (h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
+        if (cap < 1024 + 2 || cap > ((uint64_t)1 << 31)) return IMGXF_ERR_ARG;
+        const JpegLayout L = jpeg_layout(JL420, false, false, 1, h, w, (size_t)cap);
+        if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;      // 32-bit bit offsets, per frame
+        imgxf_jpeg_list_frame& f = fr[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        f.h = h; f.w = w;
+        f.mw = L.mw; f.mh = L.mh; f.bw = L.bw; f.bh = L.bh; f.nblk = L.nblk;
+        f.nparts_blk = L.nparts_blk; f.nchunks = L.nchunks; f.nparts_chunk = L.nparts_chunk;
+        const int cwg = (L.nchunks + 255) / 256;
+        f.chunk_groups = cwg < 256 ? cwg : 256;              // grid-stride over the capacity, as launch_stuff
+        f.stream_words = L.stream_words;
+        const size_t blk64 = (size_t)((L.nblk + 63) / 64) * 64;
+        f.coef_off = (int64_t)(area[0] / 2);
+        f.blk_off = (int64_t)(area[3] / 4);
+        f.part_off = (int64_t)(area[4] / 4);
+        f.stream_off = (int64_t)(area[6] / 4);
+        f.cnt_off = (int64_t)(area[7] / 4);
+        f.out_off = (int64_t)out;
+        f.out_cap = (int64_t)cap;
+        area[0] += blk64 * 128;
+        area[1] += blk64 * 2;
+        area[2] += blk64 * 2;
+        area[3] += blk64 * 4;
+        area[4] += (size_t)(L.nparts_blk > L.nparts_chunk ? L.nparts_blk : L.nparts_chunk) * 4;
+        area[6] += (size_t)L.stream_words * 4;
+        area[7] += (size_t)L.nchunks * 4;
+        out += ((size_t)cap + 15) & ~(size_t)15;
+        for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) units[s] += (size_t)list_stage_units(f, s);
+    }
+    area[5] = (size_t)n * 8;
+    size_t o = 0;
+    for (int a = 0; a < IMGXF_JPEG_LIST_AREAS; ++a) {
+        hd.area_off[a] = o;
+        o += al256(area[a]);
+    }
+    hd.workspace_bytes = o;
+    hd.out_bytes = out;
+    size_t pos = sizeof(imgxf_jpeg_list_header) + (size_t)n * sizeof(imgxf_jpeg_list_frame);
+    for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) {
+        if (units[s] > 0x7fffffffu || pos > 0x7fffffffu) return IMGXF_ERR_ARG;
+        hd.n_units[s] = (int32_t)units[s];
+        hd.units_off[s] = (int32_t)pos;
+        pos += units[s] * sizeof(imgxf_jpeg_list_unit);
+    }
+    if (pos > 0x7fffffffu) return IMGXF_ERR_ARG;
+    hd.total_bytes = (int32_t)pos;
+    *out_hd = hd;
+    if (!block) return IMGXF_OK;
+    if (block_cap < pos) return IMGXF_ERR_WORKSPACE;          // (*out_hd already states the size needed)
+    memcpy(block, &hd, sizeof(hd));
+    if (n) memcpy(block + hd.frames_off, fr.data(), (size_t)n * sizeof(imgxf_jpeg_list_frame));
+    for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) {
+        imgxf_jpeg_list_unit* u = (imgxf_jpeg_list_unit*)(block + hd.units_off[s]);
+        for (int i = 0; i < n; ++i) {
+            const imgxf_jpeg_list_frame& f = fr[(size_t)i];
+            if (s == 0) {
+                const int ngx = (f.mw + JM - 1) / JM;
+                for (int my = 0; my < f.mh; ++my)
+                    for (int gx = 0; gx < ngx; ++gx) *u++ = {i, gx | (my << 16)};
+            } else {
+                const int cnt = list_stage_units(f, s);
+                for (int k = 0; k < cnt; ++k) *u++ = {i, k};
+            }
+        }
+    }
+    return IMGXF_OK;
+}
+
+// where the SOF0 segment of a header (SOI, marker segments ...) states height and width; -1: none
+static int find_sof0(const uint8_t* h, int len) {
+    int pos = 2;
+    while (pos + 4 <= len && h[pos] == 0xff) {
+        const int m = h[pos + 1], seg = (h[pos + 2] << 8) | h[pos + 3];
+        if (m == 0xc0) return pos + 9 <= len ? pos + 5 : -1;
+        if (m == 0xda) break;
+        pos += 2 + seg;
+    }
+    return -1;
+}
+
 } // namespace imgxf
 
 using namespace imgxf;
+
+IMGXF_API int imgxf_jpeg_encode_list_layout_host(const int32_t* sizes, const uint64_t* capacities, int n, void* block, size_t block_cap,
+                                                 size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes) {
+    if (!block_bytes || !workspace_bytes || !out_bytes || (n > 0 && (!sizes || !capacities))) return IMGXF_ERR_NULL;
+    imgxf_jpeg_list_header hd;
+    // the sizes first, so that a block that is too small still learns them
+    const auto get = [&](int i, int& h, int& w, uint64_t& cap) { h = sizes[2 * i]; w = sizes[2 * i + 1]; cap = capacities[i]; };
+    int rc;
+    try {
+        rc = jpeg_list_build(n, get, (u8*)block, block_cap, &hd);
+    } catch (const std::bad_alloc&) {
+        return IMGXF_ERR_WORKSPACE;
+    }
+    if (rc != IMGXF_OK && rc != IMGXF_ERR_WORKSPACE) return rc;
+    *block_bytes = (size_t)hd.total_bytes;                       // (a block that is too small still learns the sizes)
+    *workspace_bytes = (size_t)hd.workspace_bytes;
+    *out_bytes = (size_t)hd.out_bytes;
+    return rc;
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_tables* tables,
+                                        const uint8_t* header, int header_bytes, uint8_t* out, size_t out_bytes, uint32_t* sizes,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!block_host || !tables || !header) return IMGXF_ERR_NULL;
+    const u8* hb = (const u8*)block_host;
+    imgxf_jpeg_list_header hd;
+    memcpy(&hd, hb, sizeof(hd));
+    const int n = hd.n_frames;
+    if (n < 0 || n > JLIST_MAX_FRAMES) return IMGXF_ERR_SHAPE;
+    if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
+    if (hd.frames_off != (int32_t)sizeof(imgxf_jpeg_list_header) ||
+        (int64_t)hd.total_bytes < (int64_t)hd.frames_off + (int64_t)n * (int64_t)sizeof(imgxf_jpeg_list_frame))
+        return IMGXF_ERR_ARG;
+    if (n == 0) return IMGXF_OK;
+    // the records bound every address the kernels form: each is checked, then the whole block against the one the
+    // layout function writes for these frames
+    const imgxf_jpeg_list_frame* frames = (const imgxf_jpeg_list_frame*)(hb + hd.frames_off);
+    for (int i = 0; i < n; ++i) {
+        const imgxf_jpeg_list_frame& f = frames[i];
+        if (!f.data) return IMGXF_ERR_NULL;
+        if (f.h < 1 || f.w < 1 || f.h > 32767 || f.w > 32767 || f.row_stride < (int64_t)f.w * 3) return IMGXF_ERR_SHAPE;
+        if (f.out_cap < (int64_t)header_bytes + 2) return IMGXF_ERR_ARG;
+    }
+    imgxf_jpeg_list_header rhd;
+    const auto get = [&](int i, int& h, int& w, uint64_t& cap) { h = frames[i].h; w = frames[i].w; cap = (uint64_t)frames[i].out_cap; };
+    std::vector<u8> ref;
+    try {
+        ref.resize((size_t)hd.total_bytes);
+        const int rc = jpeg_list_build(n, get, ref.data(), ref.size(), &rhd);   // one build: the block limit is IMGXF_ERR_SHAPE,
+        if (rc == IMGXF_ERR_WORKSPACE) return IMGXF_ERR_ARG;                  // a block of another size is not this layout
+        IMGXF_CHECK(rc);
+    } catch (const std::bad_alloc&) {
+        return IMGXF_ERR_WORKSPACE;
+    }
+    if (memcmp(&rhd, &hd, sizeof(hd)) != 0) return IMGXF_ERR_ARG;
+    const imgxf_jpeg_list_frame* rf = (const imgxf_jpeg_list_frame*)(ref.data() + hd.frames_off);
+    constexpr size_t given = offsetof(imgxf_jpeg_list_frame, h);            // data, row_stride: the caller's
+    for (int i = 0; i < n; ++i)
+        if (memcmp((const u8*)&rf[i] + given, (const u8*)&frames[i] + given, sizeof(imgxf_jpeg_list_frame) - given) != 0) return IMGXF_ERR_ARG;
+    const size_t units0 = (size_t)hd.units_off[0];
+    if (memcmp(ref.data() + units0, hb + units0, (size_t)hd.total_bytes - units0) != 0) return IMGXF_ERR_ARG;
+    if (!block_dev || !out || !sizes) return IMGXF_ERR_NULL;
+    if (((uintptr_t)block_dev) & 7) return IMGXF_ERR_ARG;
+    if (!workspace || workspace_bytes < hd.workspace_bytes || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
+    if (out_bytes < hd.out_bytes || (((uintptr_t)out) & 15)) return IMGXF_ERR_WORKSPACE;
+    JpegJob J;
+    IMGXF_CHECK(jpeg_prepare_tables(J, tables, 3, header, header_bytes));
+    const int sof = find_sof0(header, header_bytes);
+    if (sof < 0) return IMGXF_ERR_ARG;
+
+    hipStream_t st = (hipStream_t)stream;
+    const u8* db = (const u8*)block_dev;
+    u8* ws = (u8*)workspace;
+    int16_t* coef = (int16_t*)(ws + hd.area_off[0]);
+    int16_t* dcs = (int16_t*)(ws + hd.area_off[1]);
+    uint16_t* acb = (uint16_t*)(ws + hd.area_off[2]);
+    u32* lens = (u32*)(ws + hd.area_off[3]);
+    u32* part = (u32*)(ws + hd.area_off[4]);
+    u32* tot_bits = (u32*)(ws + hd.area_off[5]);
+    u32* tot_ff = tot_bits + n;
+    u32* ustream = (u32*)(ws + hd.area_off[6]);
+    u32* cnt = (u32*)(ws + hd.area_off[7]);
+    const auto where = [&](int stage, int which) {
+        return JpegList{(const imgxf_jpeg_list_frame*)(db + hd.frames_off), (const imgxf_jpeg_list_unit*)(db + hd.units_off[stage]), which, sof};
+    };
+    const auto grid = [&](int stage) { return dim3((unsigned)hd.n_units[stage]); };
+    const JpegGeom g0 = {0, 0, 0, 0, 0};                       // the uniform arguments: unused, the records state them
+    const int64_t z = 0;
+    hipLaunchKernelGGL(jpeg_transform_kernel<JpegList>, grid(0), dim3(JT), 0, st, View{}, coef, z, dcs, acb, 0, 0, 0, 0, J.q, where(0, 0));
+    hipLaunchKernelGGL((jpeg_lens_kernel<JL420, false, JpegList>), grid(1), dim3(256), 0, st, (const int16_t*)coef, z, (const int16_t*)dcs,
+                       (const uint16_t*)acb, lens, g0, J.hf, (const JpegHuff*)nullptr, where(1, 0));
+    IMGXF_CHECK(scan_rows_list(lens, n, hd.n_units[2], part, tot_bits, where(2, 0), st));
+    hipLaunchKernelGGL(jpeg_zero_kernel<JpegList>, grid(1), dim3(256), 0, st, ustream, z, (const u32*)lens, (const u32*)tot_bits, 0, where(1, 0));
+    hipLaunchKernelGGL((jpeg_emit_kernel<JL420, false, JpegList>), grid(1), dim3(256), 0, st, (const int16_t*)coef, z, (const int16_t*)dcs,
+                       (const u32*)lens, ustream, z, (const u32*)tot_bits, g0, J.hf, (const JpegHuff*)nullptr, where(1, 0));
+    hipLaunchKernelGGL(jpeg_ffcount_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits, cnt, z, 0,
+                       where(3, 0));
+    IMGXF_CHECK(scan_rows_list(cnt, n, hd.n_units[4], part, tot_ff, where(4, 1), st));
+    hipLaunchKernelGGL(jpeg_stuff_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits, (const u32*)cnt, z,
+                       0, (const u32*)tot_ff, out, z, sizes, J.hd, where(3, 0));
+    return launch_status();
+}
 
 IMGXF_API int imgxf_jpeg_workspace_bytes(int n, int h, int w, size_t out_frame_stride, size_t* bytes) {
     if (!bytes) return IMGXF_ERR_NULL;

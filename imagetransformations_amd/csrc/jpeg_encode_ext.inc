@@ -334,8 +334,8 @@ template <int L>
 static void launch_transform(const JpegJob& J) {
     const JpegLayout& G = J.L;
     if constexpr (L == JL420) {
-        hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((G.mw + JM - 1) / JM), (unsigned)G.mh, (unsigned)J.n), dim3(JT), 0, J.st,
-                           J.s, J.coef, J.coef_fs, J.dcs, J.acb, G.nblk, G.mw, G.bw, G.bh, J.q);
+        hipLaunchKernelGGL(jpeg_transform_kernel<JpegUniform>, dim3((unsigned)((G.mw + JM - 1) / JM), (unsigned)G.mh, (unsigned)J.n), dim3(JT),
+                           0, J.st, J.s, J.coef, J.coef_fs, J.dcs, J.acb, G.nblk, G.mw, G.bw, G.bh, J.q, JpegUniform{});
     } else {
         const int per = JXP / JLay<L>::MW;                     // MCUs per workgroup strip
         hipLaunchKernelGGL(jpeg_transform_ex_kernel<L>, dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)J.n),

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void jprog_emit_kernel(const int16_t* __restri
     __shared__ u32 lbuf[JLW];
     const int f = blockIdx.y;
     jp_load_tables<L, K>(sdc, sac, fh, f, sc);
-    span_write(lbuf, offs + (int64_t)f * sc.nb, sc.nb, total_bits[f], stream + (int64_t)f * stream_fs_words, stream_fs_words,
+    span_write(lbuf, blockIdx.x, offs + (int64_t)f * sc.nb, sc.nb, total_bits[f], stream + (int64_t)f * stream_fs_words, stream_fs_words,
                [&](int b, auto&& put) { jp_block_codes<L, K>(coef, coef_fs, dcs, runlen, g, sc, f, b, sdc, sac, put); });
 }
 
@@ -340,7 +340,8 @@ static int launch_prog_scan(const JpegJob& a, const JpScan& sc, const JpScanHdr&
     hipLaunchKernelGGL((jprog_lens_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, a.lens, a.g, sc,
                        (const JpegHuff*)a.fh);
     IMGXF_CHECK(scan_rows(a.lens, sc.nb, sc.nb, a.n, a.part, a.tot_bits, st));
-    hipLaunchKernelGGL(jpeg_zero_kernel, bgrid, dim3(256), 0, st, a.ustream, words, (const u32*)a.lens, (const u32*)a.tot_bits, sc.nb);
+    hipLaunchKernelGGL(jpeg_zero_kernel<JpegUniform>, bgrid, dim3(256), 0, st, a.ustream, words, (const u32*)a.lens, (const u32*)a.tot_bits,
+                       sc.nb, JpegUniform{});
     hipLaunchKernelGGL((jprog_emit_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, (const u32*)a.lens,
                        a.ustream, words, (const u32*)a.tot_bits, a.g, sc, (const JpegHuff*)a.fh);
     return launch_stuff(a, &sh, si, last);

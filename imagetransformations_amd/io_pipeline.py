@@ -161,22 +161,38 @@ def _write(data: bytes, path: str) -> None:
 
 
 def _save_on_device(named, out_dir: str, pool, saving: list):
-    """Encode the RGB images bound for *.jpg / *.jpeg files with the GPU writer, one batch per image size (the files are
-    Pillow's, byte for byte: tests/test_gpu_jpeg.py); queue the writes on `pool`; return what is left for Pillow
-    (other modes / formats, images carrying a comment Pillow would embed)."""
+    """Encode the RGB images bound for *.jpg / *.jpeg files with the GPU writer (the files are Pillow's, byte for byte:
+    tests/test_gpu_jpeg.py): all of them, whatever their sizes, go into ONE pinned block, cross PCIe in one copy and are
+    encoded as views of it by one `jpeg.encode_list_views` call (one size only: the batch writer, as
+    transformation._encode_held).  Queues the writes on `pool`; returns what is left for Pillow (other modes / formats,
+    images carrying a comment Pillow would embed)."""
     import numpy as np
     import torch
     from . import jpeg
-    groups, rest = {}, []
+    items, rest = [], []
     for name, img in named:
         if img.mode == "RGB" and name.lower().endswith((".jpg", ".jpeg")) and "comment" not in img.info and min(img.size) > 0:
-            groups.setdefault(img.size, []).append((name, img))
+            items.append((name, np.asarray(img)))
         else:
             rest.append((name, img))
-    for items in groups.values():
-        batch = torch.from_numpy(np.stack([np.asarray(img) for _, img in items])).cuda(non_blocking=True)
-        for (name, _), data in zip(items, jpeg.encode_views(batch)):
-            saving.append(pool.submit(_write, data, os.path.join(out_dir, name)))
+    if not items:
+        return rest
+    offs = [0]
+    for _, a in items:                                          # 16-byte aligned frames: the transform's wide loads
+        offs.append(offs[-1] + ((a.size + 15) & ~15))
+    pinned = torch.empty((offs[-1],), dtype=torch.uint8, pin_memory=True)
+    host = pinned.numpy()
+    for (_, a), o in zip(items, offs):
+        host[o:o + a.size] = a.reshape(-1)
+    block = pinned.cuda(non_blocking=True)
+    shapes = {a.shape for _, a in items}
+    if len(shapes) == 1:
+        h, w, _ = items[0][1].shape
+        files = jpeg.encode_views(torch.as_strided(block, (len(items), h, w, 3), (offs[1], 3 * w, 3, 1)))
+    else:
+        files = jpeg.encode_list_views([block[o:o + a.size].view(a.shape) for (_, a), o in zip(items, offs)])
+    for (name, _), data in zip(items, files):
+        saving.append(pool.submit(_write, data, os.path.join(out_dir, name)))
     return rest
 
 

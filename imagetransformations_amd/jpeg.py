@@ -8,8 +8,9 @@ from __future__ import annotations
 
 import ctypes
 from functools import lru_cache
-from typing import List
+from typing import List, Sequence
 
+import numpy as np
 import torch
 
 from . import _ffi as F
@@ -228,3 +229,133 @@ def encode_views(frames: torch.Tensor, quality: int = 75, capacity: int | None =
     torch.cuda.current_stream(frames.device).synchronize()
     host = memoryview(staged.numpy())                        # (keeps the pinned block alive)
     return [host[starts[i]:starts[i + 1]] for i in range(n)]
+
+
+# ---- a list of frames of different sizes: imgxf_jpeg_encode_list_u8 ---------------------------------------------------
+
+_LIST_FRAME = np.dtype([(name, np.dtype(ct)) for name, ct in F.JpegListFrame._fields_])
+assert _LIST_FRAME.itemsize == ctypes.sizeof(F.JpegListFrame)
+
+
+def list_layout(sizes: Sequence, capacities: Sequence[int]):
+    """imgxf_jpeg_encode_list_layout_host for frames of `sizes` [(h, w)] with `capacities` bytes per file → (block: uint8
+    array, header: F.JpegListHeader copy, frames: structured view INTO the block (data and row_stride are the caller's
+    to fill)).  Host only."""
+    n = len(sizes)
+    hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
+    caps = np.ascontiguousarray(np.asarray(capacities, dtype=np.uint64).reshape(n))
+    nb, nw, no = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    F.call("imgxf_jpeg_encode_list_layout_host", hw.ctypes.data, caps.ctypes.data, n, None, 0, ctypes.byref(nb), ctypes.byref(nw),
+           ctypes.byref(no))
+    block = np.zeros((nb.value,), dtype=np.uint8)
+    F.call("imgxf_jpeg_encode_list_layout_host", hw.ctypes.data, caps.ctypes.data, n, block.ctypes.data, block.nbytes, ctypes.byref(nb),
+           ctypes.byref(nw), ctypes.byref(no))
+    hd = F.JpegListHeader.from_buffer_copy(block[:ctypes.sizeof(F.JpegListHeader)].tobytes())
+    frames = block[hd.frames_off:hd.frames_off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
+    return block, hd, frames
+
+
+def _list_frames(frames) -> list:
+    """The frames of an `encode_list` call, checked: uint8 device tensors, [H, W, 3] or (grayscale) [H, W], none empty, one
+    device."""
+    frames = list(frames)
+    for t in frames:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[-1] != 3):
+            raise ValueError("jpeg.encode_list expects uint8 tensors [H, W, 3] (RGB) or [H, W] (grayscale)")
+        if t.numel() == 0:
+            raise ValueError("jpeg.encode_list: a frame has no pixels")
+    if any(not t.is_cuda for t in frames):
+        raise F.ImgxfError(F.ERR_NO_DEVICE, "frames must live on the GPU (no CPU fallback)", "jpeg.encode_list")
+    if len({t.device for t in frames}) > 1:
+        raise ValueError("jpeg.encode_list: the frames live on different devices")
+    return frames
+
+
+def _encode_list_device(frames: list, caps: list, quality: int):
+    """One imgxf_jpeg_encode_list_u8 call: → (out: uint8 device buffer, out_off: file f starts at out[out_off[f]], sizes:
+    list, 0xFFFFFFFF where file f exceeds caps[f])."""
+    dev = frames[0].device
+    block, hd, rec = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps)
+    kept = []                                        # (a copy made here must outlive the launch)
+    for i, t in enumerate(frames):
+        if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 3) or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+            t = t.contiguous()
+            kept.append(t)
+        rec["data"][i] = t.data_ptr()
+        rec["row_stride"][i] = t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1]
+    staged = torch.empty((block.nbytes,), dtype=torch.uint8, pin_memory=True)
+    staged.numpy()[:] = block
+    block_dev = staged.to(dev, non_blocking=True)
+    out = torch.empty((hd.out_bytes,), dtype=torch.uint8, device=dev)
+    sizes = torch.zeros((len(frames),), dtype=torch.int32, device=dev)
+    ws = torch.empty((hd.workspace_bytes,), dtype=torch.uint8, device=dev)
+    hdr = header(1, 1, quality)                      # the device writes each frame's height and width
+    with torch.cuda.device(dev):
+        F.call("imgxf_jpeg_encode_list_u8", block.ctypes.data, block_dev.data_ptr(), ctypes.addressof(tables(quality)), hdr, len(hdr),
+               out.data_ptr(), hd.out_bytes, sizes.data_ptr(), ws.data_ptr(), hd.workspace_bytes,
+               torch.cuda.current_stream(dev).cuda_stream)
+    lens = (sizes.to(torch.int64) & 0xFFFFFFFF).cpu().tolist()     # (synchronises: staged, kept and ws are done with)
+    return out, rec["out_off"].tolist(), lens
+
+
+def encode_list(frames: Sequence[torch.Tensor], quality: int = 75, *, subsampling=-1, optimize: bool = False,
+                progressive: bool = False) -> List[bytes]:
+    """`encode` for a sequence of frames of DIFFERENT sizes: file i equals Pillow's `Image.fromarray(frame_i).save(fp,
+    "JPEG", quality=quality, ...)`, byte for byte.  See `encode_list_views`."""
+    return [bytes(v) for v in encode_list_views(frames, quality, subsampling=subsampling, optimize=optimize, progressive=progressive)]
+
+
+def encode_list_views(frames: Sequence[torch.Tensor], quality: int = 75, *, subsampling=-1, optimize: bool = False,
+                      progressive: bool = False) -> List[memoryview]:
+    """`encode_list` without the last host copy (as `encode_views`): one memoryview per file into pinned staging memory.
+
+    frames: uint8 device tensors [H_i, W_i, 3], any row stride and byte offset (views are read in place while a pixel is
+    three consecutive bytes).  The default file (RGB, 4:2:0, Annex-K tables) of the whole list is ONE
+    imgxf_jpeg_encode_list_u8 call — a number of launches that does not depend on the frames or their sizes — with
+    `_capacities`' first-try capacity per frame; the frames that come back over capacity, and only those, are encoded
+    again in a second call with their retry capacity.  The files leave the device as one gathered copy.
+    Non-default files (`subsampling`, `optimize`, `progressive`, grayscale [H, W] frames) have no list kernels: those
+    frames are grouped by shape and each group goes through `encode_views` — the same bytes, one call per shape."""
+    frames = _list_frames(frames)
+    if not frames:
+        return []
+    sampling(subsampling, 3)                         # (refuses a bad spelling before any work)
+    optimize, progressive = bool(optimize), bool(progressive)
+    result: list = [None] * len(frames)
+    plain = sampling(subsampling, 3) == (2, 2) and not optimize and not progressive
+    default, groups = [], {}
+    for i, t in enumerate(frames):
+        if plain and t.dim() == 3:
+            default.append(i)
+        else:
+            groups.setdefault(tuple(t.shape), []).append(i)
+    for idx in groups.values():
+        views = encode_views(torch.stack([frames[i] for i in idx]), quality, subsampling=subsampling, optimize=optimize,
+                             progressive=progressive)
+        for i, v in zip(idx, views):
+            result[i] = v
+    if default:
+        todo = default
+        pieces: dict = {}                            # frame -> device view of exactly its file
+        for attempt in (0, 1):
+            caps = [_capacities(frames[i].shape[0], frames[i].shape[1], 3, (2, 2))[attempt] for i in todo]
+            out, offs, lens = _encode_list_device([frames[i] for i in todo], caps, quality)
+            for i, o, v in zip(todo, offs, lens):
+                if v != 0xFFFFFFFF:
+                    pieces[i] = out[o:o + v]
+            todo = [i for i, v in zip(todo, lens) if v == 0xFFFFFFFF]
+            if not todo:
+                break
+        if todo:
+            raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds the largest baseline stream", "jpeg.encode_list")
+        starts = [0]
+        for i in default:
+            starts.append(starts[-1] + pieces[i].numel())
+        packed = torch.cat([pieces[i] for i in default])          # one gather, one D2H (as encode_views)
+        staged = torch.empty((starts[-1],), dtype=torch.uint8, pin_memory=True)
+        staged.copy_(packed, non_blocking=True)
+        torch.cuda.current_stream(frames[0].device).synchronize()
+        host = memoryview(staged.numpy())
+        for k, i in enumerate(default):
+            result[i] = host[starts[k]:starts[k + 1]]
+    return result

@@ -439,19 +439,22 @@ def _batched_to_files(images, out_dir: str, tee: bool):
     photographs instead of three — cross PCIe.  Same draws, names, order and FILES as `apply_all_transformations_batched`
     with `output_dir` set (Pillow's encoder): tests/test_gpu_jpeg.py.  Returns [(file name, image or None)] in output order:
     `tee` also copies the results back as PIL images (apply_all_transformations_batched with `output_dir` set)."""
-    from . import jpeg
     os.makedirs(out_dir, exist_ok=True)
     # Groups are small (a handful of frames per transformation type and parameter) and a writer call costs ~0.4 ms of host
-    # time whatever its size: results are collected per frame shape and encoded SINK_FRAMES at a time.
-    held: dict = {}                                       # frame shape -> ([tensors], [names], frames)
+    # time whatever its size: the results of ALL shapes are held together, as the groups' own output tensors, and encoded
+    # SINK_FRAMES at a time by the list writer (`jpeg.encode_list_views`: one call, a fixed number of launches, whatever
+    # the mix of sizes).  A flush that holds a single shape keeps the batch writer (_encode_held).
+    held: list = [[], [], 0, 0]                           # [group outputs], [names], frames, bytes
     written: set = set()                                  # names the sink has put on disk
 
-    def flush(shape) -> None:
+    def flush() -> None:
         # (the files are written here, by this thread: a side thread pays a GIL hand-over per system call while this one
         # computes — 110 us per file against 19 us — and several threads queue on the directory's lock, 213 us per file)
-        tensors, names, _ = held.pop(shape)
-        big = tensors[0] if len(tensors) == 1 else torch.cat(tensors)
-        for name, data in zip(names, jpeg.encode_views(big)):
+        outs, names = held[0], held[1]
+        held[:] = [[], [], 0, 0]
+        if not outs:
+            return
+        for name, data in zip(names, _encode_held(outs)):
             with open(os.path.join(out_dir, name), "wb") as f:
                 f.write(data)
         written.update(names)
@@ -459,11 +462,9 @@ def _batched_to_files(images, out_dir: str, tee: bool):
     def sink(out: torch.Tensor, names: List[str]) -> None:
         on_device = [n.lower().endswith((".jpg", ".jpeg")) for n in names]
         if all(on_device) and out.dim() == 4 and out.shape[-1] == 3:
-            shape = tuple(out.shape[1:])
-            slot = held.setdefault(shape, [[], [], 0])
-            slot[0].append(out); slot[1].extend(names); slot[2] += out.shape[0]
-            if slot[2] >= SINK_FRAMES or slot[2] * out[0].numel() >= SINK_BYTES:
-                flush(shape)
+            held[0].append(out); held[1].extend(names); held[2] += out.shape[0]; held[3] += out.numel()
+            if held[2] >= SINK_FRAMES or held[3] >= SINK_BYTES:
+                flush()
         else:                                             # another format: Pillow writes it
             host = staging.download(out).numpy()
             for j, name in enumerate(names):
@@ -473,19 +474,29 @@ def _batched_to_files(images, out_dir: str, tee: bool):
     named = apply_all_transformations_batched_named(images, _sink=sink, _tee=tee)
     sunk = set()
     if tee:                                               # the names the sink has written: everything else is saved below
-        sunk = {n for _, names, _ in held.values() for n in names} | written
+        sunk = set(held[1]) | written
     for name, img in named:
         if isinstance(img, torch.Tensor):                 # apply_blur's radius-0 pass-through of a device frame
             sink(img[None], [name])
         elif img is not None and name not in sunk:        # per-image path (not RGB) or apply_blur's radius-0 pass-through
             save_image(img, os.path.join(out_dir, name))
-    for shape in list(held):
-        flush(shape)
+    flush()
     return named
 
 
-SINK_FRAMES = 1024                                        # frames of one shape per writer call in the device-save drivers ...
+SINK_FRAMES = 1024                                        # frames per writer call in the device-save drivers ...
 SINK_BYTES = 2 << 30                                      # ... or this many bytes of them (4K frames: 86 per call), whichever comes first
+
+
+def _encode_held(outs: List[torch.Tensor]):
+    """The files (memoryviews, in order) of the frames of `outs`, [B_i, H_i, W_i, 3] device tensors.  Mixed shapes: every
+    frame goes, as a view of its group's output, through ONE `jpeg.encode_list_views` call.  A single shape: the batch
+    writer `jpeg.encode_views` on the (concatenated) batch, the faster route on a uniform batch (1024 frames of 375 x 500:
+    4.85 ms against the list route's 5.88 ms, profiles/jpeg_encode_list.txt)."""
+    from . import jpeg
+    if len({tuple(o.shape[1:]) for o in outs}) == 1:
+        return jpeg.encode_views(outs[0] if len(outs) == 1 else torch.cat(outs))
+    return jpeg.encode_list_views([o[j] for o in outs for j in range(o.shape[0])])
 
 
 _TENSOR_FNS = {                                           # type -> the apply_<type> body on a [B, H, W, 3] device batch

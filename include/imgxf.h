@@ -449,6 +449,59 @@ int imgxf_jpeg_encode_u8(const imgxf_view* src, const imgxf_jpeg_tables* tables,
                          int header_bytes, uint8_t* out, size_t out_frame_stride, uint32_t* sizes,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same default file (RGB, 4:2:0, the call's tables, one quality per call) for a LIST of frames of different sizes,
+ * in a number of launches that does not depend on the list: every stage of imgxf_jpeg_encode_u8 runs once over work-unit
+ * tables instead of over a (items, frames) grid.  The HOST lays out one block
+ *     imgxf_jpeg_list_header | imgxf_jpeg_list_frame[n] | imgxf_jpeg_list_unit tables (5)
+ * which the caller completes (data, row_stride of every frame) and copies to the device once.  Each frame has its own
+ * geometry, its own piece of every workspace area, its own 32-bit bit offsets and its own slot of the output. */
+#define IMGXF_JPEG_LIST_STAGES 5    /* unit tables: 16x256-pixel transform strips (item = strip | MCU row << 16), groups of
+                                       256 blocks, scan parts of 1024 blocks, chunk groups, scan parts of 1024 chunks */
+#define IMGXF_JPEG_LIST_AREAS 8     /* workspace areas: coefficients, DC values, AC bits, lens / bit offsets, partial sums,
+                                       totals (bits[n], 0xFF counts[n]), unstuffed streams, 0xFF counts per 32-byte chunk */
+typedef struct imgxf_jpeg_list_header {
+    int32_t  n_frames, frames_off, total_bytes, pad_;       /* byte offsets into the block; its size */
+    int32_t  n_units[IMGXF_JPEG_LIST_STAGES], units_off[IMGXF_JPEG_LIST_STAGES];
+    uint64_t area_off[IMGXF_JPEG_LIST_AREAS];                /* byte offsets into the workspace, 256-byte aligned */
+    uint64_t workspace_bytes, out_bytes;
+} imgxf_jpeg_list_header;
+typedef struct imgxf_jpeg_list_frame {
+    uint64_t data;              /* DEVICE address of pixel (0, 0), any alignment; filled by the caller, as is row_stride */
+    int64_t  row_stride;        /* bytes, >= 3 w */
+    int32_t  h, w;
+    int32_t  mw, mh, bw, bh, nblk;   /* MCUs (16x16) and blocks (8x8) across / down; 6 mw mh blocks */
+    int32_t  nparts_blk, nchunks, nparts_chunk, chunk_groups;   /* scan parts of the blocks; 32-byte chunks of the stream,
+                                   their scan parts, the workgroups (<= 256) that share them */
+    int32_t  pad_;
+    int64_t  stream_words;      /* capacity of the unstuffed stream: out_cap / 4 rounded up, + 4, to a multiple of 4 */
+    int64_t  coef_off, blk_off, part_off, stream_off, cnt_off;   /* the frame's ELEMENT offset in its areas: int16
+                                   coefficients (whole groups of 64 blocks); blocks (a multiple of 64: the DC, AC-bits and
+                                   lens areas share it); uint32 partial sums; uint32 stream words (a multiple of 4); chunks */
+    int64_t  out_off, out_cap;  /* the file's slot of `out`: byte offset (a multiple of 16) and capacity */
+} imgxf_jpeg_list_frame;
+typedef struct imgxf_jpeg_list_unit {
+    int32_t frame, item;        /* one workgroup: item `item` of frame `frame` (frame-major, items ascending) */
+} imgxf_jpeg_list_unit;
+/* HOST half (no device work).  sizes: int32 [n][2] = (h, w); capacities: n file capacities in bytes (out_cap).  Writes the
+ * block (block == NULL: the sizes only) and reports the block's bytes (the tables), the workspace's and the output's.
+ * The workspace never exceeds the sum over the frames of imgxf_jpeg_workspace_bytes(1, h, w, capacity).
+ * Errors: IMGXF_ERR_NULL; IMGXF_ERR_SHAPE for n < 0 or n > 1048576, h or w outside 1..32767, more than 2097143 blocks in
+ * a frame; IMGXF_ERR_ARG for a capacity below 1024 + 2 or above 2^31, a block over 2 GiB; IMGXF_ERR_WORKSPACE when
+ * block_cap is too small. */
+int imgxf_jpeg_encode_list_layout_host(const int32_t* sizes, const uint64_t* capacities, int n, void* block, size_t block_cap,
+                                       size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes);
+/* The launches: block_host is the caller's host copy of the block, block_dev the same bytes on the device (8-byte
+ * aligned).  `header` is the file header for these tables with ANY size in its SOF0 segment: the device writes each
+ * frame's height and width there.  File f goes to out + frames[f].out_off; sizes[f] (device, n entries) as
+ * imgxf_jpeg_encode_u8.  Every record is checked on the host before anything is launched: the block must be what
+ * imgxf_jpeg_encode_list_layout_host writes for the records' (h, w, out_cap) — so offsets are aligned, ascending,
+ * disjoint and inside the workspace and `out`, and every block of every frame belongs to exactly one unit — else
+ * IMGXF_ERR_ARG; a NULL data -> IMGXF_ERR_NULL; h, w, row_stride < 3 w or the block limit -> IMGXF_ERR_SHAPE; a
+ * workspace or `out` too small or misaligned (16 bytes) -> IMGXF_ERR_WORKSPACE; a header without SOF0 -> IMGXF_ERR_ARG. */
+int imgxf_jpeg_encode_list_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_tables* tables,
+                              const uint8_t* header, int header_bytes, uint8_t* out, size_t out_bytes, uint32_t* sizes,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* The writer's options: Pillow's `save(fp, "JPEG", quality=q, subsampling=s, optimize=o)` for RGB (ncomp 3, a c == 3 view)
  * and "L" frames (ncomp 1, c == 1), bit-identical to libjpeg-turbo.  Luma sampling h_samp x v_samp: 1x1 (4:4:4, MCU 8x8:
  * Y Cb Cr; jcsample.c fullsize_downsample), 2x1 (4:2:2, MCU 16x8: Y Y Cb Cr; h2v1_downsample, bias 0,1 along a row, dummy

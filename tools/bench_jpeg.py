@@ -1,12 +1,97 @@
 """Device JPEG writer throughput: n 4K (or H W) frames → n files; per-kernel split comes from rocprofv3.
 usage: python tools/bench_jpeg.py [frames] [H W] ; env KIND=photo|noise, SUBSAMPLING=-1|0|1|2|4:4:4|4:2:2|4:2:0,
-OPTIMIZE=1, PROGRESSIVE=1, GRAY=1 (the frames converted to "L") — Pillow runs with the same options.
-The progressive rows: PROGRESSIVE=1 with SUBSAMPLING=2 / 0 / GRAY=1, for 16 frames of 4K and 256 of 375 500."""
+OPTIMIZE=1, PROGRESSIVE=1, GRAY=1 (the frames converted to "L") — Pillow runs with the same options; QUICK=1 stops before
+the threaded Pillow comparison.
+The progressive rows: PROGRESSIVE=1 with SUBSAMPLING=2 / 0 / GRAY=1, for 16 frames of 4K and 256 of 375 500.
+List mode (`jpeg.encode_list_views` against the per-shape route): python tools/bench_jpeg.py list [frames] [mixed|uniform] [a|b]"""
 import io, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from imagetransformations_amd import jpeg
+
+
+def list_mode(argv):
+    """`bench_jpeg.py list [frames] [mixed|uniform] [a|b]`: the list writer against the per-shape route on photo-like frames
+    at quality 75.  mixed: the ImageNet-like size mix of tools/bench_preprocess_list.py workload B; uniform: every frame
+    375 x 500.  Route a: group by shape, torch.cat, `encode_views` per shape; route b: one `encode_list_views`.  The two
+    alternate, four runs each after a warm-up, a host clock around calls that end in a synchronise; files compared.
+    With a third argument only that route runs, once after a warm-up, preceded by "TRACE": for
+    `rocprofv3 --kernel-trace --stats`, whose launch counts are then (warm-up + 1) x one call's.  Exits non-zero when
+    the files differ."""
+    from imagetransformations_amd import _ffi as F
+    n = int(argv[0]) if argv else 1024
+    mix = argv[1] if len(argv) > 1 else "mixed"
+    only = argv[2] if len(argv) > 2 else None
+    dev = torch.device("cuda:0")
+    if mix == "mixed":
+        from bench_preprocess_list import mixed_sizes         # (tools/ is this script's directory)
+        sizes = mixed_sizes(n)
+    else:
+        sizes = [(375, 500)] * n
+    g = torch.Generator(device=dev); g.manual_seed(3)
+    yy = torch.arange(512, device=dev)[None, :, None, None].float()
+    xx = torch.arange(512, device=dev)[None, None, :, None].float()
+    ph = torch.arange(16, device=dev)[:, None, None, None].float()
+    ch = torch.arange(3, device=dev)[None, None, None, :].float()
+    base = 128 + 60 * torch.sin(xx / (90 + 20 * ch) + ph) + 50 * torch.cos(yy / (70 + 10 * ch) + 0.5 * ph) + 30 * ((xx // 256 + yy // 256) % 2)
+    base = (base + 6 * torch.randn((16, 512, 512, 3), device=dev, generator=g)).clamp(0, 255).to(torch.uint8)
+    frames = [base[i % 16, :h, :w].contiguous() for i, (h, w) in enumerate(sizes)]
+    groups = {}
+    for i, t in enumerate(frames):
+        groups.setdefault(tuple(t.shape), []).append(i)
+
+    def route_a():
+        out = [None] * n
+        for idx in groups.values():
+            for i, v in zip(idx, jpeg.encode_views(torch.cat([frames[i][None] for i in idx]))):
+                out[i] = v
+        return out
+
+    def route_b():
+        return jpeg.encode_list_views(frames)
+
+    seen, real = {}, F.call
+
+    def counting(name, *args):
+        seen[name] = seen.get(name, 0) + 1
+        return real(name, *args)
+
+    if only:
+        fn = route_a if only == "a" else route_b
+        fn()
+        print(f"TRACE route {only}: {n} frames, {len(groups)} distinct sizes, 2 calls (warm-up + 1)", flush=True)
+        fn()
+        return 0
+    a, b = route_a(), route_b()                                # warm-up, and the comparison
+    same = all(bytes(x) == bytes(y) for x, y in zip(a, b))
+    nbytes = sum(len(x) for x in b)
+    del a, b
+    F.call = counting
+    route_a(); ca = dict(seen); seen.clear()
+    route_b(); cb = dict(seen); seen.clear()
+    F.call = real
+    ta, tb = [], []
+    for _ in range(4):
+        for fn, ts in ((route_a, ta), (route_b, tb)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+    med = lambda v: sorted(v)[len(v) // 2 - 1] / 2 + sorted(v)[len(v) // 2] / 2
+    px = sum(h * w for h, w in sizes)
+    print(f"list mode, {mix}: {n} photo-like frames, {len(groups)} distinct sizes, {px / 1e6:.1f} Mpix, quality 75, {nbytes / px:.3f} bytes/px; "
+          f"files equal: {same}")
+    for name, ts, calls in (("a: per shape, torch.cat + encode_views", ta, ca), ("b: encode_list_views", tb, cb)):
+        writer = sum(v for k, v in calls.items() if k.startswith("imgxf_jpeg_encode") and k.endswith("_u8"))
+        print(f"  {name:<40} runs (ms) {' '.join(f'{t:.2f}' for t in ts)}  median {med(ts):.2f}  spread {max(ts) - min(ts):.2f}  "
+              f"{n / med(ts) * 1e3:.0f} files/s  C calls {sum(calls.values())} ({writer} writer)")
+    gain = med(ta) - med(tb)
+    print(f"  median(a) - median(b) = {gain:.2f} ms ({med(ta) / med(tb):.2f}x); spread of a {max(ta) - min(ta):.2f} ms: "
+          f"b is {'FASTER beyond the spread' if gain > max(ta) - min(ta) else 'NOT faster beyond the spread'}", flush=True)
+    return 0 if same else 1
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "list":
+    sys.exit(list_mode(sys.argv[2:]))
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 H, W = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (2160, 3840)
 KIND = os.environ.get("KIND", "photo")
@@ -58,6 +143,8 @@ for _ in range(3):
 t1 = time.time()
 print(f"  Pillow (libjpeg-turbo, one core): {(t1 - t0) / 3 * 1e3:.1f} ms per frame  {H * W * 3 / (t1 - t0) / 1e9:.3f} Gsamples/s; "
       f"equal: {buf.getvalue() == out[0]}", flush=True)
+if os.environ.get("QUICK", "0") == "1":                      # the device figures and the comparison only
+    sys.exit(0)
 from concurrent.futures import ThreadPoolExecutor
 ncores = min(16, os.cpu_count() or 1)
 arrs = [frames[i % N].cpu().numpy() for i in range(2 * ncores)]
