@@ -7,6 +7,7 @@
 // workgroup a 256 x 4 pixel patch, so the source footprint of a workgroup is a thin
 // rotated strip that stays in the XCD's L2 while neighbouring patches reuse it.
 #include "imgxf_common.h"
+#include "pixel_ops.h"
 #include <math.h>
 #include <algorithm>
 #include <string.h>
@@ -27,14 +28,7 @@ struct AffineParams {
 };
 
 // ---- arithmetic policies -------------------------------------------------------------
-// Precise: fp64 with every multiply/add rounded separately (no FMA contraction), i.e. the
-// exact sequence libImaging's C code performs on x86-64 -> bit-identical to Pillow.
-struct PreciseArith {
-    typedef double T;
-    static __device__ __forceinline__ T mul(T a, T b) { return __dmul_rn(a, b); }
-    static __device__ __forceinline__ T add(T a, T b) { return __dadd_rn(a, b); }
-    static __device__ __forceinline__ T sub(T a, T b) { return __dsub_rn(a, b); }
-};
+// (PreciseArith, the fp64 policy that is bit-identical to Pillow, and cubic<A> are in pixel_ops.h)
 // Fast: fp32 (<= 1e-5 relative before truncation).
 struct FastArith {
     typedef float T;
@@ -55,19 +49,6 @@ __device__ __forceinline__ typename A::T lerp(typename A::T a, typename A::T b, 
     return lerp_t(A(), a, b, d);
 }
 
-template <class A>
-__device__ __forceinline__ typename A::T cubic(typename A::T v1, typename A::T v2, typename A::T v3,
-                                               typename A::T v4, typename A::T d) {
-    typedef typename A::T T;
-    const T p1 = v2;
-    const T p2 = A::add(-v1, v3);
-    const T p3 = A::sub(A::add(A::mul((T)2, A::sub(v1, v2)), v3), v4);
-    const T p4 = A::add(A::sub(A::add(-v1, v2), v3), v4);
-    return A::add(p1, A::mul(d, A::add(p2, A::mul(d, A::add(p3, A::mul(d, p4))))));
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // HONLY (BICUBIC): the matrix is a pure horizontal shear/shift (m3 == 0, m4 == 1, m5 integral),
 // so yin - 0.5 is an integer, dy == 0 exactly and libImaging's column cubic p1 + 0*(...) returns
 // the row-y value bit-for-bit: only row y's horizontal cubic is evaluated (apply_shear).
@@ -87,10 +68,8 @@ __global__ __launch_bounds__(256) void affine_kernel(View s, View d, AffineParam
         bool ok;
         u8 px[C];
         if (FILTER == IMGXF_FILTER_NEAREST) {
-            // int arithmetic wraps exactly like the C `int` accumulators of affine_fixed
-            const int xx = (int)((u32)P.fx[2] + (u32)P.fx[1] * (u32)y + (u32)P.fx[0] * (u32)x);
-            const int yy = (int)((u32)P.fx[5] + (u32)P.fx[4] * (u32)y + (u32)P.fx[3] * (u32)x);
-            const int xin = xx >> 16, yin = yy >> 16;
+            int xin, yin;
+            affine_fixed_src(P.fx, x, y, xin, yin);
             ok = xin >= 0 && xin < s.w && yin >= 0 && yin < s.h;
             if (ok) {
                 const u8* q = sp + (int64_t)yin * s.rs + xin * C;
@@ -1027,27 +1006,7 @@ typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
 // yi clamped, yok = the row passes the bounds test, a1y = m1 * (y + 0.5))
 __device__ __forceinline__ void shear_exact_px(const View& s, const AffineParams& P, const u8* row, bool yok, double a1y,
                                                int x, u8 (&px)[3]) {
-    constexpr int C = 3;
-    const double xc = (double)x + 0.5;
-    double xin = __dadd_rn(__dadd_rn(__dmul_rn(P.m[0], xc), a1y), P.m[2]);
-    if (!(yok && xin >= 0.0 && xin < (double)s.w)) {
-#pragma unroll
-        for (int j = 0; j < C; ++j) px[j] = P.fill[j];
-        return;
-    }
-    xin -= 0.5;
-    const double xfl = floor(xin);
-    const int xi = (int)xfl;
-    const double dx = xin - xfl;
-    int xs[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) xs[t] = clampi(xi - 1 + t, 0, s.w - 1) * C;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-        const double v = cubic<PreciseArith>((double)row[xs[0] + j], (double)row[xs[1] + j],
-                                             (double)row[xs[2] + j], (double)row[xs[3] + j], dx);
-        px[j] = v <= 0.0 ? (u8)0 : (v >= 255.0 ? (u8)255 : (u8)(int)v);
-    }
+    bicubic_row_exact_px(row, s.w, yok, P.m[0], a1y, P.m[2], P.fill, x, px);
 }
 
 // Unit-step rows, second pass: the few 4-pixel groups at both ends of the source row (taps

@@ -1,0 +1,513 @@
+// The transformations of apply_all_transformations on a LIST of entries over RGB frames of different sizes
+// (driver_list.apply_list): seven of the driver's eight types — scale, rotation, lighten_darken, contrast, shear,
+// translation, gaussian_noise — each entry with its own frame, type and drawn value, bit for bit what the per-type entry
+// points return (blur is not here: its four kernel families agree to 1e-5, not to the byte).
+//
+// HOST half (imgxf_driver_list_layout_host, no device work): from each entry's geometry and parameters one block of
+//   header | entry records | work units | coefficient tables
+// Lanczos tables are precompute_coeffs' (build_coeffs, resample_coeffs.h), sliced to the centre-crop window for factors
+// above 1 as resize_crop's plans slice them; entries of equal (in, out, window) on an axis share one table, so host work
+// grows with the number of distinct geometries.  Rotation matrices are ops.rotate_matrix's (Python's round(., 15) in
+// double) and go into the record as libImaging's 16.16 coefficients.
+//
+// DEVICE half (imgxf_driver_list_u8): one copy of the block, two launches.  One workgroup per work unit = a band of
+// output rows of one entry; the entry's operation is uniform over the workgroup.
+//   driver_list_plain_kernel: the six types that need no LDS.  The band is a contiguous run of the output; a lane owns 4
+//     consecutive pixels = 3 aligned dwords of it (outputs start on 16-byte boundaries), the per-pixel statements are those
+//     of the per-type kernels (pixel_ops.h).
+//   driver_list_scale_kernel: horizontal Lanczos pass of the touched source rows into an LDS intermediate (uint8, as
+//     Pillow's is), vertical pass from LDS (resample_list.h, the passes of preprocess_list_kernel); below factor 1 the
+//     unit also writes the black canvas around the pasted window.  Its launch alone carries the LDS, so the plain units'
+//     occupancy does not pay for it.
+#include "imgxf_common.h"
+#include "pixel_ops.h"
+#include "resample_coeffs.h"
+#include "resample_list.h"
+#include <map>
+#include <array>
+#include <string.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+namespace imgxf {
+
+constexpr int DL_THREADS = PL_THREADS;
+constexpr int DL_UNIT_ROWS = 16;          // window rows per scale unit when the LDS budget allows
+constexpr int DL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB
+constexpr int DL_PLAIN_BYTES = 24 * 1024; // output bytes per unit of the other types (at least one row)
+
+struct DlGeom { int frame, type, h, w, c; };
+
+// Python's float % float
+static inline double py_mod(double a, double b) {
+    double m = fmod(a, b);
+    if (m != 0.0) { if ((b < 0.0) != (m < 0.0)) m += b; } else m = copysign(0.0, b);
+    return m;
+}
+// Python's round(x, 15): the correctly rounded 15-decimal string, read back
+static inline double py_round15(double x) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%.15f", x);
+    return strtod(buf, nullptr);
+}
+
+// ops.rotate_turns + ops.rotate_matrix + affine_fixed_matrix for Image.rotate(angle): 0 the 16.16 matrix is in fx, 1 a copy,
+// 2 a transpose path, 3 a pure scale after rounding (ImagingScaleAffine's walk, not affine_fixed)
+static int dl_rotation(int w, int h, double angle, int fx[6]) {
+    const double a = py_mod(angle, 360.0);
+    if (a == 0.0) return 1;
+    if (a == 180.0 || ((a == 90.0 || a == 270.0) && w == h)) return 2;
+    const double cx = w / 2.0, cy = h / 2.0;
+    const double r = -(a * (M_PI / 180.0));                   // -math.radians(angle % 360.0)
+    double m[6] = {py_round15(cos(r)), py_round15(sin(r)), 0.0, py_round15(-sin(r)), py_round15(cos(r)), 0.0};
+    m[2] = m[0] * -cx + m[1] * -cy + m[2];
+    m[5] = m[3] * -cx + m[4] * -cy + m[5];
+    m[2] += cx;
+    m[5] += cy;
+    if (m[1] == 0.0 && m[3] == 0.0) return 3;
+    affine_fixed_matrix(m, fx);
+    return 0;
+}
+
+// Window rows per scale unit: the most, up to DL_UNIT_ROWS, whose touched rows fit the budget beside the staging (0: none).
+// The launch's LDS size is its largest unit's, so an entry takes the smallest of three steps of the budget that holds at
+// least one of its rows (pl_unit_rows of preprocess_list.hip)
+static int dl_unit_rows(int h, int nh, int ksy, int win_h, int win_w, int ncols, int lds_budget) {
+    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
+        for (int ny = win_h < DL_UNIT_ROWS ? win_h : DL_UNIT_ROWS; ny >= 1; --ny)
+            if (pl_lds_bytes(pl_rows_bound(ny, h, nh, ksy), win_w, ncols) <= limit) return ny;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// one output pixel of the types without LDS; (x, y) in the output, pk = y * ow + x
+template <int OP>
+__device__ __forceinline__ void dl_pixel(const imgxf_driver_entry& e, const u8* src, int x, int y, int pk, u8 (&px)[3]) {
+    if (OP == IMGXF_DRIVER_BRIGHTNESS || OP == IMGXF_DRIVER_CONTRAST || OP == IMGXF_DRIVER_NOISE) {
+        const u8* sp = src + (int64_t)y * e.src_stride + x * 3;
+        const float* z = (const float*)e.noise + (int64_t)pk * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float p = (float)sp[j];
+            if (OP == IMGXF_DRIVER_BRIGHTNESS) px[j] = (u8)pack_u8(blend_floor(0.0f, p, e.alpha));     // blend(black, image, factor)
+            else if (OP == IMGXF_DRIVER_CONTRAST) px[j] = (u8)pack_u8(scale_abs_value(p, e.alpha, e.beta));
+            else px[j] = (u8)add_noise_byte(p, z[j]);
+        }
+    } else if (OP == IMGXF_DRIVER_TRANSLATION) {
+        const int dxb = e.dx * 3, rowbytes = e.w * 3;
+        const int c0 = max(dxb, 0), c1 = min(rowbytes, rowbytes + dxb);
+        const int ys = y - e.dy;
+        const bool row_in = ys >= 0 && ys < e.h;
+        const u8* sp = row_in ? src + (int64_t)ys * e.src_stride - dxb : nullptr;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) px[j] = translate_byte(sp, row_in, x * 3 + j, c0, c1, (u8)0);
+    } else if (OP == IMGXF_DRIVER_ROTATION) {
+        int xin, yin;
+        affine_fixed_src(e.fx, x, y, xin, yin);
+        const bool ok = xin >= 0 && xin < e.w && yin >= 0 && yin < e.h;
+        const u8* sp = src + (ok ? (int64_t)yin * e.src_stride + xin * 3 : 0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) px[j] = ok ? sp[j] : (u8)0;
+    } else {                                                  // SHEAR: (1, m1, m2, 0, 1, 0), source row y
+        const u8 fill[3] = {255, 255, 255};
+        const double yc = (double)y + 0.5;
+        const double a1y = __dmul_rn(e.m1, yc);
+        const bool yok = yc >= 0.0 && yc < (double)e.h;
+        const u8* row = src + (int64_t)clampi(y, 0, e.h - 1) * e.src_stride;
+        bicubic_row_exact_px(row, e.w, yok, 1.0, a1y, e.m2, fill, x, px);
+    }
+}
+
+template <int OP>
+__device__ __forceinline__ void dl_band(const imgxf_driver_entry& e, const imgxf_driver_unit& u, u8* __restrict__ o) {
+    const u8* src = (const u8*)e.src;
+    const int ow = e.ow;
+    const int p_lo = u.y0 * ow, p_hi = (u.y0 + u.ny) * ow;    // the band's pixels (oh * ow < 2^31)
+    const int g_hi = (int)(((int64_t)p_hi + 3) >> 2);
+    for (int g = (p_lo >> 2) + (int)threadIdx.x; g < g_hi; g += DL_THREADS) {
+        const int p = g * 4;
+        int y = p / ow, x = p - y * ow;
+        u32 od[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int pk = p + k;
+            u8 px[3] = {0, 0, 0};
+            if (pk >= p_lo && pk < p_hi) dl_pixel<OP>(e, src, x, y, pk, px);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) od[(k * 3 + j) >> 2] |= (u32)px[j] << (8 * ((k * 3 + j) & 3));
+            if (++x == ow) { x = 0; ++y; }
+        }
+        u8* dp = o + (int64_t)p * 3;                          // 4-byte aligned: the output starts on a 16-byte boundary
+        if (p >= p_lo && (int64_t)p + 4 <= p_hi) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) ((u32*)dp)[q] = od[q];
+        } else {                                              // a group shared with the neighbouring band
+#pragma unroll
+            for (int b = 0; b < 12; ++b) {
+                const int pk = p + b / 3;
+                if (pk >= p_lo && pk < p_hi) dp[b] = (u8)(od[b >> 2] >> (8 * (b & 3)));
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(DL_THREADS) void driver_list_plain_kernel(const u8* __restrict__ block, int entries_off,
+                                                                       int units_off, u8* __restrict__ out) {
+    const imgxf_driver_unit u = ((const imgxf_driver_unit*)(block + units_off))[blockIdx.x];
+    const imgxf_driver_entry e = ((const imgxf_driver_entry*)(block + entries_off))[u.entry];
+    u8* o = out + e.out_off;
+    switch (e.op) {                                           // uniform over the workgroup
+        case IMGXF_DRIVER_ROTATION: dl_band<IMGXF_DRIVER_ROTATION>(e, u, o); break;
+        case IMGXF_DRIVER_BRIGHTNESS: dl_band<IMGXF_DRIVER_BRIGHTNESS>(e, u, o); break;
+        case IMGXF_DRIVER_CONTRAST: dl_band<IMGXF_DRIVER_CONTRAST>(e, u, o); break;
+        case IMGXF_DRIVER_SHEAR: dl_band<IMGXF_DRIVER_SHEAR>(e, u, o); break;
+        case IMGXF_DRIVER_TRANSLATION: dl_band<IMGXF_DRIVER_TRANSLATION>(e, u, o); break;
+        case IMGXF_DRIVER_NOISE: dl_band<IMGXF_DRIVER_NOISE>(e, u, o); break;
+        default: break;
+    }
+}
+
+__global__ __launch_bounds__(DL_THREADS) void driver_list_scale_kernel(const u8* __restrict__ block, int entries_off,
+                                                                       int units_off, int unit0, u8* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) u8 dl_lds[];
+    const int* words = (const int*)block;
+    const imgxf_driver_unit u = ((const imgxf_driver_unit*)(block + units_off))[unit0 + blockIdx.x];
+    const imgxf_driver_entry e = ((const imgxf_driver_entry*)(block + entries_off))[u.entry];
+    const int tid = threadIdx.x;
+    u8* o = out + e.out_off;
+    const int ow = e.ow;
+    if (e.win_w != ow || e.win_h != e.oh) {                   // factor below 1: the black canvas around the pasted window
+        const int p_lo = u.y0 * ow, p_hi = (u.y0 + u.ny) * ow;
+        for (int p = p_lo + tid; p < p_hi; p += DL_THREADS) {
+            const int y = p / ow, x = p - y * ow;
+            if (y < e.win_top || y >= e.win_top + e.win_h || x < e.win_left || x >= e.win_left + e.win_w) {
+                u8* dp = o + (int64_t)p * 3;
+                dp[0] = 0; dp[1] = 0; dp[2] = 0;
+            }
+        }
+    }
+    // the unit's rows of the window (table rows)
+    const int ja = max(u.y0, e.win_top) - e.win_top, jb = min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
+    if (jb <= ja) return;
+    const int* bx = words + e.bounds_x;
+    const int* kx = words + e.coeffs_x;
+    const int* by = words + e.bounds_y;
+    const int* ky = words + e.coeffs_y;
+    const int width = e.win_w;
+    const int pitch = ((width + 3) >> 2) * 12;
+    // source rows these rows touch (the bounds are monotone), held inside the range the record states
+    const int r_lo = max(by[2 * ja], e.row0);
+    const int r_hi = min(by[2 * (jb - 1)] + by[2 * (jb - 1) + 1], e.row0 + e.nrows);
+    const int nrows = r_hi - r_lo;
+    u8* mid = dl_lds;
+    u8* stage = dl_lds + ((nrows * pitch + 15) & ~15);
+    pl_horizontal_pass((const u8*)e.src, e.src_stride, e.col0, e.ncols, r_lo, r_hi, bx, kx, e.ksx, width, mid, pitch, stage, tid);
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int nq = (width + 3) >> 2;
+    for (int yy = wave; yy < jb - ja; yy += DL_THREADS / 64) {
+        const int j = ja + yy;
+        const int cnt = by[2 * j + 1];
+        const int ymin = min(max(by[2 * j] - r_lo, 0), max(nrows - cnt, 0));
+        const int* k = ky + (int64_t)j * e.ksy;
+        const int kv = lane < cnt ? k[lane] : 0;
+        for (int q = lane; q < nq; q += 64) {
+            int acc[12];
+            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
+            u32 od[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int b = 0; b < 12; ++b) od[b >> 2] |= (u32)clip8(acc[b]) << (8 * (b & 3));
+            const int nb = min(4, width - 4 * q) * 3;
+            u8* dp = o + ((int64_t)(e.win_top + j) * ow + e.win_left + 4 * q) * 3;
+            if (nb == 12 && (((uintptr_t)dp) & 3) == 0) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) ((u32*)dp)[d] = od[d];
+            } else {
+#pragma unroll
+                for (int b = 0; b < 12; ++b)
+                    if (b < nb) dp[b] = (u8)(od[b >> 2] >> (8 * (b & 3)));
+            }
+        }
+    }
+}
+
+} // namespace imgxf
+
+using namespace imgxf;
+
+IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const double* params, int n, int lds_budget, void* block,
+                                            size_t block_cap, size_t* block_bytes, int64_t* out_off, int32_t* out_hw,
+                                            int32_t* status, size_t* out_bytes, int32_t* lds_bytes) {
+    if (!block_bytes || (n > 0 && (!geometry || !params))) return IMGXF_ERR_NULL;
+    if (n < 0 || lds_budget < 1) return IMGXF_ERR_ARG;
+    if (lds_budget > DL_MAX_LDS) lds_budget = DL_MAX_LDS;
+    const DlGeom* geo = (const DlGeom*)geometry;
+
+    // pass over geometry and parameters alone: every record but its tables, which axes share tables -> the sections' sizes
+    struct Axis { int in, out, first, count, ks, bounds, coeffs; };
+    std::map<std::array<int, 4>, int> axis_index;
+    std::vector<Axis> axes;
+    size_t table_words = 0;
+    auto axis_of = [&](int in, int out, int first, int count) {
+        const std::array<int, 4> key = {in, out, first, count};
+        auto it = axis_index.find(key);
+        if (it != axis_index.end()) return it->second;
+        Axis a = {in, out, first, count, coeff_ksize(in, out, IMGXF_RESAMPLE_LANCZOS), -1, -1};
+        table_words += (size_t)count * (2 + a.ks);
+        axis_index.emplace(key, (int)axes.size());
+        axes.push_back(a);
+        return (int)axes.size() - 1;
+    };
+    std::vector<imgxf_driver_entry> recs((size_t)n);
+    std::vector<int> ax((size_t)n, -1), ay((size_t)n, -1);
+    size_t n_plain = 0, n_scale = 0;
+    uint64_t opos = 0;
+    int lds_bound = 0;
+    for (int i = 0; i < n; ++i) {
+        const DlGeom& g = geo[i];
+        const double p0 = params[2 * i], p1 = params[2 * i + 1];
+        imgxf_driver_entry& e = recs[i];
+        memset(&e, 0, sizeof(e));
+        e.frame = g.frame; e.op = g.type; e.h = g.h; e.w = g.w; e.oh = g.h; e.ow = g.w; e.out_off = -1;
+        int st = IMGXF_DRIVER_OK;
+        if (g.c != 3 || g.h < 1 || g.w < 1 || g.h > 32767 || g.w > 32767) {
+            st = IMGXF_DRIVER_REFUSED_FORMAT;
+        } else if (g.type == IMGXF_DRIVER_SCALE) {
+            const double fw = g.w * p0, fh = g.h * p0;
+            if (!(fw >= 1.0) || !(fh >= 1.0)) st = IMGXF_DRIVER_REFUSED_SIZE;           // int(w s) or int(h s) below 1 (or NaN)
+            else if (fw > 16777216.0 || fh > 16777216.0) st = IMGXF_DRIVER_REFUSED_OTHER;
+            else {
+                const int nw = (int)fw, nh = (int)fh;
+                int xfirst = 0, yfirst = 0;
+                if (p0 > 1.0) {                               // resize + centre crop: only the window is computed
+                    xfirst = (nw - g.w) / 2; yfirst = (nh - g.h) / 2;
+                    e.win_w = g.w; e.win_h = g.h;
+                } else if (p0 < 1.0) {                        // resize, pasted on a black canvas
+                    e.win_w = nw; e.win_h = nh;
+                    e.win_left = (g.w - nw) / 2; e.win_top = (g.h - nh) / 2;
+                } else {                                      // factor 1: a resize to the same size
+                    e.win_w = nw; e.win_h = nh; e.oh = nh; e.ow = nw;
+                }
+                e.ksx = coeff_ksize(g.w, nw, IMGXF_RESAMPLE_LANCZOS);
+                e.ksy = coeff_ksize(g.h, nh, IMGXF_RESAMPLE_LANCZOS);
+                e.unit_rows = dl_unit_rows(g.h, nh, e.ksy, e.win_h, e.win_w, pl_rows_bound(e.win_w, g.w, nw, e.ksx), lds_budget);
+                if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
+                else {
+                    ax[i] = axis_of(g.w, nw, xfirst, e.win_w);
+                    ay[i] = axis_of(g.h, nh, yfirst, e.win_h);
+                    lds_bound = std::max(lds_bound, pl_lds_bytes(pl_rows_bound(e.unit_rows, g.h, nh, e.ksy), e.win_w,
+                                                                 pl_rows_bound(e.win_w, g.w, nw, e.ksx)));
+                }
+            }
+        } else if (g.type == IMGXF_DRIVER_ROTATION) {
+            if (!isfinite(p0)) st = IMGXF_DRIVER_REFUSED_OTHER;
+            else {
+                const int kind = dl_rotation(g.w, g.h, -p0, e.fx);       // apply_rotation: img.rotate(-angle)
+                if (kind == 1) e.op = IMGXF_DRIVER_TRANSLATION;          // a copy
+                else if (kind == 2) st = IMGXF_DRIVER_REFUSED_TURN;
+                else if (kind == 3) st = IMGXF_DRIVER_REFUSED_OTHER;
+            }
+        } else if (g.type == IMGXF_DRIVER_BRIGHTNESS) {
+            e.alpha = (float)p0;
+        } else if (g.type == IMGXF_DRIVER_CONTRAST) {
+            e.alpha = (float)p0; e.beta = 0.0f;
+        } else if (g.type == IMGXF_DRIVER_SHEAR) {
+            const double shift = ceil(p0 * g.h);
+            if (!isfinite(p0) || !(shift > -(double)g.w) || g.w + shift > 32767.0) st = IMGXF_DRIVER_REFUSED_OTHER;
+            else {
+                e.ow = g.w + (int)shift;
+                e.m1 = p0; e.m2 = p0 > 0 ? -(double)(int)shift : 0.0;
+            }
+        } else if (g.type == IMGXF_DRIVER_TRANSLATION) {
+            if (!isfinite(p0) || !isfinite(p1)) st = IMGXF_DRIVER_REFUSED_OTHER;
+            else {                                            // int(tx), int(ty); beyond the frame every shift gives the fill alone
+                e.dx = (int)std::max(-(double)g.w, std::min((double)g.w, trunc(p0)));
+                e.dy = (int)std::max(-(double)g.h, std::min((double)g.h, trunc(p1)));
+            }
+        } else if (g.type != IMGXF_DRIVER_NOISE) {
+            st = IMGXF_DRIVER_REFUSED_OTHER;
+        }
+        e.status = st;
+        if (st == IMGXF_DRIVER_OK) {
+            e.out_off = (int64_t)opos;
+            // outputs start on multiples of 48: 16-byte aligned, and whole pixels into the block, so that the block as ONE
+            // run of RGB pixels can be expanded or copied without knowing where its outputs are
+            opos = (opos + (uint64_t)e.oh * e.ow * 3 + 47) / 48 * 48;
+            if (g.type == IMGXF_DRIVER_SCALE) {
+                n_scale += (size_t)(e.win_h + e.unit_rows - 1) / e.unit_rows;
+            } else {
+                e.unit_rows = std::max(1, DL_PLAIN_BYTES / (e.ow * 3));
+                n_plain += (size_t)(e.oh + e.unit_rows - 1) / e.unit_rows;
+            }
+        } else {
+            e.unit_rows = 0;
+        }
+        if (out_off) out_off[i] = e.out_off;
+        if (out_hw) { out_hw[2 * i] = e.oh; out_hw[2 * i + 1] = e.ow; }
+        if (status) status[i] = st;
+    }
+    const size_t n_units = n_plain + n_scale;
+    const size_t entries_off = sizeof(imgxf_driver_header);
+    const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_driver_entry);
+    const size_t tables_off = units_off + n_units * sizeof(imgxf_driver_unit);
+    const size_t total = (tables_off + table_words * 4 + 15) & ~(size_t)15;
+    if (total > 0x7fffffffu || n_units > 0x7fffffffu || opos > ((uint64_t)1 << 40)) return IMGXF_ERR_SHAPE;
+    *block_bytes = total;
+    if (out_bytes) *out_bytes = (size_t)opos;
+    if (lds_bytes) *lds_bytes = lds_bound;                    // an upper bound; with a block: the largest unit's own need
+    if (!block) return IMGXF_OK;
+    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
+
+    u8* out = (u8*)block;
+    memset(out, 0, total);
+    imgxf_driver_header* hd = (imgxf_driver_header*)out;
+    imgxf_driver_entry* entries = (imgxf_driver_entry*)(out + entries_off);
+    imgxf_driver_unit* units = (imgxf_driver_unit*)(out + units_off);
+    int32_t* words = (int32_t*)out;
+    size_t tpos = tables_off / 4;
+    std::vector<int> bv, kv;
+    auto build_axis = [&](Axis& a) {
+        if (a.bounds >= 0) return;
+        build_coeffs(a.in, a.out, IMGXF_RESAMPLE_LANCZOS, bv, kv);
+        slice_tables(bv, kv, a.ks, a.first, a.count);
+        a.bounds = (int)tpos; memcpy(words + tpos, bv.data(), bv.size() * 4); tpos += bv.size();
+        a.coeffs = (int)tpos; memcpy(words + tpos, kv.data(), kv.size() * 4); tpos += kv.size();
+    };
+    size_t upos = 0;
+    int lds_max = 0;
+    for (int i = 0; i < n; ++i) {                             // the units without LDS first: they are the first launch
+        imgxf_driver_entry& e = recs[i];
+        if (e.status != IMGXF_DRIVER_OK || geo[i].type == IMGXF_DRIVER_SCALE) continue;
+        for (int y0 = 0; y0 < e.oh; y0 += e.unit_rows) {
+            imgxf_driver_unit& u = units[upos++];
+            u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, e.oh - y0); u.lds_bytes = 0;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        imgxf_driver_entry& e = recs[i];
+        if (e.status != IMGXF_DRIVER_OK || geo[i].type != IMGXF_DRIVER_SCALE) continue;
+        Axis& x = axes[ax[i]];
+        Axis& y = axes[ay[i]];
+        build_axis(x);
+        build_axis(y);
+        e.bounds_x = x.bounds; e.coeffs_x = x.coeffs; e.bounds_y = y.bounds; e.coeffs_y = y.coeffs;
+        const int32_t* bx = words + x.bounds;
+        const int32_t* by = words + y.bounds;
+        int c_lo = bx[0], c_hi = 0, r_lo = by[0], r_hi = 0;
+        for (int k = 0; k < e.win_w; ++k) { c_lo = std::min(c_lo, bx[2 * k]); c_hi = std::max(c_hi, bx[2 * k] + bx[2 * k + 1]); }
+        for (int k = 0; k < e.win_h; ++k) { r_lo = std::min(r_lo, by[2 * k]); r_hi = std::max(r_hi, by[2 * k] + by[2 * k + 1]); }
+        e.col0 = c_lo; e.ncols = c_hi - c_lo; e.row0 = r_lo; e.nrows = r_hi - r_lo;
+        for (int j0 = 0; j0 < e.win_h; j0 += e.unit_rows) {
+            const int nj = std::min(e.unit_rows, e.win_h - j0);
+            int lo = by[2 * j0], hi = 0;
+            for (int j = j0; j < j0 + nj; ++j) { lo = std::min(lo, by[2 * j]); hi = std::max(hi, by[2 * j] + by[2 * j + 1]); }
+            imgxf_driver_unit& u = units[upos++];
+            u.entry = i;
+            // the first and the last band of the window take the canvas rows above and below it
+            u.y0 = j0 == 0 ? 0 : e.win_top + j0;
+            const int y1 = j0 + nj >= e.win_h ? e.oh : e.win_top + j0 + nj;
+            u.ny = y1 - u.y0;
+            u.lds_bytes = pl_lds_bytes(hi - lo, e.win_w, e.ncols);
+            lds_max = std::max(lds_max, u.lds_bytes);
+        }
+    }
+    memcpy(entries, recs.data(), (size_t)n * sizeof(imgxf_driver_entry));
+    hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->n_plain = (int32_t)n_plain; hd->lds_bytes = lds_max;
+    hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
+    hd->total_bytes = (int32_t)total; hd->out_bytes = opos;
+    if (lds_bytes) *lds_bytes = lds_max;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint8_t* out, size_t out_cap, void* stream) {
+    if (!block_host) return IMGXF_ERR_NULL;
+    const u8* hb = (const u8*)block_host;
+    const imgxf_driver_header hd = *(const imgxf_driver_header*)hb;
+    if (hd.n_entries < 0 || hd.n_units < 0 || hd.n_plain < 0 || hd.n_plain > hd.n_units || hd.lds_bytes < 0 ||
+        hd.lds_bytes > DL_MAX_LDS)
+        return IMGXF_ERR_ARG;
+    const int64_t total = hd.total_bytes, words = total / 4;
+    if (hd.entries_off != (int)sizeof(imgxf_driver_header) ||
+        hd.units_off != hd.entries_off + (int64_t)hd.n_entries * (int64_t)sizeof(imgxf_driver_entry) ||
+        hd.tables_off != hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_driver_unit) || hd.tables_off > total)
+        return IMGXF_ERR_ARG;
+    if (hd.n_units == 0) return IMGXF_OK;
+    if (!block_dev || !out) return IMGXF_ERR_NULL;
+    if ((((uintptr_t)out) & 15) || (((uintptr_t)block_dev) & 7) || hd.out_bytes > out_cap) return IMGXF_ERR_ARG;
+    // the records bound every address the kernels form: check them against the frames, the output and the block
+    const imgxf_driver_entry* entries = (const imgxf_driver_entry*)(hb + hd.entries_off);
+    const imgxf_driver_unit* units = (const imgxf_driver_unit*)(hb + hd.units_off);
+    const int64_t t0 = hd.tables_off / 4;
+    for (int i = 0; i < hd.n_entries; ++i) {
+        const imgxf_driver_entry& e = entries[i];
+        if (e.status != IMGXF_DRIVER_OK) continue;
+        if (!e.src) return IMGXF_ERR_NULL;
+        if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.oh < 1 || e.ow < 1 || e.oh > 32767 || e.ow > 32767 ||
+            e.src_stride < (int64_t)e.w * 3 || e.unit_rows < 1)
+            return IMGXF_ERR_SHAPE;
+        if (e.out_off < 0 || (e.out_off & 15) || (uint64_t)e.out_off + (uint64_t)e.oh * e.ow * 3 > hd.out_bytes) return IMGXF_ERR_ARG;
+        switch (e.op) {
+            case IMGXF_DRIVER_SCALE:
+                if (e.win_top < 0 || e.win_left < 0 || e.win_h < 1 || e.win_w < 1 || e.win_top + e.win_h > e.oh ||
+                    e.win_left + e.win_w > e.ow || e.ksx < 1 || e.ksy < 1)
+                    return IMGXF_ERR_SHAPE;
+                if (e.row0 < 0 || e.nrows < 1 || e.row0 + e.nrows > e.h || e.col0 < 0 || e.ncols < 1 || e.col0 + e.ncols > e.w)
+                    return IMGXF_ERR_SHAPE;
+                if (e.bounds_x < t0 || e.bounds_x + 2 * (int64_t)e.win_w > words || e.coeffs_x < t0 ||
+                    e.coeffs_x + (int64_t)e.win_w * e.ksx > words || e.bounds_y < t0 || e.bounds_y + 2 * (int64_t)e.win_h > words ||
+                    e.coeffs_y < t0 || e.coeffs_y + (int64_t)e.win_h * e.ksy > words)
+                    return IMGXF_ERR_ARG;
+                {                                             // every column's taps inside the staged span
+                    const int32_t* bx = (const int32_t*)hb + e.bounds_x;
+                    for (int x = 0; x < e.win_w; ++x)
+                        if (bx[2 * x] < e.col0 || bx[2 * x + 1] < 0 || bx[2 * x + 1] > e.ksx || bx[2 * x] + bx[2 * x + 1] > e.col0 + e.ncols)
+                            return IMGXF_ERR_ARG;
+                    const int32_t* by = (const int32_t*)hb + e.bounds_y;
+                    for (int y = 0; y < e.win_h; ++y)
+                        if (by[2 * y] < 0 || by[2 * y + 1] < 1 || by[2 * y + 1] > e.ksy || by[2 * y] + by[2 * y + 1] > e.h ||
+                            (y && by[2 * y] < by[2 * y - 2]))
+                            return IMGXF_ERR_ARG;
+                }
+                break;
+            case IMGXF_DRIVER_SHEAR:
+                if (e.oh != e.h) return IMGXF_ERR_SHAPE;
+                break;
+            case IMGXF_DRIVER_NOISE:
+                if (!e.noise) return IMGXF_ERR_NULL;
+                if (e.noise & 3) return IMGXF_ERR_ARG;
+                /* fall through */
+            case IMGXF_DRIVER_ROTATION: case IMGXF_DRIVER_BRIGHTNESS: case IMGXF_DRIVER_CONTRAST:
+                if (e.oh != e.h || e.ow != e.w) return IMGXF_ERR_SHAPE;
+                break;
+            case IMGXF_DRIVER_TRANSLATION:
+                if (e.oh != e.h || e.ow != e.w || e.dx < -e.w || e.dx > e.w || e.dy < -e.h || e.dy > e.h) return IMGXF_ERR_SHAPE;
+                break;
+            default: return IMGXF_ERR_ARG;
+        }
+    }
+    for (int k = 0; k < hd.n_units; ++k) {
+        const imgxf_driver_unit& u = units[k];
+        if (u.entry < 0 || u.entry >= hd.n_entries || entries[u.entry].status != IMGXF_DRIVER_OK) return IMGXF_ERR_ARG;
+        const imgxf_driver_entry& e = entries[u.entry];
+        if (u.y0 < 0 || u.ny < 1 || u.y0 + u.ny > e.oh) return IMGXF_ERR_ARG;
+        if ((e.op == IMGXF_DRIVER_SCALE) != (k >= hd.n_plain)) return IMGXF_ERR_ARG;
+        if (e.op != IMGXF_DRIVER_SCALE) continue;
+        // what the kernel will lay out: the unit's rows come from the tables, held inside [row0, row0 + nrows)
+        const int ja = std::max(u.y0, e.win_top) - e.win_top, jb = std::min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
+        if (jb <= ja) continue;
+        const int32_t* by = (const int32_t*)hb + e.bounds_y;
+        const int lo = std::max(by[2 * ja], e.row0), hi = std::min(by[2 * (jb - 1)] + by[2 * (jb - 1) + 1], e.row0 + e.nrows);
+        if (hi <= lo || pl_lds_bytes(hi - lo, e.win_w, e.ncols) > hd.lds_bytes) return IMGXF_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t ce = hipMemcpyAsync(block_dev, block_host, (size_t)total, hipMemcpyHostToDevice, st);
+    if (ce != hipSuccess) return (int)ce;
+    const u8* db = (const u8*)block_dev;
+    if (hd.n_plain)
+        hipLaunchKernelGGL(driver_list_plain_kernel, dim3((unsigned)hd.n_plain), dim3(DL_THREADS), 0, st, db, hd.entries_off,
+                           hd.units_off, out);
+    if (hd.n_units > hd.n_plain)
+        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(hd.n_units - hd.n_plain)), dim3(DL_THREADS),
+                           (size_t)hd.lds_bytes, st, db, hd.entries_off, hd.units_off, hd.n_plain, out);
+    return launch_status();
+}

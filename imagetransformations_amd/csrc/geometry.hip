@@ -2,6 +2,7 @@
 //   Image.new + Image.crop + Image.paste   /root/reference/transformation.py:187-193,287-305
 //   Image.transpose(ROTATE_90/180/270)     fast paths of Image.rotate, PIL/Image.py:2513-2521
 #include "imgxf_common.h"
+#include "pixel_ops.h"
 #include <string.h>
 
 namespace imgxf {
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void translate_kernel(View s, View d, int dxb,
             const u8* sp = row_in ? s.row(f, ys) - dxb : nullptr;
             for (int e = 0; e < nv; ++e) {
                 const int b = xb + e;
-                dp[e] = (row_in && b >= c0 && b < c1) ? sp[b] : (u8)(o[e >> 2] >> (8 * (e & 3)));
+                dp[e] = translate_byte(sp, row_in, b, c0, c1, (u8)(o[e >> 2] >> (8 * (e & 3))));
             }
         }
     }

@@ -1,0 +1,83 @@
+// Per-pixel statements shared by the per-op kernels (affine.hip, geometry.hip, pointwise.hip) and the record-driven list
+// kernel (driver_list.hip): each piece of arithmetic that has to match Pillow / NumPy / OpenCV bit for bit is stated once.
+#pragma once
+#include "imgxf_common.h"
+
+namespace imgxf {
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Precise: fp64 with every multiply/add rounded separately (no FMA contraction), i.e. the
+// exact sequence libImaging's C code performs on x86-64 -> bit-identical to Pillow.
+struct PreciseArith {
+    typedef double T;
+    static __device__ __forceinline__ T mul(T a, T b) { return __dmul_rn(a, b); }
+    static __device__ __forceinline__ T add(T a, T b) { return __dadd_rn(a, b); }
+    static __device__ __forceinline__ T sub(T a, T b) { return __dsub_rn(a, b); }
+};
+
+// libImaging BICUBIC(v, v1, v2, v3, v4, d)
+template <class A>
+__device__ __forceinline__ typename A::T cubic(typename A::T v1, typename A::T v2, typename A::T v3,
+                                               typename A::T v4, typename A::T d) {
+    typedef typename A::T T;
+    const T p1 = v2;
+    const T p2 = A::add(-v1, v3);
+    const T p3 = A::sub(A::add(A::mul((T)2, A::sub(v1, v2)), v3), v4);
+    const T p4 = A::add(A::sub(A::add(-v1, v2), v3), v4);
+    return A::add(p1, A::mul(d, A::add(p2, A::mul(d, A::add(p3, A::mul(d, p4))))));
+}
+
+// libImaging affine_fixed (NEAREST): source pixel of output (x, y) for the 16.16 matrix of affine_fixed_matrix; int
+// arithmetic wraps exactly like the C `int` accumulators
+__device__ __forceinline__ void affine_fixed_src(const int* fx, int x, int y, int& xin, int& yin) {
+    const int xx = (int)((u32)fx[2] + (u32)fx[1] * (u32)y + (u32)fx[0] * (u32)x);
+    const int yy = (int)((u32)fx[5] + (u32)fx[4] * (u32)y + (u32)fx[3] * (u32)x);
+    xin = xx >> 16;
+    yin = yy >> 16;
+}
+
+// libImaging's fp64 sequence for one RGB pixel of a horizontal-only bicubic transform (m3 == 0, m4 == 1, m5 integral):
+// row = the source row (clamped), yok = the row passes the bounds test, a1y = m1 * (y + 0.5), sw = source width
+__device__ __forceinline__ void bicubic_row_exact_px(const u8* row, int sw, bool yok, double m0, double a1y, double m2,
+                                                     const u8* fill, int x, u8 (&px)[3]) {
+    constexpr int C = 3;
+    const double xc = (double)x + 0.5;
+    double xin = __dadd_rn(__dadd_rn(__dmul_rn(m0, xc), a1y), m2);
+    if (!(yok && xin >= 0.0 && xin < (double)sw)) {
+#pragma unroll
+        for (int j = 0; j < C; ++j) px[j] = fill[j];
+        return;
+    }
+    xin -= 0.5;
+    const double xfl = floor(xin);
+    const int xi = (int)xfl;
+    const double dx = xin - xfl;
+    int xs[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) xs[t] = clampi(xi - 1 + t, 0, sw - 1) * C;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const double v = cubic<PreciseArith>((double)row[xs[0] + j], (double)row[xs[1] + j],
+                                             (double)row[xs[2] + j], (double)row[xs[3] + j], dx);
+        px[j] = v <= 0.0 ? (u8)0 : (v >= 255.0 ? (u8)255 : (u8)(int)v);
+    }
+}
+
+// cv2.convertScaleAbs before its saturating, round-half-even pack: |alpha * p + beta|
+__device__ __forceinline__ float scale_abs_value(float p, float alpha, float beta) { return fabsf(p * alpha + beta); }
+
+// np.clip(p.astype(f32) + z, 0, 255).astype(u8); NaN noise is outside the contract
+__device__ __forceinline__ u32 add_noise_byte(float p, float z) {
+    float v = __fadd_rn(p, z);
+    v = fminf(fmaxf(v, 0.0f), 255.0f);
+    return (u32)(int)v;
+}
+
+// apply_translation, byte b of a destination row: sp = the source row moved by the shift (source row - dxb; only read
+// when row_in), [c0, c1) = the destination bytes that have a source
+__device__ __forceinline__ u8 translate_byte(const u8* sp, bool row_in, int b, int c0, int c1, u8 fill) {
+    return (row_in && b >= c0 && b < c1) ? sp[b] : fill;
+}
+
+} // namespace imgxf

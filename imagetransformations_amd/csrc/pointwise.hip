@@ -8,6 +8,7 @@
 // All are pure HBM streams: one lane moves 16 bytes per access whenever the row base is
 // 16-byte aligned, rows are walked grid-stride so a 4K batch launches >= 2048 workgroups.
 #include "imgxf_common.h"
+#include "pixel_ops.h"
 #include <string.h>
 
 namespace imgxf {
@@ -95,7 +96,7 @@ struct BlendOp {
 struct ScaleAbsOp {
     float alpha, beta;
     __device__ __forceinline__ float operator()(float pa, float, int) const {
-        return fabsf(pa * alpha + beta);
+        return scale_abs_value(pa, alpha, beta);
     }
 };
 
@@ -191,11 +192,7 @@ __global__ __launch_bounds__(256) void add_noise_kernel(View s, View nz, View d)
         }
         u32 o = 0;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = __fadd_rn((float)((pv >> (8 * e)) & 0xffu), z[e]);
-            v = fminf(fmaxf(v, 0.0f), 255.0f);   // np.clip; NaN noise is outside the contract
-            o |= ((u32)(int)v) << (8 * e);
-        }
+        for (int e = 0; e < 4; ++e) o |= add_noise_byte((float)((pv >> (8 * e)) & 0xffu), z[e]) << (8 * e);
         if (vec) *(u32*)dp = o;
         else for (int e = 0; e < nv; ++e) dp[e] = (u8)(o >> (8 * e));
     }

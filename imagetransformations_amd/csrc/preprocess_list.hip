@@ -19,6 +19,7 @@
 //   3. ToTensor + Normalize (to_tensor_math.h) and planar stores, 16 bytes per lane where crop % 4 == 0.
 #include "imgxf_common.h"
 #include "resample_coeffs.h"
+#include "resample_list.h"
 #include "to_tensor_math.h"
 #include <map>
 #include <array>
@@ -26,26 +27,13 @@
 
 namespace imgxf {
 
-constexpr int PL_THREADS = 256;
-constexpr int PL_STAGE_ROWS = 4;          // source rows staged (and filtered per coefficient load) at a time
 constexpr int PL_UNIT_ROWS = 16;          // output rows per work unit when the LDS budget allows
 constexpr int PL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB whatever else runs there
-
-static inline int pl_pitch(int crop) { return ((crop + 3) >> 2) * 12; }
-static inline int pl_stage_pitch(int ncols) { return (ncols * 3 + 3 + 3) & ~3; }      // + 3: the row's shift
-static inline int pl_lds_bytes(int rows, int crop, int ncols) {
-    return ((rows * pl_pitch(crop) + 15) & ~15) + PL_STAGE_ROWS * pl_stage_pitch(ncols);
-}
+// (PL_THREADS, PL_STAGE_ROWS, pl_pitch, pl_stage_pitch, pl_lds_bytes, pl_rows_bound: resample_list.h)
 
 // geometry of one frame as the caller states it
 struct PlGeom { int h, w, nh, nw, left, top; };
 
-// Source rows that `ny` consecutive output rows can touch: the windows of precompute_coeffs are at most ksize wide and
-// their starts advance by in / out per row
-static inline int pl_rows_bound(int ny, int in, int out, int ksize) {
-    const int r = (int)ceil((ny - 1) * ((double)in / out)) + ksize;
-    return r < in ? r : in;
-}
 static inline int pl_cols_bound(int crop, int in, int out, int ksize) { return pl_rows_bound(crop, in, out, ksize); }
 
 // Output rows per unit: the most, up to PL_UNIT_ROWS, whose touched rows fit the budget beside the staging (0: none does)
@@ -81,57 +69,7 @@ __global__ __launch_bounds__(PL_THREADS) void preprocess_list_kernel(const u8* _
     const int nrows = r_hi - r_lo;
     u8* mid = pl_lds;
     u8* stage = pl_lds + ((nrows * pitch + 15) & ~15);
-    const int spitch = (fr.ncols * 3 + 3 + 3) & ~3;
-    const u8* src = (const u8*)fr.data;
-
-    for (int g0 = 0; g0 < nrows; g0 += PL_STAGE_ROWS) {
-        int sh[PL_STAGE_ROWS], ndw[PL_STAGE_ROWS];
-        const u32* base[PL_STAGE_ROWS];
-#pragma unroll
-        for (int g = 0; g < PL_STAGE_ROWS; ++g) {
-            const int r = min(r_lo + g0 + g, r_hi - 1);
-            const u8* p = src + (int64_t)r * fr.row_stride + (int64_t)fr.col0 * 3;
-            sh[g] = (int)(((uintptr_t)p) & 3);
-            base[g] = (const u32*)(p - sh[g]);
-            ndw[g] = g0 + g < nrows ? (sh[g] + fr.ncols * 3 + 3) >> 2 : 0;
-        }
-        for (int i = tid; i < (spitch >> 2); i += PL_THREADS) {
-            u32 v[PL_STAGE_ROWS];
-#pragma unroll
-            for (int g = 0; g < PL_STAGE_ROWS; ++g) v[g] = i < ndw[g] ? base[g][i] : 0u;
-#pragma unroll
-            for (int g = 0; g < PL_STAGE_ROWS; ++g) ((u32*)(stage + g * spitch))[i] = v[g];
-        }
-        __syncthreads();
-        for (int x = tid; x < crop; x += PL_THREADS) {
-            const int xmin = bx[2 * x] - fr.col0, cnt = bx[2 * x + 1];
-            const int* k = kx + (int64_t)x * fr.ksx;
-            int acc[PL_STAGE_ROWS][3];
-#pragma unroll
-            for (int g = 0; g < PL_STAGE_ROWS; ++g)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[g][c] = 1 << (PRECISION_BITS - 1);
-            const u8* p0 = stage + xmin * 3;
-            for (int t = 0; t < cnt; ++t) {
-                const int w = k[t];
-#pragma unroll
-                for (int g = 0; g < PL_STAGE_ROWS; ++g) {
-                    const u8* p = p0 + g * spitch + sh[g] + t * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) acc[g][c] += mul24((int)p[c], w);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < PL_STAGE_ROWS; ++g) {
-                if (g0 + g < nrows) {
-                    u8* m = mid + (g0 + g) * pitch + x * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) m[c] = clip8(acc[g][c]);
-                }
-            }
-        }
-        __syncthreads();
-    }
+    pl_horizontal_pass((const u8*)fr.data, fr.row_stride, fr.col0, fr.ncols, r_lo, r_hi, bx, kx, fr.ksx, crop, mid, pitch, stage, tid);
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int nq = (crop + 3) >> 2;
@@ -145,16 +83,7 @@ __global__ __launch_bounds__(PL_THREADS) void preprocess_list_kernel(const u8* _
         const int kv = lane < cnt ? k[lane] : 0;
         for (int q = lane; q < nq; q += 64) {
             int acc[12];
-#pragma unroll
-            for (int b = 0; b < 12; ++b) acc[b] = 1 << (PRECISION_BITS - 1);
-            const u32* p = (const u32*)(mid + ymin * pitch + q * 12);
-            for (int t = 0; t < cnt; ++t) {
-                const int w = t < 64 ? __builtin_amdgcn_readlane(kv, t) : k[t];
-                const u32 d[3] = {p[0], p[1], p[2]};
-#pragma unroll
-                for (int b = 0; b < 12; ++b) acc[b] += mul24((int)((d[b >> 2] >> (8 * (b & 3))) & 0xffu), w);
-                p += pitch >> 2;
-            }
+            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
             const int npx = min(4, crop - 4 * q);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {

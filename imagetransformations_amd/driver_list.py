@@ -1,0 +1,182 @@
+"""Seven of the driver's eight transformation types on a LIST of RGB frames of any sizes in one record-driven device pass
+(csrc/driver_list.hip): every entry carries its own frame, type and drawn value, and is bit for bit what
+`transformation._TENSOR_FNS[type]` / `ops.add_noise` return for that frame.  One host-to-device copy of one block and two
+launches, whatever the number of frames, entries or distinct sizes; no resample plan is created or cached.
+
+Blur is not here: the float Gaussian runs on four kernel families that agree to the 1e-5 contract, not to the byte, so
+it stays on the grouped route (batched.run_grouped), grouped by (size, radius)."""
+from __future__ import annotations
+
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _ffi as F
+from . import batched
+
+# One workgroup of the scale kernel keeps, in LDS, the horizontally filtered source rows its output rows touch (uint8,
+# 12 * ceil(window width / 4) bytes each) and four staged source-row spans, as preprocess_list's does (tensor_maps.py);
+# an entry of which not even one row fits is refused to the caller's route.
+DRIVER_LIST_LDS_BYTES = 64 * 1024
+
+# The output allocation is a whole number of rows of batched.BLOCK_ROW RGB pixels, and outputs start on multiples of 48
+# bytes (whole pixels): a caller can hand the block as one [rows, BLOCK_ROW, 3] image to any kernel (batched.CopyBack
+# expands it to RGBX in one launch).
+BLOCK_ROW_BYTES = 3 * batched.BLOCK_ROW
+
+TYPES = {'scale': 0, 'rotation': 1, 'lighten_darken': 2, 'contrast': 3, 'shear': 4, 'translation': 5, 'gaussian_noise': 6}
+OK, REFUSED_LDS, REFUSED_SIZE, REFUSED_TURN, REFUSED_FORMAT, REFUSED_OTHER = range(6)      # imgxf_driver_entry.status
+
+_HEADER = np.dtype([(k, "<i4") for k in ("n_entries", "n_units", "n_plain", "lds_bytes", "entries_off", "units_off",
+                                         "tables_off", "total_bytes")] + [("out_bytes", "<u8")])
+_ENTRY = np.dtype([("src", "<u8"), ("src_stride", "<i8"), ("noise", "<u8"), ("out_off", "<i8")] +
+                  [(k, "<i4") for k in ("op", "status", "h", "w", "oh", "ow", "unit_rows", "frame")] +
+                  [("alpha", "<f4"), ("beta", "<f4"), ("dx", "<i4"), ("dy", "<i4"), ("fx", "<i4", (6,))] +
+                  [(k, "<i4") for k in ("win_top", "win_left", "win_h", "win_w")] + [("m1", "<f8"), ("m2", "<f8")] +
+                  [(k, "<i4") for k in ("ksx", "ksy", "bounds_x", "coeffs_x", "bounds_y", "coeffs_y", "row0", "nrows",
+                                        "col0", "ncols")])              # struct imgxf_driver_entry (include/imgxf.h)
+_UNIT = np.dtype([(k, "<i4") for k in ("entry", "y0", "ny", "lds_bytes")])
+
+
+def layout(geometry, params, lds_bytes: int = DRIVER_LIST_LDS_BYTES, pinned: bool = False):
+    """The host half (imgxf_driver_list_layout_host; no device is touched) for int32 [N, 5] geometry rows
+    (frame, type code, h, w, channels) and float64 [N, 2] parameters.  Returns a dict: `block` (uint8 array), `out_off`
+    (int64 [N], -1 for a refused entry), `out_hw` (int32 [N, 2]), `status` (int32 [N]), `out_bytes`, `lds_bytes`, and
+    `owner` (the pinned tensor that holds the block when `pinned`)."""
+    geometry = np.ascontiguousarray(geometry, np.int32).reshape(-1, 5)
+    params = np.ascontiguousarray(params, np.float64).reshape(-1, 2)
+    n = len(geometry)
+    if len(params) != n:
+        raise ValueError("one parameter row per entry")
+    out_off, out_hw, status = np.empty(n, np.int64), np.empty((n, 2), np.int32), np.empty(n, np.int32)
+    need, out_bytes, lds = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int32(0)
+    gp = geometry.ctypes.data if n else None
+    pp = params.ctypes.data if n else None
+    F.call("imgxf_driver_list_layout_host", gp, pp, n, int(lds_bytes), None, 0, ctypes.byref(need), None, None, None, None, None)
+    owner = torch.empty(need.value, dtype=torch.uint8, pin_memory=True) if pinned else None
+    block = owner.numpy() if pinned else np.empty(need.value, np.uint8)
+    F.call("imgxf_driver_list_layout_host", gp, pp, n, int(lds_bytes), block.ctypes.data, block.nbytes, ctypes.byref(need),
+           out_off.ctypes.data, out_hw.ctypes.data, status.ctypes.data, ctypes.byref(out_bytes), ctypes.byref(lds))
+    return {"block": block, "owner": owner, "out_off": out_off, "out_hw": out_hw, "status": status,
+            "out_bytes": int(out_bytes.value), "lds_bytes": int(lds.value)}
+
+
+def block_views(block: np.ndarray):
+    """(header, entry records, work units) of a `layout` block as structured views into it."""
+    hd = block[:_HEADER.itemsize].view(_HEADER)[0]
+    eo, uo, n, nu = int(hd["entries_off"]), int(hd["units_off"]), int(hd["n_entries"]), int(hd["n_units"])
+    return hd, block[eo:eo + n * _ENTRY.itemsize].view(_ENTRY), block[uo:uo + nu * _UNIT.itemsize].view(_UNIT)
+
+
+def entry_params(transform_type: str, args):
+    """The two doubles the host layout takes for an entry of `plan_transformations`."""
+    if transform_type == 'translation':
+        return float(args[0]), float(args[1])
+    if transform_type == 'gaussian_noise':
+        return 0.0, 0.0
+    if transform_type == 'lighten_darken':
+        return 1.0 + args[0], 0.0                       # ImageEnhance.Brightness's factor, as apply_brightness forms it
+    return float(args[0]), 0.0
+
+
+_in_flight: collections.deque = collections.deque()     # (event, pinned block) of calls whose copy may not have run yet
+
+
+def _keep_until_copied(owner: torch.Tensor, device) -> None:
+    """The library copies the pinned block itself, so torch's host allocator does not know the stream still reads it:
+    the block is held here until an event recorded behind the copy has passed (checked, never waited for)."""
+    while _in_flight and _in_flight[0][0].query():
+        _in_flight.popleft()
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(device))
+    _in_flight.append((ev, owner))
+
+
+def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, guard: int = 0, guard_value: int = 0):
+    """`apply_list` that also returns the call's one output allocation (a flat uint8 device tensor): (block, outputs,
+    refused).  `guard` (a multiple of 16) leaves that many bytes, set to `guard_value`, before, between and after the
+    outputs (tests/test_gpu_driver_list.py)."""
+    frames, entries = list(frames), list(entries)
+    n = len(entries)
+    if guard < 0 or guard % 16:
+        raise ValueError("guard must be a non-negative multiple of 16")
+    geometry, params = np.zeros((n, 5), np.int32), np.zeros((n, 2), np.float64)
+    src, stride, noise = np.zeros(n, np.uint64), np.zeros(n, np.int64), np.zeros(n, np.uint64)
+    device = None
+    views, noises = {}, []
+    for j, (fi, transform_type, args) in enumerate(entries):
+        code = TYPES.get(transform_type)
+        if code is None:
+            raise ValueError(f"apply_list has no type {transform_type!r} (blur stays on the grouped route)")
+        view = views.get(fi)
+        if view is None:
+            t = frames[fi]
+            ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
+            if ok:
+                h, w = int(t.shape[0]), int(t.shape[1])
+                st = t.stride()
+                if h and w and (st[2] != 1 or (w > 1 and st[1] != 3) or (h > 1 and st[0] < 3 * w)):
+                    t = t.contiguous()                  # pixels of a row and their channels must be dense
+                if device is None:
+                    device = t.device
+                elif t.device != device:
+                    raise ValueError("apply_list expects all frames on one device")
+                view = (t, h, w, 3, t.data_ptr(), t.stride(0) if h > 1 else 3 * w)
+            else:
+                view = (None, 0, 0, 0, 0, 0)
+            views[fi] = view
+        t, h, w, c, src[j], stride[j] = view
+        geometry[j] = (fi, code, h, w, c)
+        params[j] = entry_params(transform_type, args)
+        if code == TYPES['gaussian_noise'] and c:
+            z = args[0] if isinstance(args, (tuple, list)) else args
+            if not isinstance(z, torch.Tensor) or z.dtype != torch.float32 or z.device != device or z.numel() != t.numel():
+                raise ValueError("a gaussian_noise entry takes the float32 device tensor of its H * W * 3 normals")
+            z = z.contiguous()
+            noises.append(z)                            # (kept until the launch is queued)
+            noise[j] = z.data_ptr()
+    lay = layout(geometry, params, lds_bytes, pinned=True)
+    host, status, out_hw = lay["block"], lay["status"], lay["out_hw"]
+    hd, rec, _ = block_views(host)
+    refused = np.flatnonzero(status != OK).tolist()
+    if device is None or not int(hd["n_units"]):
+        return None, [None] * n, refused
+    rec["src"], rec["src_stride"], rec["noise"] = src, stride, noise
+    if guard:                                           # respace the outputs: guard bytes before, between and after them
+        taken = status == OK
+        rec["out_off"] += np.where(taken, np.cumsum(taken) * guard, 0)
+        hd["out_bytes"] = int(hd["out_bytes"]) + (int(taken.sum()) + 1) * guard
+    out_bytes = int(hd["out_bytes"])
+    size = -(-out_bytes // BLOCK_ROW_BYTES) * BLOCK_ROW_BYTES
+    with torch.cuda.device(device):
+        block = torch.empty(size, dtype=torch.uint8, device=device) if not guard else \
+            torch.full((size,), guard_value, dtype=torch.uint8, device=device)
+        gpu = torch.empty(host.nbytes, dtype=torch.uint8, device=device)
+        F.call("imgxf_driver_list_u8", host.ctypes.data, gpu.data_ptr(), block.data_ptr(), out_bytes,
+               torch.cuda.current_stream(device).cuda_stream)
+        _keep_until_copied(lay["owner"], device)
+    outputs = [None] * n
+    offs, sizes = rec["out_off"].tolist(), out_hw.tolist()
+    for j in np.flatnonzero(status == OK).tolist():
+        oh, ow = sizes[j]
+        outputs[j] = block[offs[j]:offs[j] + oh * ow * 3].view(oh, ow, 3)
+    return block, outputs, refused
+
+
+def apply_list(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES):
+    """frames: a sequence of [H_i, W_i, 3] uint8 device tensors (views with any row stride and byte offset, read in
+    place); entries: a sequence of (frame index, type, args) with `type` one of TYPES and `args` what
+    `transformation.plan_transformations` puts in a plan — for 'gaussian_noise' the float32 device tensor of the
+    H * W * 3 normals the driver drew (already scaled: what `ops.add_noise` takes).
+
+    Returns (outputs, refused).  outputs[j] is the [H', W', 3] uint8 result of entry j, bit for bit
+    `transformation._TENSOR_FNS[type](frames[i][None], *args)[0]` (`ops.add_noise` for noise): a view, starting on a
+    16-byte boundary, into the ONE allocation the call makes (shear widens the frame: W' = W + ceil(shear * H)).
+    `refused` lists the entries the pass does not take (outputs[j] is None; the caller runs them through its own
+    route): a scale whose touched rows do not fit `lds_bytes` or whose resized width or height would be below 1, a
+    rotation that `ops.rotate_turns` sends to a transpose, a frame that is not 3-channel uint8.  A refusal never raises
+    and nothing here touches `random` or `np.random`."""
+    _, outputs, refused = apply_list_block(frames, entries, lds_bytes)
+    return outputs, refused

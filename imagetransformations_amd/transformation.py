@@ -370,6 +370,10 @@ def save_image(img: Image.Image, path: str, **params) -> None:
         img.save(path, **params)
 
 
+# The batched driver on frames of different sizes (driver_list.apply_list: seven of the eight types of all sizes in at most
+# two record-driven device passes per chunk, instead of one launch per (size, type, drawn value)).  "auto": a chunk that
+# holds more than one frame size takes it, a uniform chunk keeps the grouped route; "0": never; "1": always.
+DRIVER_LIST = os.environ.get("IMGXF_DRIVER_LIST", "auto")
 DRIVER = os.environ.get("IMGXF_DRIVER", "batched")       # "per-image": apply_all_transformations runs the reference's literal loop
 DRIVER_CHUNK = 256                                        # images per pass of the batched driver inside apply_all_transformations
 
@@ -379,7 +383,9 @@ def apply_all_transformations(images):
     Same draws (`random`, `np.random`), same names, same order, same pixels as the literal loop
     (`apply_all_transformations_per_image`, which tests/test_gpu_facade.py holds it against); since late round 3 the work is
     done DRIVER_CHUNK images at a time by the batched driver — images of one size share their uploads, launches and copies
-    back.  A chunk with an image that is not 8-bit RGB, and `IMGXF_DRIVER=per-image`, take the literal loop."""
+    back.  A chunk that holds more than one image size (`DRIVER_LIST`, "auto") runs everything but blur in at most two
+    `driver_list.apply_list` calls, whatever the number of sizes: the same draws, names, order and pixels.  A chunk with an
+    image that is not 8-bit RGB, and `IMGXF_DRIVER=per-image`, take the literal loop."""
     if DRIVER == "per-image":
         return apply_all_transformations_per_image(images)
     images = list(images)
@@ -524,7 +530,12 @@ def apply_all_transformations_batched_named(images, _sink=None, _tee=False):
     are not 8-bit RGB take the per-image path.  images: [(PIL image, path)] — or [(frame, path)] with [H, W, 3] uint8
     DEVICE tensors as the device JPEG reader returns them (`jpeg_decode.decode`): those are never copied to the host.  `_sink(out, names)`, when given,
     consumes a group's result ON THE DEVICE ([B, H, W, 3] tensor + its file names) instead of it being copied back:
-    those entries come back as (file name, None)."""
+    those entries come back as (file name, None).  With `DRIVER_LIST` ("auto": more than one image size among `images`)
+    the seven types other than blur of ALL sizes run in at most two `driver_list.apply_list` calls instead of one launch per
+    (size, type, value) — the second one for the noise entries, once their numbers have been collected; entries that call
+    refuses, blur and the Philox noise keep the groups."""
+    if DRIVER_LIST not in ("auto", "0", "1"):
+        raise ValueError(f'DRIVER_LIST / IMGXF_DRIVER_LIST must be "auto", "0" or "1", got {DRIVER_LIST!r}')
     dev = _device()
     plans, noise = [], {}
     draws = []                                          # (i, k, (h, w, 3), scale): np.random.normal calls in the per-image loop's order
@@ -580,7 +591,28 @@ def apply_all_transformations_batched_named(images, _sink=None, _tee=False):
             return ops.add_noise(batch, torch.stack(zs) if isinstance(zs[0], torch.Tensor) else staging.upload(zs, dev))
         return _TENSOR_FNS[transform_type](batch, *args)
 
+    # Frames of different sizes (DRIVER_LIST): everything but blur and the opt-in Philox noise leaves the groups and runs in
+    # two list calls for the whole chunk, the noise entries in the second one, after the other work has been queued.
+    def list_phase(transform_type, args):
+        if transform_type == 'blur' or (transform_type == 'gaussian_noise' and NOISE_RNG == "device"):
+            return None
+        return 1 if transform_type == 'gaussian_noise' else 0
+
+    def run_list(phase, frames, items):
+        from . import driver_list
+        if phase == 1:
+            collect_noise()
+        entries = []
+        for f, transform_type, args, i, k in items:
+            if transform_type == 'gaussian_noise':
+                z = noise[(i, k)]
+                args = (z if isinstance(z, torch.Tensor) else staging.upload(z, dev),)
+            entries.append((f, transform_type, args))
+        return driver_list.apply_list_block(frames, entries)
+
+    sizes = {batched.size_of(img) for img, _ in images if batched.is_rgb(img)}
+    use_list = DRIVER_LIST == "1" or (DRIVER_LIST == "auto" and len(sizes) > 1)
     # (noise groups last: their numbers come from the side stream's generator, which runs meanwhile)
     results = batched.run_grouped([img for img, _ in images], plans, dev, run_group, order=lambda g: g[0] == 'gaussian_noise',
-                                  other=per_image, sink=_sink, tee=_tee)
+                                  other=per_image, sink=_sink, tee=_tee, list_route=(list_phase, run_list) if use_list else None)
     return [(new_filename, results[i][k]) for i, plan in enumerate(plans) for k, (_, _, new_filename) in enumerate(plan)]
