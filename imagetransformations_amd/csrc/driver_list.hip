@@ -1,25 +1,31 @@
 // The transformations of apply_all_transformations on a LIST of entries over RGB frames of different sizes
 // (driver_list.apply_list): seven of the driver's eight types — scale, rotation, lighten_darken, contrast, shear,
-// translation, gaussian_noise — each entry with its own frame, type and drawn value, bit for bit what the per-type entry
-// points return (blur is not here: its four kernel families agree to 1e-5, not to the byte).
+// translation, gaussian_noise — and the three further bodies of the later twelve-type driver — flip, crop + resize
+// (rand_crop), perspective warp; its zoom is scale — each entry with its own frame, type and drawn value, bit for bit what
+// the per-type entry points return (blur is not here: its four kernel families agree to 1e-5, not to the byte).
 //
 // HOST half (imgxf_driver_list_layout_host, no device work): from each entry's geometry and parameters one block of
 //   header | entry records | work units | coefficient tables
 // Lanczos tables are precompute_coeffs' (build_coeffs, resample_coeffs.h), sliced to the centre-crop window for factors
-// above 1 as resize_crop's plans slice them; entries of equal (in, out, window) on an axis share one table, so host work
-// grows with the number of distinct geometries.  Rotation matrices are ops.rotate_matrix's (Python's round(., 15) in
+// above 1 as resize_crop's plans slice them; a crop's are the BICUBIC ones for (cs -> 32).  Entries of equal (filter, in,
+// out, window) on an axis share one table, so host work grows with the number of distinct geometries, and two crops of
+// one size share theirs whatever corners they drew.  Rotation matrices are ops.rotate_matrix's (Python's round(., 15) in
 // double) and go into the record as libImaging's 16.16 coefficients.
 //
-// DEVICE half (imgxf_driver_list_u8): one copy of the block, two launches.  One workgroup per work unit = a band of
-// output rows of one entry; the entry's operation is uniform over the workgroup.
-//   driver_list_plain_kernel: the six types that need no LDS.  The band is a contiguous run of the output; a lane owns 4
+// DEVICE half (imgxf_driver_list_u8): one copy of the block, at most three launches.  One workgroup per work unit = a band
+// of output rows of one entry; the entry's operation is uniform over the workgroup.
+//   driver_list_plain_kernel: the seven types that need no LDS.  The band is a contiguous run of the output; a lane owns 4
 //     consecutive pixels = 3 aligned dwords of it (outputs start on 16-byte boundaries), the per-pixel statements are those
 //     of the per-type kernels (pixel_ops.h).
-//   driver_list_scale_kernel: horizontal Lanczos pass of the touched source rows into an LDS intermediate (uint8, as
-//     Pillow's is), vertical pass from LDS (resample_list.h, the passes of preprocess_list_kernel); below factor 1 the
-//     unit also writes the black canvas around the pasted window.  Its launch alone carries the LDS, so the plain units'
-//     occupancy does not pay for it.
+//   driver_list_persp_kernel: a band of 16 output rows, walked in 64-pixel tiles with the tile body of perspective_kernel
+//     (perspective_tile.h): staged source box in LDS for interior and border tiles, global gather where the box does not
+//     fit.  Its fixed 35 KiB of LDS stay in this launch.
+//   driver_list_scale_kernel: horizontal pass of the touched source rows into an LDS intermediate (uint8, as Pillow's is),
+//     vertical pass from LDS (resample_list.h, the passes of preprocess_list_kernel); below factor 1 the unit also writes
+//     the black canvas around the pasted window; a crop's rows are read in place from its corner in the frame.  Its launch
+//     alone carries the dynamic LDS, so the other units' occupancy does not pay for it.
 #include "imgxf_common.h"
+#include "perspective_tile.h"
 #include "pixel_ops.h"
 #include "resample_coeffs.h"
 #include "resample_list.h"
@@ -34,7 +40,10 @@ namespace imgxf {
 constexpr int DL_THREADS = PL_THREADS;
 constexpr int DL_UNIT_ROWS = 16;          // window rows per scale unit when the LDS budget allows
 constexpr int DL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB
-constexpr int DL_PLAIN_BYTES = 24 * 1024; // output bytes per unit of the other types (at least one row)
+constexpr int DL_PLAIN_BYTES = 24 * 1024; // output bytes per unit of the types without LDS (at least one row)
+constexpr int DL_CROP_OUT = 32;           // rand_crop resizes its window to 32 x 32
+
+static inline bool dl_resamples(int op) { return op == IMGXF_DRIVER_SCALE || op == IMGXF_DRIVER_CROP_RESIZE; }
 
 struct DlGeom { int frame, type, h, w, c; };
 
@@ -93,6 +102,10 @@ __device__ __forceinline__ void dl_pixel(const imgxf_driver_entry& e, const u8* 
             else if (OP == IMGXF_DRIVER_CONTRAST) px[j] = (u8)pack_u8(scale_abs_value(p, e.alpha, e.beta));
             else px[j] = (u8)add_noise_byte(p, z[j]);
         }
+    } else if (OP == IMGXF_DRIVER_FLIP) {
+        const u8* sp = src + (int64_t)y * e.src_stride + (e.w - 1 - x) * 3;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) px[j] = sp[j];
     } else if (OP == IMGXF_DRIVER_TRANSLATION) {
         const int dxb = e.dx * 3, rowbytes = e.w * 3;
         const int c0 = max(dxb, 0), c1 = min(rowbytes, rowbytes + dxb);
@@ -163,8 +176,26 @@ __global__ __launch_bounds__(DL_THREADS) void driver_list_plain_kernel(const u8*
         case IMGXF_DRIVER_SHEAR: dl_band<IMGXF_DRIVER_SHEAR>(e, u, o); break;
         case IMGXF_DRIVER_TRANSLATION: dl_band<IMGXF_DRIVER_TRANSLATION>(e, u, o); break;
         case IMGXF_DRIVER_NOISE: dl_band<IMGXF_DRIVER_NOISE>(e, u, o); break;
+        case IMGXF_DRIVER_FLIP: dl_band<IMGXF_DRIVER_FLIP>(e, u, o); break;
         default: break;
     }
+}
+
+__global__ __launch_bounds__(PV_THREADS) void driver_list_persp_kernel(const u8* __restrict__ block, int entries_off,
+                                                                       int units_off, int unit0, u8* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float box[PV_LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) u8 outt[PV_TH][PV_TW * 3];
+    __shared__ int boxinfo[8];
+    const imgxf_driver_unit u = ((const imgxf_driver_unit*)(block + units_off))[unit0 + blockIdx.x];
+    const imgxf_driver_entry e = ((const imgxf_driver_entry*)(block + entries_off))[u.entry];
+    const PerspCoef k = persp_coef(e.pc, e.ow, e.oh);
+    u8* o = out + e.out_off;
+    const int64_t drs = (int64_t)e.ow * 3;
+    // frames start at any byte and outputs are dense rows of any width: dword staging and dword stores per entry
+    const bool src4 = ((e.src | (uint64_t)e.src_stride) & 3) == 0 && e.src_stride * (int64_t)e.h < ((int64_t)1 << 32);
+    const bool dst4 = ((((uintptr_t)o) | (uintptr_t)drs) & 3) == 0;
+    const PvFrame sf = {(u8*)e.src, e.src_stride, e.h, e.w, src4}, df = {o, drs, e.oh, e.ow, dst4};
+    for (int tx0 = 0; tx0 < e.ow; tx0 += PV_TW) pv_tile<3>(sf, df, k, tx0, u.y0, box, outt, boxinfo);
 }
 
 __global__ __launch_bounds__(DL_THREADS) void driver_list_scale_kernel(const u8* __restrict__ block, int entries_off,
@@ -201,7 +232,8 @@ __global__ __launch_bounds__(DL_THREADS) void driver_list_scale_kernel(const u8*
     const int nrows = r_hi - r_lo;
     u8* mid = dl_lds;
     u8* stage = dl_lds + ((nrows * pitch + 15) & ~15);
-    pl_horizontal_pass((const u8*)e.src, e.src_stride, e.col0, e.ncols, r_lo, r_hi, bx, kx, e.ksx, width, mid, pitch, stage, tid);
+    const u8* src = (const u8*)e.src + (int64_t)e.dy * e.src_stride + e.dx * 3;      // a crop's corner; (0, 0) for a scale
+    pl_horizontal_pass(src, e.src_stride, e.col0, e.ncols, r_lo, r_hi, bx, kx, e.ksx, width, mid, pitch, stage, tid);
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int nq = (width + 3) >> 2;
@@ -244,15 +276,15 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
     const DlGeom* geo = (const DlGeom*)geometry;
 
     // pass over geometry and parameters alone: every record but its tables, which axes share tables -> the sections' sizes
-    struct Axis { int in, out, first, count, ks, bounds, coeffs; };
-    std::map<std::array<int, 4>, int> axis_index;
+    struct Axis { int filter, in, out, first, count, ks, bounds, coeffs; };
+    std::map<std::array<int, 5>, int> axis_index;
     std::vector<Axis> axes;
     size_t table_words = 0;
-    auto axis_of = [&](int in, int out, int first, int count) {
-        const std::array<int, 4> key = {in, out, first, count};
+    auto axis_of = [&](int filter, int in, int out, int first, int count) {
+        const std::array<int, 5> key = {filter, in, out, first, count};
         auto it = axis_index.find(key);
         if (it != axis_index.end()) return it->second;
-        Axis a = {in, out, first, count, coeff_ksize(in, out, IMGXF_RESAMPLE_LANCZOS), -1, -1};
+        Axis a = {filter, in, out, first, count, coeff_ksize(in, out, filter), -1, -1};
         table_words += (size_t)count * (2 + a.ks);
         axis_index.emplace(key, (int)axes.size());
         axes.push_back(a);
@@ -260,7 +292,7 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
     };
     std::vector<imgxf_driver_entry> recs((size_t)n);
     std::vector<int> ax((size_t)n, -1), ay((size_t)n, -1);
-    size_t n_plain = 0, n_scale = 0;
+    size_t n_plain = 0, n_persp = 0, n_scale = 0;
     uint64_t opos = 0;
     int lds_bound = 0;
     for (int i = 0; i < n; ++i) {
@@ -288,13 +320,14 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
                 } else {                                      // factor 1: a resize to the same size
                     e.win_w = nw; e.win_h = nh; e.oh = nh; e.ow = nw;
                 }
+                e.in_h = g.h; e.in_w = g.w;
                 e.ksx = coeff_ksize(g.w, nw, IMGXF_RESAMPLE_LANCZOS);
                 e.ksy = coeff_ksize(g.h, nh, IMGXF_RESAMPLE_LANCZOS);
                 e.unit_rows = dl_unit_rows(g.h, nh, e.ksy, e.win_h, e.win_w, pl_rows_bound(e.win_w, g.w, nw, e.ksx), lds_budget);
                 if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
                 else {
-                    ax[i] = axis_of(g.w, nw, xfirst, e.win_w);
-                    ay[i] = axis_of(g.h, nh, yfirst, e.win_h);
+                    ax[i] = axis_of(IMGXF_RESAMPLE_LANCZOS, g.w, nw, xfirst, e.win_w);
+                    ay[i] = axis_of(IMGXF_RESAMPLE_LANCZOS, g.h, nh, yfirst, e.win_h);
                     lds_bound = std::max(lds_bound, pl_lds_bytes(pl_rows_bound(e.unit_rows, g.h, nh, e.ksy), e.win_w,
                                                                  pl_rows_bound(e.win_w, g.w, nw, e.ksx)));
                 }
@@ -324,7 +357,26 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
                 e.dx = (int)std::max(-(double)g.w, std::min((double)g.w, trunc(p0)));
                 e.dy = (int)std::max(-(double)g.h, std::min((double)g.h, trunc(p1)));
             }
-        } else if (g.type != IMGXF_DRIVER_NOISE) {
+        } else if (g.type == IMGXF_DRIVER_CROP_RESIZE) {
+            const int cs = (int)(0.78 * g.w);                 // int(0.78 * w), in double as Python evaluates it
+            if (cs < 1) st = IMGXF_DRIVER_REFUSED_SIZE;
+            else if (!isfinite(p0) || !isfinite(p1) || p0 < 0.0 || p1 < 0.0 || p0 + cs > g.w || p1 + cs > g.h)
+                st = IMGXF_DRIVER_REFUSED_OTHER;              // the window is not inside the frame
+            else {
+                const int side = DL_CROP_OUT;
+                e.dx = (int)p0; e.dy = (int)p1;
+                e.in_h = cs; e.in_w = cs;
+                e.oh = e.ow = e.win_h = e.win_w = side;
+                e.ksx = e.ksy = coeff_ksize(cs, side, IMGXF_RESAMPLE_BICUBIC);
+                const int ncols = pl_rows_bound(side, cs, side, e.ksx);
+                e.unit_rows = dl_unit_rows(cs, side, e.ksy, side, side, ncols, lds_budget);
+                if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
+                else {
+                    ax[i] = ay[i] = axis_of(IMGXF_RESAMPLE_BICUBIC, cs, side, 0, side);
+                    lds_bound = std::max(lds_bound, pl_lds_bytes(pl_rows_bound(e.unit_rows, cs, side, e.ksy), side, ncols));
+                }
+            }
+        } else if (g.type != IMGXF_DRIVER_NOISE && g.type != IMGXF_DRIVER_FLIP && g.type != IMGXF_DRIVER_PERSPECTIVE) {
             st = IMGXF_DRIVER_REFUSED_OTHER;
         }
         e.status = st;
@@ -333,8 +385,11 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
             // outputs start on multiples of 48: 16-byte aligned, and whole pixels into the block, so that the block as ONE
             // run of RGB pixels can be expanded or copied without knowing where its outputs are
             opos = (opos + (uint64_t)e.oh * e.ow * 3 + 47) / 48 * 48;
-            if (g.type == IMGXF_DRIVER_SCALE) {
+            if (dl_resamples(g.type)) {
                 n_scale += (size_t)(e.win_h + e.unit_rows - 1) / e.unit_rows;
+            } else if (g.type == IMGXF_DRIVER_PERSPECTIVE) {
+                e.unit_rows = PV_TH;
+                n_persp += (size_t)(e.oh + PV_TH - 1) / PV_TH;
             } else {
                 e.unit_rows = std::max(1, DL_PLAIN_BYTES / (e.ow * 3));
                 n_plain += (size_t)(e.oh + e.unit_rows - 1) / e.unit_rows;
@@ -346,7 +401,7 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         if (out_hw) { out_hw[2 * i] = e.oh; out_hw[2 * i + 1] = e.ow; }
         if (status) status[i] = st;
     }
-    const size_t n_units = n_plain + n_scale;
+    const size_t n_units = n_plain + n_persp + n_scale;
     const size_t entries_off = sizeof(imgxf_driver_header);
     const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_driver_entry);
     const size_t tables_off = units_off + n_units * sizeof(imgxf_driver_unit);
@@ -368,24 +423,27 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
     std::vector<int> bv, kv;
     auto build_axis = [&](Axis& a) {
         if (a.bounds >= 0) return;
-        build_coeffs(a.in, a.out, IMGXF_RESAMPLE_LANCZOS, bv, kv);
+        build_coeffs(a.in, a.out, a.filter, bv, kv);
         slice_tables(bv, kv, a.ks, a.first, a.count);
         a.bounds = (int)tpos; memcpy(words + tpos, bv.data(), bv.size() * 4); tpos += bv.size();
         a.coeffs = (int)tpos; memcpy(words + tpos, kv.data(), kv.size() * 4); tpos += kv.size();
     };
     size_t upos = 0;
     int lds_max = 0;
-    for (int i = 0; i < n; ++i) {                             // the units without LDS first: they are the first launch
-        imgxf_driver_entry& e = recs[i];
-        if (e.status != IMGXF_DRIVER_OK || geo[i].type == IMGXF_DRIVER_SCALE) continue;
-        for (int y0 = 0; y0 < e.oh; y0 += e.unit_rows) {
-            imgxf_driver_unit& u = units[upos++];
-            u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, e.oh - y0); u.lds_bytes = 0;
+    for (int warp = 0; warp < 2; ++warp)                      // the units without LDS first: they are the first launch;
+        for (int i = 0; i < n; ++i) {                         // then the perspective units, the second
+            imgxf_driver_entry& e = recs[i];
+            if (e.status != IMGXF_DRIVER_OK || dl_resamples(geo[i].type) ||
+                (geo[i].type == IMGXF_DRIVER_PERSPECTIVE) != (warp == 1))
+                continue;
+            for (int y0 = 0; y0 < e.oh; y0 += e.unit_rows) {
+                imgxf_driver_unit& u = units[upos++];
+                u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, e.oh - y0); u.lds_bytes = 0;
+            }
         }
-    }
     for (int i = 0; i < n; ++i) {
         imgxf_driver_entry& e = recs[i];
-        if (e.status != IMGXF_DRIVER_OK || geo[i].type != IMGXF_DRIVER_SCALE) continue;
+        if (e.status != IMGXF_DRIVER_OK || !dl_resamples(geo[i].type)) continue;
         Axis& x = axes[ax[i]];
         Axis& y = axes[ay[i]];
         build_axis(x);
@@ -412,7 +470,8 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         }
     }
     memcpy(entries, recs.data(), (size_t)n * sizeof(imgxf_driver_entry));
-    hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->n_plain = (int32_t)n_plain; hd->lds_bytes = lds_max;
+    hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->n_plain = (int32_t)n_plain; hd->n_persp = (int32_t)n_persp;
+    hd->lds_bytes = lds_max;
     hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
     hd->total_bytes = (int32_t)total; hd->out_bytes = opos;
     if (lds_bytes) *lds_bytes = lds_max;
@@ -423,7 +482,8 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
     if (!block_host) return IMGXF_ERR_NULL;
     const u8* hb = (const u8*)block_host;
     const imgxf_driver_header hd = *(const imgxf_driver_header*)hb;
-    if (hd.n_entries < 0 || hd.n_units < 0 || hd.n_plain < 0 || hd.n_plain > hd.n_units || hd.lds_bytes < 0 ||
+    if (hd.n_entries < 0 || hd.n_units < 0 || hd.n_plain < 0 || hd.n_persp < 0 ||
+        (int64_t)hd.n_plain + hd.n_persp > hd.n_units || hd.lds_bytes < 0 ||
         hd.lds_bytes > DL_MAX_LDS)
         return IMGXF_ERR_ARG;
     const int64_t total = hd.total_bytes, words = total / 4;
@@ -447,11 +507,18 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
             return IMGXF_ERR_SHAPE;
         if (e.out_off < 0 || (e.out_off & 15) || (uint64_t)e.out_off + (uint64_t)e.oh * e.ow * 3 > hd.out_bytes) return IMGXF_ERR_ARG;
         switch (e.op) {
-            case IMGXF_DRIVER_SCALE:
+            case IMGXF_DRIVER_SCALE: case IMGXF_DRIVER_CROP_RESIZE:
+                if (e.op == IMGXF_DRIVER_SCALE) {             // the tables index the frame, or the window inside it
+                    if (e.dx != 0 || e.dy != 0 || e.in_h != e.h || e.in_w != e.w) return IMGXF_ERR_SHAPE;
+                } else if (e.in_h < 1 || e.in_w < 1 || e.dx < 0 || e.dy < 0 || e.dx > e.w - e.in_w || e.dy > e.h - e.in_h ||
+                           e.oh != DL_CROP_OUT || e.ow != DL_CROP_OUT || e.win_h != e.oh || e.win_w != e.ow) {
+                    return IMGXF_ERR_SHAPE;
+                }
                 if (e.win_top < 0 || e.win_left < 0 || e.win_h < 1 || e.win_w < 1 || e.win_top + e.win_h > e.oh ||
                     e.win_left + e.win_w > e.ow || e.ksx < 1 || e.ksy < 1)
                     return IMGXF_ERR_SHAPE;
-                if (e.row0 < 0 || e.nrows < 1 || e.row0 + e.nrows > e.h || e.col0 < 0 || e.ncols < 1 || e.col0 + e.ncols > e.w)
+                if (e.row0 < 0 || e.nrows < 1 || e.row0 + e.nrows > e.in_h || e.col0 < 0 || e.ncols < 1 ||
+                    e.col0 + e.ncols > e.in_w)
                     return IMGXF_ERR_SHAPE;
                 if (e.bounds_x < t0 || e.bounds_x + 2 * (int64_t)e.win_w > words || e.coeffs_x < t0 ||
                     e.coeffs_x + (int64_t)e.win_w * e.ksx > words || e.bounds_y < t0 || e.bounds_y + 2 * (int64_t)e.win_h > words ||
@@ -464,7 +531,7 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
                             return IMGXF_ERR_ARG;
                     const int32_t* by = (const int32_t*)hb + e.bounds_y;
                     for (int y = 0; y < e.win_h; ++y)
-                        if (by[2 * y] < 0 || by[2 * y + 1] < 1 || by[2 * y + 1] > e.ksy || by[2 * y] + by[2 * y + 1] > e.h ||
+                        if (by[2 * y] < 0 || by[2 * y + 1] < 1 || by[2 * y + 1] > e.ksy || by[2 * y] + by[2 * y + 1] > e.in_h ||
                             (y && by[2 * y] < by[2 * y - 2]))
                             return IMGXF_ERR_ARG;
                 }
@@ -476,8 +543,13 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
                 if (!e.noise) return IMGXF_ERR_NULL;
                 if (e.noise & 3) return IMGXF_ERR_ARG;
                 /* fall through */
-            case IMGXF_DRIVER_ROTATION: case IMGXF_DRIVER_BRIGHTNESS: case IMGXF_DRIVER_CONTRAST:
+            case IMGXF_DRIVER_ROTATION: case IMGXF_DRIVER_BRIGHTNESS: case IMGXF_DRIVER_CONTRAST: case IMGXF_DRIVER_FLIP:
                 if (e.oh != e.h || e.ow != e.w) return IMGXF_ERR_SHAPE;
+                break;
+            case IMGXF_DRIVER_PERSPECTIVE:
+                if (e.oh != e.h || e.ow != e.w || e.unit_rows != PV_TH) return IMGXF_ERR_SHAPE;
+                for (int q = 0; q < 8; ++q)
+                    if (!(e.pc[q] == e.pc[q]) || e.pc[q] - e.pc[q] != 0.0f) return IMGXF_ERR_ARG;     // NaN / inf
                 break;
             case IMGXF_DRIVER_TRANSLATION:
                 if (e.oh != e.h || e.ow != e.w || e.dx < -e.w || e.dx > e.w || e.dy < -e.h || e.dy > e.h) return IMGXF_ERR_SHAPE;
@@ -490,8 +562,11 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
         if (u.entry < 0 || u.entry >= hd.n_entries || entries[u.entry].status != IMGXF_DRIVER_OK) return IMGXF_ERR_ARG;
         const imgxf_driver_entry& e = entries[u.entry];
         if (u.y0 < 0 || u.ny < 1 || u.y0 + u.ny > e.oh) return IMGXF_ERR_ARG;
-        if ((e.op == IMGXF_DRIVER_SCALE) != (k >= hd.n_plain)) return IMGXF_ERR_ARG;
-        if (e.op != IMGXF_DRIVER_SCALE) continue;
+        // the sections: plain units, perspective units (whole 16-row bands: a tile writes PV_TH rows or to the end), resample units
+        const int section = k < hd.n_plain ? 0 : (k < hd.n_plain + hd.n_persp ? 1 : 2);
+        if (section != (dl_resamples(e.op) ? 2 : (e.op == IMGXF_DRIVER_PERSPECTIVE ? 1 : 0))) return IMGXF_ERR_ARG;
+        if (section == 1 && (u.y0 % PV_TH || u.ny != std::min(PV_TH, e.oh - u.y0))) return IMGXF_ERR_ARG;
+        if (section != 2) continue;
         // what the kernel will lay out: the unit's rows come from the tables, held inside [row0, row0 + nrows)
         const int ja = std::max(u.y0, e.win_top) - e.win_top, jb = std::min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
         if (jb <= ja) continue;
@@ -506,8 +581,12 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
     if (hd.n_plain)
         hipLaunchKernelGGL(driver_list_plain_kernel, dim3((unsigned)hd.n_plain), dim3(DL_THREADS), 0, st, db, hd.entries_off,
                            hd.units_off, out);
-    if (hd.n_units > hd.n_plain)
-        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(hd.n_units - hd.n_plain)), dim3(DL_THREADS),
-                           (size_t)hd.lds_bytes, st, db, hd.entries_off, hd.units_off, hd.n_plain, out);
+    if (hd.n_persp)
+        hipLaunchKernelGGL(driver_list_persp_kernel, dim3((unsigned)hd.n_persp), dim3(PV_THREADS), 0, st, db, hd.entries_off,
+                           hd.units_off, hd.n_plain, out);
+    const int unit2 = hd.n_plain + hd.n_persp;
+    if (hd.n_units > unit2)
+        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(hd.n_units - unit2)), dim3(DL_THREADS),
+                           (size_t)hd.lds_bytes, st, db, hd.entries_off, hd.units_off, unit2, out);
     return launch_status();
 }

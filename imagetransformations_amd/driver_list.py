@@ -1,7 +1,9 @@
-"""Seven of the driver's eight transformation types on a LIST of RGB frames of any sizes in one record-driven device pass
-(csrc/driver_list.hip): every entry carries its own frame, type and drawn value, and is bit for bit what
-`transformation._TENSOR_FNS[type]` / `ops.add_noise` return for that frame.  One host-to-device copy of one block and two
-launches, whatever the number of frames, entries or distinct sizes; no resample plan is created or cached.
+"""Seven of the driver's eight transformation types, and the four further ones of the later twelve-type driver
+(transformations_code: vert_flip, rand_crop, zoom, perspective_warp), on a LIST of RGB frames of any sizes in one
+record-driven device pass (csrc/driver_list.hip): every entry carries its own frame, type and drawn value, and is bit for
+bit what `transformation._TENSOR_FNS[type]` / `ops.add_noise` / `ops.flip` / `ops.resize(ops.crop(...))` /
+`ops.perspective` return for that frame.  One host-to-device copy of one block and at most three launches, whatever the
+number of frames, entries or distinct sizes; no resample plan is created or cached.
 
 Blur is not here: the float Gaussian runs on four kernel families that agree to the 1e-5 contract, not to the byte, so
 it stays on the grouped route (batched.run_grouped), grouped by (size, radius)."""
@@ -26,17 +28,21 @@ DRIVER_LIST_LDS_BYTES = 64 * 1024
 # expands it to RGBX in one launch).
 BLOCK_ROW_BYTES = 3 * batched.BLOCK_ROW
 
-TYPES = {'scale': 0, 'rotation': 1, 'lighten_darken': 2, 'contrast': 3, 'shear': 4, 'translation': 5, 'gaussian_noise': 6}
+TYPES = {'scale': 0, 'rotation': 1, 'lighten_darken': 2, 'contrast': 3, 'shear': 4, 'translation': 5, 'gaussian_noise': 6,
+         'vert_flip': 7, 'rand_crop': 8, 'perspective_warp': 10, 'zoom': 0}          # zoom is apply_scale; 9 is no type
+CROP_SIZE = 32                                          # rand_crop's output is CROP_SIZE x CROP_SIZE
 OK, REFUSED_LDS, REFUSED_SIZE, REFUSED_TURN, REFUSED_FORMAT, REFUSED_OTHER = range(6)      # imgxf_driver_entry.status
 
 _HEADER = np.dtype([(k, "<i4") for k in ("n_entries", "n_units", "n_plain", "lds_bytes", "entries_off", "units_off",
-                                         "tables_off", "total_bytes")] + [("out_bytes", "<u8")])
+                                         "tables_off", "total_bytes")] + [("out_bytes", "<u8"), ("n_persp", "<i4"),
+                                                                        ("reserved", "<i4")])
 _ENTRY = np.dtype([("src", "<u8"), ("src_stride", "<i8"), ("noise", "<u8"), ("out_off", "<i8")] +
                   [(k, "<i4") for k in ("op", "status", "h", "w", "oh", "ow", "unit_rows", "frame")] +
                   [("alpha", "<f4"), ("beta", "<f4"), ("dx", "<i4"), ("dy", "<i4"), ("fx", "<i4", (6,))] +
                   [(k, "<i4") for k in ("win_top", "win_left", "win_h", "win_w")] + [("m1", "<f8"), ("m2", "<f8")] +
                   [(k, "<i4") for k in ("ksx", "ksy", "bounds_x", "coeffs_x", "bounds_y", "coeffs_y", "row0", "nrows",
-                                        "col0", "ncols")])              # struct imgxf_driver_entry (include/imgxf.h)
+                                        "col0", "ncols", "in_h", "in_w")] +
+                  [("pc", "<f4", (8,))])                # struct imgxf_driver_entry (include/imgxf.h)
 _UNIT = np.dtype([(k, "<i4") for k in ("entry", "y0", "ny", "lds_bytes")])
 
 
@@ -72,9 +78,9 @@ def block_views(block: np.ndarray):
 
 def entry_params(transform_type: str, args):
     """The two doubles the host layout takes for an entry of `plan_transformations`."""
-    if transform_type == 'translation':
+    if transform_type in ('translation', 'rand_crop'):  # (tx, ty); the crop's corner (x, y)
         return float(args[0]), float(args[1])
-    if transform_type == 'gaussian_noise':
+    if transform_type in ('gaussian_noise', 'vert_flip', 'perspective_warp'):
         return 0.0, 0.0
     if transform_type == 'lighten_darken':
         return 1.0 + args[0], 0.0                       # ImageEnhance.Brightness's factor, as apply_brightness forms it
@@ -104,12 +110,20 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
         raise ValueError("guard must be a non-negative multiple of 16")
     geometry, params = np.zeros((n, 5), np.int32), np.zeros((n, 2), np.float64)
     src, stride, noise = np.zeros(n, np.uint64), np.zeros(n, np.int64), np.zeros(n, np.uint64)
+    coeffs = np.zeros((n, 8), np.float32)
     device = None
     views, noises = {}, []
     for j, (fi, transform_type, args) in enumerate(entries):
         code = TYPES.get(transform_type)
         if code is None:
             raise ValueError(f"apply_list has no type {transform_type!r} (blur stays on the grouped route)")
+        if code == TYPES['perspective_warp']:
+            pc = np.asarray(args[0] if len(args) == 1 else args, np.float64).reshape(-1)
+            with np.errstate(over="ignore"):
+                ok = pc.size == 8 and bool(np.isfinite(pc.astype(np.float32)).all())
+            if not ok:
+                raise ValueError("a perspective_warp entry takes eight finite coefficients")
+            coeffs[j] = pc
         view = views.get(fi)
         if view is None:
             t = frames[fi]
@@ -143,7 +157,7 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
     refused = np.flatnonzero(status != OK).tolist()
     if device is None or not int(hd["n_units"]):
         return None, [None] * n, refused
-    rec["src"], rec["src_stride"], rec["noise"] = src, stride, noise
+    rec["src"], rec["src_stride"], rec["noise"], rec["pc"] = src, stride, noise, coeffs
     if guard:                                           # respace the outputs: guard bytes before, between and after them
         taken = status == OK
         rec["out_off"] += np.where(taken, np.cumsum(taken) * guard, 0)
@@ -169,14 +183,19 @@ def apply_list(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES):
     """frames: a sequence of [H_i, W_i, 3] uint8 device tensors (views with any row stride and byte offset, read in
     place); entries: a sequence of (frame index, type, args) with `type` one of TYPES and `args` what
     `transformation.plan_transformations` puts in a plan — for 'gaussian_noise' the float32 device tensor of the
-    H * W * 3 normals the driver drew (already scaled: what `ops.add_noise` takes).
+    H * W * 3 normals the driver drew (already scaled: what `ops.add_noise` takes).  The later driver's types take: `()`
+    for 'vert_flip'; the drawn corner `(x, y)` for 'rand_crop'; `(coeffs,)`, torchvision's eight coefficients, for
+    'perspective_warp' (ValueError, before any device work, unless they are eight finite numbers); `(factor,)` for
+    'zoom', which is 'scale'.
 
     Returns (outputs, refused).  outputs[j] is the [H', W', 3] uint8 result of entry j, bit for bit
-    `transformation._TENSOR_FNS[type](frames[i][None], *args)[0]` (`ops.add_noise` for noise): a view, starting on a
-    16-byte boundary, into the ONE allocation the call makes (shear widens the frame: W' = W + ceil(shear * H)).
-    `refused` lists the entries the pass does not take (outputs[j] is None; the caller runs them through its own
-    route): a scale whose touched rows do not fit `lds_bytes` or whose resized width or height would be below 1, a
+    `transformation._TENSOR_FNS[type](frames[i][None], *args)[0]` (`ops.add_noise` for noise, `ops.flip`,
+    `ops.resize(ops.crop(frame, (x, y, x + cs, y + cs)), (32, 32), BICUBIC)` with cs = int(0.78 * W), `ops.perspective`):
+    a view, starting on a 16-byte boundary, into the ONE allocation the call makes (shear widens the frame:
+    W' = W + ceil(shear * H); a crop gives 32 x 32).  `refused` lists the entries the pass does not take (outputs[j] is
+    None; the caller runs them through its own route): a scale or crop whose touched rows do not fit `lds_bytes`, a scale
+    whose resized width or height would be below 1, a crop with cs below 1 or its window not inside the frame, a
     rotation that `ops.rotate_turns` sends to a transpose, a frame that is not 3-channel uint8.  A refusal never raises
-    and nothing here touches `random` or `np.random`."""
+    and nothing here touches `random`, `np.random` or torch's generator."""
     _, outputs, refused = apply_list_block(frames, entries, lds_bytes)
     return outputs, refused

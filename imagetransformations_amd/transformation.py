@@ -372,7 +372,8 @@ def save_image(img: Image.Image, path: str, **params) -> None:
 
 # The batched driver on frames of different sizes (driver_list.apply_list: seven of the eight types of all sizes in at most
 # two record-driven device passes per chunk, instead of one launch per (size, type, drawn value)).  "auto": a chunk that
-# holds more than one frame size takes it, a uniform chunk keeps the grouped route; "0": never; "1": always.
+# holds more than one frame size takes it, a uniform chunk keeps the grouped route; "0": never; "1": always.  The twelve-type
+# driver (transformations_code.apply_all_transformations_batched) reads the same knob: eleven types in one pass per call.
 DRIVER_LIST = os.environ.get("IMGXF_DRIVER_LIST", "auto")
 DRIVER = os.environ.get("IMGXF_DRIVER", "batched")       # "per-image": apply_all_transformations runs the reference's literal loop
 DRIVER_CHUNK = 256                                        # images per pass of the batched driver inside apply_all_transformations

@@ -145,7 +145,14 @@ def apply_all_transformations_batched(images):
     `np.random` and `torch` draws in the same order, the same file names and the same pixels in
     the same output order — but every image is uploaded once and all RGB images of one size that
     drew the same (type, value) go through one batched launch (perspective warps and crops of one
-    size share a launch with per-frame coefficients / windows).  images: [(PIL image, name)]."""
+    size share a launch with per-frame coefficients / windows).  images: [(PIL image, name)].
+
+    With `transformation.DRIVER_LIST` ("1", or "auto" when the RGB images hold more than one size) every type but blur of
+    ALL sizes runs in ONE `driver_list.apply_list` call — one copy of one block, at most three launches, no resample plan
+    — instead of one launch per (size, type, value); entries that call refuses, blur and images that are not 8-bit RGB go
+    where they go without it."""
+    if T.DRIVER_LIST not in ("auto", "0", "1"):
+        raise ValueError(f'DRIVER_LIST / IMGXF_DRIVER_LIST must be "auto", "0" or "1", got {T.DRIVER_LIST!r}')
     dev = T._device()
     # ---- draws, image by image, in the order the per-image loop makes them.  The np.random calls (the noise's normals, the
     # crop's two randints) are only listed here, in that order: nothing else uses np.random, so one pass over its stream on
@@ -224,9 +231,28 @@ def apply_all_transformations_batched(images):
             return ops.flip(batch)
         return T._TENSOR_FNS['scale' if transform_type == 'zoom' else transform_type](batch, *args)
 
+    # Frames of different sizes (DRIVER_LIST): everything but blur leaves the groups and runs in one list call for the
+    # whole chunk.  One phase: every np.random number has been drawn above.
+    def run_list(phase, frames, items):
+        from . import driver_list
+        entries = []
+        for f, transform_type, args, i, k in items:
+            if transform_type == 'gaussian_noise':
+                z = extra[(i, k)]
+                args = (z if isinstance(z, torch.Tensor) else staging.upload(z, dev),)
+            elif transform_type == 'perspective_warp':
+                args = (extra[(i, k)],)
+            elif transform_type == 'rand_crop':
+                args = tuple(int(v) for v in extra[(i, k)][:2])
+            entries.append((f, transform_type, args))
+        return driver_list.apply_list_block(frames, entries)
+
+    sizes = {batched.size_of(img) for img, _ in images if batched.is_rgb(img)}
+    use_list = T.DRIVER_LIST == "1" or (T.DRIVER_LIST == "auto" and len(sizes) > 1)
     # perspective warps and crops of one size share a launch whatever they drew (per-frame coefficients / windows)
     results = batched.run_grouped([img for img, _ in images], plans, dev, run_group, other=per_image,
-                                  key=lambda t, args: (t, () if t in ('perspective_warp', 'rand_crop') else args))
+                                  key=lambda t, args: (t, () if t in ('perspective_warp', 'rand_crop') else args),
+                                  list_route=(lambda t, args: None if t == 'blur' else 0, run_list) if use_list else None)
     transformed_images = []
     for i, plan in enumerate(plans):
         for k, (_, _, new_filename) in enumerate(plan):
