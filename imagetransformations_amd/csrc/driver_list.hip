@@ -1,8 +1,10 @@
 // The transformations of apply_all_transformations on a LIST of entries over RGB frames of different sizes
-// (driver_list.apply_list): seven of the driver's eight types — scale, rotation, lighten_darken, contrast, shear,
-// translation, gaussian_noise — and the three further bodies of the later twelve-type driver — flip, crop + resize
-// (rand_crop), perspective warp; its zoom is scale — each entry with its own frame, type and drawn value, bit for bit what
-// the per-type entry points return (blur is not here: its four kernel families agree to 1e-5, not to the byte).
+// (driver_list.apply_list): the driver's eight types — scale, rotation, lighten_darken, contrast, shear, translation,
+// gaussian_noise, blur — and the three further bodies of the later twelve-type driver — flip, crop + resize (rand_crop),
+// perspective warp; its zoom is scale — each entry with its own frame, type and drawn value, bit for bit what the
+// per-type entry points return.  The float Gaussian's four kernel families agree to 1e-5, not to the byte, so a blur is
+// taken where the per-type dispatcher itself would use the LDS-tiled kernel (sepconv_family.h answers that on the host),
+// whose statements the blur units compile too; the others are refused to the caller's route.
 //
 // HOST half (imgxf_driver_list_layout_host, no device work): from each entry's geometry and parameters one block of
 //   header | entry records | work units | coefficient tables
@@ -12,8 +14,9 @@
 // one size share theirs whatever corners they drew.  Rotation matrices are ops.rotate_matrix's (Python's round(., 15) in
 // double) and go into the record as libImaging's 16.16 coefficients.
 //
-// DEVICE half (imgxf_driver_list_u8): one copy of the block, at most three launches.  One workgroup per work unit = a band
-// of output rows of one entry; the entry's operation is uniform over the workgroup.
+// DEVICE half (imgxf_driver_list_u8): one copy of the block, at most three launches plus one per distinct (fixed, radius)
+// among the blur units (driver_list_blur.hip).  One workgroup per work unit = a band of output rows of one entry; the
+// entry's operation is uniform over the workgroup.
 //   driver_list_plain_kernel: the seven types that need no LDS.  The band is a contiguous run of the output; a lane owns 4
 //     consecutive pixels = 3 aligned dwords of it (outputs start on 16-byte boundaries), the per-pixel statements are those
 //     of the per-type kernels (pixel_ops.h).
@@ -29,7 +32,10 @@
 #include "pixel_ops.h"
 #include "resample_coeffs.h"
 #include "resample_list.h"
+#include "sepconv_family.h"
 #include <map>
+#include <algorithm>
+#include <vector>
 #include <array>
 #include <string.h>
 #include <stdio.h>
@@ -42,6 +48,14 @@ constexpr int DL_UNIT_ROWS = 16;          // window rows per scale unit when the
 constexpr int DL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB
 constexpr int DL_PLAIN_BYTES = 24 * 1024; // output bytes per unit of the types without LDS (at least one row)
 constexpr int DL_CROP_OUT = 32;           // rand_crop resizes its window to 32 x 32
+constexpr int DL_BLUR_ROWS = 32;          // output rows per blur unit: sepconv_tile_kernel's tile height
+
+// driver_list_blur.hip: units [unit0, unit0 + count) are blur units of one (fixed, R)
+int driver_list_blur_launch(bool fixed, int R, const u8* block_dev, int entries_off, int units_off, int unit0, int count,
+                            u8* out, hipStream_t st);
+
+static inline bool dl_blurs(int op) { return op == IMGXF_DRIVER_BLUR || op == IMGXF_DRIVER_BLUR_FIXED; }
+static inline int dl_blur_lds(int ks) { return (DL_BLUR_ROWS + ks - 1) * 256 * (int)sizeof(float); }
 
 static inline bool dl_resamples(int op) { return op == IMGXF_DRIVER_SCALE || op == IMGXF_DRIVER_CROP_RESIZE; }
 
@@ -290,9 +304,38 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         axes.push_back(a);
         return (int)axes.size() - 1;
     };
+    // a Gaussian's taps, shared by the entries of equal (code, ksize, sigma): imgxf_gaussian_u8's / imgxf_gaussian_cv_fixed_u8's
+    struct Blur { int rc, ks, coeffs; bool used; Taps taps; };
+    std::map<std::array<int64_t, 3>, int> blur_index;
+    std::vector<Blur> blurs;
+    auto blur_of = [&](int code, int ksize, double sigma) {
+        int64_t bits;
+        memcpy(&bits, &sigma, 8);
+        const std::array<int64_t, 3> key = {code, ksize, bits};
+        auto it = blur_index.find(key);
+        if (it != blur_index.end()) return it->second;
+        Blur b;
+        memset(&b, 0, sizeof(b));
+        const int R = std::max(1, ksize / 2);                 // run_sepconv: a single tap is centred in three
+        b.ks = 2 * R + 1; b.coeffs = -1;
+        float kf[31];
+        if (code == IMGXF_DRIVER_BLUR_FIXED) {
+            uint16_t k[31];
+            b.rc = gaussian_taps_cv_fixed(ksize, sigma, k);
+            if (b.rc == IMGXF_OK) b.rc = fixed_taps(k, ksize, kf);
+        } else {
+            b.rc = gaussian_taps(ksize, sigma, kf);
+        }
+        if (b.rc == IMGXF_OK)
+            for (int i = 0; i < ksize; ++i) b.taps.x[R - ksize / 2 + i] = b.taps.y[R - ksize / 2 + i] = kf[i];
+        blur_index.emplace(key, (int)blurs.size());
+        blurs.push_back(b);
+        return (int)blurs.size() - 1;
+    };
     std::vector<imgxf_driver_entry> recs((size_t)n);
     std::vector<int> ax((size_t)n, -1), ay((size_t)n, -1);
-    size_t n_plain = 0, n_persp = 0, n_scale = 0;
+    std::vector<int> blurred;                                 // the accepted blur entries
+    size_t n_plain = 0, n_persp = 0, n_scale = 0, n_blur = 0;
     uint64_t opos = 0;
     int lds_bound = 0;
     for (int i = 0; i < n; ++i) {
@@ -376,6 +419,24 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
                     lds_bound = std::max(lds_bound, pl_lds_bytes(pl_rows_bound(e.unit_rows, cs, side, e.ksy), side, ncols));
                 }
             }
+        } else if (dl_blurs(g.type)) {
+            if (p0 == 0.0) st = IMGXF_DRIVER_REFUSED_SIZE;    // the drivers hand back the input object itself
+            else if (!(p0 >= 1.0 && p0 <= 31.0) || p0 != floor(p0) || !((int)p0 & 1)) st = IMGXF_DRIVER_REFUSED_OTHER;
+            else {
+                const bool fixed = g.type == IMGXF_DRIVER_BLUR_FIXED;
+                ax[i] = blur_of(g.type, (int)p0, p1);
+                Blur& b = blurs[ax[i]];
+                // float: only where the per-type route would run these statements too; the fixed-point families are
+                // integer-exact and agree to the byte
+                if (b.rc != IMGXF_OK) st = IMGXF_DRIVER_REFUSED_OTHER;
+                else if (!fixed && sepconv_family_c3_dense(false, b.ks / 2, g.h, g.w, b.taps) != SEPCONV_TILE)
+                    st = IMGXF_DRIVER_REFUSED_FAMILY;
+                else if (dl_blur_lds(b.ks) > lds_budget) st = IMGXF_DRIVER_REFUSED_LDS;
+                else {
+                    e.ksx = e.ksy = b.ks;
+                    if (!b.used) { b.used = true; table_words += (size_t)b.ks; }
+                }
+            }
         } else if (g.type != IMGXF_DRIVER_NOISE && g.type != IMGXF_DRIVER_FLIP && g.type != IMGXF_DRIVER_PERSPECTIVE) {
             st = IMGXF_DRIVER_REFUSED_OTHER;
         }
@@ -390,6 +451,10 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
             } else if (g.type == IMGXF_DRIVER_PERSPECTIVE) {
                 e.unit_rows = PV_TH;
                 n_persp += (size_t)(e.oh + PV_TH - 1) / PV_TH;
+            } else if (dl_blurs(g.type)) {
+                e.unit_rows = DL_BLUR_ROWS;
+                n_blur += (size_t)(e.oh + DL_BLUR_ROWS - 1) / DL_BLUR_ROWS;
+                blurred.push_back(i);
             } else {
                 e.unit_rows = std::max(1, DL_PLAIN_BYTES / (e.ow * 3));
                 n_plain += (size_t)(e.oh + e.unit_rows - 1) / e.unit_rows;
@@ -401,7 +466,7 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         if (out_hw) { out_hw[2 * i] = e.oh; out_hw[2 * i + 1] = e.ow; }
         if (status) status[i] = st;
     }
-    const size_t n_units = n_plain + n_persp + n_scale;
+    const size_t n_units = n_plain + n_persp + n_scale + n_blur;
     const size_t entries_off = sizeof(imgxf_driver_header);
     const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_driver_entry);
     const size_t tables_off = units_off + n_units * sizeof(imgxf_driver_unit);
@@ -433,7 +498,7 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
     for (int warp = 0; warp < 2; ++warp)                      // the units without LDS first: they are the first launch;
         for (int i = 0; i < n; ++i) {                         // then the perspective units, the second
             imgxf_driver_entry& e = recs[i];
-            if (e.status != IMGXF_DRIVER_OK || dl_resamples(geo[i].type) ||
+            if (e.status != IMGXF_DRIVER_OK || dl_resamples(geo[i].type) || dl_blurs(geo[i].type) ||
                 (geo[i].type == IMGXF_DRIVER_PERSPECTIVE) != (warp == 1))
                 continue;
             for (int y0 = 0; y0 < e.oh; y0 += e.unit_rows) {
@@ -469,7 +534,26 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
             lds_max = std::max(lds_max, u.lds_bytes);
         }
     }
-    memcpy(entries, recs.data(), (size_t)n * sizeof(imgxf_driver_entry));
+    // the blur units last, each distinct (fixed, R) a contiguous run = one launch; their tables behind the resample ones
+    std::stable_sort(blurred.begin(), blurred.end(), [&](int a, int b) {
+        return recs[a].op != recs[b].op ? recs[a].op < recs[b].op : recs[a].ksx < recs[b].ksx;
+    });
+    for (int i : blurred) {
+        imgxf_driver_entry& e = recs[i];
+        Blur& b = blurs[ax[i]];
+        if (b.coeffs < 0) {
+            b.coeffs = (int)tpos;
+            memcpy(words + tpos, b.taps.x, (size_t)b.ks * 4);
+            tpos += (size_t)b.ks;
+        }
+        e.coeffs_x = e.coeffs_y = b.coeffs;
+        for (int y0 = 0; y0 < e.oh; y0 += DL_BLUR_ROWS) {
+            imgxf_driver_unit& u = units[upos++];
+            u.entry = i; u.y0 = y0; u.ny = std::min(DL_BLUR_ROWS, e.oh - y0); u.lds_bytes = dl_blur_lds(b.ks);
+        }
+    }
+    if (n) memcpy(entries, recs.data(), (size_t)n * sizeof(imgxf_driver_entry));
+    hd->n_blur = (int32_t)n_blur;
     hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->n_plain = (int32_t)n_plain; hd->n_persp = (int32_t)n_persp;
     hd->lds_bytes = lds_max;
     hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
@@ -478,12 +562,15 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
     return IMGXF_OK;
 }
 
-IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint8_t* out, size_t out_cap, void* stream) {
+// The host checks of imgxf_driver_list_u8, before any device work: IMGXF_OK when the block may be copied and launched
+// (or has no units).  Reads the host block alone; the two device addresses are only tested for null and alignment.
+namespace imgxf {
+int driver_list_check(const void* block_host, const void* block_dev, const uint8_t* out, size_t out_cap) {
     if (!block_host) return IMGXF_ERR_NULL;
     const u8* hb = (const u8*)block_host;
     const imgxf_driver_header hd = *(const imgxf_driver_header*)hb;
-    if (hd.n_entries < 0 || hd.n_units < 0 || hd.n_plain < 0 || hd.n_persp < 0 ||
-        (int64_t)hd.n_plain + hd.n_persp > hd.n_units || hd.lds_bytes < 0 ||
+    if (hd.n_entries < 0 || hd.n_units < 0 || hd.n_plain < 0 || hd.n_persp < 0 || hd.n_blur < 0 ||
+        (int64_t)hd.n_plain + hd.n_persp + hd.n_blur > hd.n_units || hd.lds_bytes < 0 ||
         hd.lds_bytes > DL_MAX_LDS)
         return IMGXF_ERR_ARG;
     const int64_t total = hd.total_bytes, words = total / 4;
@@ -514,11 +601,11 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
                            e.oh != DL_CROP_OUT || e.ow != DL_CROP_OUT || e.win_h != e.oh || e.win_w != e.ow) {
                     return IMGXF_ERR_SHAPE;
                 }
-                if (e.win_top < 0 || e.win_left < 0 || e.win_h < 1 || e.win_w < 1 || e.win_top + e.win_h > e.oh ||
-                    e.win_left + e.win_w > e.ow || e.ksx < 1 || e.ksy < 1)
+                if (e.win_top < 0 || e.win_left < 0 || e.win_h < 1 || e.win_w < 1 || (int64_t)e.win_top + e.win_h > e.oh ||
+                    (int64_t)e.win_left + e.win_w > e.ow || e.ksx < 1 || e.ksy < 1)
                     return IMGXF_ERR_SHAPE;
-                if (e.row0 < 0 || e.nrows < 1 || e.row0 + e.nrows > e.in_h || e.col0 < 0 || e.ncols < 1 ||
-                    e.col0 + e.ncols > e.in_w)
+                if (e.row0 < 0 || e.nrows < 1 || (int64_t)e.row0 + e.nrows > e.in_h || e.col0 < 0 || e.ncols < 1 ||
+                    (int64_t)e.col0 + e.ncols > e.in_w)
                     return IMGXF_ERR_SHAPE;
                 if (e.bounds_x < t0 || e.bounds_x + 2 * (int64_t)e.win_w > words || e.coeffs_x < t0 ||
                     e.coeffs_x + (int64_t)e.win_w * e.ksx > words || e.bounds_y < t0 || e.bounds_y + 2 * (int64_t)e.win_h > words ||
@@ -527,11 +614,11 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
                 {                                             // every column's taps inside the staged span
                     const int32_t* bx = (const int32_t*)hb + e.bounds_x;
                     for (int x = 0; x < e.win_w; ++x)
-                        if (bx[2 * x] < e.col0 || bx[2 * x + 1] < 0 || bx[2 * x + 1] > e.ksx || bx[2 * x] + bx[2 * x + 1] > e.col0 + e.ncols)
+                        if (bx[2 * x] < e.col0 || bx[2 * x + 1] < 0 || bx[2 * x + 1] > e.ksx || (int64_t)bx[2 * x] + bx[2 * x + 1] > e.col0 + e.ncols)
                             return IMGXF_ERR_ARG;
                     const int32_t* by = (const int32_t*)hb + e.bounds_y;
                     for (int y = 0; y < e.win_h; ++y)
-                        if (by[2 * y] < 0 || by[2 * y + 1] < 1 || by[2 * y + 1] > e.ksy || by[2 * y] + by[2 * y + 1] > e.in_h ||
+                        if (by[2 * y] < 0 || by[2 * y + 1] < 1 || by[2 * y + 1] > e.ksy || (int64_t)by[2 * y] + by[2 * y + 1] > e.in_h ||
                             (y && by[2 * y] < by[2 * y - 2]))
                             return IMGXF_ERR_ARG;
                 }
@@ -554,6 +641,13 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
             case IMGXF_DRIVER_TRANSLATION:
                 if (e.oh != e.h || e.ow != e.w || e.dx < -e.w || e.dx > e.w || e.dy < -e.h || e.dy > e.h) return IMGXF_ERR_SHAPE;
                 break;
+            case IMGXF_DRIVER_BLUR: case IMGXF_DRIVER_BLUR_FIXED:
+                if (e.oh != e.h || e.ow != e.w || e.unit_rows != DL_BLUR_ROWS) return IMGXF_ERR_SHAPE;
+                if (e.ksx < 3 || e.ksx > 31 || !(e.ksx & 1) || e.ksy != e.ksx) return IMGXF_ERR_ARG;
+                if (e.coeffs_x < t0 || e.coeffs_x + (int64_t)e.ksx > words || e.coeffs_y < t0 ||
+                    e.coeffs_y + (int64_t)e.ksy > words)
+                    return IMGXF_ERR_ARG;
+                break;
             default: return IMGXF_ERR_ARG;
         }
     }
@@ -561,11 +655,20 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
         const imgxf_driver_unit& u = units[k];
         if (u.entry < 0 || u.entry >= hd.n_entries || entries[u.entry].status != IMGXF_DRIVER_OK) return IMGXF_ERR_ARG;
         const imgxf_driver_entry& e = entries[u.entry];
-        if (u.y0 < 0 || u.ny < 1 || u.y0 + u.ny > e.oh) return IMGXF_ERR_ARG;
-        // the sections: plain units, perspective units (whole 16-row bands: a tile writes PV_TH rows or to the end), resample units
-        const int section = k < hd.n_plain ? 0 : (k < hd.n_plain + hd.n_persp ? 1 : 2);
-        if (section != (dl_resamples(e.op) ? 2 : (e.op == IMGXF_DRIVER_PERSPECTIVE ? 1 : 0))) return IMGXF_ERR_ARG;
+        if (u.y0 < 0 || u.ny < 1 || (int64_t)u.y0 + u.ny > e.oh) return IMGXF_ERR_ARG;     // (64-bit: no sum here may wrap)
+        // the sections: plain units, perspective units (whole 16-row bands: a tile writes PV_TH rows or to the end), resample
+        // units, blur units (whole 32-row bands, in ascending (fixed, R): a run is one launch, its LDS the run's own)
+        const int section = k >= hd.n_units - hd.n_blur ? 3 : (k < hd.n_plain ? 0 : (k < hd.n_plain + hd.n_persp ? 1 : 2));
+        if (section != (dl_blurs(e.op) ? 3 : (dl_resamples(e.op) ? 2 : (e.op == IMGXF_DRIVER_PERSPECTIVE ? 1 : 0)))) return IMGXF_ERR_ARG;
         if (section == 1 && (u.y0 % PV_TH || u.ny != std::min(PV_TH, e.oh - u.y0))) return IMGXF_ERR_ARG;
+        if (section == 3) {
+            if (u.y0 % DL_BLUR_ROWS || u.ny != std::min(DL_BLUR_ROWS, e.oh - u.y0) || u.lds_bytes != dl_blur_lds(e.ksx))
+                return IMGXF_ERR_ARG;
+            if (k > hd.n_units - hd.n_blur) {
+                const imgxf_driver_entry& p = entries[units[k - 1].entry];
+                if (p.op > e.op || (p.op == e.op && p.ksx > e.ksx)) return IMGXF_ERR_ARG;
+            }
+        }
         if (section != 2) continue;
         // what the kernel will lay out: the unit's rows come from the tables, held inside [row0, row0 + nrows)
         const int ja = std::max(u.y0, e.win_top) - e.win_top, jb = std::min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
@@ -574,6 +677,18 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
         const int lo = std::max(by[2 * ja], e.row0), hi = std::min(by[2 * (jb - 1)] + by[2 * (jb - 1) + 1], e.row0 + e.nrows);
         if (hi <= lo || pl_lds_bytes(hi - lo, e.win_w, e.ncols) > hd.lds_bytes) return IMGXF_ERR_ARG;
     }
+    return IMGXF_OK;
+}
+} // namespace imgxf
+
+IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint8_t* out, size_t out_cap, void* stream) {
+    IMGXF_CHECK(driver_list_check(block_host, block_dev, out, out_cap));
+    const u8* hb = (const u8*)block_host;
+    const imgxf_driver_header hd = *(const imgxf_driver_header*)hb;
+    if (hd.n_units == 0) return IMGXF_OK;
+    const int64_t total = hd.total_bytes;
+    const imgxf_driver_entry* entries = (const imgxf_driver_entry*)(hb + hd.entries_off);
+    const imgxf_driver_unit* units = (const imgxf_driver_unit*)(hb + hd.units_off);
     hipStream_t st = (hipStream_t)stream;
     const hipError_t ce = hipMemcpyAsync(block_dev, block_host, (size_t)total, hipMemcpyHostToDevice, st);
     if (ce != hipSuccess) return (int)ce;
@@ -584,9 +699,19 @@ IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint
     if (hd.n_persp)
         hipLaunchKernelGGL(driver_list_persp_kernel, dim3((unsigned)hd.n_persp), dim3(PV_THREADS), 0, st, db, hd.entries_off,
                            hd.units_off, hd.n_plain, out);
-    const int unit2 = hd.n_plain + hd.n_persp;
-    if (hd.n_units > unit2)
-        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(hd.n_units - unit2)), dim3(DL_THREADS),
+    const int unit2 = hd.n_plain + hd.n_persp, unit3 = hd.n_units - hd.n_blur;
+    if (unit3 > unit2)
+        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(unit3 - unit2)), dim3(DL_THREADS),
                            (size_t)hd.lds_bytes, st, db, hd.entries_off, hd.units_off, unit2, out);
-    return launch_status();
+    IMGXF_CHECK(launch_status());
+    // one launch per run of equal (fixed, R): a radius takes its own registers and LDS, not those of R = 15
+    for (int k = unit3; k < hd.n_units;) {
+        const imgxf_driver_entry& e = entries[units[k].entry];
+        int k1 = k + 1;
+        while (k1 < hd.n_units && entries[units[k1].entry].op == e.op && entries[units[k1].entry].ksx == e.ksx) ++k1;
+        IMGXF_CHECK(driver_list_blur_launch(e.op == IMGXF_DRIVER_BLUR_FIXED, e.ksx / 2, db, hd.entries_off, hd.units_off, k,
+                                            k1 - k, out, st));
+        k = k1;
+    }
+    return IMGXF_OK;
 }

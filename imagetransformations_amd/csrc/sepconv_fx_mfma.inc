@@ -180,24 +180,6 @@ __global__ __launch_bounds__(256, 3) void sepconv_fx_mfma_kernel(View src, View 
     flush(nob - 1);
 }
 
-// integer taps <= 63 so that a reflected pair still fits a signed byte; the other conditions are the float kernel's
-inline bool fx_mfma_eligible(const View& s, const View& d, const View& df, int C, int R, int border, const Taps& taps) {
-    if (C != 3 || border != IMGXF_BORDER_REFLECT_101 || df.p) return false;
-    if (R < 2 || R > 15 || s.w < 17 || s.h < 32) return false;
-    if (s.rowbytes() % 16 || s.rowbytes() < 256) return false;
-    if (((uintptr_t)s.p | (uintptr_t)d.p) & 15) return false;
-    if ((s.rs | s.fs | d.rs | d.fs) & 15) return false;
-    if ((int64_t)s.h * s.rs >= ((int64_t)1 << 32)) return false;
-    int sx = 0, sy = 0;
-    for (int i = 0; i <= 2 * R; ++i) {
-        const int wx = (int)(taps.x[i] * 256.0f + 0.5f), wy = (int)(taps.y[i] * 256.0f + 0.5f);
-        if (wx < 0 || wy < 0 || wx > 63 || wy > 127) return false;
-        if ((float)wx != taps.x[i] * 256.0f || (float)wy != taps.y[i] * 256.0f) return false;
-        sx += wx; sy += wy;
-    }
-    return sx <= 256 && sy <= 256;
-}
-
 template <int R>
 inline int launch_sepconv_fx_mfma(const View& s, const View& d, const Taps& taps, hipStream_t st) {
     const int ng = (int)((s.rowbytes() + 31) / 32), ntx = (ng + 3) / 4;

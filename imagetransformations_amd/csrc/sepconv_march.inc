@@ -279,17 +279,6 @@ __global__ __launch_bounds__(256) void sepconv_march_kernel(View src, View dst, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// Host-side eligibility of the marching path.
-inline bool march_eligible(const View& s, const View& d, const View& df, int C, int R, int border) {
-    if (border != IMGXF_BORDER_REFLECT_101) return false;
-    if ((R + 1) * C > 16 || s.w < R + 1 || s.h < R + 1) return false;
-    if (s.rowbytes() % 16 || s.rowbytes() <= 1024) return false;
-    if (((uintptr_t)s.p | (uintptr_t)d.p) & 15) return false;
-    if ((s.rs | s.fs | d.rs | d.fs) & 15) return false;
-    if (df.p && ((((uintptr_t)df.p) & 15) || (df.rs & 15) || (df.fs & 15))) return false;
-    return true;
-}
-
 // Frames per super-row: the G <= 8 with the fewest waves per frame row, ceil(G * bpr / 64) / G
 // (4K RGB: bpr 720 -> G 4, 45 strips; 1080p: bpr 360 -> G 8, 45 strips); every lane offset
 // (G - 1) * frame_stride + rowbytes must fit 32 bits.

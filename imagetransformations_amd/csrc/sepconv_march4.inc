@@ -256,16 +256,6 @@ __global__ __launch_bounds__(256) void sepconv_march4_kernel(View src, View dst,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-inline bool march4_eligible(const View& s, const View& d, const View& df, int C, int R, int border) {
-    if (border != IMGXF_BORDER_REFLECT_101) return false;
-    if (R < 1 || R > 15 || s.w < R + 1 || s.h < R + 1) return false;
-    if (s.rowbytes() % 16 || s.rowbytes() < 256 + 32 * ((R * C + 15) / 16)) return false;
-    if (((uintptr_t)s.p | (uintptr_t)d.p) & 15) return false;
-    if ((s.rs | s.fs | d.rs | d.fs) & 15) return false;
-    if (df.p && ((((uintptr_t)df.p) & 15) || (df.rs & 15) || (df.fs & 15))) return false;
-    return true;
-}
-
 template <int C, int R, bool FIXED = false>
 inline int launch_sepconv_march4(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
     constexpr int J = march4_rows_in_flight(2 * R + 1), NE = (R * C + 15) / 16;

@@ -254,27 +254,6 @@ __global__ __launch_bounds__(256, 2) void sepconv_mfma2_rgb_kernel(View src, Vie
     flush(nob - 1);                                          // the last block's tile, written in the last iteration
 }
 
-inline bool mfma_eligible(const View& s, const View& d, const View& df, int C, int R, int border, const Taps& taps) {
-    if (C != 3 || border != IMGXF_BORDER_REFLECT_101) return false;
-    // f16 range of the operands: every tap goes in as f16(w 2^15) and the row-filtered value D1 = sum b wx is
-    // repacked as f16 for the column product, so |w| 2^15 and 255 sum|wx| must stay below 65504 (normalised
-    // Gaussians are far inside; filter2D kernels such as 2 * ones(13) are not and take the vector kernels)
-    float sx = 0.0f;
-    for (int i = 0; i <= 2 * R; ++i) {
-        const float ax = fabsf(taps.x[i]), ay = fabsf(taps.y[i]);
-        if (!(ax * 32768.0f <= 65504.0f) || !(ay * 32768.0f <= 65504.0f)) return false;    // also rejects NaN
-        sx += ax;
-    }
-    if (!(sx * 255.0f <= 65504.0f)) return false;
-    if (R < 2 || R > 15 || s.w < 17 || s.h < 32) return false;
-    if (s.rowbytes() % 16 || s.rowbytes() < 256) return false;
-    if (((uintptr_t)s.p | (uintptr_t)d.p) & 15) return false;
-    if ((s.rs | s.fs | d.rs | d.fs) & 15) return false;
-    if ((int64_t)s.h * s.rs >= ((int64_t)1 << 32)) return false;
-    if (df.p && ((((uintptr_t)df.p) & 3) || (df.rs & 3) || (df.fs & 3))) return false;
-    return true;
-}
-
 template <int R>
 inline int launch_sepconv_mfma(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
     const int ng = (int)((s.rowbytes() + 31) / 32), ntx = (ng + 3) / 4;

@@ -15,27 +15,28 @@
 //            stores packed uint8 (round-half-even, saturate).
 #pragma once
 #include "imgxf_common.h"
+#include "sepconv_family.h"
 
 namespace imgxf {
 
-struct Taps { float x[31]; float y[31]; };
-
-template <int C, int R, int TH, bool FIXED = false>
-__global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, View dstf,
-                                                           Taps taps, int border) {
+// One tile (TH rows x 256 bytes at byte column x0b, row y0) of one frame: src / dst are the addresses of the frame's
+// pixel (0, 0), srs / drs its row strides in bytes (any value: the 16-byte loads and dword stores test the actual
+// address and fall back to bytes), dstf / frs the optional fp32 copy.  The ONE copy of the filter's statements: the
+// per-type kernel below and the list kernel (driver_list_blur.hip) both compile it, so their bytes agree.  Hs: ROWS x 256
+// floats of LDS; the caller synchronises before it reuses them.
+template <int C, int R, int TH, bool FIXED>
+__device__ __forceinline__ void sepconv_tile_body(const u8* src, int64_t srs, int h, int w, u8* dst, int64_t drs,
+                                                  float* dstf, int64_t frs, int x0b, int y0, const float* __restrict__ tx,
+                                                  const float* __restrict__ ty, int border, float* Hs) {
     constexpr int HB = R * C;              // halo in bytes
     constexpr int NBH = (HB + 15) / 16;    // halo in 16-byte blocks
     constexpr int WB = 2 * NBH + 1;        // window in 16-byte blocks
     constexpr int NF = 16 + 2 * HB;        // floats a lane needs for 16 outputs
     constexpr int ROWS = TH + 2 * R;
     constexpr int VR = 8;
-    extern __shared__ __attribute__((aligned(16))) float Hs[];  // ROWS x 256 floats
 
     const int tid = threadIdx.x;
-    const int x0b = blockIdx.x * 256;
-    const int y0 = blockIdx.y * TH;
-    const int f = blockIdx.z;
-    const int rowbytes = src.w * C;
+    const int rowbytes = w * C;
 
     // ---------------- phase H ----------------
     for (int t = tid; t < ROWS * 16; t += 256) {
@@ -43,8 +44,8 @@ __global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, V
         const int xb = x0b + 16 * cx;
         if (xb >= rowbytes) continue;
         int gy = y0 - R + ry;
-        if (gy < 0 || gy >= src.h) gy = border_index(gy, src.h, border);
-        const u8* rowp = src.row(f, gy);
+        if (gy < 0 || gy >= h) gy = border_index(gy, h, border);
+        const u8* rowp = src + (int64_t)gy * srs;
         u32 wv[WB * 4];
         const bool fast = (xb - 16 * NBH >= 0) && (xb + 16 + 16 * NBH <= rowbytes) &&
                           ((((uintptr_t)(rowp + xb)) & 15) == 0);
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, V
                 const int bx = xb - 16 * NBH + j;
                 int px = bx >= 0 ? bx / C : -((-bx + C - 1) / C);
                 const int ch = bx - px * C;
-                if (px < 0 || px >= src.w) px = border_index(px, src.w, border);
+                if (px < 0 || px >= w) px = border_index(px, w, border);
                 wv[j >> 2] |= (u32)rowp[px * C + ch] << (8 * (j & 3));
             }
         }
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, V
             for (int e = 0; e < 4; ++e) {
                 float acc = 0.0f;
 #pragma unroll
-                for (int i = 0; i <= 2 * R; ++i) acc = fmaf(taps.x[i], fl[4 * q + e + i * C], acc);
+                for (int i = 0; i <= 2 * R; ++i) acc = fmaf(tx[i], fl[4 * q + e + i * C], acc);
                 o[e] = acc;
             }
             // permuted column order: consecutive lanes write consecutive 16 B (conflict-free)
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, V
             for (int o = 0; o < VR; ++o) {
                 const int i = j - o;
                 if (i >= 0 && i <= 2 * R) {
-                    const float g = taps.y[i];
+                    const float g = ty[i];
                     acc[o].x = fmaf(g, v.x, acc[o].x);
                     acc[o].y = fmaf(g, v.y, acc[o].y);
                     acc[o].z = fmaf(g, v.z, acc[o].z);
@@ -115,22 +116,31 @@ __global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, V
 #pragma unroll
         for (int o = 0; o < VR; ++o) {
             const int y = y0 + rg * VR + o;
-            if (y >= src.h) break;
+            if (y >= h) break;
             const float r[4] = {FIXED ? floorf(acc[o].x) : acc[o].x, FIXED ? floorf(acc[o].y) : acc[o].y,
                                 FIXED ? floorf(acc[o].z) : acc[o].z, FIXED ? floorf(acc[o].w) : acc[o].w};
-            u8* dp = dst.row(f, y) + xb;
+            u8* dp = dst + (int64_t)y * drs + xb;
             if (nvalid == 4 && (((uintptr_t)dp) & 3) == 0) {
                 *(u32*)dp = sat_u8_rne(r[0]) | (sat_u8_rne(r[1]) << 8) | (sat_u8_rne(r[2]) << 16) |
                             (sat_u8_rne(r[3]) << 24);
             } else {
                 for (int e = 0; e < nvalid; ++e) dp[e] = (u8)sat_u8_rne(r[e]);
             }
-            if (dstf.p) {
-                float* fp = (float*)dstf.row(f, y) + xb;
+            if (dstf) {
+                float* fp = (float*)((u8*)dstf + (int64_t)y * frs) + xb;
                 for (int e = 0; e < nvalid; ++e) fp[e] = r[e];
             }
         }
     }
+}
+
+template <int C, int R, int TH, bool FIXED = false>
+__global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, View dstf, Taps taps, int border) {
+    extern __shared__ __attribute__((aligned(16))) float Hs[];  // (TH + 2R) x 256 floats
+    const int f = blockIdx.z;
+    sepconv_tile_body<C, R, TH, FIXED>(src.row(f, 0), src.rs, src.h, src.w, dst.row(f, 0), dst.rs,
+                                       dstf.p ? (float*)dstf.row(f, 0) : nullptr, dstf.rs, blockIdx.x * 256, blockIdx.y * TH,
+                                       taps.x, taps.y, border, Hs);
 }
 
 template <int C, int R, bool FIXED = false>

@@ -1,12 +1,17 @@
-"""Seven of the driver's eight transformation types, and the four further ones of the later twelve-type driver
+"""The driver's eight transformation types, and the four further ones of the later twelve-type driver
 (transformations_code: vert_flip, rand_crop, zoom, perspective_warp), on a LIST of RGB frames of any sizes in one
 record-driven device pass (csrc/driver_list.hip): every entry carries its own frame, type and drawn value, and is bit for
-bit what `transformation._TENSOR_FNS[type]` / `ops.add_noise` / `ops.flip` / `ops.resize(ops.crop(...))` /
-`ops.perspective` return for that frame.  One host-to-device copy of one block and at most three launches, whatever the
-number of frames, entries or distinct sizes; no resample plan is created or cached.
+bit what `transformation._TENSOR_FNS[type]` / `ops.add_noise` / `ops.gaussian_blur` / `ops.flip` /
+`ops.resize(ops.crop(...))` / `ops.perspective` return for that frame.  One host-to-device copy of one block and at most
+three launches plus one per distinct blur radius in the call (the drivers' grid has ten), whatever the number of frames,
+entries or distinct sizes; no resample plan is created or cached.
 
-Blur is not here: the float Gaussian runs on four kernel families that agree to the 1e-5 contract, not to the byte, so
-it stays on the grouped route (batched.run_grouped), grouped by (size, radius)."""
+Blur: the float Gaussian runs on four kernel families that agree to the 1e-5 contract, not to the byte.  The pass
+compiles the statements of one of them, the LDS-tiled kernel, and takes a blur entry where the per-type dispatcher would
+serve a contiguous batch of that size and radius with that kernel — every width whose rows are no multiple of 16 bytes,
+and small frames — so the bytes are the grouped route's.  The other entries are refused (REFUSED_FAMILY) and stay on the
+grouped route (batched.run_grouped).  With `transformation.BLUR_FIXED_POINT` every family is integer-exact and every blur
+entry is taken."""
 from __future__ import annotations
 
 import collections
@@ -29,13 +34,15 @@ DRIVER_LIST_LDS_BYTES = 64 * 1024
 BLOCK_ROW_BYTES = 3 * batched.BLOCK_ROW
 
 TYPES = {'scale': 0, 'rotation': 1, 'lighten_darken': 2, 'contrast': 3, 'shear': 4, 'translation': 5, 'gaussian_noise': 6,
-         'vert_flip': 7, 'rand_crop': 8, 'perspective_warp': 10, 'zoom': 0}          # zoom is apply_scale; 9 is no type
+         'vert_flip': 7, 'rand_crop': 8, 'perspective_warp': 10, 'zoom': 0,           # zoom is apply_scale; 9, 11 are no type
+         'blur': 12}                                    # 13 (BLUR_FIXED) with transformation.BLUR_FIXED_POINT
+BLUR_FIXED = 13
 CROP_SIZE = 32                                          # rand_crop's output is CROP_SIZE x CROP_SIZE
-OK, REFUSED_LDS, REFUSED_SIZE, REFUSED_TURN, REFUSED_FORMAT, REFUSED_OTHER = range(6)      # imgxf_driver_entry.status
+OK, REFUSED_LDS, REFUSED_SIZE, REFUSED_TURN, REFUSED_FORMAT, REFUSED_OTHER, REFUSED_FAMILY = range(7)      # imgxf_driver_entry.status
 
 _HEADER = np.dtype([(k, "<i4") for k in ("n_entries", "n_units", "n_plain", "lds_bytes", "entries_off", "units_off",
                                          "tables_off", "total_bytes")] + [("out_bytes", "<u8"), ("n_persp", "<i4"),
-                                                                        ("reserved", "<i4")])
+                                                                        ("n_blur", "<i4")])
 _ENTRY = np.dtype([("src", "<u8"), ("src_stride", "<i8"), ("noise", "<u8"), ("out_off", "<i8")] +
                   [(k, "<i4") for k in ("op", "status", "h", "w", "oh", "ow", "unit_rows", "frame")] +
                   [("alpha", "<f4"), ("beta", "<f4"), ("dx", "<i4"), ("dy", "<i4"), ("fx", "<i4", (6,))] +
@@ -84,6 +91,9 @@ def entry_params(transform_type: str, args):
         return 0.0, 0.0
     if transform_type == 'lighten_darken':
         return 1.0 + args[0], 0.0                       # ImageEnhance.Brightness's factor, as apply_brightness forms it
+    if transform_type == 'blur':                        # (ksize, sigma) as apply_blur hands them to ops.gaussian_blur
+        from . import transformation
+        return float(transformation._blur_ksize(args[0])), float(args[0])
     return float(args[0]), 0.0
 
 
@@ -116,7 +126,11 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
     for j, (fi, transform_type, args) in enumerate(entries):
         code = TYPES.get(transform_type)
         if code is None:
-            raise ValueError(f"apply_list has no type {transform_type!r} (blur stays on the grouped route)")
+            raise ValueError(f"apply_list has no type {transform_type!r}")
+        if code == TYPES['blur']:
+            from . import transformation
+            if transformation.BLUR_FIXED_POINT:         # read at call time, as transformation._blur_group reads it
+                code = BLUR_FIXED
         if code == TYPES['perspective_warp']:
             pc = np.asarray(args[0] if len(args) == 1 else args, np.float64).reshape(-1)
             with np.errstate(over="ignore"):
@@ -186,16 +200,21 @@ def apply_list(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES):
     H * W * 3 normals the driver drew (already scaled: what `ops.add_noise` takes).  The later driver's types take: `()`
     for 'vert_flip'; the drawn corner `(x, y)` for 'rand_crop'; `(coeffs,)`, torchvision's eight coefficients, for
     'perspective_warp' (ValueError, before any device work, unless they are eight finite numbers); `(factor,)` for
-    'zoom', which is 'scale'.
+    'zoom', which is 'scale'.  A 'blur' entry takes `(radius,)`: ksize is `transformation._blur_ksize(radius)`, sigma the
+    radius, and `transformation.BLUR_FIXED_POINT`, read at call time, selects OpenCV's 8-bit evaluation.
 
     Returns (outputs, refused).  outputs[j] is the [H', W', 3] uint8 result of entry j, bit for bit
     `transformation._TENSOR_FNS[type](frames[i][None], *args)[0]` (`ops.add_noise` for noise, `ops.flip`,
-    `ops.resize(ops.crop(frame, (x, y, x + cs, y + cs)), (32, 32), BICUBIC)` with cs = int(0.78 * W), `ops.perspective`):
+    `ops.resize(ops.crop(frame, (x, y, x + cs, y + cs)), (32, 32), BICUBIC)` with cs = int(0.78 * W), `ops.perspective`,
+    `ops.gaussian_blur(frames[i][None].contiguous(), ksize, radius, fixed_point=BLUR_FIXED_POINT)[0]` for blur):
     a view, starting on a 16-byte boundary, into the ONE allocation the call makes (shear widens the frame:
     W' = W + ceil(shear * H); a crop gives 32 x 32).  `refused` lists the entries the pass does not take (outputs[j] is
     None; the caller runs them through its own route): a scale or crop whose touched rows do not fit `lds_bytes`, a scale
     whose resized width or height would be below 1, a crop with cs below 1 or its window not inside the frame, a
-    rotation that `ops.rotate_turns` sends to a transpose, a frame that is not 3-channel uint8.  A refusal never raises
+    rotation that `ops.rotate_turns` sends to a transpose, a frame that is not 3-channel uint8, a blur of radius 0
+    (the drivers hand back the input object itself) and, in float mode, a blur whose size and radius the per-type
+    dispatcher serves with another kernel family than the LDS-tiled one (16-byte rows of at least 256 bytes, by and
+    large).  A refusal never raises
     and nothing here touches `random`, `np.random` or torch's generator."""
     _, outputs, refused = apply_list_block(frames, entries, lds_bytes)
     return outputs, refused

@@ -532,9 +532,10 @@ def apply_all_transformations_batched_named(images, _sink=None, _tee=False):
     DEVICE tensors as the device JPEG reader returns them (`jpeg_decode.decode`): those are never copied to the host.  `_sink(out, names)`, when given,
     consumes a group's result ON THE DEVICE ([B, H, W, 3] tensor + its file names) instead of it being copied back:
     those entries come back as (file name, None).  With `DRIVER_LIST` ("auto": more than one image size among `images`)
-    the seven types other than blur of ALL sizes run in at most two `driver_list.apply_list` calls instead of one launch per
+    the eight types of ALL sizes run in at most two `driver_list.apply_list` calls instead of one launch per
     (size, type, value) — the second one for the noise entries, once their numbers have been collected; entries that call
-    refuses, blur and the Philox noise keep the groups."""
+    refuses (among them the float blurs that the per-type dispatcher serves with another kernel family than the list's:
+    16-byte rows, by and large), radius-0 blurs and the Philox noise keep the groups."""
     if DRIVER_LIST not in ("auto", "0", "1"):
         raise ValueError(f'DRIVER_LIST / IMGXF_DRIVER_LIST must be "auto", "0" or "1", got {DRIVER_LIST!r}')
     dev = _device()
@@ -592,10 +593,13 @@ def apply_all_transformations_batched_named(images, _sink=None, _tee=False):
             return ops.add_noise(batch, torch.stack(zs) if isinstance(zs[0], torch.Tensor) else staging.upload(zs, dev))
         return _TENSOR_FNS[transform_type](batch, *args)
 
-    # Frames of different sizes (DRIVER_LIST): everything but blur and the opt-in Philox noise leaves the groups and runs in
-    # two list calls for the whole chunk, the noise entries in the second one, after the other work has been queued.
+    # Frames of different sizes (DRIVER_LIST): everything but the radius-0 blur (the input object itself) and the opt-in
+    # Philox noise leaves the groups and runs in two list calls for the whole chunk, the noise entries in the second one,
+    # after the other work has been queued.
     def list_phase(transform_type, args):
-        if transform_type == 'blur' or (transform_type == 'gaussian_noise' and NOISE_RNG == "device"):
+        if transform_type == 'blur':
+            return 0 if _blur_ksize(args[0]) != 0 else None
+        if transform_type == 'gaussian_noise' and NOISE_RNG == "device":
             return None
         return 1 if transform_type == 'gaussian_noise' else 0
 

@@ -147,10 +147,11 @@ def apply_all_transformations_batched(images):
     drew the same (type, value) go through one batched launch (perspective warps and crops of one
     size share a launch with per-frame coefficients / windows).  images: [(PIL image, name)].
 
-    With `transformation.DRIVER_LIST` ("1", or "auto" when the RGB images hold more than one size) every type but blur of
-    ALL sizes runs in ONE `driver_list.apply_list` call — one copy of one block, at most three launches, no resample plan
-    — instead of one launch per (size, type, value); entries that call refuses, blur and images that are not 8-bit RGB go
-    where they go without it."""
+    With `transformation.DRIVER_LIST` ("1", or "auto" when the RGB images hold more than one size) every type of ALL sizes runs
+    in ONE `driver_list.apply_list` call — one copy of one block, at most three launches plus one per distinct blur
+    radius, no resample plan — instead of one launch per (size, type, value); entries that call refuses (float blurs
+    that another kernel family serves among them), radius-0 blurs and images that are not 8-bit RGB go where they go
+    without it."""
     if T.DRIVER_LIST not in ("auto", "0", "1"):
         raise ValueError(f'DRIVER_LIST / IMGXF_DRIVER_LIST must be "auto", "0" or "1", got {T.DRIVER_LIST!r}')
     dev = T._device()
@@ -231,8 +232,9 @@ def apply_all_transformations_batched(images):
             return ops.flip(batch)
         return T._TENSOR_FNS['scale' if transform_type == 'zoom' else transform_type](batch, *args)
 
-    # Frames of different sizes (DRIVER_LIST): everything but blur leaves the groups and runs in one list call for the
-    # whole chunk.  One phase: every np.random number has been drawn above.
+    # Frames of different sizes (DRIVER_LIST): everything but the radius-0 blur (the input object itself) leaves the groups
+    # and runs in one list call for the whole chunk; the float blurs that call refuses (another kernel family serves them:
+    # 16-byte rows, by and large) come back as groups.  One phase: every np.random number has been drawn above.
     def run_list(phase, frames, items):
         from . import driver_list
         entries = []
@@ -252,7 +254,8 @@ def apply_all_transformations_batched(images):
     # perspective warps and crops of one size share a launch whatever they drew (per-frame coefficients / windows)
     results = batched.run_grouped([img for img, _ in images], plans, dev, run_group, other=per_image,
                                   key=lambda t, args: (t, () if t in ('perspective_warp', 'rand_crop') else args),
-                                  list_route=(lambda t, args: None if t == 'blur' else 0, run_list) if use_list else None)
+                                  list_route=(lambda t, args: None if t == 'blur' and T._blur_ksize(args[0]) == 0 else 0,
+                                              run_list) if use_list else None)
     transformed_images = []
     for i, plan in enumerate(plans):
         for k, (_, _, new_filename) in enumerate(plan):

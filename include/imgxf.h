@@ -835,13 +835,17 @@ int imgxf_preprocess_list_f32(const void* block_host, const void* block_dev, flo
                               const float* std, void* stream);
 
 /* ---- the transformations of apply_all_transformations on a LIST of entries over frames of different sizes -------------
- * Seven of the driver's eight types and the later driver's flip, crop + resize and perspective warp (blur stays with its
- * own kernels), each entry with its own frame, type and drawn value, bit for bit what the per-type entry points give: one
- * block
- *     imgxf_driver_header | imgxf_driver_entry[n] | imgxf_driver_unit[n_units] | int32 tables
+ * The driver's eight types and the later driver's flip, crop + resize and perspective warp, each entry with its own
+ * frame, type and drawn value, bit for bit what the per-type entry points give: one block
+ *     imgxf_driver_header | imgxf_driver_entry[n] | imgxf_driver_unit[n_units] | int32 / float tables
  * laid out by the HOST, one copy of it to the device and at most three launches (the units that need no LDS, then the
- * perspective units with their fixed 32 KiB box, then the resample units of scale and crop + resize) whatever the number
- * of frames, entries or sizes.  A work unit is a band of output rows of one entry = one workgroup. */
+ * perspective units with their fixed 32 KiB box, then the resample units of scale and crop + resize) plus one launch per
+ * distinct (fixed, radius) among the blur entries — the drivers' grid has ten radii — whatever the number of frames,
+ * entries or sizes.  A work unit is a band of output rows of one entry = one workgroup.
+ * Blur is taken where the per-type dispatcher would serve a contiguous, 16-byte-aligned [n][h][w][3] batch of that size and
+ * radius with the LDS-tiled kernel, whose statements the blur units compile too (sepconv_tile.inc): the float Gaussian's
+ * other kernel families agree with it to 1e-5, not to the byte, so those entries are refused (REFUSED_FAMILY) and keep
+ * their own kernels.  The fixed-point evaluation is integer-exact in every family and is always taken. */
 enum {
     IMGXF_DRIVER_SCALE = 0,          /* param[0] = factor: LANCZOS resize + centre crop (> 1) / paste on black (< 1) */
     IMGXF_DRIVER_ROTATION = 1,       /* param[0] = apply_rotation's angle: Image.rotate(-angle, NEAREST, fill black) */
@@ -853,27 +857,38 @@ enum {
     IMGXF_DRIVER_FLIP = 7,           /* Image.transpose(FLIP_LEFT_RIGHT) */
     IMGXF_DRIVER_CROP_RESIZE = 8,    /* param[0], param[1] = x, y: the square window (x, y, x + cs, y + cs) with
                                         cs = int(0.78 w), resampled to 32 x 32 with BICUBIC; read in place */
-    IMGXF_DRIVER_PERSPECTIVE = 10    /* torchvision F.perspective(BILINEAR, fill 0) on the float tensor: eight float32
-                                        coefficients at imgxf_driver_entry.pc (code 9 is no type) */
+    IMGXF_DRIVER_PERSPECTIVE = 10,   /* torchvision F.perspective(BILINEAR, fill 0) on the float tensor: eight float32
+                                        coefficients at imgxf_driver_entry.pc (codes 9 and 11 are no type) */
+    IMGXF_DRIVER_BLUR = 12,          /* param[0] = ksize, param[1] = sigma: imgxf_gaussian_u8 (cv2.GaussianBlur by its float
+                                        definition, BORDER_REFLECT_101) */
+    IMGXF_DRIVER_BLUR_FIXED = 13     /* param[0] = ksize, param[1] = sigma: imgxf_gaussian_cv_fixed_u8 (OpenCV's 8-bit
+                                        fixed-point evaluation) */
 };
 enum {
     IMGXF_DRIVER_OK = 0,
-    IMGXF_DRIVER_REFUSED_LDS = 1,    /* scale, crop: the source rows one output row touches do not fit lds_budget */
-    IMGXF_DRIVER_REFUSED_SIZE = 2,   /* scale: the resized width or height would be below 1; crop: int(0.78 w) below 1 */
+    IMGXF_DRIVER_REFUSED_LDS = 1,    /* scale, crop: the source rows one output row touches do not fit lds_budget; blur: its
+                                        (32 + 2 R) x 1024 bytes do not */
+    IMGXF_DRIVER_REFUSED_SIZE = 2,   /* scale: the resized width or height would be below 1; crop: int(0.78 w) below 1;
+                                        blur: ksize 0 (the drivers hand back the input itself) */
     IMGXF_DRIVER_REFUSED_TURN = 3,   /* rotation: Image.rotate's transpose paths (180, and 90 / 270 on square frames) */
     IMGXF_DRIVER_REFUSED_FORMAT = 4, /* the frame is not 3-channel uint8, or larger than 32767 x 32767 */
-    IMGXF_DRIVER_REFUSED_OTHER = 5   /* unknown type; a rotation whose rounded matrix is a pure scale (ImagingScaleAffine);
-                                        a crop whose window is not inside the frame */
+    IMGXF_DRIVER_REFUSED_OTHER = 5,  /* unknown type; a rotation whose rounded matrix is a pure scale (ImagingScaleAffine);
+                                        a crop whose window is not inside the frame; a blur whose ksize is even, not in
+                                        1 ... 31 or whose taps imgxf_gaussian_* would reject */
+    IMGXF_DRIVER_REFUSED_FAMILY = 6  /* BLUR (float) only: the per-type dispatcher serves this size and radius with another
+                                        kernel family than the LDS-tiled one */
 };
 typedef struct imgxf_driver_header {
     int32_t n_entries, n_units;
     int32_t n_plain;            /* units [0, n_plain) need no LDS (first launch); [n_plain, n_plain + n_persp) are the
-                                   perspective units (second launch), the rest the resample units (third launch) */
+                                   perspective units (second launch), then the resample units (third launch); the last
+                                   n_blur units are the blur units */
     int32_t lds_bytes;          /* the largest resample unit's LDS need = the third launch's dynamic LDS size */
     int32_t entries_off, units_off, tables_off, total_bytes;   /* byte offsets of the sections, size of the block */
     uint64_t out_bytes;         /* size of the output allocation: every accepted entry's [oh][ow][3] at its out_off */
     int32_t n_persp;            /* perspective units: bands of 16 output rows, walked in 64-pixel tiles */
-    int32_t reserved;
+    int32_t n_blur;             /* blur units: bands of 32 output rows, walked in 256-byte column tiles; sorted by (fixed,
+                                   radius), one launch per distinct pair */
 } imgxf_driver_header;
 typedef struct imgxf_driver_entry {
     uint64_t src;               /* DEVICE address of the frame's pixel (0, 0); filled by the caller, as is src_stride */
@@ -891,9 +906,11 @@ typedef struct imgxf_driver_entry {
     int32_t  win_top, win_left, win_h, win_w;   /* SCALE: where the resampled pixels go in the output (all of it for
                                    factors >= 1, the pasted window on the black canvas below 1); CROP_RESIZE: all of it */
     double   m1, m2;            /* SHEAR: the matrix (1, m1, m2, 0, 1, 0) */
-    int32_t  ksx, ksy;          /* SCALE, CROP_RESIZE: taps per output column / row */
+    int32_t  ksx, ksy;          /* SCALE, CROP_RESIZE: taps per output column / row; BLUR: taps per axis, 2 R + 1 */
     int32_t  bounds_x, coeffs_x, bounds_y, coeffs_y;   /* [win_w][2], [win_w][ksx], [win_h][2], [win_h][ksy]: int32
-                                   indices into the block; entries of equal (filter, in, out, window) on an axis share them */
+                                   indices into the block; entries of equal (filter, in, out, window) on an axis share them.
+                                   BLUR: coeffs_x / coeffs_y are the word indices of its ksx / ksy float taps (the fixed-point
+                                   ones as n / 256); entries of equal (code, ksize, sigma) share one table */
     int32_t  row0, nrows, col0, ncols;   /* the rows / columns of the resampled region that the window touches */
     int32_t  in_h, in_w;        /* the resampled region, which the tables index: the frame for SCALE, the cs x cs window
                                    at (dx, dy) for CROP_RESIZE */
@@ -902,7 +919,7 @@ typedef struct imgxf_driver_entry {
 typedef struct imgxf_driver_unit {
     int32_t entry, y0, ny;      /* one workgroup: output rows [y0, y0 + ny) of entry `entry` */
     int32_t lds_bytes;          /* resample units: touched source rows x 12 ceil(win_w / 4) (rounded up to 16) + 4 staged
-                                   row spans */
+                                   row spans; blur units: (32 + 2 R) x 1024 */
 } imgxf_driver_unit;
 /* HOST half (no device work).  geometry: int32 [n][5] = (frame, type, h, w, channels; channels 0 = not uint8) per entry,
  * params: double [n][2].  Writes the block (block == NULL: only *block_bytes and the per-entry results) and, where
@@ -910,7 +927,9 @@ typedef struct imgxf_driver_unit {
  * precompute_coeffs' for (w -> int(w s)) and (h -> int(h s)), sliced to the centre-crop window for s > 1; a crop's are
  * the BICUBIC ones for (cs -> 32).  A resample unit takes up to 16 window rows, fewer where their touched source rows
  * would not fit half of lds_budget (three quarters, then all of it; capped at 64 KiB); a perspective unit takes 16 output
- * rows; the other units take the rows of about 24 KiB of output.
+ * rows; a blur unit 32; the other units take the rows of about 24 KiB of output.  A blur's taps are those of
+ * imgxf_gaussian_u8 / imgxf_gaussian_cv_fixed_u8 for (ksize, sigma), and whether it is taken follows the per-type
+ * dispatcher's own choice of kernel family (IMGXF_NO_MARCH, IMGXF_MFMA_MIN_R and IMGXF_FX_MFMA_MIN_R included).
  * Errors: IMGXF_ERR_NULL; IMGXF_ERR_ARG for n < 0 or lds_budget < 1; IMGXF_ERR_SHAPE when the block or the output passes
  * 2 GiB / 2^40 bytes; IMGXF_ERR_WORKSPACE when block_cap is too small.  A refusal is a status, never an error. */
 int imgxf_driver_list_layout_host(const int32_t* geometry, const double* params, int n, int lds_budget, void* block,

@@ -1,5 +1,6 @@
-"""The batched driver on frames of different sizes: `transformation.DRIVER_LIST` "1" (seven of the eight types of a chunk
-in two `driver_list.apply_list` calls) against "0" (one launch per size, type and drawn value: the grouped route).
+"""The batched driver on frames of different sizes: `transformation.DRIVER_LIST` "1" (the types of a chunk in two
+`driver_list.apply_list` calls; blur where its size and radius are the tile kernel's) against "0" (one launch per size,
+type and drawn value: the grouped route).
 
 Workloads (uint8 noise from a seeded generator, resident on the device before timing):
   mixed    1024 frames of ImageNet-like sizes (tools/bench_preprocess_list.py::mixed_sizes: 343 distinct sizes);
@@ -9,7 +10,8 @@ whole calls from a host clock ending in a device synchronise, `random` and `np.r
 call, the routes alternating after each has been warmed up once.  Per route: the median, best and worst of the repeats
 in images/s (worst - best is the run-to-run spread the comparison is held against).  For the list route also, from one
 more call each: the device time of the list calls (HIP events around `imgxf_driver_list_u8`: block copy + both launches),
-the host time of building the blocks (`driver_list.layout`), the C-ABI calls by name, and a digest of the files written:
+the host time of building the blocks (`driver_list.layout`), how many blur entries the calls held and how many of them
+were refused for their kernel family, the C-ABI calls by name, and a digest of the files written:
 the tool exits non-zero when the routes' files differ.
 
 `--root DIR` imports the package from another checkout (built there) instead of this one: the same script then times
@@ -85,7 +87,7 @@ def instrumented_call(pkg, T, torch, np, images, out_dir, route):
     """One more call with the C-ABI calls counted and, where the package has it, the list calls timed."""
     F = pkg._ffi
     counts, real_call = {}, F.call
-    events, host_ms = [], [0.0]
+    events, host_ms, blur = [], [0.0], [0, 0]                 # blur: entries, of them refused for their family
 
     def counting(name, *args):
         counts[name] = counts.get(name, 0) + 1
@@ -106,6 +108,10 @@ def instrumented_call(pkg, T, torch, np, images, out_dir, route):
             t0 = time.perf_counter()
             out = real_layout(*a, **k)
             host_ms[0] += (time.perf_counter() - t0) * 1e3
+            if 'blur' in DL.TYPES:
+                is_blur = np.isin(np.asarray(a[0]).reshape(-1, 5)[:, 1], (DL.TYPES['blur'], DL.BLUR_FIXED))
+                blur[0] += int(is_blur.sum())
+                blur[1] += int((out["status"][is_blur] == DL.REFUSED_FAMILY).sum())
             return out
         DL.layout = layout
     timed_call.keep = TWELVE
@@ -126,7 +132,7 @@ def instrumented_call(pkg, T, torch, np, images, out_dir, route):
         digest.update(name.encode())
         with open(os.path.join(out_dir, name), "rb") as f:
             digest.update(f.read())
-    return counts, len(events), dev_ms, host_ms[0], digest.hexdigest()
+    return counts, len(events), dev_ms, host_ms[0], digest.hexdigest(), blur
 
 
 def main():
@@ -196,13 +202,14 @@ def main():
                       f"worst {ips[0]:8.1f}   spread {ips[-1] - ips[0]:7.1f}   (s per call: {', '.join(f'{x:.3f}' for x in t)})")
             digests = set()
             for r in routes:
-                counts, n_calls, dev_ms, host_ms, digest = instrumented_call(pkg, T, torch, np, images, out_dir, r)
+                counts, n_calls, dev_ms, host_ms, digest, blur = instrumented_call(pkg, T, torch, np, images, out_dir, r)
                 digests.add(digest)
                 top = sorted(counts.items(), key=lambda kv: -kv[1])
                 print(f"  DRIVER_LIST={r:<5}: {sum(counts.values())} C-ABI calls: " + ", ".join(f"{k[6:]} {v}" for k, v in top[:12]))
                 if n_calls:
                     print(f"                     {n_calls} list calls: {dev_ms:.2f} ms on the device (events: block copy + the "
-                          f"launches), {host_ms:.2f} ms of host time building the blocks")
+                          f"launches), {host_ms:.2f} ms of host time building the blocks"
+                          + (f"; {blur[0]} blur entries, {blur[1]} refused for their kernel family" if blur[0] else ""))
             if TWELVE or not COPY_BACK:
                 print(f"  {'images' if TWELVE else 'files'} of all routes byte-identical: {len(digests) == 1}  (sha256 over names and bytes: {digest[:16]})")
                 same &= len(digests) == 1
