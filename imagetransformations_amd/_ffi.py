@@ -51,6 +51,13 @@ POOL_CODES = {"defocus_blur": 0, "enhance_sharpness": 1, "enhance_contrast": 2, 
               "enhance_brightness": 4, "gaussian_noise": 5, "impulse_noise": 6, "shot_noise": 7, "motion_blur": 8,
               "histogram_equalization": 9}
 POOL_MAX_OPS, POOL_MAX_STEPS, POOL_MAX_MOTION = 32, 16, 31
+POOL_LIST_CLASSES = 4
+
+
+class PoolListFrame(C.Structure):
+    """struct imgxf_pool_list_frame (include/imgxf.h)."""
+    _fields_ = [("src", C.c_uint64), ("src_stride", C.c_int64), ("out_off", C.c_uint64), ("ws_off", C.c_uint64),
+                ("rec_off", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32), ("steps", C.c_int32), ("pad_", C.c_int32)]
 
 
 _VP = C.POINTER(View)
@@ -109,6 +116,9 @@ SIGNATURES = {
     "imgxf_pool_chain_workspace_bytes": [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)],
     "imgxf_pool_chain_u8": [_VP, _VP, C.POINTER(PoolOp), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
                             C.c_void_p, C.c_size_t, C.c_void_p],
+    "imgxf_pool_chain_list_class": [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "imgxf_pool_chain_list_u8": [C.c_void_p, C.c_int32, C.POINTER(PoolOp), C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t,
+                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_rgb2yuv_u8": [_VP, _VP, C.c_void_p],
     "imgxf_yuv2rgb_u8": [_VP, _VP, C.c_void_p],
     "imgxf_equalize_hist_cv_u8": [_VP, _VP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],

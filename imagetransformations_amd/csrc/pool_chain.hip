@@ -16,6 +16,8 @@
 //   histogram_equalization  LDS histogram of Y, the cv2.equalizeHist table, YUV -> RGB
 // The two working frames live in LDS while they fit (see imgxf.h for the exact bound); past it the
 // same kernel keeps them in a global workspace slice of its own.  Every step ends with a barrier.
+// The steps are one device body (pool_chain_steps.inc) compiled by two kernels: the batch kernel (n frames of one size
+// behind two views) and the list kernel (per-frame records: frames of any sizes, each with its own source and output).
 #include "imgxf_common.h"
 #include <string.h>
 
@@ -65,208 +67,46 @@ __device__ __forceinline__ unsigned long long wg_sum(u32 part, u32* scratch) {
     return t;
 }
 
+#include "pool_chain_steps.inc"
+
 template <bool RESIDENT>
 __global__ __launch_bounds__(PC_THREADS) void pool_chain_kernel(PcArgs A) {
     extern __shared__ __attribute__((aligned(16))) u8 pc_lds[];
-    u32* hist = (u32*)(pc_lds + PC_HIST);
-    u8* lut = pc_lds + PC_LUT;
-    u32* scratch = (u32*)(pc_lds + PC_SCRATCH);
-
-    const int f = blockIdx.x, tid = threadIdx.x;
-    const int H = A.s.h, W = A.s.w, RB = 3 * W;
-    const u32 HW = (u32)H * (u32)W, NB = 3 * HW;
+    const int f = blockIdx.x;
     u8* fa = RESIDENT ? pc_lds + PC_FIXED : A.ws + (int64_t)f * 2 * A.frame_bytes;
-    u8* fb = fa + A.frame_bytes;
-    const u8* rec = A.plan + (int64_t)f * PC_STEP_BYTES * A.steps;
-
-    for (u32 i = tid; i < NB; i += PC_THREADS) {
-        const u32 y = i / (u32)RB;
-        fa[i] = A.s.row(f, (int)y)[i - y * (u32)RB];
-    }
-    __syncthreads();
-
-    for (int s = 0; s < A.steps; ++s) {
-        const u8* st = rec + PC_STEP_BYTES * s;
-        const int k = st[0];
-        if (k >= A.nops) continue;
-        const float factor = *(const float*)(st + 4);
-        const uint64_t off = *(const uint64_t*)(st + 8);
-        const PcOp& op = A.ops[k];
-        const double* data = nullptr;
-        if (op.code == IMGXF_POOL_GAUSSIAN_NOISE || op.code == IMGXF_POOL_IMPULSE_NOISE || op.code == IMGXF_POOL_SHOT_NOISE) {
-            const uint64_t need = 8ull * (op.code == IMGXF_POOL_IMPULSE_NOISE ? HW : NB);
-            if ((off & 7) || off > A.payload_bytes || A.payload_bytes - off < need) continue;
-            data = (const double*)(A.payload + off);
-        }
-        switch (op.code) {
-            case IMGXF_POOL_DEFOCUS_BLUR: {
-                // imgxf_box_blur_u8 with 3 passes per axis, x first; replicated edges
-                for (int p = 0; p < 6; ++p) {
-                    const bool vertical = p >= 3;
-                    for (u32 i = tid; i < NB; i += PC_THREADS) {
-                        const int y = (int)(i / (u32)RB), b = (int)i - y * RB;
-                        u32 acc = 0, far;
-                        if (!vertical) {
-                            const u8* rp = fa + y * RB;
-                            const int x = b / 3, ch = b - 3 * x;
-                            for (int t = -op.radius; t <= op.radius; ++t) acc += rp[clampi(x + t, 0, W - 1) * 3 + ch];
-                            far = (u32)rp[clampi(x - op.radius - 1, 0, W - 1) * 3 + ch] +
-                                  (u32)rp[clampi(x + op.radius + 1, 0, W - 1) * 3 + ch];
-                        } else {
-                            for (int t = -op.radius; t <= op.radius; ++t) acc += fa[clampi(y + t, 0, H - 1) * RB + b];
-                            far = (u32)fa[clampi(y - op.radius - 1, 0, H - 1) * RB + b] +
-                                  (u32)fa[clampi(y + op.radius + 1, 0, H - 1) * RB + b];
-                        }
-                        fb[i] = box_out(acc, far, op.ww, op.fw);
-                    }
-                    if (p < 5) {   // the last pass is swapped below
-                        __syncthreads();
-                        u8* t = fa; fa = fb; fb = t;
-                    }
-                }
-                break;
-            }
-            case IMGXF_POOL_ENHANCE_SHARPNESS: {
-                // blend(im1 = frame.filter(SMOOTH), im2 = frame, factor)
-                for (u32 i = tid; i < NB; i += PC_THREADS) {
-                    const int y = (int)(i / (u32)RB), b = (int)i - y * RB;
-                    const u8* r0 = fa + y * RB;
-                    const bool inner = y > 0 && y < H - 1 && W >= 3 && b >= 3 && b < RB - 3;
-                    const u8 sm = inner ? filter3x3_at(r0 - RB, r0, r0 + RB, b, 3, op.k9) : r0[b];
-                    fb[i] = (u8)pack_u8(blend_floor((float)sm, (float)r0[b], factor));
-                }
-                break;
-            }
-            case IMGXF_POOL_ENHANCE_CONTRAST: {
-                u32 part = 0;
-                for (u32 p = tid; p < HW; p += PC_THREADS) part += luma_u8(fa[3 * p], fa[3 * p + 1], fa[3 * p + 2]);
-                const float mean = contrast_mean(wg_sum(part, scratch), (int64_t)HW);
-                for (u32 i = tid; i < NB; i += PC_THREADS) fb[i] = (u8)pack_u8(blend_floor(mean, (float)fa[i], factor));
-                break;
-            }
-            case IMGXF_POOL_ENHANCE_COLOR: {
-                for (u32 p = tid; p < HW; p += PC_THREADS) {
-                    const float L = (float)luma_u8(fa[3 * p], fa[3 * p + 1], fa[3 * p + 2]);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) fb[3 * p + c] = (u8)pack_u8(blend_floor(L, (float)fa[3 * p + c], factor));
-                }
-                break;
-            }
-            case IMGXF_POOL_ENHANCE_BRIGHTNESS: {
-                for (u32 i = tid; i < NB; i += PC_THREADS) fb[i] = (u8)pack_u8(blend_floor(0.0f, (float)fa[i], factor));
-                break;
-            }
-            case IMGXF_POOL_GAUSSIAN_NOISE: {
-                for (u32 i = tid; i < NB; i += PC_THREADS) {
-                    double v = (double)(float)fa[i] + data[i];
-                    v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);                     // np.clip
-                    fb[i] = (u8)(int)v;                                               // astype(np.uint8)
-                }
-                break;
-            }
-            case IMGXF_POOL_IMPULSE_NOISE: {
-                for (u32 i = tid; i < NB; i += PC_THREADS) {
-                    const double mv = data[i / 3];
-                    fb[i] = mv < op.lo ? (u8)0 : (mv > op.hi ? (u8)255 : fa[i]);
-                }
-                break;
-            }
-            case IMGXF_POOL_SHOT_NOISE: {
-                for (u32 i = tid; i < NB; i += PC_THREADS) {
-                    double v = data[i] / op.lo * 255.0;
-                    v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);
-                    fb[i] = (u8)(int)v;
-                }
-                break;
-            }
-            case IMGXF_POOL_MOTION_BLUR: {
-                const int half = op.arg >> 1;
-                for (u32 i = tid; i < NB; i += PC_THREADS) {
-                    const int y = (int)(i / (u32)RB), b = (int)i - y * RB;
-                    const int x = b / 3, ch = b - 3 * x;
-                    const u8* rp = fa + y * RB;
-                    u32 sum = 0;
-                    for (int t = -half; t <= half; ++t) sum += rp[reflect101(x + t, W) * 3 + ch];
-                    fb[i] = (u8)sat_u8_rne((float)sum * op.tap);
-                }
-                break;
-            }
-            case IMGXF_POOL_HISTOGRAM_EQUALIZATION: {
-                const Rgb2Yuv to_yuv;
-                const Yuv2Rgb to_rgb;
-                hist[tid] = 0;
-                __syncthreads();
-                for (u32 p = tid; p < HW; p += PC_THREADS) {
-                    const u32 c[3] = {fa[3 * p], fa[3 * p + 1], fa[3 * p + 2]};
-                    u32 o[3];
-                    to_yuv(c, o);
-                    atomicAdd(&hist[o[0]], 1u);
-                }
-                __syncthreads();
-                if (tid == 0) cv_equalize_table(hist, lut);
-                __syncthreads();
-                for (u32 p = tid; p < HW; p += PC_THREADS) {
-                    const u32 c[3] = {fa[3 * p], fa[3 * p + 1], fa[3 * p + 2]};
-                    u32 yuv[3], o[3];
-                    to_yuv(c, yuv);
-                    yuv[0] = lut[yuv[0]];
-                    to_rgb(yuv, o);
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) fb[3 * p + j] = (u8)o[j];
-                }
-                break;
-            }
-            default:
-                continue;
-        }
-        __syncthreads();
-        u8* t = fa; fa = fb; fb = t;
-    }
-
-    for (u32 i = tid; i < NB; i += PC_THREADS) {
-        const u32 y = i / (u32)RB;
-        A.d.row(f, (int)y)[i - y * (u32)RB] = fa[i];
-    }
+    pc_run_frame(pc_lds, A.s.row(f, 0), A.s.rs, A.d.row(f, 0), A.d.rs, A.s.h, A.s.w, fa, fa + A.frame_bytes,
+                 A.plan + (int64_t)f * PC_STEP_BYTES * A.steps, A.steps, A.nops, A.ops, A.payload, A.payload_bytes);
 }
 
-} // namespace
-} // namespace imgxf
+// A list of frames of any sizes: workgroup b of a launch runs frame record first + b.  The records of one launch are of
+// one LDS class (imgxf_pool_chain_list_class), so the launch declares the LDS of the largest frame in it.
+struct PcListArgs {
+    const imgxf_pool_list_frame* frames;   // device copy of the records
+    const u8* block;
+    const u8* payload;
+    uint64_t payload_bytes;
+    u8* out;
+    u8* ws;
+    int first, nops;
+    PcOp ops[IMGXF_POOL_MAX_OPS];
+};
 
-using namespace imgxf;
-
-IMGXF_API int imgxf_pool_chain_record_bytes(int32_t steps, size_t* bytes) {
-    if (!bytes) return IMGXF_ERR_NULL;
-    if (steps < 1 || steps > IMGXF_POOL_MAX_STEPS) return IMGXF_ERR_ARG;
-    *bytes = (size_t)PC_STEP_BYTES * steps;
-    return IMGXF_OK;
+template <bool RESIDENT>
+__global__ __launch_bounds__(PC_THREADS) void pool_chain_list_kernel(PcListArgs A) {
+    extern __shared__ __attribute__((aligned(16))) u8 pc_lds[];
+    const imgxf_pool_list_frame& fr = A.frames[A.first + (int)blockIdx.x];
+    const int h = fr.h, w = fr.w;
+    const int frame_bytes = (3 * h * w + 15) & ~15;
+    u8* fa = RESIDENT ? pc_lds + PC_FIXED : A.ws + fr.ws_off;
+    pc_run_frame(pc_lds, (const u8*)fr.src, fr.src_stride, A.out + fr.out_off, (int64_t)3 * w, h, w, fa, fa + frame_bytes,
+                 A.block + fr.rec_off, fr.steps, A.nops, A.ops, A.payload, A.payload_bytes);
 }
 
-IMGXF_API int imgxf_pool_chain_workspace_bytes(int32_t n, int32_t h, int32_t w, size_t* bytes) {
-    if (!bytes) return IMGXF_ERR_NULL;
-    if (n < 0 || h < 1 || w < 1 || h > 32767 || w > 32767 || 3 * (int64_t)h * w > 0x7fffff00) return IMGXF_ERR_SHAPE;
-    *bytes = pc_resident(h, w) ? 0 : (size_t)n * 2 * (size_t)pc_frame_bytes(h, w);
-    return IMGXF_OK;
-}
-
-IMGXF_API int imgxf_pool_chain_u8(const imgxf_view* src, const imgxf_view* dst, const imgxf_pool_op* ops, int32_t nops,
-                                  const void* plan, int32_t steps, const void* payload, size_t payload_bytes,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    if (!ops) return IMGXF_ERR_NULL;
-    IMGXF_CHECK(check_view(src));
-    IMGXF_CHECK(check_view(dst));
-    if (!same_geometry(src, dst) || src->c != 3) return IMGXF_ERR_SHAPE;
-    const int n = src->n;
-    if (n > 0 && !plan) return IMGXF_ERR_NULL;
-    if (payload_bytes > 0 && !payload) return IMGXF_ERR_NULL;
-    size_t need = 0, rec = 0;
-    IMGXF_CHECK(imgxf_pool_chain_workspace_bytes(n, src->h < 1 ? 1 : src->h, src->w < 1 ? 1 : src->w, &need));
-    IMGXF_CHECK(imgxf_pool_chain_record_bytes(steps, &rec));
-    if (nops < 1 || nops > IMGXF_POOL_MAX_OPS) return IMGXF_ERR_ARG;
-    PcArgs A;
-    memset(&A, 0, sizeof(A));
+// The operation table as the kernels read it; IMGXF_ERR_ARG for an unknown code or an argument outside its range.
+int pc_fill_ops(const imgxf_pool_op* ops, int nops, PcOp* out) {
     for (int i = 0; i < nops; ++i) {
         const imgxf_pool_op& o = ops[i];
-        PcOp& d = A.ops[i];
+        PcOp& d = out[i];
         d.code = o.code;
         d.arg = o.arg;
         switch (o.code) {
@@ -303,6 +143,53 @@ IMGXF_API int imgxf_pool_chain_u8(const imgxf_view* src, const imgxf_view* dst, 
             default: return IMGXF_ERR_ARG;
         }
     }
+    return IMGXF_OK;
+}
+
+inline bool pc_shape_ok(int h, int w) { return h >= 1 && w >= 1 && h <= 32767 && w <= 32767 && 3 * (int64_t)h * w <= 0x7fffff00; }
+
+// LDS classes of resident frames: the dynamic LDS a frame needs is at most PC_CLASS_LDS[class].  The kernels hold about
+// 140 VGPRs, which admits three waves per SIMD, i.e. three workgroups of four waves per CU; LDS costs occupancy only past
+// a third of the CU's 160 KiB.  So: up to 52 KiB (three workgroups per CU), up to 80 KiB (two), the rest (one).
+constexpr int PC_CLASSES = 3;
+constexpr int PC_CLASS_LDS[PC_CLASSES] = {53248, 81920, PC_LDS_MAX};
+
+} // namespace
+} // namespace imgxf
+
+using namespace imgxf;
+
+IMGXF_API int imgxf_pool_chain_record_bytes(int32_t steps, size_t* bytes) {
+    if (!bytes) return IMGXF_ERR_NULL;
+    if (steps < 1 || steps > IMGXF_POOL_MAX_STEPS) return IMGXF_ERR_ARG;
+    *bytes = (size_t)PC_STEP_BYTES * steps;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_pool_chain_workspace_bytes(int32_t n, int32_t h, int32_t w, size_t* bytes) {
+    if (!bytes) return IMGXF_ERR_NULL;
+    if (n < 0 || !pc_shape_ok(h, w)) return IMGXF_ERR_SHAPE;
+    *bytes = pc_resident(h, w) ? 0 : (size_t)n * 2 * (size_t)pc_frame_bytes(h, w);
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_pool_chain_u8(const imgxf_view* src, const imgxf_view* dst, const imgxf_pool_op* ops, int32_t nops,
+                                  const void* plan, int32_t steps, const void* payload, size_t payload_bytes,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    if (!ops) return IMGXF_ERR_NULL;
+    IMGXF_CHECK(check_view(src));
+    IMGXF_CHECK(check_view(dst));
+    if (!same_geometry(src, dst) || src->c != 3) return IMGXF_ERR_SHAPE;
+    const int n = src->n;
+    if (n > 0 && !plan) return IMGXF_ERR_NULL;
+    if (payload_bytes > 0 && !payload) return IMGXF_ERR_NULL;
+    size_t need = 0, rec = 0;
+    IMGXF_CHECK(imgxf_pool_chain_workspace_bytes(n, src->h < 1 ? 1 : src->h, src->w < 1 ? 1 : src->w, &need));
+    IMGXF_CHECK(imgxf_pool_chain_record_bytes(steps, &rec));
+    if (nops < 1 || nops > IMGXF_POOL_MAX_OPS) return IMGXF_ERR_ARG;
+    PcArgs A;
+    memset(&A, 0, sizeof(A));
+    IMGXF_CHECK(pc_fill_ops(ops, nops, A.ops));
     if (empty_view(src)) return IMGXF_OK;
     if (need > 0) {
         if (workspace_bytes < need) return IMGXF_ERR_WORKSPACE;
@@ -325,4 +212,80 @@ IMGXF_API int imgxf_pool_chain_u8(const imgxf_view* src, const imgxf_view* dst, 
         hipLaunchKernelGGL(pool_chain_kernel<false>, dim3((unsigned)n), dim3(PC_THREADS), (size_t)PC_FIXED, st, A);
     }
     return launch_status();
+}
+
+IMGXF_API int imgxf_pool_chain_list_class(int32_t h, int32_t w, int32_t* cls, size_t* lds_bytes, size_t* workspace_bytes) {
+    if (!cls || !lds_bytes || !workspace_bytes) return IMGXF_ERR_NULL;
+    if (!pc_shape_ok(h, w)) return IMGXF_ERR_SHAPE;
+    const size_t pair = 2 * (size_t)pc_frame_bytes(h, w);
+    if (!pc_resident(h, w)) {
+        *cls = IMGXF_POOL_LIST_CLASSES - 1; *lds_bytes = PC_FIXED; *workspace_bytes = pair;
+        return IMGXF_OK;
+    }
+    int c = 0;
+    while (pair + PC_FIXED > (size_t)PC_CLASS_LDS[c]) ++c;
+    *cls = c; *lds_bytes = pair + PC_FIXED; *workspace_bytes = 0;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_pool_chain_list_u8(const imgxf_pool_list_frame* frames, int32_t n, const imgxf_pool_op* ops, int32_t nops,
+                                       const void* block, size_t block_bytes, size_t frames_off,
+                                       const void* payload, size_t payload_bytes, void* out, size_t out_bytes,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(PC_CLASSES + 1 == IMGXF_POOL_LIST_CLASSES, "resident classes plus the workspace class");
+    static_assert(sizeof(imgxf_pool_list_frame) == 56, "struct imgxf_pool_list_frame (include/imgxf.h)");
+    if (!ops) return IMGXF_ERR_NULL;
+    if (n < 0) return IMGXF_ERR_SHAPE;
+    if (n > 0 && (!frames || !block || !out)) return IMGXF_ERR_NULL;
+    if (payload_bytes > 0 && !payload) return IMGXF_ERR_NULL;
+    if (nops < 1 || nops > IMGXF_POOL_MAX_OPS) return IMGXF_ERR_ARG;
+    PcListArgs A;
+    memset(&A, 0, sizeof(A));
+    IMGXF_CHECK(pc_fill_ops(ops, nops, A.ops));
+    if (n == 0) return IMGXF_OK;
+    if ((((uintptr_t)block) & 7) || (((uintptr_t)payload) & 7) || (((uintptr_t)out) & 15) || (frames_off & 7)) return IMGXF_ERR_ARG;
+    if (frames_off > block_bytes || (block_bytes - frames_off) / sizeof(imgxf_pool_list_frame) < (size_t)n) return IMGXF_ERR_ARG;
+    int first[IMGXF_POOL_LIST_CLASSES + 1];          // records first[c] .. first[c + 1] - 1 are of class c
+    size_t lds_max[IMGXF_POOL_LIST_CLASSES] = {0};
+    int at = 0;
+    first[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        const imgxf_pool_list_frame& f = frames[i];
+        int32_t c = 0;
+        size_t lds = 0, ws = 0;
+        IMGXF_CHECK(imgxf_pool_chain_list_class(f.h, f.w, &c, &lds, &ws));
+        const size_t bytes = 3 * (size_t)f.h * f.w;
+        if (!f.src) return IMGXF_ERR_NULL;
+        if (f.src_stride < 3 * (int64_t)f.w) return IMGXF_ERR_SHAPE;
+        if (f.steps < 0 || f.steps > IMGXF_POOL_MAX_STEPS) return IMGXF_ERR_ARG;
+        if ((f.rec_off & 7) || f.rec_off > block_bytes || block_bytes - f.rec_off < (size_t)PC_STEP_BYTES * f.steps) return IMGXF_ERR_ARG;
+        if ((f.out_off & 15) || f.out_off > out_bytes || out_bytes - f.out_off < bytes) return IMGXF_ERR_ARG;
+        if (ws > 0) {
+            if (f.ws_off > workspace_bytes || workspace_bytes - f.ws_off < ws) return IMGXF_ERR_WORKSPACE;
+            if (!workspace) return IMGXF_ERR_NULL;
+            if ((((uintptr_t)workspace) & 15) || (f.ws_off & 15)) return IMGXF_ERR_ARG;
+        }
+        if (c < at) return IMGXF_ERR_ARG;             // the records come sorted by class
+        while (at < c) first[++at] = i;
+        if (lds > lds_max[c]) lds_max[c] = lds;
+    }
+    while (at < IMGXF_POOL_LIST_CLASSES) first[++at] = n;
+    A.frames = (const imgxf_pool_list_frame*)((const u8*)block + frames_off);
+    A.block = (const u8*)block; A.payload = (const u8*)payload; A.payload_bytes = payload_bytes;
+    A.out = (u8*)out; A.ws = (u8*)workspace; A.nops = nops;
+    hipStream_t st = (hipStream_t)stream;
+    for (int c = 0; c < IMGXF_POOL_LIST_CLASSES; ++c) {
+        const int count = first[c + 1] - first[c];
+        if (!count) continue;
+        A.first = first[c];
+        if (c < PC_CLASSES) {
+            if (lds_max[c] > 65536)   // as imgxf_pool_chain_u8 asks for it
+                (void)hipFuncSetAttribute((const void*)pool_chain_list_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max[c]);
+            hipLaunchKernelGGL(pool_chain_list_kernel<true>, dim3((unsigned)count), dim3(PC_THREADS), lds_max[c], st, A);
+        } else {
+            hipLaunchKernelGGL(pool_chain_list_kernel<false>, dim3((unsigned)count), dim3(PC_THREADS), (size_t)PC_FIXED, st, A);
+        }
+        IMGXF_CHECK(launch_status());
+    }
+    return IMGXF_OK;
 }

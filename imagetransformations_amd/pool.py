@@ -7,6 +7,7 @@ against Pillow / the reference's NumPy expressions."""
 from __future__ import annotations
 
 import ctypes
+import functools
 import random
 from collections.abc import Sequence
 from dataclasses import dataclass
@@ -232,7 +233,9 @@ class ChainPlan:
     the C float of an ENHANCE_* step's factor; table: entries (code, arg, m[10]); data: (image, step) -> the step's
     float64 normals [h,w,3] or mask [h,w] (a numpy array, or a device tensor from numpy_stream) or Poisson counts
     [h,w,3]; late: the first image holding shot_noise (n if none) — its np.random draws and all after it wait for
-    `chain_plan_finish`; split [n]: the step each image's second launch starts at (its chain length if none)."""
+    `chain_plan_finish`; split [n]: the step each image's second launch starts at (its chain length if none);
+    sizes: per image, (h, w) — `chain_plan_list` plans frames of different sizes, and h, w are then the common size,
+    or 0 where the sizes differ."""
     n: int
     h: int
     w: int
@@ -245,6 +248,11 @@ class ChainPlan:
     late: int
     split: np.ndarray
     finished: bool = False
+    sizes: list | None = None
+
+    def __post_init__(self):
+        if self.sizes is None:
+            self.sizes = [(self.h, self.w)] * self.n
 
     @property
     def steps(self) -> int:
@@ -277,7 +285,7 @@ def _entry(name: str, arg):
 def _draw_np(plan: ChainPlan, i: int, s: int, frame, device) -> None:
     """np.random draws of step s of image i, as the member makes them (frame: the host frame shot_noise reads)."""
     name, arg = plan.members[i][s], plan.args[i][s]
-    h, w = plan.h, plan.w
+    h, w = plan.sizes[i]
     if name == "gaussian_noise":
         noise_std = _SEVERITY_TABLES[name][arg - 1]
         z = T._numpy_noise([(h * w * 3, noise_std * 255)], device, f64=True)[0]    # the member's device branch
@@ -295,11 +303,22 @@ def chain_plan(n: int, h: int, w: int, chains, device=None) -> ChainPlan:
     to the first image holding shot_noise), in the loop's order, and resolve each step for the kernel.  Every chain
     must be one the kernel takes (`chain_runs`).  No device work apart from numpy_stream's, which the loop makes too;
     `device` is where gaussian_noise's device-drawn normals go (the current device by default)."""
+    plan = chain_plan_list([(h, w)] * n, chains, device)
+    plan.h, plan.w = h, w
+    return plan
+
+
+def chain_plan_list(sizes, chains, device=None) -> ChainPlan:
+    """`chain_plan` for images of their own sizes [(h, w)]: image i draws 3 * h_i * w_i normals for gaussian_noise,
+    h_i * w_i uniforms for impulse_noise, as the member does on a frame of that size.  The np.random requests still go
+    through one `T._numpy_mixed` call, gated on their total."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    n = len(sizes)
     per = _chains_per_image(chains, n)
     if not all(_kernel_takes(c) for c in per):
         raise ValueError("chain_plan: a chain holds shot_noise after a member that draws from np.random (see chain_runs)")
     choice, uniform = random.choice, random.uniform
-    severities, sizes = [1, 2, 3, 4, 5], _MOTION_SIZES
+    severities, motion_sizes = [1, 2, 3, 4, 5], _MOTION_SIZES
     members, args = [], []
     for c in per:                                            # `random` draws, in loop order
         names, vals = [], []
@@ -308,7 +327,7 @@ def chain_plan(n: int, h: int, w: int, chains, device=None) -> ChainPlan:
                 if name in _SEVERITY_TABLES:
                     arg = choice(severities)
                 elif name == "motion_blur":
-                    arg = choice(sizes)
+                    arg = choice(motion_sizes)
                 elif name in _FACTOR_RANGES:
                     arg = uniform(*_FACTOR_RANGES[name])
             names.append(name)
@@ -335,9 +354,11 @@ def chain_plan(n: int, h: int, w: int, chains, device=None) -> ChainPlan:
     split = np.array([len(m) for m in members], np.int64)
     for i in range(late, n):
         split[i] = next((s for s, name in enumerate(members[i]) if name in _NP_DRAWING), len(members[i]))
-    plan = ChainPlan(n, h, w, members, args, index, factors, table, {}, late, split)
+    h, w = sizes[0] if n and all(hw == sizes[0] for hw in sizes) else (0, 0)
+    plan = ChainPlan(n, h, w, members, args, index, factors, table, {}, late, split, sizes=sizes)
     requests, slots = [], []                                 # `np.random` draws that do not wait for pixels, in loop order
     for i in range(late):
+        h, w = sizes[i]
         for s, (name, arg) in enumerate(zip(members[i], args[i])):
             if name == "gaussian_noise":
                 requests.append(("normal", h * w * 3, _SEVERITY_TABLES[name][arg - 1] * 255))
@@ -358,8 +379,8 @@ def chain_plan(n: int, h: int, w: int, chains, device=None) -> ChainPlan:
 
 def chain_plan_finish(plan: ChainPlan, frames, device=None) -> ChainPlan:
     """The second plan step of a batch holding shot_noise: the np.random draws of images plan.late.. in loop order.
-    frames: host uint8 [n, h, w, 3], image i as it stands before step plan.split[i] (only images with a draw at
-    their split are read)."""
+    frames: host uint8 [n, h, w, 3] (or a sequence of n [h_i, w_i, 3] arrays), image i as it stands before step
+    plan.split[i] (only images with a draw at their split are read)."""
     if plan.finished:
         raise ValueError("chain_plan_finish: the plan has no draws left")
     for i in range(plan.late, plan.n):
@@ -412,6 +433,15 @@ def _run(plan: ChainPlan, src: torch.Tensor, dst: torch.Tensor, lo, hi) -> None:
     _launch_staged(src, dst, *_stage(plan, src.device, lo, hi))
 
 
+def _op_table(table):
+    """The operation table as ctypes hands it over (one zeroed entry for an empty table)."""
+    op_tab = (F.PoolOp * max(1, len(table)))()
+    for k, (code, arg, m) in enumerate(table):
+        op_tab[k].code, op_tab[k].arg = code, arg
+        op_tab[k].m[:] = m
+    return op_tab
+
+
 def _stage(plan: ChainPlan, device, lo, hi):
     """Records and payload of one launch on the device, the operation table and the workspace."""
     n, h, w = plan.n, plan.h, plan.w
@@ -428,11 +458,7 @@ def _stage(plan: ChainPlan, device, lo, hi):
         gpu[rec_bytes + off:rec_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
     ws_bytes = chain_workspace_bytes(n, h, w)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
-    op_tab = (F.PoolOp * max(1, len(plan.table)))()
-    for k, (code, arg, m) in enumerate(plan.table):
-        op_tab[k].code, op_tab[k].arg = code, arg
-        op_tab[k].m[:] = m
-    return gpu, rec.shape[1] // _STEP_BYTES, rec_bytes, payload_bytes, op_tab, max(1, len(plan.table)), ws, ws_bytes
+    return gpu, rec.shape[1] // _STEP_BYTES, rec_bytes, payload_bytes, _op_table(plan.table), max(1, len(plan.table)), ws, ws_bytes
 
 
 def _launch_staged(src, dst, gpu, steps, rec_bytes, payload_bytes, op_tab, nops, ws, ws_bytes) -> None:
@@ -500,3 +526,201 @@ def apply_chain_batch(frames: torch.Tensor, chains) -> torch.Tensor:
         else:
             out[a] = _run_loop(x[a], per[a])
     return out[0] if frames.dim() == 3 else out
+
+
+# ---- chains on a list of frames of any sizes ---------------------------------------------------------------------------
+# `apply_chain_list` is `apply_chain_batch` for frames that each have their own size: every frame of the call is one
+# workgroup of the same grid (imgxf_pool_chain_list_u8), whatever its size.
+CHAIN_LIST_BYTES = 1 << 30      # float64 payload plus workspace of one launch group (see apply_chain_list)
+_LIST_FRAME = np.dtype([("src", "<u8"), ("src_stride", "<i8"), ("out_off", "<u8"), ("ws_off", "<u8"), ("rec_off", "<u8"),
+                        ("h", "<i4"), ("w", "<i4"), ("steps", "<i4"), ("pad_", "<i4")])   # struct imgxf_pool_list_frame
+_PAYLOAD_PER_PIXEL = {"gaussian_noise": 24, "impulse_noise": 8, "shot_noise": 24}        # float64 [h,w,3] or [h,w]
+
+
+def _r16(nbytes):
+    return (nbytes + 15) & ~15
+
+
+@functools.lru_cache(maxsize=1 << 14)
+def chain_list_class(h: int, w: int):
+    """(launch class, LDS bytes, workspace bytes) of one h x w frame in a list pass (imgxf_pool_chain_list_class):
+    classes 0..2 are resident frames by LDS need, class 3 frames whose working pair lives in the workspace."""
+    cls, lds, ws = ctypes.c_int32(), ctypes.c_size_t(), ctypes.c_size_t()
+    F.call("imgxf_pool_chain_list_class", h, w, ctypes.byref(cls), ctypes.byref(lds), ctypes.byref(ws))
+    return cls.value, lds.value, ws.value
+
+
+def chain_list_bytes(size, chain) -> int:
+    """What one image counts against CHAIN_LIST_BYTES: the float64 payload of its noise members and its workspace."""
+    h, w = size
+    return h * w * sum(_PAYLOAD_PER_PIXEL.get(name, 0) for name, _ in chain) + chain_list_class(h, w)[2]
+
+
+def chain_list_groups(sizes, chains) -> list:
+    """[(start, stop, batched)] of a list call: `chain_runs`, with each batched run cut, in image order, into
+    consecutive launch groups whose payload plus workspace stays within CHAIN_LIST_BYTES (read at call time).  An image
+    above the budget by itself is a group of its own.  No draw, no device work."""
+    sizes = list(sizes)
+    per = _chains_per_image(chains, len(sizes))
+    budget, groups = int(CHAIN_LIST_BYTES), []
+    for a, b, batched in chain_runs(per, len(sizes)):
+        if not batched:
+            groups.append((a, b, False))
+            continue
+        start, used = a, 0
+        for i in range(a, b):
+            cost = chain_list_bytes(sizes[i], per[i])
+            if i > start and used + cost > budget:
+                groups.append((start, i, True))
+                start, used = i, 0
+            used += cost
+        groups.append((start, b, True))
+    return groups
+
+
+def _stage_list(plan: ChainPlan, device, lo, hi, src, src_stride, out_off):
+    """One launch group on the device: the frame records (sorted by launch class), the step records and the host-drawn
+    payload go up in ONE host-to-device copy; device-drawn payload slices are copied on the device."""
+    n = plan.n
+    rec, host, dev, payload_bytes = _records(plan, lo, hi)
+    cls = np.empty(n, np.int64)
+    ws = np.empty(n, np.int64)
+    for i, (h, w) in enumerate(plan.sizes):
+        cls[i], _, ws[i] = chain_list_class(h, w)
+    order = np.argsort(cls, kind="stable")
+    fr = np.zeros(n, _LIST_FRAME)
+    fr["src"], fr["src_stride"], fr["out_off"] = src, src_stride, out_off
+    fr["ws_off"] = np.cumsum(ws) - ws
+    fr["rec_off"] = n * _LIST_FRAME.itemsize + np.arange(n, dtype=np.uint64) * np.uint64(rec.shape[1])
+    fr["h"], fr["w"] = np.array(plan.sizes, np.int32).reshape(n, 2).T
+    fr["steps"] = np.asarray(hi, np.int64) - np.asarray(lo, np.int64)
+    fr = fr[order]
+    head = fr.nbytes + rec.nbytes
+    head_bytes = _r16(head)
+    staged = torch.empty(head_bytes + sum(a.nbytes for _, a in host), dtype=torch.uint8, pin_memory=True)
+    buf = staged.numpy()
+    buf[:fr.nbytes] = fr.view(np.uint8)
+    buf[fr.nbytes:head] = rec.reshape(-1)
+    for off, a in host:
+        buf[head_bytes + off:head_bytes + off + a.nbytes] = a.reshape(-1).view(np.uint8)
+    gpu = torch.empty(head_bytes + payload_bytes, dtype=torch.uint8, device=device)
+    gpu[:staged.numel()].copy_(staged, non_blocking=True)   # one host-to-device copy per launch group
+    for off, t in dev:
+        gpu[head_bytes + off:head_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
+    ws_bytes = int(ws.sum())
+    wsp = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
+    table = plan.table or [(F.POOL_CODES["enhance_brightness"], 0, [0.0] * 10)]   # no chain has a step: the kernel copies
+    return staged, n, _op_table(table), len(table), gpu, head_bytes, payload_bytes, wsp, ws_bytes
+
+
+def _launch_list_staged(out, staged, n, op_tab, nops, gpu, head_bytes, payload_bytes, wsp, ws_bytes) -> None:
+    ops._launch(out, "imgxf_pool_chain_list_u8", staged.data_ptr(), n, op_tab, nops, gpu.data_ptr(), head_bytes, 0,
+                gpu.data_ptr() + head_bytes if payload_bytes else None, payload_bytes, out.data_ptr(), out.numel(),
+                wsp.data_ptr() if wsp is not None else None, ws_bytes)
+
+
+def _run_list(frames, sizes, block: torch.Tensor, out_off, chains) -> None:
+    """One launch group: plan, draw and launch frames (each a [h, w, 3] view) into block at out_off."""
+    n, device = len(frames), block.device
+    plan = chain_plan_list(sizes, chains, device)
+    src = np.array([t.data_ptr() for t in frames], np.uint64)
+    stride = np.array([t.stride(0) if h > 1 else 3 * w for t, (h, w) in zip(frames, sizes)], np.int64)
+    zero, full = np.zeros(n, np.int64), np.array([len(m) for m in plan.members], np.int64)
+    if plan.finished:
+        _launch_list_staged(block, *_stage_list(plan, device, zero, full, src, stride, out_off))
+        return
+    nbytes = np.array([_r16(3 * h * w) for h, w in sizes], np.int64)
+    mid_off = np.cumsum(nbytes) - nbytes
+    mid = torch.empty(int(nbytes.sum()), dtype=torch.uint8, device=device)
+    _launch_list_staged(mid, *_stage_list(plan, device, zero, plan.split, src, stride, mid_off))
+    back = mid.cpu().numpy()                                 # the frames before shot_noise, in one device-to-host copy
+    chain_plan_finish(plan, [back[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(mid_off.tolist(), sizes)], device)
+    mid_src = (mid.data_ptr() + mid_off).astype(np.uint64)
+    _launch_list_staged(block, *_stage_list(plan, device, plan.split, full, mid_src, [3 * w for _, w in sizes], out_off))
+
+
+def _check_list_frames(frames) -> list:
+    """[(h, w)] of the frames of a list call; ValueError for what the kernel does not read."""
+    sizes, device = [], None
+    for j, t in enumerate(frames):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"apply_chain_list: frame {j} is not a device tensor (no CPU fallback)")
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] == 0 or t.shape[1] == 0:
+            raise ValueError(f"apply_chain_list: frame {j} is not a uint8 [H,W,3] frame with H, W > 0 "
+                             f"({t.dtype}, {tuple(t.shape)})")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise ValueError("apply_chain_list expects all frames on one device")
+        F.view_of(t)                                         # the layouts the kernel reads (ValueError otherwise)
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if h > 1 and t.stride(0) < 3 * w:
+            raise ValueError(f"apply_chain_list: the rows of frame {j} overlap (row stride {t.stride(0)})")
+        chain_list_class(h, w)                               # the kernel's shape limits (ValueError)
+        sizes.append((h, w))
+    return sizes
+
+
+def apply_chain_list_block(frames, chains, guard: int = 0, guard_value: int = 0):
+    """`apply_chain_list` that also returns the call's one output allocation (a flat uint8 device tensor; None for an
+    empty list): (block, outputs).  `guard` (a multiple of 16) leaves that many bytes, set to `guard_value`, before,
+    between and after the outputs (tests/test_gpu_pool_chain_list.py)."""
+    frames = list(frames)
+    if guard < 0 or guard % 16:
+        raise ValueError("guard must be a non-negative multiple of 16")
+    sizes = _check_list_frames(frames)                       # every check before the first draw
+    n = len(frames)
+    if n == 0:
+        return None, []
+    per = _chains_per_image(chains, n)
+    groups = chain_list_groups(sizes, per)
+    nbytes = np.array([_r16(3 * h * w) for h, w in sizes], np.int64) + guard
+    out_off = guard + np.cumsum(nbytes) - nbytes
+    total, device = guard + int(nbytes.sum()), frames[0].device
+    block = torch.empty(total, dtype=torch.uint8, device=device) if not guard else \
+        torch.full((total,), guard_value, dtype=torch.uint8, device=device)
+    outputs = [block.as_strided((h, w, 3), (3 * w, 3, 1), o) for o, (h, w) in zip(out_off.tolist(), sizes)]
+    for a, b, batched in groups:
+        if batched:
+            _run_list(frames[a:b], sizes[a:b], block, out_off[a:b], per[a:b])
+        else:
+            outputs[a].copy_(_run_loop(frames[a], per[a]))
+    return block, outputs
+
+
+def apply_chain_list(frames, chains) -> list:
+    """`apply_chain_batch` for a LIST of frames of any sizes: the per-image loop of Individual.apply_transformations,
+    every frame of a launch group one workgroup of the same grid.
+
+    frames: a sequence of uint8 [H_i, W_i, 3] device tensors on one device, H_i, W_i >= 1, in any layout
+    `_ffi.view_of` takes for one frame (any row stride and byte offset; read in place); a tensor may be listed more
+    than once.  chains: as `apply_chain_batch` — one chain for every frame, or a sequence of N chains.
+    Returns N contiguous [H_i, W_i, 3] uint8 tensors, each a view starting on a 16-byte boundary into the ONE output
+    allocation the call makes, with the pixels of
+
+        img = Image.fromarray(frame); for name, arg in chain: img = getattr(TransformationPool, name)(img[, arg])
+
+    bit for bit, and leaves `random` and `np.random` where that loop leaves them: gaussian_noise draws 3 * H_i * W_i
+    normals, impulse_noise H_i * W_i uniforms, shot_noise its Poisson counts from the frame as it stands.
+
+    A launch group is one host-to-device copy (frame records, step records, host-drawn payload) and one
+    imgxf_pool_chain_list_u8 call, which launches once per LDS class present — at most four launches, whatever the
+    number of frames and sizes; a group holding shot_noise runs twice, with ONE device-to-host copy of the group's
+    frames in between for the Poisson draw (the call's only synchronisation).  Chains the kernel does not take
+    (`chain_runs`) go through the per-image loop in their place, into their slot of the allocation.
+    CHAIN_LIST_BYTES (default 1 GiB, read at call time) caps the float64 payload (24 bytes per pixel for
+    gaussian_noise and shot_noise, 8 for impulse_noise) plus workspace (2 * R16(3 H W) for a frame past the LDS
+    bound) of one launch group: a batched run above it is cut into consecutive groups of images, each planned, drawn
+    and launched before the next, which keeps the draws in image order; an image above it by itself runs alone.
+
+    One workgroup runs a whole frame, so the call's parallelism is the number of frames, not their pixels.  A frame of
+    375 x 500 takes 24 ms in its workgroup ([defocus_blur, enhance_contrast, motion_blur]) however short the list, the
+    member loop 0.83 ms per frame: 16 such frames run at 650 images/s against the loop's 1200, 32 at 1160 against
+    1210, 64 at 2240 against 1210 — the crossover is about 32 frames of that size, and the call does not gate on it
+    (profiles/pool_chain_list.txt).  For a batch of one size `apply_chain_batch` stays the documented route (1024
+    CIFAR images: 159 k against 92 k images/s).
+
+    Every check runs before the first draw: ValueError for a frame that is not a uint8 [H,W,3] device tensor, has a
+    zero side or sits on another device; the member's own exception class for a bad chain item; both generators are
+    then untouched.  An empty list returns [] and draws nothing."""
+    return apply_chain_list_block(frames, chains)[1]

@@ -350,6 +350,50 @@ int imgxf_pool_chain_u8(const imgxf_view* src, const imgxf_view* dst, const imgx
                         const void* plan, int32_t steps, const void* payload, size_t payload_bytes,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- TransformationPool chains on a LIST of frames of any sizes ---------------------------------
+ * The same chains, one workgroup per frame, on frames that each have their own size, source and
+ * place in one output allocation; the steps are the statements of imgxf_pool_chain_u8 (one device
+ * body, csrc/pool_chain_steps.inc), so a frame's bytes are those of a batch of its size.
+ *
+ * Frame record (56 bytes).  The caller writes n of them once, into the block it copies to the device
+ * (with the step records and the host-drawn payload: one host-to-device copy), and hands the HOST
+ * copy as `frames` — every check reads that one — and the place of the device copy as
+ * block + frames_off.  The two copies must hold the same bytes. */
+typedef struct imgxf_pool_list_frame {
+    uint64_t src;         /* DEVICE address of the frame's first byte; RGB uint8, pixels of a row dense */
+    int64_t  src_stride;  /* bytes from one row to the next, >= 3 * w */
+    uint64_t out_off;     /* byte offset in out of the frame's contiguous [h][w][3] result; 16-aligned */
+    uint64_t ws_off;      /* byte offset in workspace of its 2 * R16(3*h*w) working bytes; 16-aligned;
+                             read only for a frame that is not resident */
+    uint64_t rec_off;     /* byte offset in block of its `steps` step records (16 bytes each, as the
+                             plan of imgxf_pool_chain_u8; their payload offsets count from payload); 8-aligned */
+    int32_t  h, w;        /* 1..32767, 3*h*w <= 0x7fffff00 */
+    int32_t  steps;       /* 0..IMGXF_POOL_MAX_STEPS; 0 copies the frame */
+    int32_t  pad_;
+} imgxf_pool_list_frame;
+/* A frame's launch class, the dynamic LDS it needs and its workspace bytes.  Resident frames (the
+ * bound of imgxf_pool_chain_u8) fall into classes 0, 1, 2 by LDS need: up to 52 KiB (three
+ * workgroups per CU, all that the kernel's registers admit), up to 80 KiB (two per CU), up to
+ * 160 KiB (one); workspace_bytes is 0.  Every other frame is of class 3: lds_bytes is the fixed 1344 and
+ * workspace_bytes 2 * R16(3*h*w).  IMGXF_ERR_SHAPE outside the limits above. */
+enum { IMGXF_POOL_LIST_CLASSES = 4 };
+int imgxf_pool_chain_list_class(int32_t h, int32_t w, int32_t* cls, size_t* lds_bytes, size_t* workspace_bytes);
+/* One launch per class present, at most IMGXF_POOL_LIST_CLASSES, whatever n and the number of
+ * distinct sizes: the records must come sorted by class (ascending), and a launch declares the LDS
+ * of the largest frame in it.  ops / nops / payload: as imgxf_pool_chain_u8.  block (DEVICE,
+ * 8-aligned, block_bytes): holds the frame records at frames_off (8-aligned) and the step records.
+ * out (DEVICE, 16-aligned, out_bytes), workspace (DEVICE, 16-aligned; may be NULL when no frame
+ * needs one).  Outputs must not overlap each other, any source, or another frame's working bytes.
+ * Errors, all found on the host before any launch: IMGXF_ERR_NULL (ops; frames, block or out when
+ * n > 0; payload when payload_bytes > 0; a frame's src; workspace when a frame needs it),
+ * IMGXF_ERR_SHAPE (n < 0, a frame's h, w or src_stride), IMGXF_ERR_ARG (the operation table, nops,
+ * a frame's steps, a misaligned pointer or offset, records or an output outside block / out,
+ * records not sorted by class), IMGXF_ERR_WORKSPACE (a frame's working bytes outside workspace). */
+int imgxf_pool_chain_list_u8(const imgxf_pool_list_frame* frames, int32_t n, const imgxf_pool_op* ops, int32_t nops,
+                             const void* block, size_t block_bytes, size_t frames_off,
+                             const void* payload, size_t payload_bytes, void* out, size_t out_bytes,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- TransformationPool.histogram_equalization  cifar_image_transformations.py:122-129 -------
  * cv2.cvtColor(RGB2YUV / YUV2RGB) for 8-bit images (integer BT.601, yuv_shift 14) and
  * cv2.equalizeHist applied to one channel of an interleaved view.  PARITY UNPINNED: OpenCV is not

@@ -5,6 +5,14 @@ time of the bare draws and of `chain_plan`, the kernel's time from HIP events, a
 pixels and generator states.  Needs a ROCm device.
 
     python tools/bench_pool_chain.py [--repeats 3] [--loop-images 1024]
+
+`list` mode times `pool.apply_chain_list` on lists of frames: the mixed photo sizes of
+tools/bench_preprocess_list.py::mixed_sizes against the per-image loop and against grouping by size with one
+`apply_chain_batch` call per group, a uniform CIFAR list against `apply_chain_batch`, and a short list of large frames.
+Every figure comes with all its repeats.
+
+    python tools/bench_pool_chain.py list [--frames 1024] [--repeats 3] [--loop-images 64] [--group-images 256]
+                                          [--noise-frames 256]
 """
 from __future__ import annotations
 
@@ -132,13 +140,142 @@ def case(label, n, size, per, repeats, loop_images):
     return same
 
 
+def loop_list(frames, per):
+    out = []
+    for t, chain in zip(frames, per):
+        img = Image.fromarray(t.cpu().numpy())
+        for item in chain:
+            name, arg = (item, None) if isinstance(item, str) else item
+            fn = getattr(P.TransformationPool, name)
+            img = fn(img) if arg is None else fn(img, arg)
+        out.append(np.asarray(img))
+    return out
+
+
+def grouped_by_size(frames, per):
+    """The route a caller has without the list call: stack the frames of each size, one apply_chain_batch per size."""
+    groups = {}
+    for j, t in enumerate(frames):
+        groups.setdefault(tuple(t.shape), []).append(j)
+    out = [None] * len(frames)
+    for idx in groups.values():
+        got = P.apply_chain_batch(torch.stack([frames[j] for j in idx]), [per[j] for j in idx])
+        for j, g in zip(idx, got):
+            out[j] = g
+    return out
+
+
+def fmt(times, n):
+    return f"{n / min(times):10.0f} images/s  ({n} images, best {min(times) * 1e3:.2f} ms, all " \
+           f"{', '.join(f'{t * 1e3:.2f}' for t in times)} ms)"
+
+
+def list_case(label, frames, chain, repeats, loop_images, group_images, batch=None):
+    n = len(frames)
+    per = [chain] * n
+    sizes = [(int(t.shape[0]), int(t.shape[1])) for t in frames]
+    calls = []
+    real = P.ops._launch
+    P.ops._launch = lambda t, name, *a: (calls.append(name), real(t, name, *a))[1]
+    try:
+        seed(99); P.apply_chain_list(frames, per)            # warm-up, and the C-ABI calls of one call
+    finally:
+        P.ops._launch = real
+    list_calls = len(calls)
+    m, g = min(n, loop_images), min(n, group_images)
+    seed(99); loop_list(frames[:4], per[:4]); grouped_by_size(frames[:4], per[:4])
+    torch.cuda.synchronize()
+    _, t_list = best(lambda: P.apply_chain_list(frames, per), repeats)
+    _, t_loop = best(lambda: loop_list(frames[:m], per[:m]), repeats)
+    calls.clear()
+    P.ops._launch = lambda t, name, *a: (calls.append(name), real(t, name, *a))[1]
+    try:
+        _, t_group = best(lambda: grouped_by_size(frames[:g], per[:g]), repeats)
+    finally:
+        P.ops._launch = real
+    group_calls = len(calls) // repeats
+    groups = P.chain_list_groups(sizes, per)
+    payload = sum(h * w * sum(P._PAYLOAD_PER_PIXEL.get(name, 0) for name in chain) for h, w in sizes)
+    workspace = sum(P.chain_list_class(h, w)[2] for h, w in sizes)
+
+    # kernel time: the launches of the first group (its whole chains), staged once
+    seed(0)
+    a, b, _ = groups[0]
+    dev = frames[0].device
+    plan = P.chain_plan_list(sizes[a:b], per[a:b], dev)
+    nbytes = np.array([(3 * h * w + 15) & ~15 for h, w in sizes[a:b]], np.int64)
+    out = torch.empty(int(nbytes.sum()), dtype=torch.uint8, device=dev)
+    src = np.array([t.data_ptr() for t in frames[a:b]], np.uint64)
+    stride = np.array([t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1] for t in frames[a:b]], np.int64)
+    staged = P._stage_list(plan, dev, np.zeros(b - a, np.int64), [len(c) for c in plan.members], src, stride,
+                           np.cumsum(nbytes) - nbytes)
+    P._launch_list_staged(out, *staged)
+    torch.cuda.synchronize()
+    k_ms = []
+    for _ in range(repeats):
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        P._launch_list_staged(out, *staged)
+        ev1.record()
+        torch.cuda.synchronize()
+        k_ms.append(ev0.elapsed_time(ev1))
+
+    seed(5); want = loop_list(frames[:m], per[:m]); ws = random.getstate(), np.random.get_state()
+    seed(5); got = P.apply_chain_list(frames[:m], per[:m]); gs = random.getstate(), np.random.get_state()
+    same = all(np.array_equal(x, y.cpu().numpy()) for x, y in zip(want, got)) and ws[0] == gs[0] and \
+        np.array_equal(ws[1][1], gs[1][1]) and ws[1][2:] == gs[1][2:]
+
+    classes = sorted({P.chain_list_class(h, w)[0] for h, w in sizes})
+    print(f"{label}: {n} frames, {len(set(sizes))} sizes, chain {chain}")
+    print(f"  apply_chain_list      : {fmt(t_list, n)}")
+    print(f"  (a) per-image loop    : {fmt(t_loop, m)}")
+    print(f"  (b) batch per size    : {fmt(t_group, g)}  ({len(set(sizes[:g]))} sizes, {group_calls} launching C-ABI calls)")
+    if batch is not None:
+        _, t_batch = best(lambda: P.apply_chain_batch(batch, per), repeats)
+        print(f"  apply_chain_batch     : {fmt(t_batch, n)}")
+    print(f"  list call             : {list_calls} launching C-ABI calls in {len(groups)} launch group(s), LDS classes {classes}, "
+          f"payload {payload} bytes, workspace {workspace} bytes")
+    print(f"  kernels (events)      : best {min(k_ms):.3f} ms for the {b - a} frames of the first group, all "
+          f"{', '.join(f'{t:.3f}' for t in k_ms)} ms")
+    print(f"  list == loop          : {same}  ({m} frames)")
+    return same
+
+
+def list_main(args):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from bench_preprocess_list import mixed_sizes, noise_frames
+    dev = torch.device("cuda:0")
+    blur, noise = ["defocus_blur", "enhance_contrast", "motion_blur"], ["gaussian_noise", "enhance_sharpness", "impulse_noise"]
+    ok = True
+    frames, _ = noise_frames(mixed_sizes(args.frames), dev, 1)
+    ok &= list_case("mixed photo sizes", frames, blur, args.repeats, args.loop_images, args.group_images)
+    few = frames[:args.noise_frames]
+    ok &= list_case("mixed photo sizes", few, noise, args.repeats, args.loop_images, args.group_images)
+    g = torch.Generator().manual_seed(2)
+    x = torch.randint(0, 256, (1024, 32, 32, 3), dtype=torch.uint8, generator=g).to(dev)
+    for chain in (blur, noise):
+        ok &= list_case("uniform CIFAR batch", list(x), chain, args.repeats, args.loop_images, 1024, batch=x)
+    for count in (16, 32, 64):                               # one workgroup per frame: where the list passes the loop
+        big, _ = noise_frames([(375, 500)] * count, dev, 3)
+        ok &= list_case("short list of large frames", big, blur, args.repeats, count, count, batch=torch.stack(big))
+    sys.exit(0 if ok else 1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("mode", nargs="?", default="batch", choices=["batch", "list"])
+    ap.add_argument("--frames", type=int, default=1024, help="list mode: frames of the mixed-size list")
+    ap.add_argument("--group-images", type=int, default=256, help="list mode: frames timed through one batch call per size")
+    ap.add_argument("--noise-frames", type=int, default=256, help="list mode: frames of the mixed-size noise chain")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--loop-images", type=int, default=1024, help="images timed in the per-image loop")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_pool_chain needs a ROCm device")
+    if args.mode == "list":
+        if "--loop-images" not in sys.argv:
+            args.loop_images = 64
+        list_main(args)
     rng = random.Random(0)
     mixed = [[rng.choice(MEMBERS) for _ in range(3)] for _ in range(1024)]
     cases = [
