@@ -143,6 +143,12 @@ SIGNATURES = {
                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_list_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p],
+    "imgxf_jpeg_roundtrip_workspace_bytes": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_roundtrip_records_host": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p],
+    "imgxf_jpeg_roundtrip_u8": [_VP, _VP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "imgxf_jpeg_roundtrip_list_layout_host": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                              C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_roundtrip_list_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_jpeg_workspace_bytes_ex": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_optimal_tables": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "imgxf_jpeg_encode_ex_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
@@ -212,6 +218,12 @@ class JpegListFrame(C.Structure):
                 ("pad_", C.c_int32), ("stream_words", C.c_int64),
                 ("coef_off", C.c_int64), ("blk_off", C.c_int64), ("part_off", C.c_int64), ("stream_off", C.c_int64),
                 ("cnt_off", C.c_int64), ("out_off", C.c_int64), ("out_cap", C.c_int64)]
+
+
+class JpegRoundtripListHeader(C.Structure):
+    """struct imgxf_jpeg_roundtrip_list_header (include/imgxf.h)."""
+    _fields_ = [("n_frames", C.c_int32), ("frames_off", C.c_int32), ("images_off", C.c_int32), ("units_off", C.c_int32),
+                ("n_units", C.c_int32), ("total_bytes", C.c_int32), ("workspace_bytes", C.c_uint64), ("out_bytes", C.c_uint64)]
 
 
 class JpegEncParams(C.Structure):

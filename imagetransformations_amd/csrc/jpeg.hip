@@ -20,6 +20,7 @@
 //
 // Integer arithmetic throughout: bit-identical to the library (tests/test_gpu_jpeg.py compares whole files).
 #include "imgxf_common.h"
+#include "jpeg_idct.h"
 #include <stddef.h>
 #include <string.h>
 #include <new>
@@ -38,6 +39,7 @@ struct JpegQuant {                           // per coefficient (natural order):
     u32 m[2][64];                            // ceil(2^32 / (8q << sh)) < 2^24, sh = the shift that brings 8q above 256
     u32 half[2][64];                         // 4q | sh << 16
     u8 aclen[2][256];                        // bits of the AC symbol (run << 4) | size: Huffman code length + size
+    u8 step[2][64];                          // q itself, as the file's DQT states it: what a reader multiplies by (jpeg_roundtrip.inc)
 };
 struct JpegHuff {                            // code | len << 16
     u32 dc[2][16];
@@ -135,14 +137,112 @@ constexpr int zz(int i) {
     return t[i];
 }
 
+// The per-block forward statements of every transform kernel (one copy: the 4:2:0 kernel, the other layouts' and the fused
+// save-and-load instances all compile this body): 8×8 samples from LDS (origin, stride bytes between rows) minus 128 →
+// jfdctint.c both passes → jcdctmgr.c's quantiser with table `chroma` (wave-uniform), in natural order in d[].
+__device__ __forceinline__ void jpeg_forward_block(const u8* origin, int stride, int chroma, const JpegQuant& q, int (&d)[64]) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const uint2 v = *(const uint2*)(origin + r * stride);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+            d[r * 8 + x] = (int)((v.x >> (8 * x)) & 255) - 128;
+            d[r * 8 + 4 + x] = (int)((v.y >> (8 * x)) & 255) - 128;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        fdct8<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        fdct8<false>(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c]);
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {                                // jcdctmgr.c quantize: sign · ((|c| + 4q) / 8q)
+        const int v = d[i], sg = v >> 31;
+        const u32 a = (u32)((v ^ sg) - sg);
+        const u32 hs = q.half[chroma][i];
+        const u32 x = (a + (hs & 0xffff)) << (hs >> 16);         // < 2^23
+        const u32 qq = (u32)(((unsigned long long)(x & 0xffffffu) * (q.m[chroma][i] & 0xffffffu)) >> 32);   // v_mul_hi_u32_u24: full rate
+        d[i] = ((int)qq ^ sg) - sg;
+    }
+}
+
+// Which block a transform thread holds: block (bx, by) of component comp (0 Y, 1 Cb, 2 Cr) of frame f, number blk in the
+// frame's MCU order; coef_o / blk_o: the frame's element offsets in the coefficient and the per-block areas.
+struct JpegBlockAt {
+    int f, comp, bx, by;
+    int64_t blk, coef_o, blk_o;
+};
+
+// Where a transformed block goes.  The writer's sink: the bits its AC symbols will take under the code lengths
+// slen[chroma] and its DC value (so that only the DC term needs the neighbours), then the zigzag int16 coefficients.
+struct JpegCoefSink {
+    static constexpr bool CODES = true;                          // the kernel stages the AC code lengths in LDS
+    int16_t* coef;
+    int64_t coef_fs;                                             // a uniform batch: int16 elements per frame (a list's records state the offsets)
+    int16_t* dcs;
+    uint16_t* acbits;
+    int nblk;                                                    // ... and blocks per frame
+    __device__ __forceinline__ int64_t coef_offset(int f) const { return (int64_t)f * coef_fs; }
+    __device__ __forceinline__ int64_t blk_offset(int f) const { return (int64_t)f * nblk; }
+    // The block's three addresses, formed before the transform.  The uniform 4:2:0 kernel sits at the edge of the scalar
+    // register file (the quantiser's constants): with the frame's offsets and the coefficient pointer alive over the
+    // transform it spilled four scalar registers and reserved scratch.  The block's index in the per-block areas and its
+    // coefficient address are therefore made vector values before the transform and pinned there (left alone, the compiler
+    // sinks the additions behind the transform again); every transform kernel then reports no scratch.
+    struct Where {
+        uint4* out;
+        int16_t* dc;
+        uint16_t* acb;
+    };
+    __device__ __forceinline__ Where locate(const JpegBlockAt& at) const {
+        int64_t i = at.blk_o + at.blk;
+        Where w = {(uint4*)(coef + at.coef_o) + (at.blk >> 6) * 512 + (at.blk & 63), nullptr, nullptr};
+        asm volatile("" : "+v"(i), "+v"(w.out));
+        w.dc = dcs + i; w.acb = acbits + i;
+        return w;
+    }
+    __device__ __forceinline__ void operator()(int (&d)[64], int chroma, const JpegQuant&, const u8 (*slen)[256], const Where& w) const {
+        {   // bits of the AC part of this block (jchuff.c encode_one_block)
+            const u8* lt = slen[chroma];
+            u32 acc = 0, run16 = 0;                                 // acc: bits | ZRL symbols << 16; run16: 16 · zero run
+#pragma unroll
+            for (int i = 1; i < 64; ++i) {
+                const int c = d[zz(i)];
+                const u32 a = (u32)max(c, -c);
+                const u32 cat = 32 - (u32)__clz((int)a);          // 0 for a == 0; <= 11 for 8-bit samples
+                const u32 add = lt[(run16 & 0xf0) | cat] + ((run16 & 0xff00) << 8);   // code length + size; runs of 16 zeros
+                acc += a ? add : 0u;
+                run16 = a ? 0u : run16 + 16;
+            }
+            u32 bits = (acc & 0xffff) + (acc >> 16) * lt[0xF0];
+            if (run16) bits += lt[0];
+            *w.acb = (uint16_t)bits;
+            *w.dc = (int16_t)d[0];
+        }
+        // zigzag order, eight coefficients (16 bytes) at a time, interleaved over groups of 64 blocks: piece g of block b
+        // at 16-byte slot (b >> 6)·512 + g·64 + (b & 63), so that the emit kernel's one-thread-per-block walk reads
+        // consecutive 16-byte pieces across a wave
+#pragma unroll
+        for (int g = 0; g < 8; ++g) {
+            uint4 v;
+            v.x = (u32)(d[zz(g * 8 + 0)] & 0xffff) | ((u32)d[zz(g * 8 + 1)] << 16);
+            v.y = (u32)(d[zz(g * 8 + 2)] & 0xffff) | ((u32)d[zz(g * 8 + 3)] << 16);
+            v.z = (u32)(d[zz(g * 8 + 4)] & 0xffff) | ((u32)d[zz(g * 8 + 5)] << 16);
+            v.w = (u32)(d[zz(g * 8 + 6)] & 0xffff) | ((u32)d[zz(g * 8 + 7)] << 16);
+            w.out[g * 64] = v;
+        }
+    }
+};
+
 // One workgroup: rows y0 .. y0+15, columns x0 .. x0+16·JM-1 of frame f.  All threads stage and convert, then one thread
 // per block transforms — wave 0 the 64 luminance blocks, half of wave 1 the 32 chrominance blocks, so that the
 // quantiser table is wave-uniform (scalar loads).
 // (a list's unit: item = strip | MCU row << 16; the `fast` test then takes the frame's own address and stride)
-template <class W>
-__global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __restrict__ coef, int64_t coef_fs,
-                                                             int16_t* __restrict__ dcs, uint16_t* __restrict__ acbits, int nblk,
-                                                             int mw, int bw, int bh, JpegQuant q, W wh) {
+// SINK: what becomes of a block once it is quantised — JpegCoefSink (the writer) or a sink of jpeg_roundtrip.inc (the
+// block dequantised, inverse-transformed and written as samples: nothing of the entropy coder's).
+template <class W, class SINK>
+__global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, SINK sink, int mw, int bw, int bh, JpegQuant q, W wh) {
     __shared__ __attribute__((aligned(4))) u8 slen[2][256];
     __shared__ __attribute__((aligned(16))) u8 rgb[16][JPX * 3];
     __shared__ __attribute__((aligned(16))) u8 yp[16][JPX + 8];
@@ -162,11 +262,11 @@ __global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __r
         blk_o = fr->blk_off;
     } else {
         base = s.p + (int64_t)f * s.fs;
-        coef_o = (int64_t)f * coef_fs;
-        blk_o = (int64_t)f * nblk;
+        coef_o = sink.coef_offset(f);
+        blk_o = sink.blk_offset(f);
     }
     const int y0 = my * 16, x0 = mx0 * 16;
-    if (tid < 128) ((u32*)slen)[tid] = ((const u32*)q.aclen)[tid];
+    if (SINK::CODES && tid < 128) ((u32*)slen)[tid] = ((const u32*)q.aclen)[tid];
     const bool fast = (x0 + JPX <= s.w) && (((uintptr_t)base | (uintptr_t)s.rs) & 15) == 0;
     constexpr int CPR = JPX * 3 / 16;                          // 16-byte pieces per row
     for (int i = tid; i < 16 * CPR; i += JT) {
@@ -241,63 +341,12 @@ __global__ __launch_bounds__(JT) void jpeg_transform_kernel(View s, int16_t* __r
         real = true;
     }
     if (mx0 + ml >= mw || !real) return;
-    // from here on the same statements as jpeg_code_block (jpeg_encode_ext.inc, the other layouts): keep them in step
+    const JpegBlockAt at = {f, chroma ? k - 3 : 0, chroma ? mx0 + ml : 2 * (mx0 + ml) + (k & 1), chroma ? my : 2 * my + (k >> 1),
+                            ((int64_t)my * mw + mx0 + ml) * 6 + k, coef_o, blk_o};
+    const typename SINK::Where to = sink.locate(at);
     int d[64];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const uint2 v = *(const uint2*)(origin + r * stride);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            d[r * 8 + x] = (int)((v.x >> (8 * x)) & 255) - 128;
-            d[r * 8 + 4 + x] = (int)((v.y >> (8 * x)) & 255) - 128;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        fdct8<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        fdct8<false>(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c]);
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {                                // jcdctmgr.c quantize: sign · ((|c| + 4q) / 8q)
-        const int v = d[i], sg = v >> 31;
-        const u32 a = (u32)((v ^ sg) - sg);
-        const u32 hs = q.half[chroma][i];
-        const u32 x = (a + (hs & 0xffff)) << (hs >> 16);         // < 2^23
-        const u32 qq = (u32)(((unsigned long long)(x & 0xffffffu) * (q.m[chroma][i] & 0xffffffu)) >> 32);   // v_mul_hi_u32_u24: full rate
-        d[i] = ((int)qq ^ sg) - sg;
-    }
-    const int64_t blk = ((int64_t)my * mw + mx0 + ml) * 6 + k;
-    {   // bits of the AC part of this block (jchuff.c encode_one_block), so that only the DC term needs the neighbours
-        const u8* lt = slen[chroma];
-        u32 acc = 0, run16 = 0;                                 // acc: bits | ZRL symbols << 16; run16: 16 · zero run
-#pragma unroll
-        for (int i = 1; i < 64; ++i) {
-            const int c = d[zz(i)];
-            const u32 a = (u32)max(c, -c);
-            const u32 cat = 32 - (u32)__clz((int)a);          // 0 for a == 0; <= 11 for 8-bit samples
-            const u32 add = lt[(run16 & 0xf0) | cat] + ((run16 & 0xff00) << 8);   // code length + size; runs of 16 zeros
-            acc += a ? add : 0u;
-            run16 = a ? 0u : run16 + 16;
-        }
-        u32 bits = (acc & 0xffff) + (acc >> 16) * lt[0xF0];
-        if (run16) bits += lt[0];
-        acbits[blk_o + blk] = (uint16_t)bits;
-        dcs[blk_o + blk] = (int16_t)d[0];
-    }
-    // zigzag order, eight coefficients (16 bytes) at a time, interleaved over groups of 64 blocks: piece g of block b
-    // at 16-byte slot (b >> 6)·512 + g·64 + (b & 63), so that the emit kernel's one-thread-per-block walk reads
-    // consecutive 16-byte pieces across a wave
-    uint4* out = (uint4*)(coef + coef_o) + (blk >> 6) * 512 + (blk & 63);
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        uint4 v;
-        v.x = (u32)(d[zz(g * 8 + 0)] & 0xffff) | ((u32)d[zz(g * 8 + 1)] << 16);
-        v.y = (u32)(d[zz(g * 8 + 2)] & 0xffff) | ((u32)d[zz(g * 8 + 3)] << 16);
-        v.z = (u32)(d[zz(g * 8 + 4)] & 0xffff) | ((u32)d[zz(g * 8 + 5)] << 16);
-        v.w = (u32)(d[zz(g * 8 + 6)] & 0xffff) | ((u32)d[zz(g * 8 + 7)] << 16);
-        out[g * 64] = v;
-    }
+    jpeg_forward_block(origin, stride, chroma, q, d);
+    sink(d, chroma, q, slen, to);
 }
 
 // ---- layouts and block order ----------------------------------------------------------------------------------------
@@ -1089,19 +1138,25 @@ struct JpegJob {
 };
 
 // the call's tables and header as the kernels take them
-static int jpeg_prepare_tables(JpegJob& J, const imgxf_jpeg_tables* tables, int ncomp, const uint8_t* header, int header_bytes) {
-    memset(&J.q, 0, sizeof(J.q));
+// the quantiser as the transform kernels take it: reciprocals and the steps themselves (and the AC symbols' lengths)
+static int jpeg_prepare_quant(JpegQuant& q, const imgxf_jpeg_tables* tables, int ncomp) {
+    memset(&q, 0, sizeof(q));
     for (int t = 0; t < (ncomp == 1 ? 1 : 2); ++t)             // grayscale: table 0 only
         for (int i = 0; i < 64; ++i) {
             const u32 qv = tables->quant[t][i];
-            if (qv < 1 || qv > 255 || !quant_entry(qv, &J.q.m[t][i], &J.q.half[t][i])) return IMGXF_ERR_ARG;
+            if (qv < 1 || qv > 255 || !quant_entry(qv, &q.m[t][i], &q.half[t][i])) return IMGXF_ERR_ARG;
+            q.step[t][i] = (u8)qv;
         }
+    for (int t = 0; t < 2; ++t)
+        for (int i = 0; i < 256; ++i) q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));    // code + magnitude bits of the symbol
+    return IMGXF_OK;
+}
+
+static int jpeg_prepare_tables(JpegJob& J, const imgxf_jpeg_tables* tables, int ncomp, const uint8_t* header, int header_bytes) {
+    IMGXF_CHECK(jpeg_prepare_quant(J.q, tables, ncomp));
     for (int t = 0; t < 2; ++t) {
         for (int i = 0; i < 16; ++i) J.hf.dc[t][i] = (u32)tables->dc_code[t][i] | ((u32)tables->dc_len[t][i] << 16);
-        for (int i = 0; i < 256; ++i) {
-            J.hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
-            J.q.aclen[t][i] = (u8)(tables->ac_len[t][i] + (i & 15));    // code + magnitude bits of the symbol
-        }
+        for (int i = 0; i < 256; ++i) J.hf.ac[t][i] = (u32)tables->ac_code[t][i] | ((u32)tables->ac_len[t][i] << 16);
     }
     memset(&J.hd, 0, sizeof(J.hd));
     memcpy(J.hd.b, header, (size_t)header_bytes);
@@ -1348,6 +1403,8 @@ static int find_sof0(const uint8_t* h, int len) {
     return -1;
 }
 
+#include "jpeg_roundtrip.inc"
+
 } // namespace imgxf
 
 using namespace imgxf;
@@ -1439,7 +1496,8 @@ IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* bloc
     const auto grid = [&](int stage) { return dim3((unsigned)hd.n_units[stage]); };
     const JpegGeom g0 = {0, 0, 0, 0, 0};                       // the uniform arguments: unused, the records state them
     const int64_t z = 0;
-    hipLaunchKernelGGL(jpeg_transform_kernel<JpegList>, grid(0), dim3(JT), 0, st, View{}, coef, z, dcs, acb, 0, 0, 0, 0, J.q, where(0, 0));
+    hipLaunchKernelGGL((jpeg_transform_kernel<JpegList, JpegCoefSink>), grid(0), dim3(JT), 0, st, View{}, JpegCoefSink{coef, z, dcs, acb, 0}, 0, 0, 0, J.q,
+                       where(0, 0));
     hipLaunchKernelGGL((jpeg_lens_kernel<JL420, false, JpegList>), grid(1), dim3(256), 0, st, (const int16_t*)coef, z, (const int16_t*)dcs,
                        (const uint16_t*)acb, lens, g0, J.hf, (const JpegHuff*)nullptr, where(1, 0));
     IMGXF_CHECK(scan_rows_list(lens, n, hd.n_units[2], part, tot_bits, where(2, 0), st));
@@ -1452,6 +1510,52 @@ IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* bloc
     hipLaunchKernelGGL(jpeg_stuff_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits, (const u32*)cnt, z,
                        0, (const u32*)tot_ff, out, z, sizes, J.hd, where(3, 0));
     return launch_status();
+}
+
+IMGXF_API int imgxf_jpeg_roundtrip_workspace_bytes(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t* bytes) {
+    if (!bytes || !params) return IMGXF_ERR_NULL;
+    const int lay = rt_layout(params);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    size_t rec_bytes, plane_fs;
+    IMGXF_CHECK(rt_workspace(lay, n, h, w, &rec_bytes, &plane_fs));
+    *bytes = rec_bytes + (size_t)n * plane_fs;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_jpeg_roundtrip_records_host(const imgxf_jpeg_enc_params* params, int n, int h, int w, int64_t out_row_stride,
+                                                int64_t out_frame_stride, imgxf_jpeg_dec_image* images) {
+    if (!params || (n > 0 && !images)) return IMGXF_ERR_NULL;
+    const int lay = rt_layout(params);
+    if (lay < 0) return IMGXF_ERR_ARG;
+    if (lay == JLGRAY) return IMGXF_ERR_UNSUPPORTED;           // a grayscale frame is its one plane: no colour stage, no records
+    return rt_records(lay, n, h, w, out_row_stride, out_frame_stride, images);
+}
+
+IMGXF_API int imgxf_jpeg_roundtrip_u8(const imgxf_view* src, const imgxf_view* dst, const imgxf_jpeg_enc_params* params,
+                                      const imgxf_jpeg_tables* tables, void* workspace, size_t workspace_bytes, void* stream) {
+    return rt_uniform(src, dst, params, tables, workspace, workspace_bytes, stream);
+}
+
+IMGXF_API int imgxf_jpeg_roundtrip_list_layout_host(const int32_t* sizes, int n, void* block, size_t block_cap, size_t* block_bytes,
+                                                    size_t* workspace_bytes, size_t* out_bytes) {
+    if (!block_bytes || !workspace_bytes || !out_bytes || (n > 0 && !sizes)) return IMGXF_ERR_NULL;
+    imgxf_jpeg_roundtrip_list_header hd;
+    int rc;
+    try {
+        rc = rt_list_build(n, sizes, (u8*)block, block_cap, &hd);
+    } catch (const std::bad_alloc&) {
+        return IMGXF_ERR_WORKSPACE;
+    }
+    if (rc != IMGXF_OK && rc != IMGXF_ERR_WORKSPACE) return rc;
+    *block_bytes = (size_t)hd.total_bytes;                       // (a block that is too small still learns the sizes)
+    *workspace_bytes = (size_t)hd.workspace_bytes;
+    *out_bytes = (size_t)hd.out_bytes;
+    return rc;
+}
+
+IMGXF_API int imgxf_jpeg_roundtrip_list_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_tables* tables, uint8_t* out,
+                                           size_t out_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    return rt_list(block_host, block_dev, tables, out, out_bytes, workspace, workspace_bytes, stream);
 }
 
 IMGXF_API int imgxf_jpeg_workspace_bytes(int n, int h, int w, size_t out_frame_stride, size_t* bytes) {

@@ -5,7 +5,7 @@
 //
 //   jpeg_transform_ex_kernel<L>  4:4:4 (MCU 8×8: Y Cb Cr), 4:2:2 (MCU 16×8: Y Y Cb Cr; jcsample.c h2v1_downsample, bias
 //                                0, 1 along a row) and grayscale (one non-interleaved component: one block per MCU); one MCU row
-//                                of 512 pixels per workgroup, one thread per block, jpeg_code_block as the 4:2:0 kernel does
+//                                of 512 pixels per workgroup, one thread per block, jpeg_forward_block + sink as the 4:2:0 kernel
 //                                (4:2:0 itself keeps jpeg_transform_kernel)
 //   jpeg_gather_kernel<L>        optimize: jchuff.c htest_one_block — DC categories and AC symbols (ZRL, EOB) of every block,
 //                                dummy blocks included, counted per table in LDS, then added to the frame's counts
@@ -17,75 +17,13 @@
 // frame's own tables (jpeg_emit_kernel<L, true>) and the file's DHT segments and SOS are written on the device
 // (jpeg_stuff_scan_kernel with a one-scan header).
 
-// jpeg_transform_kernel's per-block stage — the same statements as that kernel's tail in jpeg.hip, which keeps its own
-// copy (factored into this function it compiled to different code); a change to one must be made to both.  8×8 samples from LDS (origin, stride bytes between rows) → fdct8 → the JpegQuant
-// quantiser (table `chroma`, wave-uniform) → the AC bits under the code lengths slen[chroma] and the DC value → zigzag
-// int16 coefficients, 16-byte pieces interleaved over groups of 64 blocks; block blk of frame f.
-__device__ __forceinline__ void jpeg_code_block(const u8* origin, int stride, int chroma, const JpegQuant& q, const u8 (*slen)[256],
-                                                int16_t* __restrict__ coef, int64_t coef_fs, int16_t* __restrict__ dcs,
-                                                uint16_t* __restrict__ acbits, int nblk, int f, int64_t blk) {
-    int d[64];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const uint2 v = *(const uint2*)(origin + r * stride);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            d[r * 8 + x] = (int)((v.x >> (8 * x)) & 255) - 128;
-            d[r * 8 + 4 + x] = (int)((v.y >> (8 * x)) & 255) - 128;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-        fdct8<true>(d[r * 8], d[r * 8 + 1], d[r * 8 + 2], d[r * 8 + 3], d[r * 8 + 4], d[r * 8 + 5], d[r * 8 + 6], d[r * 8 + 7]);
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        fdct8<false>(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c]);
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {                                // jcdctmgr.c quantize: sign · ((|c| + 4q) / 8q)
-        const int v = d[i], sg = v >> 31;
-        const u32 a = (u32)((v ^ sg) - sg);
-        const u32 hs = q.half[chroma][i];
-        const u32 x = (a + (hs & 0xffff)) << (hs >> 16);
-        const u32 qq = (u32)(((unsigned long long)(x & 0xffffffu) * (q.m[chroma][i] & 0xffffffu)) >> 32);
-        d[i] = ((int)qq ^ sg) - sg;
-    }
-    {
-        const u8* lt = slen[chroma];
-        u32 acc = 0, run16 = 0;
-#pragma unroll
-        for (int i = 1; i < 64; ++i) {
-            const int c = d[zz(i)];
-            const u32 a = (u32)max(c, -c);
-            const u32 cat = 32 - (u32)__clz((int)a);
-            const u32 add = lt[(run16 & 0xf0) | cat] + ((run16 & 0xff00) << 8);
-            acc += a ? add : 0u;
-            run16 = a ? 0u : run16 + 16;
-        }
-        u32 bits = (acc & 0xffff) + (acc >> 16) * lt[0xF0];
-        if (run16) bits += lt[0];
-        acbits[(int64_t)f * nblk + blk] = (uint16_t)bits;
-        dcs[(int64_t)f * nblk + blk] = (int16_t)d[0];
-    }
-    uint4* out = (uint4*)(coef + (int64_t)f * coef_fs) + (blk >> 6) * 512 + (blk & 63);
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        uint4 v;
-        v.x = (u32)(d[zz(g * 8 + 0)] & 0xffff) | ((u32)d[zz(g * 8 + 1)] << 16);
-        v.y = (u32)(d[zz(g * 8 + 2)] & 0xffff) | ((u32)d[zz(g * 8 + 3)] << 16);
-        v.z = (u32)(d[zz(g * 8 + 4)] & 0xffff) | ((u32)d[zz(g * 8 + 5)] << 16);
-        v.w = (u32)(d[zz(g * 8 + 6)] & 0xffff) | ((u32)d[zz(g * 8 + 7)] << 16);
-        out[g * 64] = v;
-    }
-}
-
 // One workgroup: rows y0 .. y0+7 (one MCU row), columns x0 .. x0+511 of frame f.  Staging clamps to the last column / row
 // (expand_right_edge, jcprepct.c's bottom replication; v = 1 in every layout here, so input and downsampled rows coincide).
 // Threads 0..63 transform the 64 luminance blocks, the next one or two waves the chrominance blocks (4:4:4: Cb wave, Cr
 // wave; 4:2:2: 32 Cb + 32 Cr in one wave), so the quantiser table stays wave-uniform.
-template <int L>
-__global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, int16_t* __restrict__ coef, int64_t coef_fs,
-                                                                        int16_t* __restrict__ dcs, uint16_t* __restrict__ acbits,
-                                                                        int nblk, int mw, int bw, JpegQuant q) {
+// The per-block stage is jpeg_forward_block and the SINK (jpeg.hip), as in the 4:2:0 kernel.
+template <int L, class SINK>
+__global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, SINK sink, int mw, int bw, JpegQuant q) {
     using Y = JLay<L>;
     constexpr int NC = Y::NC, CW = Y::CW, T = Y::T;
     __shared__ __attribute__((aligned(4))) u8 slen[2][256];
@@ -93,7 +31,8 @@ __global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, i
     __shared__ __attribute__((aligned(16))) u8 yp[NC == 3 ? 8 : 1][JXP + 8];
     __shared__ __attribute__((aligned(16))) u8 cp[NC == 3 ? 2 : 1][NC == 3 ? 8 : 1][CW + 8];
     const int tid = threadIdx.x, f = blockIdx.z, my = blockIdx.y, x0 = blockIdx.x * JXP, y0 = my * 8;
-    for (int i = tid; i < 128; i += T) ((u32*)slen)[i] = ((const u32*)q.aclen)[i];
+    if (SINK::CODES)
+        for (int i = tid; i < 128; i += T) ((u32*)slen)[i] = ((const u32*)q.aclen)[i];
     const u8* base = s.p + (int64_t)f * s.fs;
     const bool fast = (x0 + JXP <= s.w) && (((uintptr_t)base | (uintptr_t)s.rs) & 15) == 0;
     constexpr int CPR = JXP * NC / 16;                         // 16-byte pieces per row
@@ -138,9 +77,9 @@ __global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, i
         __syncthreads();
     }
     const u8* origin;
-    int stride, mx, k;
+    int stride, mx, k, bx;
     if (tid < JXP / 8) {
-        const int bx = x0 / 8 + tid;
+        bx = x0 / 8 + tid;
         if (bx >= bw) return;                                  // past the image, or a 4:2:2 dummy block (not transformed)
         mx = bx / Y::NY;
         k = bx - mx * Y::NY;
@@ -150,12 +89,17 @@ __global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, i
         const int c = (tid - JXP / 8) / (CW / 8), ml = (tid - JXP / 8) - c * (CW / 8);
         mx = x0 / Y::MW + ml;
         k = Y::NY + c;
+        bx = mx;
         if (mx >= mw) return;
         origin = &cp[c][0][ml * 8];
         stride = CW + 8;
     }
     const int chroma = __builtin_amdgcn_readfirstlane(tid >= JXP / 8 ? 1 : 0);
-    jpeg_code_block(origin, stride, chroma, q, slen, coef, coef_fs, dcs, acbits, nblk, f, ((int64_t)my * mw + mx) * Y::B + k);
+    const JpegBlockAt at = {f, chroma ? k - Y::NY + 1 : 0, bx, my, ((int64_t)my * mw + mx) * Y::B + k, sink.coef_offset(f), sink.blk_offset(f)};
+    const typename SINK::Where to = sink.locate(at);
+    int d[64];
+    jpeg_forward_block(origin, stride, chroma, q, d);
+    sink(d, chroma, q, slen, to);
 }
 
 // ---- optimize: symbol counts, optimal tables --------------------------------------------------------------------------
@@ -334,11 +278,11 @@ template <int L>
 static void launch_transform(const JpegJob& J) {
     const JpegLayout& G = J.L;
     if constexpr (L == JL420) {
-        hipLaunchKernelGGL(jpeg_transform_kernel<JpegUniform>, dim3((unsigned)((G.mw + JM - 1) / JM), (unsigned)G.mh, (unsigned)J.n), dim3(JT),
-                           0, J.st, J.s, J.coef, J.coef_fs, J.dcs, J.acb, G.nblk, G.mw, G.bw, G.bh, J.q, JpegUniform{});
+        hipLaunchKernelGGL((jpeg_transform_kernel<JpegUniform, JpegCoefSink>), dim3((unsigned)((G.mw + JM - 1) / JM), (unsigned)G.mh, (unsigned)J.n),
+                           dim3(JT), 0, J.st, J.s, JpegCoefSink{J.coef, J.coef_fs, J.dcs, J.acb, G.nblk}, G.mw, G.bw, G.bh, J.q, JpegUniform{});
     } else {
         const int per = JXP / JLay<L>::MW;                     // MCUs per workgroup strip
-        hipLaunchKernelGGL(jpeg_transform_ex_kernel<L>, dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)J.n),
-                           dim3(JLay<L>::T), 0, J.st, J.s, J.coef, J.coef_fs, J.dcs, J.acb, G.nblk, G.mw, G.bw, J.q);
+        hipLaunchKernelGGL((jpeg_transform_ex_kernel<L, JpegCoefSink>), dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)J.n),
+                           dim3(JLay<L>::T), 0, J.st, J.s, JpegCoefSink{J.coef, J.coef_fs, J.dcs, J.acb, G.nblk}, G.mw, G.bw, J.q);
     }
 }

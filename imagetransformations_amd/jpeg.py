@@ -3,7 +3,9 @@
 Annex-K Huffman tables, no optimisation) → libjpeg-turbo.  This module holds what the host contributes — the quality →
 quantisation-table rule (jcparam.c jpeg_set_quality), the canonical Huffman codes of the Annex-K tables (jchuff.c
 jpeg_make_c_derived_tbl), the marker segments before the scan (jcmarker.c) — and `encode`, which runs a batch of frames
-through the kernels and returns one `bytes` per frame.  Nothing here computes pixels; there is no CPU fallback."""
+through the kernels and returns one `bytes` per frame.  `roundtrip` / `roundtrip_list` apply the same compression to
+frames that stay on the device: the pixels a reader gets back from the file, without the file.  Nothing here computes
+pixels; there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes
@@ -358,4 +360,214 @@ def encode_list_views(frames: Sequence[torch.Tensor], quality: int = 75, *, subs
         host = memoryview(staged.numpy())
         for k, i in enumerate(default):
             result[i] = host[starts[k]:starts[k + 1]]
+    return result
+
+
+# ---- JPEG compression without a file: imgxf_jpeg_roundtrip_u8 / imgxf_jpeg_roundtrip_list_u8 -----------------------------
+
+_RT_MAX_FRAMES = 65535               # frames per imgxf_jpeg_roundtrip_u8 / _list_u8 call (a grid dimension)
+
+
+def _qualities(quality, n: int) -> list:
+    """`quality` of a roundtrip call → one value per frame, each checked as `encode` checks its own (through `tables`, so
+    the same exceptions) and clamped to 1..100 as jpeg_set_quality clamps it.  A sequence must hold one value per frame."""
+    if isinstance(quality, (list, tuple, np.ndarray)):
+        if len(quality) != n:
+            raise ValueError(f"jpeg.roundtrip: {len(quality)} qualities for {n} frames")
+        values = list(quality)
+    else:
+        values = [quality] * n
+    for q in set(values) if all(isinstance(q, int) for q in values) else values:
+        tables(q)
+    return [min(max(int(q), 1), 100) for q in values]
+
+
+def _roundtrip_call(x: torch.Tensor, out: torch.Tensor, quality: int, hv) -> None:
+    """One quality: [N, H, W, C] device views x → out, at most _RT_MAX_FRAMES frames per C call."""
+    n, h, w, c = x.shape
+    params = F.JpegEncParams(c, hv[0], hv[1], 0)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        for lo in range(0, n, _RT_MAX_FRAMES):
+            xs, os_ = x[lo:lo + _RT_MAX_FRAMES], out[lo:lo + _RT_MAX_FRAMES]
+            nbytes = ctypes.c_size_t()
+            F.call("imgxf_jpeg_roundtrip_workspace_bytes", ctypes.byref(params), xs.shape[0], h, w, ctypes.byref(nbytes))
+            ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x.device) if nbytes.value else None
+            F.call("imgxf_jpeg_roundtrip_u8", F.vp(F.view_of(xs)), F.vp(F.view_of(os_)), ctypes.byref(params),
+                   ctypes.addressof(tables(quality)), ws.data_ptr() if ws is not None else None, nbytes.value, stream)
+
+
+def _roundtrip_view(t) -> torch.Tensor:
+    """The frames (or `out`) of a roundtrip call as a [N, H, W, C] view."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.uint8:
+        if t.dim() == 4 and t.shape[-1] in (1, 3):
+            return t
+        if t.dim() == 3:
+            return t.unsqueeze(0) if t.shape[-1] == 3 else t.unsqueeze(-1)
+    raise ValueError("jpeg.roundtrip expects a uint8 tensor [N, H, W, 3], [H, W, 3] (RGB), [N, H, W] or [N, H, W, 1] (grayscale)")
+
+
+def _span(t: torch.Tensor):
+    """[first, last + 1) byte addresses a uint8 tensor touches."""
+    lo = t.data_ptr()
+    return lo, lo + sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1
+
+
+def _dense_rows(t: torch.Tensor) -> bool:
+    """A [N, H, W, C] view the kernels read or write in place: pixels of a row consecutive, rows and frames apart."""
+    n, h, w, c = t.shape
+    return ((c == 1 or t.stride(3) == 1) and (w == 1 or t.stride(2) == c) and (h == 1 or t.stride(1) >= w * c)
+            and (n == 1 or t.stride(0) >= (t.stride(1) * h if h > 1 else w * c)))
+
+
+def roundtrip(frames: torch.Tensor, quality=75, *, subsampling=-1, out: torch.Tensor | None = None) -> torch.Tensor:
+    """JPEG compression applied to device frames without writing a file: entry i of the result is, bit for bit,
+    `np.asarray(Image.open(BytesIO(b)).convert("RGB"))` where b is what `Image.fromarray(frame_i).save(b, "JPEG",
+    quality=quality, subsampling=subsampling)` wrote — for a grayscale frame the reopened "L" image.  These are the pixels
+    of `jpeg_decode.decode(jpeg.encode(frames, ...))`, computed by one fused forward + inverse transform kernel and the
+    reader's colour stage: nothing is entropy-coded and nothing leaves the device.
+
+    frames: uint8 device tensor [N, H, W, 3] or [H, W, 3] (RGB; a 3-d tensor whose last dimension is 3 is ONE RGB frame),
+    [N, H, W] or [N, H, W, 1] (grayscale).  Views with any row and frame stride are read in place (as `encode_views` reads
+    them) while a pixel's bytes and a row's pixels are consecutive.  Returns a new contiguous tensor of the input's shape,
+    or fills and returns `out` (same shape, dtype and device, not overlapping `frames`; any row and frame stride).
+    quality: an int, or a list / tuple / array of one int per frame — frames that share a quality go through the kernels
+    together, one pair of launches per distinct quality (those frames are gathered first unless all share it); the bits are
+    those of the per-frame call.  `quality` and `subsampling` are checked as `encode` checks them, before any device work.
+    `optimize` and `progressive` are not parameters: they change the file's entropy coding, never a pixel.
+    Four-component frames are out of scope."""
+    x = _roundtrip_view(frames)
+    n, h, w, c = x.shape
+    hv = sampling(subsampling, c)
+    qs = _qualities(quality, n)
+    if not frames.is_cuda:
+        raise ValueError("jpeg.roundtrip: frames must live on the GPU (no CPU fallback)")
+    if out is None:
+        result = torch.empty(frames.shape, dtype=torch.uint8, device=frames.device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != frames.shape or out.device != frames.device:
+            raise ValueError("jpeg.roundtrip: `out` must be a uint8 tensor of the frames' shape on their device")
+        result = out
+    y = _roundtrip_view(result)
+    if n == 0 or h == 0 or w == 0:
+        return result
+    if not _dense_rows(y):
+        raise ValueError("jpeg.roundtrip: `out` must hold each row's pixels consecutively, rows and frames apart")
+    if out is not None and _span(out)[0] < _span(frames)[1] and _span(frames)[0] < _span(out)[1]:
+        raise ValueError("jpeg.roundtrip: `out` overlaps `frames`")
+    x = x if _dense_rows(x) else x.contiguous()
+    groups: dict = {}
+    for i, q in enumerate(qs):
+        groups.setdefault(q, []).append(i)
+    if len(groups) == 1:
+        _roundtrip_call(x, y, qs[0], hv)
+        return result
+    for q, idx in groups.items():
+        sel = torch.tensor(idx, dtype=torch.int64, device=x.device)
+        part = torch.empty((len(idx), h, w, c), dtype=torch.uint8, device=x.device)
+        _roundtrip_call(x.index_select(0, sel), part, q, hv)
+        y.index_copy_(0, sel, part)
+    return result
+
+
+def roundtrip_records(n: int, h: int, w: int, subsampling=-1, out_row_stride: int | None = None, out_frame_stride: int | None = None):
+    """imgxf_jpeg_roundtrip_records_host: the jpeg_decode.DecImage records `roundtrip` hands the reader's colour stage for a
+    batch of n RGB frames of h x w (a contiguous destination unless the strides are given).  Host only."""
+    from .jpeg_decode import DecImage
+    hv = sampling(subsampling, 3)
+    rs = 3 * w if out_row_stride is None else out_row_stride
+    images = (DecImage * n)()
+    F.call("imgxf_jpeg_roundtrip_records_host", ctypes.byref(F.JpegEncParams(3, hv[0], hv[1], 0)), n, h, w, rs,
+           rs * h if out_frame_stride is None else out_frame_stride, images)
+    return images
+
+
+def roundtrip_list_layout(sizes: Sequence):
+    """imgxf_jpeg_roundtrip_list_layout_host for frames of `sizes` [(h, w)] → (block: uint8 array, header:
+    F.JpegRoundtripListHeader copy, frames: structured view INTO the block (data and row_stride are the caller's to
+    fill), images: a copy of the block's jpeg_decode.DecImage records).  Host only."""
+    n = len(sizes)
+    hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
+    nb, nw, no = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    F.call("imgxf_jpeg_roundtrip_list_layout_host", hw.ctypes.data, n, None, 0, ctypes.byref(nb), ctypes.byref(nw), ctypes.byref(no))
+    block = np.zeros((nb.value,), dtype=np.uint8)
+    F.call("imgxf_jpeg_roundtrip_list_layout_host", hw.ctypes.data, n, block.ctypes.data, block.nbytes, ctypes.byref(nb), ctypes.byref(nw),
+           ctypes.byref(no))
+    hd = F.JpegRoundtripListHeader.from_buffer_copy(block[:ctypes.sizeof(F.JpegRoundtripListHeader)].tobytes())
+    frames = block[hd.frames_off:hd.frames_off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
+    from .jpeg_decode import DecImage
+    images = (DecImage * n).from_buffer_copy(block[hd.images_off:hd.images_off + n * ctypes.sizeof(DecImage)].tobytes())
+    return block, hd, frames, images
+
+
+def _roundtrip_list_call(frames: list, quality: int, out: torch.Tensor, base: int) -> list:
+    """One imgxf_jpeg_roundtrip_list_u8 call (one quality, 4:2:0): frame f's pixels at out[base + offs[f]:]; → offs."""
+    dev = frames[0].device
+    block, hd, rec, _ = roundtrip_list_layout([(t.shape[0], t.shape[1]) for t in frames])
+    kept = []                                        # (a copy made here must outlive the launch)
+    for i, t in enumerate(frames):
+        if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 3) or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+            t = t.contiguous()
+            kept.append(t)
+        rec["data"][i] = t.data_ptr()
+        rec["row_stride"][i] = t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1]
+    staged = torch.empty((block.nbytes,), dtype=torch.uint8, pin_memory=True)
+    staged.numpy()[:] = block
+    block_dev = staged.to(dev, non_blocking=True)    # the call's one host-to-device copy
+    ws = torch.empty((max(hd.workspace_bytes, 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        F.call("imgxf_jpeg_roundtrip_list_u8", block.ctypes.data, block_dev.data_ptr(), ctypes.addressof(tables(quality)),
+               out.data_ptr() + base, hd.out_bytes, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    # (staged, block_dev, ws and the copies in `kept` may go when this returns: torch's pinned-host and device allocators
+    # are stream-ordered, and everything above was enqueued on the current stream)
+    return rec["out_off"].tolist()
+
+
+def roundtrip_list(frames: Sequence[torch.Tensor], quality=75, *, subsampling=-1) -> List[torch.Tensor]:
+    """`roundtrip` for a sequence of RGB frames of DIFFERENT sizes — what `jpeg_decode.decode`, `apply_chain_list` and
+    `driver_list.apply_list` return: uint8 device tensors [H_i, W_i, 3], any row stride and byte offset (views are read in
+    place while a pixel is three consecutive bytes).  Returns one contiguous [H_i, W_i, 3] tensor per frame, each a
+    16-byte aligned view into the call's one output allocation, equal to Pillow's save-and-reopen of that frame.
+    With the default subsampling and one quality the whole list is ONE host-to-device copy (the record block) and TWO
+    kernel launches, whatever the number of frames and sizes; `quality` may be a sequence of one int per frame, which costs
+    one such pair of launches per distinct quality.  The other subsamplings have no list kernels: those frames are grouped
+    by shape (and quality) and each group goes through `roundtrip`, as `encode_list` does for its non-default files.
+    An empty list returns []."""
+    frames = list(frames)
+    for t in frames:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError("jpeg.roundtrip_list expects uint8 tensors [H, W, 3] (RGB)")
+        if t.numel() == 0:
+            raise ValueError("jpeg.roundtrip_list: a frame has no pixels")
+    hv = sampling(subsampling, 3)
+    qs = _qualities(quality, len(frames))
+    if not frames:
+        return []
+    if any(not t.is_cuda for t in frames):
+        raise ValueError("jpeg.roundtrip_list: frames must live on the GPU (no CPU fallback)")
+    if len({t.device for t in frames}) > 1:
+        raise ValueError("jpeg.roundtrip_list: the frames live on different devices")
+    dev = frames[0].device
+    slot = [(3 * t.shape[0] * t.shape[1] + 15) & ~15 for t in frames]
+    out = torch.empty((sum(slot),), dtype=torch.uint8, device=dev)
+    result: list = [None] * len(frames)
+    groups: dict = {}
+    for i, (t, q) in enumerate(zip(frames, qs)):
+        groups.setdefault((q,) if hv == (2, 2) else (q,) + tuple(t.shape), []).append(i)
+    base = 0
+    for key, members in groups.items():
+        q = key[0]
+        for lo in range(0, len(members), _RT_MAX_FRAMES):
+            idx = members[lo:lo + _RT_MAX_FRAMES]
+            if hv == (2, 2):
+                offs = _roundtrip_list_call([frames[i] for i in idx], q, out, base)
+            else:
+                h, w, _ = frames[idx[0]].shape
+                dst = out[base:base + len(idx) * slot[idx[0]]].view(len(idx), slot[idx[0]])[:, :3 * h * w].view(len(idx), h, w, 3)
+                roundtrip(torch.stack([frames[i] for i in idx]), q, subsampling=subsampling, out=dst)
+                offs = [k * slot[idx[0]] for k in range(len(idx))]
+            for i, o in zip(idx, offs):
+                h, w, _ = frames[i].shape
+                result[i] = out[base + o:base + o + 3 * h * w].view(h, w, 3)
+            base += sum(slot[i] for i in idx)
     return result

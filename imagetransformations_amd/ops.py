@@ -757,3 +757,12 @@ def dilate_cross(mask: torch.Tensor, iterations: int) -> torch.Tensor:
     out = torch.empty_like(mask, memory_format=torch.contiguous_format)
     _launch(mask, "imgxf_dilate_cross_u8", F.vp(_gray_view(mask)), F.vp(_gray_view(out)), int(iterations))
     return out
+
+
+def jpeg_compression(frames: torch.Tensor, quality=75, subsampling=-1) -> torch.Tensor:
+    """JPEG compression of a batch on the device (the ImageNet-C / CIFAR-10-C corruption): every frame as it reads back
+    from the file Pillow would save it to at `quality` (an int, or one int per frame) and `subsampling`.  The
+    batched-tensor spelling of `jpeg.roundtrip`: [N, H, W, 3], [H, W, 3] or grayscale [N, H, W] uint8 in, the same shape
+    out, bit-identical to Pillow's save and reopen."""
+    from . import jpeg
+    return jpeg.roundtrip(frames, quality, subsampling=subsampling)

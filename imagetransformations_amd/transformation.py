@@ -370,6 +370,20 @@ def save_image(img: Image.Image, path: str, **params) -> None:
         img.save(path, **params)
 
 
+def apply_jpeg_compression(image: Image.Image, quality: int = 75) -> Image.Image:
+    """An addition the reference does not have: `image` as it reads back after `image.save(path, "JPEG", quality=quality)`
+    and `Image.open(path)` — the JPEG-compression corruption of the ImageNet-C family, and what every file the reference's
+    driver saves does to its frame — computed on the device without a file (`jpeg.roundtrip`).  RGB and "L" images; the
+    result has the input's mode and size and Pillow's pixels, bit for bit."""
+    if image.mode not in ("RGB", "L"):
+        raise ValueError(f"apply_jpeg_compression takes RGB and 'L' images, not mode {image.mode!r}")
+    from . import jpeg
+    frame = _upload(image)
+    if image.mode == "L":                              # [1, H, W, 1]: a [1, H, 3] tensor would read as one RGB frame
+        return _download(jpeg.roundtrip(frame[None, :, :, None], quality)[0, :, :, 0])
+    return _download(jpeg.roundtrip(frame[None], quality)[0])
+
+
 # The batched driver on frames of different sizes (driver_list.apply_list: seven of the eight types of all sizes in at most
 # two record-driven device passes per chunk, instead of one launch per (size, type, drawn value)).  "auto": a chunk that
 # holds more than one frame size takes it, a uniform chunk keeps the grouped route; "0": never; "1": always.  The twelve-type

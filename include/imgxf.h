@@ -598,6 +598,60 @@ int imgxf_jpeg_encode_prog_u8(const imgxf_view* src, const imgxf_jpeg_enc_params
                               const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
                               uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* JPEG compression applied in place of a file: dst = the pixels of `Image.open(f).convert("RGB")` (grayscale: the "L"
+ * image) after `Image.fromarray(src).save(f, "JPEG", quality=q, subsampling=s)`, bit-identical to Pillow, for the frames
+ * and layouts of imgxf_jpeg_encode_ex_u8.  Nothing is entropy-coded: one kernel runs the writer's transform stage (colour
+ * conversion, downsampling, jfdctint, the quantiser) and, on the same registers, the reader's inverse (the quantiser
+ * steps tables->quant — what the file's DQT would state —, jidctint islow, the range limit); for colour frames the
+ * reader's colour stage (imgxf_jpeg_decode_color: fancy upsampling, jdcolor.c) then reads the component planes from the
+ * workspace.  Two launches and one small host-to-device copy (the colour stage's records); grayscale: one launch, no
+ * workspace (0 bytes, may be NULL).  params->optimize (0 / 1) is accepted and ignored — it does not change a pixel —, and
+ * only tables->quant and ac_len are read.  src and dst: same n, h, w, c == params->ncomp, any strides, not aliased.
+ * workspace: device, 16-byte aligned, >= imgxf_jpeg_roundtrip_workspace_bytes (1.5 bytes per pixel at 4:2:0, 2 at
+ * 4:2:2, 3 at 4:4:4, over MCU-padded frames, + 232 bytes per frame).  Errors: a NULL view, params, tables ->
+ * IMGXF_ERR_NULL; malformed views, different geometries, n > 65535 -> IMGXF_ERR_SHAPE; c != ncomp ->
+ * IMGXF_ERR_UNSUPPORTED; ncomp, sampling, optimize or a quantiser out of range -> IMGXF_ERR_ARG; workspace too small or
+ * misaligned -> IMGXF_ERR_WORKSPACE.  Four-component frames are out of scope.
+ * The colour stage's records (n x 232 bytes) are built in pageable host memory and sent with hipMemcpyAsync on `stream`:
+ * as the HIP API documents for pageable memory, the call returns once they are in the runtime's staging memory, which on
+ * current runtimes means the host waits until earlier work on `stream` has drained.  A caller that must not wait uses the
+ * list entry point below, whose records travel in the caller's own (pinned) block.
+ * imgxf_jpeg_roundtrip_records_host (no device work) writes those n records for a colour batch whose frame f is stored at
+ * byte f * out_frame_stride of the destination with rows of out_row_stride bytes: what imgxf_jpeg_layout_host reports
+ * for Pillow's files of such frames, planes one frame after the other.  ncomp == 1 -> IMGXF_ERR_UNSUPPORTED (a grayscale
+ * frame has no colour stage); other errors as above. */
+struct imgxf_jpeg_dec_image;
+int imgxf_jpeg_roundtrip_records_host(const imgxf_jpeg_enc_params* params, int n, int h, int w, int64_t out_row_stride,
+                                      int64_t out_frame_stride, struct imgxf_jpeg_dec_image* images);
+int imgxf_jpeg_roundtrip_workspace_bytes(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t* bytes);
+int imgxf_jpeg_roundtrip_u8(const imgxf_view* src, const imgxf_view* dst, const imgxf_jpeg_enc_params* params,
+                            const imgxf_jpeg_tables* tables, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a LIST of RGB frames of different sizes at the default sampling (4:2:0), one quality per call, in two
+ * launches whatever the list.  The HOST lays out one block
+ *     imgxf_jpeg_roundtrip_list_header | imgxf_jpeg_list_frame[n] | imgxf_jpeg_dec_image[n] | imgxf_jpeg_list_unit[n_units]
+ * which the caller completes (data, row_stride of every frame record) and copies to the device once.  Of a frame record
+ * only data, row_stride, h .. nblk and out_off / out_cap (the frame's 16-byte aligned slot of `out` and its 3 h w bytes)
+ * are used, the rest is 0; the decoder records are what imgxf_jpeg_layout_host reports for the frames' files, with the
+ * frame's planes in the workspace and out_off / out_pitch = 3 w its slot.  The unit table is the writer's transform
+ * stage's (16x256-pixel strips, item = strip | MCU row << 16). */
+typedef struct imgxf_jpeg_roundtrip_list_header {
+    int32_t  n_frames, frames_off, images_off, units_off, n_units, total_bytes;   /* byte offsets into the block; its size */
+    uint64_t workspace_bytes, out_bytes;
+} imgxf_jpeg_roundtrip_list_header;
+/* HOST half (no device work).  sizes: int32 [n][2] = (h, w).  Writes the block (block == NULL: the sizes only) and reports
+ * the block's bytes, the workspace's (the planes: 384 bytes per 16x16 MCU) and the output's.  Errors: IMGXF_ERR_NULL;
+ * IMGXF_ERR_SHAPE for n < 0 or n > 65535, h or w outside 1..32767; IMGXF_ERR_ARG for a block over 2 GiB;
+ * IMGXF_ERR_WORKSPACE when block_cap is too small. */
+int imgxf_jpeg_roundtrip_list_layout_host(const int32_t* sizes, int n, void* block, size_t block_cap, size_t* block_bytes,
+                                          size_t* workspace_bytes, size_t* out_bytes);
+/* The launches: block_host is the caller's host copy of the block, block_dev the same bytes on the device (8-byte
+ * aligned).  Frame f's pixels go to out + frames[f].out_off, rows of 3 w bytes.  Every record is checked on the host
+ * before anything is launched, as imgxf_jpeg_encode_list_u8 checks its block: a NULL data -> IMGXF_ERR_NULL; h, w or
+ * row_stride < 3 w -> IMGXF_ERR_SHAPE; a block that is not what the layout function writes for the records' (h, w) ->
+ * IMGXF_ERR_ARG; workspace or `out` too small or misaligned (16 bytes) -> IMGXF_ERR_WORKSPACE. */
+int imgxf_jpeg_roundtrip_list_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_tables* tables, uint8_t* out,
+                                 size_t out_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mask stage of apply_background_change  transformation.py:340-341 -----------------*/
 /* 256-bin histogram per frame of a c==1 view into hist[n][256] (uint32, device, zeroed by the call). */
 int imgxf_histogram_u8(const imgxf_view* src, uint32_t* hist, void* stream);

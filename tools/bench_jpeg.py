@@ -3,12 +3,77 @@ usage: python tools/bench_jpeg.py [frames] [H W] ; env KIND=photo|noise, SUBSAMP
 OPTIMIZE=1, PROGRESSIVE=1, GRAY=1 (the frames converted to "L") — Pillow runs with the same options; QUICK=1 stops before
 the threaded Pillow comparison.
 The progressive rows: PROGRESSIVE=1 with SUBSAMPLING=2 / 0 / GRAY=1, for 16 frames of 4K and 256 of 375 500.
-List mode (`jpeg.encode_list_views` against the per-shape route): python tools/bench_jpeg.py list [frames] [mixed|uniform] [a|b]"""
+List mode (`jpeg.encode_list_views` against the per-shape route): python tools/bench_jpeg.py list [frames] [mixed|uniform] [a|b]
+Round-trip mode (JPEG compression without a file against encode + decode): python tools/bench_jpeg.py roundtrip [frames]
+[mixed|uniform] [fused|compose]"""
 import io, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from imagetransformations_amd import jpeg
+
+
+def photo_frames(n, mix):
+    """n photo-like device frames: `mixed`, the ImageNet-like size mix of tools/bench_preprocess_list.py workload B, or
+    `uniform`, every frame 375 x 500.  → (sizes, frames)"""
+    dev = torch.device("cuda:0")
+    if mix == "mixed":
+        from bench_preprocess_list import mixed_sizes         # (tools/ is this script's directory)
+        sizes = mixed_sizes(n)
+    else:
+        sizes = [(375, 500)] * n
+    g = torch.Generator(device=dev); g.manual_seed(3)
+    yy = torch.arange(512, device=dev)[None, :, None, None].float()
+    xx = torch.arange(512, device=dev)[None, None, :, None].float()
+    ph = torch.arange(16, device=dev)[:, None, None, None].float()
+    ch = torch.arange(3, device=dev)[None, None, None, :].float()
+    base = 128 + 60 * torch.sin(xx / (90 + 20 * ch) + ph) + 50 * torch.cos(yy / (70 + 10 * ch) + 0.5 * ph) + 30 * ((xx // 256 + yy // 256) % 2)
+    base = (base + 6 * torch.randn((16, 512, 512, 3), device=dev, generator=g)).clamp(0, 255).to(torch.uint8)
+    return sizes, [base[i % 16, :h, :w].contiguous() for i, (h, w) in enumerate(sizes)]
+
+
+def roundtrip_mode(argv):
+    """`bench_jpeg.py roundtrip [frames] [mixed|uniform] [fused|compose]`: JPEG compression of device-resident photo-like
+    frames at quality 75, as frames per second of a host clock around calls that end in a synchronise.  fused:
+    `jpeg.roundtrip` on the uniform batch, `jpeg.roundtrip_list` on the mixed list (plus the device time between two
+    events).  compose: the route without the fused kernel, `jpeg_decode.decode(jpeg.encode(batch))` /
+    `jpeg_decode.decode(jpeg.encode_list(frames))` — the files cross to the host and back.  One route per process, so that
+    two processes (or two checkouts) can alternate; six runs after two warm-ups.  fused also checks its pixels against
+    compose and exits non-zero when they differ."""
+    from imagetransformations_amd import jpeg_decode
+    n = int(argv[0]) if argv else 1024
+    mix = argv[1] if len(argv) > 1 else "mixed"
+    route = argv[2] if len(argv) > 2 else "fused"
+    dev = torch.device("cuda:0")
+    sizes, frames = photo_frames(n, mix)
+    batch = torch.stack(frames) if mix == "uniform" else None
+    if route == "fused":
+        fn = (lambda: jpeg.roundtrip(batch)) if batch is not None else (lambda: jpeg.roundtrip_list(frames))
+    else:
+        fn = (lambda: jpeg_decode.decode(jpeg.encode(batch), dev)) if batch is not None else (lambda: jpeg_decode.decode(jpeg.encode_list(frames), dev))
+    ok = True
+    if route == "fused":
+        got = fn()
+        want = jpeg_decode.decode(jpeg.encode(batch), dev) if batch is not None else jpeg_decode.decode(jpeg.encode_list(frames), dev)
+        ok = all(torch.equal(a, b) for a, b in zip(got, want))
+        del got, want
+    fn(); fn()
+    ts, ds = [], []
+    for _ in range(6):
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter(); a.record(); out = fn(); b.record(); torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3); ds.append(a.elapsed_time(b))
+        del out
+    med = lambda v: sorted(v)[len(v) // 2 - 1] / 2 + sorted(v)[len(v) // 2] / 2
+    px = sum(h * w for h, w in sizes)
+    print(f"roundtrip mode, {mix}, {route}: {n} photo-like frames, {len(set(sizes))} distinct sizes, {px / 1e6:.1f} Mpix, quality 75"
+          + (f"; pixels equal to encode + decode: {ok}" if route == "fused" else ""))
+    print(f"  host clock, runs (ms) {' '.join(f'{t:.2f}' for t in ts)}  median {med(ts):.2f}  spread {max(ts) - min(ts):.2f}  "
+          f"{n / med(ts) * 1e3:.0f} images/s")
+    if route == "fused":
+        print(f"  device time between events (ms) {' '.join(f'{t:.2f}' for t in ds)}  median {med(ds):.2f}", flush=True)
+    return 0 if ok else 1
 
 
 def list_mode(argv):
@@ -23,20 +88,7 @@ def list_mode(argv):
     n = int(argv[0]) if argv else 1024
     mix = argv[1] if len(argv) > 1 else "mixed"
     only = argv[2] if len(argv) > 2 else None
-    dev = torch.device("cuda:0")
-    if mix == "mixed":
-        from bench_preprocess_list import mixed_sizes         # (tools/ is this script's directory)
-        sizes = mixed_sizes(n)
-    else:
-        sizes = [(375, 500)] * n
-    g = torch.Generator(device=dev); g.manual_seed(3)
-    yy = torch.arange(512, device=dev)[None, :, None, None].float()
-    xx = torch.arange(512, device=dev)[None, None, :, None].float()
-    ph = torch.arange(16, device=dev)[:, None, None, None].float()
-    ch = torch.arange(3, device=dev)[None, None, None, :].float()
-    base = 128 + 60 * torch.sin(xx / (90 + 20 * ch) + ph) + 50 * torch.cos(yy / (70 + 10 * ch) + 0.5 * ph) + 30 * ((xx // 256 + yy // 256) % 2)
-    base = (base + 6 * torch.randn((16, 512, 512, 3), device=dev, generator=g)).clamp(0, 255).to(torch.uint8)
-    frames = [base[i % 16, :h, :w].contiguous() for i, (h, w) in enumerate(sizes)]
+    sizes, frames = photo_frames(n, mix)
     groups = {}
     for i, t in enumerate(frames):
         groups.setdefault(tuple(t.shape), []).append(i)
@@ -92,6 +144,8 @@ def list_mode(argv):
 
 if len(sys.argv) > 1 and sys.argv[1] == "list":
     sys.exit(list_mode(sys.argv[2:]))
+if len(sys.argv) > 1 and sys.argv[1] == "roundtrip":
+    sys.exit(roundtrip_mode(sys.argv[2:]))
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 H, W = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (2160, 3840)
 KIND = os.environ.get("KIND", "photo")
