@@ -1,0 +1,343 @@
+// RandomResizedCrop-style crops of a LIST of RGB frames of different sizes in one launch (tensor_maps.resized_crop_list):
+// per entry k what torchvision's F.resized_crop(img, top, left, height, width, size, BILINEAR) (+ F.hflip) (+ ToTensor +
+// Normalize) gives on the PIL image — Image.crop(box).resize((Sw, Sh), BILINEAR): Pillow's horizontal pass, uint8
+// intermediate, vertical pass, 22-bit coefficients, windows clamped to the BOX — bit for bit.
+//
+// Every entry has a box of its own, so nearly every entry has coefficient tables of its own.  The HOST half
+// (imgxf_resized_crop_list_layout_host, no device work) therefore writes no table: one block of
+//   header | entry records | work units
+// with, per entry, what follows in O(1) from the box and the output size: taps per axis, output rows per unit, LDS bound.
+//
+// DEVICE half (resized_crop_list_kernel): one workgroup per work unit = up to RCL_UNIT_ROWS output rows of one entry.
+//   LDS: | bounds_x [Sw][2] | coeffs_x [Sw][ksx] | bounds_y [ny][2] | coeffs_y [ny][ksy] | mid | stage |
+//   0. a lane builds one row of a table: precompute_coeffs + normalize_coeffs_8bpc for its output column (or output row of
+//      the unit) in fp64, build_coeffs (resample_coeffs.h) restated operation by operation (rcl_build_row);
+//   1. + 2. the two passes of resample_list.h (pl_horizontal_pass, pl_vertical_taps) from those tables, on the box as the
+//      image: the source pointer is the box's first pixel, so no tap reads a pixel outside the box;
+//      (a box more than 100 times as tall as wide that loses rows: Pillow's order for it, rows first — `tall` below);
+//   3. the flip as a mirrored store column, then float32 planar stores after ToTensor + Normalize (to_tensor_math.h), 16
+//      bytes per lane where Sw % 4 == 0, or the uint8 interleaved bytes themselves.
+#include "imgxf_common.h"
+#include "resample_coeffs.h"
+#include "resample_list.h"
+#include "to_tensor_math.h"
+#include <string.h>
+
+namespace imgxf {
+
+constexpr int RCL_UNIT_ROWS = 16;         // output rows per work unit when the LDS budget allows
+constexpr int RCL_MAX_LDS = 64 * 1024;    // per workgroup, tables included: two of them fit a CU's 160 KiB
+
+// geometry of one entry as the caller states it
+struct RclGeom { int h, w, top, left, bh, bw, flip; };
+
+static inline int64_t rcl_table_bytes(int sw, int ny, int ksx, int ksy) {
+    return (4 * ((int64_t)sw * (2 + (int64_t)ksx) + (int64_t)ny * (2 + (int64_t)ksy)) + 15) & ~(int64_t)15;
+}
+// Pillow's Image.resize runs the VERTICAL pass first where the image is more than 100 times as tall as wide and loses
+// rows (its horizontal pass would otherwise filter every one of those rows): a box of that shape is a `tall` entry
+static inline int rcl_tall(int bh, int bw, int sh) { return (int64_t)bh > (int64_t)bw * 100 && sh < bh; }
+
+// LDS of a unit of `ny` output rows that touch at most `rows` source rows and `ncols` source columns.  A tall unit holds
+// its source rows and their vertical pass, both bw pixels wide, and then ny rows of the horizontal pass.
+static inline int64_t rcl_lds_bytes(int rows, int sw, int ncols, int ny, int ksx, int ksy, int tall, int bw) {
+    const int64_t fixed = rcl_table_bytes(sw, ny, ksx, ksy) + (int64_t)PL_STAGE_ROWS * pl_stage_pitch(ncols);
+    if (!tall) return fixed + (((int64_t)rows * pl_pitch(sw) + 15) & ~(int64_t)15);
+    return fixed + (((int64_t)rows * pl_pitch(bw) + 15) & ~(int64_t)15) + (((int64_t)ny * pl_pitch(bw) + 15) & ~(int64_t)15) +
+           (((int64_t)ny * pl_pitch(sw) + 15) & ~(int64_t)15);
+}
+// ... from the box and the output size alone: the bounds of resample_list.h on the rows and columns the tables can touch
+static inline int64_t rcl_unit_lds(int bh, int bw, int sh, int sw, int ny, int ksx, int ksy) {
+    return rcl_lds_bytes(pl_rows_bound(ny, bh, sh, ksy), sw, pl_rows_bound(sw, bw, sw, ksx), ny, ksx, ksy,
+                         rcl_tall(bh, bw, sh), bw);
+}
+
+// Output rows per unit: the step rule of pl_unit_rows (preprocess_list.hip) — the smallest of half, three quarters and
+// the whole budget that holds one row, and within it as many rows as fit (0: not even one row fits)
+static int rcl_unit_rows(int bh, int bw, int sh, int sw, int ksx, int ksy, int lds_budget) {
+    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
+        for (int ny = sh < RCL_UNIT_ROWS ? sh : RCL_UNIT_ROWS; ny >= 1; --ny)
+            if (rcl_unit_lds(bh, bw, sh, sw, ny, ksx, ksy) <= limit) return ny;
+    return 0;
+}
+
+// One row of precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter: build_coeffs (resample_coeffs.h) for
+// output sample xx, operation by operation in fp64 (the weights are summed in tap order; a weight is recomputed, not kept,
+// for the second loop: the same operations give the same double).  bounds: (first source index, count); kk: ksize slots.
+__device__ __forceinline__ void rcl_build_row(int in_size, int out_size, int xx, int* bounds, int* kk) {
+    double scale, filterscale;
+    filterscale = scale = (double)in_size / out_size;
+    if (filterscale < 1.0) filterscale = 1.0;
+    const double support = 1.0 * filterscale;
+    const double ss = 1.0 / filterscale;
+    const double center = 0.0 + (xx + 0.5) * scale;
+    double ww = 0.0;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    for (int x = 0; x < xmax; ++x) {
+        double a = (x + xmin - center + 0.5) * ss;
+        if (a < 0.0) a = -a;
+        const double w = a < 1.0 ? 1.0 - a : 0.0;
+        ww += w;
+    }
+    for (int x = 0; x < xmax; ++x) {
+        double a = (x + xmin - center + 0.5) * ss;
+        if (a < 0.0) a = -a;
+        double v = a < 1.0 ? 1.0 - a : 0.0;
+        if (ww != 0.0) v /= ww;
+        kk[x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
+    }
+    bounds[0] = xmin;
+    bounds[1] = xmax;
+}
+
+// F32: float32 planar [K][3][Sh][Sw] after ToTensor (+ Normalize); else uint8 interleaved [K][Sh][Sw][3].
+// VEC: Sw % 4 == 0 and `out` aligned for 16-byte (F32) / 4-byte (uint8) stores.
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(PL_THREADS) void resized_crop_list_kernel(const u8* __restrict__ block, int entries_off,
+                                                                       int units_off, int sh, int sw, int lds_bytes,
+                                                                       void* __restrict__ out, NormArgs a) {
+    extern __shared__ __attribute__((aligned(16))) u8 rcl_lds[];
+    const imgxf_resized_crop_unit u = ((const imgxf_resized_crop_unit*)(block + units_off))[blockIdx.x];
+    const imgxf_resized_crop_entry e = ((const imgxf_resized_crop_entry*)(block + entries_off))[u.entry];
+    const int tid = threadIdx.x;
+    int* bx = (int*)rcl_lds;
+    int* kx = bx + 2 * sw;
+    int* by = kx + sw * e.ksx;
+    int* ky = by + 2 * u.ny;
+    for (int i = tid; i < sw + u.ny; i += PL_THREADS) {
+        if (i < sw) rcl_build_row(e.bw, sw, i, bx + 2 * i, kx + i * e.ksx);
+        else rcl_build_row(e.bh, sh, u.y0 + (i - sw), by + 2 * (i - sw), ky + (i - sw) * e.ksy);
+    }
+    __syncthreads();
+    // source rows and columns of the box the unit touches (the bounds are monotone), laid out inside the launch's LDS
+    int r_lo = by[0], nrows = by[2 * (u.ny - 1)] + by[2 * (u.ny - 1) + 1] - r_lo;
+    const int col0 = bx[0], ncols = bx[2 * (sw - 1)] + bx[2 * (sw - 1) + 1] - col0;
+    const int pitch = ((sw + 3) >> 2) * 12;
+    const int tables = (4 * (sw * (2 + e.ksx) + u.ny * (2 + e.ksy)) + 15) & ~15;
+    const int staged = PL_STAGE_ROWS * ((ncols * 3 + 3 + 3) & ~3);
+    if (nrows < 1 || ncols < 1) return;
+    const u8* box = (const u8*)e.data + (int64_t)e.top * e.row_stride + (int64_t)e.left * 3;
+    u8* mid = rcl_lds + tables;
+    if (!e.tall) {
+        const int64_t need = tables + (((int64_t)nrows * pitch + 15) & ~(int64_t)15) + staged;
+        if (need > lds_bytes) return;                            // (the host's bounds cover the tables: never taken)
+        u8* stage = mid + ((nrows * pitch + 15) & ~15);
+        pl_horizontal_pass(box, e.row_stride, col0, ncols, r_lo, r_lo + nrows, bx, kx, e.ksx, sw, mid, pitch, stage, tid);
+    } else {
+        // Pillow's order for this shape: the vertical pass of the box's own columns first (source rows -> LDS as they
+        // are, then the shared tap loop), the horizontal pass on its result; the rows that leave it are final, which
+        // the common tail below reads through a one-tap table (coefficient 1 << 22: the byte itself)
+        const int wpitch = ((e.bw + 3) >> 2) * 12, wbytes = e.bw * 3;
+        const int64_t need = tables + (((int64_t)nrows * wpitch + 15) & ~(int64_t)15) + ((u.ny * wpitch + 15) & ~15) +
+                             ((u.ny * pitch + 15) & ~15) + staged;
+        if (need > lds_bytes) return;
+        u8* rows = rcl_lds + tables;
+        u8* vmid = rows + ((nrows * wpitch + 15) & ~15);
+        mid = vmid + ((u.ny * wpitch + 15) & ~15);
+        u8* stage = mid + ((u.ny * pitch + 15) & ~15);
+        for (int r = tid / 64; r < nrows; r += PL_THREADS / 64) {
+            const u8* g = box + (int64_t)(r_lo + r) * e.row_stride;
+            for (int b = tid & 63; b < wpitch; b += 64) rows[r * wpitch + b] = b < wbytes ? g[b] : (u8)0;
+        }
+        __syncthreads();
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
+        for (int yy = wv; yy < u.ny; yy += PL_THREADS / 64) {
+            const int cnt = by[2 * yy + 1];
+            const int ymin = min(max(by[2 * yy] - r_lo, 0), max(nrows - cnt, 0));
+            const int* k = ky + yy * e.ksy;
+            const int kv = ln < cnt ? k[ln] : 0;
+            for (int q = ln; q < (wpitch / 12); q += 64) {
+                int acc[12];
+                pl_vertical_taps(rows, wpitch, ymin, cnt, kv, k, q, acc);
+#pragma unroll
+                for (int b = 0; b < 12; ++b) vmid[yy * wpitch + q * 12 + b] = clip8(acc[b]);
+            }
+        }
+        __syncthreads();
+        for (int yy = tid; yy < u.ny; yy += PL_THREADS) {
+            by[2 * yy] = yy; by[2 * yy + 1] = 1; ky[yy * e.ksy] = 1 << PRECISION_BITS;
+        }
+        pl_horizontal_pass(vmid, wpitch, col0, ncols, 0, u.ny, bx, kx, e.ksx, sw, mid, pitch, stage, tid);
+        r_lo = 0; nrows = u.ny;
+    }
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int nq = (sw + 3) >> 2;
+    const int64_t plane = (int64_t)sh * sw;
+    for (int yy = wave; yy < u.ny; yy += PL_THREADS / 64) {
+        const int y = u.y0 + yy;
+        const int cnt = by[2 * yy + 1];
+        const int ymin = min(max(by[2 * yy] - r_lo, 0), max(nrows - cnt, 0));
+        const int* k = ky + yy * e.ksy;
+        const int kv = lane < cnt ? k[lane] : 0;
+        for (int q = lane; q < nq; q += 64) {
+            int acc[12];
+            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
+            const int npx = min(4, sw - 4 * q);
+            // store columns: pixel j of the quad is output column 4 q + j, mirrored sw - 1 - (4 q + j) under the flip
+            if (F32) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = to_tensor_value(clip8(acc[3 * j + c]), a, c);
+                    float* row = (float*)out + ((int64_t)u.entry * 3 + c) * plane + (int64_t)y * sw;
+                    if (VEC) {
+                        if (e.flip) *(float4*)(row + sw - 4 - 4 * q) = make_float4(v[3], v[2], v[1], v[0]);
+                        else *(float4*)(row + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (j < npx) row[e.flip ? sw - 1 - (4 * q + j) : 4 * q + j] = v[j];
+                    }
+                }
+            } else {
+                u8* row = (u8*)out + ((int64_t)u.entry * plane + (int64_t)y * sw) * 3;
+                if (VEC) {
+                    u32 d[3] = {0u, 0u, 0u};
+#pragma unroll
+                    for (int b = 0; b < 12; ++b) {
+                        const int j = e.flip ? 3 - b / 3 : b / 3;
+                        d[b >> 2] |= (u32)clip8(acc[3 * j + b % 3]) << (8 * (b & 3));
+                    }
+                    u32* dp = (u32*)(row + (e.flip ? sw - 4 - 4 * q : 4 * q) * 3);
+                    dp[0] = d[0]; dp[1] = d[1]; dp[2] = d[2];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (j < npx) {
+                            u8* dp = row + (e.flip ? sw - 1 - (4 * q + j) : 4 * q + j) * 3;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) dp[c] = clip8(acc[3 * j + c]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The records bound every address the kernel forms: check them against their frames, the block and the launch's LDS.
+// Host only; reads nothing outside the block the header states.
+int resized_crop_list_check(const void* block_host, size_t block_bytes) {
+    const u8* hb = (const u8*)block_host;
+    if (block_bytes < sizeof(imgxf_resized_crop_header)) return IMGXF_ERR_ARG;
+    const imgxf_resized_crop_header hd = *(const imgxf_resized_crop_header*)hb;
+    if (hd.n_entries < 0 || hd.n_units < 0 || hd.sh < 1 || hd.sh > 32767 || hd.sw < 1 || hd.sw > 32767 || hd.lds_bytes < 0 ||
+        hd.lds_bytes > RCL_MAX_LDS)
+        return IMGXF_ERR_ARG;
+    if (hd.entries_off != (int)sizeof(imgxf_resized_crop_header) ||
+        hd.units_off != hd.entries_off + (int64_t)hd.n_entries * (int64_t)sizeof(imgxf_resized_crop_entry) ||
+        hd.total_bytes < hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_resized_crop_unit) ||
+        (size_t)hd.total_bytes > block_bytes)
+        return IMGXF_ERR_ARG;
+    const imgxf_resized_crop_entry* entries = (const imgxf_resized_crop_entry*)(hb + hd.entries_off);
+    const imgxf_resized_crop_unit* units = (const imgxf_resized_crop_unit*)(hb + hd.units_off);
+    for (int i = 0; i < hd.n_entries; ++i) {
+        const imgxf_resized_crop_entry& e = entries[i];
+        if (!e.unit_rows) continue;
+        if (!e.data) return IMGXF_ERR_NULL;
+        if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.row_stride < (int64_t)e.w * 3) return IMGXF_ERR_SHAPE;
+        if (e.top < 0 || e.left < 0 || e.bh < 1 || e.bw < 1 || e.top > e.h - e.bh || e.left > e.w - e.bw) return IMGXF_ERR_SHAPE;
+        if (e.ksx != coeff_ksize(e.bw, hd.sw, IMGXF_RESAMPLE_BILINEAR) || e.ksy != coeff_ksize(e.bh, hd.sh, IMGXF_RESAMPLE_BILINEAR))
+            return IMGXF_ERR_ARG;
+        if (e.unit_rows < 0 || e.unit_rows > RCL_UNIT_ROWS || (e.flip != 0 && e.flip != 1)) return IMGXF_ERR_ARG;
+        if (e.tall != rcl_tall(e.bh, e.bw, hd.sh)) return IMGXF_ERR_ARG;
+    }
+    for (int k = 0; k < hd.n_units; ++k) {
+        const imgxf_resized_crop_unit& u = units[k];
+        if (u.entry < 0 || u.entry >= hd.n_entries || !entries[u.entry].unit_rows) return IMGXF_ERR_ARG;
+        const imgxf_resized_crop_entry& e = entries[u.entry];
+        if (u.y0 < 0 || u.ny < 1 || u.ny > e.unit_rows || u.y0 > hd.sh - u.ny || u.lds_bytes > hd.lds_bytes) return IMGXF_ERR_ARG;
+        // what the kernel can lay out: the bound on the rows and columns its own tables touch
+        if (rcl_unit_lds(e.bh, e.bw, hd.sh, hd.sw, u.ny, e.ksx, e.ksy) > u.lds_bytes) return IMGXF_ERR_ARG;
+    }
+    return IMGXF_OK;
+}
+
+} // namespace imgxf
+
+using namespace imgxf;
+
+IMGXF_API int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n, int sh, int sw, int lds_budget, void* block,
+                                                  size_t block_cap, size_t* block_bytes) {
+    if (!geometry || !block_bytes) return IMGXF_ERR_NULL;
+    if (n < 0 || sh < 1 || sh > 32767 || sw < 1 || sw > 32767 || lds_budget < 1) return IMGXF_ERR_ARG;
+    if (lds_budget > RCL_MAX_LDS) lds_budget = RCL_MAX_LDS;
+    const RclGeom* geo = (const RclGeom*)geometry;
+    size_t n_units = 0;
+    for (int i = 0; i < n; ++i) {
+        const RclGeom& g = geo[i];
+        if (g.h < 1 || g.w < 1 || g.h > 32767 || g.w > 32767 || (g.flip != 0 && g.flip != 1)) return IMGXF_ERR_ARG;
+        if (g.top < 0 || g.left < 0 || g.bh < 1 || g.bw < 1 || g.top > g.h - g.bh || g.left > g.w - g.bw)
+            return IMGXF_ERR_ARG;                                 // a box outside its frame
+        const int ur = rcl_unit_rows(g.bh, g.bw, sh, sw, coeff_ksize(g.bw, sw, IMGXF_RESAMPLE_BILINEAR),
+                                     coeff_ksize(g.bh, sh, IMGXF_RESAMPLE_BILINEAR), lds_budget);
+        if (ur) n_units += (size_t)(sh + ur - 1) / ur;
+    }
+    const size_t entries_off = sizeof(imgxf_resized_crop_header);
+    const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_resized_crop_entry);
+    const size_t total = (units_off + n_units * sizeof(imgxf_resized_crop_unit) + 15) & ~(size_t)15;
+    if (total > 0x7fffffffu) return IMGXF_ERR_SHAPE;
+    *block_bytes = total;
+    if (!block) return IMGXF_OK;                                  // the size alone
+    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
+
+    u8* out = (u8*)block;
+    memset(out, 0, total);
+    imgxf_resized_crop_header* hd = (imgxf_resized_crop_header*)out;
+    imgxf_resized_crop_entry* entries = (imgxf_resized_crop_entry*)(out + entries_off);
+    imgxf_resized_crop_unit* units = (imgxf_resized_crop_unit*)(out + units_off);
+    int lds_max = 0;
+    size_t upos = 0;
+    for (int i = 0; i < n; ++i) {
+        const RclGeom& g = geo[i];
+        imgxf_resized_crop_entry& e = entries[i];
+        e.h = g.h; e.w = g.w; e.top = g.top; e.left = g.left; e.bh = g.bh; e.bw = g.bw; e.flip = g.flip;
+        e.ksx = coeff_ksize(g.bw, sw, IMGXF_RESAMPLE_BILINEAR);
+        e.ksy = coeff_ksize(g.bh, sh, IMGXF_RESAMPLE_BILINEAR);
+        e.tall = rcl_tall(g.bh, g.bw, sh);
+        e.unit_rows = rcl_unit_rows(g.bh, g.bw, sh, sw, e.ksx, e.ksy, lds_budget);
+        if (!e.unit_rows) continue;
+        e.lds_bytes = (int32_t)rcl_unit_lds(g.bh, g.bw, sh, sw, e.unit_rows, e.ksx, e.ksy);
+        for (int y0 = 0; y0 < sh; y0 += e.unit_rows) {
+            imgxf_resized_crop_unit& u = units[upos++];
+            u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, sh - y0);
+            u.lds_bytes = (int32_t)rcl_unit_lds(g.bh, g.bw, sh, sw, u.ny, e.ksx, e.ksy);
+            lds_max = std::max(lds_max, u.lds_bytes);
+        }
+    }
+    hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->sh = sh; hd->sw = sw; hd->lds_bytes = lds_max;
+    hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->total_bytes = (int32_t)total;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_resized_crop_list(const void* block_host, size_t block_bytes, const void* block_dev, void* out,
+                                      int out_u8, const float* mean, const float* std, void* stream) {
+    if (!block_host) return IMGXF_ERR_NULL;
+    if ((mean == nullptr) != (std == nullptr)) return IMGXF_ERR_NULL;
+    if (out_u8 != 0 && out_u8 != 1) return IMGXF_ERR_ARG;
+    if (out_u8 && mean) return IMGXF_ERR_ARG;
+    const int rc = resized_crop_list_check(block_host, block_bytes);
+    if (rc != IMGXF_OK) return rc;
+    const imgxf_resized_crop_header hd = *(const imgxf_resized_crop_header*)block_host;
+    if (hd.n_units == 0) return IMGXF_OK;
+    if (!block_dev || !out) return IMGXF_ERR_NULL;
+    if ((!out_u8 && (((uintptr_t)out) & 3)) || ((uintptr_t)block_dev) & 7) return IMGXF_ERR_ARG;
+    const NormArgs a = make_norm_args(mean, std, 3);
+    const bool vec = (hd.sw & 3) == 0 && (((uintptr_t)out) & (out_u8 ? 3 : 15)) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    const u8* db = (const u8*)block_dev;
+    const dim3 grid((unsigned)hd.n_units), threads(PL_THREADS);
+#define RCL_LAUNCH(F32, VEC)                                                                                              \
+    hipLaunchKernelGGL((resized_crop_list_kernel<F32, VEC>), grid, threads, (size_t)hd.lds_bytes, st, db, hd.entries_off,  \
+                       hd.units_off, hd.sh, hd.sw, hd.lds_bytes, out, a)
+    if (out_u8) { if (vec) RCL_LAUNCH(false, true); else RCL_LAUNCH(false, false); }
+    else { if (vec) RCL_LAUNCH(true, true); else RCL_LAUNCH(true, false); }
+#undef RCL_LAUNCH
+    return launch_status();
+}

@@ -244,3 +244,242 @@ def _launch_list(block, gpu, out, mean, std, device) -> None:
         F.call("imgxf_preprocess_list_f32", block.ctypes.data, gpu.data_ptr(), out.data_ptr(),
                F.f32_array(mean) if mean is not None else None, F.f32_array(std) if std is not None else None,
                torch.cuda.current_stream(device).cuda_stream)
+
+
+# One workgroup of resized_crop_list's kernel keeps in LDS what preprocess_list's does — the horizontally filtered source
+# rows its output rows touch (uint8, 12 * ceil(Sw / 4) bytes each) and four staged source-row spans — and, before them,
+# the coefficient tables it computes itself: (first, count) + ksx 22-bit coefficients for each of the Sw output columns,
+# the same with ksy for each of its output rows.  The host knows no table, so it budgets with the bounds of the rows and
+# columns a table can touch.  An entry is taken by the kernel when ONE output row fits:
+#     r16(4 * (Sw * (2 + ksx) + 2 + ksy)) + r16(min(bh, ksy) * 12 * ceil(Sw / 4))
+#         + 4 * ((3 * min(bw, ceil((Sw - 1) * bw / Sw) + ksx) + 6) & ~3) <= RESIZED_CROP_LIST_LDS_BYTES
+# with ks = 2 * ceil(max(box / out, 1)) + 1 taps per axis and r16 rounding up to 16.  A box more than 100 times as tall as
+# wide that loses rows is filtered rows first, as Image.resize does for that shape; its second term is
+#     r16(min(bh, ksy) * 12 * ceil(bw / 4)) + r16(12 * ceil(bw / 4)) + r16(12 * ceil(Sw / 4)).
+# The column tables and the staged spans grow together with the box, so with equal scales on both axes that holds up to a
+# 10-fold reduction at Sw = 224 (21 taps, a 2240 x 2240 box), 5-fold at Sw = 384, 4-fold at Sw = 512, 77-fold at Sw = 32.
+# An entry beyond it goes through `ops.resize_crop` + `to_tensor` in its place (the host layout marks it: unit_rows == 0)
+# and `taken` reports it.
+RESIZED_CROP_LIST_LDS_BYTES = 64 * 1024
+
+_RCL_HEADER = np.dtype([(k, "<i4") for k in ("n_entries", "n_units", "sh", "sw", "lds_bytes", "entries_off", "units_off",
+                                             "total_bytes")])
+_RCL_ENTRY = np.dtype([("data", "<u8"), ("row_stride", "<i8")] + [(k, "<i4") for k in (
+    "h", "w", "top", "left", "bh", "bw", "flip", "ksx", "ksy", "unit_rows", "lds_bytes", "tall")])
+_RCL_UNIT = np.dtype([(k, "<i4") for k in ("entry", "y0", "ny", "lds_bytes")])     # structs imgxf_resized_crop_* (imgxf.h)
+
+
+def resized_crop_layout(geometry: np.ndarray, size, pinned: bool = False):
+    """The host block of `resized_crop_list` (imgxf_resized_crop_list_layout_host) for int32 [K, 7] geometry rows
+    (h, w, top, left, box height, box width, flip) and the output size (Sh, Sw), as a uint8 array.  `pinned=True`:
+    (array, the pinned uint8 tensor that owns its memory) instead.  No device is touched."""
+    geometry = np.ascontiguousarray(geometry, np.int32)
+    sh, sw = size
+    need = ctypes.c_size_t(0)
+    gp = geometry.ctypes.data if geometry.size else (ctypes.c_int32 * 1)()
+    F.call("imgxf_resized_crop_list_layout_host", gp, len(geometry), sh, sw, RESIZED_CROP_LIST_LDS_BYTES, None, 0,
+           ctypes.byref(need))
+    owner = torch.empty(need.value, dtype=torch.uint8, pin_memory=True) if pinned else None
+    block = owner.numpy() if pinned else np.empty(need.value, np.uint8)
+    F.call("imgxf_resized_crop_list_layout_host", gp, len(geometry), sh, sw, RESIZED_CROP_LIST_LDS_BYTES,
+           block.ctypes.data, block.nbytes, ctypes.byref(need))
+    return (block, owner) if pinned else block
+
+
+def resized_crop_block_views(block: np.ndarray):
+    """(header, entry records, work units) of a `resized_crop_layout` block as structured views into it."""
+    hd = block[:_RCL_HEADER.itemsize].view(_RCL_HEADER)[0]
+    eo, uo, n, nu = int(hd["entries_off"]), int(hd["units_off"]), int(hd["n_entries"]), int(hd["n_units"])
+    return (hd, block[eo:eo + n * _RCL_ENTRY.itemsize].view(_RCL_ENTRY), block[uo:uo + nu * _RCL_UNIT.itemsize].view(_RCL_UNIT))
+
+
+def _crop_size(size):
+    """(Sh, Sw) as RandomResizedCrop reads `size`: an int is both, a pair is (height, width)."""
+    if isinstance(size, (int, np.integer)) and not isinstance(size, bool):
+        pair = (int(size), int(size))
+    else:
+        try:
+            pair = tuple(size)
+        except TypeError:
+            raise ValueError(f"size must be an int or a pair of ints, got {size!r}") from None
+        if len(pair) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in pair):
+            raise ValueError(f"size must be an int or a pair of ints, got {size!r}")
+        pair = (int(pair[0]), int(pair[1]))
+    if not all(1 <= v <= 32767 for v in pair):
+        raise ValueError(f"size values must lie in 1 .. 32767, got {pair}")
+    return pair
+
+
+def _int_array(values, name: str, width=None) -> np.ndarray:
+    """`values` (tensor, array or nested sequence of integers) as an int64 array of shape [K] or [K, width]."""
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    a = np.asarray(values)
+    if a.size == 0:
+        a = a.astype(np.int64).reshape((0,) if width is None else (0, width))
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold integers, got dtype {a.dtype}")
+    if a.ndim != (1 if width is None else 2) or (width is not None and a.shape[1] != width):
+        raise ValueError(f"{name} must have shape {'[K]' if width is None else f'[K, {width}]'}, got {a.shape}")
+    return a.astype(np.int64)
+
+
+def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, std=None, dtype=torch.float32, out=None,
+                      taken=None) -> torch.Tensor:
+    """torchvision's `F.resized_crop(img, top, left, height, width, size, BILINEAR)`, then `F.hflip` where `flips[k]`,
+    then `ToTensor()` (+ `Normalize(mean, std)`) for K entries over a sequence of uint8 RGB device frames [H_i, W_i, 3] of
+    any sizes, each entry with a box of its own — `RandomResizedCrop` + `RandomHorizontalFlip` with the draws of
+    `random_resized_crop_params`, or several fixed crops per image — in ONE kernel launch and one host-to-device copy:
+    float32 [K, 3, Sh, Sw], entry k bit for bit what Pillow gives for
+    `Image.fromarray(frame).crop((left, top, left + width, top + height)).resize((Sw, Sh), Image.BILINEAR)`
+    (+ `transpose(FLIP_LEFT_RIGHT)`) followed by `to_tensor`.  No tap reads a pixel outside the box.  (That includes
+    Pillow's order of passes: rows before columns where a box is more than 100 times as tall as wide and loses rows.)
+
+    `boxes`: integer [K, 4] rows (top, left, height, width) inside their frames (torchvision pads elsewhere: not done
+    here).  `size`: an int S for (S, S) or a pair (Sh, Sw).  `index`: optional integer [K], entry k reads
+    `frames[index[k]]` (default: entry k reads frame k); one frame may serve many entries.  `dtype=torch.uint8`: the
+    bytes before ToTensor, [K, Sh, Sw, 3].  `out`: optional contiguous destination of that shape and dtype, returned when
+    given.  `taken`: optional list, filled with K bools — False where the entry exceeded RESIZED_CROP_LIST_LDS_BYTES and
+    went through `ops.resize_crop` instead; the others still share the one launch.
+
+    Frames may have any row stride and byte offset (columns and channels dense) and must share one device.  The host
+    sends one small record per entry and no coefficient table: the kernel computes the tables itself, so no resample
+    plan is created or kept, whatever the number of distinct boxes."""
+    frames = list(frames)
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std come together")
+    if mean is not None and (len(mean) != 3 or len(std) != 3):
+        raise ValueError("mean / std need 3 entries")
+    if dtype not in (torch.float32, torch.uint8):
+        raise ValueError("dtype must be torch.float32 or torch.uint8")
+    if dtype == torch.uint8 and mean is not None:
+        raise ValueError("mean / std need dtype=torch.float32 (uint8 output is not normalised)")
+    sh, sw = _crop_size(size)
+    for t in frames:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+            raise TypeError("resized_crop_list expects uint8 tensors on the HIP device")
+    for t in frames:                                             # the layouts the kernel reads, as `preprocess_list` states them
+        shape, stride = t.shape, t.stride()
+        if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"resized_crop_list expects RGB [H,W,3] frames with H, W > 0, got {tuple(shape)}")
+        if shape[0] > 32767 or shape[1] > 32767:
+            raise ValueError(f"resized_crop_list takes frames up to 32767 x 32767 (as every imgxf view), got {tuple(shape)}")
+        if stride[2] != 1 or (shape[1] > 1 and stride[1] != 3) or (shape[0] > 1 and stride[0] < 3 * shape[1]):
+            raise ValueError("pixels of a row and their channels must be contiguous (interleaved HWC layout)")
+        if t.device != frames[0].device:
+            raise ValueError("resized_crop_list expects all frames on one device")
+    boxes = _int_array(boxes, "boxes", 4)
+    k = len(boxes)
+    index = np.arange(len(frames), dtype=np.int64) if index is None else _int_array(index, "index")
+    if len(index) != k:
+        raise ValueError(f"boxes has {k} rows for {len(index)} entries (one per frame where no index is given)")
+    if flips is None:
+        flips = np.zeros(k, bool)
+    else:
+        flips = flips.detach().cpu().numpy() if isinstance(flips, torch.Tensor) else np.asarray(flips)
+        if flips.size == 0:
+            flips = flips.astype(bool).reshape(0)
+        if flips.dtype != np.bool_ or flips.ndim != 1:
+            raise ValueError(f"flips must be a bool [K] array, got {flips.dtype} {flips.shape}")
+        if len(flips) != k:
+            raise ValueError(f"flips has {len(flips)} entries for {k} boxes")
+    if k and (index.min() < 0 or index.max() >= len(frames)):
+        raise ValueError(f"index values must lie in 0 .. {len(frames) - 1}")
+    hw = np.array([(t.shape[0], t.shape[1]) for t in frames], np.int64).reshape(-1, 2)[index]
+    top, left, bh, bw = boxes.T if k else (np.zeros(0, np.int64),) * 4
+    bad = (bh < 1) | (bw < 1) | (top < 0) | (left < 0) | (top > hw[:, 0] - bh) | (left > hw[:, 1] - bw)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"box {tuple(boxes[i].tolist())} (top, left, height, width) of entry {i} is empty or not inside its "
+                         f"{int(hw[i, 0])} x {int(hw[i, 1])} frame (torchvision pads there; not done here)")
+    device = frames[0].device if frames else torch.device("cuda", torch.cuda.current_device())
+    shape = (k, 3, sh, sw) if dtype == torch.float32 else (k, sh, sw, 3)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != device or tuple(out.shape) != shape
+                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous {dtype} {list(shape)} tensor on {device}")
+    else:
+        out = torch.empty(shape, dtype=dtype, device=device)
+    if k == 0:
+        if taken is not None:
+            taken[:] = []
+        return out
+    geometry = np.empty((k, 7), np.int32)
+    geometry[:, :2], geometry[:, 2:6], geometry[:, 6] = hw, boxes, flips
+    block, staged = resized_crop_layout(geometry, (sh, sw), pinned=True)
+    hd, rec, _ = resized_crop_block_views(block)
+    ptr = np.array([t.data_ptr() for t in frames], np.uint64)
+    stride = np.array([t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1] for t in frames], np.int64)
+    rec["data"], rec["row_stride"] = ptr[index], stride[index]
+    if hd["n_units"]:
+        with torch.cuda.device(device):
+            gpu = staged.to(device, non_blocking=True)
+            F.call("imgxf_resized_crop_list", block.ctypes.data, block.nbytes, gpu.data_ptr(), out.data_ptr(),
+                   1 if dtype == torch.uint8 else 0, F.f32_array(mean) if mean is not None else None,
+                   F.f32_array(std) if std is not None else None, torch.cuda.current_stream(device).cuda_stream)
+    served = rec["unit_rows"] > 0
+    for i in np.flatnonzero(~served):
+        out[i].copy_(_resized_crop_entry(frames[index[i]], boxes[i], (sh, sw), bool(flips[i]), mean, std, dtype))
+    if taken is not None:
+        taken[:] = served.tolist()
+    return out
+
+
+def _resized_crop_entry(frame, box, size, flip: bool, mean, std, dtype):
+    """One entry of `resized_crop_list` by the calls that predate it: the resample plan of the box's own size (or a plain
+    crop where the box already has the output's size, as `preprocess` does), `to_tensor`, the flip."""
+    from . import ops
+    top, left, bh, bw = (int(v) for v in box)
+    sh, sw = size
+    view = frame[top:top + bh, left:left + bw]
+    if (bh, bw) == (sh, sw):
+        t = ops.crop(view[None], (0, 0, sw, sh))
+    elif bh > 100 * bw and sh < bh:                              # Image.resize filters such a shape rows first
+        t = ops.resize(ops.resize(view[None], (bw, sh), ops.RESAMPLE_BILINEAR), (sw, sh), ops.RESAMPLE_BILINEAR)
+    else:
+        t = ops.resize_crop(view[None], (sw, sh), (0, 0, sw, sh), ops.RESAMPLE_BILINEAR)
+    if dtype == torch.uint8:
+        return t[0].flip(1) if flip else t[0]
+    t = to_tensor(t, mean, std)[0]
+    return t.flip(2) if flip else t
+
+
+def random_resized_crop_params(sizes, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5):
+    """The draws of `transforms.Compose([RandomResizedCrop(size, scale, ratio), RandomHorizontalFlip(flip_p)])` for images
+    of the given (h, w) sizes, image by image from torch's default CPU generator exactly as that Compose consumes it:
+    (boxes int64 [N, 4] rows (top, left, height, width), flips bool [N]) for `resized_crop_list`.  `flip_p=None`: no
+    flip is drawn (the Compose without RandomHorizontalFlip) and flips is all False."""
+    import math
+    sizes = list(sizes)
+    boxes = torch.empty((len(sizes), 4), dtype=torch.int64)
+    flips = torch.zeros(len(sizes), dtype=torch.bool)
+    log_ratio = torch.log(torch.tensor(ratio))
+    for n, (h, w) in enumerate(sizes):
+        # torchvision.transforms.RandomResizedCrop.get_params, restated: up to ten draws of (area, aspect ratio), the
+        # first whose crop fits gets a uniform position; otherwise the central crop closest to the ratio range
+        h, w = int(h), int(w)
+        area = h * w
+        for _ in range(10):
+            target = area * torch.empty(1).uniform_(scale[0], scale[1]).item()
+            ar = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1])).item()
+            cw = int(round(math.sqrt(target * ar)))
+            ch = int(round(math.sqrt(target / ar)))
+            if 0 < cw <= w and 0 < ch <= h:
+                top = torch.randint(0, h - ch + 1, size=(1,)).item()
+                left = torch.randint(0, w - cw + 1, size=(1,)).item()
+                break
+        else:
+            in_ratio = float(w) / float(h)
+            if in_ratio < min(ratio):
+                cw = w
+                ch = int(round(cw / min(ratio)))
+            elif in_ratio > max(ratio):
+                ch = h
+                cw = int(round(ch * max(ratio)))
+            else:
+                cw, ch = w, h
+            top, left = (h - ch) // 2, (w - cw) // 2
+        boxes[n] = torch.tensor((top, left, ch, cw))
+        if flip_p is not None:                                   # RandomHorizontalFlip.forward: torch.rand(1) < p
+            flips[n] = bool(torch.rand(1) < flip_p)
+    return boxes, flips

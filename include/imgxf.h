@@ -932,6 +932,55 @@ int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, int crop, 
 int imgxf_preprocess_list_f32(const void* block_host, const void* block_dev, float* out, const float* mean,
                               const float* std, void* stream);
 
+/* ---- per-entry resized crops (RandomResizedCrop, TTA crops) of a LIST of frames of different sizes -------------------
+ * Entry k is torchvision's F.resized_crop(img, top, left, height, width, (sh, sw), BILINEAR), then F.hflip where its flip
+ * flag is set, on the PIL image — Image.crop(box).resize((sw, sh), BILINEAR): coefficient windows clamped to the box —
+ * and then either ToTensor() + Normalize(mean, std) (float32 planar) or the uint8 bytes themselves, all entries in ONE
+ * launch.  Image.resize filters rows before columns where the box is more than 100 times as tall as wide and loses rows;
+ * so does the kernel (imgxf_resized_crop_entry.tall).  Several entries may read one frame.  The HOST lays out one block
+ *     imgxf_resized_crop_header | imgxf_resized_crop_entry[n] | imgxf_resized_crop_unit[n_units]
+ * which the caller copies to the device once.  It holds NO coefficient table: every workgroup computes the
+ * precompute_coeffs + normalize_coeffs_8bpc tables of its own unit in fp64 into LDS. */
+typedef struct imgxf_resized_crop_header {
+    int32_t n_entries, n_units, sh, sw;
+    int32_t lds_bytes;          /* the largest unit's LDS bound = the launch's dynamic LDS size */
+    int32_t entries_off, units_off, total_bytes;   /* byte offsets of the sections, size of the block */
+} imgxf_resized_crop_header;
+typedef struct imgxf_resized_crop_entry {
+    uint64_t data;              /* DEVICE address of pixel (0, 0) of the FRAME; filled by the caller, as is row_stride
+                                   (bytes, >= 3 w) */
+    int64_t  row_stride;
+    int32_t  h, w;              /* the frame */
+    int32_t  top, left, bh, bw; /* the box, inside the frame */
+    int32_t  flip;              /* 1: output column x is stored at sw - 1 - x */
+    int32_t  ksx, ksy;          /* taps per output column / row: 2 ceil(max(bw / sw, 1)) + 1, likewise for rows */
+    int32_t  unit_rows;         /* output rows per work unit; 0: the entry exceeds the LDS budget and has no units */
+    int32_t  lds_bytes;         /* LDS bound of a unit of unit_rows rows */
+    int32_t  tall;              /* 1 where bh > 100 bw and sh < bh: Image.resize then runs its vertical pass first */
+} imgxf_resized_crop_entry;
+typedef struct imgxf_resized_crop_unit {
+    int32_t entry, y0, ny;      /* one workgroup: output rows [y0, y0 + ny) of entry `entry` */
+    int32_t lds_bytes;          /* tables 4 (sw (2 + ksx) + ny (2 + ksy)) (rounded up to 16) + R x 12 ceil(sw / 4) (rounded up
+                                   to 16) + 4 staged spans of C source columns, (3 C + 6) & ~3 bytes each, with the bounds
+                                   R = min(bh, ceil((ny - 1) bh / sh) + ksy), C = min(bw, ceil((sw - 1) bw / sw) + ksx);
+                                   a tall entry: R x 12 ceil(bw / 4) in place of the second term, plus ny x 12 ceil(bw / 4)
+                                   and ny x 12 ceil(sw / 4), each rounded up to 16 */
+} imgxf_resized_crop_unit;
+/* HOST half (no device work).  geometry: int32 [n][7] = (h, w, top, left, bh, bw, flip) per entry.  A unit takes up to 16
+ * output rows, fewer where its LDS bound would not fit half of lds_budget bytes (three quarters, then the whole of it,
+ * where not even one row fits the smaller step; lds_budget is capped at 64 KiB); an entry of which not even one row fits
+ * gets unit_rows = 0.  *block_bytes receives the block's size; block == NULL: only that.
+ * Errors: IMGXF_ERR_NULL; IMGXF_ERR_ARG for n < 0, sh or sw outside 1..32767, lds_budget < 1, h or w outside 1..32767, a
+ * box that is empty or not inside its frame, a flip other than 0 / 1; IMGXF_ERR_WORKSPACE when block_cap is too small. */
+int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n, int sh, int sw, int lds_budget, void* block,
+                                        size_t block_cap, size_t* block_bytes);
+/* The launch: block_host is the caller's host copy of the block, block_bytes its size (every record is checked against its
+ * frame, the block and the launch's LDS before the launch; nothing past block_bytes is read), block_dev the same bytes on
+ * the device (8-byte aligned).  out_u8 == 0: out is float32 [n][3][sh][sw]; mean / std HOST float[3], both or neither.
+ * out_u8 == 1: out is uint8 [n][sh][sw][3]; mean / std must be NULL.  Slots of entries without units are not written. */
+int imgxf_resized_crop_list(const void* block_host, size_t block_bytes, const void* block_dev, void* out, int out_u8,
+                            const float* mean, const float* std, void* stream);
+
 /* ---- the transformations of apply_all_transformations on a LIST of entries over frames of different sizes -------------
  * The driver's eight types and the later driver's flip, crop + resize and perspective warp, each entry with its own
  * frame, type and drawn value, bit for bit what the per-type entry points give: one block

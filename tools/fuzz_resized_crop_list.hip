@@ -1,0 +1,109 @@
+// Stand-alone CPU program for the HOST code of tensor_maps.resized_crop_list (csrc/resized_crop_list.hip): lays out blocks
+// for seeded random and hostile geometry (boxes past their frames, empty and negative extents, sizes at and past the
+// limits, tiny budgets), checks every accepted block with the launcher's own record checks, then feeds those checks
+// mutated and truncated blocks.  Meant for a sanitizer build of the host side; it never touches a device:
+//     hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//         -Iinclude -Iimagetransformations_amd/csrc tools/fuzz_resized_crop_list.hip -o _exp/fuzz_resized_crop_list
+//     ASAN_OPTIONS=detect_leaks=0 _exp/fuzz_resized_crop_list [rounds] [seed]
+// Exit status 0: every valid block passed, every hostile geometry was refused, no mutated block made the checks read
+// outside the block (the sanitizer aborts otherwise).
+#include "../imagetransformations_amd/csrc/resized_crop_list.hip"
+#include <random>
+#include <vector>
+
+int main(int argc, char** argv) {
+    const int rounds = argc > 1 ? atoi(argv[1]) : 200;
+    std::mt19937 rng(argc > 2 ? (unsigned)atoi(argv[2]) : 1u);
+    auto uni = [&](int lo, int hi) { return (int)(lo + rng() % (unsigned)(hi - lo + 1)); };
+    long laid = 0, accepted = 0, hostile = 0, refused = 0, mutated = 0, rejected = 0, entries = 0, beyond = 0, tall = 0;
+    for (int round = 0; round < rounds; ++round) {
+        const int n = uni(0, 300);
+        const int sh = uni(0, 3) ? uni(1, 300) : uni(1, 5), sw = uni(0, 3) ? uni(1, 300) : uni(1, 5);
+        const int budget = uni(0, 3) ? 65536 : uni(1, 70000);
+        std::vector<int32_t> geo((size_t)n * 7);
+        for (int i = 0; i < n; ++i) {
+            int32_t* g = &geo[(size_t)i * 7];
+            const int kind = uni(0, 5);
+            g[0] = kind == 0 ? uni(1, 8) : kind == 1 ? uni(1, 32767) : uni(1, 700);
+            g[1] = kind == 1 ? uni(1, 8) : kind == 0 ? uni(1, 32767) : uni(1, 700);
+            g[4] = uni(1, g[0]); g[5] = uni(1, g[1]);
+            g[2] = uni(0, g[0] - g[4]); g[3] = uni(0, g[1] - g[5]);
+            g[6] = uni(0, 1);
+        }
+        size_t need = 0, need2 = 0;
+        int rc = imgxf_resized_crop_list_layout_host(geo.data(), n, sh, sw, budget, nullptr, 0, &need);
+        if (rc != IMGXF_OK) { fprintf(stderr, "size pass: %d\n", rc); return 2; }
+        std::vector<u8> block(need);                          // exactly the stated size: one byte past it is the sanitizer's
+        rc = imgxf_resized_crop_list_layout_host(geo.data(), n, sh, sw, budget, block.data(), block.size(), &need2);
+        if (rc != IMGXF_OK || need2 != need) { fprintf(stderr, "layout: %d (%zu, %zu)\n", rc, need, need2); return 2; }
+        if (need && imgxf_resized_crop_list_layout_host(geo.data(), n, sh, sw, budget, block.data(), need - 1, &need2) != IMGXF_ERR_WORKSPACE) {
+            fprintf(stderr, "a short block was not refused\n");
+            return 2;
+        }
+        ++laid;
+        imgxf_resized_crop_header* hd = (imgxf_resized_crop_header*)block.data();
+        imgxf_resized_crop_entry* ent = (imgxf_resized_crop_entry*)(block.data() + hd->entries_off);
+        for (int i = 0; i < n; ++i) {                         // what the caller fills in
+            ent[i].data = 4096; ent[i].row_stride = (int64_t)ent[i].w * 3 + (uni(0, 1) ? 0 : uni(0, 40));
+            beyond += ent[i].unit_rows == 0; tall += ent[i].tall;
+        }
+        entries += n;
+        if (hd->lds_bytes > (budget < 65536 ? budget : 65536)) { fprintf(stderr, "LDS %d above the budget %d\n", hd->lds_bytes, budget); return 2; }
+        rc = imgxf::resized_crop_list_check(block.data(), block.size());
+        if (rc != IMGXF_OK) { fprintf(stderr, "a valid block was rejected: %d (round %d)\n", rc, round); return 2; }
+        ++accepted;
+        // the launcher with a valid block and no device block: it must stop at its own NULL check, before any launch
+        rc = imgxf_resized_crop_list(block.data(), block.size(), nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+        if (rc != (hd->n_units ? IMGXF_ERR_NULL : IMGXF_OK)) { fprintf(stderr, "launcher: %d\n", rc); return 2; }
+
+        for (int m = 0; m < 40 && n; ++m) {                   // hostile geometry: every one must be refused by the layout
+            std::vector<int32_t> bad = geo;
+            int32_t* g = &bad[(size_t)uni(0, n - 1) * 7];
+            switch (uni(0, 7)) {
+                case 0: g[2] = g[0] - g[4] + uni(1, 5); break;               // the box past the bottom
+                case 1: g[3] = g[1] - g[5] + uni(1, 5); break;               // past the right edge
+                case 2: g[uni(2, 3)] = -uni(1, 9); break;
+                case 3: g[uni(4, 5)] = -uni(0, 9); break;                    // empty or negative extent
+                case 4: g[uni(2, 5)] = uni(0, 1) ? INT32_MAX : INT32_MIN; break;
+                case 5: g[uni(0, 1)] = uni(0, 1) ? 0 : 32768 + uni(0, 9); break;
+                case 6: g[6] = uni(0, 1) ? 2 : -1; break;
+                default: g[4] = g[0] + 1; g[2] = 0; break;
+            }
+            ++hostile;
+            refused += imgxf_resized_crop_list_layout_host(bad.data(), n, sh, sw, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+        }
+        const int bad_sizes[] = {0, -1, 32768, INT32_MAX, INT32_MIN};
+        for (int v : bad_sizes) {
+            hostile += 2;
+            refused += imgxf_resized_crop_list_layout_host(geo.data(), n, v, sw, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+            refused += imgxf_resized_crop_list_layout_host(geo.data(), n, sh, v, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+        }
+
+        const std::vector<u8> good = block;
+        for (int m = 0; m < 300; ++m) {                       // mutated blocks through the launcher's checks
+            block = good;
+            size_t bytes = block.size();
+            const int kind = uni(0, 5);
+            if (kind == 0) {                                  // a header word
+                ((int32_t*)block.data())[uni(0, 7)] = uni(0, 1) ? uni(-2, 1 << 30) : uni(-2, 600);
+            } else if (kind <= 3 && need > sizeof(imgxf_resized_crop_header)) {   // a 32-bit field of the records and units
+                int32_t* wd = (int32_t*)(block.data() + sizeof(imgxf_resized_crop_header));
+                const int nw = (int)((need - sizeof(imgxf_resized_crop_header)) / 4);
+                const int v[] = {0, -1, 1, 15, 16, 17, 1 << 30, INT32_MIN, INT32_MAX, uni(-5, 70000), 32767, 32768};
+                wd[uni(0, nw - 1)] = v[uni(0, 11)];
+            } else if (kind == 4) {                           // a truncated block
+                bytes = (size_t)uni(0, (int)bytes);
+                block.resize(bytes);
+                block.shrink_to_fit();
+            } else {                                          // more entries or units than the block holds
+                imgxf_resized_crop_header* h2 = (imgxf_resized_crop_header*)block.data();
+                (uni(0, 1) ? h2->n_units : h2->n_entries) += uni(1, 1 << 20);
+            }
+            ++mutated;
+            rejected += imgxf::resized_crop_list_check(block.data(), bytes) != IMGXF_OK;
+        }
+    }
+    printf("%ld layouts (%ld entries, %ld beyond the budget, %ld tall), %ld valid blocks accepted, %ld of %ld hostile geometries "
+           "refused, %ld of %ld mutated blocks rejected\n", laid, entries, beyond, tall, accepted, refused, hostile, rejected, mutated);
+    return refused == hostile ? 0 : 3;
+}
