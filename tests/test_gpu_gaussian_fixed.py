@@ -1,6 +1,8 @@
 """GPU: the opt-in fixed-point Gaussian (OpenCV's uint8 evaluation order, restated — parity
 unpinned, see oracle.gaussian_blur_cv_fixed) through the C-ABI against the oracle, bit for bit,
-on every kernel family behind it (marching, 4-byte marching, LDS-tiled)."""
+on every kernel family behind it for RGB frames (marching, 4-byte marching, matrix cores, LDS-tiled).  The gray and RGBA
+shapes here reach a few radii of each family; tests/test_gpu_sepconv_channels.py takes those channel counts through
+every radius of every family, and tests/test_sepconv_route.py checks that the two grids together miss none."""
 import numpy as np
 import pytest
 import torch

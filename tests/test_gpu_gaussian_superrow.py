@@ -1,8 +1,9 @@
 """Super-row strips of the marching Gaussian (csrc/sepconv_march.inc): the same row of G frames is
 cut into 1 KiB strips as one run, so frame seams fall inside waves.  Batches whose size is not
-a multiple of G, strided frame views, the fp32 side output, the fixed-point instances and all
-channel counts must equal the per-frame oracle (cv2.GaussianBlur, float definition:
-/root/reference/transformation.py:249)."""
+a multiple of G, strided frame views, the fp32 side output, the RGB fixed-point instances and, at
+k = 5 and 7, all channel counts must equal the per-frame oracle (cv2.GaussianBlur, float definition:
+/root/reference/transformation.py:249).  Gray and RGBA batches at the other radii, in fixed point
+and through views: tests/test_gpu_sepconv_channels.py."""
 import numpy as np
 import pytest
 import torch
