@@ -23,10 +23,10 @@
 //   driver_list_persp_kernel: a band of 16 output rows, walked in 64-pixel tiles with the tile body of perspective_kernel
 //     (perspective_tile.h): staged source box in LDS for interior and border tiles, global gather where the box does not
 //     fit.  Its fixed 35 KiB of LDS stay in this launch.
-//   driver_list_scale_kernel: horizontal pass of the touched source rows into an LDS intermediate (uint8, as Pillow's is),
-//     vertical pass from LDS (resample_list.h, the passes of preprocess_list_kernel); below factor 1 the unit also writes
-//     the black canvas around the pasted window; a crop's rows are read in place from its corner in the frame.  Its launch
-//     alone carries the dynamic LDS, so the other units' occupancy does not pay for it.
+//   driver_list_scale_kernel: the band engine of resample_list.h (its LDS layout, its two passes, its packed uint8
+//     epilogue) with the block's tables; below factor 1 the unit also writes the black canvas around the pasted window; a
+//     crop's rows are read in place from its corner in the frame.  Its launch alone carries the dynamic LDS, so the other
+//     units' occupancy does not pay for it.
 #include "imgxf_common.h"
 #include "perspective_tile.h"
 #include "pixel_ops.h"
@@ -92,14 +92,13 @@ static int dl_rotation(int w, int h, double angle, int fx[6]) {
     return 0;
 }
 
-// Window rows per scale unit: the most, up to DL_UNIT_ROWS, whose touched rows fit the budget beside the staging (0: none).
-// The launch's LDS size is its largest unit's, so an entry takes the smallest of three steps of the budget that holds at
-// least one of its rows (pl_unit_rows of preprocess_list.hip)
-static int dl_unit_rows(int h, int nh, int ksy, int win_h, int win_w, int ncols, int lds_budget) {
-    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
-        for (int ny = win_h < DL_UNIT_ROWS ? win_h : DL_UNIT_ROWS; ny >= 1; --ny)
-            if (pl_lds_bytes(pl_rows_bound(ny, h, nh, ksy), win_w, ncols) <= limit) return ny;
-    return 0;
+// Window rows per scale unit (pl_unit_rows, resample_list.h) of an entry that resizes h -> nh rows with ksy taps and
+// touches at most ncols source columns; *lds: the bound on such a unit's LDS
+static int dl_unit_rows(int h, int nh, int ksy, int win_h, int win_w, int ncols, int lds_budget, int* lds) {
+    auto need = [&](int ny) { return pl_lds_bytes(pl_rows_bound(ny, h, nh, ksy), win_w, ncols); };
+    const int ny = pl_unit_rows(std::min(win_h, DL_UNIT_ROWS), lds_budget, need);
+    if (ny) *lds = std::max(*lds, (int)need(ny));
+    return ny;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -234,47 +233,14 @@ __global__ __launch_bounds__(DL_THREADS) void driver_list_scale_kernel(const u8*
     // the unit's rows of the window (table rows)
     const int ja = max(u.y0, e.win_top) - e.win_top, jb = min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
     if (jb <= ja) return;
-    const int* bx = words + e.bounds_x;
-    const int* kx = words + e.coeffs_x;
-    const int* by = words + e.bounds_y;
-    const int* ky = words + e.coeffs_y;
     const int width = e.win_w;
-    const int pitch = ((width + 3) >> 2) * 12;
-    // source rows these rows touch (the bounds are monotone), held inside the range the record states
-    const int r_lo = max(by[2 * ja], e.row0);
-    const int r_hi = min(by[2 * (jb - 1)] + by[2 * (jb - 1) + 1], e.row0 + e.nrows);
-    const int nrows = r_hi - r_lo;
-    u8* mid = dl_lds;
-    u8* stage = dl_lds + ((nrows * pitch + 15) & ~15);
     const u8* src = (const u8*)e.src + (int64_t)e.dy * e.src_stride + e.dx * 3;      // a crop's corner; (0, 0) for a scale
-    pl_horizontal_pass(src, e.src_stride, e.col0, e.ncols, r_lo, r_hi, bx, kx, e.ksx, width, mid, pitch, stage, tid);
-
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nq = (width + 3) >> 2;
-    for (int yy = wave; yy < jb - ja; yy += DL_THREADS / 64) {
-        const int j = ja + yy;
-        const int cnt = by[2 * j + 1];
-        const int ymin = min(max(by[2 * j] - r_lo, 0), max(nrows - cnt, 0));
-        const int* k = ky + (int64_t)j * e.ksy;
-        const int kv = lane < cnt ? k[lane] : 0;
-        for (int q = lane; q < nq; q += 64) {
-            int acc[12];
-            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
-            u32 od[3] = {0u, 0u, 0u};
-#pragma unroll
-            for (int b = 0; b < 12; ++b) od[b >> 2] |= (u32)clip8(acc[b]) << (8 * (b & 3));
-            const int nb = min(4, width - 4 * q) * 3;
-            u8* dp = o + ((int64_t)(e.win_top + j) * ow + e.win_left + 4 * q) * 3;
-            if (nb == 12 && (((uintptr_t)dp) & 3) == 0) {
-#pragma unroll
-                for (int d = 0; d < 3; ++d) ((u32*)dp)[d] = od[d];
-            } else {
-#pragma unroll
-                for (int b = 0; b < 12; ++b)
-                    if (b < nb) dp[b] = (u8)(od[b >> 2] >> (8 * (b & 3)));
-            }
-        }
-    }
+    pl_band(dl_lds, src, e.src_stride, e.col0, e.ncols, e.row0, e.nrows, words + e.bounds_x, words + e.coeffs_x, e.ksx,
+            words + e.bounds_y, words + e.coeffs_y, e.ksy, ja, jb - ja, width, tid,
+            [&](int j, int q, const int (&acc)[12]) __attribute__((always_inline)) {
+                u8* row = o + ((int64_t)(e.win_top + j) * ow + e.win_left) * 3;
+                pl_store_u8(acc, row, width, q, false, 4 * q + 4 <= width && (((uintptr_t)row) & 3) == 0);
+            });
 }
 
 } // namespace imgxf
@@ -366,13 +332,12 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
                 e.in_h = g.h; e.in_w = g.w;
                 e.ksx = coeff_ksize(g.w, nw, IMGXF_RESAMPLE_LANCZOS);
                 e.ksy = coeff_ksize(g.h, nh, IMGXF_RESAMPLE_LANCZOS);
-                e.unit_rows = dl_unit_rows(g.h, nh, e.ksy, e.win_h, e.win_w, pl_rows_bound(e.win_w, g.w, nw, e.ksx), lds_budget);
+                e.unit_rows = dl_unit_rows(g.h, nh, e.ksy, e.win_h, e.win_w, pl_rows_bound(e.win_w, g.w, nw, e.ksx), lds_budget,
+                                           &lds_bound);
                 if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
                 else {
                     ax[i] = axis_of(IMGXF_RESAMPLE_LANCZOS, g.w, nw, xfirst, e.win_w);
                     ay[i] = axis_of(IMGXF_RESAMPLE_LANCZOS, g.h, nh, yfirst, e.win_h);
-                    lds_bound = std::max(lds_bound, pl_lds_bytes(pl_rows_bound(e.unit_rows, g.h, nh, e.ksy), e.win_w,
-                                                                 pl_rows_bound(e.win_w, g.w, nw, e.ksx)));
                 }
             }
         } else if (g.type == IMGXF_DRIVER_ROTATION) {
@@ -411,13 +376,10 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
                 e.in_h = cs; e.in_w = cs;
                 e.oh = e.ow = e.win_h = e.win_w = side;
                 e.ksx = e.ksy = coeff_ksize(cs, side, IMGXF_RESAMPLE_BICUBIC);
-                const int ncols = pl_rows_bound(side, cs, side, e.ksx);
-                e.unit_rows = dl_unit_rows(cs, side, e.ksy, side, side, ncols, lds_budget);
+                e.unit_rows = dl_unit_rows(cs, side, e.ksy, side, side, pl_rows_bound(side, cs, side, e.ksx), lds_budget,
+                                           &lds_bound);
                 if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
-                else {
-                    ax[i] = ay[i] = axis_of(IMGXF_RESAMPLE_BICUBIC, cs, side, 0, side);
-                    lds_bound = std::max(lds_bound, pl_lds_bytes(pl_rows_bound(e.unit_rows, cs, side, e.ksy), side, ncols));
-                }
+                else ax[i] = ay[i] = axis_of(IMGXF_RESAMPLE_BICUBIC, cs, side, 0, side);
             }
         } else if (dl_blurs(g.type)) {
             if (p0 == 0.0) st = IMGXF_DRIVER_REFUSED_SIZE;    // the drivers hand back the input object itself
@@ -485,13 +447,8 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
     imgxf_driver_unit* units = (imgxf_driver_unit*)(out + units_off);
     int32_t* words = (int32_t*)out;
     size_t tpos = tables_off / 4;
-    std::vector<int> bv, kv;
     auto build_axis = [&](Axis& a) {
-        if (a.bounds >= 0) return;
-        build_coeffs(a.in, a.out, a.filter, bv, kv);
-        slice_tables(bv, kv, a.ks, a.first, a.count);
-        a.bounds = (int)tpos; memcpy(words + tpos, bv.data(), bv.size() * 4); tpos += bv.size();
-        a.coeffs = (int)tpos; memcpy(words + tpos, kv.data(), kv.size() * 4); tpos += kv.size();
+        if (a.bounds < 0) pl_append_axis(a.in, a.out, a.filter, a.ks, a.first, a.count, words, tpos, &a.bounds, &a.coeffs);
     };
     size_t upos = 0;
     int lds_max = 0;
@@ -514,23 +471,20 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         build_axis(x);
         build_axis(y);
         e.bounds_x = x.bounds; e.coeffs_x = x.coeffs; e.bounds_y = y.bounds; e.coeffs_y = y.coeffs;
-        const int32_t* bx = words + x.bounds;
-        const int32_t* by = words + y.bounds;
-        int c_lo = bx[0], c_hi = 0, r_lo = by[0], r_hi = 0;
-        for (int k = 0; k < e.win_w; ++k) { c_lo = std::min(c_lo, bx[2 * k]); c_hi = std::max(c_hi, bx[2 * k] + bx[2 * k + 1]); }
-        for (int k = 0; k < e.win_h; ++k) { r_lo = std::min(r_lo, by[2 * k]); r_hi = std::max(r_hi, by[2 * k] + by[2 * k + 1]); }
-        e.col0 = c_lo; e.ncols = c_hi - c_lo; e.row0 = r_lo; e.nrows = r_hi - r_lo;
+        int c_hi, r_hi, lo, hi;
+        pl_span(words + x.bounds, 0, e.win_w, &e.col0, &c_hi);
+        pl_span(words + y.bounds, 0, e.win_h, &e.row0, &r_hi);
+        e.ncols = c_hi - e.col0; e.nrows = r_hi - e.row0;
         for (int j0 = 0; j0 < e.win_h; j0 += e.unit_rows) {
             const int nj = std::min(e.unit_rows, e.win_h - j0);
-            int lo = by[2 * j0], hi = 0;
-            for (int j = j0; j < j0 + nj; ++j) { lo = std::min(lo, by[2 * j]); hi = std::max(hi, by[2 * j] + by[2 * j + 1]); }
+            pl_span(words + y.bounds, j0, nj, &lo, &hi);
             imgxf_driver_unit& u = units[upos++];
             u.entry = i;
             // the first and the last band of the window take the canvas rows above and below it
             u.y0 = j0 == 0 ? 0 : e.win_top + j0;
             const int y1 = j0 + nj >= e.win_h ? e.oh : e.win_top + j0 + nj;
             u.ny = y1 - u.y0;
-            u.lds_bytes = pl_lds_bytes(hi - lo, e.win_w, e.ncols);
+            u.lds_bytes = (int32_t)pl_lds_bytes(hi - lo, e.win_w, e.ncols);
             lds_max = std::max(lds_max, u.lds_bytes);
         }
     }
@@ -574,9 +528,8 @@ int driver_list_check(const void* block_host, const void* block_dev, const uint8
         hd.lds_bytes > DL_MAX_LDS)
         return IMGXF_ERR_ARG;
     const int64_t total = hd.total_bytes, words = total / 4;
-    if (hd.entries_off != (int)sizeof(imgxf_driver_header) ||
-        hd.units_off != hd.entries_off + (int64_t)hd.n_entries * (int64_t)sizeof(imgxf_driver_entry) ||
-        hd.tables_off != hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_driver_unit) || hd.tables_off > total)
+    if (!pl_check_sections(sizeof(imgxf_driver_header), hd.n_entries, sizeof(imgxf_driver_entry), hd.n_units,
+                           sizeof(imgxf_driver_unit), hd.entries_off, hd.units_off, hd.tables_off, total))
         return IMGXF_ERR_ARG;
     if (hd.n_units == 0) return IMGXF_OK;
     if (!block_dev || !out) return IMGXF_ERR_NULL;
@@ -607,21 +560,9 @@ int driver_list_check(const void* block_host, const void* block_dev, const uint8
                 if (e.row0 < 0 || e.nrows < 1 || (int64_t)e.row0 + e.nrows > e.in_h || e.col0 < 0 || e.ncols < 1 ||
                     (int64_t)e.col0 + e.ncols > e.in_w)
                     return IMGXF_ERR_SHAPE;
-                if (e.bounds_x < t0 || e.bounds_x + 2 * (int64_t)e.win_w > words || e.coeffs_x < t0 ||
-                    e.coeffs_x + (int64_t)e.win_w * e.ksx > words || e.bounds_y < t0 || e.bounds_y + 2 * (int64_t)e.win_h > words ||
-                    e.coeffs_y < t0 || e.coeffs_y + (int64_t)e.win_h * e.ksy > words)
+                if (!pl_check_axis((const int32_t*)hb, t0, words, e.bounds_x, e.coeffs_x, e.win_w, e.ksx, e.col0, e.ncols, false) ||
+                    !pl_check_axis((const int32_t*)hb, t0, words, e.bounds_y, e.coeffs_y, e.win_h, e.ksy, e.row0, e.nrows, true))
                     return IMGXF_ERR_ARG;
-                {                                             // every column's taps inside the staged span
-                    const int32_t* bx = (const int32_t*)hb + e.bounds_x;
-                    for (int x = 0; x < e.win_w; ++x)
-                        if (bx[2 * x] < e.col0 || bx[2 * x + 1] < 0 || bx[2 * x + 1] > e.ksx || (int64_t)bx[2 * x] + bx[2 * x + 1] > e.col0 + e.ncols)
-                            return IMGXF_ERR_ARG;
-                    const int32_t* by = (const int32_t*)hb + e.bounds_y;
-                    for (int y = 0; y < e.win_h; ++y)
-                        if (by[2 * y] < 0 || by[2 * y + 1] < 1 || by[2 * y + 1] > e.ksy || (int64_t)by[2 * y] + by[2 * y + 1] > e.in_h ||
-                            (y && by[2 * y] < by[2 * y - 2]))
-                            return IMGXF_ERR_ARG;
-                }
                 break;
             case IMGXF_DRIVER_SHEAR:
                 if (e.oh != e.h) return IMGXF_ERR_SHAPE;
@@ -670,11 +611,10 @@ int driver_list_check(const void* block_host, const void* block_dev, const uint8
             }
         }
         if (section != 2) continue;
-        // what the kernel will lay out: the unit's rows come from the tables, held inside [row0, row0 + nrows)
         const int ja = std::max(u.y0, e.win_top) - e.win_top, jb = std::min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
         if (jb <= ja) continue;
-        const int32_t* by = (const int32_t*)hb + e.bounds_y;
-        const int lo = std::max(by[2 * ja], e.row0), hi = std::min(by[2 * (jb - 1)] + by[2 * (jb - 1) + 1], e.row0 + e.nrows);
+        int lo, hi;                                           // what the kernel will lay out
+        pl_touched((const int32_t*)hb + e.bounds_y, ja, jb - ja, e.row0, e.nrows, &lo, &hi);
         if (hi <= lo || pl_lds_bytes(hi - lo, e.win_w, e.ncols) > hd.lds_bytes) return IMGXF_ERR_ARG;
     }
     return IMGXF_OK;

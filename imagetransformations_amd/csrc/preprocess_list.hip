@@ -8,45 +8,25 @@
 // Tables are precompute_coeffs' (build_coeffs, resample_coeffs.h) sliced to the crop window as the resample plans slice
 // them; frames of equal geometry share one set, so host work grows with the number of distinct sizes.
 //
-// DEVICE half (preprocess_list_kernel): one workgroup per work unit = up to PL_UNIT_ROWS output rows of one frame.
-//   LDS: | mid: rows_touched x pitch uint8 | stage: PL_STAGE_ROWS x spitch |      pitch = 12 * ceil(crop / 4)
-//   1. horizontal pass, PL_STAGE_ROWS source rows at a time: the aligned dwords that cover the byte span the crop columns
-//      need are staged with coalesced loads (frames start at any byte and rows are 3 W bytes, so each row has its own
-//      shift 0..3 inside its first dword; nothing outside the aligned dwords that hold the span's own bytes is read), a
-//      lane owns an output column, loads each coefficient once and applies it to the staged rows -> mid (uint8);
-//   2. vertical pass from mid: a wave owns an output row (its coefficients are wave-uniform: loaded one per lane, read
-//      across lanes in the tap loop), a lane 4 pixels = 3 dwords;
-//   3. ToTensor + Normalize (to_tensor_math.h) and planar stores, 16 bytes per lane where crop % 4 == 0.
+// DEVICE half (preprocess_list_kernel): one workgroup per work unit = up to PL_UNIT_ROWS output rows of one frame, run
+// through the band engine of resample_list.h (its LDS layout, its two passes, its float32 planar epilogue) with the
+// block's tables: 16-byte stores per lane where crop % 4 == 0.
 #include "imgxf_common.h"
 #include "resample_coeffs.h"
 #include "resample_list.h"
-#include "to_tensor_math.h"
 #include <map>
+#include <unordered_map>
 #include <array>
+#include <stddef.h>
 #include <string.h>
 
 namespace imgxf {
 
 constexpr int PL_UNIT_ROWS = 16;          // output rows per work unit when the LDS budget allows
 constexpr int PL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB whatever else runs there
-// (PL_THREADS, PL_STAGE_ROWS, pl_pitch, pl_stage_pitch, pl_lds_bytes, pl_rows_bound: resample_list.h)
 
 // geometry of one frame as the caller states it
 struct PlGeom { int h, w, nh, nw, left, top; };
-
-static inline int pl_cols_bound(int crop, int in, int out, int ksize) { return pl_rows_bound(crop, in, out, ksize); }
-
-// Output rows per unit: the most, up to PL_UNIT_ROWS, whose touched rows fit the budget beside the staging (0: none does)
-static int pl_unit_rows(const PlGeom& g, int crop, int ksx, int ksy, int lds_budget) {
-    const int ncols = pl_cols_bound(crop, g.w, g.nw, ksx);
-    // the launch's LDS size is its largest unit's, so a frame takes the smallest of three steps of the budget that holds
-    // at least one of its rows (1/2: five workgroups per CU at 64 KiB, 3/4: three, all of it: two), and within that step
-    // as many rows as fit: one large frame in a list then costs the other frames' workgroups as little room as it can
-    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
-        for (int ny = crop < PL_UNIT_ROWS ? crop : PL_UNIT_ROWS; ny >= 1; --ny)
-            if (pl_lds_bytes(pl_rows_bound(ny, g.h, g.nh, ksy), crop, ncols) <= limit) return ny;
-    return 0;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(PL_THREADS) void preprocess_list_kernel(const u8* __restrict__ block, int frames_off,
@@ -56,50 +36,58 @@ __global__ __launch_bounds__(PL_THREADS) void preprocess_list_kernel(const u8* _
     const int* words = (const int*)block;
     const imgxf_preprocess_unit u = ((const imgxf_preprocess_unit*)(block + units_off))[blockIdx.x];
     const imgxf_preprocess_frame fr = ((const imgxf_preprocess_frame*)(block + frames_off))[u.frame];
-    const int* bx = words + fr.bounds_x;
-    const int* kx = words + fr.coeffs_x;
-    const int* by = words + fr.bounds_y;
-    const int* ky = words + fr.coeffs_y;
-    const int tid = threadIdx.x;
-    const int pitch = ((crop + 3) >> 2) * 12;
-    // source rows this unit's output rows touch (the bounds are monotone), held inside the window the record states
-    const int ylast = u.y0 + u.ny - 1;
-    const int r_lo = max(by[2 * u.y0], fr.row0);
-    const int r_hi = min(by[2 * ylast] + by[2 * ylast + 1], fr.row0 + fr.nrows);
-    const int nrows = r_hi - r_lo;
-    u8* mid = pl_lds;
-    u8* stage = pl_lds + ((nrows * pitch + 15) & ~15);
-    pl_horizontal_pass((const u8*)fr.data, fr.row_stride, fr.col0, fr.ncols, r_lo, r_hi, bx, kx, fr.ksx, crop, mid, pitch, stage, tid);
-
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nq = (crop + 3) >> 2;
     const int64_t plane = (int64_t)crop * crop;
-    for (int yy = wave; yy < u.ny; yy += PL_THREADS / 64) {
-        const int y = u.y0 + yy;
-        const int cnt = by[2 * y + 1];
-        const int ymin = min(max(by[2 * y] - r_lo, 0), max(nrows - cnt, 0));
-        const int* k = ky + (int64_t)y * fr.ksy;
-        // the row's first 64 coefficients, one per lane: the tap loop reads them across lanes, not from memory
-        const int kv = lane < cnt ? k[lane] : 0;
-        for (int q = lane; q < nq; q += 64) {
-            int acc[12];
-            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
-            const int npx = min(4, crop - 4 * q);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = to_tensor_value(clip8(acc[3 * j + c]), a, c);
-                float* dp = out + ((int64_t)u.frame * 3 + c) * plane + (int64_t)y * crop + 4 * q;
-                if (VEC) {
-                    *(float4*)dp = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) if (j < npx) dp[j] = v[j];
-                }
-            }
-        }
+    float* o = out + (int64_t)u.frame * 3 * plane;
+    pl_band(pl_lds, (const u8*)fr.data, fr.row_stride, fr.col0, fr.ncols, fr.row0, fr.nrows, words + fr.bounds_x,
+            words + fr.coeffs_x, fr.ksx, words + fr.bounds_y, words + fr.coeffs_y, fr.ksy, u.y0, u.ny, crop, threadIdx.x,
+            [&](int y, int q, const int (&acc)[12]) __attribute__((always_inline)) {
+                pl_store_f32<VEC>(acc, o + (int64_t)y * crop, plane, crop, q, false, a);
+            });
+}
+
+// The host checks of imgxf_preprocess_list_f32 on the block alone, before any device is needed: IMGXF_OK when its
+// records bound every address the kernel forms inside the frames and the block (or it has no units)
+int preprocess_list_check(const void* block_host) {
+    if (!block_host) return IMGXF_ERR_NULL;
+    const u8* hb = (const u8*)block_host;
+    const imgxf_preprocess_header hd = *(const imgxf_preprocess_header*)hb;
+    if (hd.n_frames < 0 || hd.n_units < 0 || hd.crop < 1 || hd.lds_bytes < 0 || hd.lds_bytes > PL_MAX_LDS) return IMGXF_ERR_ARG;
+    const int64_t total = hd.total_bytes, words = total / 4, t0 = hd.tables_off / 4;
+    if (!pl_check_sections(sizeof(imgxf_preprocess_header), hd.n_frames, sizeof(imgxf_preprocess_frame), hd.n_units,
+                           sizeof(imgxf_preprocess_unit), hd.frames_off, hd.units_off, hd.tables_off, total))
+        return IMGXF_ERR_ARG;
+    if (hd.n_units == 0) return IMGXF_OK;
+    const imgxf_preprocess_frame* frames = (const imgxf_preprocess_frame*)(hb + hd.frames_off);
+    const imgxf_preprocess_unit* units = (const imgxf_preprocess_unit*)(hb + hd.units_off);
+    // frames of equal geometry share their tables and state the same spans: what depends on those alone is checked once
+    constexpr size_t shared = offsetof(imgxf_preprocess_frame, unit_rows) - offsetof(imgxf_preprocess_frame, h);
+    std::unordered_map<int32_t, const imgxf_preprocess_frame*> checked;       // by bounds_x
+    for (int i = 0; i < hd.n_frames; ++i) {
+        const imgxf_preprocess_frame& f = frames[i];
+        if (!f.unit_rows) continue;
+        if (!f.data) return IMGXF_ERR_NULL;
+        if (f.w < 1 || f.row_stride < (int64_t)f.w * 3) return IMGXF_ERR_SHAPE;
+        const auto seen = checked.find(f.bounds_x);
+        if (seen != checked.end() && !memcmp(&seen->second->h, &f.h, shared)) continue;
+        if (f.h < 1 || f.ksx < 1 || f.ksy < 1) return IMGXF_ERR_SHAPE;
+        if (f.row0 < 0 || f.nrows < 1 || (int64_t)f.row0 + f.nrows > f.h || f.col0 < 0 || f.ncols < 1 ||
+            (int64_t)f.col0 + f.ncols > f.w)
+            return IMGXF_ERR_SHAPE;
+        if (!pl_check_axis((const int32_t*)hb, t0, words, f.bounds_x, f.coeffs_x, hd.crop, f.ksx, f.col0, f.ncols, false) ||
+            !pl_check_axis((const int32_t*)hb, t0, words, f.bounds_y, f.coeffs_y, hd.crop, f.ksy, f.row0, f.nrows, true))
+            return IMGXF_ERR_ARG;
+        checked.emplace(f.bounds_x, &f);
     }
+    for (int k = 0; k < hd.n_units; ++k) {
+        const imgxf_preprocess_unit& u = units[k];
+        if (u.frame < 0 || u.frame >= hd.n_frames || !frames[u.frame].unit_rows) return IMGXF_ERR_ARG;
+        if (u.y0 < 0 || u.ny < 1 || (int64_t)u.y0 + u.ny > hd.crop || u.lds_bytes > hd.lds_bytes) return IMGXF_ERR_ARG;
+        const imgxf_preprocess_frame& f = frames[u.frame];
+        int lo, hi;                                               // what the kernel will lay out
+        pl_touched((const int32_t*)hb + f.bounds_y, u.y0, u.ny, f.row0, f.nrows, &lo, &hi);
+        if (hi <= lo || pl_lds_bytes(hi - lo, hd.crop, f.ncols) > hd.lds_bytes) return IMGXF_ERR_ARG;
+    }
+    return IMGXF_OK;
 }
 
 } // namespace imgxf
@@ -119,7 +107,7 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
         if (g.left < 0 || g.top < 0 || g.left + crop > g.nw || g.top + crop > g.nh) return IMGXF_ERR_ARG;   // window outside
     }
     // pass over the geometry alone: which frames share tables, taps, rows per unit -> the size of every section
-    struct Set { int first, ksx, ksy, unit_rows, table_off; };
+    struct Set { int first, ksx, ksy, unit_rows; };
     std::map<std::array<int, 6>, int> index;
     std::vector<Set> sets;
     std::vector<int> set_of(n);
@@ -133,8 +121,10 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
             s.first = i;
             s.ksx = coeff_ksize(g.w, g.nw, IMGXF_RESAMPLE_BILINEAR);
             s.ksy = coeff_ksize(g.h, g.nh, IMGXF_RESAMPLE_BILINEAR);
-            s.unit_rows = pl_unit_rows(g, crop, s.ksx, s.ksy, lds_budget);
-            s.table_off = 0;
+            const int ncols = pl_rows_bound(crop, g.w, g.nw, s.ksx);
+            s.unit_rows = pl_unit_rows(std::min(crop, PL_UNIT_ROWS), lds_budget, [&](int ny) {
+                return pl_lds_bytes(pl_rows_bound(ny, g.h, g.nh, s.ksy), crop, ncols);
+            });
             if (s.unit_rows) table_words += (size_t)crop * (4 + s.ksx + s.ksy);
             it = index.emplace(key, (int)sets.size()).first;
             sets.push_back(s);
@@ -161,43 +151,31 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
     size_t tpos = tables_off / 4;
     int lds_max = 0;
     size_t upos = 0;
-    std::vector<int> bxv, kxv, byv, kyv;
     for (int i = 0; i < n; ++i) {
         const PlGeom& g = geo[i];
-        Set& s = sets[set_of[i]];
+        const Set& s = sets[set_of[i]];
         imgxf_preprocess_frame& f = frames[i];
         if (s.first != i) {                                       // an earlier frame of this geometry built the tables
-            const imgxf_preprocess_frame& e = frames[s.first];
-            f = e;
+            f = frames[s.first];
             f.data = 0; f.row_stride = 0;
         } else {
             f.h = g.h; f.w = g.w; f.ksx = s.ksx; f.ksy = s.ksy; f.unit_rows = s.unit_rows;
             if (s.unit_rows) {
-                build_coeffs(g.w, g.nw, IMGXF_RESAMPLE_BILINEAR, bxv, kxv);
-                slice_tables(bxv, kxv, s.ksx, g.left, crop);
-                build_coeffs(g.h, g.nh, IMGXF_RESAMPLE_BILINEAR, byv, kyv);
-                slice_tables(byv, kyv, s.ksy, g.top, crop);
-                int c_lo = bxv[0], c_hi = 0, r_lo = byv[0], r_hi = 0;
-                for (int x = 0; x < crop; ++x) {
-                    c_lo = std::min(c_lo, bxv[2 * x]); c_hi = std::max(c_hi, bxv[2 * x] + bxv[2 * x + 1]);
-                    r_lo = std::min(r_lo, byv[2 * x]); r_hi = std::max(r_hi, byv[2 * x] + byv[2 * x + 1]);
-                }
-                f.col0 = c_lo; f.ncols = c_hi - c_lo; f.row0 = r_lo; f.nrows = r_hi - r_lo;
-                f.bounds_x = (int32_t)tpos; memcpy(words + tpos, bxv.data(), bxv.size() * 4); tpos += bxv.size();
-                f.coeffs_x = (int32_t)tpos; memcpy(words + tpos, kxv.data(), kxv.size() * 4); tpos += kxv.size();
-                f.bounds_y = (int32_t)tpos; memcpy(words + tpos, byv.data(), byv.size() * 4); tpos += byv.size();
-                f.coeffs_y = (int32_t)tpos; memcpy(words + tpos, kyv.data(), kyv.size() * 4); tpos += kyv.size();
+                pl_append_axis(g.w, g.nw, IMGXF_RESAMPLE_BILINEAR, s.ksx, g.left, crop, words, tpos, &f.bounds_x, &f.coeffs_x);
+                pl_append_axis(g.h, g.nh, IMGXF_RESAMPLE_BILINEAR, s.ksy, g.top, crop, words, tpos, &f.bounds_y, &f.coeffs_y);
+                int c_hi, r_hi;
+                pl_span(words + f.bounds_x, 0, crop, &f.col0, &c_hi);
+                pl_span(words + f.bounds_y, 0, crop, &f.row0, &r_hi);
+                f.ncols = c_hi - f.col0; f.nrows = r_hi - f.row0;
             }
         }
         if (!s.unit_rows) continue;
-        const int32_t* by = words + f.bounds_y;
         for (int y0 = 0; y0 < crop; y0 += s.unit_rows) {
-            const int ny = std::min(s.unit_rows, crop - y0);
-            int lo = by[2 * y0], hi = 0;
-            for (int y = y0; y < y0 + ny; ++y) { lo = std::min(lo, by[2 * y]); hi = std::max(hi, by[2 * y] + by[2 * y + 1]); }
             imgxf_preprocess_unit& u = units[upos++];
-            u.frame = i; u.y0 = y0; u.ny = ny;
-            u.lds_bytes = pl_lds_bytes(hi - lo, crop, f.ncols);
+            u.frame = i; u.y0 = y0; u.ny = std::min(s.unit_rows, crop - y0);
+            int lo, hi;
+            pl_span(words + f.bounds_y, y0, u.ny, &lo, &hi);
+            u.lds_bytes = (int32_t)pl_lds_bytes(hi - lo, crop, f.ncols);
             lds_max = std::max(lds_max, u.lds_bytes);
         }
     }
@@ -209,46 +187,12 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
 
 IMGXF_API int imgxf_preprocess_list_f32(const void* block_host, const void* block_dev, float* out, const float* mean,
                                         const float* std, void* stream) {
-    if (!block_host) return IMGXF_ERR_NULL;
-    const u8* hb = (const u8*)block_host;
-    const imgxf_preprocess_header hd = *(const imgxf_preprocess_header*)hb;
-    if ((mean == nullptr) != (std == nullptr)) return IMGXF_ERR_NULL;
-    if (hd.n_frames < 0 || hd.n_units < 0 || hd.crop < 1 || hd.lds_bytes < 0 || hd.lds_bytes > PL_MAX_LDS) return IMGXF_ERR_ARG;
-    const int64_t total = hd.total_bytes, words = total / 4;
-    if (hd.frames_off != (int)sizeof(imgxf_preprocess_header) ||
-        hd.units_off != hd.frames_off + (int64_t)hd.n_frames * (int64_t)sizeof(imgxf_preprocess_frame) ||
-        hd.tables_off != hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_preprocess_unit) || hd.tables_off > total)
-        return IMGXF_ERR_ARG;
+    if (!block_host || (mean == nullptr) != (std == nullptr)) return IMGXF_ERR_NULL;
+    IMGXF_CHECK(preprocess_list_check(block_host));
+    const imgxf_preprocess_header hd = *(const imgxf_preprocess_header*)block_host;
     if (hd.n_units == 0) return IMGXF_OK;
     if (!block_dev || !out) return IMGXF_ERR_NULL;
     if (((uintptr_t)out) & 3 || ((uintptr_t)block_dev) & 7) return IMGXF_ERR_ARG;
-    // the records bound every address the kernel forms: check them against the frames and the block
-    const imgxf_preprocess_frame* frames = (const imgxf_preprocess_frame*)(hb + hd.frames_off);
-    const imgxf_preprocess_unit* units = (const imgxf_preprocess_unit*)(hb + hd.units_off);
-    const int64_t crop = hd.crop;
-    for (int i = 0; i < hd.n_frames; ++i) {
-        const imgxf_preprocess_frame& f = frames[i];
-        if (!f.unit_rows) continue;
-        if (!f.data) return IMGXF_ERR_NULL;
-        if (f.h < 1 || f.w < 1 || f.row_stride < (int64_t)f.w * 3 || f.ksx < 1 || f.ksy < 1) return IMGXF_ERR_SHAPE;
-        if (f.row0 < 0 || f.nrows < 1 || f.row0 + f.nrows > f.h || f.col0 < 0 || f.ncols < 1 || f.col0 + f.ncols > f.w)
-            return IMGXF_ERR_SHAPE;
-        const int64_t t0 = hd.tables_off / 4;
-        if (f.bounds_x < t0 || f.bounds_x + 2 * crop > words || f.coeffs_x < t0 || f.coeffs_x + crop * f.ksx > words ||
-            f.bounds_y < t0 || f.bounds_y + 2 * crop > words || f.coeffs_y < t0 || f.coeffs_y + crop * f.ksy > words)
-            return IMGXF_ERR_ARG;
-    }
-    for (int k = 0; k < hd.n_units; ++k) {
-        const imgxf_preprocess_unit& u = units[k];
-        if (u.frame < 0 || u.frame >= hd.n_frames || !frames[u.frame].unit_rows) return IMGXF_ERR_ARG;
-        if (u.y0 < 0 || u.ny < 1 || u.y0 + u.ny > crop || u.lds_bytes > hd.lds_bytes) return IMGXF_ERR_ARG;
-        const imgxf_preprocess_frame& f = frames[u.frame];
-        // what the kernel will lay out: the unit's rows come from the tables, held inside [row0, row0 + nrows)
-        const int32_t* by = (const int32_t*)hb + f.bounds_y;
-        const int ylast = u.y0 + u.ny - 1;
-        const int lo = std::max(by[2 * u.y0], f.row0), hi = std::min(by[2 * ylast] + by[2 * ylast + 1], f.row0 + f.nrows);
-        if (hi <= lo || pl_lds_bytes(hi - lo, hd.crop, f.ncols) > hd.lds_bytes) return IMGXF_ERR_ARG;
-    }
     const NormArgs a = make_norm_args(mean, std, 3);
     const bool vec = (hd.crop & 3) == 0 && (((uintptr_t)out) & 15) == 0;
     hipStream_t st = (hipStream_t)stream;

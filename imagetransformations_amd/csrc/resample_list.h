@@ -1,21 +1,32 @@
-// The two passes of Pillow's 8-bit Image.resize on ONE workgroup's band of output rows, shared by the record-driven list
-// kernels (preprocess_list.hip, driver_list.hip): the horizontal pass of the touched source rows into an LDS intermediate
-// (uint8, as Pillow's is) and the tap loop of the vertical pass from it.  Frames start at any byte and their rows are
-// 3 W bytes at any stride.
+// The band engine of the record-driven list kernels (preprocess_list.hip, driver_list.hip, resized_crop_list.hip):
+// Pillow's two-pass 8-bit Image.resize on ONE workgroup's band of output rows of one RGB frame — the horizontal pass of
+// the touched source rows into an LDS intermediate (uint8, as Pillow's is), the vertical pass from it, the store
+// epilogues — and what the host halves share around it: the LDS layout (one statement for host and device), the
+// rows-per-unit rule, table spans and appends, the launchers' checks.  Frames start at any byte, rows at any stride.
 //   LDS: | mid: rows_touched x pitch uint8 | stage: PL_STAGE_ROWS x spitch |      pitch = 12 * ceil(width / 4)
 #pragma once
 #include "imgxf_common.h"
 #include "resample_coeffs.h"
+#include "to_tensor_math.h"
+#include <string.h>
 
 namespace imgxf {
 
 constexpr int PL_THREADS = 256;
 constexpr int PL_STAGE_ROWS = 4;          // source rows staged (and filtered per coefficient load) at a time
 
-static inline int pl_pitch(int width) { return ((width + 3) >> 2) * 12; }
-static inline int pl_stage_pitch(int ncols) { return (ncols * 3 + 3 + 3) & ~3; }      // + 3: the row's shift
-static inline int pl_lds_bytes(int rows, int width, int ncols) {
-    return ((rows * pl_pitch(width) + 15) & ~15) + PL_STAGE_ROWS * pl_stage_pitch(ncols);
+__host__ __device__ static inline int pl_pitch(int width) { return ((width + 3) >> 2) * 12; }
+__host__ __device__ static inline int pl_stage_pitch(int ncols) { return (ncols * 3 + 3 + 3) & ~3; }      // + 3: the row's shift
+__host__ __device__ static inline int64_t pl_mid_bytes(int64_t rows, int pitch) { return (rows * pitch + 15) & ~(int64_t)15; }
+__host__ __device__ static inline int64_t pl_lds_bytes(int rows, int width, int ncols) {
+    return pl_mid_bytes(rows, pl_pitch(width)) + PL_STAGE_ROWS * pl_stage_pitch(ncols);
+}
+
+// Source rows [*lo, *hi) that rows [ja, ja + nj) of a bounds table touch (the bounds are monotone), held inside the span
+// [row0, row0 + rows) its record states: what a unit stages, and what its launcher checks
+__host__ __device__ static inline void pl_touched(const int* by, int ja, int nj, int row0, int rows, int* lo, int* hi) {
+    const int jl = ja + nj - 1, a = by[2 * ja], b = by[2 * jl] + by[2 * jl + 1];
+    *lo = a > row0 ? a : row0; *hi = b < row0 + rows ? b : row0 + rows;
 }
 
 // Source rows that `ny` consecutive output rows can touch: the windows of precompute_coeffs are at most ksize wide and
@@ -23,6 +34,63 @@ static inline int pl_lds_bytes(int rows, int width, int ncols) {
 static inline int pl_rows_bound(int ny, int in, int out, int ksize) {
     const int r = (int)ceil((ny - 1) * ((double)in / out)) + ksize;
     return r < in ? r : in;
+}
+
+// Output rows per unit: the most, up to max_rows, whose LDS need lds_of_ny(ny) fits (0: not even one row does).  The
+// launch's LDS size is its largest unit's, so a frame takes the smallest of three steps of the budget that holds one of
+// its rows (1/2: five workgroups per CU at 64 KiB, 3/4: three, all of it: two), and within that step as many as fit
+template <class LdsOfNy>
+static int pl_unit_rows(int max_rows, int lds_budget, LdsOfNy lds_of_ny) {
+    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
+        for (int ny = max_rows; ny >= 1; --ny)
+            if (lds_of_ny(ny) <= limit) return ny;
+    return 0;
+}
+
+// [lo, hi): the source samples that rows [first, first + count) of a [.][2] (first, count) bounds table touch
+static inline void pl_span(const int32_t* bounds, int first, int count, int* lo, int* hi) {
+    int a = bounds[2 * first], b = 0;
+    for (int k = first; k < first + count; ++k) {
+        a = std::min(a, bounds[2 * k]);
+        b = std::max(b, bounds[2 * k] + bounds[2 * k + 1]);
+    }
+    *lo = a; *hi = b;
+}
+
+// build_coeffs' tables for (in -> out, filter), rows [first, first + count), appended to a block's words at tpos
+static void pl_append_axis(int in, int out, int filter, int ks, int first, int count, int32_t* words, size_t& tpos,
+                           int32_t* bounds, int32_t* coeffs) {
+    std::vector<int> bv, kv;
+    build_coeffs(in, out, filter, bv, kv);
+    slice_tables(bv, kv, ks, first, count);
+    *bounds = (int32_t)tpos; memcpy(words + tpos, bv.data(), bv.size() * 4); tpos += bv.size();
+    *coeffs = (int32_t)tpos; memcpy(words + tpos, kv.data(), kv.size() * 4); tpos += kv.size();
+}
+
+// Launcher check of header | records | units | tables: each section starts where the counts before it end, the tables
+// inside the block (a block without tables states the end of its units there)
+static inline bool pl_check_sections(size_t header_bytes, int64_t n_records, size_t record_bytes, int64_t n_units,
+                                     size_t unit_bytes, int64_t records_off, int64_t units_off, int64_t tables_off,
+                                     int64_t total) {
+    return records_off == (int64_t)header_bytes && units_off == records_off + n_records * (int64_t)record_bytes &&
+           tables_off == units_off + n_units * (int64_t)unit_bytes && tables_off <= total;
+}
+
+// Launcher check of one axis' tables as a record states them (host block of `words` words, tables from word t0): both
+// inside the tables section, counts within ks, taps inside the staged span [first, first + extent) — the horizontal
+// pass reads them unclamped; rows: also no empty window and non-decreasing starts (a unit's touched rows are read off
+// its first and last row)
+static inline bool pl_check_axis(const int32_t* block, int64_t t0, int64_t words, int32_t bounds, int32_t coeffs, int count,
+                                 int ks, int first, int extent, bool rows) {
+    if (bounds < t0 || bounds + 2 * (int64_t)count > words || coeffs < t0 || coeffs + (int64_t)count * ks > words) return false;
+    const int32_t* b = block + bounds;
+    for (int k = 0; k < count; ++k) {
+        if (b[2 * k] < first || b[2 * k + 1] < (rows ? 1 : 0) || b[2 * k + 1] > ks ||
+            (int64_t)b[2 * k] + b[2 * k + 1] > (int64_t)first + extent)
+            return false;
+        if (rows && k && b[2 * k] < b[2 * k - 2]) return false;
+    }
+    return true;
 }
 
 // Horizontal pass of source rows [r_lo, r_hi) into mid (row r at mid + (r - r_lo) * pitch), PL_STAGE_ROWS rows at a time:
@@ -34,7 +102,7 @@ __device__ __forceinline__ void pl_horizontal_pass(const u8* src, int64_t row_st
                                                    const int* bx, const int* kx, int ksx, int width, u8* mid, int pitch,
                                                    u8* stage, int tid) {
     const int nrows = r_hi - r_lo;
-    const int spitch = (ncols * 3 + 3 + 3) & ~3;
+    const int spitch = pl_stage_pitch(ncols);
     for (int g0 = 0; g0 < nrows; g0 += PL_STAGE_ROWS) {
         int sh[PL_STAGE_ROWS], ndw[PL_STAGE_ROWS];
         const u32* base[PL_STAGE_ROWS];
@@ -98,6 +166,93 @@ __device__ __forceinline__ void pl_vertical_taps(const u8* mid, int pitch, int y
 #pragma unroll
         for (int b = 0; b < 12; ++b) acc[b] += mul24((int)((d[b >> 2] >> (8 * (b & 3))) & 0xffu), w);
         p += pitch >> 2;
+    }
+}
+
+// Vertical pass of table rows [j0, j0 + nj), `width` pixels each, from mid (source rows [r_lo, r_lo + nrows) at `pitch`):
+// a wave owns an output row (its coefficients are wave-uniform: loaded one per lane), a lane 4 pixels = 3 dwords.  by /
+// ky: the [.][2] bounds and [.][ksy] coefficients; a row's window is held inside the staged rows.
+// store(j, q, acc): the unclipped sums of pixels 4 q .. 4 q + 3 of table row j, channels interleaved.
+template <class Store>
+__device__ __forceinline__ void pl_vertical_pass(const u8* mid, int pitch, int r_lo, int nrows, const int* by, const int* ky,
+                                                 int ksy, int j0, int nj, int width, int tid, Store store) {
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int nq = (width + 3) >> 2;
+    for (int yy = wave; yy < nj; yy += PL_THREADS / 64) {
+        const int j = j0 + yy;
+        const int cnt = by[2 * j + 1];
+        const int ymin = min(max(by[2 * j] - r_lo, 0), max(nrows - cnt, 0));
+        const int* k = ky + (int64_t)j * ksy;
+        const int kv = lane < cnt ? k[lane] : 0;
+        for (int q = lane; q < nq; q += 64) {
+            int acc[12];
+            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
+            store(j, q, acc);
+        }
+    }
+}
+
+// One unit through both passes with the tables of its frame's record: table rows [ja, ja + nj), `width` pixels each, of a
+// frame at src whose tables touch source columns [col0, col0 + ncols) and rows [row0, row0 + rows).  lds: the launch's
+// dynamic LDS, laid out as above; store: pl_vertical_pass's
+template <class Store>
+__device__ __forceinline__ void pl_band(u8* lds, const u8* src, int64_t row_stride, int col0, int ncols, int row0, int rows,
+                                        const int* bx, const int* kx, int ksx, const int* by, const int* ky, int ksy, int ja,
+                                        int nj, int width, int tid, Store store) {
+    const int pitch = pl_pitch(width);
+    int r_lo, r_hi;
+    pl_touched(by, ja, nj, row0, rows, &r_lo, &r_hi);
+    u8* stage = lds + (int)pl_mid_bytes(r_hi - r_lo, pitch);
+    pl_horizontal_pass(src, row_stride, col0, ncols, r_lo, r_hi, bx, kx, ksx, width, lds, pitch, stage, tid);
+    pl_vertical_pass(lds, pitch, r_lo, r_hi - r_lo, by, ky, ksy, ja, nj, width, tid, store);
+}
+
+// Store epilogues of a quad: pixel j is output column 4 q + j of a `width`-pixel row, width - 1 - (4 q + j) under `flip`
+// (a literal false folds the mirror away).  float32 planar after ToTensor + Normalize: `row` is the output row in channel
+// 0, the channels `plane` floats apart.  VEC: width % 4 == 0 and the rows aligned for 16-byte stores.
+template <bool VEC>
+__device__ __forceinline__ void pl_store_f32(const int (&acc)[12], float* row, int64_t plane, int width, int q, bool flip,
+                                             const NormArgs& a) {
+    const int npx = min(4, width - 4 * q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = to_tensor_value(clip8(acc[3 * j + c]), a, c);
+        float* r = row + c * plane;
+        if (VEC) {
+            if (flip) *(float4*)(r + width - 4 - 4 * q) = make_float4(v[3], v[2], v[1], v[0]);
+            else *(float4*)(r + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < npx) r[flip ? width - 1 - (4 * q + j) : 4 * q + j] = v[j];
+        }
+    }
+}
+
+// uint8 interleaved: `row` is the output row's first byte.  dwords: the caller's word that the quad is whole and starts
+// on a 4-byte boundary (three dword stores); else byte stores of the pixels inside the row.
+__device__ __forceinline__ void pl_store_u8(const int (&acc)[12], u8* row, int width, int q, bool flip, bool dwords) {
+    u32 px[12];
+#pragma unroll
+    for (int b = 0; b < 12; ++b) px[b] = clip8(acc[b]);
+    if (dwords) {
+        u32 d[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int b = 0; b < 12; ++b) d[b >> 2] |= px[3 * (flip ? 3 - b / 3 : b / 3) + b % 3] << (8 * (b & 3));
+        u32* dp = (u32*)(row + (flip ? width - 4 - 4 * q : 4 * q) * 3);
+        dp[0] = d[0]; dp[1] = d[1]; dp[2] = d[2];
+    } else {
+        const int npx = min(4, width - 4 * q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < npx) {
+                u8* dp = row + (flip ? width - 1 - (4 * q + j) : 4 * q + j) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dp[c] = (u8)px[3 * j + c];
+            }
+        }
     }
 }
 

@@ -12,15 +12,14 @@
 //   LDS: | bounds_x [Sw][2] | coeffs_x [Sw][ksx] | bounds_y [ny][2] | coeffs_y [ny][ksy] | mid | stage |
 //   0. a lane builds one row of a table: precompute_coeffs + normalize_coeffs_8bpc for its output column (or output row of
 //      the unit) in fp64, build_coeffs (resample_coeffs.h) restated operation by operation (rcl_build_row);
-//   1. + 2. the two passes of resample_list.h (pl_horizontal_pass, pl_vertical_taps) from those tables, on the box as the
-//      image: the source pointer is the box's first pixel, so no tap reads a pixel outside the box;
+//   1. + 2. the two passes of the band engine (resample_list.h: pl_horizontal_pass, pl_vertical_pass) from those tables,
+//      on the box as the image: the source pointer is the box's first pixel, so no tap reads a pixel outside the box;
 //      (a box more than 100 times as tall as wide that loses rows: Pillow's order for it, rows first — `tall` below);
-//   3. the flip as a mirrored store column, then float32 planar stores after ToTensor + Normalize (to_tensor_math.h), 16
-//      bytes per lane where Sw % 4 == 0, or the uint8 interleaved bytes themselves.
+//   3. the engine's store epilogues with the flip as a mirrored store column: float32 planar after ToTensor + Normalize
+//      (pl_store_f32), 16 bytes per lane where Sw % 4 == 0, or the uint8 interleaved bytes themselves (pl_store_u8).
 #include "imgxf_common.h"
 #include "resample_coeffs.h"
 #include "resample_list.h"
-#include "to_tensor_math.h"
 #include <string.h>
 
 namespace imgxf {
@@ -31,7 +30,8 @@ constexpr int RCL_MAX_LDS = 64 * 1024;    // per workgroup, tables included: two
 // geometry of one entry as the caller states it
 struct RclGeom { int h, w, top, left, bh, bw, flip; };
 
-static inline int64_t rcl_table_bytes(int sw, int ny, int ksx, int ksy) {
+// the unit's own tables, built in LDS before the band engine's layout
+__host__ __device__ static inline int64_t rcl_table_bytes(int sw, int ny, int ksx, int ksy) {
     return (4 * ((int64_t)sw * (2 + (int64_t)ksx) + (int64_t)ny * (2 + (int64_t)ksy)) + 15) & ~(int64_t)15;
 }
 // Pillow's Image.resize runs the VERTICAL pass first where the image is more than 100 times as tall as wide and loses
@@ -40,25 +40,22 @@ static inline int rcl_tall(int bh, int bw, int sh) { return (int64_t)bh > (int64
 
 // LDS of a unit of `ny` output rows that touch at most `rows` source rows and `ncols` source columns.  A tall unit holds
 // its source rows and their vertical pass, both bw pixels wide, and then ny rows of the horizontal pass.
-static inline int64_t rcl_lds_bytes(int rows, int sw, int ncols, int ny, int ksx, int ksy, int tall, int bw) {
-    const int64_t fixed = rcl_table_bytes(sw, ny, ksx, ksy) + (int64_t)PL_STAGE_ROWS * pl_stage_pitch(ncols);
-    if (!tall) return fixed + (((int64_t)rows * pl_pitch(sw) + 15) & ~(int64_t)15);
-    return fixed + (((int64_t)rows * pl_pitch(bw) + 15) & ~(int64_t)15) + (((int64_t)ny * pl_pitch(bw) + 15) & ~(int64_t)15) +
-           (((int64_t)ny * pl_pitch(sw) + 15) & ~(int64_t)15);
+__host__ __device__ static inline int64_t rcl_lds_bytes(int rows, int sw, int ncols, int ny, int ksx, int ksy, int tall, int bw) {
+    const int64_t tables = rcl_table_bytes(sw, ny, ksx, ksy);
+    if (!tall) return tables + pl_lds_bytes(rows, sw, ncols);
+    return tables + pl_mid_bytes(rows, pl_pitch(bw)) + pl_mid_bytes(ny, pl_pitch(bw)) + pl_lds_bytes(ny, sw, ncols);
 }
 // ... from the box and the output size alone: the bounds of resample_list.h on the rows and columns the tables can touch
-static inline int64_t rcl_unit_lds(int bh, int bw, int sh, int sw, int ny, int ksx, int ksy) {
+// (always inlined: the layout's loop over an entry's units then keeps what does not depend on ny out of the loop)
+__attribute__((always_inline)) static inline int64_t rcl_unit_lds(int bh, int bw, int sh, int sw, int ny, int ksx, int ksy) {
     return rcl_lds_bytes(pl_rows_bound(ny, bh, sh, ksy), sw, pl_rows_bound(sw, bw, sw, ksx), ny, ksx, ksy,
                          rcl_tall(bh, bw, sh), bw);
 }
 
-// Output rows per unit: the step rule of pl_unit_rows (preprocess_list.hip) — the smallest of half, three quarters and
-// the whole budget that holds one row, and within it as many rows as fit (0: not even one row fits)
+// Output rows per unit (pl_unit_rows, resample_list.h)
 static int rcl_unit_rows(int bh, int bw, int sh, int sw, int ksx, int ksy, int lds_budget) {
-    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
-        for (int ny = sh < RCL_UNIT_ROWS ? sh : RCL_UNIT_ROWS; ny >= 1; --ny)
-            if (rcl_unit_lds(bh, bw, sh, sw, ny, ksx, ksy) <= limit) return ny;
-    return 0;
+    return pl_unit_rows(std::min(sh, RCL_UNIT_ROWS), lds_budget,
+                        [&](int ny) { return rcl_unit_lds(bh, bw, sh, sw, ny, ksx, ksy); });
 }
 
 // One row of precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter: build_coeffs (resample_coeffs.h) for
@@ -116,47 +113,34 @@ __global__ __launch_bounds__(PL_THREADS) void resized_crop_list_kernel(const u8*
     // source rows and columns of the box the unit touches (the bounds are monotone), laid out inside the launch's LDS
     int r_lo = by[0], nrows = by[2 * (u.ny - 1)] + by[2 * (u.ny - 1) + 1] - r_lo;
     const int col0 = bx[0], ncols = bx[2 * (sw - 1)] + bx[2 * (sw - 1) + 1] - col0;
-    const int pitch = ((sw + 3) >> 2) * 12;
-    const int tables = (4 * (sw * (2 + e.ksx) + u.ny * (2 + e.ksy)) + 15) & ~15;
-    const int staged = PL_STAGE_ROWS * ((ncols * 3 + 3 + 3) & ~3);
+    const int pitch = pl_pitch(sw);
     if (nrows < 1 || ncols < 1) return;
+    // (the host's bounds cover the tables: never taken)
+    if (rcl_lds_bytes(nrows, sw, ncols, u.ny, e.ksx, e.ksy, e.tall, e.bw) > lds_bytes) return;
     const u8* box = (const u8*)e.data + (int64_t)e.top * e.row_stride + (int64_t)e.left * 3;
-    u8* mid = rcl_lds + tables;
+    u8* mid = rcl_lds + (int)rcl_table_bytes(sw, u.ny, e.ksx, e.ksy);
     if (!e.tall) {
-        const int64_t need = tables + (((int64_t)nrows * pitch + 15) & ~(int64_t)15) + staged;
-        if (need > lds_bytes) return;                            // (the host's bounds cover the tables: never taken)
-        u8* stage = mid + ((nrows * pitch + 15) & ~15);
+        u8* stage = mid + (int)pl_mid_bytes(nrows, pitch);
         pl_horizontal_pass(box, e.row_stride, col0, ncols, r_lo, r_lo + nrows, bx, kx, e.ksx, sw, mid, pitch, stage, tid);
     } else {
         // Pillow's order for this shape: the vertical pass of the box's own columns first (source rows -> LDS as they
-        // are, then the shared tap loop), the horizontal pass on its result; the rows that leave it are final, which
+        // are, then the shared row loop), the horizontal pass on its result; the rows that leave it are final, which
         // the common tail below reads through a one-tap table (coefficient 1 << 22: the byte itself)
-        const int wpitch = ((e.bw + 3) >> 2) * 12, wbytes = e.bw * 3;
-        const int64_t need = tables + (((int64_t)nrows * wpitch + 15) & ~(int64_t)15) + ((u.ny * wpitch + 15) & ~15) +
-                             ((u.ny * pitch + 15) & ~15) + staged;
-        if (need > lds_bytes) return;
-        u8* rows = rcl_lds + tables;
-        u8* vmid = rows + ((nrows * wpitch + 15) & ~15);
-        mid = vmid + ((u.ny * wpitch + 15) & ~15);
-        u8* stage = mid + ((u.ny * pitch + 15) & ~15);
+        const int wpitch = pl_pitch(e.bw), wbytes = e.bw * 3;
+        u8* rows = mid;
+        u8* vmid = rows + (int)pl_mid_bytes(nrows, wpitch);
+        mid = vmid + (int)pl_mid_bytes(u.ny, wpitch);
+        u8* stage = mid + (int)pl_mid_bytes(u.ny, pitch);
         for (int r = tid / 64; r < nrows; r += PL_THREADS / 64) {
             const u8* g = box + (int64_t)(r_lo + r) * e.row_stride;
             for (int b = tid & 63; b < wpitch; b += 64) rows[r * wpitch + b] = b < wbytes ? g[b] : (u8)0;
         }
         __syncthreads();
-        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
-        for (int yy = wv; yy < u.ny; yy += PL_THREADS / 64) {
-            const int cnt = by[2 * yy + 1];
-            const int ymin = min(max(by[2 * yy] - r_lo, 0), max(nrows - cnt, 0));
-            const int* k = ky + yy * e.ksy;
-            const int kv = ln < cnt ? k[ln] : 0;
-            for (int q = ln; q < (wpitch / 12); q += 64) {
-                int acc[12];
-                pl_vertical_taps(rows, wpitch, ymin, cnt, kv, k, q, acc);
+        pl_vertical_pass(rows, wpitch, r_lo, nrows, by, ky, e.ksy, 0, u.ny, e.bw, tid,
+                         [&](int yy, int q, const int (&acc)[12]) __attribute__((always_inline)) {
 #pragma unroll
-                for (int b = 0; b < 12; ++b) vmid[yy * wpitch + q * 12 + b] = clip8(acc[b]);
-            }
-        }
+                             for (int b = 0; b < 12; ++b) vmid[yy * wpitch + q * 12 + b] = clip8(acc[b]);
+                         });
         __syncthreads();
         for (int yy = tid; yy < u.ny; yy += PL_THREADS) {
             by[2 * yy] = yy; by[2 * yy + 1] = 1; ky[yy * e.ksy] = 1 << PRECISION_BITS;
@@ -165,60 +149,14 @@ __global__ __launch_bounds__(PL_THREADS) void resized_crop_list_kernel(const u8*
         r_lo = 0; nrows = u.ny;
     }
 
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nq = (sw + 3) >> 2;
+    // the flip: a mirrored store column
     const int64_t plane = (int64_t)sh * sw;
-    for (int yy = wave; yy < u.ny; yy += PL_THREADS / 64) {
-        const int y = u.y0 + yy;
-        const int cnt = by[2 * yy + 1];
-        const int ymin = min(max(by[2 * yy] - r_lo, 0), max(nrows - cnt, 0));
-        const int* k = ky + yy * e.ksy;
-        const int kv = lane < cnt ? k[lane] : 0;
-        for (int q = lane; q < nq; q += 64) {
-            int acc[12];
-            pl_vertical_taps(mid, pitch, ymin, cnt, kv, k, q, acc);
-            const int npx = min(4, sw - 4 * q);
-            // store columns: pixel j of the quad is output column 4 q + j, mirrored sw - 1 - (4 q + j) under the flip
-            if (F32) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = to_tensor_value(clip8(acc[3 * j + c]), a, c);
-                    float* row = (float*)out + ((int64_t)u.entry * 3 + c) * plane + (int64_t)y * sw;
-                    if (VEC) {
-                        if (e.flip) *(float4*)(row + sw - 4 - 4 * q) = make_float4(v[3], v[2], v[1], v[0]);
-                        else *(float4*)(row + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (j < npx) row[e.flip ? sw - 1 - (4 * q + j) : 4 * q + j] = v[j];
-                    }
-                }
-            } else {
-                u8* row = (u8*)out + ((int64_t)u.entry * plane + (int64_t)y * sw) * 3;
-                if (VEC) {
-                    u32 d[3] = {0u, 0u, 0u};
-#pragma unroll
-                    for (int b = 0; b < 12; ++b) {
-                        const int j = e.flip ? 3 - b / 3 : b / 3;
-                        d[b >> 2] |= (u32)clip8(acc[3 * j + b % 3]) << (8 * (b & 3));
-                    }
-                    u32* dp = (u32*)(row + (e.flip ? sw - 4 - 4 * q : 4 * q) * 3);
-                    dp[0] = d[0]; dp[1] = d[1]; dp[2] = d[2];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (j < npx) {
-                            u8* dp = row + (e.flip ? sw - 1 - (4 * q + j) : 4 * q + j) * 3;
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) dp[c] = clip8(acc[3 * j + c]);
-                        }
-                    }
-                }
-            }
-        }
-    }
+    pl_vertical_pass(mid, pitch, r_lo, nrows, by, ky, e.ksy, 0, u.ny, sw, tid,
+                     [&](int yy, int q, const int (&acc)[12]) __attribute__((always_inline)) {
+                         const int64_t px = (int64_t)(u.y0 + yy) * sw;           // the row's first pixel in its plane
+                         if (F32) pl_store_f32<VEC>(acc, (float*)out + (int64_t)u.entry * 3 * plane + px, plane, sw, q, e.flip, a);
+                         else pl_store_u8(acc, (u8*)out + ((int64_t)u.entry * plane + px) * 3, sw, q, e.flip, VEC);
+                     });
 }
 
 // The records bound every address the kernel forms: check them against their frames, the block and the launch's LDS.
@@ -230,10 +168,10 @@ int resized_crop_list_check(const void* block_host, size_t block_bytes) {
     if (hd.n_entries < 0 || hd.n_units < 0 || hd.sh < 1 || hd.sh > 32767 || hd.sw < 1 || hd.sw > 32767 || hd.lds_bytes < 0 ||
         hd.lds_bytes > RCL_MAX_LDS)
         return IMGXF_ERR_ARG;
-    if (hd.entries_off != (int)sizeof(imgxf_resized_crop_header) ||
-        hd.units_off != hd.entries_off + (int64_t)hd.n_entries * (int64_t)sizeof(imgxf_resized_crop_entry) ||
-        hd.total_bytes < hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_resized_crop_unit) ||
-        (size_t)hd.total_bytes > block_bytes)
+    if (!pl_check_sections(sizeof(imgxf_resized_crop_header), hd.n_entries, sizeof(imgxf_resized_crop_entry), hd.n_units,
+                           sizeof(imgxf_resized_crop_unit), hd.entries_off, hd.units_off,
+                           hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_resized_crop_unit), hd.total_bytes) ||
+        (size_t)hd.total_bytes > block_bytes)                     // (no tables: the units end the block)
         return IMGXF_ERR_ARG;
     const imgxf_resized_crop_entry* entries = (const imgxf_resized_crop_entry*)(hb + hd.entries_off);
     const imgxf_resized_crop_unit* units = (const imgxf_resized_crop_unit*)(hb + hd.units_off);

@@ -1,5 +1,5 @@
-// ToTensor (+ Normalize) of one uint8 sample, shared by to_tensor_kernel (tensor_maps.hip) and
-// preprocess_list_kernel (preprocess_list.hip) so that this arithmetic keeps one statement.
+// ToTensor (+ Normalize) of one uint8 sample, shared by to_tensor_kernel (tensor_maps.hip) and the list
+// kernels' float32 epilogue (pl_store_f32, resample_list.h) so that this arithmetic keeps one statement.
 #pragma once
 #include "imgxf_common.h"
 

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _ffi as F
+from . import _list_block
 from . import batched
 
 # One workgroup of the scale kernel keeps, in LDS, the horizontally filtered source rows its output rows touch (uint8,
@@ -64,23 +65,17 @@ def layout(geometry, params, lds_bytes: int = DRIVER_LIST_LDS_BYTES, pinned: boo
     if len(params) != n:
         raise ValueError("one parameter row per entry")
     out_off, out_hw, status = np.empty(n, np.int64), np.empty((n, 2), np.int32), np.empty(n, np.int32)
-    need, out_bytes, lds = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int32(0)
-    gp = geometry.ctypes.data if n else None
-    pp = params.ctypes.data if n else None
-    F.call("imgxf_driver_list_layout_host", gp, pp, n, int(lds_bytes), None, 0, ctypes.byref(need), None, None, None, None, None)
-    owner = torch.empty(need.value, dtype=torch.uint8, pin_memory=True) if pinned else None
-    block = owner.numpy() if pinned else np.empty(need.value, np.uint8)
-    F.call("imgxf_driver_list_layout_host", gp, pp, n, int(lds_bytes), block.ctypes.data, block.nbytes, ctypes.byref(need),
-           out_off.ctypes.data, out_hw.ctypes.data, status.ctypes.data, ctypes.byref(out_bytes), ctypes.byref(lds))
+    out_bytes, lds = ctypes.c_size_t(0), ctypes.c_int32(0)
+    tail = (out_off.ctypes.data, out_hw.ctypes.data, status.ctypes.data, ctypes.byref(out_bytes), ctypes.byref(lds))
+    args = (params.ctypes.data if n else None, n, int(lds_bytes))
+    block, owner = _list_block.layout("imgxf_driver_list_layout_host", geometry, args, pinned, tail)
     return {"block": block, "owner": owner, "out_off": out_off, "out_hw": out_hw, "status": status,
             "out_bytes": int(out_bytes.value), "lds_bytes": int(lds.value)}
 
 
 def block_views(block: np.ndarray):
     """(header, entry records, work units) of a `layout` block as structured views into it."""
-    hd = block[:_HEADER.itemsize].view(_HEADER)[0]
-    eo, uo, n, nu = int(hd["entries_off"]), int(hd["units_off"]), int(hd["n_entries"]), int(hd["n_units"])
-    return hd, block[eo:eo + n * _ENTRY.itemsize].view(_ENTRY), block[uo:uo + nu * _UNIT.itemsize].view(_UNIT)
+    return _list_block.views(block, _HEADER, _ENTRY, _UNIT, "entries")
 
 
 def entry_params(transform_type: str, args):
@@ -144,14 +139,13 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
             ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
             if ok:
                 h, w = int(t.shape[0]), int(t.shape[1])
-                st = t.stride()
-                if h and w and (st[2] != 1 or (w > 1 and st[1] != 3) or (h > 1 and st[0] < 3 * w)):
+                if h and w and not _list_block.rows_dense(t):
                     t = t.contiguous()                  # pixels of a row and their channels must be dense
                 if device is None:
                     device = t.device
                 elif t.device != device:
                     raise ValueError("apply_list expects all frames on one device")
-                view = (t, h, w, 3, t.data_ptr(), t.stride(0) if h > 1 else 3 * w)
+                view = (t, h, w, 3, *_list_block.address(t))
             else:
                 view = (None, 0, 0, 0, 0, 0)
             views[fi] = view

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _ffi as F
+from . import _list_block
 
 _BRIGHTNESS, _CONTRAST, _NOISE = 0, 1, 2
 
@@ -156,23 +157,14 @@ def preprocess_geometry(sizes, resize: int, crop: int) -> np.ndarray:
 def preprocess_layout(geometry: np.ndarray, crop: int, pinned: bool = False):
     """The host block of `preprocess_list` (imgxf_preprocess_list_layout_host) for int32 [N, 6] geometry rows as a uint8
     array.  `pinned=True`: (array, the pinned uint8 tensor that owns its memory) instead.  No device is touched."""
-    geometry = np.ascontiguousarray(geometry, np.int32)
-    need = ctypes.c_size_t(0)
-    gp = geometry.ctypes.data if geometry.size else (ctypes.c_int32 * 1)()
-    F.call("imgxf_preprocess_list_layout_host", gp, len(geometry), crop, PREPROCESS_LIST_LDS_BYTES, None, 0,
-           ctypes.byref(need))
-    owner = torch.empty(need.value, dtype=torch.uint8, pin_memory=True) if pinned else None
-    block = owner.numpy() if pinned else np.empty(need.value, np.uint8)
-    F.call("imgxf_preprocess_list_layout_host", gp, len(geometry), crop, PREPROCESS_LIST_LDS_BYTES, block.ctypes.data,
-           block.nbytes, ctypes.byref(need))
-    return (block, owner) if pinned else block
+    args = (len(geometry), crop, PREPROCESS_LIST_LDS_BYTES)
+    made = _list_block.layout("imgxf_preprocess_list_layout_host", geometry, args, pinned)
+    return made if pinned else made[0]
 
 
 def preprocess_block_views(block: np.ndarray):
     """(header, frame records, work units) of a `preprocess_layout` block as structured views into it."""
-    hd = block[:_PL_HEADER.itemsize].view(_PL_HEADER)[0]
-    fo, uo, n, nu = int(hd["frames_off"]), int(hd["units_off"]), int(hd["n_frames"]), int(hd["n_units"])
-    return (hd, block[fo:fo + n * _PL_FRAME.itemsize].view(_PL_FRAME), block[uo:uo + nu * _PL_UNIT.itemsize].view(_PL_UNIT))
+    return _list_block.views(block, _PL_HEADER, _PL_FRAME, _PL_UNIT, "frames")
 
 
 def preprocess_list(frames, resize: int = 256, crop: int = 224, mean=None, std=None, out=None) -> torch.Tensor:
@@ -193,19 +185,7 @@ def preprocess_list(frames, resize: int = 256, crop: int = 224, mean=None, std=N
         raise ValueError("mean / std need 3 entries")
     if crop < 1 or crop > resize:
         raise ValueError("CenterCrop larger than the resized image (torchvision pads; not needed by the reference)")
-    for t in frames:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
-            raise TypeError("preprocess_list expects uint8 tensors on the HIP device")
-    for t in frames:                                             # the layouts the kernel reads, as `_ffi.view_of` states them
-        shape, stride = t.shape, t.stride()
-        if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
-            raise ValueError(f"preprocess_list expects RGB [H,W,3] frames with H, W > 0, got {tuple(shape)}")
-        if shape[0] > 32767 or shape[1] > 32767:
-            raise ValueError(f"preprocess_list takes frames up to 32767 x 32767 (as every imgxf view), got {tuple(shape)}")
-        if stride[2] != 1 or (shape[1] > 1 and stride[1] != 3) or (shape[0] > 1 and stride[0] < 3 * shape[1]):
-            raise ValueError("pixels of a row and their channels must be contiguous (interleaved HWC layout)")
-        if t.device != frames[0].device:
-            raise ValueError("preprocess_list expects all frames on one device")
+    _list_block.check_frames(frames, "preprocess_list")
     n = len(frames)
     device = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
     if out is not None:
@@ -229,8 +209,7 @@ def _stage_list(frames, resize: int, crop: int, device):
     geometry = preprocess_geometry([(t.shape[0], t.shape[1]) for t in frames], resize, crop)
     block, staged = preprocess_layout(geometry, crop, pinned=True)
     hd, rec, _ = preprocess_block_views(block)
-    rec["data"] = [t.data_ptr() for t in frames]
-    rec["row_stride"] = [t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1] for t in frames]
+    rec["data"], rec["row_stride"] = _list_block.addresses(frames)
     if not hd["n_units"]:
         return block, None
     with torch.cuda.device(device):
@@ -273,24 +252,14 @@ def resized_crop_layout(geometry: np.ndarray, size, pinned: bool = False):
     """The host block of `resized_crop_list` (imgxf_resized_crop_list_layout_host) for int32 [K, 7] geometry rows
     (h, w, top, left, box height, box width, flip) and the output size (Sh, Sw), as a uint8 array.  `pinned=True`:
     (array, the pinned uint8 tensor that owns its memory) instead.  No device is touched."""
-    geometry = np.ascontiguousarray(geometry, np.int32)
-    sh, sw = size
-    need = ctypes.c_size_t(0)
-    gp = geometry.ctypes.data if geometry.size else (ctypes.c_int32 * 1)()
-    F.call("imgxf_resized_crop_list_layout_host", gp, len(geometry), sh, sw, RESIZED_CROP_LIST_LDS_BYTES, None, 0,
-           ctypes.byref(need))
-    owner = torch.empty(need.value, dtype=torch.uint8, pin_memory=True) if pinned else None
-    block = owner.numpy() if pinned else np.empty(need.value, np.uint8)
-    F.call("imgxf_resized_crop_list_layout_host", gp, len(geometry), sh, sw, RESIZED_CROP_LIST_LDS_BYTES,
-           block.ctypes.data, block.nbytes, ctypes.byref(need))
-    return (block, owner) if pinned else block
+    args = (len(geometry), *size, RESIZED_CROP_LIST_LDS_BYTES)
+    made = _list_block.layout("imgxf_resized_crop_list_layout_host", geometry, args, pinned)
+    return made if pinned else made[0]
 
 
 def resized_crop_block_views(block: np.ndarray):
     """(header, entry records, work units) of a `resized_crop_layout` block as structured views into it."""
-    hd = block[:_RCL_HEADER.itemsize].view(_RCL_HEADER)[0]
-    eo, uo, n, nu = int(hd["entries_off"]), int(hd["units_off"]), int(hd["n_entries"]), int(hd["n_units"])
-    return (hd, block[eo:eo + n * _RCL_ENTRY.itemsize].view(_RCL_ENTRY), block[uo:uo + nu * _RCL_UNIT.itemsize].view(_RCL_UNIT))
+    return _list_block.views(block, _RCL_HEADER, _RCL_ENTRY, _RCL_UNIT, "entries")
 
 
 def _crop_size(size):
@@ -355,19 +324,7 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
     if dtype == torch.uint8 and mean is not None:
         raise ValueError("mean / std need dtype=torch.float32 (uint8 output is not normalised)")
     sh, sw = _crop_size(size)
-    for t in frames:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
-            raise TypeError("resized_crop_list expects uint8 tensors on the HIP device")
-    for t in frames:                                             # the layouts the kernel reads, as `preprocess_list` states them
-        shape, stride = t.shape, t.stride()
-        if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
-            raise ValueError(f"resized_crop_list expects RGB [H,W,3] frames with H, W > 0, got {tuple(shape)}")
-        if shape[0] > 32767 or shape[1] > 32767:
-            raise ValueError(f"resized_crop_list takes frames up to 32767 x 32767 (as every imgxf view), got {tuple(shape)}")
-        if stride[2] != 1 or (shape[1] > 1 and stride[1] != 3) or (shape[0] > 1 and stride[0] < 3 * shape[1]):
-            raise ValueError("pixels of a row and their channels must be contiguous (interleaved HWC layout)")
-        if t.device != frames[0].device:
-            raise ValueError("resized_crop_list expects all frames on one device")
+    _list_block.check_frames(frames, "resized_crop_list")
     boxes = _int_array(boxes, "boxes", 4)
     k = len(boxes)
     index = np.arange(len(frames), dtype=np.int64) if index is None else _int_array(index, "index")
@@ -408,8 +365,7 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
     geometry[:, :2], geometry[:, 2:6], geometry[:, 6] = hw, boxes, flips
     block, staged = resized_crop_layout(geometry, (sh, sw), pinned=True)
     hd, rec, _ = resized_crop_block_views(block)
-    ptr = np.array([t.data_ptr() for t in frames], np.uint64)
-    stride = np.array([t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1] for t in frames], np.int64)
+    ptr, stride = _list_block.addresses(frames)
     rec["data"], rec["row_stride"] = ptr[index], stride[index]
     if hd["n_units"]:
         with torch.cuda.device(device):

@@ -102,6 +102,55 @@ def test_host_entry_point_argument_errors():
     assert _ffi.lib.imgxf_preprocess_list_f32(buf.ctypes.data, None, None, None, None, None) == _ffi.ERR_NULL
 
 
+def test_launcher_rejects_tampered_tables_without_a_device():
+    """The launcher checks every table its kernel reads through the band engine before it needs a device: a null
+    `block_dev` is only reported (ERR_NULL) for a block whose records and tables pass."""
+    from imagetransformations_amd import _ffi
+    tm = _tm()
+    fn = _ffi.lib.imgxf_preprocess_list_f32
+    crop = 32
+    good = tm.preprocess_layout(tm.preprocess_geometry([(375, 500), (61, 97), (375, 500)], 40, crop), crop)
+    hd, rec, units = tm.preprocess_block_views(good)
+    rec["data"], rec["row_stride"] = 4096, [1500, 300, 1500]
+    assert np.all(rec["unit_rows"] > 0) and len(units) >= 3
+
+    def launch(block):
+        return fn(block.ctypes.data, None, None, None, None, None)
+
+    assert launch(good) == _ffi.ERR_NULL                       # every record and table passes; the device block is missing
+    r = rec[0]
+    t0 = int(hd["tables_off"]) // 4
+    bx, kx, by = int(r["bounds_x"]), int(r["coeffs_x"]), int(r["bounds_y"])
+    ksx, col0, ncols = int(r["ksx"]), int(r["col0"]), int(r["ncols"])
+    words = good.view(np.int32)
+    last = 2 * (crop - 1)
+    assert words[bx] == col0 and words[bx + last] + words[bx + last + 1] == col0 + ncols and col0 > 0
+    assert words[by + 20] > words[by + 18]                     # (rows 9 and 10 start apart: their swap below is a change)
+
+    def tampered_word(index, value):
+        block = good.copy()
+        block.view(np.int32)[index] = value
+        return launch(block)
+
+    def tampered_field(i, field, value):
+        block = good.copy()
+        tm.preprocess_block_views(block)[1][i][field] = value
+        return launch(block)
+
+    assert tampered_word(bx, col0 - 1) == _ffi.ERR_ARG         # a column start below col0
+    assert tampered_word(bx + 1, ksx + 1) == _ffi.ERR_ARG      # a count above ks
+    assert tampered_word(by + 1, int(r["ksy"]) + 1) == _ffi.ERR_ARG
+    assert tampered_word(bx + last, int(words[bx + last]) + 1) == _ffi.ERR_ARG     # a tap past col0 + ncols
+    block = good.copy()                                        # a row start that decreases, every window still inside
+    w = block.view(np.int32)
+    w[by + 20], w[by + 18] = words[by + 18], words[by + 20]
+    assert launch(block) == _ffi.ERR_ARG
+    for field in ("bounds_x", "coeffs_x", "bounds_y", "coeffs_y"):
+        assert tampered_field(0, field, t0 - 1) == _ffi.ERR_ARG, field               # a table offset before tables_off
+        assert tampered_field(2, field, int(hd["total_bytes"]) // 4 - 1) == _ffi.ERR_ARG, field    # ... past the block
+    assert tampered_field(1, "unit_rows", 0) == _ffi.ERR_ARG   # (a unit of a frame that has none: refused as before)
+
+
 def test_geometry_is_torchvisions_rule():
     tm = _tm()
     assert tm.preprocess_geometry([(375, 500), (500, 375), (256, 256)], 256, 224).tolist() == [
