@@ -8,24 +8,14 @@
 // rotated strip that stays in the XCD's L2 while neighbouring patches reuse it.
 #include "imgxf_common.h"
 #include "pixel_ops.h"
+#include "affine_route.h"     // AffineParams, TileList, the kernels' limits, and which kernel runs when (plan_affine)
 #include <math.h>
 #include <algorithm>
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace imgxf {
-
-struct AffineParams {
-    double m[6];
-    int fx[6];       // 16.16 fixed-point matrix for NEAREST (affine_fixed)
-    int64_t q0, q3;  // m0, m3 in 2^-40 fixed point (per-pixel x increments of the BILINEAR fast path)
-    int64_t q1, q4;  // m1, m4 likewise (per-row increments, LDS-staged path)
-    int64_t x00, y00; // xin-.5, yin-.5 of output pixel (0,0) in 2^-40 fixed point (Pillow's fp64 value)
-    u32 ntx_magic;    // ceil(2^32 / ntx) of the LDS kernels' tile grid
-    int sx[4], sy[4]; // round(k*q0 / 2^16), round(k*q3 / 2^16): 8.24 steps to pixel k of a lane (LDS fast loop)
-    u8 fill[4];
-    int strip_w;      // NEAREST DMA kernel: > 0 = every XCD owns a vertical strip of this many tile columns
-};
 
 // ---- arithmetic policies -------------------------------------------------------------
 // (PreciseArith, the fp64 policy that is bit-identical to Pillow, and cubic<A> are in pixel_ops.h)
@@ -793,9 +783,7 @@ __global__ __launch_bounds__(256) void affine_bilinear_lds_interior_kernel(View 
 }
 
 // The 32x64 tiles the interior pass skipped, as 32x32 tiles: workgroup 2e + c is half c of list entry e
-constexpr int BILINEAR_LIST_MAX = 896;
-struct TileList { int n; u32 idx[BILINEAR_LIST_MAX]; };
-
+// (TileList, at most BILINEAR_LIST_MAX entries: affine_route.h)
 template <bool PRECISE, int PITCH, bool DBG, int BHT>
 __global__ __launch_bounds__(256) void affine_bilinear_lds_list_kernel(View s, View d, AffineParams P, View dbg,
                                                                        int ntx, TileList list) {
@@ -1220,146 +1208,116 @@ __global__ __launch_bounds__(256) void shear_bicubic_kernel(View s, View d, Affi
     }
 }
 
-template <int C, class A>
-static int launch_affine_filter(int filter, const View& s, const View& d, const AffineParams& P,
-                                const View& dbg, hipStream_t st) {
-    dim3 block(64, 4), grid((unsigned)((d.w + 255) / 256), (unsigned)((d.h + 3) / 4), (unsigned)d.n);
-    switch (filter) {
-        case IMGXF_FILTER_NEAREST:
-            hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_NEAREST, A>), grid, block, 0, st, s, d, P, dbg);
-            break;
-        case IMGXF_FILTER_BILINEAR:
-            hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_BILINEAR, A>), grid, block, 0, st, s, d, P, dbg);
-            break;
-        case IMGXF_FILTER_BICUBIC: {
-            const bool honly = P.m[3] == 0.0 && P.m[4] == 1.0 && P.m[5] == floor(P.m[5]) && fabs(P.m[5]) < 1.0e9;
-            if (honly) hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_BICUBIC, A, true>), grid, block, 0, st, s, d, P, dbg);
-            else hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_BICUBIC, A>), grid, block, 0, st, s, d, P, dbg);
-            break;
-        }
-        default: return IMGXF_ERR_ARG;
-    }
-    return launch_status();
-}
-
 } // namespace imgxf
 #include "affine_mf.inc"
 #include "affine_wq.inc"
 namespace imgxf {
 
-// Tall interior tiles: `affine_bilinear_lds_interior_kernel<.., BHT>` over every 32 x BHT tile (the
-// ones that are not interior leave at once) and `affine_bilinear_lds_list_kernel` over the host's
-// list of those that are not.  Returns BILINEAR_TALL_NOT_TAKEN when the taller tile's source box
-// does not fit PITCH x MAXROWS of LDS or the list does not fit the launch arguments.
-constexpr int BILINEAR_TALL_NOT_TAKEN = 1 << 30;
+// ---- launching a plan (plan_affine, affine_route.h) ------------------------------------------------------------------
+// Run-time flags and integers become template arguments here and nowhere else: f gets std::true_type or std::false_type,
+// or the std::integral_constant of the one value among Vs that v equals (false when there is none).
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type()); else f(std::false_type());
+}
+template <class F>
+static void with_bools(bool a, bool b, F&& f) {
+    with_bool(a, [&](auto A) { with_bool(b, [&](auto B) { f(A, B); }); });
+}
+template <int... Vs, class F>
+static bool with_int(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>()), true) : false) || ...);
+}
+template <bool PRECISE> using Arith = std::conditional_t<PRECISE, PreciseArith, FastArith>;
 
-template <int BHT, int PITCH, int MAXROWS>
-static int launch_bilinear_tall(const View& s, const View& d, const AffineParams& Pin, const View& dbg, const double* m,
-                                int bw, int bh, int ntx, bool pr, hipStream_t st) {
-    const AffineParams& P = Pin;
-    const int bwt = (int)ceil(fabs(m[0]) * 31 + fabs(m[1]) * (BHT - 1)) + 4;
-    const int bht = (int)ceil(fabs(m[3]) * 31 + fabs(m[4]) * (BHT - 1)) + 4;
-    const int ntyt = (d.h + BHT - 1) / BHT;
-    if (bwt > PITCH || bht > MAXROWS || bw > PITCH || (int64_t)ntx * ntyt * ntx >= ((int64_t)1 << 32))
-        return BILINEAR_TALL_NOT_TAKEN;
-    // batches: every tile loops over `fpb` frames per workgroup with the per-pixel geometry held in
-    // registers (affine_mf.inc); single frames and the fp32 side output keep the per-frame kernels
-    const bool want_f32 = dbg.p != nullptr;
-    const int fpb = knob_int(K_AFFINE_FPB, 16);
-    const int afpb = fpb;
-    const bool mf = BHT == MF_TILE_H && !want_f32 && afpb >= 2 && d.n >= 2 && bht <= 64 &&
-                    (int64_t)d.h * d.rs < ((int64_t)1 << 32);
-    // LDS-DMA staging of packed rows needs 16-byte aligned source rows and a box of <= 52 x 52 pixels; it
-    // also takes the border tiles (no list pass)
-    const int nch = (bwt * 3 + 15 + 15) / 16;                  // 16-byte chunks per packed box row (any alignment of its start)
-    const bool dma = mf && !knob_set(K_AFFINE_NO_DMA) && bht <= 52 && bwt <= 52 && 52 * nch <= 768 &&
-                     ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs) & 15) == 0 && s.w * 3 >= 16 &&
-                     (int64_t)s.h * s.rs < ((int64_t)1 << 32);
-    // round 3: wave-private boxes + whole-line stores (affine_wq.inc) when a 32 x 16 block's box fits 28 x 27 pixels
-    // and both images are 16-byte aligned with 16-byte multiples as rows
-    if (mf && !knob_set(K_AFFINE_NO_DMA)) {
-        const int bwq = (int)ceil(fabs(m[0]) * 31 + fabs(m[1]) * 15) + 4, bhq = (int)ceil(fabs(m[3]) * 31 + fabs(m[4]) * 15) + 4;
-        const int nchq = (bwq * 3 + 15 + 15) / 16;
-        const int ntxq = (d.w + 127) / 128, ntyq = (d.h + 15) / 16;
-        const bool aligned = ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0 &&
-                             (d.w * 3) % 16 == 0 && s.w * 3 >= 16;
-        if (aligned && bwq <= WQ_PITCH && bhq * nchq <= WQ_MAXCH && bhq * (WQ_PITCH / 4) <= 192 &&
-            (int64_t)s.h * s.rs < ((int64_t)1 << 32) && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
-            AffineParams Pq = Pin;
-            Pq.strip_w = 0;
-            // 24 frames per workgroup: the tile set-up (~1500 instructions) is amortised further than at 16, the launch still
-            // has > 20 000 workgroups to drain evenly (sweep 8 ... 128 on 128 4K / 512 1080p / 32 4K frames:
-            // profiles/r03_experiments/affine_fpb_sweep.txt; 24 is the fastest or within 0.5 % everywhere)
-            const int fpbq = knob_int(K_AFFINE_FPB, 24);
-            dim3 grid((unsigned)(ntxq * ntyq), (unsigned)((d.n + fpbq - 1) / fpbq));
-            // vertical strips of tile columns per XCD from 8 columns on: vertically adjacent tiles (whose boxes overlap 2x in y)
-            // then sit a few workgroups apart on ONE L2 — at 1080p (15 columns) row-major ranges fetched every source byte twice
-            if (ntxq >= 8) { Pq.strip_w = (ntxq + 7) / 8; grid.x = (unsigned)(8 * Pq.strip_w * ntyq); }
-            const size_t lds = (size_t)4 * ((size_t)bhq * WQ_PITCH * 4 + 2 * ((size_t)bhq * nchq * 16 + 64)) + 2 * 16 * 384;
-            if (pr) hipLaunchKernelGGL((affine_bilinear_wq_kernel<true>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq);
-            else hipLaunchKernelGGL((affine_bilinear_wq_kernel<false>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq);
-            return launch_status();
-        }
+template <int C, class A>
+static void launch_global(const AffineLaunch& L, const View& s, const View& d, const AffineParams& P, const View& dbg, hipStream_t st) {
+    switch (L.filter) {
+        case IMGXF_FILTER_NEAREST:
+            hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_NEAREST, A>), L.grid, L.block, 0, st, s, d, P, dbg);
+            break;
+        case IMGXF_FILTER_BILINEAR:
+            hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_BILINEAR, A>), L.grid, L.block, 0, st, s, d, P, dbg);
+            break;
+        default:
+            with_bool(L.honly, [&](auto H) {
+                hipLaunchKernelGGL((affine_kernel<C, IMGXF_FILTER_BICUBIC, A, H()>), L.grid, L.block, 0, st, s, d, P, dbg);
+            });
     }
-    if (dma) {
-        dim3 grid((unsigned)(ntx * ntyt), (unsigned)((d.n + afpb - 1) / afpb));
-        // RGBX pitch 56: fewest bank conflicts of the multiples of 4 (simulated for 30 deg / 1.5x: 4.0 vs 5.8 LDS cycles per gather read at 52)
-        AffineParams Ps = Pin;
-        if (ntx >= 16) { Ps.strip_w = (ntx + 7) / 8; grid.x = (unsigned)(8 * Ps.strip_w * ntyt); }
-        const size_t lds = (size_t)52 * 56 * 4 + 2 * ((size_t)52 * nch * 16 + 64);      // RGBX image + two packed-row buffers
-        if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, 56, 13, true>), grid, dim3(256), lds, st, s, d, Ps, ntx, ntyt, fpb, nch);
-        else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, 56, 13, true>), grid, dim3(256), lds, st, s, d, Ps, ntx, ntyt, fpb, nch);
-        return launch_status();
+}
+
+static int launch_one(const AffineLaunch& L, const View& s, const View& d, const AffineParams& P, const View& dbg,
+                      const TileList& list, hipStream_t st) {
+    const dim3 g = L.grid, b = L.block;
+    const size_t lds = L.lds;
+    bool known = true;
+    switch (L.family) {
+        case AF_NEAREST_WQ:
+            known = with_int<1, 2, 3, 4, 5, 6, 7, 8>(L.kw, [&](auto KW) {
+                hipLaunchKernelGGL((affine_nearest_wq_kernel<KW()>), g, b, lds, st, s, d, P, L.ntx, L.nty, L.fpb, L.nch, L.bh);
+            });
+            break;
+        case AF_NEAREST_DMA:
+            if (L.tile_h == 64) hipLaunchKernelGGL((affine_nearest_dma_kernel<64, 13>), g, b, lds, st, s, d, P, L.ntx, L.nty);
+            else hipLaunchKernelGGL((affine_nearest_dma_kernel<32, 11>), g, b, lds, st, s, d, P, L.ntx, L.nty);
+            break;
+        case AF_NEAREST_LDS:
+            known = with_int<49, 65, 97>(L.pitch, [&](auto PITCH) {
+                hipLaunchKernelGGL((affine_nearest_lds_kernel<PITCH()>), g, b, lds, st, s, d, P, L.ntx, L.nty);
+            });
+            break;
+        case AF_BILINEAR_WQ:
+            with_bool(L.precise, [&](auto PR) {
+                hipLaunchKernelGGL((affine_bilinear_wq_kernel<PR()>), g, b, lds, st, s, d, P, L.ntx, L.nty, L.fpb, L.nch, L.bh);
+            });
+            break;
+        case AF_BILINEAR_MF:
+            with_bool(L.precise, [&](auto PR) {
+                if (L.dma) hipLaunchKernelGGL((affine_bilinear_mf_kernel<PR(), 56, 13, true>), g, b, lds, st, s, d, P, L.ntx, L.nty, L.fpb, L.nch);
+                else if (L.nbr == 13) hipLaunchKernelGGL((affine_bilinear_mf_kernel<PR(), TALL_PITCH, 13, false>), g, b, lds, st, s, d, P, L.ntx, L.nty, L.fpb, L.nch);
+                else hipLaunchKernelGGL((affine_bilinear_mf_kernel<PR(), TALL_PITCH, 16, false>), g, b, lds, st, s, d, P, L.ntx, L.nty, L.fpb, L.nch);
+            });
+            break;
+        case AF_BILINEAR_INTERIOR:
+            with_bools(L.precise, L.dbg, [&](auto PR, auto DBG) {
+                hipLaunchKernelGGL((affine_bilinear_lds_interior_kernel<PR(), TALL_PITCH, DBG(), MF_TILE_H>), g, b, lds, st, s, d, P, dbg, L.ntx, L.nty);
+            });
+            break;
+        case AF_BILINEAR_LIST:
+            with_bools(L.precise, L.dbg, [&](auto PR, auto DBG) {
+                hipLaunchKernelGGL((affine_bilinear_lds_list_kernel<PR(), TALL_PITCH, DBG(), MF_TILE_H>), g, b, lds, st, s, d, P, dbg, L.ntx, list);
+            });
+            break;
+        case AF_BILINEAR_LDS:
+            known = with_int<49, 65, 97>(L.pitch, [&](auto PITCH) {
+                with_bools(L.precise, L.dbg, [&](auto PR, auto DBG) {
+                    hipLaunchKernelGGL((affine_bilinear_lds_kernel<PR(), PITCH(), DBG()>), g, b, lds, st, s, d, P, dbg, L.ntx, L.nty);
+                });
+            });
+            break;
+        case AF_BILINEAR_GLOBAL:
+            known = with_int<1, 3>(L.c, [&](auto C) {
+                with_bool(L.precise, [&](auto PR) {
+                    hipLaunchKernelGGL((affine_bilinear_kernel<C(), PR(), 8, 2>), g, b, 0, st, s, d, P, dbg, L.ntx, L.nty, (int)g.x);
+                });
+            });
+            break;
+        case AF_SHEAR:
+            with_bools(L.precise, L.defer, [&](auto PR, auto DEFER) {
+                hipLaunchKernelGGL((shear_bicubic_kernel<PR(), DEFER()>), g, b, 0, st, s, d, P);
+            });
+            break;
+        case AF_SHEAR_EDGES:
+            hipLaunchKernelGGL(shear_edges_kernel, g, b, 0, st, s, d, P);
+            break;
+        case AF_GLOBAL:
+            if (L.c == 4) launch_global<4, PreciseArith>(L, s, d, P, dbg, st);       // NEAREST only: always precise
+            else known = with_int<1, 3>(L.c, [&](auto C) {
+                with_bool(L.precise, [&](auto PR) { launch_global<C(), Arith<PR()>>(L, s, d, P, dbg, st); });
+            });
+            break;
     }
-    // the kernel's interior test (bilinear_tile<.., BHT, true>) with the same integers
-    TileList list;
-    list.n = 0;
-    const int64_t ax = 31 * P.q0, bx = (BHT - 1) * P.q1, ay = 31 * P.q3, by = (BHT - 1) * P.q4;
-    const int64_t xlo_o = std::min(ax, (int64_t)0) + std::min(bx, (int64_t)0), xhi_o = std::max(ax, (int64_t)0) + std::max(bx, (int64_t)0);
-    const int64_t ylo_o = std::min(ay, (int64_t)0) + std::min(by, (int64_t)0), yhi_o = std::max(ay, (int64_t)0) + std::max(by, (int64_t)0);
-    for (int ty = 0; ty < ntyt && list.n <= BILINEAR_LIST_MAX; ++ty)
-        for (int tx = 0; tx < ntx; ++tx) {
-            const int64_t XT = P.x00 + (int64_t)(tx * 32) * P.q0 + (int64_t)(ty * BHT) * P.q1;
-            const int64_t YT = P.y00 + (int64_t)(tx * 32) * P.q3 + (int64_t)(ty * BHT) * P.q4;
-            const bool clean = (int)((XT + xlo_o) >> 40) >= 0 && (int)((YT + ylo_o) >> 40) >= 0 &&
-                               (int)((XT + xhi_o) >> 40) + 1 <= s.w - 1 && (int)((YT + yhi_o) >> 40) + 1 <= s.h - 1 &&
-                               tx * 32 + 32 <= d.w && ty * BHT + BHT <= d.h &&
-                               !((int)((XT + xhi_o) >> 40) + 1 == s.w - 1 && (int)((YT + yhi_o) >> 40) + 1 == s.h - 1);
-            if (!clean) {
-                if (list.n < BILINEAR_LIST_MAX) list.idx[list.n] = (u32)(ty * ntx + tx);
-                ++list.n;
-            }
-        }
-    if (list.n > BILINEAR_LIST_MAX) return BILINEAR_TALL_NOT_TAKEN;
-    if (list.n < ntx * ntyt && mf) {
-        const dim3 grid((unsigned)(ntx * ntyt), (unsigned)((d.n + afpb - 1) / afpb));
-        const size_t lds = (size_t)2 * PITCH * (bht <= 52 ? 52 : 64) * 4 + 16;     // all 4 * NBR rows are written
-        if (bht <= 52) {
-            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, PITCH, 13, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
-            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, PITCH, 13, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
-        } else {
-            if (pr) hipLaunchKernelGGL((affine_bilinear_mf_kernel<true, PITCH, 16, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
-            else hipLaunchKernelGGL((affine_bilinear_mf_kernel<false, PITCH, 16, false>), grid, dim3(256), lds, st, s, d, P, ntx, ntyt, fpb, 0);
-        }
-        IMGXF_CHECK(launch_status());
-    } else if (list.n < ntx * ntyt) {                // at least one interior tile
-        const dim3 grid((unsigned)(ntx * ntyt), (unsigned)d.n);
-        const size_t lds = (size_t)PITCH * bht * 4 + 16;
-        if (pr && want_f32) hipLaunchKernelGGL((affine_bilinear_lds_interior_kernel<true, PITCH, true, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, ntyt);
-        else if (pr) hipLaunchKernelGGL((affine_bilinear_lds_interior_kernel<true, PITCH, false, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, ntyt);
-        else if (want_f32) hipLaunchKernelGGL((affine_bilinear_lds_interior_kernel<false, PITCH, true, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, ntyt);
-        else hipLaunchKernelGGL((affine_bilinear_lds_interior_kernel<false, PITCH, false, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, ntyt);
-        IMGXF_CHECK(launch_status());
-    }
-    if (list.n > 0) {
-        const dim3 grid((unsigned)((BHT / 32) * list.n), (unsigned)d.n);
-        const size_t lds = (size_t)PITCH * bh * 4 + 16;
-        if (pr && want_f32) hipLaunchKernelGGL((affine_bilinear_lds_list_kernel<true, PITCH, true, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, list);
-        else if (pr) hipLaunchKernelGGL((affine_bilinear_lds_list_kernel<true, PITCH, false, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, list);
-        else if (want_f32) hipLaunchKernelGGL((affine_bilinear_lds_list_kernel<false, PITCH, true, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, list);
-        else hipLaunchKernelGGL((affine_bilinear_lds_list_kernel<false, PITCH, false, BHT>), grid, dim3(256), lds, st, s, d, P, dbg, ntx, list);
-    }
-    return launch_status();
+    return known ? IMGXF_OK : IMGXF_ERR_UNSUPPORTED;
 }
 
 int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, int filter,
@@ -1373,10 +1331,6 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
     if (filter != IMGXF_FILTER_NEAREST && src->c == 4) return IMGXF_ERR_UNSUPPORTED; // Pillow premultiplies RGBA
     if (empty_view(dst)) return IMGXF_OK;
     if (empty_view(src)) return IMGXF_ERR_SHAPE;
-    AffineParams P; memset(&P, 0, sizeof(P));
-    for (int i = 0; i < 6; ++i) P.m[i] = m[i];
-    affine_fixed_matrix(m, P.fx);
-    if (fill) for (int j = 0; j < dst->c; ++j) P.fill[j] = fill[j];
     View dbg; memset(&dbg, 0, sizeof(dbg));
     if (dbg_f32) {
         IMGXF_CHECK(check_view(dbg_f32, 4));
@@ -1384,188 +1338,17 @@ int run_affine(const imgxf_view* src, const imgxf_view* dst, const double* m, in
         dbg = make_view(dbg_f32);
     }
     const View s = make_view(src), d = make_view(dst);
+    const KnobTable& kt = knob_table();
+    const AffineKnobs knobs = {kt.set[K_AFFINE_FPB], kt.ival[K_AFFINE_FPB], kt.set[K_AFFINE_NO_DMA], kt.set[K_AFFINE_NO_LDS],
+                               kt.set[K_AFFINE_NO_SHEAR_FAST], kt.set[K_AFFINE_NO_TALL]};
+    AffinePlan plan;
+    IMGXF_CHECK(plan_affine(s, d, m, filter, precise != 0, dbg.p != nullptr, fill, knobs, plan));
     hipStream_t st = (hipStream_t)stream;
-    const bool pr = precise != 0 || filter == IMGXF_FILTER_NEAREST;
-    if (filter == IMGXF_FILTER_NEAREST && src->c == 3 && !knob_set(K_AFFINE_NO_LDS) &&
-        ((((uintptr_t)src->data) | (uintptr_t)src->row_stride | (uintptr_t)src->frame_stride) & 3) == 0) {
-        // 16.16 coordinates must not wrap 32 bits anywhere in the (tile-padded) output rectangle
-        bool nowrap = true;
-        for (int cy = 0; cy < 2; ++cy)
-            for (int cx = 0; cx < 2; ++cx) {
-                const double X = cx ? dst->w + 32 : 0, Y = cy ? dst->h + 32 : 0;
-                const double xs = (double)P.fx[2] + (double)P.fx[1] * Y + (double)P.fx[0] * X;
-                const double ys = (double)P.fx[5] + (double)P.fx[4] * Y + (double)P.fx[3] * X;
-                if (fabs(xs) > 2.0e9 || fabs(ys) > 2.0e9) nowrap = false;
-            }
-        const int bw = (int)ceil((fabs((double)P.fx[0]) * 31 + fabs((double)P.fx[1]) * 31) / 65536.0) + 3;
-        const int bh = (int)ceil((fabs((double)P.fx[3]) * 31 + fabs((double)P.fx[4]) * 31) / 65536.0) + 3;
-        const int ntx = (d.w + 31) / 32, nty = (d.h + 31) / 32;
-        if (nowrap && bw <= 97 && bh <= 100 && (int64_t)ntx * nty < 0x7fffffff && d.n <= 65535) {
-            dim3 grid((unsigned)(ntx * nty), (unsigned)d.n);
-            P.ntx_magic = (u32)((((uint64_t)1 << 32) + ntx - 1) / ntx);   // ntx, nty <= 1024: exact; 0 when ntx == 1
-            const bool no_dma = knob_set(K_AFFINE_NO_DMA);
-            // round 3: 128 x 16 tiles walked over the frames, wave-private boxes, whole-line stores (affine_wq.inc) for 16-byte
-            // aligned images whose 32 x 16 block's box is at most 64 NQ_KW chunks
-            {
-                const int bwq = (int)ceil((fabs((double)P.fx[0]) * 31 + fabs((double)P.fx[1]) * 15) / 65536.0) + 3;
-                const int bhq = (int)ceil((fabs((double)P.fx[3]) * 31 + fabs((double)P.fx[4]) * 15) / 65536.0) + 3;
-                const int nchq = (bwq * 3 + 15 + 15) / 16;
-                const int kwq = (bhq * nchq + 63) / 64;
-                const int ntxq = (d.w + 127) / 128, ntyq = (d.h + 15) / 16;
-                const bool aligned = ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0 &&
-                                     (d.w * 3) % 16 == 0 && (s.w * 3) % 16 == 0 && s.w * 3 >= 16 &&
-                                     (int64_t)s.h * s.rs < ((int64_t)1 << 32);
-                if (aligned && !no_dma && kwq <= NQ_KW && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
-                    AffineParams Pq = P;
-                    Pq.strip_w = 0;
-                    unsigned gx = (unsigned)(ntxq * ntyq);
-                    // measured on 128 4K frames at 22.5 degrees (profiles/r03_experiments/ab_nearest_wq.txt): one frame per workgroup
-                    // (one box, one slot: 6 workgroups per CU) 1.43 ms, with XCD strips 1.49, 2 / 3 / 24 frames per workgroup
-                    // 1.77 / 1.63 / 1.71, affine_nearest_dma_kernel 1.52
-                    const int fpbq = max(1, min(knob_int(K_AFFINE_FPB, 1), d.n));
-                    const dim3 grid(gx, (unsigned)((d.n + fpbq - 1) / fpbq));
-                    const size_t nbufq = fpbq > 1 ? 2 : 1;
-                    const size_t lds = nbufq * ((size_t)4 * ((size_t)bhq * nchq * 16 + 16) + 16 * 384);
-#define IMGXF_NQ_LAUNCH(KWV) hipLaunchKernelGGL((affine_nearest_wq_kernel<KWV>), grid, dim3(256), lds, st, s, d, Pq, ntxq, ntyq, fpbq, nchq, bhq)
-                    switch (kwq) {
-                        case 1: IMGXF_NQ_LAUNCH(1); break; case 2: IMGXF_NQ_LAUNCH(2); break; case 3: IMGXF_NQ_LAUNCH(3); break;
-                        case 4: IMGXF_NQ_LAUNCH(4); break; case 5: IMGXF_NQ_LAUNCH(5); break; case 6: IMGXF_NQ_LAUNCH(6); break;
-                        case 7: IMGXF_NQ_LAUNCH(7); break; default: IMGXF_NQ_LAUNCH(8); break;
-                    }
-#undef IMGXF_NQ_LAUNCH
-                    return launch_status();
-                }
-            }
-            if (bw <= 49 && bh <= 52 && !no_dma && src->w * 3 >= 16 && (src->w * 3) % 16 == 0 &&
-                ((((uintptr_t)src->data) | (uintptr_t)src->row_stride | (uintptr_t)src->frame_stride) & 15) == 0) {
-                // 32x64 tiles when their source box fits 13 chunks x 80 rows, else 32x32
-                const int bw64 = (int)ceil((fabs((double)P.fx[0]) * 31 + fabs((double)P.fx[1]) * 63) / 65536.0) + 3;
-                const int bh64 = (int)ceil((fabs((double)P.fx[3]) * 31 + fabs((double)P.fx[4]) * 63) / 65536.0) + 3;
-                const bool no_tall = knob_set(K_AFFINE_NO_TALL);
-                if (bw64 <= 64 && bh64 <= 80 && !no_tall) {
-                    const int nty64 = (d.h + 63) / 64;
-                    unsigned gx = (unsigned)(ntx * nty64);
-                    // vertical strips per XCD (3 % at 4K: 0.86 -> 0.83 ms per 64 frames, against row-major ranges)
-                    if (ntx >= 16) { P.strip_w = (ntx + 7) / 8; gx = (unsigned)(8 * P.strip_w * nty64); }
-                    hipLaunchKernelGGL((affine_nearest_dma_kernel<64, 13>), dim3(gx, (unsigned)d.n), dim3(256),
-                                       (size_t)13 * 16 * bh64 + 32, st, s, d, P, ntx, nty64);
-                } else {
-                    hipLaunchKernelGGL((affine_nearest_dma_kernel<32, 11>), grid, dim3(256), (size_t)11 * 16 * bh + 32, st, s, d, P, ntx, nty);
-                }
-                return launch_status();
-            }
-            if (bw <= 49) hipLaunchKernelGGL((affine_nearest_lds_kernel<49>), grid, dim3(256), (size_t)49 * bh * 4 + 16, st, s, d, P, ntx, nty);
-            else if (bw <= 65) hipLaunchKernelGGL((affine_nearest_lds_kernel<65>), grid, dim3(256), (size_t)65 * bh * 4 + 16, st, s, d, P, ntx, nty);
-            else hipLaunchKernelGGL((affine_nearest_lds_kernel<97>), grid, dim3(256), (size_t)97 * bh * 4 + 16, st, s, d, P, ntx, nty);
-            return launch_status();
-        }
+    for (int i = 0; i < plan.n; ++i) {
+        if (i) IMGXF_CHECK(launch_status());
+        IMGXF_CHECK(launch_one(plan.launch[i], s, d, plan.P, dbg, plan.list, st));
     }
-    // fixed-point fast path: needs every source coordinate of the output rectangle below 2^21
-    bool fixed_ok = fabs(m[0]) < 64.0 && fabs(m[3]) < 64.0;
-    for (int cy = 0; cy < 2 && fixed_ok; ++cy)
-        for (int cx = 0; cx < 2; ++cx) {
-            const double X = (cx ? dst->w + 4 : 0) + 0.5, Y = (cy ? dst->h : 0) + 0.5;
-            const double xs = m[0] * X + m[1] * Y + m[2], ys = m[3] * X + m[4] * Y + m[5];
-            if (!(fabs(xs) < 2097152.0 && fabs(ys) < 2097152.0)) fixed_ok = false;
-        }
-    P.q0 = fixed_ok ? llround(m[0] * 1099511627776.0) : 0;
-    P.q3 = fixed_ok ? llround(m[3] * 1099511627776.0) : 0;
-    fixed_ok = fixed_ok && fabs(m[1]) < 64.0 && fabs(m[4]) < 64.0;
-    P.q1 = fixed_ok ? llround(m[1] * 1099511627776.0) : 0;
-    P.q4 = fixed_ok ? llround(m[4] * 1099511627776.0) : 0;
-    for (int k = 0; k < 4; ++k) {
-        P.sx[k] = (int)((k * P.q0 + (k * P.q0 >= 0 ? 32768 : -32768)) / 65536);   // round to nearest 2^-24
-        P.sy[k] = (int)((k * P.q3 + (k * P.q3 >= 0 ? 32768 : -32768)) / 65536);
-    }
-    if (fixed_ok) {
-        const double x0d = (m[0] * 0.5 + m[1] * 0.5) + m[2] - 0.5, y0d = (m[3] * 0.5 + m[4] * 0.5) + m[5] - 0.5;
-        P.x00 = (int64_t)floor(x0d * 1099511627776.0);
-        P.y00 = (int64_t)floor(y0d * 1099511627776.0);
-    }
-    if (filter == IMGXF_FILTER_BILINEAR && (src->c == 1 || src->c == 3) && src->w >= 3 && src->h >= 2 && fixed_ok) {
-        const bool no_lds = knob_set(K_AFFINE_NO_LDS);
-        if (src->c == 3 && !no_lds &&
-            ((((uintptr_t)src->data) | (uintptr_t)src->row_stride | (uintptr_t)src->frame_stride) & 3) == 0) {
-            // source bounding box of a 32x32 output tile (translation-invariant up to rounding)
-            const int bw = (int)ceil(fabs(m[0]) * 31 + fabs(m[1]) * 31) + 4;
-            const int bh = (int)ceil(fabs(m[3]) * 31 + fabs(m[4]) * 31) + 4;
-            const int ntx = (d.w + 31) / 32, nty = (d.h + 31) / 32;
-            if (bw <= 97 && bh <= 100 && (int64_t)ntx * nty < 0x7fffffff && d.n <= 65535) {
-                dim3 grid((unsigned)(ntx * nty), (unsigned)d.n);
-                P.ntx_magic = (u32)((((uint64_t)1 << 32) + ntx - 1) / ntx);   // ntx, nty <= 1024: exact; 0 when ntx == 1
-#define IMGXF_LDS_LAUNCH(KERNEL, PITCH, GRID, NTY, LDSB)                                            \
-    do {                                                                                           \
-        if (dbg.p) {                                                                               \
-            if (pr) hipLaunchKernelGGL((KERNEL<true, PITCH, true>), GRID, dim3(256), LDSB, st, s, d, P, dbg, ntx, NTY); \
-            else hipLaunchKernelGGL((KERNEL<false, PITCH, true>), GRID, dim3(256), LDSB, st, s, d, P, dbg, ntx, NTY); \
-        } else {                                                                                   \
-            if (pr) hipLaunchKernelGGL((KERNEL<true, PITCH, false>), GRID, dim3(256), LDSB, st, s, d, P, dbg, ntx, NTY); \
-            else hipLaunchKernelGGL((KERNEL<false, PITCH, false>), GRID, dim3(256), LDSB, st, s, d, P, dbg, ntx, NTY); \
-        }                                                                                          \
-    } while (0)
-#define IMGXF_LDS(PITCH)                                                                           \
-    do {                                                                                           \
-        const size_t lds = (size_t)PITCH * bh * 4 + 16;                                            \
-        IMGXF_LDS_LAUNCH(affine_bilinear_lds_kernel, PITCH, grid, nty, lds);                       \
-        return launch_status();                                                                    \
-    } while (0)
-                // interior tiles as 32x64 (8 pixels per lane) + a host-built list of the others, when
-                // the geometry qualifies
-                const bool no_tall = knob_set(K_AFFINE_NO_TALL);
-                if (!no_tall) {
-                    const int rc = launch_bilinear_tall<64, 49, 64>(s, d, P, dbg, m, bw, bh, ntx, pr, st);
-                    if (rc != BILINEAR_TALL_NOT_TAKEN) return rc;     // (32x128 tiles measured slower: 1.18 vs 1.08 ms)
-                }
-                if (bw <= 49) IMGXF_LDS(49);
-                if (bw <= 65) IMGXF_LDS(65);
-                IMGXF_LDS(97);
-#undef IMGXF_LDS
-#undef IMGXF_LDS_LAUNCH
-            }
-        }
-#define IMGXF_BIL(CC, PR, TXG, WX)                                                                 \
-    do {                                                                                           \
-        constexpr int BW = WX * TXG * 4, BH = (4 / WX) * (64 / TXG);                               \
-        const int ntx = (d.w + BW - 1) / BW, nty = (d.h + BH - 1) / BH;                            \
-        const int64_t nb = (int64_t)ntx * nty * d.n;                                               \
-        if (nb > 0x7fffffff) return IMGXF_ERR_SHAPE;                                               \
-        hipLaunchKernelGGL((affine_bilinear_kernel<CC, PR, TXG, WX>), dim3((unsigned)nb), dim3(256), 0, st, \
-                           s, d, P, dbg, ntx, nty, (int)nb);                                       \
-        return launch_status();                                                                    \
-    } while (0)
-        if (src->c == 3) {
-            if (pr) IMGXF_BIL(3, true, 8, 2); else IMGXF_BIL(3, false, 8, 2);
-        } else {
-            if (pr) IMGXF_BIL(1, true, 8, 2); else IMGXF_BIL(1, false, 8, 2);
-        }
-#undef IMGXF_BIL
-    }
-    {
-        const bool no_shear = knob_set(K_AFFINE_NO_SHEAR_FAST);
-        const bool honly = m[3] == 0.0 && m[4] == 1.0 && m[5] == floor(m[5]) && fabs(m[5]) < 1.0e9;
-        if (filter == IMGXF_FILTER_BICUBIC && honly && src->c == 3 && !dbg.p && !no_shear && src->w >= 4) {
-            dim3 block(256), grid((unsigned)((d.w + 1023) / 1024), (unsigned)d.h, (unsigned)d.n);
-            if (m[0] == 1.0) {
-                // unit-step rows (apply_shear): main pass + a tiny pass over the row-end groups
-                if (pr) hipLaunchKernelGGL((shear_bicubic_kernel<true, true>), grid, block, 0, st, s, d, P);
-                else hipLaunchKernelGGL((shear_bicubic_kernel<false, true>), grid, block, 0, st, s, d, P);
-                IMGXF_CHECK(launch_status());
-                hipLaunchKernelGGL(shear_edges_kernel, dim3((unsigned)((d.h * 8 + 255) / 256), (unsigned)d.n), dim3(256), 0, st, s, d, P);
-                return launch_status();
-            }
-            if (pr) hipLaunchKernelGGL((shear_bicubic_kernel<true, false>), grid, block, 0, st, s, d, P);
-            else hipLaunchKernelGGL((shear_bicubic_kernel<false, false>), grid, block, 0, st, s, d, P);
-            return launch_status();
-        }
-    }
-    switch (src->c) {
-        case 1: return pr ? launch_affine_filter<1, PreciseArith>(filter, s, d, P, dbg, st)
-                          : launch_affine_filter<1, FastArith>(filter, s, d, P, dbg, st);
-        case 3: return pr ? launch_affine_filter<3, PreciseArith>(filter, s, d, P, dbg, st)
-                          : launch_affine_filter<3, FastArith>(filter, s, d, P, dbg, st);
-        case 4: return launch_affine_filter<4, PreciseArith>(filter, s, d, P, dbg, st);
-        default: return IMGXF_ERR_UNSUPPORTED;
-    }
+    return launch_status();
 }
 
 // ---- ImagingScaleAffine: NEAREST with m1 == m3 == 0 ------------------------------------

@@ -26,8 +26,7 @@ namespace imgxf {
 template <int B>
 __device__ __forceinline__ float tapf(u32 w) { return (float)((w >> (8 * B)) & 0xffu); }
 
-
-constexpr int MF_TILE_H = 64;                    // tile rows (NBR: staged source rows per wave, box height <= 4 * NBR)
+// MF_TILE_H, the tile rows, is in affine_route.h (NBR: staged source rows per wave, box height <= 4 * NBR)
 
 // One LDS-DMA of 16 bytes per lane, hidden from hipcc (which would otherwise drain every pending
 // LDS-DMA with s_waitcnt vmcnt(0) in front of the next ds_read it can see): lane i's 16 bytes at

@@ -30,8 +30,7 @@
 
 namespace imgxf {
 
-constexpr int WQ_PITCH = 28;          // RGBX dwords per box row (box width <= 28 pixels)
-constexpr int WQ_MAXCH = 192;         // 16-byte chunks a wave moves per frame (3 DMA instructions)
+// WQ_PITCH (RGBX dwords per box row) and WQ_MAXCH (16-byte chunks a wave moves per frame) are in affine_route.h
 
 template <bool PRECISE>
 __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb,
@@ -340,7 +339,7 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
 // selects the loop, which the tests cover.
 // Host: rows x nch <= 64 NQ_KW chunks per box, source / destination 16-byte aligned with 16-byte multiple rows.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int NQ_KW = 8;              // DMA instructions per wave and frame (box <= 512 chunks)
+// NQ_KW, the most DMA instructions per wave and frame, is in affine_route.h
 
 template <int KWT>
 __device__ __forceinline__ void nq_wait() {       // at most KWT vector memory operations outstanding

@@ -5,11 +5,10 @@ run_affine and every bicubic one must give Pillow's bytes on every frame of a ba
 the fp32 side output must stay inside the 1e-5 contract.
 
 Each case first asserts which kernel the dispatcher takes for its geometry (`bilinear_route`, a
-restatement of the box formulas and alignment tests of run_affine / launch_bilinear_tall in
-csrc/affine.hip): a change to those limits updates the function with it, and a geometry that silently
+restatement of the box formulas and alignment tests of plan_affine in csrc/affine_route.h, kept in
+affine_route.py): a change to those limits updates the function with it, and a geometry that silently
 moves to another kernel fails here instead of leaving a kernel untested."""
 import functools
-import math
 import os
 
 import numpy as np
@@ -17,6 +16,7 @@ import pytest
 import torch
 
 import near_integer_corpus as C
+from affine_route import bicubic_route, bilinear_route
 from oracle import imgxf_oracle as O
 from test_gpu_parity import dev, host
 
@@ -24,59 +24,6 @@ pytestmark = pytest.mark.gpu
 
 MATS = {**C.BILINEAR, **C.DYADIC}
 PICK = {1: (0,), 3: (0, 7, 4), 5: (0, 7, 3, 10, 5), 12: tuple(range(12))}     # variants in a batch of n: plain and complemented mixed
-
-
-def _box(m, tw, th, extra=4):
-    return (math.ceil(abs(m[0]) * (tw - 1) + abs(m[1]) * (th - 1)) + extra,
-            math.ceil(abs(m[3]) * (tw - 1) + abs(m[4]) * (th - 1)) + extra)
-
-
-def _llround(v):
-    return int(math.copysign(math.floor(abs(v) + 0.5), v))
-
-
-def bilinear_route(t, m, out_size, return_f32=False):
-    """(kernel, uses the list kernel too) that run_affine takes for BILINEAR on source tensor `t` with
-    the knobs now in the environment; the destination is the fresh contiguous tensor ops.affine makes."""
-    from imagetransformations_amd import _ffi as F
-    s = F.view_of(t)
-    ow, oh = out_size
-    env = os.environ
-    align = lambda *v: all(int(x) % 16 == 0 for x in v)
-    if s.c == 1:
-        return "global1", False
-    if "IMGXF_AFFINE_NO_LDS" in env or (s.data | s.row_stride | s.frame_stride) & 3:
-        return "global3", False
-    (bw, bh), (bwt, bht), (bwq, bhq) = _box(m, 32, 32), _box(m, 32, 64), _box(m, 32, 16)
-    assert bw <= 97 and bh <= 100
-    ntx = (ow + 31) // 32
-    if "IMGXF_AFFINE_NO_TALL" not in env and bwt <= 49 and bht <= 64 and bw <= 49:
-        no_dma = "IMGXF_AFFINE_NO_DMA" in env
-        mf = not return_f32 and int(env.get("IMGXF_AFFINE_FPB", 16)) >= 2 and s.n >= 2
-        src16 = align(s.data, s.row_stride, s.frame_stride) and s.w * 3 >= 16
-        nch, nchq = (bwt * 3 + 30) // 16, (bwq * 3 + 30) // 16
-        if mf and not no_dma and src16 and align(ow * 3, oh * ow * 3) and bwq <= 28 and bhq * nchq <= 192 and bhq * 7 <= 192:
-            return "wq", False
-        if mf and not no_dma and src16 and bht <= 52 and bwt <= 52 and 52 * nch <= 768:
-            return "mf13_dma", False
-        # tiles that are not interior go to the list kernel (the host's integers, 2^-40 units)
-        q = [_llround(v * 2.0 ** 40) for v in m]
-        x00 = math.floor(((m[0] * 0.5 + m[1] * 0.5) + m[2] - 0.5) * 2.0 ** 40)
-        y00 = math.floor(((m[3] * 0.5 + m[4] * 0.5) + m[5] - 0.5) * 2.0 ** 40)
-        ntyt, listed = (oh + 63) // 64, 0
-        for ty in range(ntyt):
-            for tx in range(ntx):
-                xt, yt = x00 + tx * 32 * q[0] + ty * 64 * q[1], y00 + tx * 32 * q[3] + ty * 64 * q[4]
-                xs, ys = (0, 31 * q[0], 63 * q[1], 31 * q[0] + 63 * q[1]), (0, 31 * q[3], 63 * q[4], 31 * q[3] + 63 * q[4])
-                xlo, xhi, ylo, yhi = (xt + min(xs)) >> 40, ((xt + max(xs)) >> 40) + 1, (yt + min(ys)) >> 40, ((yt + max(ys)) >> 40) + 1
-                clean = (xlo >= 0 and ylo >= 0 and xhi <= s.w - 1 and yhi <= s.h - 1 and tx * 32 + 32 <= ow and ty * 64 + 64 <= oh
-                         and not (xhi == s.w - 1 and yhi == s.h - 1))
-                listed += not clean
-        assert listed <= 896
-        if listed < ntx * ntyt:
-            return ("mf13" if bht <= 52 else "mf16") if mf else "lds_interior", listed > 0
-        return "lds_list_only", True
-    return ("lds49" if bw <= 49 else "lds65" if bw <= 65 else "lds97"), False
 
 
 @functools.lru_cache(maxsize=None)
@@ -235,14 +182,6 @@ def test_bilinear_f32_side_output(device, monkeypatch, name, n, knobs, route, pr
 
 
 # ------------------------------------------------------------------ bicubic
-def bicubic_route(t, m):
-    """run_affine's choice for BICUBIC, three channels, no fp32 side output."""
-    honly = m[3] == 0.0 and m[4] == 1.0 and m[5] == math.floor(m[5]) and abs(m[5]) < 1.0e9
-    if honly and "IMGXF_AFFINE_NO_SHEAR_FAST" not in os.environ and t.shape[-2] >= 4:
-        return "shear_unit_step+edges" if m[0] == 1.0 else "shear_rows"
-    return "general"
-
-
 WHITE = (255, 255, 255)
 BICUBIC_CASES = [("B1", "B1", {}, "shear_unit_step+edges"), ("B2", "B2", {}, "shear_unit_step+edges"), ("B3", "B3", {}, "shear_rows"),
                  ("CLIP", "B1", {}, "shear_unit_step+edges"), ("CLIP", "B2", {}, "shear_unit_step+edges"), ("CLIP", "B3", {}, "shear_rows"),
