@@ -892,18 +892,11 @@ __global__ __launch_bounds__(256) void affine_nearest_dma_kernel(View s, View d,
     constexpr u32 DIVM = (65536u + DCHT - 1) / DCHT;                  // idx / DCHT == (idx * DIVM) >> 16 for idx < 2^12
     extern __shared__ __attribute__((aligned(16))) char srcb[];      // bhc x DPITCH bytes (+16)
     __shared__ __attribute__((aligned(16))) u32 stage[4][64 * C + 2 * (64 / TXG) + 4];
-    const int nblocks = ntx * nty;
-    const int orig = blockIdx.x, xcd = orig & 7, q = nblocks >> 3, r = nblocks & 7;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
     const int f = blockIdx.y;
-    int tyb = P.ntx_magic ? (int)__umulhi((u32)logical, P.ntx_magic) : logical, txb = logical - tyb * ntx;
-    if (P.strip_w) {
-        // vertical strips: a tile's box overlaps its neighbours' (2x for a pure rotation); inside a strip
-        // walked row by row both neighbours are a few workgroups away on the same L2
-        const int l = orig >> 3;
-        tyb = l / P.strip_w; txb = xcd * P.strip_w + (l - tyb * P.strip_w);
-        if (txb >= ntx || tyb >= nty) return;
-    }
+    // a tile's box overlaps its neighbours' (2x for a pure rotation); inside an XCD's region, walked row by row, both
+    // neighbours are a few workgroups away on the same L2 (xcd_tile in affine_route.h)
+    int tyb, txb;
+    if (!xcd_tile(blockIdx.x, ntx, nty, P.xcd_regions, P.ntx_magic, txb, tyb)) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lx = (lane % TXG) * 4;
     const int x0 = txb * BW + lx;

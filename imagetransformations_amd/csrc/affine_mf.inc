@@ -57,15 +57,8 @@ __global__ __launch_bounds__(256, 4) void affine_bilinear_mf_kernel(View s, View
     constexpr int FONE = 1 << 24, FHALF = 1 << 23, CG32 = 1 << 6;
     extern __shared__ __attribute__((aligned(16))) u32 srct[];          // [rows][2][PITCH] RGBX source box
     __shared__ __attribute__((aligned(16))) u32 stage[4][2][64 * 3];    // per wave: the two halves' 64 x 12 output bytes
-    const int nblocks = ntx * nty;
-    const int orig = blockIdx.x, xcd = orig & 7, q = nblocks >> 3, r = nblocks & 7;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    int tyb = P.ntx_magic ? (int)__umulhi((u32)logical, P.ntx_magic) : logical, txb = logical - tyb * ntx;
-    if (P.strip_w) {                 // vertical strips per XCD (see affine_nearest_dma_kernel)
-        const int l = orig >> 3;
-        tyb = l / P.strip_w; txb = xcd * P.strip_w + (l - tyb * P.strip_w);
-        if (txb >= ntx || tyb >= nty) return;
-    }
+    int tyb, txb;
+    if (!xcd_tile(blockIdx.x, ntx, nty, P.xcd_regions, P.ntx_magic, txb, tyb)) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int f_begin = blockIdx.y * fpb, f_end = min(d.n, f_begin + fpb);
 

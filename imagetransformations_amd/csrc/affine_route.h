@@ -24,7 +24,7 @@ struct AffineParams {
     u32 ntx_magic;    // ceil(2^32 / ntx) of the LDS kernels' tile grid
     int sx[4], sy[4]; // round(k*q0 / 2^16), round(k*q3 / 2^16): 8.24 steps to pixel k of a lane (LDS fast loop)
     u8 fill[4];
-    int strip_w;      // > 0 = every XCD owns a vertical strip of this many tile columns (xcd_strips below)
+    int xcd_regions;  // 1 = every XCD owns a compact region of the tile grid, 0 = a range of the row-major order (xcd_tile below)
 };
 
 // the border tiles of the tall bilinear route, by value in the launch arguments of affine_bilinear_lds_list_kernel
@@ -97,12 +97,46 @@ inline bool aligned(const View& v, int bytes) {
 inline bool offsets_fit_32(const View& v) { return (int64_t)v.h * v.rs < ((int64_t)1 << 32); }
 // ceil(2^32 / ntx); ntx, nty <= 1024: exact; 0 when ntx == 1
 inline u32 tile_magic(int ntx) { return (u32)((((uint64_t)1 << 32) + ntx - 1) / ntx); }
-// grid.x of an ntx x nty tile grid.  From min_cols tile columns on, every XCD owns a vertical strip of P.strip_w columns:
-// vertically adjacent tiles (whose boxes overlap 2x in y) then sit a few workgroups apart on ONE L2.
-inline unsigned xcd_strips(int ntx, int nty, int min_cols, AffineParams& P) {
-    if (ntx < min_cols) return (unsigned)(ntx * nty);
-    P.strip_w = (ntx + 7) / 8;
-    return (unsigned)(8 * P.strip_w * nty);
+// ---- which tile a workgroup takes: the one copy, for the batch kernels and for tests/test_affine_tile_map_host.py ------
+// Workgroups b and b + 8 share an XCD (the dispatcher's observed round robin: speed only), so x = b & 7 names an L2 and
+// l = b >> 3 counts the workgroups on it.  grid.x is the tile count T = ntx * nty: residue x then has q + (x < r) workgroups
+// (q = T / 8, r = T % 8) and takes as many consecutive tiles of
+//   regions == 0   the row-major order: a range of whole and partial tile rows;
+//   regions == 1   the column-major order: the tail of one tile column, whole columns, the head of the next.  Such a region
+//                  is one compact piece of the grid (from 8 columns on it holds at least a column's worth of tiles) and is
+//                  walked row by row across its width: a row is the tile of the first column (rows >= r0), the whole
+//                  columns, the tile of the last column (rows <= r1), so there are at most three bands of rows of one width.
+//                  Vertically adjacent tiles (whose boxes overlap 2x in y) then sit a few workgroups apart on ONE L2.
+// Every tile is taken once, and no XCD has more than one tile more than another.  (Whole strips of ceil(ntx / 8) columns
+// per XCD would leave one XCD half idle at 30 columns and three XCDs empty at 10: profiles/xcd_balance.txt.)
+// magic: tile_magic(ntx), or 0 to divide.  False: no tile for this workgroup (b >= T).
+__host__ __device__ inline bool xcd_tile(unsigned b, int ntx, int nty, int regions, u32 magic, int& tx, int& ty) {
+    const int T = ntx * nty, x = (int)(b & 7), l = (int)(b >> 3), q = T >> 3, r = T & 7;
+    const int first = x * q + (x < r ? x : r), count = q + (x < r);
+    if (l >= count) return false;
+    if (!regions) {
+        const int t = first + l;
+        ty = magic ? (int)(((uint64_t)(u32)t * magic) >> 32) : t / ntx;
+        tx = t - ty * ntx;
+        return true;
+    }
+    const int last = first + count - 1;
+    const int c0 = first / nty, r0 = first - c0 * nty, c1 = last / nty, r1 = last - c1 * nty;
+    if (c1 == c0) { tx = c0; ty = r0 + l; return true; }
+    const int whole = c1 - c0 - 1;
+    // rows [0, lo) | [lo, hi) | [hi, nty): the head alone, both partial columns or neither, the tail alone
+    const bool both = r0 <= r1 + 1;
+    const int lo = both ? r0 : r1 + 1, hi = both ? r1 + 1 : r0;
+    const int w1 = both ? whole + 2 : whole, n0 = lo * (whole + 1), n1 = (hi - lo) * w1;
+    if (l < n0) { ty = l / (whole + 1); tx = c0 + 1 + (l - ty * (whole + 1)); }
+    else if (l < n0 + n1) { const int k = l - n0, row = k / w1; ty = lo + row; tx = (both ? c0 : c0 + 1) + (k - row * w1); }
+    else { const int k = l - n0 - n1, row = k / (whole + 1); ty = hi + row; tx = c0 + (k - row * (whole + 1)); }
+    return true;
+}
+// grid.x of an ntx x nty tile grid, and the map that xcd_tile applies to it: regions from min_cols tile columns on
+inline unsigned xcd_tile_grid(int ntx, int nty, int min_cols, AffineParams& P) {
+    P.xcd_regions = ntx >= min_cols;
+    return (unsigned)(ntx * nty);
 }
 
 inline AffineLaunch& add_launch(AffinePlan& R, AffineFamily family, dim3 grid, dim3 block, size_t lds) {
@@ -152,8 +186,8 @@ inline bool plan_nearest_tiles(const View& s, const View& d, const AffineKnobs& 
         const int bw64 = box_fx(P.fx[0], P.fx[1], 32, 64, 3), bh64 = box_fx(P.fx[3], P.fx[4], 32, 64, 3);
         if (bw64 <= 64 && bh64 <= 80 && !K.no_tall) {
             const int nty64 = (d.h + 63) / 64;
-            // vertical strips per XCD (3 % at 4K: 0.86 -> 0.83 ms per 64 frames, against row-major ranges)
-            const unsigned gx = xcd_strips(ntx, nty64, 16, P);
+            // a compact region per XCD (whole strips of columns: 3 % at 4K, 0.86 -> 0.83 ms per 64 frames, against row-major ranges)
+            const unsigned gx = xcd_tile_grid(ntx, nty64, 16, P);
             AffineLaunch& L = add_launch(R, AF_NEAREST_DMA, dim3(gx, (unsigned)d.n), dim3(256), (size_t)13 * 16 * bh64 + 32);
             L.tile_h = 64; L.ntx = ntx; L.nty = nty64;
         } else {
@@ -221,8 +255,8 @@ inline bool plan_bilinear_tall(const View& s, const View& d, const double* m, in
             // has > 20 000 workgroups to drain evenly (sweep 8 ... 128 on 128 4K / 512 1080p / 32 4K frames:
             // profiles/r03_experiments/affine_fpb_sweep.txt; 24 is the fastest or within 0.5 % everywhere)
             const int fpbq = K.fpb_or(24);
-            // strips from 8 columns on: at 1080p (15 columns) row-major ranges fetched every source byte twice
-            const unsigned gx = xcd_strips(ntxq, ntyq, 8, P);
+            // regions from 8 columns on: at 1080p (15 columns) row-major ranges fetched every source byte twice
+            const unsigned gx = xcd_tile_grid(ntxq, ntyq, 8, P);
             AffineLaunch& L = add_launch(R, AF_BILINEAR_WQ, dim3(gx, (unsigned)((d.n + fpbq - 1) / fpbq)), dim3(256),
                                          (size_t)4 * ((size_t)bhq * WQ_PITCH * 4 + 2 * ((size_t)bhq * nchq * 16 + 64)) + 2 * 16 * 384);
             L.precise = pr; L.ntx = ntxq; L.nty = ntyq; L.fpb = fpbq; L.nch = nchq; L.bh = bhq;
@@ -233,7 +267,7 @@ inline bool plan_bilinear_tall(const View& s, const View& d, const double* m, in
     // also takes the border tiles (no list pass)
     const int nch = packed_chunks(bwt);
     if (mf && !K.no_dma && bht <= 52 && bwt <= 52 && 52 * nch <= 768 && aligned(s, 16) && s.w * 3 >= 16 && offsets_fit_32(s)) {
-        const unsigned gx = xcd_strips(ntx, ntyt, 16, P);
+        const unsigned gx = xcd_tile_grid(ntx, ntyt, 16, P);
         // RGBX pitch 56: fewest bank conflicts of the multiples of 4 (simulated for 30 deg / 1.5x: 4.0 vs 5.8 LDS cycles per gather read at 52)
         AffineLaunch& L = add_launch(R, AF_BILINEAR_MF, dim3(gx, (unsigned)((d.n + fpb - 1) / fpb)), dim3(256),
                                      (size_t)52 * 56 * 4 + 2 * ((size_t)52 * nch * 16 + 64));      // RGBX image + two packed-row buffers

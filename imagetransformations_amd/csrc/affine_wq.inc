@@ -40,13 +40,8 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
     constexpr u32 GTOP = 8u << 17;
     constexpr int FONE = 1 << 24, FHALF = 1 << 23, CG32 = 1 << 6;
     extern __shared__ __attribute__((aligned(16))) u32 wq_lds[];
-    const int orig = blockIdx.x, xcd = orig & 7, l = orig >> 3;
     int tyb, txb;
-    if (P.strip_w) { tyb = l / P.strip_w; txb = xcd * P.strip_w + (l - tyb * P.strip_w); }
-    else { const int nb = ntx * nty, q = nb >> 3, r = nb & 7;
-           const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + l;
-           tyb = logical / ntx; txb = logical - tyb * ntx; }
-    if (txb >= ntx || tyb >= nty) return;
+    if (!xcd_tile(blockIdx.x, ntx, nty, P.xcd_regions, 0, txb, tyb)) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int f_begin = blockIdx.y * fpb, f_end = min(d.n, f_begin + fpb);
     const int sx0 = txb * BW + wave * SW, sy0 = tyb * BH;            // this wave's 32 x 16 block
@@ -360,13 +355,8 @@ __global__ __launch_bounds__(256) void affine_nearest_wq_kernel(View s, View d, 
                                                                 int nch, int rows) {
     constexpr int C = 3, SW = 32, BH = 16, BW = 4 * SW;
     extern __shared__ __attribute__((aligned(16))) u32 nq_lds[];      // [wave 0 .. 3: box 0 | box 1] [slot 0 | slot 1: 16 rows x 384 bytes]
-    const int orig = blockIdx.x, xcd = orig & 7, l = orig >> 3;
     int tyb, txb;
-    if (P.strip_w) { tyb = l / P.strip_w; txb = xcd * P.strip_w + (l - tyb * P.strip_w); }
-    else { const int nb = ntx * nty, q = nb >> 3, r = nb & 7;
-           const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + l;
-           tyb = logical / ntx; txb = logical - tyb * ntx; }
-    if (txb >= ntx || tyb >= nty) return;
+    if (!xcd_tile(blockIdx.x, ntx, nty, P.xcd_regions, 0, txb, tyb)) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int f_begin = blockIdx.y * fpb, f_end = min(d.n, f_begin + fpb);
     const int sx0 = txb * BW + wave * SW, sy0 = tyb * BH;             // this wave's 32 x 16 block

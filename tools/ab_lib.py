@@ -1,6 +1,9 @@
 """Same-process A/B of two builds of libimgxf.so on the headline kernels (development aid).
 
-    python tools/ab_lib.py <libA.so> <libB.so> [affine|affine32|gaussian|nearest|all] [frames]
+    python tools/ab_lib.py <libA.so> <libB.so> [affine|affine32|gaussian|nearest|all] [frames] [height width]
+
+(frames of 2160 x 3840 unless a height and a width are given: 128 x 2160 x 4096 is the width whose 32 tile columns
+divide over the XCDs, 288 x 1440 x 2560 and 1152 x 720 x 1280 hold the bytes of 128 4K frames)
 
 Both libraries are loaded with ctypes next to each other; the same C-ABI call on the same resident
 frames is timed with HIP events, alternating A / B for ROUNDS rounds of ITERS launches, and the medians are
@@ -43,7 +46,7 @@ def main():
     what = sys.argv[3] if len(sys.argv) > 3 else "all"
     F = int(sys.argv[4]) if len(sys.argv) > 4 else 128
     libs = {"A": load(pa, os.environ.get("A_ENV")), "B": load(pb, os.environ.get("B_ENV"))}
-    H, W = 2160, 3840
+    H, W = (int(sys.argv[5]), int(sys.argv[6])) if len(sys.argv) > 6 else (2160, 3840)
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev); gen.manual_seed(1)
     src = torch.randint(0, 256, (F, H, W, 3), dtype=torch.uint8, device=dev, generator=gen)
@@ -106,8 +109,9 @@ def main():
                 e.record(); torch.cuda.synchronize()
                 res[k].append(s.elapsed_time(e) / ITERS)
         a, b = statistics.median(res["A"]), statistics.median(res["B"])
-        print(f"{name:10s} F={F}  A {a:7.4f} ms ({bpp * px / a / 1e6 / 8000:.3f})   B {b:7.4f} ms ({bpp * px / b / 1e6 / 8000:.3f})"
-              f"   B/A {b / a:.3f}   outputs equal: {equal}", flush=True)
+        print(f"{name:10s} F={F} {H}x{W}  A {a:7.4f} ms ({bpp * px / a / 1e6 / 8000:.3f})   B {b:7.4f} ms ({bpp * px / b / 1e6 / 8000:.3f})"
+              f"   B/A {b / a:.3f}   rounds A {min(res['A']):.4f} .. {max(res['A']):.4f}  B {min(res['B']):.4f} .. {max(res['B']):.4f}"
+              f"   outputs equal: {equal}", flush=True)
 
 
 if __name__ == "__main__":

@@ -15,7 +15,8 @@
 //
 // A launch line, tab separated: "L", the kernel's instantiation (dladdr on the host stub + __cxa_demangle, not the spelling
 // at the call site), grid, block, LDS bytes, then every argument field by field (doubles as hex floats; a TileList as n
-// and idx[0..n) only — its tail and every struct's padding are indeterminate, so raw bytes are never hashed).
+// and idx[0..n) only — its tail and every struct's padding are indeterminate, so raw bytes are never hashed); last, for a
+// grid.x of ntx * nty tiles, xcd_tiles=fewest..most: the tiles per residue of blockIdx.x & 7 (one XCD) under xcd_tile().
 // A call line: "C", the case number, the return code, the case.
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
@@ -39,6 +40,9 @@ namespace trace {
 static bool recording = true;
 static std::string out;                                       // the launch lines of the current call
 static std::map<std::string, long> per_kernel;
+static const imgxf::AffineParams* tile_map;                   // of the launch being recorded: its AffineParams and the ints after it
+static std::vector<int> ints;
+static void put_xcd_tiles(dim3 g);
 static void record_kernel(const void* stub, dim3 g, dim3 b, size_t lds);
 static void put(int v);                                       // the argument types of the affine kernels
 static void put(const imgxf::View& v);
@@ -49,7 +53,10 @@ template <class... A>
 static void record(const void* stub, dim3 g, dim3 b, size_t lds, const A&... a) {
     if (!recording) return;
     record_kernel(stub, g, b, lds);
+    tile_map = nullptr;
+    ints.clear();
     (put(a), ...);
+    put_xcd_tiles(g);
     out += '\n';
 }
 } // namespace trace
@@ -100,7 +107,7 @@ static void record_kernel(const void* stub, dim3 g, dim3 b, size_t lds) {
     ++per_kernel[name];
     addf("L\t%s\tgrid=%u,%u,%u\tblock=%u,%u,%u\tlds=%zu", name.c_str(), g.x, g.y, g.z, b.x, b.y, b.z, lds);
 }
-static void put(int v) { addf("\t%d", v); }
+static void put(int v) { addf("\t%d", v); ints.push_back(v); }
 static void put(const imgxf::View& v) {
     addf("\tView{p=%p n=%d h=%d w=%d c=%d rs=%lld fs=%lld}", (void*)v.p, v.n, v.h, v.w, v.c, (long long)v.rs, (long long)v.fs);
 }
@@ -109,8 +116,21 @@ static void put(const imgxf::AffineParams& P) {
          P.fx[3], P.fx[4], P.fx[5]);
     addf(" q0=%lld q3=%lld q1=%lld q4=%lld x00=%lld y00=%lld ntx_magic=%u", (long long)P.q0, (long long)P.q3, (long long)P.q1,
          (long long)P.q4, (long long)P.x00, (long long)P.y00, P.ntx_magic);
-    addf(" sx=%d,%d,%d,%d sy=%d,%d,%d,%d fill=%u,%u,%u,%u strip_w=%d}", P.sx[0], P.sx[1], P.sx[2], P.sx[3], P.sy[0], P.sy[1], P.sy[2],
-         P.sy[3], P.fill[0], P.fill[1], P.fill[2], P.fill[3], P.strip_w);
+    addf(" sx=%d,%d,%d,%d sy=%d,%d,%d,%d fill=%u,%u,%u,%u xcd_regions=%d}", P.sx[0], P.sx[1], P.sx[2], P.sx[3], P.sy[0], P.sy[1], P.sy[2],
+         P.sy[3], P.fill[0], P.fill[1], P.fill[2], P.fill[3], P.xcd_regions);
+    tile_map = &P;
+    ints.clear();
+}
+// the tiles that each residue of blockIdx.x & 7 (one XCD's workgroups) takes, fewest..most, for the kernels whose
+// grid.x is decoded by xcd_tile (arguments: ..., AffineParams, ntx, nty, ...)
+static void put_xcd_tiles(dim3 g) {
+    if (!tile_map || ints.size() < 2 || (long long)ints[0] * ints[1] != (long long)g.x) return;
+    long per[8] = {0};
+    for (unsigned b = 0; b < g.x; ++b) {
+        int tx, ty;
+        per[b & 7] += imgxf::xcd_tile(b, ints[0], ints[1], tile_map->xcd_regions, 0, tx, ty);
+    }
+    addf("\txcd_tiles=%ld..%ld", *std::min_element(per, per + 8), *std::max_element(per, per + 8));
 }
 static void put(const imgxf::TileList& l) {
     addf("\tlist{n=%d:", l.n);
