@@ -169,7 +169,7 @@ inline bool plan_nearest_tiles(const View& s, const View& d, const AffineKnobs& 
         const int nchq = packed_chunks(bwq), kwq = (bhq * nchq + 63) / 64;
         const int ntxq = (d.w + 127) / 128, ntyq = (d.h + 15) / 16;
         if (aligned(s, 16) && aligned(d, 16) && (d.w * 3) % 16 == 0 && (s.w * 3) % 16 == 0 && s.w * 3 >= 16 && offsets_fit_32(s) &&
-            !K.no_dma && kwq <= NQ_KW && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
+            offsets_fit_32(d) && !K.no_dma && kwq <= NQ_KW && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
             // measured on 128 4K frames at 22.5 degrees (profiles/r03_experiments/ab_nearest_wq.txt): one frame per workgroup
             // (one box, one slot: 6 workgroups per CU) 1.43 ms, with XCD strips 1.49, 2 / 3 / 24 frames per workgroup
             // 1.77 / 1.63 / 1.71, affine_nearest_dma_kernel 1.52

@@ -21,6 +21,11 @@
 //     stores, 0.29 and 0.35 ms on their own, 1.04 ms together).  Issued after it they are a whole iteration old at the
 //     next one.  (A fifth, store-only wave per workgroup was tried: wave w of a workgroup lives on SIMD w mod 4, so SIMD 0
 //     then holds two waves per workgroup and only two workgroups fit a CU — 2.45 ms.)
+//   * the kernel is bound by VALU issue, so what does not change from frame to frame stays out of the frame loop
+//     (profiles/affine_wq_trim.txt: 355 -> 330 VALU instructions per wave and frame): a store is the frame's scalar base,
+//     advanced by the frame stride, plus a 32-bit lane offset worked out once (no address instruction per store); the
+//     packed -> RGBX expansion has one copy per byte phase of the wave's box (3 v_alignbyte per 4 pixels instead of 6);
+//     and a block whose pixels all lie outside the source parks its fill once and stages, expands and gathers nothing.
 //
 // Exactness is that of affine_mf.inc: |v32 - v64| <= 255 * 2^-24 (weights) + 4 * 2^-16 (FMAs accumulating in [256, 512))
 // + 2 * 255 * 2^-24 (8.24 coordinates) < 1.07e-4 < GUARDP = 2^-13; pixels whose sum has frac(v + GUARDP) < 2 GUARDP, or
@@ -31,6 +36,51 @@
 namespace imgxf {
 
 // WQ_PITCH (RGBX dwords per box row) and WQ_MAXCH (16-byte chunks a wave moves per frame) are in affine_route.h
+
+// the four bytes from byte OFF (0 .. 12) of four consecutive dwords
+template <int OFF>
+__device__ __forceinline__ u32 wq_bytes_at(const u32 (&q)[4]) {
+    if constexpr ((OFF & 3) == 0) return q[OFF >> 2];
+    else return __builtin_amdgcn_alignbyte(q[(OFF >> 2) + 1], q[OFF >> 2], (u32)(OFF & 3));
+}
+
+typedef u32 wq_u32x4 __attribute__((ext_vector_type(4)));
+
+// 16 bytes per lane to base + voff.  The frame's base is scalar and the lane's offset has 32 bits, so the store needs no
+// address arithmetic of its own; from C++ hipcc widens the offset and adds the base with a v_lshl_add_u64 per store.
+__device__ __forceinline__ void store16_sv(u8* base, u32 voff, wq_u32x4 o) {
+    asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(voff), "v"(o), "s"(base) : "memory");
+}
+
+// Rows 4 wave .. 4 wave + 3 of a tile-wide slot (16 rows x 384 bytes; two slots, 6144 bytes apart) -> global memory as dense
+// 16-byte chunks, 24 per row, two per lane.  A lane's chunks are the same in every frame: their LDS address in slot 0 and
+// their byte offset in a frame (host: h x row stride < 2^32) are worked out once, the slot's parity is an immediate of the
+// LDS read, and a store is the frame's scalar base + that offset.
+struct WqFlush {
+    u32 rd[2], off[2];
+    bool ok[2];
+    __device__ __forceinline__ WqFlush(const View& d, const u32* slots, int lane, int wave, int txb, int sy0) {
+        const int rb16 = (int)((int64_t)d.w * 3 / 16);              // chunks per image row (host: row bytes % 16 == 0)
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const int ch = pass * 64 + lane;                        // 0 .. 95
+            const int r = wave * 4 + ch / 24, ck = ch - (ch / 24) * 24;
+            ok[pass] = ch < 96 && sy0 + r < d.h && txb * 24 + ck < rb16;
+            rd[pass] = (u32)(uintptr_t)(__attribute__((address_space(3))) const u32*)slots + (u32)((r * 96 + ck * 4) * 4);
+            off[pass] = (u32)(sy0 + r) * (u32)d.rs + (u32)(txb * 384 + ck * 16);
+        }
+    }
+    template <u32 SLOT_OFF>
+    __device__ __forceinline__ void rows(u8* dframe) const {
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            if (ok[pass]) store16_sv(dframe, off[pass], *(const __attribute__((address_space(3))) wq_u32x4*)(uintptr_t)(rd[pass] + SLOT_OFF));
+        }
+    }
+    __device__ __forceinline__ void operator()(u8* dframe, int par) const {
+        if (par) rows<16 * 96 * 4>(dframe); else rows<0>(dframe);
+    }
+};
 
 template <bool PRECISE>
 __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb,
@@ -101,6 +151,10 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
             }
         }
     }
+    // a border block whose every produced pixel is certainly outside the source stages, expands and gathers nothing: it parks
+    // the fill once (below) and only keeps the barriers and its share of the stores
+    const bool fill_only = wave_in && !interior && __builtin_amdgcn_ballot_w64((okm & ~fillm) != 0u) == 0;
+    const bool wave_on = wave_in && !fill_only;
     if (interior) okm = 0xffu;
 
     // ---- DMA staging of the wave's box as packed RGB rows: chunk c = 64 i + lane of the [rows][nch] grid
@@ -117,7 +171,7 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
         for (int i = 0; i < 3; ++i) {
             const int c = i * 64 + lane;
             const int row = c / nch, ch = c - row * nch;
-            dma_ok[i] = c < rows * nch && wave_in;
+            dma_ok[i] = c < rows * nch && wave_on;
             const int64_t go = (int64_t)clampi(uy_lo + row, 0, s.h - 1) * s.rs + a0 + 16 * ch;
             dma_off[i] = (u32)min(max(go, (int64_t)0), (int64_t)lim);
         }
@@ -126,32 +180,33 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
             const int u = lane + 64 * it;
             const int rr = u / NG, t = u - rr * NG;
             ex_ok[it] = u < rows * NG;
-            ex_rd[it] = (u32)(rr * nch * 16 + ((e0 + 12 * t) & ~3));
-            ex_wr[it] = (u32)((rr * PITCH + 4 * t) * 4);
+            ex_rd[it] = pk_base + (u32)(rr * nch * 16 + ((e0 + 12 * t) & ~3));     // LDS addresses: packed buffer 0, RGBX box
+            ex_wr[it] = pk_base - rgbx_bytes + (u32)((rr * PITCH + 4 * t) * 4);
+            asm volatile("" : "+v"(ex_rd[it]), "+v"(ex_wr[it]));                  // one register each, not a sum redone per frame
         }
     }
     const int kw = (rows * nch + 63) / 64;                          // DMA instructions per wave and frame (1 .. 3)
-    auto dma_issue = [&](int f, int pbuf) {
-        const u8* fb = s.p + (int64_t)f * s.fs;                     // scalar
+    // fb: the frame's base, scalar; the caller advances it by s.fs from one issue to the next
+    auto dma_issue = [&](const u8* fb, int pbuf) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const u32 ldst = __builtin_amdgcn_readfirstlane(pk_base + (u32)pbuf * pk_bytes + (u32)(i * 1024));
             if (i < kw && dma_ok[i]) glds16_hidden(fb, dma_off[i], ldst);       // (lane 0 of every i < kw is active: kw instructions per frame)
         }
     };
-    auto expand = [&](int pbuf) {
-        const char* pk = (const char*)srct + rgbx_bytes + pbuf * pk_bytes;
-        const u32 sh = (u32)(e0 & 3);
+    // packed -> RGBX.  A 4-pixel group is the 12 bytes from byte PH = e0 & 3 of four dwords, and pixel k's dword the four
+    // bytes from PH + 3 k (the top one is never read): PH is the same for the whole wave and for every frame, so each
+    // phase has its own copy in which one dword of the four needs no instruction and the others one v_alignbyte each
+    auto expand = [&](auto ph, int pbuf) {
+        constexpr int PH = decltype(ph)::value;
+        const u32 poff = (u32)pbuf * pk_bytes;
 #pragma unroll
         for (int it = 0; it < 3; ++it) {
             if (!ex_ok[it]) continue;
-            const u32* q = (const u32*)(pk + ex_rd[it]);
-            const u32 d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-            const u32 a = __builtin_amdgcn_alignbyte(d1, d0, sh), b = __builtin_amdgcn_alignbyte(d2, d1, sh);
-            const u32 c = __builtin_amdgcn_alignbyte(d3, d2, sh);      // a = R0G0B0R1  b = G1B1R2G2  c = B2R3G3B3
-            uint4 o;
-            o.x = a; o.y = __builtin_amdgcn_alignbyte(b, a, 3u); o.z = __builtin_amdgcn_alignbyte(c, b, 2u); o.w = c >> 8;
-            *(uint4*)((char*)srct + ex_wr[it]) = o;
+            const __attribute__((address_space(3))) u32* q = (const __attribute__((address_space(3))) u32*)(uintptr_t)(ex_rd[it] + poff);
+            const u32 dq[4] = {q[0], q[1], q[2], q[3]};
+            const wq_u32x4 o = {wq_bytes_at<PH>(dq), wq_bytes_at<PH + 3>(dq), wq_bytes_at<PH + 6>(dq), wq_bytes_at<PH + 9>(dq)};
+            *(__attribute__((address_space(3))) wq_u32x4*)(uintptr_t)ex_wr[it] = o;
         }
     };
 
@@ -275,48 +330,56 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
         }
     };
 
-    // rows 4 wave .. 4 wave + 3 of a slot -> global memory as dense 16-byte chunks (24 per 384-byte row)
-    const int rb16 = (int)((int64_t)d.w * C / 16);                  // chunks per image row (host: row bytes % 16 == 0)
-    auto flush = [&](int f, const u32* slot) {
-        u8* dframe = d.p + (int64_t)f * d.fs;
+    const WqFlush flush_slot(d, slots, lane, wave, txb, sy0);       // this wave's four rows of a slot -> a frame
+
+    // a fill-only block's columns of BOTH slots hold the fill from here on: no other wave writes them
+    if (fill_only) {
+        const u32 val = (u32)P.fill[0] | ((u32)P.fill[1] << 8) | ((u32)P.fill[2] << 16);
 #pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int ch = pass * 64 + lane;                        // 0 .. 95
-            const int r = wave * 4 + ch / 24, ck = ch - (ch / 24) * 24;
-            if (ch < 96 && sy0 + r < d.h && txb * 24 + ck < rb16) {
-                const uint4 o4 = *(const uint4*)(slot + r * 96 + ck * 4);
-                *(uint4*)(dframe + (int64_t)(sy0 + r) * d.rs + (int64_t)txb * (BW * C) + ck * 16) = o4;
-            }
+        for (int q = 0; q < 4; ++q) {
+            u32* ws = slots + (q >> 1) * (16 * 96) + ((q & 1) * 8 + (lane >> 3)) * 96 + wave * 24 + (lane & 7) * 3;
+            ws[0] = val | (val << 24); ws[1] = (val >> 8) | (val << 16); ws[2] = (val >> 16) | (val << 8);
         }
-    };
+    }
 
     // ---- frame loop.  Per wave: [counted wait: DMA f landed] expand f [lgkmcnt] issue DMA f+2, gather f, park f;
     // per workgroup: ONE barrier (the slot is complete); its rows leave at the start of the next iteration.  The slots
     // alternate: slot (f+1) & 1 is read by flush(f-1) at the start of iteration f, before that wave parks or reaches barrier f.
     // The wait is counted: the only loads this wave has issued after DMA f are the kw instructions of DMA f+1 (loads
-    // complete in order among themselves), so at most kw outstanding operations means DMA f is done.
-    if (wave_in) { dma_issue(f_begin, 0); if (f_begin + 1 < f_end) dma_issue(f_begin + 1, 1); }
+    // complete in order among themselves), so at most kw outstanding operations means DMA f is done.  A wave that issues
+    // no DMA (outside the image, or fill only) has nothing to wait for; it still flushes.
+    // The frame bases are scalar and advance by one frame stride per issue / per flush.
+    const u8* sdma = s.p + (int64_t)f_begin * s.fs;                 // next frame to stage
+    u8* dfl = d.p + (int64_t)f_begin * d.fs;                        // next frame to flush
+    if (wave_on) {
+        dma_issue(sdma, 0); sdma += s.fs;
+        if (f_begin + 1 < f_end) { dma_issue(sdma, 1); sdma += s.fs; }
+    }
+    const int ph = e0 & 3;
     int pb = 0;
 #pragma unroll 1
     for (int f = f_begin; f < f_end; ++f) {
-        u32* slot = slots + ((f - f_begin) & 1) * (16 * 96);
-        if (wave_in) {
+        const int par = (f - f_begin) & 1;
+        if (wave_on) {
             if (f + 1 >= f_end) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else if (kw == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
             else if (kw == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         }
-        if (f > f_begin) flush(f - 1, slots + ((f - 1 - f_begin) & 1) * (16 * 96));     // a whole iteration old at the next wait
-        if (wave_in) {
-            expand(pb);
+        if (f > f_begin) { flush_slot(dfl, par ^ 1); dfl += d.fs; }  // a whole iteration old at the next wait
+        if (wave_on) {
+            if (ph == 0) expand(std::integral_constant<int, 0>(), pb);
+            else if (ph == 1) expand(std::integral_constant<int, 1>(), pb);
+            else if (ph == 2) expand(std::integral_constant<int, 2>(), pb);
+            else expand(std::integral_constant<int, 3>(), pb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the expansion has read the packed rows: their buffer is free
-            if (f + 2 < f_end) dma_issue(f + 2, pb);
-            gather_frame(f, slot);
+            if (f + 2 < f_end) { dma_issue(sdma, pb); sdma += s.fs; }
+            gather_frame(f, slots + par * (16 * 96));
             pb ^= 1;
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
-    flush(f_end - 1, slots + ((f_end - 1 - f_begin) & 1) * (16 * 96));
+    flush_slot(dfl, (f_end - 1 - f_begin) & 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -332,7 +395,8 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
 // one box, one slot, six workgroups per CU — 1.43 ms per 128 4K frames at 22.5 degrees against 1.63 - 1.77 ms for frame loops
 // of 2 / 3 / 24 and 1.52 ms for affine_nearest_dma_kernel, profiles/r03_experiments/ab_nearest_wq.txt); IMGXF_AFFINE_FPB
 // selects the loop, which the tests cover.
-// Host: rows x nch <= 64 NQ_KW chunks per box, source / destination 16-byte aligned with 16-byte multiple rows.
+// Host: rows x nch <= 64 NQ_KW chunks per box, source / destination 16-byte aligned with 16-byte multiple rows and
+// h x row stride < 2^32 (32-bit lane offsets for the DMA and for the stores).
 // ---------------------------------------------------------------------------------------------------------------------
 // NQ_KW, the most DMA instructions per wave and frame, is in affine_route.h
 
@@ -405,8 +469,8 @@ __global__ __launch_bounds__(256) void affine_nearest_wq_kernel(View s, View d, 
         dma_off[i] = (u32)((int64_t)min(sy_lo + row, s.h - 1) * s.rs + min(a0 + ch * 16, last_chunk));     // host: frame bytes < 2^32
     }
     const u32 box_base = (u32)(uintptr_t)(__attribute__((address_space(3))) char*)boxes;
-    auto dma_issue = [&](int f, int pbuf) {
-        const u8* fb = s.p + (int64_t)f * s.fs;                         // scalar
+    // fb: the frame's base, scalar; the caller advances it by s.fs from one issue to the next
+    auto dma_issue = [&](const u8* fb, int pbuf) {
 #pragma unroll
         for (int i = 0; i < KW; ++i) {
             const u32 ldst = __builtin_amdgcn_readfirstlane(box_base + (u32)pbuf * box_bytes + (u32)(i * 1024));
@@ -432,36 +496,27 @@ __global__ __launch_bounds__(256) void affine_nearest_wq_kernel(View s, View d, 
             ws[2] = (px[2] >> 16) | (px[3] << 8);
         }
     };
-    const int rb16 = (int)((int64_t)d.w * C / 16);                      // chunks per image row (host: row bytes % 16 == 0)
-    auto flush = [&](int f, const u32* slot) {
-        u8* dframe = d.p + (int64_t)f * d.fs;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            const int ch = pass * 64 + lane;                            // 0 .. 95: rows 4 wave .. 4 wave + 3, 24 chunks each
-            const int r = wave * 4 + ch / 24, ck = ch - (ch / 24) * 24;
-            if (ch < 96 && sy0 + r < d.h && txb * 24 + ck < rb16) {
-                const uint4 o4 = *(const uint4*)(slot + r * 96 + ck * 4);
-                *(uint4*)(dframe + (int64_t)(sy0 + r) * d.rs + (int64_t)txb * (BW * C) + ck * 16) = o4;
-            }
-        }
-    };
+    const WqFlush flush_slot(d, slots, lane, wave, txb, sy0);
 
     // ---- frame loop.  Issue order per wave: DMA f (end of iteration f-2), stores of f-2 (iteration f-1), DMA f+1 (end of
     // iteration f-1); vector memory operations retire in order, so "at most KW outstanding" at the top of iteration f
     // means DMA f has landed.  Box buffer f & 1 is refilled with frame f+2 once gather f has read it (lgkmcnt(0)).
-    dma_issue(f_begin, 0);
-    if (f_begin + 1 < f_end) dma_issue(f_begin + 1, 1);
+    // The frame bases are scalar and advance by one frame stride per issue / per flush.
+    const u8* sdma = s.p + (int64_t)f_begin * s.fs;                     // next frame to stage
+    u8* dfl = d.p + (int64_t)f_begin * d.fs;                            // next frame to flush
+    dma_issue(sdma, 0); sdma += s.fs;
+    if (f_begin + 1 < f_end) { dma_issue(sdma, 1); sdma += s.fs; }
 #pragma unroll 1
     for (int f = f_begin; f < f_end; ++f) {
         const int it = f - f_begin;
         if (f + 1 >= f_end) nq_wait<0>(); else nq_wait<KW>();
-        if (it) flush(f - 1, slots + ((it - 1) & 1) * (16 * 96));
+        if (it) { flush_slot(dfl, (it - 1) & 1); dfl += d.fs; }
         gather_frame(it & 1, slots + (it & 1) * (16 * 96));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (f + 2 < f_end) dma_issue(f + 2, it & 1);
+        if (f + 2 < f_end) { dma_issue(sdma, it & 1); sdma += s.fs; }
         asm volatile("s_barrier" ::: "memory");
     }
-    flush(f_end - 1, slots + ((f_end - 1 - f_begin) & 1) * (16 * 96));
+    flush_slot(dfl, (f_end - 1 - f_begin) & 1);
 }
 
 } // namespace imgxf
