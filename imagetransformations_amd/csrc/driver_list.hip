@@ -3,7 +3,7 @@
 // gaussian_noise, blur — and the three further bodies of the later twelve-type driver — flip, crop + resize (rand_crop),
 // perspective warp; its zoom is scale — each entry with its own frame, type and drawn value, bit for bit what the
 // per-type entry points return.  The float Gaussian's four kernel families agree to 1e-5, not to the byte, so a blur is
-// taken where the per-type dispatcher itself would use the LDS-tiled kernel (sepconv_family.h answers that on the host),
+// taken where the per-type dispatcher itself would use the LDS-tiled kernel (sepconv_route.h answers that on the host),
 // whose statements the blur units compile too; the others are refused to the caller's route.
 //
 // HOST half (imgxf_driver_list_layout_host, no device work): from each entry's geometry and parameters one block of
@@ -32,7 +32,7 @@
 #include "pixel_ops.h"
 #include "resample_coeffs.h"
 #include "resample_list.h"
-#include "sepconv_family.h"
+#include "sepconv_route.h"
 #include <map>
 #include <algorithm>
 #include <vector>
@@ -271,6 +271,7 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         return (int)axes.size() - 1;
     };
     // a Gaussian's taps, shared by the entries of equal (code, ksize, sigma): imgxf_gaussian_u8's / imgxf_gaussian_cv_fixed_u8's
+    const SepconvKnobs sepconv_knobs_now = sepconv_knobs();
     struct Blur { int rc, ks, coeffs; bool used; Taps taps; };
     std::map<std::array<int64_t, 3>, int> blur_index;
     std::vector<Blur> blurs;
@@ -391,7 +392,7 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
                 // float: only where the per-type route would run these statements too; the fixed-point families are
                 // integer-exact and agree to the byte
                 if (b.rc != IMGXF_OK) st = IMGXF_DRIVER_REFUSED_OTHER;
-                else if (!fixed && sepconv_family_c3_dense(false, b.ks / 2, g.h, g.w, b.taps) != SEPCONV_TILE)
+                else if (!fixed && sepconv_route_c3_dense(false, b.ks / 2, g.h, g.w, b.taps, sepconv_knobs_now) != SEPCONV_TILE)
                     st = IMGXF_DRIVER_REFUSED_FAMILY;
                 else if (dl_blur_lds(b.ks) > lds_budget) st = IMGXF_DRIVER_REFUSED_LDS;
                 else {

@@ -1,16 +1,13 @@
 // C-ABI entry points for the separable filters (Gaussian blur).
 // Replaces cv2.GaussianBlur at /root/reference/transformation.py:249.
-#include "sepconv_tile.inc"
+#include "sepconv_route.h"
 #include <math.h>
 #include <string.h>
 
 namespace imgxf {
-int sepconv_c1(int R, const View&, const View&, const View&, const Taps&, int, hipStream_t);
-int sepconv_c3(int R, const View&, const View&, const View&, const Taps&, int, hipStream_t);
-int sepconv_c4(int R, const View&, const View&, const View&, const Taps&, int, hipStream_t);
-int sepconv_fx_c1(int R, const View&, const View&, const View&, const Taps&, int, hipStream_t);
-int sepconv_fx_c3(int R, const View&, const View&, const View&, const Taps&, int, hipStream_t);
-int sepconv_fx_c4(int R, const View&, const View&, const View&, const Taps&, int, hipStream_t);
+// sepconv_launch.inc; one instantiation in each of sepconv_{,fx_}c{1,3,4}.hip
+template <int C, bool FIXED>
+int launch_sepconv(const SepconvPlan&, const View&, const View&, const View&, const Taps&, hipStream_t);
 
 static int run_sepconv(const imgxf_view* src, const imgxf_view* dst, const float* kx, int nkx,
                        const float* ky, int nky, int border, const imgxf_view* dst_f32,
@@ -37,19 +34,16 @@ static int run_sepconv(const imgxf_view* src, const imgxf_view* dst, const float
     for (int i = 0; i < nky; ++i) taps.y[R - nky / 2 + i] = ky[i];
     const View s = make_view(src), d = make_view(dst);
     hipStream_t st = (hipStream_t)stream;
-    if (fixed) {
-        switch (src->c) {
-            case 1: return sepconv_fx_c1(R, s, d, df, taps, border, st);
-            case 3: return sepconv_fx_c3(R, s, d, df, taps, border, st);
-            case 4: return sepconv_fx_c4(R, s, d, df, taps, border, st);
-            default: return IMGXF_ERR_UNSUPPORTED;
-        }
-    }
-    switch (src->c) {
-        case 1: return sepconv_c1(R, s, d, df, taps, border, st);
-        case 3: return sepconv_c3(R, s, d, df, taps, border, st);
-        case 4: return sepconv_c4(R, s, d, df, taps, border, st);
-        default: return IMGXF_ERR_UNSUPPORTED;
+    if (src->c != 1 && src->c != 3 && src->c != 4) return IMGXF_ERR_UNSUPPORTED;
+    SepconvPlan plan;
+    IMGXF_CHECK(plan_sepconv(src->c, fixed, R, s, d, df, taps, border, sepconv_knobs(), &plan));
+    switch (2 * src->c + fixed) {
+        case 2: return launch_sepconv<1, false>(plan, s, d, df, taps, st);
+        case 3: return launch_sepconv<1, true>(plan, s, d, df, taps, st);
+        case 6: return launch_sepconv<3, false>(plan, s, d, df, taps, st);
+        case 7: return launch_sepconv<3, true>(plan, s, d, df, taps, st);
+        case 8: return launch_sepconv<4, false>(plan, s, d, df, taps, st);
+        default: return launch_sepconv<4, true>(plan, s, d, df, taps, st);
     }
 }
 } // namespace imgxf
@@ -65,7 +59,7 @@ IMGXF_API int imgxf_sepconv_u8(const imgxf_view* src, const imgxf_view* dst, con
 IMGXF_API int imgxf_gaussian_u8(const imgxf_view* src, const imgxf_view* dst, int ksize,
                                 double sigma, const imgxf_view* dst_f32, void* stream) {
     float kf[31];
-    IMGXF_CHECK(gaussian_taps(ksize, sigma, kf));          // sepconv_family.h: the list layout takes the same taps
+    IMGXF_CHECK(gaussian_taps(ksize, sigma, kf));          // sepconv_route.h: the list layout takes the same taps
     return run_sepconv(src, dst, kf, ksize, kf, ksize, IMGXF_BORDER_REFLECT_101, dst_f32, stream);
 }
 
@@ -83,6 +77,6 @@ IMGXF_API int imgxf_sepconv_fixed_u8(const imgxf_view* src, const imgxf_view* ds
 IMGXF_API int imgxf_gaussian_cv_fixed_u8(const imgxf_view* src, const imgxf_view* dst, int ksize,
                                          double sigma, void* stream) {
     uint16_t k[31];
-    IMGXF_CHECK(gaussian_taps_cv_fixed(ksize, sigma, k));  // sepconv_family.h: the list layout takes the same taps
+    IMGXF_CHECK(gaussian_taps_cv_fixed(ksize, sigma, k));  // sepconv_route.h: the list layout takes the same taps
     return imgxf_sepconv_fixed_u8(src, dst, k, ksize, k, ksize, IMGXF_BORDER_REFLECT_101, stream);
 }

@@ -180,19 +180,10 @@ __global__ __launch_bounds__(256, 3) void sepconv_fx_mfma_kernel(View src, View 
     flush(nob - 1);
 }
 
+// the launch record of plan_mfma (sepconv_route.h), fixed point
 template <int R>
-inline int launch_sepconv_fx_mfma(const View& s, const View& d, const Taps& taps, hipStream_t st) {
-    const int ng = (int)((s.rowbytes() + 31) / 32), ntx = (ng + 3) / 4;
-    const int nblocks = (s.h + 31) / 32;
-    int bpc = nblocks;
-    auto count = [&]() { return (int64_t)ntx * ((nblocks + bpc - 1) / bpc) * s.n; };
-    while (count() < 2048 && bpc > 8) bpc = (nblocks + (nblocks + bpc - 1) / bpc) / ((nblocks + bpc - 1) / bpc + 1);
-    if (const char* sh = knob_str(K_MFMA2_BPC)) bpc = std::max(1, std::min(atoi(sh), nblocks));
-    const int nchunks = (nblocks + bpc - 1) / bpc;
-    const int64_t nwg = (int64_t)ntx * nchunks * s.n;
-    if (nwg > 0x7fffffff) return IMGXF_ERR_SHAPE;
-    hipLaunchKernelGGL((sepconv_fx_mfma_kernel<R>), dim3((unsigned)nwg), dim3(256), 0, st, s, d, taps, ntx, nchunks, bpc);
-    return launch_status();
+inline void launch_sepconv_fx_mfma(const SepconvLaunch& L, const View& s, const View& d, const Taps& taps, hipStream_t st) {
+    hipLaunchKernelGGL((sepconv_fx_mfma_kernel<R>), L.grid, L.block, L.lds, st, s, d, taps, L.ntx, L.nchunks, L.bpc);
 }
 
 } // namespace imgxf

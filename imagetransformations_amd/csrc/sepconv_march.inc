@@ -37,11 +37,7 @@ namespace imgxf {
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int MARCH_SLOT = 1024 + 32;                        // [strip row 1 KiB][left halo block][right halo block]
-constexpr int march_unroll(int K) { return K < 5 ? 2 : 1; }  // row loop covers K * U rows: ring index and slot static
-constexpr int march_rows_in_flight(int R) { return (2 * R + 1) * march_unroll(2 * R + 1); }
-constexpr int march_wave_lds(int J) { return 16 + J * MARCH_SLOT; }   // 16 B pad: lane 0's left read of slot 0
-
+// (MARCH_SLOT, march_unroll, march_rows_in_flight, march_wave_lds: sepconv_route.h, which sizes the launch with them)
 #define IMGXF_GLDS16(gptr, lptr, aux)                                                         \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),   \
                                      (__attribute__((address_space(3))) void*)(lptr), 16, 0, aux)
@@ -279,67 +275,12 @@ __global__ __launch_bounds__(256) void sepconv_march_kernel(View src, View dst, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// Frames per super-row: the G <= 8 with the fewest waves per frame row, ceil(G * bpr / 64) / G
-// (4K RGB: bpr 720 -> G 4, 45 strips; 1080p: bpr 360 -> G 8, 45 strips); every lane offset
-// (G - 1) * frame_stride + rowbytes must fit 32 bits.
-inline int march_group(const View& s, const View& d, const View& df, int n) {
-    const int64_t bpr = s.rowbytes() / 16;
-    int best = 1;
-    int64_t best_w = (bpr + 63) / 64;                       // waves per frame row, scaled by G below
-    for (int g = 2; g <= 8 && g <= n; ++g) {
-        const int64_t lim = (int64_t)1 << 32;
-        if ((g - 1) * s.fs + s.rowbytes() >= lim || (g - 1) * d.fs + s.rowbytes() >= lim) break;
-        if (df.p && (g - 1) * df.fs + 4 * s.rowbytes() >= lim) break;
-        const int64_t w = (g * bpr + 63) / 64;
-        if (w * best < best_w * g) { best = g; best_w = w; }   // w / g < best_w / best
-    }
-    return best;
-}
-
-inline int march_rows_per_wave(const View& s, int G) {
-    // ~64-row chunks, balanced so the last chunk is not a stub (2160 rows -> 34 x 64): the 2R re-read
-    // rows per chunk cost 6 % for a 5x5 against 4 % at 96 rows, but the finer grid drains more evenly
-    // (A/B on two boxes, 128 4K / 512 1080p frames: 1.151 vs 1.178 ms and 1.187 vs 1.216 ms; 32- and
-    // 47-row chunks lose to the halo again).  A small batch still needs >= ~1024 waves to fill 256 CUs.
-    const int64_t strips = (G * (s.rowbytes() / 16) + 63) / 64;
-    const int64_t groups = (s.n + G - 1) / G;
-    int64_t nchunks = (s.h + 63) / 64;
-    while (nchunks * strips * groups < 1024 && (s.h + nchunks - 1) / nchunks > 16) nchunks *= 2;
-    return (int)((s.h + nchunks - 1) / nchunks);
-}
-
-template <int C, int R, bool FIXED = false>
-inline int launch_sepconv_march(const View& s0, const View& d0, const View& df0, const Taps& taps, hipStream_t st) {
-    const int g_env = knob_int(K_MARCH_GROUP, 0);   // tuning knobs
-    const int spb_env = knob_int(K_MARCH_SPB, 0);
-    const int bpr = (int)(s0.rowbytes() / 16);
-    // whole groups of G frames first, then the remainder with the best group size that still fits
-    for (int f0 = 0; f0 < s0.n;) {
-        const int left = s0.n - f0;
-        int G = march_group(s0, d0, df0, left);
-        if (g_env >= 1 && g_env <= 8 && g_env <= left) G = g_env;   // (development: unchecked 32-bit offsets)
-        View s = s0, d = d0, df = df0;
-        s.p += (int64_t)f0 * s0.fs; d.p += (int64_t)f0 * d0.fs;
-        if (df.p) df.p += (int64_t)f0 * df0.fs;
-        const int groups = left / G;
-        s.n = d.n = df.n = groups * G;
-        const int rpw = march_rows_per_wave(s, G);
-        const int nchunks = (s.h + rpw - 1) / rpw;
-        // strips per workgroup: single-wave workgroups (finest dispatch granularity; measured 1 % faster
-        // than 2..4 adjacent strips per workgroup on every box)
-        const int nstrips = (G * bpr + 63) / 64;
-        int spb = 1;
-        if (spb_env >= 1 && spb_env <= 4) spb = spb_env;
-        const int gx = (nstrips + spb - 1) / spb;
-        const int64_t nwg = (int64_t)gx * nchunks * groups;
-        if (nwg > 0x7fffffff) return IMGXF_ERR_SHAPE;
-        const size_t lds = spb * march_wave_lds(march_rows_in_flight(R));
-        hipLaunchKernelGGL((sepconv_march_kernel<C, R, FIXED>), dim3((unsigned)nwg), dim3(64 * spb), lds, st,
-                           s, d, df, taps, rpw, nchunks, gx, G, bpr);
-        IMGXF_CHECK(launch_status());
-        f0 += groups * G;
-    }
-    return IMGXF_OK;
+// one launch record of plan_march (sepconv_route.h): the views are those of the record's frames
+template <int C, int R, bool FIXED>
+inline void launch_sepconv_march(const SepconvLaunch& L, const View& s, const View& d, const View& df, const Taps& taps,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL((sepconv_march_kernel<C, R, FIXED>), L.grid, L.block, L.lds, st, s, d, df, taps, L.rpw, L.nchunks, L.gx, L.G,
+                       L.bpr);
 }
 
 } // namespace imgxf

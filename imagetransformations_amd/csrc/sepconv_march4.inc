@@ -21,15 +21,7 @@
 
 namespace imgxf {
 
-constexpr int march4_slot_bytes(int NE) { return 256 + 32 * NE; }
-constexpr int march4_wave_lds(int NE, int J) { return J * march4_slot_bytes(NE) + 16; }
-constexpr int MARCH4_EXCH_BYTES = 272 * 4;     // PX: the horizontal results of one row, 252 (+ lane 63's 10) floats
-// K <= 15: the row loop is unrolled by K, the filtered rows live in a register ring with static
-// indices and J = K rows are in flight.  Larger K: groups of 4 rows with a history array that is
-// shifted by 4 after every group (keeps the body inside the instruction cache), two groups per
-// loop iteration so that the J = 8 LDS slots are compile-time constants as well.
-constexpr bool march4_ring(int K) { return K <= 15; }
-constexpr int march4_rows_in_flight(int K) { return march4_ring(K) ? K : 8; }
+// (march4_slot_bytes, march4_wave_lds, MARCH4_EXCH_BYTES, march4_ring, march4_rows_in_flight: sepconv_route.h)
 
 // SYM: the taps are symmetric and the same in x and y (every Gaussian): both passes index the
 // R+1 distinct values, which then fit the SGPR file as {w,w} pairs — with 2K separate weights
@@ -256,35 +248,20 @@ __global__ __launch_bounds__(256) void sepconv_march4_kernel(View src, View dst,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int C, int R, bool FIXED = false>
-inline int launch_sepconv_march4(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
-    constexpr int J = march4_rows_in_flight(2 * R + 1), NE = (R * C + 15) / 16;
-    const bool no_px = knob_set(K_MARCH4_NO_PX);
-    const bool px = C == 3 && !no_px;
-    int64_t nchunks = (s.h + 239) / 240;    // tall chunks: the 2R re-filtered rows per chunk are pure VALU cost
-    const int64_t wg_cols = px ? (s.rowbytes() + 4 * 252 - 1) / (4 * 252) : (s.rowbytes() + 1023) / 1024;
-    while (nchunks * wg_cols * s.n < 2048 && (s.h + nchunks - 1) / nchunks > 4 * R + 8) nchunks *= 2;
-    int rpw = (int)((s.h + nchunks - 1) / nchunks);
-    // a chunk filters rpw + 2R input rows in steps of J: make that a multiple of J so that no step is wasted
-    rpw += (J - (rpw + 2 * R) % J) % J;
-    nchunks = (s.h + rpw - 1) / rpw;
-    dim3 grid((unsigned)wg_cols, (unsigned)nchunks, (unsigned)s.n);
-    bool sym = true;
-    for (int i = 0; i < 2 * R + 1; ++i)
-        sym = sym && taps.x[i] == taps.x[2 * R - i] && taps.x[i] == taps.y[i];
-    if (FIXED && !sym) return IMGXF_ERR_UNSUPPORTED;     // callers send asymmetric fixed-point taps to the tile kernel
-    const size_t lds = 4 * march4_wave_lds(NE, J);
+// the launch record of plan_march4 (sepconv_route.h); the asymmetric (SYM = false) instances are float ones only: the
+// planner sends asymmetric fixed-point taps to the tile kernel
+template <int C, int R, bool FIXED>
+inline void launch_sepconv_march4(const SepconvPlan& P, const SepconvLaunch& L, const View& s, const View& d, const View& df,
+                                  const Taps& taps, hipStream_t st) {
     if constexpr (C == 3) {
-        if (px) {
-            const size_t ldsp = 4 * (march4_wave_lds(NE, J) + MARCH4_EXCH_BYTES);
-            if (sym) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, true, FIXED, true>), grid, dim3(256), ldsp, st, s, d, df, taps, rpw);
-            else if (!FIXED) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, false, false, true>), grid, dim3(256), ldsp, st, s, d, df, taps, rpw);
-            return launch_status();
+        if (P.px) {
+            if (P.sym) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, true, FIXED, true>), L.grid, L.block, L.lds, st, s, d, df, taps, L.rpw);
+            else if (!FIXED) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, false, false, true>), L.grid, L.block, L.lds, st, s, d, df, taps, L.rpw);
+            return;
         }
     }
-    if (sym) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, true, FIXED>), grid, dim3(256), lds, st, s, d, df, taps, rpw);
-    else if (!FIXED) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, false, false>), grid, dim3(256), lds, st, s, d, df, taps, rpw);
-    return launch_status();
+    if (P.sym) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, true, FIXED>), L.grid, L.block, L.lds, st, s, d, df, taps, L.rpw);
+    else if (!FIXED) hipLaunchKernelGGL((sepconv_march4_kernel<C, R, false, false>), L.grid, L.block, L.lds, st, s, d, df, taps, L.rpw);
 }
 
 } // namespace imgxf

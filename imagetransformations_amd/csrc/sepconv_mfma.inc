@@ -254,22 +254,10 @@ __global__ __launch_bounds__(256, 2) void sepconv_mfma2_rgb_kernel(View src, Vie
     flush(nob - 1);                                          // the last block's tile, written in the last iteration
 }
 
+// the launch record of plan_mfma (sepconv_route.h), float
 template <int R>
-inline int launch_sepconv_mfma(const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
-    const int ng = (int)((s.rowbytes() + 31) / 32), ntx = (ng + 3) / 4;
-    const int nblocks = (s.h + 31) / 32;
-    // one frame, one 128-byte column set, one chunk of whole 32-row blocks per workgroup; every chunk costs one
-    // extra H block and one operand set-up (a few thousand VALU per wave)
-    int bpc = nblocks;
-    auto count = [&]() { return (int64_t)ntx * ((nblocks + bpc - 1) / bpc) * s.n; };
-    // (64 4K frames: whole-frame columns 1.10 ms, 2 chunks 1.12, 4 chunks 1.21): split only to fill the chip
-    while (count() < 2048 && bpc > 8) bpc = (nblocks + (nblocks + bpc - 1) / bpc) / ((nblocks + bpc - 1) / bpc + 1);   // one more chunk
-    if (const char* sh = knob_str(K_MFMA2_BPC)) bpc = std::max(1, std::min(atoi(sh), nblocks));
-    const int nchunks = (nblocks + bpc - 1) / bpc;
-    const int64_t nwg = (int64_t)ntx * nchunks * s.n;
-    if (nwg > 0x7fffffff) return IMGXF_ERR_SHAPE;
-    hipLaunchKernelGGL((sepconv_mfma2_rgb_kernel<R>), dim3((unsigned)nwg), dim3(256), 0, st, s, d, df, taps, ntx, nchunks, bpc);
-    return launch_status();
+inline void launch_sepconv_mfma(const SepconvLaunch& L, const View& s, const View& d, const View& df, const Taps& taps, hipStream_t st) {
+    hipLaunchKernelGGL((sepconv_mfma2_rgb_kernel<R>), L.grid, L.block, L.lds, st, s, d, df, taps, L.ntx, L.nchunks, L.bpc);
 }
 
 } // namespace imgxf

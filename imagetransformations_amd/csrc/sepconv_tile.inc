@@ -15,7 +15,7 @@
 //            stores packed uint8 (round-half-even, saturate).
 #pragma once
 #include "imgxf_common.h"
-#include "sepconv_family.h"
+#include "sepconv_route.h"
 
 namespace imgxf {
 
@@ -143,29 +143,12 @@ __global__ __launch_bounds__(256) void sepconv_tile_kernel(View src, View dst, V
                                        taps.x, taps.y, border, Hs);
 }
 
-template <int C, int R, bool FIXED = false>
-inline int launch_sepconv_tile(const View& s, const View& d, const View& df, const Taps& taps,
-                               int border, hipStream_t st) {
-    constexpr int TH = 32;
-    constexpr size_t lds = (size_t)(TH + 2 * R) * 256 * sizeof(float);
-    static_assert(lds <= 65536, "tile exceeds the default dynamic LDS limit");
-    dim3 grid((unsigned)((s.rowbytes() + 255) / 256), (unsigned)((s.h + TH - 1) / TH), (unsigned)s.n);
-    hipLaunchKernelGGL((sepconv_tile_kernel<C, R, TH, FIXED>), grid, dim3(256), lds, st, s, d, df, taps,
-                       border);
-    return launch_status();
-}
-
-template <int C, bool FIXED = false>
-inline int dispatch_sepconv_tile(int R, const View& s, const View& d, const View& df,
-                                 const Taps& taps, int border, hipStream_t st) {
-    switch (R) {
-#define IMGXF_CASE(r) case r: return launch_sepconv_tile<C, r, FIXED>(s, d, df, taps, border, st);
-        IMGXF_CASE(1) IMGXF_CASE(2) IMGXF_CASE(3) IMGXF_CASE(4) IMGXF_CASE(5)
-        IMGXF_CASE(6) IMGXF_CASE(7) IMGXF_CASE(8) IMGXF_CASE(9) IMGXF_CASE(10)
-        IMGXF_CASE(11) IMGXF_CASE(12) IMGXF_CASE(13) IMGXF_CASE(14) IMGXF_CASE(15)
-#undef IMGXF_CASE
-        default: return IMGXF_ERR_UNSUPPORTED;
-    }
+// the launch record of plan_tile (sepconv_route.h)
+template <int C, int R, bool FIXED>
+inline void launch_sepconv_tile(const SepconvLaunch& L, const View& s, const View& d, const View& df, const Taps& taps, int border,
+                                hipStream_t st) {
+    static_assert((size_t)(SEPCONV_TILE_H + 2 * R) * 256 * sizeof(float) <= 65536, "tile exceeds the default dynamic LDS limit");
+    hipLaunchKernelGGL((sepconv_tile_kernel<C, R, SEPCONV_TILE_H, FIXED>), L.grid, L.block, L.lds, st, s, d, df, taps, border);
 }
 
 } // namespace imgxf

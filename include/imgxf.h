@@ -990,7 +990,7 @@ int imgxf_resized_crop_list(const void* block_host, size_t block_bytes, const vo
  * distinct (fixed, radius) among the blur entries — the drivers' grid has ten radii — whatever the number of frames,
  * entries or sizes.  A work unit is a band of output rows of one entry = one workgroup.
  * Blur is taken where the per-type dispatcher would serve a contiguous, 16-byte-aligned [n][h][w][3] batch of that size and
- * radius with the LDS-tiled kernel, whose statements the blur units compile too (sepconv_tile.inc): the float Gaussian's
+ * radius with the LDS-tiled kernel (csrc/sepconv_route.h: the planner of imgxf_sepconv_u8 itself), whose statements the blur units compile too (sepconv_tile.inc): the float Gaussian's
  * other kernel families agree with it to 1e-5, not to the byte, so those entries are refused (REFUSED_FAMILY) and keep
  * their own kernels.  The fixed-point evaluation is integer-exact in every family and is always taken. */
 enum {

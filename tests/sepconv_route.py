@@ -1,27 +1,28 @@
 """Which kernel family and radius the separable-filter dispatchers launch: a restatement of the host code in
 imagetransformations_amd/csrc, at the default knobs, for tests that must know it without a device
 (test_sepconv_route.py) or that pin a geometry to a kernel (test_gpu_sepconv_channels.py, test_gpu_sepconv_borders.py).
-A change to the limits in csrc changes this function with it."""
+test_sepconv_route.py holds it to the planner (csrc/sepconv_route.h) through tools/sepconv_launch_trace.hip, so a change
+to the limits in csrc changes this function with it."""
 REFLECT_101, REFLECT = 0, 1                     # include/imgxf.h: IMGXF_BORDER_REFLECT_101, IMGXF_BORDER_REFLECT
 
 
 def _march_eligible(c, R, h, w, aligned, border):
-    """sepconv_family.h:16-24"""
+    """sepconv_route.h: march_eligible"""
     rb = w * c
     return (border == REFLECT_101 and (R + 1) * c <= 16 and w >= R + 1 and h >= R + 1
             and rb % 16 == 0 and rb > 1024 and aligned)
 
 
 def _march4_eligible(c, R, h, w, aligned, border):
-    """sepconv_family.h:26-34"""
+    """sepconv_route.h: march4_eligible"""
     rb = w * c
     return (border == REFLECT_101 and 1 <= R <= 15 and w >= R + 1 and h >= R + 1
             and rb % 16 == 0 and rb >= 256 + 32 * ((R * c + 15) // 16) and aligned)
 
 
 def _mfma_eligible(c, R, h, w, aligned, border, taps_fit_mfma):
-    """sepconv_family.h:36-55 (float) and :58-73 (fixed) without the tap tests, which the caller states as
-    taps_fit_mfma; frames of 4 GiB and more are not restated."""
+    """sepconv_route.h: mfma_views_eligible, without the tap tests of mfma_eligible (float) and fx_mfma_eligible (fixed),
+    which the caller states as taps_fit_mfma; frames of 4 GiB and more are not restated."""
     rb = w * c
     return (c == 3 and border == REFLECT_101 and taps_fit_mfma and 2 <= R <= 15 and w >= 17 and h >= 32
             and rb % 16 == 0 and rb >= 256 and aligned)
@@ -34,25 +35,25 @@ def sepconv_route(c, fixed, R, h, w, *, aligned=True, border=REFLECT_101, sym=Tr
     sym: kx is symmetric and ky == kx (every Gaussian); it selects the SYM instantiation of the marching-4 kernel and
     is a condition of the fixed-point one.  f32: an fp32 side output is asked for (float path only).
     taps_fit_mfma: the range tests of mfma_eligible / fx_mfma_eligible hold (normalised Gaussians: yes)."""
-    if c == 3:                                                              # sepconv_family.h:81-95
+    if c == 3:                                                              # route_family; march_has, mfma_has, march4_has
         if 1 <= R <= 4 and _march_eligible(3, R, h, w, aligned, border):
-            return "march", R                                               # sepconv_c3.hip:14, sepconv_fx_c3.hip:14
+            return "march", R
         if fixed:
             if R >= 5 and not f32 and _mfma_eligible(3, R, h, w, aligned, border, taps_fit_mfma):
-                return "mfma", R                                            # sepconv_fx_c3.hip:22
+                return "mfma", R                                            # SepconvKnobs::fx_mfma_min_r
             if not sym:
                 return "tile", R
         elif R >= 6 and _mfma_eligible(3, R, h, w, aligned, border, taps_fit_mfma):
-            return "mfma", R                                                # sepconv_c3.hip:22
+            return "mfma", R                                                # SepconvKnobs::mfma_min_r
         if 5 <= R <= 15 and _march4_eligible(3, R, h, w, aligned, border):
-            return "march4", R                                              # sepconv_c3.hip:30, sepconv_fx_c3.hip:30
+            return "march4", R
         return "tile", R
-    march_max = {1: 5, 4: 3}[c]                                             # sepconv_{,fx_}c1.hip:13, sepconv_{,fx_}c4.hip:13
+    march_max = {1: 5, 4: 3}[c]                                             # march_max_r
     if 1 <= R <= march_max and _march_eligible(c, R, h, w, aligned, border):
         return "march", R
     if (sym or not fixed) and march_max < R <= 15 and _march4_eligible(c, R, h, w, aligned, border):
-        return "march4", R                                                  # sepconv_{,fx_}c1.hip:20-23, sepconv_{,fx_}c4.hip:20-23
-    return "tile", R                                                        # sepconv_tile.inc:163-165: R = 1 ... 15
+        return "march4", R
+    return "tile", R                                                        # tile_has: R = 1 ... 15
 
 
 def required_instances():

@@ -1,15 +1,26 @@
 """sepconv_route (a restatement of the separable-filter dispatchers, tests/sepconv_route.py) against the library's own
 host code where that can be asked without a device, and the parameter grids of the GPU tests mapped through it: together
-they must reach every instantiation the gray and RGBA dispatchers can launch.  No device."""
+they must reach every instantiation the gray and RGBA dispatchers can launch.  The planner itself (csrc/sepconv_route.h) is
+asked through the plan build of tools/sepconv_launch_trace.hip: what it plans must be what sepconv_route states.  No device."""
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
+import pytest
 
 from oracle import imgxf_oracle as O
-from sepconv_route import REFLECT, instance, required_instances, sepconv_route
+from sepconv_route import REFLECT, REFLECT_101, instance, required_instances, sepconv_route
 from test_driver_list_blur_host import BLUR, RADII, SIZES, _ksize, _layout
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
+SRC_BASE, DST_BASE, F32_BASE = 0x7F1000000000, 0x7F2000000000, 0x7F3000000000     # 16-byte aligned, as the allocator's blocks are
 
 
 def test_rgb_float_route_agrees_with_the_list_layout():
-    """driver_list.layout refuses a float blur (REFUSED_FAMILY) exactly where sepconv_family_c3_dense reports another
+    """driver_list.layout refuses a float blur (REFUSED_FAMILY) exactly where sepconv_route_c3_dense reports another
     family than the tile kernel for the frame."""
     from imagetransformations_amd import driver_list as dl
     entries = [(f, r) for f in range(len(SIZES)) for r in RADII]
@@ -97,3 +108,130 @@ def test_references_of_the_gpu_files():
         assert k.dtype == np.float32 and k.min() > 0 and abs(float(k.astype(np.float64).sum()) - 1) < 1e-6
         assert sum(T.integer_taps(rng, n)) == 256
     assert not B.borders_can_differ(1, 1, 31, 31) and not B.borders_can_differ(5, 1, 1, 9) and B.borders_can_differ(5, 1, 3, 1)
+
+
+# ---- the planner (csrc/sepconv_route.h) against the restatement -------------------------------------------------------
+def _taps_fit_mfma(fixed, kx, ky):
+    """The tap tests of mfma_eligible (f16 range of the operands) and fx_mfma_eligible (signed bytes, sums <= 256)."""
+    if fixed:
+        ix, iy = [round(float(v) * 256) for v in kx], [round(float(v) * 256) for v in ky]
+        return max(ix) <= 63 and max(iy) <= 127 and min(ix + iy) >= 0 and sum(ix) <= 256 and sum(iy) <= 256
+    ax, ay = np.abs(np.asarray(kx, np.float32)), np.abs(np.asarray(ky, np.float32))
+    return bool((ax * np.float32(32768) <= 65504).all() and (ay * np.float32(32768) <= 65504).all() and float(ax.sum()) * 255 <= 65504)
+
+
+def _tap_sets(fixed, R):
+    """(kx, ky, sym) of radius R: the Gaussian, asymmetric taps and (float) a symmetric set outside the f16 range."""
+    import test_gpu_sepconv_channels as T
+    k = 2 * R + 1
+    rng = np.random.default_rng(R)
+    if fixed:
+        g = [int(v) / 256 for v in O.gaussian_kernel_cv_fixed(k, k / 6)]
+        a = [v / 256 for v in T.integer_taps(rng, k)]
+        return [(g, g, True), (a, g, False)]
+    g = [float(v) for v in np.asarray(O.gaussian_kernel1d(k, k / 6), np.float32)]
+    a = [float(v) for v in T.positive_taps(rng, k)]
+    return [(g, g, True), (a, g, False), ([2.0] * k, [2.0] * k, True)]
+
+
+def _shapes():
+    """(h, w) of test_route_edges, of the GPU grids and of the list layout's host test."""
+    import test_gpu_sepconv_borders as B
+    import test_gpu_sepconv_channels as T
+    edges = [(6, 1040), (5, 1040), (6, 1024), (7, 288), (7, 272), (4, 260), (5, 260), (14, 96), (14, 92), (20, 80), (20, 1040), (40, 352),
+             (40, 1040), (40, 264)]
+    shapes = set(edges) | {(h, w) for c, h, w, R in T.GRID} | {(h, w) for c, h, w, nkx, nky in T.SIGNED}
+    shapes |= {(h, w) for c, h, w, R, family in T.FIXED_ASYM} | {(T.BATCH_H, w) for c, n, w, R in T.BATCHES}
+    return sorted(shapes | set(B.ALIGNED.values()) | set(B.FRAMES) | set(SIZES))
+
+
+def _planner_grid():
+    """(c, fixed, R, h, w, aligned, border, f32, kx, ky, sym) of every case, at the default knobs."""
+    grid = []
+    for c in (1, 3, 4):
+        for fixed in (False, True):
+            for R in range(1, 16):
+                for kx, ky, sym in _tap_sets(fixed, R):
+                    for h, w in _shapes():
+                        for aligned in (True, False):
+                            for border in (REFLECT_101, REFLECT):
+                                for f32 in ((False,) if fixed else (False, True)):
+                                    grid.append((c, fixed, R, h, w, aligned, border, f32, kx, ky, sym))
+    return grid
+
+
+def _planner_case_line(case):
+    c, fixed, R, h, w, aligned, border, f32, kx, ky, sym = case
+    n, rb = 2, w * c
+    taps = " ".join(float(np.float32(v)).hex() for v in list(kx) + list(ky))
+    src = SRC_BASE + (0 if aligned else 4)                    # a base address off the 16-byte grid: no fast kernel takes it
+    f = (F32_BASE, 4 * rb, 4 * rb * h) if f32 else (0, 0, 0)
+    return f"{c} {int(fixed)} {len(kx)} {len(ky)} {taps} {n} {h} {w} {src} {rb} {rb * h} {DST_BASE} {rb} {rb * h} {f[0]} {f[1]} {f[2]} {border} -"
+
+
+KERNEL = re.compile(r"sepconv_(march|march4|tile|mfma2_rgb|fx_mfma)_kernel<([\w, ]+)>$")
+
+
+def _planned(kernel):
+    """(family, c, R, fixed, sym) that an instantiation name states; c, fixed and sym are None where the name has none."""
+    name, args = KERNEL.match(kernel).groups()
+    a = [v.strip() for v in args.split(",")]
+    flag = lambda v: v == "true"
+    if name == "march":
+        return "march", int(a[0]), int(a[1]), flag(a[2]), None
+    if name == "march4":
+        return "march4", int(a[0]), int(a[1]), flag(a[3]), flag(a[2])
+    if name == "tile":
+        return "tile", int(a[0]), int(a[1]), flag(a[3]), None
+    return "mfma", 3, int(a[0]), name == "fx_mfma", None
+
+
+@pytest.fixture(scope="session")
+def planner(tmp_path_factory):
+    if HIPCC is None:
+        pytest.skip("hipcc not found")
+    exe = tmp_path_factory.mktemp("sepconv_launch_trace") / "sepconv_plan_trace"
+    cmd = [HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1", "-ffp-contract=off", f"-I{ROOT}/include",
+           f"-I{ROOT}/imagetransformations_amd/csrc", f"{ROOT}/tools/sepconv_launch_trace.hip", "-o", str(exe)]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    return exe
+
+
+def test_planned_routes_are_the_restated_ones(planner, tmp_path):
+    """plan_sepconv's family, radius and instantiation equal sepconv_route for every case of the grid, and the grid reaches
+    every instantiation of required_instances() and every family and radius of the RGB route."""
+    grid = _planner_grid()
+    cases = tmp_path / "cases.txt"
+    cases.write_text("".join(_planner_case_line(c) + "\n" for c in grid))
+    res = subprocess.run([str(planner), "--cases", str(cases)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    planned, kernels = [], []
+    for line in res.stdout.splitlines():
+        f = line.split("\t")
+        if f[0] == "L":
+            kernels.append(f[1])
+        elif f[0] == "C":
+            assert f[2] == "rc=0", line
+            planned.append(kernels)
+            kernels = []
+    assert len(planned) == len(grid)
+    reached = set()
+    for case, kernels in zip(grid, planned):
+        c, fixed, R, h, w, aligned, border, f32, kx, ky, sym = case
+        want = sepconv_route(c, fixed, R, h, w, aligned=aligned, border=border, sym=sym, f32=f32,
+                             taps_fit_mfma=_taps_fit_mfma(fixed, kx, ky))
+        where = (c, fixed, R, h, w, aligned, border, f32, sym, kernels)
+        assert len(kernels) == 1, where                       # two frames: one launch in every family
+        family, kc, kR, kfixed, ksym = _planned(kernels[0])
+        assert (family, kR) == want and kc == c, (want, where)
+        assert kfixed == (fixed and (family != "march4" or sym)), where       # the asymmetric marching-4 instances are float ones
+        assert ksym is None or ksym == sym, where
+        reached.add((c, fixed, family, R, sym or family != "march4" or fixed))
+    need = set(required_instances())
+    for fixed in (False, True):
+        need |= {(3, fixed, "march", R, True) for R in range(1, 5)} | {(3, fixed, "mfma", R, True) for R in range(5 if fixed else 6, 16)}
+        need |= {(3, fixed, "march4", R, True) for R in range(5, 16)} | {(3, fixed, "tile", R, True) for R in range(1, 16)}
+    need |= {(3, False, "march4", R, False) for R in range(5, 16)}
+    missing = need - reached
+    assert not missing, sorted(missing)

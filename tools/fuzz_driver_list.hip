@@ -1,4 +1,4 @@
-// Stand-alone CPU program for the HOST code of the list pass (csrc/driver_list.hip with sepconv_family.h): lays out a few
+// Stand-alone CPU program for the HOST code of the list pass (csrc/driver_list.hip with sepconv_route.h): lays out a few
 // hundred random entries of every type, blur included, checks the blocks with the device half's own host checks, then
 // feeds those checks mutated blocks.  Meant for a sanitizer build of the host side; it never touches a device:
 //     hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
