@@ -253,12 +253,15 @@ inline bool plan_bilinear_tall(const View& s, const View& d, const double* m, in
             offsets_fit_32(s) && (int64_t)ntxq * ntyq < ((int64_t)1 << 27)) {
             // 24 frames per workgroup: the tile set-up (~1500 instructions) is amortised further than at 16, the launch still
             // has > 20 000 workgroups to drain evenly (sweep 8 ... 128 on 128 4K / 512 1080p / 32 4K frames:
-            // profiles/r03_experiments/affine_fpb_sweep.txt; 24 is the fastest or within 0.5 % everywhere)
+            // profiles/r03_experiments/affine_fpb_sweep.txt; 24 is the fastest or within 0.5 % everywhere; again at five
+            // workgroups per CU, 16 / 32 / 48 against 24: +0.6 ... +2.4 %, profiles/affine_wq_occupancy.txt)
             const int fpbq = K.fpb_or(24);
             // regions from 8 columns on: at 1080p (15 columns) row-major ranges fetched every source byte twice
             const unsigned gx = xcd_tile_grid(ntxq, ntyq, 8, P);
+            // LDS: per wave the RGBX box and ONE buffer of packed rows, then the two tile-wide slots; 31 680 bytes for the
+            // 27 x 23 box of 30 degrees / 1.5x, so five workgroups share a CU's 160 KiB
             AffineLaunch& L = add_launch(R, AF_BILINEAR_WQ, dim3(gx, (unsigned)((d.n + fpbq - 1) / fpbq)), dim3(256),
-                                         (size_t)4 * ((size_t)bhq * WQ_PITCH * 4 + 2 * ((size_t)bhq * nchq * 16 + 64)) + 2 * 16 * 384);
+                                         (size_t)4 * ((size_t)bhq * WQ_PITCH * 4 + (size_t)bhq * nchq * 16 + 64) + 2 * 16 * 384);
             L.precise = pr; L.ntx = ntxq; L.nty = ntyq; L.fpb = fpbq; L.nch = nchq; L.bh = bhq;
             return true;
         }

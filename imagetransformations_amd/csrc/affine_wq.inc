@@ -6,21 +6,25 @@
 // that writes the same bytes as whole 128-byte lines 0.64 ms.  The 96-byte row segments of a 32-pixel-wide tile never
 // fill a line, and the kernel's time was that of its memory chain (loop + staging + stores, which add up), not of its
 // VALU work.  This kernel keeps the per-pixel machinery of affine_mf.inc (frames looped inside the tile with the geometry
-// in registers, LDS-DMA of packed rows, counted vmcnt, the 8.15 fixed-point sum with its rotate / min3 guard, fp64
-// hand-back) and changes the shape of the work:
+// in registers, LDS-DMA of packed rows, the 8.15 fixed-point sum with its rotate / min3 guard, fp64 hand-back) and
+// changes the shape of the work:
 //
 //   * a workgroup owns a 128 x 16 output tile — rows of 384 bytes = three whole lines — and every wave a 32 x 16 column
 //     block of it (64 lanes x 8 pixels, as before);
 //   * each wave stages ITS OWN source box (27 x 23 pixels for 30 deg / 1.5x instead of the 82 x 55 pixel box of the whole
-//     tile; 1.1 staged pixels per output pixel) into its own LDS region: DMA, counted wait, packed -> RGBX expansion and
+//     tile; 1.1 staged pixels per output pixel) into its own LDS region: DMA, wait, packed -> RGBX expansion and
 //     gather need no barrier at all (a wave's LDS operations execute in order);
 //   * the results are parked in a tile-wide LDS slot (two slots, alternating), ONE barrier per frame says the slot is
 //     complete, and every wave writes four 384-byte rows of it as dense 16-byte chunks — at the START of the next
-//     iteration, right after the counted wait: s_waitcnt vmcnt counts loads and stores in one counter, and stores issued
-//     just before the wait turn the wait for a two-frames-old DMA into a wait for those stores (measured: staging and
+//     iteration, right after the wait for the DMA: s_waitcnt vmcnt counts loads and stores in one counter, and stores
+//     issued just before the wait turn the wait for an older DMA into a wait for those stores (measured: staging and
 //     stores, 0.29 and 0.35 ms on their own, 1.04 ms together).  Issued after it they are a whole iteration old at the
 //     next one.  (A fifth, store-only wave per workgroup was tried: wave w of a workgroup lives on SIMD w mod 4, so SIMD 0
 //     then holds two waves per workgroup and only two workgroups fit a CU — 2.45 ms.)
+//   * FIVE workgroups per CU (profiles/affine_wq_occupancy.txt): the kernel is bound by VALU issue with about a fifth of
+//     the slots idle, and a fifth wave per SIMD fills part of them.  That takes at most 96 VGPRs (512 / 5, granule 8; the
+//     launch bound) and at most 32 768 bytes of LDS (31 680 for the 27 x 23 box), hence ONE packed buffer per wave, which
+//     the DMA of the next frame refills as soon as the expansion has read it;
 //   * the kernel is bound by VALU issue, so what does not change from frame to frame stays out of the frame loop
 //     (profiles/affine_wq_trim.txt: 355 -> 330 VALU instructions per wave and frame): a store is the frame's scalar base,
 //     advanced by the frame stride, plus a 32-bit lane offset worked out once (no address instruction per store); the
@@ -83,7 +87,7 @@ struct WqFlush {
 };
 
 template <bool PRECISE>
-__global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb,
+__global__ __launch_bounds__(256, 5) void affine_bilinear_wq_kernel(View s, View d, AffineParams P, int ntx, int nty, int fpb,
                                                                    int nch, int rows) {
     constexpr int C = 3, SW = 32, BH = 16, BW = 4 * SW, PITCH = WQ_PITCH, NG = PITCH / 4;
     constexpr float GUARDP = 4.0f / 32768.0f;
@@ -97,9 +101,9 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
     const int sx0 = txb * BW + wave * SW, sy0 = tyb * BH;            // this wave's 32 x 16 block
     const bool wave_in = sx0 < d.w;                                  // (a block wholly right of the image still keeps the barriers)
 
-    // ---- LDS: [wave 0 .. 3: RGBX box | packed 0 | packed 1] [slot 0 | slot 1: 16 rows x 384 bytes]
+    // ---- LDS: [wave 0 .. 3: RGBX box | packed rows] [slot 0 | slot 1: 16 rows x 384 bytes]
     const u32 pk_bytes = (u32)(rows * nch * 16 + 64);
-    const u32 wave_bytes = (u32)(rows * PITCH * 4) + 2u * pk_bytes;
+    const u32 wave_bytes = (u32)(rows * PITCH * 4) + pk_bytes;
     u32* const srct = wq_lds + wave * (wave_bytes / 4);
     u32* const slots = wq_lds + 4 * (wave_bytes / 4);
 
@@ -180,30 +184,29 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
             const int u = lane + 64 * it;
             const int rr = u / NG, t = u - rr * NG;
             ex_ok[it] = u < rows * NG;
-            ex_rd[it] = pk_base + (u32)(rr * nch * 16 + ((e0 + 12 * t) & ~3));     // LDS addresses: packed buffer 0, RGBX box
+            ex_rd[it] = pk_base + (u32)(rr * nch * 16 + ((e0 + 12 * t) & ~3));     // LDS addresses: packed rows, RGBX box
             ex_wr[it] = pk_base - rgbx_bytes + (u32)((rr * PITCH + 4 * t) * 4);
             asm volatile("" : "+v"(ex_rd[it]), "+v"(ex_wr[it]));                  // one register each, not a sum redone per frame
         }
     }
     const int kw = (rows * nch + 63) / 64;                          // DMA instructions per wave and frame (1 .. 3)
     // fb: the frame's base, scalar; the caller advances it by s.fs from one issue to the next
-    auto dma_issue = [&](const u8* fb, int pbuf) {
+    auto dma_issue = [&](const u8* fb) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const u32 ldst = __builtin_amdgcn_readfirstlane(pk_base + (u32)pbuf * pk_bytes + (u32)(i * 1024));
+            const u32 ldst = __builtin_amdgcn_readfirstlane(pk_base + (u32)(i * 1024));
             if (i < kw && dma_ok[i]) glds16_hidden(fb, dma_off[i], ldst);       // (lane 0 of every i < kw is active: kw instructions per frame)
         }
     };
     // packed -> RGBX.  A 4-pixel group is the 12 bytes from byte PH = e0 & 3 of four dwords, and pixel k's dword the four
     // bytes from PH + 3 k (the top one is never read): PH is the same for the whole wave and for every frame, so each
     // phase has its own copy in which one dword of the four needs no instruction and the others one v_alignbyte each
-    auto expand = [&](auto ph, int pbuf) {
+    auto expand = [&](auto ph) {
         constexpr int PH = decltype(ph)::value;
-        const u32 poff = (u32)pbuf * pk_bytes;
 #pragma unroll
         for (int it = 0; it < 3; ++it) {
             if (!ex_ok[it]) continue;
-            const __attribute__((address_space(3))) u32* q = (const __attribute__((address_space(3))) u32*)(uintptr_t)(ex_rd[it] + poff);
+            const __attribute__((address_space(3))) u32* q = (const __attribute__((address_space(3))) u32*)(uintptr_t)ex_rd[it];
             const u32 dq[4] = {q[0], q[1], q[2], q[3]};
             const wq_u32x4 o = {wq_bytes_at<PH>(dq), wq_bytes_at<PH + 3>(dq), wq_bytes_at<PH + 6>(dq), wq_bytes_at<PH + 9>(dq)};
             *(__attribute__((address_space(3))) wq_u32x4*)(uintptr_t)ex_wr[it] = o;
@@ -330,7 +333,10 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
         }
     };
 
-    const WqFlush flush_slot(d, slots, lane, wave, txb, sy0);       // this wave's four rows of a slot -> a frame
+    WqFlush flush_slot(d, slots, lane, wave, txb, sy0);             // this wave's four rows of a slot -> a frame
+    // one register per slot read address: left to itself hipcc keeps the slots' base, the lane's part and their sum (six
+    // registers for two addresses) alive across the frame loop
+    asm volatile("" : "+v"(flush_slot.rd[0]), "+v"(flush_slot.rd[1]));
 
     // a fill-only block's columns of BOTH slots hold the fill from here on: no other wave writes them
     if (fill_only) {
@@ -342,40 +348,32 @@ __global__ __launch_bounds__(256, 3) void affine_bilinear_wq_kernel(View s, View
         }
     }
 
-    // ---- frame loop.  Per wave: [counted wait: DMA f landed] expand f [lgkmcnt] issue DMA f+2, gather f, park f;
+    // ---- frame loop.  Per wave: [wait: DMA f landed] flush f-1, expand f [lgkmcnt] issue DMA f+1, gather f, park f;
     // per workgroup: ONE barrier (the slot is complete); its rows leave at the start of the next iteration.  The slots
     // alternate: slot (f+1) & 1 is read by flush(f-1) at the start of iteration f, before that wave parks or reaches barrier f.
-    // The wait is counted: the only loads this wave has issued after DMA f are the kw instructions of DMA f+1 (loads
-    // complete in order among themselves), so at most kw outstanding operations means DMA f is done.  A wave that issues
-    // no DMA (outside the image, or fill only) has nothing to wait for; it still flushes.
-    // The frame bases are scalar and advance by one frame stride per issue / per flush.
+    // ONE packed buffer per wave: the expansion is the only reader of the packed rows, so once its reads have returned
+    // (lgkmcnt(0)) the buffer is free and DMA f+1 goes into it, with the gather, the park and the barrier of frame f to land
+    // in.  At the top of iteration f this wave's outstanding vector memory operations are, in issue order, the stores of
+    // frame f-2 (a whole iteration old) and the kw instructions of DMA f: nothing younger than DMA f exists, so the wait is
+    // vmcnt(0) whatever kw is.  A wave that issues no DMA (outside the image, or fill only) has nothing to wait for; it
+    // still flushes.  The frame bases are scalar and advance by one frame stride per issue / per flush.
     const u8* sdma = s.p + (int64_t)f_begin * s.fs;                 // next frame to stage
     u8* dfl = d.p + (int64_t)f_begin * d.fs;                        // next frame to flush
-    if (wave_on) {
-        dma_issue(sdma, 0); sdma += s.fs;
-        if (f_begin + 1 < f_end) { dma_issue(sdma, 1); sdma += s.fs; }
-    }
+    if (wave_on) { dma_issue(sdma); sdma += s.fs; }
     const int ph = e0 & 3;
-    int pb = 0;
 #pragma unroll 1
     for (int f = f_begin; f < f_end; ++f) {
         const int par = (f - f_begin) & 1;
-        if (wave_on) {
-            if (f + 1 >= f_end) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (kw == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-            else if (kw == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        }
+        if (wave_on) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (f > f_begin) { flush_slot(dfl, par ^ 1); dfl += d.fs; }  // a whole iteration old at the next wait
         if (wave_on) {
-            if (ph == 0) expand(std::integral_constant<int, 0>(), pb);
-            else if (ph == 1) expand(std::integral_constant<int, 1>(), pb);
-            else if (ph == 2) expand(std::integral_constant<int, 2>(), pb);
-            else expand(std::integral_constant<int, 3>(), pb);
+            if (ph == 0) expand(std::integral_constant<int, 0>());
+            else if (ph == 1) expand(std::integral_constant<int, 1>());
+            else if (ph == 2) expand(std::integral_constant<int, 2>());
+            else expand(std::integral_constant<int, 3>());
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the expansion has read the packed rows: their buffer is free
-            if (f + 2 < f_end) { dma_issue(sdma, pb); sdma += s.fs; }
+            if (f + 1 < f_end) { dma_issue(sdma); sdma += s.fs; }
             gather_frame(f, slots + par * (16 * 96));
-            pb ^= 1;
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
