@@ -1,7 +1,8 @@
 // Resize(shorter edge) + CenterCrop + ToTensor + Normalize of a LIST of RGB frames of different sizes in one launch
 // (tensor_maps.preprocess_list): what torchvision's Compose([Resize(r), CenterCrop(c), ToTensor(), Normalize(m, s)])
-// gives on each PIL image — Pillow's BILINEAR Image.resize (horizontal pass, uint8 intermediate, vertical pass, 22-bit
-// coefficients), restricted to the crop window — bit for bit tensor_maps.preprocess per frame.
+// gives on each PIL image — Pillow's Image.resize (horizontal pass, uint8 intermediate, vertical pass, 22-bit
+// coefficients) with any of its five convolution filters (BILINEAR where none is stated), restricted to the crop window —
+// bit for bit tensor_maps.preprocess per frame.
 //
 // HOST half (imgxf_preprocess_list_layout_host, no device work): from each frame's geometry one block of
 //   header | frame records | work units | coefficient tables
@@ -94,9 +95,10 @@ int preprocess_list_check(const void* block_host) {
 
 using namespace imgxf;
 
-IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, int crop, int lds_budget, void* block,
-                                                size_t block_cap, size_t* block_bytes) {
+IMGXF_API int imgxf_preprocess_list_layout_filter_host(const int32_t* geometry, int n, int crop, int filter, int lds_budget,
+                                                       void* block, size_t block_cap, size_t* block_bytes) {
     if (!geometry || !block_bytes) return IMGXF_ERR_NULL;
+    if (!filter_known(filter)) return IMGXF_ERR_ARG;
     if (n < 0 || crop < 1 || crop > 32767 || lds_budget < 1) return IMGXF_ERR_ARG;
     if (lds_budget > PL_MAX_LDS) lds_budget = PL_MAX_LDS;
     const PlGeom* geo = (const PlGeom*)geometry;
@@ -119,8 +121,8 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
         if (it == index.end()) {
             Set s;
             s.first = i;
-            s.ksx = coeff_ksize(g.w, g.nw, IMGXF_RESAMPLE_BILINEAR);
-            s.ksy = coeff_ksize(g.h, g.nh, IMGXF_RESAMPLE_BILINEAR);
+            s.ksx = coeff_ksize(g.w, g.nw, filter);
+            s.ksy = coeff_ksize(g.h, g.nh, filter);
             const int ncols = pl_rows_bound(crop, g.w, g.nw, s.ksx);
             s.unit_rows = pl_unit_rows(std::min(crop, PL_UNIT_ROWS), lds_budget, [&](int ny) {
                 return pl_lds_bytes(pl_rows_bound(ny, g.h, g.nh, s.ksy), crop, ncols);
@@ -161,8 +163,8 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
         } else {
             f.h = g.h; f.w = g.w; f.ksx = s.ksx; f.ksy = s.ksy; f.unit_rows = s.unit_rows;
             if (s.unit_rows) {
-                pl_append_axis(g.w, g.nw, IMGXF_RESAMPLE_BILINEAR, s.ksx, g.left, crop, words, tpos, &f.bounds_x, &f.coeffs_x);
-                pl_append_axis(g.h, g.nh, IMGXF_RESAMPLE_BILINEAR, s.ksy, g.top, crop, words, tpos, &f.bounds_y, &f.coeffs_y);
+                pl_append_axis(g.w, g.nw, filter, s.ksx, g.left, crop, words, tpos, &f.bounds_x, &f.coeffs_x);
+                pl_append_axis(g.h, g.nh, filter, s.ksy, g.top, crop, words, tpos, &f.bounds_y, &f.coeffs_y);
                 int c_hi, r_hi;
                 pl_span(words + f.bounds_x, 0, crop, &f.col0, &c_hi);
                 pl_span(words + f.bounds_y, 0, crop, &f.row0, &r_hi);
@@ -183,6 +185,12 @@ IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, 
     hd->frames_off = (int32_t)frames_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
     hd->total_bytes = (int32_t)total;
     return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, int crop, int lds_budget, void* block,
+                                                size_t block_cap, size_t* block_bytes) {
+    return imgxf_preprocess_list_layout_filter_host(geometry, n, crop, IMGXF_RESAMPLE_BILINEAR, lds_budget, block, block_cap,
+                                                    block_bytes);
 }
 
 IMGXF_API int imgxf_preprocess_list_f32(const void* block_host, const void* block_dev, float* out, const float* mean,

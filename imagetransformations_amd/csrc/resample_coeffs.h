@@ -19,9 +19,11 @@ static inline double lanczos_filter(double x) {
     if (-3.0 <= x && x < 3.0) return sinc_filter(x) * sinc_filter(x / 3);
     return 0.0;
 }
-// the other filters of libImaging Resample.c (Image.resize's default is BICUBIC)
-static inline double box_filter(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
-static inline double bilinear_filter(double x) {
+// the other filters of libImaging Resample.c (Image.resize's default is BICUBIC).  The polynomial ones (BOX, BILINEAR,
+// BICUBIC) are IEEE operations alone, so the device gives the host's doubles (-ffp-contract=off): resized_crop_list's kernel
+// compiles these bodies too.  sin and cos promise no such thing: HAMMING and LANCZOS tables are host-built only.
+__host__ __device__ static inline double box_filter(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+__host__ __device__ static inline double bilinear_filter(double x) {
     if (x < 0.0) x = -x;
     return x < 1.0 ? 1.0 - x : 0.0;
 }
@@ -32,14 +34,14 @@ static inline double hamming_filter(double x) {
     x = x * M_PI;
     return sin(x) / x * (0.54f + 0.46f * cos(x));      // float literals, as in Resample.c
 }
-static inline double bicubic_filter(double x) {
+__host__ __device__ static inline double bicubic_filter(double x) {
     const double a = -0.5;
     if (x < 0.0) x = -x;
     if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
     if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
     return 0.0;
 }
-static inline double filter_support(int filter) {
+__host__ __device__ constexpr double filter_support(int filter) {
     switch (filter) {
         case IMGXF_RESAMPLE_BOX: return 0.5;
         case IMGXF_RESAMPLE_BILINEAR: case IMGXF_RESAMPLE_HAMMING: return 1.0;
@@ -47,14 +49,15 @@ static inline double filter_support(int filter) {
         default: return 3.0;
     }
 }
-static inline double filter_value(int filter, double x) {
-    switch (filter) {
-        case IMGXF_RESAMPLE_BOX: return box_filter(x);
-        case IMGXF_RESAMPLE_BILINEAR: return bilinear_filter(x);
-        case IMGXF_RESAMPLE_HAMMING: return hamming_filter(x);
-        case IMGXF_RESAMPLE_BICUBIC: return bicubic_filter(x);
-        default: return lanczos_filter(x);
-    }
+constexpr bool filter_known(int filter) { return filter >= IMGXF_RESAMPLE_LANCZOS && filter <= IMGXF_RESAMPLE_HAMMING; }
+// the filters a device can evaluate to the host's doubles, selected at compile time
+constexpr bool filter_polynomial(int filter) {
+    return filter == IMGXF_RESAMPLE_BOX || filter == IMGXF_RESAMPLE_BILINEAR || filter == IMGXF_RESAMPLE_BICUBIC;
+}
+template <int FILTER>
+__host__ __device__ static inline double polynomial_filter_value(double x) {
+    static_assert(filter_polynomial(FILTER), "HAMMING and LANCZOS need sin / cos: host tables only");
+    return FILTER == IMGXF_RESAMPLE_BOX ? box_filter(x) : FILTER == IMGXF_RESAMPLE_BICUBIC ? bicubic_filter(x) : bilinear_filter(x);
 }
 
 // taps per output sample (precompute_coeffs' ksize)
@@ -64,8 +67,11 @@ static inline int coeff_ksize(int in_size, int out_size, int filter) {
     return (int)ceil(filter_support(filter) * filterscale) * 2 + 1;
 }
 
-// precompute_coeffs + normalize_coeffs_8bpc (whole-image box)
-static int build_coeffs(int in_size, int out_size, int filter, std::vector<int>& bounds, std::vector<int>& kk) {
+// precompute_coeffs + normalize_coeffs_8bpc (whole-image box) with the filter's function `value` (build_coeffs below
+// selects it once per table, so the tap loops call one filter directly, whatever the number of filters a caller passes)
+template <class Value>
+__attribute__((always_inline)) static inline int build_coeffs_with(int in_size, int out_size, int filter, Value value,
+                                                                   std::vector<int>& bounds, std::vector<int>& kk) {
     double scale, filterscale;
     filterscale = scale = (double)in_size / out_size;
     if (filterscale < 1.0) filterscale = 1.0;
@@ -84,7 +90,7 @@ static int build_coeffs(int in_size, int out_size, int filter, std::vector<int>&
         if (xmax > in_size) xmax = in_size;
         xmax -= xmin;
         for (int x = 0; x < xmax; ++x) {
-            const double w = filter_value(filter, (x + xmin - center + 0.5) * ss);
+            const double w = value((x + xmin - center + 0.5) * ss);
             k[x] = w;
             ww += w;
         }
@@ -98,6 +104,15 @@ static int build_coeffs(int in_size, int out_size, int filter, std::vector<int>&
         bounds[2 * xx + 1] = xmax;
     }
     return ksize;
+}
+static int build_coeffs(int in_size, int out_size, int filter, std::vector<int>& bounds, std::vector<int>& kk) {
+    switch (filter) {
+        case IMGXF_RESAMPLE_BOX: return build_coeffs_with(in_size, out_size, filter, box_filter, bounds, kk);
+        case IMGXF_RESAMPLE_BILINEAR: return build_coeffs_with(in_size, out_size, filter, bilinear_filter, bounds, kk);
+        case IMGXF_RESAMPLE_HAMMING: return build_coeffs_with(in_size, out_size, filter, hamming_filter, bounds, kk);
+        case IMGXF_RESAMPLE_BICUBIC: return build_coeffs_with(in_size, out_size, filter, bicubic_filter, bounds, kk);
+        default: return build_coeffs_with(in_size, out_size, filter, lanczos_filter, bounds, kk);
+    }
 }
 
 // keep rows [first, first + count) of a (bounds, coefficients) table pair

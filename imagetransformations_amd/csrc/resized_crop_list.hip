@@ -1,7 +1,9 @@
 // RandomResizedCrop-style crops of a LIST of RGB frames of different sizes in one launch (tensor_maps.resized_crop_list):
-// per entry k what torchvision's F.resized_crop(img, top, left, height, width, size, BILINEAR) (+ F.hflip) (+ ToTensor +
-// Normalize) gives on the PIL image — Image.crop(box).resize((Sw, Sh), BILINEAR): Pillow's horizontal pass, uint8
-// intermediate, vertical pass, 22-bit coefficients, windows clamped to the BOX — bit for bit.
+// per entry k what torchvision's F.resized_crop(img, top, left, height, width, size, filter) (+ F.hflip) (+ ToTensor +
+// Normalize) gives on the PIL image — Image.crop(box).resize((Sw, Sh), filter): Pillow's horizontal pass, uint8
+// intermediate, vertical pass, 22-bit coefficients, windows clamped to the BOX — bit for bit, for the filters whose
+// tables a device can build to the host's doubles: BILINEAR, BICUBIC, BOX (polynomials).  HAMMING and LANCZOS need sin
+// and cos: the launch refuses them and the caller takes the per-entry route.
 //
 // Every entry has a box of its own, so nearly every entry has coefficient tables of its own.  The HOST half
 // (imgxf_resized_crop_list_layout_host, no device work) therefore writes no table: one block of
@@ -11,7 +13,8 @@
 // DEVICE half (resized_crop_list_kernel): one workgroup per work unit = up to RCL_UNIT_ROWS output rows of one entry.
 //   LDS: | bounds_x [Sw][2] | coeffs_x [Sw][ksx] | bounds_y [ny][2] | coeffs_y [ny][ksy] | mid | stage |
 //   0. a lane builds one row of a table: precompute_coeffs + normalize_coeffs_8bpc for its output column (or output row of
-//      the unit) in fp64, build_coeffs (resample_coeffs.h) restated operation by operation (rcl_build_row);
+//      the unit) in fp64, build_coeffs (resample_coeffs.h) restated operation by operation (rcl_build_row<FILTER>: the
+//      filter is a template parameter of the kernel, the block has no field for it);
 //   1. + 2. the two passes of the band engine (resample_list.h: pl_horizontal_pass, pl_vertical_pass) from those tables,
 //      on the box as the image: the source pointer is the box's first pixel, so no tap reads a pixel outside the box;
 //      (a box more than 100 times as tall as wide that loses rows: Pillow's order for it, rows first — `tall` below);
@@ -58,14 +61,21 @@ static int rcl_unit_rows(int bh, int bw, int sh, int sw, int ksx, int ksy, int l
                         [&](int ny) { return rcl_unit_lds(bh, bw, sh, sw, ny, ksx, ksy); });
 }
 
-// One row of precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter: build_coeffs (resample_coeffs.h) for
-// output sample xx, operation by operation in fp64 (the weights are summed in tap order; a weight is recomputed, not kept,
-// for the second loop: the same operations give the same double).  bounds: (first source index, count); kk: ksize slots.
-__device__ __forceinline__ void rcl_build_row(int in_size, int out_size, int xx, int* bounds, int* kk) {
+// One row of precompute_coeffs + normalize_coeffs_8bpc for a polynomial filter (BILINEAR, BICUBIC, BOX: filter_polynomial,
+// resample_coeffs.h): build_coeffs for output sample xx, operation by operation in fp64 (the weights are summed in tap
+// order; a weight is recomputed, not kept, for the second loop: the same operations give the same double).  One body for
+// the kernel and the host (tools/fuzz_resized_crop_list.hip compares it with build_coeffs).  bounds: (first source index,
+// count); kk: ksize slots.
+// Signed tables (BICUBIC has negative lobes) in the band engine: a normalised coefficient has |k| < 2 — measured over in,
+// out in 1..79 and {224, 255, 256, 500, 1000}: -0.13..1.13 for BICUBIC, -0.29..1.29 for LANCZOS; the fuzz tool asserts
+// |k| < 2^23 for every table it builds — so k * 2^22 fits mul24's signed 24 bits, and a row's sum of |k| * 255 stays
+// below 2^31 - 2^21 (it would take sum |k| > 2^9), so the int32 accumulators hold it with the rounding term.
+template <int FILTER>
+__host__ __device__ __forceinline__ void rcl_build_row(int in_size, int out_size, int xx, int* bounds, int* kk) {
     double scale, filterscale;
     filterscale = scale = (double)in_size / out_size;
     if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 1.0 * filterscale;
+    const double support = filter_support(FILTER) * filterscale;
     const double ss = 1.0 / filterscale;
     const double center = 0.0 + (xx + 0.5) * scale;
     double ww = 0.0;
@@ -74,16 +84,9 @@ __device__ __forceinline__ void rcl_build_row(int in_size, int out_size, int xx,
     int xmax = (int)(center + support + 0.5);
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
+    for (int x = 0; x < xmax; ++x) ww += polynomial_filter_value<FILTER>((x + xmin - center + 0.5) * ss);
     for (int x = 0; x < xmax; ++x) {
-        double a = (x + xmin - center + 0.5) * ss;
-        if (a < 0.0) a = -a;
-        const double w = a < 1.0 ? 1.0 - a : 0.0;
-        ww += w;
-    }
-    for (int x = 0; x < xmax; ++x) {
-        double a = (x + xmin - center + 0.5) * ss;
-        if (a < 0.0) a = -a;
-        double v = a < 1.0 ? 1.0 - a : 0.0;
+        double v = polynomial_filter_value<FILTER>((x + xmin - center + 0.5) * ss);
         if (ww != 0.0) v /= ww;
         kk[x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
     }
@@ -93,7 +96,8 @@ __device__ __forceinline__ void rcl_build_row(int in_size, int out_size, int xx,
 
 // F32: float32 planar [K][3][Sh][Sw] after ToTensor (+ Normalize); else uint8 interleaved [K][Sh][Sw][3].
 // VEC: Sw % 4 == 0 and `out` aligned for 16-byte (F32) / 4-byte (uint8) stores.
-template <bool F32, bool VEC>
+// FILTER: the polynomial filter whose tables the unit builds.
+template <bool F32, bool VEC, int FILTER>
 __global__ __launch_bounds__(PL_THREADS) void resized_crop_list_kernel(const u8* __restrict__ block, int entries_off,
                                                                        int units_off, int sh, int sw, int lds_bytes,
                                                                        void* __restrict__ out, NormArgs a) {
@@ -106,8 +110,8 @@ __global__ __launch_bounds__(PL_THREADS) void resized_crop_list_kernel(const u8*
     int* by = kx + sw * e.ksx;
     int* ky = by + 2 * u.ny;
     for (int i = tid; i < sw + u.ny; i += PL_THREADS) {
-        if (i < sw) rcl_build_row(e.bw, sw, i, bx + 2 * i, kx + i * e.ksx);
-        else rcl_build_row(e.bh, sh, u.y0 + (i - sw), by + 2 * (i - sw), ky + (i - sw) * e.ksy);
+        if (i < sw) rcl_build_row<FILTER>(e.bw, sw, i, bx + 2 * i, kx + i * e.ksx);
+        else rcl_build_row<FILTER>(e.bh, sh, u.y0 + (i - sw), by + 2 * (i - sw), ky + (i - sw) * e.ksy);
     }
     __syncthreads();
     // source rows and columns of the box the unit touches (the bounds are monotone), laid out inside the launch's LDS
@@ -160,8 +164,9 @@ __global__ __launch_bounds__(PL_THREADS) void resized_crop_list_kernel(const u8*
 }
 
 // The records bound every address the kernel forms: check them against their frames, the block and the launch's LDS.
+// `filter`: the one the block was laid out for (the records have no field for it: the taps must be that filter's).
 // Host only; reads nothing outside the block the header states.
-int resized_crop_list_check(const void* block_host, size_t block_bytes) {
+int resized_crop_list_check(const void* block_host, size_t block_bytes, int filter) {
     const u8* hb = (const u8*)block_host;
     if (block_bytes < sizeof(imgxf_resized_crop_header)) return IMGXF_ERR_ARG;
     const imgxf_resized_crop_header hd = *(const imgxf_resized_crop_header*)hb;
@@ -181,8 +186,7 @@ int resized_crop_list_check(const void* block_host, size_t block_bytes) {
         if (!e.data) return IMGXF_ERR_NULL;
         if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.row_stride < (int64_t)e.w * 3) return IMGXF_ERR_SHAPE;
         if (e.top < 0 || e.left < 0 || e.bh < 1 || e.bw < 1 || e.top > e.h - e.bh || e.left > e.w - e.bw) return IMGXF_ERR_SHAPE;
-        if (e.ksx != coeff_ksize(e.bw, hd.sw, IMGXF_RESAMPLE_BILINEAR) || e.ksy != coeff_ksize(e.bh, hd.sh, IMGXF_RESAMPLE_BILINEAR))
-            return IMGXF_ERR_ARG;
+        if (e.ksx != coeff_ksize(e.bw, hd.sw, filter) || e.ksy != coeff_ksize(e.bh, hd.sh, filter)) return IMGXF_ERR_ARG;
         if (e.unit_rows < 0 || e.unit_rows > RCL_UNIT_ROWS || (e.flip != 0 && e.flip != 1)) return IMGXF_ERR_ARG;
         if (e.tall != rcl_tall(e.bh, e.bw, hd.sh)) return IMGXF_ERR_ARG;
     }
@@ -201,9 +205,10 @@ int resized_crop_list_check(const void* block_host, size_t block_bytes) {
 
 using namespace imgxf;
 
-IMGXF_API int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n, int sh, int sw, int lds_budget, void* block,
-                                                  size_t block_cap, size_t* block_bytes) {
+IMGXF_API int imgxf_resized_crop_list_layout_filter_host(const int32_t* geometry, int n, int sh, int sw, int filter,
+                                                         int lds_budget, void* block, size_t block_cap, size_t* block_bytes) {
     if (!geometry || !block_bytes) return IMGXF_ERR_NULL;
+    if (!filter_known(filter)) return IMGXF_ERR_ARG;
     if (n < 0 || sh < 1 || sh > 32767 || sw < 1 || sw > 32767 || lds_budget < 1) return IMGXF_ERR_ARG;
     if (lds_budget > RCL_MAX_LDS) lds_budget = RCL_MAX_LDS;
     const RclGeom* geo = (const RclGeom*)geometry;
@@ -213,8 +218,7 @@ IMGXF_API int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n
         if (g.h < 1 || g.w < 1 || g.h > 32767 || g.w > 32767 || (g.flip != 0 && g.flip != 1)) return IMGXF_ERR_ARG;
         if (g.top < 0 || g.left < 0 || g.bh < 1 || g.bw < 1 || g.top > g.h - g.bh || g.left > g.w - g.bw)
             return IMGXF_ERR_ARG;                                 // a box outside its frame
-        const int ur = rcl_unit_rows(g.bh, g.bw, sh, sw, coeff_ksize(g.bw, sw, IMGXF_RESAMPLE_BILINEAR),
-                                     coeff_ksize(g.bh, sh, IMGXF_RESAMPLE_BILINEAR), lds_budget);
+        const int ur = rcl_unit_rows(g.bh, g.bw, sh, sw, coeff_ksize(g.bw, sw, filter), coeff_ksize(g.bh, sh, filter), lds_budget);
         if (ur) n_units += (size_t)(sh + ur - 1) / ur;
     }
     const size_t entries_off = sizeof(imgxf_resized_crop_header);
@@ -236,8 +240,8 @@ IMGXF_API int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n
         const RclGeom& g = geo[i];
         imgxf_resized_crop_entry& e = entries[i];
         e.h = g.h; e.w = g.w; e.top = g.top; e.left = g.left; e.bh = g.bh; e.bw = g.bw; e.flip = g.flip;
-        e.ksx = coeff_ksize(g.bw, sw, IMGXF_RESAMPLE_BILINEAR);
-        e.ksy = coeff_ksize(g.bh, sh, IMGXF_RESAMPLE_BILINEAR);
+        e.ksx = coeff_ksize(g.bw, sw, filter);
+        e.ksy = coeff_ksize(g.bh, sh, filter);
         e.tall = rcl_tall(g.bh, g.bw, sh);
         e.unit_rows = rcl_unit_rows(g.bh, g.bw, sh, sw, e.ksx, e.ksy, lds_budget);
         if (!e.unit_rows) continue;
@@ -254,13 +258,21 @@ IMGXF_API int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n
     return IMGXF_OK;
 }
 
-IMGXF_API int imgxf_resized_crop_list(const void* block_host, size_t block_bytes, const void* block_dev, void* out,
-                                      int out_u8, const float* mean, const float* std, void* stream) {
+IMGXF_API int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n, int sh, int sw, int lds_budget, void* block,
+                                                  size_t block_cap, size_t* block_bytes) {
+    return imgxf_resized_crop_list_layout_filter_host(geometry, n, sh, sw, IMGXF_RESAMPLE_BILINEAR, lds_budget, block, block_cap,
+                                                      block_bytes);
+}
+
+IMGXF_API int imgxf_resized_crop_list_filter(const void* block_host, size_t block_bytes, const void* block_dev, void* out,
+                                             int out_u8, int filter, const float* mean, const float* std, void* stream) {
     if (!block_host) return IMGXF_ERR_NULL;
+    if (!filter_known(filter)) return IMGXF_ERR_ARG;
+    if (!filter_polynomial(filter)) return IMGXF_ERR_UNSUPPORTED;     // sin / cos: no table the kernel can build
     if ((mean == nullptr) != (std == nullptr)) return IMGXF_ERR_NULL;
     if (out_u8 != 0 && out_u8 != 1) return IMGXF_ERR_ARG;
     if (out_u8 && mean) return IMGXF_ERR_ARG;
-    const int rc = resized_crop_list_check(block_host, block_bytes);
+    const int rc = resized_crop_list_check(block_host, block_bytes, filter);
     if (rc != IMGXF_OK) return rc;
     const imgxf_resized_crop_header hd = *(const imgxf_resized_crop_header*)block_host;
     if (hd.n_units == 0) return IMGXF_OK;
@@ -271,11 +283,24 @@ IMGXF_API int imgxf_resized_crop_list(const void* block_host, size_t block_bytes
     hipStream_t st = (hipStream_t)stream;
     const u8* db = (const u8*)block_dev;
     const dim3 grid((unsigned)hd.n_units), threads(PL_THREADS);
-#define RCL_LAUNCH(F32, VEC)                                                                                              \
-    hipLaunchKernelGGL((resized_crop_list_kernel<F32, VEC>), grid, threads, (size_t)hd.lds_bytes, st, db, hd.entries_off,  \
-                       hd.units_off, hd.sh, hd.sw, hd.lds_bytes, out, a)
-    if (out_u8) { if (vec) RCL_LAUNCH(false, true); else RCL_LAUNCH(false, false); }
-    else { if (vec) RCL_LAUNCH(true, true); else RCL_LAUNCH(true, false); }
+#define RCL_LAUNCH(F32, VEC, FILTER)                                                                                      \
+    hipLaunchKernelGGL((resized_crop_list_kernel<F32, VEC, FILTER>), grid, threads, (size_t)hd.lds_bytes, st, db,         \
+                       hd.entries_off, hd.units_off, hd.sh, hd.sw, hd.lds_bytes, out, a)
+#define RCL_LAUNCH_FILTER(FILTER)                                                                                         \
+    if (out_u8) { if (vec) RCL_LAUNCH(false, true, FILTER); else RCL_LAUNCH(false, false, FILTER); }                      \
+    else { if (vec) RCL_LAUNCH(true, true, FILTER); else RCL_LAUNCH(true, false, FILTER); }
+    switch (filter) {
+        case IMGXF_RESAMPLE_BICUBIC: RCL_LAUNCH_FILTER(IMGXF_RESAMPLE_BICUBIC) break;
+        case IMGXF_RESAMPLE_BOX: RCL_LAUNCH_FILTER(IMGXF_RESAMPLE_BOX) break;
+        default: RCL_LAUNCH_FILTER(IMGXF_RESAMPLE_BILINEAR) break;
+    }
+#undef RCL_LAUNCH_FILTER
 #undef RCL_LAUNCH
     return launch_status();
+}
+
+IMGXF_API int imgxf_resized_crop_list(const void* block_host, size_t block_bytes, const void* block_dev, void* out,
+                                      int out_u8, const float* mean, const float* std, void* stream) {
+    return imgxf_resized_crop_list_filter(block_host, block_bytes, block_dev, out, out_u8, IMGXF_RESAMPLE_BILINEAR, mean, std,
+                                          stream);
 }

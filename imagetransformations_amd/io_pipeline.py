@@ -80,32 +80,40 @@ def _decode_on_device(read):
     return out
 
 
-def load_preprocessed(paths: Sequence[str], resize: int = 256, crop: int = 224, mean=None, std=None, workers: int = 8):
+def load_preprocessed(paths: Sequence[str], resize: int = 256, crop: int = 224, mean=None, std=None, workers: int = 8,
+                      interpolation="bilinear"):
     """From file names to a model input in one call: the files are read on a thread pool, decoded on the device as one
     chunk (`_decode_on_device`: a file the device reader refuses or finds damaged goes to Pillow, one Pillow cannot open
     is skipped with the reference's message) and preprocessed by `tensor_maps.preprocess_list` in one launch.
+    `interpolation`: Resize's filter as `tensor_maps.resample_filter` reads it (default BILINEAR), checked before any file
+    is read.
     Returns (float32 [N, 3, crop, crop], the paths of the N files kept, in order)."""
     from . import tensor_maps
+    filt = tensor_maps.resample_filter(interpolation)
     with ThreadPoolExecutor(max_workers=workers) as pool:
         read = list(pool.map(_read, paths))
     items = _decode_on_device(read)
-    return tensor_maps.preprocess_list([t for t, _ in items], resize, crop, mean, std), [p for _, p in items]
+    return (tensor_maps.preprocess_list([t for t, _ in items], resize, crop, mean, std, interpolation=filt),
+            [p for _, p in items])
 
 
 def load_random_resized_crops(paths: Sequence[str], size=224, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p=0.5,
-                              mean=None, std=None, workers: int = 8):
+                              mean=None, std=None, workers: int = 8, interpolation="bilinear"):
     """`load_preprocessed`'s training-time twin: the files are read on a thread pool and decoded on the device as one
     chunk, one box and one flip per kept file are drawn by `tensor_maps.random_resized_crop_params` (torch's default CPU
     generator, consumed as Compose([RandomResizedCrop(size, scale, ratio), RandomHorizontalFlip(flip_p)]) does image by
-    image), and `tensor_maps.resized_crop_list` makes the batch in one launch.
+    image), and `tensor_maps.resized_crop_list` makes the batch in one launch.  `interpolation`: RandomResizedCrop's
+    filter as `tensor_maps.resample_filter` reads it (default BILINEAR), checked before any file is read.
     Returns (float32 [N, 3, Sh, Sw], the paths of the N files kept, in order)."""
     from . import tensor_maps
+    filt = tensor_maps.resample_filter(interpolation)
     with ThreadPoolExecutor(max_workers=workers) as pool:
         read = list(pool.map(_read, paths))
     items = _decode_on_device(read)
     frames = [t for t, _ in items]
     boxes, flips = tensor_maps.random_resized_crop_params([(t.shape[0], t.shape[1]) for t in frames], scale, ratio, flip_p)
-    return tensor_maps.resized_crop_list(frames, boxes, size, flips, mean=mean, std=std), [p for _, p in items]
+    return (tensor_maps.resized_crop_list(frames, boxes, size, flips, mean=mean, std=std, interpolation=filt),
+            [p for _, p in items])
 
 
 def _chunks(seq: Sequence, n: int) -> Iterable[Sequence]:

@@ -103,13 +103,40 @@ def resized_output_size(height: int, width: int, size: int):
     return (new_long, new_short) if width <= height else (new_short, new_long)      # (new_h, new_w)
 
 
-def preprocess(frames: torch.Tensor, resize: int = 256, crop: int = 224, mean=None, std=None) -> torch.Tensor:
-    """transforms.Compose([Resize(resize), CenterCrop(crop), ToTensor(), Normalize(mean, std)]) on
+# Pillow's Image.Resampling integers of the convolution filters (ops.RESAMPLE_*, IMGXF_RESAMPLE_* of include/imgxf.h)
+BILINEAR = 2
+_FILTER_NAMES = {"lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}
+
+
+def resample_filter(interpolation) -> int:
+    """The `interpolation=` argument of the preprocessing calls as one of Pillow's resampling integers: such an integer
+    itself (`ops.RESAMPLE_*`, a `PIL.Image.Resampling` member), a torchvision `InterpolationMode` — any object whose
+    `.value` is a string is read through that string — or one of the lowercase names "bilinear", "bicubic", "box",
+    "hamming", "lanczos".  NEAREST (Pillow's NEAREST resize is no convolution) and anything else: ValueError."""
+    v = interpolation
+    if not isinstance(v, (str, int, np.integer)) and isinstance(getattr(v, "value", None), str):
+        v = v.value
+    if isinstance(v, str):
+        if v in _FILTER_NAMES:
+            return _FILTER_NAMES[v]
+    elif isinstance(v, (int, np.integer)) and not isinstance(v, bool) and int(v) in _FILTER_NAMES.values():
+        return int(v)
+    if (isinstance(v, str) and v == "nearest") or (isinstance(v, (int, np.integer)) and not isinstance(v, bool) and int(v) == 0):
+        raise ValueError("interpolation NEAREST is not a convolution filter: BILINEAR, BICUBIC, BOX, HAMMING or LANCZOS")
+    raise ValueError(f"unknown interpolation {interpolation!r}: a Pillow resampling integer, a torchvision InterpolationMode "
+                     f"or one of {sorted(_FILTER_NAMES)}")
+
+
+def preprocess(frames: torch.Tensor, resize: int = 256, crop: int = 224, mean=None, std=None,
+               interpolation=BILINEAR) -> torch.Tensor:
+    """transforms.Compose([Resize(resize, interpolation), CenterCrop(crop), ToTensor(), Normalize(mean, std)]) on
     uint8 [N,H,W,C] / [H,W,C] device frames — the evaluation preprocessing of the reference's
     ImageNet scripts (Resize(256), CenterCrop(224)) — as Pillow / torchvision compute it on PIL
-    images: BILINEAR `Image.resize` of the shorter edge (only the crop window is filtered),
-    crop offsets int(round((h - crop) / 2.0)), then `to_tensor`."""
+    images: `Image.resize` of the shorter edge with the given filter (`resample_filter`; BILINEAR as
+    torchvision's default; only the crop window is filtered), crop offsets int(round((h - crop) / 2.0)),
+    then `to_tensor`."""
     from . import ops
+    filt = resample_filter(interpolation)
     h, w = (frames.shape[-3], frames.shape[-2])
     nh, nw = resized_output_size(h, w, resize)
     if crop > nh or crop > nw:
@@ -119,7 +146,7 @@ def preprocess(frames: torch.Tensor, resize: int = 256, crop: int = 224, mean=No
     if (nh, nw) == (h, w):                                   # Resize returns the image itself
         t = ops.crop(frames, box)
     else:
-        t = ops.resize_crop(frames, (nw, nh), box, ops.RESAMPLE_BILINEAR)
+        t = ops.resize_crop(frames, (nw, nh), box, filt)
     return to_tensor(t, mean, std)
 
 
@@ -127,9 +154,18 @@ def preprocess(frames: torch.Tensor, resize: int = 256, crop: int = 224, mean=No
 # (uint8, 12 * ceil(crop / 4) bytes each) and four staged source-row spans (the crop columns' source bytes + 6, rounded
 # to 4).  64 KiB per workgroup leaves room for two of them in a CU's 160 KiB.  A frame fits when ONE output row does:
 #     ksy * 12 * ceil(crop / 4) + 4 * (3 * (ceil((crop - 1) * w / nw) + ksx) + 6) <= PREPROCESS_LIST_LDS_BYTES
-# with ks = 2 * ceil(max(in / out, 1)) + 1 taps per axis.  That is what bounds taps and crop: at crop 224 and equal
-# scales 33 taps (a 16-fold reduction: a shorter edge of 4096 at resize 256), at crop 384 19 taps, at crop 512 13, at
-# crop 32 223.  A frame beyond it goes through `preprocess` in its place (the host layout marks it: unit_rows == 0).
+# with ks = 2 * ceil(support * max(in / out, 1)) + 1 taps per axis, support 0.5 for BOX, 1 for BILINEAR and HAMMING, 2 for
+# BICUBIC, 3 for LANCZOS.  That is what bounds taps and crop.  With equal scales, the largest whole-number reduction that
+# fits and its taps:
+#     crop        BOX         BILINEAR, HAMMING   BICUBIC       LANCZOS
+#      224     19-fold  21      16-fold   33      11-fold  45    9-fold  55      (16-fold: a shorter edge of 4096 at
+#      384     10-fold  11       9-fold   19       6-fold  25    5-fold  31       resize 256)
+#      512      8-fold   9       6-fold   13       5-fold  21    4-fold  25
+#       32    136-fold 137     111-fold  223      81-fold 325   64-fold 385
+# A frame beyond it goes through `preprocess` in its place (the host layout marks it: unit_rows == 0).
+# The tables are signed (BICUBIC and LANCZOS have negative lobes): a normalised coefficient has |k| < 2 (-0.13..1.13 and
+# -0.29..1.29 over in, out in 1..79 and {224, 255, 256, 500, 1000}), so k * 2^22 fits the engine's signed 24-bit multiply,
+# and a row's sum of |k| * 255 is far below 2^31 (that would take sum |k| > 2^9): the int32 accumulators hold.
 PREPROCESS_LIST_LDS_BYTES = 64 * 1024
 
 _PL_HEADER = np.dtype([(k, "<i4") for k in ("n_frames", "n_units", "crop", "lds_bytes", "frames_off", "units_off",
@@ -154,11 +190,12 @@ def preprocess_geometry(sizes, resize: int, crop: int) -> np.ndarray:
     return geo
 
 
-def preprocess_layout(geometry: np.ndarray, crop: int, pinned: bool = False):
-    """The host block of `preprocess_list` (imgxf_preprocess_list_layout_host) for int32 [N, 6] geometry rows as a uint8
-    array.  `pinned=True`: (array, the pinned uint8 tensor that owns its memory) instead.  No device is touched."""
-    args = (len(geometry), crop, PREPROCESS_LIST_LDS_BYTES)
-    made = _list_block.layout("imgxf_preprocess_list_layout_host", geometry, args, pinned)
+def preprocess_layout(geometry: np.ndarray, crop: int, pinned: bool = False, interpolation=BILINEAR):
+    """The host block of `preprocess_list` (imgxf_preprocess_list_layout_filter_host) for int32 [N, 6] geometry rows and
+    Resize's filter as a uint8 array.  `pinned=True`: (array, the pinned uint8 tensor that owns its memory) instead.  No
+    device is touched."""
+    args = (len(geometry), crop, resample_filter(interpolation), PREPROCESS_LIST_LDS_BYTES)
+    made = _list_block.layout("imgxf_preprocess_list_layout_filter_host", geometry, args, pinned)
     return made if pinned else made[0]
 
 
@@ -167,17 +204,21 @@ def preprocess_block_views(block: np.ndarray):
     return _list_block.views(block, _PL_HEADER, _PL_FRAME, _PL_UNIT, "frames")
 
 
-def preprocess_list(frames, resize: int = 256, crop: int = 224, mean=None, std=None, out=None) -> torch.Tensor:
+def preprocess_list(frames, resize: int = 256, crop: int = 224, mean=None, std=None, out=None,
+                    interpolation=BILINEAR) -> torch.Tensor:
     """`preprocess` on a sequence of uint8 RGB device frames [H_i, W_i, 3] of any sizes — what `jpeg_decode.decode`
     returns — in ONE kernel launch and one host-to-device copy: float32 [N, 3, crop, crop] in the order of `frames`,
-    entry i bit for bit `preprocess(frames[i][None], resize, crop, mean, std)[0]`.
+    entry i bit for bit `preprocess(frames[i][None], resize, crop, mean, std, interpolation)[0]`.  `interpolation`:
+    Resize's filter as `resample_filter` reads it; the tables are host-built, so the launch serves all five.
 
     Frames may have any row stride and byte offset (columns and channels dense, as `_ffi.view_of` requires) and must
     share one device.  `out`: optional contiguous float32 [N, 3, crop, crop] destination on that device, returned when
     given.  Nothing is allocated with hipMalloc, synchronised or kept on the device between calls: the host lays out
     one block (records, work units, the coefficient tables of every distinct size) in pinned memory, and the launch
-    follows its copy on the current stream.  A frame beyond PREPROCESS_LIST_LDS_BYTES goes through `preprocess` and
-    its result is written into its slot; the other frames still share the one launch."""
+    follows its copy on the current stream.  A frame beyond PREPROCESS_LIST_LDS_BYTES (the limits per filter stand beside
+    that constant) goes through `preprocess` and its result is written into its slot; the other frames still share the
+    one launch."""
+    filt = resample_filter(interpolation)
     frames = list(frames)
     if (mean is None) != (std is None):
         raise ValueError("mean and std come together")
@@ -196,18 +237,18 @@ def preprocess_list(frames, resize: int = 256, crop: int = 224, mean=None, std=N
         out = torch.empty((n, 3, crop, crop), dtype=torch.float32, device=device)
     if n == 0:
         return out
-    block, gpu = _stage_list(frames, resize, crop, device)
+    block, gpu = _stage_list(frames, resize, crop, device, filt)
     _launch_list(block, gpu, out, mean, std, device)
     for i in np.flatnonzero(preprocess_block_views(block)[1]["unit_rows"] == 0):
-        out[i].copy_(preprocess(frames[i][None], resize, crop, mean, std)[0])
+        out[i].copy_(preprocess(frames[i][None], resize, crop, mean, std, filt)[0])
     return out
 
 
-def _stage_list(frames, resize: int, crop: int, device):
+def _stage_list(frames, resize: int, crop: int, device, filt: int = BILINEAR):
     """The block of one `preprocess_list` call, built in pinned memory, and its copy on the device (one non-blocking
     host-to-device copy on the current stream; None when no frame has a work unit)."""
     geometry = preprocess_geometry([(t.shape[0], t.shape[1]) for t in frames], resize, crop)
-    block, staged = preprocess_layout(geometry, crop, pinned=True)
+    block, staged = preprocess_layout(geometry, crop, pinned=True, interpolation=filt)
     hd, rec, _ = preprocess_block_views(block)
     rec["data"], rec["row_stride"] = _list_block.addresses(frames)
     if not hd["n_units"]:
@@ -232,13 +273,22 @@ def _launch_list(block, gpu, out, mean, std, device) -> None:
 # columns a table can touch.  An entry is taken by the kernel when ONE output row fits:
 #     r16(4 * (Sw * (2 + ksx) + 2 + ksy)) + r16(min(bh, ksy) * 12 * ceil(Sw / 4))
 #         + 4 * ((3 * min(bw, ceil((Sw - 1) * bw / Sw) + ksx) + 6) & ~3) <= RESIZED_CROP_LIST_LDS_BYTES
-# with ks = 2 * ceil(max(box / out, 1)) + 1 taps per axis and r16 rounding up to 16.  A box more than 100 times as tall as
+# with ks = 2 * ceil(support * max(box / out, 1)) + 1 taps per axis (support 0.5 BOX, 1 BILINEAR, 2 BICUBIC) and r16
+# rounding up to 16.  A box more than 100 times as tall as
 # wide that loses rows is filtered rows first, as Image.resize does for that shape; its second term is
 #     r16(min(bh, ksy) * 12 * ceil(bw / 4)) + r16(12 * ceil(bw / 4)) + r16(12 * ceil(Sw / 4)).
-# The column tables and the staged spans grow together with the box, so with equal scales on both axes that holds up to a
-# 10-fold reduction at Sw = 224 (21 taps, a 2240 x 2240 box), 5-fold at Sw = 384, 4-fold at Sw = 512, 77-fold at Sw = 32.
-# An entry beyond it goes through `ops.resize_crop` + `to_tensor` in its place (the host layout marks it: unit_rows == 0)
-# and `taken` reports it.
+# The column tables and the staged spans grow together with the box, so with equal scales on both axes that holds up to
+# (largest whole-number reduction, its taps)
+#     Sw          BOX          BILINEAR       BICUBIC
+#     224     14-fold  15    10-fold  21     6-fold  25       (10-fold: a 2240 x 2240 box)
+#     384      8-fold   9     5-fold  11     3-fold  13
+#     512      5-fold   7     4-fold   9     2-fold   9
+#      32    106-fold 107    77-fold 155    50-fold 201
+# BICUBIC doubles BILINEAR's taps, so it is taken up to roughly half the reduction.  An entry beyond it goes through
+# `ops.resize_crop` + `to_tensor` in its place (the host layout marks it: unit_rows == 0) and `taken` reports it.  The
+# kernel builds BOX, BILINEAR and BICUBIC tables: polynomials, IEEE operations alone, so its fp64 gives the host's doubles.
+# HAMMING and LANCZOS need sin and cos, whose device results are not promised equal to the host's: every entry of a call
+# with one of them goes that per-entry way.  Signed tables: |k| < 2, as stated above PREPROCESS_LIST_LDS_BYTES.
 RESIZED_CROP_LIST_LDS_BYTES = 64 * 1024
 
 _RCL_HEADER = np.dtype([(k, "<i4") for k in ("n_entries", "n_units", "sh", "sw", "lds_bytes", "entries_off", "units_off",
@@ -248,12 +298,12 @@ _RCL_ENTRY = np.dtype([("data", "<u8"), ("row_stride", "<i8")] + [(k, "<i4") for
 _RCL_UNIT = np.dtype([(k, "<i4") for k in ("entry", "y0", "ny", "lds_bytes")])     # structs imgxf_resized_crop_* (imgxf.h)
 
 
-def resized_crop_layout(geometry: np.ndarray, size, pinned: bool = False):
-    """The host block of `resized_crop_list` (imgxf_resized_crop_list_layout_host) for int32 [K, 7] geometry rows
-    (h, w, top, left, box height, box width, flip) and the output size (Sh, Sw), as a uint8 array.  `pinned=True`:
-    (array, the pinned uint8 tensor that owns its memory) instead.  No device is touched."""
-    args = (len(geometry), *size, RESIZED_CROP_LIST_LDS_BYTES)
-    made = _list_block.layout("imgxf_resized_crop_list_layout_host", geometry, args, pinned)
+def resized_crop_layout(geometry: np.ndarray, size, pinned: bool = False, interpolation=BILINEAR):
+    """The host block of `resized_crop_list` (imgxf_resized_crop_list_layout_filter_host) for int32 [K, 7] geometry rows
+    (h, w, top, left, box height, box width, flip), the output size (Sh, Sw) and the filter, as a uint8 array.
+    `pinned=True`: (array, the pinned uint8 tensor that owns its memory) instead.  No device is touched."""
+    args = (len(geometry), *size, resample_filter(interpolation), RESIZED_CROP_LIST_LDS_BYTES)
+    made = _list_block.layout("imgxf_resized_crop_list_layout_filter_host", geometry, args, pinned)
     return made if pinned else made[0]
 
 
@@ -293,14 +343,17 @@ def _int_array(values, name: str, width=None) -> np.ndarray:
     return a.astype(np.int64)
 
 
+_RCL_KERNEL_FILTERS = (2, 3, 4)         # BILINEAR, BICUBIC, BOX: the tables resized_crop_list's kernel builds itself
+
+
 def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, std=None, dtype=torch.float32, out=None,
-                      taken=None) -> torch.Tensor:
-    """torchvision's `F.resized_crop(img, top, left, height, width, size, BILINEAR)`, then `F.hflip` where `flips[k]`,
+                      taken=None, interpolation=BILINEAR) -> torch.Tensor:
+    """torchvision's `F.resized_crop(img, top, left, height, width, size, interpolation)`, then `F.hflip` where `flips[k]`,
     then `ToTensor()` (+ `Normalize(mean, std)`) for K entries over a sequence of uint8 RGB device frames [H_i, W_i, 3] of
     any sizes, each entry with a box of its own — `RandomResizedCrop` + `RandomHorizontalFlip` with the draws of
     `random_resized_crop_params`, or several fixed crops per image — in ONE kernel launch and one host-to-device copy:
     float32 [K, 3, Sh, Sw], entry k bit for bit what Pillow gives for
-    `Image.fromarray(frame).crop((left, top, left + width, top + height)).resize((Sw, Sh), Image.BILINEAR)`
+    `Image.fromarray(frame).crop((left, top, left + width, top + height)).resize((Sw, Sh), interpolation)`
     (+ `transpose(FLIP_LEFT_RIGHT)`) followed by `to_tensor`.  No tap reads a pixel outside the box.  (That includes
     Pillow's order of passes: rows before columns where a box is more than 100 times as tall as wide and loses rows.)
 
@@ -309,11 +362,16 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
     `frames[index[k]]` (default: entry k reads frame k); one frame may serve many entries.  `dtype=torch.uint8`: the
     bytes before ToTensor, [K, Sh, Sw, 3].  `out`: optional contiguous destination of that shape and dtype, returned when
     given.  `taken`: optional list, filled with K bools — False where the entry exceeded RESIZED_CROP_LIST_LDS_BYTES and
-    went through `ops.resize_crop` instead; the others still share the one launch.
+    went through `ops.resize_crop` instead; the others still share the one launch.  `interpolation`: the filter as
+    `resample_filter` reads it.  BILINEAR, BICUBIC and BOX run in the kernel (BICUBIC up to roughly half BILINEAR's
+    reduction: the limits per filter stand beside that constant).  HAMMING and LANCZOS need sin and cos, which the kernel
+    does not evaluate: every entry then goes through `ops.resize_crop` with the filter, the same bits, and `taken` is all
+    False.
 
     Frames may have any row stride and byte offset (columns and channels dense) and must share one device.  The host
     sends one small record per entry and no coefficient table: the kernel computes the tables itself, so no resample
     plan is created or kept, whatever the number of distinct boxes."""
+    filt = resample_filter(interpolation)
     frames = list(frames)
     if (mean is None) != (std is None):
         raise ValueError("mean and std come together")
@@ -363,25 +421,28 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
         return out
     geometry = np.empty((k, 7), np.int32)
     geometry[:, :2], geometry[:, 2:6], geometry[:, 6] = hw, boxes, flips
-    block, staged = resized_crop_layout(geometry, (sh, sw), pinned=True)
-    hd, rec, _ = resized_crop_block_views(block)
-    ptr, stride = _list_block.addresses(frames)
-    rec["data"], rec["row_stride"] = ptr[index], stride[index]
-    if hd["n_units"]:
-        with torch.cuda.device(device):
-            gpu = staged.to(device, non_blocking=True)
-            F.call("imgxf_resized_crop_list", block.ctypes.data, block.nbytes, gpu.data_ptr(), out.data_ptr(),
-                   1 if dtype == torch.uint8 else 0, F.f32_array(mean) if mean is not None else None,
-                   F.f32_array(std) if std is not None else None, torch.cuda.current_stream(device).cuda_stream)
-    served = rec["unit_rows"] > 0
+    if filt in _RCL_KERNEL_FILTERS:
+        block, staged = resized_crop_layout(geometry, (sh, sw), pinned=True, interpolation=filt)
+        hd, rec, _ = resized_crop_block_views(block)
+        ptr, stride = _list_block.addresses(frames)
+        rec["data"], rec["row_stride"] = ptr[index], stride[index]
+        if hd["n_units"]:
+            with torch.cuda.device(device):
+                gpu = staged.to(device, non_blocking=True)
+                F.call("imgxf_resized_crop_list_filter", block.ctypes.data, block.nbytes, gpu.data_ptr(), out.data_ptr(),
+                       1 if dtype == torch.uint8 else 0, filt, F.f32_array(mean) if mean is not None else None,
+                       F.f32_array(std) if std is not None else None, torch.cuda.current_stream(device).cuda_stream)
+        served = rec["unit_rows"] > 0
+    else:                                                        # HAMMING, LANCZOS: no table the kernel can build
+        served = np.zeros(k, bool)
     for i in np.flatnonzero(~served):
-        out[i].copy_(_resized_crop_entry(frames[index[i]], boxes[i], (sh, sw), bool(flips[i]), mean, std, dtype))
+        out[i].copy_(_resized_crop_entry(frames[index[i]], boxes[i], (sh, sw), bool(flips[i]), mean, std, dtype, filt))
     if taken is not None:
         taken[:] = served.tolist()
     return out
 
 
-def _resized_crop_entry(frame, box, size, flip: bool, mean, std, dtype):
+def _resized_crop_entry(frame, box, size, flip: bool, mean, std, dtype, filt: int = BILINEAR):
     """One entry of `resized_crop_list` by the calls that predate it: the resample plan of the box's own size (or a plain
     crop where the box already has the output's size, as `preprocess` does), `to_tensor`, the flip."""
     from . import ops
@@ -391,9 +452,9 @@ def _resized_crop_entry(frame, box, size, flip: bool, mean, std, dtype):
     if (bh, bw) == (sh, sw):
         t = ops.crop(view[None], (0, 0, sw, sh))
     elif bh > 100 * bw and sh < bh:                              # Image.resize filters such a shape rows first
-        t = ops.resize(ops.resize(view[None], (bw, sh), ops.RESAMPLE_BILINEAR), (sw, sh), ops.RESAMPLE_BILINEAR)
+        t = ops.resize(ops.resize(view[None], (bw, sh), filt), (sw, sh), filt)
     else:
-        t = ops.resize_crop(view[None], (sw, sh), (0, 0, sw, sh), ops.RESAMPLE_BILINEAR)
+        t = ops.resize_crop(view[None], (sw, sh), (0, 0, sw, sh), filt)
     if dtype == torch.uint8:
         return t[0].flip(1) if flip else t[0]
     t = to_tensor(t, mean, std)[0]

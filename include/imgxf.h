@@ -926,6 +926,15 @@ typedef struct imgxf_preprocess_unit {
  * resized image; IMGXF_ERR_WORKSPACE when block_cap is too small. */
 int imgxf_preprocess_list_layout_host(const int32_t* geometry, int n, int crop, int lds_budget, void* block,
                                       size_t block_cap, size_t* block_bytes);
+/* The same with Resize's filter stated: any IMGXF_RESAMPLE_* (the tables are host-built, so all five are taken; another
+ * value: IMGXF_ERR_ARG).  ksx, ksy, the LDS bounds and unit_rows follow the filter's taps, 2 ceil(support max(in / out, 1)) + 1
+ * with support 0.5 (BOX), 1 (BILINEAR, HAMMING), 2 (BICUBIC), 3 (LANCZOS): with equal scales on both axes one output row
+ * fits 64 KiB at crop 224 up to a 19-fold (BOX), 16-fold (BILINEAR, HAMMING), 11-fold (BICUBIC), 9-fold (LANCZOS)
+ * reduction.  imgxf_preprocess_list_layout_host is this call with IMGXF_RESAMPLE_BILINEAR; imgxf_preprocess_list_f32 reads
+ * the tables from the block and serves every filter.  Coefficients are signed 22-bit fixed point with |k| < 2, so a
+ * product with a byte fits the kernel's 24-bit multiply and a row's sum its int32 accumulator. */
+int imgxf_preprocess_list_layout_filter_host(const int32_t* geometry, int n, int crop, int filter, int lds_budget, void* block,
+                                             size_t block_cap, size_t* block_bytes);
 /* The launch: block_host is the caller's host copy of the block (its records are checked before the launch), block_dev
  * the same bytes on the device (8-byte aligned).  out: float32 [n][3][crop][crop], contiguous; slots of frames without
  * units are not written.  mean / std: HOST float[3], both or neither. */
@@ -953,7 +962,8 @@ typedef struct imgxf_resized_crop_entry {
     int32_t  h, w;              /* the frame */
     int32_t  top, left, bh, bw; /* the box, inside the frame */
     int32_t  flip;              /* 1: output column x is stored at sw - 1 - x */
-    int32_t  ksx, ksy;          /* taps per output column / row: 2 ceil(max(bw / sw, 1)) + 1, likewise for rows */
+    int32_t  ksx, ksy;          /* taps per output column / row: 2 ceil(support max(bw / sw, 1)) + 1, likewise for rows
+                                   (support 1: BILINEAR; the *_filter calls below: 0.5 BOX, 2 BICUBIC) */
     int32_t  unit_rows;         /* output rows per work unit; 0: the entry exceeds the LDS budget and has no units */
     int32_t  lds_bytes;         /* LDS bound of a unit of unit_rows rows */
     int32_t  tall;              /* 1 where bh > 100 bw and sh < bh: Image.resize then runs its vertical pass first */
@@ -980,6 +990,18 @@ int imgxf_resized_crop_list_layout_host(const int32_t* geometry, int n, int sh, 
  * out_u8 == 1: out is uint8 [n][sh][sw][3]; mean / std must be NULL.  Slots of entries without units are not written. */
 int imgxf_resized_crop_list(const void* block_host, size_t block_bytes, const void* block_dev, void* out, int out_u8,
                             const float* mean, const float* std, void* stream);
+/* The two calls with the filter of Image.resize stated (the block's layout is the same: its records have no field for the
+ * filter, so the caller passes the same value to both).  The layout takes any IMGXF_RESAMPLE_* (another value:
+ * IMGXF_ERR_ARG); ksx, ksy, the LDS bounds and unit_rows follow 2 ceil(support max(box / out, 1)) + 1 taps, `tall` does not
+ * depend on the filter.  The launch builds the tables of the polynomial filters — BILINEAR, BICUBIC, BOX: IEEE operations
+ * alone, so the device's fp64 gives precompute_coeffs' doubles — and refuses HAMMING and LANCZOS (sin, cos) with
+ * IMGXF_ERR_UNSUPPORTED; it checks every record's ksx / ksy against the filter it is given (IMGXF_ERR_ARG).  With equal
+ * scales on both axes one output row fits 64 KiB at sw = 224 up to a 14-fold (BOX), 10-fold (BILINEAR), 6-fold (BICUBIC)
+ * reduction.  The two calls above are these with IMGXF_RESAMPLE_BILINEAR. */
+int imgxf_resized_crop_list_layout_filter_host(const int32_t* geometry, int n, int sh, int sw, int filter, int lds_budget,
+                                               void* block, size_t block_cap, size_t* block_bytes);
+int imgxf_resized_crop_list_filter(const void* block_host, size_t block_bytes, const void* block_dev, void* out, int out_u8,
+                                   int filter, const float* mean, const float* std, void* stream);
 
 /* ---- the transformations of apply_all_transformations on a LIST of entries over frames of different sizes -------------
  * The driver's eight types and the later driver's flip, crop + resize and perspective warp, each entry with its own

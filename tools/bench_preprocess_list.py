@@ -11,7 +11,8 @@ the host time of building the block alone, and the kernel's share of the 8 TB/s 
 the crop window's touched source rows x touched columns x 3, plus 3 crop^2 x 4).  Exits non-zero when outputs differ.
 Needs a ROCm device.
 
-    python tools/bench_preprocess_list.py [--repeats 5] [--frames 1024] [--only A|B]
+    python tools/bench_preprocess_list.py [--repeats 5] [--frames 1024] [--only A|B] [--interpolation bicubic]
+`--interpolation`: Resize's filter for both routes (default bilinear), as `tensor_maps.resample_filter` reads it.
     rocprofv3 --kernel-trace --stats -- python tools/bench_preprocess_list.py --trace --repeats 3 --only A
     python tools/bench_preprocess_list.py --stats <that run's kernel_stats.csv> --repeats 3
 """
@@ -34,6 +35,7 @@ from imagetransformations_amd import tensor_maps as M
 RESIZE, CROP = 256, 224
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 HBM_BYTES_PER_S = 8.0e12
+FILTER = M.BILINEAR                                           # --interpolation
 
 
 def mixed_sizes(n, seed=0):
@@ -66,7 +68,7 @@ def per_size_route(frames):
     out = torch.empty((len(frames), 3, CROP, CROP), dtype=torch.float32, device=frames[0].device)
     for idx in groups.values():
         batch = torch.stack([frames[i] for i in idx])
-        out.index_copy_(0, torch.tensor(idx, device=out.device), M.preprocess(batch, RESIZE, CROP, MEAN, STD))
+        out.index_copy_(0, torch.tensor(idx, device=out.device), M.preprocess(batch, RESIZE, CROP, MEAN, STD, FILTER))
     return out
 
 
@@ -92,13 +94,13 @@ def kernel_and_host(frames, n):
     for _ in range(5):
         t0 = time.perf_counter()
         geo = M.preprocess_geometry([(t.shape[0], t.shape[1]) for t in frames], RESIZE, CROP)
-        block = M.preprocess_layout(geo, CROP)
+        block = M.preprocess_layout(geo, CROP, interpolation=FILTER)
         host.append((time.perf_counter() - t0) * 1e3)
     stage = []
     for _ in range(5):                                        # geometry + layout + pointers + the enqueue of the copy
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        block, gpu = M._stage_list(frames, RESIZE, CROP, dev)
+        block, gpu = M._stage_list(frames, RESIZE, CROP, dev, FILTER)
         stage.append((time.perf_counter() - t0) * 1e3)
     M._launch_list(block, gpu, out, MEAN, STD, dev)
     torch.cuda.synchronize()
@@ -117,7 +119,7 @@ def kernel_and_host(frames, n):
     hd, rec, units = M.preprocess_block_views(block)
     alg = int((rec["nrows"].astype(np.int64) * rec["ncols"] * 3).sum()) + n * 3 * CROP * CROP * 4
     print(f"  block: {block.nbytes} bytes, {int(hd['n_units'])} work units, {len(set(map(tuple, geo.tolist())))} table sets, "
-          f"dynamic LDS {int(hd['lds_bytes'])} bytes; host time of geometry + layout alone: best {min(host):.3f} ms "
+          f"dynamic LDS {int(hd['lds_bytes'])} bytes, {int((rec['unit_rows'] == 0).sum())} frames beyond the budget; host time of geometry + layout alone: best {min(host):.3f} ms "
           f"(all {', '.join(f'{t:.3f}' for t in host)})")
     print(f"  host breakdown of one call: staging the block (geometry, layout, pointers, enqueue of the copy) best "
           f"{min(stage):.3f} ms (all {', '.join(f'{t:.3f}' for t in stage)}); the launch call (record checks + enqueue) "
@@ -129,7 +131,7 @@ def kernel_and_host(frames, n):
 
 def workload(name, frames, old_route, repeats, cold, trace=False):
     n = len(frames)
-    new_route = lambda: M.preprocess_list(frames, RESIZE, CROP, MEAN, STD)
+    new_route = lambda: M.preprocess_list(frames, RESIZE, CROP, MEAN, STD, interpolation=FILTER)
     if trace:                                                 # for a kernel trace: each route `repeats` times, nothing else
         for _ in range(repeats):
             got = new_route()
@@ -204,6 +206,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--only", choices=["A", "B"])
+    ap.add_argument("--interpolation", default="bilinear", help="Resize's filter: bilinear, bicubic, box, hamming, lanczos")
     ap.add_argument("--trace", action="store_true", help="run each route --repeats times and nothing else (under rocprofv3)")
     ap.add_argument("--stats", metavar="CSV", help="print the kernels of a --trace run from its kernel_stats CSV (no device)")
     args = ap.parse_args()
@@ -212,12 +215,15 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_preprocess_list needs a ROCm device")
     dev = torch.device("cuda:0")
+    global FILTER
+    FILTER = M.resample_filter(args.interpolation)
+    print(f"interpolation: {args.interpolation} (Pillow resampling filter {FILTER})")
     ok = True
     if args.only in (None, "A"):
         frames, _ = noise_frames([(375, 500)] * args.frames, dev, 1)
         x = torch.stack(frames)                               # one tensor; the list route takes its frames
         del frames
-        ok &= workload("A (uniform 375 x 500)", list(x), lambda: M.preprocess(x, RESIZE, CROP, MEAN, STD), args.repeats, False, args.trace)
+        ok &= workload("A (uniform 375 x 500)", list(x), lambda: M.preprocess(x, RESIZE, CROP, MEAN, STD, FILTER), args.repeats, False, args.trace)
         del x
     if args.only in (None, "B"):
         sizes = mixed_sizes(args.frames)

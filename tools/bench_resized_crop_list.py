@@ -13,6 +13,9 @@ device synchronise.  The list call is also split into host time (checks, layout,
 Needs a ROCm device.
 
     python tools/bench_resized_crop_list.py [--repeats 5] [--frames 1024] [--only uniform|mixed] [--route both|loop|list]
+                                            [--interpolation bicubic]
+`--interpolation`: the filter of both routes (default bilinear; the loop passes Pillow's integer to `ops.resize_crop`, so
+`--route loop --interpolation bicubic` runs in a checkout whose list call knows BILINEAR alone).
 """
 from __future__ import annotations
 
@@ -34,6 +37,8 @@ from imagetransformations_amd import tensor_maps as M
 
 SIZE = 224
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+FILTERS = {"lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}      # Pillow's resampling integers
+FILTER = FILTERS["bilinear"]                                  # --interpolation
 
 
 def draw_params(sizes, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p=0.5):
@@ -72,7 +77,7 @@ def loop_route(frames, boxes, flips):
         if (bh, bw) == (SIZE, SIZE):
             u8 = ops.crop(view[None], (0, 0, SIZE, SIZE))
         else:
-            u8 = ops.resize_crop(view[None], (SIZE, SIZE), (0, 0, SIZE, SIZE), ops.RESAMPLE_BILINEAR)
+            u8 = ops.resize_crop(view[None], (SIZE, SIZE), (0, 0, SIZE, SIZE), FILTER)
         x = M.to_tensor(u8, MEAN, STD)[0]
         out[i] = x.flip(2) if flip else x
     return out
@@ -103,17 +108,17 @@ def split_list_call(frames, boxes, flips, n):
     layout = []
     for _ in range(5):
         t0 = time.perf_counter()
-        M.resized_crop_layout(geo, (SIZE, SIZE))
+        M.resized_crop_layout(geo, (SIZE, SIZE), interpolation=FILTER)
         layout.append((time.perf_counter() - t0) * 1e3)
     out = torch.empty((n, 3, SIZE, SIZE), dtype=torch.float32, device=dev)
     host = []
     for _ in range(5):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        M.resized_crop_list(frames, boxes, SIZE, flips, mean=MEAN, std=STD, out=out)
+        M.resized_crop_list(frames, boxes, SIZE, flips, mean=MEAN, std=STD, out=out, interpolation=FILTER)
         host.append((time.perf_counter() - t0) * 1e3)
     torch.cuda.synchronize()
-    block, staged = M.resized_crop_layout(geo, (SIZE, SIZE), pinned=True)
+    block, staged = M.resized_crop_layout(geo, (SIZE, SIZE), pinned=True, interpolation=FILTER)
     hd, rec, _ = M.resized_crop_block_views(block)
     rec["data"] = [t.data_ptr() for t in frames]
     rec["row_stride"] = [t.stride(0) for t in frames]
@@ -125,7 +130,8 @@ def split_list_call(frames, boxes, flips, n):
     mean, std = M.F.f32_array(MEAN), M.F.f32_array(STD)
     stream = torch.cuda.current_stream(dev).cuda_stream
     for _ in range(20):
-        M.F.call("imgxf_resized_crop_list", block.ctypes.data, block.nbytes, gpu.data_ptr(), out.data_ptr(), 0, mean, std, stream)
+        M.F.call("imgxf_resized_crop_list_filter", block.ctypes.data, block.nbytes, gpu.data_ptr(), out.data_ptr(), 0, FILTER, mean,
+                 std, stream)
     ev[2].record()
     torch.cuda.synchronize()
     print(f"  block: {block.nbytes} bytes for {n} entries, {int(hd['n_units'])} work units, dynamic LDS {int(hd['lds_bytes'])} bytes, "
@@ -150,7 +156,7 @@ def workload(name, frames, sizes, route, repeats):
         plans = len(ops._plans._plans)
         old()
     if route in ("both", "list"):
-        new = lambda: M.resized_crop_list(frames, boxes, SIZE, flips, mean=MEAN, std=STD)
+        new = lambda: M.resized_crop_list(frames, boxes, SIZE, flips, mean=MEAN, std=STD, interpolation=FILTER)
         before = len(ops._plans._plans)
         new(); new()
         new_plans = len(ops._plans._plans) - before
@@ -179,6 +185,8 @@ def workload(name, frames, sizes, route, repeats):
         print(f"  outputs equal: {same}")
     if route in ("both", "list"):
         split_list_call(frames, boxes, flips, n)
+    if FILTER != FILTERS["bilinear"]:
+        return same
     pre = lambda: M.preprocess_list(frames, 256, 224, MEAN, STD)     # (predates the list call: timed with either route)
     pre(); pre()
     line("preprocess_list, same frames", [timed(pre)[0] for _ in range(repeats)], n)
@@ -191,7 +199,13 @@ def main():
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--only", choices=["uniform", "mixed"])
     ap.add_argument("--route", choices=["both", "loop", "list"], default="both")
+    ap.add_argument("--interpolation", choices=sorted(FILTERS), default="bilinear")
     args = ap.parse_args()
+    global FILTER
+    FILTER = FILTERS[args.interpolation]
+    if FILTER not in (2, 3, 4) and args.route != "loop":
+        sys.exit("resized_crop_list's kernel builds bilinear, bicubic and box tables: time the others with --route loop")
+    print(f"interpolation: {args.interpolation}")
     if not torch.cuda.is_available():
         sys.exit("bench_resized_crop_list needs a ROCm device")
     dev = torch.device("cuda:0")
