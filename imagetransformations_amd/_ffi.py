@@ -196,6 +196,8 @@ SIGNATURES = {
     "imgxf_resized_crop_list_layout_filter_host": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                    C.POINTER(C.c_size_t)],
     "imgxf_resized_crop_list_filter": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _F, _F, C.c_void_p],
+    "imgxf_resize_list_layout_host": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "imgxf_resize_list_u8": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_driver_list_layout_host": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)],
     "imgxf_driver_list_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],

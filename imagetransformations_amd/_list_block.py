@@ -1,5 +1,5 @@
 """The Python side that the record-driven list passes share (tensor_maps.preprocess_list, tensor_maps.resized_crop_list,
-driver_list.apply_list): the host block `header | records | units [| tables]` of a `*_layout_host` entry point, its
+driver_list.apply_list, resize_list.resize_list): the host block `header | records | units [| tables]` of a `*_layout_host` entry point, its
 structured views, and the frames whose addresses go into its records."""
 from __future__ import annotations
 

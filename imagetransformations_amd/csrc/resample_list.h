@@ -1,4 +1,5 @@
-// The band engine of the record-driven list kernels (preprocess_list.hip, driver_list.hip, resized_crop_list.hip):
+// The band engine of the record-driven list kernels (preprocess_list.hip, driver_list.hip, resized_crop_list.hip,
+// resize_list.hip):
 // Pillow's two-pass 8-bit Image.resize on ONE workgroup's band of output rows of one RGB frame — the horizontal pass of
 // the touched source rows into an LDS intermediate (uint8, as Pillow's is), the vertical pass from it, the store
 // epilogues — and what the host halves share around it: the LDS layout (one statement for host and device), the

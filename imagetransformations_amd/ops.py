@@ -380,6 +380,13 @@ def resize(t: torch.Tensor, size: tuple[int, int], resample: int = RESAMPLE_BICU
     return out
 
 
+def resize_list(frames, sizes, interpolation=RESAMPLE_BICUBIC, boxes=None, index=None, taken=None):
+    """`resize` for a list of frames of different sizes, every entry to a (width, height) of its own, in one launch and
+    without resample plans: `resize_list.resize_list`, where the arguments are described."""
+    from . import resize_list as _module
+    return _module.resize_list(frames, sizes, interpolation, boxes, index, taken)
+
+
 def resize_crop(t: torch.Tensor, size: tuple[int, int], box: tuple[int, int, int, int],
                 resample: int = RESAMPLE_LANCZOS, out: torch.Tensor | None = None) -> torch.Tensor:
     """img.resize(size, resample).crop(box) without computing the cropped-away pixels: only the

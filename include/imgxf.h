@@ -1003,6 +1003,75 @@ int imgxf_resized_crop_list_layout_filter_host(const int32_t* geometry, int n, i
 int imgxf_resized_crop_list_filter(const void* block_host, size_t block_bytes, const void* block_dev, void* out, int out_u8,
                                    int filter, const float* mean, const float* std, void* stream);
 
+/* ---- Image.resize of a LIST of frames of different sizes, every entry to a size of its own ----------------------------
+ * Entry k is Image.fromarray(frame)[.crop(box)].resize((ow, oh), filter) for any of the five convolution filters, uint8 in
+ * and uint8 out, all entries in ONE launch; the box is the image (coefficient windows clamped to it).  Several entries
+ * may read one frame.  The HOST lays out one block
+ *     imgxf_resize_list_header | imgxf_resize_list_entry[n] | imgxf_resize_list_unit[n_units] | int32 tables
+ * which the caller copies to the device once.  The tables are precompute_coeffs' for (bw -> ow) and (bh -> oh), appended
+ * once per distinct (in, out) axis of the call's filter and shared by every entry with that axis; offsets of tables are
+ * int32 indices into the block.  The outputs are [oh][ow][3] uint8, contiguous, each at its entry's out_off (a multiple of
+ * 16) in ONE output buffer of out_bytes bytes.
+ *
+ * A work unit is a band of rows AND a chunk of columns: output rows [y0, y0 + ny) x columns [x0, x0 + nx) of one entry.
+ * Its workgroup keeps in LDS the horizontally filtered source rows the band touches, nx pixels wide (R x 12 ceil(nx / 4)
+ * bytes, rounded up to 16), and four staged spans of the C source columns the chunk's own windows touch ((3 C + 6) & ~3
+ * bytes each).  THE RULE (the one statement; `budget` = lds_budget capped at 64 KiB):
+ *   chunk:     for parts = 1, 2, 4, ...: nx = min(ow, ceil(ow / parts) rounded up to 4); the entry takes the first nx for
+ *              which rows(nx) > 0; where nx has come down to 4 (or ow < 4) and rows(nx) == 0 the entry is refused.  So an
+ *              entry keeps the full width whenever one band fits, and only wide outputs and deep reductions are cut.
+ *   rows(nx):  the most ny in 1 .. min(oh, 16) with lds(ny, nx) <= budget / 2; where none, with <= budget / 4 * 3; where
+ *              none, with <= budget; else 0 (the three steps of the older list kernels: five, three, two workgroups per CU)
+ *   lds(ny, nx) = r16(R x 12 ceil(nx / 4)) + 4 ((3 C + 6) & ~3),  R = min(bh, ceil((ny - 1) bh / oh) + ksy),
+ *                                                                 C = min(bw, ceil((nx - 1) bw / ow) + ksx)
+ *   with ks = 2 ceil(support max(in / out, 1)) + 1 taps per axis.  Chunks are x0 = 0, nx, 2 nx, ...: x0 is a multiple of 4
+ *   and so is every chunk's width but the last one's.  A unit's own lds_bytes is the same expression with the R and C its
+ *   tables really touch (never more than the bounds).
+ * An entry is also refused (unit_rows == 0) where Image.resize filters rows before columns: a box more than 100 times as
+ * tall as wide that loses rows (bh > 100 bw and oh < bh).  The caller serves refused entries by another route. */
+typedef struct imgxf_resize_list_header {
+    int32_t n_entries, n_units;
+    int32_t lds_bytes;          /* the largest unit's LDS need = the launch's dynamic LDS size */
+    int32_t pad_;
+    int32_t entries_off, units_off, tables_off, total_bytes;   /* byte offsets of the sections, size of the block */
+    int64_t out_bytes;          /* size of the output buffer: the end of the last entry's slot (refused entries have slots
+                                   too, which the launch does not write) */
+} imgxf_resize_list_header;
+typedef struct imgxf_resize_list_entry {
+    uint64_t data;              /* DEVICE address of pixel (0, 0) of the FRAME; filled by the caller, as is row_stride
+                                   (bytes, >= 3 w) */
+    int64_t  row_stride;
+    int64_t  out_off;           /* byte offset of the entry's [oh][ow][3] output in the output buffer, a multiple of 16
+                                   (the layout packs them; a caller may respace them and out_bytes) */
+    int32_t  h, w;              /* the frame */
+    int32_t  top, left, bh, bw; /* the box, inside the frame (the whole frame: 0, 0, h, w) */
+    int32_t  oh, ow;            /* the output size */
+    int32_t  ksx, ksy;          /* taps per output column / row (row length of the coefficient tables) */
+    int32_t  bounds_x, coeffs_x, bounds_y, coeffs_y;   /* [ow][2] (first source index in the box, count), [ow][ksx]; [oh]... */
+    int32_t  unit_rows;         /* output rows per work unit; 0: refused, no units, no tables */
+    int32_t  chunk;             /* output columns per work unit (ow: the units keep the full width) */
+} imgxf_resize_list_entry;
+typedef struct imgxf_resize_list_unit {
+    int32_t entry, y0, ny;      /* one workgroup: output rows [y0, y0 + ny) ... */
+    int32_t x0, nx;             /* ... x output columns [x0, x0 + nx) of entry `entry` */
+    int32_t col0, ncols;        /* the box columns the windows of those output columns touch: what the unit stages */
+    int32_t lds_bytes;
+} imgxf_resize_list_unit;
+/* HOST half (no device work).  geometry: int32 [n][8] = (h, w, top, left, bh, bw, oh, ow) per entry; filter: any
+ * IMGXF_RESAMPLE_*.  *block_bytes receives the block's size; block == NULL: only that.
+ * Errors: IMGXF_ERR_NULL; IMGXF_ERR_ARG for n < 0, an unknown filter, lds_budget < 1, a side outside 1..32767, a box that
+ * is empty or not inside its frame; IMGXF_ERR_SHAPE for a block beyond 2 GiB; IMGXF_ERR_WORKSPACE when block_cap is too
+ * small. */
+int imgxf_resize_list_layout_host(const int32_t* geometry, int n, int filter, int lds_budget, void* block, size_t block_cap,
+                                  size_t* block_bytes);
+/* The launch: block_host is the caller's host copy of the block, block_bytes its size, block_dev the same bytes on the
+ * device (8-byte aligned), out the output buffer (16-byte aligned) of out_bytes bytes.  Before the launch every record is
+ * checked against its frame, the block, the launch's LDS and the output buffer, so that they bound every address the
+ * kernel forms (IMGXF_ERR_ARG / IMGXF_ERR_SHAPE / IMGXF_ERR_NULL, never a launch); nothing past block_bytes is read.  A
+ * block without units launches nothing. */
+int imgxf_resize_list_u8(const void* block_host, size_t block_bytes, const void* block_dev, void* out, size_t out_bytes,
+                         void* stream);
+
 /* ---- the transformations of apply_all_transformations on a LIST of entries over frames of different sizes -------------
  * The driver's eight types and the later driver's flip, crop + resize and perspective warp, each entry with its own
  * frame, type and drawn value, bit for bit what the per-type entry points give: one block
