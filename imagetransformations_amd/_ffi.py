@@ -153,6 +153,10 @@ SIGNATURES = {
     "imgxf_jpeg_optimal_tables": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "imgxf_jpeg_encode_ex_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p],
+    "imgxf_jpeg_encode_list_ex_layout_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                              C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_encode_list_ex_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_jpeg_workspace_bytes_prog": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_prog_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p],
@@ -230,15 +234,23 @@ class JpegListFrame(C.Structure):
                 ("cnt_off", C.c_int64), ("out_off", C.c_int64), ("out_cap", C.c_int64)]
 
 
+class JpegEncParams(C.Structure):
+    """struct imgxf_jpeg_enc_params (include/imgxf.h)."""
+    _fields_ = [("ncomp", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32), ("optimize", C.c_int32)]
+
+
+JPEG_LIST_OPT_AREAS = 3
+
+
+class JpegListExHeader(C.Structure):
+    """struct imgxf_jpeg_list_ex_header (include/imgxf.h)."""
+    _fields_ = [("list", JpegListHeader), ("params", JpegEncParams), ("opt_off", C.c_uint64 * JPEG_LIST_OPT_AREAS)]
+
+
 class JpegRoundtripListHeader(C.Structure):
     """struct imgxf_jpeg_roundtrip_list_header (include/imgxf.h)."""
     _fields_ = [("n_frames", C.c_int32), ("frames_off", C.c_int32), ("images_off", C.c_int32), ("units_off", C.c_int32),
                 ("n_units", C.c_int32), ("total_bytes", C.c_int32), ("workspace_bytes", C.c_uint64), ("out_bytes", C.c_uint64)]
-
-
-class JpegEncParams(C.Structure):
-    """struct imgxf_jpeg_enc_params (include/imgxf.h)."""
-    _fields_ = [("ncomp", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32), ("optimize", C.c_int32)]
 
 
 def _load() -> C.CDLL:

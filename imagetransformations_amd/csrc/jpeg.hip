@@ -52,9 +52,10 @@ struct JpegHeader {
 
 // Where a workgroup works.  A uniform batch (JpegUniform): frame blockIdx.y (blockIdx.z in the transform), item blockIdx.x,
 // every per-frame area at the uniform stride the kernel's arguments state.  A list of frames of different sizes (JpegList,
-// imgxf_jpeg_encode_list_u8): entry blockIdx.x of the stage's unit table names the frame and the item, and the frame's
-// record holds what the uniform arguments hold for a batch — geometry, the frame's offset in every area, its stream and
-// chunk counts, its slot of the output.  One copy of each stage serves both: W is the stage's last template parameter.
+// imgxf_jpeg_encode_list_u8 and, for every layout and the frames' own tables, imgxf_jpeg_encode_list_ex_u8): entry
+// blockIdx.x of the stage's unit table names the frame and the item, and the frame's record holds what the uniform
+// arguments hold for a batch — geometry, the frame's offset in every area, its stream and chunk counts, its slot of the
+// output.  One copy of each stage serves both: W is the stage's last template parameter.
 struct JpegUniform {
     static constexpr bool LIST = false;
 };
@@ -956,14 +957,28 @@ __device__ __forceinline__ int write_dht_segment(u8* __restrict__ o, const JpegD
 // starts (kept on the device: no host round trip; the first scan starts at hd.len); the sequential optimize file is the
 // one-scan case (si = 0, last, pos unused).  Sentinels of pos[] / sizes[]: JSIZE_HUFF_OVERFLOW (an optimal code over 32
 // bits) and 0xFFFFFFFF (capacity); once a scan of frame f fails, the later scans carry the sentinel forward and write nothing.
+// A list's frame (JpegList): its own slot of `out`, its own height and width in the prefix's SOF segment.
+template <class W>
 __global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restrict__ stream, int64_t fs_words,
                                                               const u32* __restrict__ total_bits, const u32* __restrict__ cnt,
                                                               int64_t cnt_fs, int nchunks, const u32* __restrict__ ff_total,
                                                               u8* __restrict__ out, int64_t out_fs, u32* __restrict__ pos, int si, bool last,
                                                               u32* __restrict__ sizes, JpegHeader hd, const JpegDht* __restrict__ dht,
-                                                              JpScanHdr sh) {
+                                                              JpScanHdr sh, W wh) {
     __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
-    const int f = blockIdx.y, n = gridDim.y;
+    int f = blockIdx.y, bx = blockIdx.x, gdim = gridDim.x;
+    const int n = gridDim.y;
+    int64_t stream_o, cnt_o, out_o;
+    const imgxf_jpeg_list_frame* fr;
+    chunks_where(wh, f, bx, gdim, fs_words, stream_o, cnt_o, nchunks, cnt_fs, fr);
+    u32 dims = 0;
+    if constexpr (W::LIST) {                                    // (a list's file is one scan: si == 0, last, pos unused)
+        out_o = fr->out_off;
+        out_fs = fr->out_cap;
+        dims = ((u32)fr->h << 16) | (u32)fr->w;
+    } else {
+        out_o = (int64_t)f * out_fs;
+    }
     const u32 base = si == 0 ? (u32)hd.len : pos[(int64_t)si * n + f];
     const u32 tb = total_bits[f];
     const bool over = ((unsigned long long)tb + 31) / 32 > (unsigned long long)fs_words;
@@ -979,15 +994,22 @@ __global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restr
         }
     const int64_t end = (int64_t)base + hlen + nbytes + nff;    // the scan's end; EOI (2 bytes) must still fit
     if (!status && (over || end + 2 > out_fs)) status = 0xffffffffu;
-    u8* o = out + (int64_t)f * out_fs;
-    if (blockIdx.x == 0) {
+    u8* o = out + out_o;
+    if (bx == 0) {
         if (threadIdx.x == 0) {
             if (!last) pos[(int64_t)(si + 1) * n + f] = status ? status : (u32)end;
             else sizes[f] = status ? status : (u32)(end + 2);
         }
         if (!status) {
             if (si == 0)
-                for (int i = threadIdx.x; i < hd.len; i += 256) o[i] = hd.b[i];
+                for (int i = threadIdx.x; i < hd.len; i += 256) {
+                    u8 v = hd.b[i];
+                    if constexpr (W::LIST) {                    // the frame's own height and width, as jpeg_stuff_kernel
+                        const int d = i - wh.sof;
+                        if (d >= 0 && d < 4) v = (u8)(dims >> (24 - 8 * d));
+                    }
+                    o[i] = v;
+                }
             int p = (int)base;
             for (int s = 0; s < JSLOTS; ++s)
                 if ((sh.slots >> s) & 1) p += write_dht_segment(o + p, dht[(int64_t)f * JSLOTS + s], s);
@@ -999,7 +1021,7 @@ __global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restr
         }
     }
     if (status) return;
-    stuff_chunks(lb, blockIdx.x, gridDim.x, stream + (int64_t)f * fs_words, cnt + (int64_t)f * cnt_fs, nchunks, nbytes, tb, nff, o + base + hlen);
+    stuff_chunks(lb, bx, gdim, stream + stream_o, cnt + cnt_o, nchunks, nbytes, tb, nff, o + base + hlen);
 }
 
 // ---- host side: workspace, preparation, dispatch ---------------------------------------------------------------------
@@ -1228,14 +1250,26 @@ static int launch_stuff(const JpegJob& J, const JpScanHdr* sh, int si, bool last
                        (const u32*)J.tot_bits, J.cnt, (int64_t)L.nchunks, L.nchunks, JpegUniform{});
     IMGXF_CHECK(scan_rows(J.cnt, L.nchunks, L.nchunks, J.n, J.part, J.tot_ff, J.st));
     if (sh)
-        hipLaunchKernelGGL(jpeg_stuff_scan_kernel, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words, (const u32*)J.tot_bits,
-                           (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs, J.pos, si, last, J.sizes,
-                           J.hd, (const JpegDht*)J.dht, *sh);
+        hipLaunchKernelGGL(jpeg_stuff_scan_kernel<JpegUniform>, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words,
+                           (const u32*)J.tot_bits, (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs, J.pos,
+                           si, last, J.sizes, J.hd, (const JpegDht*)J.dht, *sh, JpegUniform{});
     else
         hipLaunchKernelGGL(jpeg_stuff_kernel<JpegUniform>, cgrid, dim3(256), 0, J.st, (const u32*)J.ustream, L.stream_words,
                            (const u32*)J.tot_bits, (const u32*)J.cnt, (int64_t)L.nchunks, L.nchunks, (const u32*)J.tot_ff, J.out, J.out_fs,
                            J.sizes, J.hd, JpegUniform{});
     return launch_status();
+}
+
+// the one scan of a sequential file with the frame's own tables: all components, all four (grayscale: two) DHT segments
+static JpScanHdr seq_scan_header(int ncomp) {
+    JpScanHdr sh;                                              // (jcmarker.c emit_sos)
+    memset(&sh, 0, sizeof(sh));
+    const u8 sos3[14] = {0xff, 0xda, 0x00, 0x0c, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3f, 0x00};
+    const u8 sos1[10] = {0xff, 0xda, 0x00, 0x08, 0x01, 0x01, 0x00, 0x00, 0x3f, 0x00};
+    sh.slots = ncomp == 3 ? 0xfu : 0x3u;
+    sh.soslen = ncomp == 3 ? 14 : 10;
+    memcpy(sh.sos, ncomp == 3 ? sos3 : sos1, (size_t)sh.soslen);
+    return sh;
 }
 
 #include "jpeg_encode_ext.inc"
@@ -1258,7 +1292,7 @@ static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* p
         launch_transform<L>(J);
         if (J.opt) {
             if (hipMemsetAsync(J.sym, 0, (size_t)J.n * JSLOTS * 256 * 4, J.st) != hipSuccess) return launch_status();
-            hipLaunchKernelGGL(jpeg_gather_kernel<L>, bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, J.g, J.sym);
+            hipLaunchKernelGGL((jpeg_gather_kernel<L, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, J.g, J.sym, JpegUniform{});
             hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(L == JLGRAY ? 2u : 4u, (unsigned)J.n), dim3(256), 0, J.st, (const u32*)J.sym, J.fh,
                                J.dht);
             hipLaunchKernelGGL((jpeg_lens_kernel<L, true, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs,
@@ -1277,13 +1311,7 @@ static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* p
             hipLaunchKernelGGL((jpeg_emit_kernel<L, false, JpegUniform>), bgrid, dim3(256), 0, J.st, coef, J.coef_fs, dcs, (const u32*)J.lens,
                                J.ustream, J.L.stream_words, (const u32*)J.tot_bits, J.g, J.hf, fh, JpegUniform{});
         if (!J.opt) return launch_stuff(J, nullptr, 0, true);
-        JpScanHdr sh;                                          // one scan over all components (jcmarker.c emit_sos)
-        memset(&sh, 0, sizeof(sh));
-        const u8 sos3[14] = {0xff, 0xda, 0x00, 0x0c, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3f, 0x00};
-        const u8 sos1[10] = {0xff, 0xda, 0x00, 0x08, 0x01, 0x01, 0x00, 0x00, 0x3f, 0x00};
-        sh.slots = J.ncomp == 3 ? 0xfu : 0x3u;
-        sh.soslen = J.ncomp == 3 ? 14 : 10;
-        memcpy(sh.sos, J.ncomp == 3 ? sos3 : sos1, (size_t)sh.soslen);
+        const JpScanHdr sh = seq_scan_header(J.ncomp);
         return launch_stuff(J, &sh, 0, true);
     });
 }
@@ -1291,12 +1319,14 @@ static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* p
 // ---- a list of frames of different sizes ------------------------------------------------------------------------------
 
 constexpr int JLIST_MAX_FRAMES = 1 << 20;
-static_assert(sizeof(imgxf_jpeg_list_header) == 136 && sizeof(imgxf_jpeg_list_frame) == 128 && sizeof(imgxf_jpeg_list_unit) == 8,
-              "include/imgxf.h documents these records");
+constexpr int JLIST_MAX_FRAMES_OPT = 65535;  // with the frames' own tables: the table stage is one workgroup per (table, frame), frames on grid y
+static_assert(sizeof(imgxf_jpeg_list_header) == 136 && sizeof(imgxf_jpeg_list_frame) == 128 && sizeof(imgxf_jpeg_list_unit) == 8 &&
+              sizeof(imgxf_jpeg_list_ex_header) == 176, "include/imgxf.h documents these records");
 
-static inline int list_stage_units(const imgxf_jpeg_list_frame& f, int stage) {
+// (stage 0 is the layout's transform kernel: 16×256-pixel strips at 4:2:0, one MCU row of JXP pixels in the other layouts)
+static inline int list_stage_units(const imgxf_jpeg_list_frame& f, int stage, int lay = JL420) {
     switch (stage) {
-    case 0: return ((f.mw + JM - 1) / JM) * f.mh;
+    case 0: return lay == JL420 ? ((f.mw + JM - 1) / JM) * f.mh : ((f.w + JXP - 1) / JXP) * f.mh;
     case 1: return (f.nblk + 255) / 256;
     case 2: return f.nparts_blk;
     case 3: return f.chunk_groups;
@@ -1307,13 +1337,21 @@ static inline int list_stage_units(const imgxf_jpeg_list_frame& f, int stage) {
 // The block of a list: get(i, h, w, cap) states frame i.  Every frame's geometry and stream capacity are what
 // jpeg_layout gives a batch of one such frame, and its piece of every area is at most that batch's (256-byte aligned)
 // area, so the workspace stays within the sum of the single-frame workspaces.  block == nullptr: the sizes alone.
+// ex == nullptr: the default file's block (imgxf_jpeg_list_header, 4:2:0, the call's tables).  Else the block of the class
+// *ex (checked by the caller) behind an imgxf_jpeg_list_ex_header: the layout's MCUs, blocks and transform strips and, with
+// optimize, three more areas indexed by the frame — symbol counts [n][4][256], code words [n], DHT records [n][4].
 template <typename Get>
-static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_jpeg_list_header* out_hd) {
-    if (n < 0 || n > JLIST_MAX_FRAMES) return IMGXF_ERR_SHAPE;
-    imgxf_jpeg_list_header hd;
-    memset(&hd, 0, sizeof(hd));
+static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_jpeg_list_ex_header* out_hd,
+                           const imgxf_jpeg_enc_params* ex = nullptr) {
+    const int lay = ex ? enc_layout(ex) : JL420;
+    const bool opt = ex && ex->optimize != 0;
+    const size_t hd_bytes = ex ? sizeof(imgxf_jpeg_list_ex_header) : sizeof(imgxf_jpeg_list_header);
+    if (n < 0 || n > (opt ? JLIST_MAX_FRAMES_OPT : JLIST_MAX_FRAMES)) return IMGXF_ERR_SHAPE;
+    imgxf_jpeg_list_ex_header xhd;
+    memset(&xhd, 0, sizeof(xhd));
+    imgxf_jpeg_list_header& hd = xhd.list;
     hd.n_frames = n;
-    hd.frames_off = (int32_t)sizeof(imgxf_jpeg_list_header);
+    hd.frames_off = (int32_t)hd_bytes;
     std::vector<imgxf_jpeg_list_frame> fr((size_t)n);
     size_t area[IMGXF_JPEG_LIST_AREAS] = {0};                // bytes so far: coef, dcs, acb, lens, part, tot, stream, cnt
     size_t units[IMGXF_JPEG_LIST_STAGES] = {0};
@@ -1324,7 +1362,7 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
         get(i, h, w, cap);
         if (h < 1 || w < 1 || h > 32767 || w > 32767) return IMGXF_ERR_SHAPE;
         if (cap < 1024 + 2 || cap > ((uint64_t)1 << 31)) return IMGXF_ERR_ARG;
-        const JpegLayout L = jpeg_layout(JL420, false, false, 1, h, w, (size_t)cap);
+        const JpegLayout L = jpeg_layout(lay, false, false, 1, h, w, (size_t)cap);
         if ((int64_t)L.nblk * 2048 > 0xfffffff0ll) return IMGXF_ERR_SHAPE;      // 32-bit bit offsets, per frame
         imgxf_jpeg_list_frame& f = fr[(size_t)i];
         memset(&f, 0, sizeof(f));
@@ -1350,7 +1388,7 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
         area[6] += (size_t)L.stream_words * 4;
         area[7] += (size_t)L.nchunks * 4;
         out += ((size_t)cap + 15) & ~(size_t)15;
-        for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) units[s] += (size_t)list_stage_units(f, s);
+        for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) units[s] += (size_t)list_stage_units(f, s, lay);
     }
     area[5] = (size_t)n * 8;
     size_t o = 0;
@@ -1358,9 +1396,17 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
         hd.area_off[a] = o;
         o += al256(area[a]);
     }
+    if (ex) {
+        xhd.params = *ex;
+        const size_t own[IMGXF_JPEG_LIST_OPT_AREAS] = {(size_t)JSLOTS * 256 * 4, sizeof(JpegHuff), (size_t)JSLOTS * sizeof(JpegDht)};
+        for (int a = 0; a < IMGXF_JPEG_LIST_OPT_AREAS; ++a) {   // (without optimize: empty, at the workspace's end)
+            xhd.opt_off[a] = o;
+            if (opt) o += al256((size_t)n * own[a]);
+        }
+    }
     hd.workspace_bytes = o;
     hd.out_bytes = out;
-    size_t pos = sizeof(imgxf_jpeg_list_header) + (size_t)n * sizeof(imgxf_jpeg_list_frame);
+    size_t pos = hd_bytes + (size_t)n * sizeof(imgxf_jpeg_list_frame);
     for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) {
         if (units[s] > 0x7fffffffu || pos > 0x7fffffffu) return IMGXF_ERR_ARG;
         hd.n_units[s] = (int32_t)units[s];
@@ -1369,21 +1415,21 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
     }
     if (pos > 0x7fffffffu) return IMGXF_ERR_ARG;
     hd.total_bytes = (int32_t)pos;
-    *out_hd = hd;
+    *out_hd = xhd;
     if (!block) return IMGXF_OK;
     if (block_cap < pos) return IMGXF_ERR_WORKSPACE;          // (*out_hd already states the size needed)
-    memcpy(block, &hd, sizeof(hd));
+    memcpy(block, &xhd, hd_bytes);                            // (the default block: the list header alone, which comes first)
     if (n) memcpy(block + hd.frames_off, fr.data(), (size_t)n * sizeof(imgxf_jpeg_list_frame));
     for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) {
         imgxf_jpeg_list_unit* u = (imgxf_jpeg_list_unit*)(block + hd.units_off[s]);
         for (int i = 0; i < n; ++i) {
             const imgxf_jpeg_list_frame& f = fr[(size_t)i];
             if (s == 0) {
-                const int ngx = (f.mw + JM - 1) / JM;
+                const int ngx = list_stage_units(f, 0, lay) / f.mh;
                 for (int my = 0; my < f.mh; ++my)
                     for (int gx = 0; gx < ngx; ++gx) *u++ = {i, gx | (my << 16)};
             } else {
-                const int cnt = list_stage_units(f, s);
+                const int cnt = list_stage_units(f, s, lay);
                 for (int k = 0; k < cnt; ++k) *u++ = {i, k};
             }
         }
@@ -1409,36 +1455,52 @@ static int find_sof0(const uint8_t* h, int len) {
 
 using namespace imgxf;
 
-IMGXF_API int imgxf_jpeg_encode_list_layout_host(const int32_t* sizes, const uint64_t* capacities, int n, void* block, size_t block_cap,
-                                                 size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes) {
+// the class of a list call: a layout the writer has; a grayscale frame is one block per MCU, and a list states it as 1x1
+static int list_class(const imgxf_jpeg_enc_params* p) {
+    const int lay = enc_layout(p);
+    if (lay < 0 || (p->ncomp == 1 && (p->h_samp != 1 || p->v_samp != 1))) return -1;
+    return lay;
+}
+
+// the host half of both list writers (ex == nullptr: the default file's block)
+static int jpeg_list_layout_host(const imgxf_jpeg_enc_params* ex, const int32_t* sizes, const uint64_t* capacities, int n, void* block,
+                                 size_t block_cap, size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes) {
     if (!block_bytes || !workspace_bytes || !out_bytes || (n > 0 && (!sizes || !capacities))) return IMGXF_ERR_NULL;
-    imgxf_jpeg_list_header hd;
+    imgxf_jpeg_list_ex_header hd;
     // the sizes first, so that a block that is too small still learns them
     const auto get = [&](int i, int& h, int& w, uint64_t& cap) { h = sizes[2 * i]; w = sizes[2 * i + 1]; cap = capacities[i]; };
     int rc;
     try {
-        rc = jpeg_list_build(n, get, (u8*)block, block_cap, &hd);
+        rc = jpeg_list_build(n, get, (u8*)block, block_cap, &hd, ex);
     } catch (const std::bad_alloc&) {
         return IMGXF_ERR_WORKSPACE;
     }
     if (rc != IMGXF_OK && rc != IMGXF_ERR_WORKSPACE) return rc;
-    *block_bytes = (size_t)hd.total_bytes;                       // (a block that is too small still learns the sizes)
-    *workspace_bytes = (size_t)hd.workspace_bytes;
-    *out_bytes = (size_t)hd.out_bytes;
+    *block_bytes = (size_t)hd.list.total_bytes;                  // (a block that is too small still learns the sizes)
+    *workspace_bytes = (size_t)hd.list.workspace_bytes;
+    *out_bytes = (size_t)hd.list.out_bytes;
     return rc;
 }
 
-IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_tables* tables,
-                                        const uint8_t* header, int header_bytes, uint8_t* out, size_t out_bytes, uint32_t* sizes,
-                                        void* workspace, size_t workspace_bytes, void* stream) {
-    if (!block_host || !tables || !header) return IMGXF_ERR_NULL;
+// Both list writers.  ex == nullptr: the default file (imgxf_jpeg_encode_list_u8's block and launches).  Else the class *ex
+// (checked by the caller) and its block.  Every record is checked and the whole block rebuilt and compared before a device
+// pointer is looked at; the launches then depend on (layout, optimize) alone.
+static int jpeg_list_encode(const void* block_host, const void* block_dev, const imgxf_jpeg_enc_params* ex, const imgxf_jpeg_tables* tables,
+                            const uint8_t* header, int header_bytes, uint8_t* out, size_t out_bytes, uint32_t* sizes, void* workspace,
+                            size_t workspace_bytes, void* stream) {
     const u8* hb = (const u8*)block_host;
-    imgxf_jpeg_list_header hd;
-    memcpy(&hd, hb, sizeof(hd));
+    const size_t hd_bytes = ex ? sizeof(imgxf_jpeg_list_ex_header) : sizeof(imgxf_jpeg_list_header);
+    const int lay = ex ? enc_layout(ex) : JL420, ncomp = ex ? ex->ncomp : 3;
+    const bool opt = ex && ex->optimize != 0;
+    imgxf_jpeg_list_ex_header xhd;
+    memset(&xhd, 0, sizeof(xhd));
+    memcpy(&xhd, hb, hd_bytes);
+    const imgxf_jpeg_list_header& hd = xhd.list;
     const int n = hd.n_frames;
-    if (n < 0 || n > JLIST_MAX_FRAMES) return IMGXF_ERR_SHAPE;
+    if (n < 0 || n > (opt ? JLIST_MAX_FRAMES_OPT : JLIST_MAX_FRAMES)) return IMGXF_ERR_SHAPE;
     if (header_bytes < 2 || header_bytes > 1024) return IMGXF_ERR_ARG;
-    if (hd.frames_off != (int32_t)sizeof(imgxf_jpeg_list_header) ||
+    if (ex && memcmp(&xhd.params, ex, sizeof(*ex)) != 0) return IMGXF_ERR_ARG;     // a block of another class
+    if (hd.frames_off != (int32_t)hd_bytes ||
         (int64_t)hd.total_bytes < (int64_t)hd.frames_off + (int64_t)n * (int64_t)sizeof(imgxf_jpeg_list_frame))
         return IMGXF_ERR_ARG;
     if (n == 0) return IMGXF_OK;
@@ -1448,21 +1510,21 @@ IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* bloc
     for (int i = 0; i < n; ++i) {
         const imgxf_jpeg_list_frame& f = frames[i];
         if (!f.data) return IMGXF_ERR_NULL;
-        if (f.h < 1 || f.w < 1 || f.h > 32767 || f.w > 32767 || f.row_stride < (int64_t)f.w * 3) return IMGXF_ERR_SHAPE;
+        if (f.h < 1 || f.w < 1 || f.h > 32767 || f.w > 32767 || f.row_stride < (int64_t)f.w * ncomp) return IMGXF_ERR_SHAPE;
         if (f.out_cap < (int64_t)header_bytes + 2) return IMGXF_ERR_ARG;
     }
-    imgxf_jpeg_list_header rhd;
+    imgxf_jpeg_list_ex_header rhd;
     const auto get = [&](int i, int& h, int& w, uint64_t& cap) { h = frames[i].h; w = frames[i].w; cap = (uint64_t)frames[i].out_cap; };
     std::vector<u8> ref;
     try {
         ref.resize((size_t)hd.total_bytes);
-        const int rc = jpeg_list_build(n, get, ref.data(), ref.size(), &rhd);   // one build: the block limit is IMGXF_ERR_SHAPE,
-        if (rc == IMGXF_ERR_WORKSPACE) return IMGXF_ERR_ARG;                  // a block of another size is not this layout
+        const int rc = jpeg_list_build(n, get, ref.data(), ref.size(), &rhd, ex);   // one build: the block limit is IMGXF_ERR_SHAPE,
+        if (rc == IMGXF_ERR_WORKSPACE) return IMGXF_ERR_ARG;                      // a block of another size is not this layout
         IMGXF_CHECK(rc);
     } catch (const std::bad_alloc&) {
         return IMGXF_ERR_WORKSPACE;
     }
-    if (memcmp(&rhd, &hd, sizeof(hd)) != 0) return IMGXF_ERR_ARG;
+    if (memcmp(&rhd, &xhd, hd_bytes) != 0) return IMGXF_ERR_ARG;
     const imgxf_jpeg_list_frame* rf = (const imgxf_jpeg_list_frame*)(ref.data() + hd.frames_off);
     constexpr size_t given = offsetof(imgxf_jpeg_list_frame, h);            // data, row_stride: the caller's
     for (int i = 0; i < n; ++i)
@@ -1474,7 +1536,7 @@ IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* bloc
     if (!workspace || workspace_bytes < hd.workspace_bytes || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
     if (out_bytes < hd.out_bytes || (((uintptr_t)out) & 15)) return IMGXF_ERR_WORKSPACE;
     JpegJob J;
-    IMGXF_CHECK(jpeg_prepare_tables(J, tables, 3, header, header_bytes));
+    IMGXF_CHECK(jpeg_prepare_tables(J, tables, ncomp, header, header_bytes));
     const int sof = find_sof0(header, header_bytes);
     if (sof < 0) return IMGXF_ERR_ARG;
 
@@ -1490,26 +1552,85 @@ IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* bloc
     u32* tot_ff = tot_bits + n;
     u32* ustream = (u32*)(ws + hd.area_off[6]);
     u32* cnt = (u32*)(ws + hd.area_off[7]);
+    u32* sym = (u32*)(ws + xhd.opt_off[0]);                    // (the default block: never touched)
+    JpegHuff* fh = (JpegHuff*)(ws + xhd.opt_off[1]);
+    JpegDht* dht = (JpegDht*)(ws + xhd.opt_off[2]);
     const auto where = [&](int stage, int which) {
         return JpegList{(const imgxf_jpeg_list_frame*)(db + hd.frames_off), (const imgxf_jpeg_list_unit*)(db + hd.units_off[stage]), which, sof};
     };
     const auto grid = [&](int stage) { return dim3((unsigned)hd.n_units[stage]); };
     const JpegGeom g0 = {0, 0, 0, 0, 0};                       // the uniform arguments: unused, the records state them
     const int64_t z = 0;
-    hipLaunchKernelGGL((jpeg_transform_kernel<JpegList, JpegCoefSink>), grid(0), dim3(JT), 0, st, View{}, JpegCoefSink{coef, z, dcs, acb, 0}, 0, 0, 0, J.q,
-                       where(0, 0));
-    hipLaunchKernelGGL((jpeg_lens_kernel<JL420, false, JpegList>), grid(1), dim3(256), 0, st, (const int16_t*)coef, z, (const int16_t*)dcs,
-                       (const uint16_t*)acb, lens, g0, J.hf, (const JpegHuff*)nullptr, where(1, 0));
-    IMGXF_CHECK(scan_rows_list(lens, n, hd.n_units[2], part, tot_bits, where(2, 0), st));
-    hipLaunchKernelGGL(jpeg_zero_kernel<JpegList>, grid(1), dim3(256), 0, st, ustream, z, (const u32*)lens, (const u32*)tot_bits, 0, where(1, 0));
-    hipLaunchKernelGGL((jpeg_emit_kernel<JL420, false, JpegList>), grid(1), dim3(256), 0, st, (const int16_t*)coef, z, (const int16_t*)dcs,
-                       (const u32*)lens, ustream, z, (const u32*)tot_bits, g0, J.hf, (const JpegHuff*)nullptr, where(1, 0));
-    hipLaunchKernelGGL(jpeg_ffcount_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits, cnt, z, 0,
-                       where(3, 0));
-    IMGXF_CHECK(scan_rows_list(cnt, n, hd.n_units[4], part, tot_ff, where(4, 1), st));
-    hipLaunchKernelGGL(jpeg_stuff_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits, (const u32*)cnt, z,
-                       0, (const u32*)tot_ff, out, z, sizes, J.hd, where(3, 0));
-    return launch_status();
+    return with_layout(lay, [&](auto l) -> int {
+        constexpr int L = decltype(l)::value;
+        const JpegCoefSink sink{coef, z, dcs, acb, 0};
+        const int16_t *ccoef = coef, *cdcs = dcs;
+        const JpegHuff* cfh = opt ? fh : nullptr;
+        if constexpr (L == JL420)
+            hipLaunchKernelGGL((jpeg_transform_kernel<JpegList, JpegCoefSink>), grid(0), dim3(JT), 0, st, View{}, sink, 0, 0, 0, J.q, where(0, 0));
+        else
+            hipLaunchKernelGGL((jpeg_transform_ex_kernel<L, JpegCoefSink, JpegList>), grid(0), dim3(JLay<L>::T), 0, st, View{}, sink, 0, 0, J.q,
+                               where(0, 0));
+        if (opt) {
+            if (hipMemsetAsync(sym, 0, (size_t)n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
+            hipLaunchKernelGGL((jpeg_gather_kernel<L, JpegList>), grid(1), dim3(256), 0, st, ccoef, z, cdcs, g0, sym, where(1, 0));
+            hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(L == JLGRAY ? 2u : 4u, (unsigned)n), dim3(256), 0, st, (const u32*)sym, fh, dht);
+            hipLaunchKernelGGL((jpeg_lens_kernel<L, true, JpegList>), grid(1), dim3(256), 0, st, ccoef, z, cdcs, (const uint16_t*)acb, lens, g0,
+                               J.hf, cfh, where(1, 0));
+        } else {
+            hipLaunchKernelGGL((jpeg_lens_kernel<L, false, JpegList>), grid(1), dim3(256), 0, st, ccoef, z, cdcs, (const uint16_t*)acb, lens, g0,
+                               J.hf, cfh, where(1, 0));
+        }
+        IMGXF_CHECK(scan_rows_list(lens, n, hd.n_units[2], part, tot_bits, where(2, 0), st));
+        hipLaunchKernelGGL(jpeg_zero_kernel<JpegList>, grid(1), dim3(256), 0, st, ustream, z, (const u32*)lens, (const u32*)tot_bits, 0, where(1, 0));
+        if (opt)
+            hipLaunchKernelGGL((jpeg_emit_kernel<L, true, JpegList>), grid(1), dim3(256), 0, st, ccoef, z, cdcs, (const u32*)lens, ustream, z,
+                               (const u32*)tot_bits, g0, J.hf, cfh, where(1, 0));
+        else
+            hipLaunchKernelGGL((jpeg_emit_kernel<L, false, JpegList>), grid(1), dim3(256), 0, st, ccoef, z, cdcs, (const u32*)lens, ustream, z,
+                               (const u32*)tot_bits, g0, J.hf, cfh, where(1, 0));
+        hipLaunchKernelGGL(jpeg_ffcount_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits, cnt, z, 0,
+                           where(3, 0));
+        IMGXF_CHECK(scan_rows_list(cnt, n, hd.n_units[4], part, tot_ff, where(4, 1), st));
+        if (opt)
+            hipLaunchKernelGGL(jpeg_stuff_scan_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits,
+                               (const u32*)cnt, z, 0, (const u32*)tot_ff, out, z, (u32*)nullptr, 0, true, sizes, J.hd, (const JpegDht*)dht,
+                               seq_scan_header(ncomp), where(3, 0));
+        else
+            hipLaunchKernelGGL(jpeg_stuff_kernel<JpegList>, grid(3), dim3(256), 0, st, (const u32*)ustream, z, (const u32*)tot_bits,
+                               (const u32*)cnt, z, 0, (const u32*)tot_ff, out, z, sizes, J.hd, where(3, 0));
+        return launch_status();
+    });
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_layout_host(const int32_t* sizes, const uint64_t* capacities, int n, void* block, size_t block_cap,
+                                                 size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes) {
+    return jpeg_list_layout_host(nullptr, sizes, capacities, n, block, block_cap, block_bytes, workspace_bytes, out_bytes);
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_tables* tables,
+                                        const uint8_t* header, int header_bytes, uint8_t* out, size_t out_bytes, uint32_t* sizes,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!block_host || !tables || !header) return IMGXF_ERR_NULL;
+    return jpeg_list_encode(block_host, block_dev, nullptr, tables, header, header_bytes, out, out_bytes, sizes, workspace, workspace_bytes,
+                            stream);
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_ex_layout_host(const imgxf_jpeg_enc_params* params, const int32_t* sizes, const uint64_t* capacities,
+                                                    int n, void* block, size_t block_cap, size_t* block_bytes, size_t* workspace_bytes,
+                                                    size_t* out_bytes) {
+    if (!params) return IMGXF_ERR_NULL;
+    if (list_class(params) < 0) return IMGXF_ERR_ARG;
+    return jpeg_list_layout_host(params, sizes, capacities, n, block, block_cap, block_bytes, workspace_bytes, out_bytes);
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_ex_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_enc_params* params,
+                                           const imgxf_jpeg_tables* tables, const uint8_t* header, int header_bytes, uint8_t* out,
+                                           size_t out_bytes, uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!block_host || !params || !tables || !header) return IMGXF_ERR_NULL;
+    if (list_class(params) < 0) return IMGXF_ERR_ARG;
+    return jpeg_list_encode(block_host, block_dev, params, tables, header, header_bytes, out, out_bytes, sizes, workspace, workspace_bytes,
+                            stream);
 }
 
 IMGXF_API int imgxf_jpeg_roundtrip_workspace_bytes(const imgxf_jpeg_enc_params* params, int n, int h, int w, size_t* bytes) {

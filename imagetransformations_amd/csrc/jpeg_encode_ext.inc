@@ -16,24 +16,44 @@
 // With optimize the lengths come from a walk under the frame's own code lengths (jpeg_lens_kernel<L, true>), emit reads the
 // frame's own tables (jpeg_emit_kernel<L, true>) and the file's DHT segments and SOS are written on the device
 // (jpeg_stuff_scan_kernel with a one-scan header).
+// The transform and the gather kernel take the placement W as jpeg.hip's stages do (JpegUniform: a batch; JpegList: a list
+// of frames of different sizes, imgxf_jpeg_encode_list_ex_u8); the table kernel is per (table, frame) in both.
 
 // One workgroup: rows y0 .. y0+7 (one MCU row), columns x0 .. x0+511 of frame f.  Staging clamps to the last column / row
 // (expand_right_edge, jcprepct.c's bottom replication; v = 1 in every layout here, so input and downsampled rows coincide).
 // Threads 0..63 transform the 64 luminance blocks, the next one or two waves the chrominance blocks (4:4:4: Cb wave, Cr
 // wave; 4:2:2: 32 Cb + 32 Cr in one wave), so the quantiser table stays wave-uniform.
 // The per-block stage is jpeg_forward_block and the SINK (jpeg.hip), as in the 4:2:0 kernel.
-template <int L, class SINK>
-__global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, SINK sink, int mw, int bw, JpegQuant q) {
+// (a list's unit: item = strip | MCU row << 16; geometry, address, stride and the frame's offsets come from its record)
+template <int L, class SINK, class W>
+__global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, SINK sink, int mw, int bw, JpegQuant q, W wh) {
     using Y = JLay<L>;
     constexpr int NC = Y::NC, CW = Y::CW, T = Y::T;
     __shared__ __attribute__((aligned(4))) u8 slen[2][256];
     __shared__ __attribute__((aligned(16))) u8 px[8][JXP * NC];
     __shared__ __attribute__((aligned(16))) u8 yp[NC == 3 ? 8 : 1][JXP + 8];
     __shared__ __attribute__((aligned(16))) u8 cp[NC == 3 ? 2 : 1][NC == 3 ? 8 : 1][CW + 8];
-    const int tid = threadIdx.x, f = blockIdx.z, my = blockIdx.y, x0 = blockIdx.x * JXP, y0 = my * 8;
+    const int tid = threadIdx.x;
+    int f = blockIdx.z, my = blockIdx.y, x0 = blockIdx.x * JXP, item = 0;
+    const u8* base;
+    int64_t coef_o, blk_o;
+    if constexpr (W::LIST) {
+        const imgxf_jpeg_list_frame* fr = jpeg_where(wh, f, item);
+        my = item >> 16;
+        x0 = (item & 0xffff) * JXP;
+        base = (const u8*)fr->data;
+        s.rs = fr->row_stride; s.h = fr->h; s.w = fr->w;
+        mw = fr->mw; bw = fr->bw;
+        coef_o = fr->coef_off;
+        blk_o = fr->blk_off;
+    } else {
+        base = s.p + (int64_t)f * s.fs;
+        coef_o = sink.coef_offset(f);
+        blk_o = sink.blk_offset(f);
+    }
+    const int y0 = my * 8;
     if (SINK::CODES)
         for (int i = tid; i < 128; i += T) ((u32*)slen)[i] = ((const u32*)q.aclen)[i];
-    const u8* base = s.p + (int64_t)f * s.fs;
     const bool fast = (x0 + JXP <= s.w) && (((uintptr_t)base | (uintptr_t)s.rs) & 15) == 0;
     constexpr int CPR = JXP * NC / 16;                         // 16-byte pieces per row
     for (int i = tid; i < 8 * CPR; i += T) {
@@ -95,7 +115,7 @@ __global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, S
         stride = CW + 8;
     }
     const int chroma = __builtin_amdgcn_readfirstlane(tid >= JXP / 8 ? 1 : 0);
-    const JpegBlockAt at = {f, chroma ? k - Y::NY + 1 : 0, bx, my, ((int64_t)my * mw + mx) * Y::B + k, sink.coef_offset(f), sink.blk_offset(f)};
+    const JpegBlockAt at = {f, chroma ? k - Y::NY + 1 : 0, bx, my, ((int64_t)my * mw + mx) * Y::B + k, coef_o, blk_o};
     const typename SINK::Where to = sink.locate(at);
     int d[64];
     jpeg_forward_block(origin, stride, chroma, q, d);
@@ -104,17 +124,27 @@ __global__ __launch_bounds__(JLay<L>::T) void jpeg_transform_ex_kernel(View s, S
 
 // ---- optimize: symbol counts, optimal tables --------------------------------------------------------------------------
 
-template <int L>
+// (a list's unit: a group of 256 blocks of a frame, the lens / emit stage's table; counts go to the frame's own slots)
+template <int L, class W>
 __global__ __launch_bounds__(256) void jpeg_gather_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
-                                                          JpegGeom g, u32* __restrict__ counts) {
+                                                          JpegGeom g, u32* __restrict__ counts, W wh) {
     constexpr int NY = JLay<L>::NY, B = JLay<L>::B, NS = L == JLGRAY ? 2 : 4;
     __shared__ u32 hist[NS][256];
-    const int f = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    int f = blockIdx.y, bx = blockIdx.x;
+    const imgxf_jpeg_list_frame* fr = jpeg_where(wh, f, bx);
+    int64_t blk_o = (int64_t)f * g.nblk;
+    if constexpr (W::LIST) {
+        g = {fr->mw, fr->mh, fr->bw, fr->bh, fr->nblk};
+        coef_fs = 0;
+        coef += fr->coef_off;
+        blk_o = fr->blk_off;
+    }
+    const int j = bx * 256 + threadIdx.x;
     for (int i = threadIdx.x; i < NS * 256; i += 256) (&hist[0][0])[i] = 0;
     __syncthreads();
     if (j < g.nblk) {
         const int mcu = j / B, k = j - mcu * B, my = mcu / g.mw, mx = mcu - my * g.mw;
-        const int16_t* dd = dcs + (int64_t)f * g.nblk;
+        const int16_t* dd = dcs + blk_o;
         bool dummy;
         const int diff = block_dc<L>(dd, g, mcu, mx, my, k, dummy) - block_pred<L>(dd, g, mcu, mx, my, k);
         const int t = k >= NY ? 1 : 0;
@@ -282,7 +312,8 @@ static void launch_transform(const JpegJob& J) {
                            dim3(JT), 0, J.st, J.s, JpegCoefSink{J.coef, J.coef_fs, J.dcs, J.acb, G.nblk}, G.mw, G.bw, G.bh, J.q, JpegUniform{});
     } else {
         const int per = JXP / JLay<L>::MW;                     // MCUs per workgroup strip
-        hipLaunchKernelGGL((jpeg_transform_ex_kernel<L, JpegCoefSink>), dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)J.n),
-                           dim3(JLay<L>::T), 0, J.st, J.s, JpegCoefSink{J.coef, J.coef_fs, J.dcs, J.acb, G.nblk}, G.mw, G.bw, J.q);
+        hipLaunchKernelGGL((jpeg_transform_ex_kernel<L, JpegCoefSink, JpegUniform>),
+                           dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)J.n), dim3(JLay<L>::T), 0, J.st, J.s,
+                           JpegCoefSink{J.coef, J.coef_fs, J.dcs, J.acb, G.nblk}, G.mw, G.bw, J.q, JpegUniform{});
     }
 }

@@ -238,8 +238,9 @@ static int rt_uniform(const imgxf_view* src, const imgxf_view* dst, const imgxf_
     const JpegLayout G = jpeg_layout(lay, false, false, 1, s.h, s.w, 4096);   // the geometry alone (mw, mh, bw, bh)
     if (lay == JLGRAY) {
         const int per = JXP / JLay<JLGRAY>::MW;
-        hipLaunchKernelGGL((jpeg_transform_ex_kernel<JLGRAY, JpegGraySink>), dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)n),
-                           dim3(JLay<JLGRAY>::T), 0, st, s, JpegGraySink{d}, G.mw, G.bw, q);
+        hipLaunchKernelGGL((jpeg_transform_ex_kernel<JLGRAY, JpegGraySink, JpegUniform>),
+                           dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)n), dim3(JLay<JLGRAY>::T), 0, st, s, JpegGraySink{d}, G.mw,
+                           G.bw, q, JpegUniform{});
         return launch_status();
     }
     std::vector<imgxf_jpeg_dec_image> im;
@@ -262,12 +263,14 @@ static int rt_uniform(const imgxf_view* src, const imgxf_view* dst, const imgxf_
                            dim3(JT), 0, st, s, sink, G.mw, G.bw, G.bh, q, JpegUniform{});
     } else if (lay == JL422) {
         const int per = JXP / JLay<JL422>::MW;
-        hipLaunchKernelGGL((jpeg_transform_ex_kernel<JL422, JpegPlaneSink>), dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)n),
-                           dim3(JLay<JL422>::T), 0, st, s, sink, G.mw, G.bw, q);
+        hipLaunchKernelGGL((jpeg_transform_ex_kernel<JL422, JpegPlaneSink, JpegUniform>),
+                           dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)n), dim3(JLay<JL422>::T), 0, st, s, sink, G.mw,
+                           G.bw, q, JpegUniform{});
     } else {
         const int per = JXP / JLay<JL444>::MW;
-        hipLaunchKernelGGL((jpeg_transform_ex_kernel<JL444, JpegPlaneSink>), dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)n),
-                           dim3(JLay<JL444>::T), 0, st, s, sink, G.mw, G.bw, q);
+        hipLaunchKernelGGL((jpeg_transform_ex_kernel<JL444, JpegPlaneSink, JpegUniform>),
+                           dim3((unsigned)((G.mw + per - 1) / per), (unsigned)G.mh, (unsigned)n), dim3(JLay<JL444>::T), 0, st, s, sink, G.mw,
+                           G.bw, q, JpegUniform{});
     }
     IMGXF_CHECK(launch_status());
     return imgxf_jpeg_decode_color(planes, images, im.data(), n, d.p, stream);

@@ -116,16 +116,20 @@ def load_random_resized_crops(paths: Sequence[str], size=224, scale=(0.08, 1.0),
             [p for _, p in items])
 
 
-def resize_files(paths: Sequence[str], out_dir: str, size, interpolation="bicubic", quality: int = 75, workers: int = 8):
+def resize_files(paths: Sequence[str], out_dir: str, size, interpolation="bicubic", quality: int = 75, workers: int = 8, *,
+                 subsampling=-1, optimize: bool = False):
     """Shrink (or enlarge) JPEG files without the pixels ever visiting the host: the files are read on a thread pool and
     decoded on the device as one chunk (`_decode_on_device`: a file the device reader refuses goes to Pillow, one Pillow
     cannot open is skipped with the reference's message), resized by `resize_list.resize_list` in one launch, written
     by `jpeg.encode_list_views` and stored under their own names in `out_dir`.  `size`: an int for torchvision
     `Resize(int)`'s shorter-side rule, or one (width, height) pair for every file.  Each stage is bit-exact, so file k is
-    byte for byte `Image.open(p).convert("RGB").resize(size_k, interpolation).save(..., "JPEG", quality=quality)`.
-    `interpolation` is checked before any file is read.  Returns the output paths of the files kept, in order."""
+    byte for byte `Image.open(p).convert("RGB").resize(size_k, interpolation).save(..., "JPEG", quality=quality,
+    subsampling=subsampling, optimize=optimize)` (Pillow's spellings; the defaults are Pillow's default file), every class
+    in one list call of the writer.  `interpolation` and `subsampling` are checked before any file is read.  Returns the
+    output paths of the files kept, in order."""
     from . import jpeg, resize_list, tensor_maps
     filt = tensor_maps.resample_filter(interpolation)
+    jpeg.sampling(subsampling, 3)
     os.makedirs(out_dir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=workers) as pool:
         items = _decode_on_device(list(pool.map(_read, paths)))
@@ -134,7 +138,8 @@ def resize_files(paths: Sequence[str], out_dir: str, size, interpolation="bicubi
             sizes = resize_list.shorter_side_sizes([(t.shape[0], t.shape[1]) for t in frames], size)
         else:
             sizes = [tuple(size)] * len(frames)
-        files = jpeg.encode_list_views(resize_list.resize_list(frames, sizes, filt), quality)
+        files = jpeg.encode_list_views(resize_list.resize_list(frames, sizes, filt), quality, subsampling=subsampling,
+                                       optimize=optimize)
         outs = [os.path.join(out_dir, os.path.basename(p)) for _, p in items]
         list(pool.map(_write, files, outs))
     return outs

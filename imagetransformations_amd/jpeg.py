@@ -239,21 +239,26 @@ _LIST_FRAME = np.dtype([(name, np.dtype(ct)) for name, ct in F.JpegListFrame._fi
 assert _LIST_FRAME.itemsize == ctypes.sizeof(F.JpegListFrame)
 
 
-def list_layout(sizes: Sequence, capacities: Sequence[int]):
+def list_layout(sizes: Sequence, capacities: Sequence[int], params: "F.JpegEncParams | None" = None):
     """imgxf_jpeg_encode_list_layout_host for frames of `sizes` [(h, w)] with `capacities` bytes per file → (block: uint8
     array, header: F.JpegListHeader copy, frames: structured view INTO the block (data and row_stride are the caller's
-    to fill)).  Host only."""
+    to fill)).  With `params` (one class: ncomp, sampling, optimize) imgxf_jpeg_encode_list_ex_layout_host, and the header
+    is a F.JpegListExHeader copy (the same fields under `.list`).  Host only."""
     n = len(sizes)
     hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
     caps = np.ascontiguousarray(np.asarray(capacities, dtype=np.uint64).reshape(n))
     nb, nw, no = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    F.call("imgxf_jpeg_encode_list_layout_host", hw.ctypes.data, caps.ctypes.data, n, None, 0, ctypes.byref(nb), ctypes.byref(nw),
-           ctypes.byref(no))
+    name, first = "imgxf_jpeg_encode_list_layout_host", ()
+    if params is not None:
+        name, first = "imgxf_jpeg_encode_list_ex_layout_host", (ctypes.addressof(params),)
+    F.call(name, *first, hw.ctypes.data, caps.ctypes.data, n, None, 0, ctypes.byref(nb), ctypes.byref(nw), ctypes.byref(no))
     block = np.zeros((nb.value,), dtype=np.uint8)
-    F.call("imgxf_jpeg_encode_list_layout_host", hw.ctypes.data, caps.ctypes.data, n, block.ctypes.data, block.nbytes, ctypes.byref(nb),
-           ctypes.byref(nw), ctypes.byref(no))
-    hd = F.JpegListHeader.from_buffer_copy(block[:ctypes.sizeof(F.JpegListHeader)].tobytes())
-    frames = block[hd.frames_off:hd.frames_off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
+    F.call(name, *first, hw.ctypes.data, caps.ctypes.data, n, block.ctypes.data, block.nbytes, ctypes.byref(nb), ctypes.byref(nw),
+           ctypes.byref(no))
+    kind = F.JpegListHeader if params is None else F.JpegListExHeader
+    hd = kind.from_buffer_copy(block[:ctypes.sizeof(kind)].tobytes())
+    off = (hd if params is None else hd.list).frames_off
+    frames = block[off:off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
     return block, hd, frames
 
 
@@ -273,28 +278,40 @@ def _list_frames(frames) -> list:
     return frames
 
 
-def _encode_list_device(frames: list, caps: list, quality: int):
-    """One imgxf_jpeg_encode_list_u8 call: → (out: uint8 device buffer, out_off: file f starts at out[out_off[f]], sizes:
-    list, 0xFFFFFFFF where file f exceeds caps[f])."""
+_SPELLING = {(1, 1): 0, (2, 1): 1, (2, 2): 2}      # luma sampling -> one `subsampling` spelling of it
+_LIST_MAX_OPT = 65535                # frames per imgxf_jpeg_encode_list_ex_u8 call with optimize (its table stage's grid)
+
+
+def _encode_list_device(frames: list, caps: list, quality: int, cls=None):
+    """One list call: → (out: uint8 device buffer, out_off: file f starts at out[out_off[f]], sizes: list, 0xFFFFFFFF where
+    file f exceeds caps[f]).  cls None: the default file, imgxf_jpeg_encode_list_u8.  Else one class (ncomp, hv, optimize)
+    of [H, W, 3] or [H, W] frames: imgxf_jpeg_encode_list_ex_u8 (a grayscale class is 1x1 to the C side; hv reaches only
+    the SOF byte of the header, as in `encode`)."""
     dev = frames[0].device
-    block, hd, rec = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps)
+    nc = 3 if cls is None else cls[0]
+    params = None if cls is None else F.JpegEncParams(nc, *((1, 1) if nc == 1 else cls[1]), int(cls[2]))
+    block, hd, rec = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps, params)
+    lhd = hd if cls is None else hd.list
     kept = []                                        # (a copy made here must outlive the launch)
     for i, t in enumerate(frames):
-        if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 3) or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+        h, w = t.shape[0], t.shape[1]
+        if (nc == 3 and t.stride(2) != 1) or (w > 1 and t.stride(1) != nc) or (h > 1 and t.stride(0) < nc * w):
             t = t.contiguous()
             kept.append(t)
         rec["data"][i] = t.data_ptr()
-        rec["row_stride"][i] = t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1]
+        rec["row_stride"][i] = t.stride(0) if h > 1 else nc * w
     staged = torch.empty((block.nbytes,), dtype=torch.uint8, pin_memory=True)
     staged.numpy()[:] = block
     block_dev = staged.to(dev, non_blocking=True)
-    out = torch.empty((hd.out_bytes,), dtype=torch.uint8, device=dev)
+    out = torch.empty((lhd.out_bytes,), dtype=torch.uint8, device=dev)
     sizes = torch.zeros((len(frames),), dtype=torch.int32, device=dev)
-    ws = torch.empty((hd.workspace_bytes,), dtype=torch.uint8, device=dev)
-    hdr = header(1, 1, quality)                      # the device writes each frame's height and width
+    ws = torch.empty((lhd.workspace_bytes,), dtype=torch.uint8, device=dev)
+    # the device writes each frame's height and width
+    hdr = header(1, 1, quality) if cls is None else header(1, 1, quality, ncomp=nc, subsampling=_SPELLING[cls[1]], optimize=cls[2])
+    name, first = ("imgxf_jpeg_encode_list_u8", ()) if cls is None else ("imgxf_jpeg_encode_list_ex_u8", (ctypes.addressof(params),))
     with torch.cuda.device(dev):
-        F.call("imgxf_jpeg_encode_list_u8", block.ctypes.data, block_dev.data_ptr(), ctypes.addressof(tables(quality)), hdr, len(hdr),
-               out.data_ptr(), hd.out_bytes, sizes.data_ptr(), ws.data_ptr(), hd.workspace_bytes,
+        F.call(name, block.ctypes.data, block_dev.data_ptr(), *first, ctypes.addressof(tables(quality)), hdr, len(hdr),
+               out.data_ptr(), lhd.out_bytes, sizes.data_ptr(), ws.data_ptr(), lhd.workspace_bytes,
                torch.cuda.current_stream(dev).cuda_stream)
     lens = (sizes.to(torch.int64) & 0xFFFFFFFF).cpu().tolist()     # (synchronises: staged, kept and ws are done with)
     return out, rec["out_off"].tolist(), lens
@@ -311,55 +328,65 @@ def encode_list_views(frames: Sequence[torch.Tensor], quality: int = 75, *, subs
                       progressive: bool = False) -> List[memoryview]:
     """`encode_list` without the last host copy (as `encode_views`): one memoryview per file into pinned staging memory.
 
-    frames: uint8 device tensors [H_i, W_i, 3], any row stride and byte offset (views are read in place while a pixel is
-    three consecutive bytes).  The default file (RGB, 4:2:0, Annex-K tables) of the whole list is ONE
-    imgxf_jpeg_encode_list_u8 call — a number of launches that does not depend on the frames or their sizes — with
-    `_capacities`' first-try capacity per frame; the frames that come back over capacity, and only those, are encoded
-    again in a second call with their retry capacity.  The files leave the device as one gathered copy.
-    Non-default files (`subsampling`, `optimize`, `progressive`, grayscale [H, W] frames) have no list kernels: those
-    frames are grouped by shape and each group goes through `encode_views` — the same bytes, one call per shape."""
+    frames: uint8 device tensors [H_i, W_i, 3] (RGB) or [H_i, W_i] (grayscale), any row stride and byte offset (views are
+    read in place while a pixel's bytes and a row's pixels are consecutive).  Every sequential file — any `subsampling`,
+    with or without `optimize` — of the whole list is ONE list call per class: imgxf_jpeg_encode_list_u8 for the default
+    file (RGB, 4:2:0, Annex-K tables), imgxf_jpeg_encode_list_ex_u8 for every other (ncomp, sampling, optimize), so a list
+    that mixes grayscale and RGB frames makes two.  A call is a number of launches that does not depend on the frames or
+    their sizes, with `_capacities`' first-try capacity per frame; the frames that come back over capacity, and only
+    those, are encoded again in a second call with their retry capacity.  All pieces of all classes leave the device as
+    one gathered copy, and the files are returned in input order.
+    `progressive=True` has no list kernels (ten scans with per-scan tables): those frames are grouped by shape and each
+    group goes through `encode_views` — the same bytes, one call per shape."""
     frames = _list_frames(frames)
     if not frames:
         return []
-    sampling(subsampling, 3)                         # (refuses a bad spelling before any work)
+    hv3 = sampling(subsampling, 3)                   # (refuses a bad spelling before any work)
     optimize, progressive = bool(optimize), bool(progressive)
     result: list = [None] * len(frames)
-    plain = sampling(subsampling, 3) == (2, 2) and not optimize and not progressive
-    default, groups = [], {}
-    for i, t in enumerate(frames):
-        if plain and t.dim() == 3:
-            default.append(i)
-        else:
+    if progressive:
+        groups: dict = {}
+        for i, t in enumerate(frames):
             groups.setdefault(tuple(t.shape), []).append(i)
-    for idx in groups.values():
-        views = encode_views(torch.stack([frames[i] for i in idx]), quality, subsampling=subsampling, optimize=optimize,
-                             progressive=progressive)
-        for i, v in zip(idx, views):
-            result[i] = v
-    if default:
-        todo = default
-        pieces: dict = {}                            # frame -> device view of exactly its file
-        for attempt in (0, 1):
-            caps = [_capacities(frames[i].shape[0], frames[i].shape[1], 3, (2, 2))[attempt] for i in todo]
-            out, offs, lens = _encode_list_device([frames[i] for i in todo], caps, quality)
-            for i, o, v in zip(todo, offs, lens):
-                if v != 0xFFFFFFFF:
-                    pieces[i] = out[o:o + v]
-            todo = [i for i, v in zip(todo, lens) if v == 0xFFFFFFFF]
-            if not todo:
-                break
-        if todo:
-            raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds the largest baseline stream", "jpeg.encode_list")
-        starts = [0]
-        for i in default:
-            starts.append(starts[-1] + pieces[i].numel())
-        packed = torch.cat([pieces[i] for i in default])          # one gather, one D2H (as encode_views)
-        staged = torch.empty((starts[-1],), dtype=torch.uint8, pin_memory=True)
-        staged.copy_(packed, non_blocking=True)
-        torch.cuda.current_stream(frames[0].device).synchronize()
-        host = memoryview(staged.numpy())
-        for k, i in enumerate(default):
-            result[i] = host[starts[k]:starts[k + 1]]
+        for idx in groups.values():
+            views = encode_views(torch.stack([frames[i] for i in idx]), quality, subsampling=subsampling, optimize=optimize,
+                                 progressive=True)
+            for i, v in zip(idx, views):
+                result[i] = v
+        return result
+    classes: dict = {}                               # None: the default file; else (ncomp, hv, optimize)
+    for i, t in enumerate(frames):
+        nc = 3 if t.dim() == 3 else 1
+        hv = hv3 if nc == 3 else sampling(subsampling, 1)
+        classes.setdefault(None if nc == 3 and hv == (2, 2) and not optimize else (nc, hv, optimize), []).append(i)
+    pieces: dict = {}                                # frame -> device view of exactly its file
+    for cls, members in classes.items():
+        nc, hv = (3, (2, 2)) if cls is None else cls[:2]
+        step = _LIST_MAX_OPT if optimize else len(members)
+        for lo in range(0, len(members), step):
+            todo = members[lo:lo + step]
+            for attempt in (0, 1):
+                caps = [_capacities(frames[i].shape[0], frames[i].shape[1], nc, hv)[attempt] for i in todo]
+                out, offs, lens = _encode_list_device([frames[i] for i in todo], caps, quality, cls)
+                _check_overflow(lens)
+                for i, o, v in zip(todo, offs, lens):
+                    if v != 0xFFFFFFFF:
+                        pieces[i] = out[o:o + v]
+                todo = [i for i, v in zip(todo, lens) if v == 0xFFFFFFFF]
+                if not todo:
+                    break
+            if todo:
+                raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds the largest baseline stream", "jpeg.encode_list")
+    starts = [0]
+    for i in range(len(frames)):
+        starts.append(starts[-1] + pieces[i].numel())
+    packed = torch.cat([pieces[i] for i in range(len(frames))])   # one gather, one D2H (as encode_views)
+    staged = torch.empty((starts[-1],), dtype=torch.uint8, pin_memory=True)
+    staged.copy_(packed, non_blocking=True)
+    torch.cuda.current_stream(frames[0].device).synchronize()
+    host = memoryview(staged.numpy())
+    for i in range(len(frames)):
+        result[i] = host[starts[i]:starts[i + 1]]
     return result
 
 

@@ -580,6 +580,41 @@ int imgxf_jpeg_encode_ex_u8(const imgxf_view* src, const imgxf_jpeg_enc_params* 
                             const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
                             uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The list writer for every sequential class of imgxf_jpeg_encode_ex_u8: one call writes a LIST of frames of different
+ * sizes that share one class (ncomp, sampling, optimize) — 4:4:4, 4:2:2, 4:2:0 or grayscale, with the call's tables or each
+ * frame's own optimal ones — in a number of launches that depends on the class alone, never on the list.  A grayscale
+ * class is stated as 1x1 (h_samp / v_samp reach only the SOF the caller writes).  The block is
+ *     imgxf_jpeg_list_ex_header | imgxf_jpeg_list_frame[n] | imgxf_jpeg_list_unit tables (5)
+ * with the records and unit tables of imgxf_jpeg_encode_list_u8, laid out for the class: MCUs of 8x8 (4:4:4, grayscale),
+ * 16x8 (4:2:2) or 16x16 pixels and 3, 1, 4 or 6 blocks; row_stride >= ncomp * w; the transform units (stage 0) are
+ * 16x256-pixel strips at 4:2:0 and one MCU row of 512 pixels in the other layouts (item = strip | MCU row << 16).  With
+ * optimize three more workspace areas, indexed by the frame, hold what imgxf_jpeg_optimal_tables describes: symbol counts
+ * uint32 [n][4][256] (zeroed by the call, in stream order), code words uint32 [n][544], DHT records [n][4] of 276 bytes;
+ * without it they are empty, at the workspace's end.  For {3, 2, 2, 0} frames, units and sizes are those of
+ * imgxf_jpeg_encode_list_layout_host and the files those of imgxf_jpeg_encode_list_u8. */
+#define IMGXF_JPEG_LIST_OPT_AREAS 3
+typedef struct imgxf_jpeg_list_ex_header {
+    imgxf_jpeg_list_header list;                             /* frames_off = sizeof(imgxf_jpeg_list_ex_header) */
+    imgxf_jpeg_enc_params  params;                           /* the class the block was laid out for */
+    uint64_t opt_off[IMGXF_JPEG_LIST_OPT_AREAS];             /* byte offsets into the workspace, 256-byte aligned */
+} imgxf_jpeg_list_ex_header;
+/* HOST half, as imgxf_jpeg_encode_list_layout_host.  The workspace never exceeds the sum over the frames of
+ * imgxf_jpeg_workspace_bytes_ex(params, 1, h, w, capacity).  Errors as there, plus IMGXF_ERR_ARG for params outside the
+ * classes above (ncomp, sampling, optimize; grayscale not 1x1) and IMGXF_ERR_SHAPE for more than 65535 frames with optimize
+ * (the table stage runs one workgroup per table and frame). */
+int imgxf_jpeg_encode_list_ex_layout_host(const imgxf_jpeg_enc_params* params, const int32_t* sizes, const uint64_t* capacities,
+                                          int n, void* block, size_t block_cap, size_t* block_bytes, size_t* workspace_bytes,
+                                          size_t* out_bytes);
+/* The launches, as imgxf_jpeg_encode_list_u8: `header` is SOI .. SOS for the class (any size in SOF0) or, with optimize,
+ * SOI .. SOF0 — the device then writes, into the frame's slot, that prefix with the frame's own height and width, the
+ * frame's DHT segments and SOS, its stuffed data and EOI.  sizes[f] as imgxf_jpeg_encode_ex_u8: the file's length,
+ * 0xFFFFFFFF when it does not fit out_cap (the slot is then untouched past that bound), 0xFFFFFFFE when an optimal table
+ * would need a code over 32 bits.  The same checks in the same order as imgxf_jpeg_encode_list_u8, all of the block's
+ * before a device pointer is looked at; a block laid out for other params -> IMGXF_ERR_ARG. */
+int imgxf_jpeg_encode_list_ex_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_enc_params* params,
+                                 const imgxf_jpeg_tables* tables, const uint8_t* header, int header_bytes, uint8_t* out,
+                                 size_t out_bytes, uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Progressive files: Pillow's `save(fp, "JPEG", progressive=True, quality=q, subsampling=s)` for the frames and layouts of
  * imgxf_jpeg_encode_ex_u8, bit-identical to libjpeg-turbo.  The coefficients are the sequential writer's; the file is
  * jcparam.c jpeg_simple_progression (colour, 10 scans: Y Cb Cr DC 0-0 Al 1; Y 1-5 Al 2; Cr, Cb 1-63 Al 1; Y 6-63 Al 2;

@@ -4,6 +4,7 @@ OPTIMIZE=1, PROGRESSIVE=1, GRAY=1 (the frames converted to "L") — Pillow runs 
 the threaded Pillow comparison.
 The progressive rows: PROGRESSIVE=1 with SUBSAMPLING=2 / 0 / GRAY=1, for 16 frames of 4K and 256 of 375 500.
 List mode (`jpeg.encode_list_views` against the per-shape route): python tools/bench_jpeg.py list [frames] [mixed|uniform] [a|b]
+[--subsampling S] [--optimize] [--gray]
 Round-trip mode (JPEG compression without a file against encode + decode): python tools/bench_jpeg.py roundtrip [frames]
 [mixed|uniform] [fused|compose]"""
 import io, os, sys, time
@@ -77,18 +78,29 @@ def roundtrip_mode(argv):
 
 
 def list_mode(argv):
-    """`bench_jpeg.py list [frames] [mixed|uniform] [a|b]`: the list writer against the per-shape route on photo-like frames
-    at quality 75.  mixed: the ImageNet-like size mix of tools/bench_preprocess_list.py workload B; uniform: every frame
+    """`bench_jpeg.py list [frames] [mixed|uniform] [a|b] [--subsampling S] [--optimize] [--gray]`: the list writer against
+    the per-shape route on photo-like frames at quality 75, for the default file or the class the options name (Pillow's
+    `subsampling` spellings; --gray: the frames' green planes as [H, W] frames).  mixed: the ImageNet-like size mix of tools/bench_preprocess_list.py workload B; uniform: every frame
     375 x 500.  Route a: group by shape, torch.cat, `encode_views` per shape; route b: one `encode_list_views`.  The two
     alternate, four runs each after a warm-up, a host clock around calls that end in a synchronise; files compared.
     With a third argument only that route runs, once after a warm-up, preceded by "TRACE": for
     `rocprofv3 --kernel-trace --stats`, whose launch counts are then (warm-up + 1) x one call's.  Exits non-zero when
     the files differ."""
     from imagetransformations_amd import _ffi as F
+    argv, opts, gray = list(argv), {}, False
+    if "--optimize" in argv:
+        argv.remove("--optimize"); opts["optimize"] = True
+    if "--gray" in argv:
+        argv.remove("--gray"); gray = True
+    if "--subsampling" in argv:
+        k = argv.index("--subsampling"); v = argv[k + 1]; del argv[k:k + 2]
+        opts["subsampling"] = v if ":" in v else int(v)
     n = int(argv[0]) if argv else 1024
     mix = argv[1] if len(argv) > 1 else "mixed"
     only = argv[2] if len(argv) > 2 else None
     sizes, frames = photo_frames(n, mix)
+    if gray:
+        frames = [t[..., 1].contiguous() for t in frames]
     groups = {}
     for i, t in enumerate(frames):
         groups.setdefault(tuple(t.shape), []).append(i)
@@ -96,12 +108,12 @@ def list_mode(argv):
     def route_a():
         out = [None] * n
         for idx in groups.values():
-            for i, v in zip(idx, jpeg.encode_views(torch.cat([frames[i][None] for i in idx]))):
+            for i, v in zip(idx, jpeg.encode_views(torch.cat([frames[i][None] for i in idx]), **opts)):
                 out[i] = v
         return out
 
     def route_b():
-        return jpeg.encode_list_views(frames)
+        return jpeg.encode_list_views(frames, **opts)
 
     seen, real = {}, F.call
 
@@ -130,7 +142,8 @@ def list_mode(argv):
             t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
     med = lambda v: sorted(v)[len(v) // 2 - 1] / 2 + sorted(v)[len(v) // 2] / 2
     px = sum(h * w for h, w in sizes)
-    print(f"list mode, {mix}: {n} photo-like frames, {len(groups)} distinct sizes, {px / 1e6:.1f} Mpix, quality 75, {nbytes / px:.3f} bytes/px; "
+    print(f"list mode, {mix}{', gray' if gray else ''} {opts or ''}: {n} photo-like frames, {len(groups)} distinct sizes, "
+          f"{px / 1e6:.1f} Mpix, quality 75, {nbytes / px:.3f} bytes/px; "
           f"files equal: {same}")
     for name, ts, calls in (("a: per shape, torch.cat + encode_views", ta, ca), ("b: encode_list_views", tb, cb)):
         writer = sum(v for k, v in calls.items() if k.startswith("imgxf_jpeg_encode") and k.endswith("_u8"))
