@@ -368,21 +368,22 @@ static inline unsigned grid_for(int64_t total) {
     return (unsigned)(blocks > 16384 ? 16384 : (blocks < 1 ? 1 : blocks));
 }
 
+static int launch_h_lds(const imgxf_lanczos_plan* p, const View& s, const View& d, hipStream_t st) {
+    const int rpb = 32;
+    dim3 grid((unsigned)((d.w + 1023) / 1024), (unsigned)((d.h + rpb - 1) / rpb), (unsigned)d.n);
+    const int bufbytes = (p->hspan + 15) & ~15;
+    const size_t lds = 2 * (size_t)bufbytes;
+    switch (p->kpx) {
+        case 8: hipLaunchKernelGGL((resample_h_lds_kernel<8>), grid, dim3(256), lds, st, s, d, p->d_start_x, p->d_pk_x, rpb, bufbytes); break;
+        case 12: hipLaunchKernelGGL((resample_h_lds_kernel<12>), grid, dim3(256), lds, st, s, d, p->d_start_x, p->d_pk_x, rpb, bufbytes); break;
+        default: hipLaunchKernelGGL((resample_h_lds_kernel<16>), grid, dim3(256), lds, st, s, d, p->d_start_x, p->d_pk_x, rpb, bufbytes); break;
+    }
+    return launch_status();
+}
+
 static int launch_h_fast(const imgxf_lanczos_plan* p, const View& s, const View& d, hipStream_t st) {
     const int rpb = 32;
     dim3 grid((unsigned)((d.w + 1023) / 1024), (unsigned)((d.h + rpb - 1) / rpb), (unsigned)d.n);
-    const bool no_lds = knob_set(K_LANCZOS_NO_LDS);
-    const bool aligned = ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs) & 15) == 0 && (s.w * 3) % 16 == 0;
-    if (!no_lds && aligned && p->hspan > 0 && p->hspan <= 8192) {
-        const int bufbytes = (p->hspan + 15) & ~15;
-        const size_t lds = 2 * (size_t)bufbytes;
-        switch (p->kpx) {
-            case 8: hipLaunchKernelGGL((resample_h_lds_kernel<8>), grid, dim3(256), lds, st, s, d, p->d_start_x, p->d_pk_x, rpb, bufbytes); break;
-            case 12: hipLaunchKernelGGL((resample_h_lds_kernel<12>), grid, dim3(256), lds, st, s, d, p->d_start_x, p->d_pk_x, rpb, bufbytes); break;
-            default: hipLaunchKernelGGL((resample_h_lds_kernel<16>), grid, dim3(256), lds, st, s, d, p->d_start_x, p->d_pk_x, rpb, bufbytes); break;
-        }
-        return launch_status();
-    }
     switch (p->kpx) {
         case 8: hipLaunchKernelGGL((resample_h_fast_kernel<8>), grid, dim3(256), 0, st, s, d, p->d_start_x, p->d_pk_x, rpb); break;
         case 12: hipLaunchKernelGGL((resample_h_fast_kernel<12>), grid, dim3(256), 0, st, s, d, p->d_start_x, p->d_pk_x, rpb); break;
@@ -391,18 +392,13 @@ static int launch_h_fast(const imgxf_lanczos_plan* p, const View& s, const View&
     return launch_status();
 }
 
-static bool v_fast_ok(const imgxf_lanczos_plan* p, const View& s, const View& d) {
-    return p->kpy > 0 && (d.rowbytes() % 16) == 0 &&
-           ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0;
+static int launch_v4(const imgxf_lanczos_plan* p, const View& s, const View& d, hipStream_t st) {
+    dim3 grid4((unsigned)(((d.rowbytes() >> 4) + 255) / 256), (unsigned)((d.h + 3) / 4), (unsigned)d.n);
+    hipLaunchKernelGGL((resample_v4_kernel<12>), grid4, dim3(256), 0, st, s, d, p->d_start4_y, p->d_pk4_y);
+    return launch_status();
 }
 
 static int launch_v_fast(const imgxf_lanczos_plan* p, const View& s, const View& d, hipStream_t st) {
-    static const bool no_v4 = knob_set(K_LANCZOS_NO_V4);
-    if (p->ku4 == 12 && !no_v4) {
-        dim3 grid4((unsigned)(((d.rowbytes() >> 4) + 255) / 256), (unsigned)((d.h + 3) / 4), (unsigned)d.n);
-        hipLaunchKernelGGL((resample_v4_kernel<12>), grid4, dim3(256), 0, st, s, d, p->d_start4_y, p->d_pk4_y);
-        return launch_status();
-    }
     dim3 grid((unsigned)(((d.rowbytes() >> 4) + 255) / 256), (unsigned)d.h, (unsigned)d.n);
     hipLaunchKernelGGL(resample_v_fast_kernel, grid, dim3(256), 0, st, s, d, p->d_start_y, p->d_pk_y, p->kpy);
     return launch_status();
@@ -453,6 +449,50 @@ static int launch_h(const View& s, const View& d, const int* b, const int* k, in
         default: return IMGXF_ERR_UNSUPPORTED;
     }
     return launch_status();
+}
+
+// Which kernels one call runs: THE decision, shared by the launch (run_resample), the workspace queries and
+// imgxf_resample_plan_route, so that none of them can disagree.  Every knob is read here, at call time.
+struct ResampleRoute {
+    bool fused;              // resample_mfma_kernel does both passes, no intermediate
+    int h, hk;               // IMGXF_ROUTE_H_*; KP of the fast / LDS kernel, the channel count of the generic one
+    int v, vk;               // IMGXF_ROUTE_V_*; KP of the fast kernel, KU of the 4-row one, 0 for the generic one
+};
+
+// `tmp`: the H -> V intermediate the call would use (only its alignment matters, and only when both passes run)
+static ResampleRoute resample_route(const imgxf_lanczos_plan* p, const View& s, const View& d, const uint8_t* tmp) {
+    ResampleRoute r = {false, IMGXF_ROUTE_H_NONE, 0, IMGXF_ROUTE_V_NONE, 0};
+    const bool both = p->need_h && p->need_v;
+    const bool slow = knob_set(K_LANCZOS_SLOW);
+    // the knobs that pick a variant of the two-pass kernels imply the two-pass path
+    if (both && !slow && !knob_set(K_RESAMPLE_NO_MFMA) && !knob_set(K_LANCZOS_NO_LDS) && !knob_set(K_LANCZOS_NO_V4) &&
+        rs_mf_ok(p, s, d)) {
+        r.fused = true;
+        return r;
+    }
+    if (p->need_h) {
+        if (p->kpx && !slow) {
+            // the H pass reads the source rows the window's vertical taps touch: they start at row ry0
+            const uintptr_t sp = (uintptr_t)(s.p + (both ? (int64_t)p->ry0 * s.rs : 0));
+            const bool aligned = ((sp | (uintptr_t)s.rs | (uintptr_t)s.fs) & 15) == 0 && (s.w * 3) % 16 == 0;
+            const bool lds = !knob_set(K_LANCZOS_NO_LDS) && aligned && p->hspan > 0 && p->hspan <= 8192;
+            r.h = lds ? IMGXF_ROUTE_H_LDS : IMGXF_ROUTE_H_FAST;
+            r.hk = p->kpx;
+        } else {
+            r.h = IMGXF_ROUTE_H_GENERIC;
+            r.hk = p->c;
+        }
+    }
+    if (p->need_v) {
+        // the V pass reads the intermediate (rows of out_w * c bytes, packed) or, alone, the source
+        const uintptr_t mid = both ? (uintptr_t)tmp : ((uintptr_t)s.p | (uintptr_t)s.rs | (uintptr_t)s.fs);
+        const bool fast = !slow && p->kpy > 0 && (d.rowbytes() % 16) == 0 &&
+                          ((mid | (uintptr_t)d.p | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0;
+        if (fast && p->ku4 == 12 && !knob_set(K_LANCZOS_NO_V4)) { r.v = IMGXF_ROUTE_V_V4; r.vk = p->ku4; }
+        else if (fast) { r.v = IMGXF_ROUTE_V_FAST; r.vk = p->kpy; }
+        else r.v = IMGXF_ROUTE_V_GENERIC;
+    }
+    return r;
 }
 
 } // namespace imgxf
@@ -653,13 +693,24 @@ IMGXF_API int imgxf_resize_lanczos_u8(const imgxf_lanczos_plan* p, const imgxf_v
     return run_resample(p, src, dst, p->d_tmp, stream);
 }
 
-// does this call run the fused matrix-core kernel (no intermediate)?
+// does this call run the fused matrix-core kernel (no intermediate)?  A 16-byte aligned intermediate stands in for
+// the caller's: it decides between vertical kernels only, never whether the call is fused.
 static bool resample_runs_fused(const imgxf_lanczos_plan* p, const imgxf_view* src, const imgxf_view* dst) {
-    if (!p->need_h || !p->need_v || !src || !dst) return false;
-    // the knobs that pick a variant of the two-pass kernels imply the two-pass path
-    if (knob_set(K_LANCZOS_SLOW) || knob_set(K_RESAMPLE_NO_MFMA) || knob_set(K_LANCZOS_NO_LDS) || knob_set(K_LANCZOS_NO_V4))
-        return false;
-    return rs_mf_ok(p, make_view(src), make_view(dst));
+    if (!src || !dst) return false;
+    return resample_route(p, make_view(src), make_view(dst), nullptr).fused;
+}
+
+IMGXF_API int imgxf_resample_plan_route(const imgxf_lanczos_plan* p, const imgxf_view* src, const imgxf_view* dst,
+                                        int route[5]) {
+    if (!p || !src || !dst || !route) return IMGXF_ERR_NULL;
+    IMGXF_CHECK(check_view(src));
+    IMGXF_CHECK(check_view(dst));
+    if (src->n != dst->n || src->c != p->c || dst->c != p->c) return IMGXF_ERR_SHAPE;
+    if (src->h != p->in_h || src->w != p->in_w || dst->h != p->out_h || dst->w != p->out_w)
+        return IMGXF_ERR_SHAPE;
+    const ResampleRoute r = resample_route(p, make_view(src), make_view(dst), nullptr);
+    route[0] = r.fused ? p->mf_nkh : 0; route[1] = r.h; route[2] = r.hk; route[3] = r.v; route[4] = r.vk;
+    return IMGXF_OK;
 }
 
 IMGXF_API int imgxf_resample_workspace_bytes_for(const imgxf_lanczos_plan* p, const imgxf_view* src,
@@ -699,13 +750,16 @@ static int run_resample(const imgxf_lanczos_plan* p, const imgxf_view* src, cons
         }
         return IMGXF_OK;
     }
-    const bool slow = knob_set(K_LANCZOS_SLOW);
+    const ResampleRoute r = resample_route(p, s, d, tmp);
     auto run_h = [&](const View& a, const View& b) {
-        if (p->kpx && !slow) return launch_h_fast(p, a, b, st);
-        return launch_h(a, b, p->d_bounds_x, p->d_kk_x, p->ksx, st);
+        switch (r.h) {
+            case IMGXF_ROUTE_H_LDS: return launch_h_lds(p, a, b, st);
+            case IMGXF_ROUTE_H_FAST: return launch_h_fast(p, a, b, st);
+            default: return launch_h(a, b, p->d_bounds_x, p->d_kk_x, p->ksx, st);
+        }
     };
     if (p->need_h && !p->need_v) return run_h(s, d);
-    if (resample_runs_fused(p, src, dst)) return launch_rs_mf(p, s, d, st);
+    if (r.fused) return launch_rs_mf(p, s, d, st);
     View mid = s;
     if (p->need_h) {
         View sub = s;                                  // the source rows the window's vertical taps touch
@@ -715,7 +769,8 @@ static int run_resample(const imgxf_lanczos_plan* p, const imgxf_view* src, cons
         mid.rs = (int64_t)p->out_w * p->c; mid.fs = mid.rs * p->rh;
         IMGXF_CHECK(run_h(sub, mid));
     }
-    if (!slow && v_fast_ok(p, mid, d)) return launch_v_fast(p, mid, d, st);
+    if (r.v == IMGXF_ROUTE_V_V4) return launch_v4(p, mid, d, st);
+    if (r.v == IMGXF_ROUTE_V_FAST) return launch_v_fast(p, mid, d, st);
     const int64_t total = (int64_t)d.n * d.h * d.rowbytes();
     hipLaunchKernelGGL(resample_v_kernel, dim3(grid_for(total)), dim3(256), 0, st, mid, d,
                        p->d_bounds_y, p->d_kk_y, p->ksy);

@@ -178,6 +178,18 @@ int imgxf_resample_workspace_bytes_for(const imgxf_lanczos_plan* plan, const img
  * (csrc/resample_mfma.inc, no intermediate traffic), the value being the 32-byte k-steps of its
  * horizontal product.  Same bytes either way; IMGXF_RESAMPLE_NO_MFMA=1 forces the former. */
 int imgxf_resample_plan_kernel(const imgxf_lanczos_plan* plan, int* ksteps);
+/* Which kernels a call with THESE views runs (alignment and strides decide with the plan; the views need no valid
+ * memory behind them), with the knobs now in force and a 16-byte aligned workspace:
+ *   route[0]  k-steps of the fused matrix-core kernel when it runs (then the other four are 0), else 0
+ *   route[1]  IMGXF_ROUTE_H_*: the horizontal kernel (NONE: out_w == in_w, the pass is skipped)
+ *   route[2]  its window KP (8, 12, 16) for FAST and LDS, the channel count it is instantiated for when GENERIC
+ *   route[3]  IMGXF_ROUTE_V_*: the vertical kernel (NONE: out_h == in_h)
+ *   route[4]  FAST: its window KP (= the plan's coefficients per row); V4: the union window KU (12); GENERIC: 0
+ * The launch asks the same function, so the answer is what runs. */
+enum { IMGXF_ROUTE_H_NONE = 0, IMGXF_ROUTE_H_GENERIC = 1, IMGXF_ROUTE_H_FAST = 2, IMGXF_ROUTE_H_LDS = 3 };
+enum { IMGXF_ROUTE_V_NONE = 0, IMGXF_ROUTE_V_GENERIC = 1, IMGXF_ROUTE_V_FAST = 2, IMGXF_ROUTE_V_V4 = 3 };
+int imgxf_resample_plan_route(const imgxf_lanczos_plan* plan, const imgxf_view* src, const imgxf_view* dst,
+                              int route[5]);
 
 /* ---- a6: elementwise colour maps ------------------------------------------------------*/
 /* Pillow convert('L') transformation.py:336: (19595R+38470G+7471B+0x8000)>>16. src c in {3,4}, dst c==1 */
