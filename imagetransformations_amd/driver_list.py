@@ -96,8 +96,9 @@ _in_flight: collections.deque = collections.deque()     # (event, pinned block) 
 
 
 def _keep_until_copied(owner: torch.Tensor, device) -> None:
-    """The library copies the pinned block itself, so torch's host allocator does not know the stream still reads it:
-    the block is held here until an event recorded behind the copy has passed (checked, never waited for)."""
+    """This pass alone does not use `_list_block.to_device`: imgxf_driver_list_u8 copies the pinned block itself, so torch's
+    host allocator does not know the stream still reads it, and the block is held here until an event recorded behind the
+    copy has passed (checked, never waited for)."""
     while _in_flight and _in_flight[0][0].query():
         _in_flight.popleft()
     ev = torch.cuda.Event()
@@ -111,8 +112,7 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
     outputs (tests/test_gpu_driver_list.py)."""
     frames, entries = list(frames), list(entries)
     n = len(entries)
-    if guard < 0 or guard % 16:
-        raise ValueError("guard must be a non-negative multiple of 16")
+    _list_block.check_guard(guard)
     geometry, params = np.zeros((n, 5), np.int32), np.zeros((n, 2), np.float64)
     src, stride, noise = np.zeros(n, np.uint64), np.zeros(n, np.int64), np.zeros(n, np.uint64)
     coeffs = np.zeros((n, 8), np.float32)
@@ -139,8 +139,8 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
             ok = isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
             if ok:
                 h, w = int(t.shape[0]), int(t.shape[1])
-                if h and w and not _list_block.rows_dense(t):
-                    t = t.contiguous()                  # pixels of a row and their channels must be dense
+                if h and w:
+                    t = _list_block.dense(t)            # (a copy lives in `views` until the launch is queued)
                 if device is None:
                     device = t.device
                 elif t.device != device:
@@ -166,25 +166,16 @@ def apply_list_block(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES, gu
     if device is None or not int(hd["n_units"]):
         return None, [None] * n, refused
     rec["src"], rec["src_stride"], rec["noise"], rec["pc"] = src, stride, noise, coeffs
-    if guard:                                           # respace the outputs: guard bytes before, between and after them
-        taken = status == OK
-        rec["out_off"] += np.where(taken, np.cumsum(taken) * guard, 0)
-        hd["out_bytes"] = int(hd["out_bytes"]) + (int(taken.sum()) + 1) * guard
-    out_bytes = int(hd["out_bytes"])
-    size = -(-out_bytes // BLOCK_ROW_BYTES) * BLOCK_ROW_BYTES
+    taken = status == OK
+    out_bytes = _list_block.respace(hd, rec, guard, taken) if guard else int(hd["out_bytes"])
     with torch.cuda.device(device):
-        block = torch.empty(size, dtype=torch.uint8, device=device) if not guard else \
-            torch.full((size,), guard_value, dtype=torch.uint8, device=device)
+        block = _list_block.allocate(-(-out_bytes // BLOCK_ROW_BYTES) * BLOCK_ROW_BYTES, device, guard, guard_value)
         gpu = torch.empty(host.nbytes, dtype=torch.uint8, device=device)
         F.call("imgxf_driver_list_u8", host.ctypes.data, gpu.data_ptr(), block.data_ptr(), out_bytes,
                torch.cuda.current_stream(device).cuda_stream)
         _keep_until_copied(lay["owner"], device)
-    outputs = [None] * n
-    offs, sizes = rec["out_off"].tolist(), out_hw.tolist()
-    for j in np.flatnonzero(status == OK).tolist():
-        oh, ow = sizes[j]
-        outputs[j] = block[offs[j]:offs[j] + oh * ow * 3].view(oh, ow, 3)
-    return block, outputs, refused
+    views = iter(_list_block.hwc_views(block, rec["out_off"][taken].tolist(), out_hw[taken].tolist()))
+    return block, [next(views) if ok else None for ok in taken.tolist()], refused
 
 
 def apply_list(frames, entries, lds_bytes: int = DRIVER_LIST_LDS_BYTES):

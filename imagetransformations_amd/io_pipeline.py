@@ -221,7 +221,7 @@ def _save_on_device(named, out_dir: str, pool, saving: list):
     images carrying a comment Pillow would embed)."""
     import numpy as np
     import torch
-    from . import jpeg
+    from . import _list_block, jpeg
     items, rest = [], []
     for name, img in named:
         if img.mode == "RGB" and name.lower().endswith((".jpg", ".jpeg")) and "comment" not in img.info and min(img.size) > 0:
@@ -230,20 +230,15 @@ def _save_on_device(named, out_dir: str, pool, saving: list):
             rest.append((name, img))
     if not items:
         return rest
-    offs = [0]
-    for _, a in items:                                          # 16-byte aligned frames: the transform's wide loads
-        offs.append(offs[-1] + ((a.size + 15) & ~15))
-    pinned = torch.empty((offs[-1],), dtype=torch.uint8, pin_memory=True)
-    host = pinned.numpy()
-    for (_, a), o in zip(items, offs):
-        host[o:o + a.size] = a.reshape(-1)
-    block = pinned.cuda(non_blocking=True)
+    offs, total = _list_block.slots([a.size for _, a in items])  # 16-byte aligned frames: the transform's wide loads
+    offs = offs.tolist()
+    block = _list_block.pack_pinned(total, zip(offs, (a for _, a in items))).cuda(non_blocking=True)
     shapes = {a.shape for _, a in items}
     if len(shapes) == 1:
         h, w, _ = items[0][1].shape
-        files = jpeg.encode_views(torch.as_strided(block, (len(items), h, w, 3), (offs[1], 3 * w, 3, 1)))
+        files = jpeg.encode_views(torch.as_strided(block, (len(items), h, w, 3), (_list_block.r16(3 * h * w), 3 * w, 3, 1)))
     else:
-        files = jpeg.encode_list_views([block[o:o + a.size].view(a.shape) for (_, a), o in zip(items, offs)])
+        files = jpeg.encode_list_views(_list_block.hwc_views(block, offs, [a.shape[:2] for _, a in items]))
     for (name, _), data in zip(items, files):
         saving.append(pool.submit(_write, data, os.path.join(out_dir, name)))
     return rest

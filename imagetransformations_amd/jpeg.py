@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _ffi as F
+from . import _list_block
 
 ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
           28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
@@ -217,20 +218,7 @@ def encode_views(frames: torch.Tensor, quality: int = 75, capacity: int | None =
         _check_overflow(lens)
         if any(v == 0xFFFFFFFF for v in lens):
             raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds the largest baseline stream", "jpeg.encode")
-    # the files leave the device as ONE copy of sum(sizes) bytes: a device-side gather of the n streams (one torch.cat
-    # kernel over views of exactly each file's length) into a packed buffer, then a single D2H into pinned memory.
-    # (Round 2 issued one exact-size copy per file: 16 copies of ~0.7 MB cost 3.6 ms against 0.63 ms of encoding.)
-    starts = [0]
-    for v in lens:
-        starts.append(starts[-1] + v)
-    if starts[-1] == 0:
-        return [memoryview(b"")] * n
-    packed = torch.cat([files[i, :v] for i, v in enumerate(lens)])
-    staged = torch.empty((starts[-1],), dtype=torch.uint8, pin_memory=True)   # torch caches pinned blocks across calls
-    staged.copy_(packed, non_blocking=True)
-    torch.cuda.current_stream(frames.device).synchronize()
-    host = memoryview(staged.numpy())                        # (keeps the pinned block alive)
-    return [host[starts[i]:starts[i + 1]] for i in range(n)]
+    return _list_block.files_to_host([files[i, :v] for i, v in enumerate(lens)], frames.device)
 
 
 # ---- a list of frames of different sizes: imgxf_jpeg_encode_list_u8 ---------------------------------------------------
@@ -239,27 +227,25 @@ _LIST_FRAME = np.dtype([(name, np.dtype(ct)) for name, ct in F.JpegListFrame._fi
 assert _LIST_FRAME.itemsize == ctypes.sizeof(F.JpegListFrame)
 
 
-def list_layout(sizes: Sequence, capacities: Sequence[int], params: "F.JpegEncParams | None" = None):
+def list_layout(sizes: Sequence, capacities: Sequence[int], params: "F.JpegEncParams | None" = None, pinned: bool = False):
     """imgxf_jpeg_encode_list_layout_host for frames of `sizes` [(h, w)] with `capacities` bytes per file → (block: uint8
     array, header: F.JpegListHeader copy, frames: structured view INTO the block (data and row_stride are the caller's
     to fill)).  With `params` (one class: ncomp, sampling, optimize) imgxf_jpeg_encode_list_ex_layout_host, and the header
-    is a F.JpegListExHeader copy (the same fields under `.list`).  Host only."""
+    is a F.JpegListExHeader copy (the same fields under `.list`).  `pinned=True`: built in pinned memory, whose tensor comes
+    fourth.  Host only."""
     n = len(sizes)
     hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
     caps = np.ascontiguousarray(np.asarray(capacities, dtype=np.uint64).reshape(n))
-    nb, nw, no = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    tail = (ctypes.byref(ctypes.c_size_t()), ctypes.byref(ctypes.c_size_t()))   # (workspace, output bytes: the header has them)
     name, first = "imgxf_jpeg_encode_list_layout_host", ()
     if params is not None:
         name, first = "imgxf_jpeg_encode_list_ex_layout_host", (ctypes.addressof(params),)
-    F.call(name, *first, hw.ctypes.data, caps.ctypes.data, n, None, 0, ctypes.byref(nb), ctypes.byref(nw), ctypes.byref(no))
-    block = np.zeros((nb.value,), dtype=np.uint8)
-    F.call(name, *first, hw.ctypes.data, caps.ctypes.data, n, block.ctypes.data, block.nbytes, ctypes.byref(nb), ctypes.byref(nw),
-           ctypes.byref(no))
+    block, owner = _list_block.build(name, (*first, hw.ctypes.data, caps.ctypes.data, n), tail, pinned)
     kind = F.JpegListHeader if params is None else F.JpegListExHeader
     hd = kind.from_buffer_copy(block[:ctypes.sizeof(kind)].tobytes())
     off = (hd if params is None else hd.list).frames_off
     frames = block[off:off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
-    return block, hd, frames
+    return (block, hd, frames, owner) if pinned else (block, hd, frames)
 
 
 def _list_frames(frames) -> list:
@@ -290,19 +276,11 @@ def _encode_list_device(frames: list, caps: list, quality: int, cls=None):
     dev = frames[0].device
     nc = 3 if cls is None else cls[0]
     params = None if cls is None else F.JpegEncParams(nc, *((1, 1) if nc == 1 else cls[1]), int(cls[2]))
-    block, hd, rec = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps, params)
+    block, hd, rec, staged = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps, params, pinned=True)
     lhd = hd if cls is None else hd.list
-    kept = []                                        # (a copy made here must outlive the launch)
-    for i, t in enumerate(frames):
-        h, w = t.shape[0], t.shape[1]
-        if (nc == 3 and t.stride(2) != 1) or (w > 1 and t.stride(1) != nc) or (h > 1 and t.stride(0) < nc * w):
-            t = t.contiguous()
-            kept.append(t)
-        rec["data"][i] = t.data_ptr()
-        rec["row_stride"][i] = t.stride(0) if h > 1 else nc * w
-    staged = torch.empty((block.nbytes,), dtype=torch.uint8, pin_memory=True)
-    staged.numpy()[:] = block
-    block_dev = staged.to(dev, non_blocking=True)
+    read = [_list_block.dense(t, nc) for t in frames]         # (held until the launch is queued)
+    rec["data"], rec["row_stride"] = _list_block.addresses(read, nc)
+    block_dev = _list_block.to_device(staged, dev)
     out = torch.empty((lhd.out_bytes,), dtype=torch.uint8, device=dev)
     sizes = torch.zeros((len(frames),), dtype=torch.int32, device=dev)
     ws = torch.empty((lhd.workspace_bytes,), dtype=torch.uint8, device=dev)
@@ -313,7 +291,7 @@ def _encode_list_device(frames: list, caps: list, quality: int, cls=None):
         F.call(name, block.ctypes.data, block_dev.data_ptr(), *first, ctypes.addressof(tables(quality)), hdr, len(hdr),
                out.data_ptr(), lhd.out_bytes, sizes.data_ptr(), ws.data_ptr(), lhd.workspace_bytes,
                torch.cuda.current_stream(dev).cuda_stream)
-    lens = (sizes.to(torch.int64) & 0xFFFFFFFF).cpu().tolist()     # (synchronises: staged, kept and ws are done with)
+    lens = (sizes.to(torch.int64) & 0xFFFFFFFF).cpu().tolist()     # (synchronises: staged, read and ws are done with)
     return out, rec["out_off"].tolist(), lens
 
 
@@ -377,17 +355,7 @@ def encode_list_views(frames: Sequence[torch.Tensor], quality: int = 75, *, subs
                     break
             if todo:
                 raise F.ImgxfError(F.ERR_WORKSPACE, "a JPEG stream exceeds the largest baseline stream", "jpeg.encode_list")
-    starts = [0]
-    for i in range(len(frames)):
-        starts.append(starts[-1] + pieces[i].numel())
-    packed = torch.cat([pieces[i] for i in range(len(frames))])   # one gather, one D2H (as encode_views)
-    staged = torch.empty((starts[-1],), dtype=torch.uint8, pin_memory=True)
-    staged.copy_(packed, non_blocking=True)
-    torch.cuda.current_stream(frames[0].device).synchronize()
-    host = memoryview(staged.numpy())
-    for i in range(len(frames)):
-        result[i] = host[starts[i]:starts[i + 1]]
-    return result
+    return _list_block.files_to_host([pieces[i] for i in range(len(frames))], frames[0].device)
 
 
 # ---- JPEG compression without a file: imgxf_jpeg_roundtrip_u8 / imgxf_jpeg_roundtrip_list_u8 -----------------------------
@@ -509,45 +477,36 @@ def roundtrip_records(n: int, h: int, w: int, subsampling=-1, out_row_stride: in
     return images
 
 
-def roundtrip_list_layout(sizes: Sequence):
+def roundtrip_list_layout(sizes: Sequence, pinned: bool = False):
     """imgxf_jpeg_roundtrip_list_layout_host for frames of `sizes` [(h, w)] → (block: uint8 array, header:
     F.JpegRoundtripListHeader copy, frames: structured view INTO the block (data and row_stride are the caller's to
-    fill), images: a copy of the block's jpeg_decode.DecImage records).  Host only."""
+    fill), images: a copy of the block's jpeg_decode.DecImage records; with `pinned=True` fifth the pinned tensor it is
+    built in).  Host only."""
     n = len(sizes)
     hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
-    nb, nw, no = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-    F.call("imgxf_jpeg_roundtrip_list_layout_host", hw.ctypes.data, n, None, 0, ctypes.byref(nb), ctypes.byref(nw), ctypes.byref(no))
-    block = np.zeros((nb.value,), dtype=np.uint8)
-    F.call("imgxf_jpeg_roundtrip_list_layout_host", hw.ctypes.data, n, block.ctypes.data, block.nbytes, ctypes.byref(nb), ctypes.byref(nw),
-           ctypes.byref(no))
+    tail = (ctypes.byref(ctypes.c_size_t()), ctypes.byref(ctypes.c_size_t()))   # (workspace, output bytes: the header has them)
+    block, owner = _list_block.build("imgxf_jpeg_roundtrip_list_layout_host", (hw.ctypes.data, n), tail, pinned)
     hd = F.JpegRoundtripListHeader.from_buffer_copy(block[:ctypes.sizeof(F.JpegRoundtripListHeader)].tobytes())
     frames = block[hd.frames_off:hd.frames_off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
     from .jpeg_decode import DecImage
     images = (DecImage * n).from_buffer_copy(block[hd.images_off:hd.images_off + n * ctypes.sizeof(DecImage)].tobytes())
-    return block, hd, frames, images
+    return (block, hd, frames, images, owner) if pinned else (block, hd, frames, images)
 
 
-def _roundtrip_list_call(frames: list, quality: int, out: torch.Tensor, base: int) -> list:
-    """One imgxf_jpeg_roundtrip_list_u8 call (one quality, 4:2:0): frame f's pixels at out[base + offs[f]:]; → offs."""
+def _roundtrip_list_call(frames: list, quality: int, out: torch.Tensor, base: int) -> None:
+    """One imgxf_jpeg_roundtrip_list_u8 call (one quality, 4:2:0): the frames' pixels from out[base:] on, in the layout's
+    out_off, which are `_list_block.slots`' (tests/test_jpeg_roundtrip_host.py)."""
     dev = frames[0].device
-    block, hd, rec, _ = roundtrip_list_layout([(t.shape[0], t.shape[1]) for t in frames])
-    kept = []                                        # (a copy made here must outlive the launch)
-    for i, t in enumerate(frames):
-        if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 3) or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
-            t = t.contiguous()
-            kept.append(t)
-        rec["data"][i] = t.data_ptr()
-        rec["row_stride"][i] = t.stride(0) if t.shape[0] > 1 else 3 * t.shape[1]
-    staged = torch.empty((block.nbytes,), dtype=torch.uint8, pin_memory=True)
-    staged.numpy()[:] = block
-    block_dev = staged.to(dev, non_blocking=True)    # the call's one host-to-device copy
+    block, hd, rec, _, staged = roundtrip_list_layout([(t.shape[0], t.shape[1]) for t in frames], pinned=True)
+    read = [_list_block.dense(t) for t in frames]
+    rec["data"], rec["row_stride"] = _list_block.addresses(read)
+    block_dev = _list_block.to_device(staged, dev)   # the call's one host-to-device copy
     ws = torch.empty((max(hd.workspace_bytes, 16),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         F.call("imgxf_jpeg_roundtrip_list_u8", block.ctypes.data, block_dev.data_ptr(), ctypes.addressof(tables(quality)),
                out.data_ptr() + base, hd.out_bytes, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    # (staged, block_dev, ws and the copies in `kept` may go when this returns: torch's pinned-host and device allocators
-    # are stream-ordered, and everything above was enqueued on the current stream)
-    return rec["out_off"].tolist()
+    # (block_dev, ws and the copies in `read` may go when this returns: torch's device allocator is stream-ordered, and
+    # everything above was enqueued on the current stream)
 
 
 def roundtrip_list(frames: Sequence[torch.Tensor], quality=75, *, subsampling=-1) -> List[torch.Tensor]:
@@ -575,26 +534,21 @@ def roundtrip_list(frames: Sequence[torch.Tensor], quality=75, *, subsampling=-1
     if len({t.device for t in frames}) > 1:
         raise ValueError("jpeg.roundtrip_list: the frames live on different devices")
     dev = frames[0].device
-    slot = [(3 * t.shape[0] * t.shape[1] + 15) & ~15 for t in frames]
-    out = torch.empty((sum(slot),), dtype=torch.uint8, device=dev)
-    result: list = [None] * len(frames)
     groups: dict = {}
     for i, (t, q) in enumerate(zip(frames, qs)):
         groups.setdefault((q,) if hv == (2, 2) else (q,) + tuple(t.shape), []).append(i)
-    base = 0
+    order = [i for members in groups.values() for i in members]       # the allocation holds the frames group by group
+    offs, total = _list_block.slots([frames[i].numel() for i in order])
+    at = dict(zip(order, offs.tolist()))                             # frame -> where its pixels start
+    out = _list_block.allocate(total, dev)
     for key, members in groups.items():
         q = key[0]
         for lo in range(0, len(members), _RT_MAX_FRAMES):
             idx = members[lo:lo + _RT_MAX_FRAMES]
             if hv == (2, 2):
-                offs = _roundtrip_list_call([frames[i] for i in idx], q, out, base)
+                _roundtrip_list_call([frames[i] for i in idx], q, out, at[idx[0]])
             else:
                 h, w, _ = frames[idx[0]].shape
-                dst = out[base:base + len(idx) * slot[idx[0]]].view(len(idx), slot[idx[0]])[:, :3 * h * w].view(len(idx), h, w, 3)
+                dst = out.as_strided((len(idx), h, w, 3), (_list_block.r16(3 * h * w), 3 * w, 3, 1), at[idx[0]])
                 roundtrip(torch.stack([frames[i] for i in idx]), q, subsampling=subsampling, out=dst)
-                offs = [k * slot[idx[0]] for k in range(len(idx))]
-            for i, o in zip(idx, offs):
-                h, w, _ = frames[i].shape
-                result[i] = out[base + o:base + o + 3 * h * w].view(h, w, 3)
-            base += sum(slot[i] for i in idx)
-    return result
+    return _list_block.hwc_views(out, [at[i] for i in range(len(frames))], [t.shape[:2] for t in frames])

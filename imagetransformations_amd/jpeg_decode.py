@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _ffi as F
+from . import _list_block
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
                    21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53,
@@ -406,7 +407,7 @@ def decode(files: Sequence[bytes], device=None, profile: bool = False, *, progre
             L.images[j].out_off = out_pos + k * h * w * 3
             L.images[j].out_pitch = w * 3
         spans.append((out_pos, len(group), h, w, group))
-        out_pos += (len(group) * h * w * 3 + 15) & ~15
+        out_pos += _list_block.r16(len(group) * h * w * 3)
     t_host = time.perf_counter()
     t_mark = [t_host]
 

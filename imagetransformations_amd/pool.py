@@ -18,6 +18,7 @@ from PIL import Image
 import torch
 
 from . import _ffi as F
+from . import _list_block
 from . import ops, transformation as T
 from .transformation import _device, _download, _upload
 
@@ -442,20 +443,25 @@ def _op_table(table):
     return op_tab
 
 
+def _upload_block(head, host, dev, payload_bytes: int, device):
+    """The block of one launch: the record arrays `head` back to back, 16-byte padding, the float64 payload.  Records and
+    host-drawn payload go up in ONE copy; numpy_stream's slices are already on the device.  → (pinned, device, head bytes)."""
+    starts = np.cumsum([0] + [a.nbytes for a in head]).tolist()
+    head_bytes = _list_block.r16(starts[-1])
+    staged = _list_block.pack_pinned(head_bytes + sum(a.nbytes for _, a in host),
+                                     list(zip(starts, head)) + [(head_bytes + off, a) for off, a in host])
+    gpu = torch.empty(head_bytes + payload_bytes, dtype=torch.uint8, device=device)
+    gpu[:staged.numel()].copy_(staged, non_blocking=True)
+    for off, t in dev:
+        gpu[head_bytes + off:head_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
+    return staged, gpu, head_bytes
+
+
 def _stage(plan: ChainPlan, device, lo, hi):
     """Records and payload of one launch on the device, the operation table and the workspace."""
     n, h, w = plan.n, plan.h, plan.w
     rec, host, dev, payload_bytes = _records(plan, lo, hi)
-    rec_bytes = (rec.nbytes + 15) & ~15
-    staged = torch.empty(rec_bytes + sum(a.nbytes for _, a in host), dtype=torch.uint8, pin_memory=True)
-    buf = staged.numpy()
-    buf[:rec.nbytes] = rec.reshape(-1)
-    for off, a in host:
-        buf[rec_bytes + off:rec_bytes + off + a.nbytes] = a.reshape(-1).view(np.uint8)
-    gpu = torch.empty(rec_bytes + payload_bytes, dtype=torch.uint8, device=device)
-    gpu[:staged.numel()].copy_(staged, non_blocking=True)   # one host-to-device copy per launch
-    for off, t in dev:                                       # numpy_stream's normals and masks are already on the device
-        gpu[rec_bytes + off:rec_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
+    _, gpu, rec_bytes = _upload_block([rec], host, dev, payload_bytes, device)
     ws_bytes = chain_workspace_bytes(n, h, w)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
     return gpu, rec.shape[1] // _STEP_BYTES, rec_bytes, payload_bytes, _op_table(plan.table), max(1, len(plan.table)), ws, ws_bytes
@@ -537,10 +543,6 @@ _LIST_FRAME = np.dtype([("src", "<u8"), ("src_stride", "<i8"), ("out_off", "<u8"
 _PAYLOAD_PER_PIXEL = {"gaussian_noise": 24, "impulse_noise": 8, "shot_noise": 24}        # float64 [h,w,3] or [h,w]
 
 
-def _r16(nbytes):
-    return (nbytes + 15) & ~15
-
-
 @functools.lru_cache(maxsize=1 << 14)
 def chain_list_class(h: int, w: int):
     """(launch class, LDS bytes, workspace bytes) of one h x w frame in a list pass (imgxf_pool_chain_list_class):
@@ -579,8 +581,7 @@ def chain_list_groups(sizes, chains) -> list:
 
 
 def _stage_list(plan: ChainPlan, device, lo, hi, src, src_stride, out_off):
-    """One launch group on the device: the frame records (sorted by launch class), the step records and the host-drawn
-    payload go up in ONE host-to-device copy; device-drawn payload slices are copied on the device."""
+    """One launch group on the device (`_upload_block`): the frame records sorted by launch class, step records, payload."""
     n = plan.n
     rec, host, dev, payload_bytes = _records(plan, lo, hi)
     cls = np.empty(n, np.int64)
@@ -594,19 +595,7 @@ def _stage_list(plan: ChainPlan, device, lo, hi, src, src_stride, out_off):
     fr["rec_off"] = n * _LIST_FRAME.itemsize + np.arange(n, dtype=np.uint64) * np.uint64(rec.shape[1])
     fr["h"], fr["w"] = np.array(plan.sizes, np.int32).reshape(n, 2).T
     fr["steps"] = np.asarray(hi, np.int64) - np.asarray(lo, np.int64)
-    fr = fr[order]
-    head = fr.nbytes + rec.nbytes
-    head_bytes = _r16(head)
-    staged = torch.empty(head_bytes + sum(a.nbytes for _, a in host), dtype=torch.uint8, pin_memory=True)
-    buf = staged.numpy()
-    buf[:fr.nbytes] = fr.view(np.uint8)
-    buf[fr.nbytes:head] = rec.reshape(-1)
-    for off, a in host:
-        buf[head_bytes + off:head_bytes + off + a.nbytes] = a.reshape(-1).view(np.uint8)
-    gpu = torch.empty(head_bytes + payload_bytes, dtype=torch.uint8, device=device)
-    gpu[:staged.numel()].copy_(staged, non_blocking=True)   # one host-to-device copy per launch group
-    for off, t in dev:
-        gpu[head_bytes + off:head_bytes + off + t.numel() * 8].view(torch.float64).copy_(t.reshape(-1))
+    staged, gpu, head_bytes = _upload_block([fr[order], rec], host, dev, payload_bytes, device)
     ws_bytes = int(ws.sum())
     wsp = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
     table = plan.table or [(F.POOL_CODES["enhance_brightness"], 0, [0.0] * 10)]   # no chain has a step: the kernel copies
@@ -623,15 +612,13 @@ def _run_list(frames, sizes, block: torch.Tensor, out_off, chains) -> None:
     """One launch group: plan, draw and launch frames (each a [h, w, 3] view) into block at out_off."""
     n, device = len(frames), block.device
     plan = chain_plan_list(sizes, chains, device)
-    src = np.array([t.data_ptr() for t in frames], np.uint64)
-    stride = np.array([t.stride(0) if h > 1 else 3 * w for t, (h, w) in zip(frames, sizes)], np.int64)
+    src, stride = _list_block.addresses(frames)
     zero, full = np.zeros(n, np.int64), np.array([len(m) for m in plan.members], np.int64)
     if plan.finished:
         _launch_list_staged(block, *_stage_list(plan, device, zero, full, src, stride, out_off))
         return
-    nbytes = np.array([_r16(3 * h * w) for h, w in sizes], np.int64)
-    mid_off = np.cumsum(nbytes) - nbytes
-    mid = torch.empty(int(nbytes.sum()), dtype=torch.uint8, device=device)
+    mid_off, mid_bytes = _list_block.slots([3 * h * w for h, w in sizes])
+    mid = torch.empty(mid_bytes, dtype=torch.uint8, device=device)
     _launch_list_staged(mid, *_stage_list(plan, device, zero, plan.split, src, stride, mid_off))
     back = mid.cpu().numpy()                                 # the frames before shot_noise, in one device-to-host copy
     chain_plan_finish(plan, [back[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(mid_off.tolist(), sizes)], device)
@@ -666,20 +653,16 @@ def apply_chain_list_block(frames, chains, guard: int = 0, guard_value: int = 0)
     empty list): (block, outputs).  `guard` (a multiple of 16) leaves that many bytes, set to `guard_value`, before,
     between and after the outputs (tests/test_gpu_pool_chain_list.py)."""
     frames = list(frames)
-    if guard < 0 or guard % 16:
-        raise ValueError("guard must be a non-negative multiple of 16")
+    _list_block.check_guard(guard)
     sizes = _check_list_frames(frames)                       # every check before the first draw
     n = len(frames)
     if n == 0:
         return None, []
     per = _chains_per_image(chains, n)
     groups = chain_list_groups(sizes, per)
-    nbytes = np.array([_r16(3 * h * w) for h, w in sizes], np.int64) + guard
-    out_off = guard + np.cumsum(nbytes) - nbytes
-    total, device = guard + int(nbytes.sum()), frames[0].device
-    block = torch.empty(total, dtype=torch.uint8, device=device) if not guard else \
-        torch.full((total,), guard_value, dtype=torch.uint8, device=device)
-    outputs = [block.as_strided((h, w, 3), (3 * w, 3, 1), o) for o, (h, w) in zip(out_off.tolist(), sizes)]
+    out_off, total = _list_block.slots([3 * h * w for h, w in sizes], guard)
+    block = _list_block.allocate(total, frames[0].device, guard, guard_value)
+    outputs = _list_block.hwc_views(block, out_off.tolist(), sizes)
     for a, b, batched in groups:
         if batched:
             _run_list(frames[a:b], sizes[a:b], block, out_off[a:b], per[a:b])

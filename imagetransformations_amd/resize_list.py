@@ -8,7 +8,7 @@ import torch
 
 from . import _ffi as F
 from . import _list_block
-from .tensor_maps import _int_array, resample_filter, resized_output_size
+from .tensor_maps import resample_filter, resized_output_size
 
 BICUBIC = 3                                             # Image.resize's default, ops.RESAMPLE_BICUBIC
 
@@ -62,37 +62,23 @@ def resize_list_block(frames, sizes, interpolation=BICUBIC, boxes=None, index=No
     entries): (block, outputs).  `guard` (a multiple of 16) leaves that many bytes, set to `guard_value`, before, between
     and after the outputs (tests/test_gpu_resize_list.py)."""
     filt = resample_filter(interpolation)
-    if guard < 0 or guard % 16:
-        raise ValueError("guard must be a non-negative multiple of 16")
-    sizes = _int_array(sizes, "sizes", 2)
+    _list_block.check_guard(guard)
+    sizes = _list_block.int_array(sizes, "sizes", 2)
     k = len(sizes)
     if k and (sizes.min() < 1 or sizes.max() > 32767):
         raise ValueError("sizes values (width, height) must lie in 1 .. 32767")
     if boxes is not None:
-        boxes = _int_array(boxes, "boxes", 4)
+        boxes = _list_block.int_array(boxes, "boxes", 4)
         if len(boxes) != k:
             raise ValueError(f"boxes has {len(boxes)} rows for {k} sizes")
     if index is not None:
-        index = _int_array(index, "index")
+        index = _list_block.int_array(index, "index")
         if len(index) != k:
             raise ValueError(f"index has {len(index)} entries for {k} sizes")
     frames = list(frames)
     _list_block.check_frames(frames, "resize_list")
-    if index is None:
-        if len(frames) != k:
-            raise ValueError(f"sizes has {k} rows for {len(frames)} frames (one per frame where no index is given)")
-        index = np.arange(k, dtype=np.int64)
-    elif k and (index.min() < 0 or index.max() >= len(frames)):
-        raise ValueError(f"index values must lie in 0 .. {len(frames) - 1}")
-    hw = np.array([(t.shape[0], t.shape[1]) for t in frames], np.int64).reshape(-1, 2)[index]
-    if boxes is None:
-        boxes = np.concatenate([np.zeros((k, 2), np.int64), hw], axis=1)
-    top, left, bh, bw = boxes.T if k else (np.zeros(0, np.int64),) * 4
-    bad = (bh < 1) | (bw < 1) | (top < 0) | (left < 0) | (top > hw[:, 0] - bh) | (left > hw[:, 1] - bw)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"box {tuple(boxes[i].tolist())} (top, left, height, width) of entry {i} is empty or not inside its "
-                         f"{int(hw[i, 0])} x {int(hw[i, 1])} frame")
+    index, hw, boxes = _list_block.entries(
+        frames, k, index, boxes, f"sizes has {k} rows for {len(frames)} frames (one per frame where no index is given)")
     if taken is not None:
         taken[:] = []
     if k == 0:
@@ -104,25 +90,20 @@ def resize_list_block(frames, sizes, interpolation=BICUBIC, boxes=None, index=No
     hd, rec, _ = block_views(host)
     ptr, stride = _list_block.addresses(frames)
     rec["data"], rec["row_stride"] = ptr[index], stride[index]
-    if guard:                                           # respace the outputs: guard bytes before, between and after them
-        rec["out_off"] += np.arange(1, k + 1, dtype=np.int64) * guard
-        hd["out_bytes"] = int(hd["out_bytes"]) + (k + 1) * guard
-    out_bytes = int(hd["out_bytes"])
+    out_bytes = _list_block.respace(hd, rec, guard) if guard else int(hd["out_bytes"])
     with torch.cuda.device(device):
-        block = torch.empty(out_bytes, dtype=torch.uint8, device=device) if not guard else \
-            torch.full((out_bytes,), guard_value, dtype=torch.uint8, device=device)
+        block = _list_block.allocate(out_bytes, device, guard, guard_value)
         if hd["n_units"]:
-            gpu = staged.to(device, non_blocking=True)
+            gpu = _list_block.to_device(staged, device)
             F.call("imgxf_resize_list_u8", host.ctypes.data, host.nbytes, gpu.data_ptr(), block.data_ptr(), out_bytes,
                    torch.cuda.current_stream(device).cuda_stream)
-    offs = rec["out_off"].tolist()
-    outputs = [block.as_strided((oh, ow, 3), (3 * ow, 3, 1), o) for o, (ow, oh) in zip(offs, sizes.tolist())]
+    outputs = _list_block.hwc_views(block, rec["out_off"].tolist(), sizes[:, ::-1].tolist())
     served = rec["unit_rows"] > 0
     if not served.all():
-        from .tensor_maps import _resized_crop_entry
+        from .tensor_maps import resized_crop_entry
         for i in np.flatnonzero(~served).tolist():      # `ops.resize` on the box alone (twice where Pillow filters rows first)
-            outputs[i].copy_(_resized_crop_entry(frames[index[i]], boxes[i], (int(sizes[i, 1]), int(sizes[i, 0])), False, None,
-                                                 None, torch.uint8, filt))
+            outputs[i].copy_(resized_crop_entry(frames[index[i]], boxes[i], (int(sizes[i, 1]), int(sizes[i, 0])), False, None,
+                                                None, torch.uint8, filt))
     if taken is not None:
         taken[:] = served.tolist()
     return block, outputs

@@ -77,21 +77,39 @@ def add_contrast(images: torch.Tensor, factor: float = 1.5) -> torch.Tensor:
     return _Map.apply(images, _CONTRAST, None, factor, 0.0)
 
 
+def _mean_std(mean, std, c=None):
+    """mean and std, checked — given together and, where the channel count is known, one value per channel — as the C entry
+    points take them: (float32 array, float32 array), or null for both."""
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std come together")
+    if c is not None and mean is not None and (len(mean) != c or len(std) != c):
+        raise ValueError(f"mean / std need {c} entries")
+    return (F.f32_array(mean), F.f32_array(std)) if mean is not None else (None, None)
+
+
+def _out_or_new(out, shape, dtype, frames, kind: str) -> torch.Tensor:
+    """The `out=` destination of a list pass, checked (`kind`: the dtype as the caller's message words it), or a new tensor."""
+    device = frames[0].device if frames else torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != device or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {kind} {list(shape)} tensor on {device}")
+    return out
+
+
 def to_tensor(frames: torch.Tensor, mean=None, std=None) -> torch.Tensor:
     """transforms.ToTensor() followed (when mean / std are given) by transforms.Normalize(mean, std)
     on a uint8 [N,H,W,C] / [H,W,C] / [H,W] device tensor -> float32 [N,C,H,W] / [C,H,W], in one
     pass and bit-identical to torchvision's `x.div(255)`, `sub_(mean)`, `div_(std)`."""
     if not frames.is_cuda or frames.dtype != torch.uint8:
         raise TypeError("to_tensor expects a uint8 tensor on the HIP device")
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std come together")
+    _mean_std(mean, std)
     v = F.view_of(frames)
     n, h, w, c = v.n, v.h, v.w, v.c
-    if mean is not None and (len(mean) != c or len(std) != c):
-        raise ValueError(f"mean / std need {c} entries")
+    norm = _mean_std(mean, std, c)
     out = torch.empty((n, c, h, w), dtype=torch.float32, device=frames.device)
-    _launch(frames, "imgxf_to_tensor_f32", F.vp(v), out.data_ptr(), F.f32_array(mean) if mean is not None else None,
-            F.f32_array(std) if std is not None else None)
+    _launch(frames, "imgxf_to_tensor_f32", F.vp(v), out.data_ptr(), *norm)
     return out if frames.dim() == 4 else out[0]
 
 
@@ -220,25 +238,16 @@ def preprocess_list(frames, resize: int = 256, crop: int = 224, mean=None, std=N
     one launch."""
     filt = resample_filter(interpolation)
     frames = list(frames)
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std come together")
-    if mean is not None and (len(mean) != 3 or len(std) != 3):
-        raise ValueError("mean / std need 3 entries")
+    _mean_std(mean, std, 3)
     if crop < 1 or crop > resize:
         raise ValueError("CenterCrop larger than the resized image (torchvision pads; not needed by the reference)")
     _list_block.check_frames(frames, "preprocess_list")
     n = len(frames)
-    device = frames[0].device if n else torch.device("cuda", torch.cuda.current_device())
-    if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != device
-                or tuple(out.shape) != (n, 3, crop, crop) or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 [{n}, 3, {crop}, {crop}] tensor on {device}")
-    else:
-        out = torch.empty((n, 3, crop, crop), dtype=torch.float32, device=device)
+    out = _out_or_new(out, (n, 3, crop, crop), torch.float32, frames, "float32")
     if n == 0:
         return out
-    block, gpu = _stage_list(frames, resize, crop, device, filt)
-    _launch_list(block, gpu, out, mean, std, device)
+    block, gpu = _stage_list(frames, resize, crop, out.device, filt)
+    _launch_list(block, gpu, out, mean, std, out.device)
     for i in np.flatnonzero(preprocess_block_views(block)[1]["unit_rows"] == 0):
         out[i].copy_(preprocess(frames[i][None], resize, crop, mean, std, filt)[0])
     return out
@@ -251,18 +260,14 @@ def _stage_list(frames, resize: int, crop: int, device, filt: int = BILINEAR):
     block, staged = preprocess_layout(geometry, crop, pinned=True, interpolation=filt)
     hd, rec, _ = preprocess_block_views(block)
     rec["data"], rec["row_stride"] = _list_block.addresses(frames)
-    if not hd["n_units"]:
-        return block, None
-    with torch.cuda.device(device):
-        return block, staged.to(device, non_blocking=True)
+    return block, _list_block.to_device(staged, device) if hd["n_units"] else None
 
 
 def _launch_list(block, gpu, out, mean, std, device) -> None:
     if gpu is None:
         return
     with torch.cuda.device(device):
-        F.call("imgxf_preprocess_list_f32", block.ctypes.data, gpu.data_ptr(), out.data_ptr(),
-               F.f32_array(mean) if mean is not None else None, F.f32_array(std) if std is not None else None,
+        F.call("imgxf_preprocess_list_f32", block.ctypes.data, gpu.data_ptr(), out.data_ptr(), *_mean_std(mean, std),
                torch.cuda.current_stream(device).cuda_stream)
 
 
@@ -329,20 +334,6 @@ def _crop_size(size):
     return pair
 
 
-def _int_array(values, name: str, width=None) -> np.ndarray:
-    """`values` (tensor, array or nested sequence of integers) as an int64 array of shape [K] or [K, width]."""
-    if isinstance(values, torch.Tensor):
-        values = values.detach().cpu().numpy()
-    a = np.asarray(values)
-    if a.size == 0:
-        a = a.astype(np.int64).reshape((0,) if width is None else (0, width))
-    if a.dtype.kind not in "iu":
-        raise ValueError(f"{name} must hold integers, got dtype {a.dtype}")
-    if a.ndim != (1 if width is None else 2) or (width is not None and a.shape[1] != width):
-        raise ValueError(f"{name} must have shape {'[K]' if width is None else f'[K, {width}]'}, got {a.shape}")
-    return a.astype(np.int64)
-
-
 _RCL_KERNEL_FILTERS = (2, 3, 4)         # BILINEAR, BICUBIC, BOX: the tables resized_crop_list's kernel builds itself
 
 
@@ -373,21 +364,19 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
     plan is created or kept, whatever the number of distinct boxes."""
     filt = resample_filter(interpolation)
     frames = list(frames)
-    if (mean is None) != (std is None):
-        raise ValueError("mean and std come together")
-    if mean is not None and (len(mean) != 3 or len(std) != 3):
-        raise ValueError("mean / std need 3 entries")
+    _mean_std(mean, std, 3)
     if dtype not in (torch.float32, torch.uint8):
         raise ValueError("dtype must be torch.float32 or torch.uint8")
     if dtype == torch.uint8 and mean is not None:
         raise ValueError("mean / std need dtype=torch.float32 (uint8 output is not normalised)")
     sh, sw = _crop_size(size)
     _list_block.check_frames(frames, "resized_crop_list")
-    boxes = _int_array(boxes, "boxes", 4)
+    boxes = _list_block.int_array(boxes, "boxes", 4)
     k = len(boxes)
-    index = np.arange(len(frames), dtype=np.int64) if index is None else _int_array(index, "index")
-    if len(index) != k:
-        raise ValueError(f"boxes has {k} rows for {len(index)} entries (one per frame where no index is given)")
+    index = np.arange(len(frames), dtype=np.int64) if index is None else _list_block.int_array(index, "index")
+    rows = f"boxes has {k} rows for {len(index)} entries (one per frame where no index is given)"
+    if len(index) != k:                                          # (before `flips` is looked at, as ever; `entries` agrees)
+        raise ValueError(rows)
     if flips is None:
         flips = np.zeros(k, bool)
     else:
@@ -398,23 +387,8 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
             raise ValueError(f"flips must be a bool [K] array, got {flips.dtype} {flips.shape}")
         if len(flips) != k:
             raise ValueError(f"flips has {len(flips)} entries for {k} boxes")
-    if k and (index.min() < 0 or index.max() >= len(frames)):
-        raise ValueError(f"index values must lie in 0 .. {len(frames) - 1}")
-    hw = np.array([(t.shape[0], t.shape[1]) for t in frames], np.int64).reshape(-1, 2)[index]
-    top, left, bh, bw = boxes.T if k else (np.zeros(0, np.int64),) * 4
-    bad = (bh < 1) | (bw < 1) | (top < 0) | (left < 0) | (top > hw[:, 0] - bh) | (left > hw[:, 1] - bw)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"box {tuple(boxes[i].tolist())} (top, left, height, width) of entry {i} is empty or not inside its "
-                         f"{int(hw[i, 0])} x {int(hw[i, 1])} frame (torchvision pads there; not done here)")
-    device = frames[0].device if frames else torch.device("cuda", torch.cuda.current_device())
-    shape = (k, 3, sh, sw) if dtype == torch.float32 else (k, sh, sw, 3)
-    if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != device or tuple(out.shape) != shape
-                or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous {dtype} {list(shape)} tensor on {device}")
-    else:
-        out = torch.empty(shape, dtype=dtype, device=device)
+    index, hw, boxes = _list_block.entries(frames, k, index, boxes, rows, " (torchvision pads there; not done here)")
+    out = _out_or_new(out, (k, 3, sh, sw) if dtype == torch.float32 else (k, sh, sw, 3), dtype, frames, str(dtype))
     if k == 0:
         if taken is not None:
             taken[:] = []
@@ -427,22 +401,22 @@ def resized_crop_list(frames, boxes, size, flips=None, index=None, mean=None, st
         ptr, stride = _list_block.addresses(frames)
         rec["data"], rec["row_stride"] = ptr[index], stride[index]
         if hd["n_units"]:
-            with torch.cuda.device(device):
-                gpu = staged.to(device, non_blocking=True)
+            with torch.cuda.device(out.device):
+                gpu = _list_block.to_device(staged, out.device)
                 F.call("imgxf_resized_crop_list_filter", block.ctypes.data, block.nbytes, gpu.data_ptr(), out.data_ptr(),
-                       1 if dtype == torch.uint8 else 0, filt, F.f32_array(mean) if mean is not None else None,
-                       F.f32_array(std) if std is not None else None, torch.cuda.current_stream(device).cuda_stream)
+                       1 if dtype == torch.uint8 else 0, filt, *_mean_std(mean, std),
+                       torch.cuda.current_stream(out.device).cuda_stream)
         served = rec["unit_rows"] > 0
     else:                                                        # HAMMING, LANCZOS: no table the kernel can build
         served = np.zeros(k, bool)
     for i in np.flatnonzero(~served):
-        out[i].copy_(_resized_crop_entry(frames[index[i]], boxes[i], (sh, sw), bool(flips[i]), mean, std, dtype, filt))
+        out[i].copy_(resized_crop_entry(frames[index[i]], boxes[i], (sh, sw), bool(flips[i]), mean, std, dtype, filt))
     if taken is not None:
         taken[:] = served.tolist()
     return out
 
 
-def _resized_crop_entry(frame, box, size, flip: bool, mean, std, dtype, filt: int = BILINEAR):
+def resized_crop_entry(frame, box, size, flip: bool, mean, std, dtype, filt: int = BILINEAR):
     """One entry of `resized_crop_list` by the calls that predate it: the resample plan of the box's own size (or a plain
     crop where the box already has the output's size, as `preprocess` does), `to_tensor`, the flip."""
     from . import ops
