@@ -89,10 +89,7 @@ inline int box_fx(int a, int b, int tw, int th, int extra) {
 }
 // 16-byte chunks per packed RGB box row of bw pixels (any alignment of its start)
 inline int packed_chunks(int bw) { return (bw * 3 + 15 + 15) / 16; }
-// base address, row stride and frame stride are multiples of `bytes` (a power of two)
-inline bool aligned(const View& v, int bytes) {
-    return ((((uintptr_t)v.p) | (uintptr_t)v.rs | (uintptr_t)v.fs) & (uintptr_t)(bytes - 1)) == 0;
-}
+// (aligned(view, bytes): imgxf_common.h)
 // byte offsets inside a frame fit 32 bits
 inline bool offsets_fit_32(const View& v) { return (int64_t)v.h * v.rs < ((int64_t)1 << 32); }
 // ceil(2^32 / ntx); ntx, nty <= 1024: exact; 0 when ntx == 1

@@ -14,31 +14,15 @@ template <class Op>
 __global__ __launch_bounds__(256) void pixel3_map_kernel(View s, View d, Op op) {
     const int ngrp = (d.w + 15) >> 4;
     const int64_t total = (int64_t)d.n * d.h * ngrp;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int g = (int)(t % ngrp);
-        const int64_t r = t / ngrp;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [g, y, f] = row_item(t, ngrp, d.h);
         const int x0 = g << 4;
         const int np = min(16, d.w - x0);
         const u8* sp = s.row(f, y) + x0 * 3;
         u8* dp = d.row(f, y) + x0 * 3;
         u32 in[12], out[12];
         const bool vec = np == 16 && ((((uintptr_t)sp) | ((uintptr_t)dp)) & 15) == 0;
-        if (vec) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const uint4 q = ((const uint4*)sp)[b];
-                in[4 * b] = q.x; in[4 * b + 1] = q.y; in[4 * b + 2] = q.z; in[4 * b + 3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) in[k] = 0;
-            for (int e = 0; e < np * 3; ++e) {
-                const u32 v = sp[e];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) if ((e >> 2) == k) in[k] |= v << (8 * (e & 3));
-            }
-        }
+        load_chunk(sp, np * 3, vec, in);
 #pragma unroll
         for (int k = 0; k < 12; ++k) out[k] = 0;
 #pragma unroll
@@ -50,17 +34,7 @@ __global__ __launch_bounds__(256) void pixel3_map_kernel(View s, View d, Op op) 
 #pragma unroll
             for (int j = 0; j < 3; ++j) { const int b = px * 3 + j; out[b >> 2] |= o[j] << (8 * (b & 3)); }
         }
-        if (vec) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) ((uint4*)dp)[b] = make_uint4(out[4 * b], out[4 * b + 1], out[4 * b + 2], out[4 * b + 3]);
-        } else {
-            for (int e = 0; e < np * 3; ++e) {
-                u32 w = 0;
-#pragma unroll
-                for (int k = 0; k < 12; ++k) if ((e >> 2) == k) w = out[k];
-                dp[e] = (u8)(w >> (8 * (e & 3)));
-            }
-        }
+        store_chunk(dp, np * 3, vec, out);
     }
 }
 
@@ -74,10 +48,7 @@ __global__ void cv_equalize_lut_kernel(const u32* hist, u8* lut, int nframes, in
     cv_equalize_table(hist + ((int64_t)f * c + ch) * 256, lut + ((int64_t)f * c + ch) * 256);
 }
 
-static inline unsigned cs_grid(int64_t total) {
-    int64_t b = (total + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+constexpr unsigned PIXEL3_GRID_CAP = 8192;   // most workgroups of a pixel3_map_kernel launch
 
 } // namespace imgxf
 
@@ -92,7 +63,7 @@ IMGXF_API int imgxf_rgb2yuv_u8(const imgxf_view* src, const imgxf_view* dst, voi
     if (!same_geometry(src, dst) || src->c != 3) return IMGXF_ERR_SHAPE;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
-    hipLaunchKernelGGL((pixel3_map_kernel<Rgb2Yuv>), dim3(cs_grid((int64_t)d.n * d.h * ((d.w + 15) >> 4))), dim3(256), 0,
+    hipLaunchKernelGGL((pixel3_map_kernel<Rgb2Yuv>), dim3(grid_for((int64_t)d.n * d.h * ((d.w + 15) >> 4), PIXEL3_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, make_view(src), d, Rgb2Yuv());
     return launch_status();
 }
@@ -103,7 +74,7 @@ IMGXF_API int imgxf_yuv2rgb_u8(const imgxf_view* src, const imgxf_view* dst, voi
     if (!same_geometry(src, dst) || src->c != 3) return IMGXF_ERR_SHAPE;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
-    hipLaunchKernelGGL((pixel3_map_kernel<Yuv2Rgb>), dim3(cs_grid((int64_t)d.n * d.h * ((d.w + 15) >> 4))), dim3(256), 0,
+    hipLaunchKernelGGL((pixel3_map_kernel<Yuv2Rgb>), dim3(grid_for((int64_t)d.n * d.h * ((d.w + 15) >> 4), PIXEL3_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, make_view(src), d, Yuv2Rgb());
     return launch_status();
 }

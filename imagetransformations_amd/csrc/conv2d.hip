@@ -112,10 +112,8 @@ __global__ __launch_bounds__(256) void filter3x3_kernel(View s, View d, K9 K) {
     const int rowbytes = s.w * C;
     const int nq = (rowbytes + 3) >> 2;
     const int64_t total = (int64_t)s.n * s.h * nq;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int qd = (int)(t % nq);
-        const int64_t r = t / nq;
-        const int y = (int)(r % s.h), f = (int)(r / s.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [qd, y, f] = row_item(t, nq, s.h);
         const u8* r0 = s.row(f, y);
         const bool inner_row = y > 0 && y < s.h - 1 && s.w >= 3;
         const u8* rm = inner_row ? s.row(f, y - 1) : r0;
@@ -139,10 +137,8 @@ __global__ __launch_bounds__(256) void filter3x3_rows16_kernel(View s, View d, K
     const int rowbytes = s.w * C;
     const int nch = (rowbytes + 15) >> 4;
     const int64_t total = (int64_t)s.n * s.h * nch;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nch);
-        const int64_t r = t / nch;
-        const int y = (int)(r % s.h), f = (int)(r / s.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nch, s.h);
         const int b0 = ck << 4;
         const u8* r0 = s.row(f, y);
         u8* dp = d.row(f, y);
@@ -198,10 +194,8 @@ __global__ __launch_bounds__(256) void box_pass_kernel(View s, View d, int radiu
     const int C = s.c;
     const int rowbytes = s.w * C;
     const int64_t total = (int64_t)s.n * s.h * rowbytes;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int b = (int)(t % rowbytes);
-        const int64_t r = t / rowbytes;
-        const int y = (int)(r % s.h), f = (int)(r / s.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [b, y, f] = row_item(t, rowbytes, s.h);
         u32 acc = 0, far;
         if (!vertical) {
             const u8* rp = s.row(f, y);
@@ -227,8 +221,8 @@ constexpr int BOX_RMAX = 10;    // round 3: up to the radii of TransformationPoo
 __global__ __launch_bounds__(256) void box_v16_kernel(View s, View d, int radius, u32 ww, u32 fw) {
     const int nch = (int)(s.rowbytes() >> 4);
     const int64_t total = (int64_t)s.n * s.h * nch;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nch);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const int ck = (int)(t % nch);                        // (spelled out: row_item() changes this loop's assembly)
         const int64_t r = t / nch;
         const int y = (int)(r % s.h), f = (int)(r / s.h);
         u32 ae[4] = {0u, 0u, 0u, 0u}, ao[4] = {0u, 0u, 0u, 0u};          // even / odd bytes as 16-bit pairs
@@ -264,8 +258,8 @@ constexpr int BOX_VRUN = 32;
 __global__ __launch_bounds__(256) void box_v16_run_kernel(View s, View d, int radius, u32 ww, u32 fw) {
     const int nch = (int)(s.rowbytes() >> 4), nruns = (s.h + BOX_VRUN - 1) / BOX_VRUN;
     const int64_t total = (int64_t)s.n * nruns * nch;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nch);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const int ck = (int)(t % nch);                        // (spelled out, as above)
         const int64_t r = t / nch;
         const int run = (int)(r % nruns), f = (int)(r / nruns);
         const int ya = run * BOX_VRUN, yb = min(s.h, ya + BOX_VRUN);
@@ -313,8 +307,8 @@ __global__ __launch_bounds__(256) void box_h16_kernel(View s, View d, u32 ww, u3
     const int rowbytes = s.w * C;
     const int nch = (rowbytes + 15) >> 4;
     const int64_t total = (int64_t)s.n * s.h * nch;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nch);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const int ck = (int)(t % nch);                        // (spelled out, as above)
         const int64_t r = t / nch;
         const int y = (int)(r % s.h), f = (int)(r / s.h);
         const int b0 = ck << 4;
@@ -402,8 +396,7 @@ IMGXF_API int imgxf_box_blur_u8(const imgxf_view* src, const imgxf_view* dst, fl
         }
         return IMGXF_OK;
     }
-    int64_t blocks = ((int64_t)need + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    const unsigned blocks = grid_for((int64_t)need, 16384);          // box_pass_kernel; the 16-byte kernels: at most 32768
     View cur = s;
     int done = 0;
     for (int axis = 0; axis < 2; ++axis) {
@@ -417,13 +410,12 @@ IMGXF_API int imgxf_box_blur_u8(const imgxf_view* src, const imgxf_view* dst, fl
             const bool to_dst = ((total_passes - 1 - done) & 1) == 0;
             const View out = to_dst ? d : ws;
             // wide-lane kernels for 16-byte aligned images and the radii GaussianBlur produces (radius <= 4)
-            const bool al16 = ((((uintptr_t)cur.p) | (uintptr_t)cur.rs | (uintptr_t)cur.fs | ((uintptr_t)out.p) | (uintptr_t)out.rs | (uintptr_t)out.fs) & 15) == 0 &&
-                              s.rowbytes() % 16 == 0 && s.rowbytes() >= 48 && !knob_set(K_BOX_BYTES);
-            const unsigned b16 = (unsigned)std::min<int64_t>(32768, ((int64_t)s.n * s.h * (s.rowbytes() >> 4) + 255) / 256);
+            const bool al16 = aligned(cur, out, 16) && s.rowbytes() % 16 == 0 && s.rowbytes() >= 48 && !knob_set(K_BOX_BYTES);
+            const unsigned b16 = grid_for((int64_t)s.n * s.h * (s.rowbytes() >> 4), 32768);
             bool launched = false;
             if (al16 && radius <= BOX_RMAX) {
                 if (axis == 1 && !knob_set(K_NO_FAST_LEFTOVERS)) {
-                    const unsigned bv = (unsigned)std::min<int64_t>(32768, ((int64_t)s.n * ((s.h + BOX_VRUN - 1) / BOX_VRUN) * (s.rowbytes() >> 4) + 255) / 256);
+                    const unsigned bv = grid_for((int64_t)s.n * ((s.h + BOX_VRUN - 1) / BOX_VRUN) * (s.rowbytes() >> 4), 32768);
                     hipLaunchKernelGGL(box_v16_run_kernel, dim3(bv), dim3(256), 0, st, cur, out, radius, ww, fw); launched = true;
                 }
                 else if (axis == 1) { hipLaunchKernelGGL(box_v16_kernel, dim3(b16), dim3(256), 0, st, cur, out, radius, ww, fw); launched = true; }
@@ -432,7 +424,7 @@ IMGXF_API int imgxf_box_blur_u8(const imgxf_view* src, const imgxf_view* dst, fl
                 else if (s.c == 4) launched = launch_box_h16<4>(cur, out, radius, ww, fw, b16, st);
             }
             if (!launched)
-                hipLaunchKernelGGL(box_pass_kernel, dim3((unsigned)blocks), dim3(256), 0, st, cur, out, radius, ww, fw, axis);
+                hipLaunchKernelGGL(box_pass_kernel, dim3(blocks), dim3(256), 0, st, cur, out, radius, ww, fw, axis);
             cur = out;
             ++done;
         }
@@ -457,22 +449,17 @@ IMGXF_API int imgxf_filter3x3_u8(const imgxf_view* src, const imgxf_view* dst, c
     if (empty_view(src)) return IMGXF_OK;
     const K9 K = filter3x3_taps(kernel9, scale, offset);
     const View s = make_view(src), d = make_view(dst);
-    if (((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0 &&
-        s.rowbytes() >= 48 && !knob_set(K_FILTER3X3_BYTES)) {
-        const int64_t total16 = (int64_t)s.n * s.h * ((s.rowbytes() + 15) >> 4);
-        int64_t blocks16 = (total16 + 255) / 256;
-        if (blocks16 > 32768) blocks16 = 32768;
+    if (aligned(s, d, 16) && s.rowbytes() >= 48 && !knob_set(K_FILTER3X3_BYTES)) {
+        const unsigned blocks16 = grid_for((int64_t)s.n * s.h * ((s.rowbytes() + 15) >> 4), 32768);
         switch (s.c) {
-            case 1: hipLaunchKernelGGL((filter3x3_rows16_kernel<1>), dim3((unsigned)blocks16), dim3(256), 0, (hipStream_t)stream, s, d, K); return launch_status();
-            case 3: hipLaunchKernelGGL((filter3x3_rows16_kernel<3>), dim3((unsigned)blocks16), dim3(256), 0, (hipStream_t)stream, s, d, K); return launch_status();
-            case 4: hipLaunchKernelGGL((filter3x3_rows16_kernel<4>), dim3((unsigned)blocks16), dim3(256), 0, (hipStream_t)stream, s, d, K); return launch_status();
+            case 1: hipLaunchKernelGGL((filter3x3_rows16_kernel<1>), dim3(blocks16), dim3(256), 0, (hipStream_t)stream, s, d, K); return launch_status();
+            case 3: hipLaunchKernelGGL((filter3x3_rows16_kernel<3>), dim3(blocks16), dim3(256), 0, (hipStream_t)stream, s, d, K); return launch_status();
+            case 4: hipLaunchKernelGGL((filter3x3_rows16_kernel<4>), dim3(blocks16), dim3(256), 0, (hipStream_t)stream, s, d, K); return launch_status();
             default: break;
         }
     }
-    const int64_t total = (int64_t)s.n * s.h * ((s.rowbytes() + 3) >> 2);
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(filter3x3_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, s, d, K);
+    const unsigned blocks = grid_for((int64_t)s.n * s.h * ((s.rowbytes() + 3) >> 2), 16384);
+    hipLaunchKernelGGL(filter3x3_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s, d, K);
     return launch_status();
 }
 

@@ -17,11 +17,9 @@ __global__ __launch_bounds__(256) void fill_kernel(View d, FillPat pat) {
     const int rowbytes = d.w * d.c;
     const int nchunks = (rowbytes + 15) >> 4;
     const int64_t total = (int64_t)d.n * d.h * nchunks;
-    const bool al = ((((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    const bool al = ((((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0;   // (aligned(d, 16) swaps two operands here)
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, d.h);
         const int xb = ck << 4;
         u8* dp = d.row(f, y) + xb;
         const int nv = min(16, rowbytes - xb);
@@ -46,10 +44,8 @@ __global__ __launch_bounds__(256) void copy_rect_kernel(View s, View d, int sxb,
                                                         int dy, int rbytes, int rh) {
     const int nchunks = (rbytes + 30) >> 4;                   // a row's run touches at most this many aligned blocks
     const int64_t total = (int64_t)d.n * rh * nchunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % rh), f = (int)(r / rh);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, rh);
         const u8* sp0 = s.row(f, sy + y) + sxb;
         u8* dp0 = d.row(f, dy + y) + dxb;
         const int lead = (int)((uintptr_t)dp0 & 15);          // bytes of the run's first block that precede it
@@ -69,12 +65,10 @@ __global__ __launch_bounds__(256) void translate_kernel(View s, View d, int dxb,
     const int rowbytes = d.w * d.c;
     const int nchunks = (rowbytes + 15) >> 4;
     const int64_t total = (int64_t)d.n * d.h * nchunks;
-    const bool al = ((((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0;
+    const bool al = aligned(d, 16);
     const int c0 = max(dxb, 0), c1 = min(rowbytes, rowbytes + dxb);      // destination bytes that have a source
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, d.h);
         const int xb = ck << 4;
         u8* dp = d.row(f, y) + xb;
         const int nv = min(16, rowbytes - xb);
@@ -100,10 +94,8 @@ __global__ __launch_bounds__(256) void translate_kernel(View s, View d, int dxb,
 // dst(y,x) = src(sy,sx) with quarter turns counter-clockwise (PIL ROTATE_90 = ccw)
 __global__ __launch_bounds__(256) void rot90_kernel(View s, View d, int turns) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         int sx, sy;
         if (turns == 1) { sx = s.w - 1 - y; sy = x; }            // np.rot90(a, 1)
         else if (turns == 2) { sx = s.w - 1 - x; sy = s.h - 1 - y; }
@@ -158,10 +150,8 @@ __global__ __launch_bounds__(256) void rot90_tile_kernel(View s, View d, int tur
 // Image.transpose(FLIP_LEFT_RIGHT / FLIP_TOP_BOTTOM): dst(y,x) = src(y, w-1-x) or src(h-1-y, x)
 __global__ __launch_bounds__(256) void flip_kernel(View s, View d, int mode) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         const int sx = mode == 0 ? s.w - 1 - x : x, sy = mode == 0 ? y : s.h - 1 - y;
         const u8* sp = s.row(f, sy) + sx * s.c;
         u8* dp = d.row(f, y) + x * d.c;
@@ -179,10 +169,8 @@ __global__ __launch_bounds__(256) void flip_rows_kernel(View s, View d) {
     const int rowbytes = d.w * d.c;
     const int nchunks = (rowbytes + 30) >> 4;
     const int64_t total = (int64_t)d.n * d.h * nchunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, d.h);
         const u8* sp0 = s.row(f, s.h - 1 - y);
         u8* dp0 = d.row(f, y);
         const int lead = (int)((uintptr_t)dp0 & 15);
@@ -196,10 +184,8 @@ __global__ __launch_bounds__(256) void flip_rows_kernel(View s, View d) {
 __global__ __launch_bounds__(256) void mirror_rgb4_kernel(View s, View d, int rows) {
     const int G = d.w >> 2;
     const int64_t total = (int64_t)d.n * d.h * G;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int g = (int)(t % G);
-        const int64_t r = t / G;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [g, y, f] = row_item(t, G, d.h);
         const u32x3_a4 v = *(const u32x3_a4*)(s.row(f, rows ? s.h - 1 - y : y) + 12 * (G - 1 - g));
         const u32 a = v.x, b = v.y, c = v.z;
         u32x3_a4 o;
@@ -210,14 +196,10 @@ __global__ __launch_bounds__(256) void mirror_rgb4_kernel(View s, View d, int ro
     }
 }
 
-static inline unsigned grid_for(int64_t total) {
-    int64_t blocks = (total + 255) / 256;
-    return (unsigned)(blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks));
-}
+constexpr unsigned ROW_GRID_CAP = 8192;     // most workgroups of a launch of the row-walking kernels above
 
 static inline bool mirror_rgb4_ok(const View& s, const View& d) {
-    return d.c == 3 && (d.w & 3) == 0 &&
-           ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 3) == 0;
+    return d.c == 3 && (d.w & 3) == 0 && aligned(s, d, 4);
 }
 
 } // namespace imgxf
@@ -234,7 +216,7 @@ IMGXF_API int imgxf_fill_u8(const imgxf_view* dst, const uint8_t* color, void* s
     memcpy(&pat, bytes, sizeof(bytes));
     const View d = make_view(dst);
     const int64_t total = (int64_t)d.n * d.h * ((d.rowbytes() + 15) >> 4);
-    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, d, pat);
+    hipLaunchKernelGGL(fill_kernel, dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, d, pat);
     return launch_status();
 }
 
@@ -248,7 +230,7 @@ IMGXF_API int imgxf_copy_rect_u8(const imgxf_view* src, const imgxf_view* dst, i
     if (rw == 0 || rh == 0 || dst->n == 0) return IMGXF_OK;
     const int c = src->c;
     const int64_t total = (int64_t)dst->n * rh * (((int64_t)rw * c + 30) >> 4);
-    hipLaunchKernelGGL(copy_rect_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(copy_rect_kernel, dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        make_view(src), make_view(dst), sx * c, sy, dx * c, dy, rw * c, rh);
     return launch_status();
 }
@@ -267,7 +249,7 @@ IMGXF_API int imgxf_translate_u8(const imgxf_view* src, const imgxf_view* dst, i
     memcpy(&pat, bytes, sizeof(bytes));
     const View s = make_view(src), d = make_view(dst);
     const int64_t total = (int64_t)d.n * d.h * ((d.rowbytes() + 15) >> 4);
-    hipLaunchKernelGGL(translate_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, s, d, dx * src->c, dy, pat);
+    hipLaunchKernelGGL(translate_kernel, dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, s, d, dx * src->c, dy, pat);
     return launch_status();
 }
 
@@ -283,7 +265,7 @@ IMGXF_API int imgxf_rot90_u8(const imgxf_view* src, const imgxf_view* dst, int q
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
     if (quarter_turns_ccw == 2 && mirror_rgb4_ok(make_view(src), d)) {
-        hipLaunchKernelGGL(mirror_rgb4_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 2))), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(mirror_rgb4_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 2), ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                            make_view(src), d, 1);
         return launch_status();
     }
@@ -301,7 +283,7 @@ IMGXF_API int imgxf_rot90_u8(const imgxf_view* src, const imgxf_view* dst, int q
             return launch_status();
         }
     }
-    hipLaunchKernelGGL(rot90_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0,
+    hipLaunchKernelGGL(rot90_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, make_view(src), d, quarter_turns_ccw);
     return launch_status();
 }
@@ -314,15 +296,15 @@ IMGXF_API int imgxf_flip_u8(const imgxf_view* src, const imgxf_view* dst, int mo
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst), s = make_view(src);
     if (mode == 1) {
-        hipLaunchKernelGGL(flip_rows_kernel, dim3(grid_for((int64_t)d.n * d.h * ((d.rowbytes() + 30) >> 4))), dim3(256), 0,
+        hipLaunchKernelGGL(flip_rows_kernel, dim3(grid_for((int64_t)d.n * d.h * ((d.rowbytes() + 30) >> 4), ROW_GRID_CAP)), dim3(256), 0,
                            (hipStream_t)stream, s, d);
         return launch_status();
     }
     if (mirror_rgb4_ok(s, d)) {
-        hipLaunchKernelGGL(mirror_rgb4_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 2))), dim3(256), 0, (hipStream_t)stream, s, d, 0);
+        hipLaunchKernelGGL(mirror_rgb4_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 2), ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, s, d, 0);
         return launch_status();
     }
-    hipLaunchKernelGGL(flip_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0,
+    hipLaunchKernelGGL(flip_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, s, d, mode);
     return launch_status();
 }

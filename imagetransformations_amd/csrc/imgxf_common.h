@@ -50,6 +50,82 @@ inline bool same_nhw(const imgxf_view* a, const imgxf_view* b) {
 }
 inline bool empty_view(const imgxf_view* v) { return v->n == 0 || v->h == 0 || v->w == 0; }
 
+// ---- the scaffolding of the per-pixel kernels, one definition of each rule ----
+// base address, row stride and frame stride are multiples of `bytes` (a power of two)
+__host__ __device__ __forceinline__ bool aligned(const View& v, int bytes) {
+    return ((((uintptr_t)v.p) | (uintptr_t)v.rs | (uintptr_t)v.fs) & (uintptr_t)(bytes - 1)) == 0;
+}
+__host__ __device__ __forceinline__ bool aligned(const View& a, const View& b, int bytes) {     // both views: one test
+    return ((((uintptr_t)a.p) | (uintptr_t)a.rs | (uintptr_t)a.fs | ((uintptr_t)b.p) | (uintptr_t)b.rs | (uintptr_t)b.fs) &
+            (uintptr_t)(bytes - 1)) == 0;
+}
+inline bool aligned(const imgxf_view* v, int bytes) {       // the f32 / f64 side inputs, before make_view
+    return ((((uintptr_t)v->data) | (uintptr_t)v->row_stride | (uintptr_t)v->frame_stride) & (uintptr_t)(bytes - 1)) == 0;
+}
+
+// workgroups of 256 lanes for a grid-stride walk over `total` items: at least 1, at most `cap` (every launch names its own)
+inline unsigned grid_for(int64_t total, unsigned cap) {
+    const int64_t blocks = (total + 255) / 256;
+    return (unsigned)(blocks > (int64_t)cap ? (int64_t)cap : (blocks < 1 ? 1 : blocks));
+}
+
+// the walk itself, in 64 bits:  for (int64_t t = walk_first(); t < total; t += walk_stride())
+__device__ __forceinline__ int64_t walk_first() { return (int64_t)blockIdx.x * 256 + threadIdx.x; }
+__device__ __forceinline__ int64_t walk_stride() { return (int64_t)gridDim.x * 256; }
+// t -> (item in its row, row, frame) for `per_row` items per row and h rows per frame; without the frame when
+// blockIdx.y names it
+struct RowItem { int i, y, f; };
+struct RowItem2 { int i, y; };
+__device__ __forceinline__ RowItem row_item(int64_t t, int per_row, int h) {
+    const int i = (int)(t % per_row);
+    const int64_t r = t / per_row;
+    return RowItem{i, (int)(r % h), (int)(r / h)};
+}
+__device__ __forceinline__ RowItem2 row_item(int64_t t, int per_row) {
+    return RowItem2{(int)(t % per_row), (int)(t / per_row)};
+}
+
+// A lane's chunk of a row, 4 NDW bytes at p of which the row holds the first `nbytes`, into the dwords v[] and back.
+// `vec` is the caller's test (a full chunk, every pointer of the lane 16-byte aligned): uint4 accesses.  Otherwise the
+// bytes go one by one, missing ones read as 0; v[] is indexed through a static unroll, since a dynamic register
+// index would move the array to scratch.
+template <int NDW>
+__device__ __forceinline__ void load_chunk(const u8* p, int nbytes, bool vec, u32 (&v)[NDW]) {
+    static_assert(NDW % 4 == 0, "whole uint4");
+    if (vec) {
+#pragma unroll
+        for (int k = 0; k < NDW / 4; ++k) {
+            const uint4 q = ((const uint4*)p)[k];
+            v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NDW; ++k) v[k] = 0;
+        for (int e = 0; e < nbytes; ++e) {
+            const u32 x = p[e];
+#pragma unroll
+            for (int k = 0; k < NDW; ++k)
+                if ((e >> 2) == k) v[k] |= x << (8 * (e & 3));
+        }
+    }
+}
+template <int NDW>
+__device__ __forceinline__ void store_chunk(u8* p, int nbytes, bool vec, const u32 (&v)[NDW]) {
+    static_assert(NDW % 4 == 0, "whole uint4");
+    if (vec) {
+#pragma unroll
+        for (int k = 0; k < NDW / 4; ++k) ((uint4*)p)[k] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+    } else {
+        for (int e = 0; e < nbytes; ++e) {
+            u32 w = 0;
+#pragma unroll
+            for (int k = 0; k < NDW; ++k)
+                if ((e >> 2) == k) w = v[k];
+            p[e] = (u8)(w >> (8 * (e & 3)));
+        }
+    }
+}
+
 // libImaging affine_fixed: the NEAREST matrix in 16.16 fixed point, the half-pixel offsets folded
 // into the constants (imgxf_affine_u8, imgxf_augmix_f32)
 inline int fix16(double v) {

@@ -68,10 +68,8 @@ template <int C>
 __global__ __launch_bounds__(256) void resample_h_kernel(View s, View d, const int* bounds,
                                                          const int* kk, int ksize) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int xx = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [xx, y, f] = row_item(t, d.w, d.h);
         const int xmin = bounds[2 * xx], cnt = bounds[2 * xx + 1];
         const int* k = kk + (int64_t)xx * ksize;
         const u8* sp = s.row(f, y) + xmin * C;
@@ -94,10 +92,8 @@ __global__ __launch_bounds__(256) void resample_v_kernel(View s, View d, const i
                                                          const int* kk, int ksize) {
     const int rowbytes = d.w * d.c;
     const int64_t total = (int64_t)d.n * d.h * rowbytes;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int xb = (int)(t % rowbytes);
-        const int64_t r = t / rowbytes;
-        const int yy = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [xb, yy, f] = row_item(t, rowbytes, d.h);
         const int ymin = bounds[2 * yy], cnt = bounds[2 * yy + 1];
         const int* k = kk + (int64_t)yy * ksize;
         int acc = 1 << (PRECISION_BITS - 1);
@@ -363,10 +359,7 @@ __global__ __launch_bounds__(256) void resample_v4_kernel(View s, View d, const 
 
 #include "resample_mfma.inc"
 
-static inline unsigned grid_for(int64_t total) {
-    int64_t blocks = (total + 255) / 256;
-    return (unsigned)(blocks > 16384 ? 16384 : (blocks < 1 ? 1 : blocks));
-}
+constexpr unsigned GENERIC_GRID_CAP = 16384;   // most workgroups of a resample_h_kernel / resample_v_kernel launch
 
 static int launch_h_lds(const imgxf_lanczos_plan* p, const View& s, const View& d, hipStream_t st) {
     const int rpb = 32;
@@ -410,7 +403,7 @@ constexpr int RS_MF_WAVES = 4;
 // the fused kernel reads and writes dwords at 4-byte aligned addresses and keeps row offsets in 32 bits
 static bool rs_mf_ok(const imgxf_lanczos_plan* p, const View& s, const View& d) {
     if (!p->mf_nkh) return false;
-    if (((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | ((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 3) != 0) return false;
+    if (!aligned(s, d, 4)) return false;
     // the workgroup count of the launch (RS_MF_WAVES column groups per workgroup) must fit the grid: decided HERE so
     // that the workspace query and the run agree and an oversized call takes the two-pass path with its intermediate
     // 
@@ -441,7 +434,7 @@ static int launch_rs_mf(const imgxf_lanczos_plan* p, const View& s, const View& 
 }
 
 static int launch_h(const View& s, const View& d, const int* b, const int* k, int ks, hipStream_t st) {
-    const unsigned g = grid_for((int64_t)d.n * d.h * d.w);
+    const unsigned g = grid_for((int64_t)d.n * d.h * d.w, GENERIC_GRID_CAP);
     switch (s.c) {
         case 1: hipLaunchKernelGGL((resample_h_kernel<1>), dim3(g), dim3(256), 0, st, s, d, b, k, ks); break;
         case 3: hipLaunchKernelGGL((resample_h_kernel<3>), dim3(g), dim3(256), 0, st, s, d, b, k, ks); break;
@@ -772,7 +765,7 @@ static int run_resample(const imgxf_lanczos_plan* p, const imgxf_view* src, cons
     if (r.v == IMGXF_ROUTE_V_V4) return launch_v4(p, mid, d, st);
     if (r.v == IMGXF_ROUTE_V_FAST) return launch_v_fast(p, mid, d, st);
     const int64_t total = (int64_t)d.n * d.h * d.rowbytes();
-    hipLaunchKernelGGL(resample_v_kernel, dim3(grid_for(total)), dim3(256), 0, st, mid, d,
+    hipLaunchKernelGGL(resample_v_kernel, dim3(grid_for(total, GENERIC_GRID_CAP)), dim3(256), 0, st, mid, d,
                        p->d_bounds_y, p->d_kk_y, p->ksy);
     return launch_status();
 }

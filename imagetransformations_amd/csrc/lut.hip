@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void chist_kernel(View s, u32* hist) {
     u32* hs = h + (threadIdx.x & (NS - 1)) * C * 256;
     const int rowbytes = s.w * C;
     const int64_t total = (int64_t)s.h * rowbytes;
-    const bool vec = (rowbytes % 4 == 0) && ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs) & 3) == 0;
+    const bool vec = (rowbytes % 4 == 0) && aligned(s, 4);
     if (vec && (int64_t)s.h * (rowbytes >> 2) < 0x7fffffff) {
         const u32 rowwords = (u32)rowbytes >> 2, words = (u32)s.h * rowwords;       // 32-bit index arithmetic
         for (u32 t = blockIdx.x * 256u + threadIdx.x; t < words; t += gridDim.x * 256u) {
@@ -37,8 +37,8 @@ __global__ __launch_bounds__(256) void chist_kernel(View s, u32* hist) {
     } else if (vec) {
         const int rowwords = rowbytes >> 2;
         const int64_t words = (int64_t)s.h * rowwords;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < words; t += (int64_t)gridDim.x * 256) {
-            const int xw = (int)(t % rowwords), y = (int)(t / rowwords);
+        for (int64_t t = walk_first(); t < words; t += walk_stride()) {
+            const auto [xw, y] = row_item(t, rowwords);
             const u32 v = ((const u32*)s.row(f, y))[xw];
             int ch = (xw * 4) % C;
 #pragma unroll
@@ -48,8 +48,8 @@ __global__ __launch_bounds__(256) void chist_kernel(View s, u32* hist) {
             }
         }
     } else {
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-            const int xb = (int)(t % rowbytes), y = (int)(t / rowbytes);
+        for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+            const auto [xb, y] = row_item(t, rowbytes);
             atomicAdd(&hs[(xb % C) * 256 + s.row(f, y)[xb]], 1u);
         }
     }
@@ -100,10 +100,8 @@ __global__ __launch_bounds__(256) void lut_apply_kernel(View s, View d, const u8
     for (int i = threadIdx.x; i < C * 256; i += 256) tab[i] = dev ? dev[(int64_t)f * C * 256 + i] : arg.t[i];
     __syncthreads();
     const int rowbytes = d.w * C;
-    const bool vec = (rowbytes % 4 == 0) &&
-                     ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | (uintptr_t)d.p | (uintptr_t)d.rs | (uintptr_t)d.fs) & 3) == 0;
-    const bool vec16 = (rowbytes % 16 == 0) && (int64_t)d.h * (rowbytes >> 4) < 0x7fffffff &&
-                       ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | (uintptr_t)d.p | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0;
+    const bool vec = (rowbytes % 4 == 0) && aligned(s, d, 4);
+    const bool vec16 = (rowbytes % 16 == 0) && (int64_t)d.h * (rowbytes >> 4) < 0x7fffffff && aligned(s, d, 16);
     if (vec16) {
         // 16 bytes per lane and 32-bit index arithmetic (the dword loop below spends more on its 64-bit
         // division per 4 bytes than on the look-ups); the table's 64 dwords sit in 64 different banks, so the
@@ -130,8 +128,8 @@ __global__ __launch_bounds__(256) void lut_apply_kernel(View s, View d, const u8
     } else if (vec) {
         const int rowwords = rowbytes >> 2;
         const int64_t words = (int64_t)d.h * rowwords;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < words; t += (int64_t)gridDim.x * 256) {
-            const int xw = (int)(t % rowwords), y = (int)(t / rowwords);
+        for (int64_t t = walk_first(); t < words; t += walk_stride()) {
+            const auto [xw, y] = row_item(t, rowwords);
             const u32 v = ((const u32*)s.row(f, y))[xw];
             int ch = (xw * 4) % C;
             u32 o = 0;
@@ -144,17 +142,14 @@ __global__ __launch_bounds__(256) void lut_apply_kernel(View s, View d, const u8
         }
     } else {
         const int64_t total = (int64_t)d.h * rowbytes;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-            const int xb = (int)(t % rowbytes), y = (int)(t / rowbytes);
+        for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+            const auto [xb, y] = row_item(t, rowbytes);
             d.row(f, y)[xb] = tab[(xb % C) * 256 + s.row(f, y)[xb]];
         }
     }
 }
 
-static inline unsigned blocks_for(int64_t items) {
-    int64_t b = (items + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
+constexpr unsigned LUT_GRID_CAP = 2048;     // most workgroups PER FRAME (grid.y) of a lut_apply_kernel launch
 
 } // namespace imgxf
 
@@ -171,10 +166,8 @@ IMGXF_API int imgxf_channel_histogram_u8(const imgxf_view* src, uint32_t* hist, 
     const View s = make_view(src);
     if (s.n > 65535) return IMGXF_ERR_SHAPE;
     // (c * 256 global atomics per workgroup: a few thousand workgroups per launch, not per frame)
-    unsigned hb = blocks_for((int64_t)s.h * s.rowbytes() / 16);
     const unsigned hcap = (unsigned)(4096 / s.n < 32 ? 32 : (4096 / s.n > 512 ? 512 : 4096 / s.n));
-    if (hb > hcap) hb = hcap;
-    hipLaunchKernelGGL(chist_kernel, dim3(hb, (unsigned)s.n), dim3(256), 0, st, s, hist);
+    hipLaunchKernelGGL(chist_kernel, dim3(grid_for((int64_t)s.h * s.rowbytes() / 16, hcap), (unsigned)s.n), dim3(256), 0, st, s, hist);
     return launch_status();
 }
 
@@ -189,7 +182,7 @@ IMGXF_API int imgxf_lut_u8(const imgxf_view* src, const imgxf_view* dst, const u
     LutArg arg;
     memset(&arg, 0, sizeof(arg));
     memcpy(arg.t, lut, (size_t)d.c * 256);
-    hipLaunchKernelGGL(lut_apply_kernel, dim3(blocks_for((int64_t)d.h * d.rowbytes() / 16), (unsigned)d.n), dim3(256), 0,
+    hipLaunchKernelGGL(lut_apply_kernel, dim3(grid_for((int64_t)d.h * d.rowbytes() / 16, LUT_GRID_CAP), (unsigned)d.n), dim3(256), 0,
                        (hipStream_t)stream, s, d, (const u8*)nullptr, arg);
     return launch_status();
 }
@@ -212,7 +205,7 @@ IMGXF_API int imgxf_equalize_u8(const imgxf_view* src, const imgxf_view* dst, vo
     hipLaunchKernelGGL(equalize_lut_kernel, dim3((unsigned)((ntab + 63) / 64)), dim3(64), 0, st, hist, lut, (int)ntab);
     LutArg arg;
     memset(&arg, 0, sizeof(arg));
-    hipLaunchKernelGGL(lut_apply_kernel, dim3(blocks_for((int64_t)d.h * d.rowbytes() / 16), (unsigned)d.n), dim3(256), 0, st,
+    hipLaunchKernelGGL(lut_apply_kernel, dim3(grid_for((int64_t)d.h * d.rowbytes() / 16, LUT_GRID_CAP), (unsigned)d.n), dim3(256), 0, st,
                        s, d, (const u8*)lut, arg);
     return launch_status();
 }
@@ -224,7 +217,7 @@ extern "C" __attribute__((visibility("hidden"))) int imgxf_lut_device_u8(const i
     if (d.n > 65535) return IMGXF_ERR_SHAPE;
     LutArg arg;
     memset(&arg, 0, sizeof(arg));
-    hipLaunchKernelGGL(lut_apply_kernel, dim3(blocks_for((int64_t)d.h * d.rowbytes() / 16), (unsigned)d.n), dim3(256), 0,
+    hipLaunchKernelGGL(lut_apply_kernel, dim3(grid_for((int64_t)d.h * d.rowbytes() / 16, LUT_GRID_CAP), (unsigned)d.n), dim3(256), 0,
                        (hipStream_t)stream, s, d, (const u8*)lut_dev, arg);
     return launch_status();
 }

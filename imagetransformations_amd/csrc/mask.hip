@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void hist_kernel(View s, u32* hist) {
     __syncthreads();
     const int f = blockIdx.y;
     u32* hs = h[threadIdx.x & 7];
-    const bool vec = (s.w % 4 == 0) && ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs) & 3) == 0;
+    const bool vec = (s.w % 4 == 0) && aligned(s, 4);
     if (vec && (int64_t)s.h * (s.w >> 2) < 0x7fffffff) {
         const u32 rowwords = (u32)s.w >> 2, words = (u32)s.h * rowwords;              // 32-bit index arithmetic
         for (u32 t = blockIdx.x * 256u + threadIdx.x; t < words; t += gridDim.x * 256u) {
@@ -33,8 +33,8 @@ __global__ __launch_bounds__(256) void hist_kernel(View s, u32* hist) {
     } else if (vec) {
         const int rowwords = s.w >> 2;
         const int64_t words = (int64_t)s.h * rowwords;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < words; t += (int64_t)gridDim.x * 256) {
-            const int xw = (int)(t % rowwords), y = (int)(t / rowwords);
+        for (int64_t t = walk_first(); t < words; t += walk_stride()) {
+            const auto [xw, y] = row_item(t, rowwords);
             const u32 v = ((const u32*)s.row(f, y))[xw];
             atomicAdd(&hs[v & 0xffu], 1u);
             atomicAdd(&hs[(v >> 8) & 0xffu], 1u);
@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void hist_kernel(View s, u32* hist) {
         }
     } else {
         const int64_t total = (int64_t)s.h * s.w;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-            const int x = (int)(t % s.w), y = (int)(t / s.w);
+        for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+            const auto [x, y] = row_item(t, s.w);
             atomicAdd(&hs[s.row(f, y)[x]], 1u);
         }
     }
@@ -91,13 +91,12 @@ __global__ void percentile_kernel(const u32* hist, int nframes, int64_t count, d
 
 __global__ __launch_bounds__(256) void gt_mask_kernel(View s, View d, const double* thr) {
     // (double)e > thr  <=>  e > floor(thr) for integer e: compare bytes against an integer limit
-    const bool vec = (d.w % 4 == 0) &&
-                     ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs | (uintptr_t)d.p | (uintptr_t)d.rs | (uintptr_t)d.fs) & 3) == 0;
+    const bool vec = (d.w % 4 == 0) && aligned(s, d, 4);
     if (vec) {
         const int rowwords = d.w >> 2;
         const int64_t total = (int64_t)d.n * d.h * rowwords;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-            const int xw = (int)(t % rowwords);
+        for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+            const int xw = (int)(t % rowwords);               // (spelled out: row_item() changes this loop's assembly)
             const int64_t r = t / rowwords;
             const int y = (int)(r % d.h), f = (int)(r / d.h);
             const double th = thr[f];
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(256) void gt_mask_kernel(View s, View d, const doub
         return;
     }
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
         const int x = (int)(t % d.w);
         const int64_t r = t / d.w;
         const int y = (int)(r % d.h), f = (int)(r / d.h);
@@ -121,10 +120,8 @@ __global__ __launch_bounds__(256) void gt_mask_kernel(View s, View d, const doub
 
 __global__ __launch_bounds__(256) void dilate_kernel(View s, View d, int k) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         u8 hit = 0;
         for (int dy = -k; dy <= k && !hit; ++dy) {
             const int yy = y + dy;
@@ -220,10 +217,7 @@ __global__ __launch_bounds__(256) void dilate_march_kernel(View s, View d, int r
     }
 }
 
-static inline unsigned grid_for(int64_t total) {
-    int64_t blocks = (total + 255) / 256;
-    return (unsigned)(blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks));
-}
+constexpr unsigned ROW_GRID_CAP = 8192;     // most workgroups of a gt_mask_kernel or dilate_kernel launch
 
 } // namespace imgxf
 
@@ -241,11 +235,8 @@ IMGXF_API int imgxf_histogram_u8(const imgxf_view* src, uint32_t* hist, void* st
     const View s = make_view(src);
     // every workgroup ends with 256 global atomics, one per bin: with ~1000 workgroups per frame those
     // same-address atomics, not the reads, set the time.  A few thousand workgroups per launch fill the chip.
-    int64_t bx = ((int64_t)s.h * s.w + 256 * 16 - 1) / (256 * 16);
-    const int64_t cap = std::max<int64_t>(32, std::min<int64_t>(512, 4096 / s.n));
-    if (bx > cap) bx = cap;
-    if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(hist_kernel, dim3((unsigned)bx, (unsigned)s.n), dim3(256), 0, st, s, hist);
+    const unsigned cap = (unsigned)std::max(32, std::min(512, 4096 / s.n));
+    hipLaunchKernelGGL(hist_kernel, dim3(grid_for(((int64_t)s.h * s.w + 15) / 16, cap), (unsigned)s.n), dim3(256), 0, st, s, hist);
     return launch_status();
 }
 
@@ -261,7 +252,7 @@ IMGXF_API int imgxf_percentile_mask_u8(const imgxf_view* src, const uint32_t* hi
     hipLaunchKernelGGL(percentile_kernel, dim3((unsigned)((src->n + 63) / 64)), dim3(64), 0, st, hist,
                        src->n, (int64_t)src->h * src->w, q, thr_out);
     const View d = make_view(dst);
-    hipLaunchKernelGGL(gt_mask_kernel, dim3(grid_for((int64_t)d.n * d.h * ((d.w + 3) / 4))), dim3(256), 0, st,
+    hipLaunchKernelGGL(gt_mask_kernel, dim3(grid_for((int64_t)d.n * d.h * ((d.w + 3) / 4), ROW_GRID_CAP)), dim3(256), 0, st,
                        make_view(src), d, (const double*)thr_out);
     return launch_status();
 }
@@ -275,8 +266,7 @@ IMGXF_API int imgxf_dilate_cross_u8(const imgxf_view* src, const imgxf_view* dst
     if (empty_view(src)) return IMGXF_OK;
     const View d = make_view(dst), sv = make_view(src);
     const bool no_march = knob_set(K_NO_MARCH);
-    if (iterations == 3 && !no_march && d.w % 16 == 0 && d.w >= 64 && d.n <= 65535 &&
-        ((((uintptr_t)sv.p) | (uintptr_t)sv.rs | (uintptr_t)sv.fs | (uintptr_t)d.p | (uintptr_t)d.rs | (uintptr_t)d.fs) & 15) == 0) {
+    if (iterations == 3 && !no_march && d.w % 16 == 0 && d.w >= 64 && d.n <= 65535 && aligned(sv, d, 16)) {
         const int nstrips = (d.w + 991) / 992;
         int64_t nchunks = (d.h + 127) / 128;
         while (nchunks * ((nstrips + 3) / 4) * d.n < 2048 && (d.h + nchunks - 1) / nchunks > 32) nchunks *= 2;
@@ -288,7 +278,7 @@ IMGXF_API int imgxf_dilate_cross_u8(const imgxf_view* src, const imgxf_view* dst
             return launch_status();
         }
     }
-    hipLaunchKernelGGL(dilate_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0,
+    hipLaunchKernelGGL(dilate_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, sv, d, iterations);
     return launch_status();
 }

@@ -41,10 +41,8 @@ __global__ __launch_bounds__(256) void add_noise_philox_kernel(View s, View d, f
     const int rowbytes = d.w * d.c;
     const int nchunks = (rowbytes + 3) >> 2;
     const int64_t total = (int64_t)d.n * d.h * nchunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, d.h);
         const int xb = ck << 2, nv = min(4, rowbytes - xb);
         const u8* sp = s.row(f, y) + xb;
         u8* dp = d.row(f, y) + xb;
@@ -70,17 +68,14 @@ __global__ __launch_bounds__(256) void add_noise_philox_kernel(View s, View d, f
 }
 
 __global__ __launch_bounds__(256) void philox_u32_kernel(u32* out, int64_t nblocks4, u32 k0, u32 k1, uint64_t offset4) {
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nblocks4; t += (int64_t)gridDim.x * 256) {
+    for (int64_t t = walk_first(); t < nblocks4; t += walk_stride()) {
         const uint64_t ctr = (uint64_t)t + offset4;
         const Philox4 q = philox4x32_10((u32)ctr, (u32)(ctr >> 32), 0u, 0u, k0, k1);
         out[4 * t + 0] = q.x; out[4 * t + 1] = q.y; out[4 * t + 2] = q.z; out[4 * t + 3] = q.w;
     }
 }
 
-static unsigned noise_grid(int64_t total) {
-    const int64_t g = (total + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
-}
+constexpr unsigned PHILOX_GRID_CAP = 65536;   // most workgroups of a launch of the two Philox kernels above
 
 } // namespace imgxf
 
@@ -470,7 +465,7 @@ IMGXF_API int imgxf_add_noise_philox_u8(const imgxf_view* src, const imgxf_view*
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
     const int64_t total = (int64_t)d.n * d.h * ((d.rowbytes() + 3) >> 2);
-    hipLaunchKernelGGL(add_noise_philox_kernel, dim3(noise_grid(total)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(add_noise_philox_kernel, dim3(grid_for(total, PHILOX_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        make_view(src), d, sigma, (u32)seed, (u32)(seed >> 32), offset >> 2);
     return launch_status();
 }
@@ -479,7 +474,7 @@ IMGXF_API int imgxf_philox4x32_u32(void* dst_u32, int64_t count, uint64_t seed, 
     if (!dst_u32) return IMGXF_ERR_NULL;
     if (count < 0 || (count & 3) || (offset & 3)) return IMGXF_ERR_ARG;
     if (count == 0) return IMGXF_OK;
-    hipLaunchKernelGGL(philox_u32_kernel, dim3(noise_grid(count / 4)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(philox_u32_kernel, dim3(grid_for(count / 4, PHILOX_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        (u32*)dst_u32, count / 4, (u32)seed, (u32)(seed >> 32), offset >> 2);
     return launch_status();
 }

@@ -30,9 +30,8 @@ __global__ __launch_bounds__(PV_THREADS) void perspective_kernel(View s, View d,
     const int f = blockIdx.z;
     const PerspCoef& k = a.k[a.per_frame ? f : 0];
     const int fr = a.frame0 + f;
-    const bool src4 = ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs) & 3) == 0 &&
-                      s.rs * (int64_t)s.h < ((int64_t)1 << 32);       // 32-bit offsets within a frame
-    const bool dst4 = ((((uintptr_t)d.p) | (uintptr_t)d.rs | (uintptr_t)d.fs) & 3) == 0;
+    const bool src4 = aligned(s, 4) && s.rs * (int64_t)s.h < ((int64_t)1 << 32);       // 32-bit offsets within a frame
+    const bool dst4 = aligned(d, 4);
     const PvFrame sf = {s.row(fr, 0), s.rs, s.h, s.w, src4}, df = {d.row(fr, 0), d.rs, d.h, d.w, dst4};
     pv_tile<C>(sf, df, k, blockIdx.x * PV_TW, blockIdx.y * PV_TH, box, outt, boxinfo);
 }

@@ -24,15 +24,15 @@ __global__ __launch_bounds__(256) void map_rows_kernel(View a, View b, View d, O
     const int rowbytes = d.w * C;
     const int nchunks = (rowbytes + CB - 1) / CB;
     const int64_t total = (int64_t)d.n * d.h * nchunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, d.h);
         const int xb = ck * CB;
         const u8* ap = a.p ? a.row(f, y) + xb : nullptr;
         const u8* bp = b.p ? b.row(f, y) + xb : nullptr;
         u8* dp = d.row(f, y) + xb;
         const int nv = min(CB, rowbytes - xb);
+        // (not load_chunk / store_chunk: with them cv2.convertScaleAbs measured 3 % slower on 4K frames, Image.blend 5 %
+        // faster, profiles/pixel_scaffold.txt; the two images load in one loop here)
         u32 av[4 * NV], bv[4 * NV], ov[4 * NV];
         const bool vec = nv == CB && (((uintptr_t)dp | (uintptr_t)ap | (uintptr_t)bp) & 15) == 0;
         if (vec) {
@@ -105,13 +105,12 @@ static int launch_map(const View& a, const View& b, const View& d, const Op& op,
     const int cb = d.c == 3 ? 48 : 16;
     const int64_t total = (int64_t)d.n * d.h * ((d.rowbytes() + cb - 1) / cb);
     if (total == 0) return IMGXF_OK;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
+    const unsigned blocks = grid_for(total, 16384);
     switch (d.c) {
-        case 1: hipLaunchKernelGGL((map_rows_kernel<1, Op>), dim3((unsigned)blocks), dim3(256), 0, st, a, b, d, op); break;
-        case 2: hipLaunchKernelGGL((map_rows_kernel<2, Op>), dim3((unsigned)blocks), dim3(256), 0, st, a, b, d, op); break;
-        case 3: hipLaunchKernelGGL((map_rows_kernel<3, Op>), dim3((unsigned)blocks), dim3(256), 0, st, a, b, d, op); break;
-        default: hipLaunchKernelGGL((map_rows_kernel<4, Op>), dim3((unsigned)blocks), dim3(256), 0, st, a, b, d, op); break;
+        case 1: hipLaunchKernelGGL((map_rows_kernel<1, Op>), dim3(blocks), dim3(256), 0, st, a, b, d, op); break;
+        case 2: hipLaunchKernelGGL((map_rows_kernel<2, Op>), dim3(blocks), dim3(256), 0, st, a, b, d, op); break;
+        case 3: hipLaunchKernelGGL((map_rows_kernel<3, Op>), dim3(blocks), dim3(256), 0, st, a, b, d, op); break;
+        default: hipLaunchKernelGGL((map_rows_kernel<4, Op>), dim3(blocks), dim3(256), 0, st, a, b, d, op); break;
     }
     return launch_status();
 }
@@ -121,33 +120,15 @@ template <int C>
 __global__ __launch_bounds__(256) void rgb2l_kernel(View s, View d) {
     const int ngrp = (d.w + 15) >> 4;
     const int64_t total = (int64_t)d.n * d.h * ngrp;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int g = (int)(t % ngrp);
-        const int64_t r = t / ngrp;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [g, y, f] = row_item(t, ngrp, d.h);
         const int x0 = g << 4;
         const int np = min(16, d.w - x0);
         const u8* sp = s.row(f, y) + x0 * C;
         u8* dp = d.row(f, y) + x0;
         u32 in[4 * C];
         const bool vec = np == 16 && ((((uintptr_t)sp) | ((uintptr_t)dp)) & 15) == 0;
-        if (vec) {
-#pragma unroll
-            for (int b = 0; b < C; ++b) {
-                const uint4 q = *(const uint4*)(sp + 16 * b);
-                in[4 * b] = q.x; in[4 * b + 1] = q.y; in[4 * b + 2] = q.z; in[4 * b + 3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4 * C; ++k) in[k] = 0;
-            for (int e = 0; e < np * C; ++e) {
-                // dynamic register index avoided: build through a byte loop over a static unroll
-                const u32 v = sp[e];
-#pragma unroll
-                for (int k = 0; k < 4 * C; ++k)
-                    if ((e >> 2) == k) in[k] |= v << (8 * (e & 3));
-            }
-        }
+        load_chunk(sp, np * C, vec, in);
         u32 out[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int px = 0; px < 16; ++px) {
@@ -158,11 +139,7 @@ __global__ __launch_bounds__(256) void rgb2l_kernel(View s, View d) {
             const u32 L = luma_u8(R, G, B);
             out[px >> 2] |= L << (8 * (px & 3));
         }
-        if (vec) {
-            *(uint4*)dp = make_uint4(out[0], out[1], out[2], out[3]);
-        } else {
-            for (int e = 0; e < np; ++e) dp[e] = (u8)(out[e >> 2] >> (8 * (e & 3)));
-        }
+        store_chunk(dp, np, vec, out);
     }
 }
 
@@ -171,10 +148,8 @@ __global__ __launch_bounds__(256) void add_noise_kernel(View s, View nz, View d)
     const int rowbytes = d.w * d.c;
     const int nchunks = (rowbytes + 3) >> 2;
     const int64_t total = (int64_t)d.n * d.h * nchunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks);
-        const int64_t r = t / nchunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, nchunks, d.h);
         const int xb = ck << 2;
         const int nv = min(4, rowbytes - xb);
         const u8* sp = s.row(f, y) + xb;
@@ -202,10 +177,8 @@ __global__ __launch_bounds__(256) void add_noise_kernel(View s, View nz, View d)
 struct Perm4 { int v[4]; };
 __global__ __launch_bounds__(256) void permute_kernel(View s, View d, Perm4 pm) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         const u8* sp = s.row(f, y) + x * s.c;
         u8* dp = d.row(f, y) + x * d.c;
         u8 px[4];
@@ -230,10 +203,8 @@ __device__ __forceinline__ u32 nonzero_bytes_to_ff(u32 x) {
 __global__ __launch_bounds__(256) void composite_rgb16_kernel(View a, View b, View m, View d) {
     const int ngrp = d.w >> 4;
     const int64_t total = (int64_t)d.n * d.h * ngrp;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int g = (int)(t % ngrp);
-        const int64_t r = t / ngrp;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [g, y, f] = row_item(t, ngrp, d.h);
         const uint4 mq = *(const uint4*)(m.row(f, y) + g * 16);
         const u32 mw[4] = {mq.x, mq.y, mq.z, mq.w};
         const uint4* ap = (const uint4*)(a.row(f, y) + g * 48);
@@ -266,10 +237,8 @@ __global__ __launch_bounds__(256) void composite_const_rgb16_kernel(View a, View
     const int ngrp = d.w >> 4;
     const int64_t total = (int64_t)d.n * d.h * ngrp;
     const u32 cpat[3] = {c0, c1, c2};                     // the colour as 12 interleaved bytes (period 3 dwords)
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int g = (int)(t % ngrp);
-        const int64_t r = t / ngrp;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [g, y, f] = row_item(t, ngrp, d.h);
         const uint4 mq = *(const uint4*)(m.row(f, y) + g * 16);
         const u32 mw[4] = {mq.x, mq.y, mq.z, mq.w};
         const uint4* ap = (const uint4*)(a.row(f, y) + g * 48);
@@ -297,10 +266,8 @@ __global__ __launch_bounds__(256) void composite_const_rgb16_kernel(View a, View
 
 __global__ __launch_bounds__(256) void composite_const_kernel(View a, View m, View d, u32 colour) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         const bool sel = m.row(f, y)[x] != 0;
         const u8* src = a.row(f, y) + x * d.c;
         u8* dp = d.row(f, y) + x * d.c;
@@ -310,10 +277,8 @@ __global__ __launch_bounds__(256) void composite_const_kernel(View a, View m, Vi
 
 __global__ __launch_bounds__(256) void composite_kernel(View a, View b, View m, View d) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         const u8* src = (m.row(f, y)[x] ? a.row(f, y) : b.row(f, y)) + x * d.c;
         u8* dp = d.row(f, y) + x * d.c;
         for (int j = 0; j < d.c; ++j) dp[j] = src[j];
@@ -325,31 +290,15 @@ __global__ __launch_bounds__(256) void composite_kernel(View a, View b, View m, 
 __global__ __launch_bounds__(256) void enhance_color_kernel(View s, View d, float factor) {
     const int ngrp = (d.w + 15) >> 4;
     const int64_t total = (int64_t)d.n * d.h * ngrp;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int g = (int)(t % ngrp);
-        const int64_t r = t / ngrp;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [g, y, f] = row_item(t, ngrp, d.h);
         const int x0 = g << 4;
         const int np = min(16, d.w - x0);
         const u8* sp = s.row(f, y) + x0 * 3;
         u8* dp = d.row(f, y) + x0 * 3;
         u32 in[12], out[12];
         const bool vec = np == 16 && ((((uintptr_t)sp) | ((uintptr_t)dp)) & 15) == 0;
-        if (vec) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const uint4 q = ((const uint4*)sp)[b];
-                in[4 * b] = q.x; in[4 * b + 1] = q.y; in[4 * b + 2] = q.z; in[4 * b + 3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) in[k] = 0;
-            for (int e = 0; e < np * 3; ++e) {
-                const u32 v = sp[e];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) if ((e >> 2) == k) in[k] |= v << (8 * (e & 3));
-            }
-        }
+        load_chunk(sp, np * 3, vec, in);
 #pragma unroll
         for (int k = 0; k < 12; ++k) out[k] = 0;
 #pragma unroll
@@ -364,17 +313,7 @@ __global__ __launch_bounds__(256) void enhance_color_kernel(View s, View d, floa
                 out[b >> 2] = __builtin_amdgcn_cvt_pk_u8_f32(blend_floor(L, (float)ch[j], factor), b & 3, out[b >> 2]);
             }
         }
-        if (vec) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) ((uint4*)dp)[b] = make_uint4(out[4 * b], out[4 * b + 1], out[4 * b + 2], out[4 * b + 3]);
-        } else {
-            for (int e = 0; e < np * 3; ++e) {
-                u32 w = 0;
-#pragma unroll
-                for (int k = 0; k < 12; ++k) if ((e >> 2) == k) w = out[k];
-                dp[e] = (u8)(w >> (8 * (e & 3)));
-            }
-        }
+        store_chunk(dp, np * 3, vec, out);
     }
 }
 
@@ -387,19 +326,14 @@ __global__ __launch_bounds__(256) void lum_sum_kernel(View s, unsigned long long
     u32 part = 0;
     // 16 pixels per lane from whole 16-byte blocks when the rows allow it (the per-pixel byte loads below ran at
     // 15 % of a copy's speed); a lane's partial sum stays below 2^32: <= 2^24 pixels per lane x 255
-    const bool vec = (s.w & 15) == 0 && ((((uintptr_t)s.p) | (uintptr_t)s.rs | (uintptr_t)s.fs) & 15) == 0;
+    const bool vec = (s.w & 15) == 0 && aligned(s, 16);
     if (vec) {
         const int ngrp = s.w >> 4;
         const int64_t groups = (int64_t)s.h * ngrp;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < groups; t += (int64_t)gridDim.x * 256) {
-            const int g = (int)(t % ngrp), y = (int)(t / ngrp);
-            const u8* sp = s.row(f, y) + (g << 4) * C;
+        for (int64_t t = walk_first(); t < groups; t += walk_stride()) {
+            const auto [g, y] = row_item(t, ngrp);
             u32 in[4 * C];
-#pragma unroll
-            for (int b = 0; b < C; ++b) {
-                const uint4 q = *(const uint4*)(sp + 16 * b);
-                in[4 * b] = q.x; in[4 * b + 1] = q.y; in[4 * b + 2] = q.z; in[4 * b + 3] = q.w;
-            }
+            load_chunk(s.row(f, y) + (g << 4) * C, 16 * C, true, in);
 #pragma unroll
             for (int px = 0; px < 16; ++px) {
                 const int b0 = px * C;
@@ -412,8 +346,8 @@ __global__ __launch_bounds__(256) void lum_sum_kernel(View s, unsigned long long
         }
     } else {
         const int64_t total = (int64_t)s.h * s.w;
-        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-            const int x = (int)(t % s.w), y = (int)(t / s.w);
+        for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+            const auto [x, y] = row_item(t, s.w);
             const u8* p = s.row(f, y) + x * C;
             part += C == 1 ? (u32)p[0] : luma_u8(p[0], p[1], p[2]);
         }
@@ -429,12 +363,6 @@ __global__ __launch_bounds__(256) void lum_sum_kernel(View s, unsigned long long
 }
 
 // pass 2: blend(solid int(mean + 0.5), image, factor); the mean is formed from the frame's sum
-struct ContrastOp {
-    float factor, mean;
-    __device__ __forceinline__ float operator()(float pa, float, int) const {
-        return blend_floor(mean, pa, factor);
-    }
-};
 template <int C>
 __global__ __launch_bounds__(256) void contrast_kernel(View s, View d, float factor, const unsigned long long* sums) {
     constexpr int NV = (C == 3) ? 3 : 1, CB = 16 * NV;
@@ -443,12 +371,13 @@ __global__ __launch_bounds__(256) void contrast_kernel(View s, View d, float fac
     const int f = blockIdx.y;
     const float mean = contrast_mean(sums[f], (int64_t)s.h * s.w);
     const int64_t total = (int64_t)d.h * nchunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % nchunks), y = (int)(t / nchunks);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y] = row_item(t, nchunks);
         const int xb = ck * CB;
         const u8* ap = s.row(f, y) + xb;
         u8* dp = d.row(f, y) + xb;
         const int nv = min(CB, rowbytes - xb);
+        // (not load_chunk / store_chunk: one uint4 at a time keeps C = 3 at 24 VGPRs; the whole 48-byte chunk took 110)
         if (nv == CB && ((((uintptr_t)dp) | ((uintptr_t)ap)) & 15) == 0) {
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -483,10 +412,8 @@ template <int MODE>
 __global__ __launch_bounds__(256) void noise_f64_kernel(View s, View z, View d, double lambda) {
     const int rowbytes = d.w * d.c;
     const int64_t total = (int64_t)d.n * d.h * rowbytes;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int b = (int)(t % rowbytes);
-        const int64_t r = t / rowbytes;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [b, y, f] = row_item(t, rowbytes, d.h);
         const double zv = ((const double*)z.row(f, y))[b];
         double v = MODE == 0 ? (double)(float)s.row(f, y)[b] + zv : zv / lambda * 255.0;
         v = v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v);                     // np.clip
@@ -496,10 +423,8 @@ __global__ __launch_bounds__(256) void noise_f64_kernel(View s, View z, View d, 
 // impulse_noise: pixels with mask < lo become 0, with mask > hi become 255 (all channels)
 __global__ __launch_bounds__(256) void impulse_kernel(View s, View m, View d, double lo, double hi) {
     const int64_t total = (int64_t)d.n * d.h * d.w;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int x = (int)(t % d.w);
-        const int64_t r = t / d.w;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [x, y, f] = row_item(t, d.w, d.h);
         const double mv = ((const double*)m.row(f, y))[x];
         const u8* sp = s.row(f, y) + x * d.c;
         u8* dp = d.row(f, y) + x * d.c;
@@ -507,10 +432,8 @@ __global__ __launch_bounds__(256) void impulse_kernel(View s, View m, View d, do
     }
 }
 
-static inline unsigned grid_for(int64_t total) {
-    int64_t blocks = (total + 255) / 256;
-    return (unsigned)(blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks));
-}
+// most workgroups of a launch of the kernels above; map_rows_kernel (launch_map) and the two contrast passes state theirs
+constexpr unsigned ROW_GRID_CAP = 8192;
 
 } // namespace imgxf
 
@@ -524,9 +447,9 @@ IMGXF_API int imgxf_rgb2l_u8(const imgxf_view* src, const imgxf_view* dst, void*
     const View s = make_view(src), d = make_view(dst);
     const int64_t total = (int64_t)d.n * d.h * ((d.w + 15) >> 4);
     if (src->c == 3)
-        hipLaunchKernelGGL((rgb2l_kernel<3>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, s, d);
+        hipLaunchKernelGGL((rgb2l_kernel<3>), dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, s, d);
     else
-        hipLaunchKernelGGL((rgb2l_kernel<4>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, s, d);
+        hipLaunchKernelGGL((rgb2l_kernel<4>), dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, s, d);
     return launch_status();
 }
 
@@ -573,12 +496,11 @@ IMGXF_API int imgxf_add_noise_u8(const imgxf_view* src, const imgxf_view* noise_
     IMGXF_CHECK(check_view(dst));
     IMGXF_CHECK(check_view(noise_f32, 4));
     if (!same_geometry(src, dst) || !same_geometry(src, noise_f32)) return IMGXF_ERR_SHAPE;
-    if (((uintptr_t)noise_f32->data & 3) || (noise_f32->row_stride & 3) || (noise_f32->frame_stride & 3))
-        return IMGXF_ERR_ARG;
+    if (!aligned(noise_f32, 4)) return IMGXF_ERR_ARG;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
     const int64_t total = (int64_t)d.n * d.h * ((d.rowbytes() + 3) >> 2);
-    hipLaunchKernelGGL(add_noise_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(add_noise_kernel, dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        make_view(src), make_view(noise_f32), d);
     return launch_status();
 }
@@ -590,10 +512,8 @@ struct PermSel { u32 s1[3], s2[3]; };
 __global__ __launch_bounds__(256) void permute_rgb16_kernel(View s, View d, PermSel ps) {
     const int chunks = (d.w * 3) / 48;                                      // host: row bytes % 48 == 0
     const int64_t total = (int64_t)d.n * d.h * chunks;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
-        const int ck = (int)(t % chunks);
-        const int64_t r = t / chunks;
-        const int y = (int)(r % d.h), f = (int)(r / d.h);
+    for (int64_t t = walk_first(); t < total; t += walk_stride()) {
+        const auto [ck, y, f] = row_item(t, chunks, d.h);
         const uint4* sp = (const uint4*)(s.row(f, y) + 48 * ck);
         uint4* dp = (uint4*)(d.row(f, y) + 48 * ck);
         const uint4 i0 = sp[0], i1 = sp[1], i2 = sp[2];
@@ -625,8 +545,7 @@ IMGXF_API int imgxf_permute_u8(const imgxf_view* src, const imgxf_view* dst, con
     const View d = make_view(dst);
     {
         const View sv = make_view(src);
-        auto al16 = [](const View& v) { return ((((uintptr_t)v.p) | (uintptr_t)v.rs | (uintptr_t)v.fs) & 15) == 0; };
-        if (src->c == 3 && dst->c == 3 && (d.w * 3) % 48 == 0 && al16(sv) && al16(d) && !knob_set(K_NO_FAST_LEFTOVERS)) {
+        if (src->c == 3 && dst->c == 3 && (d.w * 3) % 48 == 0 && aligned(sv, 16) && aligned(d, 16) && !knob_set(K_NO_FAST_LEFTOVERS)) {
             // output byte 4 j + e of a 12-byte group comes from input byte q = 3 ((4 j + e) / 3) + perm[(4 j + e) % 3] of the
             // group's three dwords: t1 = perm(dword 1, dword 0) gathers the bytes that live there, perm(dword 2, t1) the rest
             PermSel ps; memset(&ps, 0, sizeof(ps));
@@ -640,12 +559,12 @@ IMGXF_API int imgxf_permute_u8(const imgxf_view* src, const imgxf_view* dst, con
                 }
                 ps.s1[j] = s1; ps.s2[j] = s2;
             }
-            hipLaunchKernelGGL(permute_rgb16_kernel, dim3(grid_for((int64_t)d.n * d.h * ((d.w * 3) / 48))), dim3(256), 0,
+            hipLaunchKernelGGL(permute_rgb16_kernel, dim3(grid_for((int64_t)d.n * d.h * ((d.w * 3) / 48), ROW_GRID_CAP)), dim3(256), 0,
                                (hipStream_t)stream, sv, d, ps);
             return launch_status();
         }
     }
-    hipLaunchKernelGGL(permute_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0,
+    hipLaunchKernelGGL(permute_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, make_view(src), d, pm);
     return launch_status();
 }
@@ -661,13 +580,12 @@ IMGXF_API int imgxf_composite_u8(const imgxf_view* im1, const imgxf_view* im2,
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
     const View va = make_view(im1), vb = make_view(im2), vm = make_view(mask);
-    auto al16 = [](const View& v) { return ((((uintptr_t)v.p) | (uintptr_t)v.rs | (uintptr_t)v.fs) & 15) == 0; };
-    if (d.c == 3 && d.w % 16 == 0 && al16(va) && al16(vb) && al16(vm) && al16(d)) {
-        hipLaunchKernelGGL(composite_rgb16_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 4))), dim3(256), 0,
+    if (d.c == 3 && d.w % 16 == 0 && aligned(va, 16) && aligned(vb, 16) && aligned(vm, 16) && aligned(d, 16)) {
+        hipLaunchKernelGGL(composite_rgb16_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 4), ROW_GRID_CAP)), dim3(256), 0,
                            (hipStream_t)stream, va, vb, vm, d);
         return launch_status();
     }
-    hipLaunchKernelGGL(composite_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0,
+    hipLaunchKernelGGL(composite_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, va, vb, vm, d);
     return launch_status();
 }
@@ -679,7 +597,7 @@ IMGXF_API int imgxf_enhance_color_u8(const imgxf_view* src, const imgxf_view* ds
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
     const int64_t total = (int64_t)d.n * d.h * ((d.w + 15) >> 4);
-    hipLaunchKernelGGL(enhance_color_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, make_view(src), d, factor);
+    hipLaunchKernelGGL(enhance_color_kernel, dim3(grid_for(total, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream, make_view(src), d, factor);
     return launch_status();
 }
 
@@ -694,14 +612,10 @@ IMGXF_API int imgxf_enhance_contrast_u8(const imgxf_view* src, const imgxf_view*
     hipError_t e = hipMemsetAsync(sums, 0, (size_t)src->n * sizeof(uint64_t), st);
     if (e != hipSuccess) return (int)e;
     const View s = make_view(src), d = make_view(dst);
-    int64_t bx = ((int64_t)s.h * s.w + 256 * 16 - 1) / (256 * 16);
-    if (bx > 256) bx = 256;
-    if (bx < 1) bx = 1;
-    dim3 g1((unsigned)bx, (unsigned)s.n);
+    // per frame: 16 pixels per lane and at most 256 workgroups for the sum, at most 2048 for the blend
+    dim3 g1(grid_for(((int64_t)s.h * s.w + 15) / 16, 256), (unsigned)s.n);
     const int cb = s.c == 3 ? 48 : 16;
-    int64_t b2 = ((int64_t)d.h * ((d.rowbytes() + cb - 1) / cb) + 255) / 256;
-    if (b2 > 2048) b2 = 2048;
-    dim3 g2((unsigned)b2, (unsigned)s.n);
+    dim3 g2(grid_for((int64_t)d.h * ((d.rowbytes() + cb - 1) / cb), 2048), (unsigned)s.n);
     if (s.c == 3) {
         hipLaunchKernelGGL((lum_sum_kernel<3>), g1, dim3(256), 0, st, s, (unsigned long long*)sums);
         hipLaunchKernelGGL((contrast_kernel<3>), g2, dim3(256), 0, st, s, d, factor, (const unsigned long long*)sums);
@@ -717,10 +631,10 @@ IMGXF_API int imgxf_add_noise_f64_u8(const imgxf_view* src, const imgxf_view* no
     IMGXF_CHECK(check_view(dst));
     IMGXF_CHECK(check_view(noise_f64, 8));
     if (!same_geometry(src, dst) || !same_geometry(src, noise_f64)) return IMGXF_ERR_SHAPE;
-    if (((uintptr_t)noise_f64->data & 7) || (noise_f64->row_stride & 7) || (noise_f64->frame_stride & 7)) return IMGXF_ERR_ARG;
+    if (!aligned(noise_f64, 8)) return IMGXF_ERR_ARG;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
-    hipLaunchKernelGGL((noise_f64_kernel<0>), dim3(grid_for((int64_t)d.n * d.h * d.rowbytes())), dim3(256), 0,
+    hipLaunchKernelGGL((noise_f64_kernel<0>), dim3(grid_for((int64_t)d.n * d.h * d.rowbytes(), ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, make_view(src), make_view(noise_f64), d, 1.0);
     return launch_status();
 }
@@ -730,10 +644,10 @@ IMGXF_API int imgxf_shot_noise_u8(const imgxf_view* counts_f64, double lambda, c
     IMGXF_CHECK(check_view(counts_f64, 8));
     if (!same_geometry(dst, counts_f64)) return IMGXF_ERR_SHAPE;
     if (!(lambda > 0.0)) return IMGXF_ERR_ARG;
-    if (((uintptr_t)counts_f64->data & 7) || (counts_f64->row_stride & 7) || (counts_f64->frame_stride & 7)) return IMGXF_ERR_ARG;
+    if (!aligned(counts_f64, 8)) return IMGXF_ERR_ARG;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
-    hipLaunchKernelGGL((noise_f64_kernel<1>), dim3(grid_for((int64_t)d.n * d.h * d.rowbytes())), dim3(256), 0,
+    hipLaunchKernelGGL((noise_f64_kernel<1>), dim3(grid_for((int64_t)d.n * d.h * d.rowbytes(), ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, d, make_view(counts_f64), d, lambda);
     return launch_status();
 }
@@ -744,10 +658,10 @@ IMGXF_API int imgxf_impulse_noise_u8(const imgxf_view* src, const imgxf_view* ma
     IMGXF_CHECK(check_view(dst));
     IMGXF_CHECK(check_view(mask_f64, 8));
     if (!same_geometry(src, dst) || !same_nhw(src, mask_f64) || mask_f64->c != 1) return IMGXF_ERR_SHAPE;
-    if (((uintptr_t)mask_f64->data & 7) || (mask_f64->row_stride & 7) || (mask_f64->frame_stride & 7)) return IMGXF_ERR_ARG;
+    if (!aligned(mask_f64, 8)) return IMGXF_ERR_ARG;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst);
-    hipLaunchKernelGGL(impulse_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(impulse_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0, (hipStream_t)stream,
                        make_view(src), make_view(mask_f64), d, lo, hi);
     return launch_status();
 }
@@ -761,19 +675,18 @@ IMGXF_API int imgxf_composite_const_u8(const imgxf_view* im1, const uint8_t* col
     if (!same_geometry(im1, dst) || !same_nhw(mask, dst) || mask->c != 1) return IMGXF_ERR_SHAPE;
     if (empty_view(dst)) return IMGXF_OK;
     const View d = make_view(dst), va = make_view(im1), vm = make_view(mask);
-    auto al16 = [](const View& v) { return ((((uintptr_t)v.p) | (uintptr_t)v.rs | (uintptr_t)v.fs) & 15) == 0; };
-    if (d.c == 3 && d.w % 16 == 0 && al16(va) && al16(vm) && al16(d)) {
+    if (d.c == 3 && d.w % 16 == 0 && aligned(va, 16) && aligned(vm, 16) && aligned(d, 16)) {
         uint8_t pat[12];
         for (int i = 0; i < 12; ++i) pat[i] = colour[i % 3];
         u32 c[3];
         memcpy(c, pat, 12);
-        hipLaunchKernelGGL(composite_const_rgb16_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 4))), dim3(256), 0,
+        hipLaunchKernelGGL(composite_const_rgb16_kernel, dim3(grid_for((int64_t)d.n * d.h * (d.w >> 4), ROW_GRID_CAP)), dim3(256), 0,
                            (hipStream_t)stream, va, vm, d, c[0], c[1], c[2]);
         return launch_status();
     }
     u32 packed = 0;
     for (int j = 0; j < d.c; ++j) packed |= (u32)colour[j] << (8 * j);
-    hipLaunchKernelGGL(composite_const_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w)), dim3(256), 0,
+    hipLaunchKernelGGL(composite_const_kernel, dim3(grid_for((int64_t)d.n * d.h * d.w, ROW_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, va, vm, d, packed);
     return launch_status();
 }

@@ -22,8 +22,7 @@ static int run_sepconv(const imgxf_view* src, const imgxf_view* dst, const float
     if (dst_f32) {
         IMGXF_CHECK(check_view(dst_f32, 4));
         if (!same_geometry(src, dst_f32)) return IMGXF_ERR_SHAPE;
-        if (((uintptr_t)dst_f32->data & 3) || (dst_f32->row_stride & 3) || (dst_f32->frame_stride & 3))
-            return IMGXF_ERR_ARG;
+        if (!aligned(dst_f32, 4)) return IMGXF_ERR_ARG;
         df = make_view(dst_f32);
     }
     if (empty_view(src)) return IMGXF_OK;

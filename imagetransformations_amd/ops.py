@@ -83,6 +83,17 @@ def _hwc(t: torch.Tensor):
     return t.shape[-3], t.shape[-2], t.shape[-1]
 
 
+def _frames(t: torch.Tensor) -> int:
+    return t.shape[0] if t.dim() == 4 else 1
+
+
+def _same_shape(t: torch.Tensor, name: str, *args) -> torch.Tensor:
+    """A same-shape op on a checked tensor: `name`(view of t, view of a fresh contiguous destination, *args)."""
+    out = torch.empty_like(t, memory_format=torch.contiguous_format)
+    _launch(t, name, F.vp(F.view_of(t)), F.vp(F.view_of(out)), *args)
+    return out
+
+
 # ---------------------------------------------------------------- a1 Gaussian / separable
 def gaussian_blur(t: torch.Tensor, ksize: int, sigma: float, return_f32: bool = False,
                   fixed_point: bool = False, out: torch.Tensor | None = None):
@@ -117,11 +128,9 @@ def sepconv_fixed(t: torch.Tensor, kx: Sequence[int], ky: Sequence[int], border:
     columns, (v + 2^15) >> 16 — OpenCV's uint8 evaluation order."""
     import ctypes
     t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
     ax = (ctypes.c_uint16 * len(kx))(*[int(v) for v in kx])
     ay = (ctypes.c_uint16 * len(ky))(*[int(v) for v in ky])
-    _launch(t, "imgxf_sepconv_fixed_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), ax, len(kx), ay, len(ky), border)
-    return out
+    return _same_shape(t, "imgxf_sepconv_fixed_u8", ax, len(kx), ay, len(ky), border)
 
 
 # ---------------------------------------------------------------- a5 dense correlation
@@ -132,11 +141,8 @@ def conv2d(t: torch.Tensor, kernel, border: int = REFLECT_101) -> torch.Tensor:
     kh, kw = len(rows), len(rows[0])
     if any(len(r) != kw for r in rows):
         raise ValueError("kernel must be rectangular")
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
     flat = [v for r in rows for v in r]
-    _launch(t, "imgxf_conv2d_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.f32_array(flat), kh, kw,
-           border)
-    return out
+    return _same_shape(t, "imgxf_conv2d_u8", F.f32_array(flat), kh, kw, border)
 
 
 # ---------------------------------------------------------------- a4 Sobel
@@ -244,10 +250,7 @@ def rotate_zoom_matrix(w: int, h: int, angle_deg: float, zoom: float) -> list[fl
 
 def flip(t: torch.Tensor, top_bottom: bool = False) -> torch.Tensor:
     """Image.transpose(FLIP_LEFT_RIGHT) (default) / FLIP_TOP_BOTTOM."""
-    t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_flip_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), 1 if top_bottom else 0)
-    return out
+    return _same_shape(_check_u8(t), "imgxf_flip_u8", 1 if top_bottom else 0)
 
 
 def perspective(t: torch.Tensor, coeffs) -> torch.Tensor:
@@ -257,15 +260,11 @@ def perspective(t: torch.Tensor, coeffs) -> torch.Tensor:
     t = _check_u8(t)
     rows = [list(map(float, r)) for r in coeffs] if hasattr(coeffs[0], "__len__") else None
     flat = [v for r in rows for v in r] if rows is not None else list(map(float, coeffs))
-    nfr = t.shape[0] if t.dim() == 4 else 1
-    if rows is not None and (t.dim() != 4 or len(rows) != nfr):
+    if rows is not None and (t.dim() != 4 or len(rows) != _frames(t)):
         raise ValueError("per-frame coefficients need a [N,H,W,C] batch with one row of 8 per frame")
     if len(flat) != 8 * (len(rows) if rows is not None else 1):
         raise ValueError("perspective coefficients come in rows of eight")
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_perspective_bilinear_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.f32_array(flat),
-           1 if rows is not None else 0)
-    return out
+    return _same_shape(t, "imgxf_perspective_bilinear_u8", F.f32_array(flat), 1 if rows is not None else 0)
 
 
 def rot90(t: torch.Tensor, quarter_turns_ccw: int) -> torch.Tensor:
@@ -337,7 +336,7 @@ class _PlanCache:
 _plans = _PlanCache()
 
 
-def _run_plan(plan, t: torch.Tensor, out: torch.Tensor, n: int) -> None:
+def _run_plan(plan, t: torch.Tensor, out: torch.Tensor) -> None:
     import ctypes
     nbytes = ctypes.c_size_t()
     vs, vo = F.view_of(t), F.view_of(out)
@@ -366,17 +365,11 @@ def resize(t: torch.Tensor, size: tuple[int, int], resample: int = RESAMPLE_BICU
     nw, nh = int(size[0]), int(size[1])
     if nw < 1 or nh < 1:
         raise ValueError("height and width must be > 0")   # Pillow's message
-    n = t.shape[0] if t.dim() == 4 else 1
-    if out is None:
-        out = _like(t, nh, nw)
-    else:
-        want = [nh, nw] if t.dim() == 2 else list(t.shape[:-3]) + [nh, nw, t.shape[-1]]
-        if out.dtype != torch.uint8 or out.device != t.device or tuple(out.shape) != tuple(want):
-            raise ValueError(f"out must be a uint8 tensor of shape {tuple(want)} on {t.device}")
-    if n == 0:
+    out = _out(out, _like_shape(t, nh, nw), t.device, lambda: _like(t, nh, nw))
+    if _frames(t) == 0:
         return out
     plan = _plans.get(h, w, nh, nw, c, t.device.index or 0, int(resample))
-    _run_plan(plan, t, out, n)
+    _run_plan(plan, t, out)
     return out
 
 
@@ -401,12 +394,11 @@ def resize_crop(t: torch.Tensor, size: tuple[int, int], box: tuple[int, int, int
     if nw == w or nh == h:
         res = crop(resize(t, size, resample), box)
         return res if out is None else out.copy_(res)
-    n = t.shape[0] if t.dim() == 4 else 1
     out = _out(out, _like_shape(t, b - tp, r - l), t.device, lambda: _like(t, b - tp, r - l))
-    if n == 0:
+    if _frames(t) == 0:
         return out
     plan = _plans.get(h, w, nh, nw, c, t.device.index or 0, int(resample), (l, tp, r - l, b - tp))
-    _run_plan(plan, t, out, n)
+    _run_plan(plan, t, out)
     return out
 
 
@@ -456,10 +448,7 @@ def rgb2l(t: torch.Tensor) -> torch.Tensor:
 
 def scale_abs(t: torch.Tensor, alpha: float, beta: float = 0.0) -> torch.Tensor:
     """cv2.convertScaleAbs(img, alpha=alpha, beta=beta) — transformation.py:207."""
-    t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_scale_abs_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), float(alpha), float(beta))
-    return out
+    return _same_shape(_check_u8(t), "imgxf_scale_abs_u8", float(alpha), float(beta))
 
 
 def blend(im1, im2, alpha: float, like: torch.Tensor | None = None) -> torch.Tensor:
@@ -493,21 +482,15 @@ def box_blur(t: torch.Tensor, radius: float, passes: int = 1) -> torch.Tensor:
     t = _check_u8(t)
     if radius < 0:
         raise ValueError("radius must be >= 0")        # Pillow's message
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    ws = torch.empty_like(out)
-    _launch(t, "imgxf_box_blur_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), float(radius), float(radius), int(passes),
-           ws.data_ptr(), ws.numel())
-    return out
+    ws = torch.empty(t.shape, dtype=torch.uint8, device=t.device)
+    return _same_shape(t, "imgxf_box_blur_u8", float(radius), float(radius), int(passes), ws.data_ptr(), ws.numel())
 
 
 def gaussian_blur_pil(t: torch.Tensor, radius: float) -> torch.Tensor:
     """image.filter(ImageFilter.GaussianBlur(radius)) — cifar_image_transformations.py:77."""
     t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    ws = torch.empty_like(out)
-    _launch(t, "imgxf_gaussian_blur_pil_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), float(radius),
-           ws.data_ptr(), ws.numel())
-    return out
+    ws = torch.empty(t.shape, dtype=torch.uint8, device=t.device)
+    return _same_shape(t, "imgxf_gaussian_blur_pil_u8", float(radius), ws.data_ptr(), ws.numel())
 
 
 SMOOTH_KERNEL = (1, 1, 1, 1, 5, 1, 1, 1, 1)      # ImageFilter.SMOOTH (scale 13)
@@ -518,10 +501,7 @@ def filter3x3(t: torch.Tensor, kernel9: Sequence[float], scale: float, offset: f
     t = _check_u8(t)
     if len(kernel9) != 9:
         raise ValueError("not enough coefficients in kernel")      # Pillow's message
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_filter3x3_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.f32_array(kernel9), float(scale),
-           float(offset))
-    return out
+    return _same_shape(t, "imgxf_filter3x3_u8", F.f32_array(kernel9), float(scale), float(offset))
 
 
 def enhance_sharpness(t: torch.Tensor, factor: float) -> torch.Tensor:
@@ -532,21 +512,14 @@ def enhance_sharpness(t: torch.Tensor, factor: float) -> torch.Tensor:
 
 def enhance_color(t: torch.Tensor, factor: float) -> torch.Tensor:
     """ImageEnhance.Color(img).enhance(factor) — cifar_image_transformations.py:102-106."""
-    t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_enhance_color_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), float(factor))
-    return out
+    return _same_shape(_check_u8(t), "imgxf_enhance_color_u8", float(factor))
 
 
 def enhance_contrast(t: torch.Tensor, factor: float) -> torch.Tensor:
     """ImageEnhance.Contrast(img).enhance(factor) — cifar_image_transformations.py:81-85."""
     t = _check_u8(t)
-    n = t.shape[0] if t.dim() == 4 else 1
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    sums = torch.empty(max(n, 1), dtype=torch.int64, device=t.device)
-    _launch(t, "imgxf_enhance_contrast_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), float(factor),
-           sums.data_ptr())
-    return out
+    sums = torch.empty(max(_frames(t), 1), dtype=torch.int64, device=t.device)
+    return _same_shape(t, "imgxf_enhance_contrast_u8", float(factor), sums.data_ptr())
 
 
 def add_noise(t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
@@ -564,11 +537,7 @@ def add_noise_device(t: torch.Tensor, sigma: float, seed: int, offset: int = 0) 
     """apply_gaussian_noise with the normals generated on the device (Philox4x32-10 + Box-Muller):
     clip(f32(p) + N(0, sigma), 0, 255) truncated; `sigma` = noise_std * 255.  Not NumPy's stream — the
     opt-in IMGXF_NOISE_RNG=device path of the facade.  Element e of the batch uses normal number offset + e."""
-    t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_add_noise_philox_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), float(sigma),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset))
-    return out
+    return _same_shape(_check_u8(t), "imgxf_add_noise_philox_u8", float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset))
 
 
 def philox_u32(count: int, seed: int, offset: int = 0, device=None) -> torch.Tensor:
@@ -623,9 +592,7 @@ def lut(t: torch.Tensor, table) -> torch.Tensor:
         tab = tab * c
     if len(tab) != 256 * c:
         raise ValueError(f"lookup table needs 256 or {256 * c} entries, got {len(tab)}")
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_lut_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.u8_array(tab, len(tab)))
-    return out
+    return _same_shape(t, "imgxf_lut_u8", F.u8_array(tab, len(tab)))
 
 
 def posterize_table(bits: int) -> list[int]:
@@ -653,48 +620,31 @@ def equalize(t: torch.Tensor) -> torch.Tensor:
     """ImageOps.equalize per frame and channel (fall_2025/AugMix.py:36); histogram, table and
     mapping all run on the device."""
     t = _check_u8(t)
-    h, w, c = _hwc(t)
-    n = t.shape[0] if t.dim() == 4 else 1
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    ws = torch.empty(max(1, n * c * 256 * 5 // 4 + 1), dtype=torch.int32, device=t.device)
-    _launch(t, "imgxf_equalize_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), ws.data_ptr(), ws.numel() * 4)
-    return out
+    ws = torch.empty(max(1, _frames(t) * _hwc(t)[2] * 256 * 5 // 4 + 1), dtype=torch.int32, device=t.device)
+    return _same_shape(t, "imgxf_equalize_u8", ws.data_ptr(), ws.numel() * 4)
 
 
 def rgb2yuv(t: torch.Tensor) -> torch.Tensor:
     """cv2.cvtColor(img, cv2.COLOR_RGB2YUV) for 8-bit RGB (parity unpinned: OpenCV's integer definition)."""
-    t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_rgb2yuv_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)))
-    return out
+    return _same_shape(_check_u8(t), "imgxf_rgb2yuv_u8")
 
 
 def yuv2rgb(t: torch.Tensor) -> torch.Tensor:
     """cv2.cvtColor(img, cv2.COLOR_YUV2RGB) for 8-bit YUV (parity unpinned)."""
-    t = _check_u8(t)
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    _launch(t, "imgxf_yuv2rgb_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)))
-    return out
+    return _same_shape(_check_u8(t), "imgxf_yuv2rgb_u8")
 
 
 def equalize_hist_cv(t: torch.Tensor, channel: int = 0) -> torch.Tensor:
     """cv2.equalizeHist applied to one channel of an interleaved image, per frame (parity unpinned)."""
     t = _check_u8(t)
-    h, w, c = _hwc(t)
-    n = t.shape[0] if t.dim() == 4 else 1
-    out = torch.empty_like(t, memory_format=torch.contiguous_format)
-    ws = torch.empty(max(1, n * c * 256 * 5 // 4 + 1), dtype=torch.int32, device=t.device)
-    _launch(t, "imgxf_equalize_hist_cv_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), int(channel), ws.data_ptr(),
-           ws.numel() * 4)
-    return out
+    ws = torch.empty(max(1, _frames(t) * _hwc(t)[2] * 256 * 5 // 4 + 1), dtype=torch.int32, device=t.device)
+    return _same_shape(t, "imgxf_equalize_hist_cv_u8", int(channel), ws.data_ptr(), ws.numel() * 4)
 
 
 def channel_histogram(t: torch.Tensor) -> torch.Tensor:
     """[N, C, 256] int32 histogram of a [N,H,W,C] / [H,W,C] / [H,W] uint8 tensor."""
     t = _check_u8(t)
-    h, w, c = _hwc(t)
-    n = t.shape[0] if t.dim() == 4 else 1
-    hist = torch.empty((n, c, 256), dtype=torch.int32, device=t.device)
+    hist = torch.empty((_frames(t), _hwc(t)[2], 256), dtype=torch.int32, device=t.device)
     _launch(t, "imgxf_channel_histogram_u8", F.vp(F.view_of(t)), hist.data_ptr())
     return hist
 
@@ -747,7 +697,7 @@ def composite_const(im1: torch.Tensor, colour, mask: torch.Tensor) -> torch.Tens
 def percentile_mask(gray: torch.Tensor, q: float, return_threshold: bool = False):
     """(gray > np.percentile(gray, q)) * 255 per frame — transformation.py:340."""
     gray = _check_u8(gray, "gray")
-    n = gray.shape[0] if gray.dim() == 4 else 1
+    n = _frames(gray)
     hist = torch.empty((n, 256), dtype=torch.int32, device=gray.device)
     thr = torch.empty(n, dtype=torch.float64, device=gray.device)
     out = torch.empty_like(gray, memory_format=torch.contiguous_format)

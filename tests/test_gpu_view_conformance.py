@@ -541,10 +541,11 @@ def test_misaligned_destination_matches_oracle_and_keeps_guards(device, name, mo
 
 
 # ------------------------------------------------------------------ grid-stride wrap
-# Grid caps of the launchers (a capped grid walks the rest of the work grid-stride):
+# Grid caps of the launchers, each the `cap` of a grid_for(total, cap) call (imgxf_common.h; a capped grid walks the
+# rest of the work grid-stride):
 LAUNCH_MAP_SWEEP_C1 = 16384 * 256 * 16     # launch_map (pointwise.hip): 16384 workgroups x 256 lanes x 16 B (C != 3)
-GRID_FOR_RGB2L_SWEEP = 8192 * 256 * 16     # grid_for (pointwise.hip): 8192 workgroups x 256 lanes x 16 px (rgb2l_kernel)
-BLOCKS_FOR_SWEEP = 2048 * 256 * 16         # blocks_for (lut.hip): 2048 workgroups per frame x 256 lanes x 16 B (vec16)
+GRID_FOR_RGB2L_SWEEP = 8192 * 256 * 16     # ROW_GRID_CAP (pointwise.hip): 8192 workgroups x 256 lanes x 16 px (rgb2l_kernel)
+BLOCKS_FOR_SWEEP = 2048 * 256 * 16         # LUT_GRID_CAP (lut.hip): 2048 workgroups per frame x 256 lanes x 16 B (vec16)
 LUM_SUM_SWEEP = 256 * 256 * 16             # imgxf_enhance_contrast_u8: lum_sum 256 workgroups per frame x 256 x 16 px
 CONTRAST_SWEEP_C1 = 2048 * 256 * 16        # imgxf_enhance_contrast_u8: contrast 2048 per frame x 256 lanes x 16 B (C = 1)
 W4K = 3840

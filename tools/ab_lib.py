@@ -1,6 +1,6 @@
 """Same-process A/B of two builds of libimgxf.so on the headline kernels (development aid).
 
-    python tools/ab_lib.py <libA.so> <libB.so> [affine|affine32|gaussian|nearest|all] [frames] [height width]
+    python tools/ab_lib.py <libA.so> <libB.so> [affine|affine32|gaussian|nearest|all|step|pixel] [frames] [height width]
 
 (frames of 2160 x 3840 unless a height and a width are given: 128 x 2160 x 4096 is the width whose 32 tile columns
 divide over the XCDs, 288 x 1440 x 2560 and 1152 x 720 x 1280 hold the bytes of 128 4K frames)
@@ -20,10 +20,11 @@ from imagetransformations_amd import _ffi, ops  # noqa: E402
 ROUNDS, ITERS = int(os.environ.get("ROUNDS", "7")), int(os.environ.get("ITERS", "8"))
 
 
-def load(path, env=None):
+def load(path, env=None, copy=False):
     """env: "NAME=value,NAME2=value" knobs that only THIS library instance sees (every copy of libimgxf.so caches its own
-    knob table: the variables are set, the library re-reads them, they are removed again)."""
-    if env:
+    knob table: the variables are set, the library re-reads them, they are removed again).  copy: a second instance of a
+    library that is already loaded."""
+    if env or copy:
         import shutil, tempfile
         tmp = tempfile.NamedTemporaryFile(suffix=".so", delete=False).name       # a second dlopen of one path is the same instance
         shutil.copy(path, tmp)
@@ -41,6 +42,52 @@ def load(path, env=None):
     return lib
 
 
+def pixel(libs, src, st):
+    """The per-pixel kernels that move a lane's chunk through load_chunk / store_chunk (csrc/imgxf_common.h) and
+    imgxf_enhance_contrast_u8, on library A, a SECOND load of library A and library B, alternating.  A against A2 is the
+    margin: B is slow where its median lies above both of theirs."""
+    F, H, W, _ = src.shape
+    src2 = src.flip(0).contiguous()
+    rgb = {k: torch.empty_like(src) for k in libs}
+    gray = {k: torch.empty((F, H, W, 1), dtype=torch.uint8, device=src.device) for k in libs}
+    sums = torch.empty(F, dtype=torch.int64, device=src.device)
+    vs, vs2 = _ffi.view_of(src), _ffi.view_of(src2)
+    cases = {
+        "scale_abs": (rgb, lambda lib, vo: lib.imgxf_scale_abs_u8(_ffi.vp(vs), _ffi.vp(vo), 1.5, 10.0, st), 6),
+        "blend": (rgb, lambda lib, vo: lib.imgxf_blend_u8(_ffi.vp(vs), None, _ffi.vp(vs2), None, _ffi.vp(vo), 0.3, st), 9),
+        "rgb2l": (gray, lambda lib, vo: lib.imgxf_rgb2l_u8(_ffi.vp(vs), _ffi.vp(vo), st), 4),
+        "enhance_color": (rgb, lambda lib, vo: lib.imgxf_enhance_color_u8(_ffi.vp(vs), _ffi.vp(vo), 1.5, st), 6),
+        "enhance_contrast": (rgb, lambda lib, vo: lib.imgxf_enhance_contrast_u8(_ffi.vp(vs), _ffi.vp(vo), 1.5, sums.data_ptr(), st), 9),
+        "rgb2yuv": (rgb, lambda lib, vo: lib.imgxf_rgb2yuv_u8(_ffi.vp(vs), _ffi.vp(vo), st), 6),
+    }
+    px = F * H * W
+    print(f"F={F} {H}x{W}x3, {ROUNDS} rounds of {ITERS} launches, medians in ms (GB/s); A2 = library A loaded a second time")
+    for name, (outs, call, bpp) in cases.items():
+        views = {k: _ffi.view_of(outs[k]) for k in libs}
+        for k, lib in libs.items():
+            outs[k].fill_(0x5a)
+            rc = call(lib, views[k])
+            assert rc == 0, (name, k, rc)
+        torch.cuda.synchronize()
+        equal = bool(torch.equal(outs["A"], outs["B"])) and bool(torch.equal(outs["A"], outs["A2"]))
+        res = {k: [] for k in libs}
+        order = list(libs)
+        for rnd in range(ROUNDS):
+            # the order rotates: the library that ran last in every round measured 2 % slow on IDENTICAL device code
+            for k in order[rnd % 3:] + order[:rnd % 3]:
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                call(libs[k], views[k]); s.record()
+                for _ in range(ITERS):
+                    call(libs[k], views[k])
+                e.record(); torch.cuda.synchronize()
+                res[k].append(s.elapsed_time(e) / ITERS)
+        med = {k: statistics.median(v) for k, v in res.items()}
+        slow = med["B"] > max(med["A"], med["A2"])
+        print(f"{name:17s}" + "".join(f" {k} {med[k]:7.4f} ({bpp * px / med[k] / 1e6:5.0f})" for k in libs) +
+              f"   B/A {med['B'] / med['A']:.4f}  A2/A {med['A2'] / med['A']:.4f}   B rounds {min(res['B']):.4f} .. {max(res['B']):.4f}"
+              f"   {'SLOWER than both loads of A' if slow else 'inside'}   outputs equal: {equal}", flush=True)
+
+
 def main():
     pa, pb = sys.argv[1], sys.argv[2]
     what = sys.argv[3] if len(sys.argv) > 3 else "all"
@@ -50,8 +97,10 @@ def main():
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev); gen.manual_seed(1)
     src = torch.randint(0, 256, (F, H, W, 3), dtype=torch.uint8, device=dev, generator=gen)
-    outs = {k: torch.empty_like(src) for k in libs}
     st = torch.cuda.current_stream().cuda_stream
+    if what == "pixel":
+        return pixel({"A": libs["A"], "A2": load(pa, os.environ.get("A_ENV"), copy=True), "B": libs["B"]}, src, st)
+    outs = {k: torch.empty_like(src) for k in libs}
     vs = _ffi.view_of(src)
     m = _ffi.f64_array(ops.rotate_zoom_matrix(W, H, 30.0, 1.5))
     mn = _ffi.f64_array(ops.rotate_matrix(W, H, 22.5))
