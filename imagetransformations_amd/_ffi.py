@@ -206,6 +206,11 @@ SIGNATURES = {
     "imgxf_driver_list_layout_host": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)],
     "imgxf_driver_list_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "imgxf_background_list_tile": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "imgxf_background_list_layout_host": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)],
+    "imgxf_background_list_u8": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t,
+                                 C.c_void_p],
+    "imgxf_background_list_last_counts": [C.POINTER(C.c_int)],
 }
 
 

@@ -2,7 +2,7 @@
 and when it is read in place; how a host block is built and reaches the device; how the outputs of a call share one
 allocation; how files leave the device; how the resample passes validate their entries ("List passes").
 Callers: tensor_maps.preprocess_list, tensor_maps.resized_crop_list and resize_list.resize_list (frames, block, entries; the
-last also outputs), driver_list.apply_list (frames, layout, outputs; its block copy and row rounding are its own),
+last also outputs), background_list (frames, layout, addresses, respace, outputs), driver_list.apply_list (frames, layout, outputs; its block copy and row rounding are its own),
 pool.apply_chain_list (addresses, pack_pinned, outputs; its frame check is its own), jpeg.encode_list_views and
 jpeg.roundtrip_list (frames, also grayscale [H, W]; build, to_device, outputs, files_to_host), jpeg.encode_views
 (files_to_host), io_pipeline._save_on_device (slots, pack_pinned), jpeg_decode.decode (r16)."""

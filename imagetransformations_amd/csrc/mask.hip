@@ -5,6 +5,7 @@
 //   binary_dilation(mask, iterations=k) with the 4-connected cross and border 0, which for
 //   this structuring element equals "some set pixel within L1 distance k".
 #include "imgxf_common.h"
+#include "percentile.h"
 #include <algorithm>
 #include <math.h>
 #include <stdlib.h>
@@ -55,38 +56,12 @@ __global__ __launch_bounds__(256) void hist_kernel(View s, u32* hist) {
     if (sum) atomicAdd(&hist[f * 256 + threadIdx.x], sum);
 }
 
-// numpy percentile, method 'linear' (lib/_function_base_impl.py: _compute_virtual_index with
-// alpha=beta=1, _lerp), evaluated on the sorted multiset described by the histogram.
+// np.percentile(plane, q) of every frame from its histogram: percentile_linear_hist (percentile.h), one lane per frame
 __global__ void percentile_kernel(const u32* hist, int nframes, int64_t count, double q,
                                   double* thr) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nframes) return;
-    const u32* h = hist + f * 256;
-    const double quant = q / 100.0;
-    const double n = (double)count;
-    double virt = __dsub_rn(__dadd_rn(__dmul_rn(n, quant),
-                                      __dadd_rn(1.0, __dmul_rn(quant, (1.0 - 1.0 - 1.0)))), 1.0);
-    double lof = floor(virt);
-    double gamma = __dsub_rn(virt, lof);
-    int64_t lo = (int64_t)lof;
-    if (lo < 0) lo = 0;
-    if (lo > count - 1) lo = count - 1;
-    int64_t hi = lo + 1 > count - 1 ? count - 1 : lo + 1;
-    // value at sorted index i = first bin whose cumulative count exceeds i
-    int va = 255, vb = 255;
-    int64_t cum = 0;
-    bool ga = false, gb = false;
-    for (int b = 0; b < 256; ++b) {
-        cum += h[b];
-        if (!ga && cum > lo) { va = b; ga = true; }
-        if (!gb && cum > hi) { vb = b; gb = true; }
-    }
-    const double a = (double)va, bb = (double)vb;
-    const double diff = __dsub_rn(bb, a);
-    double out = __dadd_rn(a, __dmul_rn(diff, gamma));
-    if (gamma >= 0.5) out = __dsub_rn(bb, __dmul_rn(diff, __dsub_rn(1.0, gamma)));
-    if (diff == 0.0) out = a;
-    thr[f] = out;
+    thr[f] = percentile_linear_hist(hist + f * 256, count, q);
 }
 
 __global__ __launch_bounds__(256) void gt_mask_kernel(View s, View d, const double* thr) {

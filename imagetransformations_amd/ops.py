@@ -716,6 +716,28 @@ def dilate_cross(mask: torch.Tensor, iterations: int) -> torch.Tensor:
     return out
 
 
+def background_change_list(frames, colours, q=70.0):
+    """The whole of `apply_background_change` — Sobel, percentile, dilation, composite — for a list of RGB frames of
+    different sizes, each with a colour of its own, in one block copy and two launches:
+    `background_list.background_change_list`, where the arguments are described."""
+    from . import background_list as _module
+    return _module.background_change_list(frames, colours, q)
+
+
+def background_change_list_block(frames, colours, q=70.0, guard: int = 0, guard_value: int = 0):
+    """`background_change_list` that also returns its one output allocation, with guard bytes where asked for:
+    `background_list.background_change_list_block`."""
+    from . import background_list as _module
+    return _module.background_change_list_block(frames, colours, q, guard, guard_value)
+
+
+def background_change(frames: torch.Tensor, colours, q=70.0) -> torch.Tensor:
+    """`background_change_list` for a batch [N, H, W, 3] or one [H, W, 3] frame, any row and frame stride:
+    `background_list.background_change`."""
+    from . import background_list as _module
+    return _module.background_change(frames, colours, q)
+
+
 def jpeg_compression(frames: torch.Tensor, quality=75, subsampling=-1) -> torch.Tensor:
     """JPEG compression of a batch on the device (the ImageNet-C / CIFAR-10-C corruption): every frame as it reads back
     from the file Pillow would save it to at `quality` (an int, or one int per frame) and `subsampling`.  The

@@ -276,6 +276,25 @@ def apply_background_change(img: Image.Image, bg_color: Tuple[float, float, floa
     return _download(ops.composite_const(rgb, bg_rgb, foreground))   # Image.composite(img, Image.new(.., bg), mask)
 
 
+def apply_background_change_batch(images, bg_colors) -> List[Image.Image]:
+    """`[apply_background_change(img, c) for img, c in zip(images, bg_colors)]` for PIL images of any sizes through the list
+    route (`ops.background_change_list`): every image uploaded once, all of them in one block copy and two launches.
+    `bg_colors`: one float triple for every image, or one per image; bytes are int(c * 255) as above.  Alpha is dropped and
+    gray images are refused, as above."""
+    images = list(images)
+    bg_colors = list(bg_colors)
+    if bg_colors and not isinstance(bg_colors[0], (tuple, list, np.ndarray)):
+        bg_colors = [tuple(bg_colors)] * len(images)
+    if len(bg_colors) != len(images):
+        raise ValueError(f"bg_colors has {len(bg_colors)} entries for {len(images)} images")
+    bg_rgb = [tuple(int(c * 255) for c in colour) for colour in bg_colors]
+    for colour in bg_rgb:
+        if len(colour) != 3:
+            raise ValueError("a background colour is three floats (r, g, b)")
+    frames = [_rgb_tensor(img) for img in images]
+    return [_download(t) for t in ops.background_change_list(frames, bg_rgb)]
+
+
 def apply_background_change_simple(img: Image.Image, bg_color: Tuple[float, float, float]) -> Image.Image:
     bg_rgb = tuple(int(c * 255) for c in bg_color)
     return _download(ops.blend(_rgb_tensor(img), bg_rgb, 0.3))

@@ -1225,6 +1225,64 @@ int imgxf_driver_list_layout_host(const int32_t* geometry, const double* params,
  * aligned, total_bytes) on the stream and launches.  out: the output allocation (16-byte aligned, out_cap >= out_bytes).  No allocation, no synchronisation. */
 int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint8_t* out, size_t out_cap, void* stream);
 
+/* ---- apply_background_change on a LIST of RGB frames of different sizes, each with its own colour, in two launches -----
+ * Entry k is bit for bit
+ *     Image.composite(img, Image.new("RGB", img.size, colour_k),
+ *                     Image.fromarray(binary_dilation(e > np.percentile(e, q), iterations=3)))
+ *     with e = ndimage.sobel(np.array(img.convert("L")))
+ * — what imgxf_rgb_sobel_u8 (X_WRAP), imgxf_histogram_u8, imgxf_percentile_mask_u8, imgxf_dilate_cross_u8 (3) and
+ * imgxf_composite_const_u8 give in five calls — for uint8 RGB frames from 1 x 1 up, rows at any stride and byte offset,
+ * read in place.  One host block
+ *     imgxf_background_list_header | imgxf_background_list_entry[n] | imgxf_background_list_unit[n_units]
+ * one copy of it to the device, one hipMemsetAsync of the histogram workspace (hist_bytes, never uploaded) and two
+ * launches whatever the number of frames or sizes.  A work unit is one tile_h x tile_w tile of one entry, the units of
+ * an entry in row-major order, the entries in order.  Launch 1 counts the x-Sobel bytes of its tiles (staged with a
+ * one-pixel halo, no edge plane is stored) into the entry's uint32[256] histogram; launch 2 recomputes the edges of a
+ * tile plus a halo of 3, takes the entry's threshold from that histogram with the float64 statements of
+ * imgxf_percentile_mask_u8, dilates e > threshold (0 outside the image) to L1 distance 3 in LDS and stores
+ * mask ? rgb : colour.  The bytes do not depend on where a tile lies or on the width modulo anything. */
+typedef struct imgxf_background_list_header {
+    int32_t n_entries, n_units;
+    int32_t entries_off, units_off, total_bytes;   /* byte offsets of the sections, size of the block */
+    int32_t tile_h, tile_w;     /* imgxf_background_list_tile's, which the units were cut for */
+    int32_t pad_;
+    int64_t out_bytes;          /* size of the output buffer: the end of the last entry's slot */
+    int64_t hist_bytes;         /* size of the histogram workspace: 1024 n_entries */
+} imgxf_background_list_header;
+typedef struct imgxf_background_list_entry {
+    uint64_t data;              /* DEVICE address of pixel (0, 0) of the frame; filled by the caller, as is row_stride
+                                   (bytes, >= 3 w) */
+    int64_t  row_stride;
+    int64_t  out_off;           /* byte offset of the entry's [h][w][3] output in the output buffer, a multiple of 16
+                                   (the layout packs them; a caller may respace them and out_bytes) */
+    int64_t  hist_off;          /* byte offset of the entry's uint32[256] in the workspace: 1024 k */
+    int32_t  h, w;
+    uint8_t  colour[4];         /* r, g, b, 0 */
+    int32_t  first_unit;        /* index of the entry's first work unit */
+} imgxf_background_list_entry;
+typedef struct imgxf_background_list_unit {
+    int32_t entry, y0, x0;      /* one tile: rows [y0, y0 + tile_h) x columns [x0, x0 + tile_w) of entry `entry`, cut
+                                   at the frame */
+} imgxf_background_list_unit;
+/* The tile of a work unit, for callers and tests that place content on tile seams. */
+int imgxf_background_list_tile(int* tile_h, int* tile_w);
+/* HOST half (no device work).  geometry: int32 [n][5] = (h, w, r, g, b) per entry.  *block_bytes receives the block's
+ * size; block == NULL: only that.  Errors: IMGXF_ERR_NULL; IMGXF_ERR_ARG for n < 0, a side outside 1..32767, a colour
+ * byte outside 0..255; IMGXF_ERR_SHAPE for a block beyond 2 GiB; IMGXF_ERR_WORKSPACE when block_cap is too small. */
+int imgxf_background_list_layout_host(const int32_t* geometry, int n, void* block, size_t block_cap, size_t* block_bytes);
+/* The launches: block_host is the caller's host copy of the block, block_bytes its size, block_dev the same bytes on the
+ * device (8-byte aligned), out the output buffer (16-byte aligned) of out_bytes bytes, q the percentile in 0..100 (the
+ * reference: 70), workspace a device buffer (4-byte aligned) of workspace_bytes >= hist_bytes that the call zeroes.
+ * Dilation iterations are the reference's 3.  Before any device work every record is checked against its frame, the
+ * block, the workspace and the output buffer, and the units against the one tiling of their entries, so that they
+ * bound every address the kernels form (IMGXF_ERR_ARG / IMGXF_ERR_SHAPE / IMGXF_ERR_NULL, never a launch); nothing past
+ * block_bytes is read.  A block without units launches nothing.  No allocation, no synchronisation. */
+int imgxf_background_list_u8(const void* block_host, size_t block_bytes, const void* block_dev, void* out, size_t out_bytes,
+                             double q, void* workspace, size_t workspace_bytes, void* stream);
+/* Device work the last imgxf_background_list_u8 of this thread queued: counts[0] kernel launches, counts[1] memsets
+ * (for tests of the two-launch contract). */
+int imgxf_background_list_last_counts(int* counts);
+
 #ifdef __cplusplus
 }
 #endif
