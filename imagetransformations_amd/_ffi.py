@@ -77,6 +77,7 @@ SIGNATURES = {
     "imgxf_gaussian_cv_fixed_u8": [_VP, _VP, C.c_int, C.c_double, C.c_void_p],
     "imgxf_sepconv_fixed_u8": [_VP, _VP, C.POINTER(C.c_uint16), C.c_int, C.POINTER(C.c_uint16), C.c_int, C.c_int, C.c_void_p],
     "imgxf_conv2d_u8": [_VP, _VP, _F, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "imgxf_conv2d_separable_host": [_F, C.c_int, C.c_int, C.POINTER(C.c_int), _F, _F],
     "imgxf_sobel_u8": [_VP, _VP, C.c_int, C.c_void_p],
     "imgxf_rgb_sobel_mag_u8": [_VP, _VP, C.c_void_p],
     "imgxf_rgb_sobel_u8": [_VP, _VP, C.c_int, C.c_void_p],

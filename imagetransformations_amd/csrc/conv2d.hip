@@ -7,6 +7,7 @@
 // sobel:  LDS-staged L tile (the RGB->L conversion is fused into the tile load for the
 // benchmark variant), exact int32 gradients.
 #include "sobel_march.inc"
+#include "sepconv_route.h"
 #include <string.h>
 #include <algorithm>
 #include <stdlib.h>
@@ -463,6 +464,18 @@ IMGXF_API int imgxf_filter3x3_u8(const imgxf_view* src, const imgxf_view* dst, c
     return launch_status();
 }
 
+IMGXF_API int imgxf_conv2d_separable_host(const float* kernel, int kh, int kw, int* separable, float* kx, float* ky) {
+    if (!kernel || !separable || !kx || !ky) return IMGXF_ERR_NULL;
+    if (kh < 1 || kw < 1 || !(kh & 1) || !(kw & 1) || kh > 15 || kw > 15) return IMGXF_ERR_ARG;
+    float x[15], y[15];
+    *separable = conv2d_rank1_taps(kernel, kh, kw, x, y) ? 1 : 0;
+    if (*separable) {
+        memcpy(kx, x, sizeof(float) * kw);
+        memcpy(ky, y, sizeof(float) * kh);
+    }
+    return IMGXF_OK;
+}
+
 IMGXF_API int imgxf_conv2d_u8(const imgxf_view* src, const imgxf_view* dst, const float* kernel,
                               int kh, int kw, int border, void* stream) {
     IMGXF_CHECK(check_view(src));
@@ -473,29 +486,15 @@ IMGXF_API int imgxf_conv2d_u8(const imgxf_view* src, const imgxf_view* dst, cons
     if (border != IMGXF_BORDER_REFLECT_101 && border != IMGXF_BORDER_REFLECT) return IMGXF_ERR_ARG;
     if (empty_view(src)) return IMGXF_OK;
     // Rank-1 kernels — TransformationPool.motion_blur's single row of 1/size
-    // (/root/reference/pipenline/cifar_image_transformations.py:113-118), box filters, any outer product — are
-    // separable: K = ky (x) kx with kx = the pivot row and ky = the pivot column / pivot.  They run on the
-    // separable kernels (marching / matrix-core Gaussians: 0.6 - 1.1 ms per 64 4K frames instead of 4 - 14 ms
-    // here); the factorisation reproduces K to 1e-6 of its largest entry, inside the 1e-5 contract of this
-    // float filter, and both evaluate sum(w p) in fp32 with one rounding to uint8.
-    if (!knob_set(K_CONV2D_NO_SEPARABLE)) {
-        int pj = 0, pi = 0;
-        double pmax = 0.0;
-        for (int j = 0; j < kh; ++j)
-            for (int i = 0; i < kw; ++i)
-                if (fabs((double)kernel[j * kw + i]) > pmax) { pmax = fabs((double)kernel[j * kw + i]); pj = j; pi = i; }
-        bool rank1 = pmax > 0.0;
-        const double P = kernel[pj * kw + pi];
-        for (int j = 0; j < kh && rank1; ++j)
-            for (int i = 0; i < kw; ++i)
-                if (fabs((double)kernel[j * kw + i] * P - (double)kernel[j * kw + pi] * (double)kernel[pj * kw + i]) > 1e-6 * P * P) { rank1 = false; break; }
-        if (rank1) {
-            float kx[15], ky[15];
-            for (int i = 0; i < kw; ++i) kx[i] = kernel[pj * kw + i];
-            for (int j = 0; j < kh; ++j) ky[j] = (float)((double)kernel[j * kw + pi] / P);
-            const int rc = imgxf_sepconv_u8(src, dst, kx, kw, ky, kh, border, nullptr, stream);
-            if (rc != IMGXF_ERR_UNSUPPORTED) return rc;
-        }
+    // (/root/reference/pipenline/cifar_image_transformations.py:113-118), box filters, any float32 outer product — run on
+    // the separable kernels (marching / matrix-core Gaussians: 0.6 - 1.1 ms per 64 4K frames instead of 4 - 14 ms here).
+    // conv2d_rank1_taps() (sepconv_route.h) decides and factorises: every tap of an accepted kernel is reproduced to 1e-6
+    // of ITSELF, so the factorisation moves no pixel by more than 1e-6 sum|K p|, and both routes evaluate sum(w p) in fp32
+    // with one rounding to uint8.  Two channels (IMGXF_ERR_UNSUPPORTED from the separable entry) stay here.
+    float kx[15], ky[15];
+    if (!knob_set(K_CONV2D_NO_SEPARABLE) && conv2d_rank1_taps(kernel, kh, kw, kx, ky)) {
+        const int rc = imgxf_sepconv_u8(src, dst, kx, kw, ky, kh, border, nullptr, stream);
+        if (rc != IMGXF_ERR_UNSUPPORTED) return rc;
     }
     KernelTaps K; memset(&K, 0, sizeof(K));
     for (int i = 0; i < kh * kw; ++i) K.w[i] = kernel[i];

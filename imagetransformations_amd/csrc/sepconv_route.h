@@ -324,6 +324,32 @@ inline SepconvFamily sepconv_route_c3_dense(bool fixed, int R, int h, int w, con
     return plan.family;
 }
 
+// ---- filter2D's hand-off (imgxf_conv2d_u8, imgxf_conv2d_separable_host) ---------------------------------------------------
+// Whether a dense kh x kw kernel (kh, kw <= 15) goes to the separable dispatcher, and with which taps: kx = the row of the
+// pivot P (the first entry of largest magnitude), ky = the pivot's column / P, both as the float32 values handed on.
+// Accepted when, in double, every tap has |K[j][i] - ky[j] kx[i]| <= 1e-6 |K[j][i]|, so a zero tap needs a zero product.
+// The factorisation then moves a pixel by at most 1e-6 sum|K p|: for taps of one sign a tenth of the 1e-5 contract,
+// for mixed signs the quantity that the dense sum's own fp32 rounding scales with.  Float32 outer products pass (worst tap
+// 2.31e-7 over 20 000 seeded ones); the all-zero kernel and anything holding a NaN do not.
+constexpr double CONV2D_RANK1_REL = 1e-6;
+inline bool conv2d_rank1_taps(const float* K, int kh, int kw, float* kx, float* ky) {
+    int pj = 0, pi = 0;
+    double pmax = 0.0;
+    for (int j = 0; j < kh; ++j)
+        for (int i = 0; i < kw; ++i)
+            if (fabs((double)K[j * kw + i]) > pmax) { pmax = fabs((double)K[j * kw + i]); pj = j; pi = i; }
+    if (!(pmax > 0.0)) return false;
+    const double P = K[pj * kw + pi];
+    for (int i = 0; i < kw; ++i) kx[i] = K[pj * kw + i];
+    for (int j = 0; j < kh; ++j) ky[j] = (float)((double)K[j * kw + pi] / P);
+    for (int j = 0; j < kh; ++j)
+        for (int i = 0; i < kw; ++i) {
+            const double k = K[j * kw + i];
+            if (!(fabs(k - (double)ky[j] * (double)kx[i]) <= CONV2D_RANK1_REL * fabs(k))) return false;
+        }
+    return true;
+}
+
 // cv::getGaussianKernel: binomial kernels for sigma <= 0 and ksize in {1,3,5,7}
 inline double small_gaussian_tab(int ksize, int i) {
     static const double t3[3] = {0.25, 0.5, 0.25}, t5[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};

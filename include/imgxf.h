@@ -106,6 +106,13 @@ int imgxf_sepconv_fixed_u8(const imgxf_view* src, const imgxf_view* dst, const u
  * kernel: HOST pointer, row-major kh*kw floats; kh,kw odd, <= 15. */
 int imgxf_conv2d_u8(const imgxf_view* src, const imgxf_view* dst, const float* kernel, int kh,
                     int kw, int border, void* stream);
+/* HOST only, no device needed: whether imgxf_conv2d_u8 hands this kernel to the separable kernels
+ * (*separable = 1; images of 1, 3 or 4 channels, IMGXF_CONV2D_NO_SEPARABLE unset) and, if so, the
+ * taps it hands on: kx[kw] = the row of the entry of largest magnitude P, ky[kh] = its column / P.
+ * Accepted when every tap has |K[j][i] - ky[j] kx[i]| <= 1e-6 |K[j][i]| in double; kx, ky are left
+ * untouched otherwise.  Same kh, kw limits as imgxf_conv2d_u8. */
+int imgxf_conv2d_separable_host(const float* kernel, int kh, int kw, int* separable, float* kx,
+                                float* ky);
 
 /* ---- a4: scipy.ndimage.sobel(gray_u8)  transformation.py:339 ------------------------
  * src, dst: c == 1.  variant: IMGXF_SOBEL_*.  Border: SciPy 'reflect'. */

@@ -2,7 +2,8 @@
 imagetransformations_amd/csrc, at the default knobs, for tests that must know it without a device
 (test_sepconv_route.py) or that pin a geometry to a kernel (test_gpu_sepconv_channels.py, test_gpu_sepconv_borders.py).
 test_sepconv_route.py holds it to the planner (csrc/sepconv_route.h) through tools/sepconv_launch_trace.hip, so a change
-to the limits in csrc changes this function with it."""
+to the limits in csrc changes this function with it.  conv2d_separable() is no restatement: it asks the library's host
+function whether filter2D hands a kernel to these dispatchers at all."""
 REFLECT_101, REFLECT = 0, 1                     # include/imgxf.h: IMGXF_BORDER_REFLECT_101, IMGXF_BORDER_REFLECT
 
 
@@ -54,6 +55,25 @@ def sepconv_route(c, fixed, R, h, w, *, aligned=True, border=REFLECT_101, sym=Tr
     if (sym or not fixed) and march_max < R <= 15 and _march4_eligible(c, R, h, w, aligned, border):
         return "march4", R
     return "tile", R                                                        # tile_has: R = 1 ... 15
+
+
+def conv2d_separable(K):
+    """(separable, kx, ky) of imgxf_conv2d_separable_host for the kernel K as the library gets it (float32): whether
+    imgxf_conv2d_u8 hands it to the separable dispatcher (images of 1, 3 or 4 channels, default knobs) and the float32
+    taps it hands on.  Not a restatement: the library's own host function, callable without a device."""
+    import ctypes
+
+    import numpy as np
+    from imagetransformations_amd import _ffi
+    k = np.ascontiguousarray(K, np.float32)
+    kh, kw = k.shape
+    sep = ctypes.c_int(-1)
+    kx, ky = np.full(kw, np.nan, np.float32), np.full(kh, np.nan, np.float32)
+    fp = ctypes.POINTER(ctypes.c_float)
+    rc = _ffi.lib.imgxf_conv2d_separable_host(k.ctypes.data_as(fp), kh, kw, ctypes.byref(sep), kx.ctypes.data_as(fp),
+                                              ky.ctypes.data_as(fp))
+    assert rc == _ffi.OK and sep.value in (0, 1), (rc, sep.value)
+    return bool(sep.value), kx, ky
 
 
 def required_instances():

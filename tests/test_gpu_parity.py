@@ -28,6 +28,19 @@ def host(t):
 MFMA_ABS = 0.0             # (was 2^-22 x the largest pixel value until the denormal-alignment loss was understood and cut, see below)
 
 
+def assert_u8_explained(got_u8, ref, tol, quantise, max_tie_fraction=1e-3):
+    """got_u8 == quantise(ref) except where the tolerance explains it: the u8 half of assert_quantised_close."""
+    want = quantise(ref)
+    diff = got_u8.astype(np.int32) - want.astype(np.int32)
+    bad = diff != 0
+    if bad.any():
+        assert np.abs(diff[bad]).max() == 1
+        # every mismatch must be explained by the tolerance: quantising ref +- tol flips it
+        lo, hi = quantise(ref - tol), quantise(ref + tol)
+        assert ((got_u8 == lo) | (got_u8 == hi))[bad].all()
+        assert bad.mean() < max_tie_fraction      # (a sanity bound: structured images put whole classes of pixels on a tie)
+
+
 def assert_quantised_close(got_u8, got_f32, ref_f64, quantise, rel=1e-5, abs_term=0.0, max_tie_fraction=1e-3):
     """got_f32 within rel of ref; got_u8 == quantise(ref) except at boundary ties.
 
@@ -39,15 +52,7 @@ def assert_quantised_close(got_u8, got_f32, ref_f64, quantise, rel=1e-5, abs_ter
     tol = rel * np.maximum(np.abs(ref), 1.0) + abs_term
     err = np.abs(got_f32.astype(np.float64) - ref)
     assert (err <= tol).all(), f"max err {err.max()} (rel {rel})"
-    want = quantise(ref)
-    diff = got_u8.astype(np.int32) - want.astype(np.int32)
-    bad = diff != 0
-    if bad.any():
-        assert np.abs(diff[bad]).max() == 1
-        # every mismatch must be explained by the tolerance: quantising ref +- tol flips it
-        lo, hi = quantise(ref - tol), quantise(ref + tol)
-        assert ((got_u8 == lo) | (got_u8 == hi))[bad].all()
-        assert bad.mean() < max_tie_fraction      # (a sanity bound: structured images put whole classes of pixels on a tie)
+    assert_u8_explained(got_u8, ref, tol, quantise, max_tie_fraction)
 
 
 # ------------------------------------------------------------------ a1 Gaussian

@@ -31,7 +31,16 @@ Which kernel each layout reaches (dispatch conditions of the .hip files):
                  w % 16 == 0, w >= 64, 16-aligned views and 3 iterations, else dilate_kernel.
   conv2d.hip     filter3x3_rows16 (16-aligned views, row bytes >= 48, c != 2) vs filter3x3_kernel;
                  box_h16 / box_v16_run (16-aligned, row bytes % 16 == 0, >= 48, radius <= 4) vs
-                 box_pass_kernel.
+                 box_pass_kernel; conv2d_kernel (conv2d_dense on every layout, conv2d_rank1 with c = 2):
+                 128-byte x 16-row tiles, frame from blockIdx.z, every access through row(f, y) - one kernel
+                 whatever the alignment.
+  sepconv*.hip   conv2d_rank1 (imgxf_conv2d_u8 hands the outer product over: asserted with the library's
+                 host function) and sepconv, radius <= 2 so that no matrix-core kernel is in reach:
+                 sepconv_march_kernel for REFLECT_101 rows above 1024 bytes that are a multiple of 16 with
+                 every view 16-aligned (dense / every_other at w = 352 c = 3, 4 and w = 1040), else
+                 sepconv_tile_kernel (window, fs8 with N = 3, guarded destinations, narrow rows).
+                 The taps of the three are integers over a power of two (is_exact_in_fp32), so every
+                 kernel and every summation order gives the oracle's bytes.
   geometry.hip   mirror_rgb4 (c = 3, w % 4 == 0, 4-aligned) vs flip_kernel; rot90_tile for quarter
                  turns 1 and 3; fill / translate / copy_rect choose uint4 stores per destination alignment.
 The grid-stride tests at the end size their batches from the launchers' grid caps so every
@@ -85,6 +94,36 @@ def batch(rng, n, h, w, c):
         kinds = [kinds[i] for i in rng.permutation(3)]
         kinds = (kinds * n)[:n]
     return np.stack([_frame(rng, k, h, w, c) for k in kinds])
+
+
+# ------------------------------------------------------------------ exact filter taps
+def is_exact_in_fp32(K):
+    """Taps n / 2^s (n integer) with 255 2^s sum|K| < 2^24: every product with a byte and every partial sum, in any
+    order, is an integer multiple of 2^-s below 2^24 of them, so fp32 holds it exactly."""
+    K = np.asarray(K, np.float64)
+    for s in range(25):
+        if np.array_equal(K * 2.0 ** s, np.rint(K * 2.0 ** s)):
+            return 255 * 2.0 ** s * np.abs(K).sum() < 2 ** 24
+    return False
+
+
+def exact_dense_kernel(rng, kh, kw):
+    """Seeded integers over a power of two, gain near 1, rank > 1 (as test_gpu_sepconv_borders._kernels builds them)."""
+    s = max(1, 512 // (kh * kw))
+    while True:
+        n = rng.integers(-s, 3 * s + 1, (kh, kw)).astype(np.float64)
+        if n.sum() > 0 and np.linalg.matrix_rank(n) > 1:
+            K = n / 2.0 ** round(np.log2(n.sum()))
+            assert is_exact_in_fp32(K)
+            return K
+
+
+def exact_vector(rng, n):
+    """n seeded taps k / 16, |k| <= 8, the largest a power of two (8 / 16, either sign): the column / pivot division of
+    filter2D's hand-off is then exact too, and so is every partial sum of the two separable passes."""
+    k = rng.integers(-3, 8, n).astype(np.float64)
+    k[int(rng.integers(n))] = float(rng.choice([-8.0, 8.0]))
+    return k / 16.0
 
 
 # ------------------------------------------------------------------ layouts
@@ -339,6 +378,40 @@ def _ops():
                        ((-1, -1, -1, -1, 9, -1, -1, -1, -1), 1.0, -4.5)][int(rng.integers(3))]
         return ops.filter3x3(P(a), k9, sc, off), per_frame(lambda x: O.filter3x3(x, k9, sc, off), a)
 
+    index_fns = {ops.REFLECT_101: O.reflect101_index, ops.REFLECT: O.reflect_index}
+
+    def filtered(a, K, border=ops.REFLECT_101):
+        return per_frame(lambda x: O.saturate_u8(O.conv2d_f64(x, K, index_fn=index_fns[border])), a)
+
+    def conv2d_route(K):
+        from sepconv_route import conv2d_separable
+        return conv2d_separable(K)[0]
+
+    @add("conv2d_dense", (1, 2, 3, 4))
+    def _(P, a, rng):
+        kh, kw = [(3, 3), (3, 5), (7, 7)][int(rng.integers(3))]
+        border = (ops.REFLECT_101, ops.REFLECT)[int(rng.integers(2))]
+        K = exact_dense_kernel(rng, kh, kw)
+        assert not conv2d_route(K)
+        return ops.conv2d(P(a), K.tolist(), border=border), filtered(a, K, border)
+
+    def rank1_vectors(rng):
+        kx, ky = exact_vector(rng, int(rng.choice([3, 5]))), exact_vector(rng, int(rng.choice([3, 5])))
+        assert is_exact_in_fp32(np.outer(ky, kx)) and is_exact_in_fp32(np.outer(ky / np.abs(ky).max(), kx))
+        return kx, ky
+
+    @add("conv2d_rank1", (1, 2, 3, 4))
+    def _(P, a, rng):
+        kx, ky = rank1_vectors(rng)
+        K = np.outer(ky, kx)
+        assert conv2d_route(K)                                 # separable kernels, but for c = 2 (conv2d_kernel)
+        return ops.conv2d(P(a), K.tolist()), filtered(a, K)
+
+    @add("sepconv", (1, 3, 4))
+    def _(P, a, rng):
+        kx, ky = rank1_vectors(rng)
+        return ops.sepconv(P(a), kx.tolist(), ky.tolist()), filtered(a, np.outer(ky, kx))
+
     @add("box_blur", (1, 2, 3, 4))
     def _(P, a, rng):
         r = float(rng.choice([0.0, 1.0, 2.5, 6.0]))
@@ -422,7 +495,7 @@ OP_NAMES = ["scale_abs", "blend_image_image", "blend_colour_image", "blend_image
             "add_noise_f64", "shot_noise_finish", "impulse_noise", "permute_channels", "composite", "composite_const",
             "rgb2l", "enhance_color", "enhance_contrast", "lut_256", "lut_per_channel", "posterize", "solarize",
             "equalize", "channel_histogram", "rgb2yuv", "yuv2rgb", "equalize_hist_cv", "percentile_mask",
-            "dilate_cross", "filter3x3", "box_blur", "gaussian_blur_pil", "enhance_sharpness", "flip", "rot90", "crop",
+            "dilate_cross", "filter3x3", "conv2d_dense", "conv2d_rank1", "sepconv", "box_blur", "gaussian_blur_pil", "enhance_sharpness", "flip", "rot90", "crop",
             "copy_rect", "translate", "new"]
 
 
@@ -453,7 +526,8 @@ def _seed(*parts):
 
 # ops that also take a 2-D [H,W] frame
 PLANE_OPS = {"scale_abs", "blend_image_image", "brightness", "enhance_contrast", "lut_256", "posterize", "solarize",
-             "equalize", "channel_histogram", "percentile_mask", "dilate_cross", "filter3x3", "box_blur",
+             "equalize", "channel_histogram", "percentile_mask", "dilate_cross", "filter3x3", "conv2d_dense",
+             "conv2d_rank1", "sepconv", "box_blur",
              "gaussian_blur_pil", "enhance_sharpness", "flip", "rot90", "crop", "copy_rect", "translate", "new"}
 # ops whose destination is not a single fresh image of the wrapper (histogram tensor, an
 # intermediate image, a caller-given destination)
