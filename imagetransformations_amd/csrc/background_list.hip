@@ -5,9 +5,9 @@
 //   with e = ndimage.sobel(np.array(img.convert("L")))            (the x-derivative, 'reflect' border, stored mod 256)
 // bit for bit, for frames from 1 x 1 up, rows at any stride and byte offset, read in place.
 //
-// HOST half (imgxf_background_list_layout_host, no device work): one block of
-//   header | entry records | work units
-// A work unit is one BGL_TH x BGL_TW tile of one entry (row-major inside the entry, entries in order).
+// HOST half (imgxf_background_list_layout_host, no device work; the block protocol is list_layout.h's): one block of
+// header | entry records | work units.  A work unit is one BGL_TH x BGL_TW tile of one entry (row-major inside the entry,
+// entries in order).
 //
 // DEVICE half, after one hipMemsetAsync of the histogram workspace (1 KiB per entry, never uploaded):
 //   bgl_hist_kernel     a workgroup takes BGL_HIST_GROUP consecutive units: stages each tile's RGB with a one-pixel halo,
@@ -24,8 +24,8 @@
 // L is luma_u8 (imgxf_common.h), which sobel_kernel's FROM_RGB loader spells out in place; the Sobel statement is
 // RESTATED here (bgl_sobel_x): sharing it would mean editing sobel_kernel, whose assembly is pinned by its profile.
 #include "imgxf_common.h"
+#include "list_layout.h"
 #include "percentile.h"
-#include <string.h>
 
 namespace imgxf {
 
@@ -34,6 +34,7 @@ constexpr int BGL_THREADS = 256;
 constexpr int BGL_HIST_GROUP = 4;         // units per workgroup of the histogram launch: a quarter of the global atomics
 constexpr int BGL_HIST_BYTES = 256 * 4;   // one entry's histogram in the workspace
 
+using BglBlock = ListBlock<imgxf_background_list_header, imgxf_background_list_entry, imgxf_background_list_unit>;
 static thread_local int bgl_counts[2] = {0, 0};
 
 // The LDS images of a tile with a halo of HALO pixels
@@ -241,12 +242,9 @@ int background_list_check(const void* block_host, size_t block_bytes, size_t out
     if (hd.n_entries < 0 || hd.n_units < 0 || hd.total_bytes < 0 || hd.tile_h != BGL_TH || hd.tile_w != BGL_TW)
         return IMGXF_ERR_ARG;
     const int64_t total = hd.total_bytes;
-    if ((size_t)total > block_bytes || hd.entries_off < (int64_t)sizeof(imgxf_background_list_header) || (hd.entries_off & 7) ||
-        (hd.units_off & 3))
-        return IMGXF_ERR_ARG;
-    const int64_t entries_end = (int64_t)hd.entries_off + (int64_t)hd.n_entries * (int64_t)sizeof(imgxf_background_list_entry);
-    if (entries_end > total || hd.units_off < entries_end ||
-        (int64_t)hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_background_list_unit) > total)
+    if ((size_t)total > block_bytes ||                            // (no tables: the units end the block)
+        !BglBlock::pl_check_sections(hd.n_entries, hd.n_units, hd.entries_off, hd.units_off,
+                                     hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_background_list_unit), total))
         return IMGXF_ERR_ARG;
     const imgxf_background_list_entry* entries = (const imgxf_background_list_entry*)(hb + hd.entries_off);
     const imgxf_background_list_unit* units = (const imgxf_background_list_unit*)(hb + hd.units_off);
@@ -254,10 +252,8 @@ int background_list_check(const void* block_host, size_t block_bytes, size_t out
     for (int i = 0; i < hd.n_entries; ++i) {
         const imgxf_background_list_entry& e = entries[i];
         if (!e.data) return IMGXF_ERR_NULL;
-        if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.row_stride < (int64_t)e.w * 3) return IMGXF_ERR_SHAPE;
-        if (e.out_off < 0 || (e.out_off & 15) || (uint64_t)e.out_off > out_bytes ||
-            (uint64_t)e.h * e.w * 3 > out_bytes - (uint64_t)e.out_off)
-            return IMGXF_ERR_ARG;
+        if (!ll_frame_ok(e.h, e.w, e.row_stride)) return IMGXF_ERR_SHAPE;
+        if (!ll_output_ok(e.out_off, e.h, e.w, out_bytes)) return IMGXF_ERR_ARG;
         if (e.hist_off < 0 || (e.hist_off & 3) || (uint64_t)e.hist_off > workspace_bytes ||
             (uint64_t)BGL_HIST_BYTES > workspace_bytes - (uint64_t)e.hist_off)
             return IMGXF_ERR_ARG;
@@ -295,27 +291,18 @@ IMGXF_API int imgxf_background_list_layout_host(const int32_t* geometry, int n, 
     size_t n_units = 0;
     for (int i = 0; i < n; ++i) {
         const int32_t* g = geometry + 5 * (size_t)i;
-        if (g[0] < 1 || g[1] < 1 || g[0] > 32767 || g[1] > 32767) return IMGXF_ERR_ARG;
+        if (!ll_size_ok(g[0], g[1])) return IMGXF_ERR_ARG;
         if (g[2] < 0 || g[2] > 255 || g[3] < 0 || g[3] > 255 || g[4] < 0 || g[4] > 255) return IMGXF_ERR_ARG;
         n_units += (size_t)bgl_tiles(g[0], g[1]);
     }
-    const size_t entries_off = sizeof(imgxf_background_list_header);
-    const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_background_list_entry);
-    const size_t total = (units_off + n_units * sizeof(imgxf_background_list_unit) + 15) & ~(size_t)15;
-    if (total > 0x7fffffffu) return IMGXF_ERR_SHAPE;
-    *block_bytes = total;
+    BglBlock B;
+    IMGXF_CHECK(B.open((size_t)n, n_units, 0, block, block_cap, block_bytes));
     if (!block) return IMGXF_OK;                                  // the size alone
-    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
 
-    u8* out = (u8*)block;
-    memset(out, 0, total);
-    imgxf_background_list_header* hd = (imgxf_background_list_header*)out;
-    imgxf_background_list_entry* entries = (imgxf_background_list_entry*)(out + entries_off);
-    imgxf_background_list_unit* units = (imgxf_background_list_unit*)(out + units_off);
     size_t upos = 0, opos = 0;
     for (int i = 0; i < n; ++i) {
         const int32_t* g = geometry + 5 * (size_t)i;
-        imgxf_background_list_entry& e = entries[i];
+        imgxf_background_list_entry& e = B.records[i];
         e.h = g[0]; e.w = g[1];
         e.colour[0] = (u8)g[2]; e.colour[1] = (u8)g[3]; e.colour[2] = (u8)g[4];
         e.out_off = (int64_t)opos;
@@ -324,12 +311,13 @@ IMGXF_API int imgxf_background_list_layout_host(const int32_t* geometry, int n, 
         opos += ((size_t)e.h * e.w * 3 + 15) & ~(size_t)15;
         for (int y0 = 0; y0 < e.h; y0 += BGL_TH)
             for (int x0 = 0; x0 < e.w; x0 += BGL_TW) {
-                imgxf_background_list_unit& u = units[upos++];
+                imgxf_background_list_unit& u = B.units[upos++];
                 u.entry = i; u.y0 = y0; u.x0 = x0;
             }
     }
+    imgxf_background_list_header* hd = B.hd;
     hd->n_entries = n; hd->n_units = (int32_t)n_units;
-    hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->total_bytes = (int32_t)total;
+    hd->entries_off = (int32_t)B.records_off; hd->units_off = (int32_t)B.units_off; hd->total_bytes = (int32_t)B.total;
     hd->tile_h = BGL_TH; hd->tile_w = BGL_TW;
     hd->out_bytes = (int64_t)opos; hd->hist_bytes = (int64_t)n * BGL_HIST_BYTES;
     return IMGXF_OK;

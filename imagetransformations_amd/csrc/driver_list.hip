@@ -6,13 +6,12 @@
 // taken where the per-type dispatcher itself would use the LDS-tiled kernel (sepconv_route.h answers that on the host),
 // whose statements the blur units compile too; the others are refused to the caller's route.
 //
-// HOST half (imgxf_driver_list_layout_host, no device work): from each entry's geometry and parameters one block of
-//   header | entry records | work units | coefficient tables
-// Lanczos tables are precompute_coeffs' (build_coeffs, resample_coeffs.h), sliced to the centre-crop window for factors
-// above 1 as resize_crop's plans slice them; a crop's are the BICUBIC ones for (cs -> 32).  Entries of equal (filter, in,
-// out, window) on an axis share one table, so host work grows with the number of distinct geometries, and two crops of
-// one size share theirs whatever corners they drew.  Rotation matrices are ops.rotate_matrix's (Python's round(., 15) in
-// double) and go into the record as libImaging's 16.16 coefficients.
+// HOST half (imgxf_driver_list_layout_host, no device work; the block protocol, the record predicates and the axis tables
+// are list_layout.h's): a planner per type fills each entry's record from its geometry and parameters, then one block of
+// header | entry records | work units | coefficient tables is filled section by section (dl_section).  Lanczos tables are
+// sliced to the centre-crop window for factors above 1 as resize_crop's plans slice them; a crop's are the BICUBIC ones
+// for (cs -> 32), so two crops of one size share theirs whatever corners they drew.  Rotation matrices are
+// ops.rotate_matrix's (Python's round(., 15) in double) and go into the record as libImaging's 16.16 coefficients.
 //
 // DEVICE half (imgxf_driver_list_u8): one copy of the block, at most three launches plus one per distinct (fixed, radius)
 // among the blur units (driver_list_blur.hip).  One workgroup per work unit = a band of output rows of one entry; the
@@ -44,8 +43,6 @@
 namespace imgxf {
 
 constexpr int DL_THREADS = PL_THREADS;
-constexpr int DL_UNIT_ROWS = 16;          // window rows per scale unit when the LDS budget allows
-constexpr int DL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB
 constexpr int DL_PLAIN_BYTES = 24 * 1024; // output bytes per unit of the types without LDS (at least one row)
 constexpr int DL_CROP_OUT = 32;           // rand_crop resizes its window to 32 x 32
 constexpr int DL_BLUR_ROWS = 32;          // output rows per blur unit: sepconv_tile_kernel's tile height
@@ -60,6 +57,7 @@ static inline int dl_blur_lds(int ks) { return (DL_BLUR_ROWS + ks - 1) * 256 * (
 static inline bool dl_resamples(int op) { return op == IMGXF_DRIVER_SCALE || op == IMGXF_DRIVER_CROP_RESIZE; }
 
 struct DlGeom { int frame, type, h, w, c; };
+using DlBlock = ListBlock<imgxf_driver_header, imgxf_driver_entry, imgxf_driver_unit>;
 
 // Python's float % float
 static inline double py_mod(double a, double b) {
@@ -90,15 +88,6 @@ static int dl_rotation(int w, int h, double angle, int fx[6]) {
     if (m[1] == 0.0 && m[3] == 0.0) return 3;
     affine_fixed_matrix(m, fx);
     return 0;
-}
-
-// Window rows per scale unit (pl_unit_rows, resample_list.h) of an entry that resizes h -> nh rows with ksy taps and
-// touches at most ncols source columns; *lds: the bound on such a unit's LDS
-static int dl_unit_rows(int h, int nh, int ksy, int win_h, int win_w, int ncols, int lds_budget, int* lds) {
-    auto need = [&](int ny) { return pl_lds_bytes(pl_rows_bound(ny, h, nh, ksy), win_w, ncols); };
-    const int ny = pl_unit_rows(std::min(win_h, DL_UNIT_ROWS), lds_budget, need);
-    if (ny) *lds = std::max(*lds, (int)need(ny));
-    return ny;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -243,44 +232,34 @@ __global__ __launch_bounds__(DL_THREADS) void driver_list_scale_kernel(const u8*
             });
 }
 
-} // namespace imgxf
+// ---------------------------------------------------------------------------------------------------------------------
+// HOST half.  The units lie in four sections, in launch order; an op's section says which
+enum { DL_PLAIN = 0, DL_PERSP = 1, DL_RESAMPLE = 2, DL_BLUR = 3, DL_SECTIONS = 4 };
+static inline int dl_section(int op) {
+    return dl_blurs(op) ? DL_BLUR : dl_resamples(op) ? DL_RESAMPLE : op == IMGXF_DRIVER_PERSPECTIVE ? DL_PERSP : DL_PLAIN;
+}
+// Output rows per unit of an accepted entry of `section`: whole tiles of perspective_tile.h, sepconv_tile_kernel's tile
+// height, DL_PLAIN_BYTES of output (at least one row); a resample entry's rows are planned from its LDS (dl_unit_rows)
+static inline int dl_section_rows(int section, const imgxf_driver_entry& e) {
+    return section == DL_PERSP ? PV_TH : section == DL_BLUR ? DL_BLUR_ROWS : section == DL_RESAMPLE ? e.unit_rows
+                                                                           : std::max(1, DL_PLAIN_BYTES / (e.ow * 3));
+}
+// The first unit of `section` by a header's counts (checked: none negative, their sum within n_units); DL_SECTIONS: the end
+static inline int dl_section_first(const imgxf_driver_header& hd, int section) {
+    const int first[DL_SECTIONS + 1] = {0, hd.n_plain, hd.n_plain + hd.n_persp, hd.n_units - hd.n_blur, hd.n_units};
+    return first[section];
+}
 
-using namespace imgxf;
-
-IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const double* params, int n, int lds_budget, void* block,
-                                            size_t block_cap, size_t* block_bytes, int64_t* out_off, int32_t* out_hw,
-                                            int32_t* status, size_t* out_bytes, int32_t* lds_bytes) {
-    if (!block_bytes || (n > 0 && (!geometry || !params))) return IMGXF_ERR_NULL;
-    if (n < 0 || lds_budget < 1) return IMGXF_ERR_ARG;
-    if (lds_budget > DL_MAX_LDS) lds_budget = DL_MAX_LDS;
-    const DlGeom* geo = (const DlGeom*)geometry;
-
-    // pass over geometry and parameters alone: every record but its tables, which axes share tables -> the sections' sizes
-    struct Axis { int filter, in, out, first, count, ks, bounds, coeffs; };
-    std::map<std::array<int, 5>, int> axis_index;
-    std::vector<Axis> axes;
-    size_t table_words = 0;
-    auto axis_of = [&](int filter, int in, int out, int first, int count) {
-        const std::array<int, 5> key = {filter, in, out, first, count};
-        auto it = axis_index.find(key);
-        if (it != axis_index.end()) return it->second;
-        Axis a = {filter, in, out, first, count, coeff_ksize(in, out, filter), -1, -1};
-        table_words += (size_t)count * (2 + a.ks);
-        axis_index.emplace(key, (int)axes.size());
-        axes.push_back(a);
-        return (int)axes.size() - 1;
-    };
-    // a Gaussian's taps, shared by the entries of equal (code, ksize, sigma): imgxf_gaussian_u8's / imgxf_gaussian_cv_fixed_u8's
-    const SepconvKnobs sepconv_knobs_now = sepconv_knobs();
+// A Gaussian's taps, shared by the entries of equal (code, ksize, sigma): imgxf_gaussian_u8's / imgxf_gaussian_cv_fixed_u8's.
+// Like AxisTables: `intern` while planning (an accepted entry counts the words once), placed in the block on first use.
+struct DlBlurTaps {
     struct Blur { int rc, ks, coeffs; bool used; Taps taps; };
-    std::map<std::array<int64_t, 3>, int> blur_index;
-    std::vector<Blur> blurs;
-    auto blur_of = [&](int code, int ksize, double sigma) {
+    size_t words = 0;
+    int intern(int code, int ksize, double sigma) {
         int64_t bits;
         memcpy(&bits, &sigma, 8);
-        const std::array<int64_t, 3> key = {code, ksize, bits};
-        auto it = blur_index.find(key);
-        if (it != blur_index.end()) return it->second;
+        const auto made = index.emplace(std::array<int64_t, 3>{code, ksize, bits}, (int)blurs.size());
+        if (!made.second) return made.first->second;
         Blur b;
         memset(&b, 0, sizeof(b));
         const int R = std::max(1, ksize / 2);                 // run_sepconv: a single tap is centred in three
@@ -295,358 +274,368 @@ IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const doubl
         }
         if (b.rc == IMGXF_OK)
             for (int i = 0; i < ksize; ++i) b.taps.x[R - ksize / 2 + i] = b.taps.y[R - ksize / 2 + i] = kf[i];
-        blur_index.emplace(key, (int)blurs.size());
         blurs.push_back(b);
-        return (int)blurs.size() - 1;
-    };
-    std::vector<imgxf_driver_entry> recs((size_t)n);
-    std::vector<int> ax((size_t)n, -1), ay((size_t)n, -1);
-    std::vector<int> blurred;                                 // the accepted blur entries
-    size_t n_plain = 0, n_persp = 0, n_scale = 0, n_blur = 0;
-    uint64_t opos = 0;
-    int lds_bound = 0;
-    for (int i = 0; i < n; ++i) {
-        const DlGeom& g = geo[i];
-        const double p0 = params[2 * i], p1 = params[2 * i + 1];
-        imgxf_driver_entry& e = recs[i];
-        memset(&e, 0, sizeof(e));
-        e.frame = g.frame; e.op = g.type; e.h = g.h; e.w = g.w; e.oh = g.h; e.ow = g.w; e.out_off = -1;
-        int st = IMGXF_DRIVER_OK;
-        if (g.c != 3 || g.h < 1 || g.w < 1 || g.h > 32767 || g.w > 32767) {
-            st = IMGXF_DRIVER_REFUSED_FORMAT;
-        } else if (g.type == IMGXF_DRIVER_SCALE) {
-            const double fw = g.w * p0, fh = g.h * p0;
-            if (!(fw >= 1.0) || !(fh >= 1.0)) st = IMGXF_DRIVER_REFUSED_SIZE;           // int(w s) or int(h s) below 1 (or NaN)
-            else if (fw > 16777216.0 || fh > 16777216.0) st = IMGXF_DRIVER_REFUSED_OTHER;
-            else {
-                const int nw = (int)fw, nh = (int)fh;
-                int xfirst = 0, yfirst = 0;
-                if (p0 > 1.0) {                               // resize + centre crop: only the window is computed
-                    xfirst = (nw - g.w) / 2; yfirst = (nh - g.h) / 2;
-                    e.win_w = g.w; e.win_h = g.h;
-                } else if (p0 < 1.0) {                        // resize, pasted on a black canvas
-                    e.win_w = nw; e.win_h = nh;
-                    e.win_left = (g.w - nw) / 2; e.win_top = (g.h - nh) / 2;
-                } else {                                      // factor 1: a resize to the same size
-                    e.win_w = nw; e.win_h = nh; e.oh = nh; e.ow = nw;
-                }
-                e.in_h = g.h; e.in_w = g.w;
-                e.ksx = coeff_ksize(g.w, nw, IMGXF_RESAMPLE_LANCZOS);
-                e.ksy = coeff_ksize(g.h, nh, IMGXF_RESAMPLE_LANCZOS);
-                e.unit_rows = dl_unit_rows(g.h, nh, e.ksy, e.win_h, e.win_w, pl_rows_bound(e.win_w, g.w, nw, e.ksx), lds_budget,
-                                           &lds_bound);
-                if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
-                else {
-                    ax[i] = axis_of(IMGXF_RESAMPLE_LANCZOS, g.w, nw, xfirst, e.win_w);
-                    ay[i] = axis_of(IMGXF_RESAMPLE_LANCZOS, g.h, nh, yfirst, e.win_h);
-                }
-            }
-        } else if (g.type == IMGXF_DRIVER_ROTATION) {
-            if (!isfinite(p0)) st = IMGXF_DRIVER_REFUSED_OTHER;
-            else {
-                const int kind = dl_rotation(g.w, g.h, -p0, e.fx);       // apply_rotation: img.rotate(-angle)
-                if (kind == 1) e.op = IMGXF_DRIVER_TRANSLATION;          // a copy
-                else if (kind == 2) st = IMGXF_DRIVER_REFUSED_TURN;
-                else if (kind == 3) st = IMGXF_DRIVER_REFUSED_OTHER;
-            }
-        } else if (g.type == IMGXF_DRIVER_BRIGHTNESS) {
-            e.alpha = (float)p0;
-        } else if (g.type == IMGXF_DRIVER_CONTRAST) {
-            e.alpha = (float)p0; e.beta = 0.0f;
-        } else if (g.type == IMGXF_DRIVER_SHEAR) {
-            const double shift = ceil(p0 * g.h);
-            if (!isfinite(p0) || !(shift > -(double)g.w) || g.w + shift > 32767.0) st = IMGXF_DRIVER_REFUSED_OTHER;
-            else {
-                e.ow = g.w + (int)shift;
-                e.m1 = p0; e.m2 = p0 > 0 ? -(double)(int)shift : 0.0;
-            }
-        } else if (g.type == IMGXF_DRIVER_TRANSLATION) {
-            if (!isfinite(p0) || !isfinite(p1)) st = IMGXF_DRIVER_REFUSED_OTHER;
-            else {                                            // int(tx), int(ty); beyond the frame every shift gives the fill alone
-                e.dx = (int)std::max(-(double)g.w, std::min((double)g.w, trunc(p0)));
-                e.dy = (int)std::max(-(double)g.h, std::min((double)g.h, trunc(p1)));
-            }
-        } else if (g.type == IMGXF_DRIVER_CROP_RESIZE) {
-            const int cs = (int)(0.78 * g.w);                 // int(0.78 * w), in double as Python evaluates it
-            if (cs < 1) st = IMGXF_DRIVER_REFUSED_SIZE;
-            else if (!isfinite(p0) || !isfinite(p1) || p0 < 0.0 || p1 < 0.0 || p0 + cs > g.w || p1 + cs > g.h)
-                st = IMGXF_DRIVER_REFUSED_OTHER;              // the window is not inside the frame
-            else {
-                const int side = DL_CROP_OUT;
-                e.dx = (int)p0; e.dy = (int)p1;
-                e.in_h = cs; e.in_w = cs;
-                e.oh = e.ow = e.win_h = e.win_w = side;
-                e.ksx = e.ksy = coeff_ksize(cs, side, IMGXF_RESAMPLE_BICUBIC);
-                e.unit_rows = dl_unit_rows(cs, side, e.ksy, side, side, pl_rows_bound(side, cs, side, e.ksx), lds_budget,
-                                           &lds_bound);
-                if (!e.unit_rows) st = IMGXF_DRIVER_REFUSED_LDS;
-                else ax[i] = ay[i] = axis_of(IMGXF_RESAMPLE_BICUBIC, cs, side, 0, side);
-            }
-        } else if (dl_blurs(g.type)) {
-            if (p0 == 0.0) st = IMGXF_DRIVER_REFUSED_SIZE;    // the drivers hand back the input object itself
-            else if (!(p0 >= 1.0 && p0 <= 31.0) || p0 != floor(p0) || !((int)p0 & 1)) st = IMGXF_DRIVER_REFUSED_OTHER;
-            else {
-                const bool fixed = g.type == IMGXF_DRIVER_BLUR_FIXED;
-                ax[i] = blur_of(g.type, (int)p0, p1);
-                Blur& b = blurs[ax[i]];
-                // float: only where the per-type route would run these statements too; the fixed-point families are
-                // integer-exact and agree to the byte
-                if (b.rc != IMGXF_OK) st = IMGXF_DRIVER_REFUSED_OTHER;
-                else if (!fixed && sepconv_route_c3_dense(false, b.ks / 2, g.h, g.w, b.taps, sepconv_knobs_now) != SEPCONV_TILE)
-                    st = IMGXF_DRIVER_REFUSED_FAMILY;
-                else if (dl_blur_lds(b.ks) > lds_budget) st = IMGXF_DRIVER_REFUSED_LDS;
-                else {
-                    e.ksx = e.ksy = b.ks;
-                    if (!b.used) { b.used = true; table_words += (size_t)b.ks; }
-                }
-            }
-        } else if (g.type != IMGXF_DRIVER_NOISE && g.type != IMGXF_DRIVER_FLIP && g.type != IMGXF_DRIVER_PERSPECTIVE) {
-            st = IMGXF_DRIVER_REFUSED_OTHER;
-        }
-        e.status = st;
-        if (st == IMGXF_DRIVER_OK) {
-            e.out_off = (int64_t)opos;
-            // outputs start on multiples of 48: 16-byte aligned, and whole pixels into the block, so that the block as ONE
-            // run of RGB pixels can be expanded or copied without knowing where its outputs are
-            opos = (opos + (uint64_t)e.oh * e.ow * 3 + 47) / 48 * 48;
-            if (dl_resamples(g.type)) {
-                n_scale += (size_t)(e.win_h + e.unit_rows - 1) / e.unit_rows;
-            } else if (g.type == IMGXF_DRIVER_PERSPECTIVE) {
-                e.unit_rows = PV_TH;
-                n_persp += (size_t)(e.oh + PV_TH - 1) / PV_TH;
-            } else if (dl_blurs(g.type)) {
-                e.unit_rows = DL_BLUR_ROWS;
-                n_blur += (size_t)(e.oh + DL_BLUR_ROWS - 1) / DL_BLUR_ROWS;
-                blurred.push_back(i);
-            } else {
-                e.unit_rows = std::max(1, DL_PLAIN_BYTES / (e.ow * 3));
-                n_plain += (size_t)(e.oh + e.unit_rows - 1) / e.unit_rows;
-            }
-        } else {
-            e.unit_rows = 0;
-        }
-        if (out_off) out_off[i] = e.out_off;
-        if (out_hw) { out_hw[2 * i] = e.oh; out_hw[2 * i + 1] = e.ow; }
-        if (status) status[i] = st;
+        return made.first->second;
     }
-    const size_t n_units = n_plain + n_persp + n_scale + n_blur;
-    const size_t entries_off = sizeof(imgxf_driver_header);
-    const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_driver_entry);
-    const size_t tables_off = units_off + n_units * sizeof(imgxf_driver_unit);
-    const size_t total = (tables_off + table_words * 4 + 15) & ~(size_t)15;
-    if (total > 0x7fffffffu || n_units > 0x7fffffffu || opos > ((uint64_t)1 << 40)) return IMGXF_ERR_SHAPE;
-    *block_bytes = total;
-    if (out_bytes) *out_bytes = (size_t)opos;
-    if (lds_bytes) *lds_bytes = lds_bound;                    // an upper bound; with a block: the largest unit's own need
-    if (!block) return IMGXF_OK;
-    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
+    std::map<std::array<int64_t, 3>, int> index;
+    std::vector<Blur> blurs;
+};
 
-    u8* out = (u8*)block;
-    memset(out, 0, total);
-    imgxf_driver_header* hd = (imgxf_driver_header*)out;
-    imgxf_driver_entry* entries = (imgxf_driver_entry*)(out + entries_off);
-    imgxf_driver_unit* units = (imgxf_driver_unit*)(out + units_off);
-    int32_t* words = (int32_t*)out;
-    size_t tpos = tables_off / 4;
-    auto build_axis = [&](Axis& a) {
-        if (a.bounds < 0) pl_append_axis(a.in, a.out, a.filter, a.ks, a.first, a.count, words, tpos, &a.bounds, &a.coeffs);
-    };
-    size_t upos = 0;
-    int lds_max = 0;
-    for (int warp = 0; warp < 2; ++warp)                      // the units without LDS first: they are the first launch;
-        for (int i = 0; i < n; ++i) {                         // then the perspective units, the second
-            imgxf_driver_entry& e = recs[i];
-            if (e.status != IMGXF_DRIVER_OK || dl_resamples(geo[i].type) || dl_blurs(geo[i].type) ||
-                (geo[i].type == IMGXF_DRIVER_PERSPECTIVE) != (warp == 1))
-                continue;
-            for (int y0 = 0; y0 < e.oh; y0 += e.unit_rows) {
-                imgxf_driver_unit& u = units[upos++];
-                u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, e.oh - y0); u.lds_bytes = 0;
+// What the planners of one layout call share (lds_bound: the largest resample unit's LDS as the geometry alone bounds it),
+// and what a planner notes for the fill pass beside the record: a resample entry's axes, a blur entry's taps (in x)
+struct DlPlanner { int lds_budget; SepconvKnobs knobs; AxisTables axes; DlBlurTaps blurs; int lds_bound = 0; };
+struct DlTables { int x = -1, y = -1; };
+
+// The planners: one per type, from the entry's geometry and drawn values to its record (all but table offsets, spans and
+// out_off) and its IMGXF_DRIVER_* status.  A refused entry keeps what its planner had written when it refused.
+// Scale and crop end in dl_plan_window: the resample of an in_h x in_w source to nh x nw, of which the record's window
+// from (yfirst, xfirst) is computed — taps, window rows per unit (P.lds_bound raised to such a unit's LDS), the axes
+static int dl_plan_window(int filter, int in_h, int in_w, int nh, int nw, int yfirst, int xfirst, DlPlanner& P,
+                          imgxf_driver_entry& e, DlTables& t) {
+    e.in_h = in_h; e.in_w = in_w;
+    e.ksx = coeff_ksize(in_w, nw, filter);
+    e.ksy = coeff_ksize(in_h, nh, filter);
+    const int ncols = pl_rows_bound(e.win_w, in_w, nw, e.ksx);
+    auto need = [&](int ny) { return pl_lds_bytes(pl_rows_bound(ny, in_h, nh, e.ksy), e.win_w, ncols); };
+    e.unit_rows = pl_unit_rows(e.win_h, P.lds_budget, need);
+    if (!e.unit_rows) return IMGXF_DRIVER_REFUSED_LDS;
+    P.lds_bound = std::max(P.lds_bound, (int)need(e.unit_rows));
+    t.x = P.axes.intern(filter, in_w, nw, xfirst, e.win_w);
+    t.y = P.axes.intern(filter, in_h, nh, yfirst, e.win_h);
+    return IMGXF_DRIVER_OK;
+}
+
+static int dl_plan_scale(const DlGeom& g, double s, DlPlanner& P, imgxf_driver_entry& e, DlTables& t) {
+    const double fw = g.w * s, fh = g.h * s;
+    if (!(fw >= 1.0) || !(fh >= 1.0)) return IMGXF_DRIVER_REFUSED_SIZE;         // int(w s) or int(h s) below 1 (or NaN)
+    if (fw > 16777216.0 || fh > 16777216.0) return IMGXF_DRIVER_REFUSED_OTHER;
+    const int nw = (int)fw, nh = (int)fh;
+    int xfirst = 0, yfirst = 0;
+    if (s > 1.0) {                                            // resize + centre crop: only the window is computed
+        xfirst = (nw - g.w) / 2; yfirst = (nh - g.h) / 2;
+        e.win_w = g.w; e.win_h = g.h;
+    } else if (s < 1.0) {                                     // resize, pasted on a black canvas
+        e.win_w = nw; e.win_h = nh;
+        e.win_left = (g.w - nw) / 2; e.win_top = (g.h - nh) / 2;
+    } else {                                                  // factor 1: a resize to the same size
+        e.win_w = nw; e.win_h = nh; e.oh = nh; e.ow = nw;
+    }
+    return dl_plan_window(IMGXF_RESAMPLE_LANCZOS, g.h, g.w, nh, nw, yfirst, xfirst, P, e, t);
+}
+
+static int dl_plan_rotation(const DlGeom& g, double angle, imgxf_driver_entry& e) {
+    if (!isfinite(angle)) return IMGXF_DRIVER_REFUSED_OTHER;
+    const int kind = dl_rotation(g.w, g.h, -angle, e.fx);     // apply_rotation: img.rotate(-angle)
+    if (kind == 1) e.op = IMGXF_DRIVER_TRANSLATION;           // a copy
+    return kind == 2 ? IMGXF_DRIVER_REFUSED_TURN : kind == 3 ? IMGXF_DRIVER_REFUSED_OTHER : IMGXF_DRIVER_OK;
+}
+
+static int dl_plan_shear(const DlGeom& g, double m, imgxf_driver_entry& e) {
+    const double shift = ceil(m * g.h);
+    if (!isfinite(m) || !(shift > -(double)g.w) || g.w + shift > 32767.0) return IMGXF_DRIVER_REFUSED_OTHER;
+    e.ow = g.w + (int)shift;
+    e.m1 = m; e.m2 = m > 0 ? -(double)(int)shift : 0.0;
+    return IMGXF_DRIVER_OK;
+}
+
+static int dl_plan_translation(const DlGeom& g, double tx, double ty, imgxf_driver_entry& e) {
+    if (!isfinite(tx) || !isfinite(ty)) return IMGXF_DRIVER_REFUSED_OTHER;
+    e.dx = (int)std::max(-(double)g.w, std::min((double)g.w, trunc(tx)));    // int(tx), int(ty); beyond the frame every
+    e.dy = (int)std::max(-(double)g.h, std::min((double)g.h, trunc(ty)));    // shift gives the fill alone
+    return IMGXF_DRIVER_OK;
+}
+
+static int dl_plan_crop(const DlGeom& g, double left, double top, DlPlanner& P, imgxf_driver_entry& e, DlTables& t) {
+    const int cs = (int)(0.78 * g.w);                         // int(0.78 * w), in double as Python evaluates it
+    if (cs < 1) return IMGXF_DRIVER_REFUSED_SIZE;
+    if (!isfinite(left) || !isfinite(top) || left < 0.0 || top < 0.0 || left + cs > g.w || top + cs > g.h)
+        return IMGXF_DRIVER_REFUSED_OTHER;                    // the window is not inside the frame
+    const int side = DL_CROP_OUT;
+    e.dx = (int)left; e.dy = (int)top;
+    e.oh = e.ow = e.win_h = e.win_w = side;
+    return dl_plan_window(IMGXF_RESAMPLE_BICUBIC, cs, cs, side, side, 0, 0, P, e, t);
+}
+
+static int dl_plan_blur(const DlGeom& g, double ksize, double sigma, DlPlanner& P, imgxf_driver_entry& e, DlTables& t) {
+    if (ksize == 0.0) return IMGXF_DRIVER_REFUSED_SIZE;       // the drivers hand back the input object itself
+    if (!(ksize >= 1.0 && ksize <= 31.0) || ksize != floor(ksize) || !((int)ksize & 1)) return IMGXF_DRIVER_REFUSED_OTHER;
+    t.x = P.blurs.intern(g.type, (int)ksize, sigma);
+    DlBlurTaps::Blur& b = P.blurs.blurs[t.x];
+    // float: only where the per-type route would run these statements too; the fixed-point families are integer-exact
+    // and agree to the byte
+    if (b.rc != IMGXF_OK) return IMGXF_DRIVER_REFUSED_OTHER;
+    if (g.type != IMGXF_DRIVER_BLUR_FIXED && sepconv_route_c3_dense(false, b.ks / 2, g.h, g.w, b.taps, P.knobs) != SEPCONV_TILE)
+        return IMGXF_DRIVER_REFUSED_FAMILY;
+    if (dl_blur_lds(b.ks) > P.lds_budget) return IMGXF_DRIVER_REFUSED_LDS;
+    e.ksx = e.ksy = b.ks;
+    if (!b.used) { b.used = true; P.blurs.words += (size_t)b.ks; }
+    return IMGXF_DRIVER_OK;
+}
+
+static int dl_plan(const DlGeom& g, double p0, double p1, DlPlanner& P, imgxf_driver_entry& e, DlTables& t) {
+    if (g.c != 3 || !ll_size_ok(g.h, g.w)) return IMGXF_DRIVER_REFUSED_FORMAT;
+    switch (g.type) {
+        case IMGXF_DRIVER_SCALE: return dl_plan_scale(g, p0, P, e, t);
+        case IMGXF_DRIVER_ROTATION: return dl_plan_rotation(g, p0, e);
+        case IMGXF_DRIVER_SHEAR: return dl_plan_shear(g, p0, e);
+        case IMGXF_DRIVER_TRANSLATION: return dl_plan_translation(g, p0, p1, e);
+        case IMGXF_DRIVER_CROP_RESIZE: return dl_plan_crop(g, p0, p1, P, e, t);
+        case IMGXF_DRIVER_BLUR: case IMGXF_DRIVER_BLUR_FIXED: return dl_plan_blur(g, p0, p1, P, e, t);
+        case IMGXF_DRIVER_BRIGHTNESS: case IMGXF_DRIVER_CONTRAST: e.alpha = (float)p0; return IMGXF_DRIVER_OK;
+        case IMGXF_DRIVER_NOISE: case IMGXF_DRIVER_FLIP: case IMGXF_DRIVER_PERSPECTIVE: return IMGXF_DRIVER_OK;
+        default: return IMGXF_DRIVER_REFUSED_OTHER;           // no type
+    }
+}
+
+// The units of entry i outside the resample section: bands of e.unit_rows output rows
+static void dl_emit_bands(const imgxf_driver_entry& e, int i, int lds, imgxf_driver_unit* units, size_t& upos) {
+    for (int y0 = 0; y0 < e.oh; y0 += e.unit_rows) {
+        imgxf_driver_unit& u = units[upos++];
+        u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, e.oh - y0); u.lds_bytes = lds;
+    }
+}
+
+// A resample entry with its axes' tables in the block: the record's offsets and spans, then its units, bands of
+// e.unit_rows window rows with their own LDS.  Returns the largest of those.
+static int dl_emit_resample(imgxf_driver_entry& e, int i, const AxisTables::Axis& x, const AxisTables::Axis& y,
+                            const int32_t* words, imgxf_driver_unit* units, size_t& upos) {
+    e.bounds_x = x.bounds; e.coeffs_x = x.coeffs; e.bounds_y = y.bounds; e.coeffs_y = y.coeffs;
+    int c_hi, r_hi, lds_max = 0;
+    pl_span(words + x.bounds, 0, e.win_w, &e.col0, &c_hi);
+    pl_span(words + y.bounds, 0, e.win_h, &e.row0, &r_hi);
+    e.ncols = c_hi - e.col0; e.nrows = r_hi - e.row0;
+    for (int j0 = 0; j0 < e.win_h; j0 += e.unit_rows) {
+        const int nj = std::min(e.unit_rows, e.win_h - j0);
+        imgxf_driver_unit& u = units[upos++];
+        u.entry = i;
+        // the first and the last band of the window take the canvas rows above and below it
+        u.y0 = j0 == 0 ? 0 : e.win_top + j0;
+        const int y1 = j0 + nj >= e.win_h ? e.oh : e.win_top + j0 + nj;
+        u.ny = y1 - u.y0;
+        u.lds_bytes = (int32_t)pl_lds_bytes(pl_span_extent(words + y.bounds, j0, nj), e.win_w, e.ncols);
+        lds_max = std::max(lds_max, u.lds_bytes);
+    }
+    return lds_max;
+}
+
+// One accepted record against its frame, the output and the block (t0 .. words: the tables, in words)
+static int dl_check_entry(const imgxf_driver_entry& e, const imgxf_driver_header& hd, const int32_t* w32, int64_t t0,
+                          int64_t words) {
+    if (!e.src) return IMGXF_ERR_NULL;
+    if (!ll_frame_ok(e.h, e.w, e.src_stride) || !ll_size_ok(e.oh, e.ow) || e.unit_rows < 1) return IMGXF_ERR_SHAPE;
+    if (!ll_output_ok(e.out_off, e.oh, e.ow, hd.out_bytes)) return IMGXF_ERR_ARG;
+    const bool same_size = e.oh == e.h && e.ow == e.w;
+    switch (e.op) {
+        case IMGXF_DRIVER_SCALE: case IMGXF_DRIVER_CROP_RESIZE:
+            if (e.op == IMGXF_DRIVER_SCALE) {                 // the tables index the frame, or the window inside it
+                if (e.dx != 0 || e.dy != 0 || e.in_h != e.h || e.in_w != e.w) return IMGXF_ERR_SHAPE;
+            } else if (!ll_box_ok(e.h, e.w, e.dy, e.dx, e.in_h, e.in_w) || e.oh != DL_CROP_OUT || e.ow != DL_CROP_OUT ||
+                       e.win_h != e.oh || e.win_w != e.ow) {
+                return IMGXF_ERR_SHAPE;
             }
-        }
-    for (int i = 0; i < n; ++i) {
-        imgxf_driver_entry& e = recs[i];
-        if (e.status != IMGXF_DRIVER_OK || !dl_resamples(geo[i].type)) continue;
-        Axis& x = axes[ax[i]];
-        Axis& y = axes[ay[i]];
-        build_axis(x);
-        build_axis(y);
-        e.bounds_x = x.bounds; e.coeffs_x = x.coeffs; e.bounds_y = y.bounds; e.coeffs_y = y.coeffs;
-        int c_hi, r_hi, lo, hi;
-        pl_span(words + x.bounds, 0, e.win_w, &e.col0, &c_hi);
-        pl_span(words + y.bounds, 0, e.win_h, &e.row0, &r_hi);
-        e.ncols = c_hi - e.col0; e.nrows = r_hi - e.row0;
-        for (int j0 = 0; j0 < e.win_h; j0 += e.unit_rows) {
-            const int nj = std::min(e.unit_rows, e.win_h - j0);
-            pl_span(words + y.bounds, j0, nj, &lo, &hi);
-            imgxf_driver_unit& u = units[upos++];
-            u.entry = i;
-            // the first and the last band of the window take the canvas rows above and below it
-            u.y0 = j0 == 0 ? 0 : e.win_top + j0;
-            const int y1 = j0 + nj >= e.win_h ? e.oh : e.win_top + j0 + nj;
-            u.ny = y1 - u.y0;
-            u.lds_bytes = (int32_t)pl_lds_bytes(hi - lo, e.win_w, e.ncols);
-            lds_max = std::max(lds_max, u.lds_bytes);
-        }
+            // the window inside the output, the span the tables touch inside the source
+            if (!ll_box_ok(e.oh, e.ow, e.win_top, e.win_left, e.win_h, e.win_w) || e.ksx < 1 || e.ksy < 1 ||
+                !ll_box_ok(e.in_h, e.in_w, e.row0, e.col0, e.nrows, e.ncols))
+                return IMGXF_ERR_SHAPE;
+            if (!pl_check_axis(w32, t0, words, e.bounds_x, e.coeffs_x, e.win_w, e.ksx, e.col0, e.ncols, false) ||
+                !pl_check_axis(w32, t0, words, e.bounds_y, e.coeffs_y, e.win_h, e.ksy, e.row0, e.nrows, true))
+                return IMGXF_ERR_ARG;
+            break;
+        case IMGXF_DRIVER_SHEAR:
+            if (e.oh != e.h) return IMGXF_ERR_SHAPE;
+            break;
+        case IMGXF_DRIVER_NOISE:
+            if (!e.noise) return IMGXF_ERR_NULL;
+            if (e.noise & 3) return IMGXF_ERR_ARG;
+            /* fall through */
+        case IMGXF_DRIVER_ROTATION: case IMGXF_DRIVER_BRIGHTNESS: case IMGXF_DRIVER_CONTRAST: case IMGXF_DRIVER_FLIP:
+            if (!same_size) return IMGXF_ERR_SHAPE;
+            break;
+        case IMGXF_DRIVER_PERSPECTIVE:
+            if (!same_size || e.unit_rows != dl_section_rows(DL_PERSP, e)) return IMGXF_ERR_SHAPE;
+            for (int q = 0; q < 8; ++q)
+                if (!(e.pc[q] == e.pc[q]) || e.pc[q] - e.pc[q] != 0.0f) return IMGXF_ERR_ARG;     // NaN / inf
+            break;
+        case IMGXF_DRIVER_TRANSLATION:
+            if (!same_size || e.dx < -e.w || e.dx > e.w || e.dy < -e.h || e.dy > e.h) return IMGXF_ERR_SHAPE;
+            break;
+        case IMGXF_DRIVER_BLUR: case IMGXF_DRIVER_BLUR_FIXED:
+            if (!same_size || e.unit_rows != dl_section_rows(DL_BLUR, e)) return IMGXF_ERR_SHAPE;
+            if (e.ksx < 3 || e.ksx > 31 || !(e.ksx & 1) || e.ksy != e.ksx) return IMGXF_ERR_ARG;
+            if (e.coeffs_x < t0 || e.coeffs_x + (int64_t)e.ksx > words || e.coeffs_y < t0 ||
+                e.coeffs_y + (int64_t)e.ksy > words)
+                return IMGXF_ERR_ARG;
+            break;
+        default: return IMGXF_ERR_ARG;
     }
-    // the blur units last, each distinct (fixed, R) a contiguous run = one launch; their tables behind the resample ones
-    std::stable_sort(blurred.begin(), blurred.end(), [&](int a, int b) {
-        return recs[a].op != recs[b].op ? recs[a].op < recs[b].op : recs[a].ksx < recs[b].ksx;
-    });
-    for (int i : blurred) {
-        imgxf_driver_entry& e = recs[i];
-        Blur& b = blurs[ax[i]];
-        if (b.coeffs < 0) {
-            b.coeffs = (int)tpos;
-            memcpy(words + tpos, b.taps.x, (size_t)b.ks * 4);
-            tpos += (size_t)b.ks;
-        }
-        e.coeffs_x = e.coeffs_y = b.coeffs;
-        for (int y0 = 0; y0 < e.oh; y0 += DL_BLUR_ROWS) {
-            imgxf_driver_unit& u = units[upos++];
-            u.entry = i; u.y0 = y0; u.ny = std::min(DL_BLUR_ROWS, e.oh - y0); u.lds_bytes = dl_blur_lds(b.ks);
-        }
-    }
-    if (n) memcpy(entries, recs.data(), (size_t)n * sizeof(imgxf_driver_entry));
-    hd->n_blur = (int32_t)n_blur;
-    hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->n_plain = (int32_t)n_plain; hd->n_persp = (int32_t)n_persp;
-    hd->lds_bytes = lds_max;
-    hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
-    hd->total_bytes = (int32_t)total; hd->out_bytes = opos;
-    if (lds_bytes) *lds_bytes = lds_max;
     return IMGXF_OK;
+}
+
+// Unit k against its entry and its section: plain units, perspective units (whole bands: a tile writes PV_TH rows or to
+// the end), resample units, blur units (whole bands, in ascending (fixed, R): a run is one launch, its LDS the run's own)
+static bool dl_unit_ok(int k, const imgxf_driver_header& hd, const imgxf_driver_entry* entries, const imgxf_driver_unit* units,
+                       const int32_t* w32) {
+    const imgxf_driver_unit& u = units[k];
+    if (u.entry < 0 || u.entry >= hd.n_entries || entries[u.entry].status != IMGXF_DRIVER_OK) return false;
+    const imgxf_driver_entry& e = entries[u.entry];
+    if (u.y0 < 0 || u.ny < 1 || (int64_t)u.y0 + u.ny > e.oh) return false;      // (64-bit: no sum here may wrap)
+    int section = DL_BLUR;
+    while (k < dl_section_first(hd, section)) --section;
+    if (section != dl_section(e.op)) return false;
+    if (section == DL_PERSP || section == DL_BLUR) {
+        const int rows = dl_section_rows(section, e);
+        if (u.y0 % rows || u.ny != std::min(rows, e.oh - u.y0)) return false;
+    }
+    if (section == DL_BLUR) {
+        if (u.lds_bytes != dl_blur_lds(e.ksx)) return false;
+        if (k > dl_section_first(hd, DL_BLUR)) {
+            const imgxf_driver_entry& p = entries[units[k - 1].entry];
+            if (p.op > e.op || (p.op == e.op && p.ksx > e.ksx)) return false;
+        }
+    }
+    if (section != DL_RESAMPLE) return true;
+    const int ja = std::max(u.y0, e.win_top) - e.win_top, jb = std::min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
+    if (jb <= ja) return true;
+    int lo, hi;                                               // what the kernel will lay out
+    pl_touched(w32 + e.bounds_y, ja, jb - ja, e.row0, e.nrows, &lo, &hi);
+    return hi > lo && pl_lds_bytes(hi - lo, e.win_w, e.ncols) <= hd.lds_bytes;
 }
 
 // The host checks of imgxf_driver_list_u8, before any device work: IMGXF_OK when the block may be copied and launched
 // (or has no units).  Reads the host block alone; the two device addresses are only tested for null and alignment.
-namespace imgxf {
+// The records bound every address the kernels form: they are held against the frames, the output and the block.
 int driver_list_check(const void* block_host, const void* block_dev, const uint8_t* out, size_t out_cap) {
     if (!block_host) return IMGXF_ERR_NULL;
     const u8* hb = (const u8*)block_host;
     const imgxf_driver_header hd = *(const imgxf_driver_header*)hb;
     if (hd.n_entries < 0 || hd.n_units < 0 || hd.n_plain < 0 || hd.n_persp < 0 || hd.n_blur < 0 ||
         (int64_t)hd.n_plain + hd.n_persp + hd.n_blur > hd.n_units || hd.lds_bytes < 0 ||
-        hd.lds_bytes > DL_MAX_LDS)
+        hd.lds_bytes > PL_MAX_LDS)
         return IMGXF_ERR_ARG;
-    const int64_t total = hd.total_bytes, words = total / 4;
-    if (!pl_check_sections(sizeof(imgxf_driver_header), hd.n_entries, sizeof(imgxf_driver_entry), hd.n_units,
-                           sizeof(imgxf_driver_unit), hd.entries_off, hd.units_off, hd.tables_off, total))
+    const int64_t total = hd.total_bytes, words = total / 4, t0 = hd.tables_off / 4;
+    if (!DlBlock::pl_check_sections(hd.n_entries, hd.n_units, hd.entries_off, hd.units_off, hd.tables_off, total))
         return IMGXF_ERR_ARG;
     if (hd.n_units == 0) return IMGXF_OK;
     if (!block_dev || !out) return IMGXF_ERR_NULL;
     if ((((uintptr_t)out) & 15) || (((uintptr_t)block_dev) & 7) || hd.out_bytes > out_cap) return IMGXF_ERR_ARG;
-    // the records bound every address the kernels form: check them against the frames, the output and the block
     const imgxf_driver_entry* entries = (const imgxf_driver_entry*)(hb + hd.entries_off);
     const imgxf_driver_unit* units = (const imgxf_driver_unit*)(hb + hd.units_off);
-    const int64_t t0 = hd.tables_off / 4;
-    for (int i = 0; i < hd.n_entries; ++i) {
-        const imgxf_driver_entry& e = entries[i];
-        if (e.status != IMGXF_DRIVER_OK) continue;
-        if (!e.src) return IMGXF_ERR_NULL;
-        if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.oh < 1 || e.ow < 1 || e.oh > 32767 || e.ow > 32767 ||
-            e.src_stride < (int64_t)e.w * 3 || e.unit_rows < 1)
-            return IMGXF_ERR_SHAPE;
-        if (e.out_off < 0 || (e.out_off & 15) || (uint64_t)e.out_off + (uint64_t)e.oh * e.ow * 3 > hd.out_bytes) return IMGXF_ERR_ARG;
-        switch (e.op) {
-            case IMGXF_DRIVER_SCALE: case IMGXF_DRIVER_CROP_RESIZE:
-                if (e.op == IMGXF_DRIVER_SCALE) {             // the tables index the frame, or the window inside it
-                    if (e.dx != 0 || e.dy != 0 || e.in_h != e.h || e.in_w != e.w) return IMGXF_ERR_SHAPE;
-                } else if (e.in_h < 1 || e.in_w < 1 || e.dx < 0 || e.dy < 0 || e.dx > e.w - e.in_w || e.dy > e.h - e.in_h ||
-                           e.oh != DL_CROP_OUT || e.ow != DL_CROP_OUT || e.win_h != e.oh || e.win_w != e.ow) {
-                    return IMGXF_ERR_SHAPE;
-                }
-                if (e.win_top < 0 || e.win_left < 0 || e.win_h < 1 || e.win_w < 1 || (int64_t)e.win_top + e.win_h > e.oh ||
-                    (int64_t)e.win_left + e.win_w > e.ow || e.ksx < 1 || e.ksy < 1)
-                    return IMGXF_ERR_SHAPE;
-                if (e.row0 < 0 || e.nrows < 1 || (int64_t)e.row0 + e.nrows > e.in_h || e.col0 < 0 || e.ncols < 1 ||
-                    (int64_t)e.col0 + e.ncols > e.in_w)
-                    return IMGXF_ERR_SHAPE;
-                if (!pl_check_axis((const int32_t*)hb, t0, words, e.bounds_x, e.coeffs_x, e.win_w, e.ksx, e.col0, e.ncols, false) ||
-                    !pl_check_axis((const int32_t*)hb, t0, words, e.bounds_y, e.coeffs_y, e.win_h, e.ksy, e.row0, e.nrows, true))
-                    return IMGXF_ERR_ARG;
-                break;
-            case IMGXF_DRIVER_SHEAR:
-                if (e.oh != e.h) return IMGXF_ERR_SHAPE;
-                break;
-            case IMGXF_DRIVER_NOISE:
-                if (!e.noise) return IMGXF_ERR_NULL;
-                if (e.noise & 3) return IMGXF_ERR_ARG;
-                /* fall through */
-            case IMGXF_DRIVER_ROTATION: case IMGXF_DRIVER_BRIGHTNESS: case IMGXF_DRIVER_CONTRAST: case IMGXF_DRIVER_FLIP:
-                if (e.oh != e.h || e.ow != e.w) return IMGXF_ERR_SHAPE;
-                break;
-            case IMGXF_DRIVER_PERSPECTIVE:
-                if (e.oh != e.h || e.ow != e.w || e.unit_rows != PV_TH) return IMGXF_ERR_SHAPE;
-                for (int q = 0; q < 8; ++q)
-                    if (!(e.pc[q] == e.pc[q]) || e.pc[q] - e.pc[q] != 0.0f) return IMGXF_ERR_ARG;     // NaN / inf
-                break;
-            case IMGXF_DRIVER_TRANSLATION:
-                if (e.oh != e.h || e.ow != e.w || e.dx < -e.w || e.dx > e.w || e.dy < -e.h || e.dy > e.h) return IMGXF_ERR_SHAPE;
-                break;
-            case IMGXF_DRIVER_BLUR: case IMGXF_DRIVER_BLUR_FIXED:
-                if (e.oh != e.h || e.ow != e.w || e.unit_rows != DL_BLUR_ROWS) return IMGXF_ERR_SHAPE;
-                if (e.ksx < 3 || e.ksx > 31 || !(e.ksx & 1) || e.ksy != e.ksx) return IMGXF_ERR_ARG;
-                if (e.coeffs_x < t0 || e.coeffs_x + (int64_t)e.ksx > words || e.coeffs_y < t0 ||
-                    e.coeffs_y + (int64_t)e.ksy > words)
-                    return IMGXF_ERR_ARG;
-                break;
-            default: return IMGXF_ERR_ARG;
-        }
-    }
-    for (int k = 0; k < hd.n_units; ++k) {
-        const imgxf_driver_unit& u = units[k];
-        if (u.entry < 0 || u.entry >= hd.n_entries || entries[u.entry].status != IMGXF_DRIVER_OK) return IMGXF_ERR_ARG;
-        const imgxf_driver_entry& e = entries[u.entry];
-        if (u.y0 < 0 || u.ny < 1 || (int64_t)u.y0 + u.ny > e.oh) return IMGXF_ERR_ARG;     // (64-bit: no sum here may wrap)
-        // the sections: plain units, perspective units (whole 16-row bands: a tile writes PV_TH rows or to the end), resample
-        // units, blur units (whole 32-row bands, in ascending (fixed, R): a run is one launch, its LDS the run's own)
-        const int section = k >= hd.n_units - hd.n_blur ? 3 : (k < hd.n_plain ? 0 : (k < hd.n_plain + hd.n_persp ? 1 : 2));
-        if (section != (dl_blurs(e.op) ? 3 : (dl_resamples(e.op) ? 2 : (e.op == IMGXF_DRIVER_PERSPECTIVE ? 1 : 0)))) return IMGXF_ERR_ARG;
-        if (section == 1 && (u.y0 % PV_TH || u.ny != std::min(PV_TH, e.oh - u.y0))) return IMGXF_ERR_ARG;
-        if (section == 3) {
-            if (u.y0 % DL_BLUR_ROWS || u.ny != std::min(DL_BLUR_ROWS, e.oh - u.y0) || u.lds_bytes != dl_blur_lds(e.ksx))
-                return IMGXF_ERR_ARG;
-            if (k > hd.n_units - hd.n_blur) {
-                const imgxf_driver_entry& p = entries[units[k - 1].entry];
-                if (p.op > e.op || (p.op == e.op && p.ksx > e.ksx)) return IMGXF_ERR_ARG;
-            }
-        }
-        if (section != 2) continue;
-        const int ja = std::max(u.y0, e.win_top) - e.win_top, jb = std::min(u.y0 + u.ny, e.win_top + e.win_h) - e.win_top;
-        if (jb <= ja) continue;
-        int lo, hi;                                           // what the kernel will lay out
-        pl_touched((const int32_t*)hb + e.bounds_y, ja, jb - ja, e.row0, e.nrows, &lo, &hi);
-        if (hi <= lo || pl_lds_bytes(hi - lo, e.win_w, e.ncols) > hd.lds_bytes) return IMGXF_ERR_ARG;
-    }
+    for (int i = 0; i < hd.n_entries; ++i)
+        if (entries[i].status == IMGXF_DRIVER_OK) IMGXF_CHECK(dl_check_entry(entries[i], hd, (const int32_t*)hb, t0, words));
+    for (int k = 0; k < hd.n_units; ++k)
+        if (!dl_unit_ok(k, hd, entries, units, (const int32_t*)hb)) return IMGXF_ERR_ARG;
     return IMGXF_OK;
 }
+
 } // namespace imgxf
+
+using namespace imgxf;
+
+IMGXF_API int imgxf_driver_list_layout_host(const int32_t* geometry, const double* params, int n, int lds_budget, void* block,
+                                            size_t block_cap, size_t* block_bytes, int64_t* out_off, int32_t* out_hw,
+                                            int32_t* status, size_t* out_bytes, int32_t* lds_bytes) {
+    if (!block_bytes || (n > 0 && (!geometry || !params))) return IMGXF_ERR_NULL;
+    if (n < 0 || lds_budget < 1) return IMGXF_ERR_ARG;
+    const DlGeom* geo = (const DlGeom*)geometry;
+
+    // pass over geometry and parameters alone: every record but its tables, which tables are shared -> the sections' sizes
+    DlPlanner P = {std::min(lds_budget, PL_MAX_LDS), sepconv_knobs()};
+    std::vector<imgxf_driver_entry> recs((size_t)n);
+    std::vector<DlTables> tables((size_t)n);
+    std::vector<int> accepted[DL_SECTIONS];                   // the accepted entries of each section, in order
+    size_t n_section[DL_SECTIONS] = {0, 0, 0, 0};
+    uint64_t opos = 0;
+    for (int i = 0; i < n; ++i) {
+        const DlGeom& g = geo[i];
+        imgxf_driver_entry& e = recs[i];
+        memset(&e, 0, sizeof(e));
+        e.frame = g.frame; e.op = g.type; e.h = g.h; e.w = g.w; e.oh = g.h; e.ow = g.w; e.out_off = -1;
+        e.status = dl_plan(g, params[2 * i], params[2 * i + 1], P, e, tables[i]);
+        if (e.status != IMGXF_DRIVER_OK) {
+            e.unit_rows = 0;
+        } else {
+            e.out_off = (int64_t)opos;
+            // outputs start on multiples of 48: 16-byte aligned, and whole pixels into the block, so that the block as ONE
+            // run of RGB pixels can be expanded or copied without knowing where its outputs are
+            opos = (opos + (uint64_t)e.oh * e.ow * 3 + 47) / 48 * 48;
+            const int s = dl_section(e.op);
+            e.unit_rows = dl_section_rows(s, e);
+            n_section[s] += (size_t)((s == DL_RESAMPLE ? e.win_h : e.oh) + e.unit_rows - 1) / e.unit_rows;
+            accepted[s].push_back(i);
+        }
+        if (out_off) out_off[i] = e.out_off;
+        if (out_hw) { out_hw[2 * i] = e.oh; out_hw[2 * i + 1] = e.ow; }
+        if (status) status[i] = e.status;
+    }
+    const size_t n_units = n_section[DL_PLAIN] + n_section[DL_PERSP] + n_section[DL_RESAMPLE] + n_section[DL_BLUR];
+    DlBlock B;
+    if (B.size((size_t)n, n_units, P.axes.words + P.blurs.words) != IMGXF_OK || n_units > 0x7fffffffu ||
+        opos > ((uint64_t)1 << 40))
+        return IMGXF_ERR_SHAPE;
+    if (out_bytes) *out_bytes = (size_t)opos;
+    if (lds_bytes) *lds_bytes = P.lds_bound;                  // an upper bound; with a block: the largest unit's own need
+    IMGXF_CHECK(B.open((size_t)n, n_units, P.axes.words + P.blurs.words, block, block_cap, block_bytes));
+    if (!block) return IMGXF_OK;
+
+    // the sections in launch order; the resample tables in the order of first use, the blurs' taps behind them
+    size_t upos = 0;
+    int lds_max = 0;
+    for (int s : {DL_PLAIN, DL_PERSP})
+        for (int i : accepted[s]) dl_emit_bands(recs[i], i, 0, B.units, upos);
+    for (int i : accepted[DL_RESAMPLE]) {
+        const AxisTables::Axis x = P.axes.build(tables[i].x, B.words, B.tpos), y = P.axes.build(tables[i].y, B.words, B.tpos);
+        lds_max = std::max(lds_max, dl_emit_resample(recs[i], i, x, y, B.words, B.units, upos));
+    }
+    // each distinct (fixed, R) among the blur units a contiguous run = one launch
+    std::stable_sort(accepted[DL_BLUR].begin(), accepted[DL_BLUR].end(), [&](int a, int b) {
+        return recs[a].op != recs[b].op ? recs[a].op < recs[b].op : recs[a].ksx < recs[b].ksx;
+    });
+    for (int i : accepted[DL_BLUR]) {
+        imgxf_driver_entry& e = recs[i];
+        DlBlurTaps::Blur& b = P.blurs.blurs[tables[i].x];
+        if (b.coeffs < 0) {
+            b.coeffs = (int)B.tpos;
+            memcpy(B.words + B.tpos, b.taps.x, (size_t)b.ks * 4);
+            B.tpos += (size_t)b.ks;
+        }
+        e.coeffs_x = e.coeffs_y = b.coeffs;
+        dl_emit_bands(e, i, dl_blur_lds(b.ks), B.units, upos);
+    }
+    if (n) memcpy(B.records, recs.data(), (size_t)n * sizeof(imgxf_driver_entry));
+    imgxf_driver_header* hd = B.hd;
+    hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->n_plain = (int32_t)n_section[DL_PLAIN];
+    hd->n_persp = (int32_t)n_section[DL_PERSP]; hd->n_blur = (int32_t)n_section[DL_BLUR]; hd->lds_bytes = lds_max;
+    hd->entries_off = (int32_t)B.records_off; hd->units_off = (int32_t)B.units_off; hd->tables_off = (int32_t)B.tables_off;
+    hd->total_bytes = (int32_t)B.total; hd->out_bytes = opos;
+    if (lds_bytes) *lds_bytes = lds_max;
+    return IMGXF_OK;
+}
 
 IMGXF_API int imgxf_driver_list_u8(const void* block_host, void* block_dev, uint8_t* out, size_t out_cap, void* stream) {
     IMGXF_CHECK(driver_list_check(block_host, block_dev, out, out_cap));
     const u8* hb = (const u8*)block_host;
     const imgxf_driver_header hd = *(const imgxf_driver_header*)hb;
     if (hd.n_units == 0) return IMGXF_OK;
-    const int64_t total = hd.total_bytes;
     const imgxf_driver_entry* entries = (const imgxf_driver_entry*)(hb + hd.entries_off);
     const imgxf_driver_unit* units = (const imgxf_driver_unit*)(hb + hd.units_off);
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t ce = hipMemcpyAsync(block_dev, block_host, (size_t)total, hipMemcpyHostToDevice, st);
+    const hipError_t ce = hipMemcpyAsync(block_dev, block_host, (size_t)hd.total_bytes, hipMemcpyHostToDevice, st);
     if (ce != hipSuccess) return (int)ce;
     const u8* db = (const u8*)block_dev;
-    if (hd.n_plain)
-        hipLaunchKernelGGL(driver_list_plain_kernel, dim3((unsigned)hd.n_plain), dim3(DL_THREADS), 0, st, db, hd.entries_off,
+    const int persp0 = dl_section_first(hd, DL_PERSP), scale0 = dl_section_first(hd, DL_RESAMPLE);
+    const int blur0 = dl_section_first(hd, DL_BLUR);
+    if (persp0 > 0)
+        hipLaunchKernelGGL(driver_list_plain_kernel, dim3((unsigned)persp0), dim3(DL_THREADS), 0, st, db, hd.entries_off,
                            hd.units_off, out);
-    if (hd.n_persp)
-        hipLaunchKernelGGL(driver_list_persp_kernel, dim3((unsigned)hd.n_persp), dim3(PV_THREADS), 0, st, db, hd.entries_off,
-                           hd.units_off, hd.n_plain, out);
-    const int unit2 = hd.n_plain + hd.n_persp, unit3 = hd.n_units - hd.n_blur;
-    if (unit3 > unit2)
-        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(unit3 - unit2)), dim3(DL_THREADS),
-                           (size_t)hd.lds_bytes, st, db, hd.entries_off, hd.units_off, unit2, out);
+    if (scale0 > persp0)
+        hipLaunchKernelGGL(driver_list_persp_kernel, dim3((unsigned)(scale0 - persp0)), dim3(PV_THREADS), 0, st, db,
+                           hd.entries_off, hd.units_off, persp0, out);
+    if (blur0 > scale0)
+        hipLaunchKernelGGL(driver_list_scale_kernel, dim3((unsigned)(blur0 - scale0)), dim3(DL_THREADS), (size_t)hd.lds_bytes,
+                           st, db, hd.entries_off, hd.units_off, scale0, out);
     IMGXF_CHECK(launch_status());
     // one launch per run of equal (fixed, R): a radius takes its own registers and LDS, not those of R = 15
-    for (int k = unit3; k < hd.n_units;) {
+    for (int k = blur0; k < hd.n_units;) {
         const imgxf_driver_entry& e = entries[units[k].entry];
         int k1 = k + 1;
         while (k1 < hd.n_units && entries[units[k1].entry].op == e.op && entries[units[k1].entry].ksx == e.ksx) ++k1;

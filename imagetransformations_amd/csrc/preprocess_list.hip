@@ -4,10 +4,10 @@
 // coefficients) with any of its five convolution filters (BILINEAR where none is stated), restricted to the crop window —
 // bit for bit tensor_maps.preprocess per frame.
 //
-// HOST half (imgxf_preprocess_list_layout_host, no device work): from each frame's geometry one block of
-//   header | frame records | work units | coefficient tables
-// Tables are precompute_coeffs' (build_coeffs, resample_coeffs.h) sliced to the crop window as the resample plans slice
-// them; frames of equal geometry share one set, so host work grows with the number of distinct sizes.
+// HOST half (imgxf_preprocess_list_layout_host, no device work; the block protocol is list_layout.h's): from each frame's
+// geometry one block of header | frame records | work units | coefficient tables.  Tables are precompute_coeffs' sliced
+// to the crop window as the resample plans slice them; frames of equal geometry share one set (per whole geometry, not
+// per axis: the two axes of a square geometry keep tables of their own), so host work grows with the distinct sizes.
 //
 // DEVICE half (preprocess_list_kernel): one workgroup per work unit = up to PL_UNIT_ROWS output rows of one frame, run
 // through the band engine of resample_list.h (its LDS layout, its two passes, its float32 planar epilogue) with the
@@ -23,9 +23,8 @@
 
 namespace imgxf {
 
-constexpr int PL_UNIT_ROWS = 16;          // output rows per work unit when the LDS budget allows
-constexpr int PL_MAX_LDS = 64 * 1024;     // per workgroup: two of them fit a CU's 160 KiB whatever else runs there
 
+using PlBlock = ListBlock<imgxf_preprocess_header, imgxf_preprocess_frame, imgxf_preprocess_unit>;
 // geometry of one frame as the caller states it
 struct PlGeom { int h, w, nh, nw, left, top; };
 
@@ -54,8 +53,7 @@ int preprocess_list_check(const void* block_host) {
     const imgxf_preprocess_header hd = *(const imgxf_preprocess_header*)hb;
     if (hd.n_frames < 0 || hd.n_units < 0 || hd.crop < 1 || hd.lds_bytes < 0 || hd.lds_bytes > PL_MAX_LDS) return IMGXF_ERR_ARG;
     const int64_t total = hd.total_bytes, words = total / 4, t0 = hd.tables_off / 4;
-    if (!pl_check_sections(sizeof(imgxf_preprocess_header), hd.n_frames, sizeof(imgxf_preprocess_frame), hd.n_units,
-                           sizeof(imgxf_preprocess_unit), hd.frames_off, hd.units_off, hd.tables_off, total))
+    if (!PlBlock::pl_check_sections(hd.n_frames, hd.n_units, hd.frames_off, hd.units_off, hd.tables_off, total))
         return IMGXF_ERR_ARG;
     if (hd.n_units == 0) return IMGXF_OK;
     const imgxf_preprocess_frame* frames = (const imgxf_preprocess_frame*)(hb + hd.frames_off);
@@ -71,9 +69,7 @@ int preprocess_list_check(const void* block_host) {
         const auto seen = checked.find(f.bounds_x);
         if (seen != checked.end() && !memcmp(&seen->second->h, &f.h, shared)) continue;
         if (f.h < 1 || f.ksx < 1 || f.ksy < 1) return IMGXF_ERR_SHAPE;
-        if (f.row0 < 0 || f.nrows < 1 || (int64_t)f.row0 + f.nrows > f.h || f.col0 < 0 || f.ncols < 1 ||
-            (int64_t)f.col0 + f.ncols > f.w)
-            return IMGXF_ERR_SHAPE;
+        if (!ll_box_ok(f.h, f.w, f.row0, f.col0, f.nrows, f.ncols)) return IMGXF_ERR_SHAPE;       // the span the tables touch
         if (!pl_check_axis((const int32_t*)hb, t0, words, f.bounds_x, f.coeffs_x, hd.crop, f.ksx, f.col0, f.ncols, false) ||
             !pl_check_axis((const int32_t*)hb, t0, words, f.bounds_y, f.coeffs_y, hd.crop, f.ksy, f.row0, f.nrows, true))
             return IMGXF_ERR_ARG;
@@ -100,12 +96,10 @@ IMGXF_API int imgxf_preprocess_list_layout_filter_host(const int32_t* geometry, 
     if (!geometry || !block_bytes) return IMGXF_ERR_NULL;
     if (!filter_known(filter)) return IMGXF_ERR_ARG;
     if (n < 0 || crop < 1 || crop > 32767 || lds_budget < 1) return IMGXF_ERR_ARG;
-    if (lds_budget > PL_MAX_LDS) lds_budget = PL_MAX_LDS;
     const PlGeom* geo = (const PlGeom*)geometry;
     for (int i = 0; i < n; ++i) {
         const PlGeom& g = geo[i];
-        if (g.h < 1 || g.w < 1 || g.nh < 1 || g.nw < 1 || g.h > 32767 || g.w > 32767 || g.nh > (1 << 24) || g.nw > (1 << 24))
-            return IMGXF_ERR_ARG;
+        if (!ll_size_ok(g.h, g.w) || g.nh < 1 || g.nw < 1 || g.nh > (1 << 24) || g.nw > (1 << 24)) return IMGXF_ERR_ARG;
         if (g.left < 0 || g.top < 0 || g.left + crop > g.nw || g.top + crop > g.nh) return IMGXF_ERR_ARG;   // window outside
     }
     // pass over the geometry alone: which frames share tables, taps, rows per unit -> the size of every section
@@ -116,74 +110,59 @@ IMGXF_API int imgxf_preprocess_list_layout_filter_host(const int32_t* geometry, 
     size_t table_words = 0, n_units = 0;
     for (int i = 0; i < n; ++i) {
         const PlGeom& g = geo[i];
-        const std::array<int, 6> key = {g.h, g.w, g.nh, g.nw, g.left, g.top};
-        auto it = index.find(key);
-        if (it == index.end()) {
+        const auto made = index.emplace(std::array<int, 6>{g.h, g.w, g.nh, g.nw, g.left, g.top}, (int)sets.size());
+        if (made.second) {
             Set s;
             s.first = i;
             s.ksx = coeff_ksize(g.w, g.nw, filter);
             s.ksy = coeff_ksize(g.h, g.nh, filter);
             const int ncols = pl_rows_bound(crop, g.w, g.nw, s.ksx);
-            s.unit_rows = pl_unit_rows(std::min(crop, PL_UNIT_ROWS), lds_budget, [&](int ny) {
+            s.unit_rows = pl_unit_rows(crop, lds_budget, [&](int ny) {
                 return pl_lds_bytes(pl_rows_bound(ny, g.h, g.nh, s.ksy), crop, ncols);
             });
             if (s.unit_rows) table_words += (size_t)crop * (4 + s.ksx + s.ksy);
-            it = index.emplace(key, (int)sets.size()).first;
             sets.push_back(s);
         }
-        set_of[i] = it->second;
-        const int ur = sets[it->second].unit_rows;
+        set_of[i] = made.first->second;
+        const int ur = sets[set_of[i]].unit_rows;
         if (ur) n_units += (size_t)(crop + ur - 1) / ur;
     }
-    const size_t frames_off = sizeof(imgxf_preprocess_header);
-    const size_t units_off = frames_off + (size_t)n * sizeof(imgxf_preprocess_frame);
-    const size_t tables_off = units_off + n_units * sizeof(imgxf_preprocess_unit);
-    const size_t total = (tables_off + table_words * 4 + 15) & ~(size_t)15;
-    if (total > 0x7fffffffu) return IMGXF_ERR_SHAPE;
-    *block_bytes = total;
+    PlBlock B;
+    IMGXF_CHECK(B.open((size_t)n, n_units, table_words, block, block_cap, block_bytes));
     if (!block) return IMGXF_OK;                                  // the size alone
-    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
 
-    u8* out = (u8*)block;
-    memset(out, 0, total);
-    imgxf_preprocess_header* hd = (imgxf_preprocess_header*)out;
-    imgxf_preprocess_frame* frames = (imgxf_preprocess_frame*)(out + frames_off);
-    imgxf_preprocess_unit* units = (imgxf_preprocess_unit*)(out + units_off);
-    int32_t* words = (int32_t*)out;
-    size_t tpos = tables_off / 4;
     int lds_max = 0;
     size_t upos = 0;
     for (int i = 0; i < n; ++i) {
         const PlGeom& g = geo[i];
         const Set& s = sets[set_of[i]];
-        imgxf_preprocess_frame& f = frames[i];
+        imgxf_preprocess_frame& f = B.records[i];
         if (s.first != i) {                                       // an earlier frame of this geometry built the tables
-            f = frames[s.first];
+            f = B.records[s.first];
             f.data = 0; f.row_stride = 0;
         } else {
             f.h = g.h; f.w = g.w; f.ksx = s.ksx; f.ksy = s.ksy; f.unit_rows = s.unit_rows;
             if (s.unit_rows) {
-                pl_append_axis(g.w, g.nw, filter, s.ksx, g.left, crop, words, tpos, &f.bounds_x, &f.coeffs_x);
-                pl_append_axis(g.h, g.nh, filter, s.ksy, g.top, crop, words, tpos, &f.bounds_y, &f.coeffs_y);
+                pl_append_axis(g.w, g.nw, filter, s.ksx, g.left, crop, B.words, B.tpos, &f.bounds_x, &f.coeffs_x);
+                pl_append_axis(g.h, g.nh, filter, s.ksy, g.top, crop, B.words, B.tpos, &f.bounds_y, &f.coeffs_y);
                 int c_hi, r_hi;
-                pl_span(words + f.bounds_x, 0, crop, &f.col0, &c_hi);
-                pl_span(words + f.bounds_y, 0, crop, &f.row0, &r_hi);
+                pl_span(B.words + f.bounds_x, 0, crop, &f.col0, &c_hi);
+                pl_span(B.words + f.bounds_y, 0, crop, &f.row0, &r_hi);
                 f.ncols = c_hi - f.col0; f.nrows = r_hi - f.row0;
             }
         }
         if (!s.unit_rows) continue;
         for (int y0 = 0; y0 < crop; y0 += s.unit_rows) {
-            imgxf_preprocess_unit& u = units[upos++];
+            imgxf_preprocess_unit& u = B.units[upos++];
             u.frame = i; u.y0 = y0; u.ny = std::min(s.unit_rows, crop - y0);
-            int lo, hi;
-            pl_span(words + f.bounds_y, y0, u.ny, &lo, &hi);
-            u.lds_bytes = (int32_t)pl_lds_bytes(hi - lo, crop, f.ncols);
+            u.lds_bytes = (int32_t)pl_lds_bytes(pl_span_extent(B.words + f.bounds_y, y0, u.ny), crop, f.ncols);
             lds_max = std::max(lds_max, u.lds_bytes);
         }
     }
+    imgxf_preprocess_header* hd = B.hd;
     hd->n_frames = n; hd->n_units = (int32_t)n_units; hd->crop = crop; hd->lds_bytes = lds_max;
-    hd->frames_off = (int32_t)frames_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
-    hd->total_bytes = (int32_t)total;
+    hd->frames_off = (int32_t)B.records_off; hd->units_off = (int32_t)B.units_off; hd->tables_off = (int32_t)B.tables_off;
+    hd->total_bytes = (int32_t)B.total;
     return IMGXF_OK;
 }
 

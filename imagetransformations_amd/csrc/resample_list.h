@@ -2,14 +2,14 @@
 // resize_list.hip):
 // Pillow's two-pass 8-bit Image.resize on ONE workgroup's band of output rows of one RGB frame — the horizontal pass of
 // the touched source rows into an LDS intermediate (uint8, as Pillow's is), the vertical pass from it, the store
-// epilogues — and what the host halves share around it: the LDS layout (one statement for host and device), the
-// rows-per-unit rule, table spans and appends, the launchers' checks.  Frames start at any byte, rows at any stride.
+// epilogues — with what host and device both read: the LDS layout and the rows a unit touches (what the host halves
+// alone share is in list_layout.h).  Frames start at any byte, rows at any stride.
 //   LDS: | mid: rows_touched x pitch uint8 | stage: PL_STAGE_ROWS x spitch |      pitch = 12 * ceil(width / 4)
 #pragma once
 #include "imgxf_common.h"
+#include "list_layout.h"
 #include "resample_coeffs.h"
 #include "to_tensor_math.h"
-#include <string.h>
 
 namespace imgxf {
 
@@ -28,70 +28,6 @@ __host__ __device__ static inline int64_t pl_lds_bytes(int rows, int width, int 
 __host__ __device__ static inline void pl_touched(const int* by, int ja, int nj, int row0, int rows, int* lo, int* hi) {
     const int jl = ja + nj - 1, a = by[2 * ja], b = by[2 * jl] + by[2 * jl + 1];
     *lo = a > row0 ? a : row0; *hi = b < row0 + rows ? b : row0 + rows;
-}
-
-// Source rows that `ny` consecutive output rows can touch: the windows of precompute_coeffs are at most ksize wide and
-// their starts advance by in / out per row
-static inline int pl_rows_bound(int ny, int in, int out, int ksize) {
-    const int r = (int)ceil((ny - 1) * ((double)in / out)) + ksize;
-    return r < in ? r : in;
-}
-
-// Output rows per unit: the most, up to max_rows, whose LDS need lds_of_ny(ny) fits (0: not even one row does).  The
-// launch's LDS size is its largest unit's, so a frame takes the smallest of three steps of the budget that holds one of
-// its rows (1/2: five workgroups per CU at 64 KiB, 3/4: three, all of it: two), and within that step as many as fit
-template <class LdsOfNy>
-static int pl_unit_rows(int max_rows, int lds_budget, LdsOfNy lds_of_ny) {
-    for (int limit : {lds_budget / 2, lds_budget / 4 * 3, lds_budget})
-        for (int ny = max_rows; ny >= 1; --ny)
-            if (lds_of_ny(ny) <= limit) return ny;
-    return 0;
-}
-
-// [lo, hi): the source samples that rows [first, first + count) of a [.][2] (first, count) bounds table touch
-static inline void pl_span(const int32_t* bounds, int first, int count, int* lo, int* hi) {
-    int a = bounds[2 * first], b = 0;
-    for (int k = first; k < first + count; ++k) {
-        a = std::min(a, bounds[2 * k]);
-        b = std::max(b, bounds[2 * k] + bounds[2 * k + 1]);
-    }
-    *lo = a; *hi = b;
-}
-
-// build_coeffs' tables for (in -> out, filter), rows [first, first + count), appended to a block's words at tpos
-static void pl_append_axis(int in, int out, int filter, int ks, int first, int count, int32_t* words, size_t& tpos,
-                           int32_t* bounds, int32_t* coeffs) {
-    std::vector<int> bv, kv;
-    build_coeffs(in, out, filter, bv, kv);
-    slice_tables(bv, kv, ks, first, count);
-    *bounds = (int32_t)tpos; memcpy(words + tpos, bv.data(), bv.size() * 4); tpos += bv.size();
-    *coeffs = (int32_t)tpos; memcpy(words + tpos, kv.data(), kv.size() * 4); tpos += kv.size();
-}
-
-// Launcher check of header | records | units | tables: each section starts where the counts before it end, the tables
-// inside the block (a block without tables states the end of its units there)
-static inline bool pl_check_sections(size_t header_bytes, int64_t n_records, size_t record_bytes, int64_t n_units,
-                                     size_t unit_bytes, int64_t records_off, int64_t units_off, int64_t tables_off,
-                                     int64_t total) {
-    return records_off == (int64_t)header_bytes && units_off == records_off + n_records * (int64_t)record_bytes &&
-           tables_off == units_off + n_units * (int64_t)unit_bytes && tables_off <= total;
-}
-
-// Launcher check of one axis' tables as a record states them (host block of `words` words, tables from word t0): both
-// inside the tables section, counts within ks, taps inside the staged span [first, first + extent) — the horizontal
-// pass reads them unclamped; rows: also no empty window and non-decreasing starts (a unit's touched rows are read off
-// its first and last row)
-static inline bool pl_check_axis(const int32_t* block, int64_t t0, int64_t words, int32_t bounds, int32_t coeffs, int count,
-                                 int ks, int first, int extent, bool rows) {
-    if (bounds < t0 || bounds + 2 * (int64_t)count > words || coeffs < t0 || coeffs + (int64_t)count * ks > words) return false;
-    const int32_t* b = block + bounds;
-    for (int k = 0; k < count; ++k) {
-        if (b[2 * k] < first || b[2 * k + 1] < (rows ? 1 : 0) || b[2 * k + 1] > ks ||
-            (int64_t)b[2 * k] + b[2 * k + 1] > (int64_t)first + extent)
-            return false;
-        if (rows && k && b[2 * k] < b[2 * k - 2]) return false;
-    }
-    return true;
 }
 
 // Horizontal pass of source rows [r_lo, r_hi) into mid (row r at mid + (r - r_lo) * pitch), PL_STAGE_ROWS rows at a time:

@@ -3,12 +3,12 @@
 // — horizontal pass, uint8 intermediate, vertical pass, 22-bit coefficients, windows clamped to the box — bit for bit,
 // uint8 in and uint8 out, for all five convolution filters.
 //
-// HOST half (imgxf_resize_list_layout_host, no device work): from each entry's geometry one block of
-//   header | entry records | work units | coefficient tables
-// Tables are precompute_coeffs' (build_coeffs, resample_coeffs.h), appended once per distinct (in, out) axis of the call's
-// filter and shared by every entry with that axis, so host work grows with the number of distinct axes.
+// HOST half (imgxf_resize_list_layout_host, no device work; the block protocol and the axis tables are list_layout.h's):
+// from each entry's geometry one block of header | entry records | work units | coefficient tables.  Tables are
+// precompute_coeffs', appended once per distinct (in, out) axis of the call's filter in the order the entries first use
+// them and shared by every entry with that axis, so host work grows with the number of distinct axes.
 //
-// DEVICE half (resize_list_kernel): one workgroup per work unit = a band of up to RSL_UNIT_ROWS output rows AND a chunk of
+// DEVICE half (resize_list_kernel): one workgroup per work unit = a band of up to PL_UNIT_ROWS output rows AND a chunk of
 // output columns of one entry (the rule: include/imgxf.h beside the structs), run through the band engine of
 // resample_list.h as it stands.  A chunk [x0, x0 + nx) is the engine's `width = nx` with the column tables advanced to x0
 // and the staged span set to the source columns the chunk's own windows touch: each distinct source row of the band is
@@ -18,16 +18,14 @@
 #include "resample_coeffs.h"
 #include "resample_list.h"
 #include <map>
-#include <utility>
 #include <unordered_map>
 #include <array>
 #include <string.h>
 
 namespace imgxf {
 
-constexpr int RSL_UNIT_ROWS = 16;         // output rows per work unit when the LDS budget allows
-constexpr int RSL_MAX_LDS = 64 * 1024;    // per workgroup: two of them fit a CU's 160 KiB whatever else runs there
 
+using RslBlock = ListBlock<imgxf_resize_list_header, imgxf_resize_list_entry, imgxf_resize_list_unit>;
 // geometry of one entry as the caller states it
 struct RslGeom { int h, w, top, left, bh, bw, oh, ow; };
 
@@ -41,7 +39,7 @@ static void rsl_plan(int bh, int bw, int oh, int ow, int ksx, int ksy, int lds_b
     for (int parts = 1;; parts *= 2) {
         const int nx = std::min(ow, ((ow + parts - 1) / parts + 3) & ~3);
         const int ncols = pl_rows_bound(nx, bw, ow, ksx);
-        const int ur = pl_unit_rows(std::min(oh, RSL_UNIT_ROWS), lds_budget,
+        const int ur = pl_unit_rows(oh, lds_budget,
                                     [&](int ny) { return pl_lds_bytes(pl_rows_bound(ny, bh, oh, ksy), nx, ncols); });
         if (ur) { *unit_rows = ur; *chunk = nx; return; }
         if (nx <= 4) return;
@@ -79,12 +77,11 @@ int resize_list_check(const void* block_host, size_t block_bytes, size_t out_byt
     const u8* hb = (const u8*)block_host;
     if (block_bytes < sizeof(imgxf_resize_list_header)) return IMGXF_ERR_ARG;
     const imgxf_resize_list_header hd = *(const imgxf_resize_list_header*)hb;
-    if (hd.n_entries < 0 || hd.n_units < 0 || hd.lds_bytes < 0 || hd.lds_bytes > RSL_MAX_LDS || hd.total_bytes < 0 ||
+    if (hd.n_entries < 0 || hd.n_units < 0 || hd.lds_bytes < 0 || hd.lds_bytes > PL_MAX_LDS || hd.total_bytes < 0 ||
         (hd.total_bytes & 3) || (hd.tables_off & 3))
         return IMGXF_ERR_ARG;
     const int64_t total = hd.total_bytes, words = total / 4, t0 = hd.tables_off / 4;
-    if (!pl_check_sections(sizeof(imgxf_resize_list_header), hd.n_entries, sizeof(imgxf_resize_list_entry), hd.n_units,
-                           sizeof(imgxf_resize_list_unit), hd.entries_off, hd.units_off, hd.tables_off, total) ||
+    if (!RslBlock::pl_check_sections(hd.n_entries, hd.n_units, hd.entries_off, hd.units_off, hd.tables_off, total) ||
         (size_t)total > block_bytes)
         return IMGXF_ERR_ARG;
     if (hd.n_units == 0) return IMGXF_OK;
@@ -105,14 +102,11 @@ int resize_list_check(const void* block_host, size_t block_bytes, size_t out_byt
         const imgxf_resize_list_entry& e = entries[i];
         if (!e.unit_rows) continue;
         if (!e.data) return IMGXF_ERR_NULL;
-        if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.row_stride < (int64_t)e.w * 3) return IMGXF_ERR_SHAPE;
-        if (e.top < 0 || e.left < 0 || e.bh < 1 || e.bw < 1 || e.top > e.h - e.bh || e.left > e.w - e.bw) return IMGXF_ERR_SHAPE;
-        if (e.oh < 1 || e.ow < 1 || e.oh > 32767 || e.ow > 32767 || e.ksx < 1 || e.ksy < 1) return IMGXF_ERR_SHAPE;
-        if (e.unit_rows < 0 || e.unit_rows > RSL_UNIT_ROWS || e.chunk < 1 || e.chunk > e.ow || ((e.chunk & 3) && e.chunk != e.ow))
+        if (!ll_frame_ok(e.h, e.w, e.row_stride) || !ll_box_ok(e.h, e.w, e.top, e.left, e.bh, e.bw)) return IMGXF_ERR_SHAPE;
+        if (!ll_size_ok(e.oh, e.ow) || e.ksx < 1 || e.ksy < 1) return IMGXF_ERR_SHAPE;
+        if (e.unit_rows < 0 || e.unit_rows > PL_UNIT_ROWS || e.chunk < 1 || e.chunk > e.ow || ((e.chunk & 3) && e.chunk != e.ow))
             return IMGXF_ERR_ARG;
-        if (e.out_off < 0 || (e.out_off & 15) || (uint64_t)e.out_off > out_bytes ||
-            (uint64_t)e.oh * e.ow * 3 > out_bytes - (uint64_t)e.out_off)
-            return IMGXF_ERR_ARG;
+        if (!ll_output_ok(e.out_off, e.oh, e.ow, out_bytes)) return IMGXF_ERR_ARG;
         // windows inside the box, none empty, starts that never decrease (what pl_touched needs of the rows; a table may
         // serve the columns of one entry and the rows of another); a unit's staged span is checked with the unit
         if (!axis_ok(e.bounds_x, e.coeffs_x, e.bw, e.ow, e.ksx) || !axis_ok(e.bounds_y, e.coeffs_y, e.bh, e.oh, e.ksy))
@@ -152,91 +146,59 @@ IMGXF_API int imgxf_resize_list_layout_host(const int32_t* geometry, int n, int 
     if (!geometry || !block_bytes) return IMGXF_ERR_NULL;
     if (!filter_known(filter)) return IMGXF_ERR_ARG;
     if (n < 0 || lds_budget < 1) return IMGXF_ERR_ARG;
-    if (lds_budget > RSL_MAX_LDS) lds_budget = RSL_MAX_LDS;
     const RslGeom* geo = (const RslGeom*)geometry;
     for (int i = 0; i < n; ++i) {
         const RslGeom& g = geo[i];
-        if (g.h < 1 || g.w < 1 || g.h > 32767 || g.w > 32767 || g.oh < 1 || g.ow < 1 || g.oh > 32767 || g.ow > 32767)
-            return IMGXF_ERR_ARG;
-        if (g.top < 0 || g.left < 0 || g.bh < 1 || g.bw < 1 || g.top > g.h - g.bh || g.left > g.w - g.bw)
-            return IMGXF_ERR_ARG;                                 // a box outside its frame
+        if (!ll_size_ok(g.h, g.w) || !ll_size_ok(g.oh, g.ow)) return IMGXF_ERR_ARG;
+        if (!ll_box_ok(g.h, g.w, g.top, g.left, g.bh, g.bw)) return IMGXF_ERR_ARG;       // a box outside its frame
     }
     // pass over the geometry alone: rows and columns per unit, which axes are distinct -> the size of every section
-    struct Plan { int ksx, ksy, unit_rows, chunk; };
-    struct Axis { int ks; int32_t bounds, coeffs; bool built; };
+    struct Plan { int ksx, ksy, unit_rows, chunk, ax, ay; };
     std::vector<Plan> plans(n);
-    std::map<std::pair<int, int>, Axis> axes;                     // by (in, out)
+    AxisTables axes;                                              // by (in, out): the whole axis
     std::map<std::array<int, 4>, Plan> known;                     // by (bh, bw, oh, ow)
-    size_t table_words = 0, n_units = 0, out_bytes = 0;
+    size_t n_units = 0;
     for (int i = 0; i < n; ++i) {
         const RslGeom& g = geo[i];
-        const std::array<int, 4> key = {g.bh, g.bw, g.oh, g.ow};
-        auto it = known.find(key);
-        if (it == known.end()) {
-            Plan p;
+        const auto made = known.emplace(std::array<int, 4>{g.bh, g.bw, g.oh, g.ow}, Plan());
+        if (made.second) {
+            Plan& p = made.first->second;
             p.ksx = coeff_ksize(g.bw, g.ow, filter);
             p.ksy = coeff_ksize(g.bh, g.oh, filter);
             rsl_plan(g.bh, g.bw, g.oh, g.ow, p.ksx, p.ksy, lds_budget, &p.unit_rows, &p.chunk);
-            it = known.emplace(key, p).first;
+            p.ax = p.unit_rows ? axes.intern(filter, g.bw, g.ow, 0, g.ow) : -1;
+            p.ay = p.unit_rows ? axes.intern(filter, g.bh, g.oh, 0, g.oh) : -1;
         }
-        const Plan& p = plans[i] = it->second;
-        out_bytes += ((size_t)g.oh * g.ow * 3 + 15) & ~(size_t)15;
-        if (!p.unit_rows) continue;
-        n_units += (size_t)((g.oh + p.unit_rows - 1) / p.unit_rows) * (size_t)((g.ow + p.chunk - 1) / p.chunk);
-        if (axes.emplace(std::make_pair(g.bw, g.ow), Axis{p.ksx, 0, 0, false}).second) table_words += (size_t)g.ow * (2 + p.ksx);
-        if (axes.emplace(std::make_pair(g.bh, g.oh), Axis{p.ksy, 0, 0, false}).second) table_words += (size_t)g.oh * (2 + p.ksy);
+        const Plan& p = plans[i] = made.first->second;
+        if (p.unit_rows) n_units += (size_t)((g.oh + p.unit_rows - 1) / p.unit_rows) * (size_t)((g.ow + p.chunk - 1) / p.chunk);
     }
-    const size_t entries_off = sizeof(imgxf_resize_list_header);
-    const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_resize_list_entry);
-    const size_t tables_off = units_off + n_units * sizeof(imgxf_resize_list_unit);
-    const size_t total = (tables_off + table_words * 4 + 15) & ~(size_t)15;
-    if (total > 0x7fffffffu) return IMGXF_ERR_SHAPE;
-    *block_bytes = total;
+    RslBlock B;
+    IMGXF_CHECK(B.open((size_t)n, n_units, axes.words, block, block_cap, block_bytes));
     if (!block) return IMGXF_OK;                                  // the size alone
-    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
 
-    u8* out = (u8*)block;
-    memset(out, 0, tables_off);
-    memset(out + tables_off + table_words * 4, 0, total - tables_off - table_words * 4);
-    imgxf_resize_list_header* hd = (imgxf_resize_list_header*)out;
-    imgxf_resize_list_entry* entries = (imgxf_resize_list_entry*)(out + entries_off);
-    imgxf_resize_list_unit* units = (imgxf_resize_list_unit*)(out + units_off);
-    int32_t* words = (int32_t*)out;
-    size_t tpos = tables_off / 4, upos = 0, opos = 0;
+    size_t upos = 0, opos = 0;
     int lds_max = 0;
     std::vector<int> band_rows;
-    auto axis = [&](int in, int osz) -> const Axis& {
-        Axis& a = axes.find(std::make_pair(in, osz))->second;
-        if (!a.built) {
-            pl_append_axis(in, osz, filter, a.ks, 0, osz, words, tpos, &a.bounds, &a.coeffs);
-            a.built = true;
-        }
-        return a;
-    };
     for (int i = 0; i < n; ++i) {
         const RslGeom& g = geo[i];
         const Plan& p = plans[i];
-        imgxf_resize_list_entry& e = entries[i];
+        imgxf_resize_list_entry& e = B.records[i];
         e.h = g.h; e.w = g.w; e.top = g.top; e.left = g.left; e.bh = g.bh; e.bw = g.bw; e.oh = g.oh; e.ow = g.ow;
         e.ksx = p.ksx; e.ksy = p.ksy; e.unit_rows = p.unit_rows; e.chunk = p.chunk;
         e.out_off = (int64_t)opos;
         opos += ((size_t)g.oh * g.ow * 3 + 15) & ~(size_t)15;
         if (!p.unit_rows) continue;
-        const Axis& ax = axis(g.bw, g.ow);
-        const Axis& ay = axis(g.bh, g.oh);
+        const AxisTables::Axis ax = axes.build(p.ax, B.words, B.tpos), ay = axes.build(p.ay, B.words, B.tpos);
         e.bounds_x = ax.bounds; e.coeffs_x = ax.coeffs; e.bounds_y = ay.bounds; e.coeffs_y = ay.coeffs;
         band_rows.clear();
-        for (int y0 = 0; y0 < g.oh; y0 += p.unit_rows) {
-            int lo, hi;
-            pl_span(words + e.bounds_y, y0, std::min(p.unit_rows, g.oh - y0), &lo, &hi);
-            band_rows.push_back(hi - lo);
-        }
+        for (int y0 = 0; y0 < g.oh; y0 += p.unit_rows)
+            band_rows.push_back(pl_span_extent(B.words + e.bounds_y, y0, std::min(p.unit_rows, g.oh - y0)));
         for (int x0 = 0; x0 < g.ow; x0 += p.chunk) {
             const int nx = std::min(p.chunk, g.ow - x0);
             int c_lo, c_hi;
-            pl_span(words + e.bounds_x, x0, nx, &c_lo, &c_hi);
+            pl_span(B.words + e.bounds_x, x0, nx, &c_lo, &c_hi);
             for (int y0 = 0, b = 0; y0 < g.oh; y0 += p.unit_rows, ++b) {
-                imgxf_resize_list_unit& u = units[upos++];
+                imgxf_resize_list_unit& u = B.units[upos++];
                 u.entry = i; u.y0 = y0; u.ny = std::min(p.unit_rows, g.oh - y0); u.x0 = x0; u.nx = nx;
                 u.col0 = c_lo; u.ncols = c_hi - c_lo;
                 u.lds_bytes = (int32_t)pl_lds_bytes(band_rows[b], nx, u.ncols);
@@ -244,9 +206,10 @@ IMGXF_API int imgxf_resize_list_layout_host(const int32_t* geometry, int n, int 
             }
         }
     }
+    imgxf_resize_list_header* hd = B.hd;
     hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->lds_bytes = lds_max;
-    hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->tables_off = (int32_t)tables_off;
-    hd->total_bytes = (int32_t)total; hd->out_bytes = (int64_t)out_bytes;
+    hd->entries_off = (int32_t)B.records_off; hd->units_off = (int32_t)B.units_off; hd->tables_off = (int32_t)B.tables_off;
+    hd->total_bytes = (int32_t)B.total; hd->out_bytes = (int64_t)opos;
     return IMGXF_OK;
 }
 

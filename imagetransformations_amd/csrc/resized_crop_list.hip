@@ -6,11 +6,11 @@
 // and cos: the launch refuses them and the caller takes the per-entry route.
 //
 // Every entry has a box of its own, so nearly every entry has coefficient tables of its own.  The HOST half
-// (imgxf_resized_crop_list_layout_host, no device work) therefore writes no table: one block of
-//   header | entry records | work units
-// with, per entry, what follows in O(1) from the box and the output size: taps per axis, output rows per unit, LDS bound.
+// (imgxf_resized_crop_list_layout_host, no device work; the block protocol is list_layout.h's) therefore writes no table:
+// one block of header | entry records | work units with, per entry, what follows in O(1) from the box and the output
+// size: taps per axis, output rows per unit, LDS bound.
 //
-// DEVICE half (resized_crop_list_kernel): one workgroup per work unit = up to RCL_UNIT_ROWS output rows of one entry.
+// DEVICE half (resized_crop_list_kernel): one workgroup per work unit = up to PL_UNIT_ROWS output rows of one entry.
 //   LDS: | bounds_x [Sw][2] | coeffs_x [Sw][ksx] | bounds_y [ny][2] | coeffs_y [ny][ksy] | mid | stage |
 //   0. a lane builds one row of a table: precompute_coeffs + normalize_coeffs_8bpc for its output column (or output row of
 //      the unit) in fp64, build_coeffs (resample_coeffs.h) restated operation by operation (rcl_build_row<FILTER>: the
@@ -27,9 +27,8 @@
 
 namespace imgxf {
 
-constexpr int RCL_UNIT_ROWS = 16;         // output rows per work unit when the LDS budget allows
-constexpr int RCL_MAX_LDS = 64 * 1024;    // per workgroup, tables included: two of them fit a CU's 160 KiB
 
+using RclBlock = ListBlock<imgxf_resized_crop_header, imgxf_resized_crop_entry, imgxf_resized_crop_unit>;
 // geometry of one entry as the caller states it
 struct RclGeom { int h, w, top, left, bh, bw, flip; };
 
@@ -57,7 +56,7 @@ __attribute__((always_inline)) static inline int64_t rcl_unit_lds(int bh, int bw
 
 // Output rows per unit (pl_unit_rows, resample_list.h)
 static int rcl_unit_rows(int bh, int bw, int sh, int sw, int ksx, int ksy, int lds_budget) {
-    return pl_unit_rows(std::min(sh, RCL_UNIT_ROWS), lds_budget,
+    return pl_unit_rows(sh, lds_budget,
                         [&](int ny) { return rcl_unit_lds(bh, bw, sh, sw, ny, ksx, ksy); });
 }
 
@@ -170,12 +169,10 @@ int resized_crop_list_check(const void* block_host, size_t block_bytes, int filt
     const u8* hb = (const u8*)block_host;
     if (block_bytes < sizeof(imgxf_resized_crop_header)) return IMGXF_ERR_ARG;
     const imgxf_resized_crop_header hd = *(const imgxf_resized_crop_header*)hb;
-    if (hd.n_entries < 0 || hd.n_units < 0 || hd.sh < 1 || hd.sh > 32767 || hd.sw < 1 || hd.sw > 32767 || hd.lds_bytes < 0 ||
-        hd.lds_bytes > RCL_MAX_LDS)
+    if (hd.n_entries < 0 || hd.n_units < 0 || !ll_size_ok(hd.sh, hd.sw) || hd.lds_bytes < 0 || hd.lds_bytes > PL_MAX_LDS)
         return IMGXF_ERR_ARG;
-    if (!pl_check_sections(sizeof(imgxf_resized_crop_header), hd.n_entries, sizeof(imgxf_resized_crop_entry), hd.n_units,
-                           sizeof(imgxf_resized_crop_unit), hd.entries_off, hd.units_off,
-                           hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_resized_crop_unit), hd.total_bytes) ||
+    if (!RclBlock::pl_check_sections(hd.n_entries, hd.n_units, hd.entries_off, hd.units_off,
+                                     hd.units_off + (int64_t)hd.n_units * (int64_t)sizeof(imgxf_resized_crop_unit), hd.total_bytes) ||
         (size_t)hd.total_bytes > block_bytes)                     // (no tables: the units end the block)
         return IMGXF_ERR_ARG;
     const imgxf_resized_crop_entry* entries = (const imgxf_resized_crop_entry*)(hb + hd.entries_off);
@@ -184,10 +181,9 @@ int resized_crop_list_check(const void* block_host, size_t block_bytes, int filt
         const imgxf_resized_crop_entry& e = entries[i];
         if (!e.unit_rows) continue;
         if (!e.data) return IMGXF_ERR_NULL;
-        if (e.h < 1 || e.w < 1 || e.h > 32767 || e.w > 32767 || e.row_stride < (int64_t)e.w * 3) return IMGXF_ERR_SHAPE;
-        if (e.top < 0 || e.left < 0 || e.bh < 1 || e.bw < 1 || e.top > e.h - e.bh || e.left > e.w - e.bw) return IMGXF_ERR_SHAPE;
+        if (!ll_frame_ok(e.h, e.w, e.row_stride) || !ll_box_ok(e.h, e.w, e.top, e.left, e.bh, e.bw)) return IMGXF_ERR_SHAPE;
         if (e.ksx != coeff_ksize(e.bw, hd.sw, filter) || e.ksy != coeff_ksize(e.bh, hd.sh, filter)) return IMGXF_ERR_ARG;
-        if (e.unit_rows < 0 || e.unit_rows > RCL_UNIT_ROWS || (e.flip != 0 && e.flip != 1)) return IMGXF_ERR_ARG;
+        if (e.unit_rows < 0 || e.unit_rows > PL_UNIT_ROWS || (e.flip != 0 && e.flip != 1)) return IMGXF_ERR_ARG;
         if (e.tall != rcl_tall(e.bh, e.bw, hd.sh)) return IMGXF_ERR_ARG;
     }
     for (int k = 0; k < hd.n_units; ++k) {
@@ -209,36 +205,25 @@ IMGXF_API int imgxf_resized_crop_list_layout_filter_host(const int32_t* geometry
                                                          int lds_budget, void* block, size_t block_cap, size_t* block_bytes) {
     if (!geometry || !block_bytes) return IMGXF_ERR_NULL;
     if (!filter_known(filter)) return IMGXF_ERR_ARG;
-    if (n < 0 || sh < 1 || sh > 32767 || sw < 1 || sw > 32767 || lds_budget < 1) return IMGXF_ERR_ARG;
-    if (lds_budget > RCL_MAX_LDS) lds_budget = RCL_MAX_LDS;
+    if (n < 0 || !ll_size_ok(sh, sw) || lds_budget < 1) return IMGXF_ERR_ARG;
     const RclGeom* geo = (const RclGeom*)geometry;
     size_t n_units = 0;
     for (int i = 0; i < n; ++i) {
         const RclGeom& g = geo[i];
-        if (g.h < 1 || g.w < 1 || g.h > 32767 || g.w > 32767 || (g.flip != 0 && g.flip != 1)) return IMGXF_ERR_ARG;
-        if (g.top < 0 || g.left < 0 || g.bh < 1 || g.bw < 1 || g.top > g.h - g.bh || g.left > g.w - g.bw)
-            return IMGXF_ERR_ARG;                                 // a box outside its frame
+        if (!ll_size_ok(g.h, g.w) || (g.flip != 0 && g.flip != 1)) return IMGXF_ERR_ARG;
+        if (!ll_box_ok(g.h, g.w, g.top, g.left, g.bh, g.bw)) return IMGXF_ERR_ARG;       // a box outside its frame
         const int ur = rcl_unit_rows(g.bh, g.bw, sh, sw, coeff_ksize(g.bw, sw, filter), coeff_ksize(g.bh, sh, filter), lds_budget);
         if (ur) n_units += (size_t)(sh + ur - 1) / ur;
     }
-    const size_t entries_off = sizeof(imgxf_resized_crop_header);
-    const size_t units_off = entries_off + (size_t)n * sizeof(imgxf_resized_crop_entry);
-    const size_t total = (units_off + n_units * sizeof(imgxf_resized_crop_unit) + 15) & ~(size_t)15;
-    if (total > 0x7fffffffu) return IMGXF_ERR_SHAPE;
-    *block_bytes = total;
+    RclBlock B;
+    IMGXF_CHECK(B.open((size_t)n, n_units, 0, block, block_cap, block_bytes));
     if (!block) return IMGXF_OK;                                  // the size alone
-    if (block_cap < total) return IMGXF_ERR_WORKSPACE;
 
-    u8* out = (u8*)block;
-    memset(out, 0, total);
-    imgxf_resized_crop_header* hd = (imgxf_resized_crop_header*)out;
-    imgxf_resized_crop_entry* entries = (imgxf_resized_crop_entry*)(out + entries_off);
-    imgxf_resized_crop_unit* units = (imgxf_resized_crop_unit*)(out + units_off);
     int lds_max = 0;
     size_t upos = 0;
     for (int i = 0; i < n; ++i) {
         const RclGeom& g = geo[i];
-        imgxf_resized_crop_entry& e = entries[i];
+        imgxf_resized_crop_entry& e = B.records[i];
         e.h = g.h; e.w = g.w; e.top = g.top; e.left = g.left; e.bh = g.bh; e.bw = g.bw; e.flip = g.flip;
         e.ksx = coeff_ksize(g.bw, sw, filter);
         e.ksy = coeff_ksize(g.bh, sh, filter);
@@ -247,14 +232,15 @@ IMGXF_API int imgxf_resized_crop_list_layout_filter_host(const int32_t* geometry
         if (!e.unit_rows) continue;
         e.lds_bytes = (int32_t)rcl_unit_lds(g.bh, g.bw, sh, sw, e.unit_rows, e.ksx, e.ksy);
         for (int y0 = 0; y0 < sh; y0 += e.unit_rows) {
-            imgxf_resized_crop_unit& u = units[upos++];
+            imgxf_resized_crop_unit& u = B.units[upos++];
             u.entry = i; u.y0 = y0; u.ny = std::min(e.unit_rows, sh - y0);
             u.lds_bytes = (int32_t)rcl_unit_lds(g.bh, g.bw, sh, sw, u.ny, e.ksx, e.ksy);
             lds_max = std::max(lds_max, u.lds_bytes);
         }
     }
+    imgxf_resized_crop_header* hd = B.hd;
     hd->n_entries = n; hd->n_units = (int32_t)n_units; hd->sh = sh; hd->sw = sw; hd->lds_bytes = lds_max;
-    hd->entries_off = (int32_t)entries_off; hd->units_off = (int32_t)units_off; hd->total_bytes = (int32_t)total;
+    hd->entries_off = (int32_t)B.records_off; hd->units_off = (int32_t)B.units_off; hd->total_bytes = (int32_t)B.total;
     return IMGXF_OK;
 }
 

@@ -5,7 +5,8 @@
 //         -Iinclude -Iimagetransformations_amd/csrc tools/fuzz_driver_list.hip -o _exp/fuzz_driver_list
 //     ASAN_OPTIONS=detect_leaks=0 _exp/fuzz_driver_list [rounds] [seed]
 // Exit status 0: every valid block passed, no mutated block made the checks read outside the block (the sanitizer aborts
-// otherwise).  The two symbols driver_list.hip takes from other translation units are given here.
+// otherwise).  The last line printed is a running hash of every return code seen (layouts, checks of the valid and of the
+// mutated blocks): equal seeds and rounds give equal lines for as long as the host code decides the same.  The two symbols driver_list.hip takes from other translation units are given here.
 #include "../imagetransformations_amd/csrc/driver_list.hip"
 #include <random>
 #include <vector>
@@ -26,6 +27,8 @@ int main(int argc, char** argv) {
     const int types[] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 12, 13, 9, 11};
     const int widths[] = {1, 7, 16, 61, 64, 85, 86, 96, 100, 352, 500, 1024};
     long laid = 0, accepted = 0, mutated = 0, rejected = 0, family = 0;
+    uint64_t codes = 1469598103934665603ull;                  // FNV-1a over every return code seen, in order
+    auto seen = [&](int rc) { codes = (codes ^ (uint32_t)rc) * 1099511628211ull; return rc; };
     for (int round = 0; round < rounds; ++round) {
         const int n = uni(0, 400);
         std::vector<int32_t> geo((size_t)n * 5);
@@ -50,16 +53,16 @@ int main(int argc, char** argv) {
         }
         const int budget = uni(0, 3) ? 65536 : uni(1, 70000);
         size_t need = 0;
-        int rc = imgxf_driver_list_layout_host(geo.data(), par.data(), n, budget, nullptr, 0, &need, nullptr, nullptr, nullptr,
-                                               nullptr, nullptr);
+        int rc = seen(imgxf_driver_list_layout_host(geo.data(), par.data(), n, budget, nullptr, 0, &need, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr));
         if (rc != IMGXF_OK) { fprintf(stderr, "size pass: %d\n", rc); return 2; }
         std::vector<u8> block(need);                          // exactly the stated size: one byte past it is the sanitizer's
         std::vector<int64_t> off((size_t)n);
         std::vector<int32_t> hw((size_t)n * 2), status((size_t)n);
         size_t need2 = 0, out_bytes = 0;
         int32_t lds = 0;
-        rc = imgxf_driver_list_layout_host(geo.data(), par.data(), n, budget, block.data(), block.size(), &need2, off.data(),
-                                           hw.data(), status.data(), &out_bytes, &lds);
+        rc = seen(imgxf_driver_list_layout_host(geo.data(), par.data(), n, budget, block.data(), block.size(), &need2,
+                                                off.data(), hw.data(), status.data(), &out_bytes, &lds));
         if (rc != IMGXF_OK || need2 != need) { fprintf(stderr, "layout: %d (%zu, %zu)\n", rc, need, need2); return 2; }
         ++laid;
         imgxf_driver_header* hd = (imgxf_driver_header*)block.data();
@@ -82,7 +85,7 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
-        rc = driver_list_check(block.data(), (void*)4096, (const uint8_t*)4096, out_bytes);
+        rc = seen(driver_list_check(block.data(), (void*)4096, (const uint8_t*)4096, out_bytes));
         if (rc != IMGXF_OK) { fprintf(stderr, "a valid block was rejected: %d (round %d)\n", rc, round); return 2; }
         ++accepted;
         if (!hd->n_units) continue;
@@ -109,10 +112,11 @@ int main(int argc, char** argv) {
                 ((int32_t*)(block.data() + tables))[uni(0, (int)((need - tables) / 4) - 1)] = uni(0, 1) ? uni(-40000, 40000) : INT32_MAX;
             }
             ++mutated;
-            rejected += driver_list_check(block.data(), (void*)4096, (const uint8_t*)4096, out_bytes) != IMGXF_OK;
+            rejected += seen(driver_list_check(block.data(), (void*)4096, (const uint8_t*)4096, out_bytes)) != IMGXF_OK;
         }
     }
     printf("%ld layouts, %ld valid blocks accepted, %ld of %ld mutated blocks rejected, %ld entries refused for family\n", laid,
            accepted, rejected, mutated, family);
+    printf("return codes: %016llx\n", (unsigned long long)codes);
     return 0;
 }

@@ -10,6 +10,8 @@
 //     ASAN_OPTIONS=detect_leaks=0 _exp/fuzz_resize_list [rounds] [seed]
 // Exit status 0: every block tiled its entries and kept its LDS, every valid block passed, every hostile geometry was
 // refused, no mutated block made the checks read outside the block (the sanitizer aborts otherwise).
+// The last line printed is a running hash of every return code seen (layouts, launcher, checks of the valid and of the
+// mutated blocks): equal seeds and rounds give equal lines for as long as the host code decides the same.
 #include "../imagetransformations_amd/csrc/resize_list.hip"
 #include <random>
 #include <vector>
@@ -22,6 +24,8 @@ int main(int argc, char** argv) {
                            IMGXF_RESAMPLE_LANCZOS};
     long laid = 0, too_large = 0, entries = 0, beyond = 0, rows_first = 0, chunked = 0, n_units = 0, hostile = 0, refused = 0,
          mutated = 0, rejected = 0;
+    uint64_t codes = 1469598103934665603ull;                  // FNV-1a over every return code seen, in order
+    auto seen = [&](int rc) { codes = (codes ^ (uint32_t)rc) * 1099511628211ull; return rc; };
     for (int round = 0; round < rounds; ++round) {
         const int n = uni(0, 3) ? uni(0, 24) : uni(0, 200);
         const int budget = uni(0, 2) == 0 ? 65536 : uni(0, 1) ? uni(1, 70000) : uni(1, 4096);
@@ -46,13 +50,13 @@ int main(int argc, char** argv) {
             g[7] = uni(0, 5) ? side(uni(0, 3) ? okind : uni(0, 2)) : g[5];
         }
         size_t need = 0, need2 = 0;
-        int rc = imgxf_resize_list_layout_host(geo.data(), n, filter, budget, nullptr, 0, &need);
+        int rc = seen(imgxf_resize_list_layout_host(geo.data(), n, filter, budget, nullptr, 0, &need));
         if (rc == IMGXF_ERR_SHAPE || (rc == IMGXF_OK && need > ((size_t)96 << 20))) { ++too_large; continue; }
         if (rc != IMGXF_OK) { fprintf(stderr, "size pass: %d\n", rc); return 2; }
         std::vector<u8> block(need);                              // exactly the stated size: one byte past it is the sanitizer's
-        rc = imgxf_resize_list_layout_host(geo.data(), n, filter, budget, block.data(), block.size(), &need2);
+        rc = seen(imgxf_resize_list_layout_host(geo.data(), n, filter, budget, block.data(), block.size(), &need2));
         if (rc != IMGXF_OK || need2 != need) { fprintf(stderr, "layout: %d (%zu, %zu)\n", rc, need, need2); return 2; }
-        if (imgxf_resize_list_layout_host(geo.data(), n, filter, budget, block.data(), need - 1, &need2) != IMGXF_ERR_WORKSPACE) {
+        if (seen(imgxf_resize_list_layout_host(geo.data(), n, filter, budget, block.data(), need - 1, &need2)) != IMGXF_ERR_WORKSPACE) {
             fprintf(stderr, "a short block was not refused\n");
             return 2;
         }
@@ -98,10 +102,10 @@ int main(int argc, char** argv) {
             if (cx != e.ow || cy != 0 || area != (int64_t)e.oh * e.ow) { fprintf(stderr, "entry %d is not covered (round %d)\n", i, round); return 2; }
         }
         if (k != hd->n_units) { fprintf(stderr, "units out of order (round %d)\n", round); return 2; }
-        rc = imgxf::resize_list_check(block.data(), block.size(), (size_t)hd->out_bytes);
+        rc = seen(imgxf::resize_list_check(block.data(), block.size(), (size_t)hd->out_bytes));
         if (rc != IMGXF_OK) { fprintf(stderr, "a valid block was rejected: %d (round %d)\n", rc, round); return 2; }
         // the launcher with a valid block and no device block: it must stop at its own NULL check, before any launch
-        rc = imgxf_resize_list_u8(block.data(), block.size(), nullptr, nullptr, (size_t)hd->out_bytes, nullptr);
+        rc = seen(imgxf_resize_list_u8(block.data(), block.size(), nullptr, nullptr, (size_t)hd->out_bytes, nullptr));
         if (rc != (hd->n_units ? IMGXF_ERR_NULL : IMGXF_OK)) { fprintf(stderr, "launcher: %d\n", rc); return 2; }
 
         for (int m = 0; m < 40 && n; ++m) {                       // hostile geometry: every one must be refused by the layout
@@ -117,11 +121,11 @@ int main(int argc, char** argv) {
                 default: g[uni(6, 7)] = uni(0, 2) == 0 ? 0 : uni(0, 1) ? 32768 + uni(0, 9) : -uni(1, 9); break;
             }
             ++hostile;
-            refused += imgxf_resize_list_layout_host(bad.data(), n, filter, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+            refused += seen(imgxf_resize_list_layout_host(bad.data(), n, filter, budget, nullptr, 0, &need2)) == IMGXF_ERR_ARG;
         }
         hostile += 2;                                             // a filter that is none of Resample.c's, no budget
-        refused += imgxf_resize_list_layout_host(geo.data(), n, uni(0, 1) ? 0 : uni(6, 99), budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
-        refused += imgxf_resize_list_layout_host(geo.data(), n, filter, -uni(0, 9), nullptr, 0, &need2) == IMGXF_ERR_ARG;
+        refused += seen(imgxf_resize_list_layout_host(geo.data(), n, uni(0, 1) ? 0 : uni(6, 99), budget, nullptr, 0, &need2)) == IMGXF_ERR_ARG;
+        refused += seen(imgxf_resize_list_layout_host(geo.data(), n, filter, -uni(0, 9), nullptr, 0, &need2)) == IMGXF_ERR_ARG;
 
         const std::vector<u8> good = block;
         const size_t out_bytes = (size_t)hd->out_bytes;
@@ -148,11 +152,12 @@ int main(int argc, char** argv) {
                 (uni(0, 1) ? h2->n_units : h2->n_entries) += uni(1, 1 << 20);
             }
             ++mutated;
-            rejected += imgxf::resize_list_check(block.data(), bytes, uni(0, 3) ? out_bytes : (size_t)uni(0, 4096)) != IMGXF_OK;
+            rejected += seen(imgxf::resize_list_check(block.data(), bytes, uni(0, 3) ? out_bytes : (size_t)uni(0, 4096))) != IMGXF_OK;
         }
     }
     printf("%ld layouts (%ld skipped as too large), %ld entries (%ld beyond the budget, %ld rows first, %ld cut into chunks), "
            "%ld units tiled, %ld of %ld hostile geometries refused, %ld of %ld mutated blocks rejected\n", laid, too_large, entries,
            beyond, rows_first, chunked, n_units, refused, hostile, rejected, mutated);
+    printf("return codes: %016llx\n", (unsigned long long)codes);
     return refused == hostile ? 0 : 3;
 }

@@ -10,6 +10,8 @@
 //     ASAN_OPTIONS=detect_leaks=0 _exp/fuzz_resized_crop_list [rounds] [seed]
 // Exit status 0: the row builder equals build_coeffs, every valid block passed, every hostile geometry was refused, no
 // mutated block made the checks read outside the block (the sanitizer aborts otherwise).
+// The last line printed is a running hash of every return code seen (layouts, launcher, checks of the valid and of the
+// mutated blocks): equal seeds and rounds give equal lines for as long as the host code decides the same.
 #include "../imagetransformations_amd/csrc/resized_crop_list.hip"
 #include <random>
 #include <vector>
@@ -65,13 +67,15 @@ int main(int argc, char** argv) {
     const int filters[] = {IMGXF_RESAMPLE_BILINEAR, IMGXF_RESAMPLE_BICUBIC, IMGXF_RESAMPLE_BOX, IMGXF_RESAMPLE_HAMMING,
                            IMGXF_RESAMPLE_LANCZOS};
     long laid = 0, accepted = 0, hostile = 0, refused = 0, mutated = 0, rejected = 0, entries = 0, beyond = 0, tall = 0;
+    uint64_t codes = 1469598103934665603ull;                  // FNV-1a over every return code seen, in order
+    auto seen = [&](int rc) { codes = (codes ^ (uint32_t)rc) * 1099511628211ull; return rc; };
     for (int round = 0; round < rounds; ++round) {
         const int n = uni(0, 300);
         const int sh = uni(0, 3) ? uni(1, 300) : uni(1, 5), sw = uni(0, 3) ? uni(1, 300) : uni(1, 5);
         const int budget = uni(0, 3) ? 65536 : uni(1, 70000);
         const int filter = filters[uni(0, 4)];
         const bool built = filter_polynomial(filter);         // the launch builds this filter's tables
-        std::vector<int32_t> geo((size_t)n * 7);
+        std::vector<int32_t> geo((size_t)n * 7 + 1);             // (+ a spare word: an empty list still has an address)
         for (int i = 0; i < n; ++i) {
             int32_t* g = &geo[(size_t)i * 7];
             const int kind = uni(0, 5);
@@ -82,12 +86,12 @@ int main(int argc, char** argv) {
             g[6] = uni(0, 1);
         }
         size_t need = 0, need2 = 0;
-        int rc = imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, filter, budget, nullptr, 0, &need);
+        int rc = seen(imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, filter, budget, nullptr, 0, &need));
         if (rc != IMGXF_OK) { fprintf(stderr, "size pass: %d\n", rc); return 2; }
         std::vector<u8> block(need);                          // exactly the stated size: one byte past it is the sanitizer's
-        rc = imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, filter, budget, block.data(), block.size(), &need2);
+        rc = seen(imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, filter, budget, block.data(), block.size(), &need2));
         if (rc != IMGXF_OK || need2 != need) { fprintf(stderr, "layout: %d (%zu, %zu)\n", rc, need, need2); return 2; }
-        if (need && imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, filter, budget, block.data(), need - 1, &need2) != IMGXF_ERR_WORKSPACE) {
+        if (need && seen(imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, filter, budget, block.data(), need - 1, &need2)) != IMGXF_ERR_WORKSPACE) {
             fprintf(stderr, "a short block was not refused\n");
             return 2;
         }
@@ -100,14 +104,14 @@ int main(int argc, char** argv) {
         }
         entries += n;
         if (hd->lds_bytes > (budget < 65536 ? budget : 65536)) { fprintf(stderr, "LDS %d above the budget %d\n", hd->lds_bytes, budget); return 2; }
-        rc = imgxf::resized_crop_list_check(block.data(), block.size(), filter);
+        rc = seen(imgxf::resized_crop_list_check(block.data(), block.size(), filter));
         if (rc != IMGXF_OK) { fprintf(stderr, "a valid block was rejected: %d (round %d)\n", rc, round); return 2; }
         ++accepted;
         // the launcher with a valid block and no device block: it must stop at its own NULL check, before any launch
         // (a filter whose tables the kernel does not build is refused before anything else)
-        rc = imgxf_resized_crop_list_filter(block.data(), block.size(), nullptr, nullptr, 0, filter, nullptr, nullptr, nullptr);
+        rc = seen(imgxf_resized_crop_list_filter(block.data(), block.size(), nullptr, nullptr, 0, filter, nullptr, nullptr, nullptr));
         if (rc != (!built ? IMGXF_ERR_UNSUPPORTED : hd->n_units ? IMGXF_ERR_NULL : IMGXF_OK)) { fprintf(stderr, "launcher: %d\n", rc); return 2; }
-        if (imgxf_resized_crop_list_filter(block.data(), block.size(), nullptr, nullptr, 0, uni(0, 1) ? 0 : 6, nullptr, nullptr, nullptr) != IMGXF_ERR_ARG) {
+        if (seen(imgxf_resized_crop_list_filter(block.data(), block.size(), nullptr, nullptr, 0, uni(0, 1) ? 0 : 6, nullptr, nullptr, nullptr)) != IMGXF_ERR_ARG) {
             fprintf(stderr, "an unknown filter was not refused\n");
             return 2;
         }
@@ -126,15 +130,15 @@ int main(int argc, char** argv) {
                 default: g[4] = g[0] + 1; g[2] = 0; break;
             }
             ++hostile;
-            refused += imgxf_resized_crop_list_layout_filter_host(bad.data(), n, sh, sw, filter, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+            refused += seen(imgxf_resized_crop_list_layout_filter_host(bad.data(), n, sh, sw, filter, budget, nullptr, 0, &need2)) == IMGXF_ERR_ARG;
         }
         const int bad_sizes[] = {0, -1, 32768, INT32_MAX, INT32_MIN};
         hostile += 1;                                         // a filter that is none of Resample.c's
-        refused += imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, uni(0, 1) ? 0 : uni(6, 99), budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+        refused += seen(imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, sw, uni(0, 1) ? 0 : uni(6, 99), budget, nullptr, 0, &need2)) == IMGXF_ERR_ARG;
         for (int v : bad_sizes) {
             hostile += 2;
-            refused += imgxf_resized_crop_list_layout_filter_host(geo.data(), n, v, sw, filter, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
-            refused += imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, v, filter, budget, nullptr, 0, &need2) == IMGXF_ERR_ARG;
+            refused += seen(imgxf_resized_crop_list_layout_filter_host(geo.data(), n, v, sw, filter, budget, nullptr, 0, &need2)) == IMGXF_ERR_ARG;
+            refused += seen(imgxf_resized_crop_list_layout_filter_host(geo.data(), n, sh, v, filter, budget, nullptr, 0, &need2)) == IMGXF_ERR_ARG;
         }
 
         const std::vector<u8> good = block;
@@ -158,10 +162,11 @@ int main(int argc, char** argv) {
                 (uni(0, 1) ? h2->n_units : h2->n_entries) += uni(1, 1 << 20);
             }
             ++mutated;
-            rejected += imgxf::resized_crop_list_check(block.data(), bytes, filter) != IMGXF_OK;
+            rejected += seen(imgxf::resized_crop_list_check(block.data(), bytes, filter)) != IMGXF_OK;
         }
     }
     printf("%ld layouts (%ld entries, %ld beyond the budget, %ld tall), %ld valid blocks accepted, %ld of %ld hostile geometries "
            "refused, %ld of %ld mutated blocks rejected\n", laid, entries, beyond, tall, accepted, refused, hostile, rejected, mutated);
+    printf("return codes: %016llx\n", (unsigned long long)codes);
     return refused == hostile ? 0 : 3;
 }
