@@ -17,6 +17,7 @@ OK, ERR_NULL, ERR_SHAPE, ERR_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_NO_DEVICE 
 BORDER_REFLECT_101, BORDER_REFLECT = 0, 1
 FILTER_NEAREST, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
 SOBEL_X_WRAP, SOBEL_Y_WRAP, SOBEL_MAGNITUDE = 0, 1, 2
+SOBEL_PLAN_INTS = 12     # out[] of imgxf_sobel_plan_host
 
 
 class ImgxfError(RuntimeError):
@@ -81,6 +82,7 @@ SIGNATURES = {
     "imgxf_sobel_u8": [_VP, _VP, C.c_int, C.c_void_p],
     "imgxf_rgb_sobel_mag_u8": [_VP, _VP, C.c_void_p],
     "imgxf_rgb_sobel_u8": [_VP, _VP, C.c_int, C.c_void_p],
+    "imgxf_sobel_plan_host": [_VP, _VP, C.POINTER(C.c_int)],
     "imgxf_affine_u8": [_VP, _VP, _D, C.c_int, _U8, C.c_int, _VP, C.c_void_p],
     "imgxf_affine_scale_nearest_u8": [_VP, _VP, _D, _U8, C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_lanczos_plan_create": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],

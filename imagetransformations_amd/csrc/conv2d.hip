@@ -505,44 +505,67 @@ IMGXF_API int imgxf_conv2d_u8(const imgxf_view* src, const imgxf_view* dst, cons
     return launch_status();
 }
 
-IMGXF_API int imgxf_sobel_u8(const imgxf_view* src, const imgxf_view* dst, int variant, void* stream) {
-    IMGXF_CHECK(check_view(src));
-    IMGXF_CHECK(check_view(dst));
-    if (!same_geometry(src, dst) || src->c != 1) return IMGXF_ERR_SHAPE;
-    if (variant < 0 || variant > 2) return IMGXF_ERR_ARG;
-    if (empty_view(src)) return IMGXF_OK;
-    const View s = make_view(src), d = make_view(dst);
+// Both Sobel entry points after their checks: launches of at most SOBEL_MAX_FRAMES frames (blockIdx.z is the frame), each
+// from plan_sobel()'s record (sobel_march.inc), the views advanced by whole frames.
+template <int CIN>
+static int run_sobel(const View& s0, const View& d0, int variant, hipStream_t st) {
     const bool no_march = knob_set(K_NO_MARCH);
-    if (!no_march && sobel_march_eligible(s, d, 1)) {
-        switch (variant) {
-            case IMGXF_SOBEL_X_WRAP: return launch_sobel_march<1, IMGXF_SOBEL_X_WRAP>(s, d, (hipStream_t)stream);
-            case IMGXF_SOBEL_Y_WRAP: return launch_sobel_march<1, IMGXF_SOBEL_Y_WRAP>(s, d, (hipStream_t)stream);
-            default: return launch_sobel_march<1, IMGXF_SOBEL_MAGNITUDE>(s, d, (hipStream_t)stream);
+    for (int f0 = 0; f0 < s0.n; f0 += SOBEL_MAX_FRAMES) {
+        const int nf = std::min(SOBEL_MAX_FRAMES, s0.n - f0);
+        const View s = sobel_frames(s0, f0, nf), d = sobel_frames(d0, f0, nf);
+        const SobelPlan P = plan_sobel(s, d, CIN, no_march);
+        if (P.march) {
+            switch (variant) {
+                case IMGXF_SOBEL_X_WRAP: IMGXF_CHECK((launch_sobel_march<CIN, IMGXF_SOBEL_X_WRAP>(s, d, P, st))); break;
+                case IMGXF_SOBEL_Y_WRAP: IMGXF_CHECK((launch_sobel_march<CIN, IMGXF_SOBEL_Y_WRAP>(s, d, P, st))); break;
+                default: IMGXF_CHECK((launch_sobel_march<CIN, IMGXF_SOBEL_MAGNITUDE>(s, d, P, st))); break;
+            }
+        } else {
+            hipLaunchKernelGGL((sobel_kernel<CIN == 3>), P.grid, P.block, P.lds, st, s, d, variant);
+            IMGXF_CHECK(launch_status());
         }
     }
-    dim3 grid((unsigned)((s.w + 63) / 64), (unsigned)((s.h + 15) / 16), (unsigned)s.n);
-    hipLaunchKernelGGL((sobel_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, s, d, variant);
-    return launch_status();
+    return IMGXF_OK;
+}
+
+// what the entry points check before anything else; cin = 1 (imgxf_sobel_u8) or 3 (imgxf_rgb_sobel_u8)
+static int check_sobel_views(const imgxf_view* src, const imgxf_view* dst, int cin) {
+    IMGXF_CHECK(check_view(src));
+    IMGXF_CHECK(check_view(dst));
+    if (!same_nhw(src, dst) || src->c != cin || dst->c != 1) return IMGXF_ERR_SHAPE;
+    return IMGXF_OK;
+}
+
+IMGXF_API int imgxf_sobel_u8(const imgxf_view* src, const imgxf_view* dst, int variant, void* stream) {
+    IMGXF_CHECK(check_sobel_views(src, dst, 1));
+    if (variant < 0 || variant > 2) return IMGXF_ERR_ARG;
+    if (empty_view(src)) return IMGXF_OK;
+    return run_sobel<1>(make_view(src), make_view(dst), variant, (hipStream_t)stream);
 }
 
 IMGXF_API int imgxf_rgb_sobel_u8(const imgxf_view* src, const imgxf_view* dst, int variant, void* stream) {
-    IMGXF_CHECK(check_view(src));
-    IMGXF_CHECK(check_view(dst));
-    if (!same_nhw(src, dst) || src->c != 3 || dst->c != 1) return IMGXF_ERR_SHAPE;
+    IMGXF_CHECK(check_sobel_views(src, dst, 3));
     if (variant < 0 || variant > 2) return IMGXF_ERR_ARG;
     if (empty_view(src)) return IMGXF_OK;
-    const View s = make_view(src), d = make_view(dst);
-    const bool no_march = knob_set(K_NO_MARCH);
-    if (!no_march && sobel_march_eligible(s, d, 3)) {
-        switch (variant) {
-            case IMGXF_SOBEL_X_WRAP: return launch_sobel_march<3, IMGXF_SOBEL_X_WRAP>(s, d, (hipStream_t)stream);
-            case IMGXF_SOBEL_Y_WRAP: return launch_sobel_march<3, IMGXF_SOBEL_Y_WRAP>(s, d, (hipStream_t)stream);
-            default: return launch_sobel_march<3, IMGXF_SOBEL_MAGNITUDE>(s, d, (hipStream_t)stream);
-        }
-    }
-    dim3 grid((unsigned)((s.w + 63) / 64), (unsigned)((s.h + 15) / 16), (unsigned)s.n);
-    hipLaunchKernelGGL((sobel_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, s, d, variant);
-    return launch_status();
+    return run_sobel<3>(make_view(src), make_view(dst), variant, (hipStream_t)stream);
+}
+
+IMGXF_API int imgxf_sobel_plan_host(const imgxf_view* src, const imgxf_view* dst, int* out) {
+    if (!out) return IMGXF_ERR_NULL;
+    IMGXF_CHECK(check_view(src));
+    IMGXF_CHECK(check_sobel_views(src, dst, src->c == 3 ? 3 : 1));
+    for (int i = 0; i < IMGXF_SOBEL_PLAN_INTS; ++i) out[i] = 0;
+    if (empty_view(src)) return IMGXF_OK;
+    const View s0 = make_view(src), d0 = make_view(dst);
+    const int nf = std::min(SOBEL_MAX_FRAMES, s0.n);
+    const SobelPlan P = plan_sobel(sobel_frames(s0, 0, nf), sobel_frames(d0, 0, nf), src->c, knob_set(K_NO_MARCH));
+    out[0] = P.march ? 1 : 0;
+    out[1] = P.nstrips; out[2] = P.spb; out[3] = P.rpw; out[4] = P.nchunks; out[5] = P.nchunks0;
+    out[6] = (int)P.grid.x; out[7] = (int)P.grid.y; out[8] = (int)P.grid.z;
+    out[9] = (int)P.block.x;
+    out[10] = (int)P.lds;
+    out[11] = (s0.n + SOBEL_MAX_FRAMES - 1) / SOBEL_MAX_FRAMES;
+    return IMGXF_OK;
 }
 
 IMGXF_API int imgxf_rgb_sobel_mag_u8(const imgxf_view* src, const imgxf_view* dst, void* stream) {

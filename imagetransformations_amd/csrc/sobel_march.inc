@@ -182,19 +182,43 @@ __global__ __launch_bounds__(256) void sobel_march_kernel(View src, View dst, in
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-inline bool sobel_march_eligible(const View& s, const View& d, int cin) {
-    (void)cin;
-    if (s.w % 16 || s.w <= 1024 || s.h < 2) return false;   // >= 2 strips: every row step issues its edge DMA
+// ---- what a Sobel call launches, decided apart from launching it (host only: no HIP call, no look at the environment) ----
+// The entry points of conv2d.hip launch from this record and imgxf_sobel_plan_host hands it out, so the tests choose their
+// geometries from the rule itself.  Both kernels take the frame from blockIdx.z: a batch runs in launches of at most
+// SOBEL_MAX_FRAMES frames, each planned for its own frame count.
+constexpr int SOBEL_MARCH_J = 4;                 // rows in flight of sobel_march_kernel
+constexpr int SOBEL_MAX_FRAMES = 65535;          // grid.z
+
+struct SobelPlan {
+    bool march;                                  // sobel_march_kernel, else sobel_kernel (conv2d.hip)
+    int nstrips, spb, rpw, nchunks, nchunks0;    // marching: 1 KiB-pixel strips per row, strips per workgroup, rows per wave,
+                                                 // row chunks, and the chunks before the doubling that fills the chip (else 0)
+    dim3 grid, block;
+    size_t lds;
+};
+
+// marching needs >= 2 strips (every row step issues its edge DMA), whole 16-pixel lanes, >= 2 rows, and base address, row
+// and frame stride of both views as multiples of 16 (the frame stride of a single frame included)
+inline bool sobel_march_eligible(const View& s, const View& d) {
+    if (s.w % 16 || s.w <= 1024 || s.h < 2) return false;
     if (((uintptr_t)s.p | (uintptr_t)d.p) & 15) return false;
     if ((s.rs | s.fs | d.rs | d.fs) & 15) return false;
     return true;
 }
 
-template <int CIN, int VARIANT>
-inline int launch_sobel_march(const View& s, const View& d, hipStream_t st) {
-    constexpr int J = 4;
+// s.n <= SOBEL_MAX_FRAMES; cin = 1 (L in) or 3 (RGB in)
+inline SobelPlan plan_sobel(const View& s, const View& d, int cin, bool no_march) {
+    SobelPlan P = SobelPlan();
+    P.march = !no_march && sobel_march_eligible(s, d);
+    if (!P.march) {                              // 64 x 16 pixel tiles
+        P.grid = dim3((unsigned)((s.w + 63) / 64), (unsigned)((s.h + 15) / 16), (unsigned)s.n);
+        P.block = dim3(256);
+        return P;
+    }
     int64_t nchunks = (s.h + 95) / 96;
+    P.nchunks0 = (int)nchunks;
     const int nstrips = (s.w + 1023) / 1024;
+    // strips per workgroup: the largest of 4 ... 1 that leaves the fewest idle waves in the last workgroup of a row
     int spb = 4, waste = (nstrips + 3) / 4 * 4 - nstrips;
     for (int c = 3; c >= 1; --c) {
         const int w = (nstrips + c - 1) / c * c - nstrips;
@@ -203,8 +227,25 @@ inline int launch_sobel_march(const View& s, const View& d, hipStream_t st) {
     while (nchunks * ((nstrips + spb - 1) / spb) * s.n < 1024 && (s.h + nchunks - 1) / nchunks > 16) nchunks *= 2;
     const int rpw = (int)((s.h + nchunks - 1) / nchunks);
     nchunks = (s.h + rpw - 1) / rpw;
-    dim3 grid((unsigned)((nstrips + spb - 1) / spb), (unsigned)nchunks, (unsigned)s.n);
-    hipLaunchKernelGGL((sobel_march_kernel<CIN, VARIANT, J>), grid, dim3(64 * spb), spb * sobel_wave_lds(CIN, J), st, s, d, rpw);
+    P.nstrips = nstrips; P.spb = spb; P.rpw = rpw; P.nchunks = (int)nchunks;
+    P.grid = dim3((unsigned)((nstrips + spb - 1) / spb), (unsigned)nchunks, (unsigned)s.n);
+    P.block = dim3(64 * spb);
+    P.lds = (size_t)spb * sobel_wave_lds(cin, SOBEL_MARCH_J);
+    return P;
+}
+
+// frames [f0, f0 + n) of a view
+inline View sobel_frames(const View& v, int f0, int n) {
+    View o = v;
+    o.p = v.p + (int64_t)f0 * v.fs;
+    o.n = n;
+    return o;
+}
+
+template <int CIN, int VARIANT>
+inline int launch_sobel_march(const View& s, const View& d, const SobelPlan& P, hipStream_t st) {
+    constexpr int J = SOBEL_MARCH_J;
+    hipLaunchKernelGGL((sobel_march_kernel<CIN, VARIANT, J>), P.grid, P.block, P.lds, st, s, d, P.rpw);   // 64 * spb threads, spb * sobel_wave_lds(CIN, J) bytes
     return launch_status();
 }
 

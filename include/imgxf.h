@@ -122,6 +122,17 @@ int imgxf_rgb_sobel_mag_u8(const imgxf_view* src, const imgxf_view* dst, void* s
 /* Same fusion for every variant of imgxf_sobel_u8: RGB in, Pillow L on the fly, one u8 plane out
  * (apply_background_change's edge image without materialising L, transformation.py:336-339). */
 int imgxf_rgb_sobel_u8(const imgxf_view* src, const imgxf_view* dst, int variant, void* stream);
+/* HOST only, no device needed: what imgxf_sobel_u8 (src c == 1) or imgxf_rgb_sobel_u8 (src c == 3) launches
+ * for these views — addresses, strides and IMGXF_NO_MARCH read as the entry points read them, the same view
+ * checks and error codes.  A batch above 65535 frames runs in several launches; the record is the first one's.
+ * out[IMGXF_SOBEL_PLAN_INTS] (all 0 for an empty view):
+ *   [0] 1 = marching kernel, 0 = tiled kernel        [1] 1024-pixel strips per row     (marching only)
+ *   [2] strips per workgroup (marching only)          [3] rows per wave and chunk       (marching only)
+ *   [4] row chunks (marching only)                    [5] row chunks before the split that fills the chip (marching only)
+ *   [6] [7] [8] grid x, y, z                          [9] threads per workgroup
+ *   [10] dynamic LDS bytes                            [11] launches */
+enum { IMGXF_SOBEL_PLAN_INTS = 12 };
+int imgxf_sobel_plan_host(const imgxf_view* src, const imgxf_view* dst, int* out);
 
 /* ---- a2/a2'/shear: Image.transform(size, AFFINE, m, resample, fillcolor) -------------
  * transformation.py:200 (rotate -> NEAREST), :217-224 (shear -> BICUBIC); BILINEAR is

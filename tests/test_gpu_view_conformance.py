@@ -34,6 +34,11 @@ Which kernel each layout reaches (dispatch conditions of the .hip files):
                  box_pass_kernel; conv2d_kernel (conv2d_dense on every layout, conv2d_rank1 with c = 2):
                  128-byte x 16-row tiles, frame from blockIdx.z, every access through row(f, y) - one kernel
                  whatever the alignment.
+                 sobel_x / _y / _mag (imgxf_sobel_u8) and rgb_sobel_x / _y / _mag (imgxf_rgb_sobel_u8): sobel_march_kernel
+                 (sobel_march.inc) for w % 16 == 0, w > 1024, h >= 2 and every view 16-aligned (dense, single and
+                 every_other at w = 1040, where h = 7, 37 and 2), else sobel_kernel<FROM_RGB>: 64 x 16 tiles, every access through
+                 row(f, y) (every other width, h = 1, window, fs8 with its frame stride of 8 mod 16, guarded
+                 destinations).  tests/test_gpu_sobel.py holds the marching kernel's own geometry matrix.
   sepconv*.hip   conv2d_rank1 (imgxf_conv2d_u8 hands the outer product over: asserted with the library's
                  host function) and sepconv, radius <= 2 so that no matrix-core kernel is in reach:
                  sepconv_march_kernel for REFLECT_101 rows above 1024 bytes that are a multiple of 16 with
@@ -412,6 +417,20 @@ def _ops():
         kx, ky = rank1_vectors(rng)
         return ops.sepconv(P(a), kx.tolist(), ky.tolist()), filtered(a, np.outer(ky, kx))
 
+    sobel_refs = (lambda g: O.sobel_scipy(g, -1), lambda g: O.sobel_scipy(g, 0), O.sobel_magnitude)
+
+    def add_sobel(name, variant):
+        @add("sobel_" + name, (1,))
+        def _(P, a, rng):
+            return ops.sobel(P(a), variant), per_frame(lambda x: sobel_refs[variant](x[..., 0]), a)
+
+        @add("rgb_sobel_" + name, (3,))
+        def _(P, a, rng):
+            return ops.rgb_sobel(P(a), variant), per_frame(lambda x: sobel_refs[variant](O.rgb2l(x)), a)
+
+    for variant, name in enumerate(("x", "y", "mag")):
+        add_sobel(name, variant)
+
     @add("box_blur", (1, 2, 3, 4))
     def _(P, a, rng):
         r = float(rng.choice([0.0, 1.0, 2.5, 6.0]))
@@ -495,7 +514,8 @@ OP_NAMES = ["scale_abs", "blend_image_image", "blend_colour_image", "blend_image
             "add_noise_f64", "shot_noise_finish", "impulse_noise", "permute_channels", "composite", "composite_const",
             "rgb2l", "enhance_color", "enhance_contrast", "lut_256", "lut_per_channel", "posterize", "solarize",
             "equalize", "channel_histogram", "rgb2yuv", "yuv2rgb", "equalize_hist_cv", "percentile_mask",
-            "dilate_cross", "filter3x3", "conv2d_dense", "conv2d_rank1", "sepconv", "box_blur", "gaussian_blur_pil", "enhance_sharpness", "flip", "rot90", "crop",
+            "dilate_cross", "filter3x3", "conv2d_dense", "conv2d_rank1", "sepconv", "sobel_x", "rgb_sobel_x", "sobel_y", "rgb_sobel_y",
+            "sobel_mag", "rgb_sobel_mag", "box_blur", "gaussian_blur_pil", "enhance_sharpness", "flip", "rot90", "crop",
             "copy_rect", "translate", "new"]
 
 
@@ -527,7 +547,7 @@ def _seed(*parts):
 # ops that also take a 2-D [H,W] frame
 PLANE_OPS = {"scale_abs", "blend_image_image", "brightness", "enhance_contrast", "lut_256", "posterize", "solarize",
              "equalize", "channel_histogram", "percentile_mask", "dilate_cross", "filter3x3", "conv2d_dense",
-             "conv2d_rank1", "sepconv", "box_blur",
+             "conv2d_rank1", "sepconv", "sobel_x", "sobel_y", "sobel_mag", "box_blur",
              "gaussian_blur_pil", "enhance_sharpness", "flip", "rot90", "crop", "copy_rect", "translate", "new"}
 # ops whose destination is not a single fresh image of the wrapper (histogram tensor, an
 # intermediate image, a caller-given destination)
@@ -551,7 +571,9 @@ def test_op_matches_oracle_in_layout(device, name, layout):
 
 REFUSED = [("rgb2l", 1), ("rgb2l", 2), ("enhance_color", 1), ("enhance_color", 2), ("enhance_color", 4),
            ("enhance_contrast", 2), ("enhance_contrast", 4), ("rgb2yuv", 1), ("rgb2yuv", 2), ("rgb2yuv", 4),
-           ("yuv2rgb", 1), ("yuv2rgb", 4), ("percentile_mask", 3), ("dilate_cross", 3)]
+           ("yuv2rgb", 1), ("yuv2rgb", 4), ("percentile_mask", 3), ("dilate_cross", 3),
+           ("sobel_x", 3), ("sobel_y", 3), ("sobel_mag", 3), ("rgb_sobel_x", 1), ("rgb_sobel_x", 4), ("rgb_sobel_y", 1),
+           ("rgb_sobel_y", 4), ("rgb_sobel_mag", 1), ("rgb_sobel_mag", 4)]
 
 
 @pytest.mark.parametrize("name,c", REFUSED)
@@ -561,7 +583,10 @@ def test_refused_channel_count_raises(device, name, c):
     t = torch.zeros((3, 7, 17, c), dtype=torch.uint8, device=device)
     fn = {"rgb2l": ops.rgb2l, "enhance_color": lambda x: ops.enhance_color(x, 1.5),
           "enhance_contrast": lambda x: ops.enhance_contrast(x, 1.5), "rgb2yuv": ops.rgb2yuv, "yuv2rgb": ops.yuv2rgb,
-          "percentile_mask": lambda x: ops.percentile_mask(x, 70.0), "dilate_cross": lambda x: ops.dilate_cross(x, 3)}[name]
+          "percentile_mask": lambda x: ops.percentile_mask(x, 70.0), "dilate_cross": lambda x: ops.dilate_cross(x, 3),
+          "sobel_x": lambda x: ops.sobel(x, 0), "sobel_y": lambda x: ops.sobel(x, 1), "sobel_mag": lambda x: ops.sobel(x, 2),
+          "rgb_sobel_x": lambda x: ops.rgb_sobel(x, 0), "rgb_sobel_y": lambda x: ops.rgb_sobel(x, 1),
+          "rgb_sobel_mag": lambda x: ops.rgb_sobel(x, 2)}[name]
     with pytest.raises(ValueError):
         fn(t)
     torch.cuda.synchronize()
