@@ -161,6 +161,10 @@ SIGNATURES = {
                                               C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_list_ex_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p],
+    "imgxf_jpeg_encode_list_prog_layout_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "imgxf_jpeg_encode_list_prog_u8": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_jpeg_workspace_bytes_prog": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_prog_u8": [_VP, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p],
@@ -254,6 +258,14 @@ JPEG_LIST_OPT_AREAS = 3
 class JpegListExHeader(C.Structure):
     """struct imgxf_jpeg_list_ex_header (include/imgxf.h)."""
     _fields_ = [("list", JpegListHeader), ("params", JpegEncParams), ("opt_off", C.c_uint64 * JPEG_LIST_OPT_AREAS)]
+
+
+JPEG_LIST_PROG_AREAS = 4
+
+
+class JpegListProgHeader(C.Structure):
+    """struct imgxf_jpeg_list_prog_header (include/imgxf.h)."""
+    _fields_ = [("ex", JpegListExHeader), ("prog_off", C.c_uint64 * JPEG_LIST_PROG_AREAS)]
 
 
 class JpegRoundtripListHeader(C.Structure):

@@ -65,6 +65,7 @@ struct JpegList {
     const imgxf_jpeg_list_unit* units;       // the stage's table (imgxf_jpeg_list_header::units_off)
     int which;                               // the scan kernels: 0 the frame's blocks, 1 its chunks
     int sof;                                 // the stuffing kernel: where the header's SOF height / width bytes are
+    int n;                                   // the progressive scans' stuffing kernel: frames in the list (pos[scan][n])
 };
 template <class W>
 __device__ __forceinline__ const imgxf_jpeg_list_frame* jpeg_where(const W& wh, int& f, int& bx) {
@@ -957,7 +958,8 @@ __device__ __forceinline__ int write_dht_segment(u8* __restrict__ o, const JpegD
 // starts (kept on the device: no host round trip; the first scan starts at hd.len); the sequential optimize file is the
 // one-scan case (si = 0, last, pos unused).  Sentinels of pos[] / sizes[]: JSIZE_HUFF_OVERFLOW (an optimal code over 32
 // bits) and 0xFFFFFFFF (capacity); once a scan of frame f fails, the later scans carry the sentinel forward and write nothing.
-// A list's frame (JpegList): its own slot of `out`, its own height and width in the prefix's SOF segment.
+// A list's frame (JpegList): its own slot of `out` (out_cap bounds every scan: a frame that fails writes nothing past it in
+// that scan or a later one), its own height and width in the prefix's SOF segment, pos[scan][frame] over the list's wh.n frames.
 template <class W>
 __global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restrict__ stream, int64_t fs_words,
                                                               const u32* __restrict__ total_bits, const u32* __restrict__ cnt,
@@ -967,12 +969,13 @@ __global__ __launch_bounds__(256) void jpeg_stuff_scan_kernel(const u32* __restr
                                                               JpScanHdr sh, W wh) {
     __shared__ __attribute__((aligned(4))) u8 lb[256 * 2 * JCHUNK + 8];
     int f = blockIdx.y, bx = blockIdx.x, gdim = gridDim.x;
-    const int n = gridDim.y;
+    int n = gridDim.y;
     int64_t stream_o, cnt_o, out_o;
     const imgxf_jpeg_list_frame* fr;
     chunks_where(wh, f, bx, gdim, fs_words, stream_o, cnt_o, nchunks, cnt_fs, fr);
     u32 dims = 0;
-    if constexpr (W::LIST) {                                    // (a list's file is one scan: si == 0, last, pos unused)
+    if constexpr (W::LIST) {                                    // (a sequential list's file is one scan: si == 0, last, pos unused)
+        n = wh.n;
         out_o = fr->out_off;
         out_fs = fr->out_cap;
         dims = ((u32)fr->h << 16) | (u32)fr->w;
@@ -1321,7 +1324,8 @@ static int jpeg_encode_seq(const imgxf_view* src, const imgxf_jpeg_enc_params* p
 constexpr int JLIST_MAX_FRAMES = 1 << 20;
 constexpr int JLIST_MAX_FRAMES_OPT = 65535;  // with the frames' own tables: the table stage is one workgroup per (table, frame), frames on grid y
 static_assert(sizeof(imgxf_jpeg_list_header) == 136 && sizeof(imgxf_jpeg_list_frame) == 128 && sizeof(imgxf_jpeg_list_unit) == 8 &&
-              sizeof(imgxf_jpeg_list_ex_header) == 176, "include/imgxf.h documents these records");
+              sizeof(imgxf_jpeg_list_ex_header) == 176 && sizeof(imgxf_jpeg_list_prog_header) == 208,
+              "include/imgxf.h documents these records");
 
 // (stage 0 is the layout's transform kernel: 16×256-pixel strips at 4:2:0, one MCU row of JXP pixels in the other layouts)
 static inline int list_stage_units(const imgxf_jpeg_list_frame& f, int stage, int lay = JL420) {
@@ -1340,15 +1344,19 @@ static inline int list_stage_units(const imgxf_jpeg_list_frame& f, int stage, in
 // ex == nullptr: the default file's block (imgxf_jpeg_list_header, 4:2:0, the call's tables).  Else the block of the class
 // *ex (checked by the caller) behind an imgxf_jpeg_list_ex_header: the layout's MCUs, blocks and transform strips and, with
 // optimize, three more areas indexed by the frame — symbol counts [n][4][256], code words [n], DHT records [n][4].
+// prog (with ex, optimize set): the progressive class's block behind an imgxf_jpeg_list_prog_header — the same records
+// and unit tables, the own-table areas, and four more: flags, correction-bit counts and run lengths per block slot (at the
+// frame's blk_off, as lens), then pos[JP_MAXSCANS + 1][n] and the BE totals [n].
 template <typename Get>
-static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_jpeg_list_ex_header* out_hd,
-                           const imgxf_jpeg_enc_params* ex = nullptr) {
+static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_jpeg_list_prog_header* out_hd,
+                           const imgxf_jpeg_enc_params* ex = nullptr, bool prog = false) {
     const int lay = ex ? enc_layout(ex) : JL420;
     const bool opt = ex && ex->optimize != 0;
-    const size_t hd_bytes = ex ? sizeof(imgxf_jpeg_list_ex_header) : sizeof(imgxf_jpeg_list_header);
+    const size_t hd_bytes = prog ? sizeof(imgxf_jpeg_list_prog_header) : ex ? sizeof(imgxf_jpeg_list_ex_header) : sizeof(imgxf_jpeg_list_header);
     if (n < 0 || n > (opt ? JLIST_MAX_FRAMES_OPT : JLIST_MAX_FRAMES)) return IMGXF_ERR_SHAPE;
-    imgxf_jpeg_list_ex_header xhd;
-    memset(&xhd, 0, sizeof(xhd));
+    imgxf_jpeg_list_prog_header phd;
+    memset(&phd, 0, sizeof(phd));
+    imgxf_jpeg_list_ex_header& xhd = phd.ex;
     imgxf_jpeg_list_header& hd = xhd.list;
     hd.n_frames = n;
     hd.frames_off = (int32_t)hd_bytes;
@@ -1404,6 +1412,13 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
             if (opt) o += al256((size_t)n * own[a]);
         }
     }
+    if (prog) {
+        const size_t more[IMGXF_JPEG_LIST_PROG_AREAS] = {area[3], area[3], area[3], (size_t)(JP_MAXSCANS + 2) * n * 4};
+        for (int a = 0; a < IMGXF_JPEG_LIST_PROG_AREAS; ++a) {
+            phd.prog_off[a] = o;
+            o += al256(more[a]);
+        }
+    }
     hd.workspace_bytes = o;
     hd.out_bytes = out;
     size_t pos = hd_bytes + (size_t)n * sizeof(imgxf_jpeg_list_frame);
@@ -1415,10 +1430,11 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
     }
     if (pos > 0x7fffffffu) return IMGXF_ERR_ARG;
     hd.total_bytes = (int32_t)pos;
-    *out_hd = xhd;
+    *out_hd = phd;
     if (!block) return IMGXF_OK;
     if (block_cap < pos) return IMGXF_ERR_WORKSPACE;          // (*out_hd already states the size needed)
-    memcpy(block, &xhd, hd_bytes);                            // (the default block: the list header alone, which comes first)
+    memcpy(block, &phd, hd_bytes);                            // (the list header comes first in all three; then the class, then
+                                                              // the progressive areas)
     if (n) memcpy(block + hd.frames_off, fr.data(), (size_t)n * sizeof(imgxf_jpeg_list_frame));
     for (int s = 0; s < IMGXF_JPEG_LIST_STAGES; ++s) {
         imgxf_jpeg_list_unit* u = (imgxf_jpeg_list_unit*)(block + hd.units_off[s]);
@@ -1437,12 +1453,13 @@ static int jpeg_list_build(int n, Get&& get, u8* block, size_t block_cap, imgxf_
     return IMGXF_OK;
 }
 
-// where the SOF0 segment of a header (SOI, marker segments ...) states height and width; -1: none
-static int find_sof0(const uint8_t* h, int len) {
+// where the SOF0 segment (sof == 0xc2: the SOF2 segment of a progressive file) of a header (SOI, marker segments ...)
+// states height and width; -1: none
+static int find_sof0(const uint8_t* h, int len, int sof = 0xc0) {
     int pos = 2;
     while (pos + 4 <= len && h[pos] == 0xff) {
         const int m = h[pos + 1], seg = (h[pos + 2] << 8) | h[pos + 3];
-        if (m == 0xc0) return pos + 9 <= len ? pos + 5 : -1;
+        if (m == sof) return pos + 9 <= len ? pos + 5 : -1;
         if (m == 0xda) break;
         pos += 2 + seg;
     }
@@ -1462,23 +1479,23 @@ static int list_class(const imgxf_jpeg_enc_params* p) {
     return lay;
 }
 
-// the host half of both list writers (ex == nullptr: the default file's block)
+// the host half of the list writers (ex == nullptr: the default file's block; prog: the progressive class's)
 static int jpeg_list_layout_host(const imgxf_jpeg_enc_params* ex, const int32_t* sizes, const uint64_t* capacities, int n, void* block,
-                                 size_t block_cap, size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes) {
+                                 size_t block_cap, size_t* block_bytes, size_t* workspace_bytes, size_t* out_bytes, bool prog = false) {
     if (!block_bytes || !workspace_bytes || !out_bytes || (n > 0 && (!sizes || !capacities))) return IMGXF_ERR_NULL;
-    imgxf_jpeg_list_ex_header hd;
+    imgxf_jpeg_list_prog_header hd;
     // the sizes first, so that a block that is too small still learns them
     const auto get = [&](int i, int& h, int& w, uint64_t& cap) { h = sizes[2 * i]; w = sizes[2 * i + 1]; cap = capacities[i]; };
     int rc;
     try {
-        rc = jpeg_list_build(n, get, (u8*)block, block_cap, &hd, ex);
+        rc = jpeg_list_build(n, get, (u8*)block, block_cap, &hd, ex, prog);
     } catch (const std::bad_alloc&) {
         return IMGXF_ERR_WORKSPACE;
     }
     if (rc != IMGXF_OK && rc != IMGXF_ERR_WORKSPACE) return rc;
-    *block_bytes = (size_t)hd.list.total_bytes;                  // (a block that is too small still learns the sizes)
-    *workspace_bytes = (size_t)hd.list.workspace_bytes;
-    *out_bytes = (size_t)hd.list.out_bytes;
+    *block_bytes = (size_t)hd.ex.list.total_bytes;               // (a block that is too small still learns the sizes)
+    *workspace_bytes = (size_t)hd.ex.list.workspace_bytes;
+    *out_bytes = (size_t)hd.ex.list.out_bytes;
     return rc;
 }
 
@@ -1487,14 +1504,15 @@ static int jpeg_list_layout_host(const imgxf_jpeg_enc_params* ex, const int32_t*
 // pointer is looked at; the launches then depend on (layout, optimize) alone.
 static int jpeg_list_encode(const void* block_host, const void* block_dev, const imgxf_jpeg_enc_params* ex, const imgxf_jpeg_tables* tables,
                             const uint8_t* header, int header_bytes, uint8_t* out, size_t out_bytes, uint32_t* sizes, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+                            size_t workspace_bytes, void* stream, bool prog = false) {
     const u8* hb = (const u8*)block_host;
-    const size_t hd_bytes = ex ? sizeof(imgxf_jpeg_list_ex_header) : sizeof(imgxf_jpeg_list_header);
+    const size_t hd_bytes = prog ? sizeof(imgxf_jpeg_list_prog_header) : ex ? sizeof(imgxf_jpeg_list_ex_header) : sizeof(imgxf_jpeg_list_header);
     const int lay = ex ? enc_layout(ex) : JL420, ncomp = ex ? ex->ncomp : 3;
     const bool opt = ex && ex->optimize != 0;
-    imgxf_jpeg_list_ex_header xhd;
-    memset(&xhd, 0, sizeof(xhd));
-    memcpy(&xhd, hb, hd_bytes);
+    imgxf_jpeg_list_prog_header phd;
+    memset(&phd, 0, sizeof(phd));
+    memcpy(&phd, hb, hd_bytes);
+    const imgxf_jpeg_list_ex_header& xhd = phd.ex;
     const imgxf_jpeg_list_header& hd = xhd.list;
     const int n = hd.n_frames;
     if (n < 0 || n > (opt ? JLIST_MAX_FRAMES_OPT : JLIST_MAX_FRAMES)) return IMGXF_ERR_SHAPE;
@@ -1513,31 +1531,32 @@ static int jpeg_list_encode(const void* block_host, const void* block_dev, const
         if (f.h < 1 || f.w < 1 || f.h > 32767 || f.w > 32767 || f.row_stride < (int64_t)f.w * ncomp) return IMGXF_ERR_SHAPE;
         if (f.out_cap < (int64_t)header_bytes + 2) return IMGXF_ERR_ARG;
     }
-    imgxf_jpeg_list_ex_header rhd;
+    imgxf_jpeg_list_prog_header rhd;
     const auto get = [&](int i, int& h, int& w, uint64_t& cap) { h = frames[i].h; w = frames[i].w; cap = (uint64_t)frames[i].out_cap; };
     std::vector<u8> ref;
     try {
         ref.resize((size_t)hd.total_bytes);
-        const int rc = jpeg_list_build(n, get, ref.data(), ref.size(), &rhd, ex);   // one build: the block limit is IMGXF_ERR_SHAPE,
+        const int rc = jpeg_list_build(n, get, ref.data(), ref.size(), &rhd, ex, prog);   // one build: the block limit is IMGXF_ERR_SHAPE,
         if (rc == IMGXF_ERR_WORKSPACE) return IMGXF_ERR_ARG;                      // a block of another size is not this layout
         IMGXF_CHECK(rc);
     } catch (const std::bad_alloc&) {
         return IMGXF_ERR_WORKSPACE;
     }
-    if (memcmp(&rhd, &xhd, hd_bytes) != 0) return IMGXF_ERR_ARG;
+    if (memcmp(&rhd, &phd, hd_bytes) != 0) return IMGXF_ERR_ARG;
     const imgxf_jpeg_list_frame* rf = (const imgxf_jpeg_list_frame*)(ref.data() + hd.frames_off);
     constexpr size_t given = offsetof(imgxf_jpeg_list_frame, h);            // data, row_stride: the caller's
     for (int i = 0; i < n; ++i)
         if (memcmp((const u8*)&rf[i] + given, (const u8*)&frames[i] + given, sizeof(imgxf_jpeg_list_frame) - given) != 0) return IMGXF_ERR_ARG;
     const size_t units0 = (size_t)hd.units_off[0];
     if (memcmp(ref.data() + units0, hb + units0, (size_t)hd.total_bytes - units0) != 0) return IMGXF_ERR_ARG;
+    if (prog && find_sof0(header, header_bytes, 0xc2) < 0) return IMGXF_ERR_ARG;   // (the progressive call refuses its header here too)
     if (!block_dev || !out || !sizes) return IMGXF_ERR_NULL;
     if (((uintptr_t)block_dev) & 7) return IMGXF_ERR_ARG;
     if (!workspace || workspace_bytes < hd.workspace_bytes || (((uintptr_t)workspace) & 15)) return IMGXF_ERR_WORKSPACE;
     if (out_bytes < hd.out_bytes || (((uintptr_t)out) & 15)) return IMGXF_ERR_WORKSPACE;
     JpegJob J;
     IMGXF_CHECK(jpeg_prepare_tables(J, tables, ncomp, header, header_bytes));
-    const int sof = find_sof0(header, header_bytes);
+    const int sof = find_sof0(header, header_bytes, prog ? 0xc2 : 0xc0);
     if (sof < 0) return IMGXF_ERR_ARG;
 
     hipStream_t st = (hipStream_t)stream;
@@ -1556,7 +1575,7 @@ static int jpeg_list_encode(const void* block_host, const void* block_dev, const
     JpegHuff* fh = (JpegHuff*)(ws + xhd.opt_off[1]);
     JpegDht* dht = (JpegDht*)(ws + xhd.opt_off[2]);
     const auto where = [&](int stage, int which) {
-        return JpegList{(const imgxf_jpeg_list_frame*)(db + hd.frames_off), (const imgxf_jpeg_list_unit*)(db + hd.units_off[stage]), which, sof};
+        return JpegList{(const imgxf_jpeg_list_frame*)(db + hd.frames_off), (const imgxf_jpeg_list_unit*)(db + hd.units_off[stage]), which, sof, n};
     };
     const auto grid = [&](int stage) { return dim3((unsigned)hd.n_units[stage]); };
     const JpegGeom g0 = {0, 0, 0, 0, 0};                       // the uniform arguments: unused, the records state them
@@ -1571,6 +1590,20 @@ static int jpeg_list_encode(const void* block_host, const void* block_dev, const
         else
             hipLaunchKernelGGL((jpeg_transform_ex_kernel<L, JpegCoefSink, JpegList>), grid(0), dim3(JLay<L>::T), 0, st, View{}, sink, 0, 0, J.q,
                                where(0, 0));
+        if (prog) {                                            // the script's scans over the same unit tables
+            JpegProgList P;
+            P.n = n; P.ncomp = ncomp; P.sof = sof; P.hd = &hd; P.db = db; P.st = st; P.file_hd = J.hd;
+            P.coef = coef; P.dcs = dcs; P.lens = lens; P.part = part; P.tot_bits = tot_bits; P.tot_ff = tot_ff; P.ustream = ustream;
+            P.cnt = cnt; P.sym = sym; P.fh = fh; P.dht = dht; P.sizes = sizes; P.out = out;
+            P.flags = (u32*)(ws + phd.prog_off[0]);
+            P.nbe = (u32*)(ws + phd.prog_off[1]);
+            P.runlen = (u32*)(ws + phd.prog_off[2]);
+            P.pos = (u32*)(ws + phd.prog_off[3]);
+            P.tot_be = P.pos + (size_t)(JP_MAXSCANS + 1) * n;
+            return launch_prog(ncomp, g0, [&](auto k, const JpScan& sc, const JpScanHdr& sh, u32 unused, int si, bool last) {
+                return launch_prog_scan_list<L, decltype(k)::value>(P, sc, sh, unused, si, last);
+            });
+        }
         if (opt) {
             if (hipMemsetAsync(sym, 0, (size_t)n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
             hipLaunchKernelGGL((jpeg_gather_kernel<L, JpegList>), grid(1), dim3(256), 0, st, ccoef, z, cdcs, g0, sym, where(1, 0));
@@ -1726,8 +1759,37 @@ IMGXF_API int imgxf_jpeg_encode_prog_u8(const imgxf_view* src, const imgxf_jpeg_
                              stream));
     if (J.n == 0) return IMGXF_OK;
     return with_layout(J.lay, [&](auto l) -> int {
-        launch_transform<decltype(l)::value>(J);
-        IMGXF_CHECK(launch_prog<decltype(l)::value>(J));
+        constexpr int L = decltype(l)::value;
+        launch_transform<L>(J);
+        IMGXF_CHECK(launch_prog(J.ncomp, J.g, [&](auto k, const JpScan& sc, const JpScanHdr& sh, u32 unused, int si, bool last) {
+            return launch_prog_scan<L, decltype(k)::value>(J, sc, sh, unused, si, last);
+        }));
         return launch_status();
     });
+}
+
+// the progressive class of a list call: `optimize` is ignored (always the frames' own tables, stated as 1 in the block)
+static int list_prog_class(const imgxf_jpeg_enc_params* params, imgxf_jpeg_enc_params* p) {
+    *p = *params;
+    p->optimize = 1;
+    return list_class(p);
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_prog_layout_host(const imgxf_jpeg_enc_params* params, const int32_t* sizes, const uint64_t* capacities,
+                                                      int n, void* block, size_t block_cap, size_t* block_bytes, size_t* workspace_bytes,
+                                                      size_t* out_bytes) {
+    if (!params) return IMGXF_ERR_NULL;
+    imgxf_jpeg_enc_params p;
+    if (list_prog_class(params, &p) < 0) return IMGXF_ERR_ARG;
+    return jpeg_list_layout_host(&p, sizes, capacities, n, block, block_cap, block_bytes, workspace_bytes, out_bytes, true);
+}
+
+IMGXF_API int imgxf_jpeg_encode_list_prog_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_enc_params* params,
+                                             const imgxf_jpeg_tables* tables, const uint8_t* header, int header_bytes, uint8_t* out,
+                                             size_t out_bytes, uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!block_host || !params || !tables || !header) return IMGXF_ERR_NULL;
+    imgxf_jpeg_enc_params p;
+    if (list_prog_class(params, &p) < 0) return IMGXF_ERR_ARG;
+    return jpeg_list_encode(block_host, block_dev, &p, tables, header, header_bytes, out, out_bytes, sizes, workspace, workspace_bytes, stream,
+                            true);
 }

@@ -23,6 +23,19 @@
 // A run's bits are charged to the blocks that make it up: its first block carries the EOBRUN symbol (after its own
 // symbols, when it is an F block whose band ends in zeros), every block then its own correction bits — exactly the order
 // in which emit_eobrun writes the symbol and then BE, since blocks between two flushes write nothing else.
+//
+// The four kernels take the place type W last, as every stage of the writer: JpegUniform is the batch above, JpegList a
+// list of frames of different sizes (imgxf_jpeg_encode_list_prog_u8).  A list reuses the five unit tables of the
+// sequential list writer: every scan runs over the frame's nblk block slots, and the scan's own extent (JpScan::nb, cw) is
+// derived per frame from the record (jp_scan_extent).  Slots past nb are zero-length entries: the count kernel clears
+// their flags, correction-bit counts and run lengths, the length kernel writes 0 bits for them, the emit body puts
+// nothing, so no stage reads what an earlier scan left there, and a frame's flags are only ever indexed inside
+// [0, nb) of its own row.  prog_script, the SOS / DHT header and the scan-kind dispatch (launch_prog) exist once; the
+// uniform call and the list call hand it their own launch_prog_scan / launch_prog_scan_list.
+// Launches of a list call (memsets included), whatever the frames: transform 1; a DC first scan 14 (memset, count, tables,
+// lens, 3 scan_rows_list, zero, emit, ffcount, 3 scan_rows_list, stuff), an AC first scan 15 (+ runs), an AC refinement
+// 18 (+ 3 scan_rows_list of the correction bits), a DC refinement 11 (no counts, no tables) — colour (10 scans: 1 DC first,
+// 4 AC first, 4 AC refinements, 1 DC refinement) 158, grayscale (6 scans: 1, 2, 2, 1) 92.
 
 enum { JP_DCF = 0, JP_DCR = 1, JP_ACF = 2, JP_ACR = 3 };
 constexpr u32 JP_MAX_EOBRUN = 0x7FFF;
@@ -36,6 +49,44 @@ struct JpScan {
     int ss, se, ah, al;
     int slot;                                // AC scans: the table's slot (2·table + 1)
 };
+
+// The scan's own extent in a frame of geometry g: all blocks in MCU order for a DC scan, the component's own blocks for
+// an AC scan (luma bw·bh — a grayscale frame's nblk —, chroma mw·mh).  The uniform call states it once (host); a list
+// kernel derives it from the frame's record.
+__host__ __device__ inline void jp_scan_extent(const JpegGeom& g, JpScan& sc) {
+    sc.nb = sc.comp < 0 ? g.nblk : sc.comp == 0 ? g.bw * g.bh : g.mw * g.mh;
+    sc.cw = sc.comp == 0 ? g.bw : g.mw;
+}
+
+// Where a scan kernel's workgroup works.  Uniform: frame blockIdx.y, item blockIdx.x, the areas at the strides the
+// arguments state, the scan's bit lengths packed nb per frame.  List: the unit's frame and item, geometry and offsets from
+// the record, the extent derived from it, and one bit length per block slot of the frame (nblk of them, at blk_off).
+struct JpAt {
+    int f, bx;
+    int slots;                               // entries of the frame's row of bit lengths: sc.nb, or nblk in a list
+    int64_t coef_o, blk_o, lens_o;           // element offsets: coefficients; DC values, flags, nbe, runlen; bit lengths
+    const imgxf_jpeg_list_frame* fr;
+};
+template <class W>
+__device__ __forceinline__ JpAt jp_at(const W& wh, int64_t coef_fs, JpegGeom& g, JpScan& sc) {
+    JpAt a;
+    a.f = blockIdx.y;
+    a.bx = blockIdx.x;
+    a.fr = jpeg_where(wh, a.f, a.bx);
+    if constexpr (W::LIST) {
+        g = {a.fr->mw, a.fr->mh, a.fr->bw, a.fr->bh, a.fr->nblk};
+        jp_scan_extent(g, sc);
+        a.slots = g.nblk;
+        a.coef_o = a.fr->coef_off;
+        a.blk_o = a.lens_o = a.fr->blk_off;
+    } else {
+        a.slots = sc.nb;
+        a.coef_o = (int64_t)a.f * coef_fs;
+        a.blk_o = (int64_t)a.f * g.nblk;
+        a.lens_o = (int64_t)a.f * sc.nb;
+    }
+    return a;
+}
 
 // block b of a single-component scan (the component's own blocks in raster order) → its index in MCU order
 template <int L>
@@ -136,33 +187,39 @@ __device__ __forceinline__ int jp_dc(const int16_t* __restrict__ dd, const JpegG
     return (v >> sc.al) - (block_pred<L>(dd, g, mcu, mx, my, k) >> sc.al);
 }
 
-template <int L, int K>
+template <int L, int K, class W>
 __global__ __launch_bounds__(256) void jprog_count_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
                                                           JpegGeom g, JpScan sc, u32* __restrict__ counts, u32* __restrict__ flags,
-                                                          u32* __restrict__ nbe, u32* __restrict__ runlen, u32 unused_slots) {
+                                                          u32* __restrict__ nbe, u32* __restrict__ runlen, u32 unused_slots, W wh) {
     constexpr int NT = K == JP_DCF ? 2 : 1;
     __shared__ u32 hist[NT][256];
-    const int f = blockIdx.y, b = blockIdx.x * 256 + threadIdx.x;
+    const JpAt at = jp_at(wh, coef_fs, g, sc);
+    const int f = at.f, b = at.bx * 256 + threadIdx.x;
     for (int i = threadIdx.x; i < NT * 256; i += 256) (&hist[0][0])[i] = 0;
     u32* cf = counts + (int64_t)f * JSLOTS * 256;
-    if (blockIdx.x == 0 && threadIdx.x < JSLOTS && ((unused_slots >> threadIdx.x) & 1)) cf[threadIdx.x * 256] = 1;
+    if (at.bx == 0 && threadIdx.x < JSLOTS && ((unused_slots >> threadIdx.x) & 1)) cf[threadIdx.x * 256] = 1;
     __syncthreads();
     if (b < sc.nb) {
         if (K == JP_DCF) {
             int t;
-            const int diff = jp_dc<L>(dcs + (int64_t)f * g.nblk, g, sc, b, t);
+            const int diff = jp_dc<L>(dcs + at.blk_o, g, sc, b, t);
             atomicAdd(&hist[t][dc_category(diff)], 1u);
         } else {
             const int j = jp_block<L>(g, sc, b);
             unsigned long long tail;
             u32 ntail;
-            const u32 fl = jp_ac_walk<K == JP_ACR>((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63), sc.ss, sc.se,
+            const u32 fl = jp_ac_walk<K == JP_ACR>((const uint4*)(coef + at.coef_o) + (j >> 6) * 512 + (j & 63), sc.ss, sc.se,
                                                    sc.al, [&](u32 s) { atomicAdd(&hist[0][s], 1u); }, [](u32, u32) {}, tail, ntail);
-            const int64_t o = (int64_t)f * g.nblk + b;
+            const int64_t o = at.blk_o + b;
             flags[o] = fl;
             if (K == JP_ACR) nbe[o] = ntail;
             runlen[o] = 0;
         }
+    } else if (W::LIST && K != JP_DCF && b < at.slots) {       // a list's slots past the scan's own blocks: nothing of an
+        const int64_t o = at.blk_o + b;                        // earlier scan is left for the prefix sums or the runs
+        flags[o] = 0;
+        if (K == JP_ACR) nbe[o] = 0;
+        runlen[o] = 0;
     }
     __syncthreads();
     for (int i = threadIdx.x; i < NT * 256; i += 256) {
@@ -180,16 +237,20 @@ __global__ __launch_bounds__(256) void jprog_count_kernel(const int16_t* __restr
 // step, cutting as many runs per step as end in it (ballots), so a segment of B blocks costs ceil(B / 64) dependent load
 // rounds.  runlen[s] = the run's length at its first block (0 elsewhere, from jprog_count_kernel); the EOBRUN symbols go
 // to the scan's counts (LDS first).
+// (a list: fl, pp and rl are the frame's own rows and every index into them lies in [0, nb) of the frame's own extent —
+// fl[b - 1] is read for b > 0, fl[x + 1] and pp[x + 1] for x + 1 < nb — so no neighbouring frame's flags are ever seen)
+template <class W>
 __global__ __launch_bounds__(256) void jprog_runs_kernel(const u32* __restrict__ flags, const u32* __restrict__ pre, const u32* __restrict__ pre_tot,
-                                                         u32* __restrict__ runlen, u32* __restrict__ counts, int nb, int64_t fs, int slot) {
+                                                         u32* __restrict__ runlen, u32* __restrict__ counts, JpegGeom g, JpScan sc, W wh) {
     __shared__ u32 eh[16];
-    const int f = blockIdx.y, lane = threadIdx.x & 63, w0 = blockIdx.x * 256 + (threadIdx.x & ~63);
+    const JpAt at = jp_at(wh, 0, g, sc);
+    const int f = at.f, nb = sc.nb, slot = sc.slot, lane = threadIdx.x & 63, w0 = at.bx * 256 + (threadIdx.x & ~63);
     if (threadIdx.x < 16) eh[threadIdx.x] = 0;
     __syncthreads();
-    const u32* fl = flags + (int64_t)f * fs;
-    const u32* pp = pre ? pre + (int64_t)f * fs : nullptr;
+    const u32* fl = flags + at.blk_o;
+    const u32* pp = pre ? pre + at.blk_o : nullptr;
     const u32 ptot = pre ? pre_tot[f] : 0u;
-    u32* rl = runlen + (int64_t)f * fs;
+    u32* rl = runlen + at.blk_o;
     const int b = w0 + lane;
     bool start = false;
     if (b < nb) {
@@ -238,16 +299,17 @@ __global__ __launch_bounds__(256) void jprog_runs_kernel(const u32* __restrict__
 
 // Walks block b of the scan under the frame's tables (LDS): put(code, len) for every field in stream order, run symbol
 // and BE bits included.  Used by the length pass (counting) and the emit pass (writing).
+// (coef, dcs, runlen: the frame's own)
 template <int L, int K, typename P>
-__device__ __forceinline__ void jp_block_codes(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
-                                               const u32* __restrict__ runlen, const JpegGeom& g, const JpScan& sc, int f, int b,
+__device__ __forceinline__ void jp_block_codes(const int16_t* __restrict__ coef, const int16_t* __restrict__ dcs,
+                                               const u32* __restrict__ runlen, const JpegGeom& g, const JpScan& sc, int b,
                                                const u32 (*sdc)[16], const u32* sac, P&& put) {
     if (K == JP_DCR) {
         int t;
-        put((u32)jp_dc<L>(dcs + (int64_t)f * g.nblk, g, sc, b, t), 1u);
+        put((u32)jp_dc<L>(dcs, g, sc, b, t), 1u);
     } else if (K == JP_DCF) {
         int t;
-        const int diff = jp_dc<L>(dcs + (int64_t)f * g.nblk, g, sc, b, t);
+        const int diff = jp_dc<L>(dcs, g, sc, b, t);
         const u32 cat = dc_category(diff), e = sdc[t][cat];
         put(e & 0xffff, e >> 16);
         if (cat) put((u32)(diff + (diff >> 31)) & ((1u << cat) - 1), cat);
@@ -255,11 +317,11 @@ __device__ __forceinline__ void jp_block_codes(const int16_t* __restrict__ coef,
         const int j = jp_block<L>(g, sc, b);
         unsigned long long tail;
         u32 ntail;
-        jp_ac_walk<K == JP_ACR>((const uint4*)(coef + (int64_t)f * coef_fs) + (j >> 6) * 512 + (j & 63), sc.ss, sc.se, sc.al,
+        jp_ac_walk<K == JP_ACR>((const uint4*)coef + (j >> 6) * 512 + (j & 63), sc.ss, sc.se, sc.al,
                                 [&](u32 s) { put(sac[s] & 0xffff, sac[s] >> 16); },
                                 [&](u32 v, u32 n) { put(n < 32 ? v & ((1u << n) - 1) : v, n); }, tail, ntail);
         if (K == JP_ACF) ntail = 0;
-        const u32 len = runlen[(int64_t)f * g.nblk + b];
+        const u32 len = runlen[b];
         if (len) {                                             // emit_eobrun: symbol 16·n, n = floor(log2 len), n raw bits
             const u32 n = 31 - (u32)__clz((int)len), e = sac[n << 4];
             put(e & 0xffff, e >> 16);
@@ -279,34 +341,42 @@ __device__ __forceinline__ void jp_load_tables(u32 (*sdc)[16], u32* sac, const J
     }
 }
 
-template <int L, int K>
+template <int L, int K, class W>
 __global__ __launch_bounds__(256) void jprog_lens_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
                                                          const u32* __restrict__ runlen, u32* __restrict__ lens, JpegGeom g, JpScan sc,
-                                                         const JpegHuff* __restrict__ fh) {
+                                                         const JpegHuff* __restrict__ fh, W wh) {
     __shared__ u32 sdc[2][16];
     __shared__ u32 sac[256];
-    const int f = blockIdx.y, b = blockIdx.x * 256 + threadIdx.x;
-    jp_load_tables<L, K>(sdc, sac, fh, f, sc);
+    const JpAt at = jp_at(wh, coef_fs, g, sc);
+    const int b = at.bx * 256 + threadIdx.x;
+    jp_load_tables<L, K>(sdc, sac, fh, at.f, sc);
     __syncthreads();
-    if (b >= sc.nb) return;
+    if (b >= at.slots) return;
     u32 n = 0;
-    jp_block_codes<L, K>(coef, coef_fs, dcs, runlen, g, sc, f, b, sdc, sac, [&](u32, u32 len) { n += len; });
-    lens[(int64_t)f * sc.nb + b] = n;                        // (offsets: frame stride sc.nb, as jpeg_zero_kernel reads them)
-}
+    if (!W::LIST || b < sc.nb)                               // (a list's slots past the scan's own blocks: 0 bits)
+        jp_block_codes<L, K>(coef + at.coef_o, dcs + at.blk_o, runlen + at.blk_o, g, sc, b, sdc, sac, [&](u32, u32 len) { n += len; });
+    lens[at.lens_o + b] = n;                                 // (offsets: frame stride sc.nb, as jpeg_zero_kernel reads them; a
+}                                                            // list: the frame's nblk slots at blk_off)
 
-// span_write around the scan's fields (offsets: sc.nb per frame)
-template <int L, int K>
+// span_write around the scan's fields (offsets: sc.nb per frame; a list: nblk per frame, the entries past nb put nothing)
+template <int L, int K, class W>
 __global__ __launch_bounds__(256) void jprog_emit_kernel(const int16_t* __restrict__ coef, int64_t coef_fs, const int16_t* __restrict__ dcs,
                                                          const u32* __restrict__ runlen, const u32* __restrict__ offs, u32* __restrict__ stream,
                                                          int64_t stream_fs_words, const u32* __restrict__ total_bits, JpegGeom g, JpScan sc,
-                                                         const JpegHuff* __restrict__ fh) {
+                                                         const JpegHuff* __restrict__ fh, W wh) {
     __shared__ u32 sdc[2][16];
     __shared__ u32 sac[256];
     __shared__ u32 lbuf[JLW];
-    const int f = blockIdx.y;
-    jp_load_tables<L, K>(sdc, sac, fh, f, sc);
-    span_write(lbuf, blockIdx.x, offs + (int64_t)f * sc.nb, sc.nb, total_bits[f], stream + (int64_t)f * stream_fs_words, stream_fs_words,
-               [&](int b, auto&& put) { jp_block_codes<L, K>(coef, coef_fs, dcs, runlen, g, sc, f, b, sdc, sac, put); });
+    const JpAt at = jp_at(wh, coef_fs, g, sc);
+    int64_t stream_o = (int64_t)at.f * stream_fs_words;
+    if constexpr (W::LIST) {
+        stream_fs_words = at.fr->stream_words;
+        stream_o = at.fr->stream_off;
+    }
+    jp_load_tables<L, K>(sdc, sac, fh, at.f, sc);
+    span_write(lbuf, at.bx, offs + at.lens_o, at.slots, total_bits[at.f], stream + stream_o, stream_fs_words, [&](int b, auto&& put) {
+        if (!W::LIST || b < sc.nb) jp_block_codes<L, K>(coef + at.coef_o, dcs + at.blk_o, runlen + at.blk_o, g, sc, b, sdc, sac, put);
+    });
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -321,35 +391,91 @@ static int prog_script(int ncomp, int (*sc)[5]) {
     return ns;
 }
 
+// one scan of a uniform batch
 template <int L, int K>
 static int launch_prog_scan(const JpegJob& a, const JpScan& sc, const JpScanHdr& sh, u32 unused, int si, bool last) {
     const dim3 bgrid((unsigned)((sc.nb + 255) / 256), (unsigned)a.n);
     const int64_t fs = a.g.nblk, words = a.L.stream_words;
     const int16_t *coef = a.coef, *dcs = a.dcs;
     hipStream_t st = a.st;
+    const JpegUniform u;
     if (K != JP_DCR) {
         if (hipMemsetAsync(a.sym, 0, (size_t)a.n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
-        hipLaunchKernelGGL((jprog_count_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, a.g, sc, a.sym, a.flags, a.nbe,
-                           a.runlen, unused);
+        hipLaunchKernelGGL((jprog_count_kernel<L, K, JpegUniform>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, a.g, sc, a.sym, a.flags,
+                           a.nbe, a.runlen, unused, u);
         if (K == JP_ACR) IMGXF_CHECK(scan_rows(a.nbe, fs, sc.nb, a.n, a.part, a.tot_be, st));
         if (K == JP_ACF || K == JP_ACR)
-            hipLaunchKernelGGL(jprog_runs_kernel, bgrid, dim3(256), 0, st, (const u32*)a.flags, (const u32*)(K == JP_ACR ? a.nbe : nullptr),
-                               (const u32*)a.tot_be, a.runlen, a.sym, sc.nb, fs, sc.slot);
+            hipLaunchKernelGGL(jprog_runs_kernel<JpegUniform>, bgrid, dim3(256), 0, st, (const u32*)a.flags,
+                               (const u32*)(K == JP_ACR ? a.nbe : nullptr), (const u32*)a.tot_be, a.runlen, a.sym, a.g, sc, u);
         hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(a.ncomp == 1 ? 2u : 4u, (unsigned)a.n), dim3(256), 0, st, (const u32*)a.sym, a.fh, a.dht);
     }
-    hipLaunchKernelGGL((jprog_lens_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, a.lens, a.g, sc,
-                       (const JpegHuff*)a.fh);
+    hipLaunchKernelGGL((jprog_lens_kernel<L, K, JpegUniform>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, a.lens,
+                       a.g, sc, (const JpegHuff*)a.fh, u);
     IMGXF_CHECK(scan_rows(a.lens, sc.nb, sc.nb, a.n, a.part, a.tot_bits, st));
     hipLaunchKernelGGL(jpeg_zero_kernel<JpegUniform>, bgrid, dim3(256), 0, st, a.ustream, words, (const u32*)a.lens, (const u32*)a.tot_bits,
-                       sc.nb, JpegUniform{});
-    hipLaunchKernelGGL((jprog_emit_kernel<L, K>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen, (const u32*)a.lens,
-                       a.ustream, words, (const u32*)a.tot_bits, a.g, sc, (const JpegHuff*)a.fh);
+                       sc.nb, u);
+    hipLaunchKernelGGL((jprog_emit_kernel<L, K, JpegUniform>), bgrid, dim3(256), 0, st, coef, a.coef_fs, dcs, (const u32*)a.runlen,
+                       (const u32*)a.lens, a.ustream, words, (const u32*)a.tot_bits, a.g, sc, (const JpegHuff*)a.fh, u);
     return launch_stuff(a, &sh, si, last);
 }
 
-template <int L>
-static int launch_prog(const JpegJob& a) {
-    const int ncomp = a.ncomp;
+// One progressive list call, checked and resolved (jpeg_list_encode): the device copy of the block, the workspace's areas
+// and the output.  The grids are the unit tables' lengths, so a scan's launches depend on its kind alone.
+struct JpegProgList {
+    int n, ncomp, sof;
+    const imgxf_jpeg_list_header* hd;          // (the host copy's: unit counts and offsets)
+    const u8* db;                              // the block on the device
+    hipStream_t st;
+    JpegHeader file_hd;                        // SOI .. SOF2
+    int16_t *coef, *dcs;
+    u32 *lens, *part, *tot_bits, *tot_ff, *ustream, *cnt, *sym, *flags, *nbe, *runlen, *pos, *tot_be, *sizes;
+    JpegHuff* fh;
+    JpegDht* dht;
+    u8* out;
+    JpegList where(int stage, int which) const {
+        return JpegList{(const imgxf_jpeg_list_frame*)(db + hd->frames_off), (const imgxf_jpeg_list_unit*)(db + hd->units_off[stage]), which, sof, n};
+    }
+    dim3 grid(int stage) const { return dim3((unsigned)hd->n_units[stage]); }
+};
+
+// one scan of a list: the launches of launch_prog_scan over the unit tables (sc.nb, sc.cw: derived per frame on the device)
+template <int L, int K>
+static int launch_prog_scan_list(const JpegProgList& a, const JpScan& sc, const JpScanHdr& sh, u32 unused, int si, bool last) {
+    const JpegGeom g0 = {0, 0, 0, 0, 0};                       // the uniform arguments: unused, the records state them
+    const int64_t z = 0;
+    const int16_t *coef = a.coef, *dcs = a.dcs;
+    hipStream_t st = a.st;
+    if (K != JP_DCR) {
+        if (hipMemsetAsync(a.sym, 0, (size_t)a.n * JSLOTS * 256 * 4, st) != hipSuccess) return launch_status();
+        hipLaunchKernelGGL((jprog_count_kernel<L, K, JpegList>), a.grid(1), dim3(256), 0, st, coef, z, dcs, g0, sc, a.sym, a.flags, a.nbe,
+                           a.runlen, unused, a.where(1, 0));
+        if (K == JP_ACR) IMGXF_CHECK(scan_rows_list(a.nbe, a.n, a.hd->n_units[2], a.part, a.tot_be, a.where(2, 0), st));
+        if (K == JP_ACF || K == JP_ACR)
+            hipLaunchKernelGGL(jprog_runs_kernel<JpegList>, a.grid(1), dim3(256), 0, st, (const u32*)a.flags,
+                               (const u32*)(K == JP_ACR ? a.nbe : nullptr), (const u32*)a.tot_be, a.runlen, a.sym, g0, sc, a.where(1, 0));
+        hipLaunchKernelGGL(jpeg_opt_table_kernel, dim3(a.ncomp == 1 ? 2u : 4u, (unsigned)a.n), dim3(256), 0, st, (const u32*)a.sym, a.fh, a.dht);
+    }
+    hipLaunchKernelGGL((jprog_lens_kernel<L, K, JpegList>), a.grid(1), dim3(256), 0, st, coef, z, dcs, (const u32*)a.runlen, a.lens, g0, sc,
+                       (const JpegHuff*)a.fh, a.where(1, 0));
+    IMGXF_CHECK(scan_rows_list(a.lens, a.n, a.hd->n_units[2], a.part, a.tot_bits, a.where(2, 0), st));
+    hipLaunchKernelGGL(jpeg_zero_kernel<JpegList>, a.grid(1), dim3(256), 0, st, a.ustream, z, (const u32*)a.lens, (const u32*)a.tot_bits, 0,
+                       a.where(1, 0));
+    hipLaunchKernelGGL((jprog_emit_kernel<L, K, JpegList>), a.grid(1), dim3(256), 0, st, coef, z, dcs, (const u32*)a.runlen, (const u32*)a.lens,
+                       a.ustream, z, (const u32*)a.tot_bits, g0, sc, (const JpegHuff*)a.fh, a.where(1, 0));
+    hipLaunchKernelGGL(jpeg_ffcount_kernel<JpegList>, a.grid(3), dim3(256), 0, st, (const u32*)a.ustream, z, (const u32*)a.tot_bits, a.cnt, z, 0,
+                       a.where(3, 0));
+    IMGXF_CHECK(scan_rows_list(a.cnt, a.n, a.hd->n_units[4], a.part, a.tot_ff, a.where(4, 1), st));
+    hipLaunchKernelGGL(jpeg_stuff_scan_kernel<JpegList>, a.grid(3), dim3(256), 0, st, (const u32*)a.ustream, z, (const u32*)a.tot_bits,
+                       (const u32*)a.cnt, z, 0, (const u32*)a.tot_ff, a.out, z, a.pos, si, last, a.sizes, a.file_hd, (const JpegDht*)a.dht, sh,
+                       a.where(3, 0));
+    return launch_status();
+}
+
+// The script, walked once for both calls: every scan's JpScan (its extent in a frame of geometry g — a list passes zeros
+// and its kernels derive it per frame), its SOS and DHT header and its kind K, handed to
+// scan(std::integral_constant<int, K>, sc, sh, unused slots, scan index, last).
+template <typename Scan>
+static int launch_prog(int ncomp, const JpegGeom& g, Scan&& scan) {
     int script[JP_MAXSCANS][5];
     const int ns = prog_script(ncomp, script);
     const u32 all = ncomp == 3 ? 0xfu : 0x3u;
@@ -361,6 +487,7 @@ static int launch_prog(const JpegJob& a) {
         sc.se = script[si][2];
         sc.ah = script[si][3];
         sc.al = script[si][4];
+        jp_scan_extent(g, sc);
         JpScanHdr sh;
         memset(&sh, 0, sizeof(sh));
         const int nsc = comp < 0 ? ncomp : 1;
@@ -376,22 +503,21 @@ static int launch_prog(const JpegJob& a) {
         sh.sos[6 + 2 * nsc] = (u8)sc.se;
         sh.sos[7 + 2 * nsc] = (u8)((sc.ah << 4) | sc.al);
         if (comp < 0) {
-            sc.nb = a.g.nblk;
-            sc.cw = a.g.mw;
             sc.slot = 0;
             sh.slots = sc.ah ? 0u : (ncomp == 3 ? 0x5u : 0x1u);
         } else {
-            sc.cw = comp == 0 ? (L == JLGRAY ? a.g.mw : a.g.bw) : a.g.mw;
-            sc.nb = comp == 0 ? (L == JLGRAY ? a.g.nblk : a.g.bw * a.g.bh) : a.g.mw * a.g.mh;
             sc.slot = comp == 0 ? 1 : 3;
             sh.slots = 1u << sc.slot;
         }
         const u32 unused = all & ~sh.slots;
         const bool last = si == ns - 1;
         int rc;
-        if (comp < 0) rc = sc.ah ? launch_prog_scan<L, JP_DCR>(a, sc, sh, unused, si, last) : launch_prog_scan<L, JP_DCF>(a, sc, sh, unused, si, last);
-        else rc = sc.ah ? launch_prog_scan<L, JP_ACR>(a, sc, sh, unused, si, last) : launch_prog_scan<L, JP_ACF>(a, sc, sh, unused, si, last);
+        if (comp < 0) rc = sc.ah ? scan(std::integral_constant<int, JP_DCR>{}, sc, sh, unused, si, last)
+                                 : scan(std::integral_constant<int, JP_DCF>{}, sc, sh, unused, si, last);
+        else rc = sc.ah ? scan(std::integral_constant<int, JP_ACR>{}, sc, sh, unused, si, last)
+                        : scan(std::integral_constant<int, JP_ACF>{}, sc, sh, unused, si, last);
         if (rc != IMGXF_OK) return rc;
     }
     return IMGXF_OK;
 }
+

@@ -117,19 +117,22 @@ def load_random_resized_crops(paths: Sequence[str], size=224, scale=(0.08, 1.0),
 
 
 def resize_files(paths: Sequence[str], out_dir: str, size, interpolation="bicubic", quality: int = 75, workers: int = 8, *,
-                 subsampling=-1, optimize: bool = False):
+                 subsampling=-1, optimize: bool = False, progressive: bool = False):
     """Shrink (or enlarge) JPEG files without the pixels ever visiting the host: the files are read on a thread pool and
     decoded on the device as one chunk (`_decode_on_device`: a file the device reader refuses goes to Pillow, one Pillow
     cannot open is skipped with the reference's message), resized by `resize_list.resize_list` in one launch, written
     by `jpeg.encode_list_views` and stored under their own names in `out_dir`.  `size`: an int for torchvision
     `Resize(int)`'s shorter-side rule, or one (width, height) pair for every file.  Each stage is bit-exact, so file k is
     byte for byte `Image.open(p).convert("RGB").resize(size_k, interpolation).save(..., "JPEG", quality=quality,
-    subsampling=subsampling, optimize=optimize)` (Pillow's spellings; the defaults are Pillow's default file), every class
-    in one list call of the writer.  `interpolation` and `subsampling` are checked before any file is read.  Returns the
-    output paths of the files kept, in order."""
+    subsampling=subsampling, optimize=optimize, progressive=progressive)` (Pillow's spellings; the defaults are Pillow's
+    default file), every class in one list call of the writer (progressive files: from
+    `jpeg.PROGRESSIVE_LIST_MIN_SHAPES` distinct sizes on).  `interpolation`, `subsampling` and `progressive` (a bool) are
+    checked before any file is read.  Returns the output paths of the files kept, in order."""
     from . import jpeg, resize_list, tensor_maps
     filt = tensor_maps.resample_filter(interpolation)
     jpeg.sampling(subsampling, 3)
+    if not isinstance(progressive, bool):
+        raise ValueError(f"progressive must be True or False, not {progressive!r}")
     os.makedirs(out_dir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=workers) as pool:
         items = _decode_on_device(list(pool.map(_read, paths)))
@@ -139,7 +142,7 @@ def resize_files(paths: Sequence[str], out_dir: str, size, interpolation="bicubi
         else:
             sizes = [tuple(size)] * len(frames)
         files = jpeg.encode_list_views(resize_list.resize_list(frames, sizes, filt), quality, subsampling=subsampling,
-                                       optimize=optimize)
+                                       optimize=optimize, progressive=progressive)
         outs = [os.path.join(out_dir, os.path.basename(p)) for _, p in items]
         list(pool.map(_write, files, outs))
     return outs

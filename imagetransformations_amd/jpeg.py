@@ -227,23 +227,27 @@ _LIST_FRAME = np.dtype([(name, np.dtype(ct)) for name, ct in F.JpegListFrame._fi
 assert _LIST_FRAME.itemsize == ctypes.sizeof(F.JpegListFrame)
 
 
-def list_layout(sizes: Sequence, capacities: Sequence[int], params: "F.JpegEncParams | None" = None, pinned: bool = False):
+def list_layout(sizes: Sequence, capacities: Sequence[int], params: "F.JpegEncParams | None" = None, pinned: bool = False,
+                progressive: bool = False):
     """imgxf_jpeg_encode_list_layout_host for frames of `sizes` [(h, w)] with `capacities` bytes per file → (block: uint8
     array, header: F.JpegListHeader copy, frames: structured view INTO the block (data and row_stride are the caller's
     to fill)).  With `params` (one class: ncomp, sampling, optimize) imgxf_jpeg_encode_list_ex_layout_host, and the header
-    is a F.JpegListExHeader copy (the same fields under `.list`).  `pinned=True`: built in pinned memory, whose tensor comes
-    fourth.  Host only."""
+    is a F.JpegListExHeader copy (the same fields under `.list`); with `progressive` as well
+    imgxf_jpeg_encode_list_prog_layout_host and a F.JpegListProgHeader copy (`.ex.list`).  `pinned=True`: built in pinned
+    memory, whose tensor comes fourth.  Host only."""
+    if progressive and params is None:
+        raise ValueError("jpeg.list_layout: a progressive block needs its class (params)")
     n = len(sizes)
     hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(n, 2))
     caps = np.ascontiguousarray(np.asarray(capacities, dtype=np.uint64).reshape(n))
     tail = (ctypes.byref(ctypes.c_size_t()), ctypes.byref(ctypes.c_size_t()))   # (workspace, output bytes: the header has them)
     name, first = "imgxf_jpeg_encode_list_layout_host", ()
     if params is not None:
-        name, first = "imgxf_jpeg_encode_list_ex_layout_host", (ctypes.addressof(params),)
+        name, first = f"imgxf_jpeg_encode_list_{'prog' if progressive else 'ex'}_layout_host", (ctypes.addressof(params),)
     block, owner = _list_block.build(name, (*first, hw.ctypes.data, caps.ctypes.data, n), tail, pinned)
-    kind = F.JpegListHeader if params is None else F.JpegListExHeader
+    kind = F.JpegListHeader if params is None else F.JpegListProgHeader if progressive else F.JpegListExHeader
     hd = kind.from_buffer_copy(block[:ctypes.sizeof(kind)].tobytes())
-    off = (hd if params is None else hd.list).frames_off
+    off = (hd if params is None else hd.ex.list if progressive else hd.list).frames_off
     frames = block[off:off + n * _LIST_FRAME.itemsize].view(_LIST_FRAME)
     return (block, hd, frames, owner) if pinned else (block, hd, frames)
 
@@ -266,18 +270,34 @@ def _list_frames(frames) -> list:
 
 _SPELLING = {(1, 1): 0, (2, 1): 1, (2, 2): 2}      # luma sampling -> one `subsampling` spelling of it
 _LIST_MAX_OPT = 65535                # frames per imgxf_jpeg_encode_list_ex_u8 call with optimize (its table stage's grid)
+# Progressive lists: the fewest distinct shapes from which `encode_list_views` takes the list route
+# (imgxf_jpeg_encode_list_prog_u8) instead of one `encode_views` call per shape: the smallest S >= 4 from which the list
+# route's median beats the grouped route's by more than the larger of the two spreads.  Never under 4 (a 3-shape list is
+# pinned to the grouped route).  MI355X, 256 photo-like frames of S distinct sizes, 4:2:0, quality 75, medians (spread) of
+# four alternating runs in ms, two rounds (`PROGRESSIVE=1 SHAPES=S tools/bench_jpeg.py list 256 mixed`,
+# profiles/jpeg_encode_list_progressive.txt):
+#    S    grouped                        list                         list faster beyond the spread
+#    1     3.60 (0.04) /  3.61 (0.06)    3.92 (0.06) / 3.90 (0.05)    no
+#    2     4.14 (0.19) /  4.14 (0.13)    3.78 (0.11) / 3.75 (0.09)    yes
+#    3     5.09 (0.17) /  5.10 (0.06)    3.91 (0.02) / 3.94 (0.07)    yes
+#    4     5.86 (0.11) /  5.88 (0.09)    3.87 (0.07) / 3.87 (0.07)    yes
+#    6     7.79 (0.08) /  7.77 (0.09)    3.88 (0.03) / 3.84 (0.05)    yes
+#    8     9.64 (0.09) /  9.66 (0.06)    3.89 (0.11) / 3.86 (0.06)    yes
+#   16    16.89 (0.13) / 16.94 (0.10)    3.77 (0.08) / 3.76 (0.04)    yes
+PROGRESSIVE_LIST_MIN_SHAPES = 4
 
 
-def _encode_list_device(frames: list, caps: list, quality: int, cls=None):
+def _encode_list_device(frames: list, caps: list, quality: int, cls=None, progressive: bool = False):
     """One list call: → (out: uint8 device buffer, out_off: file f starts at out[out_off[f]], sizes: list, 0xFFFFFFFF where
     file f exceeds caps[f]).  cls None: the default file, imgxf_jpeg_encode_list_u8.  Else one class (ncomp, hv, optimize)
     of [H, W, 3] or [H, W] frames: imgxf_jpeg_encode_list_ex_u8 (a grayscale class is 1x1 to the C side; hv reaches only
-    the SOF byte of the header, as in `encode`)."""
+    the SOF byte of the header, as in `encode`).  `progressive` (with a class; its optimize is moot):
+    imgxf_jpeg_encode_list_prog_u8, the class's progressive files."""
     dev = frames[0].device
     nc = 3 if cls is None else cls[0]
-    params = None if cls is None else F.JpegEncParams(nc, *((1, 1) if nc == 1 else cls[1]), int(cls[2]))
-    block, hd, rec, staged = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps, params, pinned=True)
-    lhd = hd if cls is None else hd.list
+    params = None if cls is None else F.JpegEncParams(nc, *((1, 1) if nc == 1 else cls[1]), 1 if progressive else int(cls[2]))
+    block, hd, rec, staged = list_layout([(t.shape[0], t.shape[1]) for t in frames], caps, params, pinned=True, progressive=progressive)
+    lhd = hd if cls is None else hd.ex.list if progressive else hd.list
     read = [_list_block.dense(t, nc) for t in frames]         # (held until the launch is queued)
     rec["data"], rec["row_stride"] = _list_block.addresses(read, nc)
     block_dev = _list_block.to_device(staged, dev)
@@ -285,8 +305,10 @@ def _encode_list_device(frames: list, caps: list, quality: int, cls=None):
     sizes = torch.zeros((len(frames),), dtype=torch.int32, device=dev)
     ws = torch.empty((lhd.workspace_bytes,), dtype=torch.uint8, device=dev)
     # the device writes each frame's height and width
-    hdr = header(1, 1, quality) if cls is None else header(1, 1, quality, ncomp=nc, subsampling=_SPELLING[cls[1]], optimize=cls[2])
-    name, first = ("imgxf_jpeg_encode_list_u8", ()) if cls is None else ("imgxf_jpeg_encode_list_ex_u8", (ctypes.addressof(params),))
+    hdr = header(1, 1, quality) if cls is None else header(1, 1, quality, ncomp=nc, subsampling=_SPELLING[cls[1]], optimize=cls[2],
+                                                           progressive=progressive)
+    name, first = ("imgxf_jpeg_encode_list_u8", ()) if cls is None else \
+        (f"imgxf_jpeg_encode_list_{'prog' if progressive else 'ex'}_u8", (ctypes.addressof(params),))
     with torch.cuda.device(dev):
         F.call(name, block.ctypes.data, block_dev.data_ptr(), *first, ctypes.addressof(tables(quality)), hdr, len(hdr),
                out.data_ptr(), lhd.out_bytes, sizes.data_ptr(), ws.data_ptr(), lhd.workspace_bytes,
@@ -314,15 +336,17 @@ def encode_list_views(frames: Sequence[torch.Tensor], quality: int = 75, *, subs
     their sizes, with `_capacities`' first-try capacity per frame; the frames that come back over capacity, and only
     those, are encoded again in a second call with their retry capacity.  All pieces of all classes leave the device as
     one gathered copy, and the files are returned in input order.
-    `progressive=True` has no list kernels (ten scans with per-scan tables): those frames are grouped by shape and each
-    group goes through `encode_views` — the same bytes, one call per shape."""
+    `progressive=True`: a list of at least PROGRESSIVE_LIST_MIN_SHAPES distinct shapes takes the same route with
+    imgxf_jpeg_encode_list_prog_u8 — one call per class (ncomp, sampling) in chunks of 65535 frames, first-try capacities
+    `_capacities(..., progressive=True)[0]`, one second call for the frames that came back over capacity.  A list of fewer
+    shapes is grouped by shape and each group goes through `encode_views` — the same bytes, one call per shape."""
     frames = _list_frames(frames)
     if not frames:
         return []
     hv3 = sampling(subsampling, 3)                   # (refuses a bad spelling before any work)
     optimize, progressive = bool(optimize), bool(progressive)
     result: list = [None] * len(frames)
-    if progressive:
+    if progressive and len({tuple(t.shape) for t in frames}) < PROGRESSIVE_LIST_MIN_SHAPES:
         groups: dict = {}
         for i, t in enumerate(frames):
             groups.setdefault(tuple(t.shape), []).append(i)
@@ -336,16 +360,17 @@ def encode_list_views(frames: Sequence[torch.Tensor], quality: int = 75, *, subs
     for i, t in enumerate(frames):
         nc = 3 if t.dim() == 3 else 1
         hv = hv3 if nc == 3 else sampling(subsampling, 1)
-        classes.setdefault(None if nc == 3 and hv == (2, 2) and not optimize else (nc, hv, optimize), []).append(i)
+        default = nc == 3 and hv == (2, 2) and not optimize and not progressive
+        classes.setdefault(None if default else (nc, hv, optimize), []).append(i)
     pieces: dict = {}                                # frame -> device view of exactly its file
     for cls, members in classes.items():
         nc, hv = (3, (2, 2)) if cls is None else cls[:2]
-        step = _LIST_MAX_OPT if optimize else len(members)
+        step = _LIST_MAX_OPT if optimize or progressive else len(members)
         for lo in range(0, len(members), step):
             todo = members[lo:lo + step]
             for attempt in (0, 1):
-                caps = [_capacities(frames[i].shape[0], frames[i].shape[1], nc, hv)[attempt] for i in todo]
-                out, offs, lens = _encode_list_device([frames[i] for i in todo], caps, quality, cls)
+                caps = [_capacities(frames[i].shape[0], frames[i].shape[1], nc, hv, progressive)[attempt] for i in todo]
+                out, offs, lens = _encode_list_device([frames[i] for i in todo], caps, quality, cls, progressive)
                 _check_overflow(lens)
                 for i, o, v in zip(todo, offs, lens):
                     if v != 0xFFFFFFFF:

@@ -663,6 +663,41 @@ int imgxf_jpeg_encode_prog_u8(const imgxf_view* src, const imgxf_jpeg_enc_params
                               const uint8_t* header, int header_bytes, uint8_t* out, size_t out_frame_stride,
                               uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The list writer for progressive files: one call writes a LIST of frames of different sizes that share one class (ncomp,
+ * sampling) as the files of imgxf_jpeg_encode_prog_u8, in a number of launches that depends on the class alone (158 for a
+ * colour class, 92 for grayscale, memsets included), never on the frames.  params->optimize is ignored, as there (the block
+ * states it as 1).  The block is
+ *     imgxf_jpeg_list_prog_header | imgxf_jpeg_list_frame[n] | imgxf_jpeg_list_unit tables (5)
+ * whose frame records and unit tables are byte for byte those imgxf_jpeg_encode_list_ex_layout_host writes for the same
+ * class and sizes: every scan runs over the frame's nblk block slots (the slots past the scan's own blocks are zero-length
+ * entries), so the five unit tables serve all scans.  The workspace holds the areas of the sequential list, the three
+ * own-table areas (always present) and four more: per block slot, at the frame's blk_off, uint32 flags, correction-bit
+ * counts and EOB-run lengths; then uint32 pos[11][n] (where each scan of each frame starts in its file, or the sizes[]
+ * sentinel once a scan failed) followed by the correction-bit totals [n]. */
+#define IMGXF_JPEG_LIST_PROG_AREAS 4
+typedef struct imgxf_jpeg_list_prog_header {
+    imgxf_jpeg_list_ex_header ex;                            /* ex.list.frames_off = sizeof(imgxf_jpeg_list_prog_header) */
+    uint64_t prog_off[IMGXF_JPEG_LIST_PROG_AREAS];           /* byte offsets into the workspace, 256-byte aligned */
+} imgxf_jpeg_list_prog_header;
+/* HOST half, as imgxf_jpeg_encode_list_ex_layout_host.  The workspace never exceeds the sum over the frames of
+ * imgxf_jpeg_workspace_bytes_prog(params, 1, h, w, capacity).  Errors as there: IMGXF_ERR_ARG for params outside the
+ * classes, a capacity below 1024 + 2; IMGXF_ERR_SHAPE for h or w outside 1..32767, the block limit and more than 65535
+ * frames (the table stage runs one workgroup per table and frame); IMGXF_ERR_WORKSPACE when block_cap is too small (the
+ * sizes are still reported). */
+int imgxf_jpeg_encode_list_prog_layout_host(const imgxf_jpeg_enc_params* params, const int32_t* sizes, const uint64_t* capacities,
+                                            int n, void* block, size_t block_cap, size_t* block_bytes, size_t* workspace_bytes,
+                                            size_t* out_bytes);
+/* The launches, with the arguments and the contract of imgxf_jpeg_encode_list_ex_u8.  `header` is SOI .. SOF2 with any
+ * size: the device writes each frame's height and width, every scan's DHT segments and SOS, its stuffed data and EOI into
+ * the frame's slot.  sizes[f]: the file's length, 0xFFFFFFFF when the file does not fit out_cap (a frame that overflows in
+ * some scan writes nothing past its slot in that scan or a later one; the other frames' files are unaffected), 0xFFFFFFFE
+ * when a scan's optimal table would need a code over 32 bits.  Every record is checked and the block rebuilt and compared
+ * before a device pointer is looked at: a block laid out for other params (or by another layout function) and a header
+ * without SOF2 -> IMGXF_ERR_ARG, n > 65535 -> IMGXF_ERR_SHAPE; the other errors as imgxf_jpeg_encode_list_u8. */
+int imgxf_jpeg_encode_list_prog_u8(const void* block_host, const void* block_dev, const imgxf_jpeg_enc_params* params,
+                                   const imgxf_jpeg_tables* tables, const uint8_t* header, int header_bytes, uint8_t* out,
+                                   size_t out_bytes, uint32_t* sizes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* JPEG compression applied in place of a file: dst = the pixels of `Image.open(f).convert("RGB")` (grayscale: the "L"
  * image) after `Image.fromarray(src).save(f, "JPEG", quality=q, subsampling=s)`, bit-identical to Pillow, for the frames
  * and layouts of imgxf_jpeg_encode_ex_u8.  Nothing is entropy-coded: one kernel runs the writer's transform stage (colour

@@ -4,7 +4,8 @@ OPTIMIZE=1, PROGRESSIVE=1, GRAY=1 (the frames converted to "L") — Pillow runs 
 the threaded Pillow comparison.
 The progressive rows: PROGRESSIVE=1 with SUBSAMPLING=2 / 0 / GRAY=1, for 16 frames of 4K and 256 of 375 500.
 List mode (`jpeg.encode_list_views` against the per-shape route): python tools/bench_jpeg.py list [frames] [mixed|uniform] [a|b]
-[--subsampling S] [--optimize] [--gray]
+[--subsampling S] [--optimize] [--gray]; env PROGRESSIVE=1 (progressive files: the grouped route against the list route),
+SHAPES=S (only the first S distinct sizes)
 Round-trip mode (JPEG compression without a file against encode + decode): python tools/bench_jpeg.py roundtrip [frames]
 [mixed|uniform] [fused|compose]"""
 import io, os, sys, time
@@ -85,9 +86,18 @@ def list_mode(argv):
     alternate, four runs each after a warm-up, a host clock around calls that end in a synchronise; files compared.
     With a third argument only that route runs, once after a warm-up, preceded by "TRACE": for
     `rocprofv3 --kernel-trace --stats`, whose launch counts are then (warm-up + 1) x one call's.  Exits non-zero when
-    the files differ."""
+    the files differ.
+    PROGRESSIVE=1 (environment): progressive files.  Route a is then the grouped route of `encode_list_views` itself
+    (`jpeg.PROGRESSIVE_LIST_MIN_SHAPES` set huge: group by shape, torch.stack, `encode_views` per shape — the only route before
+    the list kernels), route b the list route (the constant set to 1); two rounds of four alternating runs, each with its own
+    median and spread, and the verdict against the larger of the two spreads.  SHAPES=S: the list holds only the first S
+    distinct sizes of the mix, its frames cycling through them (the sweep that sets the constant: 256 frames, S = 1, 2,
+    3, 4, 6, 8, 16)."""
     from imagetransformations_amd import _ffi as F
     argv, opts, gray = list(argv), {}, False
+    progressive = os.environ.get("PROGRESSIVE", "0") == "1"
+    if progressive:
+        opts["progressive"] = True
     if "--optimize" in argv:
         argv.remove("--optimize"); opts["optimize"] = True
     if "--gray" in argv:
@@ -99,6 +109,11 @@ def list_mode(argv):
     mix = argv[1] if len(argv) > 1 else "mixed"
     only = argv[2] if len(argv) > 2 else None
     sizes, frames = photo_frames(n, mix)
+    if os.environ.get("SHAPES"):
+        first = list(dict.fromkeys(sizes))[:int(os.environ["SHAPES"])]
+        pick = {s: frames[sizes.index(s)] for s in first}
+        sizes = [first[i % len(first)] for i in range(n)]
+        frames = [pick[s] for s in sizes]
     if gray:
         frames = [t[..., 1].contiguous() for t in frames]
     groups = {}
@@ -106,6 +121,9 @@ def list_mode(argv):
         groups.setdefault(tuple(t.shape), []).append(i)
 
     def route_a():
+        if progressive:
+            jpeg.PROGRESSIVE_LIST_MIN_SHAPES = 1 << 30
+            return jpeg.encode_list_views(frames, **opts)
         out = [None] * n
         for idx in groups.values():
             for i, v in zip(idx, jpeg.encode_views(torch.cat([frames[i][None] for i in idx]), **opts)):
@@ -113,6 +131,8 @@ def list_mode(argv):
         return out
 
     def route_b():
+        if progressive:
+            jpeg.PROGRESSIVE_LIST_MIN_SHAPES = 1
         return jpeg.encode_list_views(frames, **opts)
 
     seen, real = {}, F.call
@@ -135,23 +155,29 @@ def list_mode(argv):
     route_a(); ca = dict(seen); seen.clear()
     route_b(); cb = dict(seen); seen.clear()
     F.call = real
-    ta, tb = [], []
-    for _ in range(4):
-        for fn, ts in ((route_a, ta), (route_b, tb)):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
     med = lambda v: sorted(v)[len(v) // 2 - 1] / 2 + sorted(v)[len(v) // 2] / 2
     px = sum(h * w for h, w in sizes)
     print(f"list mode, {mix}{', gray' if gray else ''} {opts or ''}: {n} photo-like frames, {len(groups)} distinct sizes, "
           f"{px / 1e6:.1f} Mpix, quality 75, {nbytes / px:.3f} bytes/px; "
           f"files equal: {same}")
-    for name, ts, calls in (("a: per shape, torch.cat + encode_views", ta, ca), ("b: encode_list_views", tb, cb)):
-        writer = sum(v for k, v in calls.items() if k.startswith("imgxf_jpeg_encode") and k.endswith("_u8"))
-        print(f"  {name:<40} runs (ms) {' '.join(f'{t:.2f}' for t in ts)}  median {med(ts):.2f}  spread {max(ts) - min(ts):.2f}  "
-              f"{n / med(ts) * 1e3:.0f} files/s  C calls {sum(calls.values())} ({writer} writer)")
-    gain = med(ta) - med(tb)
-    print(f"  median(a) - median(b) = {gain:.2f} ms ({med(ta) / med(tb):.2f}x); spread of a {max(ta) - min(ta):.2f} ms: "
-          f"b is {'FASTER beyond the spread' if gain > max(ta) - min(ta) else 'NOT faster beyond the spread'}", flush=True)
+    for rnd in range(2 if progressive else 1):
+        ta, tb = [], []
+        for _ in range(4):
+            for fn, ts in ((route_a, ta), (route_b, tb)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+        if progressive:
+            print(f" round {rnd + 1}")
+        for name, ts, calls in (("a: per shape, torch.cat + encode_views", ta, ca), ("b: encode_list_views", tb, cb)):
+            writer = sum(v for k, v in calls.items() if k.startswith("imgxf_jpeg_encode") and k.endswith("_u8"))
+            print(f"  {name:<40} runs (ms) {' '.join(f'{t:.2f}' for t in ts)}  median {med(ts):.2f}  spread {max(ts) - min(ts):.2f}  "
+                  f"{n / med(ts) * 1e3:.0f} files/s  C calls {sum(calls.values())} ({writer} writer)")
+        gain = med(ta) - med(tb)
+        bar = max(ta) - min(ta)
+        if progressive:                                         # the larger of the two spreads
+            bar = max(bar, max(tb) - min(tb))
+        print(f"  median(a) - median(b) = {gain:.2f} ms ({med(ta) / med(tb):.2f}x); spread {'(the larger)' if progressive else 'of a'} "
+              f"{bar:.2f} ms: b is {'FASTER beyond the spread' if gain > bar else 'NOT faster beyond the spread'}", flush=True)
     return 0 if same else 1
 
 
