@@ -139,6 +139,8 @@ SIGNATURES = {
     "imgxf_f32_map": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_void_p],
     "imgxf_to_tensor_f32": [_VP, C.c_void_p, _F, _F, C.c_void_p],
     "imgxf_perspective_bilinear_u8": [_VP, _VP, C.POINTER(C.c_float), C.c_int, C.c_void_p],
+    "imgxf_perspective_tile_plan_host": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int,
+                                         C.POINTER(C.c_int)],
     "imgxf_histogram_u8": [_VP, C.c_void_p, C.c_void_p],
     "imgxf_jpeg_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)],
     "imgxf_jpeg_encode_u8": [_VP, C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,

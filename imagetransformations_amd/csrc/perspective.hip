@@ -14,7 +14,7 @@
 
 namespace imgxf {
 
-constexpr int PV_MAX_FRAMES = 48;              // coefficient sets per launch (kernarg budget)
+constexpr int PV_MAX_FRAMES = 48;              // coefficient sets per launch (kernarg budget: 48 x 48 B + 8 = 2312 B of 4 KiB)
 
 struct PerspArgs {
     PerspCoef k[PV_MAX_FRAMES];
@@ -57,6 +57,37 @@ static int launch_perspective(const View& s, const View& d, const float* coeffs,
 } // namespace imgxf
 
 using namespace imgxf;
+
+// What wave 0 of pv_tile decides for the tile at (tx0, ty0) of a w x h x c frame: the same four corner evaluations (host
+// fmaf and IEEE division, the device's values under -ffp-contract=off) and the same pv_box_rule.  No launch, no device.
+IMGXF_API int imgxf_perspective_tile_plan_host(int w, int h, int c, int src_dwords, const float* coeffs, int tx0, int ty0,
+                                               int* out) {
+    if (!coeffs || !out) return IMGXF_ERR_NULL;
+    if (w < 1 || h < 1 || w > 32767 || h > 32767) return IMGXF_ERR_SHAPE;
+    if (c != 1 && c != 3 && c != 4) return IMGXF_ERR_UNSUPPORTED;
+    if ((src_dwords != 0 && src_dwords != 1) || tx0 < 0 || ty0 < 0 || tx0 >= w || ty0 >= h || tx0 % PV_TW || ty0 % PV_TH)
+        return IMGXF_ERR_ARG;
+    for (int i = 0; i < 8; ++i)
+        if (!(coeffs[i] == coeffs[i]) || coeffs[i] - coeffs[i] != 0.0f) return IMGXF_ERR_ARG;   // NaN / inf
+    const PerspCoef k = persp_coef(coeffs, w, h);
+    const int tx1 = min(tx0 + PV_TW, w) - 1, ty1 = min(ty0 + PV_TH, h) - 1;
+    float lox = 0.0f, hix = 0.0f, loy = 0.0f, hiy = 0.0f, dmin = 0.0f;
+    bool finite = true;
+    for (int q = 0; q < 4; ++q) {
+        const float bx = (float)((q & 1) ? tx1 : tx0) + 0.5f, by = (float)((q & 2) ? ty1 : ty0) + 0.5f;
+        float ix, iy;
+        persp_src(k, bx, by, (float)w, (float)h, ix, iy);
+        const float dn = fmaf(by, k.c7, bx * k.c6) + 1.0f;
+        finite = finite && fabsf(ix) < 1.0e9f && fabsf(iy) < 1.0e9f;
+        lox = q ? fminf(lox, ix) : ix; hix = q ? fmaxf(hix, ix) : ix;
+        loy = q ? fminf(loy, iy) : iy; hiy = q ? fmaxf(hiy, iy) : iy;
+        dmin = q ? fminf(dmin, dn) : dn;
+    }
+    const PvBox b = pv_box_rule(k, lox, hix, loy, hiy, dmin, finite, w, h, c, src_dwords != 0);
+    out[0] = b.staged; out[1] = b.interior; out[2] = b.bx0; out[3] = b.by0;
+    out[4] = b.bw; out[5] = b.bh; out[6] = b.pitch; out[7] = b.gb0;
+    return IMGXF_OK;
+}
 
 IMGXF_API int imgxf_perspective_bilinear_u8(const imgxf_view* src, const imgxf_view* dst,
                                             const float* coeffs, int per_frame, void* stream) {

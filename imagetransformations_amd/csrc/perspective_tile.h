@@ -5,10 +5,11 @@
 // order (and with the fused multiply-adds) that the torch CPU build evaluates them in; the library is built with
 // -ffp-contract=off, so only the fmaf calls fuse.
 //
-// The tile maps to a convex quadrilateral of the source; its bounding box (from the four tile corners, plus a margin for
-// rounding) is staged in LDS already divided by 255 (one float per byte: 1.2 conversions per output sample instead of 4),
-// and the four taps are read from there; the output tile leaves through LDS as dwords.  Tiles whose box does not fit or
-// whose denominator changes sign (extreme coefficients) gather from global memory instead.
+// The tile maps to a convex quadrilateral of the source; its bounding box (from the four tile corners, plus a margin that
+// bounds the rounding: pv_box_rule, a host function too, which imgxf_perspective_tile_plan_host answers from) is staged in
+// LDS already divided by 255 (one float per byte: 1.2 conversions per output sample instead of 4), and the four taps are
+// read from there; the output tile leaves through LDS as dwords.  Tiles whose box does not fit or whose denominator
+// changes sign (extreme coefficients) gather from global memory instead.
 #pragma once
 #include "imgxf_common.h"
 
@@ -18,7 +19,8 @@ constexpr int PV_TW = 64, PV_TH = 16;          // output tile
 constexpr int PV_LDS_FLOATS = 8 * 1024;        // staged source box, one float per byte (32 KiB)
 constexpr int PV_THREADS = 256;
 
-struct PerspCoef { float t[6]; float c6, c7; };   // t = c[0..5] / (0.5*ow | 0.5*oh)
+// t = c[0..5] / (0.5*ow | 0.5*oh); hx, hy, dd, dsafe: the frame's part of the rounding bound of pv_box_rule
+struct PerspCoef { float t[6]; float c6, c7; float hx, hy, dd, dsafe; };
 
 // the IEEE fp32 divisions of _perspective_grid's theta by the half size
 __host__ __device__ __forceinline__ PerspCoef persp_coef(const float* c, int ow, int oh) {
@@ -27,6 +29,13 @@ __host__ __device__ __forceinline__ PerspCoef persp_coef(const float* c, int ow,
     k.t[0] = c[0] / sx; k.t[1] = c[1] / sx; k.t[2] = c[2] / sx;
     k.t[3] = c[3] / sy; k.t[4] = c[4] / sy; k.t[5] = c[5] / sy;
     k.c6 = c[6]; k.c7 = c[7];
+    const float fw = (float)ow, fh = (float)oh;
+    k.hx = sx * (fw * fabsf(k.t[0]) + fh * fabsf(k.t[1]) + fabsf(k.t[2]));
+    k.hy = sy * (fw * fabsf(k.t[3]) + fh * fabsf(k.t[4]) + fabsf(k.t[5]));
+    k.dd = fw * fabsf(k.c6) + fh * fabsf(k.c7) + 1.0f;
+    const float e = 2.384185791015625e-07f, mc1 = 65537.0f;        // 2^-22, PV_MC + 1
+    k.dsafe = 2.0f * e * k.dd + 3.0f * e * (fmaxf(k.hx, k.hy) + mc1 * k.dd) / (1.0f - 3.0f * e * (mc1 + fmaxf(fw, fh)));
+    k.dsafe = fmaxf(k.dsafe, 10.0f * e * k.dd);                    // so that dsafe implies e dd <= dlo / 8 (below)
     return k;
 }
 
@@ -46,7 +55,7 @@ __device__ __forceinline__ float unit255(float v) {
     return fmaf(fmaf(-255.0f, q, v), r, q);
 }
 
-__device__ __forceinline__ void persp_src(const PerspCoef& k, float bx, float by, float fw, float fh,
+__host__ __device__ __forceinline__ void persp_src(const PerspCoef& k, float bx, float by, float fw, float fh,
                                           float& ix, float& iy) {
     const float nx = fmaf(by, k.t[1], bx * k.t[0]) + k.t[2];
     const float ny = fmaf(by, k.t[4], bx * k.t[3]) + k.t[5];
@@ -78,6 +87,74 @@ __device__ __forceinline__ void persp_src_fast(const PerspCoef& k, float bx, flo
     iy = fmaf(gy + 1.0f, fh, -1.0f) * 0.5f;
 }
 
+// What wave 0 decides for a tile, and imgxf_perspective_tile_plan_host hands out: whether the source box is staged in LDS,
+// whether every tap may be read from it unchecked, and the box (first column and row, size, floats per staged row, first
+// staged byte of a source row).
+struct PvBox {
+    bool staged, interior;
+    int bx0, by0, bw, bh, pitch, gb0;
+};
+
+// Bound on |computed - exact| of a source coordinate anywhere in the frame's tile, in pixels.  "Exact" is the projective map
+// with the fp32 coefficients k in real arithmetic: its denominator is linear, so it keeps its sign over the tile when the
+// four corners agree, and then each coordinate takes its extremes over the tile at the corners.  The box argument needs
+// the computed values to follow it to within the margin.  With u = 2^-24, bx < ow, by < oh:
+//   numerator   nx = fl(fl(fma(by, t1, fl(bx t0))) + t2): three roundings of values <= an = ow|t0| + oh|t1| + |t2|,
+//                    so |nx - NX| <= 3u an (1 + 3u) <= e an with e = 2^-22 (a quarter spare); dn likewise with
+//                    dd = ow|c6| + oh|c7| + 1;
+//   denominator every exact and computed dn of the tile is >= dlo = dmin - 2 e dd (dmin: the computed corner minimum);
+//   quotient    |fl(nx / dn) - Q| <= e (an + |Q| dd) / dlo + u |q|;
+//   unnormalise gx = fl(q - 1), fl(gx + 1), fl(fma(., size, -1)) / 2 add (size / 2) u (2|q| + 1) + u |i|, and
+//               (size / 2)|q| <= |i| + 1/2, so with m >= |i| + 1 over the tile
+//                    E <= e ((size / 2) an + m dd) / dlo + e (m + size).
+// m is itself known only from the computed corners, mc = max(|lo|, |hi|) + 1 <= m <= mc + 2E.  Where e dd <= dlo / 8 the
+// factor of m in E is <= 1/8 + e, and solving for E costs a factor <= 1 / (1 - 1/4 - 2e) < 3/2.  A corner estimate and
+// a pixel are each off by E, so the box moves out by ceil(2E) <= ceil(3 E(mc)) on each side: 1 px for every frame of
+// ordinary size and coefficients (1080p, drawn coefficients: 3E ~ 0.01), tens of pixels where a denominator near 1e-3
+// meets a row of 32k pixels (the quotient's error 2^-22 / dn times size / 2 is then several pixels).
+// h = (size / 2) an and dd are the frame's (persp_coef), which also works out the least denominator dsafe above which
+// 3E <= 1 for every tile whose coordinates stay below PV_MC in magnitude: there a tile pays two comparisons.
+constexpr float PV_E = 2.384185791015625e-07f;       // e = 2^-22
+constexpr float PV_3E = 7.152557373046875e-07f;      // 3e
+constexpr float PV_MAX_MARGIN = 4096.0f;             // beyond it no box fits anyway
+constexpr float PV_MC = 65536.0f;                    // coordinates up to here share the frame's dsafe
+
+// The box rule.  lox .. hiy, dmin, finite: extremes of the four corner pixels' source coordinates, the least corner
+// denominator, and whether all four coordinates are below 1e9 in magnitude; w, h, C: the source; src4: rows are staged
+// as aligned dwords.
+__host__ __device__ __forceinline__ PvBox pv_box_rule(const PerspCoef& k, float lox, float hix, float loy, float hiy,
+                                                      float dmin, bool finite, int w, int h, int C, bool src4) {
+    PvBox b = {false, false, 0, 0, 0, 0, 0, 0};
+    // the denominator must keep one sign over the tile for the quadrilateral argument to hold
+    b.staged = finite && dmin > 1.0e-3f && dmin < 1.0e6f;
+    if (b.staged) {
+        // margin for the rounding of the corner estimates and of the pixels' own coordinates (at least 1 px)
+        const float ax = fmaxf(fabsf(lox), fabsf(hix)), ay = fmaxf(fabsf(loy), fabsf(hiy));
+        int mx = 1, my = 1;
+        if (!(fmaxf(ax, ay) <= PV_MC && dmin >= k.dsafe)) {
+            if (!(dmin >= 10.0f * PV_E * k.dd)) { b.staged = false; return b; }      // e dd <= dlo / 8
+            const float rdlo = 1.0f / (dmin - 2.0f * PV_E * k.dd);      // its own rounding is far inside the spare
+            const float fmx = fmaxf(PV_3E * ((k.hx + (ax + 1.0f) * k.dd) * rdlo + ((ax + 1.0f) + (float)w)), 1.0f);
+            const float fmy = fmaxf(PV_3E * ((k.hy + (ay + 1.0f) * k.dd) * rdlo + ((ay + 1.0f) + (float)h)), 1.0f);
+            if (!(fmx <= PV_MAX_MARGIN && fmy <= PV_MAX_MARGIN)) { b.staged = false; return b; }
+            mx = (int)ceilf(fmx); my = (int)ceilf(fmy);
+        }
+        // 1 more for the right / bottom tap
+        const int ux0 = (int)floorf(lox) - mx, uy0 = (int)floorf(loy) - my;
+        const int ux1 = (int)floorf(hix) + 1 + mx, uy1 = (int)floorf(hiy) + 1 + my;
+        b.bx0 = max(ux0, 0); b.by0 = max(uy0, 0);
+        const int bx1 = min(ux1, w - 1), by1 = min(uy1, h - 1);
+        b.interior = ux0 >= 0 && uy0 >= 0 && ux1 <= w - 1 && uy1 <= h - 1;
+        b.bw = bx1 - b.bx0 + 1; b.bh = by1 - b.by0 + 1;
+        if (b.bw <= 0 || b.bh <= 0) { b.bw = b.bh = 0; }   // the tile sees no source pixel at all
+        b.gb0 = b.bw <= 0 ? 0 : src4 ? (b.bx0 * C) & ~3 : b.bx0 * C;   // first staged byte of a source row
+        b.pitch = b.bw > 0 ? (((bx1 + 1) * C - b.gb0 + 3) & ~3) : 0;     // floats per staged row
+        b.staged = (int64_t)b.pitch * b.bh <= PV_LDS_FLOATS;
+        b.interior = b.interior && b.staged;
+    }
+    return b;
+}
+
 // min over the four lanes of a quad (DPP quad_perm swaps), the same value in all four
 __device__ __forceinline__ float quad_min(float v) {
     float o = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
@@ -107,34 +184,17 @@ __device__ __forceinline__ void pv_tile(const PvFrame& s, const PvFrame& d, cons
         const float bx = (float)((q & 1) ? tx1 : tx0) + 0.5f, by = (float)((q & 2) ? ty1 : ty0) + 0.5f;
         float ix, iy;
         persp_src(k, bx, by, fw, fh, ix, iy);
-        // the denominator must keep one sign over the tile for the quadrilateral argument to hold
         const float dn = fmaf(by, k.c7, bx * k.c6) + 1.0f;
         const float bad = (fabsf(ix) < 1.0e9f && fabsf(iy) < 1.0e9f) ? 0.0f : 1.0f;   // NaN -> 1
         const float lox = quad_min(ix), hix = -quad_min(-ix);
         const float loy = quad_min(iy), hiy = -quad_min(-iy);
         const float dmin = quad_min(dn);
         const bool finite = quad_min(-bad) == 0.0f;
-        bool staged = finite && dmin > 1.0e-3f && dmin < 1.0e6f;
-        bool interior = false;
-        int bx0 = 0, by0 = 0, bw = 0, bh = 0, pitch = 0, gb0 = 0;
-        if (staged) {
-            // 1 px of margin for the rounding of the corner estimates, 1 more for the right / bottom tap
-            const int ux0 = (int)floorf(lox) - 1, uy0 = (int)floorf(loy) - 1;
-            const int ux1 = (int)floorf(hix) + 2, uy1 = (int)floorf(hiy) + 2;
-            bx0 = max(ux0, 0); by0 = max(uy0, 0);
-            const int bx1 = min(ux1, s.w - 1), by1 = min(uy1, s.h - 1);
-            interior = ux0 >= 0 && uy0 >= 0 && ux1 <= s.w - 1 && uy1 <= s.h - 1;
-            bw = bx1 - bx0 + 1; bh = by1 - by0 + 1;
-            if (bw <= 0 || bh <= 0) { bw = bh = 0; }           // the tile sees no source pixel at all
-            gb0 = src4 ? (bx0 * C) & ~3 : bx0 * C;              // first staged byte of a source row
-            pitch = bw > 0 ? (((bx1 + 1) * C - gb0 + 3) & ~3) : 0;     // floats per staged row
-            staged = (int64_t)pitch * bh <= PV_LDS_FLOATS;
-            interior = interior && staged;
-        }
+        const PvBox b = pv_box_rule(k, lox, hix, loy, hiy, dmin, finite, s.w, s.h, C, src4);
         if (lane == 0) {
-            boxinfo[0] = (staged ? 1 : 0) | (interior ? 2 : 0);
-            boxinfo[1] = bx0; boxinfo[2] = by0; boxinfo[3] = bw; boxinfo[4] = bh;
-            boxinfo[5] = pitch; boxinfo[6] = gb0;
+            boxinfo[0] = (b.staged ? 1 : 0) | (b.interior ? 2 : 0);
+            boxinfo[1] = b.bx0; boxinfo[2] = b.by0; boxinfo[3] = b.bw; boxinfo[4] = b.bh;
+            boxinfo[5] = b.pitch; boxinfo[6] = b.gb0;
         }
     }
     __syncthreads();

@@ -500,6 +500,13 @@ int imgxf_to_tensor_f32(const imgxf_view* src, float* dst, const float* mean, co
  * (c in {1,3,4}) and must not alias. */
 int imgxf_perspective_bilinear_u8(const imgxf_view* src, const imgxf_view* dst,
                                   const float* coeffs, int per_frame, void* stream);
+/* HOST only, no device: what the kernel decides for the 64 x 16 output tile at (tx0, ty0) (multiples of 64 and 16 inside
+ * the frame) of a w x h x c frame (w, h <= 32767, c in {1,3,4}) with coeffs float[8]; src_dwords: 1 where the source is
+ * staged as aligned dwords (base, row and frame stride multiples of 4, a frame below 4 GiB), else 0.
+ * out[8] = staged (the tile's source box goes to LDS; 0: the taps are gathered from global memory), interior (every tap
+ * is read from the box unchecked), bx0, by0, bw, bh (the box; bw = bh = 0: the tile sees no source pixel), pitch (floats
+ * per staged row), gb0 (first staged byte of a source row).  The same function as the kernel's first wave evaluates. */
+int imgxf_perspective_tile_plan_host(int w, int h, int c, int src_dwords, const float* coeffs, int tx0, int ty0, int* out);
 
 /* ---- the driver's save step  transformation.py:161-162 (`transformed.save(path)`: Pillow ->
  * libjpeg-turbo baseline JPEG, 4:2:0, islow DCT, no restart markers) ------------------------*/
