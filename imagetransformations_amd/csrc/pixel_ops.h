@@ -64,6 +64,71 @@ __device__ __forceinline__ void bicubic_row_exact_px(const u8* row, int sw, bool
     }
 }
 
+// libImaging's fp64 sequences for one RGB pixel of a general affine transform, BILINEAR and BICUBIC (affine_transform +
+// bilinear_filter / bicubic_filter of Geometry.c), every operation rounded on its own whatever the file's contraction
+// flags: sp = pixel (0, 0) of the h x w source, rs its row stride in bytes.  false: (x, y) maps outside the source (the
+// test is on the doubles, before any conversion to int) and px is untouched — the caller stores its fill.
+__device__ __forceinline__ bool affine_src_exact(const double* m, int x, int y, int h, int w, double& xin, double& yin) {
+    const double xc = (double)x + 0.5, yc = (double)y + 0.5;
+    xin = __dadd_rn(__dadd_rn(__dmul_rn(m[0], xc), __dmul_rn(m[1], yc)), m[2]);
+    yin = __dadd_rn(__dadd_rn(__dmul_rn(m[3], xc), __dmul_rn(m[4], yc)), m[5]);
+    return xin >= 0.0 && xin < (double)w && yin >= 0.0 && yin < (double)h;
+}
+// BILINEAR(v, a, b, d) = a + (b - a) * d
+__device__ __forceinline__ double lerp_exact(double a, double b, double d) { return __dadd_rn(a, __dmul_rn(__dsub_rn(b, a), d)); }
+__device__ __forceinline__ bool affine_bilinear_exact_px(const u8* sp, int64_t rs, int h, int w, const double* m, int x, int y,
+                                                         u8 (&px)[3]) {
+    constexpr int C = 3;
+    double xin, yin;
+    if (!affine_src_exact(m, x, y, h, w, xin, yin)) return false;
+    xin = __dsub_rn(xin, 0.5); yin = __dsub_rn(yin, 0.5);
+    const double xfl = floor(xin), yfl = floor(yin);
+    const int xi = (int)xfl, yi = (int)yfl;
+    const double dx = __dsub_rn(xin, xfl), dy = __dsub_rn(yin, yfl);
+    const int xa = clampi(xi, 0, w - 1) * C, xb = clampi(xi + 1, 0, w - 1) * C;
+    const u8* r0 = sp + (int64_t)clampi(yi, 0, h - 1) * rs;
+    const bool has1 = (yi + 1 >= 0) && (yi + 1 < h);
+    const u8* r1 = sp + (int64_t)(has1 ? yi + 1 : 0) * rs;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const double v1 = lerp_exact((double)r0[xa + j], (double)r0[xb + j], dx);
+        const double v2 = has1 ? lerp_exact((double)r1[xa + j], (double)r1[xb + j], dx) : v1;
+        px[j] = (u8)(int)lerp_exact(v1, v2, dy);               // (UINT8)v truncation
+    }
+    return true;
+}
+__device__ __forceinline__ bool affine_bicubic_exact_px(const u8* sp, int64_t rs, int h, int w, const double* m, int x, int y,
+                                                        u8 (&px)[3]) {
+    constexpr int C = 3;
+    double xin, yin;
+    if (!affine_src_exact(m, x, y, h, w, xin, yin)) return false;
+    xin = __dsub_rn(xin, 0.5); yin = __dsub_rn(yin, 0.5);
+    const double xfl = floor(xin), yfl = floor(yin);
+    const int xi = (int)xfl, yi = (int)yfl;
+    const double dx = __dsub_rn(xin, xfl), dy = __dsub_rn(yin, yfl);
+    int xs[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) xs[t] = clampi(xi - 1 + t, 0, w - 1) * C;
+    double rowv[4][C];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {                               // a row outside the frame repeats the row before it
+        const int yy = yi - 1 + t;
+        const bool inr = t == 0 || (yy >= 0 && yy < h);
+        const u8* r = sp + (int64_t)clampi(yy, 0, h - 1) * rs;
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+            rowv[t][j] = inr ? cubic<PreciseArith>((double)r[xs[0] + j], (double)r[xs[1] + j], (double)r[xs[2] + j],
+                                                   (double)r[xs[3] + j], dx)
+                             : rowv[t > 0 ? t - 1 : 0][j];
+    }
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const double v = cubic<PreciseArith>(rowv[0][j], rowv[1][j], rowv[2][j], rowv[3][j], dy);
+        px[j] = v <= 0.0 ? (u8)0 : (v >= 255.0 ? (u8)255 : (u8)(int)v);
+    }
+    return true;
+}
+
 // cv2.convertScaleAbs before its saturating, round-half-even pack: |alpha * p + beta|
 __device__ __forceinline__ float scale_abs_value(float p, float alpha, float beta) { return fabsf(p * alpha + beta); }
 

@@ -745,3 +745,8 @@ def jpeg_compression(frames: torch.Tensor, quality=75, subsampling=-1) -> torch.
     out, bit-identical to Pillow's save and reopen."""
     from . import jpeg
     return jpeg.roundtrip(frames, quality, subsampling=subsampling)
+
+
+# Image.transform(AFFINE) and Image.rotate for lists of frames of different sizes, each entry with its own matrix or angle,
+# output size, filter and fill, in at most four launches: the functions of `affine_list` themselves
+from .affine_list import affine_list, affine_list_block, rotate_entries, rotate_list  # noqa: E402,F401

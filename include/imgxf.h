@@ -1343,6 +1343,83 @@ int imgxf_background_list_u8(const void* block_host, size_t block_bytes, const v
  * (for tests of the two-launch contract). */
 int imgxf_background_list_last_counts(int* counts);
 
+/* ---- Image.transform(size, AFFINE, m, resample, fillcolor) on a LIST of RGB frames of different sizes -----------------
+ * Entry k is bit for bit Image.fromarray(frame).transform((ow, oh), Image.AFFINE, m_k, filter_k, fillcolor=fill_k): every
+ * entry with its own frame, matrix, output size, filter (NEAREST, BILINEAR, BICUBIC, mixed freely in one call) and fill,
+ * uint8 RGB in and out, rows of the frames at any stride and byte offset, read in place; several entries may read one
+ * frame.  The HOST lays out one block
+ *     imgxf_affine_list_header | imgxf_affine_list_entry[n] | imgxf_affine_list_unit[n_units] | int32 tables
+ * which the caller copies to the device once.  The outputs are [oh][ow][3] uint8, contiguous, each at its entry's out_off
+ * (a multiple of 16) in ONE output buffer of out_bytes bytes.
+ *
+ * An entry takes one of four ROUTES, libImaging's own three NEAREST / filter paths less the one it is refused for:
+ *   SCALE     NEAREST with m1 == m3 == 0 (ImagingScaleAffine): per entry the tables xin[ow] at xtab and yin[oh] at ytab
+ *             (int32 indices into the block), built by the running double additions xo = m2 + m0 * 0.5; xo += m0 and
+ *             COORD(v) = v < 0 ? -1 : (int)v (stored as INT32_MAX from 2^31 up); [xmin, xmax) is the span of output columns
+ *             whose source column lies in the frame — the span libImaging copies; rows test their own yin;
+ *   FIXED     NEAREST otherwise (affine_fixed): fx[6] is the matrix in 16.16 fixed point, the half-pixel offsets folded
+ *             into fx[2] and fx[5], int arithmetic that wraps as C's does.  libImaging takes this path only where
+ *             |x m0 + y m1 + m2| < 32768 and |x m3 + y m4 + m5| < 32768 at (0, 0), (ow, 0), (0, oh), (ow, oh) and runs a
+ *             float loop elsewhere: such an entry is REFUSED by the layout (IMGXF_ERR_UNSUPPORTED), never served in
+ *             fixed point; so is one with a coefficient of magnitude 32768 or more, which no 16.16 int holds (C leaves
+ *             that conversion undefined);
+ *   BILINEAR  coordinates m0 (x + 0.5) + m1 (y + 0.5) + m2 in un-contracted fp64, the inside test on the doubles, clamped
+ *   BICUBIC   neighbours, libImaging's BILINEAR / BICUBIC macros in fp64 for every pixel, (UINT8)v truncation (BICUBIC
+ *             clipped first).
+ * A work unit is one tile of at most IMGXF_AFFINE_LIST_TILE_W x IMGXF_AFFINE_LIST_TILE_H output pixels of one entry (cut
+ * at the output's right and bottom edge) = one 256-lane workgroup, each lane four consecutive pixels of one row: a
+ * rotated gather of whole rows would have no locality.  The units are sorted by route (in the order above; within a
+ * route by entry, then row-major) and the header states each route's first unit and count: one launch per route present,
+ * four at most, so that NEAREST does not carry the registers of the fp64 routes. */
+enum {
+    IMGXF_AFFINE_LIST_SCALE = 0, IMGXF_AFFINE_LIST_FIXED = 1, IMGXF_AFFINE_LIST_BILINEAR = 2, IMGXF_AFFINE_LIST_BICUBIC = 3,
+    IMGXF_AFFINE_LIST_ROUTES = 4
+};
+#define IMGXF_AFFINE_LIST_TILE_W 64
+#define IMGXF_AFFINE_LIST_TILE_H 16
+typedef struct imgxf_affine_list_header {
+    int32_t n_entries, n_units;
+    int32_t entries_off, units_off, tables_off, total_bytes;   /* byte offsets of the sections, size of the block */
+    int32_t route_first[IMGXF_AFFINE_LIST_ROUTES];              /* units [route_first[r], route_first[r] + route_count[r]) */
+    int32_t route_count[IMGXF_AFFINE_LIST_ROUTES];              /* are route r's; the ranges follow each other from 0 */
+    int64_t out_bytes;          /* size of the output buffer: the end of the last entry's slot */
+} imgxf_affine_list_header;
+typedef struct imgxf_affine_list_entry {
+    uint64_t data;              /* DEVICE address of pixel (0, 0) of the frame; filled by the caller, as is row_stride
+                                   (bytes, >= 3 w) */
+    int64_t  row_stride;
+    int64_t  out_off;           /* byte offset of the entry's [oh][ow][3] output in the output buffer, a multiple of 16
+                                   (the layout packs them; a caller may respace them and out_bytes) */
+    int32_t  h, w;              /* the frame */
+    int32_t  oh, ow;            /* the output size */
+    int32_t  route;             /* IMGXF_AFFINE_LIST_* */
+    int32_t  xtab, ytab;        /* SCALE: word indices of xin[ow] and yin[oh]; 0 on the other routes */
+    int32_t  xmin, xmax;        /* SCALE: the output columns [xmin, xmax) have a source column inside the frame */
+    uint8_t  fill[4];           /* r, g, b, 0 */
+    double   m[6];              /* the matrix as the caller gave it (BILINEAR, BICUBIC read it) */
+    int32_t  fx[6];             /* FIXED: affine_fixed's 16.16 matrix; 0 on the other routes */
+} imgxf_affine_list_entry;
+typedef struct imgxf_affine_list_unit {
+    int32_t entry, x0, y0;      /* one tile: columns [x0, x0 + TILE_W) x rows [y0, y0 + TILE_H) of entry `entry`, cut at
+                                   the output's edges; x0 and y0 are multiples of the tile's sides */
+} imgxf_affine_list_unit;
+/* HOST half (no device work).  geometry: int32 [n][4] = (h, w, oh, ow) per entry; matrices: double [n][6]; filters: int32
+ * [n] of IMGXF_FILTER_*; fills: uint8 [n][3].  *block_bytes receives the block's size; block == NULL: only that.
+ * Errors: IMGXF_ERR_NULL; IMGXF_ERR_ARG for n < 0, a side outside 1..32767, an unknown filter, a matrix coefficient that is
+ * not finite; IMGXF_ERR_UNSUPPORTED for a NEAREST entry that libImaging takes out of 16.16 fixed point or that does not fit it (above);
+ * IMGXF_ERR_SHAPE for a block beyond 2 GiB; IMGXF_ERR_WORKSPACE when block_cap is too small. */
+int imgxf_affine_list_layout_host(const int32_t* geometry, const double* matrices, const int32_t* filters, const uint8_t* fills,
+                                  int n, void* block, size_t block_cap, size_t* block_bytes);
+/* The launches: block_host is the caller's host copy of the block, block_bytes its size, block_dev the same bytes on the
+ * device (8-byte aligned), out the output buffer (16-byte aligned) of out_bytes bytes.  Before any launch every record and
+ * unit is checked against its frame, the block, the tables and the output buffer, so that they bound every address the
+ * kernels form (IMGXF_ERR_ARG / IMGXF_ERR_SHAPE / IMGXF_ERR_NULL, never a launch); nothing past block_bytes is read.  At
+ * most one launch per route present; a block without units launches nothing.  No allocation, no synchronisation. */
+int imgxf_affine_list_u8(const void* block_host, size_t block_bytes, const void* block_dev, void* out, size_t out_bytes,
+                         void* stream);
+/* Kernel launches the last imgxf_affine_list_u8 of this thread queued (for tests of the launch count). */
+int imgxf_affine_list_last_launches(int* launches);
+
 #ifdef __cplusplus
 }
 #endif
