@@ -224,6 +224,10 @@ SIGNATURES = {
                                       C.POINTER(C.c_size_t)],
     "imgxf_affine_list_u8": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     "imgxf_affine_list_last_launches": [C.POINTER(C.c_int)],
+    "imgxf_transform_list_layout_host": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)],
+    "imgxf_transform_list_u8": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "imgxf_transform_list_last_launches": [C.POINTER(C.c_int)],
 }
 
 

@@ -112,25 +112,9 @@ __global__ __launch_bounds__(AFL_THREADS) void affine_list_kernel(const u8* __re
                 if (ok) p = (u32)px[0] | ((u32)px[1] << 8) | ((u32)px[2] << 16);
             }
         }
-        // pixel k is bytes 3k .. 3k + 2 of the lane's 12
-        if (k == 0) o[0] = p;
-        if (k == 1) { o[0] |= p << 24; o[1] = p >> 8; }
-        if (k == 2) { o[1] |= p << 16; o[2] = p >> 16; }
-        if (k == 3) o[2] |= p << 8;
+        rgb4_put(o, k, p);
     }
-    u8* dp = out + e.out_off + ((int64_t)y * ow + x0) * 3;
-    const int npx = min(4, ow - x0);
-    if (npx == 4 && (((uintptr_t)dp) & 3) == 0) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) ((u32*)dp)[q] = o[q];
-    } else {
-        for (int b = 0; b < npx * 3; ++b) {
-            u32 v = 0;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) if ((b >> 2) == q) v = o[q];
-            dp[b] = (u8)(v >> (8 * (b & 3)));
-        }
-    }
+    rgb4_store(out + e.out_off + ((int64_t)y * ow + x0) * 3, o, min(4, ow - x0));
 }
 
 // The host checks of imgxf_affine_list_u8 on the block alone, before any device is needed: IMGXF_OK when its records bound

@@ -64,23 +64,42 @@ __device__ __forceinline__ void bicubic_row_exact_px(const u8* row, int sw, bool
     }
 }
 
-// libImaging's fp64 sequences for one RGB pixel of a general affine transform, BILINEAR and BICUBIC (affine_transform +
-// bilinear_filter / bicubic_filter of Geometry.c), every operation rounded on its own whatever the file's contraction
-// flags: sp = pixel (0, 0) of the h x w source, rs its row stride in bytes.  false: (x, y) maps outside the source (the
-// test is on the doubles, before any conversion to int) and px is untouched — the caller stores its fill.
+// libImaging's fp64 sequences for one RGB pixel of Image.transform (Geometry.c: affine_transform, perspective_transform,
+// quad_transform + bilinear_filter / bicubic_filter), every operation rounded on its own whatever the file's contraction
+// flags.  The coordinate statements (`*_src_exact`) give the source position (xs, ys) of an output pixel; the filter bodies
+// (`*_exact_at`) take it: sp = pixel (0, 0) of the h x w source, rs its row stride in bytes.  false: the position lies
+// outside the source (the test is on the doubles, before any conversion to int) and px is untouched — the caller stores its
+// fill.
+__device__ __forceinline__ bool src_inside(double xs, double ys, int h, int w) {
+    return xs >= 0.0 && xs < (double)w && ys >= 0.0 && ys < (double)h;
+}
 __device__ __forceinline__ bool affine_src_exact(const double* m, int x, int y, int h, int w, double& xin, double& yin) {
     const double xc = (double)x + 0.5, yc = (double)y + 0.5;
     xin = __dadd_rn(__dadd_rn(__dmul_rn(m[0], xc), __dmul_rn(m[1], yc)), m[2]);
     yin = __dadd_rn(__dadd_rn(__dmul_rn(m[3], xc), __dmul_rn(m[4], yc)), m[5]);
-    return xin >= 0.0 && xin < (double)w && yin >= 0.0 && yin < (double)h;
+    return src_inside(xin, yin, h, w);
+}
+// perspective_transform at the pixel centre (xin, yin): xs = ((a0 xin + a1 yin) + a2) / d, ys = ((a3 xin + a4 yin) + a5) / d,
+// d = (a6 xin + a7 yin) + 1, two divisions (a reciprocal and two products give other bits).  a1y, a4y, a7y: the products
+// a1 yin, a4 yin, a7 yin, which a caller that walks a row computes once (the same doubles)
+__device__ __forceinline__ void perspective_src_exact(const double* a, double xin, double a1y, double a4y, double a7y, double& xs,
+                                                      double& ys) {
+    const double d = __dadd_rn(__dadd_rn(__dmul_rn(a[6], xin), a7y), 1.0);
+    xs = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(a[0], xin), a1y), a[2]), d);
+    ys = __ddiv_rn(__dadd_rn(__dadd_rn(__dmul_rn(a[3], xin), a4y), a[5]), d);
+}
+// quad_transform: xs = ((a0 + a1 xin) + a2 yin) + (a3 xin) yin, ys = ((a4 + a5 xin) + a6 yin) + (a7 xin) yin.  a2y, a6y: the
+// products a2 yin and a6 yin of the row
+__device__ __forceinline__ void quad_src_exact(const double* a, double xin, double yin, double a2y, double a6y, double& xs,
+                                               double& ys) {
+    xs = __dadd_rn(__dadd_rn(__dadd_rn(a[0], __dmul_rn(a[1], xin)), a2y), __dmul_rn(__dmul_rn(a[3], xin), yin));
+    ys = __dadd_rn(__dadd_rn(__dadd_rn(a[4], __dmul_rn(a[5], xin)), a6y), __dmul_rn(__dmul_rn(a[7], xin), yin));
 }
 // BILINEAR(v, a, b, d) = a + (b - a) * d
 __device__ __forceinline__ double lerp_exact(double a, double b, double d) { return __dadd_rn(a, __dmul_rn(__dsub_rn(b, a), d)); }
-__device__ __forceinline__ bool affine_bilinear_exact_px(const u8* sp, int64_t rs, int h, int w, const double* m, int x, int y,
-                                                         u8 (&px)[3]) {
+__device__ __forceinline__ bool bilinear_exact_at(const u8* sp, int64_t rs, int h, int w, double xin, double yin, u8 (&px)[3]) {
     constexpr int C = 3;
-    double xin, yin;
-    if (!affine_src_exact(m, x, y, h, w, xin, yin)) return false;
+    if (!src_inside(xin, yin, h, w)) return false;
     xin = __dsub_rn(xin, 0.5); yin = __dsub_rn(yin, 0.5);
     const double xfl = floor(xin), yfl = floor(yin);
     const int xi = (int)xfl, yi = (int)yfl;
@@ -97,11 +116,9 @@ __device__ __forceinline__ bool affine_bilinear_exact_px(const u8* sp, int64_t r
     }
     return true;
 }
-__device__ __forceinline__ bool affine_bicubic_exact_px(const u8* sp, int64_t rs, int h, int w, const double* m, int x, int y,
-                                                        u8 (&px)[3]) {
+__device__ __forceinline__ bool bicubic_exact_at(const u8* sp, int64_t rs, int h, int w, double xin, double yin, u8 (&px)[3]) {
     constexpr int C = 3;
-    double xin, yin;
-    if (!affine_src_exact(m, x, y, h, w, xin, yin)) return false;
+    if (!src_inside(xin, yin, h, w)) return false;
     xin = __dsub_rn(xin, 0.5); yin = __dsub_rn(yin, 0.5);
     const double xfl = floor(xin), yfl = floor(yin);
     const int xi = (int)xfl, yi = (int)yfl;
@@ -127,6 +144,40 @@ __device__ __forceinline__ bool affine_bicubic_exact_px(const u8* sp, int64_t rs
         px[j] = v <= 0.0 ? (u8)0 : (v >= 255.0 ? (u8)255 : (u8)(int)v);
     }
     return true;
+}
+// ... for output pixel (x, y) of the affine matrix m
+__device__ __forceinline__ bool affine_bilinear_exact_px(const u8* sp, int64_t rs, int h, int w, const double* m, int x, int y,
+                                                         u8 (&px)[3]) {
+    double xin, yin;
+    return affine_src_exact(m, x, y, h, w, xin, yin) && bilinear_exact_at(sp, rs, h, w, xin, yin, px);
+}
+__device__ __forceinline__ bool affine_bicubic_exact_px(const u8* sp, int64_t rs, int h, int w, const double* m, int x, int y,
+                                                        u8 (&px)[3]) {
+    double xin, yin;
+    return affine_src_exact(m, x, y, h, w, xin, yin) && bicubic_exact_at(sp, rs, h, w, xin, yin, px);
+}
+
+// A lane's four consecutive RGB pixels as the 12 bytes of three dwords (the list warps: rows of 3 ow bytes).  rgb4_put:
+// pixel k (r | g << 8 | b << 16) into bytes 3k .. 3k + 2; rgb4_store: the first npx pixels to dp, as dwords where all four
+// are there and dp allows, bytes elsewhere
+__device__ __forceinline__ void rgb4_put(u32 (&o)[3], int k, u32 p) {
+    if (k == 0) o[0] = p;
+    if (k == 1) { o[0] |= p << 24; o[1] = p >> 8; }
+    if (k == 2) { o[1] |= p << 16; o[2] = p >> 16; }
+    if (k == 3) o[2] |= p << 8;
+}
+__device__ __forceinline__ void rgb4_store(u8* dp, const u32 (&o)[3], int npx) {
+    if (npx == 4 && (((uintptr_t)dp) & 3) == 0) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) ((u32*)dp)[q] = o[q];
+    } else {
+        for (int b = 0; b < npx * 3; ++b) {
+            u32 v = 0;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) if ((b >> 2) == q) v = o[q];
+            dp[b] = (u8)(v >> (8 * (b & 3)));
+        }
+    }
 }
 
 // cv2.convertScaleAbs before its saturating, round-half-even pack: |alpha * p + beta|

@@ -750,3 +750,7 @@ def jpeg_compression(frames: torch.Tensor, quality=75, subsampling=-1) -> torch.
 # Image.transform(AFFINE) and Image.rotate for lists of frames of different sizes, each entry with its own matrix or angle,
 # output size, filter and fill, in at most four launches: the functions of `affine_list` themselves
 from .affine_list import affine_list, affine_list_block, rotate_entries, rotate_list  # noqa: E402,F401
+
+# Image.transform(PERSPECTIVE | QUAD) and torchvision's PIL-path F.perspective for lists of frames of different sizes, in at
+# most six launches: the functions of `transform_list` themselves
+from .transform_list import perspective_list, transform_list, transform_list_block  # noqa: E402,F401

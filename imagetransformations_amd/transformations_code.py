@@ -17,6 +17,7 @@ from PIL import Image
 
 from . import batched, numpy_stream, ops, staging
 from . import transformation as T
+from ._perspective import _perspective_coeffs, _perspective_endpoints  # noqa: F401  (shared with transform_list)
 from .transformation import (_download, _upload, apply_blur, apply_brightness, apply_contrast,  # noqa: F401
                              apply_gaussian_noise, apply_rotation, apply_scale, apply_shear,
                              apply_translation)
@@ -41,31 +42,6 @@ def rand_crop(img: Image.Image) -> Image.Image:
 def apply_random_zoom(img: Image.Image, scale_factor: float) -> Image.Image:
     """Zoom transformation (1.0 to 1.1 range) = apply_scale (:50-52)."""
     return apply_scale(img, scale_factor)
-
-
-def _perspective_endpoints(width: int, height: int, distortion_scale: float):
-    """RandomPerspective.get_params: eight torch.randint draws from torch's global CPU generator,
-    in torchvision's order (top-left x, y; top-right; bottom-right; bottom-left)."""
-    def randint(lo, hi):
-        return int(torch.randint(lo, hi, size=(1,)).item())
-    half_height, half_width = height // 2, width // 2
-    dw, dh = int(distortion_scale * half_width), int(distortion_scale * half_height)
-    topleft = [randint(0, dw + 1), randint(0, dh + 1)]
-    topright = [randint(width - dw - 1, width), randint(0, dh + 1)]
-    botright = [randint(width - dw - 1, width), randint(height - dh - 1, height)]
-    botleft = [randint(0, dw + 1), randint(height - dh - 1, height)]
-    startpoints = [[0, 0], [width - 1, 0], [width - 1, height - 1], [0, height - 1]]
-    return startpoints, [topleft, topright, botright, botleft]
-
-
-def _perspective_coeffs(startpoints, endpoints):
-    """torchvision F._get_perspective_coeffs: fp64 least squares (gels), cast to fp32."""
-    a = torch.zeros(2 * len(startpoints), 8, dtype=torch.float64)
-    for i, (p1, p2) in enumerate(zip(endpoints, startpoints)):
-        a[2 * i, :] = torch.tensor([p1[0], p1[1], 1, 0, 0, 0, -p2[0] * p1[0], -p2[0] * p1[1]], dtype=torch.float64)
-        a[2 * i + 1, :] = torch.tensor([0, 0, 0, p1[0], p1[1], 1, -p2[1] * p1[0], -p2[1] * p1[1]], dtype=torch.float64)
-    b = torch.tensor(startpoints, dtype=torch.float64).view(8)
-    return torch.linalg.lstsq(a, b, driver="gels").solution.to(torch.float32).tolist()
 
 
 def draw_perspective_coeffs(width: int, height: int, distortion_scale: float):

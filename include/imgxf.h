@@ -1420,6 +1420,82 @@ int imgxf_affine_list_u8(const void* block_host, size_t block_bytes, const void*
 /* Kernel launches the last imgxf_affine_list_u8 of this thread queued (for tests of the launch count). */
 int imgxf_affine_list_last_launches(int* launches);
 
+/* ---- Image.transform(size, PERSPECTIVE | QUAD, data, resample, fillcolor) on a LIST of RGB frames of different sizes ---
+ * Entry k is bit for bit Image.fromarray(frame).transform((ow, oh), method_k, a_k, filter_k, fillcolor=fill_k): every entry
+ * with its own frame, method, eight coefficients, output size, filter (NEAREST, BILINEAR, BICUBIC) and fill, all mixed
+ * freely in one call; frames, outputs and the block protocol as for the affine list above.  The HOST lays out one block
+ *     imgxf_transform_list_header | imgxf_transform_list_entry[n] | imgxf_transform_list_unit[n_units]
+ * (no tables: tables_off states the end of the units).
+ *
+ * The statements are libImaging's ImagingGenericTransform (Geometry.c), every operation rounded on its own in fp64, at
+ * the pixel centre xin = x + 0.5, yin = y + 0.5:
+ *   PERSPECTIVE  d = (a6 xin + a7 yin) + 1;  xs = ((a0 xin + a1 yin) + a2) / d;  ys = ((a3 xin + a4 yin) + a5) / d
+ *   QUAD         xs = ((a0 + a1 xin) + a2 yin) + (a3 xin) yin;  ys = ((a4 + a5 xin) + a6 yin) + (a7 xin) yin
+ *                (a: what Image.transform's Python layer makes of the four corners, not the corners themselves)
+ *   NEAREST      COORD(v) = v < 0 ? -1 : (int)v on xs and ys (from 2^31 up: outside), then the in-frame test;
+ *   BILINEAR,    the in-frame test 0 <= xs < w && 0 <= ys < h on the doubles, then libImaging's fp64 filters as on the
+ *   BICUBIC      affine list.
+ * A pixel that fails its test is the entry's fill.  The ROUTE of an entry is 3 method + filter: six kernels, so that
+ * NEAREST does not carry the registers of the fp64 filters and PERSPECTIVE alone carries the divisions.
+ *
+ * REFUSED (IMGXF_ERR_UNSUPPORTED), because libImaging's own result is not defined there: a coefficient of magnitude above
+ * IMGXF_TRANSFORM_LIST_MAX_COEFF — below it no product or sum of the statements overflows at sides up to 32767
+ * (|a xin yin| <= 1e290 * 32767^2 < 1.1e299, four such terms < DBL_MAX) — and a PERSPECTIVE entry whose denominator d,
+ * evaluated by the statements above, is not strictly of one sign at the four corner pixel centres (0.5 | ow - 0.5,
+ * 0.5 | oh - 0.5): the warp's horizon crosses the output.  Every rounded step of d is monotone in xin and in yin, so the
+ * corners bound d at every pixel: a served entry never divides by zero and never makes a NaN. */
+enum { IMGXF_TRANSFORM_PERSPECTIVE = 0, IMGXF_TRANSFORM_QUAD = 1, IMGXF_TRANSFORM_METHODS = 2 };
+#define IMGXF_TRANSFORM_LIST_ROUTES 6          /* route = 3 * method + IMGXF_FILTER_* (NEAREST 0, BILINEAR 1, BICUBIC 2) */
+#define IMGXF_TRANSFORM_LIST_TILE_W 64
+#define IMGXF_TRANSFORM_LIST_TILE_H 16
+#define IMGXF_TRANSFORM_LIST_MAX_COEFF 1e290
+typedef struct imgxf_transform_list_header {
+    int32_t n_entries, n_units;
+    int32_t entries_off, units_off, tables_off, total_bytes;   /* byte offsets of the sections (tables_off: the end of the
+                                                                   units), size of the block */
+    int32_t route_first[IMGXF_TRANSFORM_LIST_ROUTES];           /* units [route_first[r], route_first[r] + route_count[r]) */
+    int32_t route_count[IMGXF_TRANSFORM_LIST_ROUTES];           /* are route r's; the ranges follow each other from 0 */
+    int64_t out_bytes;          /* size of the output buffer: the end of the last entry's slot */
+} imgxf_transform_list_header;
+typedef struct imgxf_transform_list_entry {
+    uint64_t data;              /* DEVICE address of pixel (0, 0) of the frame; filled by the caller, as is row_stride
+                                   (bytes, >= 3 w) */
+    int64_t  row_stride;
+    int64_t  out_off;           /* byte offset of the entry's [oh][ow][3] output in the output buffer, a multiple of 16
+                                   (the layout packs them; a caller may respace them and out_bytes) */
+    int32_t  h, w;              /* the frame */
+    int32_t  oh, ow;            /* the output size */
+    int32_t  route;             /* 3 * IMGXF_TRANSFORM_* + IMGXF_FILTER_* */
+    uint8_t  fill[4];           /* r, g, b, 0 */
+    double   a[8];              /* the coefficients as the caller gave them */
+} imgxf_transform_list_entry;
+typedef struct imgxf_transform_list_unit {
+    int32_t entry, x0, y0;      /* one tile: columns [x0, x0 + TILE_W) x rows [y0, y0 + TILE_H) of entry `entry`, cut at
+                                   the output's edges; x0 and y0 are multiples of the tile's sides */
+} imgxf_transform_list_unit;
+/* HOST half (no device work).  geometry: int32 [n][4] = (h, w, oh, ow) per entry; methods: int32 [n] of IMGXF_TRANSFORM_*;
+ * coeffs: double [n][8]; filters: int32 [n] of IMGXF_FILTER_*; fills: uint8 [n][3].  *block_bytes receives the block's size;
+ * block == NULL: only that.  Errors: IMGXF_ERR_NULL for a null argument; IMGXF_ERR_ARG for n < 0, a side outside 1..32767, an
+ * unknown method or filter, a coefficient that is not finite; IMGXF_ERR_UNSUPPORTED for a coefficient above
+ * IMGXF_TRANSFORM_LIST_MAX_COEFF in magnitude or a PERSPECTIVE denominator that is zero at a corner pixel centre or changes
+ * sign between two (above); IMGXF_ERR_SHAPE for a block beyond 2 GiB or more than 2^31 - 1 units; IMGXF_ERR_WORKSPACE when
+ * block_cap is too small. */
+int imgxf_transform_list_layout_host(const int32_t* geometry, const int32_t* methods, const double* coeffs, const int32_t* filters,
+                                     const uint8_t* fills, int n, void* block, size_t block_cap, size_t* block_bytes);
+/* The launches: block_host is the caller's host copy of the block, block_bytes its size, block_dev the same bytes on the
+ * device (8-byte aligned), out the output buffer (16-byte aligned) of out_bytes bytes.  Before any launch every record and
+ * unit is checked: IMGXF_ERR_NULL for a null block or a frame without an address; IMGXF_ERR_SHAPE for a frame or an output
+ * with a side outside 1..32767 or a row_stride below 3 w; IMGXF_ERR_ARG for sections that do not follow from the counts
+ * or leave the block, route ranges that do not follow each other and cover the units, an unknown route, an output slot
+ * that is misaligned or leaves the buffer, a unit outside its entry, off the tile grid or in another route's range, or a
+ * misaligned device pointer; IMGXF_ERR_UNSUPPORTED for coefficients the layout would have refused.  None of them launches
+ * anything, and nothing past block_bytes is read.  At most one launch per route present, six at most; a block without
+ * units launches nothing.  No allocation, no synchronisation. */
+int imgxf_transform_list_u8(const void* block_host, size_t block_bytes, const void* block_dev, void* out, size_t out_bytes,
+                            void* stream);
+/* Kernel launches the last imgxf_transform_list_u8 of this thread queued (for tests of the launch count). */
+int imgxf_transform_list_last_launches(int* launches);
+
 #ifdef __cplusplus
 }
 #endif
