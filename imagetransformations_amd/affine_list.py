@@ -12,6 +12,7 @@ import torch
 
 from . import _ffi as F
 from . import _list_block
+from ._affine_fixed import FIXED_TEXT as _FIXED_TEXT, check_fixed, fits_fixed, refusal  # noqa: F401
 
 NEAREST, BILINEAR, BICUBIC = F.FILTER_NEAREST, F.FILTER_BILINEAR, F.FILTER_BICUBIC      # ops.NEAREST, ops.BILINEAR, ops.BICUBIC
 TILE_W, TILE_H = 64, 16                                                                  # IMGXF_AFFINE_LIST_TILE_*
@@ -24,8 +25,6 @@ _ENTRY = np.dtype([("data", "<u8"), ("row_stride", "<i8"), ("out_off", "<i8")] +
 _UNIT = np.dtype([(k, "<i4") for k in ("entry", "x0", "y0")])                            # imgxf_affine_list_*
 
 _BY_NAME = {"NEAREST": NEAREST, "BILINEAR": BILINEAR, "BICUBIC": BICUBIC}
-_FIXED_TEXT = ("Pillow leaves 16.16 fixed point for this NEAREST warp (libImaging's check_fixed fails at a corner of the "
-               "output and its float loop runs instead); this call does not follow it there")
 
 
 def _filter(value) -> int:
@@ -90,32 +89,14 @@ def _matrices(matrices) -> np.ndarray:
     return a
 
 
-def check_fixed(m, ow: int, oh: int) -> bool:
-    """libImaging's check_fixed at the four corners of an (ow, oh) output: where it fails, a NEAREST warp with m1 or m3
-    non-zero runs libImaging's float loop instead of the 16.16 `affine_fixed`."""
-    def at(x, y):
-        return abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0
-    return at(0, 0) and at(ow, oh) and at(0, oh) and at(ow, 0)
-
-
-def fits_fixed(m) -> bool:
-    """Whether the six coefficients of libImaging's 16.16 matrix (the half-pixel offsets folded into m2 and m5) fit the int
-    they are converted to: |c| < 32768.  check_fixed alone lets |m0| up to 65536 / ow through, and C leaves the conversion of
-    such a double undefined."""
-    return all(abs(c * 65536.0 + 0.5) < 2147483648.0
-               for c in (m[0], m[1], m[2] + m[0] * 0.5 + m[1] * 0.5, m[3], m[4], m[5] + m[3] * 0.5 + m[4] * 0.5))
-
-
 def _check_outputs(matrices, sizes, filters) -> None:
     """What needs the output sizes: sides 1 .. 32767, and the NEAREST entries Pillow takes out of fixed point."""
     if len(sizes) and (sizes.min() < 1 or sizes.max() > 32767):
         raise ValueError("sizes values (width, height) must lie in 1 .. 32767")
     for i in np.flatnonzero((filters == NEAREST) & ((matrices[:, 1] != 0) | (matrices[:, 3] != 0))).tolist():
-        if not check_fixed(matrices[i].tolist(), int(sizes[i, 0]), int(sizes[i, 1])):
-            raise ValueError(f"entry {i}: {_FIXED_TEXT} (matrix {tuple(matrices[i].tolist())}, size {tuple(sizes[i].tolist())})")
-        if not fits_fixed(matrices[i].tolist()):
-            raise ValueError(f"entry {i}: a coefficient of this NEAREST warp does not fit 16.16 fixed point (magnitude 32768 or "
-                             f"more), where libImaging's conversion is undefined: not served (matrix {tuple(matrices[i].tolist())})")
+        why = refusal(matrices[i].tolist(), int(sizes[i, 0]), int(sizes[i, 1]))
+        if why:
+            raise ValueError(f"entry {i}: {why}")
 
 
 def layout(geometry, matrices, filters, fills, pinned: bool = False):

@@ -48,23 +48,7 @@ static void afl_scale_axis(double a, double c, int n, int in, int32_t* tab, int*
     }
 }
 
-// libImaging's check_fixed at the four corners of the output: where it fails ImagingTransformAffine leaves affine_fixed
-static inline bool afl_check_fixed(const double* m, int ow, int oh) {
-    auto at = [&](double x, double y) {
-        return fabs(x * m[0] + y * m[1] + m[2]) < 32768.0 && fabs(x * m[3] + y * m[4] + m[5]) < 32768.0;
-    };
-    return at(0, 0) && at(ow, oh) && at(0, oh) && at(ow, 0);
-}
-
-// ... and whether every coefficient of affine_fixed_matrix fits the int that libImaging converts it to (the conversion of a
-// double outside int's range is undefined in C: check_fixed alone lets |m0| up to 65536 / ow through)
-static inline bool afl_fits_fixed(const double* m) {
-    const double v[6] = {m[0], m[1], m[2] + m[0] * 0.5 + m[1] * 0.5, m[3], m[4], m[5] + m[3] * 0.5 + m[4] * 0.5};
-    for (double c : v)
-        if (!(fabs(c * 65536.0 + 0.5) < 2147483648.0)) return false;
-    return true;
-}
-
+// (where libImaging leaves affine_fixed: affine_check_fixed / affine_fits_fixed, imgxf_common.h)
 static inline int afl_route(const double* m, int filter) {
     if (filter == IMGXF_FILTER_BILINEAR) return IMGXF_AFFINE_LIST_BILINEAR;
     if (filter == IMGXF_FILTER_BICUBIC) return IMGXF_AFFINE_LIST_BICUBIC;
@@ -188,7 +172,7 @@ IMGXF_API int imgxf_affine_list_layout_host(const int32_t* geometry, const doubl
         for (int k = 0; k < 6; ++k)
             if (!isfinite(m[k])) return IMGXF_ERR_ARG;
         route[i] = afl_route(m, filters[i]);
-        if (route[i] == IMGXF_AFFINE_LIST_FIXED && !(afl_check_fixed(m, g.ow, g.oh) && afl_fits_fixed(m))) return IMGXF_ERR_UNSUPPORTED;
+        if (route[i] == IMGXF_AFFINE_LIST_FIXED && !(affine_check_fixed(m, g.ow, g.oh) && affine_fits_fixed(m))) return IMGXF_ERR_UNSUPPORTED;
         if (route[i] == IMGXF_AFFINE_LIST_SCALE) table_words += (size_t)g.ow + g.oh;
         count[route[i]] += afl_tiles(g.oh, g.ow);
     }

@@ -2,7 +2,7 @@
 // call, no look at the environment (run_affine hands it the IMGXF_AFFINE_* knobs).  It fills an AffinePlan with the
 // finished AffineParams and one or two AffineLaunch records; launch_affine() in affine.hip turns a record into the
 // kernel instantiation with one switch.  DESIGN.md §3.2d is this file as a table; tests/affine_route.py restates the
-// bilinear and bicubic rules for the GPU tests and tests/test_affine_route_host.py holds the two together.
+// rules of the three filters for the GPU tests and tests/test_affine_route_host.py holds the two together.
 //
 // Order of attempts (part of the behaviour):
 //   NEAREST   wq -> dma 32x64 / 32x32 -> lds 49 / 65 / 97 -> global
@@ -341,11 +341,15 @@ inline int plan_affine(const View& s, const View& d, const double* m, int filter
                        const AffineKnobs& K, AffinePlan& R) {
     AffineParams& P = R.P;
     memset(&P, 0, sizeof(P));
+    R.n = 0;
+    R.list.n = 0;
+    // NEAREST is libImaging's affine_fixed.  Where check_fixed fails at a corner of the output Pillow walks the coordinates
+    // in doubles instead, and the 16.16 integers (which would wrap 32 bits there, sometimes back inside the source) give
+    // other pixels: refused, like a coefficient that fits no int, by the rule of the list pass (affine_list.hip)
+    if (filter == IMGXF_FILTER_NEAREST && !(affine_check_fixed(m, d.w, d.h) && affine_fits_fixed(m))) return IMGXF_ERR_UNSUPPORTED;
     for (int i = 0; i < 6; ++i) P.m[i] = m[i];
     affine_fixed_matrix(m, P.fx);
     if (fill) for (int j = 0; j < d.c; ++j) P.fill[j] = fill[j];
-    R.n = 0;
-    R.list.n = 0;
     const bool pr = precise || filter == IMGXF_FILTER_NEAREST;
     if (filter == IMGXF_FILTER_NEAREST && s.c == 3 && !K.no_lds && aligned(s, 4) && plan_nearest_tiles(s, d, K, R)) return IMGXF_OK;
     const bool fixed_ok = plan_fixed_point(d, m, P);

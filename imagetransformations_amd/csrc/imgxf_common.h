@@ -137,6 +137,22 @@ inline void affine_fixed_matrix(const double* m, int fx[6]) {
     fx[2] = fix16(m[2] + m[0] * 0.5 + m[1] * 0.5);
     fx[5] = fix16(m[5] + m[3] * 0.5 + m[4] * 0.5);
 }
+// libImaging's check_fixed at the four corners of the output: where it fails ImagingTransformAffine leaves affine_fixed
+// and walks the coordinates in doubles, which the 16.16 kernels do not follow (imgxf_affine_u8 and the list pass refuse)
+inline bool affine_check_fixed(const double* m, int ow, int oh) {
+    auto at = [&](double x, double y) {
+        return fabs(x * m[0] + y * m[1] + m[2]) < 32768.0 && fabs(x * m[3] + y * m[4] + m[5]) < 32768.0;
+    };
+    return at(0, 0) && at(ow, oh) && at(0, oh) && at(ow, 0);
+}
+// ... and whether every coefficient of affine_fixed_matrix fits the int that libImaging converts it to (the conversion of a
+// double outside int's range is undefined in C: check_fixed alone lets |m0| up to 65536 / ow through)
+inline bool affine_fits_fixed(const double* m) {
+    const double v[6] = {m[0], m[1], m[2] + m[0] * 0.5 + m[1] * 0.5, m[3], m[4], m[5] + m[3] * 0.5 + m[4] * 0.5};
+    for (double c : v)
+        if (!(fabs(c * 65536.0 + 0.5) < 2147483648.0)) return false;
+    return true;
+}
 
 inline int launch_status() {
     hipError_t e = hipGetLastError();

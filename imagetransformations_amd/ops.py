@@ -14,6 +14,7 @@ from typing import Sequence
 
 import torch
 
+from . import _affine_fixed
 from . import _ffi as F
 
 NEAREST, BILINEAR, BICUBIC = F.FILTER_NEAREST, F.FILTER_BILINEAR, F.FILTER_BICUBIC   # affine() filter codes
@@ -191,7 +192,9 @@ def affine(t: torch.Tensor, matrix: Sequence[float], out_size: tuple[int, int] |
     """Image.transform(out_size, AFFINE, matrix, resample, fillcolor=fillcolor).
 
     `out_size` is (width, height) like Pillow.  NEAREST with a pure scale/translate
-    matrix follows libImaging's ImagingScaleAffine; everything else its generic path."""
+    matrix follows libImaging's ImagingScaleAffine; everything else its generic path.  Any other
+    NEAREST matrix is libImaging's 16.16 `affine_fixed`; where Pillow itself leaves it (check_fixed
+    fails at a corner of the output) the call raises ValueError instead of returning other pixels."""
     t = _check_u8(t)
     h, w, c = _hwc(t)
     ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
@@ -205,6 +208,10 @@ def affine(t: torch.Tensor, matrix: Sequence[float], out_size: tuple[int, int] |
         _launch(t, "imgxf_affine_scale_nearest_u8", F.vp(F.view_of(t)), F.vp(F.view_of(out)), F.f64_array(m),
                fill, ws.data_ptr(), ws.numel() * 4)
         return out
+    if resample == NEAREST:                     # where libImaging leaves affine_fixed the 16.16 kernels would give other pixels
+        why = _affine_fixed.refusal(m, ow, oh)
+        if why:
+            raise ValueError(why)
     f32 = None
     if return_f32:
         f32 = torch.empty(out.shape, dtype=torch.float32, device=t.device)

@@ -139,7 +139,11 @@ int imgxf_sobel_plan_host(const imgxf_view* src, const imgxf_view* dst, int* out
  * benchmark configs[3].  m[6]: HOST pointer, destination->source matrix exactly as Pillow
  * takes it.  dst gives the output size.  fill[4]: HOST pointer (per channel), NULL = zeros.
  * NEAREST reproduces libImaging affine_fixed (16.16) bit-exactly when m[1]!=0 or m[3]!=0;
- * pure scale/translate NEAREST matrices need imgxf_affine_scale_nearest_u8.
+ * pure scale/translate NEAREST matrices need imgxf_affine_scale_nearest_u8.  Where libImaging
+ * itself leaves affine_fixed — check_fixed fails at a corner of the output, |x m0 + y m1 + m2|
+ * or |x m3 + y m4 + m5| >= 32768 at (0,0), (w,0), (0,h), (w,h), and its double loop runs — or a
+ * coefficient of the 16.16 matrix fits no int, NEAREST returns IMGXF_ERR_UNSUPPORTED and
+ * launches nothing (the rule of imgxf_affine_list_u8).
  * precise != 0: coordinates and interpolation in fp64 (bit-exact with Pillow);
  * precise == 0: fp64 coordinates, fp32 interpolation (<=1e-5 relative before truncation).
  * `dst_f32` (optional, may be NULL; BILINEAR/BICUBIC only): float view of dst's n,h,w,c that

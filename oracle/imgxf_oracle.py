@@ -472,12 +472,26 @@ def _fill_array(oh, ow, c, fill, dtype=np.uint8):
     return out
 
 
+def _check_fixed(m, ow, oh):
+    """libImaging's check_fixed at the four corners of the output (Geometry.c, ImagingTransformAffine)."""
+    def at(x, y):
+        return abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0
+    return at(0, 0) and at(ow, oh) and at(0, oh) and at(ow, 0)
+
+
+def _coord(v):
+    """libImaging's COORD(v) = v < 0 ? -1 : (int)v; beyond int's range (undefined in C) any value outside an image serves."""
+    return int(v) if 0.0 <= v < 2147483648.0 else (-1 if not v >= 0.0 else 2147483647)
+
+
 def affine_nearest(img, out_size, m, fill=None):
     """Image.transform(size, AFFINE, m, NEAREST, fillcolor=fill).
 
     Rotations/shears (m1 or m3 non-zero) go through `affine_fixed` (16.16 fixed
-    point); pure scale/translate matrices go through `ImagingScaleAffine`, which
-    walks the source coordinate by repeated double additions."""
+    point) where libImaging's check_fixed holds at the four corners of the output
+    and through its double loop where it does not; pure scale/translate matrices go
+    through `ImagingScaleAffine`, which walks the source coordinate by repeated
+    double additions."""
     a, was2d = _as3d(img)
     h, w, c = a.shape
     ow, oh = out_size
@@ -503,6 +517,24 @@ def affine_nearest(img, out_size, m, fill=None):
             span = np.arange(xmin, xmax)
             sub = a[yin[ys]][:, np.clip(xin[span], 0, w - 1)]
             out[np.ix_(ys, span)] = sub
+        return out[:, :, 0] if was2d else out
+    if not _check_fixed(m, ow, oh):
+        # libImaging's affine_transform with nearest_filter8 / 32RGB: the coordinates are walked in doubles by serial
+        # additions (per pixel xx += a0, per row xo += a1), COORD(v) = v < 0 ? -1 : (int)v.  (A double beyond int's range
+        # converts to INT_MIN in C on x86 and to a huge int here: outside the image either way.)
+        m = [float(v) for v in m]
+        xo = m[2] + m[1] * 0.5 + m[0] * 0.5
+        yo = m[5] + m[4] * 0.5 + m[3] * 0.5
+        for y in range(oh):
+            xx, yy = xo, yo
+            for x in range(ow):
+                xi, yi = _coord(xx), _coord(yy)
+                if 0 <= xi < w and 0 <= yi < h:
+                    out[y, x] = a[yi, xi]
+                xx += m[0]
+                yy += m[3]
+            xo += m[1]
+            yo += m[4]
         return out[:, :, 0] if was2d else out
     a0, a1, a3, a4 = (_fix16(m[0]), _fix16(m[1]), _fix16(m[3]), _fix16(m[4]))
     a2 = _fix16(m[2] + 0.5 * m[0] + 0.5 * m[1])

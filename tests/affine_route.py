@@ -1,6 +1,6 @@
-"""Which kernel imgxf_affine_u8 launches for a BILINEAR or BICUBIC geometry: a restatement of the box formulas and
+"""Which kernel imgxf_affine_u8 launches for a NEAREST, BILINEAR or BICUBIC geometry: a restatement of the box formulas and
 alignment tests of plan_affine (imagetransformations_amd/csrc/affine_route.h) with the knobs now in the environment, for
-tests that pin a geometry to a kernel (test_gpu_affine_near_integer.py).  test_affine_route_host.py holds it against the
+tests that pin a geometry to a kernel (test_gpu_affine_near_integer.py, test_gpu_affine_nearest_routes.py).  test_affine_route_host.py holds it against the
 host code itself, without a device; a change to the limits in csrc changes these functions with it."""
 import math
 import os
@@ -13,6 +13,55 @@ def _box(m, tw, th, extra=4):
 
 def _llround(v):
     return int(math.copysign(math.floor(abs(v) + 0.5), v))
+
+
+def _fix16(v):
+    return int(math.floor(v * 65536.0 + 0.5))
+
+
+def _box_fx(a, b, tw, th, extra=3):
+    return math.ceil((abs(a) * (tw - 1) + abs(b) * (th - 1)) / 65536.0) + extra
+
+
+def nearest_refused(m, out_size):
+    """plan_affine's IMGXF_ERR_UNSUPPORTED for NEAREST: libImaging's check_fixed fails at a corner of the output, or a
+    coefficient of the 16.16 matrix fits no int."""
+    ow, oh = out_size
+    at = lambda x, y: abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0
+    coeffs = (m[0], m[1], m[2] + m[0] * 0.5 + m[1] * 0.5, m[3], m[4], m[5] + m[3] * 0.5 + m[4] * 0.5)
+    return not (at(0, 0) and at(ow, oh) and at(0, oh) and at(ow, 0)) or not all(abs(c * 65536.0 + 0.5) < 2147483648.0 for c in coeffs)
+
+
+def nearest_route(t, m, out_size, dst=None):
+    """The kernel that run_affine takes for NEAREST (m1 or m3 non-zero, not refused) on source tensor `t` with the knobs
+    now in the environment: ("wq", kw), "dma64", "dma32", "lds49", "lds65", "lds97" or "global".  The destination is the
+    view `dst`, or the fresh contiguous tensor ops.affine makes (16-byte aligned base, rows of 3 ow bytes)."""
+    from imagetransformations_amd import _ffi as F
+    s = F.view_of(t)
+    ow, oh = out_size
+    env = os.environ
+    assert not nearest_refused(m, out_size) and s.n <= 65535
+    if s.c != 3 or "IMGXF_AFFINE_NO_LDS" in env or (s.data | s.row_stride | s.frame_stride) & 3:
+        return "global"
+    fx = [_fix16(m[0]), _fix16(m[1]), _fix16(m[2] + m[0] * 0.5 + m[1] * 0.5),
+          _fix16(m[3]), _fix16(m[4]), _fix16(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+    corners = [(X, Y) for Y in (0, oh + 32) for X in (0, ow + 32)]
+    nowrap = all(abs(fx[2] + fx[1] * Y + fx[0] * X) <= 2.0e9 and abs(fx[5] + fx[4] * Y + fx[3] * X) <= 2.0e9 for X, Y in corners)
+    bw, bh = _box_fx(fx[0], fx[1], 32, 32), _box_fx(fx[3], fx[4], 32, 32)
+    if not (nowrap and bw <= 97 and bh <= 100):
+        return "global"
+    no_dma = "IMGXF_AFFINE_NO_DMA" in env
+    src16 = (s.data | s.row_stride | s.frame_stride) % 16 == 0 and (s.w * 3) % 16 == 0 and s.w * 3 >= 16
+    d = (0, ow * 3, oh * ow * 3) if dst is None else (dst.data, dst.row_stride, dst.frame_stride)
+    dst16 = (d[0] | d[1] | d[2]) % 16 == 0 and (ow * 3) % 16 == 0
+    bwq, bhq = _box_fx(fx[0], fx[1], 32, 16), _box_fx(fx[3], fx[4], 32, 16)
+    kw = (bhq * ((bwq * 3 + 30) // 16) + 63) // 64
+    if src16 and dst16 and not no_dma and kw <= 8:
+        return "wq", kw
+    if bw <= 49 and bh <= 52 and not no_dma and src16:
+        bw64, bh64 = _box_fx(fx[0], fx[1], 32, 64), _box_fx(fx[3], fx[4], 32, 64)
+        return "dma64" if bw64 <= 64 and bh64 <= 80 and "IMGXF_AFFINE_NO_TALL" not in env else "dma32"
+    return "lds49" if bw <= 49 else "lds65" if bw <= 65 else "lds97"
 
 
 def bilinear_route(t, m, out_size, return_f32=False):

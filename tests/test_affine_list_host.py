@@ -287,13 +287,28 @@ def test_layout_refuses_bad_entries():
                                                   small.nbytes, ctypes.byref(need)) == _ffi.ERR_WORKSPACE
 
 
+def _affine_fixed(a, size, m):
+    """libImaging's affine_fixed (16.16 integers, fill 0) whatever check_fixed says: what the oracle did before it followed
+    Pillow out of fixed point."""
+    fix = lambda v: int(np.floor(v * 65536.0 + 0.5))
+    (ow, oh), (h, w) = size, a.shape[:2]
+    y, x = np.mgrid[0:oh, 0:ow].astype(np.int64)
+    xin = (fix(m[2] + 0.5 * m[0] + 0.5 * m[1]) + fix(m[1]) * y + fix(m[0]) * x) >> 16
+    yin = (fix(m[5] + 0.5 * m[3] + 0.5 * m[4]) + fix(m[4]) * y + fix(m[3]) * x) >> 16
+    ok = (xin >= 0) & (xin < w) & (yin >= 0) & (yin < h)
+    return np.where(ok[..., None], a[np.clip(yin, 0, h - 1), np.clip(xin, 0, w - 1)], 0).astype(np.uint8)
+
+
 def test_pillow_leaves_fixed_point_where_the_call_refuses():
-    """The case the refusal is about: on this frame Pillow's bytes are not those of 16.16 fixed point (the oracle's)."""
+    """The case the refusal is about: on this frame Pillow's bytes are not those of 16.16 fixed point but
+    those of its double loop, which the oracle follows."""
     a = noise_frames([(3, 32767)], seed=23)[0]
     got = np.asarray(Image.fromarray(a).transform((32767, 3), Image.AFFINE, OUT_OF_FIXED, Image.NEAREST))
-    assert (got != O.affine_nearest(a, (32767, 3), list(OUT_OF_FIXED))).any()
+    assert (got != _affine_fixed(a, (32767, 3), OUT_OF_FIXED)).any()
+    assert np.array_equal(got, O.affine_nearest(a, (32767, 3), list(OUT_OF_FIXED)))
     al = _al()
     assert not al.check_fixed(OUT_OF_FIXED, 32767, 3) and al.check_fixed(OUT_OF_FIXED, 32766, 3)
+    assert np.array_equal(_affine_fixed(a, (32766, 3), OUT_OF_FIXED), O.affine_nearest(a, (32766, 3), list(OUT_OF_FIXED)))
 
 
 def test_argument_errors_come_before_any_device_work():

@@ -38,6 +38,56 @@ def test_rotation_family(hw):
         assert np.array_equal(O.affine_nearest(a, (w + 5, h - 3), [float(v) for v in mm], fill=(9, 8, 7)), np.asarray(ref))
 
 
+# ---- NEAREST warps that libImaging takes out of 16.16 fixed point (check_fixed fails at a corner of the output) ----------
+WRAPS_INSIDE = (1092.5, 0.3, -546.0, 0.01, 0.9, 0.0)      # 64 x 64: the 32-bit-wrapped 16.16 coordinates land inside the source
+OUT_OF_FIXED_H, OUT_OF_FIXED_W = 90, 70
+
+
+def out_of_fixed_matrices():
+    """(kind, matrix, (ow, oh)): seeded matrices with m1 or m3 non-zero that fail check_fixed and still show source pixels.
+    Each sends the centre of one output pixel (px, py) to a point (sx, sy) inside the source; the large coefficient then
+    carries the corners of the output beyond 32768."""
+    rng = np.random.default_rng(20261021)
+    cases = [("wraps inside", WRAPS_INSIDE, (64, 64))]
+    for kind in ("large m0", "large m3", "large m1", "large m2"):
+        for _ in range(12):
+            ow, oh = int(rng.integers(40, 90)), int(rng.integers(40, 90))
+            big = float(rng.uniform(2000.0, 6000.0)) * (1 if rng.random() < 0.5 else -1)   # x 40 pixels: a span above 2 x 32768
+            m0, m1, m3, m4 = (float(v) for v in rng.uniform(-1.2, 1.2, 4))
+            px, py = int(rng.integers(0, ow)), int(rng.integers(0, oh))
+            if kind == "large m0":
+                m0 = big
+            elif kind == "large m3":
+                m3 = big
+            elif kind == "large m1":
+                m1 = big
+            else:                                             # |m2| >= 65536: a steep m0 brings a far column back
+                m0, px = big, ow - 1 - int(rng.integers(0, 4))
+            sx, sy = float(rng.uniform(1.0, OUT_OF_FIXED_W - 1.0)), float(rng.uniform(1.0, OUT_OF_FIXED_H - 1.0))
+            m2 = sx - m0 * (px + 0.5) - m1 * (py + 0.5)
+            m5 = sy - m3 * (px + 0.5) - m4 * (py + 0.5)
+            cases.append((kind, (m0, m1, m2, m3, m4, m5), (ow, oh)))
+    return cases
+
+
+def test_nearest_out_of_fixed_point_follows_the_double_walk():
+    """Where check_fixed fails Pillow walks the coordinates in doubles (xx += m0 per pixel, xo += m1 per row); the
+    16.16 integers, in int64 or wrapped at 32 bits, give other pixels there."""
+    a = np.random.default_rng(5).integers(0, 256, (OUT_OF_FIXED_H, OUT_OF_FIXED_W, 3), dtype=np.uint8)
+    img, ones = Image.fromarray(a), Image.new("L", (OUT_OF_FIXED_W, OUT_OF_FIXED_H), 255)
+    shown = {}
+    for kind, m, size in out_of_fixed_matrices():
+        assert not O._check_fixed(m, *size) and (m[1] != 0 or m[3] != 0), (kind, m)
+        if kind == "large m2":
+            assert abs(m[2]) >= 65536.0, m
+        ref = np.asarray(img.transform(size, Image.AFFINE, m, resample=Image.NEAREST, fillcolor=(9, 8, 7)))
+        assert np.array_equal(O.affine_nearest(a, size, list(m), fill=(9, 8, 7)), ref), (kind, m, size)
+        inside = np.asarray(ones.transform(size, Image.AFFINE, m, resample=Image.NEAREST, fillcolor=0)) != 0
+        assert (ref[~inside] == (9, 8, 7)).all()
+        shown[kind] = shown.get(kind, 0) + int(inside.sum())
+    assert shown["wraps inside"] == 64 and all(v >= 12 for v in shown.values()), shown
+
+
 @pytest.mark.parametrize("hw", SIZES)
 def test_scale_shear_translation(hw):
     a = synth(2, *hw)

@@ -224,9 +224,9 @@ static std::vector<Case> fixed_cases() {
             case 2: { const double v[6] = {pick(2) ? 0.8 : 1.25, 0.3, 5.0, 0.0, 1.0, (double)pick(3)}; memcpy(m, v, sizeof v); break; }
             case 3: { const double v[6] = {1.0, 0.3, 0.0, 0.0, 1.0, 2.5}; memcpy(m, v, sizeof v); break; }   // m5 not integral: no shear kernel
             case 4: { const double v[6] = {0.8, 0.3, 5.0, -0.3, 0.8, 7.0}; memcpy(m, v, sizeof v); break; }
-            case 5: rotation(m, 7.5 * pick(48), SCALES[pick(8)], sw, sh, ow, oh); m[2] += 40000.0; break;  // 16.16 coordinates wrap
+            case 5: rotation(m, 7.5 * pick(48), SCALES[pick(8)], sw, sh, ow, oh); m[2] += 40000.0; break;  // check_fixed fails: NEAREST is refused (rc -4)
             case 6: rotation(m, 7.5 * pick(48), SCALES[pick(8)], sw, sh, ow, oh); m[5] -= 3.0e6; break;    // coordinates beyond 2^21
-            case 7: { const double v[6] = {64.5, 0.1, 0.0, 0.1, 1.0, 0.0}; memcpy(m, v, sizeof v); break; }
+            case 7: { const double v[6] = {64.5, 0.1, 0.0, 0.1, 1.0, 0.0}; memcpy(m, v, sizeof v); break; }   // 7, 8: beyond the 2^-40 fixed point; NEAREST refused on the large outputs
             case 8: { const double v[6] = {0.5, 70.0, 0.0, 0.1, -65.0, 0.0}; memcpy(m, v, sizeof v); break; }
             case 9: { const double v[6] = {1.0, 0.0, 3.0, 0.0, 1.0, -2.0}; memcpy(m, v, sizeof v); break; }  // a translation
         }

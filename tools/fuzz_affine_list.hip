@@ -61,8 +61,8 @@ int main(int argc, char** argv) {
             bool any = false;
             for (int i = 0; i < n; ++i)
                 any |= filt[i] == IMGXF_FILTER_NEAREST && (mat[(size_t)i * 6 + 1] != 0 || mat[(size_t)i * 6 + 3] != 0) &&
-                       !(imgxf::afl_check_fixed(&mat[(size_t)i * 6], geo[(size_t)i * 4 + 3], geo[(size_t)i * 4 + 2]) &&
-                         imgxf::afl_fits_fixed(&mat[(size_t)i * 6]));
+                       !(imgxf::affine_check_fixed(&mat[(size_t)i * 6], geo[(size_t)i * 4 + 3], geo[(size_t)i * 4 + 2]) &&
+                         imgxf::affine_fits_fixed(&mat[(size_t)i * 6]));
             if (!any) { fprintf(stderr, "refused without a cause (round %d)\n", round); return 2; }
             ++out_of_fixed;
             for (int i = 0; i < n; ++i)                           // the same list under BILINEAR is laid out
